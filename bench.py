@@ -27,6 +27,13 @@ environment's WORLD_SIZE must equal --gpus):
       into one candidate list first (BASELINE configs[4]: 5 robots).
   --workload cfg4: BASELINE configs[3], verification only: --pairs candidate pairs (default 1 000 000) of the
       configs[1] shape round-robin over the ranks, accepted separators all-gathered.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (the contract's fields, the configuration,
+the roofline of the kernels bracketed inside the timed region).  --full adds everything that takes work of its own after
+the timed steps: the per-kernel survey, the dominant kernel alone on the chip, the ground-truth check, the untimed
+comparison runs (other NN precision, fixed iterations, strict form, VALU matcher, PCIe, ...), the CPU baseline and the
+parity of the last step's separators with the oracle.  --dump-outputs DIR writes what the last timed step handed out
+(dump_outputs below).
 """
 import argparse
 import contextlib
@@ -95,6 +102,44 @@ def spawn_ranks(n):
     raise SystemExit(wait_ranks(procs))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, m, flags, sep):
+    """--dump-outputs: what a caller of the timed path receives from its last step, one float64 row per NN match:
+    the match (idx_local, idx_other, distance), its verdict, and its accepted separator record (zeros where the
+    estimation failed).  Should the rows exceed DUMP_LIMIT_BYTES in all, a fixed, seeded sample of them is written
+    (sample_rows.npy: the match indices kept)."""
+    from multi_robot_slam_separators_amd import _abi
+    n = len(m)
+    flags = np.asarray(flags, dtype=bool)
+    if len(sep) != int(flags.sum()):
+        raise RuntimeError("--dump-outputs: %d separator records for %d accepted matches" % (len(sep), int(flags.sum())))
+    rec = np.zeros(n, dtype=_abi.RESULT_DTYPE)
+    rec[flags] = sep                          # (the records come in match order)
+    f64 = lambda x: np.ascontiguousarray(x, dtype=np.float64)
+    arrays = {
+        "match_idx_local": f64(m["idx_local"]),
+        "match_idx_other": f64(m["idx_other"]),
+        "match_distance": f64(m["distance"]),
+        "match_accepted": f64(flags),
+        "separator_position": f64(rec["position"]),
+        "separator_orientation": f64(rec["orientation"]),
+        "separator_covariance": f64(rec["covariance"]),
+        "separator_counts": f64(np.stack([rec[c] for c in ("inliers", "matches", "inliers_pass1", "matches_pass1")], 1)),
+        "separator_flags": f64(np.stack([rec[c] for c in ("success", "pass1_success", "pass2_guided")], 1)),
+    }
+    row_bytes = sum(a[:1].nbytes for a in arrays.values()) if n else 1
+    budget = DUMP_LIMIT_BYTES - 65536             # (the .npy headers)
+    if n * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, budget // (row_bytes + 8), replace=False))
+        arrays = {name: a[keep] for name, a in arrays.items()}
+        arrays["sample_rows"] = f64(keep)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -145,7 +190,16 @@ def main():
                          "pairs x 100k keyframes, K = 1000, 2000 iterations; cfg4 = configs[3]: --pairs candidate pairs "
                          "round-robin over the ranks, verification only")
     ap.add_argument("--pairs", type=int, default=1000000, help="--workload cfg4: candidate pairs per step (all ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed steps also the kernel survey, the dominant kernel alone, the ground-truth check, "
+                         "the untimed comparison runs, the CPU baseline and the oracle parity (a plain run: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's matches, verdicts and separator records to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload != "cfg2" or args.partition != "robot-pairs"):
+        ap.error("--dump-outputs: only the default workload (--workload cfg2 --partition robot-pairs)")
     big = args.workload == "cfg3"
     args.keyframes = args.keyframes if args.keyframes is not None else (100000 if big else 10000)
     args.features = args.features if args.features is not None else (1000 if big else 500)
@@ -506,50 +560,57 @@ def main():
     timed_issue_ms, timed_retire_ms = list(t_issue), list(t_retire)
     prof = f.prof_get()
     f.prof_enable(False)
-    # survey of every kernel (not timed): per-kernel HIP-event times of `survey_steps` further steps
-    survey_steps = min(args.steps, 20)
     pairs_timed = state["pairs"]
     lm, lh, ln = state["last"]
     last_timed = (lm.copy(), lh.clone(), ln)      # (the survey steps rewrite the pinned block the view points into)
-    f.prof_reset()
-    f.prof_select(None)
-    f.prof_enable(True)
-    if pipelined:
-        # (the form of the timed region: the library picks the verification's form per call -- inside overlapped steps the
-        #  split one, k_match_split + k_chain -- so the survey runs the step pair too)
-        for step_i in range(survey_steps):
-            issue(step_i)
-        while inflight[0]:
-            retire()
-        drain_exchanges()
-    else:
-        for _ in range(survey_steps):
-            step()
-    torch.cuda.synchronize()
-    prof_all = f.prof_get()
-    f.prof_enable(False)
-    # ... and the dominant kernel ALONE on the chip (one step at a time, one stream): inside the timed region up to
-    # SF_OPT_STEP_LANES launches of it run beside each other and share the CUs, so a launch's wall time there is a multiple
-    # of what it needs by itself
-    prof_alone = None
-    if pipelined and not dist_on:
-        try:
-            # (two lanes, ONE step in flight: the library keeps the form it uses inside overlapped steps -- the split one for
-            #  3D-3D -- and nothing runs beside the step's own kernels, which depend on each other)
-            f.set_option(_abi.SF_OPT_STEP_LANES, 2)
-            f.prof_reset(); f.prof_select(dominant); f.prof_enable(True)
-            for _ in range(8):
-                f.step_issue(slot_a, slot_b)
-                f.step_retire()
-            torch.cuda.synchronize()
-            prof_alone = f.prof_get()
-            f.prof_enable(False)
-            f.set_option(_abi.SF_OPT_STEP_LANES, int(os.environ.get("SF_STEP_LANES", "3")))
-        except Exception as e:
-            print("bench: exclusive-launch pass failed: %r" % (e,), file=sys.stderr)
-    state["pairs"] = pairs_timed
-    state["last"] = last_timed
+    # what the last timed step handed out: its matches, every match's verdict, the accepted separators in match order
+    m, host, n = last_timed
+    flags = state["flags_last"] if state.get("flags_last") is not None else h_flags[:n].numpy().copy()
+    sep = np.frombuffer(host.numpy().tobytes(), dtype=_abi.RESULT_DTYPE)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m, flags, sep)
     filter_dims = f.nn_last_filter_dims()      # prefix length the fp16 filter contracted (0: exact path)
+    # survey of every kernel (--full, not timed): per-kernel HIP-event times of `survey_steps` further steps
+    survey_steps = min(args.steps, 20)
+    prof_all = prof_alone = None
+    if args.full:
+        f.prof_reset()
+        f.prof_select(None)
+        f.prof_enable(True)
+        if pipelined:
+            # (the form of the timed region: the library picks the verification's form per call -- inside overlapped steps
+            #  the split one, k_match_split + k_chain -- so the survey runs the step pair too)
+            for step_i in range(survey_steps):
+                issue(step_i)
+            while inflight[0]:
+                retire()
+            drain_exchanges()
+        else:
+            for _ in range(survey_steps):
+                step()
+        torch.cuda.synchronize()
+        prof_all = f.prof_get()
+        f.prof_enable(False)
+        # ... and the dominant kernel ALONE on the chip (one step at a time, one stream): inside the timed region up to
+        # SF_OPT_STEP_LANES launches of it run beside each other and share the CUs, so a launch's wall time there is a
+        # multiple of what it needs by itself
+        if pipelined and not dist_on:
+            try:
+                # (two lanes, ONE step in flight: the library keeps the form it uses inside overlapped steps -- the split one
+                #  for 3D-3D -- and nothing runs beside the step's own kernels, which depend on each other)
+                f.set_option(_abi.SF_OPT_STEP_LANES, 2)
+                f.prof_reset(); f.prof_select(dominant); f.prof_enable(True)
+                for _ in range(8):
+                    f.step_issue(slot_a, slot_b)
+                    f.step_retire()
+                torch.cuda.synchronize()
+                prof_alone = f.prof_get()
+                f.prof_enable(False)
+                f.set_option(_abi.SF_OPT_STEP_LANES, int(os.environ.get("SF_STEP_LANES", "3")))
+            except Exception as e:
+                print("bench: exclusive-launch pass failed: %r" % (e,), file=sys.stderr)
+        state["pairs"] = pairs_timed
+        state["last"] = last_timed
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
     npairs = torch.tensor([state["pairs"]], dtype=torch.float64, device=coll_dev)
@@ -559,30 +620,32 @@ def main():
     elapsed = float(t.item())
     total_pairs = float(npairs.item())
 
-    # ---- the untimed comparison runs (bench_extras.py): other NN precision, one synchronisation per step, full-length
-    # filter, fixed iterations, the strict form, VALU matcher, PCIe-inclusive rate, NN stage alone, the next rows ----
-    import types
-    X = run_untimed_comparisons(types.SimpleNamespace(
-        _abi=_abi, args=args, cols=cols, d_acc=d_acc, d_flags=d_flags, d_res=d_res, depth=depth, dev=dev, dev_index=dev_index, dim=dim, dist_on=dist_on, f=f, feats=feats, k=k, last_timed=last_timed, lib=lib, n_kf=n_kf, nn_append_local=nn_append_local, nn_append_received=nn_append_received, p=p, pairs_timed=pairs_timed, pipelined=pipelined, rank=rank, slot_a=slot_a, slot_b=slot_b, state=state, step=step, synth=synth, ta=ta, tb=tb, torch=torch, world=world))
+    # ---- the untimed comparison runs (--full, bench_extras.py): other NN precision, one synchronisation per step,
+    # full-length filter, fixed iterations, the strict form, VALU matcher, PCIe-inclusive rate, NN stage alone, the next
+    # rows ----
+    X = dict.fromkeys(("alt", "alt_fixed", "alt_full", "alt_m", "alt_strict", "alt_sync", "alt_valu", "next_rows", "nn_only",
+                       "pcie", "piped"))
+    if args.full:
+        import types
+        X = run_untimed_comparisons(types.SimpleNamespace(
+            _abi=_abi, args=args, cols=cols, d_acc=d_acc, d_flags=d_flags, d_res=d_res, depth=depth, dev=dev, dev_index=dev_index, dim=dim, dist_on=dist_on, f=f, feats=feats, k=k, last_timed=last_timed, lib=lib, n_kf=n_kf, nn_append_local=nn_append_local, nn_append_received=nn_append_received, p=p, pairs_timed=pairs_timed, pipelined=pipelined, rank=rank, slot_a=slot_a, slot_b=slot_b, state=state, step=step, synth=synth, ta=ta, tb=tb, torch=torch, world=world))
     alt, alt_fixed, alt_full, alt_m, alt_strict, alt_sync, alt_valu, next_rows, nn_only, pcie, piped = (X["alt"], X["alt_fixed"], X["alt_full"], X["alt_m"], X["alt_strict"], X["alt_sync"], X["alt_valu"], X["next_rows"], X["nn_only"], X["pcie"], X["piped"])
-    # ---- sanity of the timed work (rank 0): the separators found are the planted revisits -----------
-    m, host, n = state["last"]
-    flags = state["flags_last"] if state.get("flags_last") is not None else h_flags[:n].numpy().copy()
-    truth = feats["is_true"][m["idx_local"]]
+    # ---- sanity of the timed work (--full, rank 0): the separators found are the planted revisits -----------
     same = m["idx_local"] == m["idx_other"]
-    accepted = int(flags.sum())
-    correct = int((flags == (truth & same)).sum())
-    sep = np.frombuffer(host.numpy().tobytes(), dtype=_abi.RESULT_DTYPE)
-    if exch is not None:      # outside the timed region: every gathered record is an accepted separator
-        allrec, cts = exch.all_gathered()
-        gat = np.frombuffer(allrec.cpu().numpy().tobytes(), dtype=_abi.RESULT_DTYPE)
-        mine = gat[sum(cts[:rank]): sum(cts[:rank + 1])]
-        # (streamed records arrive in completion order and cover every accepted CANDIDATE: a superset of the matches')
-        have = set(r.tobytes() for r in mine)
-        all_ok = (bool(gat["success"].all()) and len(gat) == state["gathered"] and len(mine) >= len(sep)
-                  and all(r.tobytes() in have for r in sep))
-    else:
-        all_ok = bool(sep["success"].all()) and len(sep) == state["gathered"]
+    if args.full:
+        truth = feats["is_true"][m["idx_local"]]
+        accepted = int(flags.sum())
+        correct = int((flags == (truth & same)).sum())
+        if exch is not None:      # outside the timed region: every gathered record is an accepted separator
+            allrec, cts = exch.all_gathered()
+            gat = np.frombuffer(allrec.cpu().numpy().tobytes(), dtype=_abi.RESULT_DTYPE)
+            mine = gat[sum(cts[:rank]): sum(cts[:rank + 1])]
+            # (streamed records arrive in completion order and cover every accepted CANDIDATE: a superset of the matches')
+            have = set(r.tobytes() for r in mine)
+            all_ok = (bool(gat["success"].all()) and len(gat) == state["gathered"] and len(mine) >= len(sep)
+                      and all(r.tobytes() in have for r in sep))
+        else:
+            all_ok = bool(sep["success"].all()) and len(sep) == state["gathered"]
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -618,14 +681,6 @@ def main():
             a_ach = pairs_per_launch * bpp_dom / (a_ms * 1e-3) / 1e9
             alone_roof = {"avg_launch_ms": a_ms, "launches": prof_alone[dom][0], "achieved": a_ach, "unit": "GB/s",
                           "frac": a_ach / HBM_PEAK_GBS}
-        nn_kernel, nn_peak = (("k_nn_filter_f16", MFMA_F16_PEAK_TF) if args.nn_precision == 1
-                              else ("k_nn_argmin", MFMA_F32_PEAK_TF))
-        nn_n, nn_t = prof_all[nn_kernel]
-        nn_ms = nn_t / max(nn_n, 1)
-        # flops the launched kernel really performs: the fp16 filter contracts a PREFIX of the descriptor
-        # (k_nn.hip, nn_run_filter: adaptive 128 / 512 / full), the fp32 ranking kernel all D dimensions
-        k_eff = dim if args.nn_precision == 0 else (filter_dims or dim)
-        nn_tf = 2.0 * n_kf * n_kf * k_eff / (nn_ms * 1e-3) / 1e12 if nn_ms > 0 else 0.0
         def survey_name(kname):
             if args.estimator == "pnp":
                 return kname.replace("k_ransac", "k_pnp")
@@ -684,20 +739,6 @@ def main():
                                   else "split (PnP): k_match_split + k_chain_pnp (the library's k_verify_fused profiling slot)"
                                   if args.estimator == "pnp" and dom == "k_verify_fused"
                                   else "fused: k_verify_fused" if dom == "k_verify_fused" else "stage kernels"),
-            "roofline_nn": {
-                "kernel": nn_kernel + ("_k128r" if nn_kernel == "k_nn_filter_f16" and k_eff == 128 else ""),
-                "bound": "mfma", "achieved": nn_tf, "peak": nn_peak,
-                "unit": "TFLOP/s", "frac": nn_tf / nn_peak, "avg_launch_ms": nn_ms, "contracted_dims": k_eff,
-            },
-            "kernel_ms_per_step": {survey_name(kname): (ms / survey_steps) for kname, (cnt, ms) in prof_all.items()},
-            "kernel_ms_per_step_source": "HIP events around every kernel in %d steps AFTER the timed region, in the timed "
-                                         "region's form (kernels of the two steps in flight run beside each other, so a "
-                                         "kernel's figure includes what it lost to its neighbour); the timed region "
-                                         "brackets only %s" % (survey_steps,
-                                                               "k_match_split and k_chain" if split_form else dom),
-            "check": {"accepted_last_step": accepted, "decisions_matching_ground_truth": correct, "of": int(n),
-                      "accepted_separators_gathered_per_step": state.get("gathered", 0),
-                      "gathered_records_all_accepted": all_ok},
             "input_generation_s": t_gen,
             # host wall time of each timed step's issue (which first retires the oldest step once the ring is full); the
             # slowest step is named, with what its issue and the retire inside it took
@@ -711,6 +752,29 @@ def main():
                                "retire_ms_max": float(np.max(timed_retire_ms)) if pipelined and timed_retire_ms else None,
                                "steps_in_flight": depth if pipelined else 1},
         }
+        if args.full:
+            nn_kernel, nn_peak = (("k_nn_filter_f16", MFMA_F16_PEAK_TF) if args.nn_precision == 1
+                                  else ("k_nn_argmin", MFMA_F32_PEAK_TF))
+            nn_n, nn_t = prof_all[nn_kernel]
+            nn_ms = nn_t / max(nn_n, 1)
+            # flops the launched kernel really performs: the fp16 filter contracts a PREFIX of the descriptor
+            # (k_nn.hip, nn_run_filter: adaptive 128 / 512 / full), the fp32 ranking kernel all D dimensions
+            k_eff = dim if args.nn_precision == 0 else (filter_dims or dim)
+            nn_tf = 2.0 * n_kf * n_kf * k_eff / (nn_ms * 1e-3) / 1e12 if nn_ms > 0 else 0.0
+            out["roofline_nn"] = {
+                "kernel": nn_kernel + ("_k128r" if nn_kernel == "k_nn_filter_f16" and k_eff == 128 else ""),
+                "bound": "mfma", "achieved": nn_tf, "peak": nn_peak,
+                "unit": "TFLOP/s", "frac": nn_tf / nn_peak, "avg_launch_ms": nn_ms, "contracted_dims": k_eff,
+            }
+            out["kernel_ms_per_step"] = {survey_name(kname): (ms / survey_steps) for kname, (cnt, ms) in prof_all.items()}
+            out["kernel_ms_per_step_source"] = (
+                "HIP events around every kernel in %d steps AFTER the timed region, in the timed region's form (kernels of "
+                "the two steps in flight run beside each other, so a kernel's figure includes what it lost to its "
+                "neighbour); the timed region brackets only %s" % (survey_steps,
+                                                                   "k_match_split and k_chain" if split_form else dom))
+            out["check"] = {"accepted_last_step": accepted, "decisions_matching_ground_truth": correct, "of": int(n),
+                            "accepted_separators_gathered_per_step": state.get("gathered", 0),
+                            "gathered_records_all_accepted": all_ok}
         if split_form:
             whole_ms = match_ms + chain_ms
             out["roofline"]["chain_kernel"] = {
@@ -831,7 +895,7 @@ def main():
             out["check"]["nn_matches_identical_fp32_vs_f16filter"] = bool(
                 np.array_equal(alt_m["idx_local"], m["idx_local"]) and np.array_equal(alt_m["idx_other"], m["idx_other"])
                 and np.array_equal(alt_m["distance"], m["distance"]))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # parity of the timed work itself: every accepted separator of the last step whose pair the oracle sample
             # covers is compared with the oracle's result of that pair, byte for byte (368 B each)
             out["cpu_baseline"] = cpu_baseline(p, feats, nv_a, nv_b, n_kf, args.cpu_sample_pairs,

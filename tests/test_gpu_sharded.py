@@ -160,7 +160,7 @@ def test_robot_pairs_bench_line_over_rccl_world_1(form):
     if form == "one_buffer":
         env["BENCH_ONE_EXCHANGE_BUFFER"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--keyframes", "1500", "--steps", "9",
-                          "--warmup", "2", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                          "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,5 +1,5 @@
 #!/bin/bash
-C="--no-extras --no-cpu-baseline"
+C="--no-extras --no-cpu-baseline --full"
 run() { name=$1; shift; timeout -k 10 400 python bench.py $C "$@" > gpurun_out/shape_$name.log 2>&1 || { echo "$name FAILED"; tail -3 gpurun_out/shape_$name.log; return 1; }
 python - <<PY
 import json

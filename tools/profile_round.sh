@@ -12,9 +12,9 @@ for a in "$@"; do
 done
 out=gpurun_out/prof_$tag
 mkdir -p $out
-B="python bench.py --steps 6 --warmup 2 --no-extras --no-cpu-baseline $*"
+B="python bench.py --steps 6 --warmup 2 --no-extras --no-cpu-baseline --full $*"
 # the stats pass times enough launches that its averages can be held against bench.py's own (HIP-event) figures
-BS="python bench.py --steps 60 --warmup 20 --no-extras --no-cpu-baseline $*"
+BS="python bench.py --steps 60 --warmup 20 --no-extras --no-cpu-baseline --full $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- $BS > $out/stats.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -- $B > $out/fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -- $B > $out/write.log 2>&1

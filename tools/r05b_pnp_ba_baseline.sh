@@ -1,5 +1,5 @@
 set -e
-A="--steps 100 --warmup 10 --no-extras --no-cpu-baseline"
+A="--steps 100 --warmup 10 --no-extras --no-cpu-baseline --full"
 run() { tag=$1; shift; echo "== $tag: $*"; timeout -k 10 400 python bench.py $A "$@" > gpurun_out/r05b/$tag.json 2> gpurun_out/r05b/$tag.err || { echo FAILED; tail -5 gpurun_out/r05b/$tag.err; return 1; }
 python - gpurun_out/r05b/$tag.json <<'PY'
 import json, sys

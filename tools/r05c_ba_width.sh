@@ -1,6 +1,6 @@
 #!/bin/bash
 # PnP + bundle adjustment / 3D-3D + bundle adjustment bench lines by width of the adjustment's workgroups (SF_BA_NW)
-A="--steps 100 --warmup 10 --no-extras --no-cpu-baseline"
+A="--steps 100 --warmup 10 --no-extras --no-cpu-baseline --full"
 mkdir -p gpurun_out/r05c
 run() { tag=$1; shift; envs=$1; shift; echo "== $tag: $envs $*"; env $envs timeout -k 10 400 python bench.py $A "$@" > gpurun_out/r05c/$tag.json 2> gpurun_out/r05c/$tag.err || { echo FAILED; tail -5 gpurun_out/r05c/$tag.err; return 1; }
 python - gpurun_out/r05c/$tag.json <<'PY'

@@ -1,5 +1,5 @@
 #!/bin/bash
-A="--steps 100 --warmup 10 --no-extras --no-cpu-baseline"
+A="--steps 100 --warmup 10 --no-extras --no-cpu-baseline --full"
 mkdir -p gpurun_out/r05e
 run() { tag=$1; shift; envs=$1; shift; echo "== $tag: $envs $*"; env $envs timeout -k 10 400 python bench.py $A "$@" > gpurun_out/r05e/$tag.json 2> gpurun_out/r05e/$tag.err || { echo FAILED; tail -5 gpurun_out/r05e/$tag.err; return 1; }
 python - gpurun_out/r05e/$tag.json <<'PY'

@@ -13,9 +13,9 @@ if "roofline_strict" in d: print("    roofline_strict", d["roofline_strict"])
 PY
 }
 run driver_command --gpus 1 --steps 20 --warmup 5 || exit 1
-run default || exit 1
-run pnp --estimator pnp || exit 1
-run pnp_ba --estimator pnp --bundle-adjustment || exit 1
-run 3d3d_ba --bundle-adjustment --no-extras || exit 1
-run strict --strict --no-extras || exit 1
+run default --full || exit 1
+run pnp --estimator pnp --full || exit 1
+run pnp_ba --estimator pnp --bundle-adjustment --full || exit 1
+run 3d3d_ba --bundle-adjustment --no-extras --full || exit 1
+run strict --strict --no-extras --full || exit 1
 run cfg3 --workload cfg3 || exit 1

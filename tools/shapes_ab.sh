@@ -1,6 +1,6 @@
 #!/bin/bash
 # default vs SF_FUSED=2 on the other shapes, interleaved on one box
-C="--no-extras --no-cpu-baseline"
+C="--no-extras --no-cpu-baseline --full"
 run() { name=$1; shift; timeout -k 10 300 python bench.py $C "$@" > gpurun_out/r03m/shape_$name.log 2>&1 || { echo "$name FAILED"; tail -3 gpurun_out/r03m/shape_$name.log; return 1; }
 python - <<PY
 import json
