@@ -57,7 +57,9 @@ extern "C" {
       sf_step_result pointers stay valid until the next sf_step_retire; sf_params grew desc_type (appended).         */
 /* 6: SF_K_BA added to the kernel ids of sf_prof_get (SF_K_COUNT 10 -> 11): the bundle adjustment is a launch of its
       own; sf_step_issue refuses more steps in flight than a mirror has buffers for.                                */
-#define SF_ABI_VERSION 6
+/* 7: sf_params.reserved0 became guess_match_to_projection (same offset, same size); SF_K_GUIDED_TP added to the kernel
+      ids of sf_prof_get (SF_K_COUNT 11 -> 12).                                                                     */
+#define SF_ABI_VERSION 7
 
 /* ---- status codes ---------------------------------------------------------------------- */
 enum {
@@ -144,7 +146,11 @@ typedef struct sf_params {
      global matching (myRegistrationVis.cpp:839-854 -> VWDictionary::addNewWords [upstream]), cv::BFMatcher(NORM_L2)
      distances in the guided matching (:739-749).  north_star's "ORB/SURF ... Hamming/L2 matching".               */
   int32_t desc_type;               /* 0 */
-  int32_t reserved0;               /* 0 (keeps the struct a multiple of 8 bytes)                               */
+  /* Vis/CorGuessMatchToProjection: 0 = the guided pass matches every projected "from" point to the "to" keypoints in
+     its window (myRegistrationVis.cpp:667-818); 1 = it matches every "to" keypoint to the projections in its window
+     (:521-666; squared L2 distances for float32 rows, :580).  Any other value: sf_create -> SF_EINVAL.  With 1 every
+     verification call runs on the stage kernels (or their two-stream halves under SF_OVERLAP).                      */
+  int32_t guess_match_to_projection; /* 0 */
 } sf_params;
 
 /* ---- wire layouts ------------------------------------------------------------------------ */
@@ -585,7 +591,8 @@ enum {
   SF_K_FUSED = 8,      /* fused per-pair pipeline: match + RANSAC + guided + RANSAC + result    */
   SF_K_NN_WALK = 9,    /* argsort of the row minima + the walk (data_handler.py:191-205), on the device */
   SF_K_BA = 10,        /* two-view bundle adjustment of a pass's estimate (a launch of its own since ABI 6) */
-  SF_K_COUNT = 11
+  SF_K_GUIDED_TP = 11, /* guided matching of the "to" keypoints to the projections (guess_match_to_projection = 1) */
+  SF_K_COUNT = 12
 };
 /* When enabled every kernel launch is bracketed by hipEvents on the handle's stream.          */
 int  sf_prof_enable(sf_handle h, int on);

@@ -31,6 +31,186 @@ namespace {
 // K = 500); a frame with more takes the per-lane loop (same integers).
 #define GUIDED_CAND_CAP_NARROW 1216
 
+// ---- pieces of the pass-2 stage shared by both sub-branches of the guided matching (guided_body: projections matched
+// to the frame, :667-818; guided_tp_body: the frame matched to the projections, :521-666) ----
+
+// The pass-2 decision (stereoCamGeometricTools.cpp:153-164, myRegistrationVis.cpp:477-479): whether the pair is
+// matched by the guided pass.  A pair that is not keeps its pass-1 state (thread 0 writes it) -- block-uniform.
+__device__ __forceinline__ bool guided_eligible(const PassState& p1, const DeviceParams& P, const int4& mF, int Kf, int Kt,
+                                                PassState& pass2_out, uint8_t& guided_flag_out, CorrHeader& hdr_out) {
+  bool ident = true;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) ident = ident && (p1.T[i] == ((i == 0 || i == 5 || i == 10) ? 1.f : 0.f));
+  // myRegistrationVis.cpp:477-479
+  const bool eligible = !p1.is_null && !ident && P.guess_win > 0 && mF.y > 0 && P.calibrated && Kf > 0 && Kt > 0;
+  if (!eligible && threadIdx.x == 0) {
+    pass2_out = p1;
+    guided_flag_out = 0;
+    CorrHeader h = {0, 0, 0, 0};
+    hdr_out = h;
+  }
+  return eligible;
+}
+
+// :486-487 guessCameraRef = (guess * localTransform).inverse(): rotation Rc and translation tc of the projection
+__device__ __forceinline__ void guided_camera(const PassState& p1, const DeviceParams& P, float Rc[9], float tc[3]) {
+  const float* g = p1.T;
+  const float* Lt = P.L;
+  float GR[9], Gt[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      GR[3 * i + j] = (g[4 * i] * Lt[j] + g[4 * i + 1] * Lt[4 + j]) + g[4 * i + 2] * Lt[8 + j];
+    Gt[i] = ((g[4 * i] * Lt[3] + g[4 * i + 1] * Lt[7]) + g[4 * i + 2] * Lt[11]) + g[4 * i + 3];
+  }
+  // Every coefficient goes through an (empty) register barrier: the twelve values must not be packed two to a
+  // v_pk_*_f32 instruction.  Round 3 found about one survivor chain in a thousand of k_verify_fused projecting the
+  // points of lanes 48-63 of one wavefront with different X coefficients (the LOW halves of the packed results; Y and
+  // Z, the high halves and the scalar ones, were right) when this block was SLP-vectorised -- DESIGN.md section 3.
+  // Kept scalar here AND the translation unit is built with -fno-slp-vectorize; either alone removed the symptom.
+#ifndef SF_NO_PK_BARRIERS      // (tools/pk_isa_scan.py builds the block WITHOUT them, SLP on, to show the instructions of the symptom)
+#pragma unroll
+  for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(GR[i]));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(Gt[i]));
+#endif
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rc[3 * i + j] = GR[3 * j + i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) tc[i] = -((Rc[3 * i] * Gt[0] + Rc[3 * i + 1] * Gt[1]) + Rc[3 * i + 2] * Gt[2]);
+#ifndef SF_NO_PK_BARRIERS
+#pragma unroll
+  for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(tc[i]));
+#endif
+}
+
+// projection of a finite "from" point with the guess (:488-515, cv::projectPoints in double): pixel position and
+// "inside the image, in front of the camera"
+__device__ __forceinline__ bool guided_project(const DeviceParams& P, const float Rc[9], const float tc[3], float x, float y,
+                                               float z, float& u, float& v) {
+  const float zf = ((Rc[6] * x + Rc[7] * y) + Rc[8] * z) + tc[2];
+  const double X = (((double)Rc[0] * (double)x + (double)Rc[1] * (double)y) + (double)Rc[2] * (double)z) + (double)tc[0];
+  const double Y = (((double)Rc[3] * (double)x + (double)Rc[4] * (double)y) + (double)Rc[5] * (double)z) + (double)tc[1];
+  const double Z = (((double)Rc[6] * (double)x + (double)Rc[7] * (double)y) + (double)Rc[8] * (double)z) + (double)tc[2];
+  const double iz = (Z != 0.0) ? 1.0 / Z : 1.0;
+  u = (float)((X * iz) * P.fx + P.cx);
+  v = (float)((Y * iz) * P.fy + P.cy);
+  return isfinite(u) && isfinite(v) && !(u < 0.f) && !(u >= P.wlim) && !(v < 0.f) && !(v >= P.hlim) && (zf > 0.f);
+}
+
+// The id-ordered compaction of the matches (wavefront ballots): out[k] = from | to << 16 for every "from" index i in
+// ascending order whose to_of(i) >= 0; returns the list's length.  Ends with a barrier.
+template <int NW, class ToOf>
+__device__ __forceinline__ int guided_compact(int Kf, uint32_t* out, int* misc, ToOf to_of) {
+  constexpr int NT = 64 * NW;
+  const int tid = (int)threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  int running = 0;
+  for (int base = 0; base < Kf; base += NT) {
+    const int i = base + tid;
+    const int m = (i < Kf) ? to_of(i) : -1;
+    const bool flag = m >= 0;
+    const unsigned long long bal = __ballot(flag);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) misc[4 + wave] = __popcll(bal);
+    __syncthreads();
+    int woff = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      int c = misc[4 + w];
+      if (w < wave) woff += c;
+      total += c;
+    }
+    if (flag) out[running + woff + before] = (uint32_t)i | ((uint32_t)m << 16);
+    running += total;
+    __syncthreads();
+  }
+  return running;
+}
+
+// Workgroup sums of the per-thread counts of finite "from" points and of projections in the image (misc[0], misc[1]:
+// 0 on entry).  Ends with a barrier.
+__device__ __forceinline__ void guided_sum_counts(int& n_finite, int& n_proj, int* misc) {
+  for (int off = 32; off >= 1; off >>= 1) {
+    n_finite += __shfl_xor(n_finite, off);
+    n_proj += __shfl_xor(n_proj, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&misc[0], n_finite);
+    atomicAdd(&misc[1], n_proj);
+  }
+  __syncthreads();
+  n_finite = misc[0];
+  n_proj = misc[1];
+}
+
+// The pair's word counts (:766-774, :793-817 and :606-665 give the same ones; :820-823 when no projection is in the
+// image) from the workgroup's n_finite / n_proj, the pass-2 motion gate, the pass-2 state of a pair that does not go
+// on, the header, and the work-list append of a survivor (list == nullptr: none, the fused kernel).  Returns whether the
+// pair needs the pass-2 motion estimation (block-uniform).  misc[2] must be 0 on entry.
+template <int NW>
+__device__ __forceinline__ bool guided_finish(const StoreView& st, int pair, int sT, const int4& mT, int Kt,
+                                              const float* xF, int n_finite, int n_proj, int n_corr, const uint32_t* out,
+                                              PassState& pass2_out, uint8_t& guided_flag_out, CorrHeader& hdr_out,
+                                              int32_t* __restrict__ list, int32_t* __restrict__ counter,
+                                              const DeviceParams& P, int* misc) {
+  constexpr int NT = 64 * NW;
+  const int tid = (int)threadIdx.x;
+  const int kcap = st.kcap;
+  const bool outside = (n_proj == 0);                                   // :820-823
+  const int words_from = outside ? 0 : n_finite;
+  const int words_to_2d = outside ? 0 : Kt;
+  const int words_to = (outside || mT.y <= 0) ? 0 : Kt;
+  const bool pnp = P.estimation_type == 1;   // guided matching implies a calibrated camera
+  // (PnP with Vis/ForwardEstOnly = false: either direction's gate, and every pair with a correspondence goes on -- as
+  //  in the global matcher, k_match.hip)
+  const bool both = pnp && P.bidirectional;
+  const bool motion = words_to_2d > 0 &&
+                      ((words_from >= P.min_inliers && (pnp ? words_to_2d : words_to) >= P.min_inliers) ||    // :1117-1118 / :1070-1071
+                       (both && words_to >= P.min_inliers && words_from >= P.min_inliers));
+  const bool survivor = both ? (motion && n_corr > 0) : (motion && n_corr >= P.min_inliers && n_corr >= (pnp ? 4 : 3));
+  if (motion && !survivor) {
+    const float* xT = st.xyz + (size_t)sT * kcap * 3;
+    for (int i = tid; i < n_corr; i += NT) {
+      uint32_t c = out[i];
+      const float* a = xF + 3 * (c & 0xFFFFu);
+      const float* b = xT + 3 * (c >> 16);
+      bool ok = sfd::finite3(a[0], a[1], a[2]);
+      if (!pnp)
+        ok = ok && sfd::finite3(b[0], b[1], b[2]) && (a[0] != 0.f || a[1] != 0.f || a[2] != 0.f) &&
+             (b[0] != 0.f || b[1] != 0.f || b[2] != 0.f);
+      if (ok) atomicAdd(&misc[2], 1);
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    CorrHeader h;
+    h.n_corr = n_corr;
+    h.words_from = words_from;
+    h.words_to = words_to;
+    h.words_to_2d = words_to_2d;
+    hdr_out = h;
+    guided_flag_out = 1;
+    PassState ps;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
+    ps.var = 1.0; ps.var_ang = 1.0;
+    ps.is_null = 1;
+    ps.inliers = 0;
+    ps.matches = (motion && !survivor) ? misc[2] : 0;
+    ps.pad = 0;
+    pass2_out = ps;
+    if (survivor && list) {
+      int pos = atomicAdd(counter, 1);
+      list[pos] = pair;
+    }
+  }
+  return survivor;
+}
+
 // Body of the pass-2 matching stage for ONE pair (the calling workgroup); returns whether the pair
 // needs the pass-2 motion estimation (block-uniform).  list == nullptr: no work-list append (fused).
 // `out` / hdr_out / pass2_out / guided_flag_out: the pair's pass-2 correspondence list, header, state and flag
@@ -54,20 +234,7 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
   const int4 mT = bad_slot ? make_int4(0, 0, 0, 0) : st.meta[sT];
   const int Kf = mF.x, Kt = mT.x;
 
-  bool ident = true;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) ident = ident && (p1.T[i] == ((i == 0 || i == 5 || i == 10) ? 1.f : 0.f));
-  // myRegistrationVis.cpp:477-479
-  const bool eligible = !p1.is_null && !ident && P.guess_win > 0 && mF.y > 0 && P.calibrated && Kf > 0 && Kt > 0;
-  if (!eligible) {
-    if (tid == 0) {
-      pass2_out = p1;
-      guided_flag_out = 0;
-      CorrHeader h = {0, 0, 0, 0};
-      hdr_out = h;
-    }
-    return false;
-  }
+  if (!guided_eligible(p1, P, mF, Kf, Kt, pass2_out, guided_flag_out, hdr_out)) return false;
 
   int* claim = smem;               // [kcap] lowest "from" index that matched each "to" row
   int* matched = smem + kcap;      // [kcap] "to" row matched by each "from" point, or -1
@@ -97,41 +264,8 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
   for (int i = tid; i < NC; i += NT) cell_fill[i] = 0;
   if (tid < 16) misc[tid] = 0;
 
-  // :486-487 guessCameraRef = (guess * localTransform).inverse()
   float Rc[9], tc[3];
-  {
-    const float* g = p1.T;
-    const float* Lt = P.L;
-    float GR[9], Gt[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        GR[3 * i + j] = (g[4 * i] * Lt[j] + g[4 * i + 1] * Lt[4 + j]) + g[4 * i + 2] * Lt[8 + j];
-      Gt[i] = ((g[4 * i] * Lt[3] + g[4 * i + 1] * Lt[7]) + g[4 * i + 2] * Lt[11]) + g[4 * i + 3];
-    }
-    // Every coefficient goes through an (empty) register barrier: the twelve values must not be packed two to a
-    // v_pk_*_f32 instruction.  Round 3 found about one survivor chain in a thousand of k_verify_fused projecting the
-    // points of lanes 48-63 of one wavefront with different X coefficients (the LOW halves of the packed results; Y and
-    // Z, the high halves and the scalar ones, were right) when this block was SLP-vectorised -- DESIGN.md section 3.
-    // Kept scalar here AND the translation unit is built with -fno-slp-vectorize; either alone removed the symptom.
-#ifndef SF_NO_PK_BARRIERS      // (tools/pk_isa_scan.py builds the block WITHOUT them, SLP on, to show the instructions of the symptom)
-#pragma unroll
-    for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(GR[i]));
-#pragma unroll
-    for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(Gt[i]));
-#endif
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) Rc[3 * i + j] = GR[3 * j + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) tc[i] = -((Rc[3 * i] * Gt[0] + Rc[3 * i + 1] * Gt[1]) + Rc[3 * i + 2] * Gt[2]);
-#ifndef SF_NO_PK_BARRIERS
-#pragma unroll
-    for (int i = 0; i < 3; ++i) asm volatile("" : "+v"(tc[i]));
-#endif
-  }
+  guided_camera(p1, P, Rc, tc);
   __syncthreads();
 
   const uint32_t* dF = st.desc + (size_t)sF * kcap * W;
@@ -258,17 +392,7 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
   for (int i = tid; i < Kt; i += NT) claim[i] = 0x7FFFFFFF;  //  the barrier behind the search's first pass)
   int n_finite = 0, n_proj = 0;
   const int cand_cap = NW == 4 ? GUIDED_CAND_CAP : min(GUIDED_CAND_CAP_NARROW, 4 * kcap);   // (NW < 4: the keys are parked in the grid's items)
-  // projection of a finite "from" point with the guess (:503-512): pixel position and "inside the image, in front"
-  auto project = [&](float x, float y, float z, float& u, float& v) -> bool {
-    const float zf = ((Rc[6] * x + Rc[7] * y) + Rc[8] * z) + tc[2];
-    const double X = (((double)Rc[0] * (double)x + (double)Rc[1] * (double)y) + (double)Rc[2] * (double)z) + (double)tc[0];
-    const double Y = (((double)Rc[3] * (double)x + (double)Rc[4] * (double)y) + (double)Rc[5] * (double)z) + (double)tc[1];
-    const double Z = (((double)Rc[6] * (double)x + (double)Rc[7] * (double)y) + (double)Rc[8] * (double)z) + (double)tc[2];
-    const double iz = (Z != 0.0) ? 1.0 / Z : 1.0;
-    u = (float)((X * iz) * P.fx + P.cx);
-    v = (float)((Y * iz) * P.fy + P.cy);
-    return isfinite(u) && isfinite(v) && !(u < 0.f) && !(u >= P.wlim) && !(v < 0.f) && !(v >= P.hlim) && (zf > 0.f);
-  };
+  auto project = [&](float x, float y, float z, float& u, float& v) -> bool { return guided_project(P, Rc, tc, x, y, z, u, v); };
   // pass A: projections, per-point candidate count / highest candidate (:751-764 needs it), candidate list
   for (int base = 0; base < Kf; base += NT) {
     const int i = base + tid;
@@ -565,89 +689,12 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
       }
     }
   }
-  for (int off = 32; off >= 1; off >>= 1) {
-    n_finite += __shfl_xor(n_finite, off);
-    n_proj += __shfl_xor(n_proj, off);
-  }
-  if (lane == 0) {
-    atomicAdd(&misc[0], n_finite);
-    atomicAdd(&misc[1], n_proj);
-  }
-  __syncthreads();
-  n_finite = misc[0];
-  n_proj = misc[1];
+  guided_sum_counts(n_finite, n_proj, misc);
   SF_TRACE_MARK(P, pair, 9);
   // id-ordered compaction
-  int running = 0;
-  for (int base = 0; base < Kf; base += NT) {
-    const int i = base + tid;
-    int m = (i < Kf) ? matched[i] : -1;
-    const bool flag = (m >= 0) && (claim[m] == i);
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) misc[4 + wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      int c = misc[4 + w];
-      if (w < wave) woff += c;
-      total += c;
-    }
-    if (flag) out[running + woff + before] = (uint32_t)i | ((uint32_t)m << 16);
-    running += total;
-    __syncthreads();
-  }
-  const int n_corr = running;
-
-  const bool outside = (n_proj == 0);                                   // :820-823
-  const int words_from = outside ? 0 : n_finite;
-  const int words_to_2d = outside ? 0 : Kt;
-  const int words_to = (outside || mT.y <= 0) ? 0 : Kt;
-  const bool pnp = P.estimation_type == 1;   // guided matching implies a calibrated camera
-  // (PnP with Vis/ForwardEstOnly = false: either direction's gate, and every pair with a correspondence goes on -- as
-  //  in the global matcher, k_match.hip)
-  const bool both = pnp && P.bidirectional;
-  const bool motion = words_to_2d > 0 &&
-                      ((words_from >= P.min_inliers && (pnp ? words_to_2d : words_to) >= P.min_inliers) ||    // :1117-1118 / :1070-1071
-                       (both && words_to >= P.min_inliers && words_from >= P.min_inliers));
-  const bool survivor = both ? (motion && n_corr > 0) : (motion && n_corr >= P.min_inliers && n_corr >= (pnp ? 4 : 3));
-  if (motion && !survivor) {
-    const float* xT = st.xyz + (size_t)sT * kcap * 3;
-    for (int i = tid; i < n_corr; i += NT) {
-      uint32_t c = out[i];
-      const float* a = xF + 3 * (c & 0xFFFFu);
-      const float* b = xT + 3 * (c >> 16);
-      bool ok = sfd::finite3(a[0], a[1], a[2]);
-      if (!pnp)
-        ok = ok && sfd::finite3(b[0], b[1], b[2]) && (a[0] != 0.f || a[1] != 0.f || a[2] != 0.f) &&
-             (b[0] != 0.f || b[1] != 0.f || b[2] != 0.f);
-      if (ok) atomicAdd(&misc[2], 1);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    CorrHeader h;
-    h.n_corr = n_corr;
-    h.words_from = words_from;
-    h.words_to = words_to;
-    h.words_to_2d = words_to_2d;
-    hdr_out = h;
-    guided_flag_out = 1;
-    PassState ps;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-    ps.var = 1.0; ps.var_ang = 1.0;
-    ps.is_null = 1;
-    ps.inliers = 0;
-    ps.matches = (motion && !survivor) ? misc[2] : 0;
-    ps.pad = 0;
-    pass2_out = ps;
-    if (survivor && list) {
-      int pos = atomicAdd(counter, 1);
-      list[pos] = pair;
-    }
-  }
+  const int n_corr = guided_compact<NW>(Kf, out, misc, [&](int i) { const int m = matched[i]; return (m >= 0 && claim[m] == i) ? m : -1; });
+  const bool survivor = guided_finish<NW>(st, pair, sT, mT, Kt, xF, n_finite, n_proj, n_corr, out, pass2_out, guided_flag_out,
+                                          hdr_out, list, counter, P, misc);
   SF_TRACE_MARK(P, pair, 10);
   return survivor;
 }
@@ -662,6 +709,205 @@ k_guided(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __r
   const int pair = (int)blockIdx.x;
   guided_body<W, L2>(st, pair, pair_from[pair], pair_to[pair], pass1[pair], pass2[pair], guided_flag[pair],
                      corr + (size_t)pair * st.kcap, hdr[pair], list, counter, P, smem);
+}
+
+// ---- pass 2 with Vis/CorGuessMatchToProjection = true (myRegistrationVis.cpp:521-666): every "to" keypoint is matched
+// to the projections of the "from" points within guess_win_size pixels of it ----
+//
+// Per "to" keypoint i: the projections in its window whose octave equals its own (oi of them); oi >= 2: kNN-2 of the
+// "to" row against theirs, the best accepted iff d0 < nndr * d1 (Hamming for binary rows; NORM_L2SQR -- the float32 sum
+// of squared differences in dimension order, no square root, :580 -- for float32 rows); oi == 1: that projection without
+// a descriptor test (:589-591 and :593-602 both come down to it).  A "from" point accepted by two or more "to" keypoints
+// only adds duplicate "to" words (:606-613), which every estimator drops (uMultimapToMapUnique, :1078-1087 /
+// :1123-1124): the correspondences are the "from" points accepted by EXACTLY one "to" keypoint, in ascending "from"
+// order -- the same whatever order the keypoints are visited in.  FLANN's kd-tree radius search over the projections
+// [upstream] is replaced by an exact scan, as in guided_body.
+//
+// CDNA4 mapping: one 256-thread workgroup per pair.  The in-image projections are counting-sorted into the uniform grid
+// of guided_body (cell >= window radius: a window covers at most 3 x 3 cells) as LDS records {u, v, octave, index};
+// one lane per "to" keypoint walks the cells around it and keeps its top two (distance, index) itself, so there is no
+// candidate list and no cap: every frame the store holds takes the same path.  A "from" point's claims are one LDS
+// word: the first claimer's "to" index (atomicCAS on the empty word), bit 31 once a second one arrives -- "exactly one"
+// without depending on which lane came first.  The compaction is guided_body's.
+template <int W, bool L2>
+__device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, int sF, int sT, const PassState& pass1,
+                                               PassState& pass2_out, uint8_t& guided_flag_out, uint32_t* out,
+                                               CorrHeader& hdr_out, int32_t* __restrict__ list,
+                                               int32_t* __restrict__ counter, const DeviceParams& P, int* smem) {
+  constexpr int NW = 4, NT = 64 * NW;
+  const int tid = (int)threadIdx.x;
+  const int kcap = st.kcap;
+  const PassState p1 = pass1;
+  const bool bad_slot = (unsigned)sF >= (unsigned)st.n_slots || (unsigned)sT >= (unsigned)st.n_slots;
+  const int4 mF = bad_slot ? make_int4(0, 0, 0, 0) : st.meta[sF];
+  const int4 mT = bad_slot ? make_int4(0, 0, 0, 0) : st.meta[sT];
+  const int Kf = mF.x, Kt = mT.x;
+  if (!guided_eligible(p1, P, mF, Kf, Kt, pass2_out, guided_flag_out, hdr_out)) return false;
+
+  // LDS (sf_guided_tp_lds_bytes): claims [kcap], misc [16], cell_start [NC + 1], cell_fill [NC], items [kcap] float4
+  const int NC = P.grid_gx * P.grid_gy;
+  uint32_t* claimw = reinterpret_cast<uint32_t*>(smem);   // per "from" point: empty, the one claimer, or bit 31
+  int* misc = smem + kcap;
+  int* cell_start = misc + 16;
+  int* cell_fill = cell_start + NC + 1;
+  float4* item4 = reinterpret_cast<float4*>(smem + ((kcap + 16 + 2 * NC + 1 + 3) & ~3));
+  constexpr uint32_t EMPTY = 0xFFFFFFFFu, SHARED = 0x80000000u;
+  for (int i = tid; i <= NC; i += NT) cell_start[i] = 0;
+  for (int i = tid; i < NC; i += NT) cell_fill[i] = 0;
+  for (int i = tid; i < Kf; i += NT) claimw[i] = EMPTY;
+  if (tid < 16) misc[tid] = 0;
+  float Rc[9], tc[3];
+  guided_camera(p1, P, Rc, tc);
+  __syncthreads();
+
+  const uint32_t* dF = st.desc + (size_t)sF * kcap * W;
+  const uint32_t* dT = st.desc + (size_t)sT * kcap * W;
+  const float* xF = st.xyz + (size_t)sF * kcap * 3;
+  const float4* kF = st.kp + (size_t)sF * kcap;
+  const float4* kT = st.kp + (size_t)sT * kcap;
+  const float r2lim = (float)P.guess_win * (float)P.guess_win;
+  const float inv_cell = P.grid_inv_cell;
+  const int gxm = P.grid_gx - 1, gym = P.grid_gy - 1;
+  const float reach = (float)P.guess_win * 1.0001f + 1e-3f;   // window radius with a rounding margin
+  // cell of an in-image projection (0 <= u < wlim, 0 <= v < hlim)
+  auto cell_of = [&](float u, float v) -> int {
+    return min((int)floorf(v * inv_cell), gym) * P.grid_gx + min((int)floorf(u * inv_cell), gxm);
+  };
+
+  // ---- counting sort of the in-image projections into the grid (projected twice: count, then place)
+  int n_finite = 0, n_proj = 0;
+  for (int i = tid; i < Kf; i += NT) {
+    const float x = xF[3 * i], y = xF[3 * i + 1], z = xF[3 * i + 2];
+    float u = 0.f, v = 0.f;
+    if (sfd::finite3(x, y, z)) {
+      ++n_finite;
+      if (guided_project(P, Rc, tc, x, y, z, u, v)) {
+        ++n_proj;
+        atomicAdd(&cell_start[cell_of(u, v) + 1], 1);
+      }
+    }
+  }
+  __syncthreads();
+  {
+    // exclusive scan of the per-cell counts (each thread owns a run of consecutive cells), as guided_body's
+    const int lane = tid & 63, wave = tid >> 6;
+    const int per = (NC + NT - 1) / NT;
+    const int c0 = tid * per, c1 = min(c0 + per, NC);
+    int local = 0;
+    for (int cidx = c0; cidx < c1; ++cidx) local += cell_start[cidx + 1];
+    int incl = local;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off);
+      if (lane >= off) incl += o;
+    }
+    if (lane == 63) misc[8 + wave] = incl;
+    __syncthreads();
+    int woff = 0;
+    for (int w = 0; w < wave; ++w) woff += misc[8 + w];
+    int run = woff + incl - local;
+    __syncthreads();
+    for (int cidx = c0; cidx < c1; ++cidx) {
+      const int cnt_c = cell_start[cidx + 1];
+      cell_start[cidx + 1] = run + cnt_c;
+      run += cnt_c;
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < Kf; i += NT) {
+    const float x = xF[3 * i], y = xF[3 * i + 1], z = xF[3 * i + 2];
+    float u = 0.f, v = 0.f;
+    if (sfd::finite3(x, y, z) && guided_project(P, Rc, tc, x, y, z, u, v)) {
+      const int cidx = cell_of(u, v);
+      const int pos = cell_start[cidx] + atomicAdd(&cell_fill[cidx], 1);
+      item4[pos] = make_float4(u, v, kF[i].z, __int_as_float(i));   // (octave: the store's sign-extended low byte)
+    }
+  }
+  __syncthreads();
+
+  // ---- one lane per "to" keypoint: window, octave, top two, NNDR, claim.  (No projection in the image: :820-823, no
+  // match; the cells are empty then.)
+  const float x_hi = P.wlim + reach, y_hi = P.hlim + reach;
+  for (int t = tid; t < Kt; t += NT) {
+    const float4 k = kT[t];
+    // a keypoint farther than the radius outside the image has no projection in its window (and a non-finite one
+    // never passes the window test)
+    if (!(isfinite(k.x) && isfinite(k.y) && k.x >= -reach && k.x < x_hi && k.y >= -reach && k.y < y_hi)) continue;
+    const int octt = __float_as_int(k.z);
+    const int cx0 = min(max((int)floorf((k.x - reach) * inv_cell), 0), gxm);
+    const int cx1 = min(max((int)floorf((k.x + reach) * inv_cell), 0), gxm);
+    const int cy0 = min(max((int)floorf((k.y - reach) * inv_cell), 0), gym);
+    const int cy1 = min(max((int)floorf((k.y + reach) * inv_cell), 0), gym);
+    const uint32_t* r = dT + (size_t)t * W;
+    int oi = 0, one = -1;
+    uint32_t b0 = 0xFFFFFFFFu, b1 = 0xFFFFFFFFu;                                // binary: (distance << 16 | from) keys
+    float f0 = __int_as_float(0x7F800000), f1 = __int_as_float(0x7F800000);    // L2: best / second-best distance ...
+    int i0 = -1;                                                                 // ... and the best's "from" index
+    for (int cy = cy0; cy <= cy1; ++cy) {
+      const int e0 = cell_start[cy * P.grid_gx + cx0], e1 = cell_start[cy * P.grid_gx + cx1 + 1];
+      for (int e = e0; e < e1; ++e) {
+        const float4 it = item4[e];
+        const float dx = it.x - k.x, dy = it.y - k.y;   // (the projection minus the keypoint, as guided_body)
+        const float d2 = dx * dx + dy * dy;
+        if (!(d2 < r2lim) || __float_as_int(it.z) != octt) continue;
+        const int i = __float_as_int(it.w);
+        const uint4* pf = reinterpret_cast<const uint4*>(dF + (size_t)i * W);
+        const uint4* pt = reinterpret_cast<const uint4*>(r);
+        if constexpr (L2) {
+          float sq = 0.f;
+#pragma unroll 8
+          for (int q4 = 0; q4 < W / 4; ++q4) {
+            const uint4 a = pt[q4], b = pf[q4];
+            float dd = __uint_as_float(a.x) - __uint_as_float(b.x); sq = sq + dd * dd;
+            dd = __uint_as_float(a.y) - __uint_as_float(b.y); sq = sq + dd * dd;
+            dd = __uint_as_float(a.z) - __uint_as_float(b.z); sq = sq + dd * dd;
+            dd = __uint_as_float(a.w) - __uint_as_float(b.w); sq = sq + dd * dd;
+          }
+          // (cells are visited in grid order, not in index order: of two equal distances the lower index is the best)
+          if (sq < f0 || (sq == f0 && i < i0)) { f1 = f0; f0 = sq; i0 = i; }
+          else if (sq < f1) { f1 = sq; }
+        } else {
+          uint32_t d = 0;
+#pragma unroll
+          for (int q4 = 0; q4 < W / 4; ++q4) {
+            const uint4 a = pt[q4], b = pf[q4];
+            d += __popc(a.x ^ b.x) + __popc(a.y ^ b.y) + __popc(a.z ^ b.z) + __popc(a.w ^ b.w);
+          }
+          const uint32_t key = (d << 16) | (uint32_t)i;
+          b1 = min(max(key, b0), b1);
+          b0 = min(b0, key);
+        }
+        ++oi;
+        one = i;
+      }
+    }
+    int m = -1;
+    if (oi >= 2) {
+      if constexpr (L2) { if (i0 >= 0 && f0 < P.nndr * f1) m = i0; }                       // :581-585
+      else if ((float)(b0 >> 16) < P.nndr * (float)(b1 >> 16)) m = (int)(b0 & 0xFFFFu);
+    } else if (oi == 1) {
+      m = one;                                                                           // :587-602
+    }
+    if (m >= 0 && atomicCAS(&claimw[m], EMPTY, (uint32_t)t) != EMPTY) atomicOr(&claimw[m], SHARED);   // :604-625
+  }
+  guided_sum_counts(n_finite, n_proj, misc);    // (its barrier also orders the claims before the compaction)
+  const int n_corr = guided_compact<NW>(Kf, out, misc, [&](int i) {
+    const uint32_t w = claimw[i];
+    return (w & SHARED) ? -1 : (int)w;          // (EMPTY has bit 31 set too)
+  });
+  return guided_finish<NW>(st, pair, sT, mT, Kt, xF, n_finite, n_proj, n_corr, out, pass2_out, guided_flag_out, hdr_out,
+                           list, counter, P, misc);
+}
+
+template <int W, bool L2 = false>
+__global__ void __launch_bounds__(SF_BLOCK)
+k_guided_tp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+            const PassState* __restrict__ pass1, PassState* __restrict__ pass2, uint8_t* __restrict__ guided_flag,
+            uint32_t* __restrict__ corr, CorrHeader* __restrict__ hdr, int32_t* __restrict__ list,
+            int32_t* __restrict__ counter, DeviceParams P) {
+  extern __shared__ __attribute__((aligned(16))) int smem[];
+  const int pair = (int)blockIdx.x;
+  guided_tp_body<W, L2>(st, pair, pair_from[pair], pair_to[pair], pass1[pair], pass2[pair], guided_flag[pair],
+                        corr + (size_t)pair * st.kcap, hdr[pair], list, counter, P, smem);
 }
 
 // ---- result assembly: myRegistration.cpp:279-295 covariance clamp + MsgConversion.cpp:61-81 ------
@@ -756,8 +1002,42 @@ size_t sf_guided_lds_bytes(int kcap, int n_cells, bool narrow) {
          sizeof(int);   // (+ the raw keypoints' overhang: they are staged over oilast / key1 / key2 / cand, 4 kcap words)
 }
 
+// claims, misc, cell_start, cell_fill, (+3: 16-byte alignment of the item block) items
+static size_t sf_guided_tp_lds_bytes(int kcap, int n_cells) {
+  return (size_t)(kcap + 16 + 2 * n_cells + 1 + 3 + 4 * kcap) * sizeof(int);
+}
+
+// Vis/CorGuessMatchToProjection = true: k_guided_tp in place of k_guided (same inputs, same outputs)
+template <int W, bool L2>
+static int launch_guided_tp(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, size_t lds) {
+  if (lds > 64 * 1024)   // (K > ~3 000 features: above the default dynamic LDS limit; never at the bench's K = 500)
+    SF_HIP(c, hipFuncSetAttribute((const void*)k_guided_tp<W, L2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL((k_guided_tp<W, L2>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
+                     (const PassState*)c->pass1.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p, (uint32_t*)c->corr2.p,
+                     (CorrHeader*)c->hdr2.p, (int32_t*)c->list3.p, (int32_t*)c->counters.p + 2, c->dparams);
+  return SF_OK;
+}
+
+static int sf_launch_guided_tp(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
+  const size_t lds = sf_guided_tp_lds_bytes(st.kcap, c->dparams.grid_gx * c->dparams.grid_gy);
+  if (lds > 160 * 1024)
+    return sf_fail(c, SF_ERANGE, "guess_match_to_projection: %d features per keyframe need %zu B of LDS (> 160 KiB)",
+                   st.kcap, lds);
+  sf_prof_begin(c, SF_K_GUIDED_TP);
+  int rc;
+  if (c->params.desc_type == 1)
+    rc = st.w == 64 ? launch_guided_tp<64, true>(c, st, d_from, d_to, n, lds) : launch_guided_tp<128, true>(c, st, d_from, d_to, n, lds);
+  else
+    rc = st.w == 8 ? launch_guided_tp<8, false>(c, st, d_from, d_to, n, lds) : launch_guided_tp<16, false>(c, st, d_from, d_to, n, lds);
+  sf_prof_end(c, SF_K_GUIDED_TP);
+  if (rc != SF_OK) return rc;
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+
 int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   if (n <= 0) return SF_OK;
+  if (c->dparams.guess_match_to_projection) return sf_launch_guided_tp(c, st, d_from, d_to, n);
   const int nc = c->dparams.grid_gx * c->dparams.grid_gy;
   const size_t lds = sf_guided_lds_bytes(st.kcap, nc);
   int32_t* counters = (int32_t*)c->counters.p;

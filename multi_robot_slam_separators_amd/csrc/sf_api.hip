@@ -74,7 +74,8 @@ StoreView sf_store_view(const Store& s) {
 // ---- profiling ------------------------------------------------------------------------------
 static const char* k_names[SF_K_COUNT] = {"k_match_global", "k_ransac(pass1)", "k_guided",
                                           "k_ransac(pass2)", "k_nn_argmin", "k_nn_select",
-                                          "k_nn_filter_f16", "k_nn_refine", "k_verify_fused", "k_nn_walk", "k_ba_pass"};
+                                          "k_nn_filter_f16", "k_nn_refine", "k_verify_fused", "k_nn_walk", "k_ba_pass",
+                                          "k_guided_tp"};
 const char* sf_kernel_name(int k) { return (k >= 0 && k < SF_K_COUNT) ? k_names[k] : "?"; }
 
 // Brackets that have completed are booked and their events reused without waiting for anything: a long profiled
@@ -647,6 +648,7 @@ extern "C" void sf_default_params(sf_params* p) {
   p->force_3dof = 0;                 // Reg/Force3DoF
   p->forward_est_only = 1;           // Vis/ForwardEstOnly
   p->desc_type = 0;                  // binary descriptors (the reference's wire carries nothing else)
+  p->guess_match_to_projection = 0;  // Vis/CorGuessMatchToProjection
 }
 
 static int fill_device_params(sf_context* c) {
@@ -678,10 +680,14 @@ static int fill_device_params(sf_context* c) {
   // matters before the first non-empty keyframe arrives -- an EMPTY first keyframe (the reference tolerates them: the
   // fake-words path) takes it for its row pitch, and 32 bytes per float row was refused by the store (round 4).
   if (p.desc_type == 1 && p.desc_bytes == 32) c->params.desc_bytes = 256;
+  if (p.guess_match_to_projection != 0 && p.guess_match_to_projection != 1)
+    return sf_fail(c, SF_EINVAL, "guess_match_to_projection %d unknown (0 = projections to frame, 1 = frame to projections)",
+                   p.guess_match_to_projection);
   DeviceParams& d = c->dparams;
   memset(&d, 0, sizeof(d));
   d.force_3dof = p.force_3dof != 0;
   d.bidirectional = p.forward_est_only == 0;
+  d.guess_match_to_projection = p.guess_match_to_projection;
   d.nndr = p.nndr;
   d.min_inliers = p.min_inliers;
   d.iterations = p.iterations;
@@ -1281,6 +1287,9 @@ static VerifyPlan verify_plan(const sf_context* c, const StoreView& v, int n) {
   VerifyPlan p;
   if (c->overlap && n >= c->overlap_min_pairs) { p.form = VerifyPlan::HALVES; p.lists = true; p.single = false; return p; }
   p.single = n <= SF_CHUNK;
+  // Vis/CorGuessMatchToProjection = true: pass 2 is k_guided_tp, a stage kernel; the fused, split and chain forms carry
+  // only the other branch (guided_body) inline
+  if (c->dparams.guess_match_to_projection) { p.form = VerifyPlan::STAGES; p.lists = true; return p; }
   if (c->chain_pnp && sf_split_pnp_applicable(c, v)) { p.form = VerifyPlan::SPLIT_PNP; p.lists = true; }
   else if (sf_use_split(c, v, n)) { p.form = VerifyPlan::SPLIT; p.lists = true; }
   else if (sf_fused_lds_bytes(c, v) != 0 && !c->dparams.bundle_adjustment) { p.form = VerifyPlan::FUSED; p.lists = c->debug_corr; }

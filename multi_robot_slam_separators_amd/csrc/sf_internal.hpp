@@ -87,6 +87,7 @@ struct DeviceParams {
   float ba_robust_kernel_delta, ba_pixel_variance, stereo_baseline;
   int32_t force_3dof;         // Reg/Force3DoF
   int32_t bidirectional;      // Vis/ForwardEstOnly = false (stage pipeline only)
+  int32_t guess_match_to_projection;   // Vis/CorGuessMatchToProjection: pass 2 by k_guided_tp (stage pipeline only)
   int32_t dbg_corr;           // fused kernel: also copy correspondence lists / headers / pass states to the global
                               // workspace (SF_OPT_DEBUG_CORR; sf_debug_correspondences)
   int32_t accept_on;          // chain kernels: accepted results also stream to the host as they are produced, into ...

@@ -70,6 +70,9 @@ class SepfinderGeometricTools {
     int est = 0;
     n.param("estimation_type", est, 0);          // Vis/EstimationType: 0 = 3D->3D, 1 = PnP
     p.estimation_type = est;
+    bool match_to_projection = false;
+    n.param("guess_match_to_projection", match_to_projection, false);   // Vis/CorGuessMatchToProjection
+    p.guess_match_to_projection = match_to_projection ? 1 : 0;
     p.fx = info_l.P[0]; p.fy = info_l.P[5]; p.cx = info_l.P[2]; p.cy = info_l.P[6];
     p.image_width = (int32_t)info_l.width;
     p.image_height = (int32_t)info_l.height;
