@@ -675,19 +675,19 @@ int sf_launch_merge_directions_ba(sf_context* c, StoreView st, const int32_t* d_
     SF_HIP(c, hipFuncSetAttribute((const void*)k_merge_directions_ba<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     c->merge_ba_attr_set = true;
   }
-  int32_t* counters = (int32_t*)c->counters.p;
-  const int32_t* list = (const int32_t*)(pass == 1 ? c->list1.p : c->list3.p);
+  int32_t* counters = (int32_t*)c->w->counters.p;
+  const int32_t* list = (const int32_t*)(pass == 1 ? c->w->list1.p : c->w->list3.p);
   const int32_t* counter = counters + (pass == 1 ? 0 : 2);
-  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->corr1.p : c->corr2.p);
-  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->hdr1.p : c->hdr2.p);
-  PassState* ps = (PassState*)(pass == 1 ? c->pass1.p : c->pass2.p);
+  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p);
+  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p);
+  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
   const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
-  const uint8_t* guided_flag = pass == 2 ? (const uint8_t*)c->flags.p : nullptr;
+  const uint8_t* guided_flag = pass == 2 ? (const uint8_t*)c->w->flags.p : nullptr;
   if (pnp)
     hipLaunchKernelGGL(k_merge_directions_ba<true>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, list, counter,
-                       corr, hdr, guided_flag, ps, (const PassState*)c->pass_back.p, mask_f, mask_b, end_3dof, c->dparams);
+                       corr, hdr, guided_flag, ps, (const PassState*)c->w->pass_back.p, mask_f, mask_b, end_3dof, c->dparams);
   else
     hipLaunchKernelGGL(k_merge_directions_ba<false>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, list, counter,
-                       corr, hdr, guided_flag, ps, (const PassState*)c->pass_back.p, mask_f, mask_b, end_3dof, c->dparams);
+                       corr, hdr, guided_flag, ps, (const PassState*)c->w->pass_back.p, mask_f, mask_b, end_3dof, c->dparams);
   return SF_OK;
 }

@@ -1013,8 +1013,8 @@ static int launch_guided_tp(sf_context* c, StoreView st, const int32_t* d_from, 
   if (lds > 64 * 1024)   // (K > ~3 000 features: above the default dynamic LDS limit; never at the bench's K = 500)
     SF_HIP(c, hipFuncSetAttribute((const void*)k_guided_tp<W, L2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   hipLaunchKernelGGL((k_guided_tp<W, L2>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                     (const PassState*)c->pass1.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p, (uint32_t*)c->corr2.p,
-                     (CorrHeader*)c->hdr2.p, (int32_t*)c->list3.p, (int32_t*)c->counters.p + 2, c->dparams);
+                     (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p, (uint32_t*)c->w->corr2.p,
+                     (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, (int32_t*)c->w->counters.p + 2, c->dparams);
   return SF_OK;
 }
 
@@ -1040,26 +1040,26 @@ int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const i
   if (c->dparams.guess_match_to_projection) return sf_launch_guided_tp(c, st, d_from, d_to, n);
   const int nc = c->dparams.grid_gx * c->dparams.grid_gy;
   const size_t lds = sf_guided_lds_bytes(st.kcap, nc);
-  int32_t* counters = (int32_t*)c->counters.p;
+  int32_t* counters = (int32_t*)c->w->counters.p;
   sf_prof_begin(c, SF_K_GUIDED);
   if (c->params.desc_type == 1) {
     if (st.w == 64)
       hipLaunchKernelGGL((k_guided<64, true>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                         (const PassState*)c->pass1.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p,
-                         (uint32_t*)c->corr2.p, (CorrHeader*)c->hdr2.p, (int32_t*)c->list3.p, counters + 2, c->dparams);
+                         (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
+                         (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2, c->dparams);
     else
       hipLaunchKernelGGL((k_guided<128, true>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                         (const PassState*)c->pass1.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p,
-                         (uint32_t*)c->corr2.p, (CorrHeader*)c->hdr2.p, (int32_t*)c->list3.p, counters + 2, c->dparams);
+                         (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
+                         (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2, c->dparams);
   } else if (st.w == 8) {
     hipLaunchKernelGGL(k_guided<8>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                       (const PassState*)c->pass1.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p,
-                       (uint32_t*)c->corr2.p, (CorrHeader*)c->hdr2.p, (int32_t*)c->list3.p, counters + 2,
+                       (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
+                       (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2,
                        c->dparams);
   } else {
     hipLaunchKernelGGL(k_guided<16>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                       (const PassState*)c->pass1.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p,
-                       (uint32_t*)c->corr2.p, (CorrHeader*)c->hdr2.p, (int32_t*)c->list3.p, counters + 2,
+                       (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
+                       (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2,
                        c->dparams);
   }
   sf_prof_end(c, SF_K_GUIDED);
@@ -1070,7 +1070,7 @@ int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const i
 int sf_launch_finalize(sf_context* c, int n, sf_result* d_out) {
   if (n <= 0) return SF_OK;
   hipLaunchKernelGGL(k_finalize, dim3((n + SF_BLOCK - 1) / SF_BLOCK), dim3(SF_BLOCK), 0, c->stream, n,
-                     (const PassState*)c->pass1.p, (const PassState*)c->pass2.p, (const uint8_t*)c->flags.p, d_out);
+                     (const PassState*)c->w->pass1.p, (const PassState*)c->w->pass2.p, (const uint8_t*)c->w->flags.p, d_out);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }

@@ -1035,33 +1035,33 @@ template <int W, int NQ, int NT>
 void launch_match_v2(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   size_t lds = sf_match_lds_bytes(st.kcap, W);
   if (const char* v = getenv("SF_MATCH_LDS_PAD")) lds += (size_t)atoi(v);   // occupancy experiment (diagnostic)
-  int32_t* counters = (int32_t*)c->counters.p;
+  int32_t* counters = (int32_t*)c->w->counters.p;
   if constexpr (NQ == 0)
     hipLaunchKernelGGL((k_match_global_mf<W, NT>), dim3(n), dim3(NT), lds, c->stream, st, d_from, d_to,
-                       c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->corr1.p,
-                       (CorrHeader*)c->hdr1.p, (PassState*)c->pass1.p, (int32_t*)c->list1.p, counters + 0);
+                       c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p,
+                       (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
   else
     hipLaunchKernelGGL((k_match_global_v2<W, NQ, NT>), dim3(n), dim3(NT), lds, c->stream, st, d_from, d_to,
-                       c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->corr1.p,
-                       (CorrHeader*)c->hdr1.p, (PassState*)c->pass1.p, (int32_t*)c->list1.p, counters + 0);
+                       c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p,
+                       (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
 }
 
 template <int W, int NQ, int NT>
 void launch_match(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   const size_t lds = (size_t)(2 * st.kcap + 16) * sizeof(int);
-  int32_t* counters = (int32_t*)c->counters.p;
+  int32_t* counters = (int32_t*)c->w->counters.p;
   hipLaunchKernelGGL((k_match_global<W, NQ, NT>), dim3(n), dim3(NT), lds, c->stream, st, d_from, d_to,
-                     c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->corr1.p, (CorrHeader*)c->hdr1.p,
-                     (PassState*)c->pass1.p, (int32_t*)c->list1.p, counters + 0);
+                     c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p,
+                     (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
 }
 
 template <int W>
 void launch_match_l2(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   const size_t lds = (size_t)(2 * st.kcap + 16) * sizeof(int);
-  int32_t* counters = (int32_t*)c->counters.p;
+  int32_t* counters = (int32_t*)c->w->counters.p;
   hipLaunchKernelGGL((k_match_global<W, 1, 256, true>), dim3(n), dim3(256), lds, c->stream, st, d_from, d_to,
-                     c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->corr1.p, (CorrHeader*)c->hdr1.p,
-                     (PassState*)c->pass1.p, (int32_t*)c->list1.p, counters + 0);
+                     c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p,
+                     (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
 }
 
 }  // namespace

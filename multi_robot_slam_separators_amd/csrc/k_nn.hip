@@ -1365,16 +1365,16 @@ static int nn_filter_reserve(sf_context* c, NnFilterBufs& fb) {
   int rc;
   const unsigned cap = (unsigned)std::max<size_t>((size_t)1 << 20, (size_t)64 * n_l);
   {
-    const void* before = c->nn_cand.p;
-    if ((rc = sf_buf_reserve(c, c->nn_cand, (size_t)cap * 16 + 128)) != SF_OK) return rc;
-    if (c->nn_cand.p != before) c->nn_count_primed = false;      // (a fresh buffer: nobody zeroed its counter blocks)
+    const void* before = c->w->nn_cand.p;
+    if ((rc = sf_buf_reserve(c, c->w->nn_cand, (size_t)cap * 16 + 128)) != SF_OK) return rc;
+    if (c->w->nn_cand.p != before) c->w->nn_count_primed = false;      // (a fresh buffer: nobody zeroed its counter blocks)
   }
   if ((rc = sf_buf_reserve(c, c->nn_rowmin, (size_t)(n_l_pad + n_r_pad) * 8)) != SF_OK) return rc;
   fb.rowc = (float2*)c->nn_rowmin.p;
   fb.colc = fb.rowc + n_l_pad;
-  fb.count = (unsigned*)c->nn_cand.p;
-  fb.cand = (uint2*)((char*)c->nn_cand.p + 128);
-  fb.cdist = (double*)((char*)c->nn_cand.p + 128 + (size_t)cap * 8);
+  fb.count = (unsigned*)c->w->nn_cand.p;
+  fb.cand = (uint2*)((char*)c->w->nn_cand.p + 128);
+  fb.cdist = (double*)((char*)c->w->nn_cand.p + 128 + (size_t)cap * 8);
   fb.cap = cap;
 
   return SF_OK;
@@ -1405,11 +1405,11 @@ static int nn_filter_launch(sf_context* c, NnFilterBufs& fb, int level, int kdim
     // |dot16 - dot32| <= (2^-10 (1 + 2^-11) + k 2^-24) * ||a|| ||b||  (operand rounding + fp32 accumulation)
     const float eps_rel = (float)(ldexp(1.0, -10) * 1.001 + (double)kdims * ldexp(1.0, -24));
     const float scale = c->nn_local.h_scale * c->nn_recv.h_scale;   // product of two powers of two: exact
-    count = (unsigned*)((char*)c->nn_cand.p + 64 * c->nn_count_idx);
-    unsigned* const count_next = (unsigned*)((char*)c->nn_cand.p + 64 * (c->nn_count_idx ^ 1));
-    if (!c->nn_count_primed) SF_HIP(c, hipMemsetAsync(count, 0, 64, c->stream));
-    c->nn_count_idx ^= 1;
-    c->nn_count_primed = false;
+    count = (unsigned*)((char*)c->w->nn_cand.p + 64 * c->w->nn_count_idx);
+    unsigned* const count_next = (unsigned*)((char*)c->w->nn_cand.p + 64 * (c->w->nn_count_idx ^ 1));
+    if (!c->w->nn_count_primed) SF_HIP(c, hipMemsetAsync(count, 0, 64, c->stream));
+    c->w->nn_count_idx ^= 1;
+    c->w->nn_count_primed = false;
     // the per-row / per-column coefficients depend only on the norms, the masks, the threshold and the
     // prefix level: rebuilt when one of them changed, not per query
     const bool coef_ok = c->nn_coef_level == level && c->nn_coef_nl == n_l && c->nn_coef_nr == n_r &&
@@ -1464,7 +1464,7 @@ static int nn_filter_launch(sf_context* c, NnFilterBufs& fb, int level, int kdim
         hipLaunchKernelGGL(kern, dim3(gy * ((gx + tps - 1) / tps)), dim3(256), 0, c->stream,
                            (const _Float16*)c->nn_local.rows_h.p, (const _Float16*)c->nn_recv.rows_h.p, rowc, colc, gx,
                            gy, tps, cand, count, cap, count_next);
-      c->nn_count_primed = true;                 // (this launch zeroes the other block for the next one)
+      c->w->nn_count_primed = true;                 // (this launch zeroes the other block for the next one)
     } else if (nn_t256_on() && kdims % 64 == 0 && kdims >= 256) {
       static bool attr256 = false;      // (one device per process in every deployment of this library; set once)
       if (!attr256) {
@@ -1556,8 +1556,7 @@ static int nn_run_filter(sf_context* c, int* done) {
         c->spec.launched = true;
       }
       {
-        const hipStream_t main_stream = c->stream;
-        c->stream = cs;                      // (sf_prof_begin / _end record on the stream the kernel runs on)
+        UseWorkspace on_cs(c, *c->w, cs);    // (sf_prof_begin / _end record on the stream the kernel runs on)
         sf_prof_begin(c, SF_K_NN_REFINE);
         // sized like the speculative copy below (2N + 1024 candidates): a grid for the whole sparse limit
         // (8N + 4096) is 4/5 empty workgroups that the dispatcher still has to walk through -- beside the
@@ -1577,7 +1576,6 @@ static int nn_run_filter(sf_context* c, int* done) {
         hipLaunchKernelGGL(k_nn_refine, dim3(refine_wgs), dim3(256), 0, cs, cand, count, spec,
                            (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, dim, ld, cdist, 0u);
         sf_prof_end(c, SF_K_NN_REFINE);
-        c->stream = main_stream;
       }
       SF_HIP(c, hipMemcpyAsync(c->nn_pinned, count, 4, hipMemcpyDeviceToHost, cs));
       SF_HIP(c, hipMemcpyAsync(h_cand, cand, (size_t)spec * 8, hipMemcpyDeviceToHost, cs));
@@ -1746,8 +1744,8 @@ int sf_nn_walk_dev(sf_context* c, const double* d_row_min, const int32_t* d_row_
   const size_t off_rows = n_pad * 8, off_sorted = off_rows + n_pad * 4, off_minpos = off_sorted + n_pad * 4,
                off_cnt = off_minpos + (((size_t)n_r * 4 + 63) & ~(size_t)63), off_nu = off_cnt + (((size_t)n_tiles * 4 + 63) & ~(size_t)63);
   int rc;
-  if ((rc = sf_buf_reserve(c, c->walk_scratch, off_nu + 64)) != SF_OK) return rc;
-  char* w = (char*)c->walk_scratch.p;
+  if ((rc = sf_buf_reserve(c, c->w->walk_scratch, off_nu + 64)) != SF_OK) return rc;
+  char* w = (char*)c->w->walk_scratch.p;
   unsigned long long* keys = (unsigned long long*)w;
   int* rows = (int*)(w + off_rows);
   int* sorted = (int*)(w + off_sorted);

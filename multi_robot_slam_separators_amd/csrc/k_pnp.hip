@@ -804,29 +804,29 @@ int sf_launch_pnp(sf_context* c, StoreView st, const int32_t* d_from, const int3
     SF_HIP(c, hipFuncSetAttribute((const void*)k_pnp<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
-  int32_t* counters = (int32_t*)c->counters.p;
-  const int32_t* list = (const int32_t*)(pass == 1 ? c->list1.p : c->list3.p);
+  int32_t* counters = (int32_t*)c->w->counters.p;
+  const int32_t* list = (const int32_t*)(pass == 1 ? c->w->list1.p : c->w->list3.p);
   const int32_t* counter = counters + (pass == 1 ? 0 : 2);
-  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->corr1.p : c->corr2.p);
-  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->hdr1.p : c->hdr2.p);
-  PassState* ps = (PassState*)(pass == 1 ? c->pass1.p : c->pass2.p);
+  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p);
+  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p);
+  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
   const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
   // (pass 1 always matches globally; pass 2's correspondences are the guided matcher's where its flag says so)
-  const uint8_t* guided_flag = pass == 2 ? (const uint8_t*)c->flags.p : nullptr;
+  const uint8_t* guided_flag = pass == 2 ? (const uint8_t*)c->w->flags.p : nullptr;
   uint8_t *mask_f = nullptr, *mask_b = nullptr;
   if (bidir) {
     int rc;
     const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->dir_mask, 2 * mb)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->pass_back, (size_t)n * sizeof(PassState))) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->dir_mask.p;
+    if ((rc = sf_buf_reserve(c, c->w->dir_mask, 2 * mb)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->w->pass_back, (size_t)n * sizeof(PassState))) != SF_OK) return rc;
+    mask_f = (uint8_t*)c->w->dir_mask.p;
     mask_b = mask_f + mb;
     SF_HIP(c, hipMemsetAsync(mask_f, 0, 2 * mb, c->stream));
   } else if (ba) {      // the estimate's inlier set, one byte per "from" feature: what the adjustment's launch rebuilds its words from
     int rc;
     const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->dir_mask, mb)) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->dir_mask.p;
+    if ((rc = sf_buf_reserve(c, c->w->dir_mask, mb)) != SF_OK) return rc;
+    mask_f = (uint8_t*)c->w->dir_mask.p;
     SF_HIP(c, hipMemsetAsync(mask_f, 0, mb, c->stream));
   }
   const int kid = pass == 1 ? SF_K_RANSAC1 : SF_K_RANSAC2;
@@ -839,13 +839,13 @@ int sf_launch_pnp(sf_context* c, StoreView st, const int32_t* d_from, const int3
   else if (!bidir) launch(k_pnp<0>, ps, nullptr, end_3dof);
   else {
     launch(k_pnp<0>, ps, mask_f, 0);
-    launch(k_pnp<1>, (PassState*)c->pass_back.p, mask_b, 0);
+    launch(k_pnp<1>, (PassState*)c->w->pass_back.p, mask_b, 0);
     if (ba) {
       const int rc = sf_launch_merge_directions_ba(c, st, d_from, d_to, n, pass, true, mask_f, mask_b);
       if (rc != SF_OK) return rc;
     } else
     hipLaunchKernelGGL(k_merge_directions_pnp, dim3(n), dim3(64), 0, c->stream, st, d_from, d_to, list, counter, corr, hdr,
-                       guided_flag, ps, (const PassState*)c->pass_back.p, (const uint8_t*)mask_f, (const uint8_t*)mask_b,
+                       guided_flag, ps, (const PassState*)c->w->pass_back.p, (const uint8_t*)mask_f, (const uint8_t*)mask_b,
                        c->dparams.min_inliers, end_3dof);
   }
   sf_prof_end(c, kid);

@@ -867,46 +867,46 @@ int sf_launch_ransac(sf_context* c, StoreView st, const int32_t* d_from, const i
     SF_HIP(c, hipFuncSetAttribute((const void*)k_ransac<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
-  int32_t* counters = (int32_t*)c->counters.p;
-  const int32_t* list = (const int32_t*)(pass == 1 ? c->list1.p : c->list3.p);
+  int32_t* counters = (int32_t*)c->w->counters.p;
+  const int32_t* list = (const int32_t*)(pass == 1 ? c->w->list1.p : c->w->list3.p);
   const int32_t* counter = counters + (pass == 1 ? 0 : 2);
-  PassState* ps = (PassState*)(pass == 1 ? c->pass1.p : c->pass2.p);
+  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
   // Reg/Force3DoF: the end-of-pass application, and for pass 1 the one its result meets as the guess of pass 2
   const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
   uint8_t *mask_f = nullptr, *mask_b = nullptr;
   if (bidir) {
     int rc;
     const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->dir_mask, 2 * mb)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->pass_back, (size_t)n * sizeof(PassState))) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->dir_mask.p;
+    if ((rc = sf_buf_reserve(c, c->w->dir_mask, 2 * mb)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->w->pass_back, (size_t)n * sizeof(PassState))) != SF_OK) return rc;
+    mask_f = (uint8_t*)c->w->dir_mask.p;
     mask_b = mask_f + mb;
     SF_HIP(c, hipMemsetAsync(mask_f, 0, 2 * mb, c->stream));
   } else if (ba) {      // the estimate's inlier set, one byte per "from" feature: what the adjustment's launch rebuilds its words from
     int rc;
     const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->dir_mask, mb)) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->dir_mask.p;
+    if ((rc = sf_buf_reserve(c, c->w->dir_mask, mb)) != SF_OK) return rc;
+    mask_f = (uint8_t*)c->w->dir_mask.p;
     SF_HIP(c, hipMemsetAsync(mask_f, 0, mb, c->stream));
   }
   const int kid = pass == 1 ? SF_K_RANSAC1 : SF_K_RANSAC2;
   sf_prof_begin(c, kid);
   auto launch = [&](auto kern, PassState* out, uint8_t* mask, int extra) {
     hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, list, counter,
-                       (const uint32_t*)(pass == 1 ? c->corr1.p : c->corr2.p),
-                       (const CorrHeader*)(pass == 1 ? c->hdr1.p : c->hdr2.p), out, mask, extra, c->dparams);
+                       (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p),
+                       (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p), out, mask, extra, c->dparams);
   };
   if (ba && !bidir) launch(k_ransac<0>, ps, mask_f, 0);     // (Reg/Force3DoF's end-of-pass application: behind the adjustment)
   else if (!bidir) launch(k_ransac<0>, ps, nullptr, end_3dof);
   else {
     launch(k_ransac<0>, ps, mask_f, 0);
-    launch(k_ransac<1>, (PassState*)c->pass_back.p, mask_b, 0);
+    launch(k_ransac<1>, (PassState*)c->w->pass_back.p, mask_b, 0);
     if (ba) {
       const int rc = sf_launch_merge_directions_ba(c, st, d_from, d_to, n, pass, false, mask_f, mask_b);
       if (rc != SF_OK) return rc;
     } else
     hipLaunchKernelGGL(k_merge_directions, dim3(n), dim3(64), 0, c->stream, list, counter, ps,
-                       (const PassState*)c->pass_back.p, (const uint8_t*)mask_f, (const uint8_t*)mask_b, st.kcap, end_3dof);
+                       (const PassState*)c->w->pass_back.p, (const uint8_t*)mask_f, (const uint8_t*)mask_b, st.kcap, end_3dof);
   }
   sf_prof_end(c, kid);
   SF_HIP(c, hipGetLastError());

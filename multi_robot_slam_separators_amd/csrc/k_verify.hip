@@ -281,8 +281,8 @@ int launch_fused(sf_context* c, StoreView st, const int32_t* d_from, const int32
     attr_set = true;
   }
   hipLaunchKernelGGL((k_verify_fused<W, NQ, WIDE>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                     (uint32_t*)c->corr1.p, (CorrHeader*)c->hdr1.p, (PassState*)c->pass1.p, (uint32_t*)c->corr2.p,
-                     (CorrHeader*)c->hdr2.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p, d_out, c->dparams,
+                     (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (uint32_t*)c->w->corr2.p,
+                     (CorrHeader*)c->w->hdr2.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p, d_out, c->dparams,
                      tail_off, c->pair_src);
   return SF_OK;
 }
@@ -465,12 +465,12 @@ int sf_launch_ba_pass(sf_context* c, StoreView st, const int32_t* d_from, const 
     return sf_fail(c, SF_ERANGE, "bundle adjustment needs %zu B of LDS (> 160 KiB)", sf_ba_lds_bytes(st.kcap));
   const bool pnp = c->dparams.estimation_type == 1;
   const int nw = c->ba_nw;
-  int32_t* counters = (int32_t*)c->counters.p;
-  const int32_t* list = (const int32_t*)(list_sel == 1 ? c->list1.p : c->list3.p);
+  int32_t* counters = (int32_t*)c->w->counters.p;
+  const int32_t* list = (const int32_t*)(list_sel == 1 ? c->w->list1.p : c->w->list3.p);
   const int32_t* counter = counters + (list_sel == 1 ? 0 : 2);
-  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->corr1.p : c->corr2.p);
-  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->hdr1.p : c->hdr2.p);
-  PassState* ps = (PassState*)(pass == 1 ? c->pass1.p : c->pass2.p);
+  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p);
+  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p);
+  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
   const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
   const bool both = st.kcap > SF_BA_SMALL_CAP;       // (a keyframe cannot give more words than it has features)
   sf_prof_begin(c, SF_K_BA);
@@ -481,7 +481,7 @@ int sf_launch_ba_pass(sf_context* c, StoreView st, const int32_t* d_from, const 
       attr = true;
     }
     hipLaunchKernelGGL(kern, dim3(n), dim3(64 * nw), lds, c->stream, st, d_from, d_to, list, counter, corr, hdr, mask, run,
-                       ps, end_3dof, fin ? 1 : 0, (const PassState*)c->pass1.p, (const uint8_t*)c->flags.p, d_out,
+                       ps, end_3dof, fin ? 1 : 0, (const PassState*)c->w->pass1.p, (const uint8_t*)c->w->flags.p, d_out,
                        c->dparams, cap, both ? 1 : 0);
     return SF_OK;
   };
@@ -530,11 +530,11 @@ int launch_chain(sf_context* c, StoreView st, const int32_t* d_from, const int32
     SF_HIP(c, hipFuncSetAttribute((const void*)k_chain<W, NW, PART>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
   }
-  int32_t* counters = (int32_t*)c->counters.p;
+  int32_t* counters = (int32_t*)c->w->counters.p;
   hipLaunchKernelGGL((k_chain<W, NW, PART>), dim3(n), dim3(64 * NW), lds, c->stream, st, d_from, d_to,
-                     (const uint32_t*)c->corr1.p, (const CorrHeader*)c->hdr1.p, (PassState*)c->pass1.p,
-                     (uint32_t*)c->corr2.p, (CorrHeader*)c->hdr2.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p,
-                     (const int32_t*)c->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams, tail_off, H);
+                     (const uint32_t*)c->w->corr1.p, (const CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p,
+                     (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
+                     (const int32_t*)c->w->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams, tail_off, H);
   return SF_OK;
 }
 
@@ -549,11 +549,11 @@ int launch_chain_pnp(sf_context* c, StoreView st, const int32_t* d_from, const i
     SF_HIP(c, hipFuncSetAttribute((const void*)k_chain_pnp<W, PART, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
-  int32_t* counters = (int32_t*)c->counters.p;
+  int32_t* counters = (int32_t*)c->w->counters.p;
   hipLaunchKernelGGL((k_chain_pnp<W, PART, NW>), dim3(n), dim3(64 * NW), lds, c->stream, st, d_from, d_to,
-                     (const uint32_t*)c->corr1.p, (const CorrHeader*)c->hdr1.p, (PassState*)c->pass1.p,
-                     (uint32_t*)c->corr2.p, (CorrHeader*)c->hdr2.p, (PassState*)c->pass2.p, (uint8_t*)c->flags.p,
-                     (const int32_t*)c->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams, H);
+                     (const uint32_t*)c->w->corr1.p, (const CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p,
+                     (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
+                     (const int32_t*)c->w->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams, H);
   return SF_OK;
 }
 
@@ -592,14 +592,14 @@ int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, c
   const bool pnp = c->dparams.estimation_type == 1;
   if (!(pnp ? sf_split_pnp_applicable(c, st) : sf_split_applicable(c, st)))
     return sf_fail(c, SF_EINVAL, "split verification pipeline not applicable");
-  SF_HIP(c, hipMemsetAsync(c->counters.p, 0, 64, c->stream));
+  SF_HIP(c, hipMemsetAsync(c->w->counters.p, 0, 64, c->stream));
   // (Round 5, profiles/r05zc_matcher_workgroups_per_cu.txt: with its workgroups per CU capped by an inflated LDS request the
   //  launch alone takes 284 us at three per CU, 296 at two and 295 at ONE -- the pipelined scan keeps the matrix pipe busy
   //  from one wavefront per SIMD.  Capping it inside the overlapped step changes nothing (23.2-23.3 M pairs/s either way):
   //  the step as a whole is bound by vector instruction issue -- 425 M busy cycles of this kernel + 196 M of the chains +
   //  35 M of the NN kernels per step over 1 024 SIMDs = 0.32-0.36 ms of the 0.43 ms step, profiles/r05w_sq_*.)
   const size_t lds_m = sf_match_lds_bytes(st.kcap, st.w);
-  int32_t* counters = (int32_t*)c->counters.p;
+  int32_t* counters = (int32_t*)c->w->counters.p;
   sf_prof_begin(c, SF_K_MATCH);
   if (lds_m > 64 * 1024 && !c->split_match_attr[st.w == 16]) {
     if (st.w == 8)
@@ -610,8 +610,8 @@ int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, c
   }
 #define SF_SPLIT_MATCH(...)                                                                                        \
   hipLaunchKernelGGL((k_match_split<__VA_ARGS__>), dim3(n), dim3(SF_BLOCK), lds_m, c->stream, st, d_from, d_to,    \
-                     (uint32_t*)c->corr1.p, (CorrHeader*)c->hdr1.p, (PassState*)c->pass1.p, (CorrHeader*)c->hdr2.p, \
-                     (PassState*)c->pass2.p, (uint8_t*)c->flags.p, (int32_t*)c->list1.p, counters + 0, d_out, c->dparams, \
+                     (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (CorrHeader*)c->w->hdr2.p, \
+                     (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p, (int32_t*)c->w->list1.p, counters + 0, d_out, c->dparams, \
                      sf_est_mode(c))
   // (shapes measured on the pipelined scan, profiles/r05t_match_split_shapes.txt: 4 tiles / 3 workgroups per CU 22.5 M
   //  pairs/s on the 3D-3D split step, 2 tiles / 4: 22.2, 2 tiles / 3: 21.3, 4 tiles / 2: 21.2; PnP 15.0 / 15.0 / 14.8 / 13.7)
@@ -624,8 +624,8 @@ int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, c
   // bundle adjustment on: [estimate 1] -> adjustment -> [guided matching + estimate 2] -> adjustment + result
   int rc;
   const size_t mb = (size_t)n * st.kcap;
-  if ((rc = sf_buf_reserve(c, c->dir_mask, 2 * mb + (size_t)n)) != SF_OK) return rc;
-  uint8_t* m1 = (uint8_t*)c->dir_mask.p;
+  if ((rc = sf_buf_reserve(c, c->w->dir_mask, 2 * mb + (size_t)n)) != SF_OK) return rc;
+  uint8_t* m1 = (uint8_t*)c->w->dir_mask.p;
   const BaHandover H = {m1, m1 + mb, m1 + 2 * mb};
   SF_HIP(c, hipMemsetAsync(m1, 0, 2 * mb + (size_t)n, c->stream));
   if ((rc = launch_chain_part<1>(c, st, d_from, d_to, n, d_out, pnp, H)) != SF_OK) return rc;

@@ -750,6 +750,7 @@ extern "C" int sf_create(const sf_params* p, int device, sf_handle* out) {
     return SF_EHIP;
   }
   c->own_stream = true;
+  c->ws[0].stream = c->stream;
   if (const char* v = getenv("SF_MATCH_VARIANT")) c->match_variant = atoi(v);
   if (const char* v = getenv("SF_FUSED")) {   // 0: stage kernels (A/B reference), 1: fused kernel, 2: split pipeline
     c->fused = atoi(v) != 0;
@@ -771,7 +772,7 @@ extern "C" int sf_create(const sf_params* p, int device, sf_handle* out) {
   if (const char* v = getenv("SF_STEP_LANES")) c->step_lanes = std::max(1, std::min(SF_STEP_MAX_LANES, atoi(v)));
   if (const char* v = getenv("SF_STEP_SPECULATE")) c->step_speculate = atoi(v) != 0;   // 0: every device step in the serial form
   if (const char* v = getenv("SF_STEP_DEVICE_WALK")) c->step_device_walk = atoi(v) != 0;   // 0: round 3's host walk inside sf_step_issue
-  if ((rc = sf_buf_reserve(c, c->counters, 64)) != SF_OK) { g_create_error = c->err; sf_destroy(c); return rc; }
+  if ((rc = sf_buf_reserve(c, c->w->counters, 64)) != SF_OK) { g_create_error = c->err; sf_destroy(c); return rc; }
   *out = c;
   return SF_OK;
 }
@@ -779,55 +780,36 @@ extern "C" int sf_create(const sf_params* p, int device, sf_handle* out) {
 extern "C" void sf_destroy(sf_handle c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->twin) {   // shadow context of the two-stream verification: workspace, counters, stream only
-    sf_context* t = c->twin;
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    prof_resolve(t);
-    for (hipEvent_t e : t->prof_event_pool) (void)hipEventDestroy(e);
-    Buf* tb[] = {&t->corr1, &t->corr2, &t->hdr1, &t->hdr2, &t->pass1, &t->pass2, &t->list1, &t->list3, &t->counters, &t->flags};
-    for (Buf* b : tb) buf_free(*b);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
-    delete t;
-    c->twin = nullptr;
-  }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   (void)sf_comm_destroy(c);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  for (Workspace& w : c->ws) {
+    if (w.stream) (void)hipStreamSynchronize(w.stream);
+    if (w.aux) (void)hipStreamSynchronize(w.aux);
+  }
   prof_resolve(c);
   for (hipEvent_t e : c->prof_event_pool) (void)hipEventDestroy(e);
   Buf* bufs[] = {&c->store.desc, &c->store.xyz, &c->store.kp, &c->store.meta, &c->scratch.desc, &c->scratch.xyz,
-                 &c->scratch.kp, &c->scratch.meta, &c->pair_from, &c->pair_to, &c->corr1, &c->corr2, &c->hdr1,
-                 &c->hdr2, &c->pass1, &c->pass2, &c->list1, &c->list3, &c->counters, &c->results,
-                 &c->flags, &c->nn_local.rows, &c->nn_local.norms, &c->nn_local.rows_h, &c->nn_local.norms_k, &c->nn_recv.norms_k, &c->nn_recv.rows,
+                 &c->scratch.kp, &c->scratch.meta, &c->nn_local.rows, &c->nn_local.norms, &c->nn_local.rows_h, &c->nn_local.norms_k, &c->nn_recv.norms_k, &c->nn_recv.rows,
                  &c->nn_recv.norms, &c->nn_recv.rows_h, &c->d_mask_local, &c->d_mask_other, &c->d_ign_ptr,
-                 &c->d_ign_col, &c->nn_rowmin, &c->nn_exact, &c->nn_cand, &c->nn_scalar, &c->comm_scratch, &c->compact_scratch, &c->trace, &c->stage_desc, &c->stage_xyz, &c->stage_kp,
+                 &c->d_ign_col, &c->nn_rowmin, &c->nn_exact, &c->nn_scalar, &c->comm_scratch, &c->trace, &c->stage_desc, &c->stage_xyz, &c->stage_kp,
                  &c->ex_integral, &c->ex_desc, &c->ex_xyz, &c->ex_keep, &c->ex_rows, &c->brief_tests,
                  &c->gf_planes, &c->gf_keys, &c->gf_tmp, &c->gf_lists, &c->gf_scalar, &c->lk_pyr, &c->ft_images, &c->ft_kpts, &c->ft_flow, &c->ft_wire,
-                 &c->ft_counts, &c->pass_back, &c->dir_mask};
+                 &c->ft_counts};
   for (Buf* b : bufs) buf_free(*b);
-  for (sf_context::StepLane& L : c->lanes) {
-    if (L.stream) (void)hipStreamSynchronize(L.stream);
-    Buf* lb[] = {&L.pair_from, &L.pair_to, &L.corr1, &L.corr2, &L.hdr1, &L.hdr2, &L.pass1, &L.pass2, &L.pass_back, &L.dir_mask,
-                 &L.list1, &L.list3, &L.counters, &L.results, &L.flags, &L.nn_cand, &L.spec_from, &L.spec_to, &L.spec_results,
-                 &L.spec_index, &L.compact_scratch, &L.step_nn, &L.walk_scratch};
-    for (Buf* b : lb) buf_free(*b);
-    if (L.ev_main) (void)hipEventDestroy(L.ev_main);
-    if (L.ev_filter) (void)hipEventDestroy(L.ev_filter);
-    if (L.ev_walk) (void)hipEventDestroy(L.ev_walk);
-    if (L.aux) { (void)hipStreamSynchronize(L.aux); (void)hipStreamDestroy(L.aux); }
-    if (L.stream) (void)hipStreamDestroy(L.stream);
+  for (int k = 0; k <= SF_STEP_MAX_LANES; ++k) {
+    Workspace& w = c->ws[k];
+    w.for_each_buf(buf_free);
+    for (hipEvent_t e : {w.ev_main, w.ev_filter, w.ev_walk})
+      if (e) (void)hipEventDestroy(e);
+    if (w.aux) (void)hipStreamDestroy(w.aux);
+    if (w.stream && (k > 0 || c->own_stream)) (void)hipStreamDestroy(w.stream);
   }
-  if (c->ev_filter) (void)hipEventDestroy(c->ev_filter);
-  if (c->ev_walk) (void)hipEventDestroy(c->ev_walk);
-  if (c->aux) { (void)hipStreamSynchronize(c->aux); (void)hipStreamDestroy(c->aux); }
   for (int k = 0; k < SF_STEP_MAX_LANES; ++k) {                 // (placed streams nobody asked for)
     if (c->placement.main[k]) (void)hipStreamDestroy(c->placement.main[k]);
     if (c->placement.aux[k]) (void)hipStreamDestroy(c->placement.aux[k]);
   }
   if (c->placement.copy) (void)hipStreamDestroy(c->placement.copy);
-  buf_free(c->step_nn);
-  buf_free(c->walk_scratch);
   if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
   sf_netvlad_free(c);
   sf_ingest_pool_destroy(c);
@@ -839,15 +821,11 @@ extern "C" void sf_destroy(sf_handle c) {
   if (c->pairs_pinned) (void)hipHostFree(c->pairs_pinned);
   if (c->count_pinned) (void)hipHostFree(c->count_pinned);
   if (c->pairs_staged) (void)hipEventDestroy(c->pairs_staged);
-  {
-    Buf* sb[] = {&c->spec_from, &c->spec_to, &c->spec_results, &c->spec_index};
-    for (Buf* b : sb) buf_free(*b);
-    if (c->spec_index_pinned) (void)hipHostFree(c->spec_index_pinned);
-    if (c->spec_index_staged) (void)hipEventDestroy(c->spec_index_staged);
-    if (c->spec.ev_refined) (void)hipEventDestroy(c->spec.ev_refined);
-    if (c->spec.ev_copied) (void)hipEventDestroy(c->spec.ev_copied);
-    if (c->spec.copy_stream) { (void)hipStreamSynchronize(c->spec.copy_stream); (void)hipStreamDestroy(c->spec.copy_stream); }
-  }
+  if (c->spec_index_pinned) (void)hipHostFree(c->spec_index_pinned);
+  if (c->spec_index_staged) (void)hipEventDestroy(c->spec_index_staged);
+  if (c->spec.ev_refined) (void)hipEventDestroy(c->spec.ev_refined);
+  if (c->spec.ev_copied) (void)hipEventDestroy(c->spec.ev_copied);
+  if (c->spec.copy_stream) { (void)hipStreamSynchronize(c->spec.copy_stream); (void)hipStreamDestroy(c->spec.copy_stream); }
   for (auto& sb : c->step_blocks) {
     if (sb.pinned) (void)hipHostFree(sb.pinned);
     if (sb.done) (void)hipEventDestroy(sb.done);
@@ -855,14 +833,13 @@ extern "C" void sf_destroy(sf_handle c) {
     buf_free(sb.dev);
     buf_free(sb.dev_records);
   }
-  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
 #ifdef SF_CHAIN_TRACE
 // diagnostic build only: phase timestamps of the last verification ([n][32] uint64, 100 MHz ticks)
 extern "C" int sf_debug_chain_trace(sf_handle c, unsigned long long* out, int32_t n) {
-  if (!c || !out || n < 0 || n > c->ws_pairs) return SF_EINVAL;
+  if (!c || !out || n < 0 || n > c->w->ws_pairs) return SF_EINVAL;
   SF_HIP(c, hipStreamSynchronize(c->stream));
   SF_HIP(c, hipMemcpy(out, c->trace.p, (size_t)n * SF_TRACE_SLOTS * 8, hipMemcpyDeviceToHost));
   return SF_OK;
@@ -882,19 +859,17 @@ extern "C" int sf_set_stream(sf_handle c, void* hip_stream) {
   (void)sf_lanes_touch(c, true);
   SF_HIP(c, hipStreamSynchronize(c->stream));
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-  c->stream = (hipStream_t)hip_stream;
+  c->stream = c->ws[0].stream = (hipStream_t)hip_stream;
   c->own_stream = false;
   return SF_OK;
 }
 
 extern "C" int sf_synchronize(sf_handle c) {
   if (!c) return SF_EINVAL;
-  SF_HIP(c, hipStreamSynchronize(c->stream));
-  for (auto& L : c->lanes) {
-    if (L.stream) SF_HIP(c, hipStreamSynchronize(L.stream));
-    if (L.aux) SF_HIP(c, hipStreamSynchronize(L.aux));
+  for (Workspace& w : c->ws) {
+    if (w.stream || &w == c->ws) SF_HIP(c, hipStreamSynchronize(w.stream));   // (the handle's own may be the null stream)
+    if (w.aux) SF_HIP(c, hipStreamSynchronize(w.aux));
   }
-  if (c->aux) SF_HIP(c, hipStreamSynchronize(c->aux));
   return SF_OK;
 }
 
@@ -1217,16 +1192,16 @@ static int ws_reserve(sf_context* c, int n, int kcap, bool lists) {
   const size_t np = (size_t)n;
   const WsBytes w = ws_bytes(n, kcap, lists);
   if (lists) {
-    if ((rc = sf_buf_reserve(c, c->corr1, w.corr1)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->corr2, w.corr2)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->w->corr1, w.corr1)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->w->corr2, w.corr2)) != SF_OK) return rc;
   }
-  if ((rc = sf_buf_reserve(c, c->hdr1, w.hdr1)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->hdr2, w.hdr2)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->pass1, w.pass1)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->pass2, w.pass2)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->list1, w.list1)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->list3, w.list3)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->flags, w.flags)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->hdr1, w.hdr1)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->hdr2, w.hdr2)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->pass1, w.pass1)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->pass2, w.pass2)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->list1, w.list1)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->list3, w.list3)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->flags, w.flags)) != SF_OK) return rc;
 #ifndef SF_CHAIN_TRACE
   if (getenv("SF_DIAG")) {     // experiment: eight 64-bit diagnostic counters the kernels may bump (sf_debug_counters)
     // [0..511]: counters; then two 64-bit planes of [pair][kcap] per-point records of the guided pass
@@ -1243,8 +1218,8 @@ static int ws_reserve(sf_context* c, int n, int kcap, bool lists) {
   SF_HIP(c, hipMemsetAsync(c->trace.p, 0, np * SF_TRACE_SLOTS * 8, c->stream));
   c->dparams.dbg_trace = (unsigned long long*)c->trace.p;
 #endif
-  c->ws_pairs = n;
-  c->ws_kcap = kcap;
+  c->w->ws_pairs = n;
+  c->w->ws_kcap = kcap;
   return SF_OK;
 }
 
@@ -1359,68 +1334,46 @@ extern "C" int sf_debug_plan_workspace(const sf_params* p, int32_t kcap, int32_t
   return rc;
 }
 
-// One launch sequence for m <= SF_CHUNK pairs on ctx's stream and workspace, in the form the call's plan names.
-static int verify_sequence(sf_context* ctx, const StoreView& view, const int32_t* d_from, const int32_t* d_to, int m,
+// One launch sequence for m <= SF_CHUNK pairs on the current stream and workspace, in the form the call's plan names.
+static int verify_sequence(sf_context* c, const StoreView& view, const int32_t* d_from, const int32_t* d_to, int m,
                            sf_result* d_out, const VerifyPlan& plan) {
   int rc;
-  ctx->dparams.dbg_corr = ctx->debug_corr ? 1 : 0;
+  c->dparams.dbg_corr = c->debug_corr ? 1 : 0;
   switch (plan.form) {
     case VerifyPlan::SPLIT_PNP:
-      ctx->last_lists_valid = true;
-      return sf_launch_verify_split(ctx, view, d_from, d_to, m, d_out);
+      c->w->last_lists_valid = true;
+      return sf_launch_verify_split(c, view, d_from, d_to, m, d_out);
     case VerifyPlan::SPLIT:
       // (pass-2 lists only with the option or the bundle adjustment, whose launches read them; pass-1 lists always)
-      ctx->last_lists_valid = ctx->debug_corr || ctx->dparams.bundle_adjustment != 0;
-      return sf_launch_verify_split(ctx, view, d_from, d_to, m, d_out);
+      c->w->last_lists_valid = c->debug_corr || c->dparams.bundle_adjustment != 0;
+      return sf_launch_verify_split(c, view, d_from, d_to, m, d_out);
     case VerifyPlan::FUSED:
       // one launch: every pair's whole two-pass pipeline inside its workgroup (k_verify.hip); no work lists
-      ctx->last_lists_valid = ctx->debug_corr;
-      return sf_launch_verify_fused(ctx, view, d_from, d_to, m, d_out);
+      c->w->last_lists_valid = c->debug_corr;
+      return sf_launch_verify_fused(c, view, d_from, d_to, m, d_out);
     default: break;
   }
-  ctx->last_lists_valid = true;
-  SF_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));   // work-list counters of the stage kernels
-  if ((rc = sf_launch_match_global(ctx, view, d_from, d_to, m)) != SF_OK) return rc;
-  const bool pnp = ctx->dparams.estimation_type == 1;
-  if ((rc = (pnp ? sf_launch_pnp : sf_launch_ransac)(ctx, view, d_from, d_to, m, 1)) != SF_OK) return rc;
-  if ((rc = sf_launch_guided(ctx, view, d_from, d_to, m)) != SF_OK) return rc;
-  if ((rc = (pnp ? sf_launch_pnp : sf_launch_ransac)(ctx, view, d_from, d_to, m, 2)) != SF_OK) return rc;
-  return sf_launch_finalize(ctx, m, d_out);
+  c->w->last_lists_valid = true;
+  SF_HIP(c, hipMemsetAsync(c->w->counters.p, 0, 64, c->stream));   // work-list counters of the stage kernels
+  if ((rc = sf_launch_match_global(c, view, d_from, d_to, m)) != SF_OK) return rc;
+  const bool pnp = c->dparams.estimation_type == 1;
+  if ((rc = (pnp ? sf_launch_pnp : sf_launch_ransac)(c, view, d_from, d_to, m, 1)) != SF_OK) return rc;
+  if ((rc = sf_launch_guided(c, view, d_from, d_to, m)) != SF_OK) return rc;
+  if ((rc = (pnp ? sf_launch_pnp : sf_launch_ransac)(c, view, d_from, d_to, m, 2)) != SF_OK) return rc;
+  return sf_launch_finalize(c, m, d_out);
 }
 
-// The shadow context of the two-stream path (see sf_context::twin): created on first use.
-static int ensure_twin(sf_context* c) {
-  if (!c->twin) {
-    sf_context* t = new (std::nothrow) sf_context();
-    if (!t) return sf_fail(c, SF_ENOMEM, "out of host memory");
-    t->device = c->device;
-    // (a lowest-priority stream was tried so that the first half would match first and its estimation kernels
-    //  overlap the second half's matching: no gain -- both matching kernels still share the chip)
-    if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete t;
-      return sf_fail(c, SF_EHIP, "hipStreamCreateWithFlags failed");
-    }
-    t->own_stream = true;
-    c->twin = t;
-    int rc = sf_buf_reserve(t, t->counters, 64);
-    if (rc != SF_OK) { c->err = t->err; return rc; }
-    SF_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    SF_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  }
-  sf_context* t = c->twin;
-  t->params = c->params;          // parameters may have changed since the last batch
-  t->dparams = c->dparams;
-  t->match_variant = c->match_variant;
-  t->match_mfma = c->match_mfma;
-  t->fused = c->fused;
-  t->split = c->split;
-  t->chain_pnp = c->chain_pnp;
-  t->chain_nw = c->chain_nw;
-  t->chain_pnp_nw = c->chain_pnp_nw;
-  t->ba_nw = c->ba_nw;
-  t->ba_occ = c->ba_occ;
-  t->debug_corr = c->debug_corr;
-  t->prof = c->prof;
+// The stream of the second half of the two-stream path (ws[SF_STEP_MAX_LANES]): created on first use.
+static int half_create(sf_context* c) {
+  Workspace& h = c->ws[SF_STEP_MAX_LANES];
+  if (h.stream) return SF_OK;
+  // (a lowest-priority stream was tried so that the first half would match first and its estimation kernels
+  //  overlap the second half's matching: no gain -- both matching kernels still share the chip)
+  SF_HIP(c, hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
+  int rc = sf_buf_reserve(c, h.counters, 64);
+  if (rc != SF_OK) return rc;
+  SF_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  SF_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   return SF_OK;
 }
 
@@ -1443,27 +1396,30 @@ static int verify_device(sf_context* c, const Store& st, const int32_t* d_from, 
   const VerifyPlan plan = given ? *given : verify_plan(c, view, n);
   int rc;
   if (plan.form == VerifyPlan::HALVES) {
-    if ((rc = ensure_twin(c)) != SF_OK) return rc;
-    sf_context* t = c->twin;
+    if ((rc = half_create(c)) != SF_OK) return rc;
+    Workspace& h = c->ws[SF_STEP_MAX_LANES];
     VerifyPlan stages;                                   // (two FUSED halves on two streams were measured too and gain nothing)
     const int span = std::min(n, 2 * SF_CHUNK);          // pairs per round: one chunk per stream
     const int half0 = (std::min(span, n) + 1) / 2;
     if ((rc = ws_reserve(c, std::min(half0, SF_CHUNK), st.kcap, stages.lists)) != SF_OK) return rc;
-    if ((rc = ws_reserve(t, std::min(half0, SF_CHUNK), st.kcap, stages.lists)) != SF_OK) { c->err = t->err; return rc; }
+    {
+      UseWorkspace on(c, h);
+      if ((rc = ws_reserve(c, std::min(half0, SF_CHUNK), st.kcap, stages.lists)) != SF_OK) return rc;
+    }
     SF_HIP(c, hipEventRecord(c->ev_fork, c->stream));
-    SF_HIP(c, hipStreamWaitEvent(t->stream, c->ev_fork, 0));
+    SF_HIP(c, hipStreamWaitEvent(h.stream, c->ev_fork, 0));
     c->ws_split = 0;
     for (int off = 0; off < n; off += span) {
       const int m = std::min(span, n - off);
       const int ma = (m + 1) / 2, mb = m - ma;
       if (off == 0) c->ws_split = ma;
       if ((rc = verify_sequence(c, view, d_from + off, d_to + off, ma, d_out + off, stages)) != SF_OK) return rc;
-      if (mb > 0 && (rc = verify_sequence(t, view, d_from + off + ma, d_to + off + ma, mb, d_out + off + ma, stages)) != SF_OK) {
-        c->err = t->err;
-        return rc;
+      if (mb > 0) {
+        UseWorkspace on(c, h);
+        if ((rc = verify_sequence(c, view, d_from + off + ma, d_to + off + ma, mb, d_out + off + ma, stages)) != SF_OK) return rc;
       }
     }
-    SF_HIP(c, hipEventRecord(c->ev_join, t->stream));
+    SF_HIP(c, hipEventRecord(c->ev_join, h.stream));
     SF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
     return SF_OK;
   }
@@ -1489,8 +1445,8 @@ extern "C" int sf_verify_matches_device(sf_handle c, const sf_match* matches, in
   if (n == 0) return SF_OK;
   SF_HIP(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = sf_buf_reserve(c, c->pair_from, (size_t)n * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->pair_to, (size_t)n * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->pair_from, (size_t)n * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->pair_to, (size_t)n * 4)) != SF_OK) return rc;
   // pinned staging of the two slot lists; the previous call's copies must have left it
   if (c->pairs_staged) SF_HIP(c, hipEventSynchronize(c->pairs_staged));
   const size_t need = (size_t)n * 8;
@@ -1510,11 +1466,11 @@ extern "C" int sf_verify_matches_device(sf_handle c, const sf_match* matches, in
     if (hf[i] < 0 || hf[i] >= c->store.slots || ht[i] < 0 || ht[i] >= c->store.slots)
       return sf_fail(c, SF_ERANGE, "match %d: slot (%d,%d) outside the store (%d slots)", i, hf[i], ht[i], c->store.slots);
   }
-  SF_HIP(c, hipMemcpyAsync(c->pair_from.p, hf, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  SF_HIP(c, hipMemcpyAsync(c->pair_to.p, ht, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipMemcpyAsync(c->w->pair_from.p, hf, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipMemcpyAsync(c->w->pair_to.p, ht, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   if (!c->pairs_staged) SF_HIP(c, hipEventCreateWithFlags(&c->pairs_staged, hipEventDisableTiming));
   SF_HIP(c, hipEventRecord(c->pairs_staged, c->stream));
-  return verify_device(c, c->store, (const int32_t*)c->pair_from.p, (const int32_t*)c->pair_to.p, n, d_out);
+  return verify_device(c, c->store, (const int32_t*)c->w->pair_from.p, (const int32_t*)c->w->pair_to.p, n, d_out);
 }
 
 // Called by the NN filter behind the refinement launch of a prefix level (k_nn.hip): candidate pair list on
@@ -1557,15 +1513,15 @@ int sf_spec_launch(sf_context* c, const void* d_cand, const unsigned* d_count) {
   } else {
     hipLaunchKernelGGL(k_spec_pairs, dim3((grid + 255) / 256), dim3(256), 0, c->stream, (const uint2*)d_cand, d_count, grid,
                        c->nn_local.n, c->nn_recv.n, c->spec.slot_other, c->spec.slot_local, c->store.slots,
-                       (int32_t*)c->spec_from.p, (int32_t*)c->spec_to.p);
+                       (int32_t*)c->w->spec_from.p, (int32_t*)c->w->spec_to.p);
     SF_HIP(c, hipGetLastError());
   }
   // (one chunk, one stream: a pair's index is its slot in the list -- the fused kernel, the 3D-3D chain kernel of the
   //  split form and the PnP estimator's chain kernel stream their accepted results)
   if (plan.streams()) rc = arm_accept_stream(c, d_count);
   if (rc == SF_OK)
-    rc = verify_device(c, c->store, (const int32_t*)c->spec_from.p, (const int32_t*)c->spec_to.p, (int)grid,
-                       (sf_result*)c->spec_results.p, &plan);
+    rc = verify_device(c, c->store, (const int32_t*)c->w->spec_from.p, (const int32_t*)c->w->spec_to.p, (int)grid,
+                       (sf_result*)c->w->spec_results.p, &plan);
   c->dparams.accept_on = 0;
   c->pair_src = PairSource();
   return rc;
@@ -1610,9 +1566,9 @@ extern "C" int sf_find_matches_and_verify_device(sf_handle c, int32_t slot_base_
       SF_HIP(c, hipEventCreateWithFlags(&c->spec_index_staged, hipEventDisableTiming));
     }
     c->spec.grid = (unsigned)(n_l + n_l / 8 + 256);       // room for rows with more than one candidate
-    if ((rc = sf_buf_reserve(c, c->spec_from, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->spec_to, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->spec_results, (size_t)c->spec.grid * sizeof(sf_result))) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->w->spec_from, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->w->spec_to, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->w->spec_results, (size_t)c->spec.grid * sizeof(sf_result))) != SF_OK) return rc;
     c->spec.slot_other = slot_base_other;
     c->spec.slot_local = slot_base_local;
   }
@@ -1630,8 +1586,8 @@ extern "C" int sf_find_matches_and_verify_device(sf_handle c, int32_t slot_base_
     //  accepted-result block is not this query's answer: streamed = 0, the block's owner resets it)
     c->accept_streamed = false;
     if (!d_out) {       // the caller only wants sf_last_match_results: an internal block takes the results
-      if ((rc = sf_buf_reserve(c, c->results, (size_t)n * sizeof(sf_result))) != SF_OK) return rc;
-      d_out = (sf_result*)c->results.p;
+      if ((rc = sf_buf_reserve(c, c->w->results, (size_t)n * sizeof(sf_result))) != SF_OK) return rc;
+      d_out = (sf_result*)c->w->results.p;
     }
     if ((rc = sf_verify_matches_device(c, out, n, slot_base_other, slot_base_local, d_out)) != SF_OK) return rc;
     c->last_results = d_out; c->last_results_index = nullptr; c->last_results_n = n;
@@ -1662,11 +1618,11 @@ extern "C" int sf_find_matches_and_verify_device(sf_handle c, int32_t slot_base_
   // The gather reads the index list straight from the pinned host block (40 KB over PCIe inside the kernel): an
   // H2D copy queued on the handle's stream would run AFTER the verification it sits behind -- ~15 us of copy
   // engine latency on the step's critical path for nothing.
-  c->last_results = (const sf_result*)c->spec_results.p; c->last_results_index = hi; c->last_results_n = n;
+  c->last_results = (const sf_result*)c->w->spec_results.p; c->last_results_index = hi; c->last_results_n = n;
   if (!d_out) return SF_OK;       // no gathered copy wanted: sf_last_match_results + an indexed consumer
   constexpr int PIECES = sizeof(sf_result) / 16;
   hipLaunchKernelGGL(k_spec_gather, dim3(((size_t)n * PIECES + 255) / 256), dim3(256), 0, c->stream,
-                     (const sf_result*)c->spec_results.p, (const int32_t*)hi, n, d_out);
+                     (const sf_result*)c->w->spec_results.p, (const int32_t*)hi, n, d_out);
   SF_HIP(c, hipGetLastError());
   SF_HIP(c, hipEventRecord(c->spec_index_staged, c->stream));   // the block may be rewritten after this
   return SF_OK;
@@ -1770,26 +1726,26 @@ static int compact_launch(sf_context* c, const sf_result* d_results, int n, sf_r
                           uint8_t* d_flags2 = nullptr, int32_t* d_count2 = nullptr, int cap2 = 0x7FFFFFFF) {
   const int chunks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
   int rc;
-  if ((rc = sf_buf_reserve(c, c->compact_scratch, (size_t)(chunks + 2) * 8)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->compact_scratch, (size_t)(chunks + 2) * 8)) != SF_OK) return rc;
   if (chunks <= COMPACT_MAX_CHUNKS) {
-    if (c->compact_state_chunks != chunks || c->compact_state_ptr != c->compact_scratch.p) {
+    if (c->w->compact_state_chunks != chunks || c->w->compact_state_ptr != c->w->compact_scratch.p) {
       // fresh (or regrown / reallocated) state, or another chunk count (the arrival word sits behind the chunks' words):
       // make every epoch tag invalid and the arrival word zero once
-      SF_HIP(c, hipMemsetAsync(c->compact_scratch.p, 0, (size_t)(chunks + 2) * 8, c->stream));
-      c->compact_state_chunks = chunks;
-      c->compact_state_ptr = c->compact_scratch.p;
+      SF_HIP(c, hipMemsetAsync(c->w->compact_scratch.p, 0, (size_t)(chunks + 2) * 8, c->stream));
+      c->w->compact_state_chunks = chunks;
+      c->w->compact_state_ptr = c->w->compact_scratch.p;
     }
-    if (++c->compact_epoch == 0) c->compact_epoch = 1;
+    if (++c->w->compact_epoch == 0) c->w->compact_epoch = 1;
     hipLaunchKernelGGL(k_compact_chain, dim3(chunks), dim3(COMPACT_CHUNK), 0, c->stream, d_results, index, n, d_accepted, d_flags,
-                       (unsigned long long*)c->compact_scratch.p, c->compact_epoch, d_count, d_accepted2, d_flags2, d_count2, cap2);
+                       (unsigned long long*)c->w->compact_scratch.p, c->w->compact_epoch, d_count, d_accepted2, d_flags2, d_count2, cap2);
     SF_HIP(c, hipGetLastError());
     if (index && index == (const int32_t*)c->spec_index_pinned)
       SF_HIP(c, hipEventRecord(c->spec_index_staged, c->stream));   // the pinned index block may be rewritten after this
     return SF_OK;
   }
   if (index || d_accepted2) return sf_fail(c, SF_ERANGE, "indexed / mirrored compaction of %d records: more than %d chunks", n, COMPACT_MAX_CHUNKS);
-  c->compact_state_chunks = 0;                  // (the two-kernel form reuses the buffer as plain counts)
-  int32_t* d_chunk = (int32_t*)c->compact_scratch.p;
+  c->w->compact_state_chunks = 0;                  // (the two-kernel form reuses the buffer as plain counts)
+  int32_t* d_chunk = (int32_t*)c->w->compact_scratch.p;
   const int chunks2 = (n + 1023) / 1024;
   hipLaunchKernelGGL(k_compact_count, dim3(chunks2), dim3(1024), 0, c->stream, d_results, n, d_flags, d_chunk);
   hipLaunchKernelGGL(k_compact_move, dim3(chunks2), dim3(1024), 0, c->stream, d_results, n, d_accepted,
@@ -1907,20 +1863,6 @@ extern "C" int sf_step_mirror(sf_handle c, sf_result* d_records2, uint32_t* d_co
 }
 
 // ---- SF_OPT_STEP_OVERLAP: the further lanes of the step pipeline ----------------------------------------------------
-static void lane_swap(sf_context* c, int k) {
-  sf_context::StepLane& L = c->lanes[k - 1];
-  std::swap(c->stream, L.stream);
-  std::swap(c->aux, L.aux); std::swap(c->ev_filter, L.ev_filter); std::swap(c->ev_walk, L.ev_walk);
-#define SF_SWAP(m) std::swap(c->m, L.m)
-  SF_SWAP(pair_from); SF_SWAP(pair_to); SF_SWAP(corr1); SF_SWAP(corr2); SF_SWAP(hdr1); SF_SWAP(hdr2); SF_SWAP(pass1);
-  SF_SWAP(pass2); SF_SWAP(pass_back); SF_SWAP(dir_mask); SF_SWAP(list1); SF_SWAP(list3); SF_SWAP(counters);
-  SF_SWAP(results); SF_SWAP(flags); SF_SWAP(nn_cand); SF_SWAP(spec_from); SF_SWAP(spec_to); SF_SWAP(spec_results);
-  SF_SWAP(spec_index); SF_SWAP(compact_scratch); SF_SWAP(step_nn); SF_SWAP(walk_scratch); SF_SWAP(ws_pairs); SF_SWAP(ws_kcap);
-  SF_SWAP(nn_count_idx); SF_SWAP(nn_count_primed); SF_SWAP(compact_epoch); SF_SWAP(compact_state_chunks);
-  SF_SWAP(compact_state_ptr);
-#undef SF_SWAP
-}
-
 // A database (or a mask) is about to change: every step in flight is settled first -- waited for, and re-run on the
 // synchronous path if its device walk asked for that -- so that no queued kernel reads what the caller is about to
 // write and a fallback still sees the state its step was issued on.  `drain` also waits for the lanes' streams.
@@ -1928,33 +1870,34 @@ int sf_lanes_touch(sf_context* c, bool drain) {
   c->db_epoch += 1;
   const int rc = step_settle_all(c);      // (a step whose fallback re-run failed: the error is the caller's to see)
   if (drain)
-    for (auto& L : c->lanes)
-      if (L.stream) SF_HIP(c, hipStreamSynchronize(L.stream));
+    for (int k = 1; k < SF_STEP_MAX_LANES; ++k)
+      if (c->ws[k].stream) SF_HIP(c, hipStreamSynchronize(c->ws[k].stream));
   return rc;
 }
 
-static int stream_with_own_queue(sf_context* c, hipStream_t* out, bool aux);
+static int stream_with_own_queue(sf_context* c, int k, hipStream_t* out, bool aux);
 
+// Lane k's stream, counters and event, created on first use
 static int lane_create(sf_context* c, int k) {
-  sf_context::StepLane& L = c->lanes[k - 1];
+  Workspace& L = c->ws[k];
   if (L.stream) return SF_OK;
-  int rc0 = stream_with_own_queue(c, &L.stream, false);
+  int rc0 = stream_with_own_queue(c, k, &L.stream, false);
   if (rc0 != SF_OK) return rc0;
   SF_HIP(c, hipEventCreateWithFlags(&L.ev_main, hipEventDisableTiming));
   return sf_buf_reserve(c, L.counters, 64);          // (the work-list counters of the stage kernels; the handle's own
 }                                                    //  are reserved at sf_create)
 
-static int lane_enter(sf_context* c, int k) {
+// Before lane k issues: the databases were written through the handle's stream since this lane last looked?  Wait for
+// that work once.
+static int lane_prepare(sf_context* c, int k) {
   int rc0 = lane_create(c, k);
   if (rc0 != SF_OK) return rc0;
-  sf_context::StepLane& L = c->lanes[k - 1];
+  Workspace& L = c->ws[k];
   if (L.seen_db_epoch != c->db_epoch) {
-    // the databases were written through the handle's stream since this lane last looked: wait for that work once
     SF_HIP(c, hipEventRecord(L.ev_main, c->stream));
     SF_HIP(c, hipStreamWaitEvent(L.stream, L.ev_main, 0));
     L.seen_db_epoch = c->db_epoch;
   }
-  lane_swap(c, k);
   return SF_OK;
 }
 
@@ -1966,11 +1909,9 @@ extern "C" int sf_step_mirror_streams(sf_handle c, void** stream_even, void** st
   SF_HIP(c, hipSetDevice(c->device));
   *stream_even = *stream_odd = (void*)c->stream;
   if (c->step_overlap && !c->overlap && c->step_lanes >= 2) {
-    c->cur_lane = 1;
     int rc = lane_create(c, 1);
-    c->cur_lane = 0;
     if (rc != SF_OK) return rc;
-    *stream_odd = (void*)c->lanes[0].stream;
+    *stream_odd = (void*)c->ws[1].stream;
     c->step_mirror_lanes = true;
   }
   return SF_OK;
@@ -2096,7 +2037,7 @@ static int place_streams(sf_context* c) {
   // measurement reads as "blocked" and is what the once-more rule below and the abandon path are for; a host that wants the
   // measurement at a quiet moment calls sf_streams_prepare (include/sf_experimental.h) when it has one.
   (void)hipStreamSynchronize(c->stream);
-  for (auto& L : c->lanes) if (L.stream) (void)hipStreamSynchronize(L.stream);
+  for (Workspace& w : c->ws) if (w.stream) (void)hipStreamSynchronize(w.stream);
   for (int i = 1; i <= NC; ++i) {
     hipLaunchKernelGGL(k_place_probe, dim3(1), dim3(64), 0, S[i], pr.d);
     (void)hipStreamSynchronize(S[i]);
@@ -2209,11 +2150,11 @@ extern "C" int sf_stream_placement(sf_handle c, char* buf, size_t n) {
   return SF_OK;
 }
 
-static int stream_with_own_queue(sf_context* c, hipStream_t* out, bool aux) {
-  // a measured place first (place_streams)
+// A stream for workspace k (a step lane): its measured place first (place_streams)
+static int stream_with_own_queue(sf_context* c, int k, hipStream_t* out, bool aux) {
   if (!c->placement.tried) (void)place_streams(c);
   if (c->placement.done) {
-    hipStream_t& slot = aux ? c->placement.aux[c->cur_lane] : c->placement.main[c->cur_lane];
+    hipStream_t& slot = aux ? c->placement.aux[k] : c->placement.main[k];
     if (slot) { *out = slot; slot = nullptr; return SF_OK; }
   }
 
@@ -2253,18 +2194,18 @@ static void step_accept_block(sf_context* c, sf_context::StepBlock& b, sf_result
 // step.  The walk's matches then name their candidate's verification slot (walk_slots); round 3 did the same with the
 // host in the middle.  A step of the reference's cadence (20 matches of 10 000 rows) would verify 500 x too much this way
 // and takes step_issue_serial.
-static int step_issue_speculative(sf_context* c, sf_context::StepBlock& b, int32_t slot_base_other, int32_t slot_base_local,
-                                  int lim) {
+static int step_issue_speculative(sf_context* c, sf_context::StepBlock& b, int lane, int32_t slot_base_other,
+                                  int32_t slot_base_local, int lim) {
   const int n_l = c->nn_local.n, n_r = c->nn_recv.n;
   int rc;
-  if (!c->aux) {
-    if ((rc = stream_with_own_queue(c, &c->aux, true)) != SF_OK) return rc;
-    SF_HIP(c, hipEventCreateWithFlags(&c->ev_filter, hipEventDisableTiming));
-    SF_HIP(c, hipEventCreateWithFlags(&c->ev_walk, hipEventDisableTiming));
+  if (!c->w->aux) {
+    if ((rc = stream_with_own_queue(c, lane, &c->w->aux, true)) != SF_OK) return rc;
+    SF_HIP(c, hipEventCreateWithFlags(&c->w->ev_filter, hipEventDisableTiming));
+    SF_HIP(c, hipEventCreateWithFlags(&c->w->ev_walk, hipEventDisableTiming));
   }
   const size_t min_b = ((size_t)n_l * 8 + 63) & ~(size_t)63, i32_b = ((size_t)n_l * 4 + 63) & ~(size_t)63;
-  if ((rc = sf_buf_reserve(c, c->step_nn, 2 * min_b + 2 * i32_b + 64)) != SF_OK) return rc;
-  char* base = (char*)c->step_nn.p;
+  if ((rc = sf_buf_reserve(c, c->w->step_nn, 2 * min_b + 2 * i32_b + 64)) != SF_OK) return rc;
+  char* base = (char*)c->w->step_nn.p;
   double* d_min = (double*)base;
   int32_t* d_arg = (int32_t*)(base + min_b);
   int32_t* d_cand = (int32_t*)(base + min_b + i32_b);
@@ -2272,14 +2213,14 @@ static int step_issue_speculative(sf_context* c, sf_context::StepBlock& b, int32
   int32_t* d_status = (int32_t*)(base + 2 * min_b + 2 * i32_b);
   NnFilterOut fo;
   if ((rc = sf_nn_filter_dev(c, &fo)) != SF_OK) return rc;
-  SF_HIP(c, hipEventRecord(c->ev_filter, c->stream));
+  SF_HIP(c, hipEventRecord(c->w->ev_filter, c->stream));
   // the step's stream: every candidate slot verified (slots past the device-side count are void)
   c->spec.grid = (unsigned)(n_l + n_l / 8 + 256);       // room for rows with more than one candidate
   c->spec.slot_other = slot_base_other;
   c->spec.slot_local = slot_base_local;
-  if ((rc = sf_buf_reserve(c, c->spec_from, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->spec_to, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->spec_results, (size_t)c->spec.grid * sizeof(sf_result))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->spec_from, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->spec_to, (size_t)c->spec.grid * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->spec_results, (size_t)c->spec.grid * sizeof(sf_result))) != SF_OK) return rc;
   sf_result* mirror_rec; uint32_t* mirror_cnt; int32_t mirror_cap;
   step_accept_block(c, b, &mirror_rec, &mirror_cnt, &mirror_cap);
   const int sel_before = c->accept_sel;
@@ -2293,20 +2234,18 @@ static int step_issue_speculative(sf_context* c, sf_context::StepBlock& b, int32
   b.pairs = (int32_t)c->spec.grid;
   if (rc != SF_OK) return rc;
   // the second stream: exact distances -> row minima (with each minimum's candidate index) -> argsort + walk
+  SF_HIP(c, hipStreamWaitEvent(c->w->aux, c->w->ev_filter, 0));
   {
-    SF_HIP(c, hipStreamWaitEvent(c->aux, c->ev_filter, 0));
-    const hipStream_t lane_stream = c->stream;
-    c->stream = c->aux;                      // (the launchers queue on, and bracket for, the handle's current stream)
+    UseWorkspace on_aux(c, *c->w, c->w->aux);   // (the launchers queue on, and bracket for, the handle's current stream)
     rc = sf_nn_minima_of_candidates_dev(c, fo, d_min, d_arg, d_status, d_cand, d_arg64, c->store.kcap >= 256);
     if (rc == SF_OK)
       rc = sf_nn_walk_dev(c, d_min, d_arg, d_status, n_l, n_r, c->params.netvlad_distance, c->params.netvlad_max_matches_nb,
                           lim, nullptr, nullptr, b.walk_matches, b.walk_n, b.walk_status, d_cand, b.walk_slots, fo.count,
                           c->spec.grid);
-    c->stream = lane_stream;
-    if (rc != SF_OK) { (void)hipStreamSynchronize(c->aux); return rc; }
-    SF_HIP(c, hipEventRecord(c->ev_walk, c->aux));
   }
-  SF_HIP(c, hipStreamWaitEvent(c->stream, c->ev_walk, 0));      // the step is done when both streams are
+  if (rc != SF_OK) { (void)hipStreamSynchronize(c->w->aux); return rc; }
+  SF_HIP(c, hipEventRecord(c->w->ev_walk, c->w->aux));
+  SF_HIP(c, hipStreamWaitEvent(c->stream, c->w->ev_walk, 0));      // the step is done when both streams are
   if (!b.streamed)      // (step_issue_device picks this form only where the launch streams: a plan / arm mismatch)
     return sf_fail(c, SF_EHIP, "speculative step: the verification launch did not arm the accepted-result stream");
   SF_HIP(c, hipEventRecord(b.done, c->stream));
@@ -2319,10 +2258,10 @@ static int step_issue_serial(sf_context* c, sf_context::StepBlock& b, int32_t sl
   const int n_l = c->nn_local.n, n_r = c->nn_recv.n;
   int rc;
   const size_t min_bytes = ((size_t)n_l * 8 + 63) & ~(size_t)63, arg_bytes = ((size_t)n_l * 4 + 63) & ~(size_t)63;
-  if ((rc = sf_buf_reserve(c, c->step_nn, min_bytes + arg_bytes + 64)) != SF_OK) return rc;
-  double* d_min = (double*)c->step_nn.p;
-  int32_t* d_arg = (int32_t*)((char*)c->step_nn.p + min_bytes);
-  int32_t* d_status = (int32_t*)((char*)c->step_nn.p + min_bytes + arg_bytes);
+  if ((rc = sf_buf_reserve(c, c->w->step_nn, min_bytes + arg_bytes + 64)) != SF_OK) return rc;
+  double* d_min = (double*)c->w->step_nn.p;
+  int32_t* d_arg = (int32_t*)((char*)c->w->step_nn.p + min_bytes);
+  int32_t* d_status = (int32_t*)((char*)c->w->step_nn.p + min_bytes + arg_bytes);
   unsigned* d_count = (unsigned*)b.dev.p;                       // {matches, -, -, -, accept slot counter, ...}
   void* d_match_rc = (char*)b.dev.p + 64;
   if ((rc = sf_nn_row_minima_dev(c, d_min, d_arg, d_status)) != SF_OK) return rc;
@@ -2332,9 +2271,9 @@ static int step_issue_serial(sf_context* c, sf_context::StepBlock& b, int32_t sl
   c->spec.grid = (unsigned)lim;
   c->spec.slot_other = slot_base_other;
   c->spec.slot_local = slot_base_local;
-  if ((rc = sf_buf_reserve(c, c->spec_from, (size_t)lim * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->spec_to, (size_t)lim * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->spec_results, (size_t)lim * sizeof(sf_result))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->spec_from, (size_t)lim * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->spec_to, (size_t)lim * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->spec_results, (size_t)lim * sizeof(sf_result))) != SF_OK) return rc;
   sf_result* mirror_rec; uint32_t* mirror_cnt; int32_t mirror_cap;
   step_accept_block(c, b, &mirror_rec, &mirror_cnt, &mirror_cap);
   const int sel_before = c->accept_sel;
@@ -2351,14 +2290,15 @@ static int step_issue_serial(sf_context* c, sf_context::StepBlock& b, int32_t sl
     // a launch shape the stream does not cover (stage kernels, more than one chunk, a mirror smaller than the query):
     // ordered compaction of the `lim` slots, match order -- the void slots past the match count carry success = 0
     if (lim > b.cap) return sf_fail(c, SF_ERANGE, "sf_step_issue: %d pair slots exceed the block's %d records", lim, b.cap);
-    if ((rc = compact_launch(c, (const sf_result*)c->spec_results.p, lim, b.records, b.flags, b.count, nullptr, mirror_rec,
+    if ((rc = compact_launch(c, (const sf_result*)c->w->spec_results.p, lim, b.records, b.flags, b.count, nullptr, mirror_rec,
                              nullptr, (int32_t*)mirror_cnt, mirror_cap)) != SF_OK) return rc;
   }
   SF_HIP(c, hipEventRecord(b.done, c->stream));
   return SF_OK;
 }
 
-static int step_issue_device(sf_context* c, sf_context::StepBlock& b, int32_t slot_base_other, int32_t slot_base_local) {
+static int step_issue_device(sf_context* c, sf_context::StepBlock& b, int lane, int32_t slot_base_other,
+                             int32_t slot_base_local) {
   const int n_l = c->nn_local.n;
   const int lim = std::min(n_l, c->params.netvlad_max_matches_nb);     // the walk looks at `lim` rows: at most `lim` matches
   b.device_walk = true;
@@ -2379,7 +2319,7 @@ static int step_issue_device(sf_context* c, sf_context::StepBlock& b, int32_t sl
     const int32_t cap = std::min(b.cap, mirror_rec ? c->step_mirror_cap : b.cap);
     if (plan.streams() && cap >= grid) {
       b.speculative = true;
-      return step_issue_speculative(c, b, slot_base_other, slot_base_local, lim);
+      return step_issue_speculative(c, b, lane, slot_base_other, slot_base_local, lim);
     }
   }
   return step_issue_serial(c, b, slot_base_other, slot_base_local, lim);
@@ -2417,27 +2357,28 @@ extern "C" int sf_step_issue(sf_handle c, int32_t slot_base_other, int32_t slot_
   b.settled = false; b.settle_rc = SF_OK;
   c->in_overlapped_step = lanes > 1;            // (sf_use_split: the form the verification takes)
   const bool device = c->step_device_walk && !c->overlap && c->store.slots > 0;
-  c->cur_lane = lane;
-  if (lane > 0 && (rc = lane_enter(c, lane)) != SF_OK) { c->in_overlapped_step = false; return rc; }
+  if (lane > 0 && (rc = lane_prepare(c, lane)) != SF_OK) { c->in_overlapped_step = false; return rc; }
+  Workspace& L = c->ws[lane];
+  UseWorkspace on(c, L);
   if (b.copy_pending) {            // (sf_memcpy_device_async out of this block's records, possibly on a stream of the caller's)
     hipError_t e = hipStreamWaitEvent(c->stream, b.copied, 0);
     if (e != hipSuccess) rc = sf_fail(c, SF_EHIP, "hipStreamWaitEvent(copy of d_records) -> %s", hipGetErrorString(e));
     b.copy_pending = false;
   }
   // state every lane reads (fp16 copies, coefficients, masks) prepared by another lane since this one last looked?
-  if (c->lane_seen_prep[lane] != c->prep_epoch && c->ev_prep) {
+  if (L.seen_prep != c->prep_epoch && c->ev_prep) {
     hipError_t e = hipStreamWaitEvent(c->stream, c->ev_prep, 0);
     if (e != hipSuccess) rc = sf_fail(c, SF_EHIP, "hipStreamWaitEvent -> %s", hipGetErrorString(e));
   }
-  c->lane_seen_prep[lane] = c->prep_epoch;
+  L.seen_prep = c->prep_epoch;
   const uint64_t prep_before = c->prep_count;
-  if (rc == SF_OK) rc = device ? step_issue_device(c, b, slot_base_other, slot_base_local)
+  if (rc == SF_OK) rc = device ? step_issue_device(c, b, lane, slot_base_other, slot_base_local)
                                : step_issue_sync(c, b, slot_base_other, slot_base_local);
   if (c->prep_count != prep_before) {
     if (!c->ev_prep) (void)hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming);
     if (c->ev_prep) (void)hipEventRecord(c->ev_prep, c->stream);
     c->prep_epoch += 1;
-    c->lane_seen_prep[lane] = c->prep_epoch;
+    L.seen_prep = c->prep_epoch;
   }
   if (rc != SF_OK) {
     // nothing of a failed issue may stay behind: whatever was queued is waited for and the block's streamed entries are
@@ -2445,7 +2386,6 @@ extern "C" int sf_step_issue(sf_handle c, int32_t slot_base_other, int32_t slot_
     (void)hipStreamSynchronize(c->stream);
     for (int32_t r = 0; r < b.cap && b.index[r] >= 0; ++r) b.index[r] = -1;
   }
-  if (lane > 0) lane_swap(c, lane);
   c->in_overlapped_step = false;
   if (rc != SF_OK) return rc;
   b.issued = true;
@@ -2610,8 +2550,8 @@ extern "C" int sf_compact_accepted_device(sf_handle c, const sf_result* d_result
   SF_HIP(c, hipSetDevice(c->device));
   const int chunks = (n + COMPACT_CHUNK - 1) / COMPACT_CHUNK;
   int rc;
-  if ((rc = sf_buf_reserve(c, c->compact_scratch, (size_t)(chunks + 2) * 8)) != SF_OK) return rc;
-  int32_t* d_count = (int32_t*)((char*)c->compact_scratch.p + (size_t)(chunks + 1) * 8);   // behind the chunk states
+  if ((rc = sf_buf_reserve(c, c->w->compact_scratch, (size_t)(chunks + 2) * 8)) != SF_OK) return rc;
+  int32_t* d_count = (int32_t*)((char*)c->w->compact_scratch.p + (size_t)(chunks + 1) * 8);   // behind the chunk states
   if ((rc = compact_launch(c, d_results, n, d_accepted, d_flags, d_count)) != SF_OK) return rc;
   if (!c->count_pinned && hipHostMalloc((void**)&c->count_pinned, 64, hipHostMallocDefault) != hipSuccess)
     return sf_fail(c, SF_ENOMEM, "hipHostMalloc(64) failed");
@@ -2629,14 +2569,14 @@ static int verify_host_indices(sf_context* c, const Store& st, const int32_t* fr
     if (from[i] < 0 || from[i] >= st.slots || to[i] < 0 || to[i] >= st.slots)
       return sf_fail(c, SF_ERANGE, "pair %d: slot (%d,%d) outside the store (%d slots)", i, from[i], to[i], st.slots);
   int rc;
-  if ((rc = sf_buf_reserve(c, c->pair_from, (size_t)n * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->pair_to, (size_t)n * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->results, (size_t)n * sizeof(sf_result))) != SF_OK) return rc;
-  SF_HIP(c, hipMemcpyAsync(c->pair_from.p, from, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  SF_HIP(c, hipMemcpyAsync(c->pair_to.p, to, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  if ((rc = verify_device(c, st, (const int32_t*)c->pair_from.p, (const int32_t*)c->pair_to.p, n,
-                          (sf_result*)c->results.p)) != SF_OK) return rc;
-  SF_HIP(c, hipMemcpyAsync(out, c->results.p, (size_t)n * sizeof(sf_result), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = sf_buf_reserve(c, c->w->pair_from, (size_t)n * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->pair_to, (size_t)n * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->w->results, (size_t)n * sizeof(sf_result))) != SF_OK) return rc;
+  SF_HIP(c, hipMemcpyAsync(c->w->pair_from.p, from, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipMemcpyAsync(c->w->pair_to.p, to, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  if ((rc = verify_device(c, st, (const int32_t*)c->w->pair_from.p, (const int32_t*)c->w->pair_to.p, n,
+                          (sf_result*)c->w->results.p)) != SF_OK) return rc;
+  SF_HIP(c, hipMemcpyAsync(out, c->w->results.p, (size_t)n * sizeof(sf_result), hipMemcpyDeviceToHost, c->stream));
   SF_HIP(c, hipStreamSynchronize(c->stream));
   return SF_OK;
 }
@@ -2676,25 +2616,32 @@ extern "C" int sf_estimate_transform(sf_handle c, const sf_features* from, const
   return sf_estimate_transform_batch(c, from, to, 1, out);
 }
 
+// The workspace pair `pair` of the last verification lives in, and its index there (the second half of a two-stream
+// batch has one of its own)
+static const Workspace& debug_workspace(const sf_context* c, int32_t* pair) {
+  if (c->ws_split > 0 && *pair >= c->ws_split) {
+    *pair -= c->ws_split;
+    return c->ws[SF_STEP_MAX_LANES];
+  }
+  return *c->w;
+}
+
 extern "C" int sf_debug_correspondences(sf_handle c, int32_t pair, int32_t pass, uint16_t* from_idx,
                                         uint16_t* to_idx, int32_t cap, int32_t* n_out) {
   if (!c || !n_out || pair < 0 || (pass != 1 && pass != 2)) return SF_EINVAL;
   SF_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->ws_split > 0 && pair >= c->ws_split) {   // second half of a two-stream batch: the shadow workspace
-    pair -= c->ws_split;
-    c = c->twin;
-  }
-  if (pair >= c->ws_pairs) return SF_EINVAL;
-  if (!c->last_lists_valid)
+  const Workspace& w = debug_workspace(c, &pair);
+  if (pair >= w.ws_pairs) return SF_EINVAL;
+  if (!w.last_lists_valid)
     return sf_fail(c, SF_EINVAL, "the fused kernel keeps correspondence lists in LDS: set SF_OPT_DEBUG_CORR (or "
                                  "SF_DEBUG_CORR=1) before the verification call");
   CorrHeader h;
-  const Buf& hb = pass == 1 ? c->hdr1 : c->hdr2;
-  const Buf& cb = pass == 1 ? c->corr1 : c->corr2;
+  const Buf& hb = pass == 1 ? w.hdr1 : w.hdr2;
+  const Buf& cb = pass == 1 ? w.corr1 : w.corr2;
   SF_HIP(c, hipMemcpy(&h, (const CorrHeader*)hb.p + pair, sizeof(h), hipMemcpyDeviceToHost));
   int n = std::min(h.n_corr, cap);
   std::vector<uint32_t> tmp(std::max(n, 1));
-  if (n > 0) SF_HIP(c, hipMemcpy(tmp.data(), (const uint32_t*)cb.p + (size_t)pair * c->ws_kcap, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (n > 0) SF_HIP(c, hipMemcpy(tmp.data(), (const uint32_t*)cb.p + (size_t)pair * w.ws_kcap, (size_t)n * 4, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; ++i) {
     if (from_idx) from_idx[i] = (uint16_t)(tmp[i] & 0xFFFFu);
     if (to_idx) to_idx[i] = (uint16_t)(tmp[i] >> 16);
@@ -2709,11 +2656,11 @@ extern "C" int sf_debug_pass_state(sf_handle c, int32_t pair, int32_t pass, floa
                                    int32_t* matches) {
   if (!c || pair < 0 || (pass != 1 && pass != 2)) return SF_EINVAL;
   SF_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->ws_split > 0 && pair >= c->ws_split) { pair -= c->ws_split; c = c->twin; }
-  if (pair >= c->ws_pairs) return SF_EINVAL;
-  if (!c->last_lists_valid) return sf_fail(c, SF_EINVAL, "set SF_OPT_DEBUG_CORR before the verification call");
+  const Workspace& w = debug_workspace(c, &pair);
+  if (pair >= w.ws_pairs) return SF_EINVAL;
+  if (!w.last_lists_valid) return sf_fail(c, SF_EINVAL, "set SF_OPT_DEBUG_CORR before the verification call");
   PassState ps;
-  SF_HIP(c, hipMemcpy(&ps, (const PassState*)(pass == 1 ? c->pass1.p : c->pass2.p) + pair, sizeof(ps), hipMemcpyDeviceToHost));
+  SF_HIP(c, hipMemcpy(&ps, (const PassState*)(pass == 1 ? w.pass1.p : w.pass2.p) + pair, sizeof(ps), hipMemcpyDeviceToHost));
   if (T12) memcpy(T12, ps.T, sizeof(ps.T));
   if (is_null) *is_null = ps.is_null;
   if (inliers) *inliers = ps.inliers;
@@ -2733,9 +2680,9 @@ extern "C" int sf_debug_counters(sf_handle c, unsigned long long* out, int32_t n
 // (experiment) per-point records of the guided pass of pair `pair` of the last verification: two planes of kcap words
 extern "C" int sf_debug_guided_points(sf_handle c, int32_t pair, unsigned long long* plane0, unsigned long long* plane1,
                                       int32_t* kcap_out) {
-  if (!c || pair < 0 || pair >= c->ws_pairs || !c->trace.p) return SF_EINVAL;
+  if (!c || pair < 0 || pair >= c->w->ws_pairs || !c->trace.p) return SF_EINVAL;
   SF_HIP(c, hipStreamSynchronize(c->stream));
-  const size_t k = (size_t)c->ws_kcap, np = (size_t)c->ws_pairs;
+  const size_t k = (size_t)c->w->ws_kcap, np = (size_t)c->w->ws_pairs;
   if (c->trace.bytes < 4096 + 2 * np * k * 8) return SF_EINVAL;
   const char* base = (const char*)c->trace.p + 4096;
   SF_HIP(c, hipMemcpy(plane0, base + ((size_t)pair * k) * 8, k * 8, hipMemcpyDeviceToHost));
@@ -2768,13 +2715,10 @@ extern "C" int sf_pack_separators(const sf_result* res, int32_t n, int8_t robot_
 }
 
 // ---- measurement ----------------------------------------------------------------------------------
-// (the launches of the second stream of a two-stream batch are booked on the shadow context and reported
-//  together with the handle's own)
 extern "C" int sf_prof_enable(sf_handle c, int on) {
   if (!c) return SF_EINVAL;
   prof_resolve(c);
   c->prof = on != 0;
-  if (c->twin) { prof_resolve(c->twin); c->twin->prof = c->prof; }
   return SF_OK;
 }
 
@@ -2782,7 +2726,6 @@ extern "C" int sf_prof_select(sf_handle c, uint32_t kernel_mask) {
   if (!c) return SF_EINVAL;
   prof_resolve(c);
   c->prof_mask = kernel_mask;
-  if (c->twin) { prof_resolve(c->twin); c->twin->prof_mask = kernel_mask; }
   return SF_OK;
 }
 
@@ -2790,25 +2733,14 @@ extern "C" int sf_prof_reset(sf_handle c) {
   if (!c) return SF_EINVAL;
   prof_resolve(c);
   for (auto& s : c->prof_slots) s = ProfSlot();
-  if (c->twin) {
-    prof_resolve(c->twin);
-    for (auto& s : c->twin->prof_slots) s = ProfSlot();
-  }
   return SF_OK;
 }
 
 extern "C" int sf_prof_get(sf_handle c, int kernel, int64_t* launches, double* total_ms) {
   if (!c || kernel < 0 || kernel >= SF_K_COUNT) return SF_EINVAL;
   prof_resolve(c);
-  int64_t n = c->prof_slots[kernel].launches;
-  double ms = c->prof_slots[kernel].total_ms;
-  if (c->twin) {
-    prof_resolve(c->twin);
-    n += c->twin->prof_slots[kernel].launches;
-    ms += c->twin->prof_slots[kernel].total_ms;
-  }
-  if (launches) *launches = n;
-  if (total_ms) *total_ms = ms;
+  if (launches) *launches = c->prof_slots[kernel].launches;
+  if (total_ms) *total_ms = c->prof_slots[kernel].total_ms;
   return SF_OK;
 }
 

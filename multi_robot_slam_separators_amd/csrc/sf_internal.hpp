@@ -147,13 +147,62 @@ struct ProfSlot {
   double total_ms = 0.0;
 };
 
+// Everything one stream of verification / NN-stage work writes or owns: the handle's own (lane 0 of the step pipeline and
+// the first half of a two-stream batch), step lanes 1..3 and the second half of a two-stream batch each have one.
+struct Workspace {
+  hipStream_t stream = nullptr;
+  hipStream_t aux = nullptr;             // speculative device step: exact re-evaluation + minima + walk beside the verification
+  hipEvent_t ev_filter = nullptr, ev_walk = nullptr;
+  hipEvent_t ev_main = nullptr;          // "the handle's stream up to here": awaited when the databases changed
+
+  // verification (sized for `ws_pairs` pairs)
+  int ws_pairs = 0, ws_kcap = 0;
+  Buf pair_from, pair_to;       // int32[n]
+  Buf corr1, corr2;             // uint32[n][kcap]
+  Buf hdr1, hdr2;               // CorrHeader[n]
+  Buf pass1, pass2;             // PassState[n]
+  Buf pass_back, dir_mask;      // Vis/ForwardEstOnly = false: the backward estimate's PassState[n], inlier masks [2][n][kcap]
+  Buf list1, list3;             // int32[n] work lists (RANSAC pass 1, RANSAC pass 2)
+  Buf counters;                 // int32[8]
+  Buf results;                  // sf_result[n]
+  Buf flags;                    // uint8[n] pass2_guided
+  bool last_lists_valid = false;   // the last verification left correspondence lists in this workspace
+
+  // NN stage and speculative verification
+  Buf nn_cand;       // filter path: two 64-byte counter blocks (alternating per launch) + candidate (row, col) pairs + exact distances
+  int nn_count_idx = 0;          // counter block of the next filter launch
+  bool nn_count_primed = false;  // ... and whether the previous k128 launch already zeroed it
+  Buf spec_from, spec_to, spec_results, spec_index;
+  Buf compact_scratch;          // per-chunk counts of sf_compact_accepted_device
+  unsigned compact_epoch = 0;   // k_compact_chain: tag of the current launch's prefix entries
+  int compact_state_chunks = 0; // ... and how many state entries have been initialised
+  void* compact_state_ptr = nullptr;
+  Buf step_nn;                  // device walk: row minima (f64) | row arg (i32) | row candidate (i32) | packed arg (u64) | status
+  Buf walk_scratch;             // device walk: tile keys / rows, sorted rows, column claims (sf_nn_walk_dev)
+
+  uint64_t seen_db_epoch = ~0ull;   // sf_context::db_epoch this lane last waited for
+  uint64_t seen_prep = 0;           // sf_context::prep_epoch this lane last waited for
+
+  // every buffer above (sf_destroy frees them from this list)
+  template <class F> void for_each_buf(F&& f) {
+    for (Buf* b : {&pair_from, &pair_to, &corr1, &corr2, &hdr1, &hdr2, &pass1, &pass2, &pass_back, &dir_mask, &list1, &list3,
+                   &counters, &results, &flags, &nn_cand, &spec_from, &spec_to, &spec_results, &spec_index, &compact_scratch,
+                   &step_nn, &walk_scratch})
+      f(*b);
+  }
+};
+
 struct sf_context {
   sf_params params;
   DeviceParams dparams;
   int device = 0;
   int n_cus = 0;            // compute units of the device (queried on first use)
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;   // the stream the launchers queue on: ws[0].stream, or another inside a UseWorkspace scope
   bool own_stream = false;
+  // [0]: the handle's own; [1 .. SF_STEP_MAX_LANES - 1]: step lanes (SF_OPT_STEP_OVERLAP); [SF_STEP_MAX_LANES]: the second
+  // half of a two-stream batch (verify_device)
+  Workspace ws[SF_STEP_MAX_LANES + 1];
+  Workspace* w = ws;              // the workspace the launchers use
   std::string err;
 
   Store store;        // persistent keyframes
@@ -172,18 +221,7 @@ struct sf_context {
   hipEvent_t nn_stage_done = nullptr;
   bool nn_stage_busy = false;
 
-  // verification workspace (sized for `ws_pairs` pairs)
-  int ws_pairs = 0, ws_kcap = 0;
-  Buf pair_from, pair_to;       // int32[n]
-  Buf corr1, corr2;             // uint32[n][kcap]
-  Buf hdr1, hdr2;               // CorrHeader[n]
-  Buf pass1, pass2;             // PassState[n]
   Buf ft_counts;                // batched feature extraction: corners per image (device)
-  Buf pass_back, dir_mask;      // Vis/ForwardEstOnly = false: the backward estimate's PassState[n], inlier masks [2][n][kcap]
-  Buf list1, list3;             // int32[n] work lists (RANSAC pass 1, RANSAC pass 2)
-  Buf counters;                 // int32[8]
-  Buf results;                  // sf_result[n]
-  Buf flags;                    // uint8[n] pass2_guided
   // feature extraction (k_extract.hip): integral image, per-corner scratch, the BRIEF test table
   Buf ex_integral, ex_desc, ex_xyz, ex_keep, ex_rows, brief_tests;
   // corner detection (k_gftt.hip): derivative-product / response planes, candidate keys (in + sorted), sort scratch,
@@ -205,9 +243,6 @@ struct sf_context {
   bool masks_dirty = true;
   Buf nn_rowmin;     // per-row packed (dist bits, idx) uint64 [n_local]
   Buf nn_exact;      // double [n_local]
-  Buf nn_cand;       // filter path: two 64-byte counter blocks (alternating per launch) + candidate (row, col) pairs + exact distances
-  int nn_count_idx = 0;          // counter block of the next filter launch
-  bool nn_count_primed = false;  // ... and whether the previous k128 launch already zeroed it
   Buf nn_scalar;     // small reduction scratch
   int nn_level = 0, nn_level_cooldown = 32, nn_last_kdims = 0;   // adaptive prefix ladder of the filter
   bool nn_force_full = false;   // SF_OPT_NN_FULL_FILTER: always contract the full descriptor length
@@ -228,7 +263,6 @@ struct sf_context {
   bool fused_attr[2][2][2] = {};   // [W == 16][matrix-core matcher][WIDE]: LDS attribute set
   bool ransac_ba_attr_set = false, pnp_ba_attr_set = false, merge_ba_attr_set = false;
   bool debug_corr = false;      // SF_OPT_DEBUG_CORR: the fused kernel also writes lists / headers / states to HBM
-  bool last_lists_valid = false;   // the last verification left correspondence lists in the global workspace
   bool fused = true;        // fused per-pair verification kernel (SF_FUSED=0 selects the stage kernels)
   int cu_count = 0;         // compute units of the device (grids sized to the chip); filled on first use
   bool gf_select_attr = false; // k_gftt_select_lds: dynamic LDS attribute set
@@ -260,7 +294,6 @@ struct sf_context {
   size_t pairs_pinned_bytes = 0;
   hipEvent_t pairs_staged = nullptr;
   int32_t* count_pinned = nullptr;
-  Buf compact_scratch;          // per-chunk counts of sf_compact_accepted_device
 
   // multi-GPU exchange (sf_comm.hip)
   void* comm = nullptr;    // ncclComm_t
@@ -269,14 +302,13 @@ struct sf_context {
   Buf comm_scratch;
 
   // Two-stream verification of large batches (sf_api.hip, verify_device): the second half of a batch runs
-  // its stage kernels on `twin` -- a shadow context with its own stream, workspace and counters that shares
-  // this handle's keyframe store and parameters -- so that the latency-bound motion-estimation kernels of
-  // one half overlap the issue-bound matching kernel of the other.  Off unless SF_OVERLAP=1 (+3-6 %).
-  sf_context* twin = nullptr;
+  // its stage kernels on ws[SF_STEP_MAX_LANES] -- a stream, workspace and counters of its own -- so that the
+  // latency-bound motion-estimation kernels of one half overlap the issue-bound matching kernel of the other.
+  // Off unless SF_OVERLAP=1 (+3-6 %).
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool overlap = false;
   int overlap_min_pairs = 4096;
-  int ws_split = 0;             // pairs [0, ws_split) of the last batch live in this workspace, the rest in twin's
+  int ws_split = 0;             // pairs [0, ws_split) of the last batch live in ws[0], the rest in ws[SF_STEP_MAX_LANES]
 
   // Speculative verification (sf_find_matches_and_verify_device): every candidate (row, column) the NN filter
   // emits is verified on the device while the host still reduces the candidates to row minima, sorts and
@@ -285,9 +317,6 @@ struct sf_context {
   const sf_result* last_results = nullptr;
   const int32_t* last_results_index = nullptr;
   int last_results_n = 0;
-  unsigned compact_epoch = 0;   // k_compact_chain: tag of the current launch's prefix entries
-  int compact_state_chunks = 0; // ... and how many state entries have been initialised
-  void* compact_state_ptr = nullptr;
   PairSource pair_src;          // candidate list the fused kernel derives its pairs from (speculative path), or empty
   struct Spec {
     bool requested = false;     // set by the entry point for the duration of one sf_nn_run
@@ -305,7 +334,6 @@ struct sf_context {
   bool accept_streamed = false;     // the last query's results are in the selected block (keyed by verified slot)
   bool accept_armed = false;        // the selected block was handed to a verification launch of the last query (it may
                                     // hold records even when the query then fell back: streamed = false)
-  Buf spec_from, spec_to, spec_results, spec_index;
   // sf_step_issue / sf_step_retire: the caller's loop body (find_separators.py:59-133) as a begin / retire pair.  A ring
   // of `step_depth + 1` blocks: up to `step_depth` steps in flight, and the block of the step retired last stays
   // untouched until the next retire.
@@ -343,24 +371,6 @@ struct sf_context {
   bool step_device_walk = true;            // SF_OPT_STEP_DEVICE_WALK: no host wait inside sf_step_issue
   uint64_t step_seq = 0;                   // steps issued so far (the next step's number)
   int step_inflight = 0;
-  // SF_OPT_STEP_OVERLAP: the steps in flight run on `step_lanes` streams -- lane k > 0 with its own copy of every device
-  // buffer a step writes (parked in `lanes[k - 1]` while another lane's step owns the handle's members of the same names,
-  // swapped in for the duration of sf_step_issue) -- so that the tail of one step's verification (its last
-  // motion-estimation chains on an emptying chip) and the NN stage of the next overlap.
-  struct StepLane {
-    hipStream_t stream = nullptr;
-    hipStream_t aux = nullptr;             // speculative device step: exact re-evaluation + minima + walk beside the verification
-    hipEvent_t ev_filter = nullptr, ev_walk = nullptr;
-    hipEvent_t ev_main = nullptr;          // "the handle's stream up to here": awaited when the databases changed
-    Buf pair_from, pair_to, corr1, corr2, hdr1, hdr2, pass1, pass2, pass_back, dir_mask, list1, list3, counters, results,
-        flags, nn_cand, spec_from, spec_to, spec_results, spec_index, compact_scratch, step_nn, walk_scratch;
-    int ws_pairs = 0, ws_kcap = 0, nn_count_idx = 0;
-    bool nn_count_primed = false;
-    unsigned compact_epoch = 0;
-    int compact_state_chunks = 0;
-    void* compact_state_ptr = nullptr;
-    uint64_t seen_db_epoch = ~0ull;
-  } lanes[SF_STEP_MAX_LANES - 1];
   // Where the pipeline's streams sit on the hardware (sf_api.hip: place_streams).  Measured once, at the first step that
   // needs a second stream: a launch that does not fit on the chip keeps the dispatcher of its queue's PIPE busy until
   // its last workgroup is placed, and every other queue of that pipe waits -- so the lanes' main streams are picked
@@ -373,18 +383,15 @@ struct sf_context {
     hipStream_t copy = nullptr;                  // the second stream of the synchronous speculative call
     char report[384] = {0};
   } placement;
-  int cur_lane = 0;                        // the lane sf_step_issue is issuing on
-  Buf step_nn;                             // device walk: row minima (f64) | row arg (i32) | row candidate (i32) | packed arg (u64) | status
-  hipStream_t aux = nullptr;               // (lane 0's; swapped with the lanes' like `stream`)
-  hipEvent_t ev_filter = nullptr, ev_walk = nullptr;
   bool step_speculate = true;              // SF_OPT_STEP_SPECULATE: batch-mode steps verify every filter candidate beside the walk
-  Buf walk_scratch;                        // device walk: tile keys / rows, sorted rows, column claims (sf_nn_walk_dev)
   // Work that prepares state ALL lanes read (fp16 copies of the databases, filter coefficients, masks) is queued by
   // whichever lane first needs it; it bumps prep_count, the issuing step records ev_prep behind it and the other lanes
-  // wait for that event once (lane_seen_prep).
+  // wait for that event once (Workspace::seen_prep).
   uint64_t prep_count = 0, prep_epoch = 0;
-  uint64_t lane_seen_prep[SF_STEP_MAX_LANES] = {0, 0, 0, 0};
   hipEvent_t ev_prep = nullptr;
+  // SF_OPT_STEP_OVERLAP: the steps in flight run on `step_lanes` streams -- lane k on ws[k], with its own stream and its
+  // own copy of every device buffer a step writes -- so that the tail of one step's verification (its last
+  // motion-estimation chains on an emptying chip) and the NN stage of the next overlap.
   bool step_overlap = true;                // the option (SF_STEP_OVERLAP=0 / sf_set_option turn it off)
   uint64_t db_epoch = 0;                   // bumped by every call that writes a database through the handle's stream
   sf_result* step_mirror_records[2] = {nullptr, nullptr};   // sf_step_mirror[_pair]: second (device) destination of every
@@ -402,6 +409,19 @@ struct sf_context {
   std::vector<hipEvent_t> prof_event_pool;   // timing events are reused, not created per launch
   ProfSlot prof_slots[SF_K_COUNT];
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending_events;
+};
+
+// Points the launchers at workspace `ws` and queues them on `stream` (by default the workspace's own) until the scope
+// ends; a stream-only scope names the workspace already in use and another of its streams.
+struct UseWorkspace {
+  sf_context* c;
+  Workspace* w;          // what the scope restores
+  hipStream_t stream;
+  UseWorkspace(sf_context* c_, Workspace& ws, hipStream_t s) : c(c_), w(c_->w), stream(c_->stream) { c->w = &ws; c->stream = s; }
+  UseWorkspace(sf_context* c_, Workspace& ws) : UseWorkspace(c_, ws, ws.stream) {}
+  ~UseWorkspace() { c->w = w; c->stream = stream; }
+  UseWorkspace(const UseWorkspace&) = delete;
+  UseWorkspace& operator=(const UseWorkspace&) = delete;
 };
 
 // ---- helpers implemented in sf_api.hip ---------------------------------------------------------

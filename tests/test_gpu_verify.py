@@ -580,8 +580,9 @@ def test_matrix_core_matcher_equals_valu_matcher(monkeypatch, fused):
 @pytest.mark.parametrize("est", [0, 1])
 def test_two_stream_batches_equal_single_stream(monkeypatch, est):
     """SF_OVERLAP=1 cuts a batch in two halves that run the stage kernels on two streams (the second on a
-    shadow workspace): results and correspondences (both halves, through sf_debug_correspondences) must be
-    identical to the single-stream path, also across repeated calls and odd batch sizes."""
+    workspace of its own): results and correspondences (both halves, through sf_debug_correspondences) must be
+    identical to the single-stream path, also across repeated calls and odd batch sizes.  The handle frees the
+    second half's workspace with its own: create -> batch -> destroy cycles give the device memory back."""
     from multi_robot_slam_separators_amd import lib
     A, B, is_true, _ = synth.make_pairs(731, 37, k=300, cols=32, true_frac=0.5)
     p = synth.camera_params()
@@ -608,6 +609,55 @@ def test_two_stream_batches_equal_single_stream(monkeypatch, est):
     for c2, c1 in zip(out["two"][1], out["single"][1]):
         assert np.array_equal(c2[0], c1[0]) and np.array_equal(c2[1], c1[1])
     assert out["single"][0][0]["success"][is_true].all()
+
+    # Vis/ForwardEstOnly = false: the second half's RANSAC / PnP launches reserve dir_mask ([2][pairs][K] bytes) and
+    # pass_back (a PassState per pair) in its workspace -- 4 MiB + 320 KiB for a half of 4096 pairs at K = 512
+    import torch
+    monkeypatch.setenv("SF_OVERLAP", "1")
+    p.forward_est_only = 0
+    A, B, _, _ = synth.make_pairs(733, 16, k=512, cols=32, true_frac=0.5)
+    n = 8192
+    one_cycle = 2 * (n // 2) * 512
+
+    def cycle():
+        with lib.SeparatorFinder(p) as f:
+            sa = np.array([f.store_add_keyframe(a) for a in A], np.int32)
+            sb = np.array([f.store_add_keyframe(b) for b in B], np.int32)
+            res = f.verify_pairs(sa[np.arange(n) % len(A)], sb[np.arange(n) % len(B)])
+        torch.cuda.synchronize()
+        return res
+    # (mem_get_info reads the whole device's free memory: the two reads bracket nothing but this process's cycles)
+    res = cycle()                                           # (the runtime's own first-use allocations)
+    assert res["success"].any()
+    free_before = torch.cuda.mem_get_info()[0]
+    for _ in range(3):
+        cycle()
+    free_after = torch.cuda.mem_get_info()[0]
+    assert free_before - free_after < one_cycle // 4, (free_before - free_after, one_cycle)
+
+
+def test_synchronize_waits_for_the_null_stream():
+    """sf_set_stream(0) (torch's default stream) then sf_synchronize: the call returns only once the work queued on the
+    handle's stream has finished."""
+    import torch
+    from multi_robot_slam_separators_amd import lib
+    A, B, _, _ = synth.make_pairs(735, 16, k=512, cols=32, true_frac=0.5)
+    p = synth.camera_params()
+    n = 8192
+    with lib.SeparatorFinder(p) as f:
+        sa = np.array([f.store_add_keyframe(a) for a in A], np.int32)
+        sb = np.array([f.store_add_keyframe(b) for b in B], np.int32)
+        f.set_stream(0)
+        d_from = torch.from_numpy(sa[np.arange(n) % len(A)]).cuda()
+        d_to = torch.from_numpy(sb[np.arange(n) % len(B)]).cuda()
+        d_out = torch.zeros((n, _abi.RESULT_DTYPE.itemsize), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        for _ in range(3):
+            f.verify_pairs_device(d_from.data_ptr(), d_to.data_ptr(), n, d_out.data_ptr())
+        f.synchronize()
+        assert torch.cuda.default_stream().query()
+        res = d_out.cpu().numpy().view(_abi.RESULT_DTYPE).reshape(n)
+        assert res["success"].any()
 
 
 @pytest.mark.parametrize("est", [0, 1])
