@@ -59,7 +59,9 @@ extern "C" {
       own; sf_step_issue refuses more steps in flight than a mirror has buffers for.                                */
 /* 7: sf_params.reserved0 became guess_match_to_projection (same offset, same size); SF_K_GUIDED_TP added to the kernel
       ids of sf_prof_get (SF_K_COUNT 11 -> 12).                                                                     */
-#define SF_ABI_VERSION 7
+/* 8: sf_orb_params, sf_orb_defaults, sf_set_feature_type, sf_get_feature_type, sf_orb_set_pattern, sf_orb_get_pattern
+      added (GFTT/ORB descriptors, Vis/FeatureType 8), nothing existing changed.                                      */
+#define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
 enum {
@@ -309,6 +311,31 @@ typedef struct sf_stereo_camera {
    install OpenCV's generated_<bytes>.i values here for descriptors identical to the reference build's.       */
 int  sf_brief_set_pattern(sf_handle h, const int8_t* tests, int32_t bytes);
 int  sf_brief_get_pattern(sf_handle h, int8_t* tests, int32_t cap_bytes, int32_t* bytes);
+/* Vis/FeatureType of the three extraction calls (sf_extract_keyframe_device, sf_get_features_and_descriptor,
+   sf_get_features_and_descriptor_batch_device).  6 = GFTT/BRIEF (a fresh handle; the BRIEF table above), 8 = GFTT/ORB:
+   cv::ORB::compute on the given corners with rtabmap's ORB/ parameters, 32-byte rows -- one pyramid level, the 7 x 7
+   sigma 2 blur in OpenCV's 8-bit fixed point, the pattern rotated by each keypoint's own angle (-1 degree for GFTT
+   corners), the border filter KeyPointsFilter::runByImageBorder(ORB/EdgeThreshold) on cvRound(pt).  Corners whose
+   octave & 255 is not 0 are dropped like border corners (multi-level pyramids are not built).  orb NULL = defaults.
+   Any other feature_type or parameter, and 8 on a handle with desc_type 1, return SF_EINVAL.                        */
+typedef struct sf_orb_params {
+  int32_t edge_threshold; /* ORB/EdgeThreshold, 19; 1 .. 64                                                         */
+  int32_t patch_size;     /* ORB/PatchSize, 31 (only value accepted)                                                */
+  int32_t wta_k;          /* ORB/WTA_K, 2 (only value accepted): 32-byte rows                                       */
+  int32_t orientation;    /* 0 = the keypoint's own angle (rtabmap GFTT/ORB; GFTT gives -1);
+                             1 = ORB's intensity-centroid angle on the unblurred image (radius-15 patch, fastAtan2),
+                             written back into the keypoint of the wire copies; needs edge_threshold >= 16.  Not
+                             rtabmap's GFTT/ORB: rows that do not change with an in-plane rotation of the image      */
+} sf_orb_params;
+void sf_orb_defaults(sf_orb_params* p);
+int  sf_set_feature_type(sf_handle h, int32_t feature_type, const sf_orb_params* orb);   /* 6 or 8 */
+int  sf_get_feature_type(sf_handle h, int32_t* feature_type, sf_orb_params* orb);       /* orb may be NULL */
+/* ORB test locations: [8 * bytes][4] int8 {x1, y1, x2, y2}, each within +-15 (the 31 px patch); bytes = 32.  Bit k of
+   byte i is I(x1, y1) < I(x2, y2) of test 8 i + k, LSB first.  A fresh handle holds OpenCV's makeRandomPattern(31, 512)
+   set (cv::RNG(0x34985739)) -- NOT OpenCV's bit_pattern_31_ table, which ORB uses: install that table here for
+   descriptors identical to a reference build's.  Out-of-range coordinates or another size return SF_EINVAL.        */
+int  sf_orb_set_pattern(sf_handle h, const int8_t* tests, int32_t bytes);
+int  sf_orb_get_pattern(sf_handle h, int8_t* tests, int32_t cap_bytes, int32_t* bytes);
 /* ---- NetVLAD descriptor inference --------------------------------- */
 /* replaces: DataHandler.compute_descriptors (data_handler.py:143-164): `self.sess.run(self.net_out, ...)` of
    `nets.vgg16NetvladPca` (data_handler.py:63; netvlad_tf_open: VGG16 trunk to conv5_3, NetVLAD layer, WPCA), keeping
@@ -396,8 +423,8 @@ int  sf_extract_keyframe_device(sf_handle h, const uint8_t* d_left, int32_t widt
    pair.  left / right: rectified MONO8 images in host memory (what cv_bridge::toCvCopy returns at :104-105), `pitch`
    bytes per row.  det NULL = rtabmap's defaults (Vis/MaxFeatures 1000, GFTT/QualityLevel 0.001, GFTT/MinDistance 3),
    flow NULL = its Stereo/ defaults.  Outputs in host memory, sized for cap_rows rows (any may be NULL): desc_out
-   [rows][bytes of the BRIEF table], xyz_out [rows][3], kpts_out [rows]; *rows_out = features of the keyframe (may
-   exceed cap_rows: only cap_rows are copied); *slot_out (optional) = its slot in the device-resident store, what
+   [rows][bytes of the active feature type: the BRIEF table's, 32 for ORB], xyz_out [rows][3], kpts_out [rows];
+   *rows_out = features of the keyframe (may exceed cap_rows: only cap_rows are copied); *slot_out (optional) = its slot in the device-resident store, what
    sf_verify_pairs refers to later.  Synchronous.                                                              */
 typedef struct sf_detector_params {
   int32_t max_features;      /* 1 .. 32767 (KeyPointVec.size is an int16) */

@@ -133,6 +133,23 @@ def detector_params(max_features=1000, quality_level=0.001, min_distance=3.0):
     return p
 
 
+class OrbParams(C.Structure):
+    """sf_orb_params (include/sepfinder.h): rtabmap's ORB/ parameters of the GFTT/ORB extraction (Vis/FeatureType 8)."""
+    _fields_ = [("edge_threshold", C.c_int32), ("patch_size", C.c_int32), ("wta_k", C.c_int32), ("orientation", C.c_int32)]
+
+
+def orb_params(edge_threshold=19, patch_size=31, wta_k=2, orientation=0):
+    """ORB/EdgeThreshold, ORB/PatchSize, ORB/WTA_K defaults (what sf_orb_defaults fills); orientation 1 = ORB's
+    intensity-centroid angle instead of the keypoint's own."""
+    p = OrbParams()
+    p.edge_threshold, p.patch_size, p.wta_k, p.orientation = edge_threshold, patch_size, wta_k, orientation
+    return p
+
+
+FEATURE_GFTT_BRIEF = 6   # Vis/FeatureType values of sf_set_feature_type
+FEATURE_GFTT_ORB = 8
+
+
 class NetvladWeights(C.Structure):
     """sf_netvlad_weights (include/sepfinder.h): host pointers to the NetVLAD network's weights, TensorFlow layouts."""
     _fields_ = [
@@ -223,7 +240,7 @@ class StepResult(C.Structure):
                 ("d_records", C.c_void_p)]
 
 
-SF_ABI_VERSION = 7      # include/sepfinder.h
+SF_ABI_VERSION = 8      # include/sepfinder.h
 
 
 def default_params() -> Params:

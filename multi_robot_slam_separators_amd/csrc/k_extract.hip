@@ -11,6 +11,9 @@
 // Arithmetic: the float operations in the order written, no contraction (this file is compiled with
 // -ffp-contract=off), IEEE division -- the outputs are compared byte for byte.
 //
+// GFTT/ORB (Vis/FeatureType 8) replaces the integral image and the BRIEF tests by k_orb_blur / k_orb_angle /
+// k_orb_points below (cv::ORB::compute on the given keypoints); the 3D points and the commit are shared.
+//
 // Kernels (one keyframe = a few hundred to a few thousand corners of one 752 x 480 .. 1280 x 720 image):
 //   k_integral_rows   one workgroup per image row: wavefront scans of 256-pixel segments, running carry
 //   k_integral_cols   one thread per column: the running column sum (coalesced across the row)
@@ -124,6 +127,36 @@ struct ExtractCam {
   int identity_local, filter;
 };
 
+// Byte 0's thread of a corner: the 3D point of the stereo pair (NaN when there is none) and the keep flag -- shared by
+// the BRIEF and the ORB descriptor kernels
+__device__ __forceinline__ void extract_point(const sf_keypoint& k, int i, bool inside, const float* __restrict__ right_x,
+                                              const uint8_t* __restrict__ status, const ExtractCam& cam,
+                                              float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep) {
+  const float qnan = __int_as_float(0x7FC00000);
+  float p0 = qnan, p1 = qnan, p2 = qnan;
+  if (inside && right_x && (!status || status[i])) {
+    const float disparity = k.x - right_x[i];
+    if (disparity != 0.0f && disparity > 0.0f && cam.baseline > 0.0f && cam.fx > 0.0f) {
+      float c = 0.0f;
+      if (cam.cx_right > 0.0f && cam.cx > 0.0f) c = cam.cx_right - cam.cx;
+      const float W = cam.baseline / (disparity + c);
+      const float x = (k.x - cam.cx) * W, y = (k.y - cam.cy) * W, z = cam.fx * W;
+      if (isfinite(x) && isfinite(y) && isfinite(z) && (cam.min_depth < 0.0f || z > cam.min_depth) &&
+          (cam.max_depth <= 0.0f || z <= cam.max_depth)) {
+        if (cam.identity_local) {
+          p0 = x; p1 = y; p2 = z;
+        } else {
+          p0 = ((cam.L[0] * x + cam.L[1] * y) + cam.L[2] * z) + cam.L[3];
+          p1 = ((cam.L[4] * x + cam.L[5] * y) + cam.L[6] * z) + cam.L[7];
+          p2 = ((cam.L[8] * x + cam.L[9] * y) + cam.L[10] * z) + cam.L[11];
+        }
+      }
+    }
+  }
+  xyz_tmp[3 * i] = p0; xyz_tmp[3 * i + 1] = p1; xyz_tmp[3 * i + 2] = p2;
+  keep[i] = (uint8_t)(inside && (!cam.filter || (isfinite(p0) && isfinite(p1) && isfinite(p2))));
+}
+
 // one thread per (corner, descriptor byte)
 __global__ void __launch_bounds__(256)
 k_extract_points(const int32_t* __restrict__ S, int w, int h, const sf_keypoint* __restrict__ kpts,
@@ -156,29 +189,173 @@ k_extract_points(const int32_t* __restrict__ S, int w, int h, const sf_keypoint*
     desc_tmp[(size_t)i * bytes + b] = (uint8_t)v;
   }
   if (b != 0) return;
-  const float qnan = __int_as_float(0x7FC00000);
-  float p0 = qnan, p1 = qnan, p2 = qnan;
-  if (inside && right_x && (!status || status[i])) {
-    const float disparity = k.x - right_x[i];
-    if (disparity != 0.0f && disparity > 0.0f && cam.baseline > 0.0f && cam.fx > 0.0f) {
-      float c = 0.0f;
-      if (cam.cx_right > 0.0f && cam.cx > 0.0f) c = cam.cx_right - cam.cx;
-      const float W = cam.baseline / (disparity + c);
-      const float x = (k.x - cam.cx) * W, y = (k.y - cam.cy) * W, z = cam.fx * W;
-      if (isfinite(x) && isfinite(y) && isfinite(z) && (cam.min_depth < 0.0f || z > cam.min_depth) &&
-          (cam.max_depth <= 0.0f || z <= cam.max_depth)) {
-        if (cam.identity_local) {
-          p0 = x; p1 = y; p2 = z;
-        } else {
-          p0 = ((cam.L[0] * x + cam.L[1] * y) + cam.L[2] * z) + cam.L[3];
-          p1 = ((cam.L[4] * x + cam.L[5] * y) + cam.L[6] * z) + cam.L[7];
-          p2 = ((cam.L[8] * x + cam.L[9] * y) + cam.L[10] * z) + cam.L[11];
-        }
+  extract_point(k, i, inside, right_x, status, cam, xyz_tmp, keep);
+}
+
+// ---- GFTT/ORB descriptors (Vis/FeatureType 8): cv::ORB::compute on provided keypoints, one pyramid level ----------
+// DESIGN.md section 4 restates the arithmetic; tests/orb_ref.py is the NumPy restatement the tests compare with.
+//   k_orb_blur    one workgroup per band of ORB_BLUR_ROWS rows (blockIdx.y = image): the 7 x 7, sigma 2 Gaussian of
+//                 the level-0 image in OpenCV's 8-bit fixed point (row pass into an LDS tile with a 3-row halo,
+//                 column pass to u8), reflect-101 beyond the image
+//   k_orb_angle   (orientation = 1 only) one wavefront per corner: ORB's intensity-centroid angle on the unblurred
+//                 image, lanes 0..30 one patch row each, moments reduced with shuffles, lane 0 writes the keypoint
+//   k_orb_points  one thread per (corner, descriptor byte): border / octave test, 16 rotated samples; byte 0's thread
+//                 also does the 3D point (extract_point)
+// k_extract_commit then compacts the kept corners exactly as for BRIEF (32-byte rows).
+constexpr int ORB_HALF = 15;           // PatchSize 31 / 2
+constexpr int ORB_BYTES = 32;          // WTA_K 2
+constexpr int ORB_BLUR_ROWS = 8;
+
+struct OrbTaps { int t[7]; };          // getGaussianKernel(7, 2) * 256, rounded (host: orb_blur_taps)
+struct OrbUmax { int u[ORB_HALF + 1]; };   // the circular patch's half widths (host: orb_umax)
+
+// cv::borderInterpolate(p, len, BORDER_REFLECT_101)
+__device__ __forceinline__ int reflect101(int p, int len) {
+  if (len == 1) return 0;
+  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
+  return p;
+}
+
+// KeyPointsFilter::runByImageBorder(kpts, size, e): Rect(e, e, w - 2e, h - 2e).contains(Point(cvRound(pt))), and
+// nothing survives when w <= 2e or h <= 2e; corners of another octave than 0 are dropped as well
+__device__ __forceinline__ bool orb_inside(const sf_keypoint& k, int w, int h, int e) {
+  if (w <= 2 * e || h <= 2 * e || (k.octave & 255) != 0) return false;
+  const float rx = rintf(k.x), ry = rintf(k.y);
+  return rx >= (float)e && rx < (float)(w - e) && ry >= (float)e && ry < (float)(h - e);
+}
+
+// cv::fastAtan2 (OpenCV 3.x): degrees, float
+__device__ __forceinline__ float orb_fast_atan2(float y, float x) {
+  constexpr float deg = (float)(180.0 / 3.14159265358979323846);
+  constexpr float p1 = 0.9997878412794807f * deg, p3 = -0.3258083974640975f * deg, p5 = 0.1555786518463281f * deg,
+                  p7 = -0.04432655554792128f * deg;
+  constexpr float eps = (float)2.220446049250313080847263336181640625e-16;   // (float)DBL_EPSILON
+  const float ax = fabsf(x), ay = fabsf(y);
+  float a;
+  if (ax >= ay) {
+    const float c = ay / (ax + eps), c2 = c * c;
+    a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+  } else {
+    const float c = ax / (ay + eps), c2 = c * c;
+    a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+  }
+  if (x < 0) a = 180.f - a;
+  if (y < 0) a = 360.f - a;
+  return a;
+}
+
+// blur: W x H per image, B.s_stride bytes apart
+__global__ void __launch_bounds__(256)
+k_orb_blur(const uint8_t* __restrict__ img, int w, int h, int pitch, uint8_t* __restrict__ blur, OrbTaps T, ExtractBatch B) {
+  __shared__ int rows[ORB_BLUR_ROWS + 6][256];
+  img += blockIdx.y * B.img_stride;
+  blur += blockIdx.y * B.s_stride;
+  const int y0 = blockIdx.x * ORB_BLUR_ROWS, tid = threadIdx.x;
+  for (int x0 = 0; x0 < w; x0 += 256) {
+    const int x = x0 + tid;
+    if (x < w) {
+      int xs[7];
+#pragma unroll
+      for (int d = 0; d < 7; ++d) xs[d] = reflect101(x + d - 3, w);
+      for (int r = 0; r < ORB_BLUR_ROWS + 6; ++r) {
+        const uint8_t* src = img + (size_t)reflect101(y0 + r - 3, h) * pitch;
+        int s = 0;
+#pragma unroll
+        for (int d = 0; d < 7; ++d) s += T.t[d] * (int)src[xs[d]];
+        rows[r][tid] = s;
       }
     }
+    __syncthreads();
+    if (x < w) {
+      for (int r = 0; r < ORB_BLUR_ROWS && y0 + r < h; ++r) {
+        int s = 0;
+#pragma unroll
+        for (int d = 0; d < 7; ++d) s += T.t[d] * rows[r + d][tid];
+        blur[(size_t)(y0 + r) * w + x] = (uint8_t)min((s + (1 << 15)) >> 16, 255);
+      }
+    }
+    __syncthreads();
   }
-  xyz_tmp[3 * i] = p0; xyz_tmp[3 * i + 1] = p1; xyz_tmp[3 * i + 2] = p2;
-  keep[i] = (uint8_t)(inside && (!cam.filter || (isfinite(p0) && isfinite(p1) && isfinite(p2))));
+}
+
+// one wavefront per corner; every corner's keypoint goes to kpts_out, the kept ones with their angle
+__global__ void __launch_bounds__(256)
+k_orb_angle(const uint8_t* __restrict__ img, int w, int h, int pitch, const sf_keypoint* __restrict__ kpts, int n, int edge,
+            OrbUmax U, sf_keypoint* __restrict__ kpts_out, ExtractBatch B) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (B.d_n) n = min(n, B.d_n[blockIdx.y]);
+  if (i >= n) return;
+  img += blockIdx.y * B.img_stride;
+  kpts += (size_t)blockIdx.y * B.per_image;
+  kpts_out += (size_t)blockIdx.y * B.per_image;
+  sf_keypoint k = kpts[i];
+  const bool inside = orb_inside(k, w, h, edge);
+  int m01 = 0, m10 = 0;
+  if (inside && lane <= 2 * ORB_HALF) {       // edge >= 16: the whole patch lies in the image
+    const int v = lane - ORB_HALF, d = U.u[v < 0 ? -v : v];
+    const uint8_t* row = img + (size_t)((int)rintf(k.y) + v) * pitch + (int)rintf(k.x);
+    int s = 0;
+    for (int u = -d; u <= d; ++u) {
+      const int val = row[u];
+      s += val;
+      m10 += u * val;
+    }
+    m01 = v * s;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    m01 += __shfl_xor(m01, off);
+    m10 += __shfl_xor(m10, off);
+  }
+  if (lane == 0) {
+    if (inside) k.angle = orb_fast_atan2((float)m01, (float)m10);
+    kpts_out[i] = k;
+  }
+}
+
+// one thread per (corner, descriptor byte); samples inside the image read the blurred copy, the others the
+// reflect-101 padding of the source, which ORB never blurs
+__global__ void __launch_bounds__(256)
+k_orb_points(const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, int w, int h, int pitch,
+             const sf_keypoint* __restrict__ kpts, const float* __restrict__ right_x, const uint8_t* __restrict__ status,
+             int n, int edge, const int8_t* __restrict__ tests, ExtractCam cam, uint8_t* __restrict__ desc_tmp,
+             float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep, ExtractBatch B) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  const int i = g / ORB_BYTES, b = g - i * ORB_BYTES;
+  if (B.d_n) n = min(n, B.d_n[blockIdx.y]);
+  if (i >= n) return;
+  {
+    const size_t o = (size_t)blockIdx.y * B.per_image;
+    img += blockIdx.y * B.img_stride;
+    blur += blockIdx.y * B.s_stride;
+    kpts += o;
+    if (right_x) right_x += o;
+    if (status) status += o;
+    desc_tmp += o * ORB_BYTES; xyz_tmp += 3 * o; keep += o;
+  }
+  const sf_keypoint k = kpts[i];
+  const bool inside = orb_inside(k, w, h, edge);
+  if (inside) {
+    const int cx = (int)rintf(k.x), cy = (int)rintf(k.y);
+    const float ang = k.angle * (float)(3.14159265358979323846 / 180.0);
+    const float ca = (float)cos((double)ang), sa = (float)sin((double)ang);
+    auto sample = [&](int px, int py) -> int {
+      const int ix = (int)rintf((float)px * ca - (float)py * sa), iy = (int)rintf((float)px * sa + (float)py * ca);
+      const int X = cx + ix, Y = cy + iy;
+      if (X >= 0 && X < w && Y >= 0 && Y < h) return blur[(size_t)Y * w + X];
+      return img[(size_t)reflect101(Y, h) * pitch + reflect101(X, w)];
+    };
+    unsigned v = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      const char4 q = reinterpret_cast<const char4*>(tests)[8 * b + t];   // x1, y1, x2, y2
+      v |= (unsigned)(sample(q.x, q.y) < sample(q.z, q.w)) << t;          // LSB first
+    }
+    desc_tmp[(size_t)i * ORB_BYTES + b] = (uint8_t)v;
+  }
+  if (b != 0) return;
+  extract_point(k, i, inside, right_x, status, cam, xyz_tmp, keep);
 }
 
 // ONE workgroup: stable compaction into the store slot (and the optional wire copies)
@@ -262,6 +439,49 @@ void sf_brief_default_pattern(int8_t* tests, int bytes) {
   }
 }
 
+// Default ORB test set of a fresh handle: OpenCV's own makeRandomPattern(31, 512) -- cv::RNG(0x34985739), uniform(-15, 16)
+// for x then y of each of the 512 points, test k = (point 2k, point 2k + 1).  NOT OpenCV's bit_pattern_31_ table.
+void sf_orb_default_pattern(int8_t* tests) {
+  uint64_t s = 0x34985739u;
+  auto next = [&]() {                       // cv::RNG::next: multiply-with-carry
+    s = (uint64_t)(uint32_t)s * 4164903690ull + (s >> 32);
+    return (uint32_t)s;
+  };
+  for (int t = 0; t < 8 * ORB_BYTES * 4; ++t) tests[t] = (int8_t)((int)(next() % 31u) - ORB_HALF);
+}
+
+// getGaussianKernel(7, 2, CV_32F), every tap times 256 rounded to an integer (OpenCV 3.x's 8-bit fixed point): the
+// taps are 18 34 49 55 49 34 18 and sum to 257
+static OrbTaps orb_blur_taps() {
+  float cf[7];
+  double sum = 0.0;
+  for (int i = 0; i < 7; ++i) {
+    const double x = i - 3.0;
+    cf[i] = (float)std::exp((-0.5 / (2.0 * 2.0)) * x * x);
+    sum += cf[i];
+  }
+  sum = 1.0 / sum;
+  OrbTaps T;
+  for (int i = 0; i < 7; ++i) T.t[i] = (int)std::lrint((double)((float)(cf[i] * sum) * 256.0f));
+  return T;
+}
+
+// ORB's umax: the half width of every row of the radius-15 circular patch, made symmetric about the diagonal
+static OrbUmax orb_umax() {
+  int umax[ORB_HALF + 2] = {};
+  const int vmax = (int)std::floor(ORB_HALF * std::sqrt(2.f) / 2 + 1);
+  const int vmin = (int)std::ceil(ORB_HALF * std::sqrt(2.f) / 2);
+  for (int v = 0; v <= vmax; ++v) umax[v] = (int)std::lrint(std::sqrt((double)ORB_HALF * ORB_HALF - v * v));
+  for (int v = ORB_HALF, v0 = 0; v >= vmin; --v) {
+    while (umax[v0] == umax[v0 + 1]) ++v0;
+    umax[v] = v0;
+    ++v0;
+  }
+  OrbUmax U;
+  for (int v = 0; v <= ORB_HALF; ++v) U.u[v] = umax[v];
+  return U;
+}
+
 // Launch sequence on the handle's stream; the store slot (kcap >= n, w dwords) has been reserved by the caller.
 // n_img > 1: a batch -- image i at d_left + i * img_stride, its corners / right_x / status / optional copies at + i * n
 // entries, its corner count in d_n[i] (device; `n` is then the per-image capacity), its store slot = slot + i.
@@ -270,19 +490,29 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                             const int32_t* d_n, const sf_stereo_camera* cam, int bytes, const int8_t* d_tests,
                             uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap, int w_dwords,
                             int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                            int32_t* d_rows_out) {
+                            int32_t* d_rows_out, const sf_orb_params* orb) {
   int rc;
-  const size_t s_entries = (size_t)(width + 1) * (height + 1);
+  if (orb && bytes != ORB_BYTES) return sf_fail(c, SF_EINVAL, "ORB rows are %d bytes, not %d", ORB_BYTES, bytes);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
-  if ((rc = sf_buf_reserve(c, c->ex_integral, s_entries * sizeof(int32_t) * n_img)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_xyz, rows_all * 12)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_keep, rows_all)) != SF_OK) return rc;
-  int32_t* S = (int32_t*)c->ex_integral.p;
   ExtractBatch B;
-  B.img_stride = img_stride; B.s_stride = s_entries; B.per_image = n; B.d_n = d_n;
-  hipLaunchKernelGGL(k_integral_rows, dim3(height + 1, n_img), dim3(256), 0, c->stream, d_left, width, height, pitch, S, B);
-  hipLaunchKernelGGL(k_integral_cols, dim3((width + 1 + 63) / 64, n_img), dim3(64), 0, c->stream, width, height, S, B);
+  B.img_stride = img_stride; B.per_image = n; B.d_n = d_n;
+  int32_t* S = nullptr;
+  if (!orb) {
+    const size_t s_entries = (size_t)(width + 1) * (height + 1);
+    if ((rc = sf_buf_reserve(c, c->ex_integral, s_entries * sizeof(int32_t) * n_img)) != SF_OK) return rc;
+    S = (int32_t*)c->ex_integral.p;
+    B.s_stride = s_entries;
+    hipLaunchKernelGGL(k_integral_rows, dim3(height + 1, n_img), dim3(256), 0, c->stream, d_left, width, height, pitch, S, B);
+    hipLaunchKernelGGL(k_integral_cols, dim3((width + 1 + 63) / 64, n_img), dim3(64), 0, c->stream, width, height, S, B);
+  } else {
+    B.s_stride = (size_t)width * height;                 // the blurred level-0 images, back to back
+    if ((rc = sf_buf_reserve(c, c->ex_blur, B.s_stride * n_img)) != SF_OK) return rc;
+    hipLaunchKernelGGL(k_orb_blur, dim3((height + ORB_BLUR_ROWS - 1) / ORB_BLUR_ROWS, n_img), dim3(256), 0, c->stream,
+                       d_left, width, height, pitch, (uint8_t*)c->ex_blur.p, orb_blur_taps(), B);
+  }
   ExtractCam ec;
   ec.fx = cam->fx; ec.fy = cam->fy; ec.cx = cam->cx; ec.cy = cam->cy; ec.cx_right = cam->cx_right;
   ec.baseline = cam->baseline; ec.min_depth = cam->min_depth; ec.max_depth = cam->max_depth;
@@ -292,13 +522,27 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
     ec.identity_local = ec.identity_local && (ec.L[e] == ((e == 0 || e == 5 || e == 10) ? 1.0f : 0.0f));
   }
   ec.filter = cam->min_depth > 0.0f || cam->max_depth > 0.0f;
+  const sf_keypoint* kp_commit = d_kpts;
   if (n > 0) {
     const long long threads = (long long)n * bytes;
-    hipLaunchKernelGGL(k_extract_points, dim3((unsigned)((threads + 255) / 256), n_img), dim3(256), 0, c->stream, S, width,
-                       height, d_kpts, d_right_x, d_status, n, bytes, d_tests, ec, (uint8_t*)c->ex_desc.p,
-                       (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);
+    if (!orb) {
+      hipLaunchKernelGGL(k_extract_points, dim3((unsigned)((threads + 255) / 256), n_img), dim3(256), 0, c->stream, S, width,
+                         height, d_kpts, d_right_x, d_status, n, bytes, d_tests, ec, (uint8_t*)c->ex_desc.p,
+                         (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);
+    } else {
+      if (orb->orientation) {                             // the keypoints with their angles, for the samples and the commit
+        if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
+        hipLaunchKernelGGL(k_orb_angle, dim3((unsigned)((n + 3) / 4), n_img), dim3(256), 0, c->stream, d_left, width,
+                           height, pitch, d_kpts, n, orb->edge_threshold, orb_umax(), (sf_keypoint*)c->ex_kpts.p, B);
+        kp_commit = (const sf_keypoint*)c->ex_kpts.p;
+      }
+      hipLaunchKernelGGL(k_orb_points, dim3((unsigned)((threads + 255) / 256), n_img), dim3(256), 0, c->stream, d_left,
+                         (const uint8_t*)c->ex_blur.p, width, height, pitch, kp_commit, d_right_x, d_status, n,
+                         orb->edge_threshold, d_tests, ec, (uint8_t*)c->ex_desc.p, (float*)c->ex_xyz.p,
+                         (uint8_t*)c->ex_keep.p, B);
+    }
   }
-  hipLaunchKernelGGL(k_extract_commit, dim3(n_img), dim3(256), 0, c->stream, d_kpts, (const uint8_t*)c->ex_desc.p,
+  hipLaunchKernelGGL(k_extract_commit, dim3(n_img), dim3(256), 0, c->stream, kp_commit, (const uint8_t*)c->ex_desc.p,
                      (const float*)c->ex_xyz.p, (const uint8_t*)c->ex_keep.p, n, bytes, d_right_x != nullptr, st_desc,
                      st_xyz, st_kp, st_meta, kcap, w_dwords, slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out, B);
   SF_HIP(c, hipGetLastError());
@@ -309,8 +553,8 @@ int sf_launch_extract(sf_context* c, const uint8_t* d_left, int width, int heigh
                       const float* d_right_x, const uint8_t* d_status, int n, const sf_stereo_camera* cam, int bytes,
                       const int8_t* d_tests, uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap,
                       int w_dwords, int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                      int32_t* d_rows_out) {
+                      int32_t* d_rows_out, const sf_orb_params* orb) {
   return sf_launch_extract_batch(c, d_left, 0, 1, width, height, pitch, d_kpts, d_right_x, d_status, n, nullptr, cam, bytes,
                                  d_tests, st_desc, st_xyz, st_kp, st_meta, kcap, w_dwords, slot, d_desc_out, d_xyz_out,
-                                 d_kpts_out, d_rows_out);
+                                 d_kpts_out, d_rows_out, orb);
 }

@@ -793,7 +793,8 @@ extern "C" void sf_destroy(sf_handle c) {
                  &c->scratch.kp, &c->scratch.meta, &c->nn_local.rows, &c->nn_local.norms, &c->nn_local.rows_h, &c->nn_local.norms_k, &c->nn_recv.norms_k, &c->nn_recv.rows,
                  &c->nn_recv.norms, &c->nn_recv.rows_h, &c->d_mask_local, &c->d_mask_other, &c->d_ign_ptr,
                  &c->d_ign_col, &c->nn_rowmin, &c->nn_exact, &c->nn_scalar, &c->comm_scratch, &c->trace, &c->stage_desc, &c->stage_xyz, &c->stage_kp,
-                 &c->ex_integral, &c->ex_desc, &c->ex_xyz, &c->ex_keep, &c->ex_rows, &c->brief_tests,
+                 &c->ex_integral, &c->ex_desc, &c->ex_xyz, &c->ex_keep, &c->ex_rows, &c->brief_tests, &c->orb_tests,
+                 &c->ex_blur, &c->ex_kpts,
                  &c->gf_planes, &c->gf_keys, &c->gf_tmp, &c->gf_lists, &c->gf_scalar, &c->lk_pyr, &c->ft_images, &c->ft_kpts, &c->ft_flow, &c->ft_wire,
                  &c->ft_counts};
   for (Buf* b : bufs) buf_free(*b);
@@ -938,6 +939,112 @@ extern "C" int sf_brief_get_pattern(sf_handle c, int8_t* tests, int32_t cap_byte
   return SF_OK;
 }
 
+// ---- GFTT/ORB (Vis/FeatureType 8) --------------------------------------------------------------------------------
+extern "C" void sf_orb_defaults(sf_orb_params* p) {
+  if (!p) return;
+  p->edge_threshold = 19;      // ORB/EdgeThreshold [upstream rtabmap Parameters.h]
+  p->patch_size = 31;          // ORB/PatchSize
+  p->wta_k = 2;                // ORB/WTA_K
+  p->orientation = 0;          // rtabmap's GFTT/ORB: the keypoint's own angle
+}
+
+static int orb_validate(sf_context* c, const sf_orb_params& o) {
+  if (o.edge_threshold < 1 || o.edge_threshold > 64)
+    return sf_fail(c, SF_EINVAL, "ORB edge_threshold %d outside 1 .. 64", o.edge_threshold);
+  if (o.patch_size != 31) return sf_fail(c, SF_EINVAL, "ORB patch_size %d: only 31 is built", o.patch_size);
+  if (o.wta_k != 2) return sf_fail(c, SF_EINVAL, "ORB wta_k %d: only 2 (32-byte rows) is built", o.wta_k);
+  if (o.orientation != 0 && o.orientation != 1)
+    return sf_fail(c, SF_EINVAL, "ORB orientation %d unknown (0 = the keypoint's angle, 1 = intensity centroid)", o.orientation);
+  if (o.orientation == 1 && o.edge_threshold < 16)
+    return sf_fail(c, SF_EINVAL, "ORB orientation 1 needs edge_threshold >= 16 (the radius-15 patch), not %d", o.edge_threshold);
+  return SF_OK;
+}
+
+static int orb_upload(sf_context* c) {
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->orb_tests, sizeof c->orb_host)) != SF_OK) return rc;
+  SF_HIP(c, hipMemcpyAsync(c->orb_tests.p, c->orb_host, sizeof c->orb_host, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));   // (the host table may change right after the call returns)
+  c->orb_loaded = true;
+  return SF_OK;
+}
+
+extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_orb_params* orb) {
+  if (!c) return SF_EINVAL;
+  if (feature_type == 6) {
+    c->feature_type = 6;
+    return SF_OK;
+  }
+  if (feature_type != 8)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (6 = GFTT/BRIEF, 8 = GFTT/ORB)", feature_type);
+  if (c->params.desc_type != 0)
+    return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+  sf_orb_params o;
+  if (orb) o = *orb; else sf_orb_defaults(&o);
+  int rc = orb_validate(c, o);
+  if (rc != SF_OK) return rc;
+  c->orb = o;
+  c->feature_type = 8;
+  return SF_OK;
+}
+
+extern "C" int sf_get_feature_type(sf_handle c, int32_t* feature_type, sf_orb_params* orb) {
+  if (!c || !feature_type) return SF_EINVAL;
+  *feature_type = c->feature_type;
+  if (orb) *orb = c->orb;
+  return SF_OK;
+}
+
+extern "C" int sf_orb_set_pattern(sf_handle c, const int8_t* tests, int32_t bytes) {
+  if (!c || !tests) return SF_EINVAL;
+  if (bytes != 32) return sf_fail(c, SF_EINVAL, "ORB descriptors (WTA_K 2) are 32 bytes, not %d", bytes);
+  for (int t = 0; t < bytes * 32; ++t)
+    if (tests[t] < -15 || tests[t] > 15) return sf_fail(c, SF_EINVAL, "ORB test coordinate %d outside the 31 px patch", (int)tests[t]);
+  SF_HIP(c, hipSetDevice(c->device));
+  memcpy(c->orb_host, tests, sizeof c->orb_host);
+  return orb_upload(c);
+}
+
+static int orb_ensure(sf_context* c) {
+  if (c->orb_loaded) return SF_OK;
+  sf_orb_default_pattern(c->orb_host);
+  return orb_upload(c);
+}
+
+extern "C" int sf_orb_get_pattern(sf_handle c, int8_t* tests, int32_t cap_bytes, int32_t* bytes) {
+  if (!c || !bytes) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  int rc = orb_ensure(c);
+  if (rc != SF_OK) return rc;
+  *bytes = 32;
+  if (tests) {
+    if (cap_bytes < 32) return sf_fail(c, SF_ERANGE, "pattern buffer holds %d of 32 descriptor bytes", cap_bytes);
+    memcpy(tests, c->orb_host, sizeof c->orb_host);
+  }
+  return SF_OK;
+}
+
+// The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF)
+struct ExtractKind {
+  int bytes;
+  const int8_t* d_tests;
+  const sf_orb_params* orb;
+};
+
+static int extract_kind(sf_context* c, ExtractKind* k) {
+  int rc;
+  if (c->feature_type == 8) {
+    if (c->params.desc_type != 0)
+      return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+    if ((rc = orb_ensure(c)) != SF_OK) return rc;
+    *k = {32, (const int8_t*)c->orb_tests.p, &c->orb};
+    return SF_OK;
+  }
+  if ((rc = brief_ensure(c)) != SF_OK) return rc;
+  *k = {c->brief_bytes, (const int8_t*)c->brief_tests.p, nullptr};
+  return SF_OK;
+}
+
 extern "C" int sf_netvlad_load(sf_handle c, const sf_netvlad_weights* w) {
   if (!c) return SF_EINVAL;
   SF_HIP(c, hipSetDevice(c->device));
@@ -1014,16 +1121,17 @@ extern "C" int sf_extract_keyframe_device(sf_handle c, const uint8_t* d_left, in
   if (n > SF_MAX_FEATURES) return sf_fail(c, SF_ERANGE, "%d corners > int16 limit of KeyPointVec.size", n);
   if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
   SF_HIP(c, hipSetDevice(c->device));
-  int rc = brief_ensure(c);
+  ExtractKind kind;
+  int rc = extract_kind(c, &kind);
   if (rc != SF_OK) return rc;
-  if ((rc = store_reserve(c, c->store, c->store.slots + 1, n, c->brief_bytes)) != SF_OK) return rc;
+  if ((rc = store_reserve(c, c->store, c->store.slots + 1, n, kind.bytes)) != SF_OK) return rc;
   if (out_rows && (rc = sf_buf_reserve(c, c->ex_rows, 16)) != SF_OK) return rc;
   Store& st = c->store;
   const int slot = st.slots;
-  if ((rc = sf_launch_extract(c, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam, c->brief_bytes,
-                              (const int8_t*)c->brief_tests.p, (uint32_t*)st.desc.p, (float*)st.xyz.p, (float4*)st.kp.p,
+  if ((rc = sf_launch_extract(c, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam, kind.bytes,
+                              kind.d_tests, (uint32_t*)st.desc.p, (float*)st.xyz.p, (float4*)st.kp.p,
                               (int4*)st.meta.p, st.kcap, st.w, slot, d_desc_out, d_xyz_out, d_kpts_out,
-                              out_rows ? (int32_t*)c->ex_rows.p : nullptr)) != SF_OK)
+                              out_rows ? (int32_t*)c->ex_rows.p : nullptr, kind.orb)) != SF_OK)
     return rc;
   st.slots += 1;
   if (out_slot) *out_slot = slot;
@@ -1057,14 +1165,15 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
     return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
   SF_HIP(c, hipSetDevice(c->device));
-  int rc = brief_ensure(c);
+  ExtractKind kind;
+  int rc = extract_kind(c, &kind);
   if (rc != SF_OK) return rc;
   const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
   const int maxf = dp.max_features;
   if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_flow, (size_t)maxf * 16)) != SF_OK) return rc;
-  const size_t row_bytes = (size_t)c->brief_bytes + 12 + sizeof(sf_keypoint);
+  const size_t row_bytes = (size_t)kind.bytes + 12 + sizeof(sf_keypoint);
   if ((rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64)) != SF_OK) return rc;
   uint8_t* d_left = (uint8_t*)c->ft_images.p;
   uint8_t* d_right = d_left + img_bytes;
@@ -1081,7 +1190,7 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   if ((rc = sf_stereo_correspondences_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, d_xy, d_status, d_rx, nullptr)) != SF_OK)
     return rc;
   uint8_t* d_desc = (uint8_t*)c->ft_wire.p;
-  float* d_xyz = (float*)(d_desc + (((size_t)maxf * c->brief_bytes + 15) & ~(size_t)15));
+  float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
   sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
   int32_t slot = -1, rows = 0;
   if ((rc = sf_extract_keyframe_device(c, d_left, width, height, width, d_kpts, d_rx, d_status, n, cam, &slot, &rows, d_desc,
@@ -1091,7 +1200,7 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   if (slot_out) *slot_out = slot;
   const int32_t k = std::min(rows, cap_rows);
   if (k > 0) {
-    if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, d_desc, (size_t)k * c->brief_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, d_desc, (size_t)k * kind.bytes, hipMemcpyDeviceToHost, c->stream));
     if (xyz_out) SF_HIP(c, hipMemcpyAsync(xyz_out, d_xyz, (size_t)k * 12, hipMemcpyDeviceToHost, c->stream));
     if (kpts_out) SF_HIP(c, hipMemcpyAsync(kpts_out, d_kp_out, (size_t)k * sizeof(sf_keypoint), hipMemcpyDeviceToHost, c->stream));
     SF_HIP(c, hipStreamSynchronize(c->stream));
@@ -1125,14 +1234,15 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
     return sf_fail(c, SF_EINVAL, "stereo flow parameters out of range (see sf_stereo_correspondences_device)");
   if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
   SF_HIP(c, hipSetDevice(c->device));
-  int rc = brief_ensure(c);
+  ExtractKind kind;
+  int rc = extract_kind(c, &kind);
   if (rc != SF_OK) return rc;
   const int maxf = dp.max_features, n = n_keyframes;
   const size_t rows_all = (size_t)maxf * n;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_flow, rows_all * 16)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_counts, (size_t)n * 4)) != SF_OK) return rc;
-  if ((rc = store_reserve(c, c->store, c->store.slots + n, maxf, c->brief_bytes)) != SF_OK) return rc;
+  if ((rc = store_reserve(c, c->store, c->store.slots + n, maxf, kind.bytes)) != SF_OK) return rc;
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t* d_n = (int32_t*)c->ft_counts.p;
   if ((rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
@@ -1147,9 +1257,9 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
   Store& st = c->store;
   const int slot = st.slots;
   if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam,
-                                    c->brief_bytes, (const int8_t*)c->brief_tests.p, (uint32_t*)st.desc.p, (float*)st.xyz.p,
+                                    kind.bytes, kind.d_tests, (uint32_t*)st.desc.p, (float*)st.xyz.p,
                                     (float4*)st.kp.p, (int4*)st.meta.p, st.kcap, st.w, slot, d_desc_out, d_xyz_out,
-                                    d_kpts_out, d_rows_out)) != SF_OK)
+                                    d_kpts_out, d_rows_out, kind.orb)) != SF_OK)
     return rc;
   st.slots += n;
   if (first_slot_out) *first_slot_out = slot;

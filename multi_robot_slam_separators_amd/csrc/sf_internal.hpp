@@ -232,6 +232,14 @@ struct sf_context {
   struct sf_netvlad_model* netvlad = nullptr;   // NetVLAD inference (k_cnn.hip): weights + activation buffers
   int brief_bytes = 0;                 // 0: table not uploaded yet
   int8_t brief_host[64 * 8 * 4] = {};
+  // Vis/FeatureType of the extraction (sf_set_feature_type): 6 = GFTT/BRIEF, 8 = GFTT/ORB with `orb` and the ORB test
+  // table (orb_host, uploaded to orb_tests; orb_loaded false: the default set, not generated yet); ex_blur / ex_kpts:
+  // the blurred level-0 images and the keypoints with their ORB angles
+  int feature_type = 6;
+  sf_orb_params orb = {19, 31, 2, 0};
+  bool orb_loaded = false;
+  int8_t orb_host[32 * 8 * 4] = {};
+  Buf orb_tests, ex_blur, ex_kpts;
   Buf trace;                    // SF_CHAIN_TRACE builds: uint64[n][32] phase timestamps of the fused kernel
 
   // NN stage
@@ -487,6 +495,7 @@ size_t sf_ba_lds_bytes(int kcap);
 size_t sf_pnp_lds_bytes(int kcap, int iterations);
 size_t sf_guided_lds_bytes(int kcap, int n_cells, bool narrow = false);   // narrow: the one- / two-wavefront chains' shorter candidate list
 void sf_brief_default_pattern(int8_t* tests, int bytes);
+void sf_orb_default_pattern(int8_t* tests);     // [256][4]: 32-byte ORB rows
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
                                    sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out);
@@ -499,7 +508,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                             const int32_t* d_n, const sf_stereo_camera* cam, int bytes, const int8_t* d_tests,
                             uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap, int w_dwords,
                             int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                            int32_t* d_rows_out);
+                            int32_t* d_rows_out, const sf_orb_params* orb = nullptr);   // orb: GFTT/ORB rows, else BRIEF
 int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
                              int32_t* n_out);
@@ -510,7 +519,7 @@ int sf_launch_extract(sf_context* c, const uint8_t* d_left, int width, int heigh
                       const float* d_right_x, const uint8_t* d_status, int n, const sf_stereo_camera* cam, int bytes,
                       const int8_t* d_tests, uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap,
                       int w_dwords, int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                      int32_t* d_rows_out);
+                      int32_t* d_rows_out, const sf_orb_params* orb = nullptr);
 // Assemble sf_result records.
 int sf_launch_finalize(sf_context* c, int n, sf_result* d_out);
 // Ingest kernels

@@ -81,6 +81,11 @@ def load():
         "sf_store_add_keyframes_device": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, P(i32)]),
         "sf_brief_set_pattern": (C.c_int, [vp, vp, i32]),
         "sf_brief_get_pattern": (C.c_int, [vp, vp, i32, P(i32)]),
+        "sf_orb_defaults": (None, [P(_abi.OrbParams)]),
+        "sf_set_feature_type": (C.c_int, [vp, i32, P(_abi.OrbParams)]),
+        "sf_get_feature_type": (C.c_int, [vp, P(i32), P(_abi.OrbParams)]),
+        "sf_orb_set_pattern": (C.c_int, [vp, vp, i32]),
+        "sf_orb_get_pattern": (C.c_int, [vp, vp, i32, P(i32)]),
         "sf_extract_keyframe_device": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, i32, P(_abi.StereoCamera),
                                                  P(i32), P(i32), vp, vp, vp]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
@@ -167,6 +172,7 @@ EXPORTED = [
     "sf_allgather_separators", "sf_allgather_separators_device", "sf_allgather_bytes_device", "sf_nn_row_minima_device", "sf_nn_walk_device",
     "sf_get_features_and_descriptor_batch_device", "sf_prof_enable", "sf_prof_select", "sf_prof_reset", "sf_prof_get",
     "sf_kernel_name", "sf_stream_placement", "sf_streams_prepare",
+    "sf_orb_defaults", "sf_set_feature_type", "sf_get_feature_type", "sf_orb_set_pattern", "sf_orb_get_pattern",
 ]
 
 
@@ -340,6 +346,32 @@ class SeparatorFinder:
         self._check(self._L.sf_brief_get_pattern(self._h, C.c_void_p(buf.ctypes.data), 64, C.byref(n)))
         return buf[:8 * n.value].copy()
 
+    def set_feature_type(self, feature_type, orb=None):
+        """Vis/FeatureType of the extraction calls: 6 = GFTT/BRIEF (a fresh handle), 8 = GFTT/ORB with orb
+        (_abi.OrbParams; None = rtabmap's ORB/ defaults)."""
+        self._check(self._L.sf_set_feature_type(self._h, int(feature_type), C.byref(orb) if orb is not None else None))
+
+    def get_feature_type(self):
+        """(feature type, _abi.OrbParams of the ORB extraction)."""
+        ft, o = C.c_int32(), _abi.OrbParams()
+        self._check(self._L.sf_get_feature_type(self._h, C.byref(ft), C.byref(o)))
+        return ft.value, o
+
+    def orb_set_pattern(self, tests):
+        """tests: int8 [256, 4] = (x1, y1, x2, y2) per descriptor bit, within +-15."""
+        t = np.ascontiguousarray(tests, dtype=np.int8).reshape(-1, 4)
+        self._check(self._L.sf_orb_set_pattern(self._h, C.c_void_p(t.ctypes.data), t.shape[0] // 8))
+
+    def orb_get_pattern(self):
+        n = C.c_int32()
+        buf = np.zeros((32 * 8, 4), np.int8)
+        self._check(self._L.sf_orb_get_pattern(self._h, C.c_void_p(buf.ctypes.data), 32, C.byref(n)))
+        return buf[:8 * n.value].copy()
+
+    def descriptor_bytes(self):
+        """Row bytes the extraction calls write with the handle's feature type."""
+        return 32 if self.get_feature_type()[0] == _abi.FEATURE_GFTT_ORB else self.brief_get_pattern().shape[0] // 8
+
     # -- NetVLAD inference (SURVEY section 8(f) rank 4) -------------------------------------------------
     def netvlad_load(self, weights):
         """weights: dict of float32 numpy arrays in TensorFlow layouts -- conv_kernel[13] ([3, 3, Cin, Cout]),
@@ -397,7 +429,7 @@ class SeparatorFinder:
             raise ValueError("left / right must be 2-D uint8 images of one shape and row stride")
         h, w = left.shape
         cap = (det.max_features if det is not None else 1000)
-        nbytes = self.brief_get_pattern().shape[0] // 8
+        nbytes = self.descriptor_bytes()
         desc = np.zeros((cap, nbytes), np.uint8)
         xyz = np.zeros((cap, 3), np.float32)
         kp = np.zeros(cap, _abi.KEYPOINT_DTYPE)

@@ -97,6 +97,25 @@ class SepfinderGeometricTools {
     } else {
       ROS_WARN("no brief_pattern_file: descriptors will not match a robot that runs the reference's OpenCV BRIEF");
     }
+
+    // Vis/FeatureType: 6 = GFTT/BRIEF (default), 8 = GFTT/ORB with ORB/EdgeThreshold; see INTEGRATION.md
+    int feature_type = 6, edge_threshold = 19;
+    n.param("feature_type", feature_type, 6);
+    n.param("orb_edge_threshold", edge_threshold, 19);
+    sf_orb_params orb;
+    sf_orb_defaults(&orb);
+    orb.edge_threshold = edge_threshold;
+    if (sf_set_feature_type(sf_, feature_type, &orb) != SF_OK)
+      ROS_ERROR("feature_type %d: %s", feature_type, sf_last_error(sf_));
+    // OpenCV's ORB bit_pattern_31_ (256 tests x 4 int8: x1 y1 x2 y2), if the integrator provides it
+    if (n.getParam("orb_pattern_file", pattern_file) && !pattern_file.empty()) {
+      std::ifstream in(pattern_file.c_str(), std::ios::binary);
+      std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+      if (raw.size() != 32 * 8 * 4 || sf_orb_set_pattern(sf_, reinterpret_cast<const int8_t*>(raw.data()), 32) != SF_OK)
+        ROS_ERROR("orb_pattern_file %s: 1024 bytes expected (%s)", pattern_file.c_str(), sf_last_error(sf_));
+    } else if (feature_type == 8) {
+      ROS_WARN("no orb_pattern_file: descriptors will not match a robot that runs the reference's OpenCV ORB");
+    }
   }
 
   ~SepfinderGeometricTools() { if (sf_) sf_destroy(sf_); }
@@ -111,8 +130,10 @@ class SepfinderGeometricTools {
                 r.encoding.c_str());
       return false;       // (cv_bridge::toCvCopy(..., MONO8) converts other encodings in the reference: convert upstream)
     }
-    int32_t bytes = 0;
-    sf_brief_get_pattern(sf_, nullptr, 0, &bytes);
+    int32_t bytes = 0, feature_type = 6;
+    sf_get_feature_type(sf_, &feature_type, nullptr);
+    if (feature_type == 8) sf_orb_get_pattern(sf_, nullptr, 0, &bytes);   // 32-byte ORB rows
+    else sf_brief_get_pattern(sf_, nullptr, 0, &bytes);
     const int cap = 32767;                                            // KeyPointVec.size is an int16
     std::vector<uint8_t> desc((size_t)cap * bytes);
     res.kpts3D.kpts3DVec.resize(cap);
