@@ -58,7 +58,7 @@ int  sf_accept_stream_status(sf_handle h, int32_t* streamed, int32_t* pairs);
    measurement brackets only the kernel it prices (bench.py: the dominant one) and surveys the rest separately.  */
 int  sf_prof_select(sf_handle h, uint32_t kernel_mask);
 /* One line on where the step pipeline's streams were placed on the hardware's dispatch pipes (measured once per handle at
-   the first step that needs a second stream: sf_api.hip place_streams; SF_STREAM_PLACEMENT=0 in the environment turns the
+   the first step that needs a second stream: sf_placement.hip place_streams; SF_STREAM_PLACEMENT=0 in the environment turns the
    measurement off, =2 also prints the line to stderr). */
 int  sf_stream_placement(sf_handle h, char* buf, size_t n);
 /* Runs that measurement now instead of inside the first step that needs a second stream (60-100 ms once per handle:

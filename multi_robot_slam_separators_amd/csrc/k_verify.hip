@@ -200,7 +200,7 @@ k_verify_fused(StoreView st, const int32_t* __restrict__ pair_from, const int32_
 // survivors' lists / headers take one trip through HBM (~2 KB per survivor) and their chains run four to a CU.  Same
 // bodies, same bytes.  On ONE stream the fused kernel is the faster form (its chains overlap other pairs' matching
 // inside the launch); since sf_step_issue alternates the steps between two streams the neighbouring step fills a
-// launch's tail anyway and the split form wins -- sf_use_split (sf_api.hip) picks it there (SF_OPT_STEP_SPLIT).
+// launch's tail anyway and the split form wins -- sf_use_split (sf_verify_host.hip) picks it there (SF_OPT_STEP_SPLIT).
 template <int W, int NTL = 4, int MINW = 3>
 __global__ void __launch_bounds__(SF_BLOCK, MINW)
 k_match_split(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,

@@ -1,0 +1,373 @@
+// sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
+// detection, stereo correspondence and keyframe extraction (kernels in k_extract.hip, k_gftt.hip, k_lk.hip, k_cnn.hip).
+#include "sf_host.hpp"
+
+// ---- feature extraction (kernels in k_extract.hip) ----------------------------------
+static int brief_upload(sf_context* c) {
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->brief_tests, sizeof c->brief_host)) != SF_OK) return rc;
+  SF_HIP(c, hipMemcpyAsync(c->brief_tests.p, c->brief_host, (size_t)c->brief_bytes * 32, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));   // (the host table may change right after the call returns)
+  return SF_OK;
+}
+
+extern "C" int sf_brief_set_pattern(sf_handle c, const int8_t* tests, int32_t bytes) {
+  if (!c || !tests) return SF_EINVAL;
+  if (bytes != 16 && bytes != 32 && bytes != 64) return sf_fail(c, SF_ERANGE, "BRIEF descriptors are 16, 32 or 64 bytes, not %d", bytes);
+  for (int t = 0; t < bytes * 32; ++t)
+    if (tests[t] < -24 || tests[t] > 24) return sf_fail(c, SF_ERANGE, "BRIEF test offset %d outside the 48 px patch", (int)tests[t]);
+  SF_HIP(c, hipSetDevice(c->device));
+  memcpy(c->brief_host, tests, (size_t)bytes * 32);
+  c->brief_bytes = bytes;
+  return brief_upload(c);
+}
+
+static int brief_ensure(sf_context* c) {
+  if (c->params.desc_type != 0)
+    return sf_fail(c, SF_EINVAL, "the feature extraction writes BRIEF (binary) descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+  if (c->brief_bytes) return SF_OK;
+  const int want = c->params.desc_bytes;
+  c->brief_bytes = (want == 16 || want == 64) ? want : 32;
+  sf_brief_default_pattern(c->brief_host, c->brief_bytes);
+  return brief_upload(c);
+}
+
+extern "C" int sf_brief_get_pattern(sf_handle c, int8_t* tests, int32_t cap_bytes, int32_t* bytes) {
+  if (!c || !bytes) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  int rc = brief_ensure(c);
+  if (rc != SF_OK) return rc;
+  *bytes = c->brief_bytes;
+  if (tests) {
+    if (cap_bytes < c->brief_bytes) return sf_fail(c, SF_ERANGE, "pattern buffer holds %d of %d descriptor bytes", cap_bytes, c->brief_bytes);
+    memcpy(tests, c->brief_host, (size_t)c->brief_bytes * 32);
+  }
+  return SF_OK;
+}
+
+// ---- GFTT/ORB (Vis/FeatureType 8) --------------------------------------------------------------------------------
+extern "C" void sf_orb_defaults(sf_orb_params* p) {
+  if (!p) return;
+  p->edge_threshold = 19;      // ORB/EdgeThreshold [upstream rtabmap Parameters.h]
+  p->patch_size = 31;          // ORB/PatchSize
+  p->wta_k = 2;                // ORB/WTA_K
+  p->orientation = 0;          // rtabmap's GFTT/ORB: the keypoint's own angle
+}
+
+static int orb_validate(sf_context* c, const sf_orb_params& o) {
+  if (o.edge_threshold < 1 || o.edge_threshold > 64)
+    return sf_fail(c, SF_EINVAL, "ORB edge_threshold %d outside 1 .. 64", o.edge_threshold);
+  if (o.patch_size != 31) return sf_fail(c, SF_EINVAL, "ORB patch_size %d: only 31 is built", o.patch_size);
+  if (o.wta_k != 2) return sf_fail(c, SF_EINVAL, "ORB wta_k %d: only 2 (32-byte rows) is built", o.wta_k);
+  if (o.orientation != 0 && o.orientation != 1)
+    return sf_fail(c, SF_EINVAL, "ORB orientation %d unknown (0 = the keypoint's angle, 1 = intensity centroid)", o.orientation);
+  if (o.orientation == 1 && o.edge_threshold < 16)
+    return sf_fail(c, SF_EINVAL, "ORB orientation 1 needs edge_threshold >= 16 (the radius-15 patch), not %d", o.edge_threshold);
+  return SF_OK;
+}
+
+static int orb_upload(sf_context* c) {
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->orb_tests, sizeof c->orb_host)) != SF_OK) return rc;
+  SF_HIP(c, hipMemcpyAsync(c->orb_tests.p, c->orb_host, sizeof c->orb_host, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));   // (the host table may change right after the call returns)
+  c->orb_loaded = true;
+  return SF_OK;
+}
+
+extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_orb_params* orb) {
+  if (!c) return SF_EINVAL;
+  if (feature_type == 6) {
+    c->feature_type = 6;
+    return SF_OK;
+  }
+  if (feature_type != 8)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (6 = GFTT/BRIEF, 8 = GFTT/ORB)", feature_type);
+  if (c->params.desc_type != 0)
+    return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+  sf_orb_params o;
+  if (orb) o = *orb; else sf_orb_defaults(&o);
+  int rc = orb_validate(c, o);
+  if (rc != SF_OK) return rc;
+  c->orb = o;
+  c->feature_type = 8;
+  return SF_OK;
+}
+
+extern "C" int sf_get_feature_type(sf_handle c, int32_t* feature_type, sf_orb_params* orb) {
+  if (!c || !feature_type) return SF_EINVAL;
+  *feature_type = c->feature_type;
+  if (orb) *orb = c->orb;
+  return SF_OK;
+}
+
+extern "C" int sf_orb_set_pattern(sf_handle c, const int8_t* tests, int32_t bytes) {
+  if (!c || !tests) return SF_EINVAL;
+  if (bytes != 32) return sf_fail(c, SF_EINVAL, "ORB descriptors (WTA_K 2) are 32 bytes, not %d", bytes);
+  for (int t = 0; t < bytes * 32; ++t)
+    if (tests[t] < -15 || tests[t] > 15) return sf_fail(c, SF_EINVAL, "ORB test coordinate %d outside the 31 px patch", (int)tests[t]);
+  SF_HIP(c, hipSetDevice(c->device));
+  memcpy(c->orb_host, tests, sizeof c->orb_host);
+  return orb_upload(c);
+}
+
+static int orb_ensure(sf_context* c) {
+  if (c->orb_loaded) return SF_OK;
+  sf_orb_default_pattern(c->orb_host);
+  return orb_upload(c);
+}
+
+extern "C" int sf_orb_get_pattern(sf_handle c, int8_t* tests, int32_t cap_bytes, int32_t* bytes) {
+  if (!c || !bytes) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  int rc = orb_ensure(c);
+  if (rc != SF_OK) return rc;
+  *bytes = 32;
+  if (tests) {
+    if (cap_bytes < 32) return sf_fail(c, SF_ERANGE, "pattern buffer holds %d of 32 descriptor bytes", cap_bytes);
+    memcpy(tests, c->orb_host, sizeof c->orb_host);
+  }
+  return SF_OK;
+}
+
+// The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF)
+struct ExtractKind {
+  int bytes;
+  const int8_t* d_tests;
+  const sf_orb_params* orb;
+};
+
+static int extract_kind(sf_context* c, ExtractKind* k) {
+  int rc;
+  if (c->feature_type == 8) {
+    if (c->params.desc_type != 0)
+      return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+    if ((rc = orb_ensure(c)) != SF_OK) return rc;
+    *k = {32, (const int8_t*)c->orb_tests.p, &c->orb};
+    return SF_OK;
+  }
+  if ((rc = brief_ensure(c)) != SF_OK) return rc;
+  *k = {c->brief_bytes, (const int8_t*)c->brief_tests.p, nullptr};
+  return SF_OK;
+}
+
+extern "C" int sf_netvlad_load(sf_handle c, const sf_netvlad_weights* w) {
+  if (!c) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_load_impl(c, w);
+}
+
+extern "C" int sf_netvlad_infer_device(sf_handle c, const float* d_image_rgb, int32_t width, int32_t height, float* d_out,
+                                       int32_t n_out) {
+  if (!c || !d_image_rgb || !d_out) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_infer_impl(c, d_image_rgb, height, width, d_out, n_out);
+}
+
+extern "C" int sf_netvlad_infer_batch_device(sf_handle c, const float* d_images_rgb, int32_t n_images, int32_t width,
+                                             int32_t height, float* d_out, int32_t n_out) {
+  if (!c || !d_images_rgb || !d_out) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_infer_batch_impl(c, d_images_rgb, n_images, height, width, d_out, n_out);
+}
+
+extern "C" int sf_detect_corners_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                        int32_t max_corners, double quality_level, double min_distance,
+                                        sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
+  if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
+  *n_out = 0;
+  if (!d_image || width < 3 || height < 3 || pitch < width)
+    return sf_fail(c, SF_EINVAL, "image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  if (!(quality_level > 0.0) || !(min_distance >= 0.0))
+    return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
+  if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_detect_corners(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out,
+                                  cap, n_out);
+}
+
+extern "C" void sf_stereo_flow_defaults(sf_stereo_flow_params* p) {
+  if (!p) return;
+  p->win_width = 15; p->win_height = 3;        // Stereo/WinWidth, Stereo/WinHeight [upstream rtabmap Parameters.h]
+  p->max_level = 5;                            // Stereo/MaxLevel
+  p->iterations = 30;                          // Stereo/Iterations
+  p->epsilon = 0.01;                           // Stereo/Eps
+  p->min_disparity = 0.5f; p->max_disparity = 128.0f;
+  p->min_eig_threshold = 1e-4f;                // the literal in StereoOpticalFlow::computeCorrespondences
+}
+
+extern "C" int sf_stereo_correspondences_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right, int32_t width,
+                                                int32_t height, int32_t pitch, const sf_keypoint* d_kpts, int32_t n,
+                                                const sf_stereo_flow_params* params, float* d_right_xy,
+                                                uint8_t* d_status, float* d_right_x, float* d_err) {
+  if (!c || n < 0) return SF_EINVAL;
+  if (!d_left || !d_right || width < 1 || height < 1 || pitch < width)
+    return sf_fail(c, SF_EINVAL, "stereo pair missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  if (n > 0 && (!d_kpts || !d_right_xy || !d_status)) return sf_fail(c, SF_EINVAL, "corners or output arrays missing");
+  sf_stereo_flow_params prm;
+  if (params) prm = *params; else sf_stereo_flow_defaults(&prm);
+  if (prm.win_width <= 2 || prm.win_height <= 2)
+    return sf_fail(c, SF_EINVAL, "window of %d x %d: both sides must be > 2 (cv::calcOpticalFlowPyrLK asserts the same)", prm.win_width, prm.win_height);
+  if ((long long)prm.win_width * prm.win_height > 1024) return sf_fail(c, SF_ERANGE, "window of %d x %d exceeds 1024 pixels", prm.win_width, prm.win_height);
+  if (prm.max_level < 0 || prm.max_level > 15) return sf_fail(c, SF_ERANGE, "max_level %d outside 0 .. 15", prm.max_level);
+  if (!(prm.epsilon == prm.epsilon)) return sf_fail(c, SF_EINVAL, "epsilon is NaN");
+  if (n == 0) return SF_OK;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_stereo_flow(c, d_left, d_right, width, height, pitch, d_kpts, n, &prm, d_right_xy, d_status, d_right_x, d_err);
+}
+
+extern "C" int sf_extract_keyframe_device(sf_handle c, const uint8_t* d_left, int32_t width, int32_t height,
+                                          int32_t pitch, const sf_keypoint* d_kpts, const float* d_right_x,
+                                          const uint8_t* d_status, int32_t n, const sf_stereo_camera* cam,
+                                          int32_t* out_slot, int32_t* out_rows, uint8_t* d_desc_out,
+                                          float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n < 0) return SF_EINVAL;
+  if (!d_left || width < 1 || height < 1 || pitch < width) return sf_fail(c, SF_EINVAL, "left image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  if (n > 0 && !d_kpts) return sf_fail(c, SF_EINVAL, "keypoints missing");
+  if (n > SF_MAX_FEATURES) return sf_fail(c, SF_ERANGE, "%d corners > int16 limit of KeyPointVec.size", n);
+  if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
+  SF_HIP(c, hipSetDevice(c->device));
+  ExtractKind kind;
+  int rc = extract_kind(c, &kind);
+  if (rc != SF_OK) return rc;
+  if ((rc = sf_store_reserve(c, c->store, c->store.slots + 1, n, kind.bytes)) != SF_OK) return rc;
+  if (out_rows && (rc = sf_buf_reserve(c, c->ex_rows, 16)) != SF_OK) return rc;
+  Store& st = c->store;
+  const int slot = st.slots;
+  if ((rc = sf_launch_extract(c, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam, kind.bytes,
+                              kind.d_tests, (uint32_t*)st.desc.p, (float*)st.xyz.p, (float4*)st.kp.p,
+                              (int4*)st.meta.p, st.kcap, st.w, slot, d_desc_out, d_xyz_out, d_kpts_out,
+                              out_rows ? (int32_t*)c->ex_rows.p : nullptr, kind.orb)) != SF_OK)
+    return rc;
+  st.slots += 1;
+  if (out_slot) *out_slot = slot;
+  if (out_rows) {
+    SF_HIP(c, hipMemcpyAsync(out_rows, c->ex_rows.p, 4, hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return SF_OK;
+}
+
+extern "C" void sf_detector_defaults(sf_detector_params* p) {
+  if (!p) return;
+  p->max_features = 1000;      // Vis/MaxFeatures [upstream rtabmap Parameters.h]; the reference sets only Vis/MinInliers
+  p->quality_level = 0.001;    // GFTT/QualityLevel
+  p->min_distance = 3.0;       // GFTT/MinDistance
+}
+
+// The GetFeatsAndDesc handler in one call on HOST buffers: upload the pair, detect, track, extract, download the
+// response.  Everything between the two copies stays on the device; the keyframe is in the store when it returns.
+extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, const uint8_t* right, int32_t width,
+                                              int32_t height, int32_t pitch, const sf_stereo_camera* cam,
+                                              const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                              uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
+                                              int32_t* rows_out, int32_t* slot_out) {
+  if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
+  *rows_out = 0;
+  if (!left || !right || width < 3 || height < 3 || pitch < width)
+    return sf_fail(c, SF_EINVAL, "stereo pair missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  sf_detector_params dp;
+  if (det) dp = *det; else sf_detector_defaults(&dp);
+  if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
+    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
+  SF_HIP(c, hipSetDevice(c->device));
+  ExtractKind kind;
+  int rc = extract_kind(c, &kind);
+  if (rc != SF_OK) return rc;
+  const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
+  const int maxf = dp.max_features;
+  if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_flow, (size_t)maxf * 16)) != SF_OK) return rc;
+  const size_t row_bytes = (size_t)kind.bytes + 12 + sizeof(sf_keypoint);
+  if ((rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64)) != SF_OK) return rc;
+  uint8_t* d_left = (uint8_t*)c->ft_images.p;
+  uint8_t* d_right = d_left + img_bytes;
+  SF_HIP(c, hipMemcpy2DAsync(d_left, width, left, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
+  int32_t n = 0;
+  if ((rc = sf_detect_corners_device(c, d_left, width, height, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n)) != SF_OK)
+    return rc;
+  n = std::min(n, maxf);
+  float* d_xy = (float*)c->ft_flow.p;                    // [n][2], then x [n], then status [n]
+  float* d_rx = d_xy + 2 * (size_t)maxf;
+  uint8_t* d_status = (uint8_t*)(d_rx + maxf);
+  if ((rc = sf_stereo_correspondences_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, d_xy, d_status, d_rx, nullptr)) != SF_OK)
+    return rc;
+  uint8_t* d_desc = (uint8_t*)c->ft_wire.p;
+  float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
+  sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
+  int32_t slot = -1, rows = 0;
+  if ((rc = sf_extract_keyframe_device(c, d_left, width, height, width, d_kpts, d_rx, d_status, n, cam, &slot, &rows, d_desc,
+                                       d_xyz, d_kp_out)) != SF_OK)
+    return rc;
+  *rows_out = rows;
+  if (slot_out) *slot_out = slot;
+  const int32_t k = std::min(rows, cap_rows);
+  if (k > 0) {
+    if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, d_desc, (size_t)k * kind.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (xyz_out) SF_HIP(c, hipMemcpyAsync(xyz_out, d_xyz, (size_t)k * 12, hipMemcpyDeviceToHost, c->stream));
+    if (kpts_out) SF_HIP(c, hipMemcpyAsync(kpts_out, d_kp_out, (size_t)k * sizeof(sf_keypoint), hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return SF_OK;
+}
+
+// n keyframes from device images to n store slots in ONE launch sequence: detector, stereo correspondence and
+// extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
+// host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.
+extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                           int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                                           size_t image_stride, const sf_stereo_camera* cam,
+                                                           const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                           int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                           float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
+  if (!d_left || !d_right || width < 3 || height < 3 || pitch < width || image_stride < (size_t)pitch * height)
+    return sf_fail(c, SF_EINVAL, "stereo pairs missing or malformed (%d x %d, pitch %d, stride %zu)", width, height, pitch, image_stride);
+  sf_detector_params dp;
+  if (det) dp = *det; else sf_detector_defaults(&dp);
+  if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
+    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
+  if (!(dp.quality_level > 0.0) || !(dp.min_distance >= 0.0))
+    return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
+  sf_stereo_flow_params prm;
+  if (flow) prm = *flow; else sf_stereo_flow_defaults(&prm);
+  if (prm.win_width <= 2 || prm.win_height <= 2 || (long long)prm.win_width * prm.win_height > 1024 || prm.max_level < 0 ||
+      prm.max_level > 15 || !(prm.epsilon == prm.epsilon))
+    return sf_fail(c, SF_EINVAL, "stereo flow parameters out of range (see sf_stereo_correspondences_device)");
+  if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
+  SF_HIP(c, hipSetDevice(c->device));
+  ExtractKind kind;
+  int rc = extract_kind(c, &kind);
+  if (rc != SF_OK) return rc;
+  const int maxf = dp.max_features, n = n_keyframes;
+  const size_t rows_all = (size_t)maxf * n;
+  if ((rc = sf_buf_reserve(c, c->ft_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_flow, rows_all * 16)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_counts, (size_t)n * 4)) != SF_OK) return rc;
+  if ((rc = sf_store_reserve(c, c->store, c->store.slots + n, maxf, kind.bytes)) != SF_OK) return rc;
+  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
+  int32_t* d_n = (int32_t*)c->ft_counts.p;
+  if ((rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
+                                           dp.min_distance, d_kpts, maxf, d_n)) != SF_OK)
+    return rc;
+  float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
+  float* d_rx = d_xy + 2 * rows_all;
+  uint8_t* d_status = (uint8_t*)(d_rx + rows_all);
+  if ((rc = sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &prm,
+                                        d_xy, d_status, d_rx, nullptr)) != SF_OK)
+    return rc;
+  Store& st = c->store;
+  const int slot = st.slots;
+  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam,
+                                    kind.bytes, kind.d_tests, (uint32_t*)st.desc.p, (float*)st.xyz.p,
+                                    (float4*)st.kp.p, (int4*)st.meta.p, st.kcap, st.w, slot, d_desc_out, d_xyz_out,
+                                    d_kpts_out, d_rows_out, kind.orb)) != SF_OK)
+    return rc;
+  st.slots += n;
+  if (first_slot_out) *first_slot_out = slot;
+  return SF_OK;
+}

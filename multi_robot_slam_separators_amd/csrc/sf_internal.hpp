@@ -200,7 +200,7 @@ struct sf_context {
   hipStream_t stream = nullptr;   // the stream the launchers queue on: ws[0].stream, or another inside a UseWorkspace scope
   bool own_stream = false;
   // [0]: the handle's own; [1 .. SF_STEP_MAX_LANES - 1]: step lanes (SF_OPT_STEP_OVERLAP); [SF_STEP_MAX_LANES]: the second
-  // half of a two-stream batch (verify_device)
+  // half of a two-stream batch (sf_verify_device)
   Workspace ws[SF_STEP_MAX_LANES + 1];
   Workspace* w = ws;              // the workspace the launchers use
   std::string err;
@@ -276,7 +276,7 @@ struct sf_context {
   bool gf_select_attr = false; // k_gftt_select_lds: dynamic LDS attribute set
   bool nn_k128_attr = false;   // k_nn_filter_f16_k128: dynamic LDS attribute set
   bool split = false;       // SF_FUSED=2: one matching launch + one chain launch over the survivors (k_verify.hip)
-  bool split_auto = true;   // SF_OPT_STEP_SPLIT: the split form inside overlapped steps (sf_use_split, sf_api.hip); on again since
+  bool split_auto = true;   // SF_OPT_STEP_SPLIT: the split form inside overlapped steps (sf_use_split, sf_verify_host.hip); on again since
                             // round 5 (its matcher is software-pipelined: 23.0 against 22.7 M pairs/s, profiles/r05u_*)
   int split_auto_min = 2048;   // ... for queries of at least this many candidates (SF_STEP_SPLIT_MIN): below, one launch wins
   bool in_overlapped_step = false;   // set around sf_step_issue's body while the steps alternate between two streams
@@ -309,7 +309,7 @@ struct sf_context {
   int32_t comm_count_host = 0;
   Buf comm_scratch;
 
-  // Two-stream verification of large batches (sf_api.hip, verify_device): the second half of a batch runs
+  // Two-stream verification of large batches (sf_verify_host.hip, sf_verify_device): the second half of a batch runs
   // its stage kernels on ws[SF_STEP_MAX_LANES] -- a stream, workspace and counters of its own -- so that the
   // latency-bound motion-estimation kernels of one half overlap the issue-bound matching kernel of the other.
   // Off unless SF_OVERLAP=1 (+3-6 %).
@@ -379,7 +379,7 @@ struct sf_context {
   bool step_device_walk = true;            // SF_OPT_STEP_DEVICE_WALK: no host wait inside sf_step_issue
   uint64_t step_seq = 0;                   // steps issued so far (the next step's number)
   int step_inflight = 0;
-  // Where the pipeline's streams sit on the hardware (sf_api.hip: place_streams).  Measured once, at the first step that
+  // Where the pipeline's streams sit on the hardware (sf_placement.hip: place_streams).  Measured once, at the first step that
   // needs a second stream: a launch that does not fit on the chip keeps the dispatcher of its queue's PIPE busy until
   // its last workgroup is placed, and every other queue of that pipe waits -- so the lanes' main streams are picked
   // from candidates on different pipes and the second streams (short chains of small launches) from a pipe none of
@@ -432,7 +432,7 @@ struct UseWorkspace {
   UseWorkspace& operator=(const UseWorkspace&) = delete;
 };
 
-// ---- helpers implemented in sf_api.hip ---------------------------------------------------------
+// ---- helpers implemented in sf_handle.hip, sf_store.hip, sf_step.hip (the host files share more: sf_host.hpp) ----
 int sf_fail(sf_context* c, int code, const char* fmt, ...);
 // a database is about to change (SF_OPT_STEP_OVERLAP): `drain` also waits for the step in flight on the second stream
 int sf_lanes_touch(sf_context* c, bool drain);
@@ -544,7 +544,7 @@ int sf_nn_minima_of_candidates_dev(sf_context* c, const NnFilterOut& fo, double*
                                    int32_t* d_status, int32_t* d_row_cand, unsigned long long* d_arg64, bool throttle);
 int sf_nn_walk_host(sf_context* c, const double* row_min, const int32_t* row_arg, int n_l, int n_r, double thr,
                     int max_matches_nb, sf_match* out, int cap, int* n_out);
-// Speculation hook (sf_api.hip), called by the NN filter right behind the refinement launch of a prefix level:
+// Speculation hook (sf_step.hip), called by the NN filter right behind the refinement launch of a prefix level:
 // builds the candidate pair list on the device and queues the verification of every candidate.
 int sf_spec_launch(sf_context* c, const void* d_cand, const unsigned* d_count);
 int sf_nn_append(sf_context* c, NNDb& db, const void* src, int n, int dim, int src_kind);

@@ -1,0 +1,440 @@
+// sf_store.hip -- the device-resident keyframe store: wire layout -> store layout (k_ingest, k_ingest_ragged), growth,
+// the host-buffer ingest with its packing workers, the sf_store_* entry points.
+#include <atomic>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+
+#include "sf_host.hpp"
+
+StoreView sf_store_view(const Store& s) {
+  StoreView v;
+  v.desc = (const uint32_t*)s.desc.p;
+  v.xyz = (const float*)s.xyz.p;
+  v.kp = (const float4*)s.kp.p;
+  v.meta = (const int4*)s.meta.p;
+  v.kcap = s.kcap;
+  v.w = s.w;
+  v.n_slots = s.slots;
+  return v;
+}
+
+// ---- ingest kernel: wire layout -> store layout ---------------------------------------------------
+namespace {
+
+// one workgroup per keyframe.  desc rows are zero padded to w dwords; keypoints are reduced to
+// {x, y, sign-extended (octave & 255)} (myRegistrationVis.cpp:709-710 compares only that byte).
+__global__ void __launch_bounds__(SF_BLOCK)
+k_ingest(uint32_t* __restrict__ desc, float* __restrict__ xyz, float4* __restrict__ kp, int4* __restrict__ meta,
+         int kcap, int w, int first_slot, int rows, int cols, int n3d, const uint8_t* __restrict__ s_desc,
+         const float* __restrict__ s_xyz, const sf_keypoint* __restrict__ s_kp) {
+  const int k = blockIdx.x;
+  const int slot = first_slot + k;
+  const int tid = threadIdx.x;
+  uint8_t* d8 = reinterpret_cast<uint8_t*>(desc + (size_t)slot * kcap * w);
+  const uint8_t* sd = s_desc + (size_t)k * rows * cols;
+  const int rowb = w * 4;
+  for (int i = tid; i < rows * rowb; i += SF_BLOCK) {
+    const int r = i / rowb, b = i - r * rowb;
+    d8[i] = (b < cols) ? sd[(size_t)r * cols + b] : (uint8_t)0;
+  }
+  float* dx = xyz + (size_t)slot * kcap * 3;
+  if (n3d > 0) {
+    const float* sx = s_xyz + (size_t)k * rows * 3;
+    for (int i = tid; i < rows * 3; i += SF_BLOCK) dx[i] = sx[i];
+  }
+  float4* dk = kp + (size_t)slot * kcap;
+  const sf_keypoint* sk = s_kp + (size_t)k * rows;
+  for (int i = tid; i < rows; i += SF_BLOCK) {
+    const sf_keypoint q = sk[i];
+    int o = q.octave & 255;
+    o = o < 128 ? o : (-128 | o);
+    dk[i] = make_float4(q.x, q.y, __int_as_float(o), 0.f);
+  }
+  if (tid == 0) meta[slot] = make_int4(rows, n3d > 0 ? rows : 0, rows, cols);
+}
+
+// ragged variant for host-buffer batches: per-keyframe table of byte offsets into ONE packed
+// staging buffer.  The host packs each keyframe as [descriptors | xyz | keypoints reduced to
+// {x, y, raw octave} (12 of the wire's 28 bytes)], every part 16-byte aligned.
+struct IngestEntry {
+  int32_t rows, cols, n3d, pad;
+  uint64_t desc_off, xyz_off, kp_off;   // byte offsets from the start of the staging buffer
+};
+struct PackedKp { float x, y; int32_t octave; };
+
+__global__ void __launch_bounds__(SF_BLOCK)
+k_ingest_ragged(uint32_t* __restrict__ desc, float* __restrict__ xyz, float4* __restrict__ kp, int4* __restrict__ meta,
+                int kcap, int w, int first_slot, const IngestEntry* __restrict__ table,
+                const uint8_t* __restrict__ stage) {
+  const int k = blockIdx.x;
+  const int slot = first_slot + k;
+  const int tid = threadIdx.x;
+  const IngestEntry e = table[k];
+  const uint8_t* sd = stage + e.desc_off;
+  if ((e.cols & 3) == 0) {
+    // dword path (descriptor bytes a multiple of 4; rows start 16-byte aligned in the staging buffer)
+    uint32_t* d32 = desc + (size_t)slot * kcap * w;
+    const uint32_t* s32 = reinterpret_cast<const uint32_t*>(sd);
+    const int cw = e.cols >> 2;
+    for (int i = tid; i < e.rows * w; i += SF_BLOCK) {
+      const int r = i / w, b = i - r * w;
+      d32[i] = (b < cw) ? s32[(size_t)r * cw + b] : 0u;
+    }
+  } else {
+    uint8_t* d8 = reinterpret_cast<uint8_t*>(desc + (size_t)slot * kcap * w);
+    const int rowb = w * 4;
+    for (int i = tid; i < e.rows * rowb; i += SF_BLOCK) {
+      const int r = i / rowb, b = i - r * rowb;
+      d8[i] = (b < e.cols) ? sd[(size_t)r * e.cols + b] : (uint8_t)0;
+    }
+  }
+  if (e.n3d > 0) {
+    float* dx = xyz + (size_t)slot * kcap * 3;
+    const float* sx = reinterpret_cast<const float*>(stage + e.xyz_off);
+    for (int i = tid; i < e.rows * 3; i += SF_BLOCK) dx[i] = sx[i];
+  }
+  float4* dk = kp + (size_t)slot * kcap;
+  const PackedKp* sk = reinterpret_cast<const PackedKp*>(stage + e.kp_off);
+  for (int i = tid; i < e.rows; i += SF_BLOCK) {
+    const PackedKp q = sk[i];
+    int o = q.octave & 255;
+    o = o < 128 ? o : (-128 | o);
+    dk[i] = make_float4(q.x, q.y, __int_as_float(o), 0.f);
+  }
+  if (tid == 0) meta[slot] = make_int4(e.rows, e.n3d > 0 ? e.rows : 0, e.rows, e.cols);
+}
+
+}  // namespace
+
+// dwords per stored descriptor row: binary rows 8 (<= 256 bits) or 16; float32 rows (desc_type 1) one per dimension
+static int desc_dwords(const sf_context* c, int cols) {
+  if (c->params.desc_type == 1) return cols / 4;
+  return cols <= 32 ? 8 : 16;
+}
+
+int sf_store_reserve(sf_context* c, Store& s, int slots_needed, int rows, int cols) {
+  if (c->params.desc_type == 1) {
+    if (cols != 256 && cols != 512)
+      return sf_fail(c, SF_ERANGE, "float32 descriptors: %d bytes per row (64 or 128 dimensions = 256 or 512 bytes)", cols);
+  } else if (cols < 1 || cols > SF_MAX_DESC_BYTES) {
+    return sf_fail(c, SF_ERANGE, "descriptor bytes %d not in 1..%d", cols, SF_MAX_DESC_BYTES);
+  }
+  if (rows > SF_MAX_FEATURES) return sf_fail(c, SF_ERANGE, "rows %d > int16 limit of KeyPointVec.size", rows);
+  const int w = desc_dwords(c, cols);
+  int kcap = s.kcap ? s.kcap : std::max(64, (c->params.max_features + 63) & ~63);
+  while (kcap < rows) kcap *= 2;
+  if (kcap > SF_MAX_KCAP) return sf_fail(c, SF_ERANGE, "%d features per keyframe exceed the kernel capacity %d", rows, SF_MAX_KCAP);
+  if (s.slots > 0 && s.w != w) return sf_fail(c, SF_EINVAL, "descriptor width %d B differs from the store's (%d dwords)", cols, s.w);
+  int cap = s.cap_slots;
+  if (cap < slots_needed) cap = std::max(slots_needed, std::max(cap * 2, &s == &c->store ? c->params.store_capacity : 64));
+  if (&s == &c->store) (void)sf_lanes_touch(c, false);     // (a slot of the store is about to be written)
+  if (kcap == s.kcap && cap == s.cap_slots && s.w == w) return SF_OK;
+  if (&s == &c->store) (void)sf_lanes_touch(c, true);      // the old buffers are freed below: nothing may still read them
+  // (re)allocate; keep old contents slot by slot (pitch copy when kcap grew)
+  Store n;
+  n.kcap = kcap; n.w = w; n.cap_slots = cap; n.slots = s.slots;
+  int rc;
+  if ((rc = sf_buf_reserve(c, n.desc, (size_t)cap * kcap * w * 4)) != SF_OK ||
+      (rc = sf_buf_reserve(c, n.xyz, (size_t)cap * kcap * 12)) != SF_OK ||
+      (rc = sf_buf_reserve(c, n.kp, (size_t)cap * kcap * 16)) != SF_OK ||
+      (rc = sf_buf_reserve(c, n.meta, (size_t)cap * 16)) != SF_OK) {
+    sf_buf_free(n.desc); sf_buf_free(n.xyz); sf_buf_free(n.kp); sf_buf_free(n.meta);   // the old store stays valid
+    return rc;
+  }
+  if (s.slots > 0) {
+    SF_HIP(c, hipMemcpy2DAsync(n.desc.p, (size_t)kcap * w * 4, s.desc.p, (size_t)s.kcap * w * 4, (size_t)s.kcap * w * 4, s.slots, hipMemcpyDeviceToDevice, c->stream));
+    SF_HIP(c, hipMemcpy2DAsync(n.xyz.p, (size_t)kcap * 12, s.xyz.p, (size_t)s.kcap * 12, (size_t)s.kcap * 12, s.slots, hipMemcpyDeviceToDevice, c->stream));
+    SF_HIP(c, hipMemcpy2DAsync(n.kp.p, (size_t)kcap * 16, s.kp.p, (size_t)s.kcap * 16, (size_t)s.kcap * 16, s.slots, hipMemcpyDeviceToDevice, c->stream));
+    SF_HIP(c, hipMemcpyAsync(n.meta.p, s.meta.p, (size_t)s.slots * 16, hipMemcpyDeviceToDevice, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  sf_buf_free(s.desc); sf_buf_free(s.xyz); sf_buf_free(s.kp); sf_buf_free(s.meta);
+  s = n;
+  return SF_OK;
+}
+
+int sf_launch_ingest(sf_context* c, Store& st, int first_slot, int n, int rows, int cols,
+                     const uint8_t* d_desc, const float* d_xyz, const sf_keypoint* d_kp) {
+  if (n <= 0) return SF_OK;
+  hipLaunchKernelGGL(k_ingest, dim3(n), dim3(SF_BLOCK), 0, c->stream, (uint32_t*)st.desc.p, (float*)st.xyz.p,
+                     (float4*)st.kp.p, (int4*)st.meta.p, st.kcap, st.w, first_slot, rows, cols, d_xyz ? rows : 0,
+                     d_desc, d_xyz, d_kp);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+
+int sf_validate_features(sf_context* c, const sf_features* f) {
+  if (!f) return sf_fail(c, SF_EINVAL, "null sf_features");
+  if (f->rows > SF_MAX_FEATURES) return sf_fail(c, SF_ERANGE, "rows %d exceed int16", (int)f->rows);
+  if (f->rows > 0 && (!f->desc || f->cols == 0)) return sf_fail(c, SF_EINVAL, "descriptors missing");
+  if (f->n3d != 0 && f->n3d != (int32_t)f->rows)
+    return sf_fail(c, SF_EINVAL, "kpts3D size %d != descriptor rows %d (myRegistrationVis.cpp:859)", f->n3d, (int)f->rows);
+  if (f->nkp != (int32_t)f->rows)
+    return sf_fail(c, SF_EINVAL, "kpts size %d != descriptor rows %d (myRegistrationVis.cpp:879)", f->nkp, (int)f->rows);
+  if (f->n3d > 0 && !f->xyz) return sf_fail(c, SF_EINVAL, "kpts3D missing");
+  if (f->nkp > 0 && !f->kpts) return sf_fail(c, SF_EINVAL, "kpts missing");
+  return SF_OK;
+}
+
+// host features -> one store slot (staged through a device bounce buffer on the handle's stream)
+struct Staging {
+  Buf &desc, &xyz, &kp;
+};
+static Staging staging(sf_context* c) { return Staging{c->stage_desc, c->stage_xyz, c->stage_kp}; }
+
+static int store_add_host(sf_context* c, Store& st, const sf_features* f, int* out_slot) {
+  int rc = sf_validate_features(c, f);
+  if (rc != SF_OK) return rc;
+  const int rows = f->rows;
+  int cols = f->cols;
+  if (rows == 0 && cols == 0) cols = st.slots > 0 ? st.w * 4 : std::max(1, c->params.desc_bytes);
+  if ((rc = sf_store_reserve(c, st, st.slots + 1, rows, cols)) != SF_OK) return rc;
+  if (st.slots > 0 || rows > 0) {
+    // all keyframes of one store share the descriptor width class
+    if (st.w != desc_dwords(c, cols)) return sf_fail(c, SF_EINVAL, "descriptor width mismatch");
+  }
+  Staging sg = staging(c);
+  const uint8_t* dd = nullptr; const float* dx = nullptr; const sf_keypoint* dk = nullptr;
+  if (rows > 0) {
+    if ((rc = sf_buf_reserve(c, sg.desc, (size_t)rows * cols)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, sg.kp, (size_t)rows * sizeof(sf_keypoint))) != SF_OK) return rc;
+    SF_HIP(c, hipMemcpyAsync(sg.desc.p, f->desc, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
+    SF_HIP(c, hipMemcpyAsync(sg.kp.p, f->kpts, (size_t)rows * sizeof(sf_keypoint), hipMemcpyHostToDevice, c->stream));
+    dd = (const uint8_t*)sg.desc.p; dk = (const sf_keypoint*)sg.kp.p;
+    if (f->n3d > 0) {
+      if ((rc = sf_buf_reserve(c, sg.xyz, (size_t)rows * 12)) != SF_OK) return rc;
+      SF_HIP(c, hipMemcpyAsync(sg.xyz.p, f->xyz, (size_t)rows * 12, hipMemcpyHostToDevice, c->stream));
+      dx = (const float*)sg.xyz.p;
+    }
+  }
+  if ((rc = sf_launch_ingest(c, st, st.slots, 1, rows, cols, dd, dx, dk)) != SF_OK) return rc;
+  // the bounce buffers are reused by the next call: drain before returning
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  if (out_slot) *out_slot = st.slots;
+  st.slots += 1;
+  return SF_OK;
+}
+
+// n host keyframes -> consecutive slots.  Features are packed into ONE pinned staging buffer in
+// chunks of a few MB: worker threads pack chunk k+1 while the H2D copy of chunk k is in flight, then
+// ONE ragged ingest launch converts everything (no per-keyframe synchronisation).  Small batches
+// (a single service call) are packed inline by the calling thread.
+static inline size_t pad16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+static void pack_keyframe(uint8_t* hp, const IngestEntry& e, const sf_features* f) {
+  if (f->rows == 0) return;
+  memcpy(hp + e.desc_off, f->desc, (size_t)f->rows * f->cols);
+  if (f->n3d > 0) memcpy(hp + e.xyz_off, f->xyz, (size_t)f->rows * 12);
+  PackedKp* k = reinterpret_cast<PackedKp*>(hp + e.kp_off);
+  const sf_keypoint* src = f->kpts;
+  for (int i = 0; i < (int)f->rows; ++i) { k[i].x = src[i].x; k[i].y = src[i].y; k[i].octave = src[i].octave; }
+}
+
+
+// Packing workers of the host-buffer batch ingest: started once per handle (first large batch), parked on a
+// condition variable between batches, joined by sf_destroy.  A batch is cut into chunks; worker t packs the
+// keyframes lo + t, lo + t + workers, ... of every chunk in turn and bumps done[k]; the calling thread ships
+// chunk k to the device as soon as every worker has passed it.
+struct IngestPool {
+  std::vector<std::thread> threads;
+  std::mutex mu;
+  std::condition_variable cv_start, cv_idle;
+  uint64_t generation = 0;
+  int running = 0;
+  bool quit = false;
+  // the job of the current generation
+  uint8_t* hp = nullptr;
+  const IngestEntry* tab = nullptr;
+  const sf_features* const* feats = nullptr;
+  const std::pair<size_t, int>* chunks = nullptr;
+  int n_chunks = 0;
+  std::vector<std::atomic<int>> done;
+  std::vector<IngestEntry> tab_storage;
+  std::vector<std::pair<size_t, int>> chunk_storage;
+
+  explicit IngestPool(int workers) : done(0) {
+    for (int t = 0; t < workers; ++t) threads.emplace_back([this, t]() { work(t); });
+  }
+  ~IngestPool() {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      quit = true;
+    }
+    cv_start.notify_all();
+    for (auto& th : threads) th.join();
+  }
+  void work(int t) {
+    uint64_t seen = 0;
+    for (;;) {
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        cv_start.wait(lk, [&] { return quit || generation != seen; });
+        if (quit) return;
+        seen = generation;
+      }
+      const int nw = (int)threads.size();
+      int lo = 0;
+      for (int k = 0; k < n_chunks; ++k) {
+        const int hi = chunks[k].second;
+        for (int i = lo + t; i < hi; i += nw) pack_keyframe(hp, tab[i], feats[i]);
+        done[k].fetch_add(1, std::memory_order_release);
+        lo = hi;
+      }
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        if (--running == 0) cv_idle.notify_all();
+      }
+    }
+  }
+  void start() {
+    if ((int)done.size() < n_chunks) done = std::vector<std::atomic<int>>(n_chunks);
+    for (int k = 0; k < n_chunks; ++k) done[k].store(0, std::memory_order_relaxed);
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      running = (int)threads.size();
+      ++generation;
+    }
+    cv_start.notify_all();
+  }
+  void wait_idle() {
+    std::unique_lock<std::mutex> lk(mu);
+    cv_idle.wait(lk, [&] { return running == 0; });
+  }
+};
+
+void sf_ingest_pool_destroy(sf_context* c) {
+  delete c->ingest_pool;
+  c->ingest_pool = nullptr;
+}
+
+int sf_store_add_host_batch(sf_context* c, Store& st, const sf_features* const* feats, int n, int* first_slot) {
+  if (n <= 0) return SF_OK;
+  int rc;
+  int max_rows = 0, cols = 0;
+  for (int i = 0; i < n; ++i) {
+    if ((rc = sf_validate_features(c, feats[i])) != SF_OK) return rc;
+    max_rows = std::max<int>(max_rows, feats[i]->rows);
+    if (feats[i]->rows > 0) {
+      if (cols == 0) cols = feats[i]->cols;
+      if (desc_dwords(c, feats[i]->cols) != desc_dwords(c, cols)) return sf_fail(c, SF_EINVAL, "descriptor width classes differ inside one batch");
+      if (feats[i]->cols > (c->params.desc_type == 1 ? SF_MAX_DESC_BYTES_F32 : SF_MAX_DESC_BYTES))
+        return sf_fail(c, SF_ERANGE, "descriptor bytes %d > %d", (int)feats[i]->cols, c->params.desc_type == 1 ? SF_MAX_DESC_BYTES_F32 : SF_MAX_DESC_BYTES);
+    }
+  }
+  if (cols == 0) cols = st.slots > 0 ? st.w * 4 : std::max(1, c->params.desc_bytes);
+  if ((rc = sf_store_reserve(c, st, st.slots + n, max_rows, cols)) != SF_OK) return rc;
+
+  // layout: [table][keyframe 0: desc | xyz | kp][keyframe 1 ...], chunk boundaries every ~4 MB
+  // (table / chunk scratch lives in the pool object when there is one, else on this call's stack vectors)
+  std::vector<IngestEntry> tab_local;
+  std::vector<std::pair<size_t, int>> chunks_local;   // (end offset, end keyframe)
+  std::vector<IngestEntry>& tab = c->ingest_pool ? c->ingest_pool->tab_storage : tab_local;
+  std::vector<std::pair<size_t, int>>& chunks = c->ingest_pool ? c->ingest_pool->chunk_storage : chunks_local;
+  tab.resize(n);
+  chunks.clear();
+  const size_t tb = pad16((size_t)n * sizeof(IngestEntry));
+  const size_t chunk_bytes = (size_t)4 << 20;
+  size_t off = tb, chunk_start = tb;
+  for (int i = 0; i < n; ++i) {
+    const sf_features* f = feats[i];
+    IngestEntry& e = tab[i];
+    e.rows = f->rows; e.cols = f->rows > 0 ? f->cols : cols; e.n3d = f->n3d; e.pad = 0;
+    e.desc_off = off; off += pad16((size_t)f->rows * f->cols);
+    e.xyz_off = off;  off += f->n3d > 0 ? pad16((size_t)f->rows * 12) : 0;
+    e.kp_off = off;   off += pad16((size_t)f->rows * sizeof(PackedKp));
+    if (off - chunk_start >= chunk_bytes || i == n - 1) { chunks.push_back({off, i + 1}); chunk_start = off; }
+  }
+  const size_t total = off;
+  // pinned host staging owned by the handle (released by sf_destroy)
+  if (total > c->ingest_pinned_bytes) {
+    if (c->ingest_pinned) (void)hipHostFree(c->ingest_pinned);
+    c->ingest_pinned = nullptr;
+    c->ingest_pinned_bytes = 0;
+    const size_t want = total + total / 2;
+    hipError_t e = hipHostMalloc(&c->ingest_pinned, want, hipHostMallocDefault);
+    if (e != hipSuccess) return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) -> %s", want, hipGetErrorString(e));
+    c->ingest_pinned_bytes = want;
+  }
+  if ((rc = sf_buf_reserve(c, c->stage_desc, total)) != SF_OK) return rc;
+  uint8_t* hp = (uint8_t*)c->ingest_pinned;
+  uint8_t* dp = (uint8_t*)c->stage_desc.p;
+  memcpy(hp, tab.data(), (size_t)n * sizeof(IngestEntry));
+
+  const int n_chunks = (int)chunks.size();
+  int workers = 0;
+  if (n_chunks >= 2) workers = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency() / 2));
+  hipError_t herr = hipSuccess;
+  if (workers <= 1) {
+    for (int i = 0; i < n; ++i) pack_keyframe(hp, tab[i], feats[i]);
+    herr = hipMemcpyAsync(dp, hp, total, hipMemcpyHostToDevice, c->stream);
+  } else {
+    if (!c->ingest_pool) {
+      // first large batch of this handle: start the workers, and move the table / chunk lists into the pool
+      c->ingest_pool = new IngestPool(workers);
+      c->ingest_pool->tab_storage.swap(tab_local);
+      c->ingest_pool->chunk_storage.swap(chunks_local);
+    }
+    IngestPool& pool = *c->ingest_pool;
+    pool.hp = hp;
+    pool.tab = pool.tab_storage.data();
+    pool.feats = feats;
+    pool.chunks = pool.chunk_storage.data();
+    pool.n_chunks = n_chunks;
+    pool.start();
+    const int nw = (int)pool.threads.size();
+    size_t sent = 0;
+    for (int k = 0; k < n_chunks; ++k) {
+      while (pool.done[k].load(std::memory_order_acquire) < nw) std::this_thread::yield();
+      const size_t end = pool.chunk_storage[k].first;
+      if (herr == hipSuccess) herr = hipMemcpyAsync(dp + sent, hp + sent, end - sent, hipMemcpyHostToDevice, c->stream);
+      sent = end;
+    }
+    pool.wait_idle();
+  }
+  if (herr != hipSuccess) return sf_fail(c, SF_EHIP, "staging H2D copy -> %s", hipGetErrorString(herr));
+  hipLaunchKernelGGL(k_ingest_ragged, dim3(n), dim3(SF_BLOCK), 0, c->stream, (uint32_t*)st.desc.p, (float*)st.xyz.p,
+                     (float4*)st.kp.p, (int4*)st.meta.p, st.kcap, st.w, st.slots, (const IngestEntry*)dp, dp);
+  SF_HIP(c, hipGetLastError());
+  // the pinned staging is reused by the next call: the copies must have left host memory
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  if (first_slot) *first_slot = st.slots;
+  st.slots += n;
+  return SF_OK;
+}
+
+// ---- keyframe store -----------------------------------------------------------------------------
+extern "C" int sf_store_add_keyframe(sf_handle c, const sf_features* f, int32_t* out_slot) {
+  if (!c) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return store_add_host(c, c->store, f, out_slot);
+}
+
+extern "C" int sf_store_add_keyframes_device(sf_handle c, int32_t n, int32_t rows, int32_t cols,
+                                             const uint8_t* d_desc, const float* d_xyz,
+                                             const sf_keypoint* d_kp, int32_t* out_first_slot) {
+  if (!c || n < 0 || rows < 0) return SF_EINVAL;
+  if (n == 0) return SF_OK;
+  if (rows > 0 && (!d_desc || !d_kp)) return sf_fail(c, SF_EINVAL, "device descriptor / keypoint pointers missing");
+  SF_HIP(c, hipSetDevice(c->device));
+  int rc = sf_store_reserve(c, c->store, c->store.slots + n, rows, cols);
+  if (rc != SF_OK) return rc;
+  if ((rc = sf_launch_ingest(c, c->store, c->store.slots, n, rows, cols, d_desc, d_xyz, d_kp)) != SF_OK) return rc;
+  if (out_first_slot) *out_first_slot = c->store.slots;
+  c->store.slots += n;
+  return SF_OK;
+}
+
+extern "C" int sf_store_size(sf_handle c, int32_t* n_slots) {
+  if (!c || !n_slots) return SF_EINVAL;
+  *n_slots = c->store.slots;
+  return SF_OK;
+}
+
+extern "C" int sf_store_clear(sf_handle c) {
+  if (!c) return SF_EINVAL;
+  (void)sf_lanes_touch(c, true);
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  c->store.slots = 0;
+  return SF_OK;
+}

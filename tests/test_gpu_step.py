@@ -560,7 +560,7 @@ def test_step_result_carries_a_device_copy_of_the_records():
 
 def test_streams_of_the_step_pipeline_are_placed_by_measurement():
     """The step pipeline's streams are picked from candidates by measuring which of them dispatch beside each other
-    (sf_api.hip place_streams): the report says so once steps on several streams have run, names a class for every lane's
+    (sf_placement.hip place_streams): the report says so once steps on several streams have run, names a class for every lane's
     main stream, and the steps' bytes are the separate calls' -- also with the streams given in another order (a foreign
     stream used first shifts every later stream's hardware queue)."""
     n_kf, k, dim = 96, 200, 512
