@@ -518,11 +518,18 @@ __device__ __forceinline__ void knn2_mfma_tile(const uint32_t* fromD, int Kf, in
                                                uint32_t (&raw)[W / 2], const uint32_t*& nxt) {
   constexpr int KS = W / 2;
   // every tile starts from the SAME accumulator tuple (the MFMA reads it as its C operand: no copy).  The ragged last
-  // tile does too and masks its missing rows behind the products -- a second tuple with -inf in those rows was kept in
-  // 16 registers across the whole scan (hoisted out of the column-group loop) for the one tile that needs it.
+  // tile's copy has -inf in its missing rows (-inf + any finite product sum = -inf: the top-2 update never takes them,
+  // whatever the LDS words behind the staged block hold); it is made here, from the tuple's own values, for the one tile
+  // that needs it -- kept across the scan it cost 16 registers.
   mf_v16f c0;
 #pragma unroll
   for (int i = 0; i < 16; ++i) c0[i] = cin[i];
+  if (TAIL) {
+    // register i holds -(its row in the tile) / 2048: the row exists when that is above -(rows left) / 2048
+    const float lim = -(float)(Kf - mt * 32) * MF_FR;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) c0[i] = c0[i] > lim ? c0[i] : -INFINITY;
+  }
   mf_v8i Af[KS];
 #pragma unroll
   for (int k = 0; k < KS; ++k) Af[k] = fp4_spread_from(raw[k], m88, c22);
@@ -549,11 +556,6 @@ __device__ __forceinline__ void knn2_mfma_tile(const uint32_t* fromD, int Kf, in
 #pragma unroll
     for (int k = 1; k < KS; ++k)
       acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(Af[k], Bf[j][k], acc, 4, 4, 0, 0, 0, 0);
-    if (TAIL) {
-      const int left = Kf - mt * 32 - 4 * h;      // rows of this lane half that exist: register i holds row (i & 3) + 8 (i >> 2)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = ((i & 3) + 8 * (i >> 2) < left) ? acc[i] : -INFINITY;
-    }
     top2_update16(acc, b[j], s[j]);
   }
 }
@@ -564,10 +566,13 @@ __device__ __forceinline__ void knn2_mfma_tile(const uint32_t* fromD, int Kf, in
 template <int W, int NTL>
 struct MfB {
   mf_v8i Bf[NTL][W / 2];
-  int tsum[NTL];
+  uint32_t psum;   // popc(row & 0x7777...) of the NTL tiles' columns, 8 bits per tile (NTL == 1: the whole word)
 };
 
-// Loads and spreads the "to" rows of the tiles tile[0..NTL) (a tile past the frame's rows is empty).
+// Loads and spreads the "to" rows of the tiles tile[0..NTL); Kt >= 1.  A column past the frame's rows holds the
+// frame's last row: its scores are computed and never read (the callers decide for columns < Kt only), which costs
+// nothing and spares the branch around the load.  All tiles' loads are issued before the first is waited for: one
+// HBM round trip per group instead of one per tile.
 template <int W, int NTL>
 __device__ __forceinline__ void mf_load_b(const uint32_t* __restrict__ dT, int Kt, const int (&tile)[NTL], int lane,
                                           MfB<W, NTL>& B) {
@@ -576,22 +581,24 @@ __device__ __forceinline__ void mf_load_b(const uint32_t* __restrict__ dT, int K
   uint32_t m88, c22;   // constants pinned in VGPRs (see fp4_spread)
   asm volatile("v_mov_b32 %0, 0x88888888" : "=v"(m88));
   asm volatile("v_mov_b32 %0, 0x22222222" : "=v"(c22));
+  uint32_t raw[NTL][KS];
+#pragma unroll
+  for (int j = 0; j < NTL; ++j) load_raw<KS>(dT + (size_t)min(tile[j] * 32 + r, Kt - 1) * W + KS * h, raw[j]);
+  // the columns' constants (see fp4_spread_from) travel as their popcounts, one byte per tile: one register across the
+  // scan and one exchange between the row halves instead of NTL of each
+  static_assert(NTL == 1 || 24 * W < 256, "a tile's popcount fits its byte");
+  uint32_t pk = 0;
 #pragma unroll
   for (int j = 0; j < NTL; ++j) {
-    const int t = tile[j] * 32 + r;
-    uint32_t raw[KS];
-#pragma unroll
-    for (int k = 0; k < KS; ++k) raw[k] = 0;
-    if (t < Kt) load_raw<KS>(dT + (size_t)t * W + KS * h, raw);
-    int p = 0;
+    uint32_t p = 0;
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
-      B.Bf[j][k] = fp4_spread_to(raw[k], m88, c22);
-      p += __popc(raw[k] & 0x77777777u);
+      B.Bf[j][k] = fp4_spread_to(raw[j][k], m88, c22);
+      p += __popc(raw[j][k] & 0x77777777u);
     }
-    p += __shfl_xor(p, 32);                 // both halves of the row
-    B.tsum[j] = 24 * W - 2 * p;             // the column's constant (see fp4_spread_from)
+    pk |= p << (8 * j);
   }
+  B.psum = pk + __shfl_xor(pk, 32);         // both halves of the row
 }
 
 // ---- round 5: the scan software-pipelined inside a wavefront (256-bit descriptors) -------------------------------------
@@ -696,14 +703,18 @@ __device__ __forceinline__ void mf_pipe_drain(const mf_v16f& old, float& b, floa
         [o12] "v"(old[12]), [o13] "v"(old[13]), [o14] "v"(old[14]), [o15] "v"(old[15]));
 }
 
-// the full "from" tiles of a scan in the pipelined form (W = 8, NTL even: tile j writes tuple j & 1 and consumes the other)
+// all "from" tiles of a scan in the pipelined form (W = 8, NTL even: tile j writes tuple j & 1 and consumes the other).
+// The ragged last tile (Kf & 31 rows) goes through the same statements as a peeled last iteration: its missing rows are
+// masked in the ORIGIN tuple (-inf + any finite product sum = -inf, so the top-2 update never takes them, whatever the
+// LDS words behind the staged block hold), 16 selects per "from" tile instead of 16 per column tile behind the
+// products.  The origin tuple is dead after the last tile, so it is masked in place: no second tuple lives across the
+// scan (docs/notebook_r05.md section 13 lost to that one's scratch).  `tail` = Kf & 31 (wave-uniform).
 template <int NTL>
-__device__ __forceinline__ void mf_scan_full_tiles_pipe(const uint32_t* fromD, int n_full, const MfB<8, NTL>& B,
-                                                        const float (&cin)[16], float (&b)[NTL], float (&s)[NTL],
-                                                        uint32_t m88, uint32_t c22, uint32_t (&raw)[4],
-                                                        const uint32_t*& nxt) {
+__device__ __forceinline__ void mf_scan_tiles_pipe(const uint32_t* fromD, int n_full, int tail, const MfB<8, NTL>& B,
+                                                   const float (&cin)[16], float (&b)[NTL], float (&s)[NTL],
+                                                   uint32_t m88, uint32_t c22, uint32_t (&raw)[4],
+                                                   const uint32_t*& nxt) {
   static_assert(NTL == 2 || NTL == 4, "tiles alternate between two accumulator tuples");
-  if (n_full <= 0) return;
   mf_v4i B4[NTL][4];
 #pragma unroll
   for (int j = 0; j < NTL; ++j) {
@@ -713,42 +724,87 @@ __device__ __forceinline__ void mf_scan_full_tiles_pipe(const uint32_t* fromD, i
   mf_v16f c0, acc0, acc1;
 #pragma unroll
   for (int i = 0; i < 16; ++i) { c0[i] = cin[i]; acc1[i] = -INFINITY; }     // nothing pending: an update that changes nothing
-  for (int mt = 0; mt < n_full; ++mt) {
-    mf_v4i A4[4];
+  // two passes over ONE loop body: the full tiles, then the ragged tile with its missing rows masked in the origin tuple
+#pragma unroll 1
+  for (int pass = 0; pass < 2; ++pass) {
+    int n = n_full, step = 32 * 8;       // words to the next tile's rows; the ragged tile has none behind it
+    if (pass) {
+      if (!tail) break;
+      // register i holds -(its row in the tile) / 2048: the row exists when that is above -tail / 2048 (exact in f32).
+      // Compared as floats against the tuple itself, so that the 16 masks are made here and not kept in 32 scalar
+      // registers across the kernel.  The selects are compiler code: the wait states of a VALU-written C operand are
+      // the ones the A operands need anyway (s_nop 1 opens mf_pipe_half1).
+      const float lim = -(float)tail * MF_FR;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const mf_v8i a = fp4_spread_from(raw[k], m88, c22);
-      A4[k] = mf_v4i{a[0], a[1], a[2], a[3]};
+      for (int i = 0; i < 16; ++i) c0[i] = c0[i] > lim ? c0[i] : -INFINITY;
+      n = 1; step = 0;
     }
-    nxt += 32 * 8;                       // the next tile's rows (see knn2_mfma_tile)
-    load_raw<4>(nxt, raw);
+    for (int mt = 0; mt < n; ++mt) {
+      mf_v4i A4[4];
 #pragma unroll
-    for (int j = 0; j < NTL; j += 2) {
-      constexpr int JP = NTL - 1;        // tile 0 consumes the LAST tile of the previous "from" tile
-      float x0, ta, tb;
-      const int jp = j == 0 ? JP : j - 1;
-      mf_pipe_half1(acc0, A4[0], A4[1], A4[2], A4[3], B4[j][0], B4[j][1], c0, acc1, b[jp], s[jp], x0, ta, tb);
-      mf_pipe_half2(acc0, A4[2], A4[3], B4[j][2], B4[j][3], acc1, b[jp], s[jp], ta, tb);
-      mf_pipe_half1(acc1, A4[0], A4[1], A4[2], A4[3], B4[j + 1][0], B4[j + 1][1], c0, acc0, b[j], s[j], x0, ta, tb);
-      mf_pipe_half2(acc1, A4[2], A4[3], B4[j + 1][2], B4[j + 1][3], acc0, b[j], s[j], ta, tb);
+      for (int k = 0; k < 4; ++k) {
+        const mf_v8i a = fp4_spread_from(raw[k], m88, c22);
+        A4[k] = mf_v4i{a[0], a[1], a[2], a[3]};
+      }
+      nxt += step;                       // the next tile's rows (see knn2_mfma_tile)
+      load_raw<4>(nxt, raw);
+#pragma unroll
+      for (int j = 0; j < NTL; j += 2) {
+        constexpr int JP = NTL - 1;      // tile 0 consumes the LAST tile of the previous "from" tile
+        float x0, ta, tb;
+        const int jp = j == 0 ? JP : j - 1;
+        mf_pipe_half1(acc0, A4[0], A4[1], A4[2], A4[3], B4[j][0], B4[j][1], c0, acc1, b[jp], s[jp], x0, ta, tb);
+        mf_pipe_half2(acc0, A4[2], A4[3], B4[j][2], B4[j][3], acc1, b[jp], s[jp], ta, tb);
+        mf_pipe_half1(acc1, A4[0], A4[1], A4[2], A4[3], B4[j + 1][0], B4[j + 1][1], c0, acc0, b[j], s[j], x0, ta, tb);
+        mf_pipe_half2(acc1, A4[2], A4[3], B4[j + 1][2], B4[j + 1][3], acc0, b[j], s[j], ta, tb);
+      }
     }
   }
   mf_pipe_drain(acc1, b[NTL - 1], s[NTL - 1]);
 }
 
-// kNN-2 of the resident "to" columns over all "from" rows; on return lanes 0..31 hold, for column tile[j] * 32 + lane:
-// d1 / d2 (Hamming, 0xFFFF when absent) and the from index of d1.
+// v_max_f32 / v_min_f32 / v_max3_f32 as they are: fmaxf() and fminf() put a canonicalising self-max in front of every
+// operand the compiler cannot prove quiet, and the scores are never NaN.
+__device__ __forceinline__ float mf_max(float a, float b) {
+  float r;
+  asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float mf_min(float a, float b) {
+  float r;
+  asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ __forceinline__ float mf_max3(float a, float b, float c) {
+  float r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
+// decode passes of a scan over NTL column tiles: a pass decides two tiles, one per lane half
+constexpr int mf_passes(int ntl) { return ntl == 1 ? 1 : ntl / 2; }
+
+// kNN-2 of the resident "to" columns over all "from" rows.  On return, NTL == 1: lanes 0..31 hold, for column
+// tile[0] * 32 + lane, d1 / d2 (Hamming, 0xFFFF when absent) and the from index of d1.  NTL even: in pass p ALL lanes
+// hold them, for column tile[2 p + (lane >> 5)] * 32 + (lane & 31) -- a column's scores live in lanes r and r + 32 (one
+// half of a tile's rows each), so each half sends the other the tile that one decodes: one exchange per value and pass,
+// one decode for two tiles.
 template <int W, int NTL, bool PIPE = false>
 __device__ __forceinline__ void mf_scan(const uint32_t* fromD, int Kf, const MfB<W, NTL>& B, int lane,
-                                        uint32_t (&d1)[NTL], uint32_t (&d2)[NTL], int (&idx)[NTL]) {
+                                        uint32_t (&d1)[mf_passes(NTL)], uint32_t (&d2)[mf_passes(NTL)],
+                                        int (&idx)[mf_passes(NTL)]) {
   constexpr int KS = W / 2;
   const int r = lane & 31, h = lane >> 5;
   uint32_t m88, c22;
   asm volatile("v_mov_b32 %0, 0x88888888" : "=v"(m88));
   asm volatile("v_mov_b32 %0, 0x22222222" : "=v"(c22));
   float cin[16], b[NTL], s[NTL];
+  // the origin tuple is rebuilt by every scan (16 subtractions; knn2_mfma made `lane` opaque): hoisted out of the
+  // column-group loop it would have to survive the in-place masking of the ragged tile as a second tuple
+  // (mf_scan_tiles_pipe)
+  const float hoff = h ? 4.f * MF_FR : 0.f;
 #pragma unroll
-  for (int i = 0; i < 16; ++i) cin[i] = -(float)((i & 3) + 8 * (i >> 2) + 4 * h) * MF_FR;
+  for (int i = 0; i < 16; ++i) cin[i] = -(float)((i & 3) + 8 * (i >> 2)) * MF_FR - hoff;   // a literal minus 4 h / 2048: exact
 #pragma unroll
   for (int j = 0; j < NTL; ++j) { b[j] = -INFINITY; s[j] = -INFINITY; }
   const int n_full = Kf >> 5;
@@ -756,28 +812,40 @@ __device__ __forceinline__ void mf_scan(const uint32_t* fromD, int Kf, const MfB
   load_raw<KS>(fromD + (size_t)min(r, Kf - 1) * W + KS * h, raw);
   const uint32_t* nxt = fromD + (size_t)r * W + KS * h;
   if constexpr (PIPE && W == 8 && (NTL == 2 || NTL == 4)) {
-    mf_scan_full_tiles_pipe<NTL>(fromD, n_full, B, cin, b, s, m88, c22, raw, nxt);
+    mf_scan_tiles_pipe<NTL>(fromD, n_full, Kf & 31, B, cin, b, s, m88, c22, raw, nxt);
   } else {
     for (int mt = 0; mt < n_full; ++mt) knn2_mfma_tile<W, NTL, false>(fromD, Kf, mt, r, h, B.Bf, cin, b, s, m88, c22, raw, nxt);
+    if (Kf & 31) knn2_mfma_tile<W, NTL, true>(fromD, Kf, n_full, r, h, B.Bf, cin, b, s, m88, c22, raw, nxt);
   }
-  if (Kf & 31) knn2_mfma_tile<W, NTL, true>(fromD, Kf, n_full, r, h, B.Bf, cin, b, s, m88, c22, raw, nxt);
   const float org = (float)(32 * (((Kf + 31) >> 5) - 1)) * MF_FR;
 #pragma unroll
-  for (int j = 0; j < NTL; ++j) {
-    const float ob = __shfl_xor(b[j], 32), os = __shfl_xor(s[j], 32);
-    const float nb = fmaxf(b[j], ob) - org;
-    const float ns = fmaxf(fminf(b[j], ob), fmaxf(s[j], os)) - org;
+  for (int p = 0; p < mf_passes(NTL); ++p) {
+    float mb, ms, ob, os;      // this lane's half of the column's rows, the other half's
+    int ts;                    // the column's constant
+    if constexpr (NTL == 1) {
+      mb = b[0]; ms = s[0]; ts = 24 * W - 2 * (int)B.psum;
+      ob = __shfl_xor(mb, 32); os = __shfl_xor(ms, 32);
+    } else {
+      const int j0 = 2 * p, j1 = 2 * p + 1;
+      mb = h ? b[j1] : b[j0]; ms = h ? s[j1] : s[j0]; ts = 24 * W - 2 * (int)((B.psum >> (16 * p + 8 * h)) & 0xFFu);
+      ob = __shfl_xor(h ? b[j0] : b[j1], 32); os = __shfl_xor(h ? s[j0] : s[j1], 32);
+    }
+    const float nb = mf_max(mb, ob) - org;
+    const float ns = mf_max3(mf_min(mb, ob), ms, os) - org;
     const float dot1 = 2.f * ceilf(nb * 0.5f), dot2 = 2.f * ceilf(ns * 0.5f);
-    idx[j] = (int)((dot1 - nb) * 2048.f);
-    d1[j] = (uint32_t)((32 * W - B.tsum[j] - (int)dot1) >> 1);
-    d2[j] = ns == -INFINITY ? 0xFFFFu : (uint32_t)((32 * W - B.tsum[j] - (int)dot2) >> 1);
+    idx[p] = (int)((dot1 - nb) * 2048.f);
+    d1[p] = (uint32_t)((32 * W - ts - (int)dot1) >> 1);
+    d2[p] = ns == -INFINITY ? 0xFFFFu : (uint32_t)((32 * W - ts - (int)dot2) >> 1);
   }
 }
 
 template <int W, int NTL, bool PIPE = false>
 __device__ __forceinline__ void knn2_mfma(const uint32_t* fromD, int Kf, const uint32_t* __restrict__ dT, int Kt,
-                                          const int (&tile)[NTL], int lane, uint32_t (&d1)[NTL], uint32_t (&d2)[NTL],
-                                          int (&idx)[NTL]) {
+                                          const int (&tile)[NTL], int lane, uint32_t (&d1)[mf_passes(NTL)],
+                                          uint32_t (&d2)[mf_passes(NTL)], int (&idx)[mf_passes(NTL)]) {
+  // what a scan derives from the lane number (row, lane half, LDS addresses) is derived again by every scan: kept across
+  // the column-group loop it would sit in registers that the scan itself is short of, i.e. in scratch
+  asm volatile("" : "+v"(lane));
   MfB<W, NTL> B;
   mf_load_b<W, NTL>(dT, Kt, tile, lane, B);
   mf_scan<W, NTL, PIPE>(fromD, Kf, B, lane, d1, d2, idx);
@@ -796,7 +864,9 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
                                               unsigned long long* trace_row = nullptr) {
   constexpr int NW = NT / 64;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  // the wavefront's number as a scalar: the loop over its column groups is then scalar control flow, not a divergent
+  // loop under exec masks with its counters in vector registers
+  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kcap = st.kcap;
   if ((unsigned)sF >= (unsigned)st.n_slots || (unsigned)sT >= (unsigned)st.n_slots) {
     if (tid == 0) {
@@ -845,31 +915,35 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
       // a wavefront owns tiles wave, wave + NW, ...; it scans them in groups of up to NTL (a group that is
       // short of tiles drops to the next smaller instantiation; a 3-tile group runs as 4 with an empty tile)
       auto group = [&](auto g, int t0) {
-        constexpr int G = decltype(g)::value;
-        int tl[G], f[G];
-        uint32_t a1[G], a2[G];
+        constexpr int G = decltype(g)::value, NP = mf_passes(G);
+        int tl[G], f[NP];
+        uint32_t a1[NP], a2[NP];
 #pragma unroll
         for (int j = 0; j < G; ++j) tl[j] = t0 + j * NW;
         knn2_mfma<W, G, MF_PIPE>(fromD, Kf, dT, Kt, tl, lane, a1, a2, f);
+        // a pass decides the columns of two tiles, one per lane half (mf_scan); `rejected` counts lanes, so it is a
+        // wave-uniform sum of ballots, not a per-lane counter to be reduced
 #pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const int t = tl[j] * 32 + lane;
-          if (lane < 32 && t < Kt) {
-            const bool acc = (Kf >= 2) && !((float)a1[j] > nndr * (float)a2[j]);
-            if (acc) {
-              atomicAdd(&cnt[f[j]], 1);
-              owner[f[j]] = t;
-            } else {
-              ++rejected;
-            }
+        for (int p = 0; p < NP; ++p) {
+          const int t = G == 1 ? tl[0] * 32 + lane : (tl[2 * p] + (lane >> 5) * NW) * 32 + (lane & 31);
+          const bool on = (G > 1 || lane < 32) && t < Kt;
+          const bool acc = (Kf >= 2) && !((float)a1[p] > nndr * (float)a2[p]);
+          if (on && acc) {
+            atomicAdd(&cnt[f[p]], 1);
+            owner[f[p]] = t;
           }
+          rejected += __popcll(__ballot(on && !acc));
         }
       };
       for (int t0 = wave; t0 < n_nt; t0 += NW * NTL) {
         const int avail = (n_nt - t0 + NW - 1) / NW;
-        if (NTL >= 4 && avail >= 3) group(std::integral_constant<int, 4>{}, t0);
-        else if (NTL >= 2 && avail >= 2) group(std::integral_constant<int, 2>{}, t0);
-        else group(std::integral_constant<int, 1>{}, t0);
+        if constexpr (NTL >= 4) {
+          if (avail >= 3) { group(std::integral_constant<int, 4>{}, t0); continue; }
+        }
+        if constexpr (NTL >= 2) {
+          if (avail >= 2) { group(std::integral_constant<int, 2>{}, t0); continue; }
+        }
+        group(std::integral_constant<int, 1>{}, t0);
       }
     }
   } else if (Kf > 0) {
@@ -926,7 +1000,9 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
       }
     }
   }
-  for (int off = 32; off >= 1; off >>= 1) rejected += __shfl_xor(rejected, off);
+  if constexpr (NQ != 0) {   // (the matrix-core path counted whole wavefronts)
+    for (int off = 32; off >= 1; off >>= 1) rejected += __shfl_xor(rejected, off);
+  }
   if (lane == 0 && rejected) atomicAdd(&misc[0], rejected);
   SF_TRACE_ROW_MARK(trace_row, 33);   // wavefront 0 done with its scans
   __syncthreads();

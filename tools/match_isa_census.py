@@ -1,0 +1,301 @@
+#!/usr/bin/env python3
+"""Static instruction census of the matcher's stage kernel, k_match_split<8, 4, 3>, made without a GPU.
+
+Compiles k_verify.hip to gfx950 assembly with the product flags (csrc/Makefile: COMMON + CANON, as tools/pk_isa_scan.py
+does), cuts the kernel into the regions a wavefront walks through and prints, per region, its vector (VALU, MFMA), scalar,
+LDS and memory instructions, then the modelled vector instructions of ONE wavefront for frames of K = 500, 512 and 1 000
+features on both sides.  The kernel is bound by vector instruction issue, so this count is its cost.
+
+The regions are found from the instruction stream, not from label numbers:
+  * basic blocks are cut at labels and behind branches; a block that branches to itself and holds MFMAs is a scan loop,
+    the one with 16 MFMAs is the scan of a 4-tile column group (the only groups a wavefront runs at these K);
+  * a group's region is what the topmost block dominates that dominates this loop alone and is itself neither a scan nor
+    a decode (v_ceil_f32) nor a claim (ds_add); inside it: in front of the loop (the "to" tiles loaded and spread, the
+    origin tuple), the loop, what lies on a cycle through the loop (the ragged tile as a second pass), what follows it
+    (blocks with MFMAs there = an unpipelined ragged tile; the rest = drain, decode, NNDR, claims);
+  * the two barriers in front of and behind the scans cut the rest: prologue + staging, scan set-up, the loop over a
+    wavefront's groups, the hand-over of the rejected count, the list compaction and the header.
+Loop bodies other than the scan loop are counted once.  The model adds up what every wavefront of a pair issues; what only
+lane 0 of the workgroup runs behind the compaction (header, pass state, the result of a pair that has no estimate) and
+the paths taken by few pairs are listed and left out of it.
+  tools/match_isa_census.py [--asm FILE] [--json]
+--asm: read an assembly file made before (the parent commit's, say) instead of compiling."""
+import argparse, collections, json, os, re, subprocess, sys, tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "multi_robot_slam_separators_amd", "csrc")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-function", "-Wno-pass-failed",
+         "-fno-slp-vectorize", "-ffp-contract=off", "-fno-vectorize"]
+SPLIT = "13k_match_splitILi8ELi4ELi3EE"
+FUSED = "14k_verify_fusedILi8ELi0ELb0EE"
+KINDS = ("valu", "mfma", "salu", "lds", "vmem")
+
+
+def compile_asm(path):
+    subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + ["-S", "--cuda-device-only", os.path.join(CSRC, "k_verify.hip"), "-o", path],
+                   check=True, stderr=subprocess.DEVNULL)
+
+
+def kind(op):
+    if op.startswith("v_mfma"):
+        return "mfma"
+    if op.startswith("v_"):
+        return "valu"
+    if op.startswith("ds_"):
+        return "lds"
+    if op.startswith(("global_", "buffer_", "flat_", "scratch_")):
+        return "vmem"
+    if op.startswith("s_"):
+        return "salu"
+    return None
+
+
+def function_lines(lines, tag):
+    """The instruction and label lines of the kernel whose mangled name holds `tag`."""
+    out, on = [], False
+    for ln in lines:
+        if re.match(r"^_Z\w+:", ln):
+            on = tag in ln
+            continue
+        if on:
+            if ln.startswith(".Lfunc_end"):
+                break
+            out.append(ln.rstrip("\n"))
+    if not out:
+        sys.exit("kernel %s not found in the assembly" % tag)
+    return out
+
+
+def resources(lines, tag):
+    """Registers, scratch and occupancy the compiler reports for the kernel."""
+    r, seen = {}, False
+    for ln in lines:                 # the "; Kernel info:" comments behind the kernel's descriptor hold the final figures
+        if ln.startswith("\t.amdhsa_kernel"):
+            seen = tag in ln
+        m = re.match(r"; (NumVgprs|ScratchSize|Occupancy): (\d+)", ln)
+        if m and seen:
+            r[m.group(1)] = int(m.group(2))
+            seen = m.group(1) != "Occupancy"
+    if len(r) != 3:
+        sys.exit("kernel info of %s not found in the assembly" % tag)
+    return {"vgprs": r["NumVgprs"], "scratch_bytes": r["ScratchSize"], "occupancy": r["Occupancy"]}
+
+
+class Block:
+    def __init__(self, name):
+        self.name, self.ins, self.succ, self.falls = name, [], [], True
+
+    def count(self, ins=None):
+        c = collections.Counter()
+        for op in (self.ins if ins is None else ins):
+            k = kind(op)
+            if k:
+                c[k] += 1
+        return c
+
+    def has(self, prefix):
+        return any(op.startswith(prefix) for op in self.ins)
+
+
+def blocks_of(fn):
+    blocks, cur, n = [], Block("entry"), 0
+    blocks.append(cur)
+    for ln in fn:
+        m = re.match(r"^(\.LBB\w+):", ln)
+        if m:
+            cur = Block(m.group(1))
+            blocks.append(cur)
+            continue
+        t = ln.strip()
+        if not ln.startswith("\t") or t.startswith((".", ";")):
+            continue
+        toks = t.split()
+        op = toks[0]
+        cur.ins.append(op)
+        if op.startswith(("s_cbranch", "s_branch", "s_endpgm", "s_setpc")):
+            if op.startswith(("s_cbranch", "s_branch")):
+                cur.succ.append(toks[1])
+            cur.falls = op.startswith("s_cbranch")
+            n += 1
+            cur = Block("%s+%d" % (blocks[-1].name.split("+")[0], n))       # the fall-through behind a branch
+            cur_prev = blocks[-1]
+            blocks.append(cur)
+            if cur_prev.falls:
+                cur_prev.succ.append(cur.name)
+    for i, b in enumerate(blocks):                                          # a block that runs into the next label
+        if b.falls and i + 1 < len(blocks) and blocks[i + 1].name not in b.succ and not (b.ins and b.ins[-1].startswith("s_cbranch")):
+            if not b.ins or not b.ins[-1].startswith(("s_branch", "s_endpgm", "s_setpc")):
+                b.succ.append(blocks[i + 1].name)
+    return blocks
+
+
+def reach(start, succ, allowed=None, skip=()):
+    seen, todo = set(), list(start)
+    while todo:
+        x = todo.pop()
+        for y in succ.get(x, ()):
+            if y in seen or y in skip or (allowed is not None and y not in allowed):
+                continue
+            seen.add(y)
+            todo.append(y)
+    return seen
+
+
+def dominators(names, succ, entry):
+    pred = collections.defaultdict(set)
+    for a in names:
+        for b in succ[a]:
+            pred[b].add(a)
+    live = reach([entry], succ) | {entry}
+    dom = {n: set(live) for n in live}
+    dom[entry] = {entry}
+    changed = True
+    while changed:
+        changed = False
+        for n in names:
+            if n not in live or n == entry:
+                continue
+            ps = [dom[p] for p in pred[n] if p in live]
+            new = set.intersection(*ps) | {n} if ps else {n}
+            if new != dom[n]:
+                dom[n], changed = new, True
+    return dom, live
+
+
+def census(fn):
+    blocks = blocks_of(fn)
+    by = {b.name: b for b in blocks}
+    names = [b.name for b in blocks]
+    succ = {b.name: [s for s in b.succ if s in by] for b in blocks}
+    back = collections.defaultdict(set)
+    for a in names:
+        for b in succ[a]:
+            back[b].add(a)
+    dom, live = dominators(names, succ, "entry")
+    scans = [n for n in names if n in live and n in succ[n] and by[n].has("v_mfma")]
+    scan4 = [n for n in scans if by[n].count()["mfma"] == 16]
+    if len(scan4) != 1:
+        sys.exit("expected one scan loop with 16 MFMAs, found %d" % len(scan4))
+    scan4 = scan4[0]
+    dominated = lambda d: set(n for n in live if d in dom[n])
+
+    def region_of(loop):
+        head, cand = loop, loop
+        while True:
+            ups = [d for d in dom[cand] if d != cand and dom[d] == dom[cand] - {cand}]      # the immediate dominator
+            if not ups:
+                break
+            cand = ups[0]
+            b = by[cand]
+            if b.has("v_mfma") or b.has("v_ceil_f32") or b.has("ds_add") or any(s != loop and s in dominated(cand) for s in scans):
+                break
+            head = cand
+        return head, dominated(head)
+
+    regions = {s: region_of(s) for s in scans}
+    head4, reg4 = regions[scan4]
+    in_groups = set().union(*[r for _, r in regions.values()])
+    inner = {n: [s for s in succ[n] if s in reg4 and s != head4] for n in reg4}
+    inner_back = collections.defaultdict(list)
+    for a, ss in inner.items():
+        for b in ss:
+            inner_back[b].append(a)
+    after_loop = reach([scan4], inner) - {scan4}
+    before_loop = reach([scan4], inner_back) - {scan4}
+    cyc = after_loop & before_loop
+    pre = (before_loop | {head4}) - cyc - {scan4}
+    post = after_loop - cyc
+    ragged = set(n for n in post if by[n].has("v_mfma"))
+    # the rest of the kernel, cut at its first two barriers that lie outside the groups
+    bars = [n for n in names if n in live and by[n].has("s_barrier") and n not in in_groups]
+    if len(bars) < 2:
+        sys.exit("expected a barrier in front of and one behind the scans")
+    bar1, bar2 = bars[0], bars[1]
+    reaches_scan = reach(scans, back) | set(scans)
+    from_scan = reach(scans, succ)
+    dispatch = (reaches_scan & from_scan) - in_groups
+    front = set(n for n in live if n in reaches_scan and n not in from_scan and n not in in_groups)
+    to_bar1 = (reach([bar1], back) | {bar1}) & front
+    setup = front - to_bar1
+    behind = set(n for n in live if n in from_scan and n not in reaches_scan and n not in in_groups)
+    to_bar2 = (reach([bar2], back) | {bar2}) & behind
+    # behind the second barrier: the compaction loop runs up to the last barrier; what follows is lane 0's (header, pass
+    # state, the result of a pair without an estimate) or runs for few pairs (the count of finite points), and so do the
+    # blocks no scan leads to (a pair whose slots do not exist)
+    to_last = (reach([bars[-1]], back) | {bars[-1]}) & (behind - to_bar2)
+    rest = set(n for n in live if n not in reaches_scan and n not in from_scan) | (behind - to_bar2 - to_last)
+
+    def cut(name, first):            # a barrier block's instructions in front of / behind its first barrier
+        ins = by[name].ins
+        i = next(k for k, op in enumerate(ins) if op.startswith("s_barrier"))
+        return ins[:i + 1] if first else ins[i + 1:]
+
+    def total(bs, extra=()):
+        c = collections.Counter()
+        for n in bs:
+            c += by[n].count()
+        for ins in extra:
+            c += Block("").count(ins)
+        return c
+
+    rows = collections.OrderedDict()
+    rows["prologue + staging of the \"from\" block (loop bodies once)"] = total(to_bar1 - {bar1}, [cut(bar1, True)])
+    rows["scan set-up in front of the groups"] = total(setup, [cut(bar1, False)])
+    rows["loop over a wavefront's groups (per group)"] = total(dispatch)
+    rows["4-tile group: \"to\" tiles loaded and spread, origin tuple"] = total(pre)
+    rows["full-tile loop body (per 32 \"from\" rows)"] = total([scan4])
+    tail = total(ragged) + total(cyc) + (total([scan4]) if cyc and not ragged else collections.Counter())
+    rows["ragged last tile%s" % (" (second pass over the loop body)" if cyc and not ragged else "")] = tail
+    rows["drain, decode, NNDR, claims"] = total(post - ragged)
+    rows["rejected count handed over"] = total(to_bar2 - {bar2}, [cut(bar2, True)])
+    rows["list compaction (loop body once)"] = total(to_last - {bar2}, [cut(bar2, False)] if bar2 != bars[-1] else [])
+    rows["behind it: lane 0's header and result, rare paths (not in the model)"] = total(rest, [cut(bar2, False)] if bar2 == bars[-1] else [])
+    keys = list(rows)
+    once = sum(rows[k]["valu"] for k in (keys[0], keys[1], keys[7], keys[8]))
+    per_group = rows[keys[2]]["valu"] + rows[keys[3]]["valu"] + rows[keys[6]]["valu"]
+    loop, rag = rows[keys[4]]["valu"], rows[keys[5]]["valu"]
+
+    def model(k):
+        tiles = (((k + 31) // 32) + 3) // 4            # column tiles of wavefront 0 (4 wavefronts per pair)
+        if tiles % 4:
+            sys.exit("K = %d: not only 4-tile groups" % k)
+        return once + (tiles // 4) * (per_group + (k // 32) * loop + (rag if k % 32 else 0))
+
+    return rows, {k: model(k) for k in (500, 512, 1000)}, total(live)
+
+
+def run(asm_path):
+    lines = open(asm_path).readlines()
+    rows, model, whole = census(function_lines(lines, SPLIT))
+    return {"regions": {k: {x: v[x] for x in KINDS} for k, v in rows.items()}, "model_valu": model,
+            "kernel_total": {x: whole[x] for x in KINDS},
+            "k_match_split<8,4,3>": resources(lines, SPLIT), "k_verify_fused<8,0,false>": resources(lines, FUSED)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--asm")
+    ap.add_argument("--json", action="store_true")
+    a = ap.parse_args()
+    if a.asm:
+        r = run(a.asm)
+    else:
+        with tempfile.TemporaryDirectory() as td:
+            compile_asm(os.path.join(td, "tu.s"))
+            r = run(os.path.join(td, "tu.s"))
+    if a.json:
+        print(json.dumps(r))
+        return
+    print("k_match_split<8, 4, 3>, per wavefront  (flags: %s)" % " ".join(FLAGS[1:]))
+    print("  %-66s %5s %5s %5s %5s %5s" % (("region",) + tuple(k.upper() for k in KINDS)))
+    for k, v in r["regions"].items():
+        print("  %-66s %5d %5d %5d %5d %5d" % ((k,) + tuple(v[x] for x in KINDS)))
+    print("  %-66s %5d %5d %5d %5d %5d" % (("whole kernel (static)",) + tuple(r["kernel_total"][x] for x in KINDS)))
+    for k, v in r["model_valu"].items():
+        print("  modelled VALU per wavefront, K = %4d: %d" % (int(k), v))
+    for name in ("k_match_split<8,4,3>", "k_verify_fused<8,0,false>"):
+        print("  %-28s VGPRs %s, scratch %s B, occupancy %s" % (name, r[name]["vgprs"], r[name]["scratch_bytes"], r[name]["occupancy"]))
+
+
+if __name__ == "__main__":
+    main()
