@@ -61,6 +61,8 @@ extern "C" {
       ids of sf_prof_get (SF_K_COUNT 11 -> 12).                                                                     */
 /* 8: sf_orb_params, sf_orb_defaults, sf_set_feature_type, sf_get_feature_type, sf_orb_set_pattern, sf_orb_get_pattern
       added (GFTT/ORB descriptors, Vis/FeatureType 8), nothing existing changed.                                      */
+/* 8, additions: sf_fast_params, sf_fast_defaults, sf_fast_set_params, sf_fast_get_params, sf_detect_fast_device;
+      sf_set_feature_type accepts 4 (FAST/BRIEF).  Nothing existing changed, the version number stays.               */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -317,7 +319,10 @@ int  sf_brief_get_pattern(sf_handle h, int8_t* tests, int32_t cap_bytes, int32_t
    sigma 2 blur in OpenCV's 8-bit fixed point, the pattern rotated by each keypoint's own angle (-1 degree for GFTT
    corners), the border filter KeyPointsFilter::runByImageBorder(ORB/EdgeThreshold) on cvRound(pt).  Corners whose
    octave & 255 is not 0 are dropped like border corners (multi-level pyramids are not built).  orb NULL = defaults.
-   Any other feature_type or parameter, and 8 on a handle with desc_type 1, return SF_EINVAL.                        */
+   4 = FAST/BRIEF: the corners of sf_get_features_and_descriptor and its batch form come from the FAST detector below
+   (the handle's sf_fast_params, det->max_features; quality_level / min_distance are validated and unused), everything
+   after the detector is type 6's -- the same BRIEF table, the same border rule; a non-NULL orb is ignored.
+   Any other feature_type or parameter, and 4 or 8 on a handle with desc_type 1, return SF_EINVAL.                   */
 typedef struct sf_orb_params {
   int32_t edge_threshold; /* ORB/EdgeThreshold, 19; 1 .. 64                                                         */
   int32_t patch_size;     /* ORB/PatchSize, 31 (only value accepted)                                                */
@@ -328,7 +333,7 @@ typedef struct sf_orb_params {
                              rtabmap's GFTT/ORB: rows that do not change with an in-plane rotation of the image      */
 } sf_orb_params;
 void sf_orb_defaults(sf_orb_params* p);
-int  sf_set_feature_type(sf_handle h, int32_t feature_type, const sf_orb_params* orb);   /* 6 or 8 */
+int  sf_set_feature_type(sf_handle h, int32_t feature_type, const sf_orb_params* orb);   /* 4, 6 or 8 */
 int  sf_get_feature_type(sf_handle h, int32_t* feature_type, sf_orb_params* orb);       /* orb may be NULL */
 /* ORB test locations: [8 * bytes][4] int8 {x1, y1, x2, y2}, each within +-15 (the 31 px patch); bytes = 32.  Bit k of
    byte i is I(x1, y1) < I(x2, y2) of test 8 i + k, LSB first.  A fresh handle holds OpenCV's makeRandomPattern(31, 512)
@@ -382,6 +387,31 @@ int  sf_netvlad_infer_batch_device(sf_handle h, const float* d_images_rgb, int32
 int  sf_detect_corners_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                               int32_t max_corners, double quality_level, double min_distance,
                               sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
+/* The FAST detector of rtabmap's Vis/FeatureType 4 (FAST/BRIEF; also behind 3 and inside 2, which are not built):
+   cv::FastFeatureDetector (FAST-9/16, TYPE_9_16) followed by Feature2D::limitKeypoints [both upstream, restated in
+   tests/fast_ref.py].  With d_k = I(p) - I(p + ring_k) over the 16 pixels of the radius-3 circle, m(p) = the maximum
+   over the 16 cyclic arcs of 9 consecutive k of max(min d, min -d); p is a corner iff m(p) > threshold, for
+   3 <= x < width - 3 and 3 <= y < height - 3 (smaller images: no corners, not an error); its score is m(p) - 1.
+   nonmax_suppression 1 keeps a corner iff its score is strictly greater than that of each of its 8 neighbours (plateaus
+   vanish entirely); 0 keeps every corner, with response 0.  Keypoints {x, y, size 7, angle -1, response = score,
+   octave 0, class_id -1}: in raster order (y, then x) when they number <= max_features or max_features <= 0, otherwise
+   the max_features strongest by descending response, ties by descending raster index.  The grid-adaptive thresholds
+   (FAST/GridRows, GridCols, MinThreshold, MaxThreshold) are not built: this is what a grid of 0 gives.             */
+typedef struct sf_fast_params {
+  int32_t threshold;           /* FAST/Threshold, 20; 1 .. 254                  */
+  int32_t nonmax_suppression;  /* FAST/NonmaxSuppression, 1; 0 or 1             */
+} sf_fast_params;
+void sf_fast_defaults(sf_fast_params* p);
+/* The handle's FAST parameters (what feature type 4 detects with); out-of-range values return SF_EINVAL and change
+   nothing.                                                                                                        */
+int  sf_fast_set_params(sf_handle h, const sf_fast_params* params);
+int  sf_fast_get_params(sf_handle h, sf_fast_params* params);
+/* Conventions of sf_detect_corners_device: d_kpts_out receives up to `cap` keypoints, *n_out = keypoints of the result
+   (after the limit); width, height >= 3.  params NULL = the handle's.  Any image size up to 2^26 pixels.  Synchronises
+   the stream twice (corner count, result count).                                                                  */
+int  sf_detect_fast_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                           int32_t max_features, const sf_fast_params* params, sf_keypoint* d_kpts_out, int32_t cap,
+                           int32_t* n_out);
 /* Stereo correspondence of the corners: replaces Feature2D::generateKeypoints3D's call of
    StereoOpticalFlow::computeCorrespondences [upstream rtabmap] behind myRegistrationVis.cpp:382 --
    cv::calcOpticalFlowPyrLK(left, right, corners, winSize, maxLevel, {COUNT + EPS, iterations, epsilon},
@@ -444,7 +474,7 @@ int  sf_get_features_and_descriptor(sf_handle h, const uint8_t* left, const uint
    slots *first_slot_out .. + n_keyframes - 1; per keyframe the results are the single call's, byte for byte.  Optional
    device outputs, each sized for n_keyframes x det->max_features rows (keyframe i at row i * max_features; any may be
    NULL): d_rows_out [n_keyframes] features kept, d_desc_out, d_xyz_out, d_kpts_out as in the single call.  Images up to
-   about 1.2 Mpixel (the corner selection keeps its bitmap in LDS).                                                 */
+   about 1.2 Mpixel (the corner selection keeps its bitmap in LDS); no such limit under feature type 4.             */
 int  sf_get_features_and_descriptor_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
                                                  int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                                  size_t image_stride, const sf_stereo_camera* cam,

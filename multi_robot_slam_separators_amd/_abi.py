@@ -146,8 +146,21 @@ def orb_params(edge_threshold=19, patch_size=31, wta_k=2, orientation=0):
     return p
 
 
+class FastParams(C.Structure):
+    """sf_fast_params (include/sepfinder.h): rtabmap's FAST/ parameters of the FAST detector (Vis/FeatureType 4)."""
+    _fields_ = [("threshold", C.c_int32), ("nonmax_suppression", C.c_int32)]
+
+
+def fast_params(threshold=20, nonmax_suppression=1):
+    """FAST/Threshold, FAST/NonmaxSuppression defaults (what sf_fast_defaults fills)."""
+    p = FastParams()
+    p.threshold, p.nonmax_suppression = threshold, nonmax_suppression
+    return p
+
+
 FEATURE_GFTT_BRIEF = 6   # Vis/FeatureType values of sf_set_feature_type
 FEATURE_GFTT_ORB = 8
+FEATURE_FAST_BRIEF = 4
 
 
 class NetvladWeights(C.Structure):

@@ -1,5 +1,6 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
-// detection, stereo correspondence and keyframe extraction (kernels in k_extract.hip, k_gftt.hip, k_lk.hip, k_cnn.hip).
+// detection (GFTT, FAST), stereo correspondence and keyframe extraction (kernels in k_extract.hip, k_gftt.hip,
+// k_fast.hip, k_lk.hip, k_cnn.hip).
 #include "sf_host.hpp"
 
 // ---- feature extraction (kernels in k_extract.hip) ----------------------------------
@@ -81,8 +82,14 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
     c->feature_type = 6;
     return SF_OK;
   }
+  if (feature_type == 4) {
+    if (c->params.desc_type != 0)
+      return sf_fail(c, SF_EINVAL, "FAST/BRIEF writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+    c->feature_type = 4;
+    return SF_OK;
+  }
   if (feature_type != 8)
-    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (6 = GFTT/BRIEF, 8 = GFTT/ORB)", feature_type);
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)", feature_type);
   if (c->params.desc_type != 0)
     return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
   sf_orb_params o;
@@ -186,6 +193,49 @@ extern "C" int sf_detect_corners_device(sf_handle c, const uint8_t* d_image, int
                                   cap, n_out);
 }
 
+// ---- FAST (Vis/FeatureType 4; kernels in k_fast.hip) ---------------------------------------------------------------
+extern "C" void sf_fast_defaults(sf_fast_params* p) {
+  if (!p) return;
+  p->threshold = 20;           // FAST/Threshold [upstream rtabmap Parameters.h]
+  p->nonmax_suppression = 1;   // FAST/NonmaxSuppression
+}
+
+static int fast_validate(sf_context* c, const sf_fast_params& f) {
+  if (f.threshold < 1 || f.threshold > 254) return sf_fail(c, SF_EINVAL, "FAST threshold %d outside 1 .. 254", f.threshold);
+  if (f.nonmax_suppression != 0 && f.nonmax_suppression != 1)
+    return sf_fail(c, SF_EINVAL, "FAST nonmax_suppression %d is neither 0 nor 1", f.nonmax_suppression);
+  return SF_OK;
+}
+
+extern "C" int sf_fast_set_params(sf_handle c, const sf_fast_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  int rc = fast_validate(c, *params);
+  if (rc != SF_OK) return rc;
+  c->fast = *params;
+  return SF_OK;
+}
+
+extern "C" int sf_fast_get_params(sf_handle c, sf_fast_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  *params = c->fast;
+  return SF_OK;
+}
+
+extern "C" int sf_detect_fast_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                     int32_t max_features, const sf_fast_params* params, sf_keypoint* d_kpts_out,
+                                     int32_t cap, int32_t* n_out) {
+  if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
+  *n_out = 0;
+  if (!d_image || width < 3 || height < 3 || pitch < width)
+    return sf_fail(c, SF_EINVAL, "image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  const sf_fast_params prm = params ? *params : c->fast;
+  int rc = fast_validate(c, prm);
+  if (rc != SF_OK) return rc;
+  if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_detect_fast(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
+}
+
 extern "C" void sf_stereo_flow_defaults(sf_stereo_flow_params* p) {
   if (!p) return;
   p->win_width = 15; p->win_height = 3;        // Stereo/WinWidth, Stereo/WinHeight [upstream rtabmap Parameters.h]
@@ -287,8 +337,14 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t n = 0;
-  if ((rc = sf_detect_corners_device(c, d_left, width, height, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n)) != SF_OK)
-    return rc;
+  if (c->feature_type == 4) {
+    if (!(dp.quality_level > 0.0) || !(dp.min_distance >= 0.0))
+      return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
+    rc = sf_detect_fast_device(c, d_left, width, height, width, maxf, nullptr, d_kpts, maxf, &n);
+  } else {
+    rc = sf_detect_corners_device(c, d_left, width, height, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
+  }
+  if (rc != SF_OK) return rc;
   n = std::min(n, maxf);
   float* d_xy = (float*)c->ft_flow.p;                    // [n][2], then x [n], then status [n]
   float* d_rx = d_xy + 2 * (size_t)maxf;
@@ -351,9 +407,14 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
   if ((rc = sf_store_reserve(c, c->store, c->store.slots + n, maxf, kind.bytes)) != SF_OK) return rc;
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t* d_n = (int32_t*)c->ft_counts.p;
-  if ((rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
-                                           dp.min_distance, d_kpts, maxf, d_n)) != SF_OK)
-    return rc;
+  if (c->feature_type == 4) {
+    if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+    rc = sf_launch_detect_fast_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
+  } else {
+    rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
+                                        dp.min_distance, d_kpts, maxf, d_n);
+  }
+  if (rc != SF_OK) return rc;
   float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
   float* d_rx = d_xy + 2 * rows_all;
   uint8_t* d_status = (uint8_t*)(d_rx + rows_all);

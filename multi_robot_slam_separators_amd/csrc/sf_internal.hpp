@@ -232,7 +232,7 @@ struct sf_context {
   struct sf_netvlad_model* netvlad = nullptr;   // NetVLAD inference (k_cnn.hip): weights + activation buffers
   int brief_bytes = 0;                 // 0: table not uploaded yet
   int8_t brief_host[64 * 8 * 4] = {};
-  // Vis/FeatureType of the extraction (sf_set_feature_type): 6 = GFTT/BRIEF, 8 = GFTT/ORB with `orb` and the ORB test
+  // Vis/FeatureType of the extraction (sf_set_feature_type): 6 = GFTT/BRIEF, 4 = FAST/BRIEF, 8 = GFTT/ORB with `orb` and the ORB test
   // table (orb_host, uploaded to orb_tests; orb_loaded false: the default set, not generated yet); ex_blur / ex_kpts:
   // the blurred level-0 images and the keypoints with their ORB angles
   int feature_type = 6;
@@ -240,6 +240,8 @@ struct sf_context {
   bool orb_loaded = false;
   int8_t orb_host[32 * 8 * 4] = {};
   Buf orb_tests, ex_blur, ex_kpts;
+  // 4 = FAST/BRIEF: the detector is k_fast.hip's with these parameters (sf_fast_set_params), the rest is type 6's
+  sf_fast_params fast = {20, 1};
   Buf trace;                    // SF_CHAIN_TRACE builds: uint64[n][32] phase timestamps of the fused kernel
 
   // NN stage
@@ -512,6 +514,12 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
 int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
                              int32_t* n_out);
+// FAST-9/16 + limitKeypoints (k_fast.hip); prm validated by the caller
+int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
+                          const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
+int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                                int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
+                                int32_t* d_n_out);
 int sf_launch_stereo_flow(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, int width, int height, int pitch,
                           const sf_keypoint* d_kpts, int n, const sf_stereo_flow_params* prm, float* d_right_xy,
                           uint8_t* d_status, float* d_right_x, float* d_err);

@@ -88,6 +88,10 @@ def load():
         "sf_orb_get_pattern": (C.c_int, [vp, vp, i32, P(i32)]),
         "sf_extract_keyframe_device": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp, i32, P(_abi.StereoCamera),
                                                  P(i32), P(i32), vp, vp, vp]),
+        "sf_fast_defaults": (None, [P(_abi.FastParams)]),
+        "sf_fast_set_params": (C.c_int, [vp, P(_abi.FastParams)]),
+        "sf_fast_get_params": (C.c_int, [vp, P(_abi.FastParams)]),
+        "sf_detect_fast_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.FastParams), vp, i32, P(i32)]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
         "sf_stereo_flow_defaults": (None, [P(_abi.StereoFlowParams)]),
         "sf_detector_defaults": (None, [P(_abi.DetectorParams)]),
@@ -173,6 +177,7 @@ EXPORTED = [
     "sf_get_features_and_descriptor_batch_device", "sf_prof_enable", "sf_prof_select", "sf_prof_reset", "sf_prof_get",
     "sf_kernel_name", "sf_stream_placement", "sf_streams_prepare",
     "sf_orb_defaults", "sf_set_feature_type", "sf_get_feature_type", "sf_orb_set_pattern", "sf_orb_get_pattern",
+    "sf_fast_defaults", "sf_fast_set_params", "sf_fast_get_params", "sf_detect_fast_device",
 ]
 
 
@@ -348,7 +353,8 @@ class SeparatorFinder:
 
     def set_feature_type(self, feature_type, orb=None):
         """Vis/FeatureType of the extraction calls: 6 = GFTT/BRIEF (a fresh handle), 8 = GFTT/ORB with orb
-        (_abi.OrbParams; None = rtabmap's ORB/ defaults)."""
+        (_abi.OrbParams; None = rtabmap's ORB/ defaults), 4 = FAST/BRIEF: type 6 with the corners of the FAST detector
+        (fast_set_params; orb is ignored)."""
         self._check(self._L.sf_set_feature_type(self._h, int(feature_type), C.byref(orb) if orb is not None else None))
 
     def get_feature_type(self):
@@ -403,6 +409,24 @@ class SeparatorFinder:
         """n_images images [H][W][3] float32 back to back on the device -> d_out [n_images][n_out] (data_handler.py:149-156)."""
         self._check(self._L.sf_netvlad_infer_batch_device(self._h, C.c_void_p(d_images_rgb), n_images, width, height,
                                                           C.c_void_p(d_out), n_out))
+
+    def fast_set_params(self, params):
+        """The handle's FAST parameters (_abi.FastParams): what feature type 4 detects with."""
+        self._check(self._L.sf_fast_set_params(self._h, C.byref(params)))
+
+    def fast_get_params(self):
+        p = _abi.FastParams()
+        self._check(self._L.sf_fast_get_params(self._h, C.byref(p)))
+        return p
+
+    def detect_fast_device(self, d_image, width, height, pitch, max_features, d_kpts_out, cap, params=None):
+        """FAST-9/16 + rtabmap's limitKeypoints on the device (params None = the handle's); returns the number of
+        keypoints of the result (<= cap are written)."""
+        n = C.c_int32()
+        self._check(self._L.sf_detect_fast_device(self._h, C.c_void_p(d_image), width, height, pitch, max_features,
+                                                  C.byref(params) if params is not None else None,
+                                                  C.c_void_p(d_kpts_out), cap, C.byref(n)))
+        return n.value
 
     def detect_corners_device(self, d_image, width, height, pitch, max_corners, quality_level, min_distance,
                               d_kpts_out, cap):

@@ -98,10 +98,16 @@ class SepfinderGeometricTools {
       ROS_WARN("no brief_pattern_file: descriptors will not match a robot that runs the reference's OpenCV BRIEF");
     }
 
-    // Vis/FeatureType: 6 = GFTT/BRIEF (default), 8 = GFTT/ORB with ORB/EdgeThreshold; see INTEGRATION.md
+    // Vis/FeatureType: 6 = GFTT/BRIEF (default), 8 = GFTT/ORB with ORB/EdgeThreshold, 4 = FAST/BRIEF with
+    // FAST/Threshold; see INTEGRATION.md
     int feature_type = 6, edge_threshold = 19;
     n.param("feature_type", feature_type, 6);
     n.param("orb_edge_threshold", edge_threshold, 19);
+    sf_fast_params fast;
+    sf_fast_defaults(&fast);
+    n.param("fast_threshold", fast.threshold, 20);
+    if (sf_fast_set_params(sf_, &fast) != SF_OK)
+      ROS_ERROR("fast_threshold %d: %s", fast.threshold, sf_last_error(sf_));
     sf_orb_params orb;
     sf_orb_defaults(&orb);
     orb.edge_threshold = edge_threshold;
