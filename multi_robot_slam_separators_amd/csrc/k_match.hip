@@ -416,7 +416,8 @@ __device__ __forceinline__ void knn2_scan_lds(const uint32_t* fromD, int Kf, con
 //   * the accumulator starts at -(from row index)/2048 instead of 0, so one f32 per (from, to) cell
 //     orders by distance first (steps of 2) and by the LOWER from index second (fraction < 1): the
 //     BFMatcher tie rule with no separate index bookkeeping;
-//   * best / second best per column: v_max_f32 + v_med3_f32 per cell, then one cross-half merge.
+//   * best per column exactly, second best optimistically (top2_update16: 10 ops per 16 cells), one cross-half merge,
+//     and the exact second best of a column that passes NNDR from the best row's class (mf_repair_d2).
 typedef int mf_v8i __attribute__((ext_vector_type(8)));
 typedef float mf_v16f __attribute__((ext_vector_type(16)));
 constexpr float MF_FR = 1.f / 2048.f;        // index fraction (kcap <= 2048 rows on this path)
@@ -474,37 +475,38 @@ __device__ __forceinline__ void load_raw(const uint32_t* p, uint32_t (&raw)[KS])
   }
 }
 
-// (b, s) <- the two largest of {b, s, v[0..15]} (b >= s on entry and exit), 20 VALU ops:
-//   per pair (v0, v1):  x = med3(b, v0, v1) is the second largest of {b, v0, v1}, b' = max3(b, v0, v1),
-//   and the second largest of {b, s, v0, v1} is max(s, x) -- so two pairs cost 2 med3 + 3 max3.
-// Written as asm because fmaxf() costs a canonicalising self-max per operand; the FIRST read of the
-// accumulator is left to the compiler (a builtin), which places the MFMA-result wait states in front of
-// it -- the hazard recogniser does not look inside an asm statement.
+// The scan's running pair per lane and column tile: b, the best score, EXACT; s, an OPTIMISTIC second best (<= the exact
+// one).  A tuple v[0..15] (one 32-row "from" tile, one lane half) meets (b, s) as two values, the maximum m of v[0..14]
+// and v[15]:  x = med3(b, m, v15) is the second largest of {b, m, v15}, b' = max3(b, m, v15), s' = max(s, x) -- 10 VALU
+// ops per tuple in the pipelined statements below (7 for m + 3) against the 20 of an exact top-2 per value pair.
+//   CLASS MAP.  Register i of a tuple holds row (i & 3) + 8 * (i >> 2) + 4 * h of its tile (h = lane half), so the rows of
+//   one "from" tile T fall into four classes: for h = 0, 1 the 15 rows T * 32 + 4 * h + {0..3, 8..11, 16..19, 24..26}
+//   (registers 0..14) and the single row T * 32 + 27 + 4 * h (register 15).  b is the maximum over all rows, as before;
+//   s is the second largest of the CLASS MAXIMA, i.e. the best score among the rows outside the best row's class.
+// The exact second best is therefore max(s, best of the OTHER rows of the best row's class): s decodes to a distance
+// d2' >= d2, the only consumer of d2 is the NNDR test of match_v2_body, a column that fails it against d2' fails it
+// against d2, and a column that passes has its class looked at again there (mf_repair_d2) -- docs/match_second_best.md,
+// tests/test_match_lazy_second_model.py.
+// Written as asm because fmaxf() costs a canonicalising self-max per operand; the FIRST read of the accumulator is
+// left to the compiler (a builtin: med3(v0, v1, +inf) = max(v0, v1), hence 11 ops on this unpipelined path), which
+// places the MFMA-result wait states in front of it -- the hazard recogniser does not look inside an asm statement.
 __device__ __forceinline__ void top2_update16(const mf_v16f& v, float& b, float& s) {
-  const float x0 = __builtin_amdgcn_fmed3f(b, v[0], v[1]);
-  float ta, tb;
-  asm("v_max3_f32 %0, %0, %4, %5\n\t"
-      "v_med3_f32 %2, %0, %6, %7\n\t"
-      "v_max3_f32 %0, %0, %6, %7\n\t"
-      "v_max3_f32 %1, %1, %20, %2\n\t"
-      "v_med3_f32 %2, %0, %8, %9\n\t"
-      "v_max3_f32 %0, %0, %8, %9\n\t"
-      "v_med3_f32 %3, %0, %10, %11\n\t"
-      "v_max3_f32 %0, %0, %10, %11\n\t"
-      "v_max3_f32 %1, %1, %2, %3\n\t"
-      "v_med3_f32 %2, %0, %12, %13\n\t"
-      "v_max3_f32 %0, %0, %12, %13\n\t"
-      "v_med3_f32 %3, %0, %14, %15\n\t"
-      "v_max3_f32 %0, %0, %14, %15\n\t"
-      "v_max3_f32 %1, %1, %2, %3\n\t"
-      "v_med3_f32 %2, %0, %16, %17\n\t"
-      "v_max3_f32 %0, %0, %16, %17\n\t"
-      "v_med3_f32 %3, %0, %18, %19\n\t"
-      "v_max3_f32 %0, %0, %18, %19\n\t"
-      "v_max3_f32 %1, %1, %2, %3"
-      : "+v"(b), "+v"(s), "=&v"(ta), "=&v"(tb)
-      : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]), "v"(v[9]),
-        "v"(v[10]), "v"(v[11]), "v"(v[12]), "v"(v[13]), "v"(v[14]), "v"(v[15]), "v"(x0));
+  float t = __builtin_amdgcn_fmed3f(v[0], v[1], INFINITY);
+  float x;
+  asm("v_max3_f32 %[t], %[t], %[o2], %[o3]\n\t"
+      "v_max3_f32 %[t], %[t], %[o4], %[o5]\n\t"
+      "v_max3_f32 %[t], %[t], %[o6], %[o7]\n\t"
+      "v_max3_f32 %[t], %[t], %[o8], %[o9]\n\t"
+      "v_max3_f32 %[t], %[t], %[o10], %[o11]\n\t"
+      "v_max3_f32 %[t], %[t], %[o12], %[o13]\n\t"
+      "v_max_f32 %[t], %[t], %[o14]\n\t"
+      "v_med3_f32 %[x], %[b], %[t], %[o15]\n\t"
+      "v_max3_f32 %[b], %[b], %[t], %[o15]\n\t"
+      "v_max_f32 %[s], %[s], %[x]"
+      : [b] "+v"(b), [s] "+v"(s), [t] "+v"(t), [x] "=&v"(x)
+      : [o2] "v"(v[2]), [o3] "v"(v[3]), [o4] "v"(v[4]), [o5] "v"(v[5]), [o6] "v"(v[6]), [o7] "v"(v[7]), [o8] "v"(v[8]),
+        [o9] "v"(v[9]), [o10] "v"(v[10]), [o11] "v"(v[11]), [o12] "v"(v[12]), [o13] "v"(v[13]), [o14] "v"(v[14]),
+        [o15] "v"(v[15]));
 }
 
 // One 32-row "from" tile against the NTL resident "to" tiles of this wavefront.
@@ -602,13 +604,14 @@ __device__ __forceinline__ void mf_load_b(const uint32_t* __restrict__ dT, int K
 }
 
 // ---- round 5: the scan software-pipelined inside a wavefront (256-bit descriptors) -------------------------------------
-// knn2_mfma_tile above runs, per column tile, 4 dependent MFMAs, waits for the result (s_nop 11), then 20 dependent
-// vector instructions that consume it, on ONE accumulator tuple: nothing of a wavefront's own stream overlaps -- matrix-pipe
-// time (4 x 32 cycles per 32 x 32 tile pair) and vector issue time (4 x 8 + 26 x 4; MI355X_MICROARCH.md, cycle constants)
-// only overlap between the wavefronts that share a SIMD.
-// Here the top-2 update of tile j - 1 is issued in the gaps of tile j's MFMAs, from a SECOND accumulator tuple: five to six
-// vector instructions per 32-cycle gap (their issue cost 8 + 6 x 4 fits it), so a tile pair costs the matrix pipe's 128
-// cycles plus what stays outside (the spread of the "from" tile, the loop).  Measured (profiles/r05s_*, r05zc_*): the
+// knn2_mfma_tile above runs, per column tile, 4 dependent MFMAs, waits for the result (s_nop 11), then the dependent
+// vector instructions that consume it (20 when this was written, 11 now), on ONE accumulator tuple: nothing of a wavefront's
+// own stream overlaps -- matrix-pipe time (4 x 32 cycles per 32 x 32 tile pair) and vector issue time (MI355X_MICROARCH.md,
+// cycle constants) only overlap between the wavefronts that share a SIMD.
+// Here the update of tile j - 1 is issued in the gaps of tile j's MFMAs, from a SECOND accumulator tuple: three vector
+// instructions per 32-cycle gap (five to six with the exact top-2 update; their issue cost 8 + 3 x 4 leaves the gap to the
+// matrix pipe, docs/match_second_best.md), so a tile pair costs the matrix pipe's 128 cycles plus what stays outside (the
+// spread of the "from" tile, the loop).  Measured (profiles/r05s_*, r05zc_*): the
 // cfg3-shaped launch 10.8 -> 10.0 ms per 100 000 pairs with the matrix pipe 75 % busy at the 1.69 GHz the chip sustains
 // under it, and ONE workgroup per CU now reaches 96 % of the rate of three.  The MFMAs have to sit in the asm statements
 // with the vector instructions (the compiler does not interleave an asm block with builtins), so the wait states are
@@ -616,88 +619,67 @@ __device__ __forceinline__ void mf_load_b(const uint32_t* __restrict__ dT, int K
 //   * a VALU-written A operand -> MFMA: s_nop 1 opens the first half (the spread is compiler code right in front); the
 //     second half's A operands are inputs of the first half too, so they are written before it;
 //   * an MFMA result -> a VALU reader: 12 states after the LAST MFMA of the tuple.  The old tuple's last MFMA is followed
-//     by 6 vector instructions (the end of the second half), then s_nop 1 (2), the new tile's first MFMA (1), the two
-//     origin shifts (2) and s_nop 1 (2) stand in front of the first read: 13.  The drain opens with s_nop 11;
+//     by 3 vector instructions (the end of the second half), then s_nop 1 (2), the new tile's first MFMA (1), the two
+//     origin shifts (2) and s_nop 4 (5) stand in front of the first read: 13.  The drain opens with s_nop 11;
 //   * an accumulate chain (the MFMA takes the previous result whole as C) needs none.
-// A statement's operands are limited to 30, hence two halves per tile (2 MFMAs + the update over 8 accumulator registers
-// each).  Same operations in the same order on the same values as top2_update16: same bytes.
+// A statement's operands are limited to 30, hence two halves per tile (2 MFMAs each; the first reduces registers 0..8 of
+// the old tuple, the second 9..14 and merges the maximum and register 15 into b and s).  The same classes as
+// top2_update16: b is the same value, s the same second largest of the class maxima.
 typedef int mf_v4i __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void mf_pipe_half1(mf_v16f& acc, const mf_v4i& a0, const mf_v4i& a1, const mf_v4i& a2,
                                               const mf_v4i& a3, const mf_v4i& b0, const mf_v4i& b1, const mf_v16f& cin,
-                                              const mf_v16f& old, float& b, float& s, float& x0, float& ta, float& tb) {
+                                              const mf_v16f& old, float& b, float& s, float& t) {
   asm volatile(
       "s_nop 1\n\t"
       "v_mfma_f32_32x32x64_f8f6f4 %[acc], %[a0], %[b0], %[cin] cbsz:4 blgp:4\n\t"
       "v_add_f32 %[b], 0x3c800000, %[b]\n\t"            // the origin moves by one tile: 32 / 2048
       "v_add_f32 %[s], 0x3c800000, %[s]\n\t"
-      "s_nop 1\n\t"
-      "v_med3_f32 %[x0], %[b], %[o0], %[o1]\n\t"
-      "v_max3_f32 %[b], %[b], %[o0], %[o1]\n\t"
+      "s_nop 4\n\t"
+      "v_max3_f32 %[t], %[o0], %[o1], %[o2]\n\t"
       "v_mfma_f32_32x32x64_f8f6f4 %[acc], %[a1], %[b1], %[acc] cbsz:4 blgp:4\n\t"
-      "v_med3_f32 %[ta], %[b], %[o2], %[o3]\n\t"
-      "v_max3_f32 %[b], %[b], %[o2], %[o3]\n\t"
-      "v_max3_f32 %[s], %[s], %[x0], %[ta]\n\t"
-      "v_med3_f32 %[ta], %[b], %[o4], %[o5]\n\t"
-      "v_max3_f32 %[b], %[b], %[o4], %[o5]\n\t"
-      "v_med3_f32 %[tb], %[b], %[o6], %[o7]"
-      : [acc] "=&v"(acc), [b] "+v"(b), [s] "+v"(s), [x0] "=&v"(x0), [ta] "=&v"(ta), [tb] "=&v"(tb)
+      "v_max3_f32 %[t], %[t], %[o3], %[o4]\n\t"
+      "v_max3_f32 %[t], %[t], %[o5], %[o6]\n\t"
+      "v_max3_f32 %[t], %[t], %[o7], %[o8]"
+      : [acc] "=&v"(acc), [b] "+v"(b), [s] "+v"(s), [t] "=&v"(t)
       : [a0] "v"(a0), [a1] "v"(a1), "v"(a2), "v"(a3), [b0] "v"(b0), [b1] "v"(b1), [cin] "v"(cin), [o0] "v"(old[0]),
         [o1] "v"(old[1]), [o2] "v"(old[2]), [o3] "v"(old[3]), [o4] "v"(old[4]), [o5] "v"(old[5]), [o6] "v"(old[6]),
-        [o7] "v"(old[7]));
+        [o7] "v"(old[7]), [o8] "v"(old[8]));
 }
 __device__ __forceinline__ void mf_pipe_half2(mf_v16f& acc, const mf_v4i& a2, const mf_v4i& a3, const mf_v4i& b2,
-                                              const mf_v4i& b3, const mf_v16f& old, float& b, float& s, float& ta,
-                                              float& tb) {
-  float x0;
+                                              const mf_v4i& b3, const mf_v16f& old, float& b, float& s, float& t) {
+  float x;
   asm volatile(
       "v_mfma_f32_32x32x64_f8f6f4 %[acc], %[a2], %[b2], %[acc] cbsz:4 blgp:4\n\t"
-      "v_max3_f32 %[b], %[b], %[o6], %[o7]\n\t"
-      "v_max3_f32 %[s], %[s], %[ta], %[tb]\n\t"
-      "v_med3_f32 %[x0], %[b], %[o8], %[o9]\n\t"
-      "v_max3_f32 %[b], %[b], %[o8], %[o9]\n\t"
-      "v_med3_f32 %[ta], %[b], %[o10], %[o11]\n\t"
-      "v_max3_f32 %[b], %[b], %[o10], %[o11]\n\t"
+      "v_max3_f32 %[t], %[t], %[o9], %[o10]\n\t"
+      "v_max3_f32 %[t], %[t], %[o11], %[o12]\n\t"
+      "v_max3_f32 %[t], %[t], %[o13], %[o14]\n\t"
       "v_mfma_f32_32x32x64_f8f6f4 %[acc], %[a3], %[b3], %[acc] cbsz:4 blgp:4\n\t"
-      "v_max3_f32 %[s], %[s], %[x0], %[ta]\n\t"
-      "v_med3_f32 %[ta], %[b], %[o12], %[o13]\n\t"
-      "v_max3_f32 %[b], %[b], %[o12], %[o13]\n\t"
-      "v_med3_f32 %[tb], %[b], %[o14], %[o15]\n\t"
-      "v_max3_f32 %[b], %[b], %[o14], %[o15]\n\t"
-      "v_max3_f32 %[s], %[s], %[ta], %[tb]"
-      : [acc] "+v"(acc), [b] "+v"(b), [s] "+v"(s), [x0] "=&v"(x0), [ta] "+v"(ta), [tb] "+v"(tb)
-      : [a2] "v"(a2), [a3] "v"(a3), [b2] "v"(b2), [b3] "v"(b3), [o6] "v"(old[6]), [o7] "v"(old[7]), [o8] "v"(old[8]),
-        [o9] "v"(old[9]), [o10] "v"(old[10]), [o11] "v"(old[11]), [o12] "v"(old[12]), [o13] "v"(old[13]),
-        [o14] "v"(old[14]), [o15] "v"(old[15]));
+      "v_med3_f32 %[x], %[b], %[t], %[o15]\n\t"
+      "v_max3_f32 %[b], %[b], %[t], %[o15]\n\t"
+      "v_max_f32 %[s], %[s], %[x]"
+      : [acc] "+v"(acc), [b] "+v"(b), [s] "+v"(s), [t] "+v"(t), [x] "=&v"(x)
+      : [a2] "v"(a2), [a3] "v"(a3), [b2] "v"(b2), [b3] "v"(b3), [o9] "v"(old[9]), [o10] "v"(old[10]), [o11] "v"(old[11]),
+        [o12] "v"(old[12]), [o13] "v"(old[13]), [o14] "v"(old[14]), [o15] "v"(old[15]));
 }
 // the pending tuple's update with no tile behind it (end of the full tiles)
 __device__ __forceinline__ void mf_pipe_drain(const mf_v16f& old, float& b, float& s) {
-  float x0, ta, tb;
+  float t, x;
   asm volatile(
       "s_nop 11\n\t"
       "v_add_f32 %[b], 0x3c800000, %[b]\n\t"
       "v_add_f32 %[s], 0x3c800000, %[s]\n\t"
-      "v_med3_f32 %[x0], %[b], %[o0], %[o1]\n\t"
-      "v_max3_f32 %[b], %[b], %[o0], %[o1]\n\t"
-      "v_med3_f32 %[ta], %[b], %[o2], %[o3]\n\t"
-      "v_max3_f32 %[b], %[b], %[o2], %[o3]\n\t"
-      "v_max3_f32 %[s], %[s], %[x0], %[ta]\n\t"
-      "v_med3_f32 %[ta], %[b], %[o4], %[o5]\n\t"
-      "v_max3_f32 %[b], %[b], %[o4], %[o5]\n\t"
-      "v_med3_f32 %[tb], %[b], %[o6], %[o7]\n\t"
-      "v_max3_f32 %[b], %[b], %[o6], %[o7]\n\t"
-      "v_max3_f32 %[s], %[s], %[ta], %[tb]\n\t"
-      "v_med3_f32 %[x0], %[b], %[o8], %[o9]\n\t"
-      "v_max3_f32 %[b], %[b], %[o8], %[o9]\n\t"
-      "v_med3_f32 %[ta], %[b], %[o10], %[o11]\n\t"
-      "v_max3_f32 %[b], %[b], %[o10], %[o11]\n\t"
-      "v_max3_f32 %[s], %[s], %[x0], %[ta]\n\t"
-      "v_med3_f32 %[ta], %[b], %[o12], %[o13]\n\t"
-      "v_max3_f32 %[b], %[b], %[o12], %[o13]\n\t"
-      "v_med3_f32 %[tb], %[b], %[o14], %[o15]\n\t"
-      "v_max3_f32 %[b], %[b], %[o14], %[o15]\n\t"
-      "v_max3_f32 %[s], %[s], %[ta], %[tb]"
-      : [b] "+v"(b), [s] "+v"(s), [x0] "=&v"(x0), [ta] "=&v"(ta), [tb] "=&v"(tb)
+      "v_max3_f32 %[t], %[o0], %[o1], %[o2]\n\t"
+      "v_max3_f32 %[t], %[t], %[o3], %[o4]\n\t"
+      "v_max3_f32 %[t], %[t], %[o5], %[o6]\n\t"
+      "v_max3_f32 %[t], %[t], %[o7], %[o8]\n\t"
+      "v_max3_f32 %[t], %[t], %[o9], %[o10]\n\t"
+      "v_max3_f32 %[t], %[t], %[o11], %[o12]\n\t"
+      "v_max3_f32 %[t], %[t], %[o13], %[o14]\n\t"
+      "v_med3_f32 %[x], %[b], %[t], %[o15]\n\t"
+      "v_max3_f32 %[b], %[b], %[t], %[o15]\n\t"
+      "v_max_f32 %[s], %[s], %[x]"
+      : [b] "+v"(b), [s] "+v"(s), [t] "=&v"(t), [x] "=&v"(x)
       : [o0] "v"(old[0]), [o1] "v"(old[1]), [o2] "v"(old[2]), [o3] "v"(old[3]), [o4] "v"(old[4]), [o5] "v"(old[5]),
         [o6] "v"(old[6]), [o7] "v"(old[7]), [o8] "v"(old[8]), [o9] "v"(old[9]), [o10] "v"(old[10]), [o11] "v"(old[11]),
         [o12] "v"(old[12]), [o13] "v"(old[13]), [o14] "v"(old[14]), [o15] "v"(old[15]));
@@ -751,12 +733,12 @@ __device__ __forceinline__ void mf_scan_tiles_pipe(const uint32_t* fromD, int n_
 #pragma unroll
       for (int j = 0; j < NTL; j += 2) {
         constexpr int JP = NTL - 1;      // tile 0 consumes the LAST tile of the previous "from" tile
-        float x0, ta, tb;
+        float t;
         const int jp = j == 0 ? JP : j - 1;
-        mf_pipe_half1(acc0, A4[0], A4[1], A4[2], A4[3], B4[j][0], B4[j][1], c0, acc1, b[jp], s[jp], x0, ta, tb);
-        mf_pipe_half2(acc0, A4[2], A4[3], B4[j][2], B4[j][3], acc1, b[jp], s[jp], ta, tb);
-        mf_pipe_half1(acc1, A4[0], A4[1], A4[2], A4[3], B4[j + 1][0], B4[j + 1][1], c0, acc0, b[j], s[j], x0, ta, tb);
-        mf_pipe_half2(acc1, A4[2], A4[3], B4[j + 1][2], B4[j + 1][3], acc0, b[j], s[j], ta, tb);
+        mf_pipe_half1(acc0, A4[0], A4[1], A4[2], A4[3], B4[j][0], B4[j][1], c0, acc1, b[jp], s[jp], t);
+        mf_pipe_half2(acc0, A4[2], A4[3], B4[j][2], B4[j][3], acc1, b[jp], s[jp], t);
+        mf_pipe_half1(acc1, A4[0], A4[1], A4[2], A4[3], B4[j + 1][0], B4[j + 1][1], c0, acc0, b[j], s[j], t);
+        mf_pipe_half2(acc1, A4[2], A4[3], B4[j + 1][2], B4[j + 1][3], acc0, b[j], s[j], t);
       }
     }
   }
@@ -789,6 +771,8 @@ constexpr int mf_passes(int ntl) { return ntl == 1 ? 1 : ntl / 2; }
 // hold them, for column tile[2 p + (lane >> 5)] * 32 + (lane & 31) -- a column's scores live in lanes r and r + 32 (one
 // half of a tile's rows each), so each half sends the other the tile that one decodes: one exchange per value and pass,
 // one decode for two tiles.
+// d1 and its index are exact; d2 is the OPTIMISTIC second best (>= the exact one: the best distance among the rows outside
+// the best row's class, top2_update16) -- its one consumer, the NNDR test of match_v2_body, repairs it where it matters.
 template <int W, int NTL, bool PIPE = false>
 __device__ __forceinline__ void mf_scan(const uint32_t* fromD, int Kf, const MfB<W, NTL>& B, int lane,
                                         uint32_t (&d1)[mf_passes(NTL)], uint32_t (&d2)[mf_passes(NTL)],
@@ -849,6 +833,38 @@ __device__ __forceinline__ void knn2_mfma(const uint32_t* fromD, int Kf, const u
   MfB<W, NTL> B;
   mf_load_b<W, NTL>(dT, Kt, tile, lane, B);
   mf_scan<W, NTL, PIPE>(fromD, Kf, B, lane, d1, d2, idx);
+}
+
+// The exact second-best distance of a column that passed NNDR against the scan's optimistic one (top2_update16: CLASS
+// MAP).  The scan's d2 is the best distance among the rows outside the best row's class, so the exact one is the minimum
+// of it and the distances of the class's OTHER rows, computed here by xor + popcount from the staged "from" block and the
+// column's own row `q_row` (global, L2-warm: mf_load_b has just read it).  The class of best row idx: its tile
+// idx & ~31, its lane half idx & 4, registers 0..14 = rows + {0..3, 8..11, 16..19, 24..26}; row 27 of the half (register
+// 15) is a class of its own, with nothing to repair.  Rows >= Kf are left out (the LDS behind the staged rows holds the
+// counters; the reads stay inside the block, sf_match_lds_bytes), and so is the best row itself.  Per lane: only lanes
+// that accepted call it.
+template <int W>
+__device__ __forceinline__ uint32_t mf_repair_d2(const uint32_t* fromD, int Kf, const uint32_t* __restrict__ q_row, int idx,
+                                                 uint32_t d2) {
+  if ((idx & 27) == 27) return d2;             // rows 27 and 31 of a tile
+  uint32_t q[W];
+  load_raw<W>(q_row, q);
+  const int base = (idx & ~31) + (idx & 4);
+#pragma unroll 1
+  for (int g = 0; g < 32; g += 8) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int row = base + g + k;
+      uint32_t x[W];
+      load_raw<W>(fromD + (size_t)row * W, x);
+      uint32_t d = 0;
+#pragma unroll
+      for (int c = 0; c < W; ++c) d = bcnt_acc(x[c] ^ q[c], d);
+      const bool other = row < Kf && row != idx && (g + k) != 27;
+      d2 = other ? min(d2, d) : d2;
+    }
+  }
+  return d2;
 }
 
 // Body of the matching stage for ONE pair (the calling workgroup); `smem` is the workgroup's dynamic
@@ -927,7 +943,17 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
         for (int p = 0; p < NP; ++p) {
           const int t = G == 1 ? tl[0] * 32 + lane : (tl[2 * p] + (lane >> 5) * NW) * 32 + (lane & 31);
           const bool on = (G > 1 || lane < 32) && t < Kt;
-          const bool acc = (Kf >= 2) && !((float)a1[p] > nndr * (float)a2[p]);
+          // a2 is optimistic (>= the exact second-best distance, top2_update16): a column rejected against it is
+          // rejected; one that passes has its exact value made and is decided again.  (A negative nndr, which accepts
+          // only d1 = d2 = 0, turns the inequality round: such a column repairs whatever the first test says.)
+          bool acc = (Kf >= 2) && !((float)a1[p] > nndr * (float)a2[p]);
+          const bool redo = on && Kf >= 2 && (acc || nndr < 0.f);
+          if (__ballot(redo)) {                  // wave-uniform: no pass of an alias pair takes it
+            if (redo) {
+              a2[p] = mf_repair_d2<W>(fromD, Kf, dT + (size_t)t * W, f[p], a2[p]);
+              acc = !((float)a1[p] > nndr * (float)a2[p]);
+            }
+          }
           if (on && acc) {
             atomicAdd(&cnt[f[p]], 1);
             owner[f[p]] = t;

@@ -13,11 +13,17 @@ The regions are found from the instruction stream, not from label numbers:
     a decode (v_ceil_f32) nor a claim (ds_add); inside it: in front of the loop (the "to" tiles loaded and spread, the
     origin tuple), the loop, what lies on a cycle through the loop (the ragged tile as a second pass), what follows it
     (blocks with MFMAs there = an unpipelined ragged tile; the rest = drain, decode, NNDR, claims);
+  * the repair of the second best (mf_repair_d2) is a region of its own behind the scan loop: a block there that branches
+    to itself and holds v_bcnt_u32_b32 is a repair loop (4 of a class's rows per trip, 4 trips), and its region is what
+    the topmost block dominates that dominates it and is neither a decode (v_ceil_f32) nor a claim (ds_add) -- one copy
+    per decode pass;
   * the two barriers in front of and behind the scans cut the rest: prologue + staging, scan set-up, the loop over a
     wavefront's groups, the hand-over of the rejected count, the list compaction and the header.
 Loop bodies other than the scan loop are counted once.  The model adds up what every wavefront of a pair issues; what only
 lane 0 of the workgroup runs behind the compaction (header, pass state, the result of a pair that has no estimate) and
-the paths taken by few pairs are listed and left out of it.
+the paths taken by few pairs are listed and left out of it.  model_valu is a wavefront none of whose decode passes
+repairs (no lane accepts against the optimistic second best: every pass of a pair of unrelated frames);
+model_valu_repaired one whose every pass does (a lane's class: the repair loop four times).
   tools/match_isa_census.py [--asm FILE] [--json]
 --asm: read an assembly file made before (the parent commit's, say) instead of compiling."""
 import argparse, collections, json, os, re, subprocess, sys, tempfile
@@ -206,6 +212,16 @@ def census(fn):
     pre = (before_loop | {head4}) - cyc - {scan4}
     post = after_loop - cyc
     ragged = set(n for n in post if by[n].has("v_mfma"))
+    repair_loops = [n for n in post if n in succ[n] and by[n].has("v_bcnt_u32_b32")]
+    repair = set()
+    for lp in repair_loops:
+        head = lp
+        while True:
+            ups = [d for d in dom[head] if d != head and dom[d] == dom[head] - {head}]
+            if not ups or ups[0] not in post or by[ups[0]].has("v_ceil_f32") or by[ups[0]].has("ds_add") or by[ups[0]].has("v_mfma"):
+                break
+            head = ups[0]
+        repair |= dominated(head) & post
     # the rest of the kernel, cut at its first two barriers that lie outside the groups
     bars = [n for n in names if n in live and by[n].has("s_barrier") and n not in in_groups]
     if len(bars) < 2:
@@ -246,28 +262,32 @@ def census(fn):
     rows["full-tile loop body (per 32 \"from\" rows)"] = total([scan4])
     tail = total(ragged) + total(cyc) + (total([scan4]) if cyc and not ragged else collections.Counter())
     rows["ragged last tile%s" % (" (second pass over the loop body)" if cyc and not ragged else "")] = tail
-    rows["drain, decode, NNDR, claims"] = total(post - ragged)
+    rows["drain, decode, NNDR, claims"] = total(post - ragged - repair)
+    rows["second best repaired (all decode passes; loop bodies once)"] = total(repair)
     rows["rejected count handed over"] = total(to_bar2 - {bar2}, [cut(bar2, True)])
     rows["list compaction (loop body once)"] = total(to_last - {bar2}, [cut(bar2, False)] if bar2 != bars[-1] else [])
     rows["behind it: lane 0's header and result, rare paths (not in the model)"] = total(rest, [cut(bar2, False)] if bar2 == bars[-1] else [])
     keys = list(rows)
-    once = sum(rows[k]["valu"] for k in (keys[0], keys[1], keys[7], keys[8]))
+    once = sum(rows[k]["valu"] for k in (keys[0], keys[1], keys[8], keys[9]))
+    rep = rows[keys[7]]["valu"] + 3 * total(repair_loops)["valu"]      # every pass repairing: 4 trips through its loop
     per_group = rows[keys[2]]["valu"] + rows[keys[3]]["valu"] + rows[keys[6]]["valu"]
     loop, rag = rows[keys[4]]["valu"], rows[keys[5]]["valu"]
 
-    def model(k):
+    def model(k, repaired=False):
         tiles = (((k + 31) // 32) + 3) // 4            # column tiles of wavefront 0 (4 wavefronts per pair)
         if tiles % 4:
             sys.exit("K = %d: not only 4-tile groups" % k)
-        return once + (tiles // 4) * (per_group + (k // 32) * loop + (rag if k % 32 else 0))
+        return once + (tiles // 4) * (per_group + (rep if repaired else 0) + (k // 32) * loop + (rag if k % 32 else 0))
 
-    return rows, {k: model(k) for k in (500, 512, 1000)}, total(live)
+    ks = (500, 512, 1000)
+    return rows, {k: model(k) for k in ks}, {k: model(k, True) for k in ks}, total(live)
 
 
 def run(asm_path):
     lines = open(asm_path).readlines()
-    rows, model, whole = census(function_lines(lines, SPLIT))
+    rows, model, repaired, whole = census(function_lines(lines, SPLIT))
     return {"regions": {k: {x: v[x] for x in KINDS} for k, v in rows.items()}, "model_valu": model,
+            "model_valu_repaired": repaired,
             "kernel_total": {x: whole[x] for x in KINDS},
             "k_match_split<8,4,3>": resources(lines, SPLIT), "k_verify_fused<8,0,false>": resources(lines, FUSED)}
 
@@ -292,7 +312,8 @@ def main():
         print("  %-66s %5d %5d %5d %5d %5d" % ((k,) + tuple(v[x] for x in KINDS)))
     print("  %-66s %5d %5d %5d %5d %5d" % (("whole kernel (static)",) + tuple(r["kernel_total"][x] for x in KINDS)))
     for k, v in r["model_valu"].items():
-        print("  modelled VALU per wavefront, K = %4d: %d" % (int(k), v))
+        print("  modelled VALU per wavefront, K = %4d: %d  (every decode pass repairing: %d)"
+              % (int(k), v, r["model_valu_repaired"][k]))
     for name in ("k_match_split<8,4,3>", "k_verify_fused<8,0,false>"):
         print("  %-28s VGPRs %s, scratch %s B, occupancy %s" % (name, r[name]["vgprs"], r[name]["scratch_bytes"], r[name]["occupancy"]))
 
