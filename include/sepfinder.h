@@ -63,6 +63,9 @@ extern "C" {
       added (GFTT/ORB descriptors, Vis/FeatureType 8), nothing existing changed.                                      */
 /* 8, additions: sf_fast_params, sf_fast_defaults, sf_fast_set_params, sf_fast_get_params, sf_detect_fast_device;
       sf_set_feature_type accepts 4 (FAST/BRIEF).  Nothing existing changed, the version number stays.               */
+/* 8, additions: sf_orb_detector_params, sf_orb_detector_defaults, sf_set_feature_type_orb, sf_get_orb_detector,
+      sf_detect_orb_device (ORB on a pyramid, Vis/FeatureType 2).  sf_set_feature_type still refuses 2; nothing existing
+      changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.                                            */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -318,11 +321,13 @@ int  sf_brief_get_pattern(sf_handle h, int8_t* tests, int32_t cap_bytes, int32_t
    cv::ORB::compute on the given corners with rtabmap's ORB/ parameters, 32-byte rows -- one pyramid level, the 7 x 7
    sigma 2 blur in OpenCV's 8-bit fixed point, the pattern rotated by each keypoint's own angle (-1 degree for GFTT
    corners), the border filter KeyPointsFilter::runByImageBorder(ORB/EdgeThreshold) on cvRound(pt).  Corners whose
-   octave & 255 is not 0 are dropped like border corners (multi-level pyramids are not built).  orb NULL = defaults.
+   octave & 255 is not 0 are dropped like border corners (one level: the pyramid is type 2's, sf_set_feature_type_orb
+   below).  orb NULL = defaults.
    4 = FAST/BRIEF: the corners of sf_get_features_and_descriptor and its batch form come from the FAST detector below
    (the handle's sf_fast_params, det->max_features; quality_level / min_distance are validated and unused), everything
    after the detector is type 6's -- the same BRIEF table, the same border rule; a non-NULL orb is ignored.
-   Any other feature_type or parameter, and 4 or 8 on a handle with desc_type 1, return SF_EINVAL.                   */
+   Any other feature_type or parameter, and 4 or 8 on a handle with desc_type 1, return SF_EINVAL -- 2 (ORB) included:
+   it takes detector parameters and is selected by sf_set_feature_type_orb.                                          */
 typedef struct sf_orb_params {
   int32_t edge_threshold; /* ORB/EdgeThreshold, 19; 1 .. 64                                                         */
   int32_t patch_size;     /* ORB/PatchSize, 31 (only value accepted)                                                */
@@ -387,7 +392,8 @@ int  sf_netvlad_infer_batch_device(sf_handle h, const float* d_images_rgb, int32
 int  sf_detect_corners_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                               int32_t max_corners, double quality_level, double min_distance,
                               sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
-/* The FAST detector of rtabmap's Vis/FeatureType 4 (FAST/BRIEF; also behind 3 and inside 2, which are not built):
+/* The FAST detector of rtabmap's Vis/FeatureType 4 (FAST/BRIEF; also inside 2, sf_detect_orb_device below, and behind 3,
+   which is not built):
    cv::FastFeatureDetector (FAST-9/16, TYPE_9_16) followed by Feature2D::limitKeypoints [both upstream, restated in
    tests/fast_ref.py].  With d_k = I(p) - I(p + ring_k) over the 16 pixels of the radius-3 circle, m(p) = the maximum
    over the 16 cyclic arcs of 9 consecutive k of max(min d, min -d); p is a corner iff m(p) > threshold, for
@@ -412,6 +418,45 @@ int  sf_fast_get_params(sf_handle h, sf_fast_params* params);
 int  sf_detect_fast_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                            int32_t max_features, const sf_fast_params* params, sf_keypoint* d_kpts_out, int32_t cap,
                            int32_t* n_out);
+/* ORB on an image pyramid: rtabmap's Vis/FeatureType 2, cv::ORB (OpenCV 3.2) as rtabmap's ORB feature type drives it
+   [both upstream, restated in tests/orb2_ref.py; DESIGN.md section 3 lists what the restatement decides].
+   Detector: level l has scale_l = (float)pow(scale_factor, l) and cvRound(width / scale_l) x cvRound(height / scale_l)
+   pixels, resized from level l - 1 with cv::resize(INTER_LINEAR)'s 8-bit arithmetic (the 2 x 2 mean when the level
+   halves exactly, 11-bit fixed-point bilinear otherwise).  Per level: FAST-9/16 with fast_threshold and suppression,
+   the border filter runByImageBorder(level size, edge_threshold), the per-level quota of nfeatures = max_features
+   (geometric in 1 / scale_factor, float arithmetic, the last level takes the remainder), retainBest(2 quota) on the FAST
+   score and retainBest(quota) on the Harris measure (block 7, k 0.04) under score_type 0, retainBest(quota) on the FAST
+   score under score_type 1 -- ties at a cut all stay; survivors in raster order, levels ascending.  Keypoints {level
+   position * scale_l, size 31 scale_l, intensity-centroid angle of the level, response, octave l, class_id -1}, then
+   Feature2D::limitKeypoints(max_features) keyed by |response|: order unchanged up to max_features keypoints, otherwise
+   the strongest first, ties by descending index.
+   Descriptors (sf_extract_keyframe_device under type 2): cv::ORB::compute on the given keypoints -- border filter on
+   the level-0 position; keypoints whose octave & 255 is not a level are dropped like border corners; rows grouped by
+   level, ascending, order kept within a level (the row order of the keyframe); type 8's blur and steered pattern on the
+   keypoint's own level around cvRound(position * (1.f / scale_l)), steered by the keypoint's own angle.
+   sf_get_features_and_descriptor runs detector -> stereo correspondence (level-0 positions) -> descriptors;
+   sf_orb_set_pattern serves type 2 as it serves 8.  NOT built for type 2: the batch call
+   sf_get_features_and_descriptor_batch_device (SF_EINVAL; the follow-up), first_level != 0, WTA_K 3 / 4.          */
+typedef struct sf_orb_detector_params {
+  float   scale_factor;    /* ORB/ScaleFactor, 2 (rtabmap's default, not OpenCV's 1.2); (1, 4]    */
+  int32_t n_levels;        /* ORB/NLevels, 3 (rtabmap's default, not OpenCV's 8); 1 .. 8          */
+  int32_t first_level;     /* ORB/FirstLevel, 0 (only value accepted)                             */
+  int32_t score_type;      /* ORB/ScoreType, 0 = Harris, 1 = FAST                                 */
+  int32_t fast_threshold;  /* ORB/FastThreshold, 20; 1 .. 254                                     */
+} sf_orb_detector_params;
+void sf_orb_detector_defaults(sf_orb_detector_params* p);
+/* Selects Vis/FeatureType 2.  det NULL = defaults; orb NULL = defaults; orb->edge_threshold 16 .. 64 here (the
+   radius-15 centroid patch and the radius-4 Harris window stay inside a level), orb->orientation is ignored: always
+   the centroid (sf_get_feature_type reports 1).  sf_get_feature_type reports 2 afterwards; sf_set_feature_type(h, 4 | 6
+   | 8, ...) switches back.  Out-of-range values and a handle with desc_type 1 return SF_EINVAL and change nothing.   */
+int  sf_set_feature_type_orb(sf_handle h, const sf_orb_detector_params* det, const sf_orb_params* orb);
+int  sf_get_orb_detector(sf_handle h, sf_orb_detector_params* out);
+/* Conventions of sf_detect_fast_device.  det NULL = the handle's detector parameters, orb NULL = the handle's ORB
+   parameters (both the defaults on a fresh handle).  Images smaller than 7 x 7 and levels not larger than 2
+   edge_threshold give no keypoints, not an error.  Synchronises the stream twice (corner counts, result count).     */
+int  sf_detect_orb_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                          int32_t max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
+                          sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
 /* Stereo correspondence of the corners: replaces Feature2D::generateKeypoints3D's call of
    StereoOpticalFlow::computeCorrespondences [upstream rtabmap] behind myRegistrationVis.cpp:382 --
    cv::calcOpticalFlowPyrLK(left, right, corners, winSize, maxLevel, {COUNT + EPS, iterations, epsilon},
@@ -474,7 +519,8 @@ int  sf_get_features_and_descriptor(sf_handle h, const uint8_t* left, const uint
    slots *first_slot_out .. + n_keyframes - 1; per keyframe the results are the single call's, byte for byte.  Optional
    device outputs, each sized for n_keyframes x det->max_features rows (keyframe i at row i * max_features; any may be
    NULL): d_rows_out [n_keyframes] features kept, d_desc_out, d_xyz_out, d_kpts_out as in the single call.  Images up to
-   about 1.2 Mpixel (the corner selection keeps its bitmap in LDS); no such limit under feature type 4.             */
+   about 1.2 Mpixel (the corner selection keeps its bitmap in LDS); no such limit under feature type 4.
+   Feature type 2 has no batch form yet: SF_EINVAL (the follow-up of sf_set_feature_type_orb).                       */
 int  sf_get_features_and_descriptor_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
                                                  int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                                  size_t image_stride, const sf_stereo_camera* cam,

@@ -158,9 +158,25 @@ def fast_params(threshold=20, nonmax_suppression=1):
     return p
 
 
+class OrbDetectorParams(C.Structure):
+    """sf_orb_detector_params (include/sepfinder.h): rtabmap's ORB/ parameters of the ORB detector (Vis/FeatureType 2)."""
+    _fields_ = [("scale_factor", C.c_float), ("n_levels", C.c_int32), ("first_level", C.c_int32), ("score_type", C.c_int32),
+                ("fast_threshold", C.c_int32)]
+
+
+def orb_detector_params(scale_factor=2.0, n_levels=3, first_level=0, score_type=0, fast_threshold=20):
+    """ORB/ScaleFactor, ORB/NLevels, ORB/FirstLevel, ORB/ScoreType (0 = Harris, 1 = FAST), ORB/FastThreshold: rtabmap's
+    defaults (what sf_orb_detector_defaults fills)."""
+    p = OrbDetectorParams()
+    p.scale_factor, p.n_levels, p.first_level, p.score_type, p.fast_threshold = (scale_factor, n_levels, first_level,
+                                                                                 score_type, fast_threshold)
+    return p
+
+
 FEATURE_GFTT_BRIEF = 6   # Vis/FeatureType values of sf_set_feature_type
 FEATURE_GFTT_ORB = 8
 FEATURE_FAST_BRIEF = 4
+FEATURE_ORB = 2          # ... and of sf_set_feature_type_orb
 
 
 class NetvladWeights(C.Structure):

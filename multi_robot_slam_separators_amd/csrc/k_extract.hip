@@ -217,9 +217,10 @@ __device__ __forceinline__ int reflect101(int p, int len) {
 }
 
 // KeyPointsFilter::runByImageBorder(kpts, size, e): Rect(e, e, w - 2e, h - 2e).contains(Point(cvRound(pt))), and
-// nothing survives when w <= 2e or h <= 2e; corners of another octave than 0 are dropped as well
-__device__ __forceinline__ bool orb_inside(const sf_keypoint& k, int w, int h, int e) {
-  if (w <= 2 * e || h <= 2 * e || (k.octave & 255) != 0) return false;
+// nothing survives when w <= 2e or h <= 2e; corners whose octave is not one of the n_levels levels are dropped as well
+// (one level for GFTT/ORB: another octave than 0)
+__device__ __forceinline__ bool orb_inside(const sf_keypoint& k, int w, int h, int e, int n_levels) {
+  if (w <= 2 * e || h <= 2 * e || (k.octave & 255) >= n_levels) return false;
   const float rx = rintf(k.x), ry = rintf(k.y);
   return rx >= (float)e && rx < (float)(w - e) && ry >= (float)e && ry < (float)(h - e);
 }
@@ -278,10 +279,11 @@ k_orb_blur(const uint8_t* __restrict__ img, int w, int h, int pitch, uint8_t* __
   }
 }
 
-// one wavefront per corner; every corner's keypoint goes to kpts_out, the kept ones with their angle
+// one wavefront per corner; every corner's keypoint goes to kpts_out, the kept ones with their angle.  The corner lies
+// on level (octave & 255) of P, in that level's coordinates (GFTT/ORB: one level, the image; the ORB detector: its pyramid)
 __global__ void __launch_bounds__(256)
-k_orb_angle(const uint8_t* __restrict__ img, int w, int h, int pitch, const sf_keypoint* __restrict__ kpts, int n, int edge,
-            OrbUmax U, sf_keypoint* __restrict__ kpts_out, ExtractBatch B) {
+k_orb_angle(const uint8_t* __restrict__ img, int pitch, const uint8_t* __restrict__ pyr, SfOrbPyr P,
+            const sf_keypoint* __restrict__ kpts, int n, int edge, OrbUmax U, sf_keypoint* __restrict__ kpts_out, ExtractBatch B) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (B.d_n) n = min(n, B.d_n[blockIdx.y]);
@@ -290,11 +292,13 @@ k_orb_angle(const uint8_t* __restrict__ img, int w, int h, int pitch, const sf_k
   kpts += (size_t)blockIdx.y * B.per_image;
   kpts_out += (size_t)blockIdx.y * B.per_image;
   sf_keypoint k = kpts[i];
-  const bool inside = orb_inside(k, w, h, edge);
+  const int l = k.octave & 255;
+  const SfOrbLevel L = sf_orb_level(P, l);
+  const bool inside = orb_inside(k, L.w, L.h, edge, P.n);
   int m01 = 0, m10 = 0;
-  if (inside && lane <= 2 * ORB_HALF) {       // edge >= 16: the whole patch lies in the image
+  if (inside && lane <= 2 * ORB_HALF) {       // edge >= 16: the whole patch lies in the level
     const int v = lane - ORB_HALF, d = U.u[v < 0 ? -v : v];
-    const uint8_t* row = img + (size_t)((int)rintf(k.y) + v) * pitch + (int)rintf(k.x);
+    const uint8_t* row = (l == 0 ? img : pyr + L.off) + (size_t)((int)rintf(k.y) + v) * (l == 0 ? pitch : L.w) + (int)rintf(k.x);
     int s = 0;
     for (int u = -d; u <= d; ++u) {
       const int val = row[u];
@@ -315,10 +319,12 @@ k_orb_angle(const uint8_t* __restrict__ img, int w, int h, int pitch, const sf_k
 }
 
 // one thread per (corner, descriptor byte); samples inside the image read the blurred copy, the others the
-// reflect-101 padding of the source, which ORB never blurs
+// reflect-101 padding of the source, which ORB never blurs.  The border filter is level 0's (w x h); the samples are
+// taken on level (octave & 255) of P around cvRound(position * (1.f / scale_l)) -- one level for GFTT/ORB, where this is
+// the image around cvRound(position)
 __global__ void __launch_bounds__(256)
 k_orb_points(const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, int w, int h, int pitch,
-             const sf_keypoint* __restrict__ kpts, const float* __restrict__ right_x, const uint8_t* __restrict__ status,
+             const uint8_t* __restrict__ pyr, SfOrbPyr P, const sf_keypoint* __restrict__ kpts, const float* __restrict__ right_x, const uint8_t* __restrict__ status,
              int n, int edge, const int8_t* __restrict__ tests, ExtractCam cam, uint8_t* __restrict__ desc_tmp,
              float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep, ExtractBatch B) {
   const int g = blockIdx.x * 256 + threadIdx.x;
@@ -335,16 +341,21 @@ k_orb_points(const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, 
     desc_tmp += o * ORB_BYTES; xyz_tmp += 3 * o; keep += o;
   }
   const sf_keypoint k = kpts[i];
-  const bool inside = orb_inside(k, w, h, edge);
+  const bool inside = orb_inside(k, w, h, edge, P.n);
   if (inside) {
-    const int cx = (int)rintf(k.x), cy = (int)rintf(k.y);
+    const int l = k.octave & 255;
+    const SfOrbLevel L = sf_orb_level(P, l);
+    const uint8_t* lim = l == 0 ? img : pyr + L.off;
+    const uint8_t* lbl = blur + L.off;
+    const int lw = L.w, lh = L.h, lp = l == 0 ? pitch : L.w;
+    const int cx = (int)rintf(k.x * L.inv_scale), cy = (int)rintf(k.y * L.inv_scale);
     const float ang = k.angle * (float)(3.14159265358979323846 / 180.0);
     const float ca = (float)cos((double)ang), sa = (float)sin((double)ang);
     auto sample = [&](int px, int py) -> int {
       const int ix = (int)rintf((float)px * ca - (float)py * sa), iy = (int)rintf((float)px * sa + (float)py * ca);
       const int X = cx + ix, Y = cy + iy;
-      if (X >= 0 && X < w && Y >= 0 && Y < h) return blur[(size_t)Y * w + X];
-      return img[(size_t)reflect101(Y, h) * pitch + reflect101(X, w)];
+      if (X >= 0 && X < lw && Y >= 0 && Y < lh) return lbl[(size_t)Y * lw + X];
+      return lim[(size_t)reflect101(Y, lh) * lp + reflect101(X, lw)];
     };
     unsigned v = 0;
 #pragma unroll
@@ -365,7 +376,8 @@ k_extract_commit(const sf_keypoint* __restrict__ kpts, const uint8_t* __restrict
                  uint32_t* __restrict__ st_desc, float* __restrict__ st_xyz, float4* __restrict__ st_kp,
                  int4* __restrict__ st_meta, int kcap, int w_dwords, int slot, uint8_t* __restrict__ desc_out,
                  float* __restrict__ xyz_out, sf_keypoint* __restrict__ kp_out, int32_t* __restrict__ rows_out,
-                 ExtractBatch B) {
+                 ExtractBatch B, int group_levels) {
+  // (group_levels > 1, the ORB pyramid: the rows of level 0 first, then level 1, ... -- one compaction pass per level)
   __shared__ int wave_cnt[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (B.d_n) n = min(n, B.d_n[blockIdx.x]);
@@ -383,9 +395,10 @@ k_extract_commit(const sf_keypoint* __restrict__ kpts, const uint8_t* __restrict
   float4* dk = st_kp + (size_t)slot * kcap;
   const int rowb = w_dwords * 4;
   int running = 0;
-  for (int base = 0; base < n; base += 256) {
-    const int i = base + tid;
-    const bool f = i < n && keep[i];
+  const int chunks = (n + 255) / 256;
+  for (int it = 0; it < chunks * max(group_levels, 1); ++it) {
+    const int lv = it / max(chunks, 1), i = (it - lv * chunks) * 256 + tid;
+    const bool f = i < n && keep[i] && (group_levels <= 1 || (kpts[i].octave & 255) == lv);
     const unsigned long long bal = __ballot(f);
     if (lane == 0) wave_cnt[wave] = __popcll(bal);
     __syncthreads();
@@ -490,8 +503,9 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                             const int32_t* d_n, const sf_stereo_camera* cam, int bytes, const int8_t* d_tests,
                             uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap, int w_dwords,
                             int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                            int32_t* d_rows_out, const sf_orb_params* orb) {
+                            int32_t* d_rows_out, const sf_orb_params* orb, const sf_orb_detector_params* pyr) {
   int rc;
+  if (pyr && (!orb || n_img != 1)) return sf_fail(c, SF_EINVAL, "ORB on a pyramid: one keyframe per call");
   if (orb && bytes != ORB_BYTES) return sf_fail(c, SF_EINVAL, "ORB rows are %d bytes, not %d", ORB_BYTES, bytes);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
@@ -499,6 +513,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   if ((rc = sf_buf_reserve(c, c->ex_keep, rows_all)) != SF_OK) return rc;
   ExtractBatch B;
   B.img_stride = img_stride; B.per_image = n; B.d_n = d_n;
+  SfOrbPyr P = sf_orb_single_level(width, height);
   int32_t* S = nullptr;
   if (!orb) {
     const size_t s_entries = (size_t)(width + 1) * (height + 1);
@@ -507,11 +522,23 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
     B.s_stride = s_entries;
     hipLaunchKernelGGL(k_integral_rows, dim3(height + 1, n_img), dim3(256), 0, c->stream, d_left, width, height, pitch, S, B);
     hipLaunchKernelGGL(k_integral_cols, dim3((width + 1 + 63) / 64, n_img), dim3(64), 0, c->stream, width, height, S, B);
-  } else {
+  } else if (!pyr) {
     B.s_stride = (size_t)width * height;                 // the blurred level-0 images, back to back
     if ((rc = sf_buf_reserve(c, c->ex_blur, B.s_stride * n_img)) != SF_OK) return rc;
     hipLaunchKernelGGL(k_orb_blur, dim3((height + ORB_BLUR_ROWS - 1) / ORB_BLUR_ROWS, n_img), dim3(256), 0, c->stream,
                        d_left, width, height, pitch, (uint8_t*)c->ex_blur.p, orb_blur_taps(), B);
+  } else {                                               // the pyramid and a blurred copy of every level, same offsets
+    P = sf_orb_pyr_layout(width, height, pyr->scale_factor, pyr->n_levels);
+    for (int l = 0; l < P.n; ++l)
+      if (P.w[l] < 1 || P.h[l] < 1)
+        return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, width, height, (double)P.scale[l]);
+    B.s_stride = 0;
+    if ((rc = sf_launch_orb_pyramid(c, d_left, pitch, P)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->ex_blur, P.total)) != SF_OK) return rc;
+    for (int l = 0; l < P.n; ++l)
+      hipLaunchKernelGGL(k_orb_blur, dim3((P.h[l] + ORB_BLUR_ROWS - 1) / ORB_BLUR_ROWS, 1), dim3(256), 0, c->stream,
+                         l == 0 ? d_left : (const uint8_t*)c->orb_pyr.p + P.off[l], P.w[l], P.h[l], l == 0 ? pitch : P.w[l],
+                         (uint8_t*)c->ex_blur.p + P.off[l], orb_blur_taps(), B);
   }
   ExtractCam ec;
   ec.fx = cam->fx; ec.fy = cam->fy; ec.cx = cam->cx; ec.cy = cam->cy; ec.cx_right = cam->cx_right;
@@ -530,21 +557,35 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                          height, d_kpts, d_right_x, d_status, n, bytes, d_tests, ec, (uint8_t*)c->ex_desc.p,
                          (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);
     } else {
-      if (orb->orientation) {                             // the keypoints with their angles, for the samples and the commit
+      if (orb->orientation && !pyr) {                     // the keypoints with their angles, for the samples and the commit
         if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
-        hipLaunchKernelGGL(k_orb_angle, dim3((unsigned)((n + 3) / 4), n_img), dim3(256), 0, c->stream, d_left, width,
-                           height, pitch, d_kpts, n, orb->edge_threshold, orb_umax(), (sf_keypoint*)c->ex_kpts.p, B);
+        hipLaunchKernelGGL(k_orb_angle, dim3((unsigned)((n + 3) / 4), n_img), dim3(256), 0, c->stream, d_left, pitch,
+                           (const uint8_t*)nullptr, P, d_kpts, n, orb->edge_threshold, orb_umax(), (sf_keypoint*)c->ex_kpts.p, B);
         kp_commit = (const sf_keypoint*)c->ex_kpts.p;
       }
       hipLaunchKernelGGL(k_orb_points, dim3((unsigned)((threads + 255) / 256), n_img), dim3(256), 0, c->stream, d_left,
-                         (const uint8_t*)c->ex_blur.p, width, height, pitch, kp_commit, d_right_x, d_status, n,
+                         (const uint8_t*)c->ex_blur.p, width, height, pitch, (const uint8_t*)(pyr ? c->orb_pyr.p : nullptr), P,
+                         kp_commit, d_right_x, d_status, n,
                          orb->edge_threshold, d_tests, ec, (uint8_t*)c->ex_desc.p, (float*)c->ex_xyz.p,
                          (uint8_t*)c->ex_keep.p, B);
     }
   }
   hipLaunchKernelGGL(k_extract_commit, dim3(n_img), dim3(256), 0, c->stream, kp_commit, (const uint8_t*)c->ex_desc.p,
                      (const float*)c->ex_xyz.p, (const uint8_t*)c->ex_keep.p, n, bytes, d_right_x != nullptr, st_desc,
-                     st_xyz, st_kp, st_meta, kcap, w_dwords, slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out, B);
+                     st_xyz, st_kp, st_meta, kcap, w_dwords, slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out, B,
+                     pyr ? P.n : 0);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+
+// The ORB detector's angles (k_orb_detect.hip): keypoints in level coordinates, their number read on the device
+int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P, const sf_keypoint* d_kpts,
+                               int n_max, const int32_t* d_n, int edge, sf_keypoint* d_kpts_out) {
+  if (n_max <= 0) return SF_OK;
+  ExtractBatch B;
+  B.img_stride = 0; B.s_stride = 0; B.per_image = n_max; B.d_n = d_n;
+  hipLaunchKernelGGL(k_orb_angle, dim3((unsigned)((n_max + 3) / 4), 1), dim3(256), 0, c->stream, d_image, pitch,
+                     (const uint8_t*)c->orb_pyr.p, P, d_kpts, n_max, edge, orb_umax(), d_kpts_out, B);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }
@@ -553,8 +594,8 @@ int sf_launch_extract(sf_context* c, const uint8_t* d_left, int width, int heigh
                       const float* d_right_x, const uint8_t* d_status, int n, const sf_stereo_camera* cam, int bytes,
                       const int8_t* d_tests, uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap,
                       int w_dwords, int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                      int32_t* d_rows_out, const sf_orb_params* orb) {
+                      int32_t* d_rows_out, const sf_orb_params* orb, const sf_orb_detector_params* pyr) {
   return sf_launch_extract_batch(c, d_left, 0, 1, width, height, pitch, d_kpts, d_right_x, d_status, n, nullptr, cam, bytes,
                                  d_tests, st_desc, st_xyz, st_kp, st_meta, kcap, w_dwords, slot, d_desc_out, d_xyz_out,
-                                 d_kpts_out, d_rows_out, orb);
+                                 d_kpts_out, d_rows_out, orb, pyr);
 }

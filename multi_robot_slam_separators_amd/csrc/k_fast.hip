@@ -201,6 +201,17 @@ constexpr int FAST_REKEY_BLOCKS = 32;
 
 }  // namespace
 
+// One image, one level: the two launches every single-image detector shares (FAST/BRIEF here, ORB's pyramid levels in
+// k_orb_detect.hip)
+void sf_launch_fast_level(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int threshold, int nonmax,
+                          uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap) {
+  const dim3 block(256);
+  hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH), block, 0, c->stream,
+                     d_image, width, height, pitch, threshold, score, (size_t)0, (size_t)0);
+  hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS), block, 0,
+                     c->stream, (const uint8_t*)score, width, height, nonmax, keys, count, key_cap, (size_t)0);
+}
+
 // Launch sequence on the handle's stream.  The corner count crosses to the host once (the sort is sized by it); which
 // order applies is decided on the device before that.
 int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
@@ -218,10 +229,7 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
   int32_t* d_n_out = (int32_t*)c->gf_scalar.p + 2;
   SF_HIP(c, hipMemsetAsync(c->gf_scalar.p, 0, 64, c->stream));
   const dim3 block(256);
-  hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH), block, 0, c->stream,
-                     d_image, width, height, pitch, prm->threshold, score, (size_t)0, (size_t)0);
-  hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS), block, 0,
-                     c->stream, (const uint8_t*)score, width, height, prm->nonmax_suppression, keys, count, key_cap, (size_t)0);
+  sf_launch_fast_level(c, d_image, width, height, pitch, prm->threshold, prm->nonmax_suppression, score, keys, count, key_cap);
   hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, 1), block, 0, c->stream, keys, (const unsigned*)count, key_cap,
                      max_features, (unsigned*)nullptr, (unsigned*)nullptr);
   SF_HIP(c, hipGetLastError());

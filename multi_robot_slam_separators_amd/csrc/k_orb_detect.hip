@@ -1,0 +1,452 @@
+// k_orb_detect.hip -- SURVEY.md section 8 row f3, the third detector: ORB on an image pyramid as rtabmap's
+// Vis/FeatureType 2 runs it -- cv::ORB::detect of OpenCV 3.2 (pyramid by cv::resize INTER_LINEAR, FAST-9/16 per level,
+// border filter, per-level quotas, retainBest on the FAST score and on the Harris measure, intensity-centroid angle),
+// then rtabmap's Feature2D::limitKeypoints.  Neither upstream text is in the reference tree: the semantics are restated
+// in tests/orb2_ref.py (DESIGN.md section 3 item 17b lists what the restatement decides).  Everything is 8-bit / int32
+// work except the Harris expression and the angle, which are float32 in the order written (this file is compiled with
+// -ffp-contract=off), so the kernels equal the restatement byte for byte.
+//
+//   k_orb_resize     one level from the level below: the 2 x 2 mean when it halves exactly, else 8-bit bilinear in 11-bit
+//                    fixed point; the coefficients of a pixel are computed by its thread (two double divisions)
+//   k_fast_score / k_fast_candidates (k_fast.hip, unchanged) per level -> keys (score << 32 | pixel) and a count per level
+//   -- the counts cross to the host once: everything below is sized by their sum C --
+//   k_orb_gather     every candidate: border filter, key (level << 40 | pixel << 8 | score), histogram of the FAST
+//                    scores of its level
+//   k_orb_cut_a      per level: the score at rank 2 quota (Harris) or quota (FAST) from the histogram -- retainBest on
+//                    8-bit scores needs no sort -- and the level's segment in the sorted list
+//   k_orb_filter_a   drops the candidates below their level's cut
+//   rocprim radix sort ascending by (level, pixel): survivors first, raster order within a level
+//   k_orb_harris     (score type Harris) one candidate per wavefront: lanes 0 .. 48 own one pixel of the 7 x 7 block each,
+//                    three integer wave reductions, one float32 expression; key (level, inverted order-preserving bits)
+//   rocprim radix sort ascending -> per level descending response; k_orb_cut_b reads the response at rank quota - 1
+//   k_orb_compact    ONE workgroup: stable compaction of the survivors (response >= cut: ties stay) in (level, raster)
+//                    order, then the keys of limitKeypoints: the index when the survivors fit max_features, else
+//                    (|response|, index)
+//   rocprim radix sort descending -> the final order
+//   k_orb_emit       keypoints in LEVEL coordinates; k_orb_angle (k_extract.hip) adds the centroid angle on the level;
+//   k_orb_finish     position * scale_l into the caller's array
+// About forty short launches for three levels: latency-bound like the rest of the front end, not tuned yet.
+#include <hip/hip_runtime.h>
+
+#include <cstring>   // (rocprim's texture_cache_iterator.hpp calls memset without declaring it)
+
+#include <rocprim/rocprim.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+
+#include "sf_internal.hpp"
+
+namespace {
+
+constexpr unsigned long long ORB_NONE = ~0ull;
+constexpr unsigned long long ORB_RASTER = 1ull << 63, ORB_LIMITED = 1ull << 62;
+// the scalar block (ints): per-level arrays of 8, then the histograms
+constexpr int S_COUNT = 0, S_CUT_A = 8, S_BEGIN = 16, S_KEPT = 24, S_TOTAL = 32, S_NFINAL = 34, S_CUT_B = 40, S_HIST = 64;
+constexpr int S_WORDS = S_HIST + SF_ORB_MAX_LEVELS * 256;
+
+struct OrbSel {
+  int n_levels, score_type, edge, max_features;
+  unsigned base[SF_ORB_MAX_LEVELS];     // first candidate of every level (0xFFFFFFFF past the last level)
+  int quota[SF_ORB_MAX_LEVELS];
+};
+
+__device__ __forceinline__ int orb_level_of(const OrbSel& S, unsigned i) {
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < SF_ORB_MAX_LEVELS; ++k) l = i >= S.base[k] ? k : l;
+  return l;
+}
+__device__ __forceinline__ unsigned orb_base_of(const OrbSel& S, int l) {
+  unsigned r = S.base[0];
+#pragma unroll
+  for (int k = 1; k < SF_ORB_MAX_LEVELS; ++k) r = l == k ? S.base[k] : r;
+  return r;
+}
+__device__ __forceinline__ int orb_quota_of(const OrbSel& S, int l) {
+  int r = S.quota[0];
+#pragma unroll
+  for (int k = 1; k < SF_ORB_MAX_LEVELS; ++k) r = l == k ? S.quota[k] : r;
+  return r;
+}
+
+// One axis of cv::resize(INTER_LINEAR) for 8-bit images: source index and the two 11-bit coefficients of destination d
+__device__ __forceinline__ void orb_lin_axis(int d, int dst, int src, int& s, int& c0, int& c1) {
+  const double scale = 1.0 / ((double)dst / (double)src);
+  float f = (float)(((double)d + 0.5) * scale - 0.5);
+  int si = (int)floorf(f);
+  f -= (float)si;
+  if (si < 0) { si = 0; f = 0.f; }
+  if (si >= src - 1) { si = src - 1; f = 0.f; }
+  s = si;
+  c0 = (int)rintf((1.f - f) * 2048.f);
+  c1 = (int)rintf(f * 2048.f);
+}
+
+__global__ void __launch_bounds__(256)
+k_orb_resize(const uint8_t* __restrict__ src, int sw, int sh, int spitch, uint8_t* __restrict__ dst, int dw, int dh) {
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= dw || y >= dh) return;
+  int v;
+  if (sw == 2 * dw && sh == 2 * dh) {
+    const uint8_t* p = src + (size_t)(2 * y) * spitch + 2 * x;
+    v = ((int)p[0] + (int)p[1] + (int)p[spitch] + (int)p[spitch + 1] + 2) >> 2;
+  } else {
+    int sx, a0, a1, sy, b0, b1;
+    orb_lin_axis(x, dw, sw, sx, a0, a1);
+    orb_lin_axis(y, dh, sh, sy, b0, b1);
+    const int sx1 = min(sx + 1, sw - 1), sy1 = min(sy + 1, sh - 1);
+    const uint8_t* r0 = src + (size_t)sy * spitch;
+    const uint8_t* r1 = src + (size_t)sy1 * spitch;
+    const int S0 = a0 * (int)r0[sx] + a1 * (int)r0[sx1], S1 = a0 * (int)r1[sx] + a1 * (int)r1[sx1];
+    v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+  }
+  dst[(size_t)y * dw + x] = (uint8_t)v;
+}
+
+// keys_f: the FAST keys of level l at keys_f + P.off[l] (arrival order)
+__global__ void __launch_bounds__(256)
+k_orb_gather(const unsigned long long* __restrict__ keys_f, SfOrbPyr P, OrbSel S, unsigned C, unsigned long long* __restrict__ cand,
+             int* __restrict__ sc) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= C) return;
+  const int l = orb_level_of(S, i);
+  const SfOrbLevel L = sf_orb_level(P, l);
+  const unsigned long long key = keys_f[(size_t)L.off + (i - orb_base_of(S, l))];
+  const unsigned idx = (unsigned)key, score = (unsigned)(key >> 32) & 255u;
+  const int y = (int)(idx / (unsigned)L.w), x = (int)(idx - (unsigned)y * (unsigned)L.w), e = S.edge;
+  const bool inside = L.w > 2 * e && L.h > 2 * e && x >= e && x < L.w - e && y >= e && y < L.h - e;
+  cand[i] = inside ? ((unsigned long long)l << 40) | ((unsigned long long)idx << 8) | score : ORB_NONE;
+  if (inside) atomicAdd(&sc[S_HIST + l * 256 + (int)score], 1);
+}
+
+// ONE workgroup, thread l = level l
+__global__ void __launch_bounds__(64)
+k_orb_cut_a(OrbSel S, int* __restrict__ sc) {
+  __shared__ int s_kept[SF_ORB_MAX_LEVELS];
+  const int l = threadIdx.x;
+  if (l < SF_ORB_MAX_LEVELS) {
+    int kept = 0, cut = 256;
+    if (l < S.n_levels) {
+      const int q = orb_quota_of(S, l), want = S.score_type == 0 ? 2 * q : q;
+      int cum = 0;
+      bool found = false;
+      for (int s = 255; s >= 1; --s) {
+        cum += sc[S_HIST + l * 256 + s];
+        if (!found && want > 0 && cum >= want) { found = true; cut = s; kept = cum; }
+      }
+      if (want > 0 && !found) { cut = 1; kept = cum; }
+    }
+    sc[S_CUT_A + l] = cut;
+    s_kept[l] = kept;
+  }
+  __syncthreads();
+  if (l == 0) {
+    int run = 0;
+    for (int k = 0; k < SF_ORB_MAX_LEVELS; ++k) {
+      sc[S_BEGIN + k] = run;
+      sc[S_KEPT + k] = s_kept[k];
+      run += s_kept[k];
+    }
+    sc[S_TOTAL] = run;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+k_orb_filter_a(unsigned long long* __restrict__ cand, unsigned C, const int* __restrict__ sc) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= C) return;
+  const unsigned long long key = cand[i];
+  if (key == ORB_NONE) return;
+  if ((int)(key & 255ull) < sc[S_CUT_A + (int)(key >> 40)]) cand[i] = ORB_NONE;
+}
+
+// ascending unsigned order = ascending float order
+__device__ __forceinline__ unsigned orb_order_bits(float r) {
+  const unsigned u = __float_as_uint(r);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float orb_order_float(unsigned o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
+// one candidate per wavefront (HarrisResponses, block 7, k 0.04); edge >= 16 keeps the radius-4 window inside the level
+__global__ void __launch_bounds__(256)
+k_orb_harris(const uint8_t* __restrict__ img, int pitch, const uint8_t* __restrict__ pyr, SfOrbPyr P,
+             const unsigned long long* __restrict__ cand_s, const int* __restrict__ sc, unsigned C, float* __restrict__ resp,
+             unsigned long long* __restrict__ key_b) {
+  const int lane = threadIdx.x & 63;
+  const unsigned i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= C) return;
+  if (i >= (unsigned)sc[S_TOTAL]) {
+    if (lane == 0) key_b[i] = ORB_NONE;
+    return;
+  }
+  const unsigned long long key = cand_s[i];
+  const int l = (int)(key >> 40);
+  const unsigned idx = (unsigned)(key >> 8);
+  const SfOrbLevel L = sf_orb_level(P, l);
+  const uint8_t* base = l == 0 ? img : pyr + L.off;
+  const int lp = l == 0 ? pitch : L.w;
+  const int y = (int)(idx / (unsigned)L.w), x = (int)(idx - (unsigned)y * (unsigned)L.w);
+  int a = 0, b = 0, cc = 0;
+  if (lane < 49) {
+    const int by = lane / 7, bx = lane - 7 * by;
+    const uint8_t* p = base + (size_t)(y + by - 3) * lp + (x + bx - 3);
+    const int mm = p[-lp - 1], m0 = p[-lp], mp = p[-lp + 1], zm = p[-1], zp = p[1], pm = p[lp - 1], p0 = p[lp], pp = p[lp + 1];
+    const int ix = (zp - zm) * 2 + (mp - mm) + (pp - pm);
+    const int iy = (p0 - m0) * 2 + (pm - mm) + (pp - mp);
+    a = ix * ix; b = iy * iy; cc = ix * iy;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    a += __shfl_xor(a, off);
+    b += __shfl_xor(b, off);
+    cc += __shfl_xor(cc, off);
+  }
+  if (lane == 0) {
+    const float fa = (float)a, fb = (float)b, fc = (float)cc;
+    const float s = 1.f / (4 * 7 * 255.f);
+    const float s4 = s * s * s * s;
+    const float sum = fa + fb;
+    const float r = ((fa * fb - fc * fc) - 0.04f * sum * sum) * s4;
+    resp[i] = r;
+    key_b[i] = ((unsigned long long)l << 32) | (unsigned)~orb_order_bits(r);
+  }
+}
+
+// ONE workgroup, thread l = level l: the response at rank quota - 1 of the level's segment (float bits)
+__global__ void __launch_bounds__(64)
+k_orb_cut_b(OrbSel S, const unsigned long long* __restrict__ key_bs, int* __restrict__ sc) {
+  const int l = threadIdx.x;
+  if (l >= S.n_levels) return;
+  const int q = orb_quota_of(S, l), m = sc[S_KEPT + l];
+  float cut = -INFINITY;
+  if (S.score_type == 0) {
+    if (q == 0) cut = INFINITY;
+    else if (m > q) cut = orb_order_float(~(unsigned)key_bs[sc[S_BEGIN + l] + q - 1]);
+  }
+  sc[S_CUT_B + l] = __float_as_int(cut);
+}
+
+// ONE workgroup: stable compaction of the survivors, then the sort keys of limitKeypoints (C entries, 0 past the end)
+__global__ void __launch_bounds__(256)
+k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const float* __restrict__ resp, unsigned C,
+              unsigned long long* __restrict__ fin_key, float* __restrict__ fin_resp, unsigned long long* __restrict__ key_c,
+              int* __restrict__ sc) {
+  __shared__ int wave_cnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int total = sc[S_TOTAL];
+  int running = 0;
+  for (int base = 0; base < total; base += 256) {
+    const int i = base + tid;
+    unsigned long long key = 0ull;
+    float r = 0.f;
+    bool f = false;
+    if (i < total) {
+      key = cand_s[i];
+      r = S.score_type == 0 ? resp[i] : (float)(unsigned)(key & 255ull);
+      f = r >= __int_as_float(sc[S_CUT_B + (int)(key >> 40)]);
+    }
+    const unsigned long long bal = __ballot(f);
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = wave_cnt[q];
+      if (q < wave) before += n;
+      all += n;
+    }
+    if (f) {
+      const int o = running + before + __popcll(bal & ((1ull << lane) - 1ull));
+      fin_key[o] = key;
+      fin_resp[o] = r;
+    }
+    running += all;
+    __syncthreads();
+  }
+  const bool limited = S.max_features > 0 && running > S.max_features;
+  for (unsigned o = tid; o < C; o += 256) {
+    unsigned long long k = 0ull;
+    if (o < (unsigned)running)
+      k = limited ? ORB_LIMITED | ((unsigned long long)(__float_as_uint(fin_resp[o]) & 0x7FFFFFFFu) << 31) | o
+                  : ORB_RASTER | (0x7FFFFFFFu - o);
+    key_c[o] = k;
+  }
+  if (tid == 0) sc[S_NFINAL] = limited ? S.max_features : running;
+}
+
+// keypoints in LEVEL coordinates, final order
+__global__ void __launch_bounds__(256)
+k_orb_emit(SfOrbPyr P, const unsigned long long* __restrict__ key_cs, const unsigned long long* __restrict__ fin_key,
+           const float* __restrict__ fin_resp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ kp) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= sc[S_NFINAL] || i >= cap) return;
+  const unsigned long long kc = key_cs[i];
+  const unsigned low = (unsigned)kc & 0x7FFFFFFFu;
+  const unsigned o = (kc & ORB_RASTER) ? 0x7FFFFFFFu - low : low;
+  const unsigned long long key = fin_key[o];
+  const int l = (int)(key >> 40);
+  const unsigned idx = (unsigned)(key >> 8);
+  const SfOrbLevel L = sf_orb_level(P, l);
+  const int y = (int)(idx / (unsigned)L.w), x = (int)(idx - (unsigned)y * (unsigned)L.w);
+  sf_keypoint k;
+  k.x = (float)x; k.y = (float)y; k.size = 31.f * L.scale; k.angle = -1.0f; k.response = fin_resp[o]; k.octave = l; k.class_id = -1;
+  kp[i] = k;
+}
+
+__global__ void __launch_bounds__(256)
+k_orb_finish(SfOrbPyr P, const sf_keypoint* __restrict__ kp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= sc[S_NFINAL] || i >= cap) return;
+  sf_keypoint k = kp[i];
+  const SfOrbLevel L = sf_orb_level(P, k.octave);
+  k.x = k.x * L.scale;
+  k.y = k.y * L.scale;
+  out[i] = k;
+}
+
+}  // namespace
+
+// Level sizes and offsets: scale_l = (float)pow((double)scale_factor, l), size cvRound(W / scale_l) in float
+SfOrbPyr sf_orb_pyr_layout(int width, int height, float scale_factor, int n_levels) {
+  SfOrbPyr P = {};
+  P.n = n_levels;
+  size_t off = 0;
+  for (int l = 0; l < SF_ORB_MAX_LEVELS; ++l) {
+    const float s = l < n_levels ? (float)std::pow((double)scale_factor, (double)l) : 1.f;
+    P.scale[l] = s;
+    P.inv_scale[l] = 1.f / s;
+    P.w[l] = l < n_levels ? (int)lrintf((float)width / s) : 0;
+    P.h[l] = l < n_levels ? (int)lrintf((float)height / s) : 0;
+    P.off[l] = (unsigned)off;
+    off += ((size_t)P.w[l] * P.h[l] + 15) & ~(size_t)15;
+  }
+  P.total = (unsigned)off;
+  return P;
+}
+
+// cv::ORB's features per level, float arithmetic: n_0 = nfeatures (1 - f) / (1 - f^n_levels), f = 1 / scale_factor
+void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota) {
+  const float factor = 1.0f / scale_factor;
+  float nd = (float)nfeatures * (1.0f - factor) / (1.0f - (float)std::pow((double)factor, (double)n_levels));
+  int sum = 0;
+  for (int l = 0; l < SF_ORB_MAX_LEVELS; ++l) quota[l] = 0;
+  for (int l = 0; l < n_levels - 1; ++l) {
+    quota[l] = (int)lrintf(nd);
+    sum += quota[l];
+    nd *= factor;
+  }
+  quota[n_levels - 1] = std::max(nfeatures - sum, 0);
+}
+
+int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P) {
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->orb_pyr, std::max<size_t>(P.total, 16))) != SF_OK) return rc;
+  uint8_t* pyr = (uint8_t*)c->orb_pyr.p;
+  for (int l = 1; l < P.n; ++l) {
+    const uint8_t* src = l == 1 ? d_image : pyr + P.off[l - 1];
+    hipLaunchKernelGGL(k_orb_resize, dim3((P.w[l] + 63) / 64, (P.h[l] + 3) / 4), dim3(256), 0, c->stream, src, P.w[l - 1],
+                       P.h[l - 1], l == 1 ? pitch : P.w[l - 1], pyr + P.off[l], P.w[l], P.h[l]);
+  }
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+
+// Launch sequence on the handle's stream.  The per-level corner counts cross to the host once (the sorts are sized by
+// their sum); the cuts, the survivors and the choice of order stay on the device.
+int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
+                         const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out, int cap,
+                         int32_t* n_out) {
+  const SfOrbPyr P = sf_orb_pyr_layout(width, height, det->scale_factor, det->n_levels);
+  for (int l = 0; l < P.n; ++l)
+    if (P.w[l] < 1 || P.h[l] < 1)
+      return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, width, height, (double)P.scale[l]);
+  int rc;
+  if ((rc = sf_launch_orb_pyramid(c, d_image, pitch, P)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_planes, P.total)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_keys, (size_t)P.total * sizeof(unsigned long long))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_scalar, (size_t)S_WORDS * 4)) != SF_OK) return rc;
+  const uint8_t* pyr = (const uint8_t*)c->orb_pyr.p;
+  uint8_t* score = (uint8_t*)c->gf_planes.p;
+  unsigned long long* keys_f = (unsigned long long*)c->gf_keys.p;
+  int* sc = (int*)c->gf_scalar.p;
+  SF_HIP(c, hipMemsetAsync(sc, 0, (size_t)S_WORDS * 4, c->stream));
+  for (int l = 0; l < P.n; ++l) {
+    if (P.w[l] < 7 || P.h[l] < 7) continue;            // (no FAST domain)
+    sf_launch_fast_level(c, l == 0 ? d_image : pyr + P.off[l], P.w[l], P.h[l], l == 0 ? pitch : P.w[l], det->fast_threshold, 1,
+                         score + P.off[l], keys_f + P.off[l], (unsigned*)sc + S_COUNT + l, (unsigned)(P.w[l] * P.h[l]));
+  }
+  SF_HIP(c, hipGetLastError());
+  unsigned h_count[SF_ORB_MAX_LEVELS] = {};
+  SF_HIP(c, hipMemcpyAsync(h_count, sc + S_COUNT, sizeof h_count, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  OrbSel S = {};
+  S.n_levels = P.n; S.score_type = det->score_type; S.edge = orb->edge_threshold; S.max_features = max_features;
+  sf_orb_quotas(max_features, det->scale_factor, det->n_levels, S.quota);
+  size_t total = 0;
+  for (int l = 0; l < SF_ORB_MAX_LEVELS; ++l) {
+    S.base[l] = l < P.n ? (unsigned)total : 0xFFFFFFFFu;
+    if (l < P.n) total += std::min(h_count[l], (unsigned)(P.w[l] * P.h[l]));
+  }
+  if (n_out) *n_out = 0;
+  if (total == 0) return SF_OK;
+  const unsigned C = (unsigned)total;
+  const int cap_tmp = (int)std::min<size_t>(C, (size_t)max_features);
+  // work lists: seven 64-bit key arrays and two float arrays of C entries, two keypoint arrays of cap_tmp
+  const size_t kp_bytes = ((size_t)cap_tmp * sizeof(sf_keypoint) + 15) & ~(size_t)15;
+  if ((rc = sf_buf_reserve(c, c->orb_work, (size_t)C * (7 * 8 + 2 * 4) + 2 * kp_bytes + 64)) != SF_OK) return rc;
+  unsigned long long* cand = (unsigned long long*)c->orb_work.p;
+  unsigned long long *cand_s = cand + C, *key_b = cand_s + C, *key_bs = key_b + C, *key_c = key_bs + C, *key_cs = key_c + C,
+                     *fin_key = key_cs + C;
+  float* resp = (float*)(fin_key + C);
+  float* fin_resp = resp + C;
+  sf_keypoint* kp1 = (sf_keypoint*)(((uintptr_t)(fin_resp + C) + 15) & ~(uintptr_t)15);
+  sf_keypoint* kp2 = (sf_keypoint*)((char*)kp1 + kp_bytes);
+  auto sort = [&](unsigned long long* in, unsigned long long* out, unsigned b0, unsigned b1, bool desc) -> int {
+    size_t tmp_bytes = 0;
+    if (desc) SF_HIP(c, rocprim::radix_sort_keys_desc(nullptr, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
+    else SF_HIP(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
+    int r = sf_buf_reserve(c, c->gf_tmp, std::max<size_t>(tmp_bytes, 16));
+    if (r != SF_OK) return r;
+    if (desc) SF_HIP(c, rocprim::radix_sort_keys_desc(c->gf_tmp.p, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
+    else SF_HIP(c, rocprim::radix_sort_keys(c->gf_tmp.p, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
+    return SF_OK;
+  };
+  const dim3 block(256), grid((C + 255) / 256);
+  hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, C, cand, sc);
+  hipLaunchKernelGGL(k_orb_cut_a, dim3(1), dim3(64), 0, c->stream, S, sc);
+  hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, cand, C, (const int*)sc);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sort(cand, cand_s, 8, 44, false)) != SF_OK) return rc;
+  if (det->score_type == 0) {
+    hipLaunchKernelGGL(k_orb_harris, dim3((C + 3) / 4), block, 0, c->stream, d_image, pitch, pyr, P,
+                       (const unsigned long long*)cand_s, (const int*)sc, C, resp, key_b);
+    SF_HIP(c, hipGetLastError());
+    if ((rc = sort(key_b, key_bs, 0, 36, false)) != SF_OK) return rc;
+  }
+  hipLaunchKernelGGL(k_orb_cut_b, dim3(1), dim3(64), 0, c->stream, S, (const unsigned long long*)key_bs, sc);
+  hipLaunchKernelGGL(k_orb_compact, dim3(1), block, 0, c->stream, S, (const unsigned long long*)cand_s, (const float*)resp, C,
+                     fin_key, fin_resp, key_c, sc);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sort(key_c, key_cs, 0, 64, true)) != SF_OK) return rc;
+  const dim3 grid_kp((cap_tmp + 255) / 256);
+  hipLaunchKernelGGL(k_orb_emit, grid_kp, block, 0, c->stream, P, (const unsigned long long*)key_cs,
+                     (const unsigned long long*)fin_key, (const float*)fin_resp, (const int*)sc, cap_tmp, kp1);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sf_launch_orb_angle_levels(c, d_image, pitch, P, kp1, cap_tmp, (const int32_t*)(sc + S_NFINAL), orb->edge_threshold,
+                                       kp2)) != SF_OK)
+    return rc;
+  const int written = std::min(cap_tmp, cap);
+  if (written > 0)
+    hipLaunchKernelGGL(k_orb_finish, dim3((written + 255) / 256), block, 0, c->stream, P, (const sf_keypoint*)kp2,
+                       (const int*)sc, written, d_kpts_out);
+  SF_HIP(c, hipGetLastError());
+  if (n_out) {
+    SF_HIP(c, hipMemcpyAsync(n_out, sc + S_NFINAL, 4, hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return SF_OK;
+}

@@ -1,6 +1,6 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
-// detection (GFTT, FAST), stereo correspondence and keyframe extraction (kernels in k_extract.hip, k_gftt.hip,
-// k_fast.hip, k_lk.hip, k_cnn.hip).
+// detection (GFTT, FAST, ORB), stereo correspondence and keyframe extraction (kernels in k_extract.hip, k_gftt.hip,
+// k_fast.hip, k_orb_detect.hip, k_lk.hip, k_cnn.hip).
 #include "sf_host.hpp"
 
 // ---- feature extraction (kernels in k_extract.hip) ----------------------------------
@@ -89,7 +89,9 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
     return SF_OK;
   }
   if (feature_type != 8)
-    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)", feature_type);
+    return sf_fail(c, SF_EINVAL, feature_type == 2 ? "Vis/FeatureType %d (ORB) takes detector parameters: select it with sf_set_feature_type_orb"
+                                                   : "Vis/FeatureType %d is not built (2 = ORB by sf_set_feature_type_orb, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
+                   feature_type);
   if (c->params.desc_type != 0)
     return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
   sf_orb_params o;
@@ -99,6 +101,73 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
   c->orb = o;
   c->feature_type = 8;
   return SF_OK;
+}
+
+// ---- ORB (Vis/FeatureType 2; detector kernels in k_orb_detect.hip) ------------------------------------------------
+extern "C" void sf_orb_detector_defaults(sf_orb_detector_params* p) {
+  if (!p) return;
+  p->scale_factor = 2.0f;      // ORB/ScaleFactor [upstream rtabmap Parameters.h; OpenCV's own default is 1.2]
+  p->n_levels = 3;             // ORB/NLevels [rtabmap; OpenCV 8]
+  p->first_level = 0;          // ORB/FirstLevel
+  p->score_type = 0;           // ORB/ScoreType: HARRIS_SCORE
+  p->fast_threshold = 20;      // ORB/FastThreshold
+}
+
+static int orb_detector_validate(sf_context* c, const sf_orb_detector_params& d, const sf_orb_params& o) {
+  if (!(d.scale_factor > 1.0f) || !(d.scale_factor <= 4.0f))
+    return sf_fail(c, SF_EINVAL, "ORB scale_factor %g outside (1, 4]", (double)d.scale_factor);
+  if (d.n_levels < 1 || d.n_levels > SF_ORB_MAX_LEVELS)
+    return sf_fail(c, SF_EINVAL, "ORB n_levels %d outside 1 .. %d", d.n_levels, SF_ORB_MAX_LEVELS);
+  if (d.first_level != 0) return sf_fail(c, SF_EINVAL, "ORB first_level %d: only 0 is built", d.first_level);
+  if (d.score_type != 0 && d.score_type != 1)
+    return sf_fail(c, SF_EINVAL, "ORB score_type %d unknown (0 = Harris, 1 = FAST)", d.score_type);
+  if (d.fast_threshold < 1 || d.fast_threshold > 254)
+    return sf_fail(c, SF_EINVAL, "ORB fast_threshold %d outside 1 .. 254", d.fast_threshold);
+  if (o.edge_threshold < 16 || o.edge_threshold > 64)
+    return sf_fail(c, SF_EINVAL, "ORB edge_threshold %d outside 16 .. 64 (the radius-15 centroid patch must stay inside a level)", o.edge_threshold);
+  if (o.patch_size != 31) return sf_fail(c, SF_EINVAL, "ORB patch_size %d: only 31 is built", o.patch_size);
+  if (o.wta_k != 2) return sf_fail(c, SF_EINVAL, "ORB wta_k %d: only 2 (32-byte rows) is built", o.wta_k);
+  return SF_OK;
+}
+
+extern "C" int sf_set_feature_type_orb(sf_handle c, const sf_orb_detector_params* det, const sf_orb_params* orb) {
+  if (!c) return SF_EINVAL;
+  if (c->params.desc_type != 0)
+    return sf_fail(c, SF_EINVAL, "ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+  sf_orb_detector_params d;
+  sf_orb_params o;
+  if (det) d = *det; else sf_orb_detector_defaults(&d);
+  if (orb) o = *orb; else sf_orb_defaults(&o);
+  int rc = orb_detector_validate(c, d, o);
+  if (rc != SF_OK) return rc;
+  o.orientation = 1;           // always the intensity centroid, computed by the detector
+  c->orb_det = d;
+  c->orb = o;
+  c->feature_type = 2;
+  return SF_OK;
+}
+
+extern "C" int sf_get_orb_detector(sf_handle c, sf_orb_detector_params* out) {
+  if (!c || !out) return SF_EINVAL;
+  *out = c->orb_det;
+  return SF_OK;
+}
+
+extern "C" int sf_detect_orb_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                    int32_t max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
+                                    sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
+  if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
+  *n_out = 0;
+  if (!d_image || width < 3 || height < 3 || pitch < width)
+    return sf_fail(c, SF_EINVAL, "image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  if (max_features < 1) return sf_fail(c, SF_EINVAL, "ORB shares out max_features = %d keypoints over its levels: it must be >= 1", max_features);
+  const sf_orb_detector_params d = det ? *det : c->orb_det;
+  const sf_orb_params o = orb ? *orb : c->orb;
+  int rc = orb_detector_validate(c, d, o);
+  if (rc != SF_OK) return rc;
+  if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_detect_orb(c, d_image, width, height, pitch, max_features, &d, &o, d_kpts_out, cap, n_out);
 }
 
 extern "C" int sf_get_feature_type(sf_handle c, int32_t* feature_type, sf_orb_params* orb) {
@@ -137,24 +206,26 @@ extern "C" int sf_orb_get_pattern(sf_handle c, int8_t* tests, int32_t cap_bytes,
   return SF_OK;
 }
 
-// The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF)
+// The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF), the pyramid
+// of ORB (NULL: one level)
 struct ExtractKind {
   int bytes;
   const int8_t* d_tests;
   const sf_orb_params* orb;
+  const sf_orb_detector_params* pyr;
 };
 
 static int extract_kind(sf_context* c, ExtractKind* k) {
   int rc;
-  if (c->feature_type == 8) {
+  if (c->feature_type == 8 || c->feature_type == 2) {
     if (c->params.desc_type != 0)
       return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
     if ((rc = orb_ensure(c)) != SF_OK) return rc;
-    *k = {32, (const int8_t*)c->orb_tests.p, &c->orb};
+    *k = {32, (const int8_t*)c->orb_tests.p, &c->orb, c->feature_type == 2 ? &c->orb_det : nullptr};
     return SF_OK;
   }
   if ((rc = brief_ensure(c)) != SF_OK) return rc;
-  *k = {c->brief_bytes, (const int8_t*)c->brief_tests.p, nullptr};
+  *k = {c->brief_bytes, (const int8_t*)c->brief_tests.p, nullptr, nullptr};
   return SF_OK;
 }
 
@@ -287,7 +358,7 @@ extern "C" int sf_extract_keyframe_device(sf_handle c, const uint8_t* d_left, in
   if ((rc = sf_launch_extract(c, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam, kind.bytes,
                               kind.d_tests, (uint32_t*)st.desc.p, (float*)st.xyz.p, (float4*)st.kp.p,
                               (int4*)st.meta.p, st.kcap, st.w, slot, d_desc_out, d_xyz_out, d_kpts_out,
-                              out_rows ? (int32_t*)c->ex_rows.p : nullptr, kind.orb)) != SF_OK)
+                              out_rows ? (int32_t*)c->ex_rows.p : nullptr, kind.orb, kind.pyr)) != SF_OK)
     return rc;
   st.slots += 1;
   if (out_slot) *out_slot = slot;
@@ -337,10 +408,11 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t n = 0;
-  if (c->feature_type == 4) {
+  if (c->feature_type == 4 || c->feature_type == 2) {
     if (!(dp.quality_level > 0.0) || !(dp.min_distance >= 0.0))
       return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
-    rc = sf_detect_fast_device(c, d_left, width, height, width, maxf, nullptr, d_kpts, maxf, &n);
+    rc = c->feature_type == 4 ? sf_detect_fast_device(c, d_left, width, height, width, maxf, nullptr, d_kpts, maxf, &n)
+                              : sf_detect_orb_device(c, d_left, width, height, width, maxf, nullptr, nullptr, d_kpts, maxf, &n);
   } else {
     rc = sf_detect_corners_device(c, d_left, width, height, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
   }
@@ -380,6 +452,8 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
                                                            int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                            float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  if (c->feature_type == 2)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has no batch form yet: use sf_get_features_and_descriptor per keyframe");
   if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
   if (!d_left || !d_right || width < 3 || height < 3 || pitch < width || image_stride < (size_t)pitch * height)
     return sf_fail(c, SF_EINVAL, "stereo pairs missing or malformed (%d x %d, pitch %d, stride %zu)", width, height, pitch, image_stride);

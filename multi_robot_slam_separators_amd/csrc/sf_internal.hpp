@@ -232,7 +232,7 @@ struct sf_context {
   struct sf_netvlad_model* netvlad = nullptr;   // NetVLAD inference (k_cnn.hip): weights + activation buffers
   int brief_bytes = 0;                 // 0: table not uploaded yet
   int8_t brief_host[64 * 8 * 4] = {};
-  // Vis/FeatureType of the extraction (sf_set_feature_type): 6 = GFTT/BRIEF, 4 = FAST/BRIEF, 8 = GFTT/ORB with `orb` and the ORB test
+  // Vis/FeatureType of the extraction (sf_set_feature_type; 2 by sf_set_feature_type_orb): 6 = GFTT/BRIEF, 4 = FAST/BRIEF, 8 = GFTT/ORB with `orb` and the ORB test
   // table (orb_host, uploaded to orb_tests; orb_loaded false: the default set, not generated yet); ex_blur / ex_kpts:
   // the blurred level-0 images and the keypoints with their ORB angles
   int feature_type = 6;
@@ -242,6 +242,11 @@ struct sf_context {
   Buf orb_tests, ex_blur, ex_kpts;
   // 4 = FAST/BRIEF: the detector is k_fast.hip's with these parameters (sf_fast_set_params), the rest is type 6's
   sf_fast_params fast = {20, 1};
+  // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
+  // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
+  // the image at hand; orb_work: the detector's candidate lists
+  sf_orb_detector_params orb_det = {2.0f, 3, 0, 0, 20};
+  Buf orb_pyr, orb_work;
   Buf trace;                    // SF_CHAIN_TRACE builds: uint64[n][32] phase timestamps of the fused kernel
 
   // NN stage
@@ -464,6 +469,40 @@ __host__ __device__ inline bool sf_pnp_dir_gate(int dir, const CorrHeader& h, in
   return h.words_to >= min_inliers && (guided ? h.words_from : rows_from) >= min_inliers;
 }
 
+// ---- ORB pyramid (Vis/FeatureType 2): the level table the kernels take BY VALUE ---------------------------------
+// Level 0 is the caller's image (its own pitch); level l >= 1 lives at pyr + off[l] with pitch w[l].  The blurred
+// copies of the extraction use the same offsets (off[0] = 0, level 0 included).
+#define SF_ORB_MAX_LEVELS 8
+struct SfOrbPyr {
+  int n;
+  int w[SF_ORB_MAX_LEVELS], h[SF_ORB_MAX_LEVELS];
+  unsigned off[SF_ORB_MAX_LEVELS];
+  float scale[SF_ORB_MAX_LEVELS], inv_scale[SF_ORB_MAX_LEVELS];   // scale_l = (float)pow((double)scale_factor, l); 1.f / scale_l
+  unsigned total;                                                  // bytes of all levels, level 0 included
+};
+struct SfOrbLevel { int w, h; unsigned off; float scale, inv_scale; };
+// (masks OR-ed together, not an index and not a chain of selects: the compiler turns both into a copy of the kernel
+//  argument in scratch, indexed at run time.  A level past the table gives an empty level.)
+__device__ __forceinline__ SfOrbLevel sf_orb_level(const SfOrbPyr& P, int l) {
+  int w = 0, h = 0, sc = 0, inv = 0;
+  unsigned off = 0u;
+#pragma unroll
+  for (int i = 0; i < SF_ORB_MAX_LEVELS; ++i) {
+    const int m = -(int)(l == i);
+    w |= m & P.w[i];
+    h |= m & P.h[i];
+    off |= (unsigned)m & P.off[i];
+    sc |= m & __float_as_int(P.scale[i]);
+    inv |= m & __float_as_int(P.inv_scale[i]);
+  }
+  return {w, h, off, __int_as_float(sc), __int_as_float(inv)};
+}
+inline SfOrbPyr sf_orb_single_level(int w, int h) {
+  SfOrbPyr P = {};
+  P.n = 1; P.w[0] = w; P.h[0] = h; P.scale[0] = 1.f; P.inv_scale[0] = 1.f; P.total = (unsigned)((size_t)w * h);
+  return P;
+}
+
 #define SF_HIP(c, expr)                                                                      \
   do {                                                                                       \
     hipError_t _e = (expr);                                                                  \
@@ -510,7 +549,8 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                             const int32_t* d_n, const sf_stereo_camera* cam, int bytes, const int8_t* d_tests,
                             uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap, int w_dwords,
                             int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                            int32_t* d_rows_out, const sf_orb_params* orb = nullptr);   // orb: GFTT/ORB rows, else BRIEF
+                            int32_t* d_rows_out, const sf_orb_params* orb = nullptr,    // orb: GFTT/ORB rows, else BRIEF
+                            const sf_orb_detector_params* pyr = nullptr);   // pyr: ORB rows on the keypoint's own level (type 2)
 int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
                              int32_t* n_out);
@@ -520,6 +560,20 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
                                 int32_t* d_n_out);
+// one level of FAST: k_fast_score + k_fast_candidates as sf_launch_detect_fast queues them (keys = score << 32 | pixel
+// index in arrival order, *count the corners found; count zeroed by the caller)
+void sf_launch_fast_level(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int threshold, int nonmax,
+                          uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap);
+// ORB detector (k_orb_detect.hip); det / orb validated by the caller
+SfOrbPyr sf_orb_pyr_layout(int width, int height, float scale_factor, int n_levels);
+void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota);
+int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P);   // levels >= 1 into c->orb_pyr
+int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
+                         const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out, int cap,
+                         int32_t* n_out);
+// k_orb_angle (k_extract.hip) on keypoints in LEVEL coordinates whose octave names their level; n read on the device
+int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P, const sf_keypoint* d_kpts,
+                               int n_max, const int32_t* d_n, int edge, sf_keypoint* d_kpts_out);
 int sf_launch_stereo_flow(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, int width, int height, int pitch,
                           const sf_keypoint* d_kpts, int n, const sf_stereo_flow_params* prm, float* d_right_xy,
                           uint8_t* d_status, float* d_right_x, float* d_err);
@@ -527,7 +581,7 @@ int sf_launch_extract(sf_context* c, const uint8_t* d_left, int width, int heigh
                       const float* d_right_x, const uint8_t* d_status, int n, const sf_stereo_camera* cam, int bytes,
                       const int8_t* d_tests, uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap,
                       int w_dwords, int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                      int32_t* d_rows_out, const sf_orb_params* orb = nullptr);
+                      int32_t* d_rows_out, const sf_orb_params* orb = nullptr, const sf_orb_detector_params* pyr = nullptr);
 // Assemble sf_result records.
 int sf_launch_finalize(sf_context* c, int n, sf_result* d_out);
 // Ingest kernels

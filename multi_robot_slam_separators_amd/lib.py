@@ -92,6 +92,11 @@ def load():
         "sf_fast_set_params": (C.c_int, [vp, P(_abi.FastParams)]),
         "sf_fast_get_params": (C.c_int, [vp, P(_abi.FastParams)]),
         "sf_detect_fast_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.FastParams), vp, i32, P(i32)]),
+        "sf_orb_detector_defaults": (None, [P(_abi.OrbDetectorParams)]),
+        "sf_set_feature_type_orb": (C.c_int, [vp, P(_abi.OrbDetectorParams), P(_abi.OrbParams)]),
+        "sf_get_orb_detector": (C.c_int, [vp, P(_abi.OrbDetectorParams)]),
+        "sf_detect_orb_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.OrbDetectorParams), P(_abi.OrbParams), vp, i32,
+                                           P(i32)]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
         "sf_stereo_flow_defaults": (None, [P(_abi.StereoFlowParams)]),
         "sf_detector_defaults": (None, [P(_abi.DetectorParams)]),
@@ -178,6 +183,7 @@ EXPORTED = [
     "sf_kernel_name", "sf_stream_placement", "sf_streams_prepare",
     "sf_orb_defaults", "sf_set_feature_type", "sf_get_feature_type", "sf_orb_set_pattern", "sf_orb_get_pattern",
     "sf_fast_defaults", "sf_fast_set_params", "sf_fast_get_params", "sf_detect_fast_device",
+    "sf_orb_detector_defaults", "sf_set_feature_type_orb", "sf_get_orb_detector", "sf_detect_orb_device",
 ]
 
 
@@ -376,7 +382,7 @@ class SeparatorFinder:
 
     def descriptor_bytes(self):
         """Row bytes the extraction calls write with the handle's feature type."""
-        return 32 if self.get_feature_type()[0] == _abi.FEATURE_GFTT_ORB else self.brief_get_pattern().shape[0] // 8
+        return 32 if self.get_feature_type()[0] in (_abi.FEATURE_GFTT_ORB, _abi.FEATURE_ORB) else self.brief_get_pattern().shape[0] // 8
 
     # -- NetVLAD inference (SURVEY section 8(f) rank 4) -------------------------------------------------
     def netvlad_load(self, weights):
@@ -409,6 +415,27 @@ class SeparatorFinder:
         """n_images images [H][W][3] float32 back to back on the device -> d_out [n_images][n_out] (data_handler.py:149-156)."""
         self._check(self._L.sf_netvlad_infer_batch_device(self._h, C.c_void_p(d_images_rgb), n_images, width, height,
                                                           C.c_void_p(d_out), n_out))
+
+    def set_feature_type_orb(self, det=None, orb=None):
+        """Vis/FeatureType 2, ORB on a pyramid: det (_abi.OrbDetectorParams; None = rtabmap's ORB/ defaults) drives the
+        detector, orb (_abi.OrbParams; None = defaults, edge_threshold 16 .. 64) the border and the descriptors."""
+        self._check(self._L.sf_set_feature_type_orb(self._h, C.byref(det) if det is not None else None,
+                                                    C.byref(orb) if orb is not None else None))
+
+    def get_orb_detector(self):
+        p = _abi.OrbDetectorParams()
+        self._check(self._L.sf_get_orb_detector(self._h, C.byref(p)))
+        return p
+
+    def detect_orb_device(self, d_image, width, height, pitch, max_features, d_kpts_out, cap, det=None, orb=None):
+        """cv::ORB::detect + rtabmap's limitKeypoints on the device (det / orb None = the handle's); returns the number
+        of keypoints of the result (<= cap are written)."""
+        n = C.c_int32()
+        self._check(self._L.sf_detect_orb_device(self._h, C.c_void_p(d_image), width, height, pitch, max_features,
+                                                 C.byref(det) if det is not None else None,
+                                                 C.byref(orb) if orb is not None else None,
+                                                 C.c_void_p(d_kpts_out), cap, C.byref(n)))
+        return n.value
 
     def fast_set_params(self, params):
         """The handle's FAST parameters (_abi.FastParams): what feature type 4 detects with."""

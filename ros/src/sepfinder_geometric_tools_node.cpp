@@ -99,7 +99,7 @@ class SepfinderGeometricTools {
     }
 
     // Vis/FeatureType: 6 = GFTT/BRIEF (default), 8 = GFTT/ORB with ORB/EdgeThreshold, 4 = FAST/BRIEF with
-    // FAST/Threshold; see INTEGRATION.md
+    // FAST/Threshold, 2 = ORB with ORB/ScaleFactor, NLevels, FirstLevel, ScoreType, FastThreshold; see INTEGRATION.md
     int feature_type = 6, edge_threshold = 19;
     n.param("feature_type", feature_type, 6);
     n.param("orb_edge_threshold", edge_threshold, 19);
@@ -111,15 +111,28 @@ class SepfinderGeometricTools {
     sf_orb_params orb;
     sf_orb_defaults(&orb);
     orb.edge_threshold = edge_threshold;
-    if (sf_set_feature_type(sf_, feature_type, &orb) != SF_OK)
+    if (feature_type == 2) {
+      sf_orb_detector_params det;
+      sf_orb_detector_defaults(&det);
+      double scale_factor = det.scale_factor;
+      n.param("orb_scale_factor", scale_factor, scale_factor);
+      det.scale_factor = (float)scale_factor;
+      n.param("orb_n_levels", det.n_levels, det.n_levels);
+      n.param("orb_first_level", det.first_level, det.first_level);
+      n.param("orb_score_type", det.score_type, det.score_type);
+      n.param("orb_fast_threshold", det.fast_threshold, det.fast_threshold);
+      if (sf_set_feature_type_orb(sf_, &det, &orb) != SF_OK)
+        ROS_ERROR("feature_type 2: %s", sf_last_error(sf_));
+    } else if (sf_set_feature_type(sf_, feature_type, &orb) != SF_OK) {
       ROS_ERROR("feature_type %d: %s", feature_type, sf_last_error(sf_));
+    }
     // OpenCV's ORB bit_pattern_31_ (256 tests x 4 int8: x1 y1 x2 y2), if the integrator provides it
     if (n.getParam("orb_pattern_file", pattern_file) && !pattern_file.empty()) {
       std::ifstream in(pattern_file.c_str(), std::ios::binary);
       std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
       if (raw.size() != 32 * 8 * 4 || sf_orb_set_pattern(sf_, reinterpret_cast<const int8_t*>(raw.data()), 32) != SF_OK)
         ROS_ERROR("orb_pattern_file %s: 1024 bytes expected (%s)", pattern_file.c_str(), sf_last_error(sf_));
-    } else if (feature_type == 8) {
+    } else if (feature_type == 8 || feature_type == 2) {
       ROS_WARN("no orb_pattern_file: descriptors will not match a robot that runs the reference's OpenCV ORB");
     }
   }
@@ -138,7 +151,7 @@ class SepfinderGeometricTools {
     }
     int32_t bytes = 0, feature_type = 6;
     sf_get_feature_type(sf_, &feature_type, nullptr);
-    if (feature_type == 8) sf_orb_get_pattern(sf_, nullptr, 0, &bytes);   // 32-byte ORB rows
+    if (feature_type == 8 || feature_type == 2) sf_orb_get_pattern(sf_, nullptr, 0, &bytes);   // 32-byte ORB rows
     else sf_brief_get_pattern(sf_, nullptr, 0, &bytes);
     const int cap = 32767;                                            // KeyPointVec.size is an int16
     std::vector<uint8_t> desc((size_t)cap * bytes);
