@@ -30,7 +30,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "sf_internal.hpp"
+#include "sf_front_device.hpp"
 
 namespace {
 
@@ -209,13 +209,6 @@ constexpr int ORB_BLUR_ROWS = 8;
 struct OrbTaps { int t[7]; };          // getGaussianKernel(7, 2) * 256, rounded (host: orb_blur_taps)
 struct OrbUmax { int u[ORB_HALF + 1]; };   // the circular patch's half widths (host: orb_umax)
 
-// cv::borderInterpolate(p, len, BORDER_REFLECT_101)
-__device__ __forceinline__ int reflect101(int p, int len) {
-  if (len == 1) return 0;
-  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
-  return p;
-}
-
 // KeyPointsFilter::runByImageBorder(kpts, size, e): Rect(e, e, w - 2e, h - 2e).contains(Point(cvRound(pt))), and
 // nothing survives when w <= 2e or h <= 2e; corners whose octave is not one of the n_levels levels are dropped as well
 // (one level for GFTT/ORB: another octave than 0)
@@ -379,7 +372,7 @@ k_extract_commit(const sf_keypoint* __restrict__ kpts, const uint8_t* __restrict
                  ExtractBatch B, int group_levels) {
   // (group_levels > 1, the ORB pyramid: the rows of level 0 first, then level 1, ... -- one compaction pass per level)
   __shared__ int wave_cnt[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   if (B.d_n) n = min(n, B.d_n[blockIdx.x]);
   {
     const size_t o = (size_t)blockIdx.x * B.per_image;
@@ -399,18 +392,9 @@ k_extract_commit(const sf_keypoint* __restrict__ kpts, const uint8_t* __restrict
   for (int it = 0; it < chunks * max(group_levels, 1); ++it) {
     const int lv = it / max(chunks, 1), i = (it - lv * chunks) * 256 + tid;
     const bool f = i < n && keep[i] && (group_levels <= 1 || (kpts[i].octave & 255) == lv);
-    const unsigned long long bal = __ballot(f);
-    if (lane == 0) wave_cnt[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int c = wave_cnt[q];
-      if (q < wave) before += c;
-      total += c;
-    }
+    const SfRank rank = sf_block_rank(f, wave_cnt);
     if (f) {
-      const int o = running + before + __popcll(bal & ((1ull << lane) - 1ull));
+      const int o = running + rank.before;
       const sf_keypoint k = kpts[i];
       for (int b = 0; b < rowb; ++b) d8[(size_t)o * rowb + b] = b < bytes ? desc_tmp[(size_t)i * bytes + b] : (uint8_t)0;
       const float p0 = xyz_tmp[3 * i], p1 = xyz_tmp[3 * i + 1], p2 = xyz_tmp[3 * i + 2];
@@ -422,7 +406,7 @@ k_extract_commit(const sf_keypoint* __restrict__ kpts, const uint8_t* __restrict
       if (xyz_out) { xyz_out[3 * o] = p0; xyz_out[3 * o + 1] = p1; xyz_out[3 * o + 2] = p2; }
       if (kp_out) kp_out[o] = k;
     }
-    running += total;
+    running += rank.total;
     __syncthreads();
   }
   if (tid == 0) {
@@ -495,15 +479,18 @@ static OrbUmax orb_umax() {
   return U;
 }
 
-// Launch sequence on the handle's stream; the store slot (kcap >= n, w dwords) has been reserved by the caller.
-// n_img > 1: a batch -- image i at d_left + i * img_stride, its corners / right_x / status / optional copies at + i * n
-// entries, its corner count in d_n[i] (device; `n` is then the per-image capacity), its store slot = slot + i.
+// Launch sequence on the handle's stream; the store slots from `slot` on (c->store: kcap >= n, w dwords) have been
+// reserved by the caller.  Image i at d_left + i * img_stride, its corners / right_x / status / optional copies at + i * n
+// entries, its store slot = slot + i.  d_n (device): the corner count of every image, `n` is then the per-image
+// capacity; null (one image): n is the count.
 int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_stride, int n_img, int width, int height,
                             int pitch, const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n,
-                            const int32_t* d_n, const sf_stereo_camera* cam, int bytes, const int8_t* d_tests,
-                            uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap, int w_dwords,
-                            int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                            int32_t* d_rows_out, const sf_orb_params* orb, const sf_orb_detector_params* pyr) {
+                            const int32_t* d_n, const sf_stereo_camera* cam, const ExtractKind& kind, int slot,
+                            uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out, int32_t* d_rows_out) {
+  const int bytes = kind.bytes;
+  const sf_orb_params* orb = kind.orb;
+  const sf_orb_detector_params* pyr = kind.pyr;
+  const Store& st = c->store;
   int rc;
   if (pyr && (!orb || n_img != 1)) return sf_fail(c, SF_EINVAL, "ORB on a pyramid: one keyframe per call");
   if (orb && bytes != ORB_BYTES) return sf_fail(c, SF_EINVAL, "ORB rows are %d bytes, not %d", ORB_BYTES, bytes);
@@ -529,9 +516,6 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                        d_left, width, height, pitch, (uint8_t*)c->ex_blur.p, orb_blur_taps(), B);
   } else {                                               // the pyramid and a blurred copy of every level, same offsets
     P = sf_orb_pyr_layout(width, height, pyr->scale_factor, pyr->n_levels);
-    for (int l = 0; l < P.n; ++l)
-      if (P.w[l] < 1 || P.h[l] < 1)
-        return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, width, height, (double)P.scale[l]);
     B.s_stride = 0;
     if ((rc = sf_launch_orb_pyramid(c, d_left, pitch, P)) != SF_OK) return rc;
     if ((rc = sf_buf_reserve(c, c->ex_blur, P.total)) != SF_OK) return rc;
@@ -554,7 +538,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
     const long long threads = (long long)n * bytes;
     if (!orb) {
       hipLaunchKernelGGL(k_extract_points, dim3((unsigned)((threads + 255) / 256), n_img), dim3(256), 0, c->stream, S, width,
-                         height, d_kpts, d_right_x, d_status, n, bytes, d_tests, ec, (uint8_t*)c->ex_desc.p,
+                         height, d_kpts, d_right_x, d_status, n, bytes, kind.d_tests, ec, (uint8_t*)c->ex_desc.p,
                          (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);
     } else {
       if (orb->orientation && !pyr) {                     // the keypoints with their angles, for the samples and the commit
@@ -566,14 +550,14 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
       hipLaunchKernelGGL(k_orb_points, dim3((unsigned)((threads + 255) / 256), n_img), dim3(256), 0, c->stream, d_left,
                          (const uint8_t*)c->ex_blur.p, width, height, pitch, (const uint8_t*)(pyr ? c->orb_pyr.p : nullptr), P,
                          kp_commit, d_right_x, d_status, n,
-                         orb->edge_threshold, d_tests, ec, (uint8_t*)c->ex_desc.p, (float*)c->ex_xyz.p,
+                         orb->edge_threshold, kind.d_tests, ec, (uint8_t*)c->ex_desc.p, (float*)c->ex_xyz.p,
                          (uint8_t*)c->ex_keep.p, B);
     }
   }
   hipLaunchKernelGGL(k_extract_commit, dim3(n_img), dim3(256), 0, c->stream, kp_commit, (const uint8_t*)c->ex_desc.p,
-                     (const float*)c->ex_xyz.p, (const uint8_t*)c->ex_keep.p, n, bytes, d_right_x != nullptr, st_desc,
-                     st_xyz, st_kp, st_meta, kcap, w_dwords, slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out, B,
-                     pyr ? P.n : 0);
+                     (const float*)c->ex_xyz.p, (const uint8_t*)c->ex_keep.p, n, bytes, d_right_x != nullptr,
+                     (uint32_t*)st.desc.p, (float*)st.xyz.p, (float4*)st.kp.p, (int4*)st.meta.p, st.kcap, st.w, slot,
+                     d_desc_out, d_xyz_out, d_kpts_out, d_rows_out, B, pyr ? P.n : 0);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }
@@ -588,14 +572,4 @@ int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_image, int pitch,
                      (const uint8_t*)c->orb_pyr.p, P, d_kpts, n_max, edge, orb_umax(), d_kpts_out, B);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
-}
-
-int sf_launch_extract(sf_context* c, const uint8_t* d_left, int width, int height, int pitch, const sf_keypoint* d_kpts,
-                      const float* d_right_x, const uint8_t* d_status, int n, const sf_stereo_camera* cam, int bytes,
-                      const int8_t* d_tests, uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap,
-                      int w_dwords, int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                      int32_t* d_rows_out, const sf_orb_params* orb, const sf_orb_detector_params* pyr) {
-  return sf_launch_extract_batch(c, d_left, 0, 1, width, height, pitch, d_kpts, d_right_x, d_status, n, nullptr, cam, bytes,
-                                 d_tests, st_desc, st_xyz, st_kp, st_meta, kcap, w_dwords, slot, d_desc_out, d_xyz_out,
-                                 d_kpts_out, d_rows_out, orb, pyr);
 }

@@ -21,21 +21,19 @@
 //   k_fast_rekey       decides the order ON THE DEVICE once the count is known: corners <= max_features (or no limit)
 //                      -> raster order, the keys become (1 << 40 | (2^32 - 1 - index) << 8 | score); otherwise they
 //                      stay, and the descending sort below gives descending response with ties by descending index.
-//                      In a batch it also writes the segment bounds of the segmented sort.
-//   rocprim radix sort keys descending (bits 0 .. 40), segmented for a batch.  Keys are unique (the pixel index), so
+//                      It also writes the segment bounds that a batch's segmented sort reads.
+//   sf_sort_keys (sf_sort.hip) descending (bits 0 .. 40), segmented for a batch.  Keys are unique (the pixel index), so
 //                      the order does not depend on the arrival order of the atomics.
 //   k_fast_emit        the first min(count, max_features) keys -> sf_keypoint {x, y, 7, -1, score, 0, -1}
 // FAST has no minimum-distance rule: no selection bitmap, no image-size limit beyond the 2^26 pixels of the index.
+// The two launchers share fast_front (workspace, score / candidates / rekey); their tails differ: the single call sizes
+// a plain sort by the corner count on the host, the batch sorts the segments whose bounds k_fast_rekey wrote.
 #include <hip/hip_runtime.h>
-
-#include <cstring>   // (rocprim's texture_cache_iterator.hpp calls memset without declaring it)
-
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cstdint>
 
-#include "sf_internal.hpp"
+#include "sf_front_device.hpp"
 
 namespace {
 
@@ -152,11 +150,7 @@ k_fast_candidates(const uint8_t* __restrict__ score, int w, int h, int nonmax, u
       }
     }
   }
-  __syncthreads();
-  if (threadIdx.x == 0 && s_n) s_base = atomicAdd(count, s_n);
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < s_n; i += 256)
-    if (s_base + i < cap) keys[s_base + i] = s_keys[i];
+  sf_flush_staged_keys(s_keys, &s_n, &s_base, keys, count, cap);
 }
 
 // blockIdx.y = image.  Raster order when the corners fit the limit; segment bounds for the batch's sort.
@@ -192,68 +186,57 @@ k_fast_emit(const unsigned long long* __restrict__ keys, int n, int w, int limit
   const unsigned idx = raster ? 0xFFFFFFFFu - (unsigned)(key >> 8) : (unsigned)key;
   const unsigned s = raster ? (unsigned)(key & 0xFFull) : (unsigned)(key >> 32);
   const int y = (int)(idx / (unsigned)w), x = (int)(idx - (unsigned)y * (unsigned)w);
-  sf_keypoint k;
-  k.x = (float)x; k.y = (float)y; k.size = 7.0f; k.angle = -1.0f; k.response = (float)s; k.octave = 0; k.class_id = -1;
-  kp_out[i] = k;
+  kp_out[i] = sf_make_keypoint((float)x, (float)y, 7.0f, (float)s, 0);
 }
 
 constexpr int FAST_REKEY_BLOCKS = 32;
 
 }  // namespace
 
-// One image, one level: the two launches every single-image detector shares (FAST/BRIEF here, ORB's pyramid levels in
-// k_orb_detect.hip)
-void sf_launch_fast_level(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int threshold, int nonmax,
-                          uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap) {
+// One level on n_img images of one size (blockIdx.z = image): the two launches every detector shares (FAST/BRIEF here,
+// ORB's pyramid levels in k_orb_detect.hip)
+void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int threshold, int nonmax, uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap) {
   const dim3 block(256);
-  hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH), block, 0, c->stream,
-                     d_image, width, height, pitch, threshold, score, (size_t)0, (size_t)0);
-  hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS), block, 0,
-                     c->stream, (const uint8_t*)score, width, height, nonmax, keys, count, key_cap, (size_t)0);
+  hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH, n_img), block, 0,
+                     c->stream, d_images, width, height, pitch, threshold, score, img_stride, (size_t)key_cap);
+  hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS, n_img), block, 0,
+                     c->stream, (const uint8_t*)score, width, height, nonmax, keys, count, key_cap, (size_t)key_cap);
+}
+
+// The front half of both launchers -- workspace and the three front kernels for n_img images of one size: every image's
+// keys, in the form of the order that applies to it, their count and its segment of the key array are on the device when
+// the stream gets there
+static int fast_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                      int max_features, const sf_fast_params* prm, SfDetectorWork* F) {
+  int rc = sf_detector_work(c, width, height, n_img, (size_t)width * height, F);
+  if (rc != SF_OK) return rc;
+  sf_launch_fast_level(c, d_images, img_stride, n_img, width, height, pitch, prm->threshold, prm->nonmax_suppression,
+                       (uint8_t*)c->gf_planes.p, F->keys, F->count, F->key_cap);
+  hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, n_img), dim3(256), 0, c->stream, F->keys, (const unsigned*)F->count,
+                     F->key_cap, max_features, F->seg_begin, F->seg_end);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
 }
 
 // Launch sequence on the handle's stream.  The corner count crosses to the host once (the sort is sized by it); which
 // order applies is decided on the device before that.
 int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
                           const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out) {
-  const size_t np = (size_t)width * height;
+  SfDetectorWork F;
   int rc;
-  if ((rc = sf_buf_reserve(c, c->gf_planes, np)) != SF_OK) return rc;
-  const unsigned key_cap = (unsigned)np;
-  if ((rc = sf_buf_reserve(c, c->gf_keys, (size_t)key_cap * 2 * sizeof(unsigned long long))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_scalar, 64)) != SF_OK) return rc;
-  uint8_t* score = (uint8_t*)c->gf_planes.p;
-  unsigned long long* keys = (unsigned long long*)c->gf_keys.p;
-  unsigned long long* keys_sorted = keys + key_cap;
-  unsigned* count = (unsigned*)c->gf_scalar.p + 1;
-  int32_t* d_n_out = (int32_t*)c->gf_scalar.p + 2;
-  SF_HIP(c, hipMemsetAsync(c->gf_scalar.p, 0, 64, c->stream));
-  const dim3 block(256);
-  sf_launch_fast_level(c, d_image, width, height, pitch, prm->threshold, prm->nonmax_suppression, score, keys, count, key_cap);
-  hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, 1), block, 0, c->stream, keys, (const unsigned*)count, key_cap,
-                     max_features, (unsigned*)nullptr, (unsigned*)nullptr);
-  SF_HIP(c, hipGetLastError());
+  if ((rc = fast_front(c, d_image, 0, 1, width, height, pitch, max_features, prm, &F)) != SF_OK) return rc;
   unsigned h_count = 0;
-  SF_HIP(c, hipMemcpyAsync(&h_count, count, 4, hipMemcpyDeviceToHost, c->stream));
-  SF_HIP(c, hipStreamSynchronize(c->stream));
-  const int n = (int)std::min(h_count, key_cap);
-  if (n > 0) {
-    size_t tmp_bytes = 0;
-    SF_HIP(c, rocprim::radix_sort_keys_desc(nullptr, tmp_bytes, keys, keys_sorted, (size_t)n, 0, FAST_KEY_BITS, c->stream));
-    if ((rc = sf_buf_reserve(c, c->gf_tmp, std::max<size_t>(tmp_bytes, 16))) != SF_OK) return rc;
-    SF_HIP(c, rocprim::radix_sort_keys_desc(c->gf_tmp.p, tmp_bytes, keys, keys_sorted, (size_t)n, 0, FAST_KEY_BITS, c->stream));
-  }
+  if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
+  const int n = (int)std::min(h_count, F.key_cap);
+  if (n > 0 && (rc = sf_sort_keys(c, F.keys, F.keys_sorted, (size_t)n, 0, FAST_KEY_BITS, true)) != SF_OK) return rc;
   const int total = (max_features > 0 && n > max_features) ? max_features : n;
   const int written = std::min(total, cap);
-  hipLaunchKernelGGL(k_fast_emit, dim3(std::max((written + 255) / 256, 1), 1), block, 0, c->stream,
-                     (const unsigned long long*)keys_sorted, n, width, max_features, d_kpts_out, cap, d_n_out,
+  hipLaunchKernelGGL(k_fast_emit, dim3(std::max((written + 255) / 256, 1), 1), dim3(256), 0, c->stream,
+                     (const unsigned long long*)F.keys_sorted, n, width, max_features, d_kpts_out, cap, F.n_single,
                      (const unsigned*)nullptr, 0u);
   SF_HIP(c, hipGetLastError());
-  if (n_out) {
-    SF_HIP(c, hipMemcpyAsync(n_out, d_n_out, 4, hipMemcpyDeviceToHost, c->stream));
-    SF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return SF_OK;
+  return n_out ? sf_word_to_host(c, F.n_single, n_out) : SF_OK;
 }
 
 // The detector on a batch of images of one size, no host round trip: corner counts and the choice of order stay on the
@@ -262,38 +245,16 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
                                 int32_t* d_n_out) {
-  const size_t np = (size_t)width * height;
-  if (np * (size_t)n_img > 0xFFFFFFFFull) return sf_fail(c, SF_ERANGE, "batched corner detection: %d images of %zu pixels", n_img, np);
+  SfDetectorWork F;
   int rc;
-  if ((rc = sf_buf_reserve(c, c->gf_planes, np * n_img)) != SF_OK) return rc;
-  const unsigned key_cap = (unsigned)np;
-  if ((rc = sf_buf_reserve(c, c->gf_keys, (size_t)key_cap * 2 * sizeof(unsigned long long) * n_img)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_scalar, 64 + (size_t)n_img * 16)) != SF_OK) return rc;
-  uint8_t* score = (uint8_t*)c->gf_planes.p;
-  unsigned long long* keys = (unsigned long long*)c->gf_keys.p;
-  unsigned long long* keys_sorted = keys + (size_t)key_cap * n_img;
-  unsigned* count = (unsigned*)((char*)c->gf_scalar.p + 64);
-  unsigned* seg_begin = count + n_img;
-  unsigned* seg_end = seg_begin + n_img;
-  SF_HIP(c, hipMemsetAsync(count, 0, (size_t)n_img * 4, c->stream));
-  const dim3 block(256);
-  hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH, n_img), block, 0,
-                     c->stream, d_images, width, height, pitch, prm->threshold, score, img_stride, np);
-  hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS, n_img), block, 0,
-                     c->stream, (const uint8_t*)score, width, height, prm->nonmax_suppression, keys, count, key_cap, np);
-  hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, n_img), block, 0, c->stream, keys, (const unsigned*)count, key_cap,
-                     max_features, seg_begin, seg_end);
-  SF_HIP(c, hipGetLastError());
-  size_t tmp_bytes = 0;
-  SF_HIP(c, rocprim::segmented_radix_sort_keys_desc(nullptr, tmp_bytes, keys, keys_sorted, (unsigned)((size_t)key_cap * n_img),
-                                                    (unsigned)n_img, seg_begin, seg_end, 0, FAST_KEY_BITS, c->stream));
-  if ((rc = sf_buf_reserve(c, c->gf_tmp, std::max<size_t>(tmp_bytes, 16))) != SF_OK) return rc;
-  SF_HIP(c, rocprim::segmented_radix_sort_keys_desc(c->gf_tmp.p, tmp_bytes, keys, keys_sorted, (unsigned)((size_t)key_cap * n_img),
-                                                    (unsigned)n_img, seg_begin, seg_end, 0, FAST_KEY_BITS, c->stream));
+  if ((rc = fast_front(c, d_images, img_stride, n_img, width, height, pitch, max_features, prm, &F)) != SF_OK) return rc;
+  if ((rc = sf_sort_keys_segmented_desc(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img,
+                                        F.seg_begin, F.seg_end, 0, FAST_KEY_BITS)) != SF_OK)
+    return rc;
   const int written = std::min(max_features, cap);
-  hipLaunchKernelGGL(k_fast_emit, dim3(std::max((written + 255) / 256, 1), n_img), block, 0, c->stream,
-                     (const unsigned long long*)keys_sorted, 0, width, max_features, d_kpts_out, cap, d_n_out,
-                     (const unsigned*)count, key_cap);
+  hipLaunchKernelGGL(k_fast_emit, dim3(std::max((written + 255) / 256, 1), n_img), dim3(256), 0, c->stream,
+                     (const unsigned long long*)F.keys_sorted, 0, width, max_features, d_kpts_out, cap, d_n_out,
+                     (const unsigned*)F.count, F.key_cap);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }

@@ -9,33 +9,25 @@
 //   k_gftt_eig         per pixel: 3 x 3 sums of the products, eig = (a + c) - sqrt((a - c)^2 + b^2); max(eig)
 //   k_gftt_candidates  interior pixels above quality * max that equal the maximum of their thresholded 3 x 3
 //                      neighbourhood -> 64-bit keys (response bits << 32 | pixel index), one global atomic per workgroup
-//   rocprim radix sort keys descending = decreasing response, ties by decreasing address (featureselect.cpp's
+//   sf_sort_keys (sf_sort.hip) descending = decreasing response, ties by decreasing address (featureselect.cpp's
 //                      greaterThanPtr); a plain library sort, the only library call of the product's compute path
 //   k_gftt_select_lds  ONE wavefront walks the sorted list 64 candidates at a time: every lane tests its candidate
 //                      against the corners already taken (a bitmap of the image in LDS), the 64 lanes settle
 //                      conflicts among themselves in list order (in rounds, not in 64 turns), the survivors are
 //                      appended -- the sequential minDistance rule of goodFeaturesToTrack, 64 candidates per step.
 //   k_gftt_select      the same with the taken corners in per-cell lists in HBM: images whose bitmap does not fit
-//                      LDS (above about 1.2 Mpixel), or SF_GFTT_LISTS=1.
+//                      LDS (above about 1.2 Mpixel).
+// The two launchers share gftt_front (workspace, the three front kernels); their tails differ: the single call sizes a
+// plain sort by the candidate count on the host, the batch sorts segments whose bounds stay on the device.
 #include <hip/hip_runtime.h>
-
-#include <cstring>   // (rocprim's texture_cache_iterator.hpp calls memset without declaring it)
-
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 
-#include "sf_internal.hpp"
+#include "sf_front_device.hpp"
 
 namespace {
-
-__device__ __forceinline__ int refl101(int i, int n) {
-  if (i < 0) i = -i;
-  if (i >= n) i = 2 * n - 2 - i;
-  return i;
-}
 
 __global__ void __launch_bounds__(256)
 k_gftt_products(const uint8_t* __restrict__ img, int w, int h, int pitch, float s1, float s2, float* __restrict__ dxx,
@@ -45,10 +37,10 @@ k_gftt_products(const uint8_t* __restrict__ img, int w, int h, int pitch, float 
   if (x >= w || y >= h) return;
   img += blockIdx.z * img_stride;
   dxx += blockIdx.z * plane_stride; dxy += blockIdx.z * plane_stride; dyy += blockIdx.z * plane_stride;
-  const int xm = refl101(x - 1, w), xp = refl101(x + 1, w);
-  const uint8_t* ru = img + (size_t)refl101(y - 1, h) * pitch;
+  const int xm = reflect101(x - 1, w), xp = reflect101(x + 1, w);
+  const uint8_t* ru = img + (size_t)reflect101(y - 1, h) * pitch;
   const uint8_t* r0 = img + (size_t)y * pitch;
-  const uint8_t* rd = img + (size_t)refl101(y + 1, h) * pitch;
+  const uint8_t* rd = img + (size_t)reflect101(y + 1, h) * pitch;
   const float um = ru[xm], uc = ru[x], up = ru[xp], cm = r0[xm], cp = r0[xp], dm = rd[xm], dc = rd[x], dp = rd[xp];
   const float dx = s2 * (cp - cm) + s1 * ((up - um) + (dp - dm));
   const float cu = s2 * uc + s1 * (um + up);
@@ -74,7 +66,7 @@ k_gftt_eig(const float* __restrict__ dxx, const float* __restrict__ dxy, const f
   max_bits += blockIdx.z;
   float e = 0.f;
   if (x < w && y < h) {
-    const int xm = refl101(x - 1, w), xp = refl101(x + 1, w), yu = refl101(y - 1, h), yd = refl101(y + 1, h);
+    const int xm = reflect101(x - 1, w), xp = reflect101(x + 1, w), yu = reflect101(y - 1, h), yd = reflect101(y + 1, h);
     const float a = box3(dxx, w, yu, y, yd, xm, x, xp) * 0.5f, b = box3(dxy, w, yu, y, yd, xm, x, xp),
                 c = box3(dyy, w, yu, y, yd, xm, x, xp) * 0.5f;
     e = (a + c) - sqrtf((a - c) * (a - c) + b * b);
@@ -132,11 +124,7 @@ k_gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __rest
       }
     }
   }
-  __syncthreads();
-  if (threadIdx.x == 0 && s_n) s_base = atomicAdd(count, s_n);
-  __syncthreads();
-  for (unsigned i = threadIdx.x; i < s_n; i += 256)
-    if (s_base + i < cap) keys[s_base + i] = s_keys[i];
+  sf_flush_staged_keys(s_keys, &s_n, &s_base, keys, count, cap);
 }
 
 __global__ void __launch_bounds__(64)
@@ -181,11 +169,7 @@ k_gftt_select(const unsigned long long* __restrict__ keys, int n, int w, int cel
       const int o = out + rank;
       pts[o] = make_int2(x, y);
       if (cell > 0) next[o] = atomicExch(&head[(y / cell) * gw + x / cell], o);
-      if (o < cap) {
-        sf_keypoint k;
-        k.x = (float)x; k.y = (float)y; k.size = 3.0f; k.angle = -1.0f; k.response = 0.0f; k.octave = 0; k.class_id = -1;
-        kp_out[o] = k;
-      }
+      if (o < cap) kp_out[o] = sf_make_keypoint((float)x, (float)y, 3.0f, 0.0f, 0);
     }
     out += min(cnt, room);
     __threadfence();          // the lists written above are read by every lane in the next step
@@ -279,15 +263,51 @@ k_gftt_select_lds(const unsigned long long* __restrict__ keys, int n, int w, int
     if (good && rank < room) {
       const int o = out + rank;
       if (radius > 0) atomicOr(&gf_bm[y * wpr + (x >> 5)], 1u << (x & 31));
-      if (o < cap) {
-        sf_keypoint k;
-        k.x = (float)x; k.y = (float)y; k.size = 3.0f; k.angle = -1.0f; k.response = 0.0f; k.octave = 0; k.class_id = -1;
-        kp_out[o] = k;
-      }
+      if (o < cap) kp_out[o] = sf_make_keypoint((float)x, (float)y, 3.0f, 0.0f, 0);
     }
     out += min(cnt, room);
   }
   if (lane == 0) *n_out = out;
+}
+
+__global__ void k_gftt_segments(const unsigned* __restrict__ count, unsigned key_cap, int n, unsigned* __restrict__ begin,
+                                unsigned* __restrict__ end) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { begin[i] = (unsigned)i * key_cap; end[i] = (unsigned)i * key_cap + min(count[i], key_cap); }
+}
+
+// The front half of both launchers -- workspace and the three front kernels for n_img images of one size (blockIdx.z =
+// image): every image's candidate keys and their count are on the device when the stream gets there
+int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+               double quality_level, SfDetectorWork* F) {
+  const size_t np = (size_t)width * height;
+  int rc = sf_detector_work(c, width, height, n_img, np * 4 * sizeof(float), F);
+  if (rc != SF_OK) return rc;
+  float* dxx = (float*)c->gf_planes.p;                    // image i: planes at + i * 4 np (dxx, dxy, dyy, eig)
+  float* dxy = dxx + np;
+  float* dyy = dxy + np;
+  float* eig = dyy + np;
+  const size_t plane_stride = 4 * np;
+  const double scale = 1.0 / ((double)(1 << 2) * 3.0 * 255.0);
+  const dim3 grid((width + 63) / 64, (height + 3) / 4, n_img), block(256);
+  hipLaunchKernelGGL(k_gftt_products, grid, block, 0, c->stream, d_images, width, height, pitch, (float)(1.0 * scale),
+                     (float)(2.0 * scale), dxx, dxy, dyy, img_stride, plane_stride);
+  hipLaunchKernelGGL(k_gftt_eig, grid, block, 0, c->stream, (const float*)dxx, (const float*)dxy, (const float*)dyy, width,
+                     height, eig, F->max_bits, plane_stride);
+  const dim3 grid_c((width + 63) / 64, (height + 4 * GFTT_CAND_TILES - 1) / (4 * GFTT_CAND_TILES), n_img);
+  hipLaunchKernelGGL(k_gftt_candidates, grid_c, block, 0, c->stream, (const float*)eig, width, height, (const int*)F->max_bits,
+                     quality_level, F->keys, F->count, F->key_cap, plane_stride);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+
+// k_gftt_select_lds may ask for up to 150 KB of dynamic LDS: said once per handle
+int gftt_select_lds_attr(sf_context* c) {
+  if (!c->gf_select_attr) {
+    SF_HIP(c, hipFuncSetAttribute((const void*)k_gftt_select_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    c->gf_select_attr = true;
+  }
+  return SF_OK;
 }
 
 }  // namespace
@@ -296,53 +316,22 @@ k_gftt_select_lds(const unsigned long long* __restrict__ keys, int n, int w, int
 int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
                              int32_t* n_out) {
-  const size_t np = (size_t)width * height;
+  SfDetectorWork F;
   int rc;
-  if ((rc = sf_buf_reserve(c, c->gf_planes, np * 4 * sizeof(float))) != SF_OK) return rc;
-  const unsigned key_cap = (unsigned)np;
-  if ((rc = sf_buf_reserve(c, c->gf_keys, (size_t)key_cap * 2 * sizeof(unsigned long long))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_scalar, 64)) != SF_OK) return rc;
-  float* dxx = (float*)c->gf_planes.p;
-  float* dxy = dxx + np;
-  float* dyy = dxy + np;
-  float* eig = dyy + np;
-  unsigned long long* keys = (unsigned long long*)c->gf_keys.p;
-  unsigned long long* keys_sorted = keys + key_cap;
-  int* max_bits = (int*)c->gf_scalar.p;
-  unsigned* count = (unsigned*)c->gf_scalar.p + 1;
-  int32_t* d_n_out = (int32_t*)c->gf_scalar.p + 2;
-  SF_HIP(c, hipMemsetAsync(c->gf_scalar.p, 0, 64, c->stream));
-  const double scale = 1.0 / ((double)(1 << 2) * 3.0 * 255.0);
-  const dim3 grid((width + 63) / 64, (height + 3) / 4), block(256);
-  hipLaunchKernelGGL(k_gftt_products, grid, block, 0, c->stream, d_image, width, height, pitch, (float)(1.0 * scale),
-                     (float)(2.0 * scale), dxx, dxy, dyy, (size_t)0, (size_t)0);
-  hipLaunchKernelGGL(k_gftt_eig, grid, block, 0, c->stream, (const float*)dxx, (const float*)dxy, (const float*)dyy, width,
-                     height, eig, max_bits, (size_t)0);
-  const dim3 grid_c((width + 63) / 64, (height + 4 * GFTT_CAND_TILES - 1) / (4 * GFTT_CAND_TILES));
-  hipLaunchKernelGGL(k_gftt_candidates, grid_c, block, 0, c->stream, (const float*)eig, width, height, (const int*)max_bits,
-                     quality_level, keys, count, key_cap, (size_t)0);
-  SF_HIP(c, hipGetLastError());
+  if ((rc = gftt_front(c, d_image, 0, 1, width, height, pitch, quality_level, &F)) != SF_OK) return rc;
   unsigned h_count = 0;
-  SF_HIP(c, hipMemcpyAsync(&h_count, count, 4, hipMemcpyDeviceToHost, c->stream));
-  SF_HIP(c, hipStreamSynchronize(c->stream));
-  const int n = (int)std::min(h_count, key_cap);
-  if (n > 0) {
-    size_t tmp_bytes = 0;
-    SF_HIP(c, rocprim::radix_sort_keys_desc(nullptr, tmp_bytes, keys, keys_sorted, (size_t)n, 0, 64, c->stream));
-    if ((rc = sf_buf_reserve(c, c->gf_tmp, std::max<size_t>(tmp_bytes, 16))) != SF_OK) return rc;
-    SF_HIP(c, rocprim::radix_sort_keys_desc(c->gf_tmp.p, tmp_bytes, keys, keys_sorted, (size_t)n, 0, 64, c->stream));
-  }
+  if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
+  const int n = (int)std::min(h_count, F.key_cap);
+  if (n > 0 && (rc = sf_sort_keys(c, F.keys, F.keys_sorted, (size_t)n, 0, 64, true)) != SF_OK) return rc;
   // taken corners as a bitmap in LDS when the image fits (up to about 1.2 Mpixel), cell lists in HBM otherwise
   const int wpr = (width + 31) / 32;
   const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
   const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
-  if (bm_bytes <= 150 * 1024 && radius <= GFTT_MAX_RADIUS && !getenv("SF_GFTT_LISTS")) {
-    if (!c->gf_select_attr) {
-      SF_HIP(c, hipFuncSetAttribute((const void*)k_gftt_select_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      c->gf_select_attr = true;
-    }
-    hipLaunchKernelGGL(k_gftt_select_lds, dim3(1), dim3(256), bm_bytes, c->stream, (const unsigned long long*)keys_sorted, n,
-                       width, height, wpr, (float)(min_distance * min_distance), radius, max_corners, d_kpts_out, cap, d_n_out);
+  const float md2 = (float)(min_distance * min_distance);
+  if (bm_bytes <= 150 * 1024 && radius <= GFTT_MAX_RADIUS) {
+    if ((rc = gftt_select_lds_attr(c)) != SF_OK) return rc;
+    hipLaunchKernelGGL(k_gftt_select_lds, dim3(1), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, n,
+                       width, height, wpr, md2, radius, max_corners, d_kpts_out, cap, F.n_single);
   } else {
     const int cell = min_distance >= 1.0 ? (int)std::lrint(min_distance) : 0;
     const int gw = cell > 0 ? (width + cell - 1) / cell : 1, gh = cell > 0 ? (height + cell - 1) / cell : 1;
@@ -353,25 +342,12 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
     int* next = head + (size_t)gw * gh;
     int2* pts = (int2*)(head + n_int);
     SF_HIP(c, hipMemsetAsync(head, 0xFF, (size_t)gw * gh * sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_gftt_select, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)keys_sorted, n, width, cell,
-                       gw, gh, (float)(min_distance * min_distance), max_corners, head, next, pts, d_kpts_out, cap, d_n_out);
+    hipLaunchKernelGGL(k_gftt_select, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)F.keys_sorted, n, width, cell,
+                       gw, gh, md2, max_corners, head, next, pts, d_kpts_out, cap, F.n_single);
   }
   SF_HIP(c, hipGetLastError());
-  if (n_out) {
-    SF_HIP(c, hipMemcpyAsync(n_out, d_n_out, 4, hipMemcpyDeviceToHost, c->stream));
-    SF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return SF_OK;
+  return n_out ? sf_word_to_host(c, F.n_single, n_out) : SF_OK;
 }
-
-
-namespace {
-__global__ void k_gftt_segments(const unsigned* __restrict__ count, unsigned key_cap, int n, unsigned* __restrict__ begin,
-                                unsigned* __restrict__ end) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) { begin[i] = (unsigned)i * key_cap; end[i] = (unsigned)i * key_cap + min(count[i], key_cap); }
-}
-}  // namespace
 
 // The detector on a batch of images of one size, no host round trip: candidate counts stay on the device (a segmented
 // sort takes the place of the sort sized by the host), one selection workgroup per image.  d_kpts_out [n_img][cap],
@@ -379,55 +355,24 @@ __global__ void k_gftt_segments(const unsigned* __restrict__ count, unsigned key
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
                                    sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out) {
-  const size_t np = (size_t)width * height;
   const int wpr = (width + 31) / 32;
   const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
   const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
   if (bm_bytes > 150 * 1024 || radius > GFTT_MAX_RADIUS)
     return sf_fail(c, SF_ERANGE, "batched corner detection: %d x %d image does not fit the LDS selection bitmap", width, height);
-  if (np * (size_t)n_img > 0xFFFFFFFFull) return sf_fail(c, SF_ERANGE, "batched corner detection: %d images of %zu pixels", n_img, np);
+  SfDetectorWork F;
   int rc;
-  if ((rc = sf_buf_reserve(c, c->gf_planes, np * 4 * sizeof(float) * n_img)) != SF_OK) return rc;
-  const unsigned key_cap = (unsigned)np;
-  if ((rc = sf_buf_reserve(c, c->gf_keys, (size_t)key_cap * 2 * sizeof(unsigned long long) * n_img)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_scalar, 64 + (size_t)n_img * 16)) != SF_OK) return rc;
-  float* dxx = (float*)c->gf_planes.p;                    // image i: planes at + i * 4 np (dxx, dxy, dyy, eig)
-  float* dxy = dxx + np;
-  float* dyy = dxy + np;
-  float* eig = dyy + np;
-  const size_t plane_stride = 4 * np;
-  unsigned long long* keys = (unsigned long long*)c->gf_keys.p;
-  unsigned long long* keys_sorted = keys + (size_t)key_cap * n_img;
-  int* max_bits = (int*)((char*)c->gf_scalar.p + 64);
-  unsigned* count = (unsigned*)(max_bits + n_img);
-  unsigned* seg_begin = count + n_img;
-  unsigned* seg_end = seg_begin + n_img;
-  SF_HIP(c, hipMemsetAsync(max_bits, 0, (size_t)n_img * 8, c->stream));
-  const double scale = 1.0 / ((double)(1 << 2) * 3.0 * 255.0);
-  const dim3 grid((width + 63) / 64, (height + 3) / 4, n_img), block(256);
-  hipLaunchKernelGGL(k_gftt_products, grid, block, 0, c->stream, d_images, width, height, pitch, (float)(1.0 * scale),
-                     (float)(2.0 * scale), dxx, dxy, dyy, img_stride, plane_stride);
-  hipLaunchKernelGGL(k_gftt_eig, grid, block, 0, c->stream, (const float*)dxx, (const float*)dxy, (const float*)dyy, width,
-                     height, eig, max_bits, plane_stride);
-  const dim3 grid_c((width + 63) / 64, (height + 4 * GFTT_CAND_TILES - 1) / (4 * GFTT_CAND_TILES), n_img);
-  hipLaunchKernelGGL(k_gftt_candidates, grid_c, block, 0, c->stream, (const float*)eig, width, height, (const int*)max_bits,
-                     quality_level, keys, count, key_cap, plane_stride);
-  hipLaunchKernelGGL(k_gftt_segments, dim3((n_img + 63) / 64), dim3(64), 0, c->stream, (const unsigned*)count, key_cap, n_img,
-                     seg_begin, seg_end);
+  if ((rc = gftt_front(c, d_images, img_stride, n_img, width, height, pitch, quality_level, &F)) != SF_OK) return rc;
+  hipLaunchKernelGGL(k_gftt_segments, dim3((n_img + 63) / 64), dim3(64), 0, c->stream, (const unsigned*)F.count, F.key_cap,
+                     n_img, F.seg_begin, F.seg_end);
   SF_HIP(c, hipGetLastError());
-  size_t tmp_bytes = 0;
-  SF_HIP(c, rocprim::segmented_radix_sort_keys_desc(nullptr, tmp_bytes, keys, keys_sorted, (unsigned)((size_t)key_cap * n_img),
-                                                    (unsigned)n_img, seg_begin, seg_end, 0, 64, c->stream));
-  if ((rc = sf_buf_reserve(c, c->gf_tmp, std::max<size_t>(tmp_bytes, 16))) != SF_OK) return rc;
-  SF_HIP(c, rocprim::segmented_radix_sort_keys_desc(c->gf_tmp.p, tmp_bytes, keys, keys_sorted, (unsigned)((size_t)key_cap * n_img),
-                                                    (unsigned)n_img, seg_begin, seg_end, 0, 64, c->stream));
-  if (!c->gf_select_attr) {
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_gftt_select_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    c->gf_select_attr = true;
-  }
-  hipLaunchKernelGGL(k_gftt_select_lds, dim3(n_img), dim3(256), bm_bytes, c->stream, (const unsigned long long*)keys_sorted, 0,
+  if ((rc = sf_sort_keys_segmented_desc(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img,
+                                        F.seg_begin, F.seg_end, 0, 64)) != SF_OK)
+    return rc;
+  if ((rc = gftt_select_lds_attr(c)) != SF_OK) return rc;
+  hipLaunchKernelGGL(k_gftt_select_lds, dim3(n_img), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, 0,
                      width, height, wpr, (float)(min_distance * min_distance), radius, max_corners, d_kpts_out, cap, d_n_out,
-                     (const unsigned*)count, key_cap);
+                     (const unsigned*)F.count, F.key_cap);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }

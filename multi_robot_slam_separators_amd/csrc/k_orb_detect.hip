@@ -15,28 +15,24 @@
 //   k_orb_cut_a      per level: the score at rank 2 quota (Harris) or quota (FAST) from the histogram -- retainBest on
 //                    8-bit scores needs no sort -- and the level's segment in the sorted list
 //   k_orb_filter_a   drops the candidates below their level's cut
-//   rocprim radix sort ascending by (level, pixel): survivors first, raster order within a level
+//   sf_sort_keys (sf_sort.hip) ascending by (level, pixel): survivors first, raster order within a level
 //   k_orb_harris     (score type Harris) one candidate per wavefront: lanes 0 .. 48 own one pixel of the 7 x 7 block each,
 //                    three integer wave reductions, one float32 expression; key (level, inverted order-preserving bits)
-//   rocprim radix sort ascending -> per level descending response; k_orb_cut_b reads the response at rank quota - 1
+//   sort ascending -> per level descending response; k_orb_cut_b reads the response at rank quota - 1
 //   k_orb_compact    ONE workgroup: stable compaction of the survivors (response >= cut: ties stay) in (level, raster)
 //                    order, then the keys of limitKeypoints: the index when the survivors fit max_features, else
 //                    (|response|, index)
-//   rocprim radix sort descending -> the final order
+//   sort descending -> the final order
 //   k_orb_emit       keypoints in LEVEL coordinates; k_orb_angle (k_extract.hip) adds the centroid angle on the level;
 //   k_orb_finish     position * scale_l into the caller's array
 // About forty short launches for three levels: latency-bound like the rest of the front end, not tuned yet.
 #include <hip/hip_runtime.h>
 
-#include <cstring>   // (rocprim's texture_cache_iterator.hpp calls memset without declaring it)
-
-#include <rocprim/rocprim.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 
-#include "sf_internal.hpp"
+#include "sf_front_device.hpp"
 
 namespace {
 
@@ -236,7 +232,7 @@ k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const flo
               unsigned long long* __restrict__ fin_key, float* __restrict__ fin_resp, unsigned long long* __restrict__ key_c,
               int* __restrict__ sc) {
   __shared__ int wave_cnt[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int total = sc[S_TOTAL];
   int running = 0;
   for (int base = 0; base < total; base += 256) {
@@ -249,22 +245,13 @@ k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const flo
       r = S.score_type == 0 ? resp[i] : (float)(unsigned)(key & 255ull);
       f = r >= __int_as_float(sc[S_CUT_B + (int)(key >> 40)]);
     }
-    const unsigned long long bal = __ballot(f);
-    if (lane == 0) wave_cnt[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int n = wave_cnt[q];
-      if (q < wave) before += n;
-      all += n;
-    }
+    const SfRank rank = sf_block_rank(f, wave_cnt);
     if (f) {
-      const int o = running + before + __popcll(bal & ((1ull << lane) - 1ull));
+      const int o = running + rank.before;
       fin_key[o] = key;
       fin_resp[o] = r;
     }
-    running += all;
+    running += rank.total;
     __syncthreads();
   }
   const bool limited = S.max_features > 0 && running > S.max_features;
@@ -292,9 +279,7 @@ k_orb_emit(SfOrbPyr P, const unsigned long long* __restrict__ key_cs, const unsi
   const unsigned idx = (unsigned)(key >> 8);
   const SfOrbLevel L = sf_orb_level(P, l);
   const int y = (int)(idx / (unsigned)L.w), x = (int)(idx - (unsigned)y * (unsigned)L.w);
-  sf_keypoint k;
-  k.x = (float)x; k.y = (float)y; k.size = 31.f * L.scale; k.angle = -1.0f; k.response = fin_resp[o]; k.octave = l; k.class_id = -1;
-  kp[i] = k;
+  kp[i] = sf_make_keypoint((float)x, (float)y, 31.f * L.scale, fin_resp[o], l);
 }
 
 __global__ void __launch_bounds__(256)
@@ -343,6 +328,9 @@ void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota) 
 }
 
 int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P) {
+  for (int l = 0; l < P.n; ++l)
+    if (P.w[l] < 1 || P.h[l] < 1)
+      return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, P.w[0], P.h[0], (double)P.scale[l]);
   int rc;
   if ((rc = sf_buf_reserve(c, c->orb_pyr, std::max<size_t>(P.total, 16))) != SF_OK) return rc;
   uint8_t* pyr = (uint8_t*)c->orb_pyr.p;
@@ -361,9 +349,6 @@ int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int h
                          const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out, int cap,
                          int32_t* n_out) {
   const SfOrbPyr P = sf_orb_pyr_layout(width, height, det->scale_factor, det->n_levels);
-  for (int l = 0; l < P.n; ++l)
-    if (P.w[l] < 1 || P.h[l] < 1)
-      return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, width, height, (double)P.scale[l]);
   int rc;
   if ((rc = sf_launch_orb_pyramid(c, d_image, pitch, P)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->gf_planes, P.total)) != SF_OK) return rc;
@@ -376,8 +361,8 @@ int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int h
   SF_HIP(c, hipMemsetAsync(sc, 0, (size_t)S_WORDS * 4, c->stream));
   for (int l = 0; l < P.n; ++l) {
     if (P.w[l] < 7 || P.h[l] < 7) continue;            // (no FAST domain)
-    sf_launch_fast_level(c, l == 0 ? d_image : pyr + P.off[l], P.w[l], P.h[l], l == 0 ? pitch : P.w[l], det->fast_threshold, 1,
-                         score + P.off[l], keys_f + P.off[l], (unsigned*)sc + S_COUNT + l, (unsigned)(P.w[l] * P.h[l]));
+    sf_launch_fast_level(c, l == 0 ? d_image : pyr + P.off[l], 0, 1, P.w[l], P.h[l], l == 0 ? pitch : P.w[l], det->fast_threshold,
+                         1, score + P.off[l], keys_f + P.off[l], (unsigned*)sc + S_COUNT + l, (unsigned)(P.w[l] * P.h[l]));
   }
   SF_HIP(c, hipGetLastError());
   unsigned h_count[SF_ORB_MAX_LEVELS] = {};
@@ -405,33 +390,23 @@ int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int h
   float* fin_resp = resp + C;
   sf_keypoint* kp1 = (sf_keypoint*)(((uintptr_t)(fin_resp + C) + 15) & ~(uintptr_t)15);
   sf_keypoint* kp2 = (sf_keypoint*)((char*)kp1 + kp_bytes);
-  auto sort = [&](unsigned long long* in, unsigned long long* out, unsigned b0, unsigned b1, bool desc) -> int {
-    size_t tmp_bytes = 0;
-    if (desc) SF_HIP(c, rocprim::radix_sort_keys_desc(nullptr, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
-    else SF_HIP(c, rocprim::radix_sort_keys(nullptr, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
-    int r = sf_buf_reserve(c, c->gf_tmp, std::max<size_t>(tmp_bytes, 16));
-    if (r != SF_OK) return r;
-    if (desc) SF_HIP(c, rocprim::radix_sort_keys_desc(c->gf_tmp.p, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
-    else SF_HIP(c, rocprim::radix_sort_keys(c->gf_tmp.p, tmp_bytes, in, out, (size_t)C, b0, b1, c->stream));
-    return SF_OK;
-  };
   const dim3 block(256), grid((C + 255) / 256);
   hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, C, cand, sc);
   hipLaunchKernelGGL(k_orb_cut_a, dim3(1), dim3(64), 0, c->stream, S, sc);
   hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, cand, C, (const int*)sc);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sort(cand, cand_s, 8, 44, false)) != SF_OK) return rc;
+  if ((rc = sf_sort_keys(c, cand, cand_s, C, 8, 44, false)) != SF_OK) return rc;
   if (det->score_type == 0) {
     hipLaunchKernelGGL(k_orb_harris, dim3((C + 3) / 4), block, 0, c->stream, d_image, pitch, pyr, P,
                        (const unsigned long long*)cand_s, (const int*)sc, C, resp, key_b);
     SF_HIP(c, hipGetLastError());
-    if ((rc = sort(key_b, key_bs, 0, 36, false)) != SF_OK) return rc;
+    if ((rc = sf_sort_keys(c, key_b, key_bs, C, 0, 36, false)) != SF_OK) return rc;
   }
   hipLaunchKernelGGL(k_orb_cut_b, dim3(1), dim3(64), 0, c->stream, S, (const unsigned long long*)key_bs, sc);
   hipLaunchKernelGGL(k_orb_compact, dim3(1), block, 0, c->stream, S, (const unsigned long long*)cand_s, (const float*)resp, C,
                      fin_key, fin_resp, key_c, sc);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sort(key_c, key_cs, 0, 64, true)) != SF_OK) return rc;
+  if ((rc = sf_sort_keys(c, key_c, key_cs, C, 0, 64, true)) != SF_OK) return rc;
   const dim3 grid_kp((cap_tmp + 255) / 256);
   hipLaunchKernelGGL(k_orb_emit, grid_kp, block, 0, c->stream, P, (const unsigned long long*)key_cs,
                      (const unsigned long long*)fin_key, (const float*)fin_resp, (const int*)sc, cap_tmp, kp1);
@@ -444,9 +419,5 @@ int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int h
     hipLaunchKernelGGL(k_orb_finish, dim3((written + 255) / 256), block, 0, c->stream, P, (const sf_keypoint*)kp2,
                        (const int*)sc, written, d_kpts_out);
   SF_HIP(c, hipGetLastError());
-  if (n_out) {
-    SF_HIP(c, hipMemcpyAsync(n_out, sc + S_NFINAL, 4, hipMemcpyDeviceToHost, c->stream));
-    SF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return SF_OK;
+  return n_out ? sf_word_to_host(c, sc + S_NFINAL, n_out) : SF_OK;
 }

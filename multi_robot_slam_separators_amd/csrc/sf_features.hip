@@ -1,7 +1,43 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
 // detection (GFTT, FAST, ORB), stereo correspondence and keyframe extraction (kernels in k_extract.hip, k_gftt.hip,
-// k_fast.hip, k_orb_detect.hip, k_lk.hip, k_cnn.hip).
+// k_fast.hip, k_orb_detect.hip, k_lk.hip, k_cnn.hip; the detectors' sort in sf_sort.hip).
 #include "sf_host.hpp"
+
+// ---- the checks the entry points below share ---------------------------------------------------------------------
+// `present`: every image pointer of the call is there; min_side 3 where a detector runs (its 3 x 3 neighbourhoods)
+static int check_image(sf_context* c, bool present, int width, int height, int pitch, int min_side, const char* what) {
+  if (!present || width < min_side || height < min_side || pitch < width)
+    return sf_fail(c, SF_EINVAL, "%s missing or malformed (%d x %d, pitch %d)", what, width, height, pitch);
+  return SF_OK;
+}
+
+// the detectors' sort keys hold a pixel index beside a score
+static int check_pixels(sf_context* c, int width, int height) {
+  if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+  return SF_OK;
+}
+
+// every feature type here writes binary rows into the keyframe store
+static int check_binary_rows(sf_context* c, int feature_type) {
+  const char* name = feature_type == 2 ? "ORB" : feature_type == 4 ? "FAST/BRIEF" : feature_type == 8 ? "GFTT/ORB" : "GFTT/BRIEF";
+  if (c->params.desc_type != 0)
+    return sf_fail(c, SF_EINVAL, "%s writes binary descriptors: a handle with desc_type %d cannot store them", name, c->params.desc_type);
+  return SF_OK;
+}
+
+static int check_gftt(sf_context* c, double quality_level, double min_distance) {
+  if (!(quality_level > 0.0) || !(min_distance >= 0.0))
+    return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
+  return SF_OK;
+}
+
+// the caller's parameter block, or the defaults when it passed none
+template <class T>
+static T arg_or_defaults(const T* given, void (*defaults)(T*)) {
+  T v;
+  if (given) v = *given; else defaults(&v);
+  return v;
+}
 
 // ---- feature extraction (kernels in k_extract.hip) ----------------------------------
 static int brief_upload(sf_context* c) {
@@ -24,8 +60,8 @@ extern "C" int sf_brief_set_pattern(sf_handle c, const int8_t* tests, int32_t by
 }
 
 static int brief_ensure(sf_context* c) {
-  if (c->params.desc_type != 0)
-    return sf_fail(c, SF_EINVAL, "the feature extraction writes BRIEF (binary) descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+  int rc = check_binary_rows(c, c->feature_type);
+  if (rc != SF_OK) return rc;
   if (c->brief_bytes) return SF_OK;
   const int want = c->params.desc_bytes;
   c->brief_bytes = (want == 16 || want == 64) ? want : 32;
@@ -78,28 +114,27 @@ static int orb_upload(sf_context* c) {
 
 extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_orb_params* orb) {
   if (!c) return SF_EINVAL;
-  if (feature_type == 6) {
-    c->feature_type = 6;
-    return SF_OK;
+  int rc;
+  switch (feature_type) {
+    case 6:
+      break;
+    case 4:
+      if ((rc = check_binary_rows(c, 4)) != SF_OK) return rc;
+      break;
+    case 8: {
+      if ((rc = check_binary_rows(c, 8)) != SF_OK) return rc;
+      const sf_orb_params o = arg_or_defaults(orb, sf_orb_defaults);
+      if ((rc = orb_validate(c, o)) != SF_OK) return rc;
+      c->orb = o;
+      break;
+    }
+    case 2:
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB) takes detector parameters: select it with sf_set_feature_type_orb");
+    default:
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (2 = ORB by sf_set_feature_type_orb, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
+                     feature_type);
   }
-  if (feature_type == 4) {
-    if (c->params.desc_type != 0)
-      return sf_fail(c, SF_EINVAL, "FAST/BRIEF writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
-    c->feature_type = 4;
-    return SF_OK;
-  }
-  if (feature_type != 8)
-    return sf_fail(c, SF_EINVAL, feature_type == 2 ? "Vis/FeatureType %d (ORB) takes detector parameters: select it with sf_set_feature_type_orb"
-                                                   : "Vis/FeatureType %d is not built (2 = ORB by sf_set_feature_type_orb, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
-                   feature_type);
-  if (c->params.desc_type != 0)
-    return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
-  sf_orb_params o;
-  if (orb) o = *orb; else sf_orb_defaults(&o);
-  int rc = orb_validate(c, o);
-  if (rc != SF_OK) return rc;
-  c->orb = o;
-  c->feature_type = 8;
+  c->feature_type = feature_type;
   return SF_OK;
 }
 
@@ -123,23 +158,20 @@ static int orb_detector_validate(sf_context* c, const sf_orb_detector_params& d,
     return sf_fail(c, SF_EINVAL, "ORB score_type %d unknown (0 = Harris, 1 = FAST)", d.score_type);
   if (d.fast_threshold < 1 || d.fast_threshold > 254)
     return sf_fail(c, SF_EINVAL, "ORB fast_threshold %d outside 1 .. 254", d.fast_threshold);
-  if (o.edge_threshold < 16 || o.edge_threshold > 64)
-    return sf_fail(c, SF_EINVAL, "ORB edge_threshold %d outside 16 .. 64 (the radius-15 centroid patch must stay inside a level)", o.edge_threshold);
-  if (o.patch_size != 31) return sf_fail(c, SF_EINVAL, "ORB patch_size %d: only 31 is built", o.patch_size);
-  if (o.wta_k != 2) return sf_fail(c, SF_EINVAL, "ORB wta_k %d: only 2 (32-byte rows) is built", o.wta_k);
-  return SF_OK;
+  // the detector always computes the intensity-centroid angle: the descriptor's parameters as under orientation 1 (the
+  // radius-15 patch must stay inside a level, edge_threshold 16 .. 64), whatever the caller's orientation says
+  sf_orb_params as_centroid = o;
+  as_centroid.orientation = 1;
+  return orb_validate(c, as_centroid);
 }
 
 extern "C" int sf_set_feature_type_orb(sf_handle c, const sf_orb_detector_params* det, const sf_orb_params* orb) {
   if (!c) return SF_EINVAL;
-  if (c->params.desc_type != 0)
-    return sf_fail(c, SF_EINVAL, "ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
-  sf_orb_detector_params d;
-  sf_orb_params o;
-  if (det) d = *det; else sf_orb_detector_defaults(&d);
-  if (orb) o = *orb; else sf_orb_defaults(&o);
-  int rc = orb_detector_validate(c, d, o);
+  int rc = check_binary_rows(c, 2);
   if (rc != SF_OK) return rc;
+  const sf_orb_detector_params d = arg_or_defaults(det, sf_orb_detector_defaults);
+  sf_orb_params o = arg_or_defaults(orb, sf_orb_defaults);
+  if ((rc = orb_detector_validate(c, d, o)) != SF_OK) return rc;
   o.orientation = 1;           // always the intensity centroid, computed by the detector
   c->orb_det = d;
   c->orb = o;
@@ -158,14 +190,13 @@ extern "C" int sf_detect_orb_device(sf_handle c, const uint8_t* d_image, int32_t
                                     sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
   if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
   *n_out = 0;
-  if (!d_image || width < 3 || height < 3 || pitch < width)
-    return sf_fail(c, SF_EINVAL, "image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  int rc = check_image(c, d_image, width, height, pitch, 3, "image");
+  if (rc != SF_OK) return rc;
   if (max_features < 1) return sf_fail(c, SF_EINVAL, "ORB shares out max_features = %d keypoints over its levels: it must be >= 1", max_features);
   const sf_orb_detector_params d = det ? *det : c->orb_det;
   const sf_orb_params o = orb ? *orb : c->orb;
-  int rc = orb_detector_validate(c, d, o);
-  if (rc != SF_OK) return rc;
-  if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+  if ((rc = orb_detector_validate(c, d, o)) != SF_OK) return rc;
+  if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
   SF_HIP(c, hipSetDevice(c->device));
   return sf_launch_detect_orb(c, d_image, width, height, pitch, max_features, &d, &o, d_kpts_out, cap, n_out);
 }
@@ -206,20 +237,11 @@ extern "C" int sf_orb_get_pattern(sf_handle c, int8_t* tests, int32_t cap_bytes,
   return SF_OK;
 }
 
-// The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF), the pyramid
-// of ORB (NULL: one level)
-struct ExtractKind {
-  int bytes;
-  const int8_t* d_tests;
-  const sf_orb_params* orb;
-  const sf_orb_detector_params* pyr;
-};
-
+// The descriptor of the handle's feature type (ExtractKind: sf_internal.hpp)
 static int extract_kind(sf_context* c, ExtractKind* k) {
   int rc;
   if (c->feature_type == 8 || c->feature_type == 2) {
-    if (c->params.desc_type != 0)
-      return sf_fail(c, SF_EINVAL, "GFTT/ORB writes binary descriptors: a handle with desc_type %d cannot store them", c->params.desc_type);
+    if ((rc = check_binary_rows(c, c->feature_type)) != SF_OK) return rc;
     if ((rc = orb_ensure(c)) != SF_OK) return rc;
     *k = {32, (const int8_t*)c->orb_tests.p, &c->orb, c->feature_type == 2 ? &c->orb_det : nullptr};
     return SF_OK;
@@ -254,11 +276,10 @@ extern "C" int sf_detect_corners_device(sf_handle c, const uint8_t* d_image, int
                                         sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
   if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
   *n_out = 0;
-  if (!d_image || width < 3 || height < 3 || pitch < width)
-    return sf_fail(c, SF_EINVAL, "image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
-  if (!(quality_level > 0.0) || !(min_distance >= 0.0))
-    return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
-  if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+  int rc;
+  if ((rc = check_image(c, d_image, width, height, pitch, 3, "image")) != SF_OK) return rc;
+  if ((rc = check_gftt(c, quality_level, min_distance)) != SF_OK) return rc;
+  if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
   SF_HIP(c, hipSetDevice(c->device));
   return sf_launch_detect_corners(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out,
                                   cap, n_out);
@@ -297,12 +318,11 @@ extern "C" int sf_detect_fast_device(sf_handle c, const uint8_t* d_image, int32_
                                      int32_t cap, int32_t* n_out) {
   if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
   *n_out = 0;
-  if (!d_image || width < 3 || height < 3 || pitch < width)
-    return sf_fail(c, SF_EINVAL, "image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  int rc;
+  if ((rc = check_image(c, d_image, width, height, pitch, 3, "image")) != SF_OK) return rc;
   const sf_fast_params prm = params ? *params : c->fast;
-  int rc = fast_validate(c, prm);
-  if (rc != SF_OK) return rc;
-  if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+  if ((rc = fast_validate(c, prm)) != SF_OK) return rc;
+  if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
   SF_HIP(c, hipSetDevice(c->device));
   return sf_launch_detect_fast(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
 }
@@ -322,11 +342,10 @@ extern "C" int sf_stereo_correspondences_device(sf_handle c, const uint8_t* d_le
                                                 const sf_stereo_flow_params* params, float* d_right_xy,
                                                 uint8_t* d_status, float* d_right_x, float* d_err) {
   if (!c || n < 0) return SF_EINVAL;
-  if (!d_left || !d_right || width < 1 || height < 1 || pitch < width)
-    return sf_fail(c, SF_EINVAL, "stereo pair missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  int rc = check_image(c, d_left && d_right, width, height, pitch, 1, "stereo pair");
+  if (rc != SF_OK) return rc;
   if (n > 0 && (!d_kpts || !d_right_xy || !d_status)) return sf_fail(c, SF_EINVAL, "corners or output arrays missing");
-  sf_stereo_flow_params prm;
-  if (params) prm = *params; else sf_stereo_flow_defaults(&prm);
+  const sf_stereo_flow_params prm = arg_or_defaults(params, sf_stereo_flow_defaults);
   if (prm.win_width <= 2 || prm.win_height <= 2)
     return sf_fail(c, SF_EINVAL, "window of %d x %d: both sides must be > 2 (cv::calcOpticalFlowPyrLK asserts the same)", prm.win_width, prm.win_height);
   if ((long long)prm.win_width * prm.win_height > 1024) return sf_fail(c, SF_ERANGE, "window of %d x %d exceeds 1024 pixels", prm.win_width, prm.win_height);
@@ -343,30 +362,24 @@ extern "C" int sf_extract_keyframe_device(sf_handle c, const uint8_t* d_left, in
                                           int32_t* out_slot, int32_t* out_rows, uint8_t* d_desc_out,
                                           float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c || !cam || n < 0) return SF_EINVAL;
-  if (!d_left || width < 1 || height < 1 || pitch < width) return sf_fail(c, SF_EINVAL, "left image missing or malformed (%d x %d, pitch %d)", width, height, pitch);
+  int rc = check_image(c, d_left, width, height, pitch, 1, "left image");
+  if (rc != SF_OK) return rc;
   if (n > 0 && !d_kpts) return sf_fail(c, SF_EINVAL, "keypoints missing");
   if (n > SF_MAX_FEATURES) return sf_fail(c, SF_ERANGE, "%d corners > int16 limit of KeyPointVec.size", n);
   if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
   SF_HIP(c, hipSetDevice(c->device));
   ExtractKind kind;
-  int rc = extract_kind(c, &kind);
-  if (rc != SF_OK) return rc;
+  if ((rc = extract_kind(c, &kind)) != SF_OK) return rc;
   if ((rc = sf_store_reserve(c, c->store, c->store.slots + 1, n, kind.bytes)) != SF_OK) return rc;
   if (out_rows && (rc = sf_buf_reserve(c, c->ex_rows, 16)) != SF_OK) return rc;
-  Store& st = c->store;
-  const int slot = st.slots;
-  if ((rc = sf_launch_extract(c, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam, kind.bytes,
-                              kind.d_tests, (uint32_t*)st.desc.p, (float*)st.xyz.p, (float4*)st.kp.p,
-                              (int4*)st.meta.p, st.kcap, st.w, slot, d_desc_out, d_xyz_out, d_kpts_out,
-                              out_rows ? (int32_t*)c->ex_rows.p : nullptr, kind.orb, kind.pyr)) != SF_OK)
+  const int slot = c->store.slots;
+  if ((rc = sf_launch_extract_batch(c, d_left, 0, 1, width, height, pitch, d_kpts, d_right_x, d_status, n, nullptr, cam, kind,
+                                    slot, d_desc_out, d_xyz_out, d_kpts_out,
+                                    out_rows ? (int32_t*)c->ex_rows.p : nullptr)) != SF_OK)
     return rc;
-  st.slots += 1;
+  c->store.slots += 1;
   if (out_slot) *out_slot = slot;
-  if (out_rows) {
-    SF_HIP(c, hipMemcpyAsync(out_rows, c->ex_rows.p, 4, hipMemcpyDeviceToHost, c->stream));
-    SF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return SF_OK;
+  return out_rows ? sf_word_to_host(c, c->ex_rows.p, out_rows) : SF_OK;
 }
 
 extern "C" void sf_detector_defaults(sf_detector_params* p) {
@@ -385,16 +398,14 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
                                               int32_t* rows_out, int32_t* slot_out) {
   if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
   *rows_out = 0;
-  if (!left || !right || width < 3 || height < 3 || pitch < width)
-    return sf_fail(c, SF_EINVAL, "stereo pair missing or malformed (%d x %d, pitch %d)", width, height, pitch);
-  sf_detector_params dp;
-  if (det) dp = *det; else sf_detector_defaults(&dp);
+  int rc = check_image(c, left && right, width, height, pitch, 3, "stereo pair");
+  if (rc != SF_OK) return rc;
+  const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
   if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
     return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
   SF_HIP(c, hipSetDevice(c->device));
   ExtractKind kind;
-  int rc = extract_kind(c, &kind);
-  if (rc != SF_OK) return rc;
+  if ((rc = extract_kind(c, &kind)) != SF_OK) return rc;
   const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
   const int maxf = dp.max_features;
   if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
@@ -408,13 +419,13 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t n = 0;
-  if (c->feature_type == 4 || c->feature_type == 2) {
-    if (!(dp.quality_level > 0.0) || !(dp.min_distance >= 0.0))
-      return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
-    rc = c->feature_type == 4 ? sf_detect_fast_device(c, d_left, width, height, width, maxf, nullptr, d_kpts, maxf, &n)
-                              : sf_detect_orb_device(c, d_left, width, height, width, maxf, nullptr, nullptr, d_kpts, maxf, &n);
-  } else {
-    rc = sf_detect_corners_device(c, d_left, width, height, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
+  // (the GFTT parameters are checked under every feature type, FAST and ORB included, which do not use them)
+  if ((rc = check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
+  switch (c->feature_type) {
+    case 4: rc = sf_detect_fast_device(c, d_left, width, height, width, maxf, nullptr, d_kpts, maxf, &n); break;
+    case 2: rc = sf_detect_orb_device(c, d_left, width, height, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
+    default:
+      rc = sf_detect_corners_device(c, d_left, width, height, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
   }
   if (rc != SF_OK) return rc;
   n = std::min(n, maxf);
@@ -455,24 +466,22 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
   if (c->feature_type == 2)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has no batch form yet: use sf_get_features_and_descriptor per keyframe");
   if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
-  if (!d_left || !d_right || width < 3 || height < 3 || pitch < width || image_stride < (size_t)pitch * height)
-    return sf_fail(c, SF_EINVAL, "stereo pairs missing or malformed (%d x %d, pitch %d, stride %zu)", width, height, pitch, image_stride);
-  sf_detector_params dp;
-  if (det) dp = *det; else sf_detector_defaults(&dp);
+  int rc = check_image(c, d_left && d_right, width, height, pitch, 3, "stereo pairs");
+  if (rc != SF_OK) return rc;
+  if (image_stride < (size_t)pitch * height)
+    return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
+  const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
   if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
     return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
-  if (!(dp.quality_level > 0.0) || !(dp.min_distance >= 0.0))
-    return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
-  sf_stereo_flow_params prm;
-  if (flow) prm = *flow; else sf_stereo_flow_defaults(&prm);
+  if ((rc = check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
+  const sf_stereo_flow_params prm = arg_or_defaults(flow, sf_stereo_flow_defaults);
   if (prm.win_width <= 2 || prm.win_height <= 2 || (long long)prm.win_width * prm.win_height > 1024 || prm.max_level < 0 ||
       prm.max_level > 15 || !(prm.epsilon == prm.epsilon))
     return sf_fail(c, SF_EINVAL, "stereo flow parameters out of range (see sf_stereo_correspondences_device)");
   if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
   SF_HIP(c, hipSetDevice(c->device));
   ExtractKind kind;
-  int rc = extract_kind(c, &kind);
-  if (rc != SF_OK) return rc;
+  if ((rc = extract_kind(c, &kind)) != SF_OK) return rc;
   const int maxf = dp.max_features, n = n_keyframes;
   const size_t rows_all = (size_t)maxf * n;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
@@ -482,7 +491,7 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t* d_n = (int32_t*)c->ft_counts.p;
   if (c->feature_type == 4) {
-    if ((long long)width * height > (1ll << 26)) return sf_fail(c, SF_ERANGE, "image of %d x %d pixels is too large", width, height);
+    if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
     rc = sf_launch_detect_fast_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
   } else {
     rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
@@ -495,14 +504,11 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
   if ((rc = sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &prm,
                                         d_xy, d_status, d_rx, nullptr)) != SF_OK)
     return rc;
-  Store& st = c->store;
-  const int slot = st.slots;
-  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam,
-                                    kind.bytes, kind.d_tests, (uint32_t*)st.desc.p, (float*)st.xyz.p,
-                                    (float4*)st.kp.p, (int4*)st.meta.p, st.kcap, st.w, slot, d_desc_out, d_xyz_out,
-                                    d_kpts_out, d_rows_out, kind.orb)) != SF_OK)
+  const int slot = c->store.slots;
+  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, kind,
+                                    slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out)) != SF_OK)
     return rc;
-  st.slots += n;
+  c->store.slots += n;
   if (first_slot_out) *first_slot_out = slot;
   return SF_OK;
 }

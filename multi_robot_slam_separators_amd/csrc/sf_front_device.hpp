@@ -1,0 +1,52 @@
+// sf_front_device.hpp -- device helpers that two or more kernel files of the feature front end (k_gftt.hip, k_fast.hip,
+// k_orb_detect.hip, k_extract.hip) share.  Everything here is forced inline: no kernel changes by calling it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "sf_internal.hpp"
+
+// cv::borderInterpolate(p, len, BORDER_REFLECT_101)
+// (k_gftt.hip asks only for offsets of +-1 on sides >= 3, where one reflection is all the loop does)
+__device__ __forceinline__ int reflect101(int p, int len) {
+  if (len == 1) return 0;
+  while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
+  return p;
+}
+
+__device__ __forceinline__ sf_keypoint sf_make_keypoint(float x, float y, float size, float response, int octave) {
+  sf_keypoint k;
+  k.x = x; k.y = y; k.size = size; k.angle = -1.0f; k.response = response; k.octave = octave; k.class_id = -1;
+  return k;
+}
+
+// The tail of a candidate kernel (256 threads): the *s_n keys its workgroup staged in LDS go to the image's list with ONE
+// global atomic on the image's counter; keys past `cap` are dropped (the counter still counts them).
+__device__ __forceinline__ void sf_flush_staged_keys(const unsigned long long* s_keys, const unsigned* s_n, unsigned* s_base,
+                                                     unsigned long long* __restrict__ keys, unsigned* __restrict__ count,
+                                                     unsigned cap) {
+  __syncthreads();
+  if (threadIdx.x == 0 && *s_n) *s_base = atomicAdd(count, *s_n);
+  __syncthreads();
+  for (unsigned i = threadIdx.x; i < *s_n; i += 256)
+    if (*s_base + i < cap) keys[*s_base + i] = s_keys[i];
+}
+
+// Stable compaction rank in a workgroup of 256 threads: the number of threads before this one whose flag is set, and the
+// workgroup's total.  wave_cnt is a __shared__ int[4]; the caller ends its loop body with a __syncthreads() before the
+// next call overwrites it.
+struct SfRank { int before, total; };
+__device__ __forceinline__ SfRank sf_block_rank(bool flag, int* wave_cnt) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(flag);
+  if (lane == 0) wave_cnt[wave] = __popcll(bal);
+  __syncthreads();
+  SfRank r = {0, 0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int n = wave_cnt[q];
+    if (q < wave) r.before += n;
+    r.total += n;
+  }
+  r.before += __popcll(bal & ((1ull << lane) - 1ull));
+  return r;
+}

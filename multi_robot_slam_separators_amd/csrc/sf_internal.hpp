@@ -509,6 +509,43 @@ inline SfOrbPyr sf_orb_single_level(int w, int h) {
     if (_e != hipSuccess) return sf_fail((c), SF_EHIP, "%s -> %s", #expr, hipGetErrorString(_e)); \
   } while (0)
 
+// one 32-bit word from the device, waited for: the counts that size a launch and the counts a caller asked for
+inline int sf_word_to_host(sf_context* c, const void* d_word, void* h_word) {
+  SF_HIP(c, hipMemcpyAsync(h_word, d_word, 4, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  return SF_OK;
+}
+
+// ---- workspace of the corner detectors (k_gftt.hip, k_fast.hip), one image and a batch alike --------------------------
+// c->gf_planes: plane_bytes per image for the detector's own planes.  c->gf_keys: the candidate keys of image i at keys +
+// i * key_cap, and as much again for their sorted copy.  c->gf_scalar: the single call's corner count at byte 0, from byte
+// 64 the per-image arrays max_bits, count, seg_begin, seg_end; the first two are zeroed on the stream.
+struct SfDetectorWork {
+  unsigned key_cap;                            // = pixels of one image
+  unsigned long long *keys, *keys_sorted;      // [n_img][key_cap] each
+  int* max_bits;                               // [n_img] GFTT: float bits of max(eig)
+  unsigned *count, *seg_begin, *seg_end;       // [n_img] candidates found; the bounds of a batch's segmented sort
+  int32_t* n_single;
+};
+inline int sf_detector_work(sf_context* c, int width, int height, int n_img, size_t plane_bytes, SfDetectorWork* W) {
+  const size_t np = (size_t)width * height;
+  if (np * (size_t)n_img > 0xFFFFFFFFull) return sf_fail(c, SF_ERANGE, "corner detection: %d images of %zu pixels", n_img, np);
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->gf_planes, plane_bytes * n_img)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_keys, np * 2 * sizeof(unsigned long long) * n_img)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_scalar, 64 + (size_t)n_img * 16)) != SF_OK) return rc;
+  W->key_cap = (unsigned)np;
+  W->keys = (unsigned long long*)c->gf_keys.p;
+  W->keys_sorted = W->keys + np * n_img;
+  W->n_single = (int32_t*)c->gf_scalar.p;
+  W->max_bits = (int*)((char*)c->gf_scalar.p + 64);
+  W->count = (unsigned*)(W->max_bits + n_img);
+  W->seg_begin = W->count + n_img;
+  W->seg_end = W->seg_begin + n_img;
+  SF_HIP(c, hipMemsetAsync(W->max_bits, 0, (size_t)n_img * 8, c->stream));
+  return SF_OK;
+}
+
 // ---- kernel launchers (one per translation unit) -----------------------------------------------
 // Pass-1 global matching for n pairs; also writes PassState defaults and the RANSAC work list.
 int sf_launch_match_global(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n);
@@ -537,6 +574,13 @@ size_t sf_pnp_lds_bytes(int kcap, int iterations);
 size_t sf_guided_lds_bytes(int kcap, int n_cells, bool narrow = false);   // narrow: the one- / two-wavefront chains' shorter candidate list
 void sf_brief_default_pattern(int8_t* tests, int bytes);
 void sf_orb_default_pattern(int8_t* tests);     // [256][4]: 32-byte ORB rows
+// The detectors' one library call (sf_sort.hip): radix sort of 64-bit keys by bits [bit0, bit1) on the handle's stream,
+// temporary storage in c->gf_tmp.  The segmented form sorts every [d_begin[s], d_end[s]) on its own, descending.
+int sf_sort_keys(sf_context* c, const unsigned long long* in, unsigned long long* out, size_t n, unsigned bit0, unsigned bit1,
+                 bool descending);
+int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
+                                unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0,
+                                unsigned bit1);
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
                                    sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out);
@@ -544,13 +588,19 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
                                 int width, int height, int pitch, const sf_keypoint* d_kpts, int n, const int32_t* d_n,
                                 const sf_stereo_flow_params* prm, float* d_right_xy, uint8_t* d_status, float* d_right_x,
                                 float* d_err);
+// The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF rows, else ORB
+// rows), the pyramid of ORB (NULL: one level; else ORB rows on the keypoint's own level, type 2)
+struct ExtractKind {
+  int bytes;
+  const int8_t* d_tests;
+  const sf_orb_params* orb;
+  const sf_orb_detector_params* pyr;
+};
+// keyframes into the slots of c->store from `slot` on (k_extract.hip); one keyframe: img_stride 0, n_img 1, d_n null
 int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_stride, int n_img, int width, int height,
                             int pitch, const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n,
-                            const int32_t* d_n, const sf_stereo_camera* cam, int bytes, const int8_t* d_tests,
-                            uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap, int w_dwords,
-                            int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                            int32_t* d_rows_out, const sf_orb_params* orb = nullptr,    // orb: GFTT/ORB rows, else BRIEF
-                            const sf_orb_detector_params* pyr = nullptr);   // pyr: ORB rows on the keypoint's own level (type 2)
+                            const int32_t* d_n, const sf_stereo_camera* cam, const ExtractKind& kind, int slot,
+                            uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out, int32_t* d_rows_out);
 int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
                              int32_t* n_out);
@@ -560,10 +610,10 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
                                 int32_t* d_n_out);
-// one level of FAST: k_fast_score + k_fast_candidates as sf_launch_detect_fast queues them (keys = score << 32 | pixel
-// index in arrival order, *count the corners found; count zeroed by the caller)
-void sf_launch_fast_level(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int threshold, int nonmax,
-                          uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap);
+// one level of FAST on n_img images img_stride bytes apart: k_fast_score + k_fast_candidates (image i: score plane and keys
+// at + i * key_cap, keys = score << 32 | pixel index in arrival order, count[i] the corners found; zeroed by the caller)
+void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int threshold, int nonmax, uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap);
 // ORB detector (k_orb_detect.hip); det / orb validated by the caller
 SfOrbPyr sf_orb_pyr_layout(int width, int height, float scale_factor, int n_levels);
 void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota);
@@ -577,11 +627,6 @@ int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_image, int pitch,
 int sf_launch_stereo_flow(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, int width, int height, int pitch,
                           const sf_keypoint* d_kpts, int n, const sf_stereo_flow_params* prm, float* d_right_xy,
                           uint8_t* d_status, float* d_right_x, float* d_err);
-int sf_launch_extract(sf_context* c, const uint8_t* d_left, int width, int height, int pitch, const sf_keypoint* d_kpts,
-                      const float* d_right_x, const uint8_t* d_status, int n, const sf_stereo_camera* cam, int bytes,
-                      const int8_t* d_tests, uint32_t* st_desc, float* st_xyz, float4* st_kp, int4* st_meta, int kcap,
-                      int w_dwords, int slot, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
-                      int32_t* d_rows_out, const sf_orb_params* orb = nullptr, const sf_orb_detector_params* pyr = nullptr);
 // Assemble sf_result records.
 int sf_launch_finalize(sf_context* c, int n, sf_result* d_out);
 // Ingest kernels

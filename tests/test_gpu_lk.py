@@ -217,11 +217,14 @@ def test_keyframes_from_pixels_verify_like_wire_features(finder):
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("shape,n_kf,det", [((480, 752), 5, None), ((240, 320), 9, (300, 0.01, 5.0)), ((100, 140), 3, (2000, 0.001, 1.0))])
+@pytest.mark.parametrize("shape,n_kf,det", [((480, 752), 5, None), ((240, 320), 9, (300, 0.01, 5.0)), ((100, 140), 3, (2000, 0.001, 1.0)),
+                                            ((100, 140), 1, (2000, 0.001, 1.0))])
 def test_batched_keyframes_equal_the_single_calls(finder, shape, n_kf, det):
     """sf_get_features_and_descriptor_batch_device: n stereo pairs in device memory -> n store slots in one launch
     sequence with the corner counts left on the device; per keyframe the rows kept, descriptors, 3D points and
-    keypoints are the single call's byte for byte, and the store slots verify like the single call's."""
+    keypoints are the single call's byte for byte, and the store slots verify like the single call's.  The batch of ONE
+    keyframe shares the detectors' front half with the single call and differs from it only in the tail (segmented sort,
+    counts left on the device)."""
     import torch
     dev = torch.device("cuda:0")
     tests = ec.brief_tests(6, 32)
@@ -231,7 +234,8 @@ def test_batched_keyframes_equal_the_single_calls(finder, shape, n_kf, det):
     h, w = shape
     cam = _abi.stereo_camera(460.0, 458.0, w / 2.0, h / 2.0, 0.11)
     pairs = [ec.make_stereo_pair(600 + i, width=w, height=h, max_disp=min(40.0, w / 6))[:2] for i in range(n_kf)]
-    pairs[1] = (np.full((h, w), 90, np.uint8), np.full((h, w), 90, np.uint8))       # a keyframe without a single corner
+    if n_kf > 1:
+        pairs[1] = (np.full((h, w), 90, np.uint8), np.full((h, w), 90, np.uint8))   # a keyframe without a single corner
     singles = [finder.get_features_and_descriptor(l, r, cam, det) for l, r in pairs]
     stride = ((h * w + 255) // 256) * 256 + 512                                      # images need not be back to back
     L = torch.zeros((n_kf, stride), dtype=torch.uint8, device=dev)
@@ -251,7 +255,7 @@ def test_batched_keyframes_equal_the_single_calls(finder, shape, n_kf, det):
     torch.cuda.synchronize()
     assert first == before and finder.store_size() == before + n_kf
     rows = rows.cpu().numpy()
-    assert rows[1] == 0 and len(singles[1][0]) == 0
+    assert n_kf == 1 or (rows[1] == 0 and len(singles[1][0]) == 0)
     for i, (d0, p0, k0, s0) in enumerate(singles):
         n = len(d0)
         assert rows[i] == n, "keyframe %d: %d rows, the single call kept %d" % (i, rows[i], n)
