@@ -66,6 +66,10 @@ extern "C" {
 /* 8, additions: sf_orb_detector_params, sf_orb_detector_defaults, sf_set_feature_type_orb, sf_get_orb_detector,
       sf_detect_orb_device (ORB on a pyramid, Vis/FeatureType 2).  sf_set_feature_type still refuses 2; nothing existing
       changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.                                            */
+/* 8, additions: sf_image_format, sf_image_set_gray_rule, sf_image_get_gray_rule, sf_image_to_gray_device,
+      sf_netvlad_infer_u8_batch_device, sf_get_features_and_descriptor_u8, sf_add_keyframes_u8_batch_device (keyframes from
+      the camera's rgb8 / bgr8 / mono8 images).  Nothing existing changed, the version number, sizeof(sf_params) and
+      SF_K_COUNT stay.                                                                                                */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -527,6 +531,75 @@ int  sf_get_features_and_descriptor_batch_device(sf_handle h, const uint8_t* d_l
                                                  const sf_detector_params* det, const sf_stereo_flow_params* flow,
                                                  int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                  float* d_xyz_out, sf_keypoint* d_kpts_out);
+
+/* ---- keyframes from the camera's own images (first step) ------------------------- */
+/* The reference keeps every image as cv_bridge's "rgb8" (data_handler.py:114-141).  For a keyframe it converts both stereo
+   images with cv2.cvtColor(image, cv2.COLOR_RGB2GRAY) before GetFeatsAndDesc (data_handler.py:424-428) and feeds the uint8
+   RGB image, unscaled, to the network's float placeholder (data_handler.py:60-61, 149-154).  The calls below take such
+   images -- 8-bit, interleaved, `pitch` bytes per row -- and do both conversions on the device; no float image and, in the
+   batch form, no host step lies between the camera's bytes and the keyframe.                                       */
+enum sf_image_format {
+  SF_IMAGE_RGB8 = 0,   /* 3 bytes per pixel: R, G, B (what the reference's queues hold); pitch >= 3 * width          */
+  SF_IMAGE_BGR8 = 1,   /* 3 bytes per pixel: B, G, R; pitch >= 3 * width                                            */
+  SF_IMAGE_MONO8 = 2   /* 1 byte per pixel; pitch >= width.  Gray = the byte; the network sees it in all 3 channels   */
+};
+/* The coefficients of the colour-to-gray conversion, gray = (R kr + G kg + B kb + (1 << (shift - 1))) >> shift in int32
+   [upstream OpenCV, restated in tests/image_ref.py; as remembered, not from the reference tree: DESIGN.md section 3]:
+     rule 0 (a fresh handle)  OpenCV 3.x: kr 4899, kg 9617, kb 1868, shift 14 -- the reference's python2 / ROS1 era and
+                              the OpenCV 3.2 the rest of the front end restates
+     rule 1                   OpenCV 4.x: kr 9798, kg 19235, kb 3735, shift 15
+   Both sets sum to 1 << shift: (v, v, v) gives v, which is why mono8 is a copy.  Any other rule: SF_EINVAL, nothing
+   changes.                                                                                                         */
+int  sf_image_set_gray_rule(sf_handle h, int32_t rule);
+int  sf_image_get_gray_rule(sf_handle h, int32_t* rule);
+/* cv2.cvtColor(..., COLOR_RGB2GRAY / COLOR_BGR2GRAY) of n_images device images of one size under the handle's rule, one
+   launch, asynchronous on the handle's stream: image i at d_src + i * src_stride (rows of src_pitch bytes) to the plane at
+   d_dst + i * dst_stride (rows of dst_pitch >= width bytes).  Any pitches, strides (>= the rows they hold; ignored when
+   n_images = 1) and base alignments; bytes outside the width x height planes are not written.  SF_IMAGE_MONO8: a pitched
+   copy.  The planes are what sf_detect_*_device, sf_stereo_correspondences_device, sf_extract_keyframe_device and
+   sf_get_features_and_descriptor_batch_device take.  Unknown format, pitch below a row: SF_EINVAL.                  */
+int  sf_image_to_gray_device(sf_handle h, const uint8_t* d_src, int32_t format, int32_t width, int32_t height,
+                             int32_t src_pitch, size_t src_stride, int32_t n_images, uint8_t* d_dst, int32_t dst_pitch,
+                             size_t dst_stride);
+/* sf_netvlad_infer_batch_device on 8-bit images: image i at d_images + i * image_stride, rows of `pitch` bytes.  The
+   first convolution reads the bytes itself ((float)byte - average_rgb[c]; channels exchanged for bgr8, the one channel
+   three times for mono8): the descriptors carry the bits of sf_netvlad_infer_batch_device on a float32 copy of the same
+   values, at a quarter of the image bytes.  Same limits, same first-call measurement per image size.                */
+int  sf_netvlad_infer_u8_batch_device(sf_handle h, const uint8_t* d_images, int32_t format, int32_t n_images,
+                                      int32_t width, int32_t height, int32_t pitch, size_t image_stride, float* d_out,
+                                      int32_t n_out);
+/* sf_get_features_and_descriptor on the images DataHandler.compute_geom_features receives (data_handler.py:424-435):
+   left / right in HOST memory in `format`, `pitch` bytes per row.  The pair is uploaded as it is and converted on the
+   device under the handle's rule; from there on it is sf_get_features_and_descriptor's own code, under every feature type
+   that call serves (6, 8, 4, 2): outputs, store slot and limits are the same, byte for byte what the gray call returns
+   for the converted pair.  Synchronous.                                                                            */
+int  sf_get_features_and_descriptor_u8(sf_handle h, const uint8_t* left, const uint8_t* right, int32_t format,
+                                       int32_t width, int32_t height, int32_t pitch, const sf_stereo_camera* cam,
+                                       const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                       uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
+                                       int32_t* rows_out, int32_t* slot_out);
+/* What get_keyframes + compute_descriptors leave behind for n_keyframes keyframes (data_handler.py:143-164, 268) in ONE
+   launch sequence with no host wait, asynchronous on the handle's stream: device images in `format` of one size, keyframe
+   i's left / right / rgb image at d_left / d_right / d_rgb + i * image_stride (rows of `pitch` bytes; d_rgb NULL = the
+   left images, as on a robot without a separate colour camera).
+     geometric_feats   all 2 n stereo images become gray planes in one launch, then the stages of
+                       sf_get_features_and_descriptor_batch_device write n store slots from *first_slot_out on
+     local_descriptors the network runs on d_rgb; the first params.netvlad_dimensions values of every descriptor are
+                       appended as n local NN rows from *first_nn_row_out on
+   Slot first_slot + i and local row first_nn_row + i are the same keyframe: the reference's one index
+   geometric_feats[i] <-> local_descriptors[i].  d_rows_out, d_desc_out, d_xyz_out, d_kpts_out: the optional device
+   outputs of sf_get_features_and_descriptor_batch_device.
+   All or nothing: arguments, the loaded model against netvlad_dimensions and the NN database's dimension are checked, and
+   the store slots, the NN rows and the call's own buffers reserved, before the first launch; the store and the NN
+   database grow last, together.  A refused call leaves sf_store_size and sf_nn_sizes as they were.  It refuses what sf_get_features_and_descriptor_batch_device
+   refuses, with the same code and message (feature type 2 among them), and what sf_netvlad_infer_u8_batch_device refuses;
+   no model, or netvlad_dimensions beyond the model's WPCA width: SF_EINVAL.                                          */
+int  sf_add_keyframes_u8_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+                                      int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                      size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
+                                      const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                      int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
+                                      sf_keypoint* d_kpts_out);
 
 /* ---- geometric verification (stereoCamGeometricTools.cpp:122-178) ---------------------------- */
 /* One estimate_transformation service call on host buffers.                                  */

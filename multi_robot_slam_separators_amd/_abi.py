@@ -179,6 +179,12 @@ FEATURE_FAST_BRIEF = 4
 FEATURE_ORB = 2          # ... and of sf_set_feature_type_orb
 
 
+SF_IMAGE_RGB8, SF_IMAGE_BGR8, SF_IMAGE_MONO8 = range(3)   # sf_image_format: the camera's images (cv_bridge encodings)
+GRAY_RULE_OPENCV3, GRAY_RULE_OPENCV4 = 0, 1               # sf_image_set_gray_rule
+# (kr, kg, kb, shift) of gray = (R kr + G kg + B kb + (1 << (shift - 1))) >> shift
+GRAY_RULES = {GRAY_RULE_OPENCV3: (4899, 9617, 1868, 14), GRAY_RULE_OPENCV4: (9798, 19235, 3735, 15)}
+
+
 class NetvladWeights(C.Structure):
     """sf_netvlad_weights (include/sepfinder.h): host pointers to the NetVLAD network's weights, TensorFlow layouts."""
     _fields_ = [

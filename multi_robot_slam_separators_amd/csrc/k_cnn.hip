@@ -102,9 +102,15 @@ __device__ __forceinline__ float4 hl4_values(const float4 p) {           // pack
 }
 
 // in: [H][W][3] float, wgt: [64][27] (tap-major, channel-minor), out: [H][W][64] (fp32, or packed split halves when `packed`); mean subtraction fused
+// U8: `in` holds 8-bit camera images instead (data_handler.py:60-61 feeds the uint8 rgb8 image to the float placeholder:
+// the values 0 .. 255, unscaled) -- image j of the stack at in + j * stride, rows of `pitch` bytes, format rgb8 (0),
+// bgr8 (1: channels exchanged) or mono8 (2: the one channel three times).  A pixel's 27 inputs are (float)u8 - mean[c],
+// the bits the float form reads from a float copy of the image; everything after them is the same code.
+template <bool U8>
 __global__ void __launch_bounds__(256)
-k_conv3x3_first(const float* __restrict__ in, int H, int W, const float* __restrict__ wgt, const float* __restrict__ bias,
-                const float* __restrict__ mean, float* __restrict__ out, int relu, int packed, int Himg) {
+k_conv3x3_first(const void* __restrict__ in_, int H, int W, const float* __restrict__ wgt, const float* __restrict__ bias,
+                const float* __restrict__ mean, float* __restrict__ out, int relu, int packed, int Himg, int format, int pitch,
+                size_t stride) {
   // (H = rows of the whole input, Himg = rows of ONE image: a batch is a stack of images, a tap never crosses into the next)
   __shared__ __attribute__((aligned(16))) float sw[64 * 27];
   __shared__ __attribute__((aligned(16))) float sb[64];
@@ -121,8 +127,20 @@ k_conv3x3_first(const float* __restrict__ in, int H, int W, const float* __restr
   for (int t = 0; t < 9; ++t) {
     const int yy = y + t / 3 - 1, xx = x + t % 3 - 1, yyi = yi + t / 3 - 1;
     const bool ok = yyi >= 0 && yyi < Himg && xx >= 0 && xx < W;
+    if constexpr (U8) {
+      // (bounds: yyi < Himg rows of image y / Himg, 3 xx + 2 < 3 W <= pitch, or xx < W <= pitch for mono8)
+      const uint8_t* px = static_cast<const uint8_t*>(in_) + (size_t)(y / Himg) * stride + (size_t)(ok ? yyi : 0) * pitch +
+                          (size_t)(ok ? xx : 0) * (format == 2 ? 1 : 3);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[3 * t + c] = ok ? in[((size_t)yy * W + xx) * 3 + c] - mean[c] : 0.f;
+      for (int c = 0; c < 3; ++c) {
+        const int cs = format == 2 ? 0 : format == 1 ? 2 - c : c;
+        v[3 * t + c] = ok ? (float)px[cs] - mean[c] : 0.f;
+      }
+    } else {
+      const float* in = static_cast<const float*>(in_);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[3 * t + c] = ok ? in[((size_t)yy * W + xx) * 3 + c] - mean[c] : 0.f;
+    }
   }
   // (four threads per pixel: the 27 inputs are fetched 4 times instead of 16, and the four write one 256-byte row)
 #pragma unroll
@@ -834,13 +852,28 @@ static int conv_autotune(sf_context* c, sf_netvlad_model* m, int H, int W, int n
 // data_handler.py:60-61, netvlad_batch_size at a time: :149-156); d_out: n x n_out floats (the first n_out of each
 // pca_dim-D unit vector).  Asynchronous on the handle's stream.  The trunk and the VLAD layer run image by image (every
 // layer already fills the chip at camera resolution); the WPCA reads its weights ONCE per group of up to four images.
-int sf_netvlad_infer_batch_impl(sf_context* c, const float* d_images, int n_img, int H, int W, float* d_out, int n_out) {
+int sf_netvlad_pca_dim(const sf_context* c) { return c->netvlad ? c->netvlad->pca_dim : 0; }
+
+// the limits of an inference call (both input forms), checked without a launch
+int sf_netvlad_check(sf_context* c, int n_img, int H, int W, int n_out) {
   sf_netvlad_model* m = c->netvlad;
   if (!m) return sf_fail(c, SF_EINVAL, "no NetVLAD model loaded (sf_netvlad_load)");
   if (n_img < 1 || n_img > 1024) return sf_fail(c, SF_ERANGE, "a batch of %d images", n_img);
   if (H < 16 || W < 16) return sf_fail(c, SF_ERANGE, "image of %d x %d is smaller than the four poolings need", W, H);
   if (n_out < 1 || n_out > m->pca_dim) return sf_fail(c, SF_ERANGE, "%d output dimensions of %d", n_out, m->pca_dim);
-  int rc;
+  if (m->split_f16 && (size_t)H * W * 64 * sizeof(float) > ((size_t)1 << 32) - 2 * CONV_ZERO_PAGE * sizeof(float))
+    return sf_fail(c, SF_ERANGE, "image of %d x %d is beyond the 32-bit activation offsets of the split-fp16 trunk", W, H);
+  return SF_OK;
+}
+
+// The input of an inference call: float32 [H][W][3] images back to back (format < 0), or 8-bit camera images (format =
+// sf_image_format, rows of `pitch` bytes, images `stride` bytes apart) that the first convolution reads as they are
+struct NetvladInput { const void* p; int format, pitch; size_t stride; };
+
+static int netvlad_infer(sf_context* c, const NetvladInput in, int n_img, int H, int W, float* d_out, int n_out) {
+  int rc = sf_netvlad_check(c, n_img, H, W, n_out);
+  if (rc != SF_OK) return rc;
+  sf_netvlad_model* m = c->netvlad;
   const int K = m->clusters, D = 512;
   const int group = std::min(n_img, 4);
   // The trunk of a group runs as ONE vertical stack of its images (split-fp16 kernels; heights that survive the four
@@ -852,8 +885,6 @@ int sf_netvlad_infer_batch_impl(sf_context* c, const float* d_images, int n_img,
   //  full resolution, has to stay under 4 GB -- 16 Mpixel for a single image; a stack is cut down to what fits)
   const size_t img_bytes = (size_t)H * W * 64 * sizeof(float);
   const size_t off_limit = ((size_t)1 << 32) - 2 * CONV_ZERO_PAGE * sizeof(float);
-  if (m->split_f16 && img_bytes > off_limit)
-    return sf_fail(c, SF_ERANGE, "image of %d x %d is beyond the 32-bit activation offsets of the split-fp16 trunk", W, H);
   const bool stackable = m->split_f16 && (H % 16) == 0;
   const int ns_max = stackable ? (int)std::max<size_t>(1, std::min<size_t>((size_t)group, off_limit / img_bytes)) : 1;
   const size_t act_max = (size_t)ns_max * H * W * 64;
@@ -878,16 +909,23 @@ int sf_netvlad_infer_batch_impl(sf_context* c, const float* d_images, int n_img,
       if ((rc = conv_autotune(c, m, H, W, ns, T)) != SF_OK) return rc;
     }
     for (int b0 = 0; b0 < gb; b0 += ns) {
-      const float* d_image = d_images + (size_t)(g0 + b0) * H * W * 3;
       int h = H * ns, himg = H, w = W, cur = 0;
-      const float* src = d_image;
+      const float* src = nullptr;
       for (int i = 0; i < 13; ++i) {
         float* dst = (float*)m->act[cur].p + CONV_ZERO_PAGE;
         const int P = h * w;
         if (i == 0) {
-          hipLaunchKernelGGL(k_conv3x3_first, dim3((unsigned)(((size_t)P * 4 + 255) / 256)), dim3(256), 0, c->stream, src, h, w,
-                             (const float*)m->conv_w[0].p, (const float*)m->conv_b[0].p, (const float*)m->mean.p, dst,
-                             VGG_RELU[0] ? 1 : 0, m->split_f16 ? 1 : 0, himg);
+          const dim3 grid((unsigned)(((size_t)P * 4 + 255) / 256));
+          if (in.format < 0)
+            hipLaunchKernelGGL(k_conv3x3_first<false>, grid, dim3(256), 0, c->stream,
+                               (const void*)((const float*)in.p + (size_t)(g0 + b0) * H * W * 3), h, w,
+                               (const float*)m->conv_w[0].p, (const float*)m->conv_b[0].p, (const float*)m->mean.p, dst,
+                               VGG_RELU[0] ? 1 : 0, m->split_f16 ? 1 : 0, himg, 0, 0, (size_t)0);
+          else
+            hipLaunchKernelGGL(k_conv3x3_first<true>, grid, dim3(256), 0, c->stream,
+                               (const void*)((const uint8_t*)in.p + (size_t)(g0 + b0) * in.stride), h, w,
+                               (const float*)m->conv_w[0].p, (const float*)m->conv_b[0].p, (const float*)m->mean.p, dst,
+                               VGG_RELU[0] ? 1 : 0, m->split_f16 ? 1 : 0, himg, in.format, in.pitch, in.stride);
         } else {
           if ((rc = conv_layer(c, m, i, src, h, w, dst, T.cfg[i], himg)) != SF_OK) return rc;
         }
@@ -938,6 +976,15 @@ int sf_netvlad_infer_batch_impl(sf_context* c, const float* d_images, int n_img,
   }
   SF_HIP(c, hipGetLastError());
   return SF_OK;
+}
+
+int sf_netvlad_infer_batch_impl(sf_context* c, const float* d_images, int n_img, int H, int W, float* d_out, int n_out) {
+  return netvlad_infer(c, NetvladInput{d_images, -1, 0, 0}, n_img, H, W, d_out, n_out);
+}
+
+int sf_netvlad_infer_u8_batch_impl(sf_context* c, const uint8_t* d_images, int format, int n_img, int H, int W, int pitch,
+                                   size_t stride, float* d_out, int n_out) {
+  return netvlad_infer(c, NetvladInput{d_images, format, pitch, stride}, n_img, H, W, d_out, n_out);
 }
 
 int sf_netvlad_infer_impl(sf_context* c, const float* d_image, int H, int W, float* d_out, int n_out) {

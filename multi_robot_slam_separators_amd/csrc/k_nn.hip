@@ -1224,6 +1224,18 @@ static int nn_reserve(sf_context* c, NNDb& db, int n_total, int ld) {
   return SF_OK;
 }
 
+// Room for n more rows ahead of an append that must not fail half-way (sf_add_keyframes_u8_batch_device): the checks of
+// sf_nn_append and its reservation, nothing appended, nn_dim untouched.
+int sf_nn_reserve_rows(sf_context* c, NNDb& db, int n, int dim) {
+  if (n < 0 || dim <= 0) return sf_fail(c, SF_EINVAL, "bad descriptor block %d x %d", n, dim);
+  if (c->nn_dim != 0 && dim != c->nn_dim)
+    return sf_fail(c, SF_EINVAL, "descriptor dimension %d differs from the database's %d (data_handler.py:300-301 reshape)", dim, c->nn_dim);
+  if (n == 0) return SF_OK;
+  (void)sf_lanes_touch(c, false);
+  SF_HIP(c, hipSetDevice(c->device));
+  return nn_reserve(c, db, db.n + n, (dim + NN_BK - 1) / NN_BK * NN_BK);
+}
+
 // staging of the per-tick host append: pinned host + device bounce buffers owned by the handle (grow-only).  The
 // caller's rows are copied into the pinned block before the call returns (the pointer is only borrowed), the H2D
 // copy and the cast kernel are asynchronous; the next append waits for `nn_stage_done` before it overwrites the

@@ -1,6 +1,7 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
-// detection (GFTT, FAST, ORB), stereo correspondence and keyframe extraction (kernels in k_extract.hip, k_gftt.hip,
-// k_fast.hip, k_orb_detect.hip, k_lk.hip, k_cnn.hip; the detectors' sort in sf_sort.hip).
+// detection (GFTT, FAST, ORB), stereo correspondence, keyframe extraction and the camera-image forms of these calls
+// (kernels in k_extract.hip, k_gftt.hip, k_fast.hip, k_orb_detect.hip, k_lk.hip, k_cnn.hip, k_image.hip; the detectors'
+// sort in sf_sort.hip).
 #include "sf_host.hpp"
 
 // ---- the checks the entry points below share ---------------------------------------------------------------------
@@ -8,6 +9,25 @@
 static int check_image(sf_context* c, bool present, int width, int height, int pitch, int min_side, const char* what) {
   if (!present || width < min_side || height < min_side || pitch < width)
     return sf_fail(c, SF_EINVAL, "%s missing or malformed (%d x %d, pitch %d)", what, width, height, pitch);
+  return SF_OK;
+}
+
+// a camera image (sf_image_format): a row holds 3 bytes per pixel for the colour formats
+static int check_format(sf_context* c, int format) {
+  if (format != SF_IMAGE_RGB8 && format != SF_IMAGE_BGR8 && format != SF_IMAGE_MONO8)
+    return sf_fail(c, SF_EINVAL, "image format %d unknown (0 = rgb8, 1 = bgr8, 2 = mono8)", format);
+  return SF_OK;
+}
+
+static long long image_row_bytes(int format, int width) { return (long long)width * (format == SF_IMAGE_MONO8 ? 1 : 3); }
+
+static int check_camera_image(sf_context* c, bool present, int format, int width, int height, int pitch, int min_side,
+                              const char* what) {
+  int rc = check_format(c, format);
+  if (rc != SF_OK) return rc;
+  if (!present || width < min_side || height < min_side || pitch < image_row_bytes(format, width))
+    return sf_fail(c, SF_EINVAL, "%s missing or malformed (%d x %d, pitch %d, %d byte(s) per pixel)", what, width, height, pitch,
+                   format == SF_IMAGE_MONO8 ? 1 : 3);
   return SF_OK;
 }
 
@@ -391,14 +411,16 @@ extern "C" void sf_detector_defaults(sf_detector_params* p) {
 
 // The GetFeatsAndDesc handler in one call on HOST buffers: upload the pair, detect, track, extract, download the
 // response.  Everything between the two copies stays on the device; the keyframe is in the store when it returns.
-extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, const uint8_t* right, int32_t width,
-                                              int32_t height, int32_t pitch, const sf_stereo_camera* cam,
-                                              const sf_detector_params* det, const sf_stereo_flow_params* flow,
-                                              uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
-                                              int32_t* rows_out, int32_t* slot_out) {
+// format < 0: rectified MONO8 planes (sf_get_features_and_descriptor); otherwise the camera's images in that
+// sf_image_format (sf_get_features_and_descriptor_u8), converted on the device behind the upload.
+static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* right, int format, int32_t width,
+                             int32_t height, int32_t pitch, const sf_stereo_camera* cam, const sf_detector_params* det,
+                             const sf_stereo_flow_params* flow, uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out,
+                             int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
   if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
   *rows_out = 0;
-  int rc = check_image(c, left && right, width, height, pitch, 3, "stereo pair");
+  int rc = format < 0 ? check_image(c, left && right, width, height, pitch, 3, "stereo pair")
+                      : check_camera_image(c, left && right, format, width, height, pitch, 3, "stereo pair");
   if (rc != SF_OK) return rc;
   const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
   if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
@@ -415,8 +437,21 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   if ((rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64)) != SF_OK) return rc;
   uint8_t* d_left = (uint8_t*)c->ft_images.p;
   uint8_t* d_right = d_left + img_bytes;
-  SF_HIP(c, hipMemcpy2DAsync(d_left, width, left, pitch, width, height, hipMemcpyHostToDevice, c->stream));
-  SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+  if (format == SF_IMAGE_RGB8 || format == SF_IMAGE_BGR8) {
+    // the colour pair as it is (rows padded to 16 bytes: the conversion's wide path), then both planes in one launch
+    const int src_pitch = (3 * width + 15) & ~15;
+    const size_t src_bytes = ((size_t)src_pitch * height + 255) & ~(size_t)255;
+    if ((rc = sf_buf_reserve(c, c->img_src, 2 * src_bytes)) != SF_OK) return rc;
+    uint8_t* d_src = (uint8_t*)c->img_src.p;
+    SF_HIP(c, hipMemcpy2DAsync(d_src, src_pitch, left, pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
+    SF_HIP(c, hipMemcpy2DAsync(d_src + src_bytes, src_pitch, right, pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
+    if ((rc = sf_launch_image_gray(c, d_src, nullptr, 2, format, c->gray_rule, width, height, src_pitch, src_bytes, 2, d_left,
+                                   width, img_bytes)) != SF_OK)
+      return rc;
+  } else {                                                 // MONO8 planes, or mono8 camera images: the pitched copy is the upload
+    SF_HIP(c, hipMemcpy2DAsync(d_left, width, left, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+    SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+  }
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t n = 0;
   // (the GFTT parameters are checked under every feature type, FAST and ORB included, which do not use them)
@@ -453,45 +488,85 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
   return SF_OK;
 }
 
+extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, const uint8_t* right, int32_t width,
+                                              int32_t height, int32_t pitch, const sf_stereo_camera* cam,
+                                              const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                              uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
+                                              int32_t* rows_out, int32_t* slot_out) {
+  return get_features_host(c, left, right, -1, width, height, pitch, cam, det, flow, desc_out, xyz_out, kpts_out, cap_rows,
+                           rows_out, slot_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_u8(sf_handle c, const uint8_t* left, const uint8_t* right, int32_t format,
+                                                 int32_t width, int32_t height, int32_t pitch, const sf_stereo_camera* cam,
+                                                 const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                 uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
+                                                 int32_t* rows_out, int32_t* slot_out) {
+  if (!c) return SF_EINVAL;
+  const int rc = check_format(c, format);
+  if (rc != SF_OK) return rc;
+  return get_features_host(c, left, right, format, width, height, pitch, cam, det, flow, desc_out, xyz_out, kpts_out, cap_rows,
+                           rows_out, slot_out);
+}
+
 // n keyframes from device images to n store slots in ONE launch sequence: detector, stereo correspondence and
 // extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
 // host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.
-extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
-                                                           int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
-                                                           size_t image_stride, const sf_stereo_camera* cam,
-                                                           const sf_detector_params* det, const sf_stereo_flow_params* flow,
-                                                           int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
-                                                           float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+// The batch form in three parts, shared by sf_get_features_and_descriptor_batch_device and
+// sf_add_keyframes_u8_batch_device: batch_check refuses (nothing is touched; n_keyframes = 0 passes without a look at the
+// images), batch_reserve takes the store slots and the call's buffers, batch_launch queues the three stages.
+struct BatchPlan {
+  sf_detector_params dp;
+  sf_stereo_flow_params prm;
+  ExtractKind kind;
+};
+
+static int batch_check(sf_context* c, bool images, int n_keyframes, int width, int height, int pitch, size_t image_stride,
+                       const sf_detector_params* det, const sf_stereo_flow_params* flow, BatchPlan* plan) {
   if (c->feature_type == 2)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has no batch form yet: use sf_get_features_and_descriptor per keyframe");
-  if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
-  int rc = check_image(c, d_left && d_right, width, height, pitch, 3, "stereo pairs");
+  if (n_keyframes == 0) return SF_OK;
+  int rc = check_image(c, images, width, height, pitch, 3, "stereo pairs");
   if (rc != SF_OK) return rc;
   if (image_stride < (size_t)pitch * height)
     return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
-  const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
-  if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
-    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
-  if ((rc = check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
-  const sf_stereo_flow_params prm = arg_or_defaults(flow, sf_stereo_flow_defaults);
+  plan->dp = arg_or_defaults(det, sf_detector_defaults);
+  if (plan->dp.max_features <= 0 || plan->dp.max_features > SF_MAX_FEATURES)
+    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", plan->dp.max_features, SF_MAX_FEATURES);
+  if ((rc = check_gftt(c, plan->dp.quality_level, plan->dp.min_distance)) != SF_OK) return rc;
+  plan->prm = arg_or_defaults(flow, sf_stereo_flow_defaults);
+  const sf_stereo_flow_params& prm = plan->prm;
   if (prm.win_width <= 2 || prm.win_height <= 2 || (long long)prm.win_width * prm.win_height > 1024 || prm.max_level < 0 ||
       prm.max_level > 15 || !(prm.epsilon == prm.epsilon))
     return sf_fail(c, SF_EINVAL, "stereo flow parameters out of range (see sf_stereo_correspondences_device)");
   if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
+  return SF_OK;
+}
+
+static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan* plan) {
+  int rc;
   SF_HIP(c, hipSetDevice(c->device));
-  ExtractKind kind;
-  if ((rc = extract_kind(c, &kind)) != SF_OK) return rc;
-  const int maxf = dp.max_features, n = n_keyframes;
+  if ((rc = extract_kind(c, &plan->kind)) != SF_OK) return rc;
+  const int maxf = plan->dp.max_features;
   const size_t rows_all = (size_t)maxf * n;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_flow, rows_all * 16)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_counts, (size_t)n * 4)) != SF_OK) return rc;
-  if ((rc = sf_store_reserve(c, c->store, c->store.slots + n, maxf, kind.bytes)) != SF_OK) return rc;
+  if ((rc = sf_store_reserve(c, c->store, c->store.slots + n, maxf, plan->kind.bytes)) != SF_OK) return rc;
+  if (c->feature_type == 4 && (rc = check_pixels(c, width, height)) != SF_OK) return rc;
+  return SF_OK;
+}
+
+static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_left, const uint8_t* d_right, int n, int width,
+                        int height, int pitch, size_t image_stride, const sf_stereo_camera* cam, int32_t* first_slot_out,
+                        int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  const sf_detector_params& dp = plan.dp;
+  const int maxf = dp.max_features;
+  const size_t rows_all = (size_t)maxf * n;
+  int rc;
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t* d_n = (int32_t*)c->ft_counts.p;
   if (c->feature_type == 4) {
-    if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
     rc = sf_launch_detect_fast_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
   } else {
     rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
@@ -501,14 +576,141 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
   float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
   float* d_rx = d_xy + 2 * rows_all;
   uint8_t* d_status = (uint8_t*)(d_rx + rows_all);
-  if ((rc = sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &prm,
+  if ((rc = sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &plan.prm,
                                         d_xy, d_status, d_rx, nullptr)) != SF_OK)
     return rc;
   const int slot = c->store.slots;
-  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, kind,
+  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, plan.kind,
                                     slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out)) != SF_OK)
     return rc;
   c->store.slots += n;
   if (first_slot_out) *first_slot_out = slot;
+  return SF_OK;
+}
+
+extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                           int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                                           size_t image_stride, const sf_stereo_camera* cam,
+                                                           const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                           int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                           float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  BatchPlan plan;
+  int rc = batch_check(c, d_left && d_right, n_keyframes, width, height, pitch, image_stride, det, flow, &plan);
+  if (rc != SF_OK) return rc;
+  if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
+  if ((rc = batch_reserve(c, n_keyframes, width, height, &plan)) != SF_OK) return rc;
+  return batch_launch(c, plan, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, first_slot_out, d_rows_out,
+                      d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+// ---- the camera's own images (kernels in k_image.hip, k_cnn.hip) ---------------------------------------------------
+extern "C" int sf_image_set_gray_rule(sf_handle c, int32_t rule) {
+  if (!c) return SF_EINVAL;
+  int k[4];
+  if (!sf_gray_rule(rule, &k[0], &k[1], &k[2], &k[3]))
+    return sf_fail(c, SF_EINVAL, "gray rule %d unknown (0 = OpenCV 3.x, 1 = OpenCV 4.x)", rule);
+  c->gray_rule = rule;
+  return SF_OK;
+}
+
+extern "C" int sf_image_get_gray_rule(sf_handle c, int32_t* rule) {
+  if (!c || !rule) return SF_EINVAL;
+  *rule = c->gray_rule;
+  return SF_OK;
+}
+
+// an array of n images `stride` bytes apart: the last image needs its rows only, not a whole stride
+static int check_stride(sf_context* c, int n, size_t stride, int pitch, int height, long long last_row, const char* what) {
+  if (n > 1 && stride < (size_t)pitch * (height - 1) + (size_t)last_row)
+    return sf_fail(c, SF_EINVAL, "%s stride %zu is less than an image (%d rows of pitch %d)", what, stride, height, pitch);
+  return SF_OK;
+}
+
+extern "C" int sf_image_to_gray_device(sf_handle c, const uint8_t* d_src, int32_t format, int32_t width, int32_t height,
+                                       int32_t src_pitch, size_t src_stride, int32_t n_images, uint8_t* d_dst,
+                                       int32_t dst_pitch, size_t dst_stride) {
+  if (!c || n_images < 0) return SF_EINVAL;
+  int rc = check_format(c, format);
+  if (rc != SF_OK) return rc;
+  if (n_images == 0) return SF_OK;
+  if ((rc = check_camera_image(c, d_src, format, width, height, src_pitch, 1, "source images")) != SF_OK) return rc;
+  if ((rc = check_image(c, d_dst, width, height, dst_pitch, 1, "gray planes")) != SF_OK) return rc;
+  if ((rc = check_stride(c, n_images, src_stride, src_pitch, height, image_row_bytes(format, width), "source")) != SF_OK) return rc;
+  if ((rc = check_stride(c, n_images, dst_stride, dst_pitch, height, width, "destination")) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_image_gray(c, d_src, nullptr, n_images, format, c->gray_rule, width, height, src_pitch, src_stride, n_images,
+                              d_dst, dst_pitch, dst_stride);
+}
+
+extern "C" int sf_netvlad_infer_u8_batch_device(sf_handle c, const uint8_t* d_images, int32_t format, int32_t n_images,
+                                                int32_t width, int32_t height, int32_t pitch, size_t image_stride,
+                                                float* d_out, int32_t n_out) {
+  if (!c || !d_out) return SF_EINVAL;
+  int rc = check_camera_image(c, d_images, format, width, height, pitch, 1, "images");
+  if (rc != SF_OK) return rc;
+  if ((rc = check_stride(c, n_images, image_stride, pitch, height, image_row_bytes(format, width), "image")) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_infer_u8_batch_impl(c, d_images, format, n_images, height, width, pitch, image_stride, d_out, n_out);
+}
+
+// get_keyframes + compute_descriptors for n keyframes (data_handler.py:143-164, 212-295): gray planes of all 2 n stereo
+// images (one launch), the network on the colour images, the batch feature stages on the planes, the descriptors' prefix
+// into the local NN rows.  Everything that can refuse does so before the first launch; the store and the NN database
+// grow last, together.
+extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                int32_t height, int32_t pitch, size_t image_stride,
+                                                const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  const int n = n_keyframes;
+  int rc;
+  if ((rc = check_format(c, format)) != SF_OK) return rc;
+  if (n > 0) {
+    if ((rc = check_camera_image(c, d_left && d_right, format, width, height, pitch, 3, "stereo pairs")) != SF_OK) return rc;
+    if (image_stride < (size_t)pitch * height)
+      return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
+  }
+  // the planes this call makes: rows padded to 16 bytes, n left then n right
+  const int g_pitch = n > 0 ? (width + 15) & ~15 : 0;
+  const size_t g_stride = ((size_t)g_pitch * (n > 0 ? height : 0) + 255) & ~(size_t)255;
+  BatchPlan plan;
+  if ((rc = batch_check(c, true, n, width, height, g_pitch, g_stride, det, flow, &plan)) != SF_OK) return rc;
+  if (n == 0) {
+    if (first_slot_out) *first_slot_out = c->store.slots;
+    if (first_nn_row_out) *first_nn_row_out = c->nn_local.n;
+    return SF_OK;
+  }
+  const int dims = c->params.netvlad_dimensions, pca_dim = sf_netvlad_pca_dim(c);
+  if (pca_dim == 0) return sf_fail(c, SF_EINVAL, "no NetVLAD model loaded (sf_netvlad_load)");
+  if (dims < 1 || dims > pca_dim)
+    return sf_fail(c, SF_EINVAL, "netvlad_dimensions %d is beyond the loaded model's %d WPCA outputs", dims, pca_dim);
+  if ((rc = sf_netvlad_check(c, n, height, width, dims)) != SF_OK) return rc;
+  if ((rc = sf_nn_reserve_rows(c, c->nn_local, n, dims)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->img_gray, 2 * (size_t)n * g_stride)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->img_desc, (size_t)n * dims * sizeof(float))) != SF_OK) return rc;
+  if ((rc = batch_reserve(c, n, width, height, &plan)) != SF_OK) return rc;
+  uint8_t* g_left = (uint8_t*)c->img_gray.p;
+  uint8_t* g_right = g_left + (size_t)n * g_stride;
+  if ((rc = sf_launch_image_gray(c, d_left, d_right, n, format, c->gray_rule, width, height, pitch, image_stride, 2 * n, g_left,
+                                 g_pitch, g_stride)) != SF_OK)
+    return rc;
+  if ((rc = sf_netvlad_infer_u8_batch_impl(c, d_rgb ? d_rgb : d_left, format, n, height, width, pitch, image_stride,
+                                           (float*)c->img_desc.p, dims)) != SF_OK)
+    return rc;
+  int32_t slot = -1;
+  if ((rc = batch_launch(c, plan, g_left, g_right, n, width, height, g_pitch, g_stride, cam, &slot, d_rows_out, d_desc_out,
+                         d_xyz_out, d_kpts_out)) != SF_OK)
+    return rc;
+  const int row = c->nn_local.n;
+  if ((rc = sf_nn_append(c, c->nn_local, c->img_desc.p, n, dims, 1)) != SF_OK) {
+    c->store.slots -= n;             // (the slots' rows stay behind the end of the store: the keyframes were never added)
+    return rc;
+  }
+  if (first_slot_out) *first_slot_out = slot;
+  if (first_nn_row_out) *first_nn_row_out = row;
   return SF_OK;
 }

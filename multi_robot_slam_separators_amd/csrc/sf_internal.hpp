@@ -229,6 +229,11 @@ struct sf_context {
   Buf gf_planes, gf_keys, gf_tmp, gf_lists, gf_scalar;
   Buf lk_pyr;                      // pyramid levels >= 1 of both images (k_lk.hip)
   Buf ft_images, ft_kpts, ft_flow, ft_wire;   // sf_get_features_and_descriptor: device copies of the pair, corners, LK outputs, response
+  // camera images (k_image.hip): the uploaded rgb8 / bgr8 / mono8 pair of sf_get_features_and_descriptor_u8, the gray
+  // planes of a batch (sf_add_keyframes_u8_batch_device: n left, then n right) and its NetVLAD rows; the colour-to-gray
+  // coefficients (sf_image_set_gray_rule: 0 = OpenCV 3.x, 1 = OpenCV 4.x)
+  Buf img_src, img_gray, img_desc;
+  int gray_rule = 0;
   struct sf_netvlad_model* netvlad = nullptr;   // NetVLAD inference (k_cnn.hip): weights + activation buffers
   int brief_bytes = 0;                 // 0: table not uploaded yet
   int8_t brief_host[64 * 8 * 4] = {};
@@ -450,6 +455,19 @@ void sf_netvlad_free(sf_context* c);
 int sf_netvlad_load_impl(sf_context* c, const sf_netvlad_weights* w);
 int sf_netvlad_infer_impl(sf_context* c, const float* d_image, int H, int W, float* d_out, int n_out);
 int sf_netvlad_infer_batch_impl(sf_context* c, const float* d_images, int n_img, int H, int W, float* d_out, int n_out);
+// the same from 8-bit camera images (format: sf_image_format; rows of `pitch` bytes, images `stride` bytes apart);
+// sf_netvlad_check: the argument checks of both, without a launch
+int sf_netvlad_infer_u8_batch_impl(sf_context* c, const uint8_t* d_images, int format, int n_img, int H, int W, int pitch,
+                                   size_t stride, float* d_out, int n_out);
+int sf_netvlad_check(sf_context* c, int n_img, int H, int W, int n_out);
+int sf_netvlad_pca_dim(const sf_context* c);   // 0: no model loaded
+// k_image.hip
+bool sf_gray_rule(int rule, int* kr, int* kg, int* kb, int* shift);
+int sf_launch_image_gray(sf_context* c, const uint8_t* d_src0, const uint8_t* d_src1, int n_first, int format, int rule,
+                         int width, int height, int src_pitch, size_t src_stride, int n_images, uint8_t* d_dst, int dst_pitch,
+                         size_t dst_stride);
+// k_nn.hip: room for n more rows of `dim` values in a database, without appending (SF_EINVAL: another dimension)
+int sf_nn_reserve_rows(sf_context* c, NNDb& db, int n, int dim);
 StoreView sf_store_view(const Store& s);
 void sf_prof_begin(sf_context* c, int kernel);
 void sf_prof_end(sf_context* c, int kernel);

@@ -4,11 +4,20 @@ argument meaning and state (`local_kf_already_used`, `other_kf_already_used`,
 `frames_kept_pairs_ignored`, `kf_ids_of_frames_kept`, `nb_descriptors_already_sent`), with the
 arithmetic delegated to the MI355X library through a small backend interface.
 
-Out of scope and therefore absent: image queues, keyframe selection, TensorFlow NetVLAD
-inference, GPS logging, rospy plumbing.  Keyframes enter through `add_keyframe()` with their
-already-computed NetVLAD descriptor and geometric features (what `get_keyframes` +
-`compute_descriptors` produce in the reference, data_handler.py:143-164,212-295).
+Keyframes enter in one of two ways.  `add_keyframe()` takes an already-computed NetVLAD descriptor
+and geometric features.  `add_keyframe_images()` takes the images the reference's queues hold --
+`[h, w, 3]` uint8 "rgb8" (data_handler.py:114-141) -- and does what `get_keyframes` does once it has
+picked them (:268-271): `compute_geom_features()` (:424-435: both stereo images to gray, then
+GetFeatsAndDesc) into `geometric_feats`, the rgb image into `images_rgb_kf`; `compute_descriptors()`
+(:143-164) then runs the network on up to `netvlad_batch_size` queued images per call.  Both
+conversions -- colour to gray, uint8 to the network's float input -- happen on the device inside the
+backend's calls; TensorFlow is replaced by the library's NetVLAD kernels.
+
+Out of scope and therefore absent: the image queues by timestamp and the keyframe selection of
+`get_keyframes` (closest stamps, `number_of_kf_skipped`), GPS logging, rospy plumbing.
 """
+import collections
+
 import numpy as np
 
 from . import _abi
@@ -55,11 +64,28 @@ class FinderBackend:
         self.slots.append(slot)
         return desc, xyz, kp
 
+    def get_features_u8(self, left, right, format=_abi.SF_IMAGE_RGB8):
+        """get_features on the camera's images ([h, w, 3] uint8 rgb8 / bgr8, [h, w] mono8): gray conversion on the device."""
+        if self.cam is None:
+            raise ValueError("FinderBackend needs the stereo camera model for get_features_u8")
+        desc, xyz, kp, slot = self.f.get_features_and_descriptor_u8(left, right, format, self.cam, self.detector,
+                                                                    self.stereo_flow)
+        self.slots.append(slot)
+        return desc, xyz, kp
+
+    def netvlad_u8(self, images, format=_abi.SF_IMAGE_RGB8):
+        """[n, netvlad_dimensions] float32: the descriptors' prefix of n uint8 images of one size (needs a loaded model)."""
+        return self.f.netvlad_u8(images, format)
+
 
 class DataHandler:
     def __init__(self, backend, local_robot_id, other_robot_id, netvlad_dimensions=128,
-                 send_estimates_of_poses=False, add_separators_pose_graph=None):
+                 send_estimates_of_poses=False, add_separators_pose_graph=None, netvlad_batch_size=3,
+                 image_format=_abi.SF_IMAGE_RGB8):
         self.backend = backend
+        self.netvlad_batch_size = netvlad_batch_size  # :98, multi_robot_separators.launch
+        self.image_format = image_format              # "rgb8" in the reference (:114-141)
+        self.images_rgb_kf = collections.deque()      # :44
         self.local_robot_id = local_robot_id          # data_handler.py:88-89
         self.other_robot_id = other_robot_id
         self.netvlad_dimensions = netvlad_dimensions  # :97
@@ -90,6 +116,44 @@ class DataHandler:
         self.backend.nn_append_local(d.reshape(1, -1))
         self.geometric_feats.append(geometric_feats)
         self.kf_ids_of_frames_kept.append(kf_id)
+
+    # ---- data_handler.py:268-271 (the tail of get_keyframes, once the three images are picked) ---
+    def add_keyframe_images(self, image_l, image_r, image_rgb=None, kf_id=None):
+        """Returns False, and adds nothing, when no features could be computed (:264-266).  image_rgb None: the left image."""
+        self.nb_kf_odom += 1
+        geometric_feats = self.compute_geom_features(image_l, image_r)
+        if not geometric_feats:
+            return False
+        kf_id = self.nb_kf_odom - 1 if kf_id is None else kf_id
+        check_int16([kf_id, len(self.geometric_feats)], "keyframe id")
+        self.geometric_feats.append(geometric_feats)
+        self.images_rgb_kf.append(image_l if image_rgb is None else image_rgb)
+        self.kf_ids_of_frames_kept.append(kf_id)       # :287
+        return True
+
+    # ---- data_handler.py:424-435 ----------------------------------------------------------------
+    def compute_geom_features(self, image_l, image_r):
+        """image_l / image_r as the reference's queues hold them: [h, w, 3] uint8 (self.image_format)."""
+        desc, xyz, kp = self.backend.get_features_u8(image_l, image_r, self.image_format)
+        return GeomFeatures(desc, xyz, kp)
+
+    # ---- data_handler.py:143-164 ----------------------------------------------------------------
+    def compute_descriptors(self):
+        """As much of the queue as one batch takes, from the left; returns the number of descriptors added."""
+        nb_images_batch = min(len(self.images_rgb_kf), self.netvlad_batch_size)
+        if nb_images_batch == 0:                      # :163-164 "Empty batch"
+            return 0
+        batch = [self.images_rgb_kf[i] for i in range(nb_images_batch)]
+        descriptors = np.asarray(self.backend.netvlad_u8(batch, self.image_format), dtype=np.float64)
+        descriptors = descriptors.reshape(nb_images_batch, -1)
+        if descriptors.shape[1] < self.netvlad_dimensions:
+            raise ValueError("NetVLAD descriptor shorter than netvlad_dimensions")
+        rows = np.ascontiguousarray(descriptors[:, :self.netvlad_dimensions])   # :157-158
+        self.local_descriptors.extend(rows)
+        self.backend.nn_append_local(rows)
+        for _ in range(nb_images_batch):              # :161-162
+            self.images_rgb_kf.popleft()
+        return nb_images_batch
 
     # ---- data_handler.py:166-209 ----------------------------------------------------------------
     def find_matches(self):

@@ -145,6 +145,16 @@ def load():
         "sf_nn_walk_device": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, i32, vp]),
         "sf_get_features_and_descriptor_batch_device": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, C.c_size_t, vp, vp, vp,
                                                                    P(i32), vp, vp, vp, vp]),
+        "sf_image_set_gray_rule": (C.c_int, [vp, i32]),
+        "sf_image_get_gray_rule": (C.c_int, [vp, P(i32)]),
+        "sf_image_to_gray_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]),
+        "sf_netvlad_infer_u8_batch_device": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, C.c_size_t, vp, i32]),
+        "sf_get_features_and_descriptor_u8": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, P(_abi.StereoCamera),
+                                                        P(_abi.DetectorParams), P(_abi.StereoFlowParams), vp, vp, vp, i32,
+                                                        P(i32), P(i32)]),
+        "sf_add_keyframes_u8_batch_device": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_size_t,
+                                                       P(_abi.StereoCamera), P(_abi.DetectorParams),
+                                                       P(_abi.StereoFlowParams), P(i32), P(i32), vp, vp, vp, vp]),
         "sf_prof_enable": (C.c_int, [vp, C.c_int]),
         "sf_prof_select": (C.c_int, [vp, C.c_uint32]),
         "sf_stream_placement": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
@@ -184,11 +194,38 @@ EXPORTED = [
     "sf_orb_defaults", "sf_set_feature_type", "sf_get_feature_type", "sf_orb_set_pattern", "sf_orb_get_pattern",
     "sf_fast_defaults", "sf_fast_set_params", "sf_fast_get_params", "sf_detect_fast_device",
     "sf_orb_detector_defaults", "sf_set_feature_type_orb", "sf_get_orb_detector", "sf_detect_orb_device",
+    "sf_image_set_gray_rule", "sf_image_get_gray_rule", "sf_image_to_gray_device", "sf_netvlad_infer_u8_batch_device",
+    "sf_get_features_and_descriptor_u8", "sf_add_keyframes_u8_batch_device",
 ]
 
 
 def _ptr(a):
     return a.ctypes.data if a is not None and a.size else None
+
+
+def upload(array, device=0):
+    """A host array as a torch tensor on the GPU (the small upload helper of the calls that take device images: torch is
+    the plumbing here, and the tensor keeps the memory alive)."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(array)).to(torch.device("cuda:%d" % device))
+
+
+def _camera_image(image, fmt):
+    """A uint8 image as the camera calls take it: [h, w, 3] for rgb8 / bgr8, [h, w] (or [h, w, 1]) for mono8, bytes of a
+    pixel and pixels of a row contiguous, any row stride.  Returns (array, width, height, pitch)."""
+    a = np.asarray(image)
+    if a.dtype != np.uint8:
+        raise ValueError("camera images are uint8, not %s" % a.dtype)
+    if fmt == _abi.SF_IMAGE_MONO8 and a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    ch = 1 if fmt == _abi.SF_IMAGE_MONO8 else 3
+    ok = (a.ndim == 2 and a.strides[1] == 1) if ch == 1 else (a.ndim == 3 and a.shape[2] == 3 and a.strides[2] == 1
+                                                              and a.strides[1] == 3)
+    if not ok or a.strides[0] < a.shape[1] * ch:
+        a = np.ascontiguousarray(a)
+        if a.ndim != (2 if ch == 1 else 3) or (ch == 3 and a.shape[2] != 3):
+            raise ValueError("image of shape %s does not fit format %d" % (a.shape, fmt))
+    return a, a.shape[1], a.shape[0], a.strides[0]
 
 
 class SeparatorFinder:
@@ -415,6 +452,83 @@ class SeparatorFinder:
         """n_images images [H][W][3] float32 back to back on the device -> d_out [n_images][n_out] (data_handler.py:149-156)."""
         self._check(self._L.sf_netvlad_infer_batch_device(self._h, C.c_void_p(d_images_rgb), n_images, width, height,
                                                           C.c_void_p(d_out), n_out))
+
+    # -- the camera's own images (rgb8 / bgr8 / mono8: _abi.SF_IMAGE_*) -----------------------------------------------
+    def image_set_gray_rule(self, rule):
+        """Coefficients of the colour-to-gray conversion: _abi.GRAY_RULE_OPENCV3 (a fresh handle) or GRAY_RULE_OPENCV4."""
+        self._check(self._L.sf_image_set_gray_rule(self._h, int(rule)))
+
+    def image_get_gray_rule(self):
+        r = C.c_int32()
+        self._check(self._L.sf_image_get_gray_rule(self._h, C.byref(r)))
+        return r.value
+
+    def image_to_gray_device(self, d_src, fmt, width, height, src_pitch, src_stride, n_images, d_dst, dst_pitch,
+                             dst_stride):
+        """cv2.cvtColor(..., COLOR_RGB2GRAY) of n_images device images (raw pointers) in one launch; asynchronous."""
+        self._check(self._L.sf_image_to_gray_device(self._h, C.c_void_p(d_src), int(fmt), width, height, src_pitch,
+                                                    int(src_stride), n_images, C.c_void_p(d_dst), dst_pitch,
+                                                    int(dst_stride)))
+
+    def netvlad_infer_u8_batch_device(self, d_images, fmt, n_images, width, height, pitch, image_stride, d_out, n_out):
+        """netvlad_infer_batch_device on 8-bit device images (rows of `pitch` bytes, images image_stride bytes apart)."""
+        self._check(self._L.sf_netvlad_infer_u8_batch_device(self._h, C.c_void_p(d_images), int(fmt), n_images, width,
+                                                             height, pitch, int(image_stride), C.c_void_p(d_out), n_out))
+
+    def netvlad_u8(self, images, fmt=_abi.SF_IMAGE_RGB8, n_out=None):
+        """NetVLAD descriptors of host images of one size (a sequence of uint8 arrays in `fmt`): uploads the bytes, runs
+        the network on them, returns [n, n_out] float32 (n_out None: params.netvlad_dimensions)."""
+        imgs = [np.ascontiguousarray(_camera_image(im, fmt)[0]) for im in images]
+        n_out = self.params.netvlad_dimensions if n_out is None else int(n_out)
+        if not imgs:
+            return np.zeros((0, n_out), np.float32)
+        batch = np.stack(imgs)
+        h, w = batch.shape[1], batch.shape[2]
+        import torch
+        d_in = upload(batch, self.device)
+        d_out = torch.zeros((len(imgs), n_out), dtype=torch.float32, device=d_in.device)
+        torch.cuda.current_stream(d_in.device).synchronize()       # (the handle's stream may be another one)
+        self.netvlad_infer_u8_batch_device(d_in.data_ptr(), fmt, len(imgs), w, h, batch.strides[1], batch.strides[0],
+                                           d_out.data_ptr(), n_out)
+        self.synchronize()
+        return d_out.cpu().numpy()
+
+    def get_features_and_descriptor_u8(self, left, right, fmt, cam, det=None, flow=None):
+        """get_features_and_descriptor on the camera's images (host uint8, [h, w, 3] for rgb8 / bgr8, [h, w] for mono8):
+        uploaded as they are, converted to gray on the device under the handle's gray rule."""
+        left, w, h, pitch = _camera_image(left, fmt)
+        right, w2, h2, pitch2 = _camera_image(right, fmt)
+        if (w, h) != (w2, h2):
+            raise ValueError("left / right must be images of one shape")
+        if pitch != pitch2:
+            left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+            pitch = left.strides[0]
+        cap = (det.max_features if det is not None else 1000)
+        nbytes = self.descriptor_bytes()
+        desc = np.zeros((cap, nbytes), np.uint8)
+        xyz = np.zeros((cap, 3), np.float32)
+        kp = np.zeros(cap, _abi.KEYPOINT_DTYPE)
+        rows, slot = C.c_int32(), C.c_int32()
+        self._check(self._L.sf_get_features_and_descriptor_u8(
+            self._h, C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data), int(fmt), w, h, pitch, C.byref(cam),
+            C.byref(det) if det is not None else None, C.byref(flow) if flow is not None else None,
+            C.c_void_p(desc.ctypes.data), C.c_void_p(xyz.ctypes.data), C.c_void_p(kp.ctypes.data), cap, C.byref(rows),
+            C.byref(slot)))
+        n = min(rows.value, cap)
+        return desc[:n].copy(), xyz[:n].copy(), kp[:n].copy(), slot.value
+
+    def add_keyframes_u8_batch_device(self, d_left, d_right, d_rgb, fmt, n_keyframes, width, height, pitch, image_stride,
+                                      cam, det=None, flow=None, d_rows_out=None, d_desc_out=None, d_xyz_out=None,
+                                      d_kpts_out=None):
+        """n keyframes from the camera's device images (raw pointers; d_rgb None = the left images) to n store slots and n
+        local NN rows in one launch sequence, no host wait.  Returns (first slot, first local NN row)."""
+        first, row = C.c_int32(-1), C.c_int32(-1)
+        self._check(self._L.sf_add_keyframes_u8_batch_device(
+            self._h, C.c_void_p(d_left), C.c_void_p(d_right), C.c_void_p(d_rgb), int(fmt), n_keyframes, width, height,
+            pitch, int(image_stride), C.byref(cam), C.byref(det) if det is not None else None,
+            C.byref(flow) if flow is not None else None, C.byref(first), C.byref(row), C.c_void_p(d_rows_out),
+            C.c_void_p(d_desc_out), C.c_void_p(d_xyz_out), C.c_void_p(d_kpts_out)))
+        return first.value, row.value
 
     def set_feature_type_orb(self, det=None, orb=None):
         """Vis/FeatureType 2, ORB on a pyramid: det (_abi.OrbDetectorParams; None = rtabmap's ORB/ defaults) drives the
