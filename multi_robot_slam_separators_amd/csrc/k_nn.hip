@@ -50,54 +50,17 @@ __device__ __forceinline__ void nn_tile_of_block(int bid, int gx, int gy, int& t
   tx = in / gsz;
 }
 
-// SF_NN_T256 = 0: the 128 x 128-tile filter for every non-128 level (A/B runs)
-static bool nn_t256_on() {
-  static const bool on = !(getenv("SF_NN_T256") && atoi(getenv("SF_NN_T256")) == 0);
-  return on;
-}
-
+// Row ingest, one wavefront per row: T rows -> f32 rows (zero padded to ld) + squared norms of the f32 values.
+// T = double (host rows through the staging buffer), float, or _Float16 (BASELINE configs[4] ships NetVLAD in fp16:
+// every half is exactly representable in fp32, so the database holds the same numbers and everything downstream is
+// unchanged).
+template <typename T>
 __global__ void __launch_bounds__(256)
-k_nn_cast_rows(const double* __restrict__ src, float* __restrict__ dst, float* __restrict__ norms, int n, int dim,
-               int ld) {
-  // one wavefront per row: f64 -> f32 rows (zero padded to ld) + squared norms of the f32 values
+k_nn_ingest_rows(const T* __restrict__ src, float* __restrict__ dst, float* __restrict__ norms, int n, int dim, int ld) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= n) return;
   double s = 0.0;   // squared norm of the float32 row, accumulated in float64 (error 2^-24 relative)
-  for (int k = lane; k < ld; k += 64) {
-    float v = (k < dim) ? (float)src[(size_t)row * dim + k] : 0.f;
-    dst[(size_t)row * ld + k] = v;
-    s += (double)v * (double)v;
-  }
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-  if (lane == 0) norms[row] = (float)s;
-}
-
-__global__ void __launch_bounds__(256)
-k_nn_copy_rows(const float* __restrict__ src, float* __restrict__ dst, float* __restrict__ norms, int n, int dim,
-               int ld) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  double s = 0.0;
-  for (int k = lane; k < ld; k += 64) {
-    float v = (k < dim) ? src[(size_t)row * dim + k] : 0.f;
-    dst[(size_t)row * ld + k] = v;
-    s += (double)v * (double)v;
-  }
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-  if (lane == 0) norms[row] = (float)s;
-}
-
-// fp16 descriptors (BASELINE configs[4] ships NetVLAD in fp16): every half is exactly representable in fp32, so
-// the database holds the same numbers and everything downstream is unchanged.
-__global__ void __launch_bounds__(256)
-k_nn_copy_rows_f16(const _Float16* __restrict__ src, float* __restrict__ dst, float* __restrict__ norms, int n,
-                   int dim, int ld) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  double s = 0.0;
   for (int k = lane; k < ld; k += 64) {
     float v = (k < dim) ? (float)src[(size_t)row * dim + k] : 0.f;
     dst[(size_t)row * ld + k] = v;
@@ -352,10 +315,10 @@ __global__ void __launch_bounds__(256) k_nn_to_f16(const float* __restrict__ row
 // (delta = 2e-6 also covers the rounding of this rearrangement).  Masked / padding rows and columns get
 // A = +inf (resp. B = +inf) and C = D = 0, so they can never be candidates.
 // C_i and D_j are rounded UP to fp16-representable values (a larger error allowance keeps the filter a superset):
-// the resident-panel kernel feeds them to the matrix cores as one more contraction step.  Their product is
+// k_nn_filter_f16_k128r feeds them to the matrix cores as one more contraction step.  Their product is
 // eps (s_a |a|)(s_b |b|); the scaled norms reach sqrt(k) 2^15, so the split is C = 64 eps s_a |a| (<= 2.4e4 at
 // k = 128) and D = s_b |b| / 64 (<= 5.8e3): both inside fp16's range whatever the data.  delta = 2e-6 plus
-// (k + 8) 2^-24 for the fp32 additions that now also carry -A_i (k_nn_filter_f16_k128 starts its accumulators there).
+// (k + 8) 2^-24 for the fp32 additions that now also carry -A_i (k_nn_filter_f16_k128r starts its accumulators there).
 __device__ __forceinline__ float nn_up_to_f16(float x) {   // x >= 0
   _Float16 hv = (_Float16)x;
   if ((float)hv < x) {
@@ -388,6 +351,9 @@ __global__ void k_nn_filter_col_coef(float2* colc, const float* nb, const uint8_
 // A16: local rows [n_l_pad][ld] fp16 (x scale_a), B16: received rows [n_r_pad][ld] fp16 (x scale_b).
 // A (row, col) pair is emitted when its fp16 distance estimate can be below thr2 given the
 // rigorous error bound  |dot16 - dot32| <= eps_rel * sqrt(na * nb).
+// The classic structure: 128 x 128 tile, register-staged, two barriers per 64-deep K step.  It serves the contraction
+// lengths the two kernels below do not: 64 and 192 halfs, the full-length level of descriptors of at most 64 and of
+// 129 .. 192 dimensions (128 goes to k_nn_filter_f16_k128r, 256 and longer to k_nn_filter_f16_t256).
 __global__ void __launch_bounds__(256)
 k_nn_filter_f16(const _Float16* __restrict__ A, const _Float16* __restrict__ B, const float2* __restrict__ rowc,
                 const float2* __restrict__ colc, int ld, int kdims, int gx, int gy,
@@ -495,10 +461,11 @@ k_nn_filter_f16(const _Float16* __restrict__ A, const _Float16* __restrict__ B, 
   }
 }
 
-// ---- the same filter on 256 x 256 tiles, LDS-DMA fed (round 5; the full-length contraction of --strict) ------------
-// k_nn_filter_f16 above is the classic structure -- 128 x 128 tile, register-staged, two barriers per 64-deep K step --
-// and sits at its ceiling (0.89 PF = 36 % of the fp16 peak on the 10 000 x 10 000 x 4096 contraction; fabric traffic
-// 3 GB per launch: each operand panel is re-read 79 times).  This form: eight wavefronts (2 x 4) own a 256 x 256 tile,
+// ---- the same filter on 256 x 256 tiles, LDS-DMA fed: every contraction of 256 halfs or more (the 512 prefix level and
+// the full length of descriptors over 192 dimensions, among them the full-length contraction of --strict) -------------
+// k_nn_filter_f16's structure sits at its ceiling on a long contraction (0.89 PF = 36 % of the fp16 peak on
+// 10 000 x 10 000 x 4096; fabric traffic 3 GB per launch: each operand panel is re-read 79 times).
+// This form: eight wavefronts (2 x 4) own a 256 x 256 tile,
 // 128 x 64 of it each (8 x 4 accumulator tiles of v_mfma_f32_16x16x32_f16: 128 VGPRs); a K step of 64 is 64 KB of
 // operands in LDS, double buffered (128 KB: one workgroup per CU); the NEXT step's operands arrive by
 // global_load_lds_dwordx4 -- no staging registers, no ds_write -- issued a quarter per phase while the current step's
@@ -630,183 +597,36 @@ k_nn_filter_f16_t256(const _Float16* __restrict__ A, const _Float16* __restrict_
   }
 }
 
-// ---- the same filter for a 128-dimension contraction, with the row panel resident ----------------------------
+// ---- the same filter for a 128-dimension contraction: the row panel in REGISTERS, the column tiles by LDS-DMA --
 // k_nn_filter_f16 at k = 128 spent its time outside the matrix cores: every 128 x 128 tile paid the global-load
 // latency of both operand panels (two barriers per 64-dimension step, nothing to overlap it with) and ~10 VALU
 // instructions per pair of outputs in the compare epilogue (profiles/r02b: 73 us for 25.6 GFLOP).  Here
-//   * a workgroup keeps ONE 128-row panel of the local descriptors in LDS (32 KB) and walks a strip of column
-//     tiles: the received panel of tile t + 1 is in flight (registers) while tile t is contracted, one LDS buffer,
-//     two barriers per TILE;
+//   * a workgroup keeps ONE 128-row panel of the local descriptors and walks a strip of column tiles.  A wavefront's
+//     share of the panel (64 rows x 128 halfs = 64 VGPRs per lane) is loaded once per strip and kept in MFMA operand
+//     layout; LDS holds only column tiles, two of them, filled by global_load_lds_dwordx4 (no staging registers, no
+//     ds_write): tile t + 1 is in flight while tile t is contracted, ONE barrier per tile, 16 ds_read_b128 per
+//     wavefront and tile;
+//   * an LDS-DMA instruction writes 1 KiB contiguously (four 256-byte rows), so the image cannot be padded; it is
+//     XOR-swizzled instead -- the 16-byte chunk c of row r sits at chunk c ^ (r & 15), applied on the SOURCE address of
+//     the DMA and on the ds_read address -- which makes every ds_read_b128 lane group (16 rows, one chunk each) hit 16
+//     different bank quads;
 //   * the inequality  acc > (A_i + B_j) - C_i D_j  is folded into the contraction: the accumulators START at -A_i
 //     (the MFMA's C operand, free), C_i D_j is a ninth contraction step (C_i and D_j are fp16-representable by
 //     construction, their product is exact), and what is left per output is  acc' > B_j;
 //   * that compare is done on the MAXIMUM of each lane's 16 outputs of a 32 x 32 block (v_max3), one compare and a
-//     ballot per block; only blocks with a hit look at their 16 outputs one by one;
+//     ballot per block; only blocks with a hit look at their 16 outputs one by one.  The block test runs on the BIT
+//     PATTERNS as signed integers (v_max3_i32; a float maximum of MFMA results costs a canonicalising instruction per
+//     operand): B_j >= +0, among non-negative floats the integer order is the float order, and every negative float
+//     is a negative integer.  A NaN output (NaN descriptor) can pass this test; the per-output float compare then
+//     rejects it;
 //   * hits go to a list in LDS and the workgroup takes its slots of the global candidate list with ONE atomic at the
 //     end of its strip: one returning atomic per hit on the single global counter serialises in L2 at ~3 ns each,
-//     which -- not the contraction -- was what both this kernel and k_nn_filter_f16 took 73 us for at ~25 000 hits.
-// Per 64 x 64 wavefront tile: 36 MFMAs (1152 matrix-pipe cycles) against ~150 other instructions.
-constexpr int NN_KP = 68;                 // LDS row pitch in dwords: 64 dwords (128 halfs) + 4
+//     which -- not the contraction -- was what k_nn_filter_f16 took 73 us for at ~25 000 hits.  (A candidate's
+//     position in the list is free: the consumers take row minima.)
 constexpr int NN_K128_HITS = 1024;        // candidates a workgroup collects in LDS before it takes global slots
-constexpr int NN_K128_LDS = 2 * NN_BM * NN_KP * 4 + NN_K128_HITS * 8 + 16;
-
-__global__ void __launch_bounds__(256, 2)
-k_nn_filter_f16_k128(const _Float16* __restrict__ A, const _Float16* __restrict__ B, const float2* __restrict__ rowc,
-                     const float2* __restrict__ colc, int gx, int gy, int tiles_per_strip,
-                     uint2* __restrict__ cand, unsigned* __restrict__ cand_count, unsigned cand_cap,
-                     unsigned* __restrict__ next_count) {
-  extern __shared__ __attribute__((aligned(16))) float nn_lds[];
-  // the NEXT launch's counter block (the launches alternate between two): zeroed here, so that no memset launch
-  // stands in front of the next query's filter
-  if (blockIdx.x == 0 && threadIdx.x < 16 && next_count) next_count[threadIdx.x] = 0u;
-  float* sA = nn_lds;                         // [128][NN_KP]
-  float* sB = nn_lds + NN_BM * NN_KP;         // [128][NN_KP]
-  uint2* s_hits = reinterpret_cast<uint2*>(nn_lds + 2 * NN_BM * NN_KP);   // [NN_K128_HITS]
-  unsigned* s_nhits = reinterpret_cast<unsigned*>(s_hits + NN_K128_HITS);  // [0] count, [1] global base
-  const int tid = threadIdx.x;
-  if (tid == 0) s_nhits[0] = 0;               // (visible after the first barrier of the tile loop)
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int l31 = lane & 31, h = lane >> 5;
-  const int strips = (gx + tiles_per_strip - 1) / tiles_per_strip;
-  const int tile_y = blockIdx.x / strips, strip = blockIdx.x - tile_y * strips;   // (gy row panels) x strips
-  const int t_first = strip * tiles_per_strip;
-  const int t_last = min(gx, t_first + tiles_per_strip);
-  const int row0 = tile_y * NN_BM;
-  const float4* Ag = reinterpret_cast<const float4*>(A) + (size_t)row0 * 16;   // 16 float4 per 128-half row
-
-  // the column panel of the first tile is requested first, then the row panel (written to LDS straight away)
-  // (named registers, not an array: hipcc demotes a float4[8] carried around the tile loop to scratch)
-  float4 rb0, rb1, rb2, rb3, rb4, rb5, rb6, rb7;
-#define SF_K128_LOAD(Bg)                                                                              \
-  rb0 = (Bg)[tid]; rb1 = (Bg)[tid + 256]; rb2 = (Bg)[tid + 512]; rb3 = (Bg)[tid + 768];               \
-  rb4 = (Bg)[tid + 1024]; rb5 = (Bg)[tid + 1280]; rb6 = (Bg)[tid + 1536]; rb7 = (Bg)[tid + 1792]
-#define SF_K128_STORE(u, v)                                                                           \
-  *reinterpret_cast<float4*>(&sB[((tid + 256 * (u)) >> 4) * NN_KP + ((tid + 256 * (u)) & 15) * 4]) = (v)
-  {
-    const float4* Bg = reinterpret_cast<const float4*>(B) + (size_t)t_first * NN_BN * 16;
-    SF_K128_LOAD(Bg);
-  }
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int ch = tid + 256 * u;
-    *reinterpret_cast<float4*>(&sA[(ch >> 4) * NN_KP + (ch & 15) * 4]) = Ag[ch];
-  }
-  // accumulator start values -A_i and the row half of the ninth step, for this lane's rows
-  f32x16 cinit[2];
-  half8 a_ext[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cinit[i][r] = -rowc[row0 + 64 * wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h].x;
-    const float ci = rowc[row0 + 64 * wr + 32 * i + l31].y;
-    const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    a_ext[i] = z;
-    if (h == 0) a_ext[i][0] = (_Float16)ci;      // k = 0 of the extra step lives in lanes 0..31
-  }
-
-  for (int t = t_first; t < t_last; ++t) {
-    const int col0 = t * NN_BN;
-    __syncthreads();                              // the previous tile's reads of sB are complete
-    SF_K128_STORE(0, rb0); SF_K128_STORE(1, rb1); SF_K128_STORE(2, rb2); SF_K128_STORE(3, rb3);
-    SF_K128_STORE(4, rb4); SF_K128_STORE(5, rb5); SF_K128_STORE(6, rb6); SF_K128_STORE(7, rb7);
-    __syncthreads();
-    if (t + 1 < t_last) {
-      const float4* Bg = reinterpret_cast<const float4*>(B) + (size_t)(t + 1) * NN_BN * 16;
-      SF_K128_LOAD(Bg);
-    }
-    float bj[2];
-    half8 b_ext[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float2 cj = colc[col0 + 64 * wc + 32 * j + l31];
-      bj[j] = cj.x;
-      const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-      b_ext[j] = z;
-      if (h == 0) b_ext[j][0] = (_Float16)cj.y;
-    }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {   // 16 halfs of K per MFMA: lane holds k = 16 q + 8 h + 0..7
-      half8 a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        a[i] = *reinterpret_cast<const half8*>(&sA[(64 * wr + 32 * i + l31) * NN_KP + 8 * q + 4 * h]);
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        b[j] = *reinterpret_cast<const half8*>(&sB[(64 * wc + 32 * j + l31) * NN_KP + 8 * q + 4 * h]);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], q == 0 ? cinit[i] : acc[i][j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_ext[i], b_ext[j], acc[i][j], 0, 0, 0);
-
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const f32x16& v = acc[i][j];
-        // the block test runs on the BIT PATTERNS as signed integers (v_max3_i32; a float maximum of MFMA results
-        // costs a canonicalising instruction per operand): B_j >= +0, among non-negative floats the integer order is
-        // the float order, and every negative float is a negative integer.  A NaN output (NaN descriptor) can pass
-        // this test; the per-output float compare below then rejects it.
-        int m = max(max(__float_as_int(v[0]), __float_as_int(v[1])), __float_as_int(v[2]));
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) m = max(max(m, __float_as_int(v[r])), __float_as_int(v[r + 1]));
-        m = max(m, __float_as_int(v[15]));
-        if (__ballot(m > __float_as_int(bj[j])) != 0ull) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            if (v[r] > bj[j]) {
-              const uint2 e = make_uint2((unsigned)(row0 + 64 * wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h),
-                                         (unsigned)(col0 + 64 * wc + 32 * j + l31));
-              const unsigned lp = atomicAdd(&s_nhits[0], 1u);
-              if (lp < (unsigned)NN_K128_HITS) {
-                s_hits[lp] = e;
-              } else {                        // dense tile: past the LDS list every hit takes its own slot
-                const unsigned pos = atomicAdd(cand_count, 1u);
-                if (pos < cand_cap) cand[pos] = e;
-              }
-            }
-          }
-        }
-      }
-    }
-  }
-#undef SF_K128_LOAD
-#undef SF_K128_STORE
-  __syncthreads();
-  const unsigned nh = min(s_nhits[0], (unsigned)NN_K128_HITS);
-  if (tid == 0 && nh) s_nhits[1] = atomicAdd(cand_count, nh);
-  __syncthreads();
-  if (nh) {
-    const unsigned base = s_nhits[1];
-    for (unsigned e = tid; e < nh; e += 256)
-      if (base + e < cand_cap) cand[base + e] = s_hits[e];
-  }
-}
-
-// ---- round 3: the row panel in REGISTERS, the column tiles by LDS-DMA -----------------------------------------
-// k_nn_filter_f16_k128 above reads both operands of every MFMA from LDS (32 ds_read_b128 per wavefront and tile for
-// 36 MFMAs), stages the column tile through 32 registers per lane and fills its single buffer between two barriers.
-// Here a wavefront's share of the row panel (64 rows x 128 halfs = 64 VGPRs per lane) is loaded once per strip
-// straight from global memory in MFMA operand layout and kept; LDS holds only column tiles, two of them, filled by
-// global_load_lds_dwordx4 (no staging registers, no ds_write): tile t + 1 is in flight while tile t is contracted,
-// ONE barrier per tile, 16 ds_read_b128 per wavefront and tile.  An LDS-DMA instruction writes 1 KiB contiguously
-// (four 256-byte rows), so the image cannot be padded; it is XOR-swizzled instead -- the 16-byte chunk c of row r
-// sits at chunk c ^ (r & 15), applied on the SOURCE address of the DMA and on the ds_read address -- which makes every
-// ds_read_b128 lane group (16 rows, one chunk each) hit 16 different bank quads.
-// Same arithmetic, same order of the contraction steps, same candidate set as the kernel above (a candidate's
-// position in the list is free: the consumers take row minima).
 constexpr int NN_K128R_ROWS = NN_BN * 64;            // dwords of the rows of one column tile (128 rows x 256 B)
 constexpr int NN_K128R_TILE = NN_K128R_ROWS + 256;   // + the tile's 128 column coefficients (one more 1 KiB piece)
 
-template <int ABL>     // ABL != 0: timing-only ablations (tools/nn_filter_time.py), never launched by the product path
 __global__ void __launch_bounds__(256, 2)
 k_nn_filter_f16_k128r(const _Float16* __restrict__ A, const _Float16* __restrict__ B, const float2* __restrict__ rowc,
                       const float2* __restrict__ colc, int gx, int gy, int tiles_per_strip,
@@ -857,10 +677,8 @@ k_nn_filter_f16_k128r(const _Float16* __restrict__ A, const _Float16* __restrict
   // prologue: the first column tile into buffer 0 and the ROW panel, with its coefficients, into buffer 1 -- by the
   // same coalesced 1 KiB pieces; fragment-shaped loads straight from global memory (32 rows x 32 B per instruction)
   // and 32 scalar coefficient loads per lane made the prologue a third of the kernel at 10 000 x 10 000
-  if (!(ABL & 16)) {
-    dma_block(B + (size_t)t_first * NN_BN * 128, colc + (size_t)t_first * NN_BN, sB0);
-    dma_block(A + (size_t)row0 * 128, rowc + row0, sB1);
-  }
+  dma_block(B + (size_t)t_first * NN_BN * 128, colc + (size_t)t_first * NN_BN, sB0);
+  dma_block(A + (size_t)row0 * 128, rowc + row0, sB1);
   __syncthreads();                                    // (vmcnt(0) in front of it: both blocks have landed)
   // this wavefront's rows of the panel, in operand layout: lane (l31, h) holds halfs 16 q + 8 h .. + 7 of row
   // 64 wr + 32 i + l31 for q = 0 .. 7
@@ -898,8 +716,7 @@ k_nn_filter_f16_k128r(const _Float16* __restrict__ A, const _Float16* __restrict
       f32x16 acc[2];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {   // 16 halfs of K per MFMA: lane holds k = 16 q + 8 h + 0..7
-        const half8 b = (ABL & 2) ? a[1][q ^ 1]
-                                  : *reinterpret_cast<const half8*>(&cur[rd_row + 32 * 64 * j + (((2 * q + h) ^ rd_sw) << 2)]);
+        const half8 b = *reinterpret_cast<const half8*>(&cur[rd_row + 32 * 64 * j + (((2 * q + h) ^ rd_sw) << 2)]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
           acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][q], b, q == 0 ? cinit[i] : acc[i], 0, 0, 0);
@@ -919,12 +736,11 @@ k_nn_filter_f16_k128r(const _Float16* __restrict__ A, const _Float16* __restrict
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const f32x16& v = acc[i];
-        // (block test on the bit patterns as signed integers: see k_nn_filter_f16_k128)
+        // (block test on the bit patterns as signed integers: see the header)
         int m = max(max(__float_as_int(v[0]), __float_as_int(v[1])), __float_as_int(v[2]));
 #pragma unroll
         for (int r = 3; r < 15; r += 2) m = max(max(m, __float_as_int(v[r])), __float_as_int(v[r + 1]));
         m = max(m, __float_as_int(v[15]));
-        if (ABL & 1) { asm volatile("" :: "v"(m)); continue; }
         if (__ballot(m > __float_as_int(bj)) != 0ull) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -944,10 +760,8 @@ k_nn_filter_f16_k128r(const _Float16* __restrict__ A, const _Float16* __restrict
       }
     }
   };
-  auto dma_tile = [&](int t, float* buf) {
-    if (!(ABL & 4)) dma_block(B + (size_t)t * NN_BN * 128, colc + (size_t)t * NN_BN, buf);
-  };
-  for (int t = t_first; t < ((ABL & 8) ? t_first : t_last); t += 2) {
+  auto dma_tile = [&](int t, float* buf) { dma_block(B + (size_t)t * NN_BN * 128, colc + (size_t)t * NN_BN, buf); };
+  for (int t = t_first; t < t_last; t += 2) {
     if (t + 1 < t_last) dma_tile(t + 1, sB1);       // (its last reads ended before the previous barrier)
     contract(sB0, t);
     __syncthreads();            // vmcnt(0) + barrier: the next tile has landed, this tile's reads are complete
@@ -983,7 +797,7 @@ k_nn_refine(const uint2* __restrict__ cand, const unsigned* __restrict__ count, 
 }
 
 // ---- per-row minima of the candidate list, on the device (the row-sharded NN stage of SURVEY.md section 8(e): no
-// candidate list travels to the host).  Same rule as the host loop of nn_run_filter: smallest exact float64 distance,
+// candidate list travels to the host).  Same rule as nn_host_row_minima: smallest exact float64 distance,
 // ties to the lowest column, ignored pairs skipped, rows without a candidate = (+inf, 0).  Non-negative doubles order
 // like their bit patterns, so the minimum is an atomicMin on 64-bit integers; the column is settled in a second pass
 // over the candidates that hold their row's minimum.
@@ -1197,6 +1011,40 @@ k_walk_emit(const int* __restrict__ sorted_rows, const int* __restrict__ nu_p, i
 
 }  // namespace
 
+// float row pitch of the database: the dimension rounded up to the K step of k_nn_argmin
+static int nn_row_pitch(int dim) { return (dim + NN_BK - 1) / NN_BK * NN_BK; }
+
+// Geometry of one query, taken from the handle once per entry point.
+struct NnShape {
+  int n_l, n_r, dim;
+  int ld;                  // float row pitch
+  int ld16;                // full contraction length of the fp16 filter: the dimension rounded up to 64 halfs
+  int n_l_pad, n_r_pad;    // rows / columns rounded up to the 128 x 128 tile
+  int n_strips;            // 64-column strips of the exact path's partial minima
+  explicit NnShape(const sf_context* c)
+      : n_l(c->nn_local.n), n_r(c->nn_recv.n), dim(c->nn_dim), ld(nn_row_pitch(dim)), ld16((dim + 63) / 64 * 64),
+        n_l_pad((n_l + NN_BM - 1) / NN_BM * NN_BM), n_r_pad((n_r + NN_BN - 1) / NN_BN * NN_BN), n_strips(n_r_pad / 64) {}
+};
+
+// compute units of the device (grids sized to the chip), queried on first use
+static int sf_cu_count(sf_context* c) {
+  if (c->cu_count <= 0) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || v <= 0) v = 256;
+    c->cu_count = v;
+  }
+  return c->cu_count;
+}
+
+// Workgroups of a k_nn_refine launch over n candidates: one per four candidates.  Throttled -- beside a verification
+// launch, where the re-evaluation has several times its own run time of slack -- one workgroup per CU at the most
+// walks the list (grid-stride), which leaves the HBM and the dispatcher to the verification kernel's first third
+// (k_verify_fused 0.60 -> 0.58 ms, the re-evaluation 0.09 -> 0.16 ms in its shadow).
+static unsigned nn_refine_grid(sf_context* c, unsigned n, bool throttled) {
+  const unsigned wgs = (n + 3) / 4;
+  return throttled ? std::min(wgs, (unsigned)sf_cu_count(c)) : wgs;
+}
+
 static int nn_reserve(sf_context* c, NNDb& db, int n_total, int ld) {
   const int cap = std::max(128, (n_total + 127) & ~127);
   if (ld != db.ld) {
@@ -1233,7 +1081,7 @@ int sf_nn_reserve_rows(sf_context* c, NNDb& db, int n, int dim) {
   if (n == 0) return SF_OK;
   (void)sf_lanes_touch(c, false);
   SF_HIP(c, hipSetDevice(c->device));
-  return nn_reserve(c, db, db.n + n, (dim + NN_BK - 1) / NN_BK * NN_BK);
+  return nn_reserve(c, db, db.n + n, nn_row_pitch(dim));
 }
 
 // staging of the per-tick host append: pinned host + device bounce buffers owned by the handle (grow-only).  The
@@ -1258,7 +1106,7 @@ static int nn_stage_reserve(sf_context* c, size_t bytes) {
   return sf_buf_reserve(c, c->nn_stage_dev, std::max<size_t>(bytes, (size_t)1 << 16));
 }
 
-// src_kind 0: host float64 rows ; 1: device float32 rows
+// src_kind 0: host float64 rows ; 1: device float32 rows ; 2: device float16 rows
 int sf_nn_append(sf_context* c, NNDb& db, const void* src, int n, int dim, int src_kind) {
   (void)sf_lanes_touch(c, false);     // rows are written through the handle's stream: the second step lane waits for them
   if (n < 0 || dim <= 0) return sf_fail(c, SF_EINVAL, "bad descriptor block %d x %d", n, dim);
@@ -1268,26 +1116,27 @@ int sf_nn_append(sf_context* c, NNDb& db, const void* src, int n, int dim, int s
   if (dim != c->nn_dim)
     return sf_fail(c, SF_EINVAL, "descriptor dimension %d differs from the database's %d (data_handler.py:300-301 reshape)", dim, c->nn_dim);
   SF_HIP(c, hipSetDevice(c->device));
-  const int ld = (dim + NN_BK - 1) / NN_BK * NN_BK;
+  const int ld = nn_row_pitch(dim);
   int rc = nn_reserve(c, db, db.n + n, ld);
   if (rc != SF_OK) return rc;
   float* dst = (float*)db.rows.p + (size_t)db.n * ld;
   float* nrm = (float*)db.norms.p + db.n;
+  const dim3 grid((n + 3) / 4);   // one wavefront per row
   if (src_kind == 0) {
     const size_t bytes = (size_t)n * dim * 8;
     if ((rc = nn_stage_reserve(c, bytes)) != SF_OK) return rc;
     memcpy(c->nn_stage_pinned, src, bytes);
     SF_HIP(c, hipMemcpyAsync(c->nn_stage_dev.p, c->nn_stage_pinned, bytes, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_nn_cast_rows, dim3((n + 3) / 4), dim3(256), 0, c->stream, (const double*)c->nn_stage_dev.p, dst,
-                       nrm, n, dim, ld);
+    hipLaunchKernelGGL(k_nn_ingest_rows<double>, grid, dim3(256), 0, c->stream, (const double*)c->nn_stage_dev.p, dst, nrm, n,
+                       dim, ld);
     SF_HIP(c, hipGetLastError());
     SF_HIP(c, hipEventRecord(c->nn_stage_done, c->stream));
     c->nn_stage_busy = true;
   } else if (src_kind == 2) {
-    hipLaunchKernelGGL(k_nn_copy_rows_f16, dim3((n + 3) / 4), dim3(256), 0, c->stream, (const _Float16*)src, dst, nrm, n, dim, ld);
+    hipLaunchKernelGGL(k_nn_ingest_rows<_Float16>, grid, dim3(256), 0, c->stream, (const _Float16*)src, dst, nrm, n, dim, ld);
     SF_HIP(c, hipGetLastError());
   } else {
-    hipLaunchKernelGGL(k_nn_copy_rows, dim3((n + 3) / 4), dim3(256), 0, c->stream, (const float*)src, dst, nrm, n, dim, ld);
+    hipLaunchKernelGGL(k_nn_ingest_rows<float>, grid, dim3(256), 0, c->stream, (const float*)src, dst, nrm, n, dim, ld);
     SF_HIP(c, hipGetLastError());
   }
   db.n += n;
@@ -1333,8 +1182,6 @@ static int nn_prepare_f16(sf_context* c, NNDb& db, int ld, int ld16, int kprefix
   return SF_OK;
 }
 
-// Returns SF_OK with *done = 1 when the filter path produced the row minima; *done = 0 means the
-// candidate buffer overflowed (threshold too loose for a sparse filter) -> caller runs the exact path.
 // SF_NN_TRACE=1: host-side stage times of one query on stderr (diagnostic)
 struct NnTrace {
   bool on;
@@ -1362,6 +1209,31 @@ static int nn_pinned_reserve(sf_context* c, size_t need) {
   return SF_OK;
 }
 
+// Stage 1 contracts only a PREFIX of the descriptor: the squared distance over the first k
+// dimensions is a lower bound of the full squared distance, so "prefix distance (within the fp16
+// error band) under the threshold" is a necessary condition.  PCA-whitened NetVLAD spreads its
+// energy evenly (the reference itself ranks on a 128-dim prefix, data_handler.py:157-158), so an
+// eighth of the dimensions already rejects everything but real neighbours.
+// The prefix ladder: 128 and 512 dimensions when they are at most a quarter of the descriptor, then the
+// full length.  The handle remembers the level that last produced a sparse candidate set (nn_level).
+struct NnLadder {
+  int levels[3], n_levels = 0;
+  int current;              // the handle's level, clamped to this ladder
+  size_t n_l;
+  NnLadder(const sf_context* c, const NnShape& sh) : n_l((size_t)sh.n_l) {
+    if (128 * 4 <= sh.dim) levels[n_levels++] = 128;
+    if (512 * 4 <= sh.dim) levels[n_levels++] = 512;
+    levels[n_levels++] = sh.ld16;
+    current = std::min(std::max(c->nn_level, 0), n_levels - 1);
+  }
+  int full() const { return n_levels - 1; }
+  // a dense prefix result would make the exact refinement the expensive part: insist on a sparse
+  // candidate set from a prefix level, accept anything that fits the buffer (`cap`) from the full-length level
+  unsigned limit(int level, unsigned cap) const { return level < full() ? (unsigned)(8 * n_l + 4096) : cap; }
+  // what a sparse list typically holds: the grids and the first copies are sized for it
+  unsigned typical(int level, unsigned cap) const { return std::min<unsigned>(limit(level, cap), (unsigned)(2 * n_l + 1024)); }
+};
+
 struct NnFilterBufs {
   unsigned cap = 0;
   float2* rowc = nullptr;
@@ -1371,156 +1243,227 @@ struct NnFilterBufs {
   double* cdist = nullptr;
 };
 
-static int nn_filter_reserve(sf_context* c, NnFilterBufs& fb) {
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n;
-  const int n_l_pad = (n_l + NN_BM - 1) / NN_BM * NN_BM, n_r_pad = (n_r + NN_BN - 1) / NN_BN * NN_BN;
+static int nn_filter_reserve(sf_context* c, const NnShape& sh, NnFilterBufs& fb) {
   int rc;
-  const unsigned cap = (unsigned)std::max<size_t>((size_t)1 << 20, (size_t)64 * n_l);
+  const unsigned cap = (unsigned)std::max<size_t>((size_t)1 << 20, (size_t)64 * sh.n_l);
   {
     const void* before = c->w->nn_cand.p;
     if ((rc = sf_buf_reserve(c, c->w->nn_cand, (size_t)cap * 16 + 128)) != SF_OK) return rc;
     if (c->w->nn_cand.p != before) c->w->nn_count_primed = false;      // (a fresh buffer: nobody zeroed its counter blocks)
   }
-  if ((rc = sf_buf_reserve(c, c->nn_rowmin, (size_t)(n_l_pad + n_r_pad) * 8)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->nn_rowmin, (size_t)(sh.n_l_pad + sh.n_r_pad) * 8)) != SF_OK) return rc;
   fb.rowc = (float2*)c->nn_rowmin.p;
-  fb.colc = fb.rowc + n_l_pad;
+  fb.colc = fb.rowc + sh.n_l_pad;
   fb.count = (unsigned*)c->w->nn_cand.p;
   fb.cand = (uint2*)((char*)c->w->nn_cand.p + 128);
   fb.cdist = (double*)((char*)c->w->nn_cand.p + 128 + (size_t)cap * 8);
   fb.cap = cap;
-
   return SF_OK;
 }
 
 // One launch of the stage-1 filter at prefix length `kdims` (ladder level `level`): fp16 copies, coefficients, kernel.
 // Leaves the candidate list in fb.cand and its length in *fb.count (device).
-static int nn_filter_launch(sf_context* c, NnFilterBufs& fb, int level, int kdims, NnTrace* trp) {
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n, dim = c->nn_dim;
-  const int ld = (dim + NN_BK - 1) / NN_BK * NN_BK;
-  const int n_l_pad = (n_l + NN_BM - 1) / NN_BM * NN_BM, n_r_pad = (n_r + NN_BN - 1) / NN_BN * NN_BN;
-  const unsigned cap = fb.cap;
+static int nn_filter_launch(sf_context* c, const NnShape& sh, NnFilterBufs& fb, int level, int kdims, NnTrace& tr) {
+  const int n_l = sh.n_l, n_r = sh.n_r, n_l_pad = sh.n_l_pad, n_r_pad = sh.n_r_pad;
   float2* const rowc = fb.rowc;
   float2* const colc = fb.colc;
-  uint2* const cand = fb.cand;
-  unsigned* count;
-  NnTrace& tr = *trp;
   const double thr = c->params.netvlad_distance;
   float thr2 = (float)(thr * thr);
   thr2 = nextafterf(thr2, INFINITY);
   int rc;
-    // the fp16 copy of a prefix level is stored COMPACT (pitch = prefix length): a 128-row operand tile is
-    // then one contiguous 32 / 128 KB block instead of 128 pieces 2 * dim bytes apart
-    const int pitch16 = kdims;
-    if ((rc = nn_prepare_f16(c, c->nn_local, ld, pitch16, kdims)) != SF_OK) return rc;
-    if ((rc = nn_prepare_f16(c, c->nn_recv, ld, pitch16, kdims)) != SF_OK) return rc;
-    if (tr.on) { (void)hipStreamSynchronize(c->stream); tr.mark("prepare f16", kdims); }
-    // |dot16 - dot32| <= (2^-10 (1 + 2^-11) + k 2^-24) * ||a|| ||b||  (operand rounding + fp32 accumulation)
-    const float eps_rel = (float)(ldexp(1.0, -10) * 1.001 + (double)kdims * ldexp(1.0, -24));
-    const float scale = c->nn_local.h_scale * c->nn_recv.h_scale;   // product of two powers of two: exact
-    count = (unsigned*)((char*)c->w->nn_cand.p + 64 * c->w->nn_count_idx);
-    unsigned* const count_next = (unsigned*)((char*)c->w->nn_cand.p + 64 * (c->w->nn_count_idx ^ 1));
-    if (!c->w->nn_count_primed) SF_HIP(c, hipMemsetAsync(count, 0, 64, c->stream));
-    c->w->nn_count_idx ^= 1;
-    c->w->nn_count_primed = false;
-    // the per-row / per-column coefficients depend only on the norms, the masks, the threshold and the
-    // prefix level: rebuilt when one of them changed, not per query
-    const bool coef_ok = c->nn_coef_level == level && c->nn_coef_nl == n_l && c->nn_coef_nr == n_r &&
-                         c->nn_coef_thr == thr && c->nn_coef_ptr == (const void*)rowc && c->nn_coef_scale == scale;
+  // the fp16 copy of a prefix level is stored COMPACT (pitch = prefix length): a 128-row operand tile is
+  // then one contiguous 32 / 128 KB block instead of 128 pieces 2 * dim bytes apart
+  const int pitch16 = kdims;
+  if ((rc = nn_prepare_f16(c, c->nn_local, sh.ld, pitch16, kdims)) != SF_OK) return rc;
+  if ((rc = nn_prepare_f16(c, c->nn_recv, sh.ld, pitch16, kdims)) != SF_OK) return rc;
+  if (tr.on) { (void)hipStreamSynchronize(c->stream); tr.mark("prepare f16", kdims); }
+  // |dot16 - dot32| <= (2^-10 (1 + 2^-11) + k 2^-24) * ||a|| ||b||  (operand rounding + fp32 accumulation)
+  const float eps_rel = (float)(ldexp(1.0, -10) * 1.001 + (double)kdims * ldexp(1.0, -24));
+  const float scale = c->nn_local.h_scale * c->nn_recv.h_scale;   // product of two powers of two: exact
+  unsigned* const count = (unsigned*)((char*)c->w->nn_cand.p + 64 * c->w->nn_count_idx);
+  unsigned* const count_next = (unsigned*)((char*)c->w->nn_cand.p + 64 * (c->w->nn_count_idx ^ 1));
+  if (!c->w->nn_count_primed) SF_HIP(c, hipMemsetAsync(count, 0, 64, c->stream));
+  c->w->nn_count_idx ^= 1;
+  c->w->nn_count_primed = false;
+  // the per-row / per-column coefficients depend only on the norms, the masks, the threshold and the
+  // prefix level: rebuilt when one of them changed, not per query
+  const bool coef_ok = c->nn_coef_level == level && c->nn_coef_nl == n_l && c->nn_coef_nr == n_r &&
+                       c->nn_coef_thr == thr && c->nn_coef_ptr == (const void*)rowc && c->nn_coef_scale == scale;
+  if (!coef_ok) {
     const float delta = 2e-6f + (float)((double)(kdims + 8) * ldexp(1.0, -24));
-    if (!coef_ok) c->prep_count += 1;
-    if (!coef_ok)
+    c->prep_count += 1;
     hipLaunchKernelGGL(k_nn_filter_row_coef, dim3((n_l_pad + 255) / 256), dim3(256), 0, c->stream, rowc,
                        (const float*)c->nn_local.norms_k.p, (const uint8_t*)c->d_mask_local.p, n_l, n_l_pad,
                        0.5f * scale, thr2, eps_rel * c->nn_local.h_scale * 64.f, delta);
-    if (!coef_ok) {
-      hipLaunchKernelGGL(k_nn_filter_col_coef, dim3((n_r_pad + 255) / 256), dim3(256), 0, c->stream, colc,
-                         (const float*)c->nn_recv.norms_k.p, (const uint8_t*)c->d_mask_other.p, n_r, n_r_pad,
-                         0.5f * scale, c->nn_recv.h_scale / 64.f, delta);
-      c->nn_coef_level = level; c->nn_coef_nl = n_l; c->nn_coef_nr = n_r; c->nn_coef_thr = thr;
-      c->nn_coef_ptr = (const void*)rowc;
-      c->nn_coef_scale = scale;
+    hipLaunchKernelGGL(k_nn_filter_col_coef, dim3((n_r_pad + 255) / 256), dim3(256), 0, c->stream, colc,
+                       (const float*)c->nn_recv.norms_k.p, (const uint8_t*)c->d_mask_other.p, n_r, n_r_pad,
+                       0.5f * scale, c->nn_recv.h_scale / 64.f, delta);
+    c->nn_coef_level = level; c->nn_coef_nl = n_l; c->nn_coef_nr = n_r; c->nn_coef_thr = thr;
+    c->nn_coef_ptr = (const void*)rowc;
+    c->nn_coef_scale = scale;
+  }
+  const _Float16* const A16 = (const _Float16*)c->nn_local.rows_h.p;
+  const _Float16* const B16 = (const _Float16*)c->nn_recv.rows_h.p;
+  const int gx = n_r_pad / NN_BN, gy = n_l_pad / NN_BM;
+  sf_prof_begin(c, SF_K_NN_FILTER);
+  if (kdims == 128) {
+    // resident row panel, strips of column tiles: about two workgroups per CU in one wave of the grid
+    const int strips = std::max(1, std::min(gx, (2 * sf_cu_count(c)) / std::max(1, gy)));
+    const int tps = (gx + strips - 1) / strips;
+    // (static LDS: two tile buffers + the hit list, 74 KB)
+    hipLaunchKernelGGL(k_nn_filter_f16_k128r, dim3(gy * ((gx + tps - 1) / tps)), dim3(256), 0, c->stream, A16, B16, rowc,
+                       colc, gx, gy, tps, fb.cand, count, fb.cap, count_next);
+    c->w->nn_count_primed = true;                 // (this launch zeroes the other block for the next one)
+  } else if (kdims >= 256) {
+    if (!c->nn_t256_attr) {
+      SF_HIP(c, hipFuncSetAttribute((const void*)k_nn_filter_f16_t256, hipFuncAttributeMaxDynamicSharedMemorySize, NN256_LDS));
+      c->nn_t256_attr = true;
     }
-    sf_prof_begin(c, SF_K_NN_FILTER);
-    if (kdims == 128 && getenv("SF_NN_K128_OFF") == nullptr) {
-      // resident row panel, strips of column tiles: about two workgroups per CU in one wave of the grid
-      const int gx = n_r_pad / NN_BN, gy = n_l_pad / NN_BM;
-      if (c->cu_count <= 0) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || v <= 0) v = 256;
-        c->cu_count = v;
-      }
-      const int strips = std::max(1, std::min(gx, (2 * c->cu_count) / std::max(1, gy)));
-      const int tps = (gx + strips - 1) / strips;
-      static const bool k128_lds_panel = getenv("SF_NN_K128_LDS_PANEL") != nullptr;   // (round-2 form, for A/B runs)
-#ifdef SF_NN_ABLATION
-      // timing-only forms (make NN_ABLATION=1; tools/nn_filter_time.py): bit 0 no hit scan, bit 1 no LDS operand reads,
-      // bit 2 no DMA of the next tile, bit 3 no tile loop, bit 4 no prologue DMA -- never compiled into the product build
-      static const int k128_abl = getenv("SF_NN_K128_ABL") ? atoi(getenv("SF_NN_K128_ABL")) : 0;
-      auto kern = k128_abl == 1 ? k_nn_filter_f16_k128r<1> : k128_abl == 3 ? k_nn_filter_f16_k128r<3>
-                  : k128_abl == 5 ? k_nn_filter_f16_k128r<5> : k128_abl == 7 ? k_nn_filter_f16_k128r<7>
-                  : k128_abl == 8 ? k_nn_filter_f16_k128r<8> : k128_abl == 24 ? k_nn_filter_f16_k128r<24>
-                  : k_nn_filter_f16_k128r<0>;
-#else
-      auto kern = k_nn_filter_f16_k128r<0>;
-#endif
-      if (!c->nn_k128_attr) {
-        SF_HIP(c, hipFuncSetAttribute((const void*)k_nn_filter_f16_k128, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      NN_K128_LDS));
-        c->nn_k128_attr = true;
-      }
-      if (k128_lds_panel)
-        hipLaunchKernelGGL(k_nn_filter_f16_k128, dim3(gy * ((gx + tps - 1) / tps)), dim3(256), NN_K128_LDS, c->stream,
-                           (const _Float16*)c->nn_local.rows_h.p, (const _Float16*)c->nn_recv.rows_h.p, rowc, colc, gx,
-                           gy, tps, cand, count, cap, count_next);
-      else      // (static LDS: two tile buffers + the hit list, 74 KB)
-        hipLaunchKernelGGL(kern, dim3(gy * ((gx + tps - 1) / tps)), dim3(256), 0, c->stream,
-                           (const _Float16*)c->nn_local.rows_h.p, (const _Float16*)c->nn_recv.rows_h.p, rowc, colc, gx,
-                           gy, tps, cand, count, cap, count_next);
-      c->w->nn_count_primed = true;                 // (this launch zeroes the other block for the next one)
-    } else if (nn_t256_on() && kdims % 64 == 0 && kdims >= 256) {
-      static bool attr256 = false;      // (one device per process in every deployment of this library; set once)
-      if (!attr256) {
-        SF_HIP(c, hipFuncSetAttribute((const void*)k_nn_filter_f16_t256, hipFuncAttributeMaxDynamicSharedMemorySize, NN256_LDS));
-        attr256 = true;
-      }
-      const int gx256 = (n_r_pad + 255) / 256, gy256 = (n_l_pad + 255) / 256;
-      hipLaunchKernelGGL(k_nn_filter_f16_t256, dim3(gx256 * gy256), dim3(512), NN256_LDS, c->stream,
-                         (const _Float16*)c->nn_local.rows_h.p, (const _Float16*)c->nn_recv.rows_h.p, rowc, colc,
-                         pitch16, kdims, gx256, gy256, n_l_pad, n_r_pad, cand, count, cap);
-    } else {
-      hipLaunchKernelGGL(k_nn_filter_f16, dim3((n_r_pad / NN_BN) * (n_l_pad / NN_BM)), dim3(256), 0, c->stream,
-                         (const _Float16*)c->nn_local.rows_h.p, (const _Float16*)c->nn_recv.rows_h.p, rowc, colc,
-                         pitch16, kdims, n_r_pad / NN_BN, n_l_pad / NN_BM, cand, count, cap);
-    }
-    sf_prof_end(c, SF_K_NN_FILTER);
-    SF_HIP(c, hipGetLastError());
-    fb.count = count;
+    const int gx256 = (n_r_pad + 255) / 256, gy256 = (n_l_pad + 255) / 256;
+    hipLaunchKernelGGL(k_nn_filter_f16_t256, dim3(gx256 * gy256), dim3(512), NN256_LDS, c->stream, A16, B16, rowc, colc,
+                       pitch16, kdims, gx256, gy256, n_l_pad, n_r_pad, fb.cand, count, fb.cap);
+  } else {   // 64 or 192
+    hipLaunchKernelGGL(k_nn_filter_f16, dim3(gx * gy), dim3(256), 0, c->stream, A16, B16, rowc, colc, pitch16, kdims, gx,
+                       gy, fb.cand, count, fb.cap);
+  }
+  sf_prof_end(c, SF_K_NN_FILTER);
+  SF_HIP(c, hipGetLastError());
+  fb.count = count;
   return SF_OK;
 }
 
-static int nn_run_filter(sf_context* c, int* done) {
+// The candidate list of one query on the host: pinned staging (pageable D2H copies are staged and slow).
+struct NnHostCand {
+  unsigned n = 0;
+  uint2* cand = nullptr;
+  double* dist = nullptr;
+  int reserve(sf_context* c, unsigned entries) {
+    const int rc = nn_pinned_reserve(c, (size_t)entries * 16 + 64);
+    if (rc != SF_OK) return rc;
+    cand = (uint2*)((char*)c->nn_pinned + 64);
+    dist = (double*)((char*)c->nn_pinned + 64 + (size_t)entries * 8);
+    return SF_OK;
+  }
+};
+
+// Exact distances of a PREFIX level's candidates, and the list on the host.  No host round trip between the filter
+// and the refinement: the refine grid is sized for the typical list (`spec` = 2N + 1024 entries) and reads the count
+// on the device; count, candidates and distances come back behind ONE synchronisation, the rare rest of a list of up
+// to `limit` entries once its size is known.  *ok: the list is within `limit`.
+static int nn_refine_prefix(sf_context* c, const NnShape& sh, const NnFilterBufs& fb, unsigned limit, unsigned spec,
+                            NnTrace& tr, NnHostCand& hc, bool* ok) {
+  const float* const A = (const float*)c->nn_local.rows.p;
+  const float* const B = (const float*)c->nn_recv.rows.p;
+  int rc;
+  if ((rc = hc.reserve(c, limit)) != SF_OK) return rc;
+  // With a speculative verification requested (sf_find_matches_and_verify_device) the handle's stream goes
+  // from the filter straight into the verification of every candidate -- which needs the candidates' (row,
+  // column), not their exact distances -- while the exact re-evaluation (HBM-bound) and the copies back to
+  // the host run on a second stream beside it; the host's row minima / sort / walk then run beside the
+  // verification kernels too.
+  const bool speculate = c->spec.requested && !c->spec.launched;
+  hipStream_t cs = c->stream;
+  if (speculate) {
+    SF_HIP(c, hipEventRecord(c->spec.ev_refined, c->stream));          // = the filter has finished
+    SF_HIP(c, hipStreamWaitEvent(c->spec.copy_stream, c->spec.ev_refined, 0));
+    cs = c->spec.copy_stream;
+    if ((rc = sf_spec_launch(c, fb.cand, fb.count)) != SF_OK) return rc;     // handle's stream: pair list + verification
+    c->spec.launched = true;
+  }
+  {
+    UseWorkspace on_cs(c, *c->w, cs);    // (sf_prof_begin / _end record on the stream the kernel runs on)
+    sf_prof_begin(c, SF_K_NN_REFINE);
+    // sized like the speculative copy below (2N + 1024 candidates): a grid for the whole sparse limit
+    // (8N + 4096) is 4/5 empty workgroups that the dispatcher still has to walk through -- beside the
+    // verification kernel in the speculative path; throttled beside a speculative verification of full-size frames
+    hipLaunchKernelGGL(k_nn_refine, dim3(nn_refine_grid(c, spec, speculate && c->store.kcap >= 256)), dim3(256), 0, cs,
+                       fb.cand, fb.count, spec, A, B, sh.dim, sh.ld, fb.cdist, 0u);
+    sf_prof_end(c, SF_K_NN_REFINE);
+  }
+  SF_HIP(c, hipMemcpyAsync(c->nn_pinned, fb.count, 4, hipMemcpyDeviceToHost, cs));
+  SF_HIP(c, hipMemcpyAsync(hc.cand, fb.cand, (size_t)spec * 8, hipMemcpyDeviceToHost, cs));
+  SF_HIP(c, hipMemcpyAsync(hc.dist, fb.cdist, (size_t)spec * 8, hipMemcpyDeviceToHost, cs));
+  if (speculate) {
+    SF_HIP(c, hipEventRecord(c->spec.ev_copied, cs));
+    SF_HIP(c, hipEventSynchronize(c->spec.ev_copied));
+  } else {
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  hc.n = *(const unsigned*)c->nn_pinned;
+  tr.mark("filter + refine + D2H", hc.n);
+  *ok = hc.n <= limit;
+  if (speculate) c->spec.valid = *ok && hc.n <= c->spec.grid;
+  if (*ok && hc.n > spec) {
+    // (rare) the tail of the candidate list; on the copy stream when the handle's stream is already busy
+    // with the speculative verification
+    hipLaunchKernelGGL(k_nn_refine, dim3((hc.n - spec + 3) / 4), dim3(256), 0, cs, fb.cand, fb.count, hc.n, A, B, sh.dim,
+                       sh.ld, fb.cdist, spec);
+    SF_HIP(c, hipMemcpyAsync(hc.cand + spec, fb.cand + spec, (size_t)(hc.n - spec) * 8, hipMemcpyDeviceToHost, cs));
+    SF_HIP(c, hipMemcpyAsync(hc.dist + spec, fb.cdist + spec, (size_t)(hc.n - spec) * 8, hipMemcpyDeviceToHost, cs));
+    SF_HIP(c, hipStreamSynchronize(cs));
+  }
+  return SF_OK;
+}
+
+// The same for the FULL-length level, whose list may be anything that fits the buffer (`limit`): the count makes a
+// round trip first, then the refinement and the copies are sized for it.
+static int nn_refine_full(sf_context* c, const NnShape& sh, const NnFilterBufs& fb, unsigned limit, NnTrace& tr,
+                          NnHostCand& hc, bool* ok) {
+  int rc;
+  SF_HIP(c, hipMemcpyAsync(&hc.n, fb.count, 4, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  tr.mark("filter + count", hc.n);
+  *ok = hc.n <= limit;
+  if (!*ok) return SF_OK;
+  if ((rc = hc.reserve(c, hc.n)) != SF_OK) return rc;
+  if (hc.n) {
+    sf_prof_begin(c, SF_K_NN_REFINE);
+    hipLaunchKernelGGL(k_nn_refine, dim3((hc.n + 3) / 4), dim3(256), 0, c->stream, fb.cand, fb.count, hc.n,
+                       (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, sh.dim, sh.ld, fb.cdist);
+    sf_prof_end(c, SF_K_NN_REFINE);
+    SF_HIP(c, hipMemcpyAsync(hc.cand, fb.cand, (size_t)hc.n * 8, hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipMemcpyAsync(hc.dist, fb.cdist, (size_t)hc.n * 8, hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return SF_OK;
+}
+
+// Per-row minimum over the exact candidate distances (ties: lowest column), ignored pairs skipped.
+// Rows without a candidate have their true minimum >= netvlad_distance: reported as +inf.
+// A candidate admitted only by the error band may still be >= the threshold: that is fine, the
+// walk compares the exact float64 value.
+static void nn_host_row_minima(sf_context* c, const NnShape& sh, const NnHostCand& hc) {
+  c->last_row_min.assign(sh.n_l, (double)INFINITY);
+  c->last_row_arg.assign(sh.n_l, 0);
+  c->last_row_cand.assign(sh.n_l, -1);
+  std::vector<std::pair<int, int>> ign;
+  for (size_t e = 0; e + 1 < c->ignored.size(); e += 2) ign.push_back({c->ignored[e], c->ignored[e + 1]});
+  std::sort(ign.begin(), ign.end());
+  for (unsigned i = 0; i < hc.n; ++i) {
+    const int r = (int)hc.cand[i].x, col = (int)hc.cand[i].y;
+    if (r >= sh.n_l || col >= sh.n_r) continue;
+    if (!ign.empty() && std::binary_search(ign.begin(), ign.end(), std::make_pair(r, col))) continue;
+    const double d = hc.dist[i];
+    if (d < c->last_row_min[r] || (d == c->last_row_min[r] && col < c->last_row_arg[r])) {
+      c->last_row_min[r] = d;
+      c->last_row_arg[r] = col;
+      c->last_row_cand[r] = (int32_t)i;
+    }
+  }
+}
+
+// Returns SF_OK with *done = 1 when the filter path produced the row minima; *done = 0 means the
+// candidate buffer overflowed (threshold too loose for a sparse filter) -> caller runs the exact path.
+// Walks the ladder from the handle's level: if a level's candidate list is too dense the next one is tried, the
+// full length last, and after that the exact fp32-ranking path.
+static int nn_run_filter(sf_context* c, const NnShape& sh, int* done) {
   *done = 0;
   NnTrace tr;
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n, dim = c->nn_dim;
-  const int ld = (dim + NN_BK - 1) / NN_BK * NN_BK;
-  const int ld16 = (dim + 63) / 64 * 64;
   int rc;
-  // Stage 1 contracts only a PREFIX of the descriptor: the squared distance over the first k
-  // dimensions is a lower bound of the full squared distance, so "prefix distance (within the fp16
-  // error band) under the threshold" is a necessary condition.  PCA-whitened NetVLAD spreads its
-  // energy evenly (the reference itself ranks on a 128-dim prefix, data_handler.py:157-158), so an
-  // eighth of the dimensions already rejects everything but real neighbours.  If the candidate
-  // buffer overflows the full length is tried, and after that the exact fp32-ranking path.
-  const int kfull = ld16;
-  // prefix ladder: 128 and 512 dimensions when they are at most a quarter of the descriptor, then the
-  // full length.  The handle remembers the level that last produced a sparse candidate set.
-  int levels[3], n_levels = 0;
-  if (128 * 4 <= dim) levels[n_levels++] = 128;
-  if (512 * 4 <= dim) levels[n_levels++] = 512;
-  levels[n_levels++] = kfull;
-  int level = std::min(std::max(c->nn_level, 0), n_levels - 1);
+  const NnLadder ladder(c, sh);
+  int level = ladder.current;
   if (c->nn_force_full) {
-    level = n_levels - 1;      // SF_OPT_NN_FULL_FILTER: no prefix level (the worst case of the adaptive ladder)
+    level = ladder.full();     // SF_OPT_NN_FULL_FILTER: no prefix level (the worst case of the adaptive ladder)
   } else if (level > 0 && c->nn_level_cooldown == 0) {   // now and then re-try the cheaper level
     --level;
     c->nn_level_cooldown = 32;
@@ -1528,109 +1471,16 @@ static int nn_run_filter(sf_context* c, int* done) {
     --c->nn_level_cooldown;
   }
   NnFilterBufs fb;
-  if ((rc = nn_filter_reserve(c, fb)) != SF_OK) return rc;
-  const unsigned cap = fb.cap;
-  uint2* const cand = fb.cand;
-  double* const cdist = fb.cdist;
-  unsigned* count = fb.count;
-  unsigned n_cand = 0;
+  if ((rc = nn_filter_reserve(c, sh, fb)) != SF_OK) return rc;
+  NnHostCand hc;
   bool ok = false;
-  uint2* h_cand = nullptr;     // pinned staging of the candidate list (pageable D2H copies are staged and slow)
-  double* h_dist = nullptr;
-  for (; level < n_levels && !ok; ++level) {
-    const int kdims = levels[level];
-    if ((rc = nn_filter_launch(c, fb, level, kdims, &tr)) != SF_OK) return rc;
-    count = fb.count;
-    const bool prefix_level = level < n_levels - 1;
-    // a dense prefix result would make the exact refinement the expensive part: insist on a sparse
-    // candidate set from a prefix level, accept anything that fits the buffer from the full-length level
-    const unsigned limit = prefix_level ? (unsigned)(8 * (size_t)n_l + 4096) : cap;
-    if (prefix_level) {
-      // no host round trip between the filter and the refinement: the refine grid is sized for the
-      // sparse limit and reads the count on the device; count, candidates and distances come back
-      // behind ONE synchronisation (a speculative prefix of 2N + 1024 entries, the rest if needed)
-      if ((rc = nn_pinned_reserve(c, (size_t)limit * 16 + 64)) != SF_OK) return rc;
-      h_cand = (uint2*)((char*)c->nn_pinned + 64);
-      h_dist = (double*)((char*)c->nn_pinned + 64 + (size_t)limit * 8);
-      const unsigned spec = std::min<unsigned>(limit, (unsigned)(2 * (size_t)n_l + 1024));
-      // With a speculative verification requested (sf_find_matches_and_verify_device) the handle's stream goes
-      // from the filter straight into the verification of every candidate -- which needs the candidates' (row,
-      // column), not their exact distances -- while the exact re-evaluation (HBM-bound) and the copies back to
-      // the host run on a second stream beside it; the host's row minima / sort / walk then run beside the
-      // verification kernels too.
-      const bool speculate = c->spec.requested && !c->spec.launched;
-      hipStream_t cs = c->stream;
-      if (speculate) {
-        SF_HIP(c, hipEventRecord(c->spec.ev_refined, c->stream));          // = the filter has finished
-        SF_HIP(c, hipStreamWaitEvent(c->spec.copy_stream, c->spec.ev_refined, 0));
-        cs = c->spec.copy_stream;
-        if ((rc = sf_spec_launch(c, cand, count)) != SF_OK) return rc;     // handle's stream: pair list + verification
-        c->spec.launched = true;
-      }
-      {
-        UseWorkspace on_cs(c, *c->w, cs);    // (sf_prof_begin / _end record on the stream the kernel runs on)
-        sf_prof_begin(c, SF_K_NN_REFINE);
-        // sized like the speculative copy below (2N + 1024 candidates): a grid for the whole sparse limit
-        // (8N + 4096) is 4/5 empty workgroups that the dispatcher still has to walk through -- beside the
-        // verification kernel in the speculative path; the rare tail is re-evaluated once its size is known
-        // beside a speculative verification of full-size frames the re-evaluation has ~10x its own run time of
-        // slack: one workgroup per CU walks the list (grid-stride) instead of a workgroup per four candidates, which
-        // leaves the HBM and the dispatcher to the verification kernel's first third (k_verify_fused 0.60 -> 0.58 ms,
-        // the re-evaluation 0.09 -> 0.16 ms in its shadow)
-        unsigned refine_wgs = (spec + 3) / 4;
-        if (speculate && c->store.kcap >= 256) {
-          if (c->n_cus <= 0) {
-            int v = 0;
-            c->n_cus = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0) ? v : 256;
-          }
-          refine_wgs = std::min(refine_wgs, (unsigned)c->n_cus);
-        }
-        hipLaunchKernelGGL(k_nn_refine, dim3(refine_wgs), dim3(256), 0, cs, cand, count, spec,
-                           (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, dim, ld, cdist, 0u);
-        sf_prof_end(c, SF_K_NN_REFINE);
-      }
-      SF_HIP(c, hipMemcpyAsync(c->nn_pinned, count, 4, hipMemcpyDeviceToHost, cs));
-      SF_HIP(c, hipMemcpyAsync(h_cand, cand, (size_t)spec * 8, hipMemcpyDeviceToHost, cs));
-      SF_HIP(c, hipMemcpyAsync(h_dist, cdist, (size_t)spec * 8, hipMemcpyDeviceToHost, cs));
-      if (speculate) {
-        SF_HIP(c, hipEventRecord(c->spec.ev_copied, cs));
-        SF_HIP(c, hipEventSynchronize(c->spec.ev_copied));
-      } else {
-        SF_HIP(c, hipStreamSynchronize(c->stream));
-      }
-      n_cand = *(const unsigned*)c->nn_pinned;
-      tr.mark("filter + refine + D2H", n_cand);
-      ok = n_cand <= limit;
-      if (speculate) c->spec.valid = ok && n_cand <= c->spec.grid;
-      if (ok && n_cand > spec) {
-        // (rare) the tail of the candidate list; on the copy stream when the handle's stream is already busy
-        // with the speculative verification
-        hipLaunchKernelGGL(k_nn_refine, dim3((n_cand - spec + 3) / 4), dim3(256), 0, cs, cand, count, n_cand,
-                           (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, dim, ld, cdist, spec);
-        SF_HIP(c, hipMemcpyAsync(h_cand + spec, cand + spec, (size_t)(n_cand - spec) * 8, hipMemcpyDeviceToHost, cs));
-        SF_HIP(c, hipMemcpyAsync(h_dist + spec, cdist + spec, (size_t)(n_cand - spec) * 8, hipMemcpyDeviceToHost, cs));
-        SF_HIP(c, hipStreamSynchronize(cs));
-      }
-    } else {
-      SF_HIP(c, hipMemcpyAsync(&n_cand, count, 4, hipMemcpyDeviceToHost, c->stream));
-      SF_HIP(c, hipStreamSynchronize(c->stream));
-      tr.mark("filter + count", n_cand);
-      ok = n_cand <= limit;
-      if (ok) {
-        if ((rc = nn_pinned_reserve(c, (size_t)n_cand * 16 + 64)) != SF_OK) return rc;
-        h_cand = (uint2*)((char*)c->nn_pinned + 64);
-        h_dist = (double*)((char*)c->nn_pinned + 64 + (size_t)n_cand * 8);
-        if (n_cand) {
-          sf_prof_begin(c, SF_K_NN_REFINE);
-          hipLaunchKernelGGL(k_nn_refine, dim3((n_cand + 3) / 4), dim3(256), 0, c->stream, cand, count, n_cand,
-                             (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, dim, ld, cdist);
-          sf_prof_end(c, SF_K_NN_REFINE);
-          SF_HIP(c, hipMemcpyAsync(h_cand, cand, (size_t)n_cand * 8, hipMemcpyDeviceToHost, c->stream));
-          SF_HIP(c, hipMemcpyAsync(h_dist, cdist, (size_t)n_cand * 8, hipMemcpyDeviceToHost, c->stream));
-          SF_HIP(c, hipStreamSynchronize(c->stream));
-        }
-      }
-    }
+  for (; level < ladder.n_levels && !ok; ++level) {
+    const int kdims = ladder.levels[level];
+    if ((rc = nn_filter_launch(c, sh, fb, level, kdims, tr)) != SF_OK) return rc;
+    const unsigned limit = ladder.limit(level, fb.cap);
+    if (level < ladder.full()) rc = nn_refine_prefix(c, sh, fb, limit, ladder.typical(level, fb.cap), tr, hc, &ok);
+    else rc = nn_refine_full(c, sh, fb, limit, tr, hc, &ok);
+    if (rc != SF_OK) return rc;
     if (ok) {
       if (!c->nn_force_full) c->nn_level = level;
       c->nn_last_kdims = kdims;
@@ -1641,28 +1491,8 @@ static int nn_run_filter(sf_context* c, int* done) {
     return SF_OK;
   }
   tr.mark("refine + D2H");
-  // per-row minimum over the exact candidate distances (ties: lowest column), ignored pairs skipped.
-  // Rows without a candidate have their true minimum >= netvlad_distance: reported as +inf.
-  c->last_row_min.assign(n_l, (double)INFINITY);
-  c->last_row_arg.assign(n_l, 0);
-  c->last_row_cand.assign(n_l, -1);
-  std::vector<std::pair<int, int>> ign;
-  for (size_t e = 0; e + 1 < c->ignored.size(); e += 2) ign.push_back({c->ignored[e], c->ignored[e + 1]});
-  std::sort(ign.begin(), ign.end());
-  for (unsigned i = 0; i < n_cand; ++i) {
-    const int r = (int)h_cand[i].x, col = (int)h_cand[i].y;
-    if (r >= n_l || col >= n_r) continue;
-    if (!ign.empty() && std::binary_search(ign.begin(), ign.end(), std::make_pair(r, col))) continue;
-    const double d = h_dist[i];
-    if (d < c->last_row_min[r] || (d == c->last_row_min[r] && col < c->last_row_arg[r])) {
-      c->last_row_min[r] = d;
-      c->last_row_arg[r] = col;
-      c->last_row_cand[r] = (int32_t)i;
-    }
-  }
+  nn_host_row_minima(c, sh, hc);
   tr.mark("host row minima");
-  // a candidate admitted only by the error band may still be >= the threshold: that is fine, the
-  // walk compares the exact float64 value
   *done = 1;
   return SF_OK;
 }
@@ -1779,9 +1609,8 @@ int sf_nn_walk_dev(sf_context* c, const double* d_row_min, const int32_t* d_row_
 }
 
 // masks / ignore CSR on the device (rebuilt only when they changed)
-static int nn_sync_masks(sf_context* c) {
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n;
-  const int n_l_pad = (n_l + NN_BM - 1) / NN_BM * NN_BM, n_r_pad = (n_r + NN_BN - 1) / NN_BN * NN_BN;
+static int nn_sync_masks(sf_context* c, const NnShape& sh) {
+  const int n_l = sh.n_l, n_r = sh.n_r, n_l_pad = sh.n_l_pad, n_r_pad = sh.n_r_pad;
   int rc;
   c->mask_local.resize(n_l, 0);
   c->mask_other.resize(n_r, 0);
@@ -1809,95 +1638,91 @@ static int nn_sync_masks(sf_context* c) {
   return SF_OK;
 }
 
-int sf_nn_run(sf_context* c, sf_match* out, int cap, int* n_out) {
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n, dim = c->nn_dim;
-  if (c->params.nn_precision != 0 && c->params.nn_precision != 1)
-    return sf_fail(c, SF_EINVAL, "nn_precision %d unknown (0 = fp32 exact ranking, 1 = fp16 filter + exact refine)", c->params.nn_precision);
-  const int ld = (dim + NN_BK - 1) / NN_BK * NN_BK;
-  const int n_l_pad = (n_l + NN_BM - 1) / NN_BM * NN_BM, n_r_pad = (n_r + NN_BN - 1) / NN_BN * NN_BN;
-  const int n_strips = n_r_pad / 64;
+// The exact fp32-ranking path on the handle's stream: per-row minima (float64) and their columns into the DEVICE
+// arrays d_min[n_l] / d_arg[n_l].  The partial minima take over the filter's coefficient buffer (the callers void
+// nn_coef_level).
+static int nn_launch_exact(sf_context* c, const NnShape& sh, double* d_min, int32_t* d_arg) {
   int rc;
-  if ((rc = nn_sync_masks(c)) != SF_OK) return rc;
-  int filtered = 0;
-  c->nn_last_kdims = 0;
-  if (c->params.nn_precision == 1) {
-    if ((rc = nn_run_filter(c, &filtered)) != SF_OK) return rc;
-  }
-  if (!filtered) {
-  c->spec.valid = false;   // the exact path has no candidate list
-  c->last_row_cand.clear();
-  c->nn_coef_level = -1;   // the exact path re-uses the coefficient buffer for its partial minima
-  // workspace: partial minima, effective column norms, per-row results
-  const size_t part_bytes = (size_t)n_strips * n_l_pad * 16;   // best + second-best key per (strip, row)
+  const size_t part_bytes = (size_t)sh.n_strips * sh.n_l_pad * 16;   // best + second-best key per (strip, row)
   if ((rc = sf_buf_reserve(c, c->nn_scalar, 64)) != SF_OK) return rc;
   unsigned* nb_max_bits = (unsigned*)((char*)c->nn_scalar.p + 16);
   SF_HIP(c, hipMemsetAsync(nb_max_bits, 0, 4, c->stream));
-  if ((rc = sf_buf_reserve(c, c->nn_rowmin, part_bytes + (size_t)n_r_pad * 4)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->nn_exact, (size_t)n_l * 12)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->nn_rowmin, part_bytes + (size_t)sh.n_r_pad * 4)) != SF_OK) return rc;
   unsigned long long* part = (unsigned long long*)c->nn_rowmin.p;
-  float* nb_eff = (float*)((char*)c->nn_rowmin.p + part_bytes);
-  double* d_dist = (double*)c->nn_exact.p;
-  int* d_idx = (int*)((char*)c->nn_exact.p + (size_t)n_l * 8);
+  float* nb_eff = (float*)((char*)c->nn_rowmin.p + part_bytes);   // effective column norms
+  const float* const A = (const float*)c->nn_local.rows.p;
+  const float* const B = (const float*)c->nn_recv.rows.p;
+  const int gx = sh.n_r_pad / NN_BN, gy = sh.n_l_pad / NN_BM;
 
-  hipLaunchKernelGGL(k_nn_fill_norms, dim3((n_r_pad + 255) / 256), dim3(256), 0, c->stream, nb_eff,
-                     (const float*)c->nn_recv.norms.p, (const uint8_t*)c->d_mask_other.p, n_r, n_r_pad, nb_max_bits);
+  hipLaunchKernelGGL(k_nn_fill_norms, dim3((sh.n_r_pad + 255) / 256), dim3(256), 0, c->stream, nb_eff,
+                     (const float*)c->nn_recv.norms.p, (const uint8_t*)c->d_mask_other.p, sh.n_r, sh.n_r_pad, nb_max_bits);
   sf_prof_begin(c, SF_K_NN);
-  hipLaunchKernelGGL(k_nn_argmin, dim3((n_r_pad / NN_BN) * (n_l_pad / NN_BM)), dim3(256), 0, c->stream,
-                     (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p,
-                     (const float*)c->nn_local.norms.p, nb_eff, (const int*)c->d_ign_ptr.p,
-                     (const int*)c->d_ign_col.p, part, n_l_pad, ld, n_r_pad / NN_BN, n_l_pad / NN_BM);
+  hipLaunchKernelGGL(k_nn_argmin, dim3(gx * gy), dim3(256), 0, c->stream, A, B, (const float*)c->nn_local.norms.p, nb_eff,
+                     (const int*)c->d_ign_ptr.p, (const int*)c->d_ign_col.p, part, sh.n_l_pad, sh.ld, gx, gy);
   sf_prof_end(c, SF_K_NN);
   sf_prof_begin(c, SF_K_NN_SELECT);
-  hipLaunchKernelGGL(k_nn_select, dim3((n_l + 3) / 4), dim3(256), 0, c->stream, part, n_strips, n_l, n_l_pad,
-                     (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, dim, ld,
-                     (const uint8_t*)c->d_mask_local.p, (const float*)c->nn_local.norms.p, nb_eff, nb_max_bits,
-                     (const int*)c->d_ign_ptr.p, (const int*)c->d_ign_col.p, n_r, d_dist, d_idx);
+  hipLaunchKernelGGL(k_nn_select, dim3((sh.n_l + 3) / 4), dim3(256), 0, c->stream, part, sh.n_strips, sh.n_l, sh.n_l_pad,
+                     A, B, sh.dim, sh.ld, (const uint8_t*)c->d_mask_local.p, (const float*)c->nn_local.norms.p, nb_eff,
+                     nb_max_bits, (const int*)c->d_ign_ptr.p, (const int*)c->d_ign_col.p, sh.n_r, d_min, d_arg);
   sf_prof_end(c, SF_K_NN_SELECT);
   SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
 
-  c->last_row_min.resize(n_l);
-  c->last_row_arg.resize(n_l);
-  SF_HIP(c, hipMemcpyAsync(c->last_row_min.data(), d_dist, (size_t)n_l * 8, hipMemcpyDeviceToHost, c->stream));
-  SF_HIP(c, hipMemcpyAsync(c->last_row_arg.data(), d_idx, (size_t)n_l * 4, hipMemcpyDeviceToHost, c->stream));
-  SF_HIP(c, hipStreamSynchronize(c->stream));
+int sf_nn_run(sf_context* c, sf_match* out, int cap, int* n_out) {
+  if (c->params.nn_precision != 0 && c->params.nn_precision != 1)
+    return sf_fail(c, SF_EINVAL, "nn_precision %d unknown (0 = fp32 exact ranking, 1 = fp16 filter + exact refine)", c->params.nn_precision);
+  const NnShape sh(c);
+  const int n_l = sh.n_l;
+  int rc;
+  if ((rc = nn_sync_masks(c, sh)) != SF_OK) return rc;
+  int filtered = 0;
+  c->nn_last_kdims = 0;
+  if (c->params.nn_precision == 1) {
+    if ((rc = nn_run_filter(c, sh, &filtered)) != SF_OK) return rc;
+  }
+  if (!filtered) {
+    c->spec.valid = false;   // the exact path has no candidate list
+    c->last_row_cand.clear();
+    c->nn_coef_level = -1;   // the exact path re-uses the coefficient buffer for its partial minima
+    if ((rc = sf_buf_reserve(c, c->nn_exact, (size_t)n_l * 12)) != SF_OK) return rc;
+    double* d_dist = (double*)c->nn_exact.p;
+    int32_t* d_idx = (int32_t*)((char*)c->nn_exact.p + (size_t)n_l * 8);
+    if ((rc = nn_launch_exact(c, sh, d_dist, d_idx)) != SF_OK) return rc;
+    c->last_row_min.resize(n_l);
+    c->last_row_arg.resize(n_l);
+    SF_HIP(c, hipMemcpyAsync(c->last_row_min.data(), d_dist, (size_t)n_l * 8, hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipMemcpyAsync(c->last_row_arg.data(), d_idx, (size_t)n_l * 4, hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
   }
 
-  return sf_nn_walk_host(c, c->last_row_min.data(), c->last_row_arg.data(), n_l, n_r, c->params.netvlad_distance,
+  return sf_nn_walk_host(c, c->last_row_min.data(), c->last_row_arg.data(), n_l, sh.n_r, c->params.netvlad_distance,
                          c->params.netvlad_max_matches_nb, out, cap, n_out);
 }
 
-// The NN kernels of this handle's local rows WITHOUT the walk and without a host round trip: d_row_min[n_local]
-// (float64) and d_row_arg[n_local] (int32) in DEVICE memory, asynchronous on the handle's stream.  This is what one
-// rank of the row-sharded NN stage contributes to the all-gather (SURVEY.md section 8(e); data_handler.py:166-189 on
-// a block of rows).  With nn_precision 1 the prefix filter runs at the ladder level the handle last settled on;
-// d_status[0] = 1 reports a candidate set denser than the sparse limit (the minima are then undefined and the caller
-// takes sf_nn_find_matches + sf_nn_last_row_minima, which walks the ladder), 0 otherwise.
 // The filter path of the row minima in its two halves (the speculative step puts the verification of every candidate
-// between them, on another stream): the stage-1 filter at the ladder level the handle last settled on ...
+// between them, on another stream): the stage-1 filter at the ladder level the handle last settled on (the ladder is
+// not walked and its state not touched) ...
 int sf_nn_filter_dev(sf_context* c, NnFilterOut* out) {
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n, dim = c->nn_dim;
-  if (n_l <= 0 || n_r <= 0) return sf_fail(c, SF_EINVAL, "NN filter on an empty database (%d x %d)", n_l, n_r);
+  const NnShape sh(c);
+  if (sh.n_l <= 0 || sh.n_r <= 0) return sf_fail(c, SF_EINVAL, "NN filter on an empty database (%d x %d)", sh.n_l, sh.n_r);
   int rc;
-  if ((rc = nn_sync_masks(c)) != SF_OK) return rc;
+  if ((rc = nn_sync_masks(c, sh)) != SF_OK) return rc;
   c->spec.valid = false;
   c->last_row_cand.clear();
   c->last_row_min.clear();        // (sf_nn_last_row_minima has nothing to report after this call)
   c->last_row_arg.clear();
   NnTrace tr;
-  const int ld16 = (dim + 63) / 64 * 64;
-  int levels[3], n_levels = 0;
-  if (128 * 4 <= dim) levels[n_levels++] = 128;
-  if (512 * 4 <= dim) levels[n_levels++] = 512;
-  levels[n_levels++] = ld16;
-  const int level = c->nn_force_full ? n_levels - 1 : std::min(std::max(c->nn_level, 0), n_levels - 1);
+  const NnLadder ladder(c, sh);
+  const int level = c->nn_force_full ? ladder.full() : ladder.current;
   NnFilterBufs fb;
-  if ((rc = nn_filter_reserve(c, fb)) != SF_OK) return rc;
-  if ((rc = nn_filter_launch(c, fb, level, levels[level], &tr)) != SF_OK) return rc;
-  c->nn_last_kdims = levels[level];
+  if ((rc = nn_filter_reserve(c, sh, fb)) != SF_OK) return rc;
+  if ((rc = nn_filter_launch(c, sh, fb, level, ladder.levels[level], tr)) != SF_OK) return rc;
+  c->nn_last_kdims = ladder.levels[level];
   out->cand = fb.cand; out->count = fb.count; out->cdist = fb.cdist;
-  out->limit = level < n_levels - 1 ? (unsigned)(8 * (size_t)n_l + 4096) : fb.cap;
+  out->limit = ladder.limit(level, fb.cap);
   // the count stays on the device: the grids are sized for a typical sparse list and stride over a longer one
-  out->typical = std::min<unsigned>(out->limit, (unsigned)(2 * (size_t)n_l + 1024));
+  out->typical = ladder.typical(level, fb.cap);
   return SF_OK;
 }
 
@@ -1905,22 +1730,12 @@ int sf_nn_filter_dev(sf_context* c, NnFilterOut* out) {
 // d_row_cand / d_arg64 (both or neither): also the candidate-list index of each row's minimum.
 int sf_nn_minima_of_candidates_dev(sf_context* c, const NnFilterOut& fo, double* d_row_min, int32_t* d_row_arg,
                                    int32_t* d_status, int32_t* d_row_cand, unsigned long long* d_arg64, bool throttle) {
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n, dim = c->nn_dim;
-  const int ld = (dim + NN_BK - 1) / NN_BK * NN_BK;
+  const NnShape sh(c);
+  const int n_l = sh.n_l, n_r = sh.n_r;
   const uint2* cand = (const uint2*)fo.cand;
-  unsigned refine_wgs = (fo.typical + 3) / 4;
-  if (throttle) {
-    // beside a verification launch the re-evaluation has several times its own run time of slack: one workgroup per CU
-    // walks the list (grid-stride) and leaves the HBM and the dispatcher to the verification kernel's first third
-    if (c->n_cus <= 0) {
-      int v = 0;
-      c->n_cus = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0) ? v : 256;
-    }
-    refine_wgs = std::min(refine_wgs, (unsigned)c->n_cus);
-  }
   sf_prof_begin(c, SF_K_NN_REFINE);
-  hipLaunchKernelGGL(k_nn_refine, dim3(refine_wgs), dim3(256), 0, c->stream, cand, fo.count, fo.limit,
-                     (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, dim, ld, fo.cdist, 0u);
+  hipLaunchKernelGGL(k_nn_refine, dim3(nn_refine_grid(c, fo.typical, throttle)), dim3(256), 0, c->stream, cand, fo.count,
+                     fo.limit, (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, sh.dim, sh.ld, fo.cdist, 0u);
   sf_prof_end(c, SF_K_NN_REFINE);
   unsigned long long* mn = (unsigned long long*)d_row_min;
   const int wgs = (int)std::min<unsigned>((fo.typical + 255) / 256, 1024u);
@@ -1935,50 +1750,32 @@ int sf_nn_minima_of_candidates_dev(sf_context* c, const NnFilterOut& fo, double*
   return SF_OK;
 }
 
+// The NN kernels of this handle's local rows WITHOUT the walk and without a host round trip: d_row_min[n_local]
+// (float64) and d_row_arg[n_local] (int32) in DEVICE memory, asynchronous on the handle's stream.  This is what one
+// rank of the row-sharded NN stage contributes to the all-gather (SURVEY.md section 8(e); data_handler.py:166-189 on
+// a block of rows).  With nn_precision 1 the prefix filter runs at the ladder level the handle last settled on;
+// d_status[0] = 1 reports a candidate set denser than the sparse limit (the minima are then undefined and the caller
+// takes sf_nn_find_matches + sf_nn_last_row_minima, which walks the ladder), 0 otherwise.
 int sf_nn_row_minima_dev(sf_context* c, double* d_row_min, int32_t* d_row_arg, int32_t* d_status) {
-  const int n_l = c->nn_local.n, n_r = c->nn_recv.n, dim = c->nn_dim;
-  if (n_l <= 0 || n_r <= 0) return sf_fail(c, SF_EINVAL, "sf_nn_row_minima_device on an empty database (%d x %d)", n_l, n_r);
+  const NnShape sh(c);
+  if (sh.n_l <= 0 || sh.n_r <= 0)
+    return sf_fail(c, SF_EINVAL, "sf_nn_row_minima_device on an empty database (%d x %d)", sh.n_l, sh.n_r);
   if (c->params.nn_precision != 0 && c->params.nn_precision != 1)
     return sf_fail(c, SF_EINVAL, "nn_precision %d unknown", c->params.nn_precision);
-  const int ld = (dim + NN_BK - 1) / NN_BK * NN_BK;
-  const int n_l_pad = (n_l + NN_BM - 1) / NN_BM * NN_BM, n_r_pad = (n_r + NN_BN - 1) / NN_BN * NN_BN;
   int rc;
   if (c->params.nn_precision == 1) {
     NnFilterOut fo;
     if ((rc = sf_nn_filter_dev(c, &fo)) != SF_OK) return rc;
     return sf_nn_minima_of_candidates_dev(c, fo, d_row_min, d_row_arg, d_status, nullptr, nullptr, false);
   }
-  if ((rc = nn_sync_masks(c)) != SF_OK) return rc;
+  if ((rc = nn_sync_masks(c, sh)) != SF_OK) return rc;
   c->spec.valid = false;
   c->last_row_cand.clear();
   c->last_row_min.clear();        // (sf_nn_last_row_minima has nothing to report after this call)
   c->last_row_arg.clear();
   // exact fp32-ranking path: its select kernel already leaves the minima in device memory
-  const int n_strips = n_r_pad / 64;
   c->nn_last_kdims = 0;
   c->nn_coef_level = -1;
-  const size_t part_bytes = (size_t)n_strips * n_l_pad * 16;
-  if ((rc = sf_buf_reserve(c, c->nn_scalar, 64)) != SF_OK) return rc;
-  unsigned* nb_max_bits = (unsigned*)((char*)c->nn_scalar.p + 16);
-  SF_HIP(c, hipMemsetAsync(nb_max_bits, 0, 4, c->stream));
   SF_HIP(c, hipMemsetAsync(d_status, 0, 4, c->stream));
-  if ((rc = sf_buf_reserve(c, c->nn_rowmin, part_bytes + (size_t)n_r_pad * 4)) != SF_OK) return rc;
-  unsigned long long* part = (unsigned long long*)c->nn_rowmin.p;
-  float* nb_eff = (float*)((char*)c->nn_rowmin.p + part_bytes);
-  hipLaunchKernelGGL(k_nn_fill_norms, dim3((n_r_pad + 255) / 256), dim3(256), 0, c->stream, nb_eff,
-                     (const float*)c->nn_recv.norms.p, (const uint8_t*)c->d_mask_other.p, n_r, n_r_pad, nb_max_bits);
-  sf_prof_begin(c, SF_K_NN);
-  hipLaunchKernelGGL(k_nn_argmin, dim3((n_r_pad / NN_BN) * (n_l_pad / NN_BM)), dim3(256), 0, c->stream,
-                     (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p,
-                     (const float*)c->nn_local.norms.p, nb_eff, (const int*)c->d_ign_ptr.p,
-                     (const int*)c->d_ign_col.p, part, n_l_pad, ld, n_r_pad / NN_BN, n_l_pad / NN_BM);
-  sf_prof_end(c, SF_K_NN);
-  sf_prof_begin(c, SF_K_NN_SELECT);
-  hipLaunchKernelGGL(k_nn_select, dim3((n_l + 3) / 4), dim3(256), 0, c->stream, part, n_strips, n_l, n_l_pad,
-                     (const float*)c->nn_local.rows.p, (const float*)c->nn_recv.rows.p, dim, ld,
-                     (const uint8_t*)c->d_mask_local.p, (const float*)c->nn_local.norms.p, nb_eff, nb_max_bits,
-                     (const int*)c->d_ign_ptr.p, (const int*)c->d_ign_col.p, n_r, d_row_min, d_row_arg);
-  sf_prof_end(c, SF_K_NN_SELECT);
-  SF_HIP(c, hipGetLastError());
-  return SF_OK;
+  return nn_launch_exact(c, sh, d_row_min, d_row_arg);
 }

@@ -196,7 +196,6 @@ struct sf_context {
   sf_params params;
   DeviceParams dparams;
   int device = 0;
-  int n_cus = 0;            // compute units of the device (queried on first use)
   hipStream_t stream = nullptr;   // the stream the launchers queue on: ws[0].stream, or another inside a UseWorkspace scope
   bool own_stream = false;
   // [0]: the handle's own; [1 .. SF_STEP_MAX_LANES - 1]: step lanes (SF_OPT_STEP_OVERLAP); [SF_STEP_MAX_LANES]: the second
@@ -284,9 +283,9 @@ struct sf_context {
   bool ransac_ba_attr_set = false, pnp_ba_attr_set = false, merge_ba_attr_set = false;
   bool debug_corr = false;      // SF_OPT_DEBUG_CORR: the fused kernel also writes lists / headers / states to HBM
   bool fused = true;        // fused per-pair verification kernel (SF_FUSED=0 selects the stage kernels)
-  int cu_count = 0;         // compute units of the device (grids sized to the chip); filled on first use
+  int cu_count = 0;         // compute units of the device (grids sized to the chip); read through sf_cu_count (k_nn.hip), which fills it on first use
   bool gf_select_attr = false; // k_gftt_select_lds: dynamic LDS attribute set
-  bool nn_k128_attr = false;   // k_nn_filter_f16_k128: dynamic LDS attribute set
+  bool nn_t256_attr = false;   // k_nn_filter_f16_t256: dynamic LDS attribute set
   bool split = false;       // SF_FUSED=2: one matching launch + one chain launch over the survivors (k_verify.hip)
   bool split_auto = true;   // SF_OPT_STEP_SPLIT: the split form inside overlapped steps (sf_use_split, sf_verify_host.hip); on again since
                             // round 5 (its matcher is software-pipelined: 23.0 against 22.7 M pairs/s, profiles/r05u_*)
