@@ -70,6 +70,9 @@ extern "C" {
       sf_netvlad_infer_u8_batch_device, sf_get_features_and_descriptor_u8, sf_add_keyframes_u8_batch_device (keyframes from
       the camera's rgb8 / bgr8 / mono8 images).  Nothing existing changed, the version number, sizeof(sf_params) and
       SF_K_COUNT stay.                                                                                                */
+/* 8, additions: sf_get_features_and_descriptor_orb_batch_device, sf_add_keyframes_orb_u8_batch_device (the batch forms of
+      Vis/FeatureType 2).  The generic batch calls still refuse a type-2 handle, with a message that now names these two;
+      nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.                            */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -439,8 +442,9 @@ int  sf_detect_fast_device(sf_handle h, const uint8_t* d_image, int32_t width, i
    level, ascending, order kept within a level (the row order of the keyframe); type 8's blur and steered pattern on the
    keypoint's own level around cvRound(position * (1.f / scale_l)), steered by the keypoint's own angle.
    sf_get_features_and_descriptor runs detector -> stereo correspondence (level-0 positions) -> descriptors;
-   sf_orb_set_pattern serves type 2 as it serves 8.  NOT built for type 2: the batch call
-   sf_get_features_and_descriptor_batch_device (SF_EINVAL; the follow-up), first_level != 0, WTA_K 3 / 4.          */
+   sf_orb_set_pattern serves type 2 as it serves 8.  A batch of keyframes under type 2 goes through calls of its own,
+   sf_get_features_and_descriptor_orb_batch_device and sf_add_keyframes_orb_u8_batch_device (the generic batch calls
+   return SF_EINVAL and name them).  NOT built for type 2: first_level != 0, WTA_K 3 / 4.                            */
 typedef struct sf_orb_detector_params {
   float   scale_factor;    /* ORB/ScaleFactor, 2 (rtabmap's default, not OpenCV's 1.2); (1, 4]    */
   int32_t n_levels;        /* ORB/NLevels, 3 (rtabmap's default, not OpenCV's 8); 1 .. 8          */
@@ -524,13 +528,30 @@ int  sf_get_features_and_descriptor(sf_handle h, const uint8_t* left, const uint
    device outputs, each sized for n_keyframes x det->max_features rows (keyframe i at row i * max_features; any may be
    NULL): d_rows_out [n_keyframes] features kept, d_desc_out, d_xyz_out, d_kpts_out as in the single call.  Images up to
    about 1.2 Mpixel (the corner selection keeps its bitmap in LDS); no such limit under feature type 4.
-   Feature type 2 has no batch form yet: SF_EINVAL (the follow-up of sf_set_feature_type_orb).                       */
+   Feature type 2 has a batch call of its own, sf_get_features_and_descriptor_orb_batch_device: on a type-2 handle this
+   one returns SF_EINVAL, says so and changes nothing.                                                               */
 int  sf_get_features_and_descriptor_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
                                                  int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                                  size_t image_stride, const sf_stereo_camera* cam,
                                                  const sf_detector_params* det, const sf_stereo_flow_params* flow,
                                                  int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                  float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* The same under Vis/FeatureType 2 (sf_set_feature_type_orb; the handle's detector and ORB parameters): arguments,
+   outputs, limits and refusals of sf_get_features_and_descriptor_batch_device, and per keyframe the bytes of
+   sf_get_features_and_descriptor under type 2 -- keypoint order, rows grouped by level and the store slot included.  One
+   launch sequence with no host wait: the pyramids of all images are built once (the extraction reads the detector's),
+   FAST runs once per level over the batch, the per-level counts, cuts and segment bounds stay on the device and the
+   three sorts of the selection are segmented sorts.  The workspace is sized from the image size, n_keyframes and
+   max_features alone and never truncates an image's candidates (6.7 MB per 752 x 480 pair at three levels of scale 2:
+   DESIGN.md section 3 item 17b).  It also refuses what sf_detect_orb_device refuses (an empty pyramid level:
+   SF_ERANGE).  On a handle of any other feature type: SF_EINVAL, the message names the generic call, nothing changes.
+   A refused call leaves the store, the NN database, the feature type and the detector parameters as they were.       */
+int  sf_get_features_and_descriptor_orb_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
+                                                     int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                                     size_t image_stride, const sf_stereo_camera* cam,
+                                                     const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                     int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                     float* d_xyz_out, sf_keypoint* d_kpts_out);
 
 /* ---- keyframes from the camera's own images (first step) ------------------------- */
 /* The reference keeps every image as cv_bridge's "rgb8" (data_handler.py:114-141).  For a keyframe it converts both stereo
@@ -592,14 +613,25 @@ int  sf_get_features_and_descriptor_u8(sf_handle h, const uint8_t* left, const u
    All or nothing: arguments, the loaded model against netvlad_dimensions and the NN database's dimension are checked, and
    the store slots, the NN rows and the call's own buffers reserved, before the first launch; the store and the NN
    database grow last, together.  A refused call leaves sf_store_size and sf_nn_sizes as they were.  It refuses what sf_get_features_and_descriptor_batch_device
-   refuses, with the same code and message (feature type 2 among them), and what sf_netvlad_infer_u8_batch_device refuses;
-   no model, or netvlad_dimensions beyond the model's WPCA width: SF_EINVAL.                                          */
+   refuses, with the same code and message (feature type 2 among them: its twin is sf_add_keyframes_orb_u8_batch_device),
+   and what sf_netvlad_infer_u8_batch_device refuses; no model, or netvlad_dimensions beyond the model's WPCA width:
+   SF_EINVAL.                                                                                                         */
 int  sf_add_keyframes_u8_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
                                       int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                       size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
                                       const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                       int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
                                       sf_keypoint* d_kpts_out);
+/* The same under Vis/FeatureType 2: sf_add_keyframes_u8_batch_device with the feature stages of
+   sf_get_features_and_descriptor_orb_batch_device -- the same formats and gray rule, the same network call, n store slots
+   and n NN rows under one index, all or nothing.  Slot first_slot + i holds the bytes of sf_get_features_and_descriptor_u8
+   on pair i.  Refuses what either of the two refuses; on a handle of another feature type: SF_EINVAL, nothing changes. */
+int  sf_add_keyframes_orb_u8_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+                                          int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                          size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
+                                          const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                          int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                          float* d_xyz_out, sf_keypoint* d_kpts_out);
 
 /* ---- geometric verification (stereoCamGeometricTools.cpp:122-178) ---------------------------- */
 /* One estimate_transformation service call on host buffers.                                  */

@@ -40,9 +40,10 @@ constexpr int BRIEF_BORDER = BRIEF_PATCH / 2 + BRIEF_KERNEL / 2;   // KeyPointsF
 
 // A batch of keyframes in one launch sequence (blockIdx.y = image, except k_extract_commit: blockIdx.x): images
 // img_stride bytes apart, integral images s_stride entries apart, per-corner arrays per_image entries apart, the corner
-// count of every image in d_n (device; null = the scalar n of the single-image call).
+// count of every image in d_n (device; null = the scalar n of the single-image call).  ORB on a pyramid: the pyramids
+// (levels >= 1) pyr_stride bytes apart.
 struct ExtractBatch {
-  size_t img_stride, s_stride;
+  size_t img_stride, s_stride, pyr_stride;
   int per_image;
   const int32_t* d_n;
 };
@@ -282,6 +283,7 @@ k_orb_angle(const uint8_t* __restrict__ img, int pitch, const uint8_t* __restric
   if (B.d_n) n = min(n, B.d_n[blockIdx.y]);
   if (i >= n) return;
   img += blockIdx.y * B.img_stride;
+  if (pyr) pyr += blockIdx.y * B.pyr_stride;
   kpts += (size_t)blockIdx.y * B.per_image;
   kpts_out += (size_t)blockIdx.y * B.per_image;
   sf_keypoint k = kpts[i];
@@ -328,6 +330,7 @@ k_orb_points(const uint8_t* __restrict__ img, const uint8_t* __restrict__ blur, 
     const size_t o = (size_t)blockIdx.y * B.per_image;
     img += blockIdx.y * B.img_stride;
     blur += blockIdx.y * B.s_stride;
+    if (pyr) pyr += blockIdx.y * B.pyr_stride;
     kpts += o;
     if (right_x) right_x += o;
     if (status) status += o;
@@ -492,14 +495,15 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   const sf_orb_detector_params* pyr = kind.pyr;
   const Store& st = c->store;
   int rc;
-  if (pyr && (!orb || n_img != 1)) return sf_fail(c, SF_EINVAL, "ORB on a pyramid: one keyframe per call");
+  if (pyr && (!orb || (!kind.pyr_stride && n_img != 1)))
+    return sf_fail(c, SF_EINVAL, "ORB on a pyramid: one keyframe per call unless the detector has left the batch's pyramids");
   if (orb && bytes != ORB_BYTES) return sf_fail(c, SF_EINVAL, "ORB rows are %d bytes, not %d", ORB_BYTES, bytes);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_xyz, rows_all * 12)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_keep, rows_all)) != SF_OK) return rc;
   ExtractBatch B;
-  B.img_stride = img_stride; B.per_image = n; B.d_n = d_n;
+  B.img_stride = img_stride; B.pyr_stride = 0; B.per_image = n; B.d_n = d_n;
   SfOrbPyr P = sf_orb_single_level(width, height);
   int32_t* S = nullptr;
   if (!orb) {
@@ -516,13 +520,20 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                        d_left, width, height, pitch, (uint8_t*)c->ex_blur.p, orb_blur_taps(), B);
   } else {                                               // the pyramid and a blurred copy of every level, same offsets
     P = sf_orb_pyr_layout(width, height, pyr->scale_factor, pyr->n_levels);
-    B.s_stride = 0;
-    if ((rc = sf_launch_orb_pyramid(c, d_left, pitch, P)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->ex_blur, P.total)) != SF_OK) return rc;
-    for (int l = 0; l < P.n; ++l)
-      hipLaunchKernelGGL(k_orb_blur, dim3((P.h[l] + ORB_BLUR_ROWS - 1) / ORB_BLUR_ROWS, 1), dim3(256), 0, c->stream,
+    if (!kind.pyr_stride) {
+      if ((rc = sf_launch_orb_pyramid(c, d_left, pitch, P, 1, 0)) != SF_OK) return rc;
+    } else if (kind.pyr_stride != P.total || c->orb_pyr.bytes < (size_t)P.total * n_img) {
+      return sf_fail(c, SF_EINVAL, "ORB on a pyramid: the batch's pyramids are not the detector's");
+    }
+    B.s_stride = B.pyr_stride = P.total;                 // image i's blurred levels at ex_blur + i * P.total + off[l]
+    if ((rc = sf_buf_reserve(c, c->ex_blur, (size_t)P.total * n_img)) != SF_OK) return rc;
+    for (int l = 0; l < P.n; ++l) {
+      ExtractBatch Bl = B;                               // level 0 is the caller's image, the others the pyramid's
+      if (l > 0) Bl.img_stride = P.total;
+      hipLaunchKernelGGL(k_orb_blur, dim3((P.h[l] + ORB_BLUR_ROWS - 1) / ORB_BLUR_ROWS, n_img), dim3(256), 0, c->stream,
                          l == 0 ? d_left : (const uint8_t*)c->orb_pyr.p + P.off[l], P.w[l], P.h[l], l == 0 ? pitch : P.w[l],
-                         (uint8_t*)c->ex_blur.p + P.off[l], orb_blur_taps(), B);
+                         (uint8_t*)c->ex_blur.p + P.off[l], orb_blur_taps(), Bl);
+    }
   }
   ExtractCam ec;
   ec.fx = cam->fx; ec.fy = cam->fy; ec.cx = cam->cx; ec.cy = cam->cy; ec.cx_right = cam->cx_right;
@@ -563,12 +574,13 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
 }
 
 // The ORB detector's angles (k_orb_detect.hip): keypoints in level coordinates, their number read on the device
-int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P, const sf_keypoint* d_kpts,
-                               int n_max, const int32_t* d_n, int edge, sf_keypoint* d_kpts_out) {
+int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int pitch, const SfOrbPyr& P,
+                               size_t pyr_stride, const sf_keypoint* d_kpts, int n_max, const int32_t* d_n, int edge,
+                               sf_keypoint* d_kpts_out) {
   if (n_max <= 0) return SF_OK;
   ExtractBatch B;
-  B.img_stride = 0; B.s_stride = 0; B.per_image = n_max; B.d_n = d_n;
-  hipLaunchKernelGGL(k_orb_angle, dim3((unsigned)((n_max + 3) / 4), 1), dim3(256), 0, c->stream, d_image, pitch,
+  B.img_stride = img_stride; B.s_stride = 0; B.pyr_stride = pyr_stride; B.per_image = n_max; B.d_n = d_n;
+  hipLaunchKernelGGL(k_orb_angle, dim3((unsigned)((n_max + 3) / 4), n_img), dim3(256), 0, c->stream, d_images, pitch,
                      (const uint8_t*)c->orb_pyr.p, P, d_kpts, n_max, edge, orb_umax(), d_kpts_out, B);
   SF_HIP(c, hipGetLastError());
   return SF_OK;

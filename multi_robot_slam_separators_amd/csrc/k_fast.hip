@@ -196,12 +196,13 @@ constexpr int FAST_REKEY_BLOCKS = 32;
 // One level on n_img images of one size (blockIdx.z = image): the two launches every detector shares (FAST/BRIEF here,
 // ORB's pyramid levels in k_orb_detect.hip)
 void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
-                          int threshold, int nonmax, uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap) {
+                          int threshold, int nonmax, uint8_t* score, size_t plane_stride, unsigned long long* keys, unsigned* count,
+                          unsigned key_cap) {
   const dim3 block(256);
   hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH, n_img), block, 0,
-                     c->stream, d_images, width, height, pitch, threshold, score, img_stride, (size_t)key_cap);
+                     c->stream, d_images, width, height, pitch, threshold, score, img_stride, plane_stride);
   hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS, n_img), block, 0,
-                     c->stream, (const uint8_t*)score, width, height, nonmax, keys, count, key_cap, (size_t)key_cap);
+                     c->stream, (const uint8_t*)score, width, height, nonmax, keys, count, key_cap, plane_stride);
 }
 
 // The front half of both launchers -- workspace and the three front kernels for n_img images of one size: every image's
@@ -212,7 +213,7 @@ static int fast_front(sf_context* c, const uint8_t* d_images, size_t img_stride,
   int rc = sf_detector_work(c, width, height, n_img, (size_t)width * height, F);
   if (rc != SF_OK) return rc;
   sf_launch_fast_level(c, d_images, img_stride, n_img, width, height, pitch, prm->threshold, prm->nonmax_suppression,
-                       (uint8_t*)c->gf_planes.p, F->keys, F->count, F->key_cap);
+                       (uint8_t*)c->gf_planes.p, (size_t)F->key_cap, F->keys, F->count, F->key_cap);
   hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, n_img), dim3(256), 0, c->stream, F->keys, (const unsigned*)F->count,
                      F->key_cap, max_features, F->seg_begin, F->seg_end);
   SF_HIP(c, hipGetLastError());

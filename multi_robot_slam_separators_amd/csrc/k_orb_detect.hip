@@ -26,6 +26,13 @@
 //   k_orb_emit       keypoints in LEVEL coordinates; k_orb_angle (k_extract.hip) adds the centroid angle on the level;
 //   k_orb_finish     position * scale_l into the caller's array
 // About forty short launches for three levels: latency-bound like the rest of the front end, not tuned yet.
+//
+// Two launchers over these kernels (as in k_fast.hip).  sf_launch_detect_orb sizes the lists by the corner counts it
+// reads back.  sf_launch_detect_orb_batch runs n images of one size with no host round trip: the image is a grid axis
+// (blockIdx.y; blockIdx.x for the one-workgroup kernels), every list has a fixed capacity per image (3 x 3 strict
+// maxima: a level of w x h pixels holds at most ceil(w / 2) ceil(h / 2) corners, so nothing is ever truncated), the
+// per-level segments of an image come from the counts on the device, and the three sorts are segmented sorts whose
+// bounds the kernels before them write (k_orb_gather, k_orb_cut_a, k_orb_compact).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,8 +46,10 @@ namespace {
 constexpr unsigned long long ORB_NONE = ~0ull;
 constexpr unsigned long long ORB_RASTER = 1ull << 63, ORB_LIMITED = 1ull << 62;
 // the scalar block (ints): per-level arrays of 8, then the histograms
-constexpr int S_COUNT = 0, S_CUT_A = 8, S_BEGIN = 16, S_KEPT = 24, S_TOTAL = 32, S_NFINAL = 34, S_CUT_B = 40, S_HIST = 64;
+// (a batch: one such block per image; S_NCAND = the image's candidates, which the single call knows on the host)
+constexpr int S_COUNT = 0, S_CUT_A = 8, S_BEGIN = 16, S_KEPT = 24, S_TOTAL = 32, S_NCAND = 33, S_NFINAL = 34, S_CUT_B = 40, S_HIST = 64;
 constexpr int S_WORDS = S_HIST + SF_ORB_MAX_LEVELS * 256;
+constexpr int ORB_HARRIS_BLOCKS = 1024;    // k_orb_harris of a batch: workgroups per image (4 candidates each per step)
 
 struct OrbSel {
   int n_levels, score_type, edge, max_features;
@@ -48,18 +57,20 @@ struct OrbSel {
   int quota[SF_ORB_MAX_LEVELS];
 };
 
-__device__ __forceinline__ int orb_level_of(const OrbSel& S, unsigned i) {
-  int l = 0;
-#pragma unroll
-  for (int k = 1; k < SF_ORB_MAX_LEVELS; ++k) l = i >= S.base[k] ? k : l;
-  return l;
-}
-__device__ __forceinline__ unsigned orb_base_of(const OrbSel& S, int l) {
-  unsigned r = S.base[0];
-#pragma unroll
-  for (int k = 1; k < SF_ORB_MAX_LEVELS; ++k) r = l == k ? S.base[k] : r;
-  return r;
-}
+// Where the lists of one image are.  The single call: n_img 0, everything at its base, the counts known on the host.
+// A batch (n_img >= 1): image i's source at + i * img_stride, its pyramid at + i * pyr_stride, its entries of every work
+// list at + i * cand_cap, its scalar block at + i * S_WORDS, its keypoints at + i * kp_cap.
+struct OrbBatch {
+  size_t img_stride, pyr_stride;
+  unsigned cand_cap;
+  int n_img, kp_cap;
+  unsigned key_off[SF_ORB_MAX_LEVELS];   // the FAST keys of (image i, level l) at keys_f + key_off[l] + i * key_cap[l]
+  unsigned key_cap[SF_ORB_MAX_LEVELS];
+  const unsigned* d_count;               // [level][n_img] corners found by FAST (batch)
+  unsigned* seg;                         // [6][n_img] begin / end of the three segmented sorts (batch)
+  int32_t* n_out;                        // [n_img] keypoints of every image (batch)
+};
+
 __device__ __forceinline__ int orb_quota_of(const OrbSel& S, int l) {
   int r = S.quota[0];
 #pragma unroll
@@ -81,7 +92,11 @@ __device__ __forceinline__ void orb_lin_axis(int d, int dst, int src, int& s, in
 }
 
 __global__ void __launch_bounds__(256)
-k_orb_resize(const uint8_t* __restrict__ src, int sw, int sh, int spitch, uint8_t* __restrict__ dst, int dw, int dh) {
+k_orb_resize(const uint8_t* __restrict__ src, int sw, int sh, int spitch, uint8_t* __restrict__ dst, int dw, int dh,
+             size_t src_stride, size_t dst_stride) {
+  // (blockIdx.z = image of a batch)
+  src += blockIdx.z * src_stride;
+  dst += blockIdx.z * dst_stride;
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= dw || y >= dh) return;
   int v;
@@ -101,15 +116,34 @@ k_orb_resize(const uint8_t* __restrict__ src, int sw, int sh, int spitch, uint8_
   dst[(size_t)y * dw + x] = (uint8_t)v;
 }
 
-// keys_f: the FAST keys of level l at keys_f + P.off[l] (arrival order)
+// keys_f: the FAST keys of level l of image blockIdx.y at keys_f + B.key_off[l] + blockIdx.y * B.key_cap[l] (arrival order)
 __global__ void __launch_bounds__(256)
 k_orb_gather(const unsigned long long* __restrict__ keys_f, SfOrbPyr P, OrbSel S, unsigned C, unsigned long long* __restrict__ cand,
-             int* __restrict__ sc) {
-  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+             int* __restrict__ sc, OrbBatch B) {
+  const unsigned i = blockIdx.x * 256 + threadIdx.x, img = blockIdx.y;
+  // candidate i's level, the level's first candidate and its FAST keys.  The single call has the level segments from
+  // the host (S.base); a batch sums the image's counts here, as the host does there
+  int l = 0;
+  unsigned first = 0u, koff = B.key_off[0], kcap = B.key_cap[0], run = 0u;
+#pragma unroll
+  for (int k = 0; k < SF_ORB_MAX_LEVELS; ++k) {
+    const unsigned b = !B.n_img ? S.base[k] : (k < S.n_levels ? run : 0xFFFFFFFFu);
+    if (k > 0 && i >= b) { l = k; first = b; koff = B.key_off[k]; kcap = B.key_cap[k]; }
+    if (B.n_img && k < S.n_levels) run += min(B.d_count[(unsigned)k * (unsigned)B.n_img + img], B.key_cap[k]);
+  }
+  if (B.n_img) {
+    C = run;
+    sc += (size_t)img * S_WORDS;
+    cand += (size_t)img * B.cand_cap;
+    if (i == 0) {
+      sc[S_NCAND] = (int)C;
+      B.seg[img] = img * B.cand_cap;
+      B.seg[B.n_img + img] = img * B.cand_cap + C;
+    }
+  }
   if (i >= C) return;
-  const int l = orb_level_of(S, i);
   const SfOrbLevel L = sf_orb_level(P, l);
-  const unsigned long long key = keys_f[(size_t)L.off + (i - orb_base_of(S, l))];
+  const unsigned long long key = keys_f[(size_t)koff + (size_t)img * kcap + (i - first)];
   const unsigned idx = (unsigned)key, score = (unsigned)(key >> 32) & 255u;
   const int y = (int)(idx / (unsigned)L.w), x = (int)(idx - (unsigned)y * (unsigned)L.w), e = S.edge;
   const bool inside = L.w > 2 * e && L.h > 2 * e && x >= e && x < L.w - e && y >= e && y < L.h - e;
@@ -117,11 +151,13 @@ k_orb_gather(const unsigned long long* __restrict__ keys_f, SfOrbPyr P, OrbSel S
   if (inside) atomicAdd(&sc[S_HIST + l * 256 + (int)score], 1);
 }
 
-// ONE workgroup, thread l = level l
+// ONE workgroup per image, thread l = level l
 __global__ void __launch_bounds__(64)
-k_orb_cut_a(OrbSel S, int* __restrict__ sc) {
+k_orb_cut_a(OrbSel S, int* __restrict__ sc, OrbBatch B) {
   __shared__ int s_kept[SF_ORB_MAX_LEVELS];
   const int l = threadIdx.x;
+  const unsigned img = blockIdx.x;
+  sc += (size_t)img * S_WORDS;
   if (l < SF_ORB_MAX_LEVELS) {
     int kept = 0, cut = 256;
     if (l < S.n_levels) {
@@ -146,12 +182,21 @@ k_orb_cut_a(OrbSel S, int* __restrict__ sc) {
       run += s_kept[k];
     }
     sc[S_TOTAL] = run;
+    if (B.n_img) {                     // the Harris sort's segment: the survivors of the first cut
+      B.seg[2 * B.n_img + img] = img * B.cand_cap;
+      B.seg[3 * B.n_img + img] = img * B.cand_cap + (unsigned)run;
+    }
   }
 }
 
 __global__ void __launch_bounds__(256)
-k_orb_filter_a(unsigned long long* __restrict__ cand, unsigned C, const int* __restrict__ sc) {
+k_orb_filter_a(unsigned long long* __restrict__ cand, unsigned C, const int* __restrict__ sc, OrbBatch B) {
   const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (B.n_img) {
+    sc += (size_t)blockIdx.y * S_WORDS;
+    cand += (size_t)blockIdx.y * B.cand_cap;
+    C = (unsigned)sc[S_NCAND];
+  }
   if (i >= C) return;
   const unsigned long long key = cand[i];
   if (key == ORB_NONE) return;
@@ -167,55 +212,67 @@ __device__ __forceinline__ float orb_order_float(unsigned o) {
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
 }
 
-// one candidate per wavefront (HarrisResponses, block 7, k 0.04); edge >= 16 keeps the radius-4 window inside the level
+// one candidate per wavefront and step (HarrisResponses, block 7, k 0.04); edge >= 16 keeps the radius-4 window inside the
+// level.  The single call's grid covers its C candidates in one step; a batch's fixed grid strides over the image's.
 __global__ void __launch_bounds__(256)
 k_orb_harris(const uint8_t* __restrict__ img, int pitch, const uint8_t* __restrict__ pyr, SfOrbPyr P,
              const unsigned long long* __restrict__ cand_s, const int* __restrict__ sc, unsigned C, float* __restrict__ resp,
-             unsigned long long* __restrict__ key_b) {
+             unsigned long long* __restrict__ key_b, OrbBatch B) {
   const int lane = threadIdx.x & 63;
-  const unsigned i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= C) return;
-  if (i >= (unsigned)sc[S_TOTAL]) {
-    if (lane == 0) key_b[i] = ORB_NONE;
-    return;
+  if (B.n_img) {
+    const size_t o = (size_t)blockIdx.y * B.cand_cap;
+    sc += (size_t)blockIdx.y * S_WORDS;
+    img += blockIdx.y * B.img_stride;
+    pyr += blockIdx.y * B.pyr_stride;
+    cand_s += o; resp += o; key_b += o;
+    C = (unsigned)sc[S_NCAND];
   }
-  const unsigned long long key = cand_s[i];
-  const int l = (int)(key >> 40);
-  const unsigned idx = (unsigned)(key >> 8);
-  const SfOrbLevel L = sf_orb_level(P, l);
-  const uint8_t* base = l == 0 ? img : pyr + L.off;
-  const int lp = l == 0 ? pitch : L.w;
-  const int y = (int)(idx / (unsigned)L.w), x = (int)(idx - (unsigned)y * (unsigned)L.w);
-  int a = 0, b = 0, cc = 0;
-  if (lane < 49) {
-    const int by = lane / 7, bx = lane - 7 * by;
-    const uint8_t* p = base + (size_t)(y + by - 3) * lp + (x + bx - 3);
-    const int mm = p[-lp - 1], m0 = p[-lp], mp = p[-lp + 1], zm = p[-1], zp = p[1], pm = p[lp - 1], p0 = p[lp], pp = p[lp + 1];
-    const int ix = (zp - zm) * 2 + (mp - mm) + (pp - pm);
-    const int iy = (p0 - m0) * 2 + (pm - mm) + (pp - mp);
-    a = ix * ix; b = iy * iy; cc = ix * iy;
-  }
+  const unsigned total = (unsigned)sc[S_TOTAL];
+  for (unsigned i = blockIdx.x * 4 + (threadIdx.x >> 6); i < C; i += gridDim.x * 4) {
+    if (i >= total) {
+      if (lane == 0) key_b[i] = ORB_NONE;
+      continue;
+    }
+    const unsigned long long key = cand_s[i];
+    const int l = (int)(key >> 40);
+    const unsigned idx = (unsigned)(key >> 8);
+    const SfOrbLevel L = sf_orb_level(P, l);
+    const uint8_t* base = l == 0 ? img : pyr + L.off;
+    const int lp = l == 0 ? pitch : L.w;
+    const int y = (int)(idx / (unsigned)L.w), x = (int)(idx - (unsigned)y * (unsigned)L.w);
+    int a = 0, b = 0, cc = 0;
+    if (lane < 49) {
+      const int by = lane / 7, bx = lane - 7 * by;
+      const uint8_t* p = base + (size_t)(y + by - 3) * lp + (x + bx - 3);
+      const int mm = p[-lp - 1], m0 = p[-lp], mp = p[-lp + 1], zm = p[-1], zp = p[1], pm = p[lp - 1], p0 = p[lp], pp = p[lp + 1];
+      const int ix = (zp - zm) * 2 + (mp - mm) + (pp - pm);
+      const int iy = (p0 - m0) * 2 + (pm - mm) + (pp - mp);
+      a = ix * ix; b = iy * iy; cc = ix * iy;
+    }
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    a += __shfl_xor(a, off);
-    b += __shfl_xor(b, off);
-    cc += __shfl_xor(cc, off);
-  }
-  if (lane == 0) {
-    const float fa = (float)a, fb = (float)b, fc = (float)cc;
-    const float s = 1.f / (4 * 7 * 255.f);
-    const float s4 = s * s * s * s;
-    const float sum = fa + fb;
-    const float r = ((fa * fb - fc * fc) - 0.04f * sum * sum) * s4;
-    resp[i] = r;
-    key_b[i] = ((unsigned long long)l << 32) | (unsigned)~orb_order_bits(r);
+    for (int off = 32; off >= 1; off >>= 1) {
+      a += __shfl_xor(a, off);
+      b += __shfl_xor(b, off);
+      cc += __shfl_xor(cc, off);
+    }
+    if (lane == 0) {
+      const float fa = (float)a, fb = (float)b, fc = (float)cc;
+      const float s = 1.f / (4 * 7 * 255.f);
+      const float s4 = s * s * s * s;
+      const float sum = fa + fb;
+      const float r = ((fa * fb - fc * fc) - 0.04f * sum * sum) * s4;
+      resp[i] = r;
+      key_b[i] = ((unsigned long long)l << 32) | (unsigned)~orb_order_bits(r);
+    }
   }
 }
 
-// ONE workgroup, thread l = level l: the response at rank quota - 1 of the level's segment (float bits)
+// ONE workgroup per image, thread l = level l: the response at rank quota - 1 of the level's segment (float bits)
 __global__ void __launch_bounds__(64)
-k_orb_cut_b(OrbSel S, const unsigned long long* __restrict__ key_bs, int* __restrict__ sc) {
+k_orb_cut_b(OrbSel S, const unsigned long long* __restrict__ key_bs, int* __restrict__ sc, OrbBatch B) {
   const int l = threadIdx.x;
+  sc += (size_t)blockIdx.x * S_WORDS;
+  key_bs += (size_t)blockIdx.x * B.cand_cap;
   if (l >= S.n_levels) return;
   const int q = orb_quota_of(S, l), m = sc[S_KEPT + l];
   float cut = -INFINITY;
@@ -226,13 +283,21 @@ k_orb_cut_b(OrbSel S, const unsigned long long* __restrict__ key_bs, int* __rest
   sc[S_CUT_B + l] = __float_as_int(cut);
 }
 
-// ONE workgroup: stable compaction of the survivors, then the sort keys of limitKeypoints (C entries, 0 past the end)
+// ONE workgroup per image: stable compaction of the survivors, then the sort keys of limitKeypoints (C entries, 0 past the
+// end)
 __global__ void __launch_bounds__(256)
 k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const float* __restrict__ resp, unsigned C,
               unsigned long long* __restrict__ fin_key, float* __restrict__ fin_resp, unsigned long long* __restrict__ key_c,
-              int* __restrict__ sc) {
+              int* __restrict__ sc, OrbBatch B) {
   __shared__ int wave_cnt[4];
   const int tid = threadIdx.x;
+  const unsigned img = blockIdx.x;
+  if (B.n_img) {
+    const size_t o = (size_t)img * B.cand_cap;
+    sc += (size_t)img * S_WORDS;
+    cand_s += o; resp += o; fin_key += o; fin_resp += o; key_c += o;
+    C = (unsigned)sc[S_NCAND];
+  }
   const int total = sc[S_TOTAL];
   int running = 0;
   for (int base = 0; base < total; base += 256) {
@@ -262,14 +327,28 @@ k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const flo
                   : ORB_RASTER | (0x7FFFFFFFu - o);
     key_c[o] = k;
   }
-  if (tid == 0) sc[S_NFINAL] = limited ? S.max_features : running;
+  if (tid == 0) {
+    const int n_final = limited ? S.max_features : running;
+    sc[S_NFINAL] = n_final;
+    if (B.n_img) {                     // the last sort's segment: the survivors; the image's count for the caller
+      B.seg[4 * B.n_img + img] = img * B.cand_cap;
+      B.seg[5 * B.n_img + img] = img * B.cand_cap + (unsigned)running;
+      B.n_out[img] = n_final;
+    }
+  }
 }
 
 // keypoints in LEVEL coordinates, final order
 __global__ void __launch_bounds__(256)
 k_orb_emit(SfOrbPyr P, const unsigned long long* __restrict__ key_cs, const unsigned long long* __restrict__ fin_key,
-           const float* __restrict__ fin_resp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ kp) {
+           const float* __restrict__ fin_resp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ kp, OrbBatch B) {
   const int i = blockIdx.x * 256 + threadIdx.x;
+  if (B.n_img) {
+    const size_t o = (size_t)blockIdx.y * B.cand_cap;
+    sc += (size_t)blockIdx.y * S_WORDS;
+    key_cs += o; fin_key += o; fin_resp += o;
+    kp += (size_t)blockIdx.y * B.kp_cap;
+  }
   if (i >= sc[S_NFINAL] || i >= cap) return;
   const unsigned long long kc = key_cs[i];
   const unsigned low = (unsigned)kc & 0x7FFFFFFFu;
@@ -283,8 +362,15 @@ k_orb_emit(SfOrbPyr P, const unsigned long long* __restrict__ key_cs, const unsi
 }
 
 __global__ void __launch_bounds__(256)
-k_orb_finish(SfOrbPyr P, const sf_keypoint* __restrict__ kp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ out) {
+k_orb_finish(SfOrbPyr P, const sf_keypoint* __restrict__ kp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ out,
+             OrbBatch B, int out_cap) {
+  // (batch: image blockIdx.y's keypoints to out + blockIdx.y * out_cap)
   const int i = blockIdx.x * 256 + threadIdx.x;
+  if (B.n_img) {
+    sc += (size_t)blockIdx.y * S_WORDS;
+    kp += (size_t)blockIdx.y * B.kp_cap;
+    out += (size_t)blockIdx.y * out_cap;
+  }
   if (i >= sc[S_NFINAL] || i >= cap) return;
   sf_keypoint k = kp[i];
   const SfOrbLevel L = sf_orb_level(P, k.octave);
@@ -327,20 +413,56 @@ void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota) 
   quota[n_levels - 1] = std::max(nfeatures - sum, 0);
 }
 
-int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P) {
+// Levels >= 1 of n_img images of one size (img_stride bytes apart) into c->orb_pyr, image i's at + i * P.total
+int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P, int n_img, size_t img_stride) {
   for (int l = 0; l < P.n; ++l)
     if (P.w[l] < 1 || P.h[l] < 1)
       return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, P.w[0], P.h[0], (double)P.scale[l]);
   int rc;
-  if ((rc = sf_buf_reserve(c, c->orb_pyr, std::max<size_t>(P.total, 16))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->orb_pyr, std::max<size_t>((size_t)P.total * n_img, 16))) != SF_OK) return rc;
   uint8_t* pyr = (uint8_t*)c->orb_pyr.p;
   for (int l = 1; l < P.n; ++l) {
     const uint8_t* src = l == 1 ? d_image : pyr + P.off[l - 1];
-    hipLaunchKernelGGL(k_orb_resize, dim3((P.w[l] + 63) / 64, (P.h[l] + 3) / 4), dim3(256), 0, c->stream, src, P.w[l - 1],
-                       P.h[l - 1], l == 1 ? pitch : P.w[l - 1], pyr + P.off[l], P.w[l], P.h[l]);
+    hipLaunchKernelGGL(k_orb_resize, dim3((P.w[l] + 63) / 64, (P.h[l] + 3) / 4, n_img), dim3(256), 0, c->stream, src, P.w[l - 1],
+                       P.h[l - 1], l == 1 ? pitch : P.w[l - 1], pyr + P.off[l], P.w[l], P.h[l], l == 1 ? img_stride : (size_t)P.total,
+                       (size_t)P.total);
   }
   SF_HIP(c, hipGetLastError());
   return SF_OK;
+}
+
+// The work lists of both launchers in c->orb_work: `entries` candidates (all images), `kp_entries` keypoints.  Four key
+// arrays serve the seven lists -- a list takes the place of one that nothing reads any more (cand is dead after the first
+// sort, key_b after the second, key_bs after k_orb_cut_b) and no sort runs in place.
+struct OrbLists {
+  unsigned long long *cand, *cand_s, *key_b, *key_bs, *key_c, *key_cs, *fin_key;
+  float *resp, *fin_resp;
+  sf_keypoint *kp1, *kp2;
+};
+static size_t orb_lists_bytes(size_t entries, size_t kp_entries) {
+  return entries * (4 * 8 + 2 * 4) + 2 * ((kp_entries * sizeof(sf_keypoint) + 15) & ~(size_t)15) + 64;
+}
+static int orb_lists(sf_context* c, size_t entries, size_t kp_entries, OrbLists* W) {
+  const size_t kp_bytes = (kp_entries * sizeof(sf_keypoint) + 15) & ~(size_t)15;
+  int rc = sf_buf_reserve(c, c->orb_work, orb_lists_bytes(entries, kp_entries));
+  if (rc != SF_OK) return rc;
+  unsigned long long* a = (unsigned long long*)c->orb_work.p;
+  W->cand = a;                 W->key_b = a;                 W->key_cs = a;
+  W->cand_s = a + entries;
+  W->key_bs = a + 2 * entries; W->key_c = a + 2 * entries;
+  W->fin_key = a + 3 * entries;
+  W->resp = (float*)(a + 4 * entries);
+  W->fin_resp = W->resp + entries;
+  W->kp1 = (sf_keypoint*)(((uintptr_t)(W->fin_resp + entries) + 15) & ~(uintptr_t)15);
+  W->kp2 = (sf_keypoint*)((char*)W->kp1 + kp_bytes);
+  return SF_OK;
+}
+
+static OrbSel orb_selection(const SfOrbPyr& P, int max_features, const sf_orb_detector_params* det, const sf_orb_params* orb) {
+  OrbSel S = {};
+  S.n_levels = P.n; S.score_type = det->score_type; S.edge = orb->edge_threshold; S.max_features = max_features;
+  sf_orb_quotas(max_features, det->scale_factor, det->n_levels, S.quota);
+  return S;
 }
 
 // Launch sequence on the handle's stream.  The per-level corner counts cross to the host once (the sorts are sized by
@@ -350,7 +472,7 @@ int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int h
                          int32_t* n_out) {
   const SfOrbPyr P = sf_orb_pyr_layout(width, height, det->scale_factor, det->n_levels);
   int rc;
-  if ((rc = sf_launch_orb_pyramid(c, d_image, pitch, P)) != SF_OK) return rc;
+  if ((rc = sf_launch_orb_pyramid(c, d_image, pitch, P, 1, 0)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->gf_planes, P.total)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->gf_keys, (size_t)P.total * sizeof(unsigned long long))) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->gf_scalar, (size_t)S_WORDS * 4)) != SF_OK) return rc;
@@ -359,65 +481,150 @@ int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int h
   unsigned long long* keys_f = (unsigned long long*)c->gf_keys.p;
   int* sc = (int*)c->gf_scalar.p;
   SF_HIP(c, hipMemsetAsync(sc, 0, (size_t)S_WORDS * 4, c->stream));
+  OrbBatch B = {};                                     // (n_img 0: one image, the counts on the host)
   for (int l = 0; l < P.n; ++l) {
+    B.key_off[l] = P.off[l];
+    B.key_cap[l] = (unsigned)(P.w[l] * P.h[l]);
     if (P.w[l] < 7 || P.h[l] < 7) continue;            // (no FAST domain)
     sf_launch_fast_level(c, l == 0 ? d_image : pyr + P.off[l], 0, 1, P.w[l], P.h[l], l == 0 ? pitch : P.w[l], det->fast_threshold,
-                         1, score + P.off[l], keys_f + P.off[l], (unsigned*)sc + S_COUNT + l, (unsigned)(P.w[l] * P.h[l]));
+                         1, score + P.off[l], B.key_cap[l], keys_f + P.off[l], (unsigned*)sc + S_COUNT + l, B.key_cap[l]);
   }
   SF_HIP(c, hipGetLastError());
   unsigned h_count[SF_ORB_MAX_LEVELS] = {};
   SF_HIP(c, hipMemcpyAsync(h_count, sc + S_COUNT, sizeof h_count, hipMemcpyDeviceToHost, c->stream));
   SF_HIP(c, hipStreamSynchronize(c->stream));
-  OrbSel S = {};
-  S.n_levels = P.n; S.score_type = det->score_type; S.edge = orb->edge_threshold; S.max_features = max_features;
-  sf_orb_quotas(max_features, det->scale_factor, det->n_levels, S.quota);
+  OrbSel S = orb_selection(P, max_features, det, orb);
   size_t total = 0;
   for (int l = 0; l < SF_ORB_MAX_LEVELS; ++l) {
     S.base[l] = l < P.n ? (unsigned)total : 0xFFFFFFFFu;
-    if (l < P.n) total += std::min(h_count[l], (unsigned)(P.w[l] * P.h[l]));
+    if (l < P.n) total += std::min(h_count[l], B.key_cap[l]);
   }
   if (n_out) *n_out = 0;
   if (total == 0) return SF_OK;
   const unsigned C = (unsigned)total;
   const int cap_tmp = (int)std::min<size_t>(C, (size_t)max_features);
-  // work lists: seven 64-bit key arrays and two float arrays of C entries, two keypoint arrays of cap_tmp
-  const size_t kp_bytes = ((size_t)cap_tmp * sizeof(sf_keypoint) + 15) & ~(size_t)15;
-  if ((rc = sf_buf_reserve(c, c->orb_work, (size_t)C * (7 * 8 + 2 * 4) + 2 * kp_bytes + 64)) != SF_OK) return rc;
-  unsigned long long* cand = (unsigned long long*)c->orb_work.p;
-  unsigned long long *cand_s = cand + C, *key_b = cand_s + C, *key_bs = key_b + C, *key_c = key_bs + C, *key_cs = key_c + C,
-                     *fin_key = key_cs + C;
-  float* resp = (float*)(fin_key + C);
-  float* fin_resp = resp + C;
-  sf_keypoint* kp1 = (sf_keypoint*)(((uintptr_t)(fin_resp + C) + 15) & ~(uintptr_t)15);
-  sf_keypoint* kp2 = (sf_keypoint*)((char*)kp1 + kp_bytes);
+  OrbLists W;
+  if ((rc = orb_lists(c, C, (size_t)cap_tmp, &W)) != SF_OK) return rc;
   const dim3 block(256), grid((C + 255) / 256);
-  hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, C, cand, sc);
-  hipLaunchKernelGGL(k_orb_cut_a, dim3(1), dim3(64), 0, c->stream, S, sc);
-  hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, cand, C, (const int*)sc);
+  hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, C, W.cand, sc, B);
+  hipLaunchKernelGGL(k_orb_cut_a, dim3(1), dim3(64), 0, c->stream, S, sc, B);
+  hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, W.cand, C, (const int*)sc, B);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys(c, cand, cand_s, C, 8, 44, false)) != SF_OK) return rc;
+  if ((rc = sf_sort_keys(c, W.cand, W.cand_s, C, 8, 44, false)) != SF_OK) return rc;
   if (det->score_type == 0) {
     hipLaunchKernelGGL(k_orb_harris, dim3((C + 3) / 4), block, 0, c->stream, d_image, pitch, pyr, P,
-                       (const unsigned long long*)cand_s, (const int*)sc, C, resp, key_b);
+                       (const unsigned long long*)W.cand_s, (const int*)sc, C, W.resp, W.key_b, B);
     SF_HIP(c, hipGetLastError());
-    if ((rc = sf_sort_keys(c, key_b, key_bs, C, 0, 36, false)) != SF_OK) return rc;
+    if ((rc = sf_sort_keys(c, W.key_b, W.key_bs, C, 0, 36, false)) != SF_OK) return rc;
   }
-  hipLaunchKernelGGL(k_orb_cut_b, dim3(1), dim3(64), 0, c->stream, S, (const unsigned long long*)key_bs, sc);
-  hipLaunchKernelGGL(k_orb_compact, dim3(1), block, 0, c->stream, S, (const unsigned long long*)cand_s, (const float*)resp, C,
-                     fin_key, fin_resp, key_c, sc);
+  hipLaunchKernelGGL(k_orb_cut_b, dim3(1), dim3(64), 0, c->stream, S, (const unsigned long long*)W.key_bs, sc, B);
+  hipLaunchKernelGGL(k_orb_compact, dim3(1), block, 0, c->stream, S, (const unsigned long long*)W.cand_s, (const float*)W.resp, C,
+                     W.fin_key, W.fin_resp, W.key_c, sc, B);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys(c, key_c, key_cs, C, 0, 64, true)) != SF_OK) return rc;
+  if ((rc = sf_sort_keys(c, W.key_c, W.key_cs, C, 0, 64, true)) != SF_OK) return rc;
   const dim3 grid_kp((cap_tmp + 255) / 256);
-  hipLaunchKernelGGL(k_orb_emit, grid_kp, block, 0, c->stream, P, (const unsigned long long*)key_cs,
-                     (const unsigned long long*)fin_key, (const float*)fin_resp, (const int*)sc, cap_tmp, kp1);
+  hipLaunchKernelGGL(k_orb_emit, grid_kp, block, 0, c->stream, P, (const unsigned long long*)W.key_cs,
+                     (const unsigned long long*)W.fin_key, (const float*)W.fin_resp, (const int*)sc, cap_tmp, W.kp1, B);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sf_launch_orb_angle_levels(c, d_image, pitch, P, kp1, cap_tmp, (const int32_t*)(sc + S_NFINAL), orb->edge_threshold,
-                                       kp2)) != SF_OK)
+  if ((rc = sf_launch_orb_angle_levels(c, d_image, 0, 1, pitch, P, 0, W.kp1, cap_tmp, (const int32_t*)(sc + S_NFINAL),
+                                       orb->edge_threshold, W.kp2)) != SF_OK)
     return rc;
   const int written = std::min(cap_tmp, cap);
   if (written > 0)
-    hipLaunchKernelGGL(k_orb_finish, dim3((written + 255) / 256), block, 0, c->stream, P, (const sf_keypoint*)kp2,
-                       (const int*)sc, written, d_kpts_out);
+    hipLaunchKernelGGL(k_orb_finish, dim3((written + 255) / 256), block, 0, c->stream, P, (const sf_keypoint*)W.kp2,
+                       (const int*)sc, written, d_kpts_out, B, 0);
   SF_HIP(c, hipGetLastError());
   return n_out ? sf_word_to_host(c, sc + S_NFINAL, n_out) : SF_OK;
+}
+
+// What sf_launch_detect_orb_batch keeps on the device for n_img images, from the image size, n_img and max_features alone
+// (a level of w x h pixels holds at most ceil(w / 2) ceil(h / 2) strict 3 x 3 maxima):
+//   c->orb_pyr     P.total bytes per image            the pyramid (the extraction reuses it)
+//   c->gf_planes   P.total bytes per image            FAST score planes
+//   c->gf_keys     8 bytes per candidate              FAST keys, level by level
+//   c->orb_work    40 bytes per candidate + 2 x 28 bytes per keypoint (min(candidates, max_features) per image)
+//   c->gf_scalar   S_WORDS + 8 + 6 words per image    scalar blocks, FAST counts, segment bounds
+static unsigned orb_level_cap(const SfOrbPyr& P, int l) { return (unsigned)(((P.w[l] + 1) / 2) * ((P.h[l] + 1) / 2)); }
+
+// The detector on a batch of images of one size, no host round trip (see the head of the file).  d_kpts_out [n_img][cap],
+// d_n_out [n_img] (device): the keypoints of every image in the single call's order, their number (which `cap` does not
+// clip).  max_features >= 1.
+int sf_launch_detect_orb_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                               int pitch, int max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
+                               sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out) {
+  const SfOrbPyr P = sf_orb_pyr_layout(width, height, det->scale_factor, det->n_levels);
+  int rc;
+  if (n_img < 1 || n_img > 65535) return sf_fail(c, SF_ERANGE, "ORB batch of %d images (1 .. 65535)", n_img);
+  if ((rc = sf_launch_orb_pyramid(c, d_images, pitch, P, n_img, img_stride)) != SF_OK) return rc;
+  OrbBatch B = {};
+  B.img_stride = img_stride; B.pyr_stride = P.total; B.n_img = n_img; B.n_out = d_n_out;
+  size_t per_image = 0;
+  for (int l = 0; l < P.n; ++l) {
+    B.key_cap[l] = orb_level_cap(P, l);
+    per_image += B.key_cap[l];
+  }
+  const size_t entries = per_image * n_img;
+  if (entries > 0xFFFFFFFFull) return sf_fail(c, SF_ERANGE, "ORB batch: %d images of up to %zu candidates", n_img, per_image);
+  B.cand_cap = (unsigned)per_image;
+  for (int l = 0, run = 0; l < P.n; ++l) {
+    B.key_off[l] = (unsigned)run * (unsigned)n_img;
+    run += (int)B.key_cap[l];
+  }
+  const int cap_tmp = (int)std::min<size_t>(per_image, (size_t)max_features);
+  B.kp_cap = cap_tmp;
+  const size_t sc_words = (size_t)n_img * (S_WORDS + SF_ORB_MAX_LEVELS + 6);
+  if ((rc = sf_buf_reserve(c, c->gf_planes, (size_t)P.total * n_img)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_keys, entries * sizeof(unsigned long long))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_scalar, sc_words * 4)) != SF_OK) return rc;
+  OrbLists W;
+  if ((rc = orb_lists(c, entries, (size_t)cap_tmp * n_img, &W)) != SF_OK) return rc;
+  const uint8_t* pyr = (const uint8_t*)c->orb_pyr.p;
+  uint8_t* score = (uint8_t*)c->gf_planes.p;
+  unsigned long long* keys_f = (unsigned long long*)c->gf_keys.p;
+  int* sc = (int*)c->gf_scalar.p;
+  unsigned* count = (unsigned*)(sc + (size_t)n_img * S_WORDS);
+  B.d_count = count;
+  B.seg = count + (size_t)n_img * SF_ORB_MAX_LEVELS;
+  // histograms, counts and bounds of the call before are gone before the first kernel reads them
+  SF_HIP(c, hipMemsetAsync(sc, 0, sc_words * 4, c->stream));
+  for (int l = 0; l < P.n; ++l) {
+    if (P.w[l] < 7 || P.h[l] < 7) continue;            // (no FAST domain)
+    sf_launch_fast_level(c, l == 0 ? d_images : pyr + P.off[l], l == 0 ? img_stride : (size_t)P.total, n_img, P.w[l], P.h[l],
+                         l == 0 ? pitch : P.w[l], det->fast_threshold, 1, score + P.off[l], (size_t)P.total, keys_f + B.key_off[l],
+                         count + (size_t)l * n_img, B.key_cap[l]);
+  }
+  SF_HIP(c, hipGetLastError());
+  const OrbSel S = orb_selection(P, max_features, det, orb);
+  const unsigned n = (unsigned)n_img, cap_all = (unsigned)entries;
+  const dim3 block(256), grid((B.cand_cap + 255) / 256, n);
+  hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, 0u, W.cand, sc, B);
+  hipLaunchKernelGGL(k_orb_cut_a, dim3(n), dim3(64), 0, c->stream, S, sc, B);
+  hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, W.cand, 0u, (const int*)sc, B);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sf_sort_keys_segmented(c, W.cand, W.cand_s, cap_all, n, B.seg, B.seg + n, 8, 44, false)) != SF_OK) return rc;
+  if (det->score_type == 0) {
+    const unsigned blocks = std::min((B.cand_cap + 3) / 4, (unsigned)ORB_HARRIS_BLOCKS);
+    hipLaunchKernelGGL(k_orb_harris, dim3(blocks, n), block, 0, c->stream, d_images, pitch, pyr, P,
+                       (const unsigned long long*)W.cand_s, (const int*)sc, 0u, W.resp, W.key_b, B);
+    SF_HIP(c, hipGetLastError());
+    if ((rc = sf_sort_keys_segmented(c, W.key_b, W.key_bs, cap_all, n, B.seg + 2 * n, B.seg + 3 * n, 0, 36, false)) != SF_OK)
+      return rc;
+  }
+  hipLaunchKernelGGL(k_orb_cut_b, dim3(n), dim3(64), 0, c->stream, S, (const unsigned long long*)W.key_bs, sc, B);
+  hipLaunchKernelGGL(k_orb_compact, dim3(n), block, 0, c->stream, S, (const unsigned long long*)W.cand_s, (const float*)W.resp, 0u,
+                     W.fin_key, W.fin_resp, W.key_c, sc, B);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sf_sort_keys_segmented(c, W.key_c, W.key_cs, cap_all, n, B.seg + 4 * n, B.seg + 5 * n, 0, 64, true)) != SF_OK) return rc;
+  hipLaunchKernelGGL(k_orb_emit, dim3((cap_tmp + 255) / 256, n), block, 0, c->stream, P, (const unsigned long long*)W.key_cs,
+                     (const unsigned long long*)W.fin_key, (const float*)W.fin_resp, (const int*)sc, cap_tmp, W.kp1, B);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sf_launch_orb_angle_levels(c, d_images, img_stride, n_img, pitch, P, P.total, W.kp1, cap_tmp, d_n_out,
+                                       orb->edge_threshold, W.kp2)) != SF_OK)
+    return rc;
+  const int written = std::min(cap_tmp, cap);
+  if (written > 0)
+    hipLaunchKernelGGL(k_orb_finish, dim3((written + 255) / 256, n), block, 0, c->stream, P, (const sf_keypoint*)W.kp2,
+                       (const int*)sc, written, d_kpts_out, B, cap);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
 }

@@ -263,11 +263,11 @@ static int extract_kind(sf_context* c, ExtractKind* k) {
   if (c->feature_type == 8 || c->feature_type == 2) {
     if ((rc = check_binary_rows(c, c->feature_type)) != SF_OK) return rc;
     if ((rc = orb_ensure(c)) != SF_OK) return rc;
-    *k = {32, (const int8_t*)c->orb_tests.p, &c->orb, c->feature_type == 2 ? &c->orb_det : nullptr};
+    *k = {32, (const int8_t*)c->orb_tests.p, &c->orb, c->feature_type == 2 ? &c->orb_det : nullptr, 0};
     return SF_OK;
   }
   if ((rc = brief_ensure(c)) != SF_OK) return rc;
-  *k = {c->brief_bytes, (const int8_t*)c->brief_tests.p, nullptr, nullptr};
+  *k = {c->brief_bytes, (const int8_t*)c->brief_tests.p, nullptr, nullptr, 0};
   return SF_OK;
 }
 
@@ -512,19 +512,23 @@ extern "C" int sf_get_features_and_descriptor_u8(sf_handle c, const uint8_t* lef
 // n keyframes from device images to n store slots in ONE launch sequence: detector, stereo correspondence and
 // extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
 // host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.
-// The batch form in three parts, shared by sf_get_features_and_descriptor_batch_device and
-// sf_add_keyframes_u8_batch_device: batch_check refuses (nothing is touched; n_keyframes = 0 passes without a look at the
-// images), batch_reserve takes the store slots and the call's buffers, batch_launch queues the three stages.
+// The batch form in three parts, shared by sf_get_features_and_descriptor_batch_device, sf_add_keyframes_u8_batch_device
+// and their Vis/FeatureType 2 twins (the _orb_ calls; `orb_call`): batch_check refuses (nothing is touched;
+// n_keyframes = 0 passes without a look at the images), batch_reserve takes the store slots and the call's buffers,
+// batch_launch queues the three stages.  Type 2 is reached through its own calls only, as it is selected through its own.
 struct BatchPlan {
   sf_detector_params dp;
   sf_stereo_flow_params prm;
   ExtractKind kind;
 };
 
-static int batch_check(sf_context* c, bool images, int n_keyframes, int width, int height, int pitch, size_t image_stride,
-                       const sf_detector_params* det, const sf_stereo_flow_params* flow, BatchPlan* plan) {
-  if (c->feature_type == 2)
-    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has no batch form yet: use sf_get_features_and_descriptor per keyframe");
+static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframes, int width, int height, int pitch,
+                       size_t image_stride, const sf_detector_params* det, const sf_stereo_flow_params* flow, BatchPlan* plan) {
+  if (c->feature_type == 2 && !orb_call)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has batch forms of its own: sf_get_features_and_descriptor_orb_batch_device, sf_add_keyframes_orb_u8_batch_device");
+  if (c->feature_type != 2 && orb_call)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the ORB batch calls need type 2 (sf_set_feature_type_orb); use sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device",
+                   c->feature_type);
   if (n_keyframes == 0) return SF_OK;
   int rc = check_image(c, images, width, height, pitch, 3, "stereo pairs");
   if (rc != SF_OK) return rc;
@@ -540,6 +544,15 @@ static int batch_check(sf_context* c, bool images, int n_keyframes, int width, i
       prm.max_level > 15 || !(prm.epsilon == prm.epsilon))
     return sf_fail(c, SF_EINVAL, "stereo flow parameters out of range (see sf_stereo_correspondences_device)");
   if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
+  if (orb_call) {                                        // what sf_detect_orb_device refuses
+    if ((rc = orb_detector_validate(c, c->orb_det, c->orb)) != SF_OK) return rc;
+    if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
+    if (n_keyframes > 65535) return sf_fail(c, SF_ERANGE, "ORB batch of %d keyframes (at most 65535)", n_keyframes);
+    const SfOrbPyr P = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels);
+    for (int l = 0; l < P.n; ++l)
+      if (P.w[l] < 1 || P.h[l] < 1)
+        return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, width, height, (double)P.scale[l]);
+  }
   return SF_OK;
 }
 
@@ -566,7 +579,11 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   int rc;
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t* d_n = (int32_t*)c->ft_counts.p;
-  if (c->feature_type == 4) {
+  ExtractKind kind = plan.kind;
+  if (c->feature_type == 2) {                            // (keypoints in level-0 coordinates; the pyramids stay for the extraction)
+    rc = sf_launch_detect_orb_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
+    kind.pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;
+  } else if (c->feature_type == 4) {
     rc = sf_launch_detect_fast_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
   } else {
     rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
@@ -580,12 +597,26 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
                                         d_xy, d_status, d_rx, nullptr)) != SF_OK)
     return rc;
   const int slot = c->store.slots;
-  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, plan.kind,
+  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, kind,
                                     slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out)) != SF_OK)
     return rc;
   c->store.slots += n;
   if (first_slot_out) *first_slot_out = slot;
   return SF_OK;
+}
+
+static int features_batch(sf_context* c, bool orb_call, const uint8_t* d_left, const uint8_t* d_right, int32_t n_keyframes,
+                          int32_t width, int32_t height, int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                          const sf_detector_params* det, const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                          int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  BatchPlan plan;
+  int rc = batch_check(c, orb_call, d_left && d_right, n_keyframes, width, height, pitch, image_stride, det, flow, &plan);
+  if (rc != SF_OK) return rc;
+  if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
+  if ((rc = batch_reserve(c, n_keyframes, width, height, &plan)) != SF_OK) return rc;
+  return batch_launch(c, plan, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, first_slot_out, d_rows_out,
+                      d_desc_out, d_xyz_out, d_kpts_out);
 }
 
 extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
@@ -594,14 +625,19 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
                                                            const sf_detector_params* det, const sf_stereo_flow_params* flow,
                                                            int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                            float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
-  BatchPlan plan;
-  int rc = batch_check(c, d_left && d_right, n_keyframes, width, height, pitch, image_stride, det, flow, &plan);
-  if (rc != SF_OK) return rc;
-  if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
-  if ((rc = batch_reserve(c, n_keyframes, width, height, &plan)) != SF_OK) return rc;
-  return batch_launch(c, plan, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, first_slot_out, d_rows_out,
-                      d_desc_out, d_xyz_out, d_kpts_out);
+  return features_batch(c, false, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_orb_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                               int32_t n_keyframes, int32_t width, int32_t height,
+                                                               int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                                                               const sf_detector_params* det,
+                                                               const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                               int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
+                                                               sf_keypoint* d_kpts_out) {
+  return features_batch(c, true, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
 // ---- the camera's own images (kernels in k_image.hip, k_cnn.hip) ---------------------------------------------------
@@ -658,13 +694,11 @@ extern "C" int sf_netvlad_infer_u8_batch_device(sf_handle c, const uint8_t* d_im
 // images (one launch), the network on the colour images, the batch feature stages on the planes, the descriptors' prefix
 // into the local NN rows.  Everything that can refuse does so before the first launch; the store and the NN database
 // grow last, together.
-extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
-                                                const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
-                                                int32_t height, int32_t pitch, size_t image_stride,
-                                                const sf_stereo_camera* cam, const sf_detector_params* det,
-                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
-                                                int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
-                                                float* d_xyz_out, sf_keypoint* d_kpts_out) {
+static int add_keyframes_batch(sf_context* c, bool orb_call, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+                               int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                               size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
+                               const sf_stereo_flow_params* flow, int32_t* first_slot_out, int32_t* first_nn_row_out,
+                               int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
   const int n = n_keyframes;
   int rc;
@@ -678,7 +712,7 @@ extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_le
   const int g_pitch = n > 0 ? (width + 15) & ~15 : 0;
   const size_t g_stride = ((size_t)g_pitch * (n > 0 ? height : 0) + 255) & ~(size_t)255;
   BatchPlan plan;
-  if ((rc = batch_check(c, true, n, width, height, g_pitch, g_stride, det, flow, &plan)) != SF_OK) return rc;
+  if ((rc = batch_check(c, orb_call, true, n, width, height, g_pitch, g_stride, det, flow, &plan)) != SF_OK) return rc;
   if (n == 0) {
     if (first_slot_out) *first_slot_out = c->store.slots;
     if (first_nn_row_out) *first_nn_row_out = c->nn_local.n;
@@ -713,4 +747,26 @@ extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_le
   if (first_slot_out) *first_slot_out = slot;
   if (first_nn_row_out) *first_nn_row_out = row;
   return SF_OK;
+}
+
+extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                int32_t height, int32_t pitch, size_t image_stride,
+                                                const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, false, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_add_keyframes_orb_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                    const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                    int32_t height, int32_t pitch, size_t image_stride,
+                                                    const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                    const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                    int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                    float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, true, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }

@@ -592,9 +592,13 @@ size_t sf_guided_lds_bytes(int kcap, int n_cells, bool narrow = false);   // nar
 void sf_brief_default_pattern(int8_t* tests, int bytes);
 void sf_orb_default_pattern(int8_t* tests);     // [256][4]: 32-byte ORB rows
 // The detectors' one library call (sf_sort.hip): radix sort of 64-bit keys by bits [bit0, bit1) on the handle's stream,
-// temporary storage in c->gf_tmp.  The segmented form sorts every [d_begin[s], d_end[s]) on its own, descending.
+// temporary storage in c->gf_tmp.  The segmented forms sort every [d_begin[s], d_end[s]) on its own, the bounds read on the
+// device.
 int sf_sort_keys(sf_context* c, const unsigned long long* in, unsigned long long* out, size_t n, unsigned bit0, unsigned bit1,
                  bool descending);
+int sf_sort_keys_segmented(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
+                           unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0, unsigned bit1,
+                           bool descending);
 int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
                                 unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0,
                                 unsigned bit1);
@@ -606,12 +610,15 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
                                 const sf_stereo_flow_params* prm, float* d_right_xy, uint8_t* d_status, float* d_right_x,
                                 float* d_err);
 // The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF rows, else ORB
-// rows), the pyramid of ORB (NULL: one level; else ORB rows on the keypoint's own level, type 2)
+// rows), the pyramid of ORB (NULL: one level; else ORB rows on the keypoint's own level, type 2).  pyr_stride 0: the
+// extraction builds the pyramid of its one image; else sf_launch_detect_orb_batch has left the pyramids of the call's
+// images in c->orb_pyr, pyr_stride bytes apart, and the extraction reads them there
 struct ExtractKind {
   int bytes;
   const int8_t* d_tests;
   const sf_orb_params* orb;
   const sf_orb_detector_params* pyr;
+  size_t pyr_stride;
 };
 // keyframes into the slots of c->store from `slot` on (k_extract.hip); one keyframe: img_stride 0, n_img 1, d_n null
 int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_stride, int n_img, int width, int height,
@@ -627,20 +634,30 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
                                 int32_t* d_n_out);
-// one level of FAST on n_img images img_stride bytes apart: k_fast_score + k_fast_candidates (image i: score plane and keys
-// at + i * key_cap, keys = score << 32 | pixel index in arrival order, count[i] the corners found; zeroed by the caller)
+// one level of FAST on n_img images img_stride bytes apart: k_fast_score + k_fast_candidates (image i: score plane at
+// + i * plane_stride, keys at + i * key_cap, keys = score << 32 | pixel index in arrival order, count[i] the corners found;
+// zeroed by the caller)
 void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
-                          int threshold, int nonmax, uint8_t* score, unsigned long long* keys, unsigned* count, unsigned key_cap);
+                          int threshold, int nonmax, uint8_t* score, size_t plane_stride, unsigned long long* keys, unsigned* count,
+                          unsigned key_cap);
 // ORB detector (k_orb_detect.hip); det / orb validated by the caller
 SfOrbPyr sf_orb_pyr_layout(int width, int height, float scale_factor, int n_levels);
 void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota);
-int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P);   // levels >= 1 into c->orb_pyr
+// levels >= 1 of n_img images (img_stride bytes apart) into c->orb_pyr, image i's at + i * P.total
+int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P, int n_img, size_t img_stride);
 int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
                          const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out, int cap,
                          int32_t* n_out);
-// k_orb_angle (k_extract.hip) on keypoints in LEVEL coordinates whose octave names their level; n read on the device
-int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P, const sf_keypoint* d_kpts,
-                               int n_max, const int32_t* d_n, int edge, sf_keypoint* d_kpts_out);
+// the same on n_img images of one size with no host round trip: d_kpts_out [n_img][cap], d_n_out [n_img] on the device; the
+// pyramids stay in c->orb_pyr (P.total bytes apart) for the extraction
+int sf_launch_detect_orb_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                               int pitch, int max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
+                               sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out);
+// k_orb_angle (k_extract.hip) on keypoints in LEVEL coordinates whose octave names their level: n_img images img_stride
+// apart, their pyramids pyr_stride apart in c->orb_pyr, n_max keypoints apiece, d_n [n_img] read on the device
+int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int pitch, const SfOrbPyr& P,
+                               size_t pyr_stride, const sf_keypoint* d_kpts, int n_max, const int32_t* d_n, int edge,
+                               sf_keypoint* d_kpts_out);
 int sf_launch_stereo_flow(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, int width, int height, int pitch,
                           const sf_keypoint* d_kpts, int n, const sf_stereo_flow_params* prm, float* d_right_xy,
                           uint8_t* d_status, float* d_right_x, float* d_err);

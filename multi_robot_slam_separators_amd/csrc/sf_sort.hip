@@ -1,6 +1,6 @@
 // sf_sort.hip -- the one library call of the product's compute path: rocprim's radix sort of 64-bit keys, for the
 // detectors of the feature front end (k_gftt.hip, k_fast.hip, k_orb_detect.hip).  This is the only translation unit that
-// includes rocprim, so its sort kernels are compiled once.  Both functions size the temporary storage, keep it in
+// includes rocprim, so its sort kernels are compiled once.  All functions size the temporary storage, keep it in
 // c->gf_tmp and sort on the handle's stream; the keys are integers, so the file needs no floating-point flags.
 #include <hip/hip_runtime.h>
 
@@ -32,12 +32,21 @@ int sf_sort_keys(sf_context* c, const unsigned long long* in, unsigned long long
   });
 }
 
-// every segment [d_begin[s], d_end[s]) of the n_total keys on its own, descending; the bounds are read on the device
+// every segment [d_begin[s], d_end[s]) of the n_total keys on its own, ascending or descending; the bounds are read on the
+// device, keys outside every segment are neither read nor written
+int sf_sort_keys_segmented(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
+                           unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0, unsigned bit1,
+                           bool descending) {
+  return sort_with_tmp(c, [&](void* tmp, size_t& tmp_bytes) {
+    return descending ? rocprim::segmented_radix_sort_keys_desc(tmp, tmp_bytes, in, out, n_total, n_segments, d_begin, d_end,
+                                                                bit0, bit1, c->stream)
+                      : rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, in, out, n_total, n_segments, d_begin, d_end, bit0,
+                                                           bit1, c->stream);
+  });
+}
+
 int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
                                 unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0,
                                 unsigned bit1) {
-  return sort_with_tmp(c, [&](void* tmp, size_t& tmp_bytes) {
-    return rocprim::segmented_radix_sort_keys_desc(tmp, tmp_bytes, in, out, n_total, n_segments, d_begin, d_end, bit0, bit1,
-                                                   c->stream);
-  });
+  return sf_sort_keys_segmented(c, in, out, n_total, n_segments, d_begin, d_end, bit0, bit1, true);
 }

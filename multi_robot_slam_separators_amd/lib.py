@@ -163,6 +163,9 @@ def load():
         "sf_prof_get": (C.c_int, [vp, C.c_int, P(i64), P(C.c_double)]),
         "sf_kernel_name": (C.c_char_p, [C.c_int]),
     }
+    # the batch forms of Vis/FeatureType 2: the argument lists of their generic twins
+    sig["sf_get_features_and_descriptor_orb_batch_device"] = sig["sf_get_features_and_descriptor_batch_device"]
+    sig["sf_add_keyframes_orb_u8_batch_device"] = sig["sf_add_keyframes_u8_batch_device"]
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export the ABI
         fn.restype = res
@@ -196,6 +199,7 @@ EXPORTED = [
     "sf_orb_detector_defaults", "sf_set_feature_type_orb", "sf_get_orb_detector", "sf_detect_orb_device",
     "sf_image_set_gray_rule", "sf_image_get_gray_rule", "sf_image_to_gray_device", "sf_netvlad_infer_u8_batch_device",
     "sf_get_features_and_descriptor_u8", "sf_add_keyframes_u8_batch_device",
+    "sf_get_features_and_descriptor_orb_batch_device", "sf_add_keyframes_orb_u8_batch_device",
 ]
 
 
@@ -519,16 +523,21 @@ class SeparatorFinder:
 
     def add_keyframes_u8_batch_device(self, d_left, d_right, d_rgb, fmt, n_keyframes, width, height, pitch, image_stride,
                                       cam, det=None, flow=None, d_rows_out=None, d_desc_out=None, d_xyz_out=None,
-                                      d_kpts_out=None):
+                                      d_kpts_out=None, _call="sf_add_keyframes_u8_batch_device"):
         """n keyframes from the camera's device images (raw pointers; d_rgb None = the left images) to n store slots and n
         local NN rows in one launch sequence, no host wait.  Returns (first slot, first local NN row)."""
         first, row = C.c_int32(-1), C.c_int32(-1)
-        self._check(self._L.sf_add_keyframes_u8_batch_device(
+        self._check(getattr(self._L, _call)(
             self._h, C.c_void_p(d_left), C.c_void_p(d_right), C.c_void_p(d_rgb), int(fmt), n_keyframes, width, height,
             pitch, int(image_stride), C.byref(cam), C.byref(det) if det is not None else None,
             C.byref(flow) if flow is not None else None, C.byref(first), C.byref(row), C.c_void_p(d_rows_out),
             C.c_void_p(d_desc_out), C.c_void_p(d_xyz_out), C.c_void_p(d_kpts_out)))
         return first.value, row.value
+
+    def add_keyframes_orb_u8_batch_device(self, *args, **kw):
+        """add_keyframes_u8_batch_device on a handle of Vis/FeatureType 2 (set_feature_type_orb): same arguments, same
+        return value; slot i holds what get_features_and_descriptor_u8 gives for pair i."""
+        return self.add_keyframes_u8_batch_device(*args, _call="sf_add_keyframes_orb_u8_batch_device", **kw)
 
     def set_feature_type_orb(self, det=None, orb=None):
         """Vis/FeatureType 2, ORB on a pyramid: det (_abi.OrbDetectorParams; None = rtabmap's ORB/ defaults) drives the
@@ -609,15 +618,22 @@ class SeparatorFinder:
 
     def get_features_and_descriptor_batch_device(self, d_left, d_right, n_keyframes, width, height, pitch, image_stride,
                                                  cam, det=None, flow=None, d_rows_out=None, d_desc_out=None,
-                                                 d_xyz_out=None, d_kpts_out=None):
+                                                 d_xyz_out=None, d_kpts_out=None,
+                                                 _call="sf_get_features_and_descriptor_batch_device"):
         """n keyframes from device images (raw pointers) to n store slots in one launch sequence, no host wait; optional
         device outputs sized for n_keyframes x max_features rows.  Returns the first slot."""
         first = C.c_int32()
-        self._check(self._L.sf_get_features_and_descriptor_batch_device(
+        self._check(getattr(self._L, _call)(
             self._h, C.c_void_p(d_left), C.c_void_p(d_right), n_keyframes, width, height, pitch, int(image_stride),
             C.byref(cam), C.byref(det) if det is not None else None, C.byref(flow) if flow is not None else None,
             C.byref(first), C.c_void_p(d_rows_out), C.c_void_p(d_desc_out), C.c_void_p(d_xyz_out), C.c_void_p(d_kpts_out)))
         return first.value
+
+    def get_features_and_descriptor_orb_batch_device(self, *args, **kw):
+        """get_features_and_descriptor_batch_device on a handle of Vis/FeatureType 2 (set_feature_type_orb): same arguments,
+        same return value; per keyframe the bytes of get_features_and_descriptor under type 2."""
+        return self.get_features_and_descriptor_batch_device(*args, _call="sf_get_features_and_descriptor_orb_batch_device",
+                                                             **kw)
 
     def extract_keyframe_device(self, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam,
                                 d_desc_out=None, d_xyz_out=None, d_kpts_out=None, want_rows=True):
