@@ -73,6 +73,9 @@ extern "C" {
 /* 8, additions: sf_get_features_and_descriptor_orb_batch_device, sf_add_keyframes_orb_u8_batch_device (the batch forms of
       Vis/FeatureType 2).  The generic batch calls still refuse a type-2 handle, with a message that now names these two;
       nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.                            */
+/* 8, additions: sf_front_params, sf_front_defaults, sf_front_set_params, sf_front_get_params, sf_compute_roi,
+      sf_corner_subpix_device (Vis/RoiRatios and the Vis/SubPix* refinement around every detector).  Both steps are off on
+      a fresh handle; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.             */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -465,6 +468,50 @@ int  sf_get_orb_detector(sf_handle h, sf_orb_detector_params* out);
 int  sf_detect_orb_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                           int32_t max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
                           sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
+/* The two steps rtabmap's Feature2D::generateKeypoints puts around every detector, whatever the feature type
+   [upstream rtabmap / OpenCV 3.2, restated in tests/subpix_ref.py; DESIGN.md section 3 item 17d lists what the restatement
+   decides].  The reference reaches that function at myRegistrationVis.cpp:282 and leaves both steps off (INTEGRATION.md
+   section 12), and so does a fresh handle.
+   ROI, Vis/RoiRatios {left, right, top, bottom}, each in [0, 1]: the detector is handed the sub-image
+     x = 0; if (r0 > 0 && r0 < 1 - r1) x = (int)(W * r0);   w = W - x; if (r1 > 0 && r1 < 1 - r0) w = (int)((float)w - W * r1);
+   (y, h alike from r2, r3, H; float arithmetic, truncating) as an image of its own -- pointer at its first pixel, its
+   size, the parent's pitch -- and every keypoint is shifted back by (x, y).  The result equals a detection on a copy of the
+   crop plus the offset: upstream's behaviour for FAST and ORB; for GFTT upstream's Sobel reads the parent's pixels
+   across an interior ROI edge, which this does not (a listed deviation).  A ROI with a side below 3: SF_EINVAL.
+   NOT built: a ROI under feature type 2 -- its batch form reuses the detector's pyramid for the descriptors, and a ROI
+   would need a second pyramid; the extraction calls on a type-2 handle with any ratio != 0 return SF_EINVAL, say so
+   and change nothing.
+   Refinement, Vis/SubPixWinSize / Vis/SubPixIterations / Vis/SubPixEps: when subpix_win_size > 0 and
+   subpix_iterations > 0, cv::cornerSubPix(image, pts, Size(win, win), Size(-1, -1), {COUNT + EPS, iterations, eps}) moves
+   the kept keypoints on the FULL image; only x and y change.  Stereo correspondence, 3D points, the border filters
+   and the descriptors see the refined positions.  Under type 2 the positions are level-0 coordinates.
+   Both steps sit between the detector and the stereo correspondence of sf_get_features_and_descriptor, its _u8 form,
+   sf_get_features_and_descriptor_batch_device, sf_add_keyframes_u8_batch_device and the two _orb_ batch calls (the batch
+   forms stay one launch sequence with no host wait); with refinement on these calls need width, height >= 2 win + 5.
+   The explicit sf_detect_*_device calls are untouched: their caller passes a sub-image itself.                      */
+typedef struct sf_front_params {
+  float   roi_ratios[4];      /* Vis/RoiRatios "0.0 0.0 0.0 0.0": left, right, top, bottom; each in [0, 1]        */
+  int32_t subpix_win_size;    /* Vis/SubPixWinSize, 3; 0 .. 15, 0 = no refinement                                  */
+  int32_t subpix_iterations;  /* Vis/SubPixIterations, 0 = no refinement; >= 0, clamped to 100 like cv::TermCriteria */
+  float   subpix_eps;         /* Vis/SubPixEps, 0.02; compared squared with |step|^2, negative values count as 0     */
+} sf_front_params;            /* 28 bytes */
+void sf_front_defaults(sf_front_params* p);
+/* The handle's parameters; out-of-range values (a ratio outside [0, 1] or NaN, win outside 0 .. 15, negative
+   iterations, NaN eps) return SF_EINVAL and change nothing.                                                        */
+int  sf_front_set_params(sf_handle h, const sf_front_params* params);
+int  sf_front_get_params(sf_handle h, sf_front_params* params);
+/* Feature2D::computeRoi as above, pure host code: roi_xywh = {x, y, width, height}.  SF_EINVAL for a ratio outside
+   [0, 1], an image side < 1 or a ROI side < 3 (the rectangle is written whenever the ratios are valid).             */
+int  sf_compute_roi(int32_t width, int32_t height, const float ratios[4], int32_t roi_xywh[4]);
+/* cv::cornerSubPix on n keypoints of a device image, in place and asynchronous on the handle's stream; writes only x and
+   y of each 28-byte record.  Per corner, from c = c0: the (2 win + 3)^2 float patch of cv::getRectSubPix around c
+   (bilinear, taps outside the image clamped to the edge), central differences, the separable Gaussian mask
+   exp(-(k - win)^2 / win^2) (evaluated on the host), five double sums over the (2 win + 1)^2 window in raster order, the 2 x 2
+   solve; stops when |det| <= DBL_EPSILON^2, when c leaves the image, after clamp(iterations, 1, 100) steps or when a
+   step's squared length is <= max(eps, 0)^2; a corner that moved more than win in x or y returns to c0.
+   win 1 .. 15, iterations >= 1, width and height >= 2 win + 5 (OpenCV asserts this), else SF_EINVAL; n = 0 is SF_OK.     */
+int  sf_corner_subpix_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                             sf_keypoint* d_kpts, int32_t n, int32_t win, int32_t iterations, float eps);
 /* Stereo correspondence of the corners: replaces Feature2D::generateKeypoints3D's call of
    StereoOpticalFlow::computeCorrespondences [upstream rtabmap] behind myRegistrationVis.cpp:382 --
    cv::calcOpticalFlowPyrLK(left, right, corners, winSize, maxLevel, {COUNT + EPS, iterations, epsilon},

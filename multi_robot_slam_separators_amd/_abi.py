@@ -158,6 +158,50 @@ def fast_params(threshold=20, nonmax_suppression=1):
     return p
 
 
+class FrontParams(C.Structure):
+    """sf_front_params (include/sepfinder.h): what rtabmap's Feature2D::generateKeypoints puts around every detector --
+    Vis/RoiRatios {left, right, top, bottom} and cv::cornerSubPix (Vis/SubPixWinSize, SubPixIterations, SubPixEps)."""
+    _fields_ = [("roi_ratios", C.c_float * 4), ("subpix_win_size", C.c_int32), ("subpix_iterations", C.c_int32),
+                ("subpix_eps", C.c_float)]
+
+
+assert C.sizeof(FrontParams) == 28
+
+
+def front_params(roi_ratios=(0.0, 0.0, 0.0, 0.0), subpix_win_size=3, subpix_iterations=0, subpix_eps=0.02):
+    """rtabmap's defaults (what sf_front_defaults fills): no ROI, no refinement (0 iterations)."""
+    p = FrontParams()
+    for k in range(4):
+        p.roi_ratios[k] = roi_ratios[k]
+    p.subpix_win_size, p.subpix_iterations, p.subpix_eps = subpix_win_size, subpix_iterations, subpix_eps
+    return p
+
+
+def compute_roi(width, height, ratios):
+    """Feature2D::computeRoi restated: (x, y, w, h) of the sub-image the detector sees for Vis/RoiRatios {left, right,
+    top, bottom}.  Float32 arithmetic with C++'s truncating assignment; ValueError for what sf_compute_roi refuses (a
+    ratio outside [0, 1], an empty image, a ROI side below 3)."""
+    f = np.float32
+    r = [f(v) for v in ratios]
+    if len(r) != 4 or width < 1 or height < 1 or not all(f(0) <= v <= f(1) for v in r):
+        raise ValueError("Vis/RoiRatios %s on %d x %d" % (list(ratios), width, height))
+
+    def side(n, lo, hi):
+        o = 0
+        if lo > 0 and lo < f(1) - hi:
+            o = int(f(n) * lo)
+        m = n - o
+        if hi > 0 and hi < f(1) - lo:
+            m = int(f(m) - f(n) * hi)
+        return o, m
+
+    x, w = side(width, r[0], r[1])
+    y, h = side(height, r[2], r[3])
+    if w < 3 or h < 3:
+        raise ValueError("Vis/RoiRatios %s leave %d x %d of %d x %d" % (list(ratios), w, h, width, height))
+    return x, y, w, h
+
+
 class OrbDetectorParams(C.Structure):
     """sf_orb_detector_params (include/sepfinder.h): rtabmap's ORB/ parameters of the ORB detector (Vis/FeatureType 2)."""
     _fields_ = [("scale_factor", C.c_float), ("n_levels", C.c_int32), ("first_level", C.c_int32), ("score_type", C.c_int32),

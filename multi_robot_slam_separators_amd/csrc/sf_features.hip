@@ -1,7 +1,7 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
-// detection (GFTT, FAST, ORB), stereo correspondence, keyframe extraction and the camera-image forms of these calls
-// (kernels in k_extract.hip, k_gftt.hip, k_fast.hip, k_orb_detect.hip, k_lk.hip, k_cnn.hip, k_image.hip; the detectors'
-// sort in sf_sort.hip).
+// detection (GFTT, FAST, ORB), the ROI and the sub-pixel refinement around it, stereo correspondence, keyframe extraction
+// and the camera-image forms of these calls (kernels in k_extract.hip, k_gftt.hip, k_fast.hip, k_orb_detect.hip,
+// k_subpix.hip, k_lk.hip, k_cnn.hip, k_image.hip; the detectors' sort in sf_sort.hip).
 #include "sf_host.hpp"
 
 // ---- the checks the entry points below share ---------------------------------------------------------------------
@@ -347,6 +347,104 @@ extern "C" int sf_detect_fast_device(sf_handle c, const uint8_t* d_image, int32_
   return sf_launch_detect_fast(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
 }
 
+// ---- around every detector: Vis/RoiRatios and cv::cornerSubPix (Feature2D::generateKeypoints; kernel in k_subpix.hip) ----
+extern "C" void sf_front_defaults(sf_front_params* p) {
+  if (!p) return;
+  for (float& r : p->roi_ratios) r = 0.f;   // Vis/RoiRatios "0.0 0.0 0.0 0.0" [upstream rtabmap Parameters.h]
+  p->subpix_win_size = 3;                   // Vis/SubPixWinSize
+  p->subpix_iterations = 0;                 // Vis/SubPixIterations: 0 = no refinement
+  p->subpix_eps = 0.02f;                    // Vis/SubPixEps
+}
+
+static bool roi_ratios_valid(const float* r) {
+  for (int k = 0; k < 4; ++k)
+    if (!(r[k] >= 0.f && r[k] <= 1.f)) return false;
+  return true;
+}
+
+// Feature2D::computeRoi: float arithmetic, C++'s truncating assignment
+extern "C" int sf_compute_roi(int32_t width, int32_t height, const float* ratios, int32_t* roi_xywh) {
+  if (!ratios || !roi_xywh || width < 1 || height < 1 || !roi_ratios_valid(ratios)) return SF_EINVAL;
+  const float r0 = ratios[0], r1 = ratios[1], r2 = ratios[2], r3 = ratios[3];
+  int x = 0, y = 0;
+  if (r0 > 0.f && r0 < 1.f - r1) x = (int)(width * r0);
+  int w = width - x;
+  if (r1 > 0.f && r1 < 1.f - r0) w = (int)((float)w - width * r1);
+  if (r2 > 0.f && r2 < 1.f - r3) y = (int)(height * r2);
+  int h = height - y;
+  if (r3 > 0.f && r3 < 1.f - r2) h = (int)((float)h - height * r3);
+  roi_xywh[0] = x; roi_xywh[1] = y; roi_xywh[2] = w; roi_xywh[3] = h;
+  return (w < 3 || h < 3) ? SF_EINVAL : SF_OK;
+}
+
+static int front_validate(sf_context* c, const sf_front_params& f) {
+  if (!roi_ratios_valid(f.roi_ratios))
+    return sf_fail(c, SF_EINVAL, "Vis/RoiRatios %g %g %g %g: every ratio must lie in [0, 1]", (double)f.roi_ratios[0],
+                   (double)f.roi_ratios[1], (double)f.roi_ratios[2], (double)f.roi_ratios[3]);
+  if (f.subpix_win_size < 0 || f.subpix_win_size > 15) return sf_fail(c, SF_EINVAL, "subpix_win_size %d outside 0 .. 15", f.subpix_win_size);
+  if (f.subpix_iterations < 0) return sf_fail(c, SF_EINVAL, "subpix_iterations %d is negative", f.subpix_iterations);
+  if (!(f.subpix_eps == f.subpix_eps)) return sf_fail(c, SF_EINVAL, "subpix_eps is NaN");
+  return SF_OK;
+}
+
+extern "C" int sf_front_set_params(sf_handle c, const sf_front_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  int rc = front_validate(c, *params);
+  if (rc != SF_OK) return rc;
+  c->front = *params;
+  return SF_OK;
+}
+
+extern "C" int sf_front_get_params(sf_handle c, sf_front_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  *params = c->front;
+  return SF_OK;
+}
+
+static int check_subpix(sf_context* c, int width, int height, int win, int iterations) {
+  if (win < 1 || win > 15) return sf_fail(c, SF_EINVAL, "cornerSubPix window %d outside 1 .. 15", win);
+  if (iterations < 1) return sf_fail(c, SF_EINVAL, "cornerSubPix iterations %d: at least 1", iterations);
+  if (width < 2 * win + 5 || height < 2 * win + 5)
+    return sf_fail(c, SF_EINVAL, "cornerSubPix with window %d needs an image of at least %d x %d, not %d x %d (cv::cornerSubPix asserts the same)",
+                   win, 2 * win + 5, 2 * win + 5, width, height);
+  return SF_OK;
+}
+
+extern "C" int sf_corner_subpix_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                       sf_keypoint* d_kpts, int32_t n, int32_t win, int32_t iterations, float eps) {
+  if (!c || n < 0) return SF_EINVAL;
+  int rc = check_image(c, d_image, width, height, pitch, 1, "image");
+  if (rc != SF_OK) return rc;
+  if ((rc = check_subpix(c, width, height, win, iterations)) != SF_OK) return rc;
+  if (!(eps == eps)) return sf_fail(c, SF_EINVAL, "cornerSubPix eps is NaN");
+  if (n > 0 && !d_kpts) return sf_fail(c, SF_EINVAL, "keypoints missing");
+  if (n == 0) return SF_OK;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_corner_subpix(c, d_image, 0, 1, width, height, pitch, d_kpts, n, nullptr, n, 0, 0, win, iterations, eps);
+}
+
+// What the extraction calls do around their detector: the ROI of the handle's ratios on a width x height image and
+// whether the corners are refined.  Refuses, before anything is touched, what the two steps cannot do.
+struct FrontPlan {
+  int x = 0, y = 0, w = 0, h = 0;
+  bool refine = false;
+  bool launch() const { return refine || x || y; }         // (an offset of zero and no refinement: no launch at all)
+};
+
+static int front_plan(sf_context* c, int width, int height, FrontPlan* fp) {
+  const sf_front_params& f = c->front;
+  int32_t roi[4] = {0, 0, 0, 0};
+  const int rc = sf_compute_roi(width, height, f.roi_ratios, roi);
+  if (c->feature_type == 2 && (f.roi_ratios[0] != 0.f || f.roi_ratios[1] != 0.f || f.roi_ratios[2] != 0.f || f.roi_ratios[3] != 0.f))
+    return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 2 (ORB) is not built: the batch form reuses the detector's pyramid for the descriptors; set the ratios to 0 or choose feature type 4, 6 or 8");
+  if (rc != SF_OK)
+    return sf_fail(c, SF_EINVAL, "Vis/RoiRatios %g %g %g %g leave a ROI of %d x %d in a %d x %d image: both sides must be >= 3",
+                   (double)f.roi_ratios[0], (double)f.roi_ratios[1], (double)f.roi_ratios[2], (double)f.roi_ratios[3], roi[2], roi[3], width, height);
+  fp->x = roi[0]; fp->y = roi[1]; fp->w = roi[2]; fp->h = roi[3];
+  fp->refine = f.subpix_win_size > 0 && f.subpix_iterations > 0;
+  return fp->refine ? check_subpix(c, width, height, f.subpix_win_size, f.subpix_iterations) : SF_OK;
+}
+
 extern "C" void sf_stereo_flow_defaults(sf_stereo_flow_params* p) {
   if (!p) return;
   p->win_width = 15; p->win_height = 3;        // Stereo/WinWidth, Stereo/WinHeight [upstream rtabmap Parameters.h]
@@ -422,6 +520,8 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
   int rc = format < 0 ? check_image(c, left && right, width, height, pitch, 3, "stereo pair")
                       : check_camera_image(c, left && right, format, width, height, pitch, 3, "stereo pair");
   if (rc != SF_OK) return rc;
+  FrontPlan fp;
+  if ((rc = front_plan(c, width, height, &fp)) != SF_OK) return rc;
   const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
   if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
     return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
@@ -456,14 +556,19 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
   int32_t n = 0;
   // (the GFTT parameters are checked under every feature type, FAST and ORB included, which do not use them)
   if ((rc = check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
+  const uint8_t* d_roi = d_left + (size_t)fp.y * width + fp.x;   // the detector's image: the ROI, at the parent's pitch
   switch (c->feature_type) {
-    case 4: rc = sf_detect_fast_device(c, d_left, width, height, width, maxf, nullptr, d_kpts, maxf, &n); break;
-    case 2: rc = sf_detect_orb_device(c, d_left, width, height, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
+    case 4: rc = sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
+    case 2: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
     default:
-      rc = sf_detect_corners_device(c, d_left, width, height, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
+      rc = sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
   }
   if (rc != SF_OK) return rc;
   n = std::min(n, maxf);
+  if (fp.launch() &&
+      (rc = sf_launch_corner_subpix(c, d_left, 0, 1, width, height, width, d_kpts, n, nullptr, maxf, fp.x, fp.y,
+                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
+    return rc;
   float* d_xy = (float*)c->ft_flow.p;                    // [n][2], then x [n], then status [n]
   float* d_rx = d_xy + 2 * (size_t)maxf;
   uint8_t* d_status = (uint8_t*)(d_rx + maxf);
@@ -520,6 +625,7 @@ struct BatchPlan {
   sf_detector_params dp;
   sf_stereo_flow_params prm;
   ExtractKind kind;
+  FrontPlan front;
 };
 
 static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframes, int width, int height, int pitch,
@@ -534,6 +640,7 @@ static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframe
   if (rc != SF_OK) return rc;
   if (image_stride < (size_t)pitch * height)
     return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
+  if ((rc = front_plan(c, width, height, &plan->front)) != SF_OK) return rc;
   plan->dp = arg_or_defaults(det, sf_detector_defaults);
   if (plan->dp.max_features <= 0 || plan->dp.max_features > SF_MAX_FEATURES)
     return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", plan->dp.max_features, SF_MAX_FEATURES);
@@ -580,16 +687,22 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t* d_n = (int32_t*)c->ft_counts.p;
   ExtractKind kind = plan.kind;
-  if (c->feature_type == 2) {                            // (keypoints in level-0 coordinates; the pyramids stay for the extraction)
+  const FrontPlan& fp = plan.front;
+  const uint8_t* d_roi = d_left + (size_t)fp.y * pitch + fp.x;   // the detector's images: the ROI, at the parent's pitch and stride
+  if (c->feature_type == 2) {                            // (keypoints in level-0 coordinates; the pyramids stay for the extraction;
     rc = sf_launch_detect_orb_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
-    kind.pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;
+    kind.pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;   // no ROI: front_plan)
   } else if (c->feature_type == 4) {
-    rc = sf_launch_detect_fast_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
+    rc = sf_launch_detect_fast_batch(c, d_roi, image_stride, n, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
   } else {
-    rc = sf_launch_detect_corners_batch(c, d_left, image_stride, n, width, height, pitch, maxf, dp.quality_level,
+    rc = sf_launch_detect_corners_batch(c, d_roi, image_stride, n, fp.w, fp.h, pitch, maxf, dp.quality_level,
                                         dp.min_distance, d_kpts, maxf, d_n);
   }
   if (rc != SF_OK) return rc;
+  if (fp.launch() &&
+      (rc = sf_launch_corner_subpix(c, d_left, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, maxf, fp.x, fp.y,
+                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
+    return rc;
   float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
   float* d_rx = d_xy + 2 * rows_all;
   uint8_t* d_status = (uint8_t*)(d_rx + rows_all);

@@ -250,6 +250,9 @@ struct sf_context {
   // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
   // the image at hand; orb_work: the detector's candidate lists
   sf_orb_detector_params orb_det = {2.0f, 3, 0, 0, 20};
+  // every type: what Feature2D::generateKeypoints puts around the detector (sf_front_set_params; k_subpix.hip) -- the ROI
+  // the detector sees and cv::cornerSubPix on the kept corners; both off on a fresh handle
+  sf_front_params front = {{0.f, 0.f, 0.f, 0.f}, 3, 0, 0.02f};
   Buf orb_pyr, orb_work;
   Buf trace;                    // SF_CHAIN_TRACE builds: uint64[n][32] phase timestamps of the fused kernel
 
@@ -658,6 +661,11 @@ int sf_launch_detect_orb_batch(sf_context* c, const uint8_t* d_images, size_t im
 int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int pitch, const SfOrbPyr& P,
                                size_t pyr_stride, const sf_keypoint* d_kpts, int n_max, const int32_t* d_n, int edge,
                                sf_keypoint* d_kpts_out);
+// ROI offset + cv::cornerSubPix in place (k_subpix.hip): n keypoints per image, or min(d_n[image], kp_stride) read on the
+// device; win 0 or iterations 0: the offset alone
+int sf_launch_corner_subpix(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                            sf_keypoint* d_kpts, int n, const int32_t* d_n, int kp_stride, int off_x, int off_y, int win,
+                            int iterations, float eps);
 int sf_launch_stereo_flow(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, int width, int height, int pitch,
                           const sf_keypoint* d_kpts, int n, const sf_stereo_flow_params* prm, float* d_right_xy,
                           uint8_t* d_status, float* d_right_x, float* d_err);

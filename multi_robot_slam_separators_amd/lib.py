@@ -92,6 +92,11 @@ def load():
         "sf_fast_set_params": (C.c_int, [vp, P(_abi.FastParams)]),
         "sf_fast_get_params": (C.c_int, [vp, P(_abi.FastParams)]),
         "sf_detect_fast_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.FastParams), vp, i32, P(i32)]),
+        "sf_front_defaults": (None, [P(_abi.FrontParams)]),
+        "sf_front_set_params": (C.c_int, [vp, P(_abi.FrontParams)]),
+        "sf_front_get_params": (C.c_int, [vp, P(_abi.FrontParams)]),
+        "sf_compute_roi": (C.c_int, [i32, i32, P(C.c_float), P(i32)]),
+        "sf_corner_subpix_device": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, i32, C.c_float]),
         "sf_orb_detector_defaults": (None, [P(_abi.OrbDetectorParams)]),
         "sf_set_feature_type_orb": (C.c_int, [vp, P(_abi.OrbDetectorParams), P(_abi.OrbParams)]),
         "sf_get_orb_detector": (C.c_int, [vp, P(_abi.OrbDetectorParams)]),
@@ -200,6 +205,7 @@ EXPORTED = [
     "sf_image_set_gray_rule", "sf_image_get_gray_rule", "sf_image_to_gray_device", "sf_netvlad_infer_u8_batch_device",
     "sf_get_features_and_descriptor_u8", "sf_add_keyframes_u8_batch_device",
     "sf_get_features_and_descriptor_orb_batch_device", "sf_add_keyframes_orb_u8_batch_device",
+    "sf_front_defaults", "sf_front_set_params", "sf_front_get_params", "sf_compute_roi", "sf_corner_subpix_device",
 ]
 
 
@@ -577,6 +583,31 @@ class SeparatorFinder:
                                                   C.byref(params) if params is not None else None,
                                                   C.c_void_p(d_kpts_out), cap, C.byref(n)))
         return n.value
+
+    def front_set_params(self, params):
+        """The handle's _abi.FrontParams: the ROI every detector sees (Vis/RoiRatios) and cv::cornerSubPix on the kept
+        corners (Vis/SubPix*), applied by the keyframe extraction calls; both off on a fresh handle."""
+        self._check(self._L.sf_front_set_params(self._h, C.byref(params)))
+
+    def front_get_params(self):
+        p = _abi.FrontParams()
+        self._check(self._L.sf_front_get_params(self._h, C.byref(p)))
+        return p
+
+    def compute_roi(self, width, height, ratios):
+        """sf_compute_roi (pure host code): (x, y, w, h); what _abi.compute_roi restates."""
+        r = (C.c_float * 4)(*ratios)
+        out = (C.c_int32 * 4)()
+        rc = self._L.sf_compute_roi(width, height, r, out)
+        if rc != _abi.SF_OK:
+            raise SepfinderError(rc, "Vis/RoiRatios %s on a %d x %d image" % (list(ratios), width, height))
+        return tuple(out)
+
+    def corner_subpix_device(self, d_image, width, height, pitch, d_kpts, n, win, iterations, eps):
+        """cv::cornerSubPix on n 28-byte keypoint records of a device image, in place (x and y only), asynchronous on the
+        handle's stream; device pointers (ints)."""
+        self._check(self._L.sf_corner_subpix_device(self._h, C.c_void_p(d_image), width, height, pitch, C.c_void_p(d_kpts),
+                                                    n, win, iterations, eps))
 
     def detect_corners_device(self, d_image, width, height, pitch, max_corners, quality_level, min_distance,
                               d_kpts_out, cap):

@@ -126,6 +126,22 @@ class SepfinderGeometricTools {
     } else if (sf_set_feature_type(sf_, feature_type, &orb) != SF_OK) {
       ROS_ERROR("feature_type %d: %s", feature_type, sf_last_error(sf_));
     }
+    // Vis/RoiRatios "left right top bottom" and Vis/SubPixWinSize / SubPixIterations / SubPixEps: the two steps around every
+    // detector; both off by default, like the reference (the reference's crossed SubPix keys)
+    sf_front_params front;
+    sf_front_defaults(&front);
+    std::string roi_ratios = "0.0 0.0 0.0 0.0";
+    n.param("roi_ratios", roi_ratios, roi_ratios);
+    if (std::sscanf(roi_ratios.c_str(), "%f %f %f %f", &front.roi_ratios[0], &front.roi_ratios[1], &front.roi_ratios[2],
+                    &front.roi_ratios[3]) != 4)
+      ROS_ERROR("roi_ratios \"%s\": four numbers expected (left right top bottom)", roi_ratios.c_str());
+    n.param("subpix_win_size", front.subpix_win_size, front.subpix_win_size);
+    n.param("subpix_iterations", front.subpix_iterations, front.subpix_iterations);
+    double subpix_eps = front.subpix_eps;
+    n.param("subpix_eps", subpix_eps, subpix_eps);
+    front.subpix_eps = (float)subpix_eps;
+    if (sf_front_set_params(sf_, &front) != SF_OK)
+      ROS_ERROR("roi_ratios / subpix_*: %s", sf_last_error(sf_));
     // OpenCV's ORB bit_pattern_31_ (256 tests x 4 int8: x1 y1 x2 y2), if the integrator provides it
     if (n.getParam("orb_pattern_file", pattern_file) && !pattern_file.empty()) {
       std::ifstream in(pattern_file.c_str(), std::ios::binary);
