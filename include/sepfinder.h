@@ -76,6 +76,9 @@ extern "C" {
 /* 8, additions: sf_front_params, sf_front_defaults, sf_front_set_params, sf_front_get_params, sf_compute_roi,
       sf_corner_subpix_device (Vis/RoiRatios and the Vis/SubPix* refinement around every detector).  Both steps are off on
       a fresh handle; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.             */
+/* 8, additions: sf_stereo_params, sf_stereo_defaults, sf_stereo_set_params, sf_stereo_get_params,
+      sf_stereo_block_match_device (Stereo/OpticalFlow false: block-matching stereo correspondence).  A fresh handle runs
+      pyramidal LK as before; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.     */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -537,6 +540,41 @@ int  sf_stereo_correspondences_device(sf_handle h, const uint8_t* d_left, const 
                                       int32_t height, int32_t pitch, const sf_keypoint* d_kpts, int32_t n,
                                       const sf_stereo_flow_params* params, float* d_right_xy, uint8_t* d_status,
                                       float* d_right_x, float* d_err);
+/* The second stereo correspondence of rtabmap's Stereo class, Stereo/OpticalFlow = false: Stereo::computeCorrespondences
+   -> util2d::calcStereoCorrespondences [upstream rtabmap, restated in tests/stereo_bm_ref.py; DESIGN.md section 3 item
+   17e lists what the restatement decides].  Block matching along the row of a rectified pair: on the pyramid of the LK path,
+   from the last level down, the window of win_width x win_height around (int)(x / 2^level) is compared with the
+   right-image windows of every disparity candidate of the level's range (exact integer sums of squared or absolute
+   differences; the smallest POSITIVE score wins, the earliest on a tie) and a winner above level 0 narrows the range; the
+   level-0 winner is refined by bisection (step 0.5, halved whenever neither neighbour is better, `iterations` steps,
+   clamped to 0 .. 100) on float32 scores of bilinear patches; a step that leaves left.x - right.x <= min_disparity ends the
+   loop with status 0.  There is no maximum-disparity gate behind the search (upstream has none).  A corner without a
+   level-0 winner -- window outside the image, empty range, no positive score, a coordinate that is not finite -- gets
+   status 0, position (0, 0), right_x 0 and score -1.
+   The handle's sf_stereo_params choose between the two for sf_get_features_and_descriptor, its _u8 form,
+   sf_get_features_and_descriptor_batch_device, sf_add_keyframes_u8_batch_device and the two _orb_ batch calls: with
+   optical_flow = 0 their stereo stage is block matching on the same `flow` argument (NULL = the same defaults), the batch
+   forms stay one launch sequence with no host wait, and a `flow` that block matching refuses makes the call return
+   SF_EINVAL before the store or the NN database change.  A fresh handle has {1, 1}: pyramidal LK, as before.          */
+typedef struct sf_stereo_params {
+  int32_t optical_flow;   /* Stereo/OpticalFlow, 1 = pyramidal LK, 0 = block matching                                  */
+  int32_t ssd;            /* Stereo/SSD, 1 = squared differences, 0 = absolute differences; block matching only       */
+} sf_stereo_params;       /* 8 bytes */
+void sf_stereo_defaults(sf_stereo_params* p);
+/* Values other than 0 or 1 return SF_EINVAL and change nothing.                                                      */
+int  sf_stereo_set_params(sf_handle h, const sf_stereo_params* params);
+int  sf_stereo_get_params(sf_handle h, sf_stereo_params* params);
+/* Block matching on n corners, the conventions of sf_stereo_correspondences_device: asynchronous on the handle's stream,
+   params NULL = sf_stereo_flow_defaults, d_right_x [n] and d_score [n] optional (d_score: the score at the position found,
+   the level-0 integer score when no bisection step improved on it).  Reads win_width, win_height, max_level, iterations,
+   min_disparity and max_disparity of `params`; epsilon and min_eig_threshold are ignored.  ssd: 1 or 0 as above.
+   SF_EINVAL for an even window side, a window above 1024 pixels, disparities that are not finite or violate
+   0 <= min <= max, floor(max_disparity) > 1024 or ssd outside {0, 1}; SF_ERANGE for max_level outside 0 .. 15; a refused
+   call changes nothing.  n = 0 is SF_OK.  Windows whose right-image strip does not fit the kernel's LDS budget run on
+   a slower path that reads global memory.                                                                             */
+int  sf_stereo_block_match_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right, int32_t width, int32_t height,
+                                  int32_t pitch, const sf_keypoint* d_kpts, int32_t n, const sf_stereo_flow_params* params,
+                                  int32_t ssd, float* d_right_xy, uint8_t* d_status, float* d_right_x, float* d_score);
 /* d_left: 8-bit image on the device (height rows of `pitch` bytes); d_kpts: n corners; d_right_x: their x in the
    right image (NULL: no 3D); d_status: per-corner validity of d_right_x (NULL: all valid).  Appends ONE keyframe
    to the store; *out_slot = its slot, *out_rows = features kept (the call synchronises the stream to read it;

@@ -177,6 +177,22 @@ def front_params(roi_ratios=(0.0, 0.0, 0.0, 0.0), subpix_win_size=3, subpix_iter
     return p
 
 
+class StereoParams(C.Structure):
+    """sf_stereo_params (include/sepfinder.h): which stereo correspondence the extraction calls run -- Stereo/OpticalFlow
+    (1 = pyramidal LK, 0 = block matching) and Stereo/SSD (block matching: 1 = squared, 0 = absolute differences)."""
+    _fields_ = [("optical_flow", C.c_int32), ("ssd", C.c_int32)]
+
+
+assert C.sizeof(StereoParams) == 8
+
+
+def stereo_params(optical_flow=1, ssd=1):
+    """rtabmap's defaults (what sf_stereo_defaults fills): pyramidal LK; squared differences where block matching runs."""
+    p = StereoParams()
+    p.optical_flow, p.ssd = optical_flow, ssd
+    return p
+
+
 def compute_roi(width, height, ratios):
     """Feature2D::computeRoi restated: (x, y, w, h) of the sub-image the detector sees for Vis/RoiRatios {left, right,
     top, bottom}.  Float32 arithmetic with C++'s truncating assignment; ValueError for what sf_compute_roi refuses (a

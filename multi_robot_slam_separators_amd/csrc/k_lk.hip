@@ -26,22 +26,8 @@
 
 namespace {
 
-constexpr int LK_MAX_LEVELS = 16;
 constexpr int LK_W_BITS = 14;
 constexpr int LK_REGION_X = 8, LK_REGION_Y = 3;
-
-struct LkLevel {
-  const uint8_t* l;
-  const uint8_t* r;
-  int w, h, pitch, pad_;
-};
-struct LkLevels {
-  LkLevel v[LK_MAX_LEVELS];
-  int n;
-  int per_image;                  // batch (blockIdx.y = image): corners / outputs of consecutive images this many apart
-  size_t stride0, stride_pyr;     // bytes between consecutive images at level 0 / between their pyramid blocks
-  const int32_t* d_n;             // batch: corners of every image (device); null: the scalar n
-};
 
 __device__ __forceinline__ int border_101(int p, int len) {       // cv::borderInterpolate(p, len, BORDER_REFLECT_101)
   if ((unsigned)p < (unsigned)len) return p;
@@ -293,13 +279,10 @@ __global__ __launch_bounds__(64) void k_lk_track(const LkLevels P, const sf_keyp
 
 }  // namespace
 
-// n_img > 1: a batch -- image i at d_left / d_right + i * img_stride, its corners / outputs at + i * n entries, its corner
-// count in d_n[i] (device; `n` is then the per-image capacity the grid is sized for).
-int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride, int n_img,
-                                int width, int height, int pitch, const sf_keypoint* d_kpts, int n, const int32_t* d_n,
-                                const sf_stereo_flow_params* prm, float* d_right_xy, uint8_t* d_status, float* d_right_x,
-                                float* d_err) {
-  const int ww = prm->win_width, wh = prm->win_height;
+// The pyramid both stereo paths search (k_lk_track here, k_stereo_bm in k_stereo_bm.hip): levels >= 1 of both images of
+// every pair into c->lk_pyr, one launch per level, and the level table the kernels take.
+int sf_lk_build_pyramid(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride, int n_img, int width,
+                        int height, int pitch, int ww, int wh, int max_level, int n, const int32_t* d_n, LkLevels* out) {
   // buildOpticalFlowPyramid: the level whose successor would be <= winSize in either direction is the last
   int lw[LK_MAX_LEVELS], lh[LK_MAX_LEVELS];
   size_t off[LK_MAX_LEVELS];
@@ -307,7 +290,7 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
   size_t bytes = 0;
   {
     int w = width, h = height;
-    for (int l = 0; l <= prm->max_level; ++l) {
+    for (int l = 0; l <= max_level; ++l) {
       lw[l] = w; lh[l] = h;
       off[l] = bytes;
       if (l > 0) bytes += ((size_t)w * h + 15) & ~(size_t)15;
@@ -320,7 +303,7 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
   if ((rc = sf_buf_reserve(c, c->lk_pyr, std::max<size_t>(2 * bytes * n_img, 16))) != SF_OK) return rc;
   uint8_t* base_l = (uint8_t*)c->lk_pyr.p;
   uint8_t* base_r = base_l + bytes * n_img;
-  LkLevels P;
+  LkLevels& P = *out;
   P.n = nl;
   P.per_image = n;
   P.stride0 = img_stride;
@@ -337,6 +320,20 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
                        P.v[l - 1].pitch, (uint8_t*)P.v[l].l, (uint8_t*)P.v[l].r, lw[l], lh[l],
                        l == 1 ? img_stride : bytes, bytes);
   }
+  return SF_OK;
+}
+
+// n_img > 1: a batch -- image i at d_left / d_right + i * img_stride, its corners / outputs at + i * n entries, its corner
+// count in d_n[i] (device; `n` is then the per-image capacity the grid is sized for).
+int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride, int n_img,
+                                int width, int height, int pitch, const sf_keypoint* d_kpts, int n, const int32_t* d_n,
+                                const sf_stereo_flow_params* prm, float* d_right_xy, uint8_t* d_status, float* d_right_x,
+                                float* d_err) {
+  const int ww = prm->win_width, wh = prm->win_height;
+  LkLevels P;
+  int rc;
+  if ((rc = sf_lk_build_pyramid(c, d_left, d_right, img_stride, n_img, width, height, pitch, ww, wh, prm->max_level, n, d_n, &P)) != SF_OK)
+    return rc;
   const int max_count = std::min(std::max(prm->iterations, 0), 100);
   double eps = std::min(std::max(prm->epsilon, 0.0), 10.0);
   eps *= eps;

@@ -1,7 +1,9 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
 // detection (GFTT, FAST, ORB), the ROI and the sub-pixel refinement around it, stereo correspondence, keyframe extraction
 // and the camera-image forms of these calls (kernels in k_extract.hip, k_gftt.hip, k_fast.hip, k_orb_detect.hip,
-// k_subpix.hip, k_lk.hip, k_cnn.hip, k_image.hip; the detectors' sort in sf_sort.hip).
+// k_subpix.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in sf_sort.hip).
+#include <cmath>
+
 #include "sf_host.hpp"
 
 // ---- the checks the entry points below share ---------------------------------------------------------------------
@@ -474,6 +476,60 @@ extern "C" int sf_stereo_correspondences_device(sf_handle c, const uint8_t* d_le
   return sf_launch_stereo_flow(c, d_left, d_right, width, height, pitch, d_kpts, n, &prm, d_right_xy, d_status, d_right_x, d_err);
 }
 
+// ---- block matching (Stereo/OpticalFlow false; kernel in k_stereo_bm.hip) ------------------------------------------
+extern "C" void sf_stereo_defaults(sf_stereo_params* p) {
+  if (!p) return;
+  p->optical_flow = 1;                         // Stereo/OpticalFlow [upstream rtabmap Parameters.h]
+  p->ssd = 1;                                  // Stereo/SSD
+}
+
+extern "C" int sf_stereo_set_params(sf_handle c, const sf_stereo_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  if ((params->optical_flow != 0 && params->optical_flow != 1) || (params->ssd != 0 && params->ssd != 1))
+    return sf_fail(c, SF_EINVAL, "Stereo/OpticalFlow %d, Stereo/SSD %d: each is 0 or 1", params->optical_flow, params->ssd);
+  c->stereo = *params;
+  return SF_OK;
+}
+
+extern "C" int sf_stereo_get_params(sf_handle c, sf_stereo_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  *params = c->stereo;
+  return SF_OK;
+}
+
+// what block matching refuses of the flow parameters (epsilon and min_eig_threshold are not read)
+static int check_block_match(sf_context* c, const sf_stereo_flow_params& prm) {
+  if (prm.win_width < 1 || prm.win_height < 1 || !(prm.win_width & 1) || !(prm.win_height & 1))
+    return sf_fail(c, SF_EINVAL, "block matching window of %d x %d: both sides must be odd", prm.win_width, prm.win_height);
+  if ((long long)prm.win_width * prm.win_height > 1024)
+    return sf_fail(c, SF_EINVAL, "block matching window of %d x %d exceeds 1024 pixels", prm.win_width, prm.win_height);
+  if (prm.max_level < 0 || prm.max_level > 15) return sf_fail(c, SF_ERANGE, "max_level %d outside 0 .. 15", prm.max_level);
+  if (!std::isfinite(prm.min_disparity) || !std::isfinite(prm.max_disparity) || prm.min_disparity < 0.f ||
+      prm.min_disparity > prm.max_disparity)
+    return sf_fail(c, SF_EINVAL, "block matching disparities %g .. %g: finite, 0 <= min <= max", (double)prm.min_disparity,
+                   (double)prm.max_disparity);
+  if (std::floor(prm.max_disparity) > 1024.f)
+    return sf_fail(c, SF_EINVAL, "block matching max_disparity %g: at most 1024 whole pixels", (double)prm.max_disparity);
+  return SF_OK;
+}
+
+extern "C" int sf_stereo_block_match_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right, int32_t width,
+                                            int32_t height, int32_t pitch, const sf_keypoint* d_kpts, int32_t n,
+                                            const sf_stereo_flow_params* params, int32_t ssd, float* d_right_xy,
+                                            uint8_t* d_status, float* d_right_x, float* d_score) {
+  if (!c || n < 0) return SF_EINVAL;
+  int rc = check_image(c, d_left && d_right, width, height, pitch, 1, "stereo pair");
+  if (rc != SF_OK) return rc;
+  if (n > 0 && (!d_kpts || !d_right_xy || !d_status)) return sf_fail(c, SF_EINVAL, "corners or output arrays missing");
+  if (ssd != 0 && ssd != 1) return sf_fail(c, SF_EINVAL, "ssd %d: 1 = squared, 0 = absolute differences", ssd);
+  const sf_stereo_flow_params prm = arg_or_defaults(params, sf_stereo_flow_defaults);
+  if ((rc = check_block_match(c, prm)) != SF_OK) return rc;
+  if (n == 0) return SF_OK;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_stereo_bm_batch(c, d_left, d_right, 0, 1, width, height, pitch, d_kpts, n, nullptr, &prm, ssd, d_right_xy,
+                                   d_status, d_right_x, d_score);
+}
+
 extern "C" int sf_extract_keyframe_device(sf_handle c, const uint8_t* d_left, int32_t width, int32_t height,
                                           int32_t pitch, const sf_keypoint* d_kpts, const float* d_right_x,
                                           const uint8_t* d_status, int32_t n, const sf_stereo_camera* cam,
@@ -572,8 +628,10 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
   float* d_xy = (float*)c->ft_flow.p;                    // [n][2], then x [n], then status [n]
   float* d_rx = d_xy + 2 * (size_t)maxf;
   uint8_t* d_status = (uint8_t*)(d_rx + maxf);
-  if ((rc = sf_stereo_correspondences_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, d_xy, d_status, d_rx, nullptr)) != SF_OK)
-    return rc;
+  rc = c->stereo.optical_flow
+           ? sf_stereo_correspondences_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, d_xy, d_status, d_rx, nullptr)
+           : sf_stereo_block_match_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
+  if (rc != SF_OK) return rc;
   uint8_t* d_desc = (uint8_t*)c->ft_wire.p;
   float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
   sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
@@ -647,7 +705,9 @@ static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframe
   if ((rc = check_gftt(c, plan->dp.quality_level, plan->dp.min_distance)) != SF_OK) return rc;
   plan->prm = arg_or_defaults(flow, sf_stereo_flow_defaults);
   const sf_stereo_flow_params& prm = plan->prm;
-  if (prm.win_width <= 2 || prm.win_height <= 2 || (long long)prm.win_width * prm.win_height > 1024 || prm.max_level < 0 ||
+  if (!c->stereo.optical_flow) {
+    if ((rc = check_block_match(c, prm)) != SF_OK) return rc;
+  } else if (prm.win_width <= 2 || prm.win_height <= 2 || (long long)prm.win_width * prm.win_height > 1024 || prm.max_level < 0 ||
       prm.max_level > 15 || !(prm.epsilon == prm.epsilon))
     return sf_fail(c, SF_EINVAL, "stereo flow parameters out of range (see sf_stereo_correspondences_device)");
   if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
@@ -706,9 +766,12 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
   float* d_rx = d_xy + 2 * rows_all;
   uint8_t* d_status = (uint8_t*)(d_rx + rows_all);
-  if ((rc = sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &plan.prm,
-                                        d_xy, d_status, d_rx, nullptr)) != SF_OK)
-    return rc;
+  rc = c->stereo.optical_flow
+           ? sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &plan.prm, d_xy,
+                                         d_status, d_rx, nullptr)
+           : sf_launch_stereo_bm_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &plan.prm,
+                                       c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
+  if (rc != SF_OK) return rc;
   const int slot = c->store.slots;
   if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, kind,
                                     slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out)) != SF_OK)

@@ -253,6 +253,9 @@ struct sf_context {
   // every type: what Feature2D::generateKeypoints puts around the detector (sf_front_set_params; k_subpix.hip) -- the ROI
   // the detector sees and cv::cornerSubPix on the kept corners; both off on a fresh handle
   sf_front_params front = {{0.f, 0.f, 0.f, 0.f}, 3, 0, 0.02f};
+  // which stereo correspondence the extraction calls run (sf_stereo_set_params): pyramidal LK (k_lk.hip) or block
+  // matching (k_stereo_bm.hip) with SSD or SAD scores
+  sf_stereo_params stereo = {1, 1};
   Buf orb_pyr, orb_work;
   Buf trace;                    // SF_CHAIN_TRACE builds: uint64[n][32] phase timestamps of the fused kernel
 
@@ -608,6 +611,27 @@ int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, uns
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
                                    sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out);
+// the pyramid of the two stereo paths (k_lk.hip builds it, k_lk_track and k_stereo_bm read it)
+constexpr int LK_MAX_LEVELS = 16;
+struct LkLevel {
+  const uint8_t* l;
+  const uint8_t* r;
+  int w, h, pitch, pad_;
+};
+struct LkLevels {
+  LkLevel v[LK_MAX_LEVELS];
+  int n;
+  int per_image;                  // batch (blockIdx.y = image): corners / outputs of consecutive images this many apart
+  size_t stride0, stride_pyr;     // bytes between consecutive images at level 0 / between their pyramid blocks
+  const int32_t* d_n;             // batch: corners of every image (device); null: the scalar n
+};
+int sf_lk_build_pyramid(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride, int n_img, int width,
+                        int height, int pitch, int ww, int wh, int max_level, int n, const int32_t* d_n, LkLevels* out);
+// block matching (k_stereo_bm.hip), the arguments of sf_launch_stereo_flow_batch; prm validated by the caller
+int sf_launch_stereo_bm_batch(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride, int n_img,
+                              int width, int height, int pitch, const sf_keypoint* d_kpts, int n, const int32_t* d_n,
+                              const sf_stereo_flow_params* prm, int ssd, float* d_right_xy, uint8_t* d_status,
+                              float* d_right_x, float* d_score);
 int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride, int n_img,
                                 int width, int height, int pitch, const sf_keypoint* d_kpts, int n, const int32_t* d_n,
                                 const sf_stereo_flow_params* prm, float* d_right_xy, uint8_t* d_status, float* d_right_x,

@@ -109,6 +109,11 @@ def load():
                                                      P(_abi.StereoFlowParams), vp, vp, vp, i32, P(i32), P(i32)]),
         "sf_stereo_correspondences_device": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, i32, P(_abi.StereoFlowParams),
                                                        vp, vp, vp, vp]),
+        "sf_stereo_defaults": (None, [P(_abi.StereoParams)]),
+        "sf_stereo_set_params": (C.c_int, [vp, P(_abi.StereoParams)]),
+        "sf_stereo_get_params": (C.c_int, [vp, P(_abi.StereoParams)]),
+        "sf_stereo_block_match_device": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, i32, P(_abi.StereoFlowParams), i32,
+                                                   vp, vp, vp, vp]),
         "sf_netvlad_load": (C.c_int, [vp, P(_abi.NetvladWeights)]),
         "sf_netvlad_infer_device": (C.c_int, [vp, vp, i32, i32, vp, i32]),
         "sf_netvlad_infer_batch_device": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
@@ -206,6 +211,7 @@ EXPORTED = [
     "sf_get_features_and_descriptor_u8", "sf_add_keyframes_u8_batch_device",
     "sf_get_features_and_descriptor_orb_batch_device", "sf_add_keyframes_orb_u8_batch_device",
     "sf_front_defaults", "sf_front_set_params", "sf_front_get_params", "sf_compute_roi", "sf_corner_subpix_device",
+    "sf_stereo_defaults", "sf_stereo_set_params", "sf_stereo_get_params", "sf_stereo_block_match_device",
 ]
 
 
@@ -625,6 +631,25 @@ class SeparatorFinder:
             self._h, C.c_void_p(d_left), C.c_void_p(d_right), width, height, pitch, C.c_void_p(d_kpts), n,
             C.byref(params) if params is not None else None, C.c_void_p(d_right_xy), C.c_void_p(d_status),
             C.c_void_p(d_right_x), C.c_void_p(d_err)))
+
+    def stereo_set_params(self, params):
+        """The handle's _abi.StereoParams: which stereo correspondence the keyframe extraction calls run (Stereo/OpticalFlow:
+        pyramidal LK or block matching) and block matching's score (Stereo/SSD); LK on a fresh handle."""
+        self._check(self._L.sf_stereo_set_params(self._h, C.byref(params)))
+
+    def stereo_get_params(self):
+        p = _abi.StereoParams()
+        self._check(self._L.sf_stereo_get_params(self._h, C.byref(p)))
+        return p
+
+    def stereo_block_match_device(self, d_left, d_right, width, height, pitch, d_kpts, n, d_right_xy, d_status,
+                                  d_right_x=None, d_score=None, params=None, ssd=1):
+        """rtabmap's block-matching stereo correspondence (Stereo/OpticalFlow false) on the device (asynchronous); device
+        pointers (ints)."""
+        self._check(self._L.sf_stereo_block_match_device(
+            self._h, C.c_void_p(d_left), C.c_void_p(d_right), width, height, pitch, C.c_void_p(d_kpts), n,
+            C.byref(params) if params is not None else None, ssd, C.c_void_p(d_right_xy), C.c_void_p(d_status),
+            C.c_void_p(d_right_x), C.c_void_p(d_score)))
 
     def get_features_and_descriptor(self, left, right, cam, det=None, flow=None):
         """GetFeatsAndDesc on host images (uint8 [h, w], same row stride): returns (descriptors [rows, bytes] uint8,

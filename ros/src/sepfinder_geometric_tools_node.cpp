@@ -142,6 +142,17 @@ class SepfinderGeometricTools {
     front.subpix_eps = (float)subpix_eps;
     if (sf_front_set_params(sf_, &front) != SF_OK)
       ROS_ERROR("roi_ratios / subpix_*: %s", sf_last_error(sf_));
+    // Stereo/OpticalFlow (true = pyramidal LK, the default; false = block matching) and Stereo/SSD (block matching: squared
+    // or absolute differences): which stereo correspondence the extraction calls run
+    sf_stereo_params stereo;
+    sf_stereo_defaults(&stereo);
+    bool stereo_optical_flow = stereo.optical_flow != 0, stereo_ssd = stereo.ssd != 0;
+    n.param("stereo_optical_flow", stereo_optical_flow, stereo_optical_flow);
+    n.param("stereo_ssd", stereo_ssd, stereo_ssd);
+    stereo.optical_flow = stereo_optical_flow ? 1 : 0;
+    stereo.ssd = stereo_ssd ? 1 : 0;
+    if (sf_stereo_set_params(sf_, &stereo) != SF_OK)
+      ROS_ERROR("stereo_optical_flow / stereo_ssd: %s", sf_last_error(sf_));
     // OpenCV's ORB bit_pattern_31_ (256 tests x 4 int8: x1 y1 x2 y2), if the integrator provides it
     if (n.getParam("orb_pattern_file", pattern_file) && !pattern_file.empty()) {
       std::ifstream in(pattern_file.c_str(), std::ios::binary);
