@@ -368,8 +368,7 @@ __device__ __forceinline__ void ba_solve(const BaLds& L, const BaCam& cam, int n
     }
     n_out += bad ? 1 : 0;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) n_out += __shfl_xor(n_out, off);
+  n_out = sfd::wave_sum(n_out);             // (ahead of a barrier: all 64 lanes active)
   __syncthreads();
   if (lane == 0) L.misc[8 + wave] = n_out;
   __syncthreads();
@@ -615,8 +614,7 @@ k_merge_directions_ba(StoreView st, const int32_t* __restrict__ pair_from, const
     n_ba += total;
     __syncthreads();
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { uni += __shfl_xor(uni, off); uni_m += __shfl_xor(uni_m, off); }
+  uni = sfd::wave_sum(uni); uni_m = sfd::wave_sum(uni_m);
   if (lane == 0) { atomicAdd(&misc[0], uni); atomicAdd(&misc[1], uni_m); }
   __syncthreads();
   uni = misc[0];

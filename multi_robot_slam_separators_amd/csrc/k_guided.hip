@@ -133,10 +133,18 @@ __device__ __forceinline__ int guided_compact(int Kf, uint32_t* out, int* misc, 
 
 // Workgroup sums of the per-thread counts of finite "from" points and of projections in the image (misc[0], misc[1]:
 // 0 on entry).  Ends with a barrier.
+// LANES = false: the __shfl_xor loops, for k_guided_tp (its W = 16 instantiation sits at 64 registers, eight wavefronts per
+// SIMD; with the register moves here or in its cell scan it takes 66 and loses one).
+template <bool LANES = true>
 __device__ __forceinline__ void guided_sum_counts(int& n_finite, int& n_proj, int* misc) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    n_finite += __shfl_xor(n_finite, off);
-    n_proj += __shfl_xor(n_proj, off);
+  if constexpr (LANES) {
+    n_finite = sfd::wave_sum(n_finite);     // (called by the whole workgroup: all 64 lanes active)
+    n_proj = sfd::wave_sum(n_proj);
+  } else {
+    for (int off = 32; off >= 1; off >>= 1) {
+      n_finite += __shfl_xor(n_finite, off);
+      n_proj += __shfl_xor(n_proj, off);
+    }
   }
   if ((threadIdx.x & 63) == 0) {
     atomicAdd(&misc[0], n_finite);
@@ -339,11 +347,7 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
     const int c0 = tid * per, c1 = min(c0 + per, NC);
     int local = 0;
     for (int cidx = c0; cidx < c1; ++cidx) local += cell_start[cidx + 1];
-    int incl = local;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int o = __shfl_up(incl, off);
-      if (lane >= off) incl += o;
-    }
+    const int incl = sfd::wave_scan_add(local);
     if (lane == 63) misc[8 + wave] = incl;
     __syncthreads();
     int woff = 0;
@@ -468,20 +472,15 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
 #ifdef SF_CHAIN_TRACE
     if (base == 0 && wave == 0 && P.dbg_trace) {
       int mx = dbg_trips, sm = dbg_entries;
-      for (int off = 32; off >= 1; off >>= 1) { mx = max(mx, __shfl_xor(mx, off)); sm += __shfl_xor(sm, off); }
+      mx = sfd::wave_max(mx); sm = sfd::wave_sum(sm);
       if (lane == 0) P.dbg_trace[(size_t)pair * SF_TRACE_SLOTS + 31] = ((unsigned long long)mx << 32) | (unsigned)sm;
     }
 #endif
     if (base == 0) SF_TRACE_MARK(P, pair, 29);   // ... its cells scanned
     {
       // bulk hand-over of the parked combinations of this wavefront
-      int incl = nb;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off);
-        if (lane >= off) incl += o;
-      }
-      const int wtot = __shfl(incl, 63);
+      const int incl = sfd::wave_scan_add(nb);          // (the body of a workgroup-uniform loop: all 64 lanes active)
+      const int wtot = __builtin_amdgcn_readlane(incl, 63);
       int wbase = 0;
       if (wtot > 0) {
         if (lane == 0) wbase = atomicAdd(&misc[3], wtot);
@@ -519,7 +518,7 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
     // every point's candidate count (oilast >> 16, written by its lane) must add up to the list's length
     int mine = 0;
     for (int i = tid; i < Kf; i += NT) mine += (int)(oilast[i] >> 16);
-    for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off);
+    mine = sfd::wave_sum(mine);
     if (lane == 0) atomicAdd(&misc[12], mine);        // misc[12..]: free words
     __syncthreads();
     if (tid == 0 && misc[12] != n_cand) atomicAdd(&P.dbg_trace[2], 1ull);
@@ -795,6 +794,7 @@ __device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, in
     const int c0 = tid * per, c1 = min(c0 + per, NC);
     int local = 0;
     for (int cidx = c0; cidx < c1; ++cidx) local += cell_start[cidx + 1];
+    // (the __shfl_up loop stays in this kernel: see guided_sum_counts)
     int incl = local;
     for (int off = 1; off < 64; off <<= 1) {
       const int o = __shfl_up(incl, off);
@@ -889,7 +889,7 @@ __device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, in
     }
     if (m >= 0 && atomicCAS(&claimw[m], EMPTY, (uint32_t)t) != EMPTY) atomicOr(&claimw[m], SHARED);   // :604-625
   }
-  guided_sum_counts(n_finite, n_proj, misc);    // (its barrier also orders the claims before the compaction)
+  guided_sum_counts<false>(n_finite, n_proj, misc);    // (its barrier also orders the claims before the compaction)
   const int n_corr = guided_compact<NW>(Kf, out, misc, [&](int i) {
     const uint32_t w = claimw[i];
     return (w & SHARED) ? -1 : (int)w;          // (EMPTY has bit 31 set too)

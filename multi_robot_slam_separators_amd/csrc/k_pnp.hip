@@ -67,11 +67,17 @@ struct PnpLds {
   double* ne_b;     // [32] normal equations of the candidate pose
 };
 
+// Which form of sfd::sum_stage this file's canonical sums take.  The four-wavefront bodies stay on the __shfl_xor form:
+// with the register form the stage kernel k_pnp (168 registers at 3 waves per SIMD) spills 4 B per lane more
+// (112 against 108), and this file's kernels sit in the allocation class of the open fault recorded above k_chain_pnp
+// (k_verify.hip) -- no growth of their scratch is accepted.  The one- and two-wavefront chains lose 20-40 B with it.
+template <int NW>
+constexpr bool PNP_SUM_LANES = SF_SUM_LANES != 0 && NW != 4;
+
 template <int NW = 4>
 __device__ __forceinline__ int block_sum_i(int v, int* misc, int tid) {
   const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  v = sfd::wave_sum(v);                     // (ahead of a barrier: all 64 lanes active)
   __syncthreads();
   if (lane == 0) misc[8 + wave] = v;
   __syncthreads();
@@ -141,7 +147,7 @@ __device__ inline void pnp_normal_eq(const PnpLds& L, const PnpCam& cam, int m, 
                                      const double (&q)[4], const double (&t)[3], double* out, int tid) {
   double R[9];
   sfd::quat_to_R(q, R);
-  sfd::canon_reduce_to_lds<PNP_NSUM, 32, NW>(m, tid, L.red, out, [&](int i, double (&ne)[PNP_NSUM]) {
+  sfd::canon_reduce_to_lds<PNP_NSUM, 32, NW, false, PNP_SUM_LANES<NW>>(m, tid, L.red, out, [&](int i, double (&ne)[PNP_NSUM]) {
     if (!mask[i]) return;
     const float4 p = L.obj[i];
     const float2 o = L.img[i];
@@ -582,7 +588,7 @@ __device__ __forceinline__ PnpTail pnp_body(const StoreView& st, int pair, const
       double s1[1] = {0.0};
       if constexpr (NW == 4) {
         for (int i = tid; i < m; i += NT) if (neu[i]) s1[0] += (double)L.e1[i];
-        sfd::block_sum_canon<1, 32>(s1, L.red, tid);
+        sfd::block_sum_canon<1, 32, PNP_SUM_LANES<NW>>(s1, L.red, tid);
       } else {
         sfd::canon_reduce<1, 32, NW>(m, tid, L.red, s1, [&](int i, double (&a)[1]) { if (neu[i]) a[0] += (double)L.e1[i]; });
       }
@@ -594,7 +600,7 @@ __device__ __forceinline__ PnpTail pnp_body(const StoreView& st, int pair, const
           for (int i = tid; i < m; i += NT) {
             if (neu[i]) { const float dlt = L.e1[i] - mean; s2[0] += (double)(dlt * dlt); }
           }
-          sfd::block_sum_canon<1, 32>(s2, L.red, tid);
+          sfd::block_sum_canon<1, 32, PNP_SUM_LANES<NW>>(s2, L.red, tid);
         } else {
           sfd::canon_reduce<1, 32, NW>(m, tid, L.red, s2, [&](int i, double (&a)[1]) {
             if (neu[i]) { const float dlt = L.e1[i] - mean; a[0] += (double)(dlt * dlt); }
@@ -756,8 +762,7 @@ k_merge_directions_pnp(StoreView st, const int32_t* __restrict__ pair_from, cons
     if (g1 && !m) { const float* b = xT + 3 * (c >> 16); m = sfd::finite3(b[0], b[1], b[2]); }
     uni_m += m ? 1 : 0;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) { uni += __shfl_xor(uni, off); uni_m += __shfl_xor(uni_m, off); }
+  uni = sfd::wave_sum(uni); uni_m = sfd::wave_sum(uni_m);
   if (lane != 0) return;
   PassState a = fwd[pair];
   const PassState b = back[pair];

@@ -192,8 +192,7 @@ __device__ inline SelCounts select_within(const RansacLds& L, int m, const float
     L.d2[i] = r2;
   }
   const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+  acc = sfd::wave_sum(acc);               // (behind the loop: all 64 lanes active)
   __syncthreads();
   if (lane == 0) L.sums[wave] = acc;
   __syncthreads();
@@ -240,12 +239,7 @@ __device__ __attribute__((noinline)) float radix_select_rank(lds_cfloat_p d2, ld
       const unsigned h0 = hist[p * 256 + 4 * lane], h1 = hist[p * 256 + 4 * lane + 1], h2 = hist[p * 256 + 4 * lane + 2],
                      h3 = hist[p * 256 + 4 * lane + 3];
       const unsigned s = (h0 + h1) + (h2 + h3);
-      unsigned incl = s;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned y = __shfl_up(incl, off);
-        if (lane >= off) incl += y;
-      }
+      const unsigned incl = (unsigned)sfd::wave_scan_add((int)s);   // (wavefront 0 as a whole: all 64 lanes active)
       const unsigned excl = incl - s;
       if (excl <= (unsigned)rank && (unsigned)rank < incl) {   // exactly one lane
         unsigned r = (unsigned)rank - excl;
@@ -332,12 +326,8 @@ struct ScanState {
 };
 
 // __shfl_up with the source lane derived from the CALLER's lane number: the library form derives it from the hardware
-// lane id, which is loop invariant -- the six source addresses of the scan below were hoisted in front of the
-// hypothesis loop and spilled around the fit.
-__device__ __forceinline__ int shfl_up_from(int v, int off, int lane) {
-  const int src = lane >= off ? lane - off : lane;
-  return __builtin_amdgcn_ds_bpermute(src << 2, v);
-}
+// lane id, which is loop invariant -- the source address of the move below was hoisted in front of the hypothesis loop
+// and spilled around the fit.  (The prefix maximum in front of it needs no address at all: sfd::wave_scan_max.)
 __device__ __forceinline__ double shfl_up_from(double v, int off, int lane) {
   const int src = lane >= off ? lane - off : lane;
   const long long b = __double_as_longlong(v);
@@ -358,12 +348,7 @@ __device__ __forceinline__ double shfl_up_from(double v, int off, int lane) {
 __device__ __forceinline__ bool replay_round(const RansacLds& L, ScanState& S, int base, int R, int lane, int c,
                                              bool present, int max_it, bool adaptive, double inv_m,
                                              double log_probability, bool park = true) {
-  int x = present ? c : -1;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = shfl_up_from(x, off, lane);
-    if (lane >= off) x = max(x, y);
-  }
+  int x = sfd::wave_scan_max(present ? c : -1);         // (called by the solving wavefront as a whole: all 64 lanes active)
   x = max(x, S.best);                                   // inclusive prefix maximum incl. the earlier rounds
   double kj = 1.0;                                      // (no best yet: k keeps its initial value)
   if (x >= 0) {
@@ -817,8 +802,7 @@ k_merge_directions(const int32_t* __restrict__ list, const int32_t* __restrict__
   const int pair = list[blockIdx.x], lane = threadIdx.x;
   int uni = 0;
   for (int i = lane; i < kcap; i += 64) uni += (mask_f[(size_t)pair * kcap + i] | mask_b[(size_t)pair * kcap + i]) ? 1 : 0;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) uni += __shfl_xor(uni, off);
+  uni = sfd::wave_sum(uni);
   if (lane != 0) return;
   PassState a = fwd[pair];
   const PassState b = back[pair];

@@ -268,6 +268,131 @@ __device__ __forceinline__ float residual2(const float (&c)[12], float px, float
 }
 
 
+// ---- cross-lane moves in registers (gfx950) ---------------------------------------------------------------------
+// __shfl_xor / __shfl_up are ds_bpermute_b32: a round trip through the LDS crossbar and a wait per dependent step.
+// The same exchanges exist in the vector ALU: v_permlane32_swap / v_permlane16_swap trade registers between the
+// halves of a wavefront / the odd and even rows of 16 lanes, and a DPP move reads another lane of the same row.
+// All of them read whatever an INACTIVE lane's register holds: call them with all 64 lanes active (wave-uniform
+// control flow) only.  Builtins, not inline assembly: the hazard recogniser places the wait states between a vector
+// write and a swap / DPP read of the same register.
+#define SF_DPP_QUAD_XOR1 0xB1     // quad_perm:[1,0,3,2]
+#define SF_DPP_QUAD_XOR2 0x4E     // quad_perm:[2,3,0,1]
+#define SF_DPP_ROW_SHL4 0x104     // lane i reads lane i + 4 of its row
+#define SF_DPP_ROW_SHR1 0x111     // lane i reads lane i - n of its row (row_shr:n = 0x110 + n)
+#define SF_DPP_ROW_SHR2 0x112
+#define SF_DPP_ROW_SHR4 0x114
+#define SF_DPP_ROW_SHR8 0x118
+#define SF_DPP_ROW_ROR8 0x128     // lane i reads lane (i + 8) mod 16 of its row
+#define SF_DPP_ROW_MIRROR 0x140   // lane i reads lane 15 - i of its row
+#define SF_DPP_ROW_HALF_MIRROR 0x141   // lane i reads lane 7 - i of its half row
+#define SF_DPP_ROW_BCAST15 0x142  // lane 15 of a row to every lane of the next row
+#define SF_DPP_ROW_BCAST31 0x143  // lane 31 to every lane of rows 2 and 3
+
+// x of lane (lane ^ OFF), OFF = 1, 2, 4, 8: one DPP move (two bank-masked ones for 4: banks 0 and 2 of a row read
+// four lanes up, banks 1 and 3 four lanes down).
+template <int OFF>
+__device__ __forceinline__ int lane_xor_dpp(int x) {
+  static_assert(OFF == 1 || OFF == 2 || OFF == 4 || OFF == 8, "a lane distance inside a row of 16");
+  if constexpr (OFF == 1) return __builtin_amdgcn_mov_dpp(x, SF_DPP_QUAD_XOR1, 0xf, 0xf, false);
+  else if constexpr (OFF == 2) return __builtin_amdgcn_mov_dpp(x, SF_DPP_QUAD_XOR2, 0xf, 0xf, false);
+  else if constexpr (OFF == 8) return __builtin_amdgcn_mov_dpp(x, SF_DPP_ROW_ROR8, 0xf, 0xf, false);
+  else {
+    const int t = __builtin_amdgcn_mov_dpp(x, SF_DPP_ROW_SHL4, 0xf, 0x5, false);
+    return __builtin_amdgcn_update_dpp(t, x, SF_DPP_ROW_SHR4, 0xf, 0xa, false);
+  }
+}
+template <int OFF>
+__device__ __forceinline__ double lane_xor_dpp(double x) {
+  return __hiloint2double(lane_xor_dpp<OFF>(__double2hiint(x)), lane_xor_dpp<OFF>(__double2loint(x)));
+}
+
+// OFF = 32 / 16: the lanes with (lane & OFF) != 0 trade their a for the b of lane ^ OFF; the other a's and b's stay.
+// Afterwards a lane without the bit holds (its a, the partner's a) and a lane with it (the partner's b, its b).
+template <int OFF>
+__device__ __forceinline__ void lane_swap(unsigned& a, unsigned& b) {
+  static_assert(OFF == 16 || OFF == 32, "the two swap distances");
+  if constexpr (OFF == 32) {
+    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = r[0]; b = r[1];
+  } else {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0]; b = r[1];
+  }
+}
+template <int OFF>
+__device__ __forceinline__ void lane_swap(double& a, double& b) {
+  unsigned al = (unsigned)__double2loint(a), ah = (unsigned)__double2hiint(a);
+  unsigned bl = (unsigned)__double2loint(b), bh = (unsigned)__double2hiint(b);
+  lane_swap<OFF>(al, bl);
+  lane_swap<OFF>(ah, bh);
+  a = __hiloint2double((int)ah, (int)al);
+  b = __hiloint2double((int)bh, (int)bl);
+}
+
+// Inclusive prefix sum / prefix maximum over the 64 lanes of a wavefront: four shifts inside the rows of 16 (a lane
+// without a source keeps `old`: 0 for the sum, its own value for the maximum), then the last lane of row 0 / 2 into
+// row 1 / 3 and lane 31 into the upper half.  Six dependent vector instructions (the DPP read folds into the add).
+__device__ __forceinline__ int wave_scan_add(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, SF_DPP_ROW_SHR1, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, SF_DPP_ROW_SHR2, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, SF_DPP_ROW_SHR4, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, SF_DPP_ROW_SHR8, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, SF_DPP_ROW_BCAST15, 0xa, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, SF_DPP_ROW_BCAST31, 0xc, 0xf, false);
+  return v;
+}
+__device__ __forceinline__ int wave_scan_max(int v) {
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, SF_DPP_ROW_SHR1, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, SF_DPP_ROW_SHR2, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, SF_DPP_ROW_SHR4, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, SF_DPP_ROW_SHR8, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, SF_DPP_ROW_BCAST15, 0xa, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, SF_DPP_ROW_BCAST31, 0xc, 0xf, false));
+  return v;
+}
+
+// Sum / maximum over the 64 lanes, the total in every lane (what the __shfl_xor loop over 32 .. 1 leaves): lanes
+// ^1 and ^2 inside the quads, the mirrored quad and the mirrored half row (every lane of a quad / half row holds the
+// same value by then, so the mirror pairs the same groups as ^4 / ^8), then the two swaps.  Integers: any pairing
+// gives the same total.
+template <class OP>
+__device__ __forceinline__ int wave_reduce_i(int v, OP op) {
+  v = op(v, __builtin_amdgcn_mov_dpp(v, SF_DPP_QUAD_XOR1, 0xf, 0xf, false));
+  v = op(v, __builtin_amdgcn_mov_dpp(v, SF_DPP_QUAD_XOR2, 0xf, 0xf, false));
+  v = op(v, __builtin_amdgcn_mov_dpp(v, SF_DPP_ROW_HALF_MIRROR, 0xf, 0xf, false));
+  v = op(v, __builtin_amdgcn_mov_dpp(v, SF_DPP_ROW_MIRROR, 0xf, 0xf, false));
+  unsigned a = (unsigned)v, b = (unsigned)v;
+  lane_swap<16>(a, b);
+  v = op((int)a, (int)b);
+  a = (unsigned)v; b = (unsigned)v;
+  lane_swap<32>(a, b);
+  return op((int)a, (int)b);
+}
+__device__ __forceinline__ int wave_sum(int v) { return wave_reduce_i(v, [](int x, int y) { return x + y; }); }
+__device__ __forceinline__ int wave_max(int v) { return wave_reduce_i(v, [](int x, int y) { return max(x, y); }); }
+// (packed 64-bit counters: both words travel, the add carries)
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_mov64(unsigned long long x) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)x, CTRL, 0xf, 0xf, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_mov_dpp((int)(unsigned)(x >> 32), CTRL, 0xf, 0xf, false);
+  return ((unsigned long long)hi << 32) | lo;
+}
+template <int OFF>
+__device__ __forceinline__ unsigned long long swap_sum64(unsigned long long v) {
+  unsigned al = (unsigned)v, ah = (unsigned)(v >> 32), bl = al, bh = ah;
+  lane_swap<OFF>(al, bl);
+  lane_swap<OFF>(ah, bh);
+  return (((unsigned long long)ah << 32) | al) + (((unsigned long long)bh << 32) | bl);
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+  v += dpp_mov64<SF_DPP_QUAD_XOR1>(v);
+  v += dpp_mov64<SF_DPP_QUAD_XOR2>(v);
+  v += dpp_mov64<SF_DPP_ROW_HALF_MIRROR>(v);
+  v += dpp_mov64<SF_DPP_ROW_MIRROR>(v);
+  v = swap_sum64<16>(v);
+  return swap_sum64<32>(v);
+}
+
 // Block-wide sum of N doubles per thread (256 threads) in the canonical order of DESIGN.md section 4:
 // inside each wavefront the xor butterfly over lane distances 32, 16, 8, 4, 2, 1 (own + partner), then
 // the four wave totals folded left to right.  The butterfly is evaluated TRANSPOSED: at every stage a
@@ -275,41 +400,94 @@ __device__ __forceinline__ float residual2(const float (&c)[12], float px, float
 // additions are exactly the butterfly's (a + b is commutative in IEEE arithmetic, both lanes of a pair
 // would have computed the same sum) but only ~N cross-lane moves are issued instead of 6 N -- the
 // full butterfly made the LDS crossbar the bottleneck of the refinement loops.
+// LANES (the default): the trades stay in registers.  At distances 32 and 16 the pair (w[k], w[k + C/2]) goes through
+// lane_swap, after which each half of the pair holds "kept" and "received" in the two registers -- no select -- and
+// adds them; at 8, 4, 2 and 1 the traded value comes through a DPP move.  The pairs of values added are those of the
+// __shfl_xor form (LANES = false, kept selectable for an instantiation whose register allocation the new form
+// upsets); after a swap the lanes with the distance bit set add "received + kept" where that form adds "kept +
+// received".  Every non-NaN sum is the same bits.  Where BOTH addends are NaNs the result is still a NaN, but the
+// hardware returns the quieted payload (and sign) of its first operand, so which of the two payloads survives can
+// differ from the old form in those lanes -- as it already could between the two lanes of a pair.  Nothing reads a
+// payload: a NaN total fails every comparison that follows.
+// All 64 lanes must be active (see above).
 // red: [4][STRIDE] doubles of LDS scratch, STRIDE >= the power of two above N.
-template <int C>
-__device__ __forceinline__ void sum_stage(double (&w)[32], int& idx, int lane, int off) {
-  if constexpr (C > 1) {
-    const bool up = (lane & off) != 0;
+#ifndef SF_SUM_LANES
+#define SF_SUM_LANES 1            // (-DSF_SUM_LANES=0: every canonical sum on the __shfl_xor form, for A/B builds)
+#endif
+template <int C, int OFF, bool LANES>
+__device__ __forceinline__ void sum_stage(double (&w)[32], int& idx, int lane) {
+  if constexpr (!LANES) {
+    if constexpr (C > 1) {
+      const bool up = (lane & OFF) != 0;
 #pragma unroll
-    for (int k = 0; k < C / 2; ++k) {
-      const double send = up ? w[k] : w[k + C / 2];
-      const double keep = up ? w[k + C / 2] : w[k];
-      w[k] = keep + __shfl_xor(send, off);
+      for (int k = 0; k < C / 2; ++k) {
+        const double send = up ? w[k] : w[k + C / 2];
+        const double keep = up ? w[k + C / 2] : w[k];
+        w[k] = keep + __shfl_xor(send, OFF);
+      }
+      idx += up ? C / 2 : 0;
+    } else {
+      w[0] = w[0] + __shfl_xor(w[0], OFF);
     }
-    idx += up ? C / 2 : 0;
+  } else if constexpr (OFF >= 16) {
+    if constexpr (C > 1) {
+#pragma unroll
+      for (int k = 0; k < C / 2; ++k) {
+        double a = w[k], b = w[k + C / 2];
+        lane_swap<OFF>(a, b);
+        w[k] = a + b;
+      }
+      idx += (lane & OFF) ? C / 2 : 0;
+    } else {
+      double a = w[0], b = w[0];
+      lane_swap<OFF>(a, b);
+      w[0] = a + b;
+    }
   } else {
-    w[0] = w[0] + __shfl_xor(w[0], off);
+    if constexpr (C > 1) {
+      const bool up = (lane & OFF) != 0;
+#pragma unroll
+      for (int k = 0; k < C / 2; ++k) {
+        const double send = up ? w[k] : w[k + C / 2];
+        const double keep = up ? w[k + C / 2] : w[k];
+        w[k] = keep + lane_xor_dpp<OFF>(send);
+      }
+      idx += up ? C / 2 : 0;
+    } else {
+      w[0] = w[0] + lane_xor_dpp<OFF>(w[0]);
+    }
   }
 }
 
-template <int N, int STRIDE>
-__device__ __forceinline__ void block_sum_canon(double (&v)[N], double* red, int tid) {
+// The six stages on the P (a power of two) values of w: the total of value idx ends in w[0].
+template <int P, bool LANES>
+__device__ __forceinline__ void sum_stages(double (&w)[32], int& idx, int lane) {
+  sum_stage<P, 32, LANES>(w, idx, lane);
+  sum_stage<(P / 2 > 1 ? P / 2 : 1), 16, LANES>(w, idx, lane);
+  sum_stage<(P / 4 > 1 ? P / 4 : 1), 8, LANES>(w, idx, lane);
+  sum_stage<(P / 8 > 1 ? P / 8 : 1), 4, LANES>(w, idx, lane);
+  sum_stage<(P / 16 > 1 ? P / 16 : 1), 2, LANES>(w, idx, lane);
+  sum_stage<(P / 32 > 1 ? P / 32 : 1), 1, LANES>(w, idx, lane);
+}
+
+// live (wave-uniform): false for a wavefront none of whose lanes holds an element -- its partials are all +0.0 and so
+// are their sums, so it writes +0.0 to its row of `red` and skips the stages.
+template <int N, int STRIDE, bool LANES = (SF_SUM_LANES != 0)>
+__device__ __forceinline__ void block_sum_canon(double (&v)[N], double* red, int tid, bool live = true) {
   static_assert(N >= 1 && N <= 32 && STRIDE >= N, "at most 32 values");
   constexpr int P = N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : 32;
   static_assert(STRIDE >= P, "scratch rows must hold the padded count");
   const int lane = tid & 63, wave = tid >> 6;
   double w[32];
-#pragma unroll
-  for (int k = 0; k < 32; ++k) w[k] = k < N ? v[k] : 0.0;
   int idx = 0;
-  sum_stage<P>(w, idx, lane, 32);
-  sum_stage<(P / 2 > 1 ? P / 2 : 1)>(w, idx, lane, 16);
-  sum_stage<(P / 4 > 1 ? P / 4 : 1)>(w, idx, lane, 8);
-  sum_stage<(P / 8 > 1 ? P / 8 : 1)>(w, idx, lane, 4);
-  sum_stage<(P / 16 > 1 ? P / 16 : 1)>(w, idx, lane, 2);
-  sum_stage<(P / 32 > 1 ? P / 32 : 1)>(w, idx, lane, 1);
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 32; ++k) w[k] = k < N ? v[k] : 0.0;
+    sum_stages<P, LANES>(w, idx, lane);
+  }
   __syncthreads();  // previous users of `red` are done
-  red[wave * STRIDE + idx] = w[0];   // every lane of a group holds the same total: identical writes
+  if (live) red[wave * STRIDE + idx] = w[0];   // every lane of a group holds the same total: identical writes
+  else if (lane < P) red[wave * STRIDE + lane] = 0.0;
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < N; ++k) v[k] = ((red[k] + red[STRIDE + k]) + red[2 * STRIDE + k]) + red[3 * STRIDE + k];
@@ -320,13 +498,16 @@ __device__ __forceinline__ void block_sum_canon(double (&v)[N], double* red, int
 // 4 / NW wavefronts of the 256-thread version one after the other -- the same strided partials, the same in-wave
 // stages, the same four-row fold, hence the same bits.  NW = 4 is the 256-thread form (partials +
 // block_sum_canon).  tid = 64 * (wavefront index among the NW) + lane.  `red` as above.
-template <int N, int STRIDE, int NW, class F>
+// In every width a wavefront of the canonical scheme with no element (64 * its index >= m) skips its partials and
+// stages and writes +0.0 to its row.
+template <int N, int STRIDE, int NW, bool LANES = (SF_SUM_LANES != 0), class F>
 __device__ __forceinline__ void canon_reduce(int m, int tid, double* red, double (&out)[N], F acc) {
   if constexpr (NW == 4) {
+    const bool live = 64 * (tid >> 6) < m;
 #pragma unroll
     for (int k = 0; k < N; ++k) out[k] = 0.0;
-    for (int i = tid; i < m; i += 256) acc(i, out);
-    block_sum_canon<N, STRIDE>(out, red, tid);
+    if (live) for (int i = tid; i < m; i += 256) acc(i, out);
+    block_sum_canon<N, STRIDE, LANES>(out, red, tid, live);
   } else {
     static_assert(NW == 1 || NW == 2, "one, two or four wavefronts");
     constexpr int P = N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : 32;
@@ -352,12 +533,7 @@ __device__ __forceinline__ void canon_reduce(int m, int tid, double* red, double
         for (int k = 0; k < N; ++k) w[k] = v[k];
       }
       int idx = 0;
-      sum_stage<P>(w, idx, lane, 32);
-      sum_stage<(P / 2 > 1 ? P / 2 : 1)>(w, idx, lane, 16);
-      sum_stage<(P / 4 > 1 ? P / 4 : 1)>(w, idx, lane, 8);
-      sum_stage<(P / 8 > 1 ? P / 8 : 1)>(w, idx, lane, 4);
-      sum_stage<(P / 16 > 1 ? P / 16 : 1)>(w, idx, lane, 2);
-      sum_stage<(P / 32 > 1 ? P / 32 : 1)>(w, idx, lane, 1);
+      sum_stages<P, LANES>(w, idx, lane);
       red[vw * STRIDE + idx] = w[0];
     }
     __syncthreads();
@@ -368,25 +544,24 @@ __device__ __forceinline__ void canon_reduce(int m, int tid, double* red, double
 
 // Same sums, but the N totals are left in LDS (out[0..N)) instead of in every thread's registers: for
 // callers that only need them as operands of a short scalar computation (k_pnp's 28-value normal
-// equations would otherwise pin 56 VGPRs per copy).  out must not alias red.
-template <int N, int STRIDE>
-__device__ __forceinline__ void block_sum_canon_to_lds(const double (&v)[N], double* red, double* out, int tid) {
+// equations would otherwise pin 56 VGPRs per copy).  out must not alias red.  live: as block_sum_canon's.
+template <int N, int STRIDE, bool LANES = (SF_SUM_LANES != 0)>
+__device__ __forceinline__ void block_sum_canon_to_lds(const double (&v)[N], double* red, double* out, int tid,
+                                                       bool live = true) {
   static_assert(N >= 1 && N <= 32 && STRIDE >= N, "at most 32 values");
   constexpr int P = N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : 32;
   static_assert(STRIDE >= P, "scratch rows must hold the padded count");
   const int lane = tid & 63, wave = tid >> 6;
   double w[32];
-#pragma unroll
-  for (int k = 0; k < 32; ++k) w[k] = k < N ? v[k] : 0.0;
   int idx = 0;
-  sum_stage<P>(w, idx, lane, 32);
-  sum_stage<(P / 2 > 1 ? P / 2 : 1)>(w, idx, lane, 16);
-  sum_stage<(P / 4 > 1 ? P / 4 : 1)>(w, idx, lane, 8);
-  sum_stage<(P / 8 > 1 ? P / 8 : 1)>(w, idx, lane, 4);
-  sum_stage<(P / 16 > 1 ? P / 16 : 1)>(w, idx, lane, 2);
-  sum_stage<(P / 32 > 1 ? P / 32 : 1)>(w, idx, lane, 1);
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 32; ++k) w[k] = k < N ? v[k] : 0.0;
+    sum_stages<P, LANES>(w, idx, lane);
+  }
   __syncthreads();  // previous users of `red` / `out` are done
-  red[wave * STRIDE + idx] = w[0];
+  if (live) red[wave * STRIDE + idx] = w[0];
+  else if (lane < P) red[wave * STRIDE + lane] = 0.0;
   __syncthreads();
   if (tid < N) out[tid] = ((red[tid] + red[STRIDE + tid]) + red[2 * STRIDE + tid]) + red[3 * STRIDE + tid];
   __syncthreads();
@@ -397,15 +572,18 @@ __device__ __forceinline__ void block_sum_canon_to_lds(const double (&v)[N], dou
 // the other (see canon_reduce).  `acc(i, v)` adds element i's terms to v[0..N).
 // ONCE: the caller guarantees m <= 256 -- every lane of the canonical scheme has at most one element, so its partial is
 // 0.0 + that element's terms and no accumulator stays live across a loop.
-template <int N, int STRIDE, int NW, bool ONCE = false, class F>
+template <int N, int STRIDE, int NW, bool ONCE = false, bool LANES = (SF_SUM_LANES != 0), class F>
 __device__ __forceinline__ void canon_reduce_to_lds(int m, int tid, double* red, double* out, F acc) {
   if constexpr (NW == 4) {
+    const bool live = 64 * (tid >> 6) < m;
     double v[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) v[k] = 0.0;
-    if constexpr (ONCE) { if (tid < m) acc(tid, v); }
-    else { for (int i = tid; i < m; i += 256) acc(i, v); }
-    block_sum_canon_to_lds<N, STRIDE>(v, red, out, tid);
+    if (live) {
+      if constexpr (ONCE) { if (tid < m) acc(tid, v); }
+      else { for (int i = tid; i < m; i += 256) acc(i, v); }
+    }
+    block_sum_canon_to_lds<N, STRIDE, LANES>(v, red, out, tid, live);
   } else {
     static_assert(NW == 1 || NW == 2, "one, two or four wavefronts");
     constexpr int P = N <= 1 ? 1 : N <= 2 ? 2 : N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : 32;
@@ -432,12 +610,7 @@ __device__ __forceinline__ void canon_reduce_to_lds(int m, int tid, double* red,
         for (int k = 0; k < N; ++k) w[k] = v[k];
       }
       int idx = 0;
-      sum_stage<P>(w, idx, lane, 32);
-      sum_stage<(P / 2 > 1 ? P / 2 : 1)>(w, idx, lane, 16);
-      sum_stage<(P / 4 > 1 ? P / 4 : 1)>(w, idx, lane, 8);
-      sum_stage<(P / 8 > 1 ? P / 8 : 1)>(w, idx, lane, 4);
-      sum_stage<(P / 16 > 1 ? P / 16 : 1)>(w, idx, lane, 2);
-      sum_stage<(P / 32 > 1 ? P / 32 : 1)>(w, idx, lane, 1);
+      sum_stages<P, LANES>(w, idx, lane);
       red[vw * STRIDE + idx] = w[0];
     }
     __syncthreads();

@@ -5,7 +5,7 @@ launch, reads the [pair][48] wall-clock stamps thread 0 of every workgroup left,
 ran the whole chain, the mean / median / p90 duration of every phase -- under load (the 10 000-pair launch) and
 uncontended (a launch with fewer surviving pairs than CUs).  Also the launch's wall time from HIP events.
 
-usage: python tools/chain_trace.py [n_pairs=10000] [k=500] [cols=32] [iterations=500] [pnp]
+usage: [SEPFINDER_TRACE_LIB=other_trace.so] python tools/chain_trace.py [n_pairs=10000] [k=500] [cols=32] [iterations=500] [pnp]
 """
 import ctypes
 import os
@@ -14,7 +14,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
-os.environ["SEPFINDER_LIB"] = os.path.join(ROOT, "multi_robot_slam_separators_amd", "libsepfinder_trace.so")
+# (SEPFINDER_TRACE_LIB: another trace build, e.g. the parent commit's for an A/B of the phases)
+os.environ["SEPFINDER_LIB"] = os.environ.get("SEPFINDER_TRACE_LIB") or os.path.join(
+    ROOT, "multi_robot_slam_separators_amd", "libsepfinder_trace.so")
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
