@@ -79,6 +79,9 @@ extern "C" {
 /* 8, additions: sf_stereo_params, sf_stereo_defaults, sf_stereo_set_params, sf_stereo_get_params,
       sf_stereo_block_match_device (Stereo/OpticalFlow false: block-matching stereo correspondence).  A fresh handle runs
       pyramidal LK as before; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.     */
+/* 8, additions: sf_grid_params, sf_grid_defaults, sf_grid_set_params, sf_grid_get_params, sf_compute_grid (Vis/GridRows x
+      Vis/GridCols: the detector per cell of the ROI; 1 x 1 on a fresh handle, which changes nothing); the version
+      number, sizeof(sf_front_params), sizeof(sf_params) and SF_K_COUNT stay.                                          */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -506,6 +509,47 @@ int  sf_front_get_params(sf_handle h, sf_front_params* params);
 /* Feature2D::computeRoi as above, pure host code: roi_xywh = {x, y, width, height}.  SF_EINVAL for a ratio outside
    [0, 1], an image side < 1 or a ROI side < 3 (the rectangle is written whenever the ratios are valid).             */
 int  sf_compute_roi(int32_t width, int32_t height, const float ratios[4], int32_t roi_xywh[4]);
+/* The third step of Feature2D::generateKeypoints, Vis/GridRows x Vis/GridCols [upstream rtabmap 0.19 / 0.20, restated in
+   tests/grid_ref.py; DESIGN.md section 3 item 17f lists what the restatement decides; the reference forwards both keys at
+   myRegistrationVis.cpp:84-85 and 171-178].  With R = grid_rows, C = grid_cols and (X, Y, W, H) the rectangle of
+   sf_compute_roi:
+     row_size = H / R;  col_size = W / C;      (integer division: the W % C right-most columns and the H % R bottom rows of
+                                                the ROI are seen by no cell)
+     quota    = ceil((float)max_features / (float)(R * C))
+     for i in 0 .. R-1, for j in 0 .. C-1:     (row-major)
+       the detector on image(X + j col_size, Y + i row_size, col_size, row_size) as an image of its own, at most `quota`
+       keypoints, shifted by the cell's origin, appended
+   and then the refinement above on the full image.  A keyframe holds up to rows_cap = R C quota keypoints, which can
+   exceed max_features (1000 on 3 x 3: 9 x 112 = 1008); upstream does not truncate and neither does this.
+   Type 4: sf_detect_fast_device on the cell with max_features = quota (limitKeypoints); no corner within 3 px of a cell
+   edge, cells below 7 x 7 give none.  Types 6 and 8: sf_detect_corners_device on the cell with max_corners = quota -- the
+   cell's strongest corners at min_distance, against quality_level x the CELL's own maximum, the cell edge reflecting.
+   That is a listed deviation: upstream hands GFTT the full Vis/MaxFeatures per cell and limitKeypoints then keeps the
+   LAST quota of a list whose responses are all 0, the cell's weakest corners.
+   NOT built: a grid under feature type 2 (as the ROI: a second pyramid); the extraction calls on a type-2 handle with a
+   grid other than 1 x 1 return SF_EINVAL, say so and change nothing.  Not FAST/GridRows, FAST/GridCols (per-cell
+   adaptive thresholds inside the FAST detector) either.
+   The grid is honoured by sf_get_features_and_descriptor, its _u8 form, sf_get_features_and_descriptor_batch_device and
+   sf_add_keyframes_u8_batch_device.  The batch forms stay one launch sequence with no host wait: the cells are the images
+   of the detector's one batch launch, one more kernel joins their lists.  UNDER A GRID THE ROW STRIDE of the batch calls'
+   per-keyframe outputs (d_desc_out, d_xyz_out, d_kpts_out) and the row capacity the store is given is rows_cap, not
+   max_features (sf_compute_grid tells).  A call whose cells fall below 3 px returns SF_EINVAL, one whose rows_cap exceeds
+   SF_MAX_FEATURES or whose n_keyframes R C exceeds 65535 SF_ERANGE, before the store or the NN database change.  A fresh
+   handle has 1 x 1: no cell, no new launch, every byte as before.  The explicit sf_detect_*_device calls are untouched.  */
+typedef struct sf_grid_params {
+  int32_t grid_rows;      /* Vis/GridRows, 1; 1 .. 16                                                                  */
+  int32_t grid_cols;      /* Vis/GridCols, 1; 1 .. 16                                                                  */
+} sf_grid_params;         /* 8 bytes */
+void sf_grid_defaults(sf_grid_params* p);
+/* A value outside 1 .. 16 returns SF_EINVAL and changes nothing.                                                      */
+int  sf_grid_set_params(sf_handle h, const sf_grid_params* params);
+int  sf_grid_get_params(sf_handle h, sf_grid_params* params);
+/* The cells as above, pure host code: out = {x, y, col_size, row_size, quota, rows_cap}, (x, y) the first cell's origin
+   (the ROI's).  roi_ratios NULL = no ROI, grid NULL = 1 x 1.  SF_EINVAL for what sf_compute_roi refuses, a grid value
+   outside 1 .. 16, max_features < 1 or a cell side below 3; SF_ERANGE when rows_cap > SF_MAX_FEATURES (out is written
+   whenever the arguments before it are valid).                                                                        */
+int  sf_compute_grid(int32_t width, int32_t height, const float roi_ratios[4], const sf_grid_params* grid,
+                     int32_t max_features, int32_t out[6]);
 /* cv::cornerSubPix on n keypoints of a device image, in place and asynchronous on the handle's stream; writes only x and
    y of each 28-byte record.  Per corner, from c = c0: the (2 win + 3)^2 float patch of cv::getRectSubPix around c
    (bilinear, taps outside the image clamped to the edge), central differences, the separable Gaussian mask

@@ -218,6 +218,41 @@ def compute_roi(width, height, ratios):
     return x, y, w, h
 
 
+class GridParams(C.Structure):
+    """sf_grid_params (include/sepfinder.h): Vis/GridRows x Vis/GridCols of Feature2D::generateKeypoints -- the detector of
+    feature types 4, 6 and 8 runs on every cell of the ROI and keeps ceil(max_features / cells) keypoints there."""
+    _fields_ = [("grid_rows", C.c_int32), ("grid_cols", C.c_int32)]
+
+
+assert C.sizeof(GridParams) == 8
+
+
+def grid_params(grid_rows=1, grid_cols=1):
+    """rtabmap's defaults (what sf_grid_defaults fills): 1 x 1, no cells."""
+    p = GridParams()
+    p.grid_rows, p.grid_cols = grid_rows, grid_cols
+    return p
+
+
+def compute_grid(width, height, roi_ratios, grid_rows, grid_cols, max_features):
+    """The cells of Vis/GridRows x Vis/GridCols restated: (x, y, col_size, row_size, quota, rows_cap) -- the first cell's
+    origin (the ROI's), the cells' size (integer division: the remainder columns and rows belong to no cell), the
+    keypoints a cell may keep, ceil(max_features / cells) in float32, and the rows a keyframe can hold.  ValueError for what
+    sf_compute_grid answers with SF_EINVAL (compute_roi's refusals, a grid value outside 1 .. 16, max_features < 1, a cell
+    side below 3), OverflowError for its SF_ERANGE (rows_cap > SF_MAX_FEATURES)."""
+    if not (1 <= grid_rows <= 16 and 1 <= grid_cols <= 16) or max_features < 1:
+        raise ValueError("Vis/GridRows %d, Vis/GridCols %d, %d features" % (grid_rows, grid_cols, max_features))
+    x, y, w, h = compute_roi(width, height, roi_ratios)
+    cells = grid_rows * grid_cols
+    quota = int(np.ceil(np.float32(max_features) / np.float32(cells)))
+    col_size, row_size = w // grid_cols, h // grid_rows
+    if col_size < 3 or row_size < 3:
+        raise ValueError("%d x %d cells of %d x %d in a ROI of %d x %d" % (grid_rows, grid_cols, col_size, row_size, w, h))
+    if cells * quota > SF_MAX_FEATURES:
+        raise OverflowError("%d cells of %d keypoints > %d" % (cells, quota, SF_MAX_FEATURES))
+    return x, y, col_size, row_size, quota, cells * quota
+
+
 class OrbDetectorParams(C.Structure):
     """sf_orb_detector_params (include/sepfinder.h): rtabmap's ORB/ parameters of the ORB detector (Vis/FeatureType 2)."""
     _fields_ = [("scale_factor", C.c_float), ("n_levels", C.c_int32), ("first_level", C.c_int32), ("score_type", C.c_int32),

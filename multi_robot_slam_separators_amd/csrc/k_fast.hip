@@ -53,10 +53,11 @@ __device__ __forceinline__ bool fast_run9(unsigned m) {
 
 __global__ void __launch_bounds__(256)
 k_fast_score(const uint8_t* __restrict__ img, int w, int h, int pitch, int t, uint8_t* __restrict__ score, size_t img_stride,
-             size_t plane_stride) {
-  // (blockIdx.z = image of a batch: images img_stride bytes apart, score planes plane_stride bytes apart)
+             size_t plane_stride, SfCells cells) {
+  // (blockIdx.z = image of a batch: images img_stride bytes apart -- or the cells of a grid inside them, sf_cell_base --
+  // score planes plane_stride bytes apart.  The dword path is chosen per image: cells of one launch differ in alignment)
   __shared__ __attribute__((aligned(4))) uint8_t tile[FAST_LH * FAST_LW];
-  img += blockIdx.z * img_stride;
+  img += sf_cell_base(blockIdx.z, img_stride, cells);
   score += blockIdx.z * plane_stride;
   const int x0 = blockIdx.x * FAST_TW, y0 = blockIdx.y * FAST_TH;
   const bool aligned = (((uintptr_t)img | (uintptr_t)pitch) & 3u) == 0u;
@@ -197,10 +198,10 @@ constexpr int FAST_REKEY_BLOCKS = 32;
 // ORB's pyramid levels in k_orb_detect.hip)
 void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
                           int threshold, int nonmax, uint8_t* score, size_t plane_stride, unsigned long long* keys, unsigned* count,
-                          unsigned key_cap) {
+                          unsigned key_cap, const SfCells& cells) {
   const dim3 block(256);
   hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH, n_img), block, 0,
-                     c->stream, d_images, width, height, pitch, threshold, score, img_stride, plane_stride);
+                     c->stream, d_images, width, height, pitch, threshold, score, img_stride, plane_stride, cells);
   hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS, n_img), block, 0,
                      c->stream, (const uint8_t*)score, width, height, nonmax, keys, count, key_cap, plane_stride);
 }
@@ -209,11 +210,11 @@ void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_str
 // keys, in the form of the order that applies to it, their count and its segment of the key array are on the device when
 // the stream gets there
 static int fast_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
-                      int max_features, const sf_fast_params* prm, SfDetectorWork* F) {
+                      int max_features, const sf_fast_params* prm, const SfCells& cells, SfDetectorWork* F) {
   int rc = sf_detector_work(c, width, height, n_img, (size_t)width * height, F);
   if (rc != SF_OK) return rc;
   sf_launch_fast_level(c, d_images, img_stride, n_img, width, height, pitch, prm->threshold, prm->nonmax_suppression,
-                       (uint8_t*)c->gf_planes.p, (size_t)F->key_cap, F->keys, F->count, F->key_cap);
+                       (uint8_t*)c->gf_planes.p, (size_t)F->key_cap, F->keys, F->count, F->key_cap, cells);
   hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, n_img), dim3(256), 0, c->stream, F->keys, (const unsigned*)F->count,
                      F->key_cap, max_features, F->seg_begin, F->seg_end);
   SF_HIP(c, hipGetLastError());
@@ -226,7 +227,7 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
                           const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out) {
   SfDetectorWork F;
   int rc;
-  if ((rc = fast_front(c, d_image, 0, 1, width, height, pitch, max_features, prm, &F)) != SF_OK) return rc;
+  if ((rc = fast_front(c, d_image, 0, 1, width, height, pitch, max_features, prm, SfCells(), &F)) != SF_OK) return rc;
   unsigned h_count = 0;
   if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
   const int n = (int)std::min(h_count, F.key_cap);
@@ -242,13 +243,14 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
 
 // The detector on a batch of images of one size, no host round trip: corner counts and the choice of order stay on the
 // device, a segmented sort takes the place of the sort sized by the host.  d_kpts_out [n_img][cap], d_n_out [n_img]
-// (device).  max_features > 0 here (the batch's outputs are sized by it).
+// (device).  max_features > 0 here (the batch's outputs are sized by it).  With `cells` the n_img images are the cells of
+// a grid inside n_img / cells.per_image images (width x height: one cell), keypoints in the cell's own coordinates.
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out) {
+                                int32_t* d_n_out, const SfCells& cells) {
   SfDetectorWork F;
   int rc;
-  if ((rc = fast_front(c, d_images, img_stride, n_img, width, height, pitch, max_features, prm, &F)) != SF_OK) return rc;
+  if ((rc = fast_front(c, d_images, img_stride, n_img, width, height, pitch, max_features, prm, cells, &F)) != SF_OK) return rc;
   if ((rc = sf_sort_keys_segmented_desc(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img,
                                         F.seg_begin, F.seg_end, 0, FAST_KEY_BITS)) != SF_OK)
     return rc;

@@ -31,11 +31,12 @@ namespace {
 
 __global__ void __launch_bounds__(256)
 k_gftt_products(const uint8_t* __restrict__ img, int w, int h, int pitch, float s1, float s2, float* __restrict__ dxx,
-                float* __restrict__ dxy, float* __restrict__ dyy, size_t img_stride, size_t plane_stride) {
-  // (blockIdx.z = image of a batch: images img_stride bytes apart, every image's planes plane_stride floats apart)
+                float* __restrict__ dxy, float* __restrict__ dyy, size_t img_stride, size_t plane_stride, SfCells cells) {
+  // (blockIdx.z = image of a batch: images img_stride bytes apart -- or the cells of a grid inside them, sf_cell_base --
+  // every image's planes plane_stride floats apart)
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= w || y >= h) return;
-  img += blockIdx.z * img_stride;
+  img += sf_cell_base(blockIdx.z, img_stride, cells);
   dxx += blockIdx.z * plane_stride; dxy += blockIdx.z * plane_stride; dyy += blockIdx.z * plane_stride;
   const int xm = reflect101(x - 1, w), xp = reflect101(x + 1, w);
   const uint8_t* ru = img + (size_t)reflect101(y - 1, h) * pitch;
@@ -279,7 +280,7 @@ __global__ void k_gftt_segments(const unsigned* __restrict__ count, unsigned key
 // The front half of both launchers -- workspace and the three front kernels for n_img images of one size (blockIdx.z =
 // image): every image's candidate keys and their count are on the device when the stream gets there
 int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
-               double quality_level, SfDetectorWork* F) {
+               double quality_level, const SfCells& cells, SfDetectorWork* F) {
   const size_t np = (size_t)width * height;
   int rc = sf_detector_work(c, width, height, n_img, np * 4 * sizeof(float), F);
   if (rc != SF_OK) return rc;
@@ -291,7 +292,7 @@ int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_
   const double scale = 1.0 / ((double)(1 << 2) * 3.0 * 255.0);
   const dim3 grid((width + 63) / 64, (height + 3) / 4, n_img), block(256);
   hipLaunchKernelGGL(k_gftt_products, grid, block, 0, c->stream, d_images, width, height, pitch, (float)(1.0 * scale),
-                     (float)(2.0 * scale), dxx, dxy, dyy, img_stride, plane_stride);
+                     (float)(2.0 * scale), dxx, dxy, dyy, img_stride, plane_stride, cells);
   hipLaunchKernelGGL(k_gftt_eig, grid, block, 0, c->stream, (const float*)dxx, (const float*)dxy, (const float*)dyy, width,
                      height, eig, F->max_bits, plane_stride);
   const dim3 grid_c((width + 63) / 64, (height + 4 * GFTT_CAND_TILES - 1) / (4 * GFTT_CAND_TILES), n_img);
@@ -318,7 +319,7 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
                              int32_t* n_out) {
   SfDetectorWork F;
   int rc;
-  if ((rc = gftt_front(c, d_image, 0, 1, width, height, pitch, quality_level, &F)) != SF_OK) return rc;
+  if ((rc = gftt_front(c, d_image, 0, 1, width, height, pitch, quality_level, SfCells(), &F)) != SF_OK) return rc;
   unsigned h_count = 0;
   if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
   const int n = (int)std::min(h_count, F.key_cap);
@@ -351,10 +352,12 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
 
 // The detector on a batch of images of one size, no host round trip: candidate counts stay on the device (a segmented
 // sort takes the place of the sort sized by the host), one selection workgroup per image.  d_kpts_out [n_img][cap],
-// d_n_out [n_img] (device).  Needs the LDS bitmap form of the selection (images up to about 1.2 Mpixel).
+// d_n_out [n_img] (device).  Needs the LDS bitmap form of the selection (images up to about 1.2 Mpixel).  With `cells` the
+// n_img images are the cells of a grid inside n_img / cells.per_image images (width x height: one cell; its edge reflects),
+// keypoints in the cell's own coordinates.
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
-                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out) {
+                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells) {
   const int wpr = (width + 31) / 32;
   const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
   const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
@@ -362,7 +365,7 @@ int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_
     return sf_fail(c, SF_ERANGE, "batched corner detection: %d x %d image does not fit the LDS selection bitmap", width, height);
   SfDetectorWork F;
   int rc;
-  if ((rc = gftt_front(c, d_images, img_stride, n_img, width, height, pitch, quality_level, &F)) != SF_OK) return rc;
+  if ((rc = gftt_front(c, d_images, img_stride, n_img, width, height, pitch, quality_level, cells, &F)) != SF_OK) return rc;
   hipLaunchKernelGGL(k_gftt_segments, dim3((n_img + 63) / 64), dim3(64), 0, c->stream, (const unsigned*)F.count, F.key_cap,
                      n_img, F.seg_begin, F.seg_end);
   SF_HIP(c, hipGetLastError());

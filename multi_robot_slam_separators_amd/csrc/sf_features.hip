@@ -1,7 +1,8 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
-// detection (GFTT, FAST, ORB), the ROI and the sub-pixel refinement around it, stereo correspondence, keyframe extraction
-// and the camera-image forms of these calls (kernels in k_extract.hip, k_gftt.hip, k_fast.hip, k_orb_detect.hip,
-// k_subpix.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in sf_sort.hip).
+// detection (GFTT, FAST, ORB), the ROI, the grid of cells and the sub-pixel refinement around it, stereo correspondence,
+// keyframe extraction and the camera-image forms of these calls (kernels in k_extract.hip, k_gftt.hip, k_fast.hip,
+// k_orb_detect.hip, k_subpix.hip, k_grid.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in
+// sf_sort.hip).
 #include <cmath>
 
 #include "sf_host.hpp"
@@ -430,7 +431,13 @@ extern "C" int sf_corner_subpix_device(sf_handle c, const uint8_t* d_image, int3
 struct FrontPlan {
   int x = 0, y = 0, w = 0, h = 0;
   bool refine = false;
-  bool launch() const { return refine || x || y; }         // (an offset of zero and no refinement: no launch at all)
+  // Vis/GridRows x Vis/GridCols (grid_plan): the cells, what each may keep, the rows a keyframe can hold (1 x 1: the ROI,
+  // max_features, max_features).  Under a grid k_grid_gather shifts the keypoints, not k_corner_subpix
+  int rows = 1, cols = 1, col_size = 0, row_size = 0, quota = 0, rows_cap = 0;
+  bool grid() const { return rows * cols > 1; }
+  bool launch() const { return refine || (!grid() && (x || y)); }   // (an offset of zero and no refinement: no launch at all)
+  int off_x() const { return grid() ? 0 : x; }
+  int off_y() const { return grid() ? 0 : y; }
 };
 
 static int front_plan(sf_context* c, int width, int height, FrontPlan* fp) {
@@ -445,6 +452,99 @@ static int front_plan(sf_context* c, int width, int height, FrontPlan* fp) {
   fp->x = roi[0]; fp->y = roi[1]; fp->w = roi[2]; fp->h = roi[3];
   fp->refine = f.subpix_win_size > 0 && f.subpix_iterations > 0;
   return fp->refine ? check_subpix(c, width, height, f.subpix_win_size, f.subpix_iterations) : SF_OK;
+}
+
+// ---- Vis/GridRows x Vis/GridCols: the detector per cell of the ROI (Feature2D::generateKeypoints; kernel in k_grid.hip) ----
+extern "C" void sf_grid_defaults(sf_grid_params* p) {
+  if (!p) return;
+  p->grid_rows = 1;            // Vis/GridRows [upstream rtabmap Parameters.h]
+  p->grid_cols = 1;            // Vis/GridCols
+}
+
+static bool grid_valid(const sf_grid_params& g) {
+  return g.grid_rows >= 1 && g.grid_rows <= 16 && g.grid_cols >= 1 && g.grid_cols <= 16;
+}
+
+extern "C" int sf_grid_set_params(sf_handle c, const sf_grid_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  if (!grid_valid(*params))
+    return sf_fail(c, SF_EINVAL, "Vis/GridRows %d, Vis/GridCols %d: each lies in 1 .. 16", params->grid_rows, params->grid_cols);
+  c->grid = *params;
+  return SF_OK;
+}
+
+extern "C" int sf_grid_get_params(sf_handle c, sf_grid_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  *params = c->grid;
+  return SF_OK;
+}
+
+extern "C" int sf_compute_grid(int32_t width, int32_t height, const float* roi_ratios, const sf_grid_params* grid,
+                               int32_t max_features, int32_t* out) {
+  static const float no_roi[4] = {0.f, 0.f, 0.f, 0.f};
+  const sf_grid_params g = arg_or_defaults(grid, sf_grid_defaults);
+  if (!out || !grid_valid(g) || max_features < 1) return SF_EINVAL;
+  int32_t roi[4];
+  const int rc = sf_compute_roi(width, height, roi_ratios ? roi_ratios : no_roi, roi);
+  if (rc != SF_OK) return rc;
+  const int cells = g.grid_rows * g.grid_cols;
+  const int quota = (int)std::ceil((float)max_features / (float)cells);
+  const long long rows_cap = (long long)cells * quota;
+  out[0] = roi[0]; out[1] = roi[1];
+  out[2] = roi[2] / g.grid_cols; out[3] = roi[3] / g.grid_rows;
+  out[4] = quota;
+  out[5] = (int32_t)std::min(rows_cap, (long long)INT32_MAX);
+  if (out[2] < 3 || out[3] < 3) return SF_EINVAL;
+  return rows_cap > SF_MAX_FEATURES ? SF_ERANGE : SF_OK;
+}
+
+// The cells of an extraction call, behind front_plan and the check of max_features: nothing to do on a 1 x 1 grid (one
+// "cell", the ROI, with the whole of max_features), else what sf_compute_grid says -- refused before anything is touched
+static int grid_plan(sf_context* c, int width, int height, int max_features, FrontPlan* fp) {
+  fp->rows = fp->cols = 1;
+  fp->col_size = fp->w; fp->row_size = fp->h;
+  fp->quota = fp->rows_cap = max_features;
+  const sf_grid_params& g = c->grid;
+  if (g.grid_rows == 1 && g.grid_cols == 1) return SF_OK;
+  if (c->feature_type == 2)
+    return sf_fail(c, SF_EINVAL, "Vis/GridRows x Vis/GridCols %d x %d under Vis/FeatureType 2 (ORB) is not built: every cell would need a pyramid of its own; set the grid to 1 x 1 or choose feature type 4, 6 or 8",
+                   g.grid_rows, g.grid_cols);
+  int32_t o[6];
+  const int rc = sf_compute_grid(width, height, c->front.roi_ratios, &g, max_features, o);
+  if (rc == SF_ERANGE)
+    return sf_fail(c, SF_ERANGE, "a grid of %d x %d cells with %d keypoints apiece holds %d rows > %d (KeyPointVec.size is an int16)",
+                   g.grid_rows, g.grid_cols, o[4], o[5], SF_MAX_FEATURES);
+  if (rc != SF_OK)
+    return sf_fail(c, SF_EINVAL, "a grid of %d x %d on a ROI of %d x %d leaves cells of %d x %d: both sides must be >= 3", g.grid_rows,
+                   g.grid_cols, fp->w, fp->h, o[2], o[3]);
+  fp->rows = g.grid_rows; fp->cols = g.grid_cols;
+  fp->col_size = o[2]; fp->row_size = o[3]; fp->quota = o[4]; fp->rows_cap = o[5];
+  return SF_OK;
+}
+
+// The detection stage under a grid, for n images (the single calls: n = 1): the batch launchers with the cells as their
+// images, then k_grid_gather -- d_kpts [n][rows_cap] in full-image coordinates, d_n [n], nothing waited for
+static int grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_params& dp, const uint8_t* d_left, size_t image_stride,
+                       int n, int pitch, sf_keypoint* d_kpts, int32_t* d_n) {
+  const int cells = fp.rows * fp.cols;
+  const size_t count_bytes = ((size_t)n * cells * 4 + 255) & ~(size_t)255;
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->ft_cells, count_bytes + (size_t)n * fp.rows_cap * sizeof(sf_keypoint))) != SF_OK) return rc;
+  int32_t* d_cell_n = (int32_t*)c->ft_cells.p;
+  sf_keypoint* d_cell_kpts = (sf_keypoint*)((char*)c->ft_cells.p + count_bytes);
+  SfCells g;
+  g.per_image = cells; g.cols = fp.cols;
+  g.row_step = (size_t)fp.row_size * pitch; g.col_step = (size_t)fp.col_size;
+  const uint8_t* d_roi = d_left + (size_t)fp.y * pitch + fp.x;
+  if (c->feature_type == 4)
+    rc = sf_launch_detect_fast_batch(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota, &c->fast,
+                                     d_cell_kpts, fp.quota, d_cell_n, g);
+  else
+    rc = sf_launch_detect_corners_batch(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota,
+                                        dp.quality_level, dp.min_distance, d_cell_kpts, fp.quota, d_cell_n, g);
+  if (rc != SF_OK) return rc;
+  return sf_launch_grid_gather(c, d_cell_kpts, d_cell_n, n, fp.rows, fp.cols, fp.quota, fp.x, fp.y, fp.col_size, fp.row_size, d_kpts,
+                               fp.rows_cap, d_n);
 }
 
 extern "C" void sf_stereo_flow_defaults(sf_stereo_flow_params* p) {
@@ -581,11 +681,12 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
   const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
   if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
     return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
+  if ((rc = grid_plan(c, width, height, dp.max_features, &fp)) != SF_OK) return rc;
   SF_HIP(c, hipSetDevice(c->device));
   ExtractKind kind;
   if ((rc = extract_kind(c, &kind)) != SF_OK) return rc;
   const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
-  const int maxf = dp.max_features;
+  const int maxf = fp.rows_cap;                            // the rows of the call's buffers: max_features, or the grid's R C quota
   if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_flow, (size_t)maxf * 16)) != SF_OK) return rc;
@@ -613,7 +714,12 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
   // (the GFTT parameters are checked under every feature type, FAST and ORB included, which do not use them)
   if ((rc = check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
   const uint8_t* d_roi = d_left + (size_t)fp.y * width + fp.x;   // the detector's image: the ROI, at the parent's pitch
-  switch (c->feature_type) {
+  if (fp.grid()) {                                       // every cell in one launch sequence, one wait for the keyframe's count
+    if ((rc = check_pixels(c, fp.col_size, fp.row_size)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->ft_counts, 4)) != SF_OK) return rc;
+    if ((rc = grid_detect(c, fp, dp, d_left, 0, 1, width, d_kpts, (int32_t*)c->ft_counts.p)) != SF_OK) return rc;
+    rc = sf_word_to_host(c, c->ft_counts.p, &n);
+  } else switch (c->feature_type) {
     case 4: rc = sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
     case 2: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
     default:
@@ -622,7 +728,7 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
   if (rc != SF_OK) return rc;
   n = std::min(n, maxf);
   if (fp.launch() &&
-      (rc = sf_launch_corner_subpix(c, d_left, 0, 1, width, height, width, d_kpts, n, nullptr, maxf, fp.x, fp.y,
+      (rc = sf_launch_corner_subpix(c, d_left, 0, 1, width, height, width, d_kpts, n, nullptr, maxf, fp.off_x(), fp.off_y(),
                                     fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
     return rc;
   float* d_xy = (float*)c->ft_flow.p;                    // [n][2], then x [n], then status [n]
@@ -703,6 +809,9 @@ static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframe
   if (plan->dp.max_features <= 0 || plan->dp.max_features > SF_MAX_FEATURES)
     return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", plan->dp.max_features, SF_MAX_FEATURES);
   if ((rc = check_gftt(c, plan->dp.quality_level, plan->dp.min_distance)) != SF_OK) return rc;
+  if ((rc = grid_plan(c, width, height, plan->dp.max_features, &plan->front)) != SF_OK) return rc;
+  if (plan->front.grid() && (long long)n_keyframes * plan->front.rows * plan->front.cols > 65535)
+    return sf_fail(c, SF_ERANGE, "%d keyframes of %d x %d cells: at most 65535 cells per call", n_keyframes, plan->front.rows, plan->front.cols);
   plan->prm = arg_or_defaults(flow, sf_stereo_flow_defaults);
   const sf_stereo_flow_params& prm = plan->prm;
   if (!c->stereo.optical_flow) {
@@ -727,7 +836,7 @@ static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan*
   int rc;
   SF_HIP(c, hipSetDevice(c->device));
   if ((rc = extract_kind(c, &plan->kind)) != SF_OK) return rc;
-  const int maxf = plan->dp.max_features;
+  const int maxf = plan->front.rows_cap;                   // rows per keyframe: max_features, or the grid's R C quota
   const size_t rows_all = (size_t)maxf * n;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_flow, rows_all * 16)) != SF_OK) return rc;
@@ -741,7 +850,7 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
                         int height, int pitch, size_t image_stride, const sf_stereo_camera* cam, int32_t* first_slot_out,
                         int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
   const sf_detector_params& dp = plan.dp;
-  const int maxf = dp.max_features;
+  const int maxf = plan.front.rows_cap;                    // rows per keyframe, everywhere below: max_features, or R C quota
   const size_t rows_all = (size_t)maxf * n;
   int rc;
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
@@ -752,6 +861,8 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   if (c->feature_type == 2) {                            // (keypoints in level-0 coordinates; the pyramids stay for the extraction;
     rc = sf_launch_detect_orb_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
     kind.pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;   // no ROI: front_plan)
+  } else if (fp.grid()) {                                // the cells as the detector's images, joined by k_grid_gather
+    rc = grid_detect(c, fp, dp, d_left, image_stride, n, pitch, d_kpts, d_n);
   } else if (c->feature_type == 4) {
     rc = sf_launch_detect_fast_batch(c, d_roi, image_stride, n, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
   } else {
@@ -760,7 +871,7 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   }
   if (rc != SF_OK) return rc;
   if (fp.launch() &&
-      (rc = sf_launch_corner_subpix(c, d_left, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, maxf, fp.x, fp.y,
+      (rc = sf_launch_corner_subpix(c, d_left, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, maxf, fp.off_x(), fp.off_y(),
                                     fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
     return rc;
   float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]

@@ -13,6 +13,15 @@ __device__ __forceinline__ int reflect101(int p, int len) {
   return p;
 }
 
+// Byte offset of image z of a detector launch (SfCells: sf_internal.hpp): z * img_stride, or with cells the cell's first
+// pixel inside its image.  Uniform per workgroup: scalar arithmetic.
+__device__ __forceinline__ size_t sf_cell_base(unsigned z, size_t img_stride, const SfCells& g) {
+  if (g.per_image == 1) return z * img_stride;
+  const unsigned image = z / (unsigned)g.per_image, cell = z - image * (unsigned)g.per_image;
+  const unsigned i = cell / (unsigned)g.cols, j = cell - i * (unsigned)g.cols;
+  return image * img_stride + i * g.row_step + j * g.col_step;
+}
+
 __device__ __forceinline__ sf_keypoint sf_make_keypoint(float x, float y, float size, float response, int octave) {
   sf_keypoint k;
   k.x = x; k.y = y; k.size = size; k.angle = -1.0f; k.response = response; k.octave = octave; k.class_id = -1;

@@ -256,6 +256,10 @@ struct sf_context {
   // which stereo correspondence the extraction calls run (sf_stereo_set_params): pyramidal LK (k_lk.hip) or block
   // matching (k_stereo_bm.hip) with SSD or SAD scores
   sf_stereo_params stereo = {1, 1};
+  // Vis/GridRows x Vis/GridCols (sf_grid_set_params; k_grid.hip): the detector of types 4, 6 and 8 runs per cell of the
+  // ROI; 1 x 1 = no cells.  ft_cells: every cell's count, then every cell's keypoints, before k_grid_gather joins them
+  sf_grid_params grid = {1, 1};
+  Buf ft_cells;
   Buf orb_pyr, orb_work;
   Buf trace;                    // SF_CHAIN_TRACE builds: uint64[n][32] phase timestamps of the fused kernel
 
@@ -539,6 +543,14 @@ inline int sf_word_to_host(sf_context* c, const void* d_word, void* h_word) {
   return SF_OK;
 }
 
+// ---- the cells of Vis/GridRows x Vis/GridCols as the images of a detector launch (k_fast.hip, k_gftt.hip, k_grid.hip) ----
+// Image z of the launch is cell z % per_image (row-major, `cols` per row) of caller's image z / per_image: its first pixel
+// lies at (z / per_image) * img_stride + i * row_step + j * col_step.  per_image 1 (the default): no cells, z * img_stride.
+struct SfCells {
+  int per_image = 1, cols = 1;
+  size_t row_step = 0, col_step = 0;           // bytes: row_size * pitch, col_size
+};
+
 // ---- workspace of the corner detectors (k_gftt.hip, k_fast.hip), one image and a batch alike --------------------------
 // c->gf_planes: plane_bytes per image for the detector's own planes.  c->gf_keys: the candidate keys of image i at keys +
 // i * key_cap, and as much again for their sorted copy.  c->gf_scalar: the single call's corner count at byte 0, from byte
@@ -610,7 +622,7 @@ int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, uns
                                 unsigned bit1);
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
-                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out);
+                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells = SfCells());
 // the pyramid of the two stereo paths (k_lk.hip builds it, k_lk_track and k_stereo_bm read it)
 constexpr int LK_MAX_LEVELS = 16;
 struct LkLevel {
@@ -660,13 +672,13 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
                           const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out);
+                                int32_t* d_n_out, const SfCells& cells = SfCells());
 // one level of FAST on n_img images img_stride bytes apart: k_fast_score + k_fast_candidates (image i: score plane at
 // + i * plane_stride, keys at + i * key_cap, keys = score << 32 | pixel index in arrival order, count[i] the corners found;
 // zeroed by the caller)
 void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
                           int threshold, int nonmax, uint8_t* score, size_t plane_stride, unsigned long long* keys, unsigned* count,
-                          unsigned key_cap);
+                          unsigned key_cap, const SfCells& cells = SfCells());
 // ORB detector (k_orb_detect.hip); det / orb validated by the caller
 SfOrbPyr sf_orb_pyr_layout(int width, int height, float scale_factor, int n_levels);
 void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota);
@@ -690,6 +702,11 @@ int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_images, size_t im
 int sf_launch_corner_subpix(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
                             sf_keypoint* d_kpts, int n, const int32_t* d_n, int kp_stride, int off_x, int off_y, int win,
                             int iterations, float eps);
+// Vis/GridRows x Vis/GridCols (k_grid.hip): the keypoints a detector left per cell -- cell q of keyframe f: d_cell_n[f * cells
+// + q] of them at d_cell_kpts + (f * cells + q) * quota -- into the keyframe's list d_kpts + f * rows_cap in cell order, the
+// cell's origin (x0 + j * col_size, y0 + i * row_size) added; d_n[f] = the keyframe's count
+int sf_launch_grid_gather(sf_context* c, const sf_keypoint* d_cell_kpts, const int32_t* d_cell_n, int n_img, int rows, int cols,
+                          int quota, int x0, int y0, int col_size, int row_size, sf_keypoint* d_kpts, int rows_cap, int32_t* d_n);
 int sf_launch_stereo_flow(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, int width, int height, int pitch,
                           const sf_keypoint* d_kpts, int n, const sf_stereo_flow_params* prm, float* d_right_xy,
                           uint8_t* d_status, float* d_right_x, float* d_err);

@@ -109,6 +109,10 @@ def load():
                                                      P(_abi.StereoFlowParams), vp, vp, vp, i32, P(i32), P(i32)]),
         "sf_stereo_correspondences_device": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, i32, P(_abi.StereoFlowParams),
                                                        vp, vp, vp, vp]),
+        "sf_grid_defaults": (None, [P(_abi.GridParams)]),
+        "sf_grid_set_params": (C.c_int, [vp, P(_abi.GridParams)]),
+        "sf_grid_get_params": (C.c_int, [vp, P(_abi.GridParams)]),
+        "sf_compute_grid": (C.c_int, [i32, i32, P(C.c_float), P(_abi.GridParams), i32, P(i32)]),
         "sf_stereo_defaults": (None, [P(_abi.StereoParams)]),
         "sf_stereo_set_params": (C.c_int, [vp, P(_abi.StereoParams)]),
         "sf_stereo_get_params": (C.c_int, [vp, P(_abi.StereoParams)]),
@@ -212,6 +216,7 @@ EXPORTED = [
     "sf_get_features_and_descriptor_orb_batch_device", "sf_add_keyframes_orb_u8_batch_device",
     "sf_front_defaults", "sf_front_set_params", "sf_front_get_params", "sf_compute_roi", "sf_corner_subpix_device",
     "sf_stereo_defaults", "sf_stereo_set_params", "sf_stereo_get_params", "sf_stereo_block_match_device",
+    "sf_grid_defaults", "sf_grid_set_params", "sf_grid_get_params", "sf_compute_grid",
 ]
 
 
@@ -519,7 +524,7 @@ class SeparatorFinder:
         if pitch != pitch2:
             left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
             pitch = left.strides[0]
-        cap = (det.max_features if det is not None else 1000)
+        cap = self._rows_cap(w, h, det.max_features if det is not None else 1000)
         nbytes = self.descriptor_bytes()
         desc = np.zeros((cap, nbytes), np.uint8)
         xyz = np.zeros((cap, 3), np.float32)
@@ -609,6 +614,28 @@ class SeparatorFinder:
             raise SepfinderError(rc, "Vis/RoiRatios %s on a %d x %d image" % (list(ratios), width, height))
         return tuple(out)
 
+    def grid_set_params(self, params):
+        """The handle's _abi.GridParams: Vis/GridRows x Vis/GridCols, the detector per cell of the ROI in the keyframe
+        extraction calls (feature types 4, 6, 8); 1 x 1 on a fresh handle.  Under a grid the batch calls' per-keyframe
+        outputs and the store's rows are rows_cap of compute_grid apart, not max_features."""
+        self._check(self._L.sf_grid_set_params(self._h, C.byref(params)))
+
+    def grid_get_params(self):
+        p = _abi.GridParams()
+        self._check(self._L.sf_grid_get_params(self._h, C.byref(p)))
+        return p
+
+    def compute_grid(self, width, height, roi_ratios, grid_rows, grid_cols, max_features):
+        """sf_compute_grid (pure host code): (x, y, col_size, row_size, quota, rows_cap); what _abi.compute_grid restates."""
+        r = (C.c_float * 4)(*roi_ratios)
+        g = _abi.grid_params(grid_rows, grid_cols)
+        out = (C.c_int32 * 6)()
+        rc = self._L.sf_compute_grid(width, height, r, C.byref(g), max_features, out)
+        if rc != _abi.SF_OK:
+            raise SepfinderError(rc, "a grid of %d x %d with %d features, Vis/RoiRatios %s, on a %d x %d image"
+                                 % (grid_rows, grid_cols, max_features, list(roi_ratios), width, height))
+        return tuple(out)
+
     def corner_subpix_device(self, d_image, width, height, pitch, d_kpts, n, win, iterations, eps):
         """cv::cornerSubPix on n 28-byte keypoint records of a device image, in place (x and y only), asynchronous on the
         handle's stream; device pointers (ints)."""
@@ -651,6 +678,18 @@ class SeparatorFinder:
             C.byref(params) if params is not None else None, ssd, C.c_void_p(d_right_xy), C.c_void_p(d_status),
             C.c_void_p(d_right_x), C.c_void_p(d_score)))
 
+    def _rows_cap(self, width, height, max_features):
+        """The rows a keyframe of the single extraction calls can hold: max_features, or under a grid its R C quota
+        (compute_grid), which can be more.  What the call itself refuses is left to the call."""
+        g = self.grid_get_params()
+        if (g.grid_rows, g.grid_cols) == (1, 1):
+            return max_features
+        try:
+            return max(max_features, _abi.compute_grid(width, height, list(self.front_get_params().roi_ratios), g.grid_rows,
+                                                       g.grid_cols, max_features)[5])
+        except (ValueError, OverflowError):
+            return max_features
+
     def get_features_and_descriptor(self, left, right, cam, det=None, flow=None):
         """GetFeatsAndDesc on host images (uint8 [h, w], same row stride): returns (descriptors [rows, bytes] uint8,
         kpts3D [rows, 3] float32, kpts [rows] KEYPOINT_DTYPE, slot of the keyframe in the device-resident store)."""
@@ -658,7 +697,7 @@ class SeparatorFinder:
         if left.ndim != 2 or left.shape != right.shape or left.strides != right.strides or left.strides[1] != 1:
             raise ValueError("left / right must be 2-D uint8 images of one shape and row stride")
         h, w = left.shape
-        cap = (det.max_features if det is not None else 1000)
+        cap = self._rows_cap(w, h, det.max_features if det is not None else 1000)
         nbytes = self.descriptor_bytes()
         desc = np.zeros((cap, nbytes), np.uint8)
         xyz = np.zeros((cap, 3), np.float32)
@@ -677,7 +716,8 @@ class SeparatorFinder:
                                                  d_xyz_out=None, d_kpts_out=None,
                                                  _call="sf_get_features_and_descriptor_batch_device"):
         """n keyframes from device images (raw pointers) to n store slots in one launch sequence, no host wait; optional
-        device outputs sized for n_keyframes x max_features rows.  Returns the first slot."""
+        device outputs sized for n_keyframes x max_features rows -- under a grid (grid_set_params) n_keyframes x rows_cap of
+        compute_grid, the stride of the keyframes' blocks.  Returns the first slot."""
         first = C.c_int32()
         self._check(getattr(self._L, _call)(
             self._h, C.c_void_p(d_left), C.c_void_p(d_right), n_keyframes, width, height, pitch, int(image_stride),

@@ -142,6 +142,14 @@ class SepfinderGeometricTools {
     front.subpix_eps = (float)subpix_eps;
     if (sf_front_set_params(sf_, &front) != SF_OK)
       ROS_ERROR("roi_ratios / subpix_*: %s", sf_last_error(sf_));
+    // Vis/GridRows x Vis/GridCols: the detector per cell of the ROI, ceil(max_features / cells) keypoints apiece (feature
+    // types 4, 6, 8); 1 x 1 by default, like the reference
+    sf_grid_params grid;
+    sf_grid_defaults(&grid);
+    n.param("grid_rows", grid.grid_rows, grid.grid_rows);
+    n.param("grid_cols", grid.grid_cols, grid.grid_cols);
+    if (sf_grid_set_params(sf_, &grid) != SF_OK)
+      ROS_ERROR("grid_rows / grid_cols: %s", sf_last_error(sf_));
     // Stereo/OpticalFlow (true = pyramidal LK, the default; false = block matching) and Stereo/SSD (block matching: squared
     // or absolute differences): which stereo correspondence the extraction calls run
     sf_stereo_params stereo;
