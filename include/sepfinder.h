@@ -972,6 +972,12 @@ enum {
                              filter candidate straight behind the filter and runs the exact re-evaluation, the row
                              minima and the walk on a second stream beside it; 0: always NN -> walk -> verification of
                              the walk's matches on one stream.  Results unchanged.  Not while a step is in flight.   */
+  SF_OPT_CHAIN_NARROW_EST = 12, /* 1 (default): where the 3D-3D verification takes the split form without the bundle
+                             adjustment and with ransac_adaptive_stop on, a survivor's two motion estimates run one wavefront wide in a 16 KB LDS slot of their own
+                             (lists of up to 256 correspondences; longer ones stay in the wide kernel), as launches before
+                             and behind the guided matching: three chain launches instead of one.  0: one launch, four
+                             wavefronts per survivor.  Results unchanged.  Environment twin: SF_CHAIN_NARROW_EST.
+                             Measured faster on the bench step (docs/chain_narrow_estimates.md).                     */
   SF_OPT_DEBUG_CORR = 4   /* 1: the fused kernel also copies every pair's correspondence lists, headers and pass states
                              to the global workspace, which sf_debug_correspondences reads (default 0: they never
                              leave the workgroup's LDS; the stage kernels always keep them in the workspace)       */

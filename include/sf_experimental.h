@@ -84,7 +84,8 @@ int  sf_debug_guided_points(sf_handle h, int32_t pair, unsigned long long* plane
    writes correspondence lists on a workspace reserved without them).  out (>= 22 values): [0] form (0 stages, 1 fused,
    2 split, 3 split PnP, 4 two-stream halves), [1] lists in HBM, [2] one chunk, [3] pairs of the largest launch
    sequence, [4..12] bytes reserved for corr1, corr2, hdr1, hdr2, pass1, pass2, list1, list3, flags, [13..21] bytes the
-   form's launches write to them.                                                                                 */
+   form's launches write to them; with n_out >= 23 also [22] = 1 where the split form runs its estimates as the
+   one-wavefront launches of SF_OPT_CHAIN_NARROW_EST.                                                             */
 int  sf_debug_plan_workspace(const sf_params* p, int32_t kcap, int32_t desc_words, int32_t n_pairs,
                              int32_t in_overlapped_step, int32_t debug_corr, int64_t* out, int32_t n_out);
 

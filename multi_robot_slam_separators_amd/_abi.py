@@ -17,7 +17,7 @@ SF_MAX_DESC_BYTES_F32 = 512
  SF_K_NN_REFINE, SF_K_FUSED, SF_K_NN_WALK, SF_K_BA, SF_K_GUIDED_TP, SF_K_COUNT) = range(13)
 (SF_OPT_MATCH_MFMA, SF_OPT_FUSED, SF_OPT_OVERLAP, SF_OPT_CHAIN_WAVES, SF_OPT_DEBUG_CORR, SF_OPT_NN_FULL_FILTER,
  SF_OPT_STEP_OVERLAP, SF_OPT_STEP_SPLIT, SF_OPT_STEP_DEPTH, SF_OPT_STEP_LANES, SF_OPT_STEP_DEVICE_WALK,
- SF_OPT_STEP_SPECULATE) = range(12)      # sf_set_option
+ SF_OPT_STEP_SPECULATE, SF_OPT_CHAIN_NARROW_EST) = range(13)      # sf_set_option
 
 STATUS_NAMES = {0: "SF_OK", 1: "SF_EINVAL", 2: "SF_EHIP", 3: "SF_ENOMEM", 4: "SF_ERANGE", 5: "SF_ENODEV", 6: "SF_ERCCL"}
 

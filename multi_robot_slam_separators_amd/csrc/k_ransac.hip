@@ -48,16 +48,17 @@ struct RansacLds {
   uint32_t* cidx;   // [kcap] packed (from | to << 16) feature indices of the gathered correspondences (bundle adjustment)
 };
 
-__device__ __forceinline__ RansacLds ransac_carve(unsigned char* p, int kcap) {
+// mcap: the capacity of the per-correspondence arrays marked [kcap] above (sf_ransac_lds_bytes_dev of the same number)
+__device__ __forceinline__ RansacLds ransac_carve(unsigned char* p, int mcap) {
   RansacLds L;
-  L.src = (float4*)p; p += (size_t)kcap * 16;
-  L.dst = (float4*)p; p += (size_t)kcap * 16;
+  L.src = (float4*)p; p += (size_t)mcap * 16;
+  L.dst = (float4*)p; p += (size_t)mcap * 16;
   L.red = (double*)p; p += 64 * 8;
   L.sums = (unsigned long long*)p; p += 4 * 8;
-  L.d2 = (float*)p; p += (size_t)kcap * 4;
+  L.d2 = (float*)p; p += (size_t)mcap * 4;
   L.misc = (int*)p; p += 16 * 4;
-  L.mask_a = p; p += kcap;
-  L.mask_b = p; p += kcap;
+  L.mask_a = p; p += mcap;
+  L.mask_b = p; p += mcap;
   L.hyp = (float*)p; p += 12 * 64 * 4;
   L.hyp_cnt = (int*)p; p += 5 * 64 * 4;
   L.best = (float*)p; p += 16 * 4;
@@ -404,19 +405,20 @@ __device__ __forceinline__ void write_null_pass(PassState& out, int matches) {
 
 // Body of one RANSAC pass for ONE pair (the calling 256-thread workgroup).  `cl` = the pair's n_corr
 // correspondences (from | to << 16, ascending "from"; LDS in the fused kernel, global in the stage kernel);
-// `lds` = this stage's region of the workgroup's dynamic LDS (sf_ransac_lds_bytes).  The result is written to
-// `out` by thread 0.
+// `lds` = this stage's region of the workgroup's dynamic LDS, sf_ransac_lds_bytes_dev(mcap): `mcap` >= n_corr is the
+// capacity of its per-correspondence arrays (kcap in the wide kernels, SF_EST_CAP in k_chain_est), while the rows of the
+// store and of `mask_out` keep the stride kcap.  The result is written to `out` by thread 0.
 // DIR = 1: the backward estimate of Vis/ForwardEstOnly = false (myRegistrationVis.cpp:936-978: A = "to", B = "from");
 // `mask_out` (stage kernel, DIR form only): one byte per "from" feature of the pair, set for this estimate's inliers.
 template <int DIR = 0, int NW = 4>
 __device__ __forceinline__ void ransac_body(const StoreView& st, int pair, int sF, int sT, const uint32_t* cl, int n_corr,
-                                            PassState& out, const DeviceParams& P, unsigned char* lds,
+                                            PassState& out, const DeviceParams& P, unsigned char* lds, int mcap,
                                             int trace_base = 2, uint8_t* mask_out = nullptr) {
   constexpr int NT = 64 * NW;      // NW = 4: the 256-thread workgroup of the fused / stage kernels; 1, 2: the low-occupancy chains
   const int tid = (int)threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int kcap = st.kcap;
-  const RansacLds L = ransac_carve(lds, kcap);
+  const RansacLds L = ransac_carve(lds, mcap);
 
   // ---- util3d::findCorrespondences: finite, non-zero, id-ordered ---------------------------------
   const float* xF = st.xyz + (size_t)sF * kcap * 3;
@@ -787,7 +789,7 @@ k_ransac(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __r
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int pair = list[blockIdx.x];
   ransac_body<DIR>(st, pair, pair_from[pair], pair_to[pair], corr + (size_t)pair * st.kcap, hdr[pair].n_corr,
-                       pass[pair], P, smem_raw, 2, mask ? mask + (size_t)pair * st.kcap : nullptr);
+                       pass[pair], P, smem_raw, st.kcap, 2, mask ? mask + (size_t)pair * st.kcap : nullptr);
   if (extra_3dof && threadIdx.x == 0) pass_to3dof(pass[pair], extra_3dof);
 }
 

@@ -56,8 +56,15 @@ struct FusedTail {
 struct BaHandover {
   uint8_t* mask1;     // [pairs][kcap] inlier bytes of the first estimate, per "from" feature (zeroed before the launch)
   uint8_t* mask2;     // ... of the second
-  uint8_t* est2;      // [pairs] 1 = the pair's second estimate ran (its state is to be adjusted)
-};
+  uint8_t* est2;      // [pairs] 1 = the pair's second estimate ran (its state is to be adjusted); PART 3: 0 / 1 = handed
+};                    // to k_chain_est<2> without / with a second estimate to run, 2 = finished by the wide kernel
+
+// The narrow estimates (k_chain_est): correspondences a RANSAC pass on ONE wavefront takes.  Its LDS slot is
+// sf_ransac_lds_bytes_dev(SF_EST_CAP) = 15 840 B -- ten to a CU, where the wide chain's 30-32 KB (sized by kcap and by
+// the guided pass) allow five; a longer list keeps the wide kernel.
+#ifndef SF_EST_CAP
+#define SF_EST_CAP 256
+#endif
 
 // the accepted result of a finished pair leaves for the host NOW (posted PCIe writes beside the other pairs' work)
 // instead of through a compaction kernel behind the launch: thread 0 takes the slot, 23 lanes move the 368 bytes
@@ -89,6 +96,10 @@ __device__ __forceinline__ void stream_accepted(int pair, const sf_result* __res
 // PART 1 = the first estimate (its state and inlier bytes go to HBM), PART 2 = guided matching + the second estimate
 // from the ADJUSTED first state (list, header, flag, state, inlier bytes to HBM; the result is assembled by the second
 // adjustment's launch).
+// PART 3: the middle launch of the three-launch form [k_chain_est<1>] -> k_chain<.., 3> -> [k_chain_est<2>] -- guided
+// matching, with the estimates of the lists beyond SF_EST_CAP around it.  `est1`: the pair's first list is such a list (else
+// T.pass1 is k_chain_est<1>'s result).  A pair whose second list is one too is finished here as PART 0 does; every other
+// pair leaves list, header, flag and states in HBM for k_chain_est<2>.
 template <int W, int NW = 4, int PART = 0>
 __device__ __forceinline__ void chain_after_match(const StoreView& st, int pair, int sF, int sT, bool est1, FusedTail& T,
                                                   uint32_t* cl, unsigned char* chain_lds, uint32_t* __restrict__ corr2,
@@ -105,9 +116,9 @@ __device__ __forceinline__ void chain_after_match(const StoreView& st, int pair,
   __builtin_amdgcn_s_setprio(3);
   if constexpr (PART != 2) {
     if (est1) {
-      ransac_body<0, NW>(st, pair, sF, sT, cl, T.hdr1.n_corr, T.pass1, P, chain_lds, 2,
+      ransac_body<0, NW>(st, pair, sF, sT, cl, T.hdr1.n_corr, T.pass1, P, chain_lds, kcap, 2,
                          PART == 1 ? H.mask1 + (size_t)pair * kcap : nullptr);
-      if constexpr (PART == 0) {
+      if constexpr (PART == 0 || PART == 3) {
         if (P.force_3dof && tid == 0) pass_to3dof(T.pass1, 2);    // myRegistration.cpp:269-276, then :245-248 as pass 2's guess
       }
       __syncthreads();
@@ -121,15 +132,24 @@ __device__ __forceinline__ void chain_after_match(const StoreView& st, int pair,
   const bool est2 = guided_body<W, false, NW>(st, pair, sF, sT, T.pass1, T.pass2, T.guided_flag, cl, T.hdr2, nullptr, nullptr,
                                               P, reinterpret_cast<int*>(chain_lds));
   __syncthreads();
-  if (P.dbg_corr || PART == 2) {
+  const bool hand_over = PART == 3 && !(est2 && T.hdr2.n_corr > SF_EST_CAP);     // (block-uniform)
+  if (P.dbg_corr || PART == 2 || hand_over) {
     const int n = T.hdr2.n_corr;
     for (int i = tid; i < n; i += NT) corr2[(size_t)pair * kcap + i] = cl[i];
     if (tid == 0) hdr2[pair] = T.hdr2;
   }
+  if constexpr (PART == 3) {
+    if (tid == 0) {
+      if (est1) pass1[pair] = T.pass1;           // (the other pairs' is k_chain_est<1>'s, in place)
+      H.est2[pair] = hand_over ? (est2 ? 1 : 0) : 2;
+      if (hand_over) { pass2[pair] = T.pass2; guided_flag[pair] = T.guided_flag; }
+    }
+    if (hand_over) return;
+  }
   if (est2) {
-    ransac_body<0, NW>(st, pair, sF, sT, cl, T.hdr2.n_corr, T.pass2, P, chain_lds, 11,
+    ransac_body<0, NW>(st, pair, sF, sT, cl, T.hdr2.n_corr, T.pass2, P, chain_lds, kcap, 11,
                        PART == 2 ? H.mask2 + (size_t)pair * kcap : nullptr);
-    if constexpr (PART == 0) {
+    if constexpr (PART == 0 || PART == 3) {
       if (P.force_3dof && tid == 0) pass_to3dof(T.pass2, 1);
     }
     __syncthreads();
@@ -259,16 +279,62 @@ k_chain(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __re
   FusedTail& T = *reinterpret_cast<FusedTail*>(smem_raw + tail_off);
   uint32_t* cl = reinterpret_cast<uint32_t*>(smem_raw);
   unsigned char* chain_lds = smem_raw + (size_t)kcap * 4;
+  bool est1 = true;
   if constexpr (PART != 2) {
     const CorrHeader h1 = hdr1[pair];
+    if constexpr (PART == 3) est1 = h1.n_corr > SF_EST_CAP;      // (else k_chain_est<1> has made the first estimate)
     if (tid == 0) { T.hdr1 = h1; T.pass1 = pass1[pair]; }
-    for (int i = tid; i < h1.n_corr; i += 64 * NW) cl[i] = corr1[(size_t)pair * kcap + i];
+    if (est1)
+      for (int i = tid; i < h1.n_corr; i += 64 * NW) cl[i] = corr1[(size_t)pair * kcap + i];
   } else {
     if (tid == 0) T.pass1 = pass1[pair];              // (the adjusted first estimate)
   }
   __syncthreads();
-  SF_TRACE_MARK(P, pair, 1);
-  chain_after_match<W, NW, PART>(st, pair, sF, sT, true, T, cl, chain_lds, corr2, hdr2, pass1, pass2, guided_flag, out, P, H);
+  if (PART != 3 || est1) SF_TRACE_MARK(P, pair, 1);
+  chain_after_match<W, NW, PART>(st, pair, sF, sT, est1, T, cl, chain_lds, corr2, hdr2, pass1, pass2, guided_flag, out, P, H);
+}
+
+// The estimates of the three-launch form on ONE wavefront in a 16 KB slot (SF_EST_CAP): 2.2 x the work per wavefront
+// cycle of the four-wavefront chain (no wavefront waits at a barrier while another one samples, fits or solves), ten to a
+// CU.  PASS 1: the first estimate of every survivor whose list fits, from the list k_match_split left in HBM, into
+// pass1[pair] (Reg/Force3DoF's applications as PART 0 makes them).  PASS 2: for the pairs k_chain<.., 3> handed over, the
+// second estimate where guided matching asked for one, then the result and its way to the host -- the tail of PART 0.
+template <int PASS>
+__global__ void __launch_bounds__(64, 4)
+k_chain_est(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+            const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr, PassState* __restrict__ pass1,
+            PassState* __restrict__ pass2, const uint8_t* __restrict__ guided_flag, const uint8_t* __restrict__ est2,
+            const int32_t* __restrict__ list, const int32_t* __restrict__ counter, sf_result* __restrict__ out,
+            DeviceParams P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  if ((int)blockIdx.x >= *counter) return;
+  const int pair = list[blockIdx.x];
+  // pass 2: what the wide kernel left for the pair -- 0: no second estimate, 1: one to run, 2: finished there (its
+  // second header is then not written: read nothing of it)
+  const int run = PASS == 1 ? 1 : est2[pair];
+  if (run == 2) return;
+  const int n_corr = hdr[pair].n_corr;
+  if (PASS == 1 && n_corr > SF_EST_CAP) return;              // the wide kernel's own (a list handed over for pass 2 fits:
+                                                             //  chain_after_match hands over only lists up to the cap)
+  __builtin_amdgcn_s_setprio(3);
+  if constexpr (PASS == 1) {
+    SF_TRACE_MARK(P, pair, 1);
+    ransac_body<0, 1>(st, pair, pair_from[pair], pair_to[pair], corr + (size_t)pair * st.kcap, n_corr, pass1[pair], P,
+                      smem_raw, SF_EST_CAP, 2);
+    if (P.force_3dof && threadIdx.x == 0) pass_to3dof(pass1[pair], 2);
+  } else {
+    if (run) {
+      ransac_body<0, 1>(st, pair, pair_from[pair], pair_to[pair], corr + (size_t)pair * st.kcap, n_corr, pass2[pair], P,
+                        smem_raw, SF_EST_CAP, 11);
+      if (P.force_3dof && threadIdx.x == 0) pass_to3dof(pass2[pair], 1);
+    }
+    SF_TRACE_MARK(P, pair, 17);
+    if (threadIdx.x == 0) finalize_one(pass1[pair], pass2[pair], guided_flag[pair], out[pair]);
+    if (P.accept_on) {
+      __syncthreads();            // (the estimate is done with the LDS: its first word carries the slot)
+      stream_accepted(pair, out, P, *reinterpret_cast<int32_t*>(smem_raw));
+    }
+  }
 }
 
 template <int W, int NQ, bool WIDE = false>
@@ -525,6 +591,7 @@ namespace {
 template <int W, int NW, int PART>
 int launch_chain(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, sf_result* d_out,
                  size_t lds, int tail_off, const BaHandover& H) {
+  static_assert(PART >= 0 && PART <= 3, "chain_attr has one row per part");
   bool& attr_set = c->chain_attr[W == 16][PART][NW == 4 ? 2 : NW - 1];
   if (lds > 64 * 1024 && !attr_set) {
     SF_HIP(c, hipFuncSetAttribute((const void*)k_chain<W, NW, PART>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -560,15 +627,18 @@ int launch_chain_pnp(sf_context* c, StoreView st, const int32_t* d_from, const i
 template <int PART>
 int launch_chain_part(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, sf_result* d_out,
                       bool pnp, const BaHandover& H) {
-  int rc;
-  sf_prof_begin(c, SF_K_FUSED);
+  int rc = SF_OK;
+  if (PART == 3 && pnp) return sf_fail(c, SF_EINVAL, "the PnP chain has no three-launch form");
+  if (PART != 3) sf_prof_begin(c, SF_K_FUSED);        // (part 3: its caller books the three launches as one interval)
   if (pnp) {
+   if constexpr (PART != 3) {         // (k_chain_pnp has parts 0 .. 2 only)
 #define SF_CHAIN_PNP_CASE(W_)                                                                            \
     rc = c->chain_pnp_nw == 1   ? launch_chain_pnp<W_, PART, 1>(c, st, d_from, d_to, n, d_out, H)          \
          : c->chain_pnp_nw == 2 ? launch_chain_pnp<W_, PART, 2>(c, st, d_from, d_to, n, d_out, H)          \
                                 : launch_chain_pnp<W_, PART, 4>(c, st, d_from, d_to, n, d_out, H)
     if (st.w == 8) SF_CHAIN_PNP_CASE(8); else SF_CHAIN_PNP_CASE(16);
 #undef SF_CHAIN_PNP_CASE
+   }
   } else {
     const int tail_off = (int)fused_tail_offset(c, st, false);
     const size_t lds_c = (size_t)tail_off + ((sizeof(FusedTail) + 15) & ~(size_t)15);
@@ -579,15 +649,33 @@ int launch_chain_part(sf_context* c, StoreView st, const int32_t* d_from, const 
     if (st.w == 8) SF_CHAIN_CASE(8); else SF_CHAIN_CASE(16);
 #undef SF_CHAIN_CASE
   }
-  sf_prof_end(c, SF_K_FUSED);
+  if (PART != 3) sf_prof_end(c, SF_K_FUSED);
   if (rc != SF_OK) return rc;
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }
 }  // namespace
 
+namespace {
+// k_chain_est<PASS> over the survivor list: pass 1 reads the first lists, pass 2 the second and finishes the pairs
+template <int PASS>
+int launch_chain_est(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, sf_result* d_out,
+                     const BaHandover& H) {
+  int32_t* counters = (int32_t*)c->w->counters.p;
+  hipLaunchKernelGGL((k_chain_est<PASS>), dim3(n), dim3(64), sf_ransac_lds_bytes_dev(SF_EST_CAP), c->stream, st, d_from, d_to,
+                     (const uint32_t*)(PASS == 1 ? c->w->corr1.p : c->w->corr2.p),
+                     (const CorrHeader*)(PASS == 1 ? c->w->hdr1.p : c->w->hdr2.p), (PassState*)c->w->pass1.p,
+                     (PassState*)c->w->pass2.p, (const uint8_t*)c->w->flags.p, (const uint8_t*)H.est2,
+                     (const int32_t*)c->w->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+}  // namespace
+
+// narrow_est (VerifyPlan, sf_verify_host.hip): the 3D-3D survivors' chains as three launches -- both estimates on one
+// wavefront each (k_chain_est) around the wide kernel's guided matching
 int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n,
-                           sf_result* d_out) {
+                           sf_result* d_out, bool narrow_est) {
   if (n <= 0) return SF_OK;
   const bool pnp = c->dparams.estimation_type == 1;
   if (!(pnp ? sf_split_pnp_applicable(c, st) : sf_split_applicable(c, st)))
@@ -619,10 +707,21 @@ int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, c
 #undef SF_SPLIT_MATCH
   sf_prof_end(c, SF_K_MATCH);
   SF_HIP(c, hipGetLastError());
+  int rc;
+  if (narrow_est) {
+    if (pnp || c->dparams.bundle_adjustment) return sf_fail(c, SF_EINVAL, "narrow estimates: 3D-3D without bundle adjustment only");
+    if ((rc = sf_buf_reserve(c, c->w->dir_mask, (size_t)n)) != SF_OK) return rc;      // (every survivor's byte is written by
+    const BaHandover H = {nullptr, nullptr, (uint8_t*)c->w->dir_mask.p};               //  the middle launch: no memset)
+    sf_prof_begin(c, SF_K_FUSED);                // (the three launches are one entry of the chain's profiling slot)
+    if ((rc = launch_chain_est<1>(c, st, d_from, d_to, n, d_out, H)) == SF_OK &&
+        (rc = launch_chain_part<3>(c, st, d_from, d_to, n, d_out, false, H)) == SF_OK)
+      rc = launch_chain_est<2>(c, st, d_from, d_to, n, d_out, H);
+    sf_prof_end(c, SF_K_FUSED);
+    return rc;
+  }
   if (!c->dparams.bundle_adjustment)
     return launch_chain_part<0>(c, st, d_from, d_to, n, d_out, pnp, BaHandover{nullptr, nullptr, nullptr});
   // bundle adjustment on: [estimate 1] -> adjustment -> [guided matching + estimate 2] -> adjustment + result
-  int rc;
   const size_t mb = (size_t)n * st.kcap;
   if ((rc = sf_buf_reserve(c, c->w->dir_mask, 2 * mb + (size_t)n)) != SF_OK) return rc;
   uint8_t* m1 = (uint8_t*)c->w->dir_mask.p;

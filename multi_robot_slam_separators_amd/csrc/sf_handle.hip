@@ -231,6 +231,7 @@ void sf_env_knobs(sf_context* c) {
   if (const char* v = getenv("SF_BA_NW")) { const int nw = atoi(v); c->ba_nw = (nw == 1 || nw == 2) ? nw : 4; }
   if (const char* v = getenv("SF_CHAIN_PNP_NW")) { const int nw = atoi(v); c->chain_pnp_nw = (nw == 1 || nw == 2) ? nw : 4; }
   if (const char* v = getenv("SF_CHAIN_NW")) { const int nw = atoi(v); c->chain_nw = (nw == 1 || nw == 2) ? nw : 4; }
+  if (const char* v = getenv("SF_CHAIN_NARROW_EST")) c->chain_narrow_est = atoi(v) != 0;   // the three-launch 3D-3D chain
   if (const char* v = getenv("SF_MATCH_MFMA")) c->match_mfma = atoi(v) != 0;   // 0: VALU matcher (A/B reference)
   if (const char* v = getenv("SF_DEBUG_CORR")) c->debug_corr = atoi(v) != 0;   // 1: correspondence lists kept in HBM
   if (const char* v = getenv("SF_OVERLAP")) c->overlap = atoi(v) != 0;         // 1: two-stream halves (sf_verify_device)
@@ -421,6 +422,7 @@ extern "C" int sf_set_option(sf_handle c, int32_t option, int32_t value) {
     case SF_OPT_DEBUG_CORR: c->debug_corr = value != 0; return SF_OK;
     case SF_OPT_NN_FULL_FILTER: c->nn_force_full = value != 0; c->nn_coef_level = -1; return SF_OK;
     case SF_OPT_STEP_SPLIT: c->split_auto = value != 0; return SF_OK;
+    case SF_OPT_CHAIN_NARROW_EST: c->chain_narrow_est = value != 0; return SF_OK;
     case SF_OPT_STEP_OVERLAP:
       if (c->step_inflight) return sf_fail(c, SF_EINVAL, "SF_OPT_STEP_OVERLAP cannot change while steps are in flight");
       c->step_overlap = value != 0;

@@ -30,6 +30,7 @@ struct VerifyPlan {
   enum Form { STAGES = 0, FUSED = 1, SPLIT = 2, SPLIT_PNP = 3, HALVES = 4 } form = STAGES;
   bool lists = true;        // the correspondence lists live in HBM (every form but the plain fused kernel)
   bool single = false;      // one launch sequence on one stream: a pair's index IS its position in the call
+  bool narrow_est = false;  // SPLIT only: the survivors' chains as three launches, the estimates one wavefront wide (k_chain_est)
   bool streams() const { return single && (form == FUSED || form == SPLIT || form == SPLIT_PNP); }   // chain kernels that can
 };                                                                                                // stream accepted results
 VerifyPlan sf_verify_plan(const sf_context* c, const StoreView& v, int n);

@@ -12,6 +12,7 @@
 #define SF_BLOCK 256            // every verification kernel runs 256-thread workgroups (4 waves)
 #define SF_MAX_KCAP 4096        // per-keyframe feature capacity ceiling of the GPU kernels
 #define SF_STEP_MAX_DEPTH 16     // sf_step_issue: steps in flight at most (SF_OPT_STEP_DEPTH)
+#define SF_CHAIN_NARROW_EST_DEFAULT true   // SF_OPT_CHAIN_NARROW_EST as a handle starts (docs/chain_narrow_estimates.md)
 #define SF_STEP_MAX_LANES 4      // ... dealt over at most this many streams (SF_OPT_STEP_LANES)
 
 // ---- device-resident keyframe store (one arena per field, fixed per-slot stride) ---------------
@@ -301,9 +302,11 @@ struct sf_context {
                             // round 5 (its matcher is software-pipelined: 23.0 against 22.7 M pairs/s, profiles/r05u_*)
   int split_auto_min = 2048;   // ... for queries of at least this many candidates (SF_STEP_SPLIT_MIN): below, one launch wins
   bool in_overlapped_step = false;   // set around sf_step_issue's body while the steps alternate between two streams
-  bool chain_attr[2][3][3] = {};   // k_chain [W == 16][part 0 / 1 / 2][wavefronts per chain 1 / 2 / 4]: LDS attribute set
+  bool chain_attr[2][4][3] = {};   // k_chain [W == 16][part 0 .. 3][wavefronts per chain 1 / 2 / 4]: LDS attribute set
   int chain_nw = 4;                // wavefronts per motion-estimation chain of the split forms: 1, 2 (round 5), or 4 = the
                                    // 256-thread workgroup of rounds 2-4 (SF_CHAIN_NW)
+  bool chain_narrow_est = SF_CHAIN_NARROW_EST_DEFAULT;   // SF_OPT_CHAIN_NARROW_EST: the 3D-3D split form's estimates on one wavefront
+                                   // each, around the wide kernel's guided matching (k_chain_est, k_verify.hip)
   bool split_match_attr[2] = {};   // k_match_split [W == 16]
   bool chain_pnp_attr[2][3][3] = {};  // k_chain_pnp [W == 16][part 0 / 1 / 2][wavefronts 1 / 2 / 4]
   int chain_pnp_nw = 2;            // wavefronts per PnP chain (SF_CHAIN_PNP_NW; 2 measured fastest: profiles/r05i_pnp_chain_width.txt)
@@ -600,7 +603,7 @@ size_t sf_fused_lds_bytes(const sf_context* c, const StoreView& st);
 bool sf_split_applicable(const sf_context* c, const StoreView& st);
 bool sf_split_pnp_applicable(const sf_context* c, const StoreView& st);
 int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n,
-                           sf_result* d_out);
+                           sf_result* d_out, bool narrow_est = false);
 int sf_launch_verify_fused(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n,
                            sf_result* d_out);
 size_t sf_ransac_lds_bytes(int kcap, int iterations);

@@ -82,7 +82,13 @@ VerifyPlan sf_verify_plan(const sf_context* c, const StoreView& v, int n) {
   // only the other branch (guided_body) inline
   if (c->dparams.guess_match_to_projection) { p.form = VerifyPlan::STAGES; p.lists = true; return p; }
   if (c->chain_pnp && sf_split_pnp_applicable(c, v)) { p.form = VerifyPlan::SPLIT_PNP; p.lists = true; }
-  else if (sf_use_split(c, v, n)) { p.form = VerifyPlan::SPLIT; p.lists = true; }
+  else if (sf_use_split(c, v, n)) {
+    p.form = VerifyPlan::SPLIT; p.lists = true;
+    // (SPLIT is the 3D-3D estimator's, without Vis/CorGuessMatchToProjection; the bundle adjustment cuts the chain its own
+    //  way.  With PCL's adaptive stop off every pass evaluates all its hypotheses, 64 per wavefront and round: that work is
+    //  data-parallel and keeps the four-wavefront chain: docs/chain_narrow_estimates.md, "What lost".)
+    p.narrow_est = c->chain_narrow_est && !c->dparams.bundle_adjustment && c->dparams.adaptive_stop != 0;
+  }
   else if (sf_fused_lds_bytes(c, v) != 0 && !c->dparams.bundle_adjustment) { p.form = VerifyPlan::FUSED; p.lists = c->debug_corr; }
   else { p.form = VerifyPlan::STAGES; p.lists = true; }
   return p;
@@ -92,7 +98,7 @@ VerifyPlan sf_verify_plan(const sf_context* c, const StoreView& v, int n) {
 // ws_bytes / ws_reserve, from the kernels' own indexing (k_verify.hip, k_match.hip, k_ransac.hip, k_pnp.hip,
 // k_guided.hip): lists are [pair][kcap] words, headers / states / flags one entry per pair, work lists one int per pair.
 // (The `4822be5` fault of round 3 was a form that writes lists on a workspace reserved without them.)
-static WsBytes form_writes(VerifyPlan::Form form, int m, int kcap, bool debug_corr, bool ba) {
+static WsBytes form_writes(VerifyPlan::Form form, int m, int kcap, bool debug_corr, bool ba, bool narrow_est) {
   const size_t np = (size_t)m, list = np * (size_t)kcap * 4;
   WsBytes w = {};
   switch (form) {
@@ -101,7 +107,8 @@ static WsBytes form_writes(VerifyPlan::Form form, int m, int kcap, bool debug_co
       break;
     case VerifyPlan::SPLIT:            // k_match_split: corr1, hdr1, pass1, list1 (+ hdr2 / pass2 / flags of non-survivors with
       w.corr1 = list; w.hdr1 = np * sizeof(CorrHeader); w.pass1 = np * sizeof(PassState); w.list1 = np * 4;   // the debug option)
-      if (debug_corr || ba) { w.corr2 = list; w.hdr2 = np * sizeof(CorrHeader); w.pass2 = np * sizeof(PassState); w.flags = np; }
+      // (narrow_est: k_chain<.., 3> hands the second list, header, state and flag to k_chain_est<2> through the workspace)
+      if (debug_corr || ba || narrow_est) { w.corr2 = list; w.hdr2 = np * sizeof(CorrHeader); w.pass2 = np * sizeof(PassState); w.flags = np; }
       break;
     case VerifyPlan::SPLIT_PNP:        // k_chain_pnp hands everything over through the workspace
     case VerifyPlan::STAGES:
@@ -116,7 +123,7 @@ static WsBytes form_writes(VerifyPlan::Form form, int m, int kcap, bool debug_co
 // include/sf_experimental.h: the plan of a verification call and its workspace, computed WITHOUT a device (no HIP call):
 // out[0] = form, out[1] = lists, out[2] = single, out[3] = pairs of the largest launch sequence, out[4..12] = bytes
 // ws_reserve reserves (corr1, corr2, hdr1, hdr2, pass1, pass2, list1, list3, flags), out[13..21] = bytes the form's
-// launches write for that sequence.
+// launches write for that sequence; with n_out >= 23, out[22] = the split form's estimates run as k_chain_est (three launches).
 extern "C" int sf_debug_plan_workspace(const sf_params* p, int32_t kcap, int32_t desc_words, int32_t n_pairs,
                                        int32_t in_overlapped_step, int32_t debug_corr, int64_t* out, int32_t n_out) {
   if (!p || !out || n_out < 22 || kcap <= 0 || (kcap & 63) || (desc_words != 8 && desc_words != 16 && desc_words != 64 && desc_words != 128) || n_pairs <= 0)
@@ -137,7 +144,8 @@ extern "C" int sf_debug_plan_workspace(const sf_params* p, int32_t kcap, int32_t
     const bool lists = plan.form == VerifyPlan::HALVES ? true : plan.lists;
     const WsBytes r = ws_bytes(seq, kcap, lists);
     const WsBytes w = form_writes(plan.form == VerifyPlan::HALVES ? VerifyPlan::STAGES : plan.form, seq, kcap, c->debug_corr,
-                                  c->dparams.bundle_adjustment != 0);
+                                  c->dparams.bundle_adjustment != 0, plan.narrow_est);
+    if (n_out >= 23) out[22] = plan.narrow_est;
     out[0] = (int64_t)plan.form; out[1] = plan.lists; out[2] = plan.single; out[3] = seq;
     for (int i = 0; i < 9; ++i) { out[4 + i] = (int64_t)(r.*WS_ROW[i]); out[13 + i] = (int64_t)(w.*WS_ROW[i]); }
   }
@@ -157,7 +165,7 @@ static int verify_sequence(sf_context* c, const StoreView& view, const int32_t* 
     case VerifyPlan::SPLIT:
       // (pass-2 lists only with the option or the bundle adjustment, whose launches read them; pass-1 lists always)
       c->w->last_lists_valid = c->debug_corr || c->dparams.bundle_adjustment != 0;
-      return sf_launch_verify_split(c, view, d_from, d_to, m, d_out);
+      return sf_launch_verify_split(c, view, d_from, d_to, m, d_out, plan.narrow_est);
     case VerifyPlan::FUSED:
       // one launch: every pair's whole two-pass pipeline inside its workgroup (k_verify.hip); no work lists
       c->w->last_lists_valid = c->debug_corr;
