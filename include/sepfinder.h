@@ -82,6 +82,10 @@ extern "C" {
 /* 8, additions: sf_grid_params, sf_grid_defaults, sf_grid_set_params, sf_grid_get_params, sf_compute_grid (Vis/GridRows x
       Vis/GridCols: the detector per cell of the ROI; 1 x 1 on a fresh handle, which changes nothing); the version
       number, sizeof(sf_front_params), sizeof(sf_params) and SF_K_COUNT stay.                                          */
+/* 8, additions: sf_freak_params, sf_freak_defaults, sf_set_feature_type_freak, sf_get_freak_params, sf_freak_set_pairs,
+      sf_freak_get_pairs, sf_freak_build_pattern, sf_freak_default_pairs (FAST/FREAK and GFTT/FREAK, Vis/FeatureType 3 and
+      5: 64-byte rows).  sf_set_feature_type still refuses 3 and 5; nothing existing changed, the version number,
+      sizeof(sf_params) and SF_K_COUNT stay.                                                                           */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -343,7 +347,8 @@ int  sf_brief_get_pattern(sf_handle h, int8_t* tests, int32_t cap_bytes, int32_t
    (the handle's sf_fast_params, det->max_features; quality_level / min_distance are validated and unused), everything
    after the detector is type 6's -- the same BRIEF table, the same border rule; a non-NULL orb is ignored.
    Any other feature_type or parameter, and 4 or 8 on a handle with desc_type 1, return SF_EINVAL -- 2 (ORB) included:
-   it takes detector parameters and is selected by sf_set_feature_type_orb.                                          */
+   it takes detector parameters and is selected by sf_set_feature_type_orb; 3 and 5 (FAST/FREAK, GFTT/FREAK) likewise
+   take parameters of their own and are selected by sf_set_feature_type_freak.                                       */
 typedef struct sf_orb_params {
   int32_t edge_threshold; /* ORB/EdgeThreshold, 19; 1 .. 64                                                         */
   int32_t patch_size;     /* ORB/PatchSize, 31 (only value accepted)                                                */
@@ -409,7 +414,7 @@ int  sf_detect_corners_device(sf_handle h, const uint8_t* d_image, int32_t width
                               int32_t max_corners, double quality_level, double min_distance,
                               sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
 /* The FAST detector of rtabmap's Vis/FeatureType 4 (FAST/BRIEF; also inside 2, sf_detect_orb_device below, and behind 3,
-   which is not built):
+   FAST/FREAK, sf_set_feature_type_freak below):
    cv::FastFeatureDetector (FAST-9/16, TYPE_9_16) followed by Feature2D::limitKeypoints [both upstream, restated in
    tests/fast_ref.py].  With d_k = I(p) - I(p + ring_k) over the 16 pixels of the radius-3 circle, m(p) = the maximum
    over the 16 cyclic arcs of 9 consecutive k of max(min d, min -d); p is a corner iff m(p) > threshold, for
@@ -474,6 +479,51 @@ int  sf_get_orb_detector(sf_handle h, sf_orb_detector_params* out);
 int  sf_detect_orb_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                           int32_t max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
                           sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
+/* FREAK descriptors: rtabmap's Vis/FeatureType 3 (FAST/FREAK: the corners of the FAST detector above) and 5 (GFTT/FREAK:
+   the corners of sf_detect_corners_device), cv::xfeatures2d::FREAK::compute on the given keypoints [upstream opencv_contrib,
+   restated in tests/freak_ref.py; DESIGN.md section 3 item 17g lists what the restatement decides].  Rows are 64 bytes
+   (512 bits) -- the store's one-width rule applies: a store that already holds 32-byte rows refuses them.
+   Pattern: 43 receptive fields (rings of 6 6 6 6 6 6 6 1, the centre last) at 64 scales x 256 orientations; scale s
+   multiplies the pattern by 2^(s n_octaves / 64).  Per keypoint: the scale index from its `size` (scale_normalized 1:
+   max((int)(log(size / 7) * 64 / (LOG2 n_octaves) + 0.5), 0), at most 63; 0: the fixed index of size 21), the border test
+   against that scale's pattern size (the keypoint is dropped when x <= P, y <= P, x >= width - P or y >= height - P), the
+   43 field means (a box on BRIEF's integral image; 10-bit bilinear interpolation for fields with sigma < 0.5), the angle
+   from 45 symmetric field pairs (orientation_normalized 1; else 0) -- written into the keypoint whatever it held -- and 512
+   comparisons mean_i >= mean_j on the fields of the nearest of the 256 orientations.  Bit layout: upstream's SSE order,
+   pair c = 128 q + 16 r + u (q < 4, r < 8, u < 16) is bit r (LSB = 0) of byte 16 q + 15 - u.
+   Everything around the descriptor -- ROI, grid, sub-pixel refinement, LK or block matching, the camera-image forms, the
+   3D points and the depth filter -- is what types 4 and 6 do; the keypoint's octave is not looked at.                */
+typedef struct sf_freak_params {
+  int32_t orientation_normalized;  /* FREAK/OrientationNormalized, 1; 0 or 1   */
+  int32_t scale_normalized;        /* FREAK/ScaleNormalized, 1; 0 or 1         */
+  float   pattern_scale;           /* FREAK/PatternScale, 22; (0, 64]          */
+  int32_t n_octaves;               /* FREAK/NOctaves, 4; 1 .. 8                */
+} sf_freak_params;                 /* 16 bytes */
+void sf_freak_defaults(sf_freak_params* p);
+/* Selects Vis/FeatureType 3 or 5 (freak NULL = defaults).  Another feature_type, out-of-range parameters and a handle
+   with desc_type 1 return SF_EINVAL and change nothing.  sf_get_feature_type reports 3 / 5 afterwards;
+   sf_set_feature_type(h, 4 | 6 | 8, ...) and sf_set_feature_type_orb switch back.  The pattern (8.4 MB of device memory)
+   is built and uploaded by the first extraction after the parameters changed; a handle that never selects FREAK
+   reserves nothing.  The two _orb_ batch calls refuse these types as they refuse every type but 2.                   */
+int  sf_set_feature_type_freak(sf_handle h, int32_t feature_type /* 3 or 5 */, const sf_freak_params* freak);
+int  sf_get_freak_params(sf_handle h, sf_freak_params* out);
+/* The 512 description pairs in OpenCV's own format (cv::xfeatures2d::FREAK::create's selectedPairs, the values of
+   FREAK_DEF_PAIRS): indices into the enumeration `for i in 1..42: for j in 0..i-1` of the 903 field pairs, index =
+   i (i - 1) / 2 + j.  n != 512 or an index outside [0, 903) returns SF_ERANGE and changes nothing; duplicates are
+   allowed, as upstream.  A fresh handle holds a GENERATED selection (sf_freak_default_pairs) -- NOT OpenCV's
+   FREAK_DEF_PAIRS, which is in neither the reference tree nor OpenCV's main repository: install that table here for
+   descriptors identical to a reference build's.  sf_freak_get_pairs: *n = 512; selected may be NULL, cap < 512 with
+   selected set returns SF_ERANGE.                                                                                    */
+int  sf_freak_set_pairs(sf_handle h, const int32_t* selected, int32_t n);
+int  sf_freak_get_pairs(sf_handle h, int32_t* selected, int32_t cap, int32_t* n);
+/* Handle-free host functions, usable without a GPU.  sf_freak_build_pattern: the table the kernel samples with, table
+   [64 scales][256 orientations][43 points][3] = {x, y, sigma} float32 (float64 arithmetic, rounded once) and sizes [64],
+   the border every scale asks for; p NULL = defaults; SF_EINVAL for out-of-range parameters.  Either output may be NULL.
+   sf_freak_default_pairs: the first 512 values of a Fisher-Yates shuffle of 0 .. 902 -- for k = 0 .. 511: swap a[k] with
+   a[k + next() % (903 - k)] -- driven by cv::RNG's multiply-with-carry step (s = (uint32)s * 4164903690 + (s >> 32),
+   next() = (uint32)s) from the seed 0x46524B21.                                                                       */
+int  sf_freak_build_pattern(const sf_freak_params* p, float* table, int32_t* sizes);
+void sf_freak_default_pairs(int32_t* selected /* [512] */);
 /* The two steps rtabmap's Feature2D::generateKeypoints puts around every detector, whatever the feature type
    [upstream rtabmap / OpenCV 3.2, restated in tests/subpix_ref.py; DESIGN.md section 3 item 17d lists what the restatement
    decides].  The reference reaches that function at myRegistrationVis.cpp:282 and leaves both steps off (INTEGRATION.md

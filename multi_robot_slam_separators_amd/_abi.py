@@ -272,6 +272,26 @@ FEATURE_GFTT_BRIEF = 6   # Vis/FeatureType values of sf_set_feature_type
 FEATURE_GFTT_ORB = 8
 FEATURE_FAST_BRIEF = 4
 FEATURE_ORB = 2          # ... and of sf_set_feature_type_orb
+FEATURE_FAST_FREAK = 3   # ... and of sf_set_feature_type_freak
+FEATURE_GFTT_FREAK = 5
+
+
+class FreakParams(C.Structure):
+    """sf_freak_params (include/sepfinder.h): rtabmap's FREAK/ parameters (Vis/FeatureType 3 and 5)."""
+    _fields_ = [("orientation_normalized", C.c_int32), ("scale_normalized", C.c_int32), ("pattern_scale", C.c_float),
+                ("n_octaves", C.c_int32)]
+
+
+def freak_params(orientation_normalized=1, scale_normalized=1, pattern_scale=22.0, n_octaves=4):
+    """FREAK/OrientationNormalized, FREAK/ScaleNormalized, FREAK/PatternScale, FREAK/NOctaves: rtabmap's defaults (what
+    sf_freak_defaults fills)."""
+    p = FreakParams()
+    p.orientation_normalized, p.scale_normalized, p.pattern_scale, p.n_octaves = (orientation_normalized, scale_normalized,
+                                                                                  pattern_scale, n_octaves)
+    return p
+
+
+FREAK_SCALES, FREAK_ORIENTATIONS, FREAK_POINTS, FREAK_PAIRS, FREAK_ALL_PAIRS, FREAK_BYTES = 64, 256, 43, 512, 903, 64
 
 
 SF_IMAGE_RGB8, SF_IMAGE_BGR8, SF_IMAGE_MONO8 = range(3)   # sf_image_format: the camera's images (cv_bridge encodings)

@@ -13,6 +13,7 @@
 //
 // GFTT/ORB (Vis/FeatureType 8) replaces the integral image and the BRIEF tests by k_orb_blur / k_orb_angle /
 // k_orb_points below (cv::ORB::compute on the given keypoints); the 3D points and the commit are shared.
+// FREAK (Vis/FeatureType 3 and 5) keeps the integral image and replaces k_extract_points by k_freak_points (k_freak.hip).
 //
 // Kernels (one keyframe = a few hundred to a few thousand corners of one 752 x 480 .. 1280 x 720 image):
 //   k_integral_rows   one workgroup per image row: wavefront scans of 256-pixel segments, running carry
@@ -30,6 +31,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "sf_extract_device.hpp"
 #include "sf_front_device.hpp"
 
 namespace {
@@ -37,16 +39,6 @@ namespace {
 constexpr int BRIEF_PATCH = 48;
 constexpr int BRIEF_KERNEL = 9;
 constexpr int BRIEF_BORDER = BRIEF_PATCH / 2 + BRIEF_KERNEL / 2;   // KeyPointsFilter::runByImageBorder margin
-
-// A batch of keyframes in one launch sequence (blockIdx.y = image, except k_extract_commit: blockIdx.x): images
-// img_stride bytes apart, integral images s_stride entries apart, per-corner arrays per_image entries apart, the corner
-// count of every image in d_n (device; null = the scalar n of the single-image call).  ORB on a pyramid: the pyramids
-// (levels >= 1) pyr_stride bytes apart.
-struct ExtractBatch {
-  size_t img_stride, s_stride, pyr_stride;
-  int per_image;
-  const int32_t* d_n;
-};
 
 // S is (h + 1) x (w + 1); this pass leaves ROW prefix sums in rows 1..h and zeroes row 0 / column 0.
 __global__ void __launch_bounds__(256)
@@ -121,41 +113,6 @@ __device__ __forceinline__ int32_t smoothed(const int32_t* __restrict__ S, int w
   const int y1 = min(y + hk + 1, h1 - 1), x1 = min(x + hk + 1, w1 - 1);
   return S[(size_t)y1 * w1 + x1] - S[(size_t)y1 * w1 + x - hk] - S[(size_t)(y - hk) * w1 + x1] +
          S[(size_t)(y - hk) * w1 + x - hk];
-}
-
-struct ExtractCam {
-  float fx, fy, cx, cy, cx_right, baseline, L[12], min_depth, max_depth;
-  int identity_local, filter;
-};
-
-// Byte 0's thread of a corner: the 3D point of the stereo pair (NaN when there is none) and the keep flag -- shared by
-// the BRIEF and the ORB descriptor kernels
-__device__ __forceinline__ void extract_point(const sf_keypoint& k, int i, bool inside, const float* __restrict__ right_x,
-                                              const uint8_t* __restrict__ status, const ExtractCam& cam,
-                                              float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep) {
-  const float qnan = __int_as_float(0x7FC00000);
-  float p0 = qnan, p1 = qnan, p2 = qnan;
-  if (inside && right_x && (!status || status[i])) {
-    const float disparity = k.x - right_x[i];
-    if (disparity != 0.0f && disparity > 0.0f && cam.baseline > 0.0f && cam.fx > 0.0f) {
-      float c = 0.0f;
-      if (cam.cx_right > 0.0f && cam.cx > 0.0f) c = cam.cx_right - cam.cx;
-      const float W = cam.baseline / (disparity + c);
-      const float x = (k.x - cam.cx) * W, y = (k.y - cam.cy) * W, z = cam.fx * W;
-      if (isfinite(x) && isfinite(y) && isfinite(z) && (cam.min_depth < 0.0f || z > cam.min_depth) &&
-          (cam.max_depth <= 0.0f || z <= cam.max_depth)) {
-        if (cam.identity_local) {
-          p0 = x; p1 = y; p2 = z;
-        } else {
-          p0 = ((cam.L[0] * x + cam.L[1] * y) + cam.L[2] * z) + cam.L[3];
-          p1 = ((cam.L[4] * x + cam.L[5] * y) + cam.L[6] * z) + cam.L[7];
-          p2 = ((cam.L[8] * x + cam.L[9] * y) + cam.L[10] * z) + cam.L[11];
-        }
-      }
-    }
-  }
-  xyz_tmp[3 * i] = p0; xyz_tmp[3 * i + 1] = p1; xyz_tmp[3 * i + 2] = p2;
-  keep[i] = (uint8_t)(inside && (!cam.filter || (isfinite(p0) && isfinite(p1) && isfinite(p2))));
 }
 
 // one thread per (corner, descriptor byte)
@@ -498,6 +455,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   if (pyr && (!orb || (!kind.pyr_stride && n_img != 1)))
     return sf_fail(c, SF_EINVAL, "ORB on a pyramid: one keyframe per call unless the detector has left the batch's pyramids");
   if (orb && bytes != ORB_BYTES) return sf_fail(c, SF_EINVAL, "ORB rows are %d bytes, not %d", ORB_BYTES, bytes);
+  if (kind.freak && (orb || bytes != FREAK_BYTES)) return sf_fail(c, SF_EINVAL, "FREAK rows are %d bytes, not %d", FREAK_BYTES, bytes);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_xyz, rows_all * 12)) != SF_OK) return rc;
@@ -547,7 +505,12 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   const sf_keypoint* kp_commit = d_kpts;
   if (n > 0) {
     const long long threads = (long long)n * bytes;
-    if (!orb) {
+    if (kind.freak) {                                     // the keypoints with their angles, for the commit
+      if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
+      sf_launch_freak_points(c, d_left, pitch, S, width, height, d_kpts, d_right_x, d_status, n, n_img, *kind.freak, ec,
+                             (sf_keypoint*)c->ex_kpts.p, (uint8_t*)c->ex_desc.p, (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);
+      kp_commit = (const sf_keypoint*)c->ex_kpts.p;
+    } else if (!orb) {
       hipLaunchKernelGGL(k_extract_points, dim3((unsigned)((threads + 255) / 256), n_img), dim3(256), 0, c->stream, S, width,
                          height, d_kpts, d_right_x, d_status, n, bytes, kind.d_tests, ec, (uint8_t*)c->ex_desc.p,
                          (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);

@@ -1,9 +1,10 @@
-// sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, Vis/FeatureType, NetVLAD, corner
+// sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, the FREAK tables, Vis/FeatureType, NetVLAD, corner
 // detection (GFTT, FAST, ORB), the ROI, the grid of cells and the sub-pixel refinement around it, stereo correspondence,
 // keyframe extraction and the camera-image forms of these calls (kernels in k_extract.hip, k_gftt.hip, k_fast.hip,
-// k_orb_detect.hip, k_subpix.hip, k_grid.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in
+// k_orb_detect.hip, k_freak.hip, k_subpix.hip, k_grid.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in
 // sf_sort.hip).
 #include <cmath>
+#include <vector>
 
 #include "sf_host.hpp"
 
@@ -42,7 +43,8 @@ static int check_pixels(sf_context* c, int width, int height) {
 
 // every feature type here writes binary rows into the keyframe store
 static int check_binary_rows(sf_context* c, int feature_type) {
-  const char* name = feature_type == 2 ? "ORB" : feature_type == 4 ? "FAST/BRIEF" : feature_type == 8 ? "GFTT/ORB" : "GFTT/BRIEF";
+  const char* name = feature_type == 2 ? "ORB" : feature_type == 4 ? "FAST/BRIEF" : feature_type == 8 ? "GFTT/ORB" :
+                     feature_type == 3 ? "FAST/FREAK" : feature_type == 5 ? "GFTT/FREAK" : "GFTT/BRIEF";
   if (c->params.desc_type != 0)
     return sf_fail(c, SF_EINVAL, "%s writes binary descriptors: a handle with desc_type %d cannot store them", name, c->params.desc_type);
   return SF_OK;
@@ -53,6 +55,9 @@ static int check_gftt(sf_context* c, double quality_level, double min_distance) 
     return sf_fail(c, SF_EINVAL, "qualityLevel must be > 0 and minDistance >= 0 (cv::goodFeaturesToTrack asserts the same)");
   return SF_OK;
 }
+
+// the types whose corners come from the FAST detector (the others of 3 .. 8: GFTT)
+static bool fast_corners(int feature_type) { return feature_type == 4 || feature_type == 3; }
 
 // the caller's parameter block, or the defaults when it passed none
 template <class T>
@@ -153,8 +158,12 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
     }
     case 2:
       return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB) takes detector parameters: select it with sf_set_feature_type_orb");
+    case 3:
+    case 5:
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d (%s/FREAK) takes parameters of its own: select it with sf_set_feature_type_freak",
+                     feature_type, feature_type == 3 ? "FAST" : "GFTT");
     default:
-      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (2 = ORB by sf_set_feature_type_orb, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (2 = ORB by sf_set_feature_type_orb, 3 = FAST/FREAK and 5 = GFTT/FREAK by sf_set_feature_type_freak, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
                      feature_type);
   }
   c->feature_type = feature_type;
@@ -260,9 +269,108 @@ extern "C" int sf_orb_get_pattern(sf_handle c, int8_t* tests, int32_t cap_bytes,
   return SF_OK;
 }
 
+// ---- FAST/FREAK and GFTT/FREAK (Vis/FeatureType 3 and 5; kernel and table builders in k_freak.hip) -------------------
+static int freak_validate(sf_context* c, const sf_freak_params& f) {
+  if ((f.orientation_normalized != 0 && f.orientation_normalized != 1) || (f.scale_normalized != 0 && f.scale_normalized != 1))
+    return sf_fail(c, SF_EINVAL, "FREAK orientation_normalized %d, scale_normalized %d: each is 0 or 1", f.orientation_normalized,
+                   f.scale_normalized);
+  if (!(f.pattern_scale > 0.0f) || !(f.pattern_scale <= 64.0f))
+    return sf_fail(c, SF_EINVAL, "FREAK pattern_scale %g outside (0, 64]", (double)f.pattern_scale);
+  if (f.n_octaves < 1 || f.n_octaves > 8) return sf_fail(c, SF_EINVAL, "FREAK n_octaves %d outside 1 .. 8", f.n_octaves);
+  return SF_OK;
+}
+
+extern "C" int sf_set_feature_type_freak(sf_handle c, int32_t feature_type, const sf_freak_params* freak) {
+  if (!c) return SF_EINVAL;
+  if (feature_type != 3 && feature_type != 5)
+    return sf_fail(c, SF_EINVAL, "sf_set_feature_type_freak selects Vis/FeatureType 3 (FAST/FREAK) or 5 (GFTT/FREAK), not %d", feature_type);
+  int rc = check_binary_rows(c, feature_type);
+  if (rc != SF_OK) return rc;
+  const sf_freak_params f = arg_or_defaults(freak, sf_freak_defaults);
+  if ((rc = freak_validate(c, f)) != SF_OK) return rc;
+  if (memcmp(&f, &c->freak, sizeof f) != 0) c->freak_pattern_ok = c->freak_tables_ok = false;   // rebuilt by the next extraction
+  c->freak = f;
+  c->feature_type = feature_type;
+  return SF_OK;
+}
+
+extern "C" int sf_get_freak_params(sf_handle c, sf_freak_params* out) {
+  if (!c || !out) return SF_EINVAL;
+  *out = c->freak;
+  return SF_OK;
+}
+
+static const int32_t* freak_pairs(sf_context* c) {
+  if (!c->freak_pairs_set) {
+    sf_freak_default_pairs(c->freak_pairs);
+    c->freak_pairs_set = true;
+  }
+  return c->freak_pairs;
+}
+
+extern "C" int sf_freak_set_pairs(sf_handle c, const int32_t* selected, int32_t n) {
+  if (!c || !selected) return SF_EINVAL;
+  if (n != FREAK_PAIRS) return sf_fail(c, SF_ERANGE, "FREAK descriptors are %d pairs, not %d", FREAK_PAIRS, n);
+  for (int k = 0; k < n; ++k)
+    if (selected[k] < 0 || selected[k] >= FREAK_ALL_PAIRS)
+      return sf_fail(c, SF_ERANGE, "FREAK pair index %d (entry %d) outside [0, %d)", selected[k], k, FREAK_ALL_PAIRS);
+  memcpy(c->freak_pairs, selected, sizeof c->freak_pairs);
+  c->freak_pairs_set = true;
+  c->freak_tables_ok = false;
+  return SF_OK;
+}
+
+extern "C" int sf_freak_get_pairs(sf_handle c, int32_t* selected, int32_t cap, int32_t* n) {
+  if (!c || !n) return SF_EINVAL;
+  *n = FREAK_PAIRS;
+  if (selected) {
+    if (cap < FREAK_PAIRS) return sf_fail(c, SF_ERANGE, "pair buffer holds %d of %d indices", cap, FREAK_PAIRS);
+    memcpy(selected, freak_pairs(c), sizeof c->freak_pairs);
+  }
+  return SF_OK;
+}
+
+// The device tables of the handle's FREAK parameters and pairs, built and uploaded when either has changed since the
+// last upload (the pattern, 8.4 MB, only with the parameters)
+static int freak_ensure(sf_context* c) {
+  if (c->freak_pattern_ok && c->freak_tables_ok) return SF_OK;
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->freak_pattern, FREAK_PATTERN_FLOATS * sizeof(float))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->freak_tables, FREAK_TABLE_BYTES)) != SF_OK) return rc;
+  uint8_t* tables = c->freak_tables_host;
+  std::vector<float> pattern;
+  if (!c->freak_pattern_ok) {
+    pattern.resize(FREAK_PATTERN_FLOATS);
+    if (sf_freak_build_pattern(&c->freak, pattern.data(), (int32_t*)(tables + FREAK_TABLE_SIZES)) != SF_OK)
+      return sf_fail(c, SF_EINVAL, "FREAK parameters out of range");
+    sf_freak_orientation_table(pattern.data(), (int32_t*)(tables + FREAK_TABLE_ORIENT));
+    SF_HIP(c, hipMemcpyAsync(c->freak_pattern.p, pattern.data(), FREAK_PATTERN_FLOATS * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  }
+  sf_freak_bit_table(freak_pairs(c), tables + FREAK_TABLE_PAIRS);
+  SF_HIP(c, hipMemcpyAsync(c->freak_tables.p, tables, FREAK_TABLE_BYTES, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));   // (the host pattern goes away with this call)
+  SfFreakTables& T = c->freak_dev;
+  T.pattern = (const float*)c->freak_pattern.p;
+  T.pairs = (const uint8_t*)c->freak_tables.p + FREAK_TABLE_PAIRS;
+  T.orient = (const int32_t*)((const uint8_t*)c->freak_tables.p + FREAK_TABLE_ORIENT);
+  T.sizes = (const int32_t*)((const uint8_t*)c->freak_tables.p + FREAK_TABLE_SIZES);
+  T.size_cst = (float)(FREAK_SCALES / (0.693147180559945 * c->freak.n_octaves));
+  T.fixed_idx = std::min(std::max((int)(1.0986122886681 * T.size_cst + 0.5), 0), FREAK_SCALES - 1);   // (upstream does not clamp: n_octaves 1)
+  T.orientation_normalized = c->freak.orientation_normalized;
+  T.scale_normalized = c->freak.scale_normalized;
+  c->freak_pattern_ok = c->freak_tables_ok = true;
+  return SF_OK;
+}
+
 // The descriptor of the handle's feature type (ExtractKind: sf_internal.hpp)
 static int extract_kind(sf_context* c, ExtractKind* k) {
   int rc;
+  if (c->feature_type == 3 || c->feature_type == 5) {
+    if ((rc = check_binary_rows(c, c->feature_type)) != SF_OK) return rc;
+    if ((rc = freak_ensure(c)) != SF_OK) return rc;
+    *k = {FREAK_BYTES, nullptr, nullptr, nullptr, 0, &c->freak_dev};
+    return SF_OK;
+  }
   if (c->feature_type == 8 || c->feature_type == 2) {
     if ((rc = check_binary_rows(c, c->feature_type)) != SF_OK) return rc;
     if ((rc = orb_ensure(c)) != SF_OK) return rc;
@@ -445,7 +553,7 @@ static int front_plan(sf_context* c, int width, int height, FrontPlan* fp) {
   int32_t roi[4] = {0, 0, 0, 0};
   const int rc = sf_compute_roi(width, height, f.roi_ratios, roi);
   if (c->feature_type == 2 && (f.roi_ratios[0] != 0.f || f.roi_ratios[1] != 0.f || f.roi_ratios[2] != 0.f || f.roi_ratios[3] != 0.f))
-    return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 2 (ORB) is not built: the batch form reuses the detector's pyramid for the descriptors; set the ratios to 0 or choose feature type 4, 6 or 8");
+    return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 2 (ORB) is not built: the batch form reuses the detector's pyramid for the descriptors; set the ratios to 0 or choose feature type 3, 4, 5, 6 or 8");
   if (rc != SF_OK)
     return sf_fail(c, SF_EINVAL, "Vis/RoiRatios %g %g %g %g leave a ROI of %d x %d in a %d x %d image: both sides must be >= 3",
                    (double)f.roi_ratios[0], (double)f.roi_ratios[1], (double)f.roi_ratios[2], (double)f.roi_ratios[3], roi[2], roi[3], width, height);
@@ -507,7 +615,7 @@ static int grid_plan(sf_context* c, int width, int height, int max_features, Fro
   const sf_grid_params& g = c->grid;
   if (g.grid_rows == 1 && g.grid_cols == 1) return SF_OK;
   if (c->feature_type == 2)
-    return sf_fail(c, SF_EINVAL, "Vis/GridRows x Vis/GridCols %d x %d under Vis/FeatureType 2 (ORB) is not built: every cell would need a pyramid of its own; set the grid to 1 x 1 or choose feature type 4, 6 or 8",
+    return sf_fail(c, SF_EINVAL, "Vis/GridRows x Vis/GridCols %d x %d under Vis/FeatureType 2 (ORB) is not built: every cell would need a pyramid of its own; set the grid to 1 x 1 or choose feature type 3, 4, 5, 6 or 8",
                    g.grid_rows, g.grid_cols);
   int32_t o[6];
   const int rc = sf_compute_grid(width, height, c->front.roi_ratios, &g, max_features, o);
@@ -536,7 +644,7 @@ static int grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_par
   g.per_image = cells; g.cols = fp.cols;
   g.row_step = (size_t)fp.row_size * pitch; g.col_step = (size_t)fp.col_size;
   const uint8_t* d_roi = d_left + (size_t)fp.y * pitch + fp.x;
-  if (c->feature_type == 4)
+  if (fast_corners(c->feature_type))
     rc = sf_launch_detect_fast_batch(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota, &c->fast,
                                      d_cell_kpts, fp.quota, d_cell_n, g);
   else
@@ -720,6 +828,7 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
     if ((rc = grid_detect(c, fp, dp, d_left, 0, 1, width, d_kpts, (int32_t*)c->ft_counts.p)) != SF_OK) return rc;
     rc = sf_word_to_host(c, c->ft_counts.p, &n);
   } else switch (c->feature_type) {
+    case 3:
     case 4: rc = sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
     case 2: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
     default:
@@ -842,7 +951,7 @@ static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan*
   if ((rc = sf_buf_reserve(c, c->ft_flow, rows_all * 16)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ft_counts, (size_t)n * 4)) != SF_OK) return rc;
   if ((rc = sf_store_reserve(c, c->store, c->store.slots + n, maxf, plan->kind.bytes)) != SF_OK) return rc;
-  if (c->feature_type == 4 && (rc = check_pixels(c, width, height)) != SF_OK) return rc;
+  if (fast_corners(c->feature_type) && (rc = check_pixels(c, width, height)) != SF_OK) return rc;
   return SF_OK;
 }
 
@@ -863,7 +972,7 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
     kind.pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;   // no ROI: front_plan)
   } else if (fp.grid()) {                                // the cells as the detector's images, joined by k_grid_gather
     rc = grid_detect(c, fp, dp, d_left, image_stride, n, pitch, d_kpts, d_n);
-  } else if (c->feature_type == 4) {
+  } else if (fast_corners(c->feature_type)) {
     rc = sf_launch_detect_fast_batch(c, d_roi, image_stride, n, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
   } else {
     rc = sf_launch_detect_corners_batch(c, d_roi, image_stride, n, fp.w, fp.h, pitch, maxf, dp.quality_level,

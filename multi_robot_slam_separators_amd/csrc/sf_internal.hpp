@@ -193,6 +193,21 @@ struct Workspace {
   }
 };
 
+// FREAK rows (types 3 and 5): the tables of k_freak_points -- the integral image is BRIEF's, the rows are 64 bytes
+struct SfFreakTables {
+  const float* pattern;        // [64][256][43] {x, y, sigma}: sf_freak_build_pattern's table
+  const uint8_t* pairs;        // [64 bytes][8 bits] {i, j}: the pair behind every descriptor bit (sf_freak_bit_table)
+  const int32_t* orient;       // [45] {i, j, weight_dx, weight_dy}
+  const int32_t* sizes;        // [64]: the border every scale asks for
+  float size_cst;              // (float)(64 / (LOG2 n_octaves))
+  int fixed_idx;               // the scale index of every keypoint when scale_normalized is 0
+  int orientation_normalized, scale_normalized;
+};
+constexpr int FREAK_SCALES = 64, FREAK_ORIENTATIONS = 256, FREAK_POINTS = 43, FREAK_PAIRS = 512, FREAK_ORIENT_PAIRS = 45,
+              FREAK_ALL_PAIRS = 903, FREAK_BYTES = 64;
+constexpr size_t FREAK_PATTERN_FLOATS = (size_t)FREAK_SCALES * FREAK_ORIENTATIONS * FREAK_POINTS * 3;
+constexpr size_t FREAK_TABLE_PAIRS = 0, FREAK_TABLE_ORIENT = 1024, FREAK_TABLE_SIZES = 1792, FREAK_TABLE_BYTES = 2048;
+
 struct sf_context {
   sf_params params;
   DeviceParams dparams;
@@ -247,6 +262,18 @@ struct sf_context {
   Buf orb_tests, ex_blur, ex_kpts;
   // 4 = FAST/BRIEF: the detector is k_fast.hip's with these parameters (sf_fast_set_params), the rest is type 6's
   sf_fast_params fast = {20, 1};
+  // 3 = FAST/FREAK, 5 = GFTT/FREAK (sf_set_feature_type_freak; k_freak.hip): type 4's / type 6's corners with 64-byte FREAK
+  // rows.  freak_pairs: the 512 selected pairs in OpenCV's selectedPairs format (freak_pairs_set false: the generated
+  // default selection, not made yet).  On the device, reserved by the first extraction under a FREAK type only:
+  // freak_pattern [64 scales][256 orientations][43 points] {x, y, sigma} and freak_tables (FREAK_TABLE_BYTES: the pairs of
+  // every descriptor byte, the 45 orientation pairs with their weights, the 64 pattern sizes); freak_pattern_ok /
+  // freak_tables_ok false: what is there was built for other parameters / pairs
+  sf_freak_params freak = {1, 1, 22.0f, 4};
+  bool freak_pairs_set = false, freak_pattern_ok = false, freak_tables_ok = false;
+  int32_t freak_pairs[512] = {};
+  Buf freak_pattern, freak_tables;
+  alignas(16) uint8_t freak_tables_host[FREAK_TABLE_BYTES] = {};   // the host copy of freak_tables
+  SfFreakTables freak_dev = {};                // the kernel's view of the two buffers and the parameters
   // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
   // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
   // the image at hand; orb_work: the detector's candidate lists
@@ -652,7 +679,8 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
                                 const sf_stereo_flow_params* prm, float* d_right_xy, uint8_t* d_status, float* d_right_x,
                                 float* d_err);
 // The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF rows, else ORB
-// rows), the pyramid of ORB (NULL: one level; else ORB rows on the keypoint's own level, type 2).  pyr_stride 0: the
+// rows), the pyramid of ORB (NULL: one level; else ORB rows on the keypoint's own level, type 2), the FREAK tables (NULL
+// unless the type is 3 or 5).  pyr_stride 0: the
 // extraction builds the pyramid of its one image; else sf_launch_detect_orb_batch has left the pyramids of the call's
 // images in c->orb_pyr, pyr_stride bytes apart, and the extraction reads them there
 struct ExtractKind {
@@ -661,7 +689,12 @@ struct ExtractKind {
   const sf_orb_params* orb;
   const sf_orb_detector_params* pyr;
   size_t pyr_stride;
+  const SfFreakTables* freak = nullptr;   // not null: FREAK rows (bytes 64; d_tests, orb and pyr unused)
 };
+// host halves of the FREAK tables (k_freak.hip): the orientation pairs' weights from scale 0 / orientation 0 of a pattern,
+// and the device layout of the selected pairs
+void sf_freak_orientation_table(const float* pattern, int32_t* orient /* [45][4] */);
+void sf_freak_bit_table(const int32_t* selected /* [512] */, uint8_t* table /* [64][8][2] */);
 // keyframes into the slots of c->store from `slot` on (k_extract.hip); one keyframe: img_stride 0, n_img 1, d_n null
 int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_stride, int n_img, int width, int height,
                             int pitch, const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n,

@@ -102,6 +102,13 @@ def load():
         "sf_get_orb_detector": (C.c_int, [vp, P(_abi.OrbDetectorParams)]),
         "sf_detect_orb_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.OrbDetectorParams), P(_abi.OrbParams), vp, i32,
                                            P(i32)]),
+        "sf_freak_defaults": (None, [P(_abi.FreakParams)]),
+        "sf_set_feature_type_freak": (C.c_int, [vp, i32, P(_abi.FreakParams)]),
+        "sf_get_freak_params": (C.c_int, [vp, P(_abi.FreakParams)]),
+        "sf_freak_set_pairs": (C.c_int, [vp, vp, i32]),
+        "sf_freak_get_pairs": (C.c_int, [vp, vp, i32, P(i32)]),
+        "sf_freak_build_pattern": (C.c_int, [P(_abi.FreakParams), vp, vp]),
+        "sf_freak_default_pairs": (None, [vp]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
         "sf_stereo_flow_defaults": (None, [P(_abi.StereoFlowParams)]),
         "sf_detector_defaults": (None, [P(_abi.DetectorParams)]),
@@ -217,7 +224,29 @@ EXPORTED = [
     "sf_front_defaults", "sf_front_set_params", "sf_front_get_params", "sf_compute_roi", "sf_corner_subpix_device",
     "sf_stereo_defaults", "sf_stereo_set_params", "sf_stereo_get_params", "sf_stereo_block_match_device",
     "sf_grid_defaults", "sf_grid_set_params", "sf_grid_get_params", "sf_compute_grid",
+    "sf_freak_defaults", "sf_set_feature_type_freak", "sf_get_freak_params", "sf_freak_set_pairs", "sf_freak_get_pairs",
+    "sf_freak_build_pattern", "sf_freak_default_pairs",
 ]
+
+
+def freak_build_pattern(params=None):
+    """sf_freak_build_pattern (no GPU, no handle): the table FREAK samples with, float32 [64, 256, 43, 3] = (x, y, sigma)
+    per scale, orientation and receptive field, and the int32 [64] border every scale asks for."""
+    table = np.zeros((_abi.FREAK_SCALES, _abi.FREAK_ORIENTATIONS, _abi.FREAK_POINTS, 3), np.float32)
+    sizes = np.zeros(_abi.FREAK_SCALES, np.int32)
+    rc = load().sf_freak_build_pattern(C.byref(params) if params is not None else None, C.c_void_p(table.ctypes.data),
+                                       C.c_void_p(sizes.ctypes.data))
+    if rc != _abi.SF_OK:
+        raise SepfinderError(rc, "FREAK parameters out of range")
+    return table, sizes
+
+
+def freak_default_pairs():
+    """sf_freak_default_pairs (no GPU, no handle): the generated selection of a fresh handle, int32 [512] indices into
+    the 903 pairs (i, j < i) -- NOT OpenCV's FREAK_DEF_PAIRS."""
+    sel = np.zeros(_abi.FREAK_PAIRS, np.int32)
+    load().sf_freak_default_pairs(C.c_void_p(sel.ctypes.data))
+    return sel
 
 
 def _ptr(a):
@@ -438,8 +467,33 @@ class SeparatorFinder:
         self._check(self._L.sf_orb_get_pattern(self._h, C.c_void_p(buf.ctypes.data), 32, C.byref(n)))
         return buf[:8 * n.value].copy()
 
+    def set_feature_type_freak(self, feature_type, freak=None):
+        """Vis/FeatureType 3 (FAST/FREAK: the corners of fast_set_params) or 5 (GFTT/FREAK) with freak (_abi.FreakParams;
+        None = rtabmap's FREAK/ defaults): 64-byte rows.  set_feature_type(4 | 6 | 8) and set_feature_type_orb switch
+        back."""
+        self._check(self._L.sf_set_feature_type_freak(self._h, int(feature_type), C.byref(freak) if freak is not None else None))
+
+    def get_freak_params(self):
+        f = _abi.FreakParams()
+        self._check(self._L.sf_get_freak_params(self._h, C.byref(f)))
+        return f
+
+    def freak_set_pairs(self, selected):
+        """selected: 512 indices into the 903 pairs `for i in 1..42: for j in 0..i-1` -- OpenCV's selectedPairs format
+        (FREAK_DEF_PAIRS pastes in unchanged)."""
+        t = np.ascontiguousarray(selected, dtype=np.int32).reshape(-1)
+        self._check(self._L.sf_freak_set_pairs(self._h, C.c_void_p(t.ctypes.data), t.size))
+
+    def freak_get_pairs(self):
+        n = C.c_int32()
+        buf = np.zeros(_abi.FREAK_PAIRS, np.int32)
+        self._check(self._L.sf_freak_get_pairs(self._h, C.c_void_p(buf.ctypes.data), buf.size, C.byref(n)))
+        return buf[:n.value].copy()
+
     def descriptor_bytes(self):
         """Row bytes the extraction calls write with the handle's feature type."""
+        if self.get_feature_type()[0] in (_abi.FEATURE_FAST_FREAK, _abi.FEATURE_GFTT_FREAK):
+            return _abi.FREAK_BYTES
         return 32 if self.get_feature_type()[0] in (_abi.FEATURE_GFTT_ORB, _abi.FEATURE_ORB) else self.brief_get_pattern().shape[0] // 8
 
     # -- NetVLAD inference (SURVEY section 8(f) rank 4) -------------------------------------------------

@@ -99,7 +99,8 @@ class SepfinderGeometricTools {
     }
 
     // Vis/FeatureType: 6 = GFTT/BRIEF (default), 8 = GFTT/ORB with ORB/EdgeThreshold, 4 = FAST/BRIEF with
-    // FAST/Threshold, 2 = ORB with ORB/ScaleFactor, NLevels, FirstLevel, ScoreType, FastThreshold; see INTEGRATION.md
+    // FAST/Threshold, 2 = ORB with ORB/ScaleFactor, NLevels, FirstLevel, ScoreType, FastThreshold, 3 = FAST/FREAK and
+    // 5 = GFTT/FREAK with FREAK/OrientationNormalized, ScaleNormalized, PatternScale, NOctaves; see INTEGRATION.md
     int feature_type = 6, edge_threshold = 19;
     n.param("feature_type", feature_type, 6);
     n.param("orb_edge_threshold", edge_threshold, 19);
@@ -123,6 +124,31 @@ class SepfinderGeometricTools {
       n.param("orb_fast_threshold", det.fast_threshold, det.fast_threshold);
       if (sf_set_feature_type_orb(sf_, &det, &orb) != SF_OK)
         ROS_ERROR("feature_type 2: %s", sf_last_error(sf_));
+    } else if (feature_type == 3 || feature_type == 5) {
+      sf_freak_params freak;
+      sf_freak_defaults(&freak);
+      bool orientation_normalized = freak.orientation_normalized != 0, scale_normalized = freak.scale_normalized != 0;
+      double pattern_scale = freak.pattern_scale;
+      n.param("freak_orientation_normalized", orientation_normalized, orientation_normalized);
+      n.param("freak_scale_normalized", scale_normalized, scale_normalized);
+      n.param("freak_pattern_scale", pattern_scale, pattern_scale);
+      n.param("freak_n_octaves", freak.n_octaves, freak.n_octaves);
+      freak.orientation_normalized = orientation_normalized ? 1 : 0;
+      freak.scale_normalized = scale_normalized ? 1 : 0;
+      freak.pattern_scale = (float)pattern_scale;
+      if (sf_set_feature_type_freak(sf_, feature_type, &freak) != SF_OK)
+        ROS_ERROR("feature_type %d: %s", feature_type, sf_last_error(sf_));
+      // OpenCV's FREAK_DEF_PAIRS (512 int32: the selectedPairs indices), if the integrator provides them
+      std::string pairs_file;
+      if (n.getParam("freak_pairs_file", pairs_file) && !pairs_file.empty()) {
+        std::ifstream in(pairs_file.c_str(), std::ios::binary);
+        std::vector<char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+        if (raw.size() != 512 * sizeof(int32_t) ||
+            sf_freak_set_pairs(sf_, reinterpret_cast<const int32_t*>(raw.data()), 512) != SF_OK)
+          ROS_ERROR("freak_pairs_file %s: 2048 bytes expected (%s)", pairs_file.c_str(), sf_last_error(sf_));
+      } else {
+        ROS_WARN("no freak_pairs_file: descriptors will not match a robot that runs the reference's OpenCV FREAK");
+      }
     } else if (sf_set_feature_type(sf_, feature_type, &orb) != SF_OK) {
       ROS_ERROR("feature_type %d: %s", feature_type, sf_last_error(sf_));
     }
@@ -187,6 +213,7 @@ class SepfinderGeometricTools {
     int32_t bytes = 0, feature_type = 6;
     sf_get_feature_type(sf_, &feature_type, nullptr);
     if (feature_type == 8 || feature_type == 2) sf_orb_get_pattern(sf_, nullptr, 0, &bytes);   // 32-byte ORB rows
+    else if (feature_type == 3 || feature_type == 5) bytes = 64;                               // 64-byte FREAK rows
     else sf_brief_get_pattern(sf_, nullptr, 0, &bytes);
     const int cap = 32767;                                            // KeyPointVec.size is an int16
     std::vector<uint8_t> desc((size_t)cap * bytes);
