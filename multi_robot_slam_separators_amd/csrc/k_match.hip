@@ -417,7 +417,7 @@ __device__ __forceinline__ void knn2_scan_lds(const uint32_t* fromD, int Kf, con
 //     orders by distance first (steps of 2) and by the LOWER from index second (fraction < 1): the
 //     BFMatcher tie rule with no separate index bookkeeping;
 //   * best per column exactly, second best optimistically (top2_update16: 10 ops per 16 cells), one cross-half merge,
-//     and the exact second best of a column that passes NNDR from the best row's class (mf_repair_d2).
+//     and, for a column that passes NNDR, the decision again on the best row's class (mf_repair_accept: once per group).
 typedef int mf_v8i __attribute__((ext_vector_type(8)));
 typedef float mf_v16f __attribute__((ext_vector_type(16)));
 constexpr float MF_FR = 1.f / 2048.f;        // index fraction (kcap <= 2048 rows on this path)
@@ -448,13 +448,22 @@ __device__ __forceinline__ mf_v8i fp4_spread_from(uint32_t x, uint32_t m88, uint
   o[3] = (int)(x & 0x11111111u);
   return o;
 }
-__device__ __forceinline__ mf_v8i fp4_spread_to(uint32_t y, uint32_t m88, uint32_t c22) {
+// The three shifted classes carry the NEGATED bit under the sign: (~y << k) & 0x8888.. | code.  Written as the bit-field
+// insert code' ^ ((y << k) & (code ^ code')) with code' = code | 0x8888.. -- where the shifted bit is set the code alone,
+// elsewhere the code under a set sign -- it is one three-input instruction behind the shift (v_bfi_b32 / v_bitop3_b32) and
+// needs no ~y: 7 VALU ops per raw dword instead of 8.  The compiler forms it only from constants it cannot see through
+// (FpB: the codes in scalar registers, the signed codes in VGPRs, mf_load_b); with literals it folds the expression
+// back into a negation and three v_and_or_b32.
+struct FpB {
+  uint32_t c2, c4, c6;   // 0x2222.., 0x4444.., 0x6666..
+  uint32_t e2, e4, e6;   // the same under 0x8888..
+};
+__device__ __forceinline__ mf_v8i fp4_spread_to(uint32_t y, uint32_t m88, uint32_t c22, const FpB& K) {
   mf_v8i o = {0, 0, 0, 0, 0, 0, 0, 0};
-  const uint32_t n = ~y;
   o[0] = (int)((y & m88) | c22);
-  o[1] = (int)(((n << 1) & m88) | c22);
-  o[2] = (int)(((n << 2) & m88) | 0x44444444u);
-  o[3] = (int)(((n << 3) & m88) | 0x66666666u);
+  o[1] = (int)(K.e2 ^ ((y << 1) & (K.c2 ^ K.e2)));
+  o[2] = (int)(K.e4 ^ ((y << 2) & (K.c4 ^ K.e4)));
+  o[3] = (int)(K.e6 ^ ((y << 3) & (K.c6 ^ K.e6)));
   return o;
 }
 
@@ -485,8 +494,9 @@ __device__ __forceinline__ void load_raw(const uint32_t* p, uint32_t (&raw)[KS])
 //   s is the second largest of the CLASS MAXIMA, i.e. the best score among the rows outside the best row's class.
 // The exact second best is therefore max(s, best of the OTHER rows of the best row's class): s decodes to a distance
 // d2' >= d2, the only consumer of d2 is the NNDR test of match_v2_body, a column that fails it against d2' fails it
-// against d2, and a column that passes has its class looked at again there (mf_repair_d2) -- docs/match_second_best.md,
-// tests/test_match_lazy_second_model.py.
+// against d2, and a column that passes has its class looked at again there (mf_repair_accept: certified on half rows,
+// exactly otherwise -- mf_repair_d2) -- docs/match_second_best.md, docs/match_repair_once.md,
+// tests/test_match_lazy_second_model.py, tests/test_match_half_bound_model.py.
 // Written as asm because fmaxf() costs a canonicalising self-max per operand; the FIRST read of the accumulator is
 // left to the compiler (a builtin: med3(v0, v1, +inf) = max(v0, v1), hence 11 ops on this unpipelined path), which
 // places the MFMA-result wait states in front of it -- the hazard recogniser does not look inside an asm statement.
@@ -583,6 +593,13 @@ __device__ __forceinline__ void mf_load_b(const uint32_t* __restrict__ dT, int K
   uint32_t m88, c22;   // constants pinned in VGPRs (see fp4_spread)
   asm volatile("v_mov_b32 %0, 0x88888888" : "=v"(m88));
   asm volatile("v_mov_b32 %0, 0x22222222" : "=v"(c22));
+  FpB K;
+  asm volatile("s_mov_b32 %0, 0x22222222" : "=s"(K.c2));
+  asm volatile("s_mov_b32 %0, 0x44444444" : "=s"(K.c4));
+  asm volatile("s_mov_b32 %0, 0x66666666" : "=s"(K.c6));
+  asm volatile("v_mov_b32 %0, 0xaaaaaaaa" : "=v"(K.e2));
+  asm volatile("v_mov_b32 %0, 0xcccccccc" : "=v"(K.e4));
+  asm volatile("v_mov_b32 %0, 0xeeeeeeee" : "=v"(K.e6));
   uint32_t raw[NTL][KS];
 #pragma unroll
   for (int j = 0; j < NTL; ++j) load_raw<KS>(dT + (size_t)min(tile[j] * 32 + r, Kt - 1) * W + KS * h, raw[j]);
@@ -595,7 +612,7 @@ __device__ __forceinline__ void mf_load_b(const uint32_t* __restrict__ dT, int K
     uint32_t p = 0;
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
-      B.Bf[j][k] = fp4_spread_to(raw[j][k], m88, c22);
+      B.Bf[j][k] = fp4_spread_to(raw[j][k], m88, c22, K);
       p += __popc(raw[j][k] & 0x77777777u);
     }
     pk |= p << (8 * j);
@@ -772,7 +789,8 @@ constexpr int mf_passes(int ntl) { return ntl == 1 ? 1 : ntl / 2; }
 // half of a tile's rows each), so each half sends the other the tile that one decodes: one exchange per value and pass,
 // one decode for two tiles.
 // d1 and its index are exact; d2 is the OPTIMISTIC second best (>= the exact one: the best distance among the rows outside
-// the best row's class, top2_update16) -- its one consumer, the NNDR test of match_v2_body, repairs it where it matters.
+// the best row's class, top2_update16) -- its one consumer, the NNDR test of match_v2_body, decides again on the class
+// where it matters.
 template <int W, int NTL, bool PIPE = false>
 __device__ __forceinline__ void mf_scan(const uint32_t* fromD, int Kf, const MfB<W, NTL>& B, int lane,
                                         uint32_t (&d1)[mf_passes(NTL)], uint32_t (&d2)[mf_passes(NTL)],
@@ -842,7 +860,7 @@ __device__ __forceinline__ void knn2_mfma(const uint32_t* fromD, int Kf, const u
 // idx & ~31, its lane half idx & 4, registers 0..14 = rows + {0..3, 8..11, 16..19, 24..26}; row 27 of the half (register
 // 15) is a class of its own, with nothing to repair.  Rows >= Kf are left out (the LDS behind the staged rows holds the
 // counters; the reads stay inside the block, sf_match_lds_bytes), and so is the best row itself.  Per lane: only lanes
-// that accepted call it.
+// that the half-row certificate of mf_repair_accept left undecided call it (all repairing lanes when nndr < 0).
 template <int W>
 __device__ __forceinline__ uint32_t mf_repair_d2(const uint32_t* fromD, int Kf, const uint32_t* __restrict__ q_row, int idx,
                                                  uint32_t d2) {
@@ -865,6 +883,63 @@ __device__ __forceinline__ uint32_t mf_repair_d2(const uint32_t* fromD, int Kf, 
     }
   }
   return d2;
+}
+
+// popc(mask & lanes below this one)
+__device__ __forceinline__ int mf_rank_below(unsigned long long mask) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The NNDR decision of a column that passed against the optimistic d2 -- the decision, not a distance: the exact d2 has no
+// other consumer (docs/match_repair_once.md).  For nndr >= 0 the predicate !((float)d1 > nndr * (float)d2) is monotone
+// non-decreasing in d2, and the Hamming distance p over a row's first four dwords is <= the row's distance d.  So with
+// pmin = the minimum of p over the class's other rows (the exclusions of mf_repair_d2), min(d2, pmin) <= the exact second
+// best: a column that passes against it passes against the exact one, on one ds_read_b128 and four xor / popcount per row
+// and ONE conversion, multiply and compare for the class.  A column that does not pass is not rejected: it is
+// uncertified, and under a wave-uniform ballot the uncertified lanes run the exact loop and decide as before.  A negative
+// (or NaN) nndr keeps the exact path as a whole: the predicate is not monotone there.
+// Called under wave-uniform control flow with the lanes that repair in `active`; returns the decision of those lanes.
+template <int W>
+__device__ __forceinline__ bool mf_repair_accept(const uint32_t* fromD, int Kf, const uint32_t* __restrict__ q_row, int idx,
+                                                 uint32_t d1, uint32_t d2, float nndr, bool active) {
+  bool acc = false, exact = active;
+  if (nndr >= 0.f) {                             // a kernel argument: wave-uniform
+    if (active) {
+      uint32_t pmin = d2;
+      if ((idx & 27) != 27) {                    // (rows 27 and 31 of a tile: nothing to repair, d2 is exact)
+        uint32_t q[4];
+        load_raw<4>(q_row, q);
+        const int base = (idx & ~31) + (idx & 4);
+        // The exclusions as ONE instruction per row: bit j of `no` is set where row base + j is left out (rows >= Kf: bits
+        // Kf - base and up, at least 1 as idx < Kf; the best row; bit 27, register 15's row), and a row's popcount chain
+        // starts from its bit moved to 512 or above instead of from 0.  A row left out then counts 512 or more: no less
+        // than any distance of up to 512 bits, so the minimum with d2 is untouched (a second best that is absent, 0xFFFF,
+        // comes out at 512 or more instead: smaller, i.e. at worst uncertified, never wrongly certified).  `no` is kept
+        // rotated left by 9, and right by 8 per trip: row g + k sits at bit 9 + k.
+        const uint32_t ok = ((1u << min(Kf - base, 31)) - 1u) & ~(1u << (idx - base)) & ~(1u << 27);
+        uint32_t no = __builtin_amdgcn_alignbit(~ok, ~ok, 23);
+#pragma unroll 1
+        for (int g = 0; g < 32; g += 8) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            uint32_t x[4];
+            load_raw<4>(fromD + (size_t)(base + g + k) * W, x);
+            uint32_t p = no & (512u << k);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) p = bcnt_acc(x[c] ^ q[c], p);
+            pmin = min(pmin, p);
+          }
+          no = __builtin_amdgcn_alignbit(no, no, 8);
+        }
+      }
+      acc = !((float)d1 > nndr * (float)pmin);
+      exact = !acc;
+    }
+  }
+  if (__ballot(exact)) {                         // wave-uniform: no certified wavefront takes it
+    if (exact) acc = !((float)d1 > nndr * (float)mf_repair_d2<W>(fromD, Kf, q_row, idx, d2));
+  }
+  return acc;
 }
 
 // Body of the matching stage for ONE pair (the calling workgroup); `smem` is the workgroup's dynamic
@@ -939,26 +1014,83 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
         knn2_mfma<W, G, MF_PIPE>(fromD, Kf, dT, Kt, tl, lane, a1, a2, f);
         // a pass decides the columns of two tiles, one per lane half (mf_scan); `rejected` counts lanes, so it is a
         // wave-uniform sum of ballots, not a per-lane counter to be reduced
+        int t[NP];
+        bool on[NP], acc[NP], redo[NP];
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-          const int t = G == 1 ? tl[0] * 32 + lane : (tl[2 * p] + (lane >> 5) * NW) * 32 + (lane & 31);
-          const bool on = (G > 1 || lane < 32) && t < Kt;
+          t[p] = G == 1 ? tl[0] * 32 + lane : (tl[2 * p] + (lane >> 5) * NW) * 32 + (lane & 31);
+          on[p] = (G > 1 || lane < 32) && t[p] < Kt;
           // a2 is optimistic (>= the exact second-best distance, top2_update16): a column rejected against it is
-          // rejected; one that passes has its exact value made and is decided again.  (A negative nndr, which accepts
-          // only d1 = d2 = 0, turns the inequality round: such a column repairs whatever the first test says.)
-          bool acc = (Kf >= 2) && !((float)a1[p] > nndr * (float)a2[p]);
-          const bool redo = on && Kf >= 2 && (acc || nndr < 0.f);
-          if (__ballot(redo)) {                  // wave-uniform: no pass of an alias pair takes it
-            if (redo) {
-              a2[p] = mf_repair_d2<W>(fromD, Kf, dT + (size_t)t * W, f[p], a2[p]);
-              acc = !((float)a1[p] > nndr * (float)a2[p]);
+          // rejected; one that passes is decided again on its best row's class (mf_repair_accept).  (A negative nndr,
+          // which accepts only d1 = d2 = 0, turns the inequality round: such a column repairs whatever the first test
+          // says.)
+          acc[p] = (Kf >= 2) && !((float)a1[p] > nndr * (float)a2[p]);
+          redo[p] = on[p] && Kf >= 2 && (acc[p] || !(nndr >= 0.f));
+        }
+        if constexpr (NP == 1) {
+          if (__ballot(redo[0])) {               // wave-uniform: no pass of an alias pair takes it
+            const bool r = mf_repair_accept<W>(fromD, Kf, dT + (size_t)t[0] * W, f[0], a1[0], a2[0], nndr, redo[0]);
+            acc[0] = redo[0] ? r : acc[0];
+          }
+        } else {
+          // ONE repair per group: where the two passes' repairing columns fit one set of 64 lanes, those of pass 1 move
+          // into lanes that have none of pass 0 and the decisions come back to the lanes that own the columns (claims
+          // and `rejected` stay with the owner).  The hand-over is four lane permutations, each a bijection of the 64
+          // lanes issued with all of them active (docs/chain_lane_sums.md), and no LDS of its own:
+          //   slot: the lanes without a pass-0 repair in order (then the others), pushed by their rank;
+          //   tgt : a pass-1 lane of rank r pulls slot[r] (a lane without a pass-1 repair: what is left, in order);
+          //   the column travels to tgt packed in two words, the decision is pulled back from tgt.
+          // Otherwise (more than 64 columns, one pass with nothing to repair, nndr < 0) the passes go one after the other
+          // through the same statements.
+          static_assert(NP == 2, "a group has one or two decode passes");
+          const unsigned long long bal0 = __ballot(redo[0]), bal1 = __ballot(redo[1]);
+          const int n0 = __popcll(bal0), n1 = __popcll(bal1);
+          // (a pass with nothing to repair needs no hand-over: the trips below skip it at the price of a ballot)
+          const bool merged = nndr >= 0.f && n0 != 0 && n1 != 0 && n0 + n1 <= 64;      // wave-uniform
+          int tgt = 0;
+          uint32_t m0 = 0, m1 = 0;
+          bool mine = false;
+          if (merged) {
+            const int jf = mf_rank_below(~bal0), r1 = mf_rank_below(bal1);
+            const int dest = redo[0] ? 64 - n0 + lane - jf : jf;
+            const int slot = __builtin_amdgcn_ds_permute(dest << 2, lane);
+            tgt = __builtin_amdgcn_ds_bpermute((redo[1] ? r1 : n1 + lane - r1) << 2, slot);
+            m0 = (uint32_t)__builtin_amdgcn_ds_permute(tgt << 2, (int)((uint32_t)t[1] | ((uint32_t)f[1] << 16)));
+            m1 = (uint32_t)__builtin_amdgcn_ds_permute(tgt << 2, (int)(a1[1] | (a2[1] << 16)));
+            mine = !redo[0] && jf < n1;
+          }
+#pragma unroll 1
+          for (int it = 0; it < 2; ++it) {
+            bool act = it ? redo[1] : redo[0];
+            int wt = it ? t[1] : t[0], wf = it ? f[1] : f[0];
+            uint32_t w1 = it ? a1[1] : a1[0], w2 = it ? a2[1] : a2[0];
+            if (mine) {                          // (set in the merged form only)
+              act = true;
+              wt = (int)(m0 & 0xFFFFu); wf = (int)(m0 >> 16);
+              w1 = m1 & 0xFFFFu; w2 = m1 >> 16;
             }
+            if (__ballot(act)) {
+              const bool r = mf_repair_accept<W>(fromD, Kf, dT + (size_t)wt * W, wf, w1, w2, nndr, act);
+              if (merged) {
+                const bool back = __builtin_amdgcn_ds_bpermute(tgt << 2, (int)r) != 0;
+                acc[0] = redo[0] ? r : acc[0];
+                acc[1] = redo[1] ? back : acc[1];
+              } else if (it) {
+                acc[1] = redo[1] ? r : acc[1];
+              } else {
+                acc[0] = redo[0] ? r : acc[0];
+              }
+            }
+            if (merged) break;
           }
-          if (on && acc) {
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          if (on[p] && acc[p]) {
             atomicAdd(&cnt[f[p]], 1);
-            owner[f[p]] = t;
+            owner[f[p]] = t[p];
           }
-          rejected += __popcll(__ballot(on && !acc));
+          rejected += __popcll(__ballot(on[p] && !acc[p]));
         }
       };
       for (int t0 = wave; t0 < n_nt; t0 += NW * NTL) {

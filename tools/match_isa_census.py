@@ -13,17 +13,21 @@ The regions are found from the instruction stream, not from label numbers:
     a decode (v_ceil_f32) nor a claim (ds_add); inside it: in front of the loop (the "to" tiles loaded and spread, the
     origin tuple), the loop, what lies on a cycle through the loop (the ragged tile as a second pass), what follows it
     (blocks with MFMAs there = an unpipelined ragged tile; the rest = drain, decode, NNDR, claims);
-  * the repair of the second best (mf_repair_d2) is a region of its own behind the scan loop: a block there that branches
-    to itself and holds v_bcnt_u32_b32 is a repair loop (4 of a class's rows per trip, 4 trips), and its region is what
-    the topmost block dominates that dominates it and is neither a decode (v_ceil_f32) nor a claim (ds_add) -- one copy
-    per decode pass;
+  * the repair of the second best (mf_repair_accept, mf_repair_d2) is a region of its own behind the scan loop: a block
+    there that branches to itself and holds v_bcnt_u32_b32 is a repair loop (4 of a class's rows per trip, 4 trips), and
+    its region is what the topmost block dominates that dominates it and is neither a decode (v_ceil_f32) nor a claim
+    (ds_add).  A group has ONE copy: the hand-over of pass 1's columns to free lanes, the loop of the half-row certificate
+    (the repair loop with the fewest v_bcnt_u32_b32) and the exact path for uncertified lanes (the other loop and what
+    the topmost block dominates that dominates it and not the certificate's loop);
   * the two barriers in front of and behind the scans cut the rest: prologue + staging, scan set-up, the loop over a
     wavefront's groups, the hand-over of the rejected count, the list compaction and the header.
 Loop bodies other than the scan loop are counted once.  The model adds up what every wavefront of a pair issues; what only
 lane 0 of the workgroup runs behind the compaction (header, pass state, the result of a pair that has no estimate) and
 the paths taken by few pairs are listed and left out of it.  model_valu is a wavefront none of whose decode passes
 repairs (no lane accepts against the optimistic second best: every pass of a pair of unrelated frames);
-model_valu_repaired one whose every pass does (a lane's class: the repair loop four times).
+model_valu_repaired one whose every group repairs ONCE, both passes' columns merged into one set of lanes and all of them
+certified (the repair region less its exact path, the certificate's loop four times).  Assembly from before the certificate
+(one kind of repair loop, one copy per decode pass) is modelled as it was: every pass repairing, its loop four times.
   tools/match_isa_census.py [--asm FILE] [--json]
 --asm: read an assembly file made before (the parent commit's, say) instead of compiling."""
 import argparse, collections, json, os, re, subprocess, sys, tempfile
@@ -263,13 +267,36 @@ def census(fn):
     tail = total(ragged) + total(cyc) + (total([scan4]) if cyc and not ragged else collections.Counter())
     rows["ragged last tile%s" % (" (second pass over the loop body)" if cyc and not ragged else "")] = tail
     rows["drain, decode, NNDR, claims"] = total(post - ragged - repair)
-    rows["second best repaired (all decode passes; loop bodies once)"] = total(repair)
+    rows["second best decided again (hand-over, certificate, exact path; loop bodies once)"] = total(repair)
     rows["rejected count handed over"] = total(to_bar2 - {bar2}, [cut(bar2, True)])
     rows["list compaction (loop body once)"] = total(to_last - {bar2}, [cut(bar2, False)] if bar2 != bars[-1] else [])
     rows["behind it: lane 0's header and result, rare paths (not in the model)"] = total(rest, [cut(bar2, False)] if bar2 == bars[-1] else [])
     keys = list(rows)
     once = sum(rows[k]["valu"] for k in (keys[0], keys[1], keys[8], keys[9]))
-    rep = rows[keys[7]]["valu"] + 3 * total(repair_loops)["valu"]      # every pass repairing: 4 trips through its loop
+    bcnts = {lp: sum(op.startswith("v_bcnt_u32_b32") for op in by[lp].ins) for lp in repair_loops}
+    shapes = {lp: (bcnts[lp], by[lp].count()["lds"], by[lp].count()["valu"]) for lp in repair_loops}
+    if len(set(shapes.values())) > 1 and len(set(bcnts.values())) == 1:
+        # two kinds of repair loop are there, and the rule that tells them apart does not: no silent fall-back to the old model
+        sys.exit("repair loops of different shape with the same number of v_bcnt_u32_b32: cannot tell the certificate's loop")
+    cert = [lp for lp in repair_loops if bcnts[lp] == min(bcnts.values()) and len(set(bcnts.values())) > 1]
+    if cert:                       # one merged, certified repair: not the exact path, 4 trips through the certificate's loop
+        exact_path = set()
+        for lp in repair_loops:
+            if lp in cert:
+                continue
+            head = lp
+            while True:
+                ups = [d for d in dom[head] if d != head and dom[d] == dom[head] - {head}]
+                if not ups or ups[0] not in repair or any(c in dominated(ups[0]) for c in cert):
+                    break
+                head = ups[0]
+            exact_path |= dominated(head) & repair
+        rows = collections.OrderedDict(
+            (k2, v2) for k, v in rows.items()
+            for k2, v2 in ([(k, v), ("... of which the exact path of uncertified lanes", total(exact_path))] if k == keys[7] else [(k, v)]))
+        rep = total(repair - exact_path)["valu"] + 3 * total(cert)["valu"]
+    else:                          # before the certificate: every pass repairing, 4 trips through its loop
+        rep = rows[keys[7]]["valu"] + 3 * total(repair_loops)["valu"]
     per_group = rows[keys[2]]["valu"] + rows[keys[3]]["valu"] + rows[keys[6]]["valu"]
     loop, rag = rows[keys[4]]["valu"], rows[keys[5]]["valu"]
 
@@ -307,12 +334,12 @@ def main():
         print(json.dumps(r))
         return
     print("k_match_split<8, 4, 3>, per wavefront  (flags: %s)" % " ".join(FLAGS[1:]))
-    print("  %-66s %5s %5s %5s %5s %5s" % (("region",) + tuple(k.upper() for k in KINDS)))
+    print("  %-82s %5s %5s %5s %5s %5s" % (("region",) + tuple(k.upper() for k in KINDS)))
     for k, v in r["regions"].items():
-        print("  %-66s %5d %5d %5d %5d %5d" % ((k,) + tuple(v[x] for x in KINDS)))
-    print("  %-66s %5d %5d %5d %5d %5d" % (("whole kernel (static)",) + tuple(r["kernel_total"][x] for x in KINDS)))
+        print("  %-82s %5d %5d %5d %5d %5d" % ((k,) + tuple(v[x] for x in KINDS)))
+    print("  %-82s %5d %5d %5d %5d %5d" % (("whole kernel (static)",) + tuple(r["kernel_total"][x] for x in KINDS)))
     for k, v in r["model_valu"].items():
-        print("  modelled VALU per wavefront, K = %4d: %d  (every decode pass repairing: %d)"
+        print("  modelled VALU per wavefront, K = %4d: %d  (second best decided again: %d)"
               % (int(k), v, r["model_valu_repaired"][k]))
     for name in ("k_match_split<8,4,3>", "k_verify_fused<8,0,false>"):
         print("  %-28s VGPRs %s, scratch %s B, occupancy %s" % (name, r[name]["vgprs"], r[name]["scratch_bytes"], r[name]["occupancy"]))
