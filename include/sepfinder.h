@@ -86,6 +86,9 @@ extern "C" {
       sf_freak_get_pairs, sf_freak_build_pattern, sf_freak_default_pairs (FAST/FREAK and GFTT/FREAK, Vis/FeatureType 3 and
       5: 64-byte rows).  sf_set_feature_type still refuses 3 and 5; nothing existing changed, the version number,
       sizeof(sf_params) and SF_K_COUNT stay.                                                                           */
+/* 8, additions: sf_surf_params, sf_surf_defaults, sf_set_feature_type_surf, sf_get_surf_params, sf_detect_surf_device
+      (SURF, Vis/FeatureType 0: float32 rows of 64 or 128 dimensions on a handle with desc_type 1).  sf_set_feature_type
+      still refuses 0; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.            */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -348,7 +351,8 @@ int  sf_brief_get_pattern(sf_handle h, int8_t* tests, int32_t cap_bytes, int32_t
    after the detector is type 6's -- the same BRIEF table, the same border rule; a non-NULL orb is ignored.
    Any other feature_type or parameter, and 4 or 8 on a handle with desc_type 1, return SF_EINVAL -- 2 (ORB) included:
    it takes detector parameters and is selected by sf_set_feature_type_orb; 3 and 5 (FAST/FREAK, GFTT/FREAK) likewise
-   take parameters of their own and are selected by sf_set_feature_type_freak.                                       */
+   take parameters of their own and are selected by sf_set_feature_type_freak, and 0 (SURF) by
+   sf_set_feature_type_surf.                                                                                         */
 typedef struct sf_orb_params {
   int32_t edge_threshold; /* ORB/EdgeThreshold, 19; 1 .. 64                                                         */
   int32_t patch_size;     /* ORB/PatchSize, 31 (only value accepted)                                                */
@@ -524,6 +528,44 @@ int  sf_freak_get_pairs(sf_handle h, int32_t* selected, int32_t cap, int32_t* n)
    next() = (uint32)s) from the seed 0x46524B21.                                                                       */
 int  sf_freak_build_pattern(const sf_freak_params* p, float* table, int32_t* sizes);
 void sf_freak_default_pairs(int32_t* selected /* [512] */);
+/* SURF: rtabmap's Vis/FeatureType 0, cv::xfeatures2d::SURF of OpenCV 3.2 with rtabmap's SURF/ parameters [upstream
+   opencv_contrib, restated in tests/surf_ref.py; DESIGN.md section 3 item 17h lists what the restatement decides].  The
+   only type with float32 rows: 64 dimensions (256 bytes), or 128 (512 bytes) with extended = 1, for a handle created
+   with desc_type 1 and that desc_bytes -- the L2 matcher's rows.
+   Detector (sf_detect_surf_device; usable on any handle, it writes no descriptor): box-filter Hessian layers of size
+   (9 + 6 l) << o sampled every 1 << o pixels on the int32 integral image, l = 0 .. n_octave_layers + 1, o = 0 ..
+   n_octaves - 1 (a layer larger than the image is skipped); det = dxx dyy - 0.81 dxy^2; a sample of a middle layer is a
+   keypoint when its det exceeds hessian_threshold and all 26 neighbours, and the 3 x 3 solve for the sub-sample offset
+   gives no component beyond 1.  Keypoint: the interpolated position, size = cvRound(size + offset ds), angle -1,
+   response = det, octave = o, class_id = the sign of the trace.  Order: descending response, equal responses by layer
+   then sample; then rtabmap's limitKeypoints (max_features <= 0: no limit), the rule of sf_detect_fast_device.  An image
+   with more than 262144 maxima returns SF_ERANGE.  surf NULL = the handle's parameters.
+   Under type 0 sf_extract_keyframe_device is SURF::compute on the given keypoints: it reads x, y and size and writes
+   angle -- the dominant direction of the 109 Haar responses of side 2 cvRound(2 s), s = size 1.2 / 9, within radius 6 s
+   (270 with upright = 1) -- and drops a keypoint whose wavelet is larger than the image, whose samples all fall outside
+   it, or whose size is not in (0, 1e6); the row is the 4 x 4 x (4 | 8) sums of Gaussian-weighted gradients over the
+   (int)(21 s) window reduced to 21 x 21, normalised to unit length.  d_desc_out receives rows x dims float32 through
+   its uint8_t pointer.  3D points, the depth filter and the store slot are every other type's.
+   sf_get_features_and_descriptor and its _u8 form run detector, sub-pixel refinement when it is on, LK or block matching,
+   extraction.  NOT BUILT under type 0 and refused with SF_EINVAL: Vis/RoiRatios, a grid of cells (as under type 2), and
+   every batch form.                                                                                                  */
+typedef struct sf_surf_params {
+  float   hessian_threshold;   /* SURF/HessianThreshold, 500; >= 0 and finite  */
+  int32_t n_octaves;           /* SURF/Octaves, 4; 1 .. 8                      */
+  int32_t n_octave_layers;     /* SURF/OctaveLayers, 2; 1 .. 8                 */
+  int32_t upright;             /* SURF/Upright, 0; 0 or 1                      */
+  int32_t extended;            /* SURF/Extended, 0; 0 or 1: 128 dimensions     */
+} sf_surf_params;              /* 20 bytes */
+void sf_surf_defaults(sf_surf_params* p);
+/* Selects Vis/FeatureType 0 (surf NULL = defaults).  Out-of-range parameters, a handle with desc_type 0, and a
+   desc_bytes that is not 256 (extended 0) / 512 (extended 1) return SF_EINVAL and change nothing.  sf_get_feature_type
+   reports 0 afterwards.  On a handle with desc_type 1 every other type stays refused: there is no way back, and none is
+   needed.                                                                                                            */
+int  sf_set_feature_type_surf(sf_handle h, const sf_surf_params* surf);
+int  sf_get_surf_params(sf_handle h, sf_surf_params* out);
+int  sf_detect_surf_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                           int32_t max_features, const sf_surf_params* surf, sf_keypoint* d_kpts_out, int32_t cap,
+                           int32_t* n_out);
 /* The two steps rtabmap's Feature2D::generateKeypoints puts around every detector, whatever the feature type
    [upstream rtabmap / OpenCV 3.2, restated in tests/subpix_ref.py; DESIGN.md section 3 item 17d lists what the restatement
    decides].  The reference reaches that function at myRegistrationVis.cpp:282 and leaves both steps off (INTEGRATION.md

@@ -89,6 +89,15 @@ int  sf_debug_guided_points(sf_handle h, int32_t pair, unsigned long long* plane
 int  sf_debug_plan_workspace(const sf_params* p, int32_t kcap, int32_t desc_words, int32_t n_pairs,
                              int32_t in_overlapped_step, int32_t debug_corr, int64_t* out, int32_t n_out);
 
+/* The two Gaussian tables of SURF (Vis/FeatureType 0), handle-free and usable without a GPU; float64 arithmetic, every
+   weight rounded to float32 once.  ori_xy [109][2] int8 {x, y}: the lattice points with x^2 + y^2 < 36, x outer, y
+   inner; ori_w [109]: g13[x + 6] g13[y + 6], g13 = the normalised 13-tap Gaussian of sigma 2.5; desc_w [400]:
+   g20[i] g20[j] at 20 i + j, sigma 3.3.  Any output may be NULL.                                                  */
+void sf_surf_build_tables(float* ori_w, int8_t* ori_xy, float* desc_w);
+/* The ranges sf_set_feature_type_surf and sf_detect_surf_device hold sf_surf_params to, without a handle: SF_OK or
+   SF_EINVAL; NULL = the defaults.                                                                                 */
+int  sf_surf_check_params(const sf_surf_params* params);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,6 +292,25 @@ def freak_params(orientation_normalized=1, scale_normalized=1, pattern_scale=22.
 
 
 FREAK_SCALES, FREAK_ORIENTATIONS, FREAK_POINTS, FREAK_PAIRS, FREAK_ALL_PAIRS, FREAK_BYTES = 64, 256, 43, 512, 903, 64
+FEATURE_SURF = 0         # ... and of sf_set_feature_type_surf (a handle with desc_type 1)
+
+
+class SurfParams(C.Structure):
+    """sf_surf_params (include/sepfinder.h): rtabmap's SURF/ parameters (Vis/FeatureType 0)."""
+    _fields_ = [("hessian_threshold", C.c_float), ("n_octaves", C.c_int32), ("n_octave_layers", C.c_int32),
+                ("upright", C.c_int32), ("extended", C.c_int32)]
+
+
+def surf_params(hessian_threshold=500.0, n_octaves=4, n_octave_layers=2, upright=0, extended=0):
+    """SURF/HessianThreshold, SURF/Octaves, SURF/OctaveLayers, SURF/Upright, SURF/Extended: rtabmap's defaults (what
+    sf_surf_defaults fills)."""
+    p = SurfParams()
+    p.hessian_threshold, p.n_octaves, p.n_octave_layers, p.upright, p.extended = (hessian_threshold, n_octaves,
+                                                                                  n_octave_layers, upright, extended)
+    return p
+
+
+SURF_ORI_SAMPLES, SURF_PATCH = 109, 20
 
 
 SF_IMAGE_RGB8, SF_IMAGE_BGR8, SF_IMAGE_MONO8 = range(3)   # sf_image_format: the camera's images (cv_bridge encodings)

@@ -14,6 +14,7 @@
 // GFTT/ORB (Vis/FeatureType 8) replaces the integral image and the BRIEF tests by k_orb_blur / k_orb_angle /
 // k_orb_points below (cv::ORB::compute on the given keypoints); the 3D points and the commit are shared.
 // FREAK (Vis/FeatureType 3 and 5) keeps the integral image and replaces k_extract_points by k_freak_points (k_freak.hip).
+// SURF (Vis/FeatureType 0) does the same with k_surf_describe (k_surf.hip) and float32 rows.
 //
 // Kernels (one keyframe = a few hundred to a few thousand corners of one 752 x 480 .. 1280 x 720 image):
 //   k_integral_rows   one workgroup per image row: wavefront scans of 256-pixel segments, running carry
@@ -176,26 +177,6 @@ __device__ __forceinline__ bool orb_inside(const sf_keypoint& k, int w, int h, i
   return rx >= (float)e && rx < (float)(w - e) && ry >= (float)e && ry < (float)(h - e);
 }
 
-// cv::fastAtan2 (OpenCV 3.x): degrees, float
-__device__ __forceinline__ float orb_fast_atan2(float y, float x) {
-  constexpr float deg = (float)(180.0 / 3.14159265358979323846);
-  constexpr float p1 = 0.9997878412794807f * deg, p3 = -0.3258083974640975f * deg, p5 = 0.1555786518463281f * deg,
-                  p7 = -0.04432655554792128f * deg;
-  constexpr float eps = (float)2.220446049250313080847263336181640625e-16;   // (float)DBL_EPSILON
-  const float ax = fabsf(x), ay = fabsf(y);
-  float a;
-  if (ax >= ay) {
-    const float c = ay / (ax + eps), c2 = c * c;
-    a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-  } else {
-    const float c = ax / (ay + eps), c2 = c * c;
-    a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
-  }
-  if (x < 0) a = 180.f - a;
-  if (y < 0) a = 360.f - a;
-  return a;
-}
-
 // blur: W x H per image, B.s_stride bytes apart
 __global__ void __launch_bounds__(256)
 k_orb_blur(const uint8_t* __restrict__ img, int w, int h, int pitch, uint8_t* __restrict__ blur, OrbTaps T, ExtractBatch B) {
@@ -265,7 +246,7 @@ k_orb_angle(const uint8_t* __restrict__ img, int pitch, const uint8_t* __restric
     m10 += __shfl_xor(m10, off);
   }
   if (lane == 0) {
-    if (inside) k.angle = orb_fast_atan2((float)m01, (float)m10);
+    if (inside) k.angle = sf_fast_atan2((float)m01, (float)m10);
     kpts_out[i] = k;
   }
 }
@@ -439,6 +420,32 @@ static OrbUmax orb_umax() {
   return U;
 }
 
+// The integral images of n_img images (B->img_stride apart) into c->ex_integral, B->s_stride entries apart
+static int integral_images(sf_context* c, const uint8_t* d_left, int n_img, int width, int height, int pitch, ExtractBatch* B,
+                           int32_t** S_out) {
+  const size_t s_entries = (size_t)(width + 1) * (height + 1);
+  const int rc = sf_buf_reserve(c, c->ex_integral, s_entries * sizeof(int32_t) * n_img);
+  if (rc != SF_OK) return rc;
+  int32_t* S = (int32_t*)c->ex_integral.p;
+  B->s_stride = s_entries;
+  hipLaunchKernelGGL(k_integral_rows, dim3(height + 1, n_img), dim3(256), 0, c->stream, d_left, width, height, pitch, S, *B);
+  hipLaunchKernelGGL(k_integral_cols, dim3((width + 1 + 63) / 64, n_img), dim3(64), 0, c->stream, width, height, S, *B);
+  *S_out = S;
+  return SF_OK;
+}
+
+// One image's integral image for a detector that reads it (SURF, k_surf.hip); the extraction call behind builds its own
+int sf_launch_integral(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const int32_t** S_out) {
+  ExtractBatch B;
+  B.img_stride = 0; B.s_stride = 0; B.pyr_stride = 0; B.per_image = 0; B.d_n = nullptr;
+  int32_t* S = nullptr;
+  const int rc = integral_images(c, d_image, 1, width, height, pitch, &B, &S);
+  if (rc != SF_OK) return rc;
+  SF_HIP(c, hipGetLastError());
+  *S_out = S;
+  return SF_OK;
+}
+
 // Launch sequence on the handle's stream; the store slots from `slot` on (c->store: kcap >= n, w dwords) have been
 // reserved by the caller.  Image i at d_left + i * img_stride, its corners / right_x / status / optional copies at + i * n
 // entries, its store slot = slot + i.  d_n (device): the corner count of every image, `n` is then the per-image
@@ -456,6 +463,8 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
     return sf_fail(c, SF_EINVAL, "ORB on a pyramid: one keyframe per call unless the detector has left the batch's pyramids");
   if (orb && bytes != ORB_BYTES) return sf_fail(c, SF_EINVAL, "ORB rows are %d bytes, not %d", ORB_BYTES, bytes);
   if (kind.freak && (orb || bytes != FREAK_BYTES)) return sf_fail(c, SF_EINVAL, "FREAK rows are %d bytes, not %d", FREAK_BYTES, bytes);
+  if (kind.surf && (orb || kind.freak || bytes != (kind.surf->extended ? 512 : 256)))
+    return sf_fail(c, SF_EINVAL, "SURF rows are %d bytes, not %d", kind.surf->extended ? 512 : 256, bytes);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_xyz, rows_all * 12)) != SF_OK) return rc;
@@ -465,12 +474,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   SfOrbPyr P = sf_orb_single_level(width, height);
   int32_t* S = nullptr;
   if (!orb) {
-    const size_t s_entries = (size_t)(width + 1) * (height + 1);
-    if ((rc = sf_buf_reserve(c, c->ex_integral, s_entries * sizeof(int32_t) * n_img)) != SF_OK) return rc;
-    S = (int32_t*)c->ex_integral.p;
-    B.s_stride = s_entries;
-    hipLaunchKernelGGL(k_integral_rows, dim3(height + 1, n_img), dim3(256), 0, c->stream, d_left, width, height, pitch, S, B);
-    hipLaunchKernelGGL(k_integral_cols, dim3((width + 1 + 63) / 64, n_img), dim3(64), 0, c->stream, width, height, S, B);
+    if ((rc = integral_images(c, d_left, n_img, width, height, pitch, &B, &S)) != SF_OK) return rc;
   } else if (!pyr) {
     B.s_stride = (size_t)width * height;                 // the blurred level-0 images, back to back
     if ((rc = sf_buf_reserve(c, c->ex_blur, B.s_stride * n_img)) != SF_OK) return rc;
@@ -505,7 +509,12 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   const sf_keypoint* kp_commit = d_kpts;
   if (n > 0) {
     const long long threads = (long long)n * bytes;
-    if (kind.freak) {                                     // the keypoints with their angles, for the commit
+    if (kind.surf) {                                      // the keypoints with their angles, for the commit
+      if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
+      sf_launch_surf_describe(c, d_left, pitch, S, width, height, d_kpts, d_right_x, d_status, n, n_img, *kind.surf, ec,
+                              (sf_keypoint*)c->ex_kpts.p, (float*)c->ex_desc.p, (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);
+      kp_commit = (const sf_keypoint*)c->ex_kpts.p;
+    } else if (kind.freak) {                              // the keypoints with their angles, for the commit
       if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
       sf_launch_freak_points(c, d_left, pitch, S, width, height, d_kpts, d_right_x, d_status, n, n_img, *kind.freak, ec,
                              (sf_keypoint*)c->ex_kpts.p, (uint8_t*)c->ex_desc.p, (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);

@@ -59,3 +59,10 @@ void sf_launch_freak_points(sf_context* c, const uint8_t* d_left, int pitch, con
                             const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n, int n_img,
                             const SfFreakTables& T, const ExtractCam& cam, sf_keypoint* d_kpts_angle, uint8_t* desc_tmp,
                             float* xyz_tmp, uint8_t* keep, const ExtractBatch& B);
+
+// k_surf_describe (k_surf.hip) in the same place: SURF rows (float32, 64 or 128 per keypoint) into desc_tmp, every
+// keypoint (the kept ones with their SURF angle) into d_kpts_angle, 3D points and keep flags
+void sf_launch_surf_describe(sf_context* c, const uint8_t* d_left, int pitch, const int32_t* S, int width, int height,
+                             const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n, int n_img,
+                             const SfSurfTables& T, const ExtractCam& cam, sf_keypoint* d_kpts_angle, float* desc_tmp,
+                             float* xyz_tmp, uint8_t* keep, const ExtractBatch& B);

@@ -1,7 +1,7 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, the FREAK tables, Vis/FeatureType, NetVLAD, corner
-// detection (GFTT, FAST, ORB), the ROI, the grid of cells and the sub-pixel refinement around it, stereo correspondence,
+// detection (GFTT, FAST, ORB, SURF), the ROI, the grid of cells and the sub-pixel refinement around it, stereo correspondence,
 // keyframe extraction and the camera-image forms of these calls (kernels in k_extract.hip, k_gftt.hip, k_fast.hip,
-// k_orb_detect.hip, k_freak.hip, k_subpix.hip, k_grid.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in
+// k_orb_detect.hip, k_freak.hip, k_surf.hip, k_subpix.hip, k_grid.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in
 // sf_sort.hip).
 #include <cmath>
 #include <vector>
@@ -144,7 +144,8 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
   if (!c) return SF_EINVAL;
   int rc;
   switch (feature_type) {
-    case 6:
+    case 6:                      // (a handle with desc_type 1 starts here and may stay; none goes back from SURF)
+      if (c->feature_type != 6 && (rc = check_binary_rows(c, 6)) != SF_OK) return rc;
       break;
     case 4:
       if ((rc = check_binary_rows(c, 4)) != SF_OK) return rc;
@@ -158,12 +159,14 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
     }
     case 2:
       return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB) takes detector parameters: select it with sf_set_feature_type_orb");
+    case 0:
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType 0 (SURF) takes parameters of its own and a handle with desc_type 1: select it with sf_set_feature_type_surf");
     case 3:
     case 5:
       return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d (%s/FREAK) takes parameters of its own: select it with sf_set_feature_type_freak",
                      feature_type, feature_type == 3 ? "FAST" : "GFTT");
     default:
-      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (2 = ORB by sf_set_feature_type_orb, 3 = FAST/FREAK and 5 = GFTT/FREAK by sf_set_feature_type_freak, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (0 = SURF by sf_set_feature_type_surf, 2 = ORB by sf_set_feature_type_orb, 3 = FAST/FREAK and 5 = GFTT/FREAK by sf_set_feature_type_freak, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
                      feature_type);
   }
   c->feature_type = feature_type;
@@ -362,9 +365,88 @@ static int freak_ensure(sf_context* c) {
   return SF_OK;
 }
 
+// ---- SURF (Vis/FeatureType 0; kernels and table builder in k_surf.hip) -------------------------------------------------
+static int surf_validate(sf_context* c, const sf_surf_params& p) {
+  if (!(p.hessian_threshold >= 0.0f) || !std::isfinite(p.hessian_threshold))
+    return sf_fail(c, SF_EINVAL, "SURF hessian_threshold %g: finite and >= 0", (double)p.hessian_threshold);
+  if (p.n_octaves < 1 || p.n_octaves > SURF_MAX_OCTAVES) return sf_fail(c, SF_EINVAL, "SURF n_octaves %d outside 1 .. %d", p.n_octaves, SURF_MAX_OCTAVES);
+  if (p.n_octave_layers < 1 || p.n_octave_layers > SURF_MAX_LAYERS)
+    return sf_fail(c, SF_EINVAL, "SURF n_octave_layers %d outside 1 .. %d", p.n_octave_layers, SURF_MAX_LAYERS);
+  if ((p.upright != 0 && p.upright != 1) || (p.extended != 0 && p.extended != 1))
+    return sf_fail(c, SF_EINVAL, "SURF upright %d, extended %d: each is 0 or 1", p.upright, p.extended);
+  return SF_OK;
+}
+
+// the same ranges without a handle (sf_experimental.h; NULL = the defaults)
+extern "C" int sf_surf_check_params(const sf_surf_params* params) {
+  return surf_validate(nullptr, arg_or_defaults(params, sf_surf_defaults));
+}
+
+extern "C" int sf_set_feature_type_surf(sf_handle c, const sf_surf_params* surf) {
+  if (!c) return SF_EINVAL;
+  if (c->params.desc_type != 1)
+    return sf_fail(c, SF_EINVAL, "SURF writes float32 descriptors: a handle with desc_type %d cannot store them (create it with desc_type 1 and desc_bytes 256, or 512 for extended rows)",
+                   c->params.desc_type);
+  const sf_surf_params p = arg_or_defaults(surf, sf_surf_defaults);
+  int rc = surf_validate(c, p);
+  if (rc != SF_OK) return rc;
+  const int bytes = p.extended ? 512 : 256;
+  if (c->params.desc_bytes != bytes)
+    return sf_fail(c, SF_EINVAL, "SURF rows with extended %d are %d bytes: the handle was created with desc_bytes %d", p.extended, bytes,
+                   c->params.desc_bytes);
+  c->surf = p;
+  c->feature_type = 0;
+  return SF_OK;
+}
+
+extern "C" int sf_get_surf_params(sf_handle c, sf_surf_params* out) {
+  if (!c || !out) return SF_EINVAL;
+  *out = c->surf;
+  return SF_OK;
+}
+
+extern "C" int sf_detect_surf_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                     int32_t max_features, const sf_surf_params* surf, sf_keypoint* d_kpts_out, int32_t cap,
+                                     int32_t* n_out) {
+  if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
+  *n_out = 0;
+  int rc;
+  if ((rc = check_image(c, d_image, width, height, pitch, 3, "image")) != SF_OK) return rc;
+  const sf_surf_params prm = surf ? *surf : c->surf;
+  if ((rc = surf_validate(c, prm)) != SF_OK) return rc;
+  if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
+  if ((long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return sf_fail(c, SF_ERANGE, "image too large for a 32-bit integral image");
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_detect_surf(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
+}
+
+// The two Gaussian tables on the device, uploaded once: they depend on no parameter
+static int surf_ensure(sf_context* c) {
+  c->surf_dev.upright = c->surf.upright;
+  c->surf_dev.extended = c->surf.extended;
+  if (c->surf_tables_ok) return SF_OK;
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->surf_tables, SURF_TABLE_BYTES)) != SF_OK) return rc;
+  alignas(16) uint8_t host[SURF_TABLE_BYTES] = {};
+  sf_surf_build_tables((float*)(host + SURF_TABLE_ORI_W), (int8_t*)(host + SURF_TABLE_ORI_XY), (float*)(host + SURF_TABLE_DESC_W));
+  SF_HIP(c, hipMemcpyAsync(c->surf_tables.p, host, SURF_TABLE_BYTES, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));   // (the host copy goes away with this call)
+  const uint8_t* d = (const uint8_t*)c->surf_tables.p;
+  c->surf_dev.ori_w = (const float*)(d + SURF_TABLE_ORI_W);
+  c->surf_dev.ori_xy = (const int8_t*)(d + SURF_TABLE_ORI_XY);
+  c->surf_dev.desc_w = (const float*)(d + SURF_TABLE_DESC_W);
+  c->surf_tables_ok = true;
+  return SF_OK;
+}
+
 // The descriptor of the handle's feature type (ExtractKind: sf_internal.hpp)
 static int extract_kind(sf_context* c, ExtractKind* k) {
   int rc;
+  if (c->feature_type == 0) {                              // (selected on a handle with desc_type 1 and these row bytes only)
+    if ((rc = surf_ensure(c)) != SF_OK) return rc;
+    *k = {c->surf.extended ? 512 : 256, nullptr, nullptr, nullptr, 0, nullptr, &c->surf_dev};
+    return SF_OK;
+  }
   if (c->feature_type == 3 || c->feature_type == 5) {
     if ((rc = check_binary_rows(c, c->feature_type)) != SF_OK) return rc;
     if ((rc = freak_ensure(c)) != SF_OK) return rc;
@@ -554,6 +636,8 @@ static int front_plan(sf_context* c, int width, int height, FrontPlan* fp) {
   const int rc = sf_compute_roi(width, height, f.roi_ratios, roi);
   if (c->feature_type == 2 && (f.roi_ratios[0] != 0.f || f.roi_ratios[1] != 0.f || f.roi_ratios[2] != 0.f || f.roi_ratios[3] != 0.f))
     return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 2 (ORB) is not built: the batch form reuses the detector's pyramid for the descriptors; set the ratios to 0 or choose feature type 3, 4, 5, 6 or 8");
+  if (c->feature_type == 0 && (f.roi_ratios[0] != 0.f || f.roi_ratios[1] != 0.f || f.roi_ratios[2] != 0.f || f.roi_ratios[3] != 0.f))
+    return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 0 (SURF) is not built; set the ratios to 0");
   if (rc != SF_OK)
     return sf_fail(c, SF_EINVAL, "Vis/RoiRatios %g %g %g %g leave a ROI of %d x %d in a %d x %d image: both sides must be >= 3",
                    (double)f.roi_ratios[0], (double)f.roi_ratios[1], (double)f.roi_ratios[2], (double)f.roi_ratios[3], roi[2], roi[3], width, height);
@@ -616,6 +700,9 @@ static int grid_plan(sf_context* c, int width, int height, int max_features, Fro
   if (g.grid_rows == 1 && g.grid_cols == 1) return SF_OK;
   if (c->feature_type == 2)
     return sf_fail(c, SF_EINVAL, "Vis/GridRows x Vis/GridCols %d x %d under Vis/FeatureType 2 (ORB) is not built: every cell would need a pyramid of its own; set the grid to 1 x 1 or choose feature type 3, 4, 5, 6 or 8",
+                   g.grid_rows, g.grid_cols);
+  if (c->feature_type == 0)
+    return sf_fail(c, SF_EINVAL, "Vis/GridRows x Vis/GridCols %d x %d under Vis/FeatureType 0 (SURF) is not built; set the grid to 1 x 1",
                    g.grid_rows, g.grid_cols);
   int32_t o[6];
   const int rc = sf_compute_grid(width, height, c->front.roi_ratios, &g, max_features, o);
@@ -831,6 +918,7 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
     case 3:
     case 4: rc = sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
     case 2: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
+    case 0: rc = sf_detect_surf_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;   // (no ROI: front_plan)
     default:
       rc = sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
   }
@@ -908,6 +996,8 @@ static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframe
   if (c->feature_type != 2 && orb_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the ORB batch calls need type 2 (sf_set_feature_type_orb); use sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device",
                    c->feature_type);
+  if (c->feature_type == 0)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 0 (SURF): the batch forms are not built; use sf_get_features_and_descriptor or sf_extract_keyframe_device per keyframe");
   if (n_keyframes == 0) return SF_OK;
   int rc = check_image(c, images, width, height, pitch, 3, "stereo pairs");
   if (rc != SF_OK) return rc;

@@ -13,6 +13,26 @@ __device__ __forceinline__ int reflect101(int p, int len) {
   return p;
 }
 
+// cv::fastAtan2 (OpenCV 3.x): degrees, float (ORB's centroid angle in k_extract.hip, SURF's orientation in k_surf.hip)
+__device__ __forceinline__ float sf_fast_atan2(float y, float x) {
+  constexpr float deg = (float)(180.0 / 3.14159265358979323846);
+  constexpr float p1 = 0.9997878412794807f * deg, p3 = -0.3258083974640975f * deg, p5 = 0.1555786518463281f * deg,
+                  p7 = -0.04432655554792128f * deg;
+  constexpr float eps = (float)2.220446049250313080847263336181640625e-16;   // (float)DBL_EPSILON
+  const float ax = fabsf(x), ay = fabsf(y);
+  float a;
+  if (ax >= ay) {
+    const float c = ay / (ax + eps), c2 = c * c;
+    a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+  } else {
+    const float c = ax / (ay + eps), c2 = c * c;
+    a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+  }
+  if (x < 0) a = 180.f - a;
+  if (y < 0) a = 360.f - a;
+  return a;
+}
+
 // Byte offset of image z of a detector launch (SfCells: sf_internal.hpp): z * img_stride, or with cells the cell's first
 // pixel inside its image.  Uniform per workgroup: scalar arithmetic.
 __device__ __forceinline__ size_t sf_cell_base(unsigned z, size_t img_stride, const SfCells& g) {

@@ -208,6 +208,18 @@ constexpr int FREAK_SCALES = 64, FREAK_ORIENTATIONS = 256, FREAK_POINTS = 43, FR
 constexpr size_t FREAK_PATTERN_FLOATS = (size_t)FREAK_SCALES * FREAK_ORIENTATIONS * FREAK_POINTS * 3;
 constexpr size_t FREAK_TABLE_PAIRS = 0, FREAK_TABLE_ORIENT = 1024, FREAK_TABLE_SIZES = 1792, FREAK_TABLE_BYTES = 2048;
 
+// SURF rows (type 0): what k_surf_describe reads beside the integral image -- the two Gaussian tables of
+// sf_surf_build_tables in one device buffer, and the two flags of sf_surf_params that shape the rows
+struct SfSurfTables {
+  const float* ori_w;          // [109] weights of the orientation samples
+  const int8_t* ori_xy;        // [109] {x, y}
+  const float* desc_w;         // [400] weights of the 20 x 20 gradient samples
+  int upright, extended;
+};
+constexpr int SURF_ORI_SAMPLES = 109, SURF_PATCH = 20, SURF_MAX_OCTAVES = 8, SURF_MAX_LAYERS = 8;
+constexpr unsigned SURF_MAX_CANDIDATES = 1u << 18;   // maxima per image; more is SF_ERANGE, never a truncated list
+constexpr size_t SURF_TABLE_ORI_W = 0, SURF_TABLE_DESC_W = 512, SURF_TABLE_ORI_XY = 2112, SURF_TABLE_BYTES = 2368;
+
 struct sf_context {
   sf_params params;
   DeviceParams dparams;
@@ -274,6 +286,13 @@ struct sf_context {
   Buf freak_pattern, freak_tables;
   alignas(16) uint8_t freak_tables_host[FREAK_TABLE_BYTES] = {};   // the host copy of freak_tables
   SfFreakTables freak_dev = {};                // the kernel's view of the two buffers and the parameters
+  // 0 = SURF (sf_set_feature_type_surf; k_surf.hip), on a handle with desc_type 1 only: float32 rows of 64 or 128
+  // dimensions.  surf_planes: the det and trace planes of every layer; surf_keys: the maxima's sort keys, unsorted then
+  // sorted, and the counter; surf_tables: the Gaussian tables (uploaded once, they depend on no parameter)
+  sf_surf_params surf = {500.0f, 4, 2, 0, 0};
+  bool surf_tables_ok = false;
+  Buf surf_planes, surf_keys, surf_tables;
+  SfSurfTables surf_dev = {};
   // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
   // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
   // the image at hand; orb_work: the detector's candidate lists
@@ -690,7 +709,13 @@ struct ExtractKind {
   const sf_orb_detector_params* pyr;
   size_t pyr_stride;
   const SfFreakTables* freak = nullptr;   // not null: FREAK rows (bytes 64; d_tests, orb and pyr unused)
+  const SfSurfTables* surf = nullptr;     // not null: SURF rows (bytes 256 or 512, float32; the rest unused)
 };
+// the integral image of one image into c->ex_integral (k_extract.hip): (height + 1) x (width + 1) int32
+int sf_launch_integral(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const int32_t** S_out);
+// the fast-Hessian detector of SURF + limitKeypoints (k_surf.hip); prm validated by the caller
+int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
+                          const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
 // host halves of the FREAK tables (k_freak.hip): the orientation pairs' weights from scale 0 / orientation 0 of a pattern,
 // and the device layout of the selected pairs
 void sf_freak_orientation_table(const float* pattern, int32_t* orient /* [45][4] */);

@@ -109,6 +109,12 @@ def load():
         "sf_freak_get_pairs": (C.c_int, [vp, vp, i32, P(i32)]),
         "sf_freak_build_pattern": (C.c_int, [P(_abi.FreakParams), vp, vp]),
         "sf_freak_default_pairs": (None, [vp]),
+        "sf_surf_defaults": (None, [P(_abi.SurfParams)]),
+        "sf_set_feature_type_surf": (C.c_int, [vp, P(_abi.SurfParams)]),
+        "sf_get_surf_params": (C.c_int, [vp, P(_abi.SurfParams)]),
+        "sf_detect_surf_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.SurfParams), vp, i32, P(i32)]),
+        "sf_surf_build_tables": (None, [vp, vp, vp]),
+        "sf_surf_check_params": (C.c_int, [P(_abi.SurfParams)]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
         "sf_stereo_flow_defaults": (None, [P(_abi.StereoFlowParams)]),
         "sf_detector_defaults": (None, [P(_abi.DetectorParams)]),
@@ -226,6 +232,8 @@ EXPORTED = [
     "sf_grid_defaults", "sf_grid_set_params", "sf_grid_get_params", "sf_compute_grid",
     "sf_freak_defaults", "sf_set_feature_type_freak", "sf_get_freak_params", "sf_freak_set_pairs", "sf_freak_get_pairs",
     "sf_freak_build_pattern", "sf_freak_default_pairs",
+    "sf_surf_defaults", "sf_set_feature_type_surf", "sf_get_surf_params", "sf_detect_surf_device", "sf_surf_build_tables",
+    "sf_surf_check_params",
 ]
 
 
@@ -247,6 +255,16 @@ def freak_default_pairs():
     sel = np.zeros(_abi.FREAK_PAIRS, np.int32)
     load().sf_freak_default_pairs(C.c_void_p(sel.ctypes.data))
     return sel
+
+
+def surf_build_tables():
+    """sf_surf_build_tables (no GPU, no handle): the orientation samples' offsets int8 [109, 2] = (x, y) and weights float32
+    [109], and the float32 [400] weights of the 20 x 20 descriptor gradients."""
+    ori_w = np.zeros(_abi.SURF_ORI_SAMPLES, np.float32)
+    ori_xy = np.zeros((_abi.SURF_ORI_SAMPLES, 2), np.int8)
+    desc_w = np.zeros(_abi.SURF_PATCH * _abi.SURF_PATCH, np.float32)
+    load().sf_surf_build_tables(C.c_void_p(ori_w.ctypes.data), C.c_void_p(ori_xy.ctypes.data), C.c_void_p(desc_w.ctypes.data))
+    return ori_xy, ori_w, desc_w
 
 
 def _ptr(a):
@@ -490,8 +508,29 @@ class SeparatorFinder:
         self._check(self._L.sf_freak_get_pairs(self._h, C.c_void_p(buf.ctypes.data), buf.size, C.byref(n)))
         return buf[:n.value].copy()
 
+    def set_feature_type_surf(self, surf=None):
+        """Vis/FeatureType 0 (SURF) with surf (_abi.SurfParams; None = rtabmap's SURF/ defaults) on a handle created with
+        desc_type 1 and desc_bytes 256 (512 with extended = 1): float32 rows of 64 (128) dimensions."""
+        self._check(self._L.sf_set_feature_type_surf(self._h, C.byref(surf) if surf is not None else None))
+
+    def get_surf_params(self):
+        p = _abi.SurfParams()
+        self._check(self._L.sf_get_surf_params(self._h, C.byref(p)))
+        return p
+
+    def detect_surf(self, d_image, width, height, pitch, max_features, d_kpts_out, cap, surf=None):
+        """The fast-Hessian detector of SURF + rtabmap's limitKeypoints on the device (surf None = the handle's; any
+        handle); returns the number of keypoints of the result (<= cap are written)."""
+        n = C.c_int32()
+        self._check(self._L.sf_detect_surf_device(self._h, C.c_void_p(d_image), width, height, pitch, max_features,
+                                                  C.byref(surf) if surf is not None else None, C.c_void_p(d_kpts_out), cap,
+                                                  C.byref(n)))
+        return n.value
+
     def descriptor_bytes(self):
         """Row bytes the extraction calls write with the handle's feature type."""
+        if self.get_feature_type()[0] == _abi.FEATURE_SURF:
+            return 512 if self.get_surf_params().extended else 256
         if self.get_feature_type()[0] in (_abi.FEATURE_FAST_FREAK, _abi.FEATURE_GFTT_FREAK):
             return _abi.FREAK_BYTES
         return 32 if self.get_feature_type()[0] in (_abi.FEATURE_GFTT_ORB, _abi.FEATURE_ORB) else self.brief_get_pattern().shape[0] // 8
