@@ -89,6 +89,9 @@ extern "C" {
 /* 8, additions: sf_surf_params, sf_surf_defaults, sf_set_feature_type_surf, sf_get_surf_params, sf_detect_surf_device
       (SURF, Vis/FeatureType 0: float32 rows of 64 or 128 dimensions on a handle with desc_type 1).  sf_set_feature_type
       still refuses 0; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.            */
+/* 8, additions: sf_get_features_and_descriptor_surf_batch_device, sf_add_keyframes_surf_u8_batch_device,
+      sf_surf_batch_status (the batch forms of Vis/FeatureType 0).  The four existing batch calls still refuse a type-0
+      handle, now naming these; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.  */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -547,8 +550,9 @@ void sf_freak_default_pairs(int32_t* selected /* [512] */);
    (int)(21 s) window reduced to 21 x 21, normalised to unit length.  d_desc_out receives rows x dims float32 through
    its uint8_t pointer.  3D points, the depth filter and the store slot are every other type's.
    sf_get_features_and_descriptor and its _u8 form run detector, sub-pixel refinement when it is on, LK or block matching,
-   extraction.  NOT BUILT under type 0 and refused with SF_EINVAL: Vis/RoiRatios, a grid of cells (as under type 2), and
-   every batch form.                                                                                                  */
+   extraction.  NOT BUILT under type 0 and refused with SF_EINVAL: Vis/RoiRatios and a grid of cells (as under type 2).
+   The batch forms are sf_get_features_and_descriptor_surf_batch_device and sf_add_keyframes_surf_u8_batch_device; the
+   generic batch calls and the _orb_ ones refuse a type-0 handle with SF_EINVAL and name them.                        */
 typedef struct sf_surf_params {
   float   hessian_threshold;   /* SURF/HessianThreshold, 500; >= 0 and finite  */
   int32_t n_octaves;           /* SURF/Octaves, 4; 1 .. 8                      */
@@ -749,8 +753,9 @@ int  sf_get_features_and_descriptor(sf_handle h, const uint8_t* left, const uint
    device outputs, each sized for n_keyframes x det->max_features rows (keyframe i at row i * max_features; any may be
    NULL): d_rows_out [n_keyframes] features kept, d_desc_out, d_xyz_out, d_kpts_out as in the single call.  Images up to
    about 1.2 Mpixel (the corner selection keeps its bitmap in LDS); no such limit under feature type 4.
-   Feature type 2 has a batch call of its own, sf_get_features_and_descriptor_orb_batch_device: on a type-2 handle this
-   one returns SF_EINVAL, says so and changes nothing.                                                               */
+   Feature types 2 and 0 have batch calls of their own, sf_get_features_and_descriptor_orb_batch_device and
+   sf_get_features_and_descriptor_surf_batch_device: on a handle of either type this one returns SF_EINVAL, says so and
+   changes nothing.                                                                                                  */
 int  sf_get_features_and_descriptor_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
                                                  int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                                  size_t image_stride, const sf_stereo_camera* cam,
@@ -773,6 +778,35 @@ int  sf_get_features_and_descriptor_orb_batch_device(sf_handle h, const uint8_t*
                                                      const sf_detector_params* det, const sf_stereo_flow_params* flow,
                                                      int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                      float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* The same under Vis/FeatureType 0 (sf_set_feature_type_surf; the handle's SURF parameters): arguments and outputs of
+   sf_get_features_and_descriptor_batch_device, and per keyframe the bytes of sf_get_features_and_descriptor under type 0
+   -- the row count, float32 rows of 256 or 512 bytes (d_desc_out receives them through its uint8_t pointer, keyframe i
+   at row i * max_features), 3D points with their NaNs, keypoints with all seven fields, the store slot.  One launch
+   sequence with no host wait: the integral images of all left images are built once (the extraction reads the
+   detector's); the fast-Hessian layers, the maxima, the per-image decisions the single call takes on the host (the cut
+   at max_features and the order of equal responses that goes with it), a segmented sort and the keypoints run over
+   chunks of images whose planes and keys fit a fixed workspace of 256 MB (one image always runs; the chunks are
+   consecutive launches on the handle's stream); sub-pixel refinement, LK or block matching and the extraction follow as
+   in the single call.
+   An image's key capacity is min(262144, B), B a bound on the maxima an image of this size can have (two maxima of a
+   layer are never 8-adjacent: DESIGN.md section 3 item 17h); up to about a megapixel B is the smaller and nothing can
+   overflow.  Beyond that, a keyframe with more maxima than the capacity is NOT truncated and does not fail the call,
+   which cannot wait for the count: it gets 0 rows and an empty store slot, and sf_surf_batch_status reports it.
+   Refusals, all before the first launch and without a change to the store, the NN database or the handle: what
+   sf_get_features_and_descriptor_batch_device refuses; Vis/RoiRatios and a grid (SF_EINVAL); n_keyframes > 65535
+   (SF_ERANGE: the image is a grid dimension); what sf_detect_surf_device refuses (the parameter ranges, more than 2^31
+   plane samples, an image too large for a 32-bit integral image).  On a handle of any other feature type: SF_EINVAL, the
+   message names the call to use.  n_keyframes = 0: SF_OK with *first_slot_out = sf_store_size.                      */
+int  sf_get_features_and_descriptor_surf_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
+                                                      int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                                      size_t image_stride, const sf_stereo_camera* cam,
+                                                      const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                      int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                      float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* Waits for the handle's stream and writes how many keyframes of the most recent SURF batch call (either form) had more
+   maxima than their key capacity and therefore hold no rows.  SF_OK when none did (and on a handle that has run no such
+   call); SF_ERANGE when some did, with a message that says to raise hessian_threshold.  n_overflowed_out may be NULL.  */
+int  sf_surf_batch_status(sf_handle h, int32_t* n_overflowed_out);
 
 /* ---- keyframes from the camera's own images (first step) ------------------------- */
 /* The reference keeps every image as cv_bridge's "rgb8" (data_handler.py:114-141).  For a keyframe it converts both stereo
@@ -853,6 +887,18 @@ int  sf_add_keyframes_orb_u8_batch_device(sf_handle h, const uint8_t* d_left, co
                                           const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                           int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                           float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* The same under Vis/FeatureType 0: sf_add_keyframes_u8_batch_device with the feature stages of
+   sf_get_features_and_descriptor_surf_batch_device -- the same formats and gray rule, the same network call, n store slots
+   and n NN rows under one index, all or nothing.  Slot first_slot + i holds the bytes of sf_get_features_and_descriptor_u8
+   on pair i; a keyframe whose maxima exceed the key capacity keeps its slot and its NN row, holds no rows, and is counted
+   by sf_surf_batch_status.  Refuses what either of the two refuses; on a handle of another feature type: SF_EINVAL,
+   nothing changes.                                                                                                    */
+int  sf_add_keyframes_surf_u8_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+                                           int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                           size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
+                                           const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                           int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                           float* d_xyz_out, sf_keypoint* d_kpts_out);
 
 /* ---- geometric verification (stereoCamGeometricTools.cpp:122-178) ---------------------------- */
 /* One estimate_transformation service call on host buffers.                                  */

@@ -97,6 +97,22 @@ void sf_surf_build_tables(float* ori_w, int8_t* ori_xy, float* desc_w);
 /* The ranges sf_set_feature_type_surf and sf_detect_surf_device hold sf_surf_params to, without a handle: SF_OK or
    SF_EINVAL; NULL = the defaults.                                                                                 */
 int  sf_surf_check_params(const sf_surf_params* params);
+/* Small shapes for the tests of SURF's batch form; a fresh handle behaves as if neither had been called.  candidate_cap
+   (0 = the default, at most 262144) takes the place of the 262144 maxima an image may have, in sf_detect_surf_device
+   and the single extraction calls (more: SF_ERANGE) and in the batch forms (more: the keyframe holds no rows, see
+   sf_surf_batch_status); batch_chunk (0 = what the 256 MB workspace allows, at most 65535) is the number of images the
+   batch detector runs per chunk.  Out of range: SF_EINVAL, nothing changes.                                       */
+int  sf_debug_surf_limits(sf_handle h, int32_t candidate_cap, int32_t batch_chunk);
+/* The host arithmetic of the SURF batch forms for n_keyframes images of width x height, without a GPU or a handle (surf
+   NULL = the defaults): *cap_img_out = min(262144, B), B = the sum over octaves o and middle layers l = 1 ..
+   n_octave_layers of ceil(r / 2) ceil(c / 2) with r = max((height >> o) - 2 m, 0), c = max((width >> o) - 2 m, 0) and
+   m = (((9 + 6 (l + 1)) << o) / 2 >> o) + 1; *chunk_out = the images per chunk, min(n_keyframes, 65535, 2^31 - 1 keys,
+   the 256 MB workspace / bytes per image), at least 1; bytes per image = 8 per plane sample + 16 per key (at least one
+   key) + 16; *workspace_bytes_out = chunk x bytes per image.  Any output may be NULL.  SF_EINVAL: parameters out of
+   range, an image below 3 x 3, n_keyframes outside 1 .. 65535; SF_ERANGE: what sf_detect_surf_device refuses of an
+   image's size.                                                                                                   */
+int  sf_surf_batch_plan(int32_t width, int32_t height, const sf_surf_params* surf, int32_t n_keyframes,
+                        int32_t* cap_img_out, int32_t* chunk_out, int64_t* workspace_bytes_out);
 
 #ifdef __cplusplus
 }

@@ -446,6 +446,21 @@ int sf_launch_integral(sf_context* c, const uint8_t* d_image, int width, int hei
   return SF_OK;
 }
 
+// The same for the n_img images of a batch, *s_stride entries apart: the detector reads them, and so does the extraction
+// behind it (ExtractKind::integral_ready)
+int sf_launch_integral_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                             int pitch, const int32_t** S_out, size_t* s_stride) {
+  ExtractBatch B;
+  B.img_stride = img_stride; B.s_stride = 0; B.pyr_stride = 0; B.per_image = 0; B.d_n = nullptr;
+  int32_t* S = nullptr;
+  const int rc = integral_images(c, d_images, n_img, width, height, pitch, &B, &S);
+  if (rc != SF_OK) return rc;
+  SF_HIP(c, hipGetLastError());
+  *S_out = S;
+  *s_stride = B.s_stride;
+  return SF_OK;
+}
+
 // Launch sequence on the handle's stream; the store slots from `slot` on (c->store: kcap >= n, w dwords) have been
 // reserved by the caller.  Image i at d_left + i * img_stride, its corners / right_x / status / optional copies at + i * n
 // entries, its store slot = slot + i.  d_n (device): the corner count of every image, `n` is then the per-image
@@ -473,7 +488,12 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   B.img_stride = img_stride; B.pyr_stride = 0; B.per_image = n; B.d_n = d_n;
   SfOrbPyr P = sf_orb_single_level(width, height);
   int32_t* S = nullptr;
-  if (!orb) {
+  if (kind.integral_ready) {                             // the detector's, of these images: nothing has written the buffer since
+    B.s_stride = (size_t)(width + 1) * (height + 1);
+    if (orb || c->ex_integral.bytes < B.s_stride * sizeof(int32_t) * n_img)
+      return sf_fail(c, SF_EINVAL, "the batch's integral images are not the detector's");
+    S = (int32_t*)c->ex_integral.p;
+  } else if (!orb) {
     if ((rc = integral_images(c, d_left, n_img, width, height, pitch, &B, &S)) != SF_OK) return rc;
   } else if (!pyr) {
     B.s_stride = (size_t)width * height;                 // the blurred level-0 images, back to back

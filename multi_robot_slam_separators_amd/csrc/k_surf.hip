@@ -18,7 +18,12 @@
 //   k_surf_rekey     only when limitKeypoints will cut the list: flips the position bits, so that equal responses sort by
 //                    DESCENDING position -- the rule FAST and ORB share (tests/orb2_ref.py limit_keypoints)
 //   sf_sort_keys     (sf_sort.hip) descending, 64 bits
+//   k_surf_segments  the batch form's stand-in for the host's decisions (sf_launch_detect_surf_batch; blockIdx.y = image):
+//                    reads the image's count; more than the key capacity: the image is marked as overflowed (the handle's
+//                    counter) and gets an empty segment; else the rekey above where the count exceeds max_features, and
+//                    the image's segment of the key array for sf_sort_keys_segmented_desc
 //   k_surf_emit      the first min(count, max_features) keys -> keypoints, the interpolation done again from the planes
+//                    (k_surf_emit_batch: blockIdx.y = image, count and rekey flag read on the device, the count written)
 //   k_surf_describe  one workgroup of 512 per keypoint.  Wavefront 0: the 109 orientation samples over its lanes in two
 //                    rounds (Haar responses, weights, cvRound(fastAtan2)) into LDS; lanes 0 .. 63 and 0 .. 7 again sum
 //                    the 72 windows, each in sample order; the best window by a butterfly that prefers the lower
@@ -56,7 +61,13 @@ struct SurfLayout {
   unsigned plane_off[SURF_MAX_OCTAVES], pos_off[SURF_MAX_OCTAVES + 1];
 };
 
-__device__ __forceinline__ int surf_size(int o, int l) { return (SURF_HAAR0 + SURF_HAAR_INC * l) << o; }
+// Image blockIdx.z of a detector launch: its integral image, its det and trace planes and its keys lie this many
+// entries behind those of image 0 (one image: all zero); its count, segment bounds and flag at index blockIdx.z
+struct SurfBatch {
+  size_t s_stride, plane_stride, key_stride;
+};
+
+__host__ __device__ __forceinline__ int surf_size(int o, int l) { return (SURF_HAAR0 + SURF_HAAR_INC * l) << o; }
 
 // (float)(the box sum) * weight; unsigned arithmetic: the four terms may wrap, the box itself fits an int
 __device__ __forceinline__ float surf_box(const int32_t* __restrict__ S, size_t w1, int y, int x, int x1, int y1, int x2, int y2,
@@ -70,7 +81,8 @@ __device__ __forceinline__ float surf_box(const int32_t* __restrict__ S, size_t 
 __device__ __forceinline__ float surf_weight(float wt, int dx, int dy) { return wt / ((float)dx * (float)dy); }
 
 __global__ void __launch_bounds__(256)
-k_surf_hessian(const int32_t* __restrict__ S, SurfLayout L, float* __restrict__ det, float* __restrict__ trace) {
+k_surf_hessian(const int32_t* __restrict__ S, SurfLayout L, float* __restrict__ det, float* __restrict__ trace, SurfBatch B) {
+  S += blockIdx.z * B.s_stride; det += blockIdx.z * B.plane_stride; trace += blockIdx.z * B.plane_stride;
   const int index = blockIdx.y;
   const int o = index / (L.n_layers + 2), l = index - o * (L.n_layers + 2);
   const int step = 1 << o, size = surf_size(o, l);
@@ -170,7 +182,9 @@ __device__ __forceinline__ bool surf_keypoint(const SurfLayout& L, const float* 
 
 __global__ void __launch_bounds__(256)
 k_surf_maxima(SurfLayout L, const float* __restrict__ det, const float* __restrict__ trace, float thr,
-              unsigned long long* __restrict__ keys, unsigned* __restrict__ count, unsigned cap) {
+              unsigned long long* __restrict__ keys, unsigned* __restrict__ count, unsigned cap, SurfBatch B) {
+  det += blockIdx.z * B.plane_stride; trace += blockIdx.z * B.plane_stride;
+  keys += blockIdx.z * B.key_stride; count += blockIdx.z;
   const int m = blockIdx.y;                          // middle layer l = 1 .. n_layers of octave o
   const int o = m / L.n_layers, l = 1 + m - o * L.n_layers;
   const int step = 1 << o, rows = L.h >> o, cols = L.w >> o;
@@ -191,7 +205,7 @@ k_surf_maxima(SurfLayout L, const float* __restrict__ det, const float* __restri
   base = (unsigned)__shfl((int)base, leader);
   if (!found) return;
   const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-  if (slot >= cap) return;                           // (the counter has counted it: the host refuses the image)
+  if (slot >= cap) return;                           // (the counter has counted it: the image is refused, or marked as overflowed)
   const unsigned pos = L.pos_off[o] + (unsigned)(l - 1) * (unsigned)(rows * cols) + e;
   keys[slot] = ((unsigned long long)__float_as_uint(k.response) << 32) | (unsigned long long)(0xFFFFFFFFu - pos);
 }
@@ -202,12 +216,10 @@ k_surf_rekey(unsigned long long* __restrict__ keys, unsigned n) {
   if (i < n) keys[i] ^= 0xFFFFFFFFull;
 }
 
-__global__ void __launch_bounds__(256)
-k_surf_emit(SurfLayout L, const float* __restrict__ det, const float* __restrict__ trace, float thr,
-            const unsigned long long* __restrict__ keys, int total, int flipped, sf_keypoint* __restrict__ kp_out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const unsigned low = (unsigned)keys[i];
+// key i of a sorted list -> its keypoint, the interpolation done again from the planes
+__device__ __forceinline__ sf_keypoint surf_emit_one(const SurfLayout& L, const float* __restrict__ det, const float* __restrict__ trace,
+                                                     float thr, unsigned long long key, int flipped) {
+  const unsigned low = (unsigned)key;
   const unsigned pos = flipped ? low : 0xFFFFFFFFu - low;
   int o = 0;
   while (o + 1 < L.n_octaves && pos >= L.pos_off[o + 1]) ++o;
@@ -218,7 +230,58 @@ k_surf_emit(SurfLayout L, const float* __restrict__ det, const float* __restrict
   // (the same function on the same planes as k_surf_maxima: it finds the keypoint again)
   if (!surf_keypoint(L, det, trace, thr, o, l, (int)(e / (unsigned)cols), (int)(e % (unsigned)cols), &k))
     k = sf_make_keypoint(0.0f, 0.0f, 0.0f, 0.0f, 0);
-  kp_out[i] = k;
+  return k;
+}
+
+__global__ void __launch_bounds__(256)
+k_surf_emit(SurfLayout L, const float* __restrict__ det, const float* __restrict__ trace, float thr,
+            const unsigned long long* __restrict__ keys, int total, int flipped, sf_keypoint* __restrict__ kp_out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  kp_out[i] = surf_emit_one(L, det, trace, thr, keys[i], flipped);
+}
+
+// ---- the batch form: what the host decides in sf_launch_detect_surf, per image on the device ---------------------------
+constexpr int SURF_SEGMENT_BLOCKS = 32;
+
+// blockIdx.y = image.  count / seg_begin / seg_end / flipped: [images of the launch]; the segment bounds count from the
+// launch's first key.  overflowed: the handle's counter of the call.
+__global__ void __launch_bounds__(256)
+k_surf_segments(unsigned long long* __restrict__ keys, const unsigned* __restrict__ count, unsigned cap_img, size_t key_stride,
+                int max_features, unsigned* __restrict__ seg_begin, unsigned* __restrict__ seg_end, unsigned* __restrict__ flipped,
+                unsigned* __restrict__ overflowed) {
+  const unsigned img = blockIdx.y;
+  const unsigned n = count[img];
+  const bool over = n > cap_img;
+  const bool cut = !over && max_features > 0 && n > (unsigned)max_features;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned begin = (unsigned)(img * key_stride);
+    seg_begin[img] = begin;
+    seg_end[img] = begin + (over ? 0u : n);
+    flipped[img] = cut ? 1u : 0u;
+    if (over) atomicAdd(overflowed, 1u);
+  }
+  if (!cut) return;
+  keys += img * key_stride;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) keys[i] ^= 0xFFFFFFFFull;
+}
+
+// blockIdx.y = image: the first min(count, max_features) sorted keys of the image -> kp_out [image][cap], n_out [image];
+// an overflowed image: no keypoint
+__global__ void __launch_bounds__(256)
+k_surf_emit_batch(SurfLayout L, const float* __restrict__ det, const float* __restrict__ trace, float thr,
+                  const unsigned long long* __restrict__ keys, const unsigned* __restrict__ count, const unsigned* __restrict__ flipped,
+                  unsigned cap_img, int max_features, sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out,
+                  SurfBatch B) {
+  const unsigned img = blockIdx.y;
+  const unsigned n = count[img];
+  int total = n > cap_img ? 0 : (int)n;
+  if (max_features > 0 && total > max_features) total = max_features;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) n_out[img] = total;
+  if (i >= total || i >= cap) return;
+  det += img * B.plane_stride; trace += img * B.plane_stride;
+  kp_out[(size_t)img * cap + i] = surf_emit_one(L, det, trace, thr, keys[img * B.key_stride + i], (int)flipped[img]);
 }
 
 // ---- orientation and descriptor ------------------------------------------------------------------------------------------
@@ -491,6 +554,9 @@ extern "C" void sf_surf_build_tables(float* ori_w, int8_t* ori_xy, float* desc_w
       for (int j = 0; j < SURF_PATCH; ++j) desc_w[i * SURF_PATCH + j] = (float)(g20[i] * g20[j]);
 }
 
+// The candidate capacity of one image: SURF_MAX_CANDIDATES, or what sf_debug_surf_limits has put in its place
+static unsigned surf_candidate_cap(const sf_context* c) { return c->surf_debug_cap > 0 ? (unsigned)c->surf_debug_cap : SURF_MAX_CANDIDATES; }
+
 // Launch sequence on the handle's stream.  The count of maxima crosses to the host once: the sort is sized by it, and an
 // image with more maxima than the key buffer holds is refused there.
 int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
@@ -506,20 +572,22 @@ int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int 
   unsigned long long* keys = (unsigned long long*)c->surf_keys.p;
   unsigned long long* keys_sorted = keys + SURF_MAX_CANDIDATES;
   unsigned* count = (unsigned*)(keys_sorted + SURF_MAX_CANDIDATES);
+  const unsigned cand_cap = surf_candidate_cap(c);
   const int32_t* S = nullptr;
   if ((rc = sf_launch_integral(c, d_image, width, height, pitch, &S)) != SF_OK) return rc;
   SF_HIP(c, hipMemsetAsync(count, 0, 4, c->stream));
   const unsigned blocks = (unsigned)(((size_t)width * height + 255) / 256);
   const int n_all = prm->n_octaves * (prm->n_octave_layers + 2), n_middle = prm->n_octaves * prm->n_octave_layers;
-  hipLaunchKernelGGL(k_surf_hessian, dim3(blocks, n_all), dim3(256), 0, c->stream, S, L, det, trace);
+  const SurfBatch one = {0, 0, 0};
+  hipLaunchKernelGGL(k_surf_hessian, dim3(blocks, n_all), dim3(256), 0, c->stream, S, L, det, trace, one);
   hipLaunchKernelGGL(k_surf_maxima, dim3(blocks, n_middle), dim3(256), 0, c->stream, L, (const float*)det, (const float*)trace,
-                     prm->hessian_threshold, keys, count, SURF_MAX_CANDIDATES);
+                     prm->hessian_threshold, keys, count, cand_cap, one);
   SF_HIP(c, hipGetLastError());
   unsigned h_count = 0;
   if ((rc = sf_word_to_host(c, count, &h_count)) != SF_OK) return rc;
-  if (h_count > SURF_MAX_CANDIDATES)
+  if (h_count > cand_cap)
     return sf_fail(c, SF_ERANGE, "SURF: %u maxima in a %d x %d image exceed the candidate capacity %u; raise hessian_threshold", h_count,
-                   width, height, SURF_MAX_CANDIDATES);
+                   width, height, cand_cap);
   const int n = (int)h_count;
   const bool cut = max_features > 0 && n > max_features;   // limitKeypoints: equal responses by descending position
   const int total = cut ? max_features : n, written = std::min(total, cap);
@@ -532,6 +600,102 @@ int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int 
     SF_HIP(c, hipGetLastError());
   }
   if (n_out) *n_out = total;
+  return SF_OK;
+}
+
+// The host arithmetic of the batch form (no device, c may be null).  B bounds the maxima an image of this layout can have:
+// surf_keypoint demands v > q of all 26 neighbours, so two maxima of one layer are never 8-adjacent, and a layer whose
+// interior (the samples k_surf_maxima looks at) is r x c holds at most ceil(r / 2) ceil(c / 2) of them.  An image's key
+// capacity is the smaller of B and the candidate capacity: where B is the smaller (up to about a megapixel under the
+// defaults) no image can overflow.
+int sf_surf_batch_plan_host(sf_context* c, int width, int height, const sf_surf_params& p, int n, unsigned candidate_cap,
+                            int forced_chunk, SfSurfBatchPlan* out) {
+  SurfLayout L;
+  size_t floats = 0;
+  const int rc = surf_layout(c, width, height, p, &L, &floats);
+  if (rc != SF_OK) return rc;
+  unsigned long long bound = 0;
+  for (int o = 0; o < p.n_octaves; ++o)
+    for (int l = 1; l <= p.n_octave_layers; ++l) {
+      const int step = 1 << o, margin = (surf_size(o, l + 1) / 2) / step + 1;
+      const long long r = std::max((height >> o) - 2 * margin, 0), q = std::max((width >> o) - 2 * margin, 0);
+      bound += (unsigned long long)(((r + 1) / 2) * ((q + 1) / 2));
+    }
+  if (candidate_cap == 0) candidate_cap = SURF_MAX_CANDIDATES;
+  out->bound = bound;
+  out->cap_img = (unsigned)std::min<unsigned long long>(candidate_cap, bound);
+  out->key_stride = std::max(out->cap_img, 1u);
+  out->plane_floats = std::max<size_t>(floats, 1);
+  // per image: det and trace planes, the keys and their sorted copy, count / segment bounds / flag
+  out->per_image = out->plane_floats * 2 * sizeof(float) + (size_t)out->key_stride * 16 + 16;
+  long long chunk = forced_chunk > 0 ? forced_chunk : (long long)(SURF_BATCH_WORKSPACE_BYTES / out->per_image);
+  chunk = std::min<long long>(chunk, 0x7FFFFFFFll / out->key_stride);   // (the segmented sort counts its keys in 32 bits)
+  chunk = std::min<long long>(chunk, 65535);                            // (the image is a grid dimension)
+  out->chunk = (int)std::max<long long>(std::min<long long>(chunk, n), 1);
+  out->workspace_bytes = (size_t)out->chunk * out->per_image;
+  return SF_OK;
+}
+
+// The plan of a batch under the handle's limits and its buffers (a caller reserves before its first launch; the launcher
+// below asks again and finds them there)
+int sf_surf_batch_reserve(sf_context* c, int width, int height, const sf_surf_params& p, int n_img, SfSurfBatchPlan* plan) {
+  int rc;
+  if ((rc = sf_surf_batch_plan_host(c, width, height, p, n_img, surf_candidate_cap(c), c->surf_debug_chunk, plan)) != SF_OK) return rc;
+  const size_t ctl_words = ((size_t)n_img + 15) & ~(size_t)15;
+  if ((rc = sf_buf_reserve(c, c->surf_planes, (size_t)plan->chunk * plan->plane_floats * 2 * sizeof(float))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->surf_keys, std::max((size_t)plan->chunk * plan->key_stride * 16, (size_t)SURF_MAX_CANDIDATES * 16 + 16))) != SF_OK)
+    return rc;
+  if ((rc = sf_buf_reserve(c, c->surf_ctl, 64 + 4 * ctl_words * sizeof(unsigned))) != SF_OK) return rc;
+  return sf_buf_reserve(c, c->ex_integral, (size_t)(width + 1) * (height + 1) * sizeof(int32_t) * n_img);
+}
+
+// The detector on n_img images of one size with no host round trip: d_kpts_out [n_img][cap], d_n_out [n_img] on the device,
+// max_features > 0.  The integral images of ALL images are built first and stay in c->ex_integral for the extraction; the
+// rest runs over chunks of plan.chunk images -- consecutive launches on the handle's stream -- so that planes and keys keep
+// to SURF_BATCH_WORKSPACE_BYTES.  An image with more maxima than its key capacity keeps no keypoint and is counted in the
+// first word of c->surf_ctl (sf_surf_batch_status); the per-image words follow from byte 64 on.
+int sf_launch_detect_surf_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                                int pitch, int max_features, const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap,
+                                int32_t* d_n_out) {
+  SurfLayout L;
+  size_t floats = 0;
+  SfSurfBatchPlan plan;
+  int rc;
+  if ((rc = surf_layout(c, width, height, *prm, &L, &floats)) != SF_OK) return rc;
+  if ((rc = sf_surf_batch_reserve(c, width, height, *prm, n_img, &plan)) != SF_OK) return rc;   // (the caller's: nothing moves)
+  const size_t ctl_words = ((size_t)n_img + 15) & ~(size_t)15;
+  float* planes = (float*)c->surf_planes.p;
+  unsigned long long* keys = (unsigned long long*)c->surf_keys.p;
+  unsigned long long* keys_sorted = keys + (size_t)plan.chunk * plan.key_stride;
+  unsigned* overflowed = (unsigned*)c->surf_ctl.p;
+  unsigned* count = overflowed + 16;
+  unsigned *seg_begin = count + ctl_words, *seg_end = seg_begin + ctl_words, *flipped = seg_end + ctl_words;
+  const int32_t* S = nullptr;
+  size_t s_stride = 0;
+  if ((rc = sf_launch_integral_batch(c, d_images, img_stride, n_img, width, height, pitch, &S, &s_stride)) != SF_OK) return rc;
+  SF_HIP(c, hipMemsetAsync(overflowed, 0, 64 + ctl_words * sizeof(unsigned), c->stream));   // the counter and every count
+  const unsigned blocks = (unsigned)(((size_t)width * height + 255) / 256);
+  const int n_all = prm->n_octaves * (prm->n_octave_layers + 2), n_middle = prm->n_octaves * prm->n_octave_layers;
+  const int written = std::min(max_features, cap);
+  const SurfBatch B = {s_stride, 2 * plan.plane_floats, plan.key_stride};
+  float* det = planes;
+  float* trace = planes + plan.plane_floats;
+  for (int i0 = 0; i0 < n_img; i0 += plan.chunk) {
+    const int m = std::min(plan.chunk, n_img - i0);
+    hipLaunchKernelGGL(k_surf_hessian, dim3(blocks, n_all, m), dim3(256), 0, c->stream, S + (size_t)i0 * s_stride, L, det, trace, B);
+    hipLaunchKernelGGL(k_surf_maxima, dim3(blocks, n_middle, m), dim3(256), 0, c->stream, L, (const float*)det, (const float*)trace,
+                       prm->hessian_threshold, keys, count + i0, plan.cap_img, B);
+    hipLaunchKernelGGL(k_surf_segments, dim3(SURF_SEGMENT_BLOCKS, m), dim3(256), 0, c->stream, keys, (const unsigned*)(count + i0),
+                       plan.cap_img, plan.key_stride, max_features, seg_begin + i0, seg_end + i0, flipped + i0, overflowed);
+    SF_HIP(c, hipGetLastError());
+    if ((rc = sf_sort_keys_segmented_desc(c, keys, keys_sorted, (unsigned)((size_t)m * plan.key_stride), (unsigned)m, seg_begin + i0,
+                                          seg_end + i0, 0, 64)) != SF_OK)
+      return rc;
+    hipLaunchKernelGGL(k_surf_emit_batch, dim3(std::max((written + 255) / 256, 1), m), dim3(256), 0, c->stream, L, (const float*)det,
+                       (const float*)trace, prm->hessian_threshold, (const unsigned long long*)keys_sorted, (const unsigned*)(count + i0),
+                       (const unsigned*)(flipped + i0), plan.cap_img, max_features, d_kpts_out + (size_t)i0 * cap, cap, d_n_out + i0, B);
+    SF_HIP(c, hipGetLastError());
+  }
   return SF_OK;
 }
 

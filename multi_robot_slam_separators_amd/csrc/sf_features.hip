@@ -979,9 +979,12 @@ extern "C" int sf_get_features_and_descriptor_u8(sf_handle c, const uint8_t* lef
 // extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
 // host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.
 // The batch form in three parts, shared by sf_get_features_and_descriptor_batch_device, sf_add_keyframes_u8_batch_device
-// and their Vis/FeatureType 2 twins (the _orb_ calls; `orb_call`): batch_check refuses (nothing is touched;
+// and their Vis/FeatureType 2 and 0 twins (the _orb_ and _surf_ calls; `family`): batch_check refuses (nothing is touched;
 // n_keyframes = 0 passes without a look at the images), batch_reserve takes the store slots and the call's buffers,
-// batch_launch queues the three stages.  Type 2 is reached through its own calls only, as it is selected through its own.
+// batch_launch queues the three stages.  Types 2 and 0 are reached through their own calls only, as they are selected
+// through their own.
+enum BatchFamily { BATCH_GENERIC, BATCH_ORB, BATCH_SURF };
+
 struct BatchPlan {
   sf_detector_params dp;
   sf_stereo_flow_params prm;
@@ -989,15 +992,21 @@ struct BatchPlan {
   FrontPlan front;
 };
 
-static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframes, int width, int height, int pitch,
+static int batch_check(sf_context* c, BatchFamily family, bool images, int n_keyframes, int width, int height, int pitch,
                        size_t image_stride, const sf_detector_params* det, const sf_stereo_flow_params* flow, BatchPlan* plan) {
+  const bool orb_call = family == BATCH_ORB, surf_call = family == BATCH_SURF;
   if (c->feature_type == 2 && !orb_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has batch forms of its own: sf_get_features_and_descriptor_orb_batch_device, sf_add_keyframes_orb_u8_batch_device");
+  if (c->feature_type == 0 && !surf_call)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 0 (SURF) has batch forms of its own: sf_get_features_and_descriptor_surf_batch_device, sf_add_keyframes_surf_u8_batch_device");
   if (c->feature_type != 2 && orb_call)
-    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the ORB batch calls need type 2 (sf_set_feature_type_orb); use sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device",
-                   c->feature_type);
-  if (c->feature_type == 0)
-    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 0 (SURF): the batch forms are not built; use sf_get_features_and_descriptor or sf_extract_keyframe_device per keyframe");
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the ORB batch calls need type 2 (sf_set_feature_type_orb); use %s",
+                   c->feature_type, c->feature_type == 0 ? "sf_get_features_and_descriptor_surf_batch_device / sf_add_keyframes_surf_u8_batch_device"
+                                                         : "sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device");
+  if (c->feature_type != 0 && surf_call)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the SURF batch calls need type 0 (sf_set_feature_type_surf); use %s",
+                   c->feature_type, c->feature_type == 2 ? "sf_get_features_and_descriptor_orb_batch_device / sf_add_keyframes_orb_u8_batch_device"
+                                                         : "sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device");
   if (n_keyframes == 0) return SF_OK;
   int rc = check_image(c, images, width, height, pitch, 3, "stereo pairs");
   if (rc != SF_OK) return rc;
@@ -1028,6 +1037,13 @@ static int batch_check(sf_context* c, bool orb_call, bool images, int n_keyframe
       if (P.w[l] < 1 || P.h[l] < 1)
         return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, width, height, (double)P.scale[l]);
   }
+  if (surf_call) {                                       // what sf_detect_surf_device refuses
+    if ((rc = surf_validate(c, c->surf)) != SF_OK) return rc;
+    if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
+    if (n_keyframes > 65535) return sf_fail(c, SF_ERANGE, "SURF batch of %d keyframes (at most 65535)", n_keyframes);
+    SfSurfBatchPlan sp;                                  // (the layout's 2^31 plane samples)
+    if ((rc = sf_surf_batch_plan_host(c, width, height, c->surf, n_keyframes, 0, 0, &sp)) != SF_OK) return rc;
+  }
   return SF_OK;
 }
 
@@ -1042,6 +1058,10 @@ static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan*
   if ((rc = sf_buf_reserve(c, c->ft_counts, (size_t)n * 4)) != SF_OK) return rc;
   if ((rc = sf_store_reserve(c, c->store, c->store.slots + n, maxf, plan->kind.bytes)) != SF_OK) return rc;
   if (fast_corners(c->feature_type) && (rc = check_pixels(c, width, height)) != SF_OK) return rc;
+  if (c->feature_type == 0) {                              // the detector's planes, keys and integral images
+    SfSurfBatchPlan sp;
+    if ((rc = sf_surf_batch_reserve(c, width, height, c->surf, n, &sp)) != SF_OK) return rc;
+  }
   return SF_OK;
 }
 
@@ -1060,6 +1080,9 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   if (c->feature_type == 2) {                            // (keypoints in level-0 coordinates; the pyramids stay for the extraction;
     rc = sf_launch_detect_orb_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
     kind.pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;   // no ROI: front_plan)
+  } else if (c->feature_type == 0) {                     // (no ROI, no grid: front_plan, grid_plan; the integral images stay
+    rc = sf_launch_detect_surf_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->surf, d_kpts, maxf, d_n);
+    kind.integral_ready = true;                          // for the extraction)
   } else if (fp.grid()) {                                // the cells as the detector's images, joined by k_grid_gather
     rc = grid_detect(c, fp, dp, d_left, image_stride, n, pitch, d_kpts, d_n);
   } else if (fast_corners(c->feature_type)) {
@@ -1091,13 +1114,13 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   return SF_OK;
 }
 
-static int features_batch(sf_context* c, bool orb_call, const uint8_t* d_left, const uint8_t* d_right, int32_t n_keyframes,
+static int features_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const uint8_t* d_right, int32_t n_keyframes,
                           int32_t width, int32_t height, int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
                           const sf_detector_params* det, const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                           int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
   BatchPlan plan;
-  int rc = batch_check(c, orb_call, d_left && d_right, n_keyframes, width, height, pitch, image_stride, det, flow, &plan);
+  int rc = batch_check(c, family, d_left && d_right, n_keyframes, width, height, pitch, image_stride, det, flow, &plan);
   if (rc != SF_OK) return rc;
   if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
   if ((rc = batch_reserve(c, n_keyframes, width, height, &plan)) != SF_OK) return rc;
@@ -1111,7 +1134,7 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
                                                            const sf_detector_params* det, const sf_stereo_flow_params* flow,
                                                            int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                            float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return features_batch(c, false, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+  return features_batch(c, BATCH_GENERIC, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
                         d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
@@ -1122,8 +1145,64 @@ extern "C" int sf_get_features_and_descriptor_orb_batch_device(sf_handle c, cons
                                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                                int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
                                                                sf_keypoint* d_kpts_out) {
-  return features_batch(c, true, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+  return features_batch(c, BATCH_ORB, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
                         d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_surf_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                                int32_t n_keyframes, int32_t width, int32_t height,
+                                                                int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                                                                const sf_detector_params* det,
+                                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                                int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
+                                                                sf_keypoint* d_kpts_out) {
+  return features_batch(c, BATCH_SURF, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+// How many keyframes of the most recent SURF batch call had more maxima than their key capacity (they hold no rows)
+extern "C" int sf_surf_batch_status(sf_handle c, int32_t* n_overflowed_out) {
+  if (!c) return SF_EINVAL;
+  if (n_overflowed_out) *n_overflowed_out = 0;
+  SF_HIP(c, hipSetDevice(c->device));
+  int32_t n = 0;
+  if (c->surf_ctl.p) {
+    const int rc = sf_word_to_host(c, c->surf_ctl.p, &n);
+    if (rc != SF_OK) return rc;
+  } else {
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  if (n_overflowed_out) *n_overflowed_out = n;
+  if (n > 0)
+    return sf_fail(c, SF_ERANGE, "SURF: %d keyframe(s) of the last batch call had more maxima than the candidate capacity and hold no rows; raise hessian_threshold",
+                   n);
+  return SF_OK;
+}
+
+// ---- sf_experimental.h: small shapes for the tests of SURF's batch form ----------------------------------------------
+extern "C" int sf_debug_surf_limits(sf_handle c, int32_t candidate_cap, int32_t batch_chunk) {
+  if (!c) return SF_EINVAL;
+  if (candidate_cap < 0 || (unsigned)candidate_cap > SURF_MAX_CANDIDATES || batch_chunk < 0 || batch_chunk > 65535)
+    return sf_fail(c, SF_EINVAL, "sf_debug_surf_limits: candidate_cap %d outside 0 .. %u or batch_chunk %d outside 0 .. 65535", candidate_cap,
+                   SURF_MAX_CANDIDATES, batch_chunk);
+  c->surf_debug_cap = candidate_cap;
+  c->surf_debug_chunk = batch_chunk;
+  return SF_OK;
+}
+
+extern "C" int sf_surf_batch_plan(int32_t width, int32_t height, const sf_surf_params* surf, int32_t n_keyframes,
+                                  int32_t* cap_img_out, int32_t* chunk_out, int64_t* workspace_bytes_out) {
+  const sf_surf_params p = arg_or_defaults(surf, sf_surf_defaults);
+  if (width < 3 || height < 3 || n_keyframes < 1 || n_keyframes > 65535) return SF_EINVAL;
+  int rc = surf_validate(nullptr, p);
+  if (rc != SF_OK) return rc;
+  if ((long long)width * height > (1ll << 26) || (long long)(width + 1) * (height + 1) * 255 > 0x7FFFFFFFll) return SF_ERANGE;
+  SfSurfBatchPlan sp;
+  if ((rc = sf_surf_batch_plan_host(nullptr, width, height, p, n_keyframes, 0, 0, &sp)) != SF_OK) return rc;
+  if (cap_img_out) *cap_img_out = (int32_t)sp.cap_img;
+  if (chunk_out) *chunk_out = sp.chunk;
+  if (workspace_bytes_out) *workspace_bytes_out = (int64_t)sp.workspace_bytes;
+  return SF_OK;
 }
 
 // ---- the camera's own images (kernels in k_image.hip, k_cnn.hip) ---------------------------------------------------
@@ -1180,7 +1259,7 @@ extern "C" int sf_netvlad_infer_u8_batch_device(sf_handle c, const uint8_t* d_im
 // images (one launch), the network on the colour images, the batch feature stages on the planes, the descriptors' prefix
 // into the local NN rows.  Everything that can refuse does so before the first launch; the store and the NN database
 // grow last, together.
-static int add_keyframes_batch(sf_context* c, bool orb_call, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+static int add_keyframes_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
                                int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
                                const sf_stereo_flow_params* flow, int32_t* first_slot_out, int32_t* first_nn_row_out,
@@ -1198,7 +1277,7 @@ static int add_keyframes_batch(sf_context* c, bool orb_call, const uint8_t* d_le
   const int g_pitch = n > 0 ? (width + 15) & ~15 : 0;
   const size_t g_stride = ((size_t)g_pitch * (n > 0 ? height : 0) + 255) & ~(size_t)255;
   BatchPlan plan;
-  if ((rc = batch_check(c, orb_call, true, n, width, height, g_pitch, g_stride, det, flow, &plan)) != SF_OK) return rc;
+  if ((rc = batch_check(c, family, true, n, width, height, g_pitch, g_stride, det, flow, &plan)) != SF_OK) return rc;
   if (n == 0) {
     if (first_slot_out) *first_slot_out = c->store.slots;
     if (first_nn_row_out) *first_nn_row_out = c->nn_local.n;
@@ -1242,7 +1321,7 @@ extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_le
                                                 const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                 int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                 float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return add_keyframes_batch(c, false, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+  return add_keyframes_batch(c, BATCH_GENERIC, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
                              flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
@@ -1253,6 +1332,17 @@ extern "C" int sf_add_keyframes_orb_u8_batch_device(sf_handle c, const uint8_t* 
                                                     const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                     int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                     float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return add_keyframes_batch(c, true, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+  return add_keyframes_batch(c, BATCH_ORB, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_add_keyframes_surf_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                     const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                     int32_t height, int32_t pitch, size_t image_stride,
+                                                     const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                     const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                     int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                     float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, BATCH_SURF, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
                              flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }

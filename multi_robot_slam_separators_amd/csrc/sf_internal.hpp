@@ -218,6 +218,19 @@ struct SfSurfTables {
 };
 constexpr int SURF_ORI_SAMPLES = 109, SURF_PATCH = 20, SURF_MAX_OCTAVES = 8, SURF_MAX_LAYERS = 8;
 constexpr unsigned SURF_MAX_CANDIDATES = 1u << 18;   // maxima per image; more is SF_ERANGE, never a truncated list
+// The batch form of the detector (sf_launch_detect_surf_batch) runs over chunks of images whose det / trace planes and keys
+// fit this much workspace: the size of the Infinity Cache, so that the planes k_surf_hessian writes are still on the die
+// when k_surf_maxima and k_surf_emit_batch read them, and two orders of magnitude more workgroups per launch than the chip
+// has compute units.  One image always runs, whatever it needs.
+constexpr size_t SURF_BATCH_WORKSPACE_BYTES = (size_t)256 << 20;
+// What sf_surf_batch_plan_host computes for n images of one size: the bound on an image's maxima, its key capacity
+// cap_img = min(candidate capacity, bound) (key_stride: at least one key), the images per chunk and their workspace
+struct SfSurfBatchPlan {
+  unsigned long long bound;
+  unsigned cap_img, key_stride;
+  int chunk;
+  size_t plane_floats, per_image, workspace_bytes;
+};
 constexpr size_t SURF_TABLE_ORI_W = 0, SURF_TABLE_DESC_W = 512, SURF_TABLE_ORI_XY = 2112, SURF_TABLE_BYTES = 2368;
 
 struct sf_context {
@@ -292,6 +305,11 @@ struct sf_context {
   sf_surf_params surf = {500.0f, 4, 2, 0, 0};
   bool surf_tables_ok = false;
   Buf surf_planes, surf_keys, surf_tables;
+  // the batch form: surf_ctl holds the number of keyframes of the most recent batch call whose maxima exceeded the key
+  // capacity (word 0) and, from byte 64 on, every image's count, segment bounds and rekey flag.  surf_debug_cap /
+  // surf_debug_chunk (sf_debug_surf_limits; 0 = the defaults): the candidate capacity and the images per chunk
+  Buf surf_ctl;
+  int surf_debug_cap = 0, surf_debug_chunk = 0;
   SfSurfTables surf_dev = {};
   // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
   // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
@@ -710,12 +728,29 @@ struct ExtractKind {
   size_t pyr_stride;
   const SfFreakTables* freak = nullptr;   // not null: FREAK rows (bytes 64; d_tests, orb and pyr unused)
   const SfSurfTables* surf = nullptr;     // not null: SURF rows (bytes 256 or 512, float32; the rest unused)
+  // sf_launch_detect_surf_batch has left the integral images of the call's images in c->ex_integral: the extraction reads
+  // them there and builds none (as pyr_stride for ORB's pyramids)
+  bool integral_ready = false;
 };
 // the integral image of one image into c->ex_integral (k_extract.hip): (height + 1) x (width + 1) int32
 int sf_launch_integral(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const int32_t** S_out);
 // the fast-Hessian detector of SURF + limitKeypoints (k_surf.hip); prm validated by the caller
 int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
                           const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
+// the integral images of n_img images img_stride bytes apart into c->ex_integral, *s_stride entries apart (k_extract.hip)
+int sf_launch_integral_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                             int pitch, const int32_t** S_out, size_t* s_stride);
+// the host arithmetic of SURF's batch form, no device call (c may be null); candidate_cap 0 = SURF_MAX_CANDIDATES,
+// forced_chunk 0 = what SURF_BATCH_WORKSPACE_BYTES allows
+int sf_surf_batch_plan_host(sf_context* c, int width, int height, const sf_surf_params& p, int n, unsigned candidate_cap,
+                            int forced_chunk, SfSurfBatchPlan* out);
+// the plan under the handle's limits (sf_debug_surf_limits) and every buffer sf_launch_detect_surf_batch takes
+int sf_surf_batch_reserve(sf_context* c, int width, int height, const sf_surf_params& p, int n_img, SfSurfBatchPlan* plan);
+// the same detector on n_img images of one size with no host round trip: d_kpts_out [n_img][cap], d_n_out [n_img] on the
+// device; the integral images of all images stay in c->ex_integral for the extraction
+int sf_launch_detect_surf_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                                int pitch, int max_features, const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap,
+                                int32_t* d_n_out);
 // host halves of the FREAK tables (k_freak.hip): the orientation pairs' weights from scale 0 / orientation 0 of a pattern,
 // and the device layout of the selected pairs
 void sf_freak_orientation_table(const float* pattern, int32_t* orient /* [45][4] */);

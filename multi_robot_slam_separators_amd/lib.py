@@ -115,6 +115,9 @@ def load():
         "sf_detect_surf_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.SurfParams), vp, i32, P(i32)]),
         "sf_surf_build_tables": (None, [vp, vp, vp]),
         "sf_surf_check_params": (C.c_int, [P(_abi.SurfParams)]),
+        "sf_surf_batch_status": (C.c_int, [vp, P(i32)]),
+        "sf_debug_surf_limits": (C.c_int, [vp, i32, i32]),
+        "sf_surf_batch_plan": (C.c_int, [i32, i32, P(_abi.SurfParams), i32, P(i32), P(i32), P(i64)]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
         "sf_stereo_flow_defaults": (None, [P(_abi.StereoFlowParams)]),
         "sf_detector_defaults": (None, [P(_abi.DetectorParams)]),
@@ -193,6 +196,9 @@ def load():
     # the batch forms of Vis/FeatureType 2: the argument lists of their generic twins
     sig["sf_get_features_and_descriptor_orb_batch_device"] = sig["sf_get_features_and_descriptor_batch_device"]
     sig["sf_add_keyframes_orb_u8_batch_device"] = sig["sf_add_keyframes_u8_batch_device"]
+    # ... and of Vis/FeatureType 0
+    sig["sf_get_features_and_descriptor_surf_batch_device"] = sig["sf_get_features_and_descriptor_batch_device"]
+    sig["sf_add_keyframes_surf_u8_batch_device"] = sig["sf_add_keyframes_u8_batch_device"]
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export the ABI
         fn.restype = res
@@ -234,6 +240,8 @@ EXPORTED = [
     "sf_freak_build_pattern", "sf_freak_default_pairs",
     "sf_surf_defaults", "sf_set_feature_type_surf", "sf_get_surf_params", "sf_detect_surf_device", "sf_surf_build_tables",
     "sf_surf_check_params",
+    "sf_get_features_and_descriptor_surf_batch_device", "sf_add_keyframes_surf_u8_batch_device", "sf_surf_batch_status",
+    "sf_debug_surf_limits", "sf_surf_batch_plan",
 ]
 
 
@@ -265,6 +273,17 @@ def surf_build_tables():
     desc_w = np.zeros(_abi.SURF_PATCH * _abi.SURF_PATCH, np.float32)
     load().sf_surf_build_tables(C.c_void_p(ori_w.ctypes.data), C.c_void_p(ori_xy.ctypes.data), C.c_void_p(desc_w.ctypes.data))
     return ori_xy, ori_w, desc_w
+
+
+def surf_batch_plan(width, height, n_keyframes, surf=None):
+    """sf_surf_batch_plan (no GPU, no handle): (key capacity per image, images per chunk, workspace bytes) of the SURF batch
+    forms on n_keyframes images of width x height (surf: _abi.SurfParams; None = the defaults)."""
+    cap, chunk, ws = C.c_int32(), C.c_int32(), C.c_int64()
+    rc = load().sf_surf_batch_plan(width, height, C.byref(surf) if surf is not None else None, n_keyframes, C.byref(cap),
+                                   C.byref(chunk), C.byref(ws))
+    if rc != _abi.SF_OK:
+        raise SepfinderError(rc, "sf_surf_batch_plan refuses %d x %d, %d keyframes" % (width, height, n_keyframes))
+    return cap.value, chunk.value, ws.value
 
 
 def _ptr(a):
@@ -649,6 +668,11 @@ class SeparatorFinder:
         return value; slot i holds what get_features_and_descriptor_u8 gives for pair i."""
         return self.add_keyframes_u8_batch_device(*args, _call="sf_add_keyframes_orb_u8_batch_device", **kw)
 
+    def add_keyframes_surf_u8_batch_device(self, *args, **kw):
+        """add_keyframes_u8_batch_device on a handle of Vis/FeatureType 0 (set_feature_type_surf): same arguments, same
+        return value; slot i holds what get_features_and_descriptor_u8 gives for pair i (surf_batch_status: overflow)."""
+        return self.add_keyframes_u8_batch_device(*args, _call="sf_add_keyframes_surf_u8_batch_device", **kw)
+
     def set_feature_type_orb(self, det=None, orb=None):
         """Vis/FeatureType 2, ORB on a pyramid: det (_abi.OrbDetectorParams; None = rtabmap's ORB/ defaults) drives the
         detector, orb (_abi.OrbParams; None = defaults, edge_threshold 16 .. 64) the border and the descriptors."""
@@ -823,6 +847,26 @@ class SeparatorFinder:
         same return value; per keyframe the bytes of get_features_and_descriptor under type 2."""
         return self.get_features_and_descriptor_batch_device(*args, _call="sf_get_features_and_descriptor_orb_batch_device",
                                                              **kw)
+
+    def get_features_and_descriptor_surf_batch_device(self, *args, **kw):
+        """get_features_and_descriptor_batch_device on a handle of Vis/FeatureType 0 (set_feature_type_surf): same arguments,
+        same return value; per keyframe the bytes of get_features_and_descriptor under type 0, float32 rows."""
+        return self.get_features_and_descriptor_batch_device(*args, _call="sf_get_features_and_descriptor_surf_batch_device",
+                                                             **kw)
+
+    def surf_batch_status(self, check=True):
+        """sf_surf_batch_status: waits for the stream; the number of keyframes of the most recent SURF batch call that had
+        more maxima than their key capacity (they hold no rows).  check: raise SepfinderError (SF_ERANGE) when it is not 0."""
+        n = C.c_int32()
+        rc = self._L.sf_surf_batch_status(self._h, C.byref(n))
+        if check or rc not in (_abi.SF_OK, _abi.SF_ERANGE):
+            self._check(rc)
+        return n.value
+
+    def debug_surf_limits(self, candidate_cap=0, batch_chunk=0):
+        """sf_debug_surf_limits (include/sf_experimental.h): the candidate capacity per image and the images per chunk of
+        the SURF detector, for tests on small shapes; 0 = the default."""
+        self._check(self._L.sf_debug_surf_limits(self._h, candidate_cap, batch_chunk))
 
     def extract_keyframe_device(self, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam,
                                 d_desc_out=None, d_xyz_out=None, d_kpts_out=None, want_rows=True):
