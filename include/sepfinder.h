@@ -92,6 +92,10 @@ extern "C" {
 /* 8, additions: sf_get_features_and_descriptor_surf_batch_device, sf_add_keyframes_surf_u8_batch_device,
       sf_surf_batch_status (the batch forms of Vis/FeatureType 0).  The four existing batch calls still refuse a type-0
       handle, now naming these; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.  */
+/* 8, additions: sf_sift_params, sf_sift_defaults, sf_set_feature_type_sift, sf_get_sift_params, sf_detect_sift_device
+      (SIFT, Vis/FeatureType 1: float32 rows of 128 dimensions on a handle with desc_type 1 and desc_bytes 512; the single
+      calls only).  sf_set_feature_type still refuses 1; nothing existing changed, the version number, sizeof(sf_params)
+      and SF_K_COUNT stay.                                                                                             */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -569,6 +573,52 @@ int  sf_set_feature_type_surf(sf_handle h, const sf_surf_params* surf);
 int  sf_get_surf_params(sf_handle h, sf_surf_params* out);
 int  sf_detect_surf_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                            int32_t max_features, const sf_surf_params* surf, sf_keypoint* d_kpts_out, int32_t cap,
+                           int32_t* n_out);
+/* SIFT: rtabmap's Vis/FeatureType 1, cv::xfeatures2d::SIFT of OpenCV 3.2 with rtabmap's SIFT/ parameters
+   [upstream opencv_contrib, restated in tests/sift_ref.py; DESIGN.md section 3 item 17i lists what the restatement
+   decides].  Rows are 128 float32 holding the integers 0 .. 255 (512 bytes), for a handle created with desc_type 1 and
+   desc_bytes 512 -- the L2 matcher's rows.
+   Detector (sf_detect_sift_device; usable on any handle, it writes no descriptor).  The uint8 image times 48 is enlarged
+   2 x bilinearly into int16 fixed point and blurred to sigma; every octave (cvRound(log2(min side of the enlarged
+   image) - 2) + 1 of them) holds n_octave_layers + 3 Gaussian planes, each blurred from its predecessor, and their
+   n_octave_layers + 2 differences; the next octave starts from every second pixel of plane n_octave_layers.  A sample of
+   a middle difference plane at least 5 pixels inside is a candidate when it exceeds floor(0.5 contrast_threshold /
+   n_octave_layers 255 48) in magnitude and is >= (<=) all 26 neighbours; up to 5 steps of the 3 x 3 solve move it to the
+   sample its offset is within half a step of, where |contrast| n_octave_layers >= contrast_threshold and the edge test
+   tr^2 e < (e + 1)^2 det must hold.  Two candidates that converge to one sample give one keypoint.  A 36-bin gradient
+   histogram of the keypoint's own Gaussian plane gives one keypoint per peak >= 0.8 of the maximum.  Keypoint: position
+   and size in image pixels (halved from the enlarged image), angle in degrees, response = |contrast|, octave = (octave -
+   1) & 255 | layer << 8 | cvRound((offset + 0.5) 255) << 16, class_id -1.  Order: descending response, equal responses
+   by sample of the difference pyramid, then histogram bin; then one cut at the smaller positive of n_features
+   (retainBest) and max_features (rtabmap's limitKeypoints; <= 0: no limit), with the rule of sf_detect_fast_device for
+   equal responses.  An image with more than 262144 extrema or keypoints, or more than 2^26 difference samples, returns
+   SF_ERANGE and writes nothing.  sift NULL = the handle's parameters (the defaults until sf_set_feature_type_sift).
+   Under type 1 sf_extract_keyframe_device is SIFT::compute on the given keypoints: it builds the pyramid of the enlarged
+   image (always: octave byte -1 is its first octave, whatever octaves the keypoints name), reads x, y, size, angle and
+   octave (octave byte and layer name the Gaussian plane) and leaves the keypoint as it is; the row is the 4 x 4 x 8
+   histogram of Gaussian-weighted gradients over the window of radius cvRound(3 scl sqrt(2) 2.5), scl = size / 2 in the
+   plane's pixels, rotated by the angle, with trilinear votes; normalised, clamped at 0.2 of the norm, and scaled to
+   0 .. 255.  Dropped: a keypoint whose octave byte or layer names no plane, whose size is not in (0, 1e6), whose |x| or
+   |y| is not below 1e6, or whose angle is not in [0, 360].  d_desc_out receives rows x 128 float32 through its uint8_t
+   pointer.  3D points, the depth filter and the store slot are every other type's.
+   sf_get_features_and_descriptor and its _u8 form run detector, sub-pixel refinement when it is on, LK or block matching,
+   extraction (which reuses the detector's pyramid).  NOT BUILT under type 1 and refused with SF_EINVAL: Vis/RoiRatios, a
+   grid of cells, and every batch call.                                                                                */
+typedef struct sf_sift_params {
+  int32_t n_features;          /* SIFT/NFeatures, 0; >= 0                         */
+  int32_t n_octave_layers;     /* SIFT/NOctaveLayers, 3; 1 .. 8                   */
+  float   contrast_threshold;  /* SIFT/ContrastThreshold, 0.04; finite, >= 0      */
+  float   edge_threshold;      /* SIFT/EdgeThreshold, 10; finite, > 0             */
+  float   sigma;               /* SIFT/Sigma, 1.6; finite, in [0.8, 8]            */
+} sf_sift_params;              /* 20 bytes */
+void sf_sift_defaults(sf_sift_params* p);
+/* Selects Vis/FeatureType 1 (sift NULL = defaults) on any handle with desc_type 1 and desc_bytes 512, whatever its current
+   type (6, 0 with extended rows, or 1); sf_set_feature_type_surf with extended = 1 leads back likewise.  Out-of-range
+   parameters and any other handle return SF_EINVAL and change nothing.  sf_get_feature_type reports 1 afterwards.      */
+int  sf_set_feature_type_sift(sf_handle h, const sf_sift_params* sift);
+int  sf_get_sift_params(sf_handle h, sf_sift_params* out);
+int  sf_detect_sift_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                           int32_t max_features, const sf_sift_params* sift, sf_keypoint* d_kpts_out, int32_t cap,
                            int32_t* n_out);
 /* The two steps rtabmap's Feature2D::generateKeypoints puts around every detector, whatever the feature type
    [upstream rtabmap / OpenCV 3.2, restated in tests/subpix_ref.py; DESIGN.md section 3 item 17d lists what the restatement

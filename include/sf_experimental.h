@@ -114,6 +114,30 @@ int  sf_debug_surf_limits(sf_handle h, int32_t candidate_cap, int32_t batch_chun
 int  sf_surf_batch_plan(int32_t width, int32_t height, const sf_surf_params* surf, int32_t n_keyframes,
                         int32_t* cap_img_out, int32_t* chunk_out, int64_t* workspace_bytes_out);
 
+
+/* The SIFT detector's host arithmetic, handle-free and usable without a GPU (params NULL = the defaults; out-of-range
+   parameters: SF_EINVAL).  sf_sift_check_params: the ranges sf_detect_sift_device holds sf_sift_params to.
+   sf_sift_build_tables, for i = 0 .. n_octave_layers + 2: sigmas[i] = the blur (float64, libm) that makes the enlarged
+   image's first plane (i = 0: sqrt(max(sigma^2 - 1, 0.01))) or Gaussian plane i from plane i - 1 (sigma k^(i-1)
+   sqrt(k^2 - 1), k = 2^(1/n)); lengths[i] = cvRound(8 sigmas[i] + 1) | 1; coef[520 i + t] = tap t of
+   cv::getGaussianKernel: float64 exp, divided by the sum taken in index order, rounded to float32 once (zero beyond the
+   length).  Any output may be NULL.
+   sf_sift_plan: the octaves of a width x height image -- their number, widths[16] and heights[16] (zero beyond it), and
+   the int16 samples of all Gaussian and all difference planes.  SF_EINVAL: a side below 3; SF_ERANGE: a side above
+   16384 or more than 2^26 difference samples.                                                                       */
+int  sf_sift_check_params(const sf_sift_params* params);
+int  sf_sift_build_tables(const sf_sift_params* params, double* sigmas, int32_t* lengths, float* coef);
+int  sf_sift_plan(int32_t width, int32_t height, const sf_sift_params* params, int32_t* n_octaves_out, int32_t* widths,
+                  int32_t* heights, int64_t* gauss_samples_out, int64_t* dog_samples_out);
+/* candidate_cap (0 = the default, at most 262144) takes the place of the 262144 extrema, and keypoints, an image may have
+   in sf_detect_sift_device (more: SF_ERANGE).  Out of range: SF_EINVAL, nothing changes.                           */
+int  sf_debug_sift_limits(sf_handle h, int32_t candidate_cap);
+/* Copies one int16 plane of the pyramid the most recent sf_detect_sift_device call on this handle built to d_out (dense,
+   the octave's width x height; on the handle's stream): dog = 0, layer 0 .. n_octave_layers + 2: a Gaussian plane;
+   dog = 1, layer 0 .. n_octave_layers + 1: a difference plane.  A failing keypoint comparison can be narrowed to the
+   pyramid with it.  SF_EINVAL: no such call, or no such plane.                                                       */
+int  sf_debug_sift_plane(sf_handle h, int32_t octave, int32_t layer, int32_t dog, int16_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

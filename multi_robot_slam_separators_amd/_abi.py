@@ -311,6 +311,25 @@ def surf_params(hessian_threshold=500.0, n_octaves=4, n_octave_layers=2, upright
 
 
 SURF_ORI_SAMPLES, SURF_PATCH = 109, 20
+FEATURE_SIFT = 1         # ... and of sf_set_feature_type_sift (a handle with desc_type 1 and desc_bytes 512)
+
+
+class SiftParams(C.Structure):
+    """sf_sift_params (include/sepfinder.h): rtabmap's SIFT/ parameters."""
+    _fields_ = [("n_features", C.c_int32), ("n_octave_layers", C.c_int32), ("contrast_threshold", C.c_float),
+                ("edge_threshold", C.c_float), ("sigma", C.c_float)]
+
+
+def sift_params(n_features=0, n_octave_layers=3, contrast_threshold=0.04, edge_threshold=10.0, sigma=1.6):
+    """SIFT/NFeatures, SIFT/NOctaveLayers, SIFT/ContrastThreshold, SIFT/EdgeThreshold, SIFT/Sigma: rtabmap's defaults (what
+    sf_sift_defaults fills)."""
+    p = SiftParams()
+    p.n_features, p.n_octave_layers, p.contrast_threshold, p.edge_threshold, p.sigma = (n_features, n_octave_layers,
+                                                                                          contrast_threshold, edge_threshold, sigma)
+    return p
+
+
+SIFT_MAX_OCTAVES, SIFT_MAX_LAYERS, SIFT_MAX_KLEN = 16, 8, 520
 
 
 SF_IMAGE_RGB8, SF_IMAGE_BGR8, SF_IMAGE_MONO8 = range(3)   # sf_image_format: the camera's images (cv_bridge encodings)

@@ -15,6 +15,7 @@
 // k_orb_points below (cv::ORB::compute on the given keypoints); the 3D points and the commit are shared.
 // FREAK (Vis/FeatureType 3 and 5) keeps the integral image and replaces k_extract_points by k_freak_points (k_freak.hip).
 // SURF (Vis/FeatureType 0) does the same with k_surf_describe (k_surf.hip) and float32 rows.
+// SIFT (Vis/FeatureType 1) reads no integral image: k_sift_describe (k_sift.hip) works on the Gaussian pyramid, float32 rows.
 //
 // Kernels (one keyframe = a few hundred to a few thousand corners of one 752 x 480 .. 1280 x 720 image):
 //   k_integral_rows   one workgroup per image row: wavefront scans of 256-pixel segments, running carry
@@ -480,6 +481,8 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   if (kind.freak && (orb || bytes != FREAK_BYTES)) return sf_fail(c, SF_EINVAL, "FREAK rows are %d bytes, not %d", FREAK_BYTES, bytes);
   if (kind.surf && (orb || kind.freak || bytes != (kind.surf->extended ? 512 : 256)))
     return sf_fail(c, SF_EINVAL, "SURF rows are %d bytes, not %d", kind.surf->extended ? 512 : 256, bytes);
+  if (kind.sift && (orb || kind.freak || kind.surf || bytes != 512 || n_img != 1))
+    return sf_fail(c, SF_EINVAL, "SIFT rows are 512 bytes, one keyframe per call (not %d bytes, %d keyframes)", bytes, n_img);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_xyz, rows_all * 12)) != SF_OK) return rc;
@@ -493,6 +496,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
     if (orb || c->ex_integral.bytes < B.s_stride * sizeof(int32_t) * n_img)
       return sf_fail(c, SF_EINVAL, "the batch's integral images are not the detector's");
     S = (int32_t*)c->ex_integral.p;
+  } else if (kind.sift) {                                // (no integral image: k_sift_describe reads the Gaussian pyramid)
   } else if (!orb) {
     if ((rc = integral_images(c, d_left, n_img, width, height, pitch, &B, &S)) != SF_OK) return rc;
   } else if (!pyr) {
@@ -529,7 +533,14 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   const sf_keypoint* kp_commit = d_kpts;
   if (n > 0) {
     const long long threads = (long long)n * bytes;
-    if (kind.surf) {                                      // the keypoints with their angles, for the commit
+    if (kind.sift) {
+      if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
+      if ((rc = sf_launch_sift_describe(c, d_left, pitch, width, height, *kind.sift, d_kpts, d_right_x, d_status, n, ec,
+                                        (sf_keypoint*)c->ex_kpts.p, (float*)c->ex_desc.p, (float*)c->ex_xyz.p,
+                                        (uint8_t*)c->ex_keep.p)) != SF_OK)
+        return rc;
+      kp_commit = (const sf_keypoint*)c->ex_kpts.p;
+    } else if (kind.surf) {                               // the keypoints with their angles, for the commit
       if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
       sf_launch_surf_describe(c, d_left, pitch, S, width, height, d_kpts, d_right_x, d_status, n, n_img, *kind.surf, ec,
                               (sf_keypoint*)c->ex_kpts.p, (float*)c->ex_desc.p, (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p, B);

@@ -1,0 +1,760 @@
+// k_sift.hip -- SIFT of the keyframe front end (Vis/FeatureType 1; sf_detect_sift_device, k_sift_describe under
+// sf_extract_keyframe_device): cv::xfeatures2d::SIFT of OpenCV 3.2 as rtabmap drives it, float32 rows of 128 dimensions.  opencv_contrib is not in the reference tree; the algorithm is restated in DESIGN.md section 3 item 17i
+// and in tests/sift_ref.py, which the tests compare with byte for byte.  Arithmetic: the float operations in the order
+// written, no contraction (compiled with -ffp-contract=off); the planes are int16 fixed point of scale 48; the sigma and
+// kernel tables are host arithmetic in double (sf_sift_build_tables); the Gaussian weights of orientation and descriptor go
+// through sift_exp (double + - x and exponent arithmetic only); histogram votes are summed as integers, so no kernel
+// has a summation order to keep.
+//
+//   k_sift_base       uint8 -> x 48 -> 2 x bilinear enlargement (weights 1/4, 3/4, clamped edges): 3 (wx wy v ...) with
+//                     w in {1, 3} is an integer, nothing is rounded
+//   k_sift_blur_rows  int16 -> float32, k_sift_blur_cols float32 -> int16 (cvRound, saturated): one thread per sample, the
+//                     taps in index order, BORDER_REFLECT_101 reflected repeatedly (the top octaves are a few pixels wide);
+//                     the kernel length is a launch argument, the coefficients sit in a device table
+//   k_sift_half       every second pixel of Gaussian plane n -> plane 0 of the next octave
+//   k_sift_dog        plane l + 1 - plane l, all n + 2 planes of an octave in one launch
+//   k_sift_extrema    one thread per sample of DoG planes 1 .. n of all octaves (blockIdx.y = octave n + layer - 1):
+//                     contrast floor, the 26-neighbour test, adjustLocalExtrema.  A survivor claims its CONVERGED sample in
+//                     a bitmap (atomicOr): two candidates that converge to one sample give bit-identical keypoints, the
+//                     first claim appends the sample to the list (wave-aggregated), the second does nothing -- whichever
+//                     comes first, the list holds the same set
+//   k_sift_orient     one wavefront per listed sample: the refinement again (it converges at once: the sample is the one
+//                     the loop ended on), the 36-bin histogram as 64-bit integers in LDS, smoothing, one sort key per
+//                     peak: response bits << 32 | ~(sample << 6 | bin)
+//   k_surf_rekey's twin, sf_sort_keys (sf_sort.hip), then
+//   k_sift_emit       one wavefront per sorted key: refinement and histogram again, the lane of the key's bin writes the
+//                     keypoint
+//   k_sift_describe   (Vis/FeatureType 1) one workgroup of 256 per given keypoint: calcSIFTDescriptor on the Gaussian plane the
+//                     keypoint's octave field names.  The window's samples are spread over the threads; a sample's 8
+//                     trilinear votes (float32 as upstream) go as rint(vote 2^20) into 360 64-bit bins in LDS (ds_add_u64:
+//                     integers, so no order to keep); the orientation wrap is folded in integers, a bin goes back to
+//                     float32 once; then a thread per dimension adds the 128 float32 squares in index order in float64,
+//                     clamps at 0.2 of the norm, adds again and scales to 0 .. 255.  Thread 0 does the 3D point
+//                     (extract_point).  LDS: 2880 + 512 bytes.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "sf_extract_device.hpp"
+#include "sf_front_device.hpp"
+
+namespace {
+
+constexpr int SIFT_BORDER = 5, SIFT_STEPS = 5, SIFT_BINS = 36;
+constexpr float SIFT_IMG_SCALE = 1.0f / (255 * 48);
+constexpr double SIFT_VOTE_SCALE = 1048576.0;       // votes are summed as rint(vote 2^20) in 64-bit integers
+
+__device__ __forceinline__ short sift_sat16(float v) {
+  const float r = rintf(v);
+  return (short)(r < -32768.0f ? -32768.0f : (r > 32767.0f ? 32767.0f : r));
+}
+
+// exp(x) from double + - x, rint and ldexp only (tests/sift_ref.py sift_exp64); the callers round to float once
+__device__ __forceinline__ double sift_exp64(double x) {
+  if (x < -700.0) return 0.0;
+  const double k = rint(x * 1.4426950408889634);
+  const double r = (x - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10;
+  double p = 1.0 / 479001600.0;
+  p = p * r + 1.0 / 39916800.0;
+  p = p * r + 1.0 / 3628800.0;
+  p = p * r + 1.0 / 362880.0;
+  p = p * r + 1.0 / 40320.0;
+  p = p * r + 1.0 / 5040.0;
+  p = p * r + 1.0 / 720.0;
+  p = p * r + 1.0 / 120.0;
+  p = p * r + 1.0 / 24.0;
+  p = p * r + 1.0 / 6.0;
+  p = p * r + 1.0 / 2.0;
+  p = p * r + 1.0;
+  p = p * r + 1.0;
+  return ldexp(p, (int)k);
+}
+
+__global__ void __launch_bounds__(256)
+k_sift_base(const uint8_t* __restrict__ img, int pitch, int w, int h, short* __restrict__ out) {
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  const int W = 2 * w, H = 2 * h;
+  if (e >= (unsigned)W * (unsigned)H) return;
+  const int y = (int)(e / (unsigned)W), x = (int)(e - (unsigned)y * (unsigned)W);
+  const int kx = x >> 1, ky = y >> 1;
+  const bool ex = !(x & 1), ey = !(y & 1);
+  const int xa = min(max(ex ? kx - 1 : kx, 0), w - 1), xb = min(max(ex ? kx : kx + 1, 0), w - 1);
+  const int ya = min(max(ey ? ky - 1 : ky, 0), h - 1), yb = min(max(ey ? ky : ky + 1, 0), h - 1);
+  const int wxa = ex ? 1 : 3, wya = ey ? 1 : 3;
+  const uint8_t* ra = img + (size_t)ya * pitch;
+  const uint8_t* rb = img + (size_t)yb * pitch;
+  const int top = ra[xa] * wxa + ra[xb] * (4 - wxa), bot = rb[xa] * wxa + rb[xb] * (4 - wxa);
+  out[e] = (short)(3 * (top * wya + bot * (4 - wya)));
+}
+
+__global__ void __launch_bounds__(256)
+k_sift_blur_rows(const short* __restrict__ in, float* __restrict__ tmp, int w, int h, const float* __restrict__ coef, int klen) {
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= (unsigned)w * (unsigned)h) return;
+  const int y = (int)(e / (unsigned)w), x = (int)(e - (unsigned)y * (unsigned)w);
+  const int r = klen >> 1;
+  const short* row = in + (size_t)y * w;
+  float s;
+  if (x - r >= 0 && x + r < w) {
+    s = (float)row[x - r] * coef[0];
+    for (int t = 1; t < klen; ++t) s += (float)row[x - r + t] * coef[t];
+  } else {
+    s = (float)row[reflect101(x - r, w)] * coef[0];
+    for (int t = 1; t < klen; ++t) s += (float)row[reflect101(x - r + t, w)] * coef[t];
+  }
+  tmp[e] = s;
+}
+
+__global__ void __launch_bounds__(256)
+k_sift_blur_cols(const float* __restrict__ tmp, short* __restrict__ out, int w, int h, const float* __restrict__ coef, int klen) {
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= (unsigned)w * (unsigned)h) return;
+  const int y = (int)(e / (unsigned)w), x = (int)(e - (unsigned)y * (unsigned)w);
+  const int r = klen >> 1;
+  float s;
+  if (y - r >= 0 && y + r < h) {
+    s = tmp[(size_t)(y - r) * w + x] * coef[0];
+    for (int t = 1; t < klen; ++t) s += tmp[(size_t)(y - r + t) * w + x] * coef[t];
+  } else {
+    s = tmp[(size_t)reflect101(y - r, h) * w + x] * coef[0];
+    for (int t = 1; t < klen; ++t) s += tmp[(size_t)reflect101(y - r + t, h) * w + x] * coef[t];
+  }
+  out[e] = sift_sat16(s);
+}
+
+__global__ void __launch_bounds__(256)
+k_sift_half(const short* __restrict__ in, int w_in, short* __restrict__ out, int w, int h) {
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= (unsigned)w * (unsigned)h) return;
+  const int y = (int)(e / (unsigned)w), x = (int)(e - (unsigned)y * (unsigned)w);
+  out[e] = in[(size_t)(2 * y) * w_in + 2 * x];
+}
+
+// d [n_dog planes] = g [plane + 1] - g [plane]; total = n_dog x plane samples
+__global__ void __launch_bounds__(256)
+k_sift_dog(const short* __restrict__ g, short* __restrict__ d, unsigned plane, unsigned total) {
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  if (e >= total) return;
+  const int v = (int)g[(size_t)e + plane] - (int)g[e];
+  d[e] = (short)min(max(v, -32768), 32767);
+}
+
+struct SiftPrm {
+  int n;                      // n_octave_layers
+  int floor_thr;              // floor(0.5 contrast_threshold / n * 255 * 48)
+  float contrast, edge, sigma;
+};
+
+// adjustLocalExtrema from sample (layer, r, c) of octave o: true when it converges and passes the contrast and edge tests;
+// layer, r, c then hold the converged sample, xc / xr / xi the offsets, contr the contrast
+__device__ __forceinline__ bool sift_refine(const SfSiftPlan& P, const short* __restrict__ dog, const SiftPrm& prm, int o, int& layer,
+                                            int& r, int& c, float& xc, float& xr, float& xi, float& contr) {
+  const int w = P.w[o], h = P.h[o];
+  const size_t plane = (size_t)w * h;
+  const short* D = dog + P.dog_off[o];
+  const float deriv = SIFT_IMG_SCALE * 0.5f, second = SIFT_IMG_SCALE, cross = SIFT_IMG_SCALE * 0.25f;
+  float d0 = 0.f, d1 = 0.f, d2 = 0.f, dxx = 0.f, dyy = 0.f, dxy = 0.f;
+  int centre = 0;
+  bool converged = false;
+  for (int step = 0; step < SIFT_STEPS; ++step) {
+    const short* img = D + (size_t)layer * plane + (size_t)r * w + c;
+    const short* prev = img - plane;
+    const short* next = img + plane;
+    centre = img[0];
+    d0 = (float)((int)img[1] - (int)img[-1]) * deriv;
+    d1 = (float)((int)img[w] - (int)img[-w]) * deriv;
+    d2 = (float)((int)next[0] - (int)prev[0]) * deriv;
+    const int v2 = 2 * centre;
+    dxx = (float)((int)img[1] + (int)img[-1] - v2) * second;
+    dyy = (float)((int)img[w] + (int)img[-w] - v2) * second;
+    const float dss = (float)((int)next[0] + (int)prev[0] - v2) * second;
+    dxy = (float)((int)img[w + 1] - (int)img[w - 1] - (int)img[-w + 1] + (int)img[-w - 1]) * cross;
+    const float dxs = (float)((int)next[1] - (int)next[-1] - (int)prev[1] + (int)prev[-1]) * cross;
+    const float dys = (float)((int)next[w] - (int)next[-w] - (int)prev[w] + (int)prev[-w]) * cross;
+    // H x = dD by Cramer's rule in the order of tests/surf_ref.py solve3; the offsets are -x
+    const float a00 = dxx, a01 = dxy, a02 = dxs, a10 = dxy, a11 = dyy, a12 = dys, a20 = dxs, a21 = dys, a22 = dss;
+    const float m0 = a11 * a22 - a12 * a21, m1 = a10 * a22 - a12 * a20, m2 = a10 * a21 - a11 * a20;
+    const float dt = (a00 * m0 - a01 * m1) + a02 * m2;
+    const float d = 1.0f / dt;
+    const float p = d1 * a22 - a12 * d2, q = d1 * a21 - a11 * d2, rr = a10 * d2 - d1 * a20;
+    xc = -(d * ((d0 * m0 - a01 * p) + a02 * q));
+    xr = -(d * ((a00 * p - d0 * m1) + a02 * rr));
+    xi = -(d * ((d0 * m2 - a01 * rr) - a00 * q));
+    if (fabsf(xc) < 0.5f && fabsf(xr) < 0.5f && fabsf(xi) < 0.5f) { converged = true; break; }
+    const float big = (float)(2147483647 / 3);
+    if (!(fabsf(xc) <= big && fabsf(xr) <= big && fabsf(xi) <= big)) return false;     // (NaN too)
+    c += (int)rintf(xc); r += (int)rintf(xr); layer += (int)rintf(xi);
+    if (layer < 1 || layer > prm.n || c < SIFT_BORDER || c >= w - SIFT_BORDER || r < SIFT_BORDER || r >= h - SIFT_BORDER) return false;
+  }
+  if (!converged) return false;
+  const float t = ((d0 * xc) + (d1 * xr)) + (d2 * xi);
+  contr = (float)centre * SIFT_IMG_SCALE + t * 0.5f;
+  if (fabsf(contr) * (float)prm.n < prm.contrast) return false;
+  const float tr = dxx + dyy, det = dxx * dyy - dxy * dxy;
+  const float e = prm.edge;
+  if (det <= 0.0f || (tr * tr) * e >= ((e + 1.0f) * (e + 1.0f)) * det) return false;
+  return true;
+}
+
+__global__ void __launch_bounds__(256)
+k_sift_extrema(SfSiftPlan P, const short* __restrict__ dog, SiftPrm prm, unsigned* __restrict__ claimed, unsigned* __restrict__ list,
+               unsigned* __restrict__ count, unsigned cap) {
+  const int o = blockIdx.y / prm.n, l0 = 1 + (int)blockIdx.y - o * prm.n;
+  const int w = P.w[o], h = P.h[o];
+  const unsigned e = blockIdx.x * 256u + threadIdx.x;
+  bool found = false;
+  unsigned pos = 0;
+  if (e < (unsigned)w * (unsigned)h) {                    // (uniform exit is not possible: the ballot below)
+    const int r0 = (int)(e / (unsigned)w), c0 = (int)(e - (unsigned)r0 * (unsigned)w);
+    if (r0 >= SIFT_BORDER && r0 < h - SIFT_BORDER && c0 >= SIFT_BORDER && c0 < w - SIFT_BORDER) {
+      const size_t plane = (size_t)w * h;
+      const short* ctr = dog + P.dog_off[o] + (size_t)l0 * plane + e;
+      const int v = ctr[0];
+      if (abs(v) > prm.floor_thr) {
+        bool is_max = v > 0, is_min = v < 0;
+#pragma unroll
+        for (int k = -1; k <= 1; ++k)
+#pragma unroll
+          for (int di = -1; di <= 1; ++di)
+#pragma unroll
+            for (int dj = -1; dj <= 1; ++dj) {
+              const int q = (ctr + (ptrdiff_t)k * (ptrdiff_t)plane)[di * w + dj];
+              is_max = is_max && v >= q;
+              is_min = is_min && v <= q;
+            }
+        if (is_max || is_min) {
+          int layer = l0, r = r0, c = c0;
+          float xc, xr, xi, contr;
+          if (sift_refine(P, dog, prm, o, layer, r, c, xc, xr, xi, contr)) {
+            pos = P.pos_off[o] + (unsigned)((size_t)layer * plane + (size_t)r * w + c);
+            const unsigned bit = 1u << (pos & 31u);
+            found = !(atomicOr(&claimed[pos >> 5], bit) & bit);
+          }
+        }
+      }
+    }
+  }
+  const unsigned long long bal = __ballot(found);
+  if (bal == 0ull) return;
+  const int lane = threadIdx.x & 63, leader = __ffsll((long long)bal) - 1;
+  unsigned base = 0u;
+  if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(bal));
+  base = (unsigned)__shfl((int)base, leader);
+  if (!found) return;
+  const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+  if (slot < cap) list[slot] = pos;                      // (the counter has counted it: the host refuses the image)
+}
+
+// One wavefront on the converged sample `pos`: the keypoint without its angle, and the smoothed histogram in hist[36]
+// (LDS, this wavefront's).  raw: this wavefront's 36 64-bit bins.  False when the refinement does not hold (never, for a
+// listed sample).
+__device__ __forceinline__ bool sift_keypoint(const SfSiftPlan& P, const short* __restrict__ gauss, const short* __restrict__ dog,
+                                              const SiftPrm& prm, unsigned pos, int lane, unsigned long long* raw, float* hist,
+                                              sf_keypoint* out) {
+  int o = 0;
+  while (o + 1 < P.n_octaves && pos >= P.pos_off[o + 1]) ++o;
+  const int w = P.w[o], h = P.h[o];
+  const unsigned plane = (unsigned)w * (unsigned)h, rel = pos - P.pos_off[o];
+  int layer = (int)(rel / plane);
+  const unsigned in_plane = rel - (unsigned)layer * plane;
+  int r = (int)(in_plane / (unsigned)w), c = (int)(in_plane - (unsigned)r * (unsigned)w);
+  if (layer < 1 || layer > prm.n || c < SIFT_BORDER || c >= w - SIFT_BORDER || r < SIFT_BORDER || r >= h - SIFT_BORDER) return false;
+  float xc, xr, xi, contr;
+  const int l_in = layer, r_in = r, c_in = c;
+  if (!sift_refine(P, dog, prm, o, layer, r, c, xc, xr, xi, contr)) return false;
+  if (layer != l_in || r != r_in || c != c_in) return false;
+  const float step = (float)(1 << o);
+  const float x = ((float)c + xc) * step, y = ((float)r + xr) * step;
+  const float t = ((float)layer + xi) / (float)prm.n;
+  const float p2 = (float)sift_exp64((double)t * 0.6931471805599453);
+  const float size = ((prm.sigma * p2) * step) * 2.0f;
+  const int octave = o + (layer << 8) + ((int)rintf((xi + 0.5f) * 255.0f) << 16);
+  out->x = x * 0.5f; out->y = y * 0.5f; out->size = size * 0.5f;
+  out->angle = -1.0f;
+  out->response = fabsf(contr);
+  out->octave = (octave & ~255) | ((octave - 1) & 255);
+  out->class_id = -1;
+  // calcOrientationHist on the keypoint's own Gaussian plane
+  const float scl = (size * 0.5f) / step;
+  const int radius = (int)rintf(4.5f * scl);
+  const float sigma = 1.5f * scl;
+  const float escale = -1.0f / ((2.0f * sigma) * sigma);
+  if (lane < SIFT_BINS) raw[lane] = 0ull;
+  __syncthreads();
+  const short* G = gauss + P.gauss_off[o] + (size_t)layer * plane;
+  const int side = 2 * radius + 1, samples = side * side;
+  for (int k = lane; k < samples; k += 64) {
+    const int i = k / side - radius, j = k - (k / side) * side - radius;
+    const int yy = r + i, xx = c + j;
+    if (yy <= 0 || yy >= h - 1 || xx <= 0 || xx >= w - 1) continue;
+    const short* g = G + (size_t)yy * w + xx;
+    const float dx = (float)((int)g[1] - (int)g[-1]), dy = (float)((int)g[-w] - (int)g[w]);
+    const float wt = (float)sift_exp64((double)((float)(i * i + j * j) * escale));
+    const float mag = sqrtf(dx * dx + dy * dy);
+    const float ang = sf_fast_atan2(dy, dx);
+    int bin = (int)rintf((float)(SIFT_BINS / 360.0) * ang);
+    if (bin >= SIFT_BINS) bin -= SIFT_BINS;
+    if (bin < 0) bin += SIFT_BINS;
+    const float vote = wt * mag;
+    atomicAdd(&raw[bin], (unsigned long long)llrint((double)vote * SIFT_VOTE_SCALE));
+  }
+  __syncthreads();
+  float tj = 0.0f;
+  if (lane < SIFT_BINS) {
+    tj = (float)((double)(long long)raw[lane] * (1.0 / SIFT_VOTE_SCALE));
+    hist[lane + SIFT_BINS] = tj;                        // hist[36 .. 71]: the unsmoothed bins
+  }
+  __syncthreads();
+  if (lane < SIFT_BINS) {
+    const float* u = hist + SIFT_BINS;
+    const int a2 = (lane + 34) % SIFT_BINS, a1 = (lane + 35) % SIFT_BINS, b1 = (lane + 1) % SIFT_BINS, b2 = (lane + 2) % SIFT_BINS;
+    hist[lane] = ((u[a2] + u[b2]) * (1.0f / 16.0f) + (u[a1] + u[b1]) * (4.0f / 16.0f)) + u[lane] * (6.0f / 16.0f);
+  }
+  __syncthreads();
+  return true;
+}
+
+// lane j < 36: whether bin j is a peak, and its angle
+__device__ __forceinline__ bool sift_peak(const float* hist, int j, float* angle) {
+  float omax = hist[0];
+  for (int k = 1; k < SIFT_BINS; ++k) omax = fmaxf(omax, hist[k]);
+  const float thr = omax * 0.8f;
+  const float l = hist[(j + 35) % SIFT_BINS], r2 = hist[(j + 1) % SIFT_BINS], v = hist[j];
+  if (!(v > l && v > r2 && v >= thr)) return false;
+  float b = (float)j + (0.5f * (l - r2)) / ((l - 2.0f * v) + r2);
+  b = b < 0.0f ? b + (float)SIFT_BINS : (b >= (float)SIFT_BINS ? b - (float)SIFT_BINS : b);
+  float a = 360.0f - (float)(360.0 / SIFT_BINS) * b;
+  if (fabsf(a - 360.0f) < FLT_EPSILON) a = 0.0f;
+  *angle = a;
+  return true;
+}
+
+// blocks of ONE wavefront: the __syncthreads() of sift_keypoint are this wavefront's own
+__global__ void __launch_bounds__(64)
+k_sift_orient(SfSiftPlan P, const short* __restrict__ gauss, const short* __restrict__ dog, SiftPrm prm,
+              const unsigned* __restrict__ list, unsigned n_list, unsigned long long* __restrict__ keys,
+              unsigned* __restrict__ count, unsigned cap) {
+  __shared__ unsigned long long raw[SIFT_BINS];
+  __shared__ float hist[2 * SIFT_BINS];
+  const unsigned item = blockIdx.x;
+  if (item >= n_list) return;
+  const int lane = threadIdx.x;
+  const unsigned pos = list[item];
+  sf_keypoint k;
+  if (!sift_keypoint(P, gauss, dog, prm, pos, lane, raw, hist, &k)) return;
+  float angle = 0.0f;
+  const bool peak = lane < SIFT_BINS && sift_peak(hist, lane, &angle);
+  const unsigned long long bal = __ballot(peak);
+  if (bal == 0ull) return;
+  const int leader = __ffsll((long long)bal) - 1;
+  unsigned base = 0u;
+  if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(bal));
+  base = (unsigned)__shfl((int)base, leader);
+  if (!peak) return;
+  const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+  if (slot >= cap) return;
+  keys[slot] = ((unsigned long long)__float_as_uint(k.response) << 32) | (unsigned long long)(0xFFFFFFFFu - ((pos << 6) | (unsigned)lane));
+}
+
+__global__ void __launch_bounds__(256)
+k_sift_rekey(unsigned long long* __restrict__ keys, unsigned n) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n) keys[i] ^= 0xFFFFFFFFull;
+}
+
+__global__ void __launch_bounds__(64)
+k_sift_emit(SfSiftPlan P, const short* __restrict__ gauss, const short* __restrict__ dog, SiftPrm prm,
+            const unsigned long long* __restrict__ keys, int total, int flipped, sf_keypoint* __restrict__ kp_out) {
+  __shared__ unsigned long long raw[SIFT_BINS];
+  __shared__ float hist[2 * SIFT_BINS];
+  const int item = blockIdx.x;
+  if (item >= total) return;
+  const int lane = threadIdx.x;
+  const unsigned low = (unsigned)keys[item];
+  const unsigned posbin = flipped ? low : 0xFFFFFFFFu - low;
+  const unsigned pos = posbin >> 6;
+  const int bin = (int)(posbin & 63u);
+  sf_keypoint k;
+  const bool ok = sift_keypoint(P, gauss, dog, prm, pos, lane, raw, hist, &k);
+  if (lane != bin) return;
+  float angle = 0.0f;
+  if (ok && bin < SIFT_BINS && sift_peak(hist, bin, &angle)) k.angle = angle;
+  else k = sf_make_keypoint(0.0f, 0.0f, 0.0f, 0.0f, 0);
+  kp_out[item] = k;
+}
+
+constexpr int SIFT_D = 4, SIFT_N = 8, SIFT_HIST = (SIFT_D + 2) * (SIFT_D + 2) * (SIFT_N + 2), SIFT_DIMS = SIFT_D * SIFT_D * SIFT_N;
+constexpr float SIFT_MAX_SIZE = 1.0e6f;             // keypoint sizes and coordinates beyond it are dropped
+
+__device__ __forceinline__ void sift_vote(unsigned long long* bins, int idx, float v) {
+  atomicAdd(&bins[idx], (unsigned long long)llrint((double)v * SIFT_VOTE_SCALE));
+}
+
+__global__ void __launch_bounds__(256)
+k_sift_describe(SfSiftPlan P, const short* __restrict__ gauss, const sf_keypoint* __restrict__ kpts, const float* __restrict__ right_x,
+                const uint8_t* __restrict__ status, int n, ExtractCam cam, sf_keypoint* __restrict__ kpts_out,
+                float* __restrict__ desc_tmp, float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep) {
+  __shared__ unsigned long long s_bins[SIFT_HIST];
+  __shared__ float s_row[SIFT_DIMS];
+  const int tid = threadIdx.x, i = blockIdx.x;
+  if (i >= n) return;                                // (the whole workgroup)
+  const sf_keypoint k = kpts[i];
+  // (every thread holds the same keypoint: the conditions around the barriers below are the same in every thread)
+  int o = k.octave & 255;
+  const int layer = (k.octave >> 8) & 255;
+  o = o < 128 ? o : o - 256;
+  const bool inside = o >= -1 && o + 1 < P.n_octaves && layer <= P.n_layers + 2 && k.size > 0.0f && k.size < SIFT_MAX_SIZE &&
+                      fabsf(k.x) < SIFT_MAX_SIZE && fabsf(k.y) < SIFT_MAX_SIZE && k.angle >= 0.0f && k.angle <= 360.0f;
+  for (int b = tid; b < SIFT_HIST; b += 256) s_bins[b] = 0ull;
+  __syncthreads();
+  if (inside) {
+    const float scale = o >= 0 ? 1.0f / (float)(1 << o) : (float)(1 << -o);
+    const int w = P.w[o + 1], h = P.h[o + 1];
+    const short* G = gauss + P.gauss_off[o + 1] + (size_t)layer * ((size_t)w * h);
+    const int px = (int)rintf(k.x * scale), py = (int)rintf(k.y * scale);
+    float ori = 360.0f - k.angle;
+    if (fabsf(ori - 360.0f) < FLT_EPSILON) ori = 0.0f;
+    const float scl = (k.size * scale) * 0.5f;
+    const float rad = ori * (float)(3.14159265358979323846 / 180.0);
+    float cos_t = (float)cos((double)rad), sin_t = (float)sin((double)rad);
+    const float bins_per_deg = (float)SIFT_N / 360.0f;
+    const float hist_width = 3.0f * scl;
+    int radius = (int)rintf(((hist_width * 1.4142135623730951f) * (float)(SIFT_D + 1)) * 0.5f);
+    radius = min(radius, (int)sqrt((double)w * w + (double)h * h));
+    cos_t /= hist_width; sin_t /= hist_width;
+    const long long side = 2ll * radius + 1, samples = side * side;
+    for (long long s = tid; s < samples; s += 256) {
+      const int si = (int)(s / side);
+      const int ii = si - radius, jj = (int)(s - (long long)si * side) - radius;
+      const float c_rot = (float)jj * cos_t - (float)ii * sin_t, r_rot = (float)jj * sin_t + (float)ii * cos_t;
+      float rbin = (r_rot + (float)(SIFT_D / 2)) - 0.5f, cbin = (c_rot + (float)(SIFT_D / 2)) - 0.5f;
+      const int r = py + ii, c = px + jj;
+      if (!(rbin > -1.0f && rbin < (float)SIFT_D && cbin > -1.0f && cbin < (float)SIFT_D && r > 0 && r < h - 1 && c > 0 && c < w - 1)) continue;
+      const short* g = G + (size_t)r * w + c;
+      const float dx = (float)((int)g[1] - (int)g[-1]), dy = (float)((int)g[-w] - (int)g[w]);
+      const float wt = (float)sift_exp64((double)((c_rot * c_rot + r_rot * r_rot) * -0.125f));
+      const float mag = sqrtf(dx * dx + dy * dy) * wt;
+      float obin = (sf_fast_atan2(dy, dx) - ori) * bins_per_deg;
+      const float fr = floorf(rbin), fc = floorf(cbin), fo = floorf(obin);
+      rbin -= fr; cbin -= fc; obin -= fo;
+      const int r0 = (int)fr, c0 = (int)fc;
+      int o0 = (int)fo;
+      if (o0 < 0) o0 += SIFT_N;
+      if (o0 >= SIFT_N) o0 -= SIFT_N;
+      if (o0 < 0 || o0 >= SIFT_N) continue;           // (not reached: both angles lie in [0, 360])
+      const float v_r1 = mag * rbin, v_r0 = mag - v_r1;
+      const float v_rc11 = v_r1 * cbin, v_rc10 = v_r1 - v_rc11;
+      const float v_rc01 = v_r0 * cbin, v_rc00 = v_r0 - v_rc01;
+      const float v111 = v_rc11 * obin, v110 = v_rc11 - v111;
+      const float v101 = v_rc10 * obin, v100 = v_rc10 - v101;
+      const float v011 = v_rc01 * obin, v010 = v_rc01 - v011;
+      const float v001 = v_rc00 * obin, v000 = v_rc00 - v001;
+      const int idx = ((r0 + 1) * (SIFT_D + 2) + c0 + 1) * (SIFT_N + 2) + o0;
+      constexpr int ROW = (SIFT_D + 2) * (SIFT_N + 2), COL = SIFT_N + 2;
+      sift_vote(s_bins, idx, v000); sift_vote(s_bins, idx + 1, v001);
+      sift_vote(s_bins, idx + COL, v010); sift_vote(s_bins, idx + COL + 1, v011);
+      sift_vote(s_bins, idx + ROW, v100); sift_vote(s_bins, idx + ROW + 1, v101);
+      sift_vote(s_bins, idx + ROW + COL, v110); sift_vote(s_bins, idx + ROW + COL + 1, v111);
+    }
+  }
+  __syncthreads();
+  float own = 0.0f;
+  if (tid < SIFT_DIMS) {
+    const int cell = tid >> 3, kk = tid & 7, ci = cell >> 2, cj = cell & 3;
+    const int idx = ((ci + 1) * (SIFT_D + 2) + cj + 1) * (SIFT_N + 2) + kk;
+    long long v = (long long)s_bins[idx];
+    if (kk < 2) v += (long long)s_bins[idx + SIFT_N];
+    own = (float)((double)v * (1.0 / SIFT_VOTE_SCALE));
+    s_row[tid] = own;
+  }
+  __syncthreads();
+  float val = 0.0f;
+  if (tid < SIFT_DIMS) {
+    double nrm2 = 0.0;
+    for (int q = 0; q < SIFT_DIMS; ++q) {
+      const float f = s_row[q];
+      nrm2 += (double)(f * f);
+    }
+    const float thr = (float)sqrt(nrm2) * 0.2f;
+    val = fminf(own, thr);
+  }
+  __syncthreads();
+  if (tid < SIFT_DIMS) s_row[tid] = val;
+  __syncthreads();
+  if (inside && tid < SIFT_DIMS) {
+    double nrm2 = 0.0;
+    for (int q = 0; q < SIFT_DIMS; ++q) {
+      const float f = s_row[q];
+      nrm2 += (double)(f * f);
+    }
+    const float scale = 512.0f / fmaxf((float)sqrt(nrm2), FLT_EPSILON);
+    const float r = rintf(val * scale);
+    desc_tmp[(size_t)i * SIFT_DIMS + tid] = r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r);
+  }
+  if (tid != 0) return;
+  kpts_out[i] = k;
+  extract_point(k, i, inside, right_x, status, cam, xyz_tmp, keep);
+}
+
+void sift_gaussian_kernel(double sigma, int* klen, float* coef) {
+  const int n = (int)std::nearbyint(sigma * 8.0 + 1.0) | 1;
+  *klen = n;
+  if (!coef) return;
+  const double scale = -0.5 / (sigma * sigma);
+  double sum = 0.0;
+  double t[SIFT_MAX_KLEN];
+  for (int i = 0; i < n; ++i) {
+    const double x = i - (n - 1) * 0.5;
+    t[i] = std::exp(scale * x * x);
+    sum += t[i];
+  }
+  for (int i = 0; i < n; ++i) coef[i] = (float)(t[i] / sum);
+}
+
+void sift_sigmas(const sf_sift_params& p, double* sig) {
+  const int n = p.n_octave_layers;
+  const double sigma = (double)p.sigma;
+  sig[0] = std::sqrt(std::max(sigma * sigma - 1.0, 0.01));
+  const double k = std::pow(2.0, 1.0 / n);
+  for (int i = 1; i < n + 3; ++i) {
+    const double prev = std::pow(k, (double)(i - 1)) * sigma, total = prev * k;
+    sig[i] = std::sqrt(total * total - prev * prev);
+  }
+}
+
+unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+extern "C" void sf_sift_defaults(sf_sift_params* p) {
+  if (!p) return;
+  p->n_features = 0;               // SIFT/NFeatures [upstream rtabmap Parameters.h]
+  p->n_octave_layers = 3;          // SIFT/NOctaveLayers
+  p->contrast_threshold = 0.04f;   // SIFT/ContrastThreshold
+  p->edge_threshold = 10.0f;       // SIFT/EdgeThreshold
+  p->sigma = 1.6f;                 // SIFT/Sigma
+}
+
+int sf_sift_validate(sf_context* c, const sf_sift_params& p) {
+  if (p.n_features < 0) return sf_fail(c, SF_EINVAL, "SIFT n_features %d: >= 0", p.n_features);
+  if (p.n_octave_layers < 1 || p.n_octave_layers > SIFT_MAX_LAYERS)
+    return sf_fail(c, SF_EINVAL, "SIFT n_octave_layers %d outside 1 .. %d", p.n_octave_layers, SIFT_MAX_LAYERS);
+  if (!std::isfinite(p.contrast_threshold) || !(p.contrast_threshold >= 0.0f))
+    return sf_fail(c, SF_EINVAL, "SIFT contrast_threshold %g: finite and >= 0", (double)p.contrast_threshold);
+  if (!std::isfinite(p.edge_threshold) || !(p.edge_threshold > 0.0f))
+    return sf_fail(c, SF_EINVAL, "SIFT edge_threshold %g: finite and > 0", (double)p.edge_threshold);
+  if (!std::isfinite(p.sigma) || !(p.sigma >= 0.8f && p.sigma <= 8.0f))
+    return sf_fail(c, SF_EINVAL, "SIFT sigma %g outside 0.8 .. 8", (double)p.sigma);
+  return SF_OK;
+}
+
+extern "C" int sf_sift_build_tables(const sf_sift_params* params, double* sigmas, int32_t* lengths, float* coef) {
+  sf_sift_params p;
+  if (params) p = *params; else sf_sift_defaults(&p);
+  const int rc = sf_sift_validate(nullptr, p);
+  if (rc != SF_OK) return rc;
+  double sig[SIFT_MAX_LAYERS + 3];
+  sift_sigmas(p, sig);
+  for (int i = 0; i < p.n_octave_layers + 3; ++i) {
+    int klen = 0;
+    if (coef) std::fill(coef + (size_t)i * SIFT_MAX_KLEN, coef + (size_t)(i + 1) * SIFT_MAX_KLEN, 0.0f);
+    sift_gaussian_kernel(sig[i], &klen, coef ? coef + (size_t)i * SIFT_MAX_KLEN : nullptr);
+    if (sigmas) sigmas[i] = sig[i];
+    if (lengths) lengths[i] = klen;
+  }
+  return SF_OK;
+}
+
+// The pyramid of a width x height image (host arithmetic; c may be null)
+int sf_sift_plan_host(sf_context* c, int width, int height, const sf_sift_params& p, SfSiftPlan* P) {
+  if (width < 3 || height < 3 || width > 16384 || height > 16384)
+    return sf_fail(c, width < 3 || height < 3 ? SF_EINVAL : SF_ERANGE, "SIFT: image %d x %d outside 3 .. 16384 a side", width, height);
+  *P = SfSiftPlan();
+  int w = 2 * width, h = 2 * height;
+  const int n_oct = (int)std::nearbyint(std::log((double)std::min(w, h)) / std::log(2.0) - 2.0) + 1;
+  if (n_oct < 1 || n_oct > SIFT_MAX_OCTAVES) return sf_fail(c, SF_ERANGE, "SIFT: %d octaves", n_oct);
+  P->n_octaves = n_oct;
+  P->n_layers = p.n_octave_layers;
+  unsigned long long g = 0, d = 0;
+  for (int o = 0; o < n_oct; ++o) {
+    P->w[o] = w; P->h[o] = h;
+    P->gauss_off[o] = g; P->dog_off[o] = d;
+    P->pos_off[o] = (unsigned)d;
+    const unsigned long long plane = (unsigned long long)w * h;
+    g += plane * (p.n_octave_layers + 3);
+    d += plane * (p.n_octave_layers + 2);
+    w /= 2; h /= 2;
+  }
+  for (int o = n_oct; o <= SIFT_MAX_OCTAVES; ++o) P->pos_off[o] = (unsigned)d;
+  P->gauss_samples = g; P->dog_samples = d;
+  if (d >= (1ull << 26))
+    return sf_fail(c, SF_ERANGE, "SIFT: %llu difference-of-Gaussian samples on %d x %d pixels (the sort key holds 2^26)", d, width, height);
+  return SF_OK;
+}
+
+extern "C" int sf_sift_plan(int32_t width, int32_t height, const sf_sift_params* params, int32_t* n_octaves_out, int32_t* widths,
+                            int32_t* heights, int64_t* gauss_samples_out, int64_t* dog_samples_out) {
+  sf_sift_params p;
+  if (params) p = *params; else sf_sift_defaults(&p);
+  int rc = sf_sift_validate(nullptr, p);
+  if (rc != SF_OK) return rc;
+  SfSiftPlan P;
+  if ((rc = sf_sift_plan_host(nullptr, width, height, p, &P)) != SF_OK) return rc;
+  if (n_octaves_out) *n_octaves_out = P.n_octaves;
+  for (int o = 0; o < SIFT_MAX_OCTAVES; ++o) {
+    if (widths) widths[o] = P.w[o];
+    if (heights) heights[o] = P.h[o];
+  }
+  if (gauss_samples_out) *gauss_samples_out = (int64_t)P.gauss_samples;
+  if (dog_samples_out) *dog_samples_out = (int64_t)P.dog_samples;
+  return SF_OK;
+}
+
+// The Gaussian and difference pyramids of an image into c->sift_planes, on the handle's stream; c->sift_last describes them
+int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const sf_sift_params* prm) {
+  SfSiftPlan P;
+  int rc;
+  c->sift_last_ok = false;
+  if ((rc = sf_sift_plan_host(c, width, height, *prm, &P)) != SF_OK) return rc;
+  const int n = prm->n_octave_layers;
+  const size_t base_samples = (size_t)P.w[0] * P.h[0];
+  const size_t claim_words = (size_t)((P.dog_samples + 31) / 32);
+  // sift_planes: Gaussian planes | DoG planes (int16) | the row pass's float32 plane | the claim bitmap
+  const size_t off_dog = ((size_t)P.gauss_samples * 2 + 255) & ~(size_t)255;
+  const size_t off_tmp = (off_dog + (size_t)P.dog_samples * 2 + 255) & ~(size_t)255;
+  const size_t off_claim = (off_tmp + base_samples * 4 + 255) & ~(size_t)255;
+  if ((rc = sf_buf_reserve(c, c->sift_planes, off_claim + claim_words * 4)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->sift_tables, (size_t)(SIFT_MAX_LAYERS + 3) * SIFT_MAX_KLEN * 4)) != SF_OK) return rc;
+  short* gauss = (short*)c->sift_planes.p;
+  short* dog = (short*)((uint8_t*)c->sift_planes.p + off_dog);
+  float* tmp = (float*)((uint8_t*)c->sift_planes.p + off_tmp);
+  unsigned* claimed = (unsigned*)((uint8_t*)c->sift_planes.p + off_claim);
+
+  // the kernel tables of this parameter set (host arithmetic; uploaded when the parameters change)
+  if (!c->sift_tables_ok || c->sift_tables_n != n || c->sift_tables_sigma != prm->sigma) {
+    c->sift_coef_host.assign((size_t)(SIFT_MAX_LAYERS + 3) * SIFT_MAX_KLEN, 0.0f);
+    if ((rc = sf_sift_build_tables(prm, nullptr, c->sift_klen, c->sift_coef_host.data())) != SF_OK) return rc;
+    SF_HIP(c, hipMemcpyAsync(c->sift_tables.p, c->sift_coef_host.data(), c->sift_coef_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+    c->sift_tables_ok = true; c->sift_tables_n = n; c->sift_tables_sigma = prm->sigma;
+  }
+  const float* coef = (const float*)c->sift_tables.p;
+
+  SF_HIP(c, hipMemsetAsync(claimed, 0, claim_words * 4, c->stream));
+  hipLaunchKernelGGL(k_sift_base, dim3(blocks_of(base_samples)), dim3(256), 0, c->stream, d_image, pitch, width, height, gauss);
+  for (int o = 0; o < P.n_octaves; ++o) {
+    const int w = P.w[o], h = P.h[o];
+    const size_t plane = (size_t)w * h;
+    short* g = gauss + P.gauss_off[o];
+    const unsigned nb = blocks_of(plane);
+    if (o > 0)
+      hipLaunchKernelGGL(k_sift_half, dim3(nb), dim3(256), 0, c->stream, (const short*)(gauss + P.gauss_off[o - 1] + (size_t)n * P.w[o - 1] * P.h[o - 1]),
+                         P.w[o - 1], g, w, h);
+    for (int i = (o == 0 ? 0 : 1); i < n + 3; ++i) {      // octave 0, i = 0: the enlarged image blurred in place
+      const short* src = i == 0 ? g : g + (size_t)(i - 1) * plane;
+      hipLaunchKernelGGL(k_sift_blur_rows, dim3(nb), dim3(256), 0, c->stream, src, tmp, w, h, coef + (size_t)i * SIFT_MAX_KLEN, c->sift_klen[i]);
+      hipLaunchKernelGGL(k_sift_blur_cols, dim3(nb), dim3(256), 0, c->stream, (const float*)tmp, g + (size_t)i * plane, w, h,
+                         coef + (size_t)i * SIFT_MAX_KLEN, c->sift_klen[i]);
+    }
+    hipLaunchKernelGGL(k_sift_dog, dim3(blocks_of(plane * (n + 2))), dim3(256), 0, c->stream, (const short*)g, dog + P.dog_off[o],
+                       (unsigned)plane, (unsigned)(plane * (n + 2)));
+  }
+  SF_HIP(c, hipGetLastError());
+  c->sift_last = P; c->sift_last_off_dog = off_dog; c->sift_last_off_claim = off_claim; c->sift_last_ok = true;
+  c->sift_last_prm = *prm; c->sift_last_width = width; c->sift_last_height = height;
+  return SF_OK;
+}
+
+// Launch sequence on the handle's stream.  Two counts cross to the host: the extrema (one wavefront each follows) and the
+// keypoints (the sort is sized by it; more than the key buffer holds is refused there).
+int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
+                          const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out) {
+  int rc;
+  // sift_keys: keys | sorted keys | the extrema list | two counters
+  if ((rc = sf_buf_reserve(c, c->sift_keys, (size_t)SIFT_MAX_CANDIDATES * 20 + 16)) != SF_OK) return rc;
+  if ((rc = sf_sift_build_pyramid(c, d_image, width, height, pitch, prm)) != SF_OK) return rc;
+  const SfSiftPlan P = c->sift_last;
+  const int n = prm->n_octave_layers;
+  const size_t base_samples = (size_t)P.w[0] * P.h[0];
+  short* gauss = (short*)c->sift_planes.p;
+  short* dog = (short*)((uint8_t*)c->sift_planes.p + c->sift_last_off_dog);
+  unsigned* claimed = (unsigned*)((uint8_t*)c->sift_planes.p + c->sift_last_off_claim);
+  unsigned long long* keys = (unsigned long long*)c->sift_keys.p;
+  unsigned long long* keys_sorted = keys + SIFT_MAX_CANDIDATES;
+  unsigned* list = (unsigned*)(keys_sorted + SIFT_MAX_CANDIDATES);
+  unsigned* count = list + SIFT_MAX_CANDIDATES;
+  const unsigned cand_cap = c->sift_debug_cap > 0 ? (unsigned)c->sift_debug_cap : SIFT_MAX_CANDIDATES;
+  SF_HIP(c, hipMemsetAsync(count, 0, 8, c->stream));
+
+  SiftPrm K;
+  K.n = n;
+  K.floor_thr = (int)std::floor(0.5 * (double)prm->contrast_threshold / n * 255 * 48);
+  K.contrast = prm->contrast_threshold; K.edge = prm->edge_threshold; K.sigma = prm->sigma;
+  hipLaunchKernelGGL(k_sift_extrema, dim3(blocks_of(base_samples), P.n_octaves * n), dim3(256), 0, c->stream, P, (const short*)dog, K,
+                     claimed, list, count, cand_cap);
+  SF_HIP(c, hipGetLastError());
+  unsigned n_ext = 0, h_count = 0;
+  if ((rc = sf_word_to_host(c, count, &n_ext)) != SF_OK) return rc;
+  if (n_ext > cand_cap)
+    return sf_fail(c, SF_ERANGE, "SIFT: %u extrema in a %d x %d image exceed the capacity %u; raise contrast_threshold", n_ext, width,
+                   height, cand_cap);
+  if (n_ext > 0) {
+    hipLaunchKernelGGL(k_sift_orient, dim3(n_ext), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
+                       (const unsigned*)list, n_ext, keys, count + 1, cand_cap);
+    SF_HIP(c, hipGetLastError());
+    if ((rc = sf_word_to_host(c, count + 1, &h_count)) != SF_OK) return rc;
+  }
+  if (h_count > cand_cap)
+    return sf_fail(c, SF_ERANGE, "SIFT: %u keypoints in a %d x %d image exceed the capacity %u; raise contrast_threshold", h_count,
+                   width, height, cand_cap);
+  const int total_found = (int)h_count;
+  int limit = 0;                                          // retainBest(n_features), limitKeypoints(max_features): one cut
+  if (prm->n_features > 0) limit = prm->n_features;
+  if (max_features > 0 && (limit == 0 || max_features < limit)) limit = max_features;
+  const bool cut = limit > 0 && total_found > limit;      // equal responses by descending position (sf_detect_fast_device)
+  const int total = cut ? limit : total_found, written = std::min(total, cap);
+  if (total_found > 0) {
+    if (cut) hipLaunchKernelGGL(k_sift_rekey, dim3(blocks_of(total_found)), dim3(256), 0, c->stream, keys, (unsigned)total_found);
+    if ((rc = sf_sort_keys(c, keys, keys_sorted, (size_t)total_found, 0, 64, true)) != SF_OK) return rc;
+    if (written > 0)
+      hipLaunchKernelGGL(k_sift_emit, dim3(written), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
+                         (const unsigned long long*)keys_sorted, written, cut ? 1 : 0, d_kpts_out);
+    SF_HIP(c, hipGetLastError());
+  }
+  if (n_out) *n_out = total;
+  return SF_OK;
+}
+
+// k_sift_describe for sf_launch_extract_batch (k_extract.hip), one image: the pyramid is the detector's when the full call
+// has just run it on this image with these parameters (reuse), else it is built here
+int sf_launch_sift_describe(sf_context* c, const uint8_t* d_left, int pitch, int width, int height, const SfSiftKind& kind,
+                            const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n, const ExtractCam& cam,
+                            sf_keypoint* d_kpts_out, float* desc_tmp, float* xyz_tmp, uint8_t* keep) {
+  const sf_sift_params& a = kind.prm;
+  const sf_sift_params& b = c->sift_last_prm;
+  const bool reuse = kind.reuse && c->sift_last_ok && c->sift_last_width == width && c->sift_last_height == height &&
+                     a.n_octave_layers == b.n_octave_layers && a.sigma == b.sigma;
+  int rc;
+  if (!reuse && (rc = sf_sift_build_pyramid(c, d_left, width, height, pitch, &kind.prm)) != SF_OK) return rc;
+  hipLaunchKernelGGL(k_sift_describe, dim3((unsigned)n), dim3(256), 0, c->stream, c->sift_last, (const short*)c->sift_planes.p, d_kpts,
+                     d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep);
+  return SF_OK;
+}
+
+// One plane of the most recent detector call -> d_out (int16, w x h of the octave, dense)
+int sf_sift_copy_plane(sf_context* c, int octave, int layer, int dog, int16_t* d_out) {
+  if (!c->sift_last_ok) return sf_fail(c, SF_EINVAL, "sf_debug_sift_plane: no SIFT detector call has built a pyramid on this handle");
+  const SfSiftPlan& P = c->sift_last;
+  const int planes = P.n_layers + (dog ? 2 : 3);
+  if (octave < 0 || octave >= P.n_octaves || layer < 0 || layer >= planes || !d_out)
+    return sf_fail(c, SF_EINVAL, "sf_debug_sift_plane: octave %d outside 0 .. %d or layer %d outside 0 .. %d", octave, P.n_octaves - 1, layer,
+                   planes - 1);
+  const size_t plane = (size_t)P.w[octave] * P.h[octave];
+  const uint8_t* base = (const uint8_t*)c->sift_planes.p + (dog ? c->sift_last_off_dog : 0);
+  const short* src = (const short*)base + (dog ? P.dog_off[octave] : P.gauss_off[octave]) + (size_t)layer * plane;
+  SF_HIP(c, hipMemcpyAsync(d_out, src, plane * 2, hipMemcpyDeviceToDevice, c->stream));
+  return SF_OK;
+}

@@ -1,7 +1,7 @@
 // sf_features.hip -- entry points of the feature front-end: BRIEF / ORB test tables, the FREAK tables, Vis/FeatureType, NetVLAD, corner
-// detection (GFTT, FAST, ORB, SURF), the ROI, the grid of cells and the sub-pixel refinement around it, stereo correspondence,
+// detection (GFTT, FAST, ORB, SURF, SIFT), the ROI, the grid of cells and the sub-pixel refinement around it, stereo correspondence,
 // keyframe extraction and the camera-image forms of these calls (kernels in k_extract.hip, k_gftt.hip, k_fast.hip,
-// k_orb_detect.hip, k_freak.hip, k_surf.hip, k_subpix.hip, k_grid.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in
+// k_orb_detect.hip, k_freak.hip, k_surf.hip, k_sift.hip, k_subpix.hip, k_grid.hip, k_lk.hip, k_stereo_bm.hip, k_cnn.hip, k_image.hip; the detectors' sort in
 // sf_sort.hip).
 #include <cmath>
 #include <vector>
@@ -165,8 +165,10 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
     case 5:
       return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d (%s/FREAK) takes parameters of its own: select it with sf_set_feature_type_freak",
                      feature_type, feature_type == 3 ? "FAST" : "GFTT");
+    case 1:
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType 1 (SIFT) takes parameters of its own and a handle with desc_type 1 and desc_bytes 512: select it with sf_set_feature_type_sift");
     default:
-      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (0 = SURF by sf_set_feature_type_surf, 2 = ORB by sf_set_feature_type_orb, 3 = FAST/FREAK and 5 = GFTT/FREAK by sf_set_feature_type_freak, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
+      return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (1 = SIFT by sf_set_feature_type_sift, 0 = SURF by sf_set_feature_type_surf, 2 = ORB by sf_set_feature_type_orb, 3 = FAST/FREAK and 5 = GFTT/FREAK by sf_set_feature_type_freak, 4 = FAST/BRIEF, 6 = GFTT/BRIEF, 8 = GFTT/ORB)",
                      feature_type);
   }
   c->feature_type = feature_type;
@@ -420,6 +422,58 @@ extern "C" int sf_detect_surf_device(sf_handle c, const uint8_t* d_image, int32_
   return sf_launch_detect_surf(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
 }
 
+// ---- the SIFT detector (kernels, tables and plan in k_sift.hip) ------------------------------------------------------------
+extern "C" int sf_sift_check_params(const sf_sift_params* params) {
+  return sf_sift_validate(nullptr, arg_or_defaults(params, sf_sift_defaults));
+}
+
+extern "C" int sf_set_feature_type_sift(sf_handle c, const sf_sift_params* sift) {
+  if (!c) return SF_EINVAL;
+  if (c->params.desc_type != 1 || c->params.desc_bytes != 512)
+    return sf_fail(c, SF_EINVAL, "SIFT writes 128 float32 per row: a handle with desc_type %d and desc_bytes %d cannot store them (create it with desc_type 1 and desc_bytes 512)",
+                   c->params.desc_type, c->params.desc_bytes);
+  const sf_sift_params p = arg_or_defaults(sift, sf_sift_defaults);
+  const int rc = sf_sift_validate(c, p);
+  if (rc != SF_OK) return rc;
+  c->sift = p;
+  c->feature_type = 1;
+  return SF_OK;
+}
+
+extern "C" int sf_get_sift_params(sf_handle c, sf_sift_params* out) {
+  if (!c || !out) return SF_EINVAL;
+  *out = c->sift;
+  return SF_OK;
+}
+
+extern "C" int sf_detect_sift_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                     int32_t max_features, const sf_sift_params* sift, sf_keypoint* d_kpts_out, int32_t cap,
+                                     int32_t* n_out) {
+  if (!c || !n_out || cap < 0 || (cap > 0 && !d_kpts_out)) return SF_EINVAL;
+  *n_out = 0;
+  int rc;
+  if ((rc = check_image(c, d_image, width, height, pitch, 3, "image")) != SF_OK) return rc;
+  const sf_sift_params prm = sift ? *sift : c->sift;
+  if ((rc = sf_sift_validate(c, prm)) != SF_OK) return rc;
+  if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_detect_sift(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
+}
+
+extern "C" int sf_debug_sift_limits(sf_handle c, int32_t candidate_cap) {
+  if (!c) return SF_EINVAL;
+  if (candidate_cap < 0 || (unsigned)candidate_cap > SIFT_MAX_CANDIDATES)
+    return sf_fail(c, SF_EINVAL, "sf_debug_sift_limits: candidate_cap %d outside 0 .. %u", candidate_cap, SIFT_MAX_CANDIDATES);
+  c->sift_debug_cap = candidate_cap;
+  return SF_OK;
+}
+
+extern "C" int sf_debug_sift_plane(sf_handle c, int32_t octave, int32_t layer, int32_t dog, int16_t* d_out) {
+  if (!c) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_sift_copy_plane(c, octave, layer, dog, d_out);
+}
+
 // The two Gaussian tables on the device, uploaded once: they depend on no parameter
 static int surf_ensure(sf_context* c) {
   c->surf_dev.upright = c->surf.upright;
@@ -442,6 +496,11 @@ static int surf_ensure(sf_context* c) {
 // The descriptor of the handle's feature type (ExtractKind: sf_internal.hpp)
 static int extract_kind(sf_context* c, ExtractKind* k) {
   int rc;
+  if (c->feature_type == 1) {                              // (selected on a handle with desc_type 1 and 512-byte rows only)
+    c->sift_kind = {c->sift, c->sift_reuse_pyramid};
+    *k = {512, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &c->sift_kind};
+    return SF_OK;
+  }
   if (c->feature_type == 0) {                              // (selected on a handle with desc_type 1 and these row bytes only)
     if ((rc = surf_ensure(c)) != SF_OK) return rc;
     *k = {c->surf.extended ? 512 : 256, nullptr, nullptr, nullptr, 0, nullptr, &c->surf_dev};
@@ -638,6 +697,8 @@ static int front_plan(sf_context* c, int width, int height, FrontPlan* fp) {
     return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 2 (ORB) is not built: the batch form reuses the detector's pyramid for the descriptors; set the ratios to 0 or choose feature type 3, 4, 5, 6 or 8");
   if (c->feature_type == 0 && (f.roi_ratios[0] != 0.f || f.roi_ratios[1] != 0.f || f.roi_ratios[2] != 0.f || f.roi_ratios[3] != 0.f))
     return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 0 (SURF) is not built; set the ratios to 0");
+  if (c->feature_type == 1 && (f.roi_ratios[0] != 0.f || f.roi_ratios[1] != 0.f || f.roi_ratios[2] != 0.f || f.roi_ratios[3] != 0.f))
+    return sf_fail(c, SF_EINVAL, "Vis/RoiRatios under Vis/FeatureType 1 (SIFT) is not built; set the ratios to 0");
   if (rc != SF_OK)
     return sf_fail(c, SF_EINVAL, "Vis/RoiRatios %g %g %g %g leave a ROI of %d x %d in a %d x %d image: both sides must be >= 3",
                    (double)f.roi_ratios[0], (double)f.roi_ratios[1], (double)f.roi_ratios[2], (double)f.roi_ratios[3], roi[2], roi[3], width, height);
@@ -703,6 +764,9 @@ static int grid_plan(sf_context* c, int width, int height, int max_features, Fro
                    g.grid_rows, g.grid_cols);
   if (c->feature_type == 0)
     return sf_fail(c, SF_EINVAL, "Vis/GridRows x Vis/GridCols %d x %d under Vis/FeatureType 0 (SURF) is not built; set the grid to 1 x 1",
+                   g.grid_rows, g.grid_cols);
+  if (c->feature_type == 1)
+    return sf_fail(c, SF_EINVAL, "Vis/GridRows x Vis/GridCols %d x %d under Vis/FeatureType 1 (SIFT) is not built; set the grid to 1 x 1",
                    g.grid_rows, g.grid_cols);
   int32_t o[6];
   const int rc = sf_compute_grid(width, height, c->front.roi_ratios, &g, max_features, o);
@@ -919,6 +983,7 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
     case 4: rc = sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
     case 2: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
     case 0: rc = sf_detect_surf_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;   // (no ROI: front_plan)
+    case 1: rc = sf_detect_sift_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;   // (likewise)
     default:
       rc = sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
   }
@@ -939,9 +1004,11 @@ static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* 
   float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
   sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
   int32_t slot = -1, rows = 0;
-  if ((rc = sf_extract_keyframe_device(c, d_left, width, height, width, d_kpts, d_rx, d_status, n, cam, &slot, &rows, d_desc,
-                                       d_xyz, d_kp_out)) != SF_OK)
-    return rc;
+  c->sift_reuse_pyramid = c->feature_type == 1;          // the detector's pyramid of this image: the refinement moved x and y only
+  rc = sf_extract_keyframe_device(c, d_left, width, height, width, d_kpts, d_rx, d_status, n, cam, &slot, &rows, d_desc, d_xyz,
+                                  d_kp_out);
+  c->sift_reuse_pyramid = false;
+  if (rc != SF_OK) return rc;
   *rows_out = rows;
   if (slot_out) *slot_out = slot;
   const int32_t k = std::min(rows, cap_rows);
@@ -997,6 +1064,8 @@ static int batch_check(sf_context* c, BatchFamily family, bool images, int n_key
   const bool orb_call = family == BATCH_ORB, surf_call = family == BATCH_SURF;
   if (c->feature_type == 2 && !orb_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has batch forms of its own: sf_get_features_and_descriptor_orb_batch_device, sf_add_keyframes_orb_u8_batch_device");
+  if (c->feature_type == 1)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 1 (SIFT): the batch form of type 1 is not built; use sf_get_features_and_descriptor or sf_extract_keyframe_device per keyframe");
   if (c->feature_type == 0 && !surf_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType 0 (SURF) has batch forms of its own: sf_get_features_and_descriptor_surf_batch_device, sf_add_keyframes_surf_u8_batch_device");
   if (c->feature_type != 2 && orb_call)

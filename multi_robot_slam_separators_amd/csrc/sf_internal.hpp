@@ -233,6 +233,24 @@ struct SfSurfBatchPlan {
 };
 constexpr size_t SURF_TABLE_ORI_W = 0, SURF_TABLE_DESC_W = 512, SURF_TABLE_ORI_XY = 2112, SURF_TABLE_BYTES = 2368;
 
+// The SIFT detector (k_sift.hip).  The pyramid of an image enlarged 2 x: octave o holds n_layers + 3 Gaussian planes of
+// w[o] x h[o] int16 from gauss_off[o] on and n_layers + 2 difference planes from dog_off[o] on (offsets in samples);
+// pos_off[o] = dog_off[o] as the 32-bit sample number the sort key carries (at most 2^26 samples: sf_sift_plan_host)
+constexpr int SIFT_MAX_OCTAVES = 16, SIFT_MAX_LAYERS = 8, SIFT_MAX_KLEN = 520;   // sigma <= 8: the longest kernel has 515 taps
+constexpr unsigned SIFT_MAX_CANDIDATES = 1u << 18;   // extrema, and keypoints, per image; more is SF_ERANGE
+// SIFT rows (type 1): the handle's parameters, and whether the pyramid the detector has just left is this image's
+struct SfSiftKind {
+  sf_sift_params prm;
+  bool reuse;
+};
+struct SfSiftPlan {
+  int n_octaves = 0, n_layers = 0;
+  int w[SIFT_MAX_OCTAVES] = {}, h[SIFT_MAX_OCTAVES] = {};
+  unsigned long long gauss_off[SIFT_MAX_OCTAVES] = {}, dog_off[SIFT_MAX_OCTAVES] = {};
+  unsigned pos_off[SIFT_MAX_OCTAVES + 1] = {};
+  unsigned long long gauss_samples = 0, dog_samples = 0;
+};
+
 struct sf_context {
   sf_params params;
   DeviceParams dparams;
@@ -311,6 +329,23 @@ struct sf_context {
   Buf surf_ctl;
   int surf_debug_cap = 0, surf_debug_chunk = 0;
   SfSurfTables surf_dev = {};
+  // the SIFT detector (sf_detect_sift_device; k_sift.hip).  sift_planes: the int16 Gaussian and difference planes of every
+  // octave, the row pass's float32 plane and the bitmap of claimed samples; sift_keys: sort keys, sorted keys, the list of
+  // extrema and two counters; sift_tables: the blur kernels of the parameter set last used (sift_klen their lengths).
+  // sift_last: the layout of the most recent call's pyramid (sf_debug_sift_plane); sift_debug_cap: sf_debug_sift_limits
+  sf_sift_params sift = {0, 3, 0.04f, 10.0f, 1.6f};
+  Buf sift_planes, sift_keys, sift_tables;
+  bool sift_tables_ok = false, sift_last_ok = false;
+  int sift_tables_n = 0, sift_debug_cap = 0;
+  float sift_tables_sigma = 0.0f;
+  int32_t sift_klen[SIFT_MAX_LAYERS + 3] = {};
+  std::vector<float> sift_coef_host;
+  SfSiftPlan sift_last;
+  size_t sift_last_off_dog = 0, sift_last_off_claim = 0;
+  sf_sift_params sift_last_prm = {};
+  int sift_last_width = 0, sift_last_height = 0;
+  SfSiftKind sift_kind = {};                   // what extract_kind hands the extraction under type 1
+  bool sift_reuse_pyramid = false;             // set by the full call between its detector and its extraction
   // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
   // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
   // the image at hand; orb_work: the detector's candidate lists
@@ -728,6 +763,7 @@ struct ExtractKind {
   size_t pyr_stride;
   const SfFreakTables* freak = nullptr;   // not null: FREAK rows (bytes 64; d_tests, orb and pyr unused)
   const SfSurfTables* surf = nullptr;     // not null: SURF rows (bytes 256 or 512, float32; the rest unused)
+  const SfSiftKind* sift = nullptr;       // not null: SIFT rows (bytes 512, float32; one image per call; the rest unused)
   // sf_launch_detect_surf_batch has left the integral images of the call's images in c->ex_integral: the extraction reads
   // them there and builds none (as pyr_stride for ORB's pyramids)
   bool integral_ready = false;
@@ -740,6 +776,13 @@ int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int 
 // the integral images of n_img images img_stride bytes apart into c->ex_integral, *s_stride entries apart (k_extract.hip)
 int sf_launch_integral_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                              int pitch, const int32_t** S_out, size_t* s_stride);
+// the SIFT detector + limitKeypoints (k_sift.hip); prm validated by the caller
+int sf_sift_validate(sf_context* c, const sf_sift_params& p);
+int sf_sift_plan_host(sf_context* c, int width, int height, const sf_sift_params& p, SfSiftPlan* P);
+int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
+                          const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
+int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const sf_sift_params* prm);
+int sf_sift_copy_plane(sf_context* c, int octave, int layer, int dog, int16_t* d_out);
 // the host arithmetic of SURF's batch form, no device call (c may be null); candidate_cap 0 = SURF_MAX_CANDIDATES,
 // forced_chunk 0 = what SURF_BATCH_WORKSPACE_BYTES allows
 int sf_surf_batch_plan_host(sf_context* c, int width, int height, const sf_surf_params& p, int n, unsigned candidate_cap,

@@ -118,6 +118,15 @@ def load():
         "sf_surf_batch_status": (C.c_int, [vp, P(i32)]),
         "sf_debug_surf_limits": (C.c_int, [vp, i32, i32]),
         "sf_surf_batch_plan": (C.c_int, [i32, i32, P(_abi.SurfParams), i32, P(i32), P(i32), P(i64)]),
+        "sf_sift_defaults": (None, [P(_abi.SiftParams)]),
+        "sf_set_feature_type_sift": (C.c_int, [vp, P(_abi.SiftParams)]),
+        "sf_get_sift_params": (C.c_int, [vp, P(_abi.SiftParams)]),
+        "sf_detect_sift_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.SiftParams), vp, i32, P(i32)]),
+        "sf_sift_check_params": (C.c_int, [P(_abi.SiftParams)]),
+        "sf_sift_build_tables": (C.c_int, [P(_abi.SiftParams), vp, vp, vp]),
+        "sf_sift_plan": (C.c_int, [i32, i32, P(_abi.SiftParams), P(i32), vp, vp, P(i64), P(i64)]),
+        "sf_debug_sift_limits": (C.c_int, [vp, i32]),
+        "sf_debug_sift_plane": (C.c_int, [vp, i32, i32, i32, vp]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
         "sf_stereo_flow_defaults": (None, [P(_abi.StereoFlowParams)]),
         "sf_detector_defaults": (None, [P(_abi.DetectorParams)]),
@@ -242,6 +251,8 @@ EXPORTED = [
     "sf_surf_check_params",
     "sf_get_features_and_descriptor_surf_batch_device", "sf_add_keyframes_surf_u8_batch_device", "sf_surf_batch_status",
     "sf_debug_surf_limits", "sf_surf_batch_plan",
+    "sf_sift_defaults", "sf_set_feature_type_sift", "sf_get_sift_params", "sf_detect_sift_device", "sf_sift_check_params", "sf_sift_build_tables", "sf_sift_plan",
+    "sf_debug_sift_limits", "sf_debug_sift_plane",
 ]
 
 
@@ -284,6 +295,31 @@ def surf_batch_plan(width, height, n_keyframes, surf=None):
     if rc != _abi.SF_OK:
         raise SepfinderError(rc, "sf_surf_batch_plan refuses %d x %d, %d keyframes" % (width, height, n_keyframes))
     return cap.value, chunk.value, ws.value
+
+
+def sift_build_tables(sift=None):
+    """sf_sift_build_tables (no GPU, no handle): (sigmas float64 [n + 3], lengths int32 [n + 3], coefficients float32
+    [n + 3, 520]) of the SIFT detector's blurs under sift (_abi.SiftParams; None = the defaults)."""
+    n = (sift.n_octave_layers if sift is not None else 3) + 3
+    rows = max(min(n, _abi.SIFT_MAX_LAYERS + 3), 4)
+    sig, klen = np.zeros(rows, np.float64), np.zeros(rows, np.int32)
+    coef = np.zeros((rows, _abi.SIFT_MAX_KLEN), np.float32)
+    rc = load().sf_sift_build_tables(C.byref(sift) if sift is not None else None, C.c_void_p(sig.ctypes.data),
+                                     C.c_void_p(klen.ctypes.data), C.c_void_p(coef.ctypes.data))
+    if rc != _abi.SF_OK:
+        raise SepfinderError(rc, "SIFT parameters out of range")
+    return sig[:n], klen[:n], coef[:n]
+
+
+def sift_plan(width, height, sift=None):
+    """sf_sift_plan (no GPU, no handle): (octaves, [(w, h)] per octave, Gaussian samples, difference samples)."""
+    n, g, d = C.c_int32(), C.c_int64(), C.c_int64()
+    w, h = np.zeros(_abi.SIFT_MAX_OCTAVES, np.int32), np.zeros(_abi.SIFT_MAX_OCTAVES, np.int32)
+    rc = load().sf_sift_plan(width, height, C.byref(sift) if sift is not None else None, C.byref(n), C.c_void_p(w.ctypes.data),
+                             C.c_void_p(h.ctypes.data), C.byref(g), C.byref(d))
+    if rc != _abi.SF_OK:
+        raise SepfinderError(rc, "sf_sift_plan refuses %d x %d" % (width, height))
+    return n.value, [(int(w[o]), int(h[o])) for o in range(n.value)], g.value, d.value
 
 
 def _ptr(a):
@@ -546,10 +582,39 @@ class SeparatorFinder:
                                                   C.byref(n)))
         return n.value
 
+    def set_feature_type_sift(self, sift=None):
+        """Vis/FeatureType 1 (SIFT) with sift (_abi.SiftParams; None = rtabmap's SIFT/ defaults) on a handle created with
+        desc_type 1 and desc_bytes 512: float32 rows of 128 dimensions."""
+        self._check(self._L.sf_set_feature_type_sift(self._h, C.byref(sift) if sift is not None else None))
+
+    def get_sift_params(self):
+        p = _abi.SiftParams()
+        self._check(self._L.sf_get_sift_params(self._h, C.byref(p)))
+        return p
+
+    def detect_sift(self, d_image, width, height, pitch, max_features, d_kpts_out, cap, sift=None):
+        """The SIFT detector + retainBest / rtabmap's limitKeypoints on the device (sift: _abi.SiftParams, None = the
+        handle's; any handle); returns the number of keypoints of the result (<= cap are written)."""
+        n = C.c_int32()
+        self._check(self._L.sf_detect_sift_device(self._h, C.c_void_p(d_image), width, height, pitch, max_features,
+                                                  C.byref(sift) if sift is not None else None, C.c_void_p(d_kpts_out), cap,
+                                                  C.byref(n)))
+        return n.value
+
+    def debug_sift_limits(self, candidate_cap=0):
+        """sf_debug_sift_limits (include/sf_experimental.h): the extrema / keypoint capacity per image; 0 = the default."""
+        self._check(self._L.sf_debug_sift_limits(self._h, candidate_cap))
+
+    def debug_sift_plane(self, octave, layer, dog, d_out):
+        """sf_debug_sift_plane: one int16 plane of the most recent detect_sift call's pyramid -> d_out (device pointer)."""
+        self._check(self._L.sf_debug_sift_plane(self._h, octave, layer, int(bool(dog)), C.c_void_p(d_out)))
+
     def descriptor_bytes(self):
         """Row bytes the extraction calls write with the handle's feature type."""
         if self.get_feature_type()[0] == _abi.FEATURE_SURF:
             return 512 if self.get_surf_params().extended else 256
+        if self.get_feature_type()[0] == _abi.FEATURE_SIFT:
+            return 512
         if self.get_feature_type()[0] in (_abi.FEATURE_FAST_FREAK, _abi.FEATURE_GFTT_FREAK):
             return _abi.FREAK_BYTES
         return 32 if self.get_feature_type()[0] in (_abi.FEATURE_GFTT_ORB, _abi.FEATURE_ORB) else self.brief_get_pattern().shape[0] // 8
