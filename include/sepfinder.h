@@ -96,6 +96,9 @@ extern "C" {
       (SIFT, Vis/FeatureType 1: float32 rows of 128 dimensions on a handle with desc_type 1 and desc_bytes 512; the single
       calls only).  sf_set_feature_type still refuses 1; nothing existing changed, the version number, sizeof(sf_params)
       and SF_K_COUNT stay.                                                                                             */
+/* 8, additions: sf_get_features_and_descriptor_sift_batch_device, sf_add_keyframes_sift_u8_batch_device,
+      sf_sift_batch_status (the batch forms of Vis/FeatureType 1).  The six existing batch calls still refuse a type-1
+      handle, now naming these; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.  */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -602,8 +605,9 @@ int  sf_detect_surf_device(sf_handle h, const uint8_t* d_image, int32_t width, i
    |y| is not below 1e6, or whose angle is not in [0, 360].  d_desc_out receives rows x 128 float32 through its uint8_t
    pointer.  3D points, the depth filter and the store slot are every other type's.
    sf_get_features_and_descriptor and its _u8 form run detector, sub-pixel refinement when it is on, LK or block matching,
-   extraction (which reuses the detector's pyramid).  NOT BUILT under type 1 and refused with SF_EINVAL: Vis/RoiRatios, a
-   grid of cells, and every batch call.                                                                                */
+   extraction (which reuses the detector's pyramid).  The batch forms are sf_get_features_and_descriptor_sift_batch_device
+   and sf_add_keyframes_sift_u8_batch_device; the batch calls of the other types refuse a type-1 handle (the batch form of
+   type 1 is not built into them).  NOT BUILT under type 1 and refused with SF_EINVAL: Vis/RoiRatios and a grid of cells. */
 typedef struct sf_sift_params {
   int32_t n_features;          /* SIFT/NFeatures, 0; >= 0                         */
   int32_t n_octave_layers;     /* SIFT/NOctaveLayers, 3; 1 .. 8                   */
@@ -803,9 +807,9 @@ int  sf_get_features_and_descriptor(sf_handle h, const uint8_t* left, const uint
    device outputs, each sized for n_keyframes x det->max_features rows (keyframe i at row i * max_features; any may be
    NULL): d_rows_out [n_keyframes] features kept, d_desc_out, d_xyz_out, d_kpts_out as in the single call.  Images up to
    about 1.2 Mpixel (the corner selection keeps its bitmap in LDS); no such limit under feature type 4.
-   Feature types 2 and 0 have batch calls of their own, sf_get_features_and_descriptor_orb_batch_device and
-   sf_get_features_and_descriptor_surf_batch_device: on a handle of either type this one returns SF_EINVAL, says so and
-   changes nothing.                                                                                                  */
+   Feature types 2, 0 and 1 have batch calls of their own, sf_get_features_and_descriptor_orb_batch_device,
+   sf_get_features_and_descriptor_surf_batch_device and sf_get_features_and_descriptor_sift_batch_device: on a handle of
+   one of these types this one returns SF_EINVAL, says so and changes nothing.                                                                                                 */
 int  sf_get_features_and_descriptor_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
                                                  int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                                  size_t image_stride, const sf_stereo_camera* cam,
@@ -857,6 +861,37 @@ int  sf_get_features_and_descriptor_surf_batch_device(sf_handle h, const uint8_t
    maxima than their key capacity and therefore hold no rows.  SF_OK when none did (and on a handle that has run no such
    call); SF_ERANGE when some did, with a message that says to raise hessian_threshold.  n_overflowed_out may be NULL.  */
 int  sf_surf_batch_status(sf_handle h, int32_t* n_overflowed_out);
+/* The same under Vis/FeatureType 1 (sf_set_feature_type_sift; the handle's SIFT parameters): arguments and outputs of
+   sf_get_features_and_descriptor_batch_device, and per keyframe the bytes of sf_get_features_and_descriptor under type 1
+   -- the row count, 128 float32 per row (d_desc_out receives them through its uint8_t pointer, keyframe i at row i *
+   max_features), 3D points with their NaNs, keypoints with all seven fields, the store slot.  One launch sequence with
+   no host wait.  The Gaussian planes the rows are computed from are too large to keep for a whole batch (23 MB per
+   752 x 480 image), so the WHOLE chain -- pyramid, extrema, orientation, the per-image decisions the single call takes
+   on the host (overflow, the one cut at the smaller of n_features and max_features with the order of equal responses
+   that goes with it), a segmented sort, the keypoints, sub-pixel refinement, LK or block matching, the rows -- runs over
+   chunks of images whose planes and keys fit a fixed workspace of 1 GB (one image always runs; the chunks are
+   consecutive launches on the handle's stream; every kernel of the pyramid takes the image of the chunk as a grid
+   dimension).  The one wait: when n_octave_layers or sigma differ from the blur tables on the handle, the tables are
+   uploaded before the first launch.
+   An image holds at most 262144 extrema and 262144 keypoints (no smaller bound is known: equal neighbours count as
+   extrema).  A keyframe with more of either is NOT truncated and does not fail the call, which cannot wait for the
+   count: it gets 0 rows and an empty store slot, and sf_sift_batch_status reports it.
+   Refusals, all before the first launch and without a change to the store, the NN database or the handle: what
+   sf_get_features_and_descriptor_batch_device refuses; Vis/RoiRatios and a grid (SF_EINVAL, "not built"); n_keyframes >
+   65535 (SF_ERANGE); what sf_detect_sift_device refuses (the parameter ranges, an image side outside 3 .. 16384, more
+   than 2^26 difference samples).  On a handle of any other feature type: SF_EINVAL, the message names the call to use.
+   n_keyframes = 0: SF_OK with *first_slot_out = sf_store_size.                                                        */
+int  sf_get_features_and_descriptor_sift_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right,
+                                                      int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                                      size_t image_stride, const sf_stereo_camera* cam,
+                                                      const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                      int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                      float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* Waits for the handle's stream and writes how many keyframes of the most recent SIFT batch call (either form) had more
+   extrema or keypoints than an image holds and therefore hold no rows.  SF_OK when none did (and on a handle that has
+   run no such call); SF_ERANGE when some did, with a message that says to raise contrast_threshold.  n_overflowed_out
+   may be NULL.                                                                                                        */
+int  sf_sift_batch_status(sf_handle h, int32_t* n_overflowed_out);
 
 /* ---- keyframes from the camera's own images (first step) ------------------------- */
 /* The reference keeps every image as cv_bridge's "rgb8" (data_handler.py:114-141).  For a keyframe it converts both stereo
@@ -944,6 +979,18 @@ int  sf_add_keyframes_orb_u8_batch_device(sf_handle h, const uint8_t* d_left, co
    by sf_surf_batch_status.  Refuses what either of the two refuses; on a handle of another feature type: SF_EINVAL,
    nothing changes.                                                                                                    */
 int  sf_add_keyframes_surf_u8_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+                                           int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                           size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
+                                           const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                           int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                           float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* The same under Vis/FeatureType 1: sf_add_keyframes_u8_batch_device with the feature stages of
+   sf_get_features_and_descriptor_sift_batch_device -- the same formats and gray rule, the same network call (both over
+   all n images, before the chunks of the feature stages), n store slots and n NN rows under one index, all or nothing.
+   Slot first_slot + i holds the bytes of sf_get_features_and_descriptor_u8 on pair i; a keyframe with more extrema or
+   keypoints than an image holds keeps its slot and its NN row, holds no rows, and is counted by sf_sift_batch_status.
+   Refuses what either of the two refuses; on a handle of another feature type: SF_EINVAL, nothing changes.            */
+int  sf_add_keyframes_sift_u8_batch_device(sf_handle h, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
                                            int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                            size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
                                            const sf_stereo_flow_params* flow, int32_t* first_slot_out,

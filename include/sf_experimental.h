@@ -130,8 +130,22 @@ int  sf_sift_build_tables(const sf_sift_params* params, double* sigmas, int32_t*
 int  sf_sift_plan(int32_t width, int32_t height, const sf_sift_params* params, int32_t* n_octaves_out, int32_t* widths,
                   int32_t* heights, int64_t* gauss_samples_out, int64_t* dog_samples_out);
 /* candidate_cap (0 = the default, at most 262144) takes the place of the 262144 extrema, and keypoints, an image may have
-   in sf_detect_sift_device (more: SF_ERANGE).  Out of range: SF_EINVAL, nothing changes.                           */
+   in sf_detect_sift_device (more: SF_ERANGE) and in every image of the batch forms (more: the keyframe holds no rows, see
+   sf_sift_batch_status).  Out of range: SF_EINVAL, nothing changes.                                                */
 int  sf_debug_sift_limits(sf_handle h, int32_t candidate_cap);
+/* batch_chunk (0 = what the 1 GB workspace allows, at most 65535) is the number of images the SIFT batch forms run per
+   chunk; a fresh handle behaves as if it had not been called.  Out of range: SF_EINVAL, nothing changes.           */
+int  sf_debug_sift_batch_chunk(sf_handle h, int32_t batch_chunk);
+/* The host arithmetic of the SIFT batch forms for n_keyframes images of width x height, without a GPU or a handle (params
+   NULL = the defaults).  With g, d the Gaussian and difference samples of sf_sift_plan, b the samples of the enlarged
+   image and a(x) = x rounded up to a multiple of 256, an image needs a(a(a(2 g) + 2 d) + 4 b) bytes of planes (Gaussian,
+   difference, the row pass's float32 plane), a(4 ceil(d / 32)) bytes of claim bits, 20 bytes per key (key, sorted key,
+   list entry) and 32 bytes of counters.  *cap_img_out = 262144 keys; *chunk_out = the images per chunk, min(n_keyframes,
+   65535, (2^31 - 1) / 262144, the 1 GB workspace / bytes per image), at least 1; *workspace_bytes_out = chunk x bytes
+   per image.  Any output may be NULL.  SF_EINVAL: parameters out of range, n_keyframes outside 1 .. 65535; otherwise what
+   sf_sift_plan refuses.                                                                                            */
+int  sf_sift_batch_plan(int32_t width, int32_t height, const sf_sift_params* params, int32_t n_keyframes,
+                        int32_t* cap_img_out, int32_t* chunk_out, int64_t* workspace_bytes_out);
 /* Copies one int16 plane of the pyramid the most recent sf_detect_sift_device call on this handle built to d_out (dense,
    the octave's width x height; on the handle's stream): dog = 0, layer 0 .. n_octave_layers + 2: a Gaussian plane;
    dog = 1, layer 0 .. n_octave_layers + 1: a difference plane.  A failing keypoint comparison can be narrowed to the

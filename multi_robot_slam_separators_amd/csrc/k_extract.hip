@@ -481,8 +481,9 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   if (kind.freak && (orb || bytes != FREAK_BYTES)) return sf_fail(c, SF_EINVAL, "FREAK rows are %d bytes, not %d", FREAK_BYTES, bytes);
   if (kind.surf && (orb || kind.freak || bytes != (kind.surf->extended ? 512 : 256)))
     return sf_fail(c, SF_EINVAL, "SURF rows are %d bytes, not %d", kind.surf->extended ? 512 : 256, bytes);
-  if (kind.sift && (orb || kind.freak || kind.surf || bytes != 512 || n_img != 1))
-    return sf_fail(c, SF_EINVAL, "SIFT rows are 512 bytes, one keyframe per call (not %d bytes, %d keyframes)", bytes, n_img);
+  if (kind.sift && (orb || kind.freak || kind.surf || bytes != 512 || (n_img != 1 && !kind.sift->batch)))
+    return sf_fail(c, SF_EINVAL, "SIFT rows are 512 bytes, one keyframe per call unless the detector has left the chunk's pyramids (not %d bytes, %d keyframes)",
+                   bytes, n_img);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_xyz, rows_all * 12)) != SF_OK) return rc;
@@ -535,9 +536,9 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
     const long long threads = (long long)n * bytes;
     if (kind.sift) {
       if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
-      if ((rc = sf_launch_sift_describe(c, d_left, pitch, width, height, *kind.sift, d_kpts, d_right_x, d_status, n, ec,
+      if ((rc = sf_launch_sift_describe(c, d_left, pitch, width, height, *kind.sift, d_kpts, d_right_x, d_status, n, n_img, ec,
                                         (sf_keypoint*)c->ex_kpts.p, (float*)c->ex_desc.p, (float*)c->ex_xyz.p,
-                                        (uint8_t*)c->ex_keep.p)) != SF_OK)
+                                        (uint8_t*)c->ex_keep.p, B)) != SF_OK)
         return rc;
       kp_commit = (const sf_keypoint*)c->ex_kpts.p;
     } else if (kind.surf) {                               // the keypoints with their angles, for the commit

@@ -21,7 +21,9 @@
 //   k_sift_orient     one wavefront per listed sample: the refinement again (it converges at once: the sample is the one
 //                     the loop ended on), the 36-bin histogram as 64-bit integers in LDS, smoothing, one sort key per
 //                     peak: response bits << 32 | ~(sample << 6 | bin)
-//   k_surf_rekey's twin, sf_sort_keys (sf_sort.hip), then
+//   k_sift_segments   (the batch form only) one thread per image of a chunk: what the single call decides on the host
+//                     between its launches -- overflow, the cut and its rekey flag, the image's sort segment, its row count
+//   k_surf_rekey's twin, sf_sort_keys or sf_sort_keys_segmented_desc (sf_sort.hip), then
 //   k_sift_emit       one wavefront per sorted key: refinement and histogram again, the lane of the key's bin writes the
 //                     keypoint
 //   k_sift_describe   (Vis/FeatureType 1) one workgroup of 256 per given keypoint: calcSIFTDescriptor on the Gaussian plane the
@@ -31,6 +33,8 @@
 //                     float32 once; then a thread per dimension adds the 128 float32 squares in index order in float64,
 //                     clamps at 0.2 of the norm, adds again and scales to 0 .. 255.  Thread 0 does the 3D point
 //                     (extract_point).  LDS: 2880 + 512 bytes.
+// Every kernel takes the image of a chunk as its last grid dimension (SiftBatch); the single calls run a chunk of one
+// through the same kernels, so the batch form (sf_launch_detect_sift_batch) has no arithmetic of its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +50,15 @@ namespace {
 constexpr int SIFT_BORDER = 5, SIFT_STEPS = 5, SIFT_BINS = 36;
 constexpr float SIFT_IMG_SCALE = 1.0f / (255 * 48);
 constexpr double SIFT_VOTE_SCALE = 1048576.0;       // votes are summed as rint(vote 2^20) in 64-bit integers
+
+// The batch form: every kernel below takes the image of the chunk as its last grid dimension and finds that image's data
+// these strides behind image 0's.  The single calls are a chunk of one: every stride 0.
+struct SiftBatch {
+  size_t img_stride;          // bytes between the uint8 images
+  size_t plane_stride;        // int16 samples between the images' plane blocks (Gaussian | difference | row plane)
+  size_t claim_stride;        // words between the claim bitmaps
+  size_t key_stride;          // entries between the images' keys, sorted keys and extrema lists
+};
 
 __device__ __forceinline__ short sift_sat16(float v) {
   const float r = rintf(v);
@@ -74,7 +87,8 @@ __device__ __forceinline__ double sift_exp64(double x) {
 }
 
 __global__ void __launch_bounds__(256)
-k_sift_base(const uint8_t* __restrict__ img, int pitch, int w, int h, short* __restrict__ out) {
+k_sift_base(const uint8_t* __restrict__ img, int pitch, int w, int h, short* __restrict__ out, SiftBatch B) {
+  img += blockIdx.z * B.img_stride; out += blockIdx.z * B.plane_stride;
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
   const int W = 2 * w, H = 2 * h;
   if (e >= (unsigned)W * (unsigned)H) return;
@@ -91,7 +105,9 @@ k_sift_base(const uint8_t* __restrict__ img, int pitch, int w, int h, short* __r
 }
 
 __global__ void __launch_bounds__(256)
-k_sift_blur_rows(const short* __restrict__ in, float* __restrict__ tmp, int w, int h, const float* __restrict__ coef, int klen) {
+k_sift_blur_rows(const short* __restrict__ in, float* __restrict__ tmp, int w, int h, const float* __restrict__ coef, int klen,
+                 SiftBatch B) {
+  in += blockIdx.z * B.plane_stride; tmp += blockIdx.z * (B.plane_stride / 2);   // (the stride counts int16 samples)
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
   if (e >= (unsigned)w * (unsigned)h) return;
   const int y = (int)(e / (unsigned)w), x = (int)(e - (unsigned)y * (unsigned)w);
@@ -109,7 +125,9 @@ k_sift_blur_rows(const short* __restrict__ in, float* __restrict__ tmp, int w, i
 }
 
 __global__ void __launch_bounds__(256)
-k_sift_blur_cols(const float* __restrict__ tmp, short* __restrict__ out, int w, int h, const float* __restrict__ coef, int klen) {
+k_sift_blur_cols(const float* __restrict__ tmp, short* __restrict__ out, int w, int h, const float* __restrict__ coef, int klen,
+                 SiftBatch B) {
+  tmp += blockIdx.z * (B.plane_stride / 2); out += blockIdx.z * B.plane_stride;
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
   if (e >= (unsigned)w * (unsigned)h) return;
   const int y = (int)(e / (unsigned)w), x = (int)(e - (unsigned)y * (unsigned)w);
@@ -126,7 +144,8 @@ k_sift_blur_cols(const float* __restrict__ tmp, short* __restrict__ out, int w, 
 }
 
 __global__ void __launch_bounds__(256)
-k_sift_half(const short* __restrict__ in, int w_in, short* __restrict__ out, int w, int h) {
+k_sift_half(const short* __restrict__ in, int w_in, short* __restrict__ out, int w, int h, SiftBatch B) {
+  in += blockIdx.z * B.plane_stride; out += blockIdx.z * B.plane_stride;
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
   if (e >= (unsigned)w * (unsigned)h) return;
   const int y = (int)(e / (unsigned)w), x = (int)(e - (unsigned)y * (unsigned)w);
@@ -135,7 +154,8 @@ k_sift_half(const short* __restrict__ in, int w_in, short* __restrict__ out, int
 
 // d [n_dog planes] = g [plane + 1] - g [plane]; total = n_dog x plane samples
 __global__ void __launch_bounds__(256)
-k_sift_dog(const short* __restrict__ g, short* __restrict__ d, unsigned plane, unsigned total) {
+k_sift_dog(const short* __restrict__ g, short* __restrict__ d, unsigned plane, unsigned total, SiftBatch B) {
+  g += blockIdx.z * B.plane_stride; d += blockIdx.z * B.plane_stride;
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
   if (e >= total) return;
   const int v = (int)g[(size_t)e + plane] - (int)g[e];
@@ -201,7 +221,9 @@ __device__ __forceinline__ bool sift_refine(const SfSiftPlan& P, const short* __
 
 __global__ void __launch_bounds__(256)
 k_sift_extrema(SfSiftPlan P, const short* __restrict__ dog, SiftPrm prm, unsigned* __restrict__ claimed, unsigned* __restrict__ list,
-               unsigned* __restrict__ count, unsigned cap) {
+               unsigned* __restrict__ count, unsigned cap, SiftBatch B) {
+  dog += blockIdx.z * B.plane_stride; claimed += blockIdx.z * B.claim_stride;
+  list += blockIdx.z * B.key_stride; count += blockIdx.z;
   const int o = blockIdx.y / prm.n, l0 = 1 + (int)blockIdx.y - o * prm.n;
   const int w = P.w[o], h = P.h[o];
   const unsigned e = blockIdx.x * 256u + threadIdx.x;
@@ -245,7 +267,7 @@ k_sift_extrema(SfSiftPlan P, const short* __restrict__ dog, SiftPrm prm, unsigne
   base = (unsigned)__shfl((int)base, leader);
   if (!found) return;
   const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-  if (slot < cap) list[slot] = pos;                      // (the counter has counted it: the host refuses the image)
+  if (slot < cap) list[slot] = pos;                      // (the counter has counted it: the image is refused, or marked as overflowed)
 }
 
 // One wavefront on the converged sample `pos`: the keypoint without its angle, and the smoothed histogram in hist[36]
@@ -332,46 +354,103 @@ __device__ __forceinline__ bool sift_peak(const float* hist, int j, float* angle
   return true;
 }
 
-// blocks of ONE wavefront: the __syncthreads() of sift_keypoint are this wavefront's own
+// What the single call decides on the host between its launches and the batch form per image on the device
+// (k_sift_segments), [images of the chunk] each; all null in the single call, which passes the scalars beside them
+struct SiftCounts {
+  const unsigned* n_list;     // k_sift_orient: the image's extrema (more than cap: none of them is read)
+  const unsigned* n_keys;     // k_sift_rekey: the image's keys, and
+  const unsigned* flipped;    // ... whether the cut at the limit rekeys them (k_sift_emit: how to read a key)
+  const int32_t* total;       // k_sift_emit: the image's keypoints behind the cut
+};
+
+// blocks of ONE wavefront: the __syncthreads() of sift_keypoint are this wavefront's own.  The wavefront takes the listed
+// samples blockIdx.x, + gridDim.x, ... : one apiece in the single call, whose grid is the list; the batch form bounds the grid
 __global__ void __launch_bounds__(64)
 k_sift_orient(SfSiftPlan P, const short* __restrict__ gauss, const short* __restrict__ dog, SiftPrm prm,
               const unsigned* __restrict__ list, unsigned n_list, unsigned long long* __restrict__ keys,
-              unsigned* __restrict__ count, unsigned cap) {
+              unsigned* __restrict__ count, unsigned cap, SiftCounts C, SiftBatch B) {
   __shared__ unsigned long long raw[SIFT_BINS];
   __shared__ float hist[2 * SIFT_BINS];
-  const unsigned item = blockIdx.x;
-  if (item >= n_list) return;
+  if (C.n_list) {
+    n_list = C.n_list[blockIdx.z];
+    if (n_list > cap) return;                          // (an overflowed image: its list is not whole)
+  }
+  gauss += blockIdx.z * B.plane_stride; dog += blockIdx.z * B.plane_stride;
+  list += blockIdx.z * B.key_stride; keys += blockIdx.z * B.key_stride; count += blockIdx.z;
   const int lane = threadIdx.x;
-  const unsigned pos = list[item];
-  sf_keypoint k;
-  if (!sift_keypoint(P, gauss, dog, prm, pos, lane, raw, hist, &k)) return;
-  float angle = 0.0f;
-  const bool peak = lane < SIFT_BINS && sift_peak(hist, lane, &angle);
-  const unsigned long long bal = __ballot(peak);
-  if (bal == 0ull) return;
-  const int leader = __ffsll((long long)bal) - 1;
-  unsigned base = 0u;
-  if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(bal));
-  base = (unsigned)__shfl((int)base, leader);
-  if (!peak) return;
-  const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-  if (slot >= cap) return;
-  keys[slot] = ((unsigned long long)__float_as_uint(k.response) << 32) | (unsigned long long)(0xFFFFFFFFu - ((pos << 6) | (unsigned)lane));
+  for (unsigned item = blockIdx.x; item < n_list; item += gridDim.x) {
+    const unsigned pos = list[item];
+    sf_keypoint k;
+    // (every lane holds the same sample: the conditions around the barriers are the same in every lane)
+    if (sift_keypoint(P, gauss, dog, prm, pos, lane, raw, hist, &k)) {
+      float angle = 0.0f;
+      const bool peak = lane < SIFT_BINS && sift_peak(hist, lane, &angle);
+      const unsigned long long bal = __ballot(peak);
+      if (bal != 0ull) {
+        const int leader = __ffsll((long long)bal) - 1;
+        unsigned base = 0u;
+        if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(bal));
+        base = (unsigned)__shfl((int)base, leader);
+        const unsigned slot = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+        if (peak && slot < cap)
+          keys[slot] = ((unsigned long long)__float_as_uint(k.response) << 32) |
+                       (unsigned long long)(0xFFFFFFFFu - ((pos << 6) | (unsigned)lane));
+      }
+    }
+    __syncthreads();                                   // the next sample's histogram goes where this one's was read
+  }
 }
 
+// (key, image) grid: a thread takes the keys blockIdx.x 256 + threadIdx.x, + gridDim.x 256, ... of its image
 __global__ void __launch_bounds__(256)
-k_sift_rekey(unsigned long long* __restrict__ keys, unsigned n) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) keys[i] ^= 0xFFFFFFFFull;
+k_sift_rekey(unsigned long long* __restrict__ keys, unsigned n, SiftCounts C, SiftBatch B) {
+  if (C.n_keys) {
+    if (!C.flipped[blockIdx.z]) return;
+    n = C.n_keys[blockIdx.z];
+  }
+  keys += blockIdx.z * B.key_stride;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) keys[i] ^= 0xFFFFFFFFull;
 }
 
+// One thread per image of the chunk: what sf_launch_detect_sift decides on the host.  n_ext / n_kp: the counters of
+// k_sift_extrema and k_sift_orient.  An image with more extrema or more keypoints than cap_img (as many is not more) is
+// never truncated: it gets an empty segment and no keypoint, and the call's counter counts it.  Otherwise the image's
+// keys are its segment of the segmented sort (bounds counted from the chunk's first key), and they are cut once, at the
+// smaller positive of n_features and max_features; a cut list is rekeyed first (k_sift_rekey: equal responses by
+// descending position).  total: the keypoints k_sift_emit writes, at most cap_rows.
+__global__ void __launch_bounds__(256)
+k_sift_segments(const unsigned* __restrict__ n_ext, unsigned* __restrict__ n_kp, int n_img, unsigned cap_img, size_t key_stride,
+                int n_features, int max_features, int cap_rows, unsigned* __restrict__ seg_begin, unsigned* __restrict__ seg_end,
+                unsigned* __restrict__ flipped, int32_t* __restrict__ total, unsigned* __restrict__ overflowed) {
+  const int img = blockIdx.x * 256 + threadIdx.x;
+  if (img >= n_img) return;
+  const bool over = n_ext[img] > cap_img || n_kp[img] > cap_img;
+  const unsigned n = over ? 0u : n_kp[img];
+  int limit = 0;
+  if (n_features > 0) limit = n_features;
+  if (max_features > 0 && (limit == 0 || max_features < limit)) limit = max_features;
+  const bool cut = limit > 0 && n > (unsigned)limit;
+  const unsigned begin = (unsigned)(img * key_stride);
+  seg_begin[img] = begin;
+  seg_end[img] = begin + n;
+  flipped[img] = cut ? 1u : 0u;
+  n_kp[img] = n;                                       // (what k_sift_rekey reads: nothing of an overflowed image)
+  total[img] = min((int)(cut ? (unsigned)limit : n), cap_rows);
+  if (over) atomicAdd(overflowed, 1u);
+}
+
+// (keypoint, image) grid of one-wavefront blocks
 __global__ void __launch_bounds__(64)
 k_sift_emit(SfSiftPlan P, const short* __restrict__ gauss, const short* __restrict__ dog, SiftPrm prm,
-            const unsigned long long* __restrict__ keys, int total, int flipped, sf_keypoint* __restrict__ kp_out) {
+            const unsigned long long* __restrict__ keys, int total, int flipped, sf_keypoint* __restrict__ kp_out, int kp_stride,
+            SiftCounts C, SiftBatch B) {
   __shared__ unsigned long long raw[SIFT_BINS];
   __shared__ float hist[2 * SIFT_BINS];
+  if (C.total) { total = C.total[blockIdx.z]; flipped = (int)C.flipped[blockIdx.z]; }
   const int item = blockIdx.x;
   if (item >= total) return;
+  gauss += blockIdx.z * B.plane_stride; dog += blockIdx.z * B.plane_stride;
+  keys += blockIdx.z * B.key_stride; kp_out += (size_t)blockIdx.z * kp_stride;
   const int lane = threadIdx.x;
   const unsigned low = (unsigned)keys[item];
   const unsigned posbin = flipped ? low : 0xFFFFFFFFu - low;
@@ -396,11 +475,21 @@ __device__ __forceinline__ void sift_vote(unsigned long long* bins, int idx, flo
 __global__ void __launch_bounds__(256)
 k_sift_describe(SfSiftPlan P, const short* __restrict__ gauss, const sf_keypoint* __restrict__ kpts, const float* __restrict__ right_x,
                 const uint8_t* __restrict__ status, int n, ExtractCam cam, sf_keypoint* __restrict__ kpts_out,
-                float* __restrict__ desc_tmp, float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep) {
+                float* __restrict__ desc_tmp, float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep, ExtractBatch B,
+                size_t plane_stride) {
   __shared__ unsigned long long s_bins[SIFT_HIST];
   __shared__ float s_row[SIFT_DIMS];
   const int tid = threadIdx.x, i = blockIdx.x;
+  if (B.d_n) n = min(n, B.d_n[blockIdx.y]);
   if (i >= n) return;                                // (the whole workgroup)
+  {                                                  // blockIdx.y = image: its pyramid plane_stride samples behind the first's
+    const size_t o = (size_t)blockIdx.y * B.per_image;
+    gauss += blockIdx.y * plane_stride;
+    kpts += o; kpts_out += o;
+    if (right_x) right_x += o;
+    if (status) status += o;
+    desc_tmp += o * SIFT_DIMS; xyz_tmp += 3 * o; keep += o;
+  }
   const sf_keypoint k = kpts[i];
   // (every thread holds the same keypoint: the conditions around the barriers below are the same in every thread)
   int o = k.octave & 255;
@@ -527,6 +616,18 @@ void sift_sigmas(const sf_sift_params& p, double* sig) {
 
 unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
+SiftPrm sift_kernel_params(const sf_sift_params& p) {
+  SiftPrm K;
+  K.n = p.n_octave_layers;
+  K.floor_thr = (int)std::floor(0.5 * (double)p.contrast_threshold / p.n_octave_layers * 255 * 48);
+  K.contrast = p.contrast_threshold; K.edge = p.edge_threshold; K.sigma = p.sigma;
+  return K;
+}
+
+// k_sift_orient in the batch form: this many one-wavefront blocks per image share the image's extrema (a few thousand on a
+// camera image), whose number stays on the device
+constexpr unsigned SIFT_ORIENT_BLOCKS = 1024;
+
 }  // namespace
 
 extern "C" void sf_sift_defaults(sf_sift_params* p) {
@@ -613,57 +714,94 @@ extern "C" int sf_sift_plan(int32_t width, int32_t height, const sf_sift_params*
   return SF_OK;
 }
 
-// The Gaussian and difference pyramids of an image into c->sift_planes, on the handle's stream; c->sift_last describes them
-int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const sf_sift_params* prm) {
-  SfSiftPlan P;
+// The host arithmetic of the batch form (no device, c may be null): the layout of one image's planes, claim bits, keys and
+// counters, and how many images fit SIFT_BATCH_WORKSPACE_BYTES.  An image's capacity is the candidate capacity: k_sift_extrema
+// takes >= plateaus, so no adjacency argument bounds the extrema of an image below its samples.
+int sf_sift_batch_plan_host(sf_context* c, int width, int height, const sf_sift_params& p, int n, unsigned candidate_cap,
+                            int forced_chunk, SfSiftBatchPlan* out) {
+  const int rc = sf_sift_plan_host(c, width, height, p, &out->P);
+  if (rc != SF_OK) return rc;
+  const SfSiftPlan& P = out->P;
+  const auto a256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  out->off_dog = a256((size_t)P.gauss_samples * 2);
+  out->off_tmp = a256(out->off_dog + (size_t)P.dog_samples * 2);
+  out->plane_bytes = a256(out->off_tmp + (size_t)P.w[0] * P.h[0] * 4);
+  out->claim_words = a256((size_t)((P.dog_samples + 31) / 32) * 4) / 4;
+  out->cap_img = candidate_cap == 0 ? SIFT_MAX_CANDIDATES : std::min(candidate_cap, SIFT_MAX_CANDIDATES);
+  // per image: the planes, the claim bits, key + sorted key + list entry per candidate, 32 bytes of counters and bounds
+  out->per_image = out->plane_bytes + out->claim_words * 4 + (size_t)out->cap_img * 20 + 32;
+  long long chunk = forced_chunk > 0 ? forced_chunk : (long long)(SIFT_BATCH_WORKSPACE_BYTES / out->per_image);
+  chunk = std::min<long long>(chunk, 0x7FFFFFFFll / out->cap_img);      // (the segmented sort counts its keys in 32 bits)
+  chunk = std::min<long long>(chunk, 65535);                            // (the image is a grid dimension)
+  out->chunk = (int)std::max<long long>(std::min<long long>(chunk, n), 1);
+  out->workspace_bytes = (size_t)out->chunk * out->per_image;
+  return SF_OK;
+}
+
+// the kernel tables of a parameter set (host arithmetic) on the device; uploaded, with a wait, when n_octave_layers or
+// sigma differ from the tables there
+static int sift_upload_tables(sf_context* c, const sf_sift_params* prm) {
   int rc;
-  c->sift_last_ok = false;
-  if ((rc = sf_sift_plan_host(c, width, height, *prm, &P)) != SF_OK) return rc;
-  const int n = prm->n_octave_layers;
-  const size_t base_samples = (size_t)P.w[0] * P.h[0];
-  const size_t claim_words = (size_t)((P.dog_samples + 31) / 32);
-  // sift_planes: Gaussian planes | DoG planes (int16) | the row pass's float32 plane | the claim bitmap
-  const size_t off_dog = ((size_t)P.gauss_samples * 2 + 255) & ~(size_t)255;
-  const size_t off_tmp = (off_dog + (size_t)P.dog_samples * 2 + 255) & ~(size_t)255;
-  const size_t off_claim = (off_tmp + base_samples * 4 + 255) & ~(size_t)255;
-  if ((rc = sf_buf_reserve(c, c->sift_planes, off_claim + claim_words * 4)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->sift_tables, (size_t)(SIFT_MAX_LAYERS + 3) * SIFT_MAX_KLEN * 4)) != SF_OK) return rc;
+  if (c->sift_tables_ok && c->sift_tables_n == prm->n_octave_layers && c->sift_tables_sigma == prm->sigma) return SF_OK;
+  c->sift_tables_ok = false;
+  c->sift_coef_host.assign((size_t)(SIFT_MAX_LAYERS + 3) * SIFT_MAX_KLEN, 0.0f);
+  if ((rc = sf_sift_build_tables(prm, nullptr, c->sift_klen, c->sift_coef_host.data())) != SF_OK) return rc;
+  SF_HIP(c, hipMemcpyAsync(c->sift_tables.p, c->sift_coef_host.data(), c->sift_coef_host.size() * 4, hipMemcpyHostToDevice, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  c->sift_tables_ok = true; c->sift_tables_n = prm->n_octave_layers; c->sift_tables_sigma = prm->sigma;
+  return SF_OK;
+}
+
+// The Gaussian and difference pyramids of m images (B.img_stride apart) into c->sift_planes, laid out by bp, and their
+// claim bitmaps cleared: one launch per plane and pass for all m images (blockIdx.z).  The tables on the handle are the
+// parameters' (sift_upload_tables).
+static int sift_launch_pyramids(sf_context* c, const SfSiftBatchPlan& bp, int n, const uint8_t* d_images, int width, int height,
+                                int pitch, int m, const SiftBatch& B) {
+  const SfSiftPlan& P = bp.P;
   short* gauss = (short*)c->sift_planes.p;
-  short* dog = (short*)((uint8_t*)c->sift_planes.p + off_dog);
-  float* tmp = (float*)((uint8_t*)c->sift_planes.p + off_tmp);
-  unsigned* claimed = (unsigned*)((uint8_t*)c->sift_planes.p + off_claim);
-
-  // the kernel tables of this parameter set (host arithmetic; uploaded when the parameters change)
-  if (!c->sift_tables_ok || c->sift_tables_n != n || c->sift_tables_sigma != prm->sigma) {
-    c->sift_coef_host.assign((size_t)(SIFT_MAX_LAYERS + 3) * SIFT_MAX_KLEN, 0.0f);
-    if ((rc = sf_sift_build_tables(prm, nullptr, c->sift_klen, c->sift_coef_host.data())) != SF_OK) return rc;
-    SF_HIP(c, hipMemcpyAsync(c->sift_tables.p, c->sift_coef_host.data(), c->sift_coef_host.size() * 4, hipMemcpyHostToDevice, c->stream));
-    SF_HIP(c, hipStreamSynchronize(c->stream));
-    c->sift_tables_ok = true; c->sift_tables_n = n; c->sift_tables_sigma = prm->sigma;
-  }
+  short* dog = (short*)((uint8_t*)c->sift_planes.p + bp.off_dog);
+  float* tmp = (float*)((uint8_t*)c->sift_planes.p + bp.off_tmp);
+  unsigned* claimed = (unsigned*)((uint8_t*)c->sift_planes.p + (size_t)bp.chunk * bp.plane_bytes);   // behind the chunk's planes
   const float* coef = (const float*)c->sift_tables.p;
-
-  SF_HIP(c, hipMemsetAsync(claimed, 0, claim_words * 4, c->stream));
-  hipLaunchKernelGGL(k_sift_base, dim3(blocks_of(base_samples)), dim3(256), 0, c->stream, d_image, pitch, width, height, gauss);
+  const unsigned z = (unsigned)m;
+  SF_HIP(c, hipMemsetAsync(claimed, 0, (size_t)m * bp.claim_words * 4, c->stream));
+  hipLaunchKernelGGL(k_sift_base, dim3(blocks_of((size_t)P.w[0] * P.h[0]), 1, z), dim3(256), 0, c->stream, d_images, pitch, width, height,
+                     gauss, B);
   for (int o = 0; o < P.n_octaves; ++o) {
     const int w = P.w[o], h = P.h[o];
     const size_t plane = (size_t)w * h;
     short* g = gauss + P.gauss_off[o];
     const unsigned nb = blocks_of(plane);
     if (o > 0)
-      hipLaunchKernelGGL(k_sift_half, dim3(nb), dim3(256), 0, c->stream, (const short*)(gauss + P.gauss_off[o - 1] + (size_t)n * P.w[o - 1] * P.h[o - 1]),
-                         P.w[o - 1], g, w, h);
+      hipLaunchKernelGGL(k_sift_half, dim3(nb, 1, z), dim3(256), 0, c->stream,
+                         (const short*)(gauss + P.gauss_off[o - 1] + (size_t)n * P.w[o - 1] * P.h[o - 1]), P.w[o - 1], g, w, h, B);
     for (int i = (o == 0 ? 0 : 1); i < n + 3; ++i) {      // octave 0, i = 0: the enlarged image blurred in place
       const short* src = i == 0 ? g : g + (size_t)(i - 1) * plane;
-      hipLaunchKernelGGL(k_sift_blur_rows, dim3(nb), dim3(256), 0, c->stream, src, tmp, w, h, coef + (size_t)i * SIFT_MAX_KLEN, c->sift_klen[i]);
-      hipLaunchKernelGGL(k_sift_blur_cols, dim3(nb), dim3(256), 0, c->stream, (const float*)tmp, g + (size_t)i * plane, w, h,
-                         coef + (size_t)i * SIFT_MAX_KLEN, c->sift_klen[i]);
+      hipLaunchKernelGGL(k_sift_blur_rows, dim3(nb, 1, z), dim3(256), 0, c->stream, src, tmp, w, h, coef + (size_t)i * SIFT_MAX_KLEN,
+                         c->sift_klen[i], B);
+      hipLaunchKernelGGL(k_sift_blur_cols, dim3(nb, 1, z), dim3(256), 0, c->stream, (const float*)tmp, g + (size_t)i * plane, w, h,
+                         coef + (size_t)i * SIFT_MAX_KLEN, c->sift_klen[i], B);
     }
-    hipLaunchKernelGGL(k_sift_dog, dim3(blocks_of(plane * (n + 2))), dim3(256), 0, c->stream, (const short*)g, dog + P.dog_off[o],
-                       (unsigned)plane, (unsigned)(plane * (n + 2)));
+    hipLaunchKernelGGL(k_sift_dog, dim3(blocks_of(plane * (n + 2)), 1, z), dim3(256), 0, c->stream, (const short*)g, dog + P.dog_off[o],
+                       (unsigned)plane, (unsigned)(plane * (n + 2)), B);
   }
   SF_HIP(c, hipGetLastError());
-  c->sift_last = P; c->sift_last_off_dog = off_dog; c->sift_last_off_claim = off_claim; c->sift_last_ok = true;
+  return SF_OK;
+}
+
+// The Gaussian and difference pyramids of an image into c->sift_planes, on the handle's stream; c->sift_last describes them
+int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const sf_sift_params* prm) {
+  SfSiftBatchPlan bp;
+  int rc;
+  c->sift_last_ok = false;
+  if ((rc = sf_sift_batch_plan_host(c, width, height, *prm, 1, 0, 1, &bp)) != SF_OK) return rc;   // a chunk of one
+  // sift_planes: Gaussian planes | DoG planes (int16) | the row pass's float32 plane | the claim bitmap
+  if ((rc = sf_buf_reserve(c, c->sift_planes, bp.plane_bytes + bp.claim_words * 4)) != SF_OK) return rc;
+  if ((rc = sift_upload_tables(c, prm)) != SF_OK) return rc;
+  const SiftBatch one = {0, 0, 0, 0};
+  if ((rc = sift_launch_pyramids(c, bp, prm->n_octave_layers, d_image, width, height, pitch, 1, one)) != SF_OK) return rc;
+  c->sift_last = bp.P; c->sift_last_off_dog = bp.off_dog; c->sift_last_off_claim = bp.plane_bytes; c->sift_last_ok = true;
   c->sift_last_prm = *prm; c->sift_last_width = width; c->sift_last_height = height;
   return SF_OK;
 }
@@ -689,12 +827,11 @@ int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int 
   const unsigned cand_cap = c->sift_debug_cap > 0 ? (unsigned)c->sift_debug_cap : SIFT_MAX_CANDIDATES;
   SF_HIP(c, hipMemsetAsync(count, 0, 8, c->stream));
 
-  SiftPrm K;
-  K.n = n;
-  K.floor_thr = (int)std::floor(0.5 * (double)prm->contrast_threshold / n * 255 * 48);
-  K.contrast = prm->contrast_threshold; K.edge = prm->edge_threshold; K.sigma = prm->sigma;
+  const SiftPrm K = sift_kernel_params(*prm);
+  const SiftBatch one = {0, 0, 0, 0};
+  const SiftCounts host = {nullptr, nullptr, nullptr, nullptr};   // the counts cross to the host below
   hipLaunchKernelGGL(k_sift_extrema, dim3(blocks_of(base_samples), P.n_octaves * n), dim3(256), 0, c->stream, P, (const short*)dog, K,
-                     claimed, list, count, cand_cap);
+                     claimed, list, count, cand_cap, one);
   SF_HIP(c, hipGetLastError());
   unsigned n_ext = 0, h_count = 0;
   if ((rc = sf_word_to_host(c, count, &n_ext)) != SF_OK) return rc;
@@ -703,7 +840,7 @@ int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int 
                    height, cand_cap);
   if (n_ext > 0) {
     hipLaunchKernelGGL(k_sift_orient, dim3(n_ext), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
-                       (const unsigned*)list, n_ext, keys, count + 1, cand_cap);
+                       (const unsigned*)list, n_ext, keys, count + 1, cand_cap, host, one);
     SF_HIP(c, hipGetLastError());
     if ((rc = sf_word_to_host(c, count + 1, &h_count)) != SF_OK) return rc;
   }
@@ -717,30 +854,113 @@ int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int 
   const bool cut = limit > 0 && total_found > limit;      // equal responses by descending position (sf_detect_fast_device)
   const int total = cut ? limit : total_found, written = std::min(total, cap);
   if (total_found > 0) {
-    if (cut) hipLaunchKernelGGL(k_sift_rekey, dim3(blocks_of(total_found)), dim3(256), 0, c->stream, keys, (unsigned)total_found);
+    if (cut)
+      hipLaunchKernelGGL(k_sift_rekey, dim3(blocks_of(total_found)), dim3(256), 0, c->stream, keys, (unsigned)total_found, host, one);
     if ((rc = sf_sort_keys(c, keys, keys_sorted, (size_t)total_found, 0, 64, true)) != SF_OK) return rc;
     if (written > 0)
       hipLaunchKernelGGL(k_sift_emit, dim3(written), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
-                         (const unsigned long long*)keys_sorted, written, cut ? 1 : 0, d_kpts_out);
+                         (const unsigned long long*)keys_sorted, written, cut ? 1 : 0, d_kpts_out, 0, host, one);
     SF_HIP(c, hipGetLastError());
   }
   if (n_out) *n_out = total;
   return SF_OK;
 }
 
-// k_sift_describe for sf_launch_extract_batch (k_extract.hip), one image: the pyramid is the detector's when the full call
-// has just run it on this image with these parameters (reuse), else it is built here
+// The plan of a batch under the handle's limits, its buffers and the blur tables.  sift_keys keeps room for the single
+// call's layout, which a call after the batch finds there.
+int sf_sift_batch_reserve(sf_context* c, int width, int height, const sf_sift_params& p, int n_img) {
+  SfSiftBatchPlan& bp = c->sift_batch;
+  int rc;
+  if ((rc = sf_sift_batch_plan_host(c, width, height, p, n_img, (unsigned)c->sift_debug_cap, c->sift_debug_chunk, &bp)) != SF_OK) return rc;
+  const size_t ctl_words = ((size_t)bp.chunk + 15) & ~(size_t)15;
+  if ((rc = sf_buf_reserve(c, c->sift_planes, (size_t)bp.chunk * (bp.plane_bytes + bp.claim_words * 4))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->sift_keys, std::max((size_t)bp.chunk * bp.cap_img * 20, (size_t)SIFT_MAX_CANDIDATES * 20 + 16))) != SF_OK)
+    return rc;
+  if ((rc = sf_buf_reserve(c, c->sift_ctl, 64 + 5 * ctl_words * sizeof(unsigned))) != SF_OK) return rc;
+  return sift_upload_tables(c, &p);
+}
+
+int sf_sift_batch_begin(sf_context* c) {
+  c->sift_last_ok = false;                               // (the chunks overwrite the single call's pyramid)
+  SF_HIP(c, hipMemsetAsync(c->sift_ctl.p, 0, 64, c->stream));
+  return SF_OK;
+}
+
+// The detector on one chunk of a batch with no host round trip.  What sf_launch_detect_sift reads on the host stays on the
+// device: k_sift_orient reads the image's extrema count and shares its list among SIFT_ORIENT_BLOCKS wavefronts,
+// k_sift_segments takes the decisions, the sort is segmented, k_sift_rekey and k_sift_emit exit past their image's counts.
+// sift_ctl from byte 64 on, [chunk] words each: extrema, keypoints, segment begin, segment end, rekey flag -- the two
+// counters are cleared per chunk, as the claim bitmaps are.
+int sf_launch_detect_sift_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                                int pitch, int max_features, const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap,
+                                int32_t* d_n_out) {
+  const SfSiftBatchPlan& bp = c->sift_batch;
+  const SfSiftPlan& P = bp.P;
+  const int n = prm->n_octave_layers, m = n_img;
+  const size_t ctl_words = ((size_t)bp.chunk + 15) & ~(size_t)15;
+  if (m < 1 || m > bp.chunk || P.w[0] != 2 * width || P.h[0] != 2 * height || P.n_layers != n || !c->sift_tables_ok ||
+      c->sift_tables_n != n || c->sift_tables_sigma != prm->sigma || max_features < 1 ||
+      c->sift_planes.bytes < (size_t)bp.chunk * (bp.plane_bytes + bp.claim_words * 4) ||
+      c->sift_keys.bytes < (size_t)bp.chunk * bp.cap_img * 20 || c->sift_ctl.bytes < 64 + 5 * ctl_words * sizeof(unsigned))
+    return sf_fail(c, SF_EINVAL, "SIFT batch: a chunk of %d images of %d x %d is not what sf_sift_batch_reserve has planned", m, width, height);
+  int rc;
+  const SiftBatch B = {img_stride, bp.plane_bytes / 2, bp.claim_words, bp.cap_img};
+  if ((rc = sift_launch_pyramids(c, bp, n, d_images, width, height, pitch, m, B)) != SF_OK) return rc;
+  short* gauss = (short*)c->sift_planes.p;
+  short* dog = (short*)((uint8_t*)c->sift_planes.p + bp.off_dog);
+  unsigned* claimed = (unsigned*)((uint8_t*)c->sift_planes.p + (size_t)bp.chunk * bp.plane_bytes);
+  unsigned long long* keys = (unsigned long long*)c->sift_keys.p;
+  unsigned long long* keys_sorted = keys + (size_t)bp.chunk * bp.cap_img;
+  unsigned* list = (unsigned*)(keys_sorted + (size_t)bp.chunk * bp.cap_img);
+  unsigned* overflowed = (unsigned*)c->sift_ctl.p;
+  unsigned *n_ext = overflowed + 16, *n_kp = n_ext + ctl_words, *seg_begin = n_kp + ctl_words, *seg_end = seg_begin + ctl_words,
+           *flipped = seg_end + ctl_words;
+  SF_HIP(c, hipMemsetAsync(n_ext, 0, 2 * ctl_words * sizeof(unsigned), c->stream));
+  const SiftPrm K = sift_kernel_params(*prm);
+  const SiftCounts C = {n_ext, n_kp, flipped, d_n_out};
+  const unsigned z = (unsigned)m;
+  const int rows = std::min(max_features, cap);
+  hipLaunchKernelGGL(k_sift_extrema, dim3(blocks_of((size_t)P.w[0] * P.h[0]), P.n_octaves * n, z), dim3(256), 0, c->stream, P,
+                     (const short*)dog, K, claimed, list, n_ext, bp.cap_img, B);
+  hipLaunchKernelGGL(k_sift_orient, dim3(std::min(SIFT_ORIENT_BLOCKS, bp.cap_img), 1, z), dim3(64), 0, c->stream, P, (const short*)gauss,
+                     (const short*)dog, K, (const unsigned*)list, 0u, keys, n_kp, bp.cap_img, C, B);
+  hipLaunchKernelGGL(k_sift_segments, dim3(blocks_of(m)), dim3(256), 0, c->stream, (const unsigned*)n_ext, n_kp, m, bp.cap_img,
+                     (size_t)bp.cap_img, prm->n_features, max_features, rows, seg_begin, seg_end, flipped, d_n_out, overflowed);
+  hipLaunchKernelGGL(k_sift_rekey, dim3(blocks_of(rows), 1, z), dim3(256), 0, c->stream, keys, 0u, C, B);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sf_sort_keys_segmented_desc(c, keys, keys_sorted, (unsigned)((size_t)m * bp.cap_img), (unsigned)m, seg_begin, seg_end, 0,
+                                        64)) != SF_OK)
+    return rc;
+  hipLaunchKernelGGL(k_sift_emit, dim3(rows, 1, z), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
+                     (const unsigned long long*)keys_sorted, 0, 0, d_kpts_out, cap, C, B);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+
+// k_sift_describe for sf_launch_extract_batch (k_extract.hip).  One image: the pyramid is the detector's when the full call
+// has just run it on this image with these parameters (reuse), else it is built here.  kind.batch: the n_img images of the
+// chunk sf_launch_detect_sift_batch has just run -- their pyramids are read where it left them.
 int sf_launch_sift_describe(sf_context* c, const uint8_t* d_left, int pitch, int width, int height, const SfSiftKind& kind,
-                            const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n, const ExtractCam& cam,
-                            sf_keypoint* d_kpts_out, float* desc_tmp, float* xyz_tmp, uint8_t* keep) {
+                            const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n, int n_img,
+                            const ExtractCam& cam, sf_keypoint* d_kpts_out, float* desc_tmp, float* xyz_tmp, uint8_t* keep,
+                            const ExtractBatch& B) {
   const sf_sift_params& a = kind.prm;
+  if (kind.batch) {
+    const SfSiftBatchPlan& bp = c->sift_batch;
+    if (n_img > bp.chunk || bp.P.w[0] != 2 * width || bp.P.h[0] != 2 * height || bp.P.n_layers != a.n_octave_layers ||
+        c->sift_planes.bytes < (size_t)bp.chunk * bp.plane_bytes)
+      return sf_fail(c, SF_EINVAL, "SIFT batch: the chunk's pyramids are not the detector's");
+    hipLaunchKernelGGL(k_sift_describe, dim3((unsigned)n, (unsigned)n_img), dim3(256), 0, c->stream, bp.P, (const short*)c->sift_planes.p,
+                       d_kpts, d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep, B, bp.plane_bytes / 2);
+    return SF_OK;
+  }
   const sf_sift_params& b = c->sift_last_prm;
   const bool reuse = kind.reuse && c->sift_last_ok && c->sift_last_width == width && c->sift_last_height == height &&
                      a.n_octave_layers == b.n_octave_layers && a.sigma == b.sigma;
   int rc;
   if (!reuse && (rc = sf_sift_build_pyramid(c, d_left, width, height, pitch, &kind.prm)) != SF_OK) return rc;
   hipLaunchKernelGGL(k_sift_describe, dim3((unsigned)n), dim3(256), 0, c->stream, c->sift_last, (const short*)c->sift_planes.p, d_kpts,
-                     d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep);
+                     d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep, B, (size_t)0);
   return SF_OK;
 }
 

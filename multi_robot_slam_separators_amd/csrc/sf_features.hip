@@ -468,6 +468,28 @@ extern "C" int sf_debug_sift_limits(sf_handle c, int32_t candidate_cap) {
   return SF_OK;
 }
 
+extern "C" int sf_debug_sift_batch_chunk(sf_handle c, int32_t batch_chunk) {
+  if (!c) return SF_EINVAL;
+  if (batch_chunk < 0 || batch_chunk > 65535)
+    return sf_fail(c, SF_EINVAL, "sf_debug_sift_batch_chunk: batch_chunk %d outside 0 .. 65535", batch_chunk);
+  c->sift_debug_chunk = batch_chunk;
+  return SF_OK;
+}
+
+extern "C" int sf_sift_batch_plan(int32_t width, int32_t height, const sf_sift_params* params, int32_t n_keyframes,
+                                  int32_t* cap_img_out, int32_t* chunk_out, int64_t* workspace_bytes_out) {
+  const sf_sift_params p = arg_or_defaults(params, sf_sift_defaults);
+  if (n_keyframes < 1 || n_keyframes > 65535) return SF_EINVAL;
+  int rc = sf_sift_validate(nullptr, p);
+  if (rc != SF_OK) return rc;
+  SfSiftBatchPlan sp;
+  if ((rc = sf_sift_batch_plan_host(nullptr, width, height, p, n_keyframes, 0, 0, &sp)) != SF_OK) return rc;
+  if (cap_img_out) *cap_img_out = (int32_t)sp.cap_img;
+  if (chunk_out) *chunk_out = sp.chunk;
+  if (workspace_bytes_out) *workspace_bytes_out = (int64_t)sp.workspace_bytes;
+  return SF_OK;
+}
+
 extern "C" int sf_debug_sift_plane(sf_handle c, int32_t octave, int32_t layer, int32_t dog, int16_t* d_out) {
   if (!c) return SF_EINVAL;
   SF_HIP(c, hipSetDevice(c->device));
@@ -1046,11 +1068,21 @@ extern "C" int sf_get_features_and_descriptor_u8(sf_handle c, const uint8_t* lef
 // extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
 // host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.
 // The batch form in three parts, shared by sf_get_features_and_descriptor_batch_device, sf_add_keyframes_u8_batch_device
-// and their Vis/FeatureType 2 and 0 twins (the _orb_ and _surf_ calls; `family`): batch_check refuses (nothing is touched;
-// n_keyframes = 0 passes without a look at the images), batch_reserve takes the store slots and the call's buffers,
-// batch_launch queues the three stages.  Types 2 and 0 are reached through their own calls only, as they are selected
-// through their own.
-enum BatchFamily { BATCH_GENERIC, BATCH_ORB, BATCH_SURF };
+// and their Vis/FeatureType 2, 0 and 1 twins (the _orb_, _surf_ and _sift_ calls; `family`): batch_check refuses (nothing is
+// touched; n_keyframes = 0 passes without a look at the images), batch_reserve takes the store slots and the call's buffers,
+// batch_launch queues the three stages (under type 1 chunk by chunk: batch_launch_sift).  Types 2, 0 and 1 are reached
+// through their own calls only, as they are selected through their own.
+enum BatchFamily { BATCH_GENERIC, BATCH_ORB, BATCH_SURF, BATCH_SIFT };
+
+// the batch calls of a feature type, for the message of a call that is not one of them
+static const char* batch_calls_of(int feature_type) {
+  switch (feature_type) {
+    case 2: return "sf_get_features_and_descriptor_orb_batch_device / sf_add_keyframes_orb_u8_batch_device";
+    case 0: return "sf_get_features_and_descriptor_surf_batch_device / sf_add_keyframes_surf_u8_batch_device";
+    case 1: return "sf_get_features_and_descriptor_sift_batch_device / sf_add_keyframes_sift_u8_batch_device";
+    default: return "sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device";
+  }
+}
 
 struct BatchPlan {
   sf_detector_params dp;
@@ -1061,21 +1093,22 @@ struct BatchPlan {
 
 static int batch_check(sf_context* c, BatchFamily family, bool images, int n_keyframes, int width, int height, int pitch,
                        size_t image_stride, const sf_detector_params* det, const sf_stereo_flow_params* flow, BatchPlan* plan) {
-  const bool orb_call = family == BATCH_ORB, surf_call = family == BATCH_SURF;
+  const bool orb_call = family == BATCH_ORB, surf_call = family == BATCH_SURF, sift_call = family == BATCH_SIFT;
   if (c->feature_type == 2 && !orb_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType 2 (ORB on a pyramid) has batch forms of its own: sf_get_features_and_descriptor_orb_batch_device, sf_add_keyframes_orb_u8_batch_device");
-  if (c->feature_type == 1)
-    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 1 (SIFT): the batch form of type 1 is not built; use sf_get_features_and_descriptor or sf_extract_keyframe_device per keyframe");
+  if (c->feature_type == 1 && !sift_call)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType 1 (SIFT): the batch form of type 1 is not built into this call: use %s", batch_calls_of(1));
   if (c->feature_type == 0 && !surf_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType 0 (SURF) has batch forms of its own: sf_get_features_and_descriptor_surf_batch_device, sf_add_keyframes_surf_u8_batch_device");
   if (c->feature_type != 2 && orb_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the ORB batch calls need type 2 (sf_set_feature_type_orb); use %s",
-                   c->feature_type, c->feature_type == 0 ? "sf_get_features_and_descriptor_surf_batch_device / sf_add_keyframes_surf_u8_batch_device"
-                                                         : "sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device");
+                   c->feature_type, batch_calls_of(c->feature_type));
   if (c->feature_type != 0 && surf_call)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the SURF batch calls need type 0 (sf_set_feature_type_surf); use %s",
-                   c->feature_type, c->feature_type == 2 ? "sf_get_features_and_descriptor_orb_batch_device / sf_add_keyframes_orb_u8_batch_device"
-                                                         : "sf_get_features_and_descriptor_batch_device / sf_add_keyframes_u8_batch_device");
+                   c->feature_type, batch_calls_of(c->feature_type));
+  if (c->feature_type != 1 && sift_call)
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the SIFT batch calls need type 1 (sf_set_feature_type_sift); use %s",
+                   c->feature_type, batch_calls_of(c->feature_type));
   if (n_keyframes == 0) return SF_OK;
   int rc = check_image(c, images, width, height, pitch, 3, "stereo pairs");
   if (rc != SF_OK) return rc;
@@ -1113,6 +1146,13 @@ static int batch_check(sf_context* c, BatchFamily family, bool images, int n_key
     SfSurfBatchPlan sp;                                  // (the layout's 2^31 plane samples)
     if ((rc = sf_surf_batch_plan_host(c, width, height, c->surf, n_keyframes, 0, 0, &sp)) != SF_OK) return rc;
   }
+  if (sift_call) {                                       // what sf_detect_sift_device refuses
+    if ((rc = sf_sift_validate(c, c->sift)) != SF_OK) return rc;
+    if ((rc = check_pixels(c, width, height)) != SF_OK) return rc;
+    if (n_keyframes > 65535) return sf_fail(c, SF_ERANGE, "SIFT batch of %d keyframes (at most 65535)", n_keyframes);
+    SfSiftBatchPlan sp;                                  // (the image's sides, the 2^26 difference samples)
+    if ((rc = sf_sift_batch_plan_host(c, width, height, c->sift, n_keyframes, 0, 0, &sp)) != SF_OK) return rc;
+  }
   return SF_OK;
 }
 
@@ -1131,6 +1171,64 @@ static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan*
     SfSurfBatchPlan sp;
     if ((rc = sf_surf_batch_reserve(c, width, height, c->surf, n, &sp)) != SF_OK) return rc;
   }
+  // the chunk's planes, keys and counters; the blur tables, uploaded with the call's one wait when they are not the handle's
+  if (c->feature_type == 1 && (rc = sf_sift_batch_reserve(c, width, height, c->sift, n)) != SF_OK) return rc;
+  return SF_OK;
+}
+
+// The stages behind the detector -- refinement, stereo correspondence, extraction -- for the m images from i0 on of a batch
+// of n whose keypoints and counts the detector has left in c->ft_kpts / c->ft_counts: every array at that sub-range, the
+// store slots from slot + i0 on.  The whole batch is i0 = 0, m = n; type 1 comes here chunk by chunk.
+static int batch_follow(sf_context* c, const BatchPlan& plan, const ExtractKind& kind, const uint8_t* d_left, const uint8_t* d_right,
+                        int n, int i0, int m, int width, int height, int pitch, size_t image_stride, const sf_stereo_camera* cam,
+                        int slot, int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  const int maxf = plan.front.rows_cap;
+  const size_t rows_all = (size_t)maxf * n, r0 = (size_t)maxf * i0;
+  const FrontPlan& fp = plan.front;
+  int rc;
+  d_left += (size_t)i0 * image_stride; d_right += (size_t)i0 * image_stride;
+  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p + r0;
+  const int32_t* d_n = (const int32_t*)c->ft_counts.p + i0;
+  if (fp.launch() &&
+      (rc = sf_launch_corner_subpix(c, d_left, image_stride, m, width, height, pitch, d_kpts, maxf, d_n, maxf, fp.off_x(), fp.off_y(),
+                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
+    return rc;
+  float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
+  float* d_rx = d_xy + 2 * rows_all;
+  uint8_t* d_status = (uint8_t*)(d_rx + rows_all);
+  d_xy += 2 * r0; d_rx += r0; d_status += r0;
+  rc = c->stereo.optical_flow
+           ? sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, m, width, height, pitch, d_kpts, maxf, d_n, &plan.prm, d_xy,
+                                         d_status, d_rx, nullptr)
+           : sf_launch_stereo_bm_batch(c, d_left, d_right, image_stride, m, width, height, pitch, d_kpts, maxf, d_n, &plan.prm,
+                                       c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
+  if (rc != SF_OK) return rc;
+  return sf_launch_extract_batch(c, d_left, image_stride, m, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, kind,
+                                 slot + i0, d_desc_out ? d_desc_out + r0 * kind.bytes : nullptr, d_xyz_out ? d_xyz_out + 3 * r0 : nullptr,
+                                 d_kpts_out ? d_kpts_out + r0 : nullptr, d_rows_out ? d_rows_out + i0 : nullptr);
+}
+
+// Vis/FeatureType 1: the Gaussian planes the rows are computed from are too large to keep for a whole batch, so detector
+// AND the stages behind it run chunk by chunk -- consecutive launches on the one stream, each chunk's extraction reading
+// the pyramids before the next chunk's detector overwrites them
+static int batch_launch_sift(sf_context* c, const BatchPlan& plan, const uint8_t* d_left, const uint8_t* d_right, int n, int width,
+                             int height, int pitch, size_t image_stride, const sf_stereo_camera* cam, int slot, int32_t* d_rows_out,
+                             uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  const int maxf = plan.front.rows_cap, chunk = c->sift_batch.chunk;
+  SfSiftKind sift = {c->sift, false, true};
+  ExtractKind kind = plan.kind;
+  kind.sift = &sift;
+  int rc;
+  if ((rc = sf_sift_batch_begin(c)) != SF_OK) return rc;
+  for (int i0 = 0; i0 < n; i0 += chunk) {
+    const int m = std::min(chunk, n - i0);
+    if ((rc = sf_launch_detect_sift_batch(c, d_left + (size_t)i0 * image_stride, image_stride, m, width, height, pitch, maxf, &c->sift,
+                                          (sf_keypoint*)c->ft_kpts.p + (size_t)i0 * maxf, maxf, (int32_t*)c->ft_counts.p + i0)) != SF_OK)
+      return rc;
+    if ((rc = batch_follow(c, plan, kind, d_left, d_right, n, i0, m, width, height, pitch, image_stride, cam, slot, d_rows_out,
+                           d_desc_out, d_xyz_out, d_kpts_out)) != SF_OK)
+      return rc;
+  }
   return SF_OK;
 }
 
@@ -1139,13 +1237,21 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
                         int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
   const sf_detector_params& dp = plan.dp;
   const int maxf = plan.front.rows_cap;                    // rows per keyframe, everywhere below: max_features, or R C quota
-  const size_t rows_all = (size_t)maxf * n;
+  const int slot = c->store.slots;
   int rc;
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t* d_n = (int32_t*)c->ft_counts.p;
   ExtractKind kind = plan.kind;
   const FrontPlan& fp = plan.front;
   const uint8_t* d_roi = d_left + (size_t)fp.y * pitch + fp.x;   // the detector's images: the ROI, at the parent's pitch and stride
+  if (c->feature_type == 1) {                            // (no ROI, no grid: front_plan, grid_plan)
+    if ((rc = batch_launch_sift(c, plan, d_left, d_right, n, width, height, pitch, image_stride, cam, slot, d_rows_out, d_desc_out,
+                                d_xyz_out, d_kpts_out)) != SF_OK)
+      return rc;
+    c->store.slots += n;
+    if (first_slot_out) *first_slot_out = slot;
+    return SF_OK;
+  }
   if (c->feature_type == 2) {                            // (keypoints in level-0 coordinates; the pyramids stay for the extraction;
     rc = sf_launch_detect_orb_batch(c, d_left, image_stride, n, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
     kind.pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;   // no ROI: front_plan)
@@ -1161,22 +1267,8 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
                                         dp.min_distance, d_kpts, maxf, d_n);
   }
   if (rc != SF_OK) return rc;
-  if (fp.launch() &&
-      (rc = sf_launch_corner_subpix(c, d_left, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, maxf, fp.off_x(), fp.off_y(),
-                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
-    return rc;
-  float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
-  float* d_rx = d_xy + 2 * rows_all;
-  uint8_t* d_status = (uint8_t*)(d_rx + rows_all);
-  rc = c->stereo.optical_flow
-           ? sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &plan.prm, d_xy,
-                                         d_status, d_rx, nullptr)
-           : sf_launch_stereo_bm_batch(c, d_left, d_right, image_stride, n, width, height, pitch, d_kpts, maxf, d_n, &plan.prm,
-                                       c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
-  if (rc != SF_OK) return rc;
-  const int slot = c->store.slots;
-  if ((rc = sf_launch_extract_batch(c, d_left, image_stride, n, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, kind,
-                                    slot, d_desc_out, d_xyz_out, d_kpts_out, d_rows_out)) != SF_OK)
+  if ((rc = batch_follow(c, plan, kind, d_left, d_right, n, 0, n, width, height, pitch, image_stride, cam, slot, d_rows_out, d_desc_out,
+                         d_xyz_out, d_kpts_out)) != SF_OK)
     return rc;
   c->store.slots += n;
   if (first_slot_out) *first_slot_out = slot;
@@ -1244,6 +1336,36 @@ extern "C" int sf_surf_batch_status(sf_handle c, int32_t* n_overflowed_out) {
   if (n_overflowed_out) *n_overflowed_out = n;
   if (n > 0)
     return sf_fail(c, SF_ERANGE, "SURF: %d keyframe(s) of the last batch call had more maxima than the candidate capacity and hold no rows; raise hessian_threshold",
+                   n);
+  return SF_OK;
+}
+
+extern "C" int sf_get_features_and_descriptor_sift_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                                int32_t n_keyframes, int32_t width, int32_t height,
+                                                                int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                                                                const sf_detector_params* det,
+                                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                                int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
+                                                                sf_keypoint* d_kpts_out) {
+  return features_batch(c, BATCH_SIFT, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+// How many keyframes of the most recent SIFT batch call had more extrema or keypoints than an image holds (they hold no rows)
+extern "C" int sf_sift_batch_status(sf_handle c, int32_t* n_overflowed_out) {
+  if (!c) return SF_EINVAL;
+  if (n_overflowed_out) *n_overflowed_out = 0;
+  SF_HIP(c, hipSetDevice(c->device));
+  int32_t n = 0;
+  if (c->sift_ctl.p) {
+    const int rc = sf_word_to_host(c, c->sift_ctl.p, &n);
+    if (rc != SF_OK) return rc;
+  } else {
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  if (n_overflowed_out) *n_overflowed_out = n;
+  if (n > 0)
+    return sf_fail(c, SF_ERANGE, "SIFT: %d keyframe(s) of the last batch call had more extrema or keypoints than the capacity of an image and hold no rows; raise contrast_threshold",
                    n);
   return SF_OK;
 }
@@ -1413,5 +1535,16 @@ extern "C" int sf_add_keyframes_surf_u8_batch_device(sf_handle c, const uint8_t*
                                                      int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                      float* d_xyz_out, sf_keypoint* d_kpts_out) {
   return add_keyframes_batch(c, BATCH_SURF, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_add_keyframes_sift_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                     const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                     int32_t height, int32_t pitch, size_t image_stride,
+                                                     const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                     const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                     int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                     float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, BATCH_SIFT, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
                              flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }

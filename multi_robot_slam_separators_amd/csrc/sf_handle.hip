@@ -289,7 +289,7 @@ extern "C" void sf_destroy(sf_handle c) {
                  &c->nn_recv.norms, &c->nn_recv.rows_h, &c->d_mask_local, &c->d_mask_other, &c->d_ign_ptr,
                  &c->d_ign_col, &c->nn_rowmin, &c->nn_exact, &c->nn_scalar, &c->comm_scratch, &c->trace, &c->stage_desc, &c->stage_xyz, &c->stage_kp,
                  &c->ex_integral, &c->ex_desc, &c->ex_xyz, &c->ex_keep, &c->ex_rows, &c->brief_tests, &c->orb_tests,
-                 &c->ex_blur, &c->ex_kpts, &c->orb_pyr, &c->orb_work, &c->freak_pattern, &c->freak_tables, &c->surf_planes, &c->surf_keys, &c->surf_tables, &c->surf_ctl, &c->sift_planes, &c->sift_keys, &c->sift_tables,
+                 &c->ex_blur, &c->ex_kpts, &c->orb_pyr, &c->orb_work, &c->freak_pattern, &c->freak_tables, &c->surf_planes, &c->surf_keys, &c->surf_tables, &c->surf_ctl, &c->sift_planes, &c->sift_keys, &c->sift_tables, &c->sift_ctl,
                  &c->gf_planes, &c->gf_keys, &c->gf_tmp, &c->gf_lists, &c->gf_scalar, &c->lk_pyr, &c->ft_images, &c->ft_kpts, &c->ft_flow, &c->ft_wire,
                  &c->ft_counts, &c->ft_cells, &c->img_src, &c->img_gray, &c->img_desc};
   for (Buf* b : bufs) sf_buf_free(*b);

@@ -239,9 +239,11 @@ constexpr size_t SURF_TABLE_ORI_W = 0, SURF_TABLE_DESC_W = 512, SURF_TABLE_ORI_X
 constexpr int SIFT_MAX_OCTAVES = 16, SIFT_MAX_LAYERS = 8, SIFT_MAX_KLEN = 520;   // sigma <= 8: the longest kernel has 515 taps
 constexpr unsigned SIFT_MAX_CANDIDATES = 1u << 18;   // extrema, and keypoints, per image; more is SF_ERANGE
 // SIFT rows (type 1): the handle's parameters, and whether the pyramid the detector has just left is this image's
+// (batch: the pyramids of the launch's images are the batch detector's, c->sift_batch describes them)
 struct SfSiftKind {
   sf_sift_params prm;
   bool reuse;
+  bool batch = false;
 };
 struct SfSiftPlan {
   int n_octaves = 0, n_layers = 0;
@@ -249,6 +251,22 @@ struct SfSiftPlan {
   unsigned long long gauss_off[SIFT_MAX_OCTAVES] = {}, dog_off[SIFT_MAX_OCTAVES] = {};
   unsigned pos_off[SIFT_MAX_OCTAVES + 1] = {};
   unsigned long long gauss_samples = 0, dog_samples = 0;
+};
+// The batch form runs its whole chain -- pyramid, keypoints, refinement, stereo correspondence, rows -- over chunks of
+// images whose planes and keys fit this much workspace.  One image always runs.  SURF's 256 MB (the Infinity Cache) gives
+// chunks of 4 camera images here, and the chain is about 130 launches per chunk whatever its size: timed alternately in
+// one run, 64 pairs of 752 x 480 took 0.745 ms per keyframe in chunks of 4 and 0.465 ms in chunks of 18, the 1 GB kept
+// here.
+constexpr size_t SIFT_BATCH_WORKSPACE_BYTES = (size_t)1 << 30;
+// What sf_sift_batch_plan_host computes for n images of one size.  Image i of a chunk: its Gaussian planes at
+// c->sift_planes + i plane_bytes, its difference planes off_dog bytes and the row pass's float32 plane off_tmp bytes
+// behind them; behind the chunk's planes the claim bitmaps, claim_words apart; in c->sift_keys the chunk's keys, sorted
+// keys and extrema lists, cap_img apart
+struct SfSiftBatchPlan {
+  SfSiftPlan P;
+  unsigned cap_img = 0;
+  int chunk = 0;
+  size_t off_dog = 0, off_tmp = 0, plane_bytes = 0, claim_words = 0, per_image = 0, workspace_bytes = 0;
 };
 
 struct sf_context {
@@ -346,6 +364,13 @@ struct sf_context {
   int sift_last_width = 0, sift_last_height = 0;
   SfSiftKind sift_kind = {};                   // what extract_kind hands the extraction under type 1
   bool sift_reuse_pyramid = false;             // set by the full call between its detector and its extraction
+  // the batch form: sift_ctl holds the number of keyframes of the most recent batch call with more extrema or keypoints
+  // than an image holds (word 0) and, from byte 64 on, the chunk's per-image words -- both counters, segment bounds,
+  // rekey flag; sift_batch: the plan of that call (the extraction reads the chunk's pyramids by it); sift_debug_chunk
+  // (sf_debug_sift_batch_chunk; 0 = the default): the images per chunk
+  Buf sift_ctl;
+  SfSiftBatchPlan sift_batch;
+  int sift_debug_chunk = 0;
   // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
   // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
   // the image at hand; orb_work: the detector's candidate lists
@@ -763,7 +788,8 @@ struct ExtractKind {
   size_t pyr_stride;
   const SfFreakTables* freak = nullptr;   // not null: FREAK rows (bytes 64; d_tests, orb and pyr unused)
   const SfSurfTables* surf = nullptr;     // not null: SURF rows (bytes 256 or 512, float32; the rest unused)
-  const SfSiftKind* sift = nullptr;       // not null: SIFT rows (bytes 512, float32; one image per call; the rest unused)
+  const SfSiftKind* sift = nullptr;       // not null: SIFT rows (bytes 512, float32; one image per call, or the chunk
+                                          // whose pyramids sf_launch_detect_sift_batch has left; the rest unused)
   // sf_launch_detect_surf_batch has left the integral images of the call's images in c->ex_integral: the extraction reads
   // them there and builds none (as pyr_stride for ORB's pyramids)
   bool integral_ready = false;
@@ -783,6 +809,20 @@ int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int 
                           const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
 int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const sf_sift_params* prm);
 int sf_sift_copy_plane(sf_context* c, int octave, int layer, int dog, int16_t* d_out);
+// the host arithmetic of SIFT's batch form, no device call (c may be null); candidate_cap 0 = SIFT_MAX_CANDIDATES,
+// forced_chunk 0 = what SIFT_BATCH_WORKSPACE_BYTES allows
+int sf_sift_batch_plan_host(sf_context* c, int width, int height, const sf_sift_params& p, int n, unsigned candidate_cap,
+                            int forced_chunk, SfSiftBatchPlan* out);
+// the plan under the handle's limits into c->sift_batch, every buffer of the batch detector, and the blur tables of p (the
+// one wait, when they differ from the handle's): a batch call's last step before its first launch
+int sf_sift_batch_reserve(sf_context* c, int width, int height, const sf_sift_params& p, int n_img);
+// resets the call's counter of overflowed keyframes and retires the single call's pyramid (on the stream, no wait)
+int sf_sift_batch_begin(sf_context* c);
+// the detector on ONE chunk (n_img <= c->sift_batch.chunk images of the size reserved for) with no host round trip:
+// d_kpts_out [n_img][cap], d_n_out [n_img] on the device; the chunk's pyramids stay in c->sift_planes for the extraction
+int sf_launch_detect_sift_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                                int pitch, int max_features, const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap,
+                                int32_t* d_n_out);
 // the host arithmetic of SURF's batch form, no device call (c may be null); candidate_cap 0 = SURF_MAX_CANDIDATES,
 // forced_chunk 0 = what SURF_BATCH_WORKSPACE_BYTES allows
 int sf_surf_batch_plan_host(sf_context* c, int width, int height, const sf_surf_params& p, int n, unsigned candidate_cap,

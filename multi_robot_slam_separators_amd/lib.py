@@ -127,6 +127,9 @@ def load():
         "sf_sift_plan": (C.c_int, [i32, i32, P(_abi.SiftParams), P(i32), vp, vp, P(i64), P(i64)]),
         "sf_debug_sift_limits": (C.c_int, [vp, i32]),
         "sf_debug_sift_plane": (C.c_int, [vp, i32, i32, i32, vp]),
+        "sf_sift_batch_status": (C.c_int, [vp, P(i32)]),
+        "sf_debug_sift_batch_chunk": (C.c_int, [vp, i32]),
+        "sf_sift_batch_plan": (C.c_int, [i32, i32, P(_abi.SiftParams), i32, P(i32), P(i32), P(i64)]),
         "sf_detect_corners_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_double, C.c_double, vp, i32, P(i32)]),
         "sf_stereo_flow_defaults": (None, [P(_abi.StereoFlowParams)]),
         "sf_detector_defaults": (None, [P(_abi.DetectorParams)]),
@@ -208,6 +211,9 @@ def load():
     # ... and of Vis/FeatureType 0
     sig["sf_get_features_and_descriptor_surf_batch_device"] = sig["sf_get_features_and_descriptor_batch_device"]
     sig["sf_add_keyframes_surf_u8_batch_device"] = sig["sf_add_keyframes_u8_batch_device"]
+    # ... and of Vis/FeatureType 1
+    sig["sf_get_features_and_descriptor_sift_batch_device"] = sig["sf_get_features_and_descriptor_batch_device"]
+    sig["sf_add_keyframes_sift_u8_batch_device"] = sig["sf_add_keyframes_u8_batch_device"]
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the library does not export the ABI
         fn.restype = res
@@ -253,6 +259,8 @@ EXPORTED = [
     "sf_debug_surf_limits", "sf_surf_batch_plan",
     "sf_sift_defaults", "sf_set_feature_type_sift", "sf_get_sift_params", "sf_detect_sift_device", "sf_sift_check_params", "sf_sift_build_tables", "sf_sift_plan",
     "sf_debug_sift_limits", "sf_debug_sift_plane",
+    "sf_get_features_and_descriptor_sift_batch_device", "sf_add_keyframes_sift_u8_batch_device", "sf_sift_batch_status",
+    "sf_debug_sift_batch_chunk", "sf_sift_batch_plan",
 ]
 
 
@@ -320,6 +328,17 @@ def sift_plan(width, height, sift=None):
     if rc != _abi.SF_OK:
         raise SepfinderError(rc, "sf_sift_plan refuses %d x %d" % (width, height))
     return n.value, [(int(w[o]), int(h[o])) for o in range(n.value)], g.value, d.value
+
+
+def sift_batch_plan(width, height, n_keyframes, sift=None):
+    """sf_sift_batch_plan (no GPU, no handle): (extrema / keypoint capacity per image, images per chunk, workspace bytes) of
+    the SIFT batch forms on n_keyframes images of width x height (sift: _abi.SiftParams; None = the defaults)."""
+    cap, chunk, ws = C.c_int32(), C.c_int32(), C.c_int64()
+    rc = load().sf_sift_batch_plan(width, height, C.byref(sift) if sift is not None else None, n_keyframes, C.byref(cap),
+                                   C.byref(chunk), C.byref(ws))
+    if rc != _abi.SF_OK:
+        raise SepfinderError(rc, "sf_sift_batch_plan refuses %d x %d, %d keyframes" % (width, height, n_keyframes))
+    return cap.value, chunk.value, ws.value
 
 
 def _ptr(a):
@@ -738,6 +757,11 @@ class SeparatorFinder:
         return value; slot i holds what get_features_and_descriptor_u8 gives for pair i (surf_batch_status: overflow)."""
         return self.add_keyframes_u8_batch_device(*args, _call="sf_add_keyframes_surf_u8_batch_device", **kw)
 
+    def add_keyframes_sift_u8_batch_device(self, *args, **kw):
+        """add_keyframes_u8_batch_device on a handle of Vis/FeatureType 1 (set_feature_type_sift): same arguments, same
+        return value; slot i holds what get_features_and_descriptor_u8 gives for pair i (sift_batch_status: overflow)."""
+        return self.add_keyframes_u8_batch_device(*args, _call="sf_add_keyframes_sift_u8_batch_device", **kw)
+
     def set_feature_type_orb(self, det=None, orb=None):
         """Vis/FeatureType 2, ORB on a pyramid: det (_abi.OrbDetectorParams; None = rtabmap's ORB/ defaults) drives the
         detector, orb (_abi.OrbParams; None = defaults, edge_threshold 16 .. 64) the border and the descriptors."""
@@ -927,6 +951,27 @@ class SeparatorFinder:
         if check or rc not in (_abi.SF_OK, _abi.SF_ERANGE):
             self._check(rc)
         return n.value
+
+    def get_features_and_descriptor_sift_batch_device(self, *args, **kw):
+        """get_features_and_descriptor_batch_device on a handle of Vis/FeatureType 1 (set_feature_type_sift): same arguments,
+        same return value; per keyframe the bytes of get_features_and_descriptor under type 1, 128 float32 per row."""
+        return self.get_features_and_descriptor_batch_device(*args, _call="sf_get_features_and_descriptor_sift_batch_device",
+                                                             **kw)
+
+    def sift_batch_status(self, check=True):
+        """sf_sift_batch_status: waits for the stream; the number of keyframes of the most recent SIFT batch call that had
+        more extrema or keypoints than an image holds (they hold no rows).  check: raise SepfinderError (SF_ERANGE) when it
+        is not 0."""
+        n = C.c_int32()
+        rc = self._L.sf_sift_batch_status(self._h, C.byref(n))
+        if check or rc not in (_abi.SF_OK, _abi.SF_ERANGE):
+            self._check(rc)
+        return n.value
+
+    def debug_sift_batch_chunk(self, batch_chunk=0):
+        """sf_debug_sift_batch_chunk (include/sf_experimental.h): the images per chunk of the SIFT batch forms, for tests on
+        small shapes; 0 = what the workspace allows."""
+        self._check(self._L.sf_debug_sift_batch_chunk(self._h, batch_chunk))
 
     def debug_surf_limits(self, candidate_cap=0, batch_chunk=0):
         """sf_debug_surf_limits (include/sf_experimental.h): the candidate capacity per image and the images per chunk of
