@@ -481,7 +481,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   if (kind.freak && (orb || bytes != FREAK_BYTES)) return sf_fail(c, SF_EINVAL, "FREAK rows are %d bytes, not %d", FREAK_BYTES, bytes);
   if (kind.surf && (orb || kind.freak || bytes != (kind.surf->extended ? 512 : 256)))
     return sf_fail(c, SF_EINVAL, "SURF rows are %d bytes, not %d", kind.surf->extended ? 512 : 256, bytes);
-  if (kind.sift && (orb || kind.freak || kind.surf || bytes != 512 || (n_img != 1 && !kind.sift->batch)))
+  if (kind.has_sift && (orb || kind.freak || kind.surf || bytes != 512 || (n_img != 1 && !kind.sift.batch)))
     return sf_fail(c, SF_EINVAL, "SIFT rows are 512 bytes, one keyframe per call unless the detector has left the chunk's pyramids (not %d bytes, %d keyframes)",
                    bytes, n_img);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
@@ -497,7 +497,7 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
     if (orb || c->ex_integral.bytes < B.s_stride * sizeof(int32_t) * n_img)
       return sf_fail(c, SF_EINVAL, "the batch's integral images are not the detector's");
     S = (int32_t*)c->ex_integral.p;
-  } else if (kind.sift) {                                // (no integral image: k_sift_describe reads the Gaussian pyramid)
+  } else if (kind.has_sift) {                            // (no integral image: k_sift_describe reads the Gaussian pyramid)
   } else if (!orb) {
     if ((rc = integral_images(c, d_left, n_img, width, height, pitch, &B, &S)) != SF_OK) return rc;
   } else if (!pyr) {
@@ -534,9 +534,9 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   const sf_keypoint* kp_commit = d_kpts;
   if (n > 0) {
     const long long threads = (long long)n * bytes;
-    if (kind.sift) {
+    if (kind.has_sift) {
       if ((rc = sf_buf_reserve(c, c->ex_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
-      if ((rc = sf_launch_sift_describe(c, d_left, pitch, width, height, *kind.sift, d_kpts, d_right_x, d_status, n, n_img, ec,
+      if ((rc = sf_launch_sift_describe(c, d_left, pitch, width, height, kind.sift, d_kpts, d_right_x, d_status, n, n_img, ec,
                                         (sf_keypoint*)c->ex_kpts.p, (float*)c->ex_desc.p, (float*)c->ex_xyz.p,
                                         (uint8_t*)c->ex_keep.p, B)) != SF_OK)
         return rc;

@@ -114,7 +114,7 @@ bool sf_gray_rule(int rule, int* kr, int* kg, int* kb, int* shift) {
 
 // n_images images of `format` -> gray planes, asynchronous on the handle's stream.  Images [0, n_first) lie at
 // d_src0 + i * src_stride, images [n_first, n_images) at d_src1 + (i - n_first) * src_stride; image i's plane at
-// d_dst + i * dst_stride.  The caller has validated the geometry (sf_features.hip).
+// d_dst + i * dst_stride.  The caller has validated the geometry (sf_keyframes.hip).
 int sf_launch_image_gray(sf_context* c, const uint8_t* d_src0, const uint8_t* d_src1, int n_first, int format, int rule,
                          int width, int height, int src_pitch, size_t src_stride, int n_images, uint8_t* d_dst, int dst_pitch,
                          size_t dst_stride) {

@@ -212,7 +212,7 @@ __global__ __launch_bounds__(64) void k_stereo_bm(const LkLevels P, const sf_key
 
 }  // namespace
 
-// The arguments of sf_launch_stereo_flow_batch (k_lk.hip); prm validated by the caller (sf_features.hip).
+// The arguments of sf_launch_stereo_flow_batch (k_lk.hip); prm validated by the caller (sf_detect.hip, sf_keyframes.hip).
 int sf_launch_stereo_bm_batch(sf_context* c, const uint8_t* d_left, const uint8_t* d_right, size_t img_stride, int n_img,
                               int width, int height, int pitch, const sf_keypoint* d_kpts, int n, const int32_t* d_n,
                               const sf_stereo_flow_params* prm, int ssd, float* d_right_xy, uint8_t* d_status,

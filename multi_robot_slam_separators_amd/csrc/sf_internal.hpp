@@ -241,8 +241,8 @@ constexpr unsigned SIFT_MAX_CANDIDATES = 1u << 18;   // extrema, and keypoints, 
 // SIFT rows (type 1): the handle's parameters, and whether the pyramid the detector has just left is this image's
 // (batch: the pyramids of the launch's images are the batch detector's, c->sift_batch describes them)
 struct SfSiftKind {
-  sf_sift_params prm;
-  bool reuse;
+  sf_sift_params prm = {};
+  bool reuse = false;
   bool batch = false;
 };
 struct SfSiftPlan {
@@ -362,8 +362,6 @@ struct sf_context {
   size_t sift_last_off_dog = 0, sift_last_off_claim = 0;
   sf_sift_params sift_last_prm = {};
   int sift_last_width = 0, sift_last_height = 0;
-  SfSiftKind sift_kind = {};                   // what extract_kind hands the extraction under type 1
-  bool sift_reuse_pyramid = false;             // set by the full call between its detector and its extraction
   // the batch form: sift_ctl holds the number of keyframes of the most recent batch call with more extrema or keypoints
   // than an image holds (word 0) and, from byte 64 on, the chunk's per-image words -- both counters, segment bounds,
   // rekey flag; sift_batch: the plan of that call (the extraction reads the chunk's pyramids by it); sift_debug_chunk
@@ -781,15 +779,15 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
 // extraction builds the pyramid of its one image; else sf_launch_detect_orb_batch has left the pyramids of the call's
 // images in c->orb_pyr, pyr_stride bytes apart, and the extraction reads them there
 struct ExtractKind {
-  int bytes;
-  const int8_t* d_tests;
-  const sf_orb_params* orb;
-  const sf_orb_detector_params* pyr;
-  size_t pyr_stride;
+  int bytes = 0;
+  const int8_t* d_tests = nullptr;
+  const sf_orb_params* orb = nullptr;
+  const sf_orb_detector_params* pyr = nullptr;
+  size_t pyr_stride = 0;
   const SfFreakTables* freak = nullptr;   // not null: FREAK rows (bytes 64; d_tests, orb and pyr unused)
   const SfSurfTables* surf = nullptr;     // not null: SURF rows (bytes 256 or 512, float32; the rest unused)
-  const SfSiftKind* sift = nullptr;       // not null: SIFT rows (bytes 512, float32; one image per call, or the chunk
-                                          // whose pyramids sf_launch_detect_sift_batch has left; the rest unused)
+  bool has_sift = false;                  // true: SIFT rows (bytes 512, float32; `sift` says how, the rest unused)
+  SfSiftKind sift;                        // read under has_sift: one image per call, or the chunk the batch detector has left
   // sf_launch_detect_surf_batch has left the integral images of the call's images in c->ex_integral: the extraction reads
   // them there and builds none (as pyr_stride for ORB's pyramids)
   bool integral_ready = false;

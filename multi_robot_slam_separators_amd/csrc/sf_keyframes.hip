@@ -1,0 +1,625 @@
+// sf_keyframes.hip -- images to keyframes of the store: sf_extract_keyframe_device, the full call on host images, the batch
+// pipeline of the four families of batch calls, the camera's own images and the calls that add keyframes with NetVLAD rows.
+#include "sf_host.hpp"
+
+// a camera image (sf_image_format): a row holds 3 bytes per pixel for the colour formats
+static int check_format(sf_context* c, int format) {
+  if (format != SF_IMAGE_RGB8 && format != SF_IMAGE_BGR8 && format != SF_IMAGE_MONO8)
+    return sf_fail(c, SF_EINVAL, "image format %d unknown (0 = rgb8, 1 = bgr8, 2 = mono8)", format);
+  return SF_OK;
+}
+
+static long long image_row_bytes(int format, int width) { return (long long)width * (format == SF_IMAGE_MONO8 ? 1 : 3); }
+
+static int check_camera_image(sf_context* c, bool present, int format, int width, int height, int pitch, int min_side,
+                              const char* what) {
+  int rc = check_format(c, format);
+  if (rc != SF_OK) return rc;
+  if (!present || width < min_side || height < min_side || pitch < image_row_bytes(format, width))
+    return sf_fail(c, SF_EINVAL, "%s missing or malformed (%d x %d, pitch %d, %d byte(s) per pixel)", what, width, height, pitch,
+                   format == SF_IMAGE_MONO8 ? 1 : 3);
+  return SF_OK;
+}
+
+static int extract_keyframe(sf_context* c, const uint8_t* d_left, int32_t width, int32_t height, int32_t pitch,
+                            const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int32_t n,
+                            const sf_stereo_camera* cam, int32_t* out_slot, int32_t* out_rows, uint8_t* d_desc_out,
+                            float* d_xyz_out, sf_keypoint* d_kpts_out, bool reuse_sift_pyramid) {
+  if (!c || !cam || n < 0) return SF_EINVAL;
+  int rc = sf_check_image(c, d_left, width, height, pitch, 1, "left image");
+  if (rc != SF_OK) return rc;
+  if (n > 0 && !d_kpts) return sf_fail(c, SF_EINVAL, "keypoints missing");
+  if (n > SF_MAX_FEATURES) return sf_fail(c, SF_ERANGE, "%d corners > int16 limit of KeyPointVec.size", n);
+  if ((rc = sf_check_integral(c, width, height)) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  ExtractKind kind;
+  if ((rc = sf_extract_kind(c, &kind)) != SF_OK) return rc;
+  kind.sift.reuse = reuse_sift_pyramid;                    // (the full call: the SIFT detector has just run on this image)
+  if ((rc = sf_store_reserve(c, c->store, c->store.slots + 1, n, kind.bytes)) != SF_OK) return rc;
+  if (out_rows && (rc = sf_buf_reserve(c, c->ex_rows, 16)) != SF_OK) return rc;
+  const int slot = c->store.slots;
+  if ((rc = sf_launch_extract_batch(c, d_left, 0, 1, width, height, pitch, d_kpts, d_right_x, d_status, n, nullptr, cam, kind,
+                                    slot, d_desc_out, d_xyz_out, d_kpts_out,
+                                    out_rows ? (int32_t*)c->ex_rows.p : nullptr)) != SF_OK)
+    return rc;
+  c->store.slots += 1;
+  if (out_slot) *out_slot = slot;
+  return out_rows ? sf_word_to_host(c, c->ex_rows.p, out_rows) : SF_OK;
+}
+
+extern "C" int sf_extract_keyframe_device(sf_handle c, const uint8_t* d_left, int32_t width, int32_t height,
+                                          int32_t pitch, const sf_keypoint* d_kpts, const float* d_right_x,
+                                          const uint8_t* d_status, int32_t n, const sf_stereo_camera* cam,
+                                          int32_t* out_slot, int32_t* out_rows, uint8_t* d_desc_out,
+                                          float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return extract_keyframe(c, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam, out_slot, out_rows, d_desc_out,
+                          d_xyz_out, d_kpts_out, false);
+}
+
+// ---- what differs between the families of batch calls (the generic calls of types 3 .. 8; the _orb_, _surf_ and _sift_ calls of
+// types 2, 0 and 1): what the family's detector refuses, what it reserves, its launch -- three switches side by side ---------
+struct BatchPlan {
+  sf_detector_params dp;
+  sf_stereo_flow_params prm;
+  ExtractKind kind;
+  FrontPlan front;
+};
+
+// behind a detector's own parameters (`validated`): the pixels of an image, the images of a grid dimension
+static int batch_limits(sf_context* c, int validated, const char* name, int n_keyframes, int width, int height) {
+  if (validated != SF_OK || (validated = sf_check_pixels(c, width, height)) != SF_OK) return validated;
+  return n_keyframes <= 65535 ? SF_OK : sf_fail(c, SF_ERANGE, "%s batch of %d keyframes (at most 65535)", name, n_keyframes);
+}
+
+// what sf_detect_orb_device, sf_detect_surf_device and sf_detect_sift_device refuse, then what the family's batch layout does
+static int family_check(sf_context* c, BatchFamily family, int n_keyframes, int width, int height) {
+  int rc;
+  switch (family) {
+    case BATCH_GENERIC: break;                             // (GFTT's parameters: batch_check; FAST's pixels: family_reserve)
+    case BATCH_ORB: {
+      if ((rc = batch_limits(c, sf_orb_detector_validate(c, c->orb_det, c->orb), "ORB", n_keyframes, width, height)) != SF_OK) return rc;
+      const SfOrbPyr P = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels);
+      for (int l = 0; l < P.n; ++l)
+        if (P.w[l] < 1 || P.h[l] < 1)
+          return sf_fail(c, SF_ERANGE, "pyramid level %d of a %d x %d image at scale %g is empty", l, width, height, (double)P.scale[l]);
+      break;
+    }
+    case BATCH_SURF: {                                     // (the layout's 2^31 plane samples)
+      SfSurfBatchPlan sp;
+      if ((rc = batch_limits(c, sf_surf_validate(c, c->surf), "SURF", n_keyframes, width, height)) != SF_OK) return rc;
+      return sf_surf_batch_plan_host(c, width, height, c->surf, n_keyframes, 0, 0, &sp);
+    }
+    case BATCH_SIFT: {                                     // (the image's sides, the 2^26 difference samples)
+      SfSiftBatchPlan sp;
+      if ((rc = batch_limits(c, sf_sift_validate(c, c->sift), "SIFT", n_keyframes, width, height)) != SF_OK) return rc;
+      return sf_sift_batch_plan_host(c, width, height, c->sift, n_keyframes, 0, 0, &sp);
+    }
+  }
+  return SF_OK;
+}
+
+static int family_reserve(sf_context* c, const SfFeatureType& t, int n, int width, int height) {
+  SfSurfBatchPlan surf;
+  switch (t.family) {
+    case BATCH_GENERIC: return t.corners == CORNERS_FAST ? sf_check_pixels(c, width, height) : SF_OK;
+    case BATCH_ORB: return SF_OK;                          // (the detector's launcher reserves its pyramids)
+    case BATCH_SURF: return sf_surf_batch_reserve(c, width, height, c->surf, n, &surf);   // planes, keys and integral images
+    case BATCH_SIFT: return sf_sift_batch_reserve(c, width, height, c->sift, n);          // the chunk's planes and keys; the blur tables
+  }
+  return SF_OK;
+}
+
+// The detector on images [i0, i0 + m) of a batch, into that sub-range of c->ft_kpts / c->ft_counts; `kind`: what it leaves the extraction
+static int family_detect(sf_context* c, const SfFeatureType& t, const BatchPlan& plan, ExtractKind* kind, const uint8_t* d_left,
+                         size_t image_stride, int i0, int m, int width, int height, int pitch) {
+  const FrontPlan& fp = plan.front;
+  const int maxf = fp.rows_cap;                            // rows per keyframe: max_features, or the grid's R C quota
+  const uint8_t* d_images = d_left + (size_t)i0 * image_stride;
+  const uint8_t* d_roi = d_images + (size_t)fp.y * pitch + fp.x;   // the ROI, at the parent's pitch and stride
+  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p + (size_t)i0 * maxf;
+  int32_t* d_n = (int32_t*)c->ft_counts.p + i0;
+  switch (t.family) {
+    case BATCH_ORB:                                        // (keypoints in level-0 coordinates; the pyramids stay for the extraction;
+      kind->pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;   // no ROI: sf_front_plan)
+      return sf_launch_detect_orb_batch(c, d_images, image_stride, m, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
+    case BATCH_SURF:                                       // (no ROI, no grid: sf_front_plan, sf_grid_plan; the integral images stay
+      kind->integral_ready = true;                         // for the extraction)
+      return sf_launch_detect_surf_batch(c, d_images, image_stride, m, width, height, pitch, maxf, &c->surf, d_kpts, maxf, d_n);
+    case BATCH_SIFT:                                       // (likewise; the chunk's pyramids stay for the extraction)
+      kind->sift.batch = true;
+      return sf_launch_detect_sift_batch(c, d_images, image_stride, m, width, height, pitch, maxf, &c->sift, d_kpts, maxf, d_n);
+    case BATCH_GENERIC:
+      if (fp.grid())                                       // the cells as the detector's images, joined by k_grid_gather
+        return sf_grid_detect(c, fp, plan.dp, d_images, image_stride, m, pitch, d_kpts, d_n);
+      if (t.corners == CORNERS_FAST)
+        return sf_launch_detect_fast_batch(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
+      return sf_launch_detect_corners_batch(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, plan.dp.quality_level,
+                                            plan.dp.min_distance, d_kpts, maxf, d_n);
+  }
+  return SF_EINVAL;
+}
+
+// The GetFeatsAndDesc handler in one call on HOST buffers: upload the pair, detect, track, extract, download the
+// response.  Everything between the two copies stays on the device; the keyframe is in the store when it returns.
+// format < 0: rectified MONO8 planes (sf_get_features_and_descriptor); otherwise the camera's images in that
+// sf_image_format (sf_get_features_and_descriptor_u8), converted on the device behind the upload.
+static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* right, int format, int32_t width,
+                             int32_t height, int32_t pitch, const sf_stereo_camera* cam, const sf_detector_params* det,
+                             const sf_stereo_flow_params* flow, uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out,
+                             int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
+  if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
+  *rows_out = 0;
+  int rc = format < 0 ? sf_check_image(c, left && right, width, height, pitch, 3, "stereo pair")
+                      : check_camera_image(c, left && right, format, width, height, pitch, 3, "stereo pair");
+  if (rc != SF_OK) return rc;
+  FrontPlan fp;
+  if ((rc = sf_front_plan(c, width, height, &fp)) != SF_OK) return rc;
+  const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
+  if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
+    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
+  if ((rc = sf_grid_plan(c, width, height, dp.max_features, &fp)) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  ExtractKind kind;
+  if ((rc = sf_extract_kind(c, &kind)) != SF_OK) return rc;
+  const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
+  const int maxf = fp.rows_cap;                            // the rows of the call's buffers: max_features, or the grid's R C quota
+  if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_flow, (size_t)maxf * 16)) != SF_OK) return rc;
+  const size_t row_bytes = (size_t)kind.bytes + 12 + sizeof(sf_keypoint);
+  if ((rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64)) != SF_OK) return rc;
+  uint8_t* d_left = (uint8_t*)c->ft_images.p;
+  uint8_t* d_right = d_left + img_bytes;
+  if (format == SF_IMAGE_RGB8 || format == SF_IMAGE_BGR8) {
+    // the colour pair as it is (rows padded to 16 bytes: the conversion's wide path), then both planes in one launch
+    const int src_pitch = (3 * width + 15) & ~15;
+    const size_t src_bytes = ((size_t)src_pitch * height + 255) & ~(size_t)255;
+    if ((rc = sf_buf_reserve(c, c->img_src, 2 * src_bytes)) != SF_OK) return rc;
+    uint8_t* d_src = (uint8_t*)c->img_src.p;
+    SF_HIP(c, hipMemcpy2DAsync(d_src, src_pitch, left, pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
+    SF_HIP(c, hipMemcpy2DAsync(d_src + src_bytes, src_pitch, right, pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
+    if ((rc = sf_launch_image_gray(c, d_src, nullptr, 2, format, c->gray_rule, width, height, src_pitch, src_bytes, 2, d_left,
+                                   width, img_bytes)) != SF_OK)
+      return rc;
+  } else {                                                 // MONO8 planes, or mono8 camera images: the pitched copy is the upload
+    SF_HIP(c, hipMemcpy2DAsync(d_left, width, left, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+    SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+  }
+  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
+  int32_t n = 0;
+  // (the GFTT parameters are checked under every feature type, FAST and ORB included, which do not use them)
+  if ((rc = sf_check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
+  const uint8_t* d_roi = d_left + (size_t)fp.y * width + fp.x;   // the detector's image: the ROI, at the parent's pitch
+  if (fp.grid()) {                                       // every cell in one launch sequence, one wait for the keyframe's count
+    if ((rc = sf_check_pixels(c, fp.col_size, fp.row_size)) != SF_OK) return rc;
+    if ((rc = sf_buf_reserve(c, c->ft_counts, 4)) != SF_OK) return rc;
+    if ((rc = sf_grid_detect(c, fp, dp, d_left, 0, 1, width, d_kpts, (int32_t*)c->ft_counts.p)) != SF_OK) return rc;
+    rc = sf_word_to_host(c, c->ft_counts.p, &n);
+  } else {                                               // the public detector call of the type's family, the count on the host
+    const SfFeatureType& t = sf_type_of(c);
+    switch (t.family) {
+      case BATCH_ORB: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
+      case BATCH_SURF: rc = sf_detect_surf_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;   // (no ROI: sf_front_plan)
+      case BATCH_SIFT: rc = sf_detect_sift_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;   // (likewise)
+      case BATCH_GENERIC:
+        rc = t.corners == CORNERS_FAST ? sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n)
+                                       : sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
+    }
+  }
+  if (rc != SF_OK) return rc;
+  n = std::min(n, maxf);
+  if (fp.launch() &&
+      (rc = sf_launch_corner_subpix(c, d_left, 0, 1, width, height, width, d_kpts, n, nullptr, maxf, fp.off_x(), fp.off_y(),
+                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
+    return rc;
+  float* d_xy = (float*)c->ft_flow.p;                    // [n][2], then x [n], then status [n]
+  float* d_rx = d_xy + 2 * (size_t)maxf;
+  uint8_t* d_status = (uint8_t*)(d_rx + maxf);
+  rc = c->stereo.optical_flow
+           ? sf_stereo_correspondences_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, d_xy, d_status, d_rx, nullptr)
+           : sf_stereo_block_match_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
+  if (rc != SF_OK) return rc;
+  uint8_t* d_desc = (uint8_t*)c->ft_wire.p;
+  float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
+  sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
+  int32_t slot = -1, rows = 0;
+  if ((rc = extract_keyframe(c, d_left, width, height, width, d_kpts, d_rx, d_status, n, cam, &slot, &rows, d_desc, d_xyz, d_kp_out,
+                             kind.has_sift)) != SF_OK)     // (SIFT: the detector's pyramid serves, the refinement moved x and y only)
+    return rc;
+  *rows_out = rows;
+  if (slot_out) *slot_out = slot;
+  const int32_t k = std::min(rows, cap_rows);
+  if (k > 0) {
+    if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, d_desc, (size_t)k * kind.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (xyz_out) SF_HIP(c, hipMemcpyAsync(xyz_out, d_xyz, (size_t)k * 12, hipMemcpyDeviceToHost, c->stream));
+    if (kpts_out) SF_HIP(c, hipMemcpyAsync(kpts_out, d_kp_out, (size_t)k * sizeof(sf_keypoint), hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return SF_OK;
+}
+
+extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, const uint8_t* right, int32_t width,
+                                              int32_t height, int32_t pitch, const sf_stereo_camera* cam,
+                                              const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                              uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
+                                              int32_t* rows_out, int32_t* slot_out) {
+  return get_features_host(c, left, right, -1, width, height, pitch, cam, det, flow, desc_out, xyz_out, kpts_out, cap_rows,
+                           rows_out, slot_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_u8(sf_handle c, const uint8_t* left, const uint8_t* right, int32_t format,
+                                                 int32_t width, int32_t height, int32_t pitch, const sf_stereo_camera* cam,
+                                                 const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                 uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
+                                                 int32_t* rows_out, int32_t* slot_out) {
+  if (!c) return SF_EINVAL;
+  const int rc = check_format(c, format);
+  if (rc != SF_OK) return rc;
+  return get_features_host(c, left, right, format, width, height, pitch, cam, det, flow, desc_out, xyz_out, kpts_out, cap_rows,
+                           rows_out, slot_out);
+}
+
+// n keyframes from device images to n store slots in ONE launch sequence: detector, stereo correspondence and
+// extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
+// host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.  In three parts, shared by the eight batch
+// calls (`family`): batch_check refuses (nothing is touched; n_keyframes = 0 passes without a look at the images),
+// batch_reserve takes the store slots and the call's buffers, batch_launch queues the three stages, chunk by chunk.
+static int batch_check(sf_context* c, BatchFamily family, bool images, int n_keyframes, int width, int height, int pitch,
+                       size_t image_stride, const sf_detector_params* det, const sf_stereo_flow_params* flow, BatchPlan* plan) {
+  const SfFeatureType& t = sf_type_of(c);
+  if (t.family != family && t.other_call) return sf_fail(c, SF_EINVAL, "%s", t.other_call);   // a type with calls of its own
+  if (t.family != family) {
+    const SfFeatureType& need = sf_type_of_family(family);
+    return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the %s batch calls need type %d (%s); use %s / %s", t.type, need.name, need.type,
+                   need.setter, t.get_features_batch, t.add_keyframes_batch);
+  }
+  if (n_keyframes == 0) return SF_OK;
+  int rc = sf_check_image(c, images, width, height, pitch, 3, "stereo pairs");
+  if (rc != SF_OK) return rc;
+  if (image_stride < (size_t)pitch * height)
+    return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
+  if ((rc = sf_front_plan(c, width, height, &plan->front)) != SF_OK) return rc;
+  plan->dp = arg_or_defaults(det, sf_detector_defaults);
+  if (plan->dp.max_features <= 0 || plan->dp.max_features > SF_MAX_FEATURES)
+    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", plan->dp.max_features, SF_MAX_FEATURES);
+  if ((rc = sf_check_gftt(c, plan->dp.quality_level, plan->dp.min_distance)) != SF_OK) return rc;
+  if ((rc = sf_grid_plan(c, width, height, plan->dp.max_features, &plan->front)) != SF_OK) return rc;
+  if (plan->front.grid() && (long long)n_keyframes * plan->front.rows * plan->front.cols > 65535)
+    return sf_fail(c, SF_ERANGE, "%d keyframes of %d x %d cells: at most 65535 cells per call", n_keyframes, plan->front.rows, plan->front.cols);
+  plan->prm = arg_or_defaults(flow, sf_stereo_flow_defaults);
+  if (!c->stereo.optical_flow) {
+    if ((rc = sf_check_block_match(c, plan->prm)) != SF_OK) return rc;
+  } else if (!sf_stereo_flow_ok(plan->prm)) {
+    return sf_fail(c, SF_EINVAL, "stereo flow parameters out of range (see sf_stereo_correspondences_device)");
+  }
+  if ((rc = sf_check_integral(c, width, height)) != SF_OK) return rc;
+  return family_check(c, family, n_keyframes, width, height);
+}
+
+static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan* plan) {
+  int rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  if ((rc = sf_extract_kind(c, &plan->kind)) != SF_OK) return rc;
+  const int maxf = plan->front.rows_cap;                   // rows per keyframe: max_features, or the grid's R C quota
+  const size_t rows_all = (size_t)maxf * n;
+  if ((rc = sf_buf_reserve(c, c->ft_kpts, rows_all * sizeof(sf_keypoint))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_flow, rows_all * 16)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_counts, (size_t)n * 4)) != SF_OK) return rc;
+  if ((rc = sf_store_reserve(c, c->store, c->store.slots + n, maxf, plan->kind.bytes)) != SF_OK) return rc;
+  return family_reserve(c, sf_type_of(c), n, width, height);
+}
+
+// The stages behind the detector -- refinement, stereo correspondence, extraction -- for the m images from i0 on of a batch
+// of n whose keypoints and counts the detector has left in c->ft_kpts / c->ft_counts: every array at that sub-range, the
+// store slots from slot + i0 on
+static int batch_follow(sf_context* c, const BatchPlan& plan, const ExtractKind& kind, const uint8_t* d_left, const uint8_t* d_right,
+                        int n, int i0, int m, int width, int height, int pitch, size_t image_stride, const sf_stereo_camera* cam,
+                        int slot, int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  const int maxf = plan.front.rows_cap;
+  const size_t rows_all = (size_t)maxf * n, r0 = (size_t)maxf * i0;
+  const FrontPlan& fp = plan.front;
+  int rc;
+  d_left += (size_t)i0 * image_stride; d_right += (size_t)i0 * image_stride;
+  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p + r0;
+  const int32_t* d_n = (const int32_t*)c->ft_counts.p + i0;
+  if (fp.launch() &&
+      (rc = sf_launch_corner_subpix(c, d_left, image_stride, m, width, height, pitch, d_kpts, maxf, d_n, maxf, fp.off_x(), fp.off_y(),
+                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
+    return rc;
+  float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
+  float* d_rx = d_xy + 2 * rows_all;
+  uint8_t* d_status = (uint8_t*)(d_rx + rows_all);
+  d_xy += 2 * r0; d_rx += r0; d_status += r0;
+  rc = c->stereo.optical_flow
+           ? sf_launch_stereo_flow_batch(c, d_left, d_right, image_stride, m, width, height, pitch, d_kpts, maxf, d_n, &plan.prm, d_xy,
+                                         d_status, d_rx, nullptr)
+           : sf_launch_stereo_bm_batch(c, d_left, d_right, image_stride, m, width, height, pitch, d_kpts, maxf, d_n, &plan.prm,
+                                       c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
+  if (rc != SF_OK) return rc;
+  return sf_launch_extract_batch(c, d_left, image_stride, m, width, height, pitch, d_kpts, d_rx, d_status, maxf, d_n, cam, kind,
+                                 slot + i0, d_desc_out ? d_desc_out + r0 * kind.bytes : nullptr, d_xyz_out ? d_xyz_out + 3 * r0 : nullptr,
+                                 d_kpts_out ? d_kpts_out + r0 : nullptr, d_rows_out ? d_rows_out + i0 : nullptr);
+}
+
+// One loop over chunks, detector then the stages behind it.  A batch is one chunk, but under SIFT: its Gaussian planes are too
+// large to keep for a whole batch, so a chunk's extraction reads them before the next chunk's detector overwrites them
+static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_left, const uint8_t* d_right, int n, int width,
+                        int height, int pitch, size_t image_stride, const sf_stereo_camera* cam, int32_t* first_slot_out,
+                        int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  const SfFeatureType& t = sf_type_of(c);
+  const int slot = c->store.slots;
+  ExtractKind kind = plan.kind;
+  int rc, chunk = n;
+  if (t.family == BATCH_SIFT) {
+    chunk = c->sift_batch.chunk;
+    if ((rc = sf_sift_batch_begin(c)) != SF_OK) return rc;
+  }
+  for (int i0 = 0; i0 < n; i0 += chunk) {
+    const int m = std::min(chunk, n - i0);
+    if ((rc = family_detect(c, t, plan, &kind, d_left, image_stride, i0, m, width, height, pitch)) != SF_OK) return rc;
+    if ((rc = batch_follow(c, plan, kind, d_left, d_right, n, i0, m, width, height, pitch, image_stride, cam, slot, d_rows_out,
+                           d_desc_out, d_xyz_out, d_kpts_out)) != SF_OK)
+      return rc;
+  }
+  c->store.slots += n;
+  if (first_slot_out) *first_slot_out = slot;
+  return SF_OK;
+}
+
+static int features_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const uint8_t* d_right, int32_t n_keyframes,
+                          int32_t width, int32_t height, int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                          const sf_detector_params* det, const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                          int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  BatchPlan plan;
+  int rc = batch_check(c, family, d_left && d_right, n_keyframes, width, height, pitch, image_stride, det, flow, &plan);
+  if (rc != SF_OK) return rc;
+  if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
+  if ((rc = batch_reserve(c, n_keyframes, width, height, &plan)) != SF_OK) return rc;
+  return batch_launch(c, plan, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, first_slot_out, d_rows_out,
+                      d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                           int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                                                           size_t image_stride, const sf_stereo_camera* cam,
+                                                           const sf_detector_params* det, const sf_stereo_flow_params* flow,
+                                                           int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                           float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return features_batch(c, BATCH_GENERIC, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_orb_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                               int32_t n_keyframes, int32_t width, int32_t height,
+                                                               int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                                                               const sf_detector_params* det,
+                                                               const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                               int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
+                                                               sf_keypoint* d_kpts_out) {
+  return features_batch(c, BATCH_ORB, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_surf_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                                int32_t n_keyframes, int32_t width, int32_t height,
+                                                                int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                                                                const sf_detector_params* det,
+                                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                                int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
+                                                                sf_keypoint* d_kpts_out) {
+  return features_batch(c, BATCH_SURF, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+// How many keyframes of the most recent SURF / SIFT batch call overflowed and hold no rows (word 0 of the family's control
+// buffer): waits for the stream, `message` says what overflowed, with the count
+static int batch_status(sf_context* c, Buf sf_context::*control, const char* message, int32_t* n_overflowed_out) {
+  if (!c) return SF_EINVAL;
+  if (n_overflowed_out) *n_overflowed_out = 0;
+  SF_HIP(c, hipSetDevice(c->device));
+  int32_t n = 0;
+  const Buf& ctl = c->*control;
+  if (ctl.p) {
+    const int rc = sf_word_to_host(c, ctl.p, &n);
+    if (rc != SF_OK) return rc;
+  } else {
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  if (n_overflowed_out) *n_overflowed_out = n;
+  return n > 0 ? sf_fail(c, SF_ERANGE, message, n) : SF_OK;
+}
+
+extern "C" int sf_surf_batch_status(sf_handle c, int32_t* n_overflowed_out) {
+  return batch_status(c, &sf_context::surf_ctl, "SURF: %d keyframe(s) of the last batch call had more maxima than the candidate capacity and hold no rows; raise hessian_threshold",
+                      n_overflowed_out);
+}
+
+extern "C" int sf_get_features_and_descriptor_sift_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                                int32_t n_keyframes, int32_t width, int32_t height,
+                                                                int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
+                                                                const sf_detector_params* det,
+                                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                                int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
+                                                                sf_keypoint* d_kpts_out) {
+  return features_batch(c, BATCH_SIFT, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+                        d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_sift_batch_status(sf_handle c, int32_t* n_overflowed_out) {
+  return batch_status(c, &sf_context::sift_ctl, "SIFT: %d keyframe(s) of the last batch call had more extrema or keypoints than the capacity of an image and hold no rows; raise contrast_threshold",
+                      n_overflowed_out);
+}
+
+// ---- the camera's own images (kernels in k_image.hip, k_cnn.hip) ---------------------------------------------------
+extern "C" int sf_image_set_gray_rule(sf_handle c, int32_t rule) {
+  if (!c) return SF_EINVAL;
+  int k[4];
+  if (!sf_gray_rule(rule, &k[0], &k[1], &k[2], &k[3]))
+    return sf_fail(c, SF_EINVAL, "gray rule %d unknown (0 = OpenCV 3.x, 1 = OpenCV 4.x)", rule);
+  c->gray_rule = rule;
+  return SF_OK;
+}
+
+extern "C" int sf_image_get_gray_rule(sf_handle c, int32_t* rule) {
+  if (!c || !rule) return SF_EINVAL;
+  *rule = c->gray_rule;
+  return SF_OK;
+}
+
+// an array of n images `stride` bytes apart: the last image needs its rows only, not a whole stride
+static int check_stride(sf_context* c, int n, size_t stride, int pitch, int height, long long last_row, const char* what) {
+  if (n > 1 && stride < (size_t)pitch * (height - 1) + (size_t)last_row)
+    return sf_fail(c, SF_EINVAL, "%s stride %zu is less than an image (%d rows of pitch %d)", what, stride, height, pitch);
+  return SF_OK;
+}
+
+extern "C" int sf_image_to_gray_device(sf_handle c, const uint8_t* d_src, int32_t format, int32_t width, int32_t height,
+                                       int32_t src_pitch, size_t src_stride, int32_t n_images, uint8_t* d_dst,
+                                       int32_t dst_pitch, size_t dst_stride) {
+  if (!c || n_images < 0) return SF_EINVAL;
+  int rc = check_format(c, format);
+  if (rc != SF_OK) return rc;
+  if (n_images == 0) return SF_OK;
+  if ((rc = check_camera_image(c, d_src, format, width, height, src_pitch, 1, "source images")) != SF_OK) return rc;
+  if ((rc = sf_check_image(c, d_dst, width, height, dst_pitch, 1, "gray planes")) != SF_OK) return rc;
+  if ((rc = check_stride(c, n_images, src_stride, src_pitch, height, image_row_bytes(format, width), "source")) != SF_OK) return rc;
+  if ((rc = check_stride(c, n_images, dst_stride, dst_pitch, height, width, "destination")) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_launch_image_gray(c, d_src, nullptr, n_images, format, c->gray_rule, width, height, src_pitch, src_stride, n_images,
+                              d_dst, dst_pitch, dst_stride);
+}
+
+extern "C" int sf_netvlad_infer_u8_batch_device(sf_handle c, const uint8_t* d_images, int32_t format, int32_t n_images,
+                                                int32_t width, int32_t height, int32_t pitch, size_t image_stride,
+                                                float* d_out, int32_t n_out) {
+  if (!c || !d_out) return SF_EINVAL;
+  int rc = check_camera_image(c, d_images, format, width, height, pitch, 1, "images");
+  if (rc != SF_OK) return rc;
+  if ((rc = check_stride(c, n_images, image_stride, pitch, height, image_row_bytes(format, width), "image")) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_infer_u8_batch_impl(c, d_images, format, n_images, height, width, pitch, image_stride, d_out, n_out);
+}
+
+extern "C" int sf_netvlad_load(sf_handle c, const sf_netvlad_weights* w) {
+  if (!c) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_load_impl(c, w);
+}
+
+extern "C" int sf_netvlad_infer_device(sf_handle c, const float* d_image_rgb, int32_t width, int32_t height, float* d_out,
+                                       int32_t n_out) {
+  if (!c || !d_image_rgb || !d_out) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_infer_impl(c, d_image_rgb, height, width, d_out, n_out);
+}
+
+extern "C" int sf_netvlad_infer_batch_device(sf_handle c, const float* d_images_rgb, int32_t n_images, int32_t width,
+                                             int32_t height, float* d_out, int32_t n_out) {
+  if (!c || !d_images_rgb || !d_out) return SF_EINVAL;
+  SF_HIP(c, hipSetDevice(c->device));
+  return sf_netvlad_infer_batch_impl(c, d_images_rgb, n_images, height, width, d_out, n_out);
+}
+
+// get_keyframes + compute_descriptors for n keyframes (data_handler.py:143-164, 212-295): gray planes of all 2 n stereo
+// images (one launch), the network on the colour images, the batch feature stages on the planes, the descriptors' prefix
+// into the local NN rows.  Everything that can refuse does so before the first launch; the store and the NN database
+// grow last, together.
+static int add_keyframes_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+                               int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
+                               size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
+                               const sf_stereo_flow_params* flow, int32_t* first_slot_out, int32_t* first_nn_row_out,
+                               int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  const int n = n_keyframes;
+  int rc;
+  if ((rc = check_format(c, format)) != SF_OK) return rc;
+  if (n > 0) {
+    if ((rc = check_camera_image(c, d_left && d_right, format, width, height, pitch, 3, "stereo pairs")) != SF_OK) return rc;
+    if (image_stride < (size_t)pitch * height)
+      return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
+  }
+  // the planes this call makes: rows padded to 16 bytes, n left then n right
+  const int g_pitch = n > 0 ? (width + 15) & ~15 : 0;
+  const size_t g_stride = ((size_t)g_pitch * (n > 0 ? height : 0) + 255) & ~(size_t)255;
+  BatchPlan plan;
+  if ((rc = batch_check(c, family, true, n, width, height, g_pitch, g_stride, det, flow, &plan)) != SF_OK) return rc;
+  if (n == 0) {
+    if (first_slot_out) *first_slot_out = c->store.slots;
+    if (first_nn_row_out) *first_nn_row_out = c->nn_local.n;
+    return SF_OK;
+  }
+  const int dims = c->params.netvlad_dimensions, pca_dim = sf_netvlad_pca_dim(c);
+  if (pca_dim == 0) return sf_fail(c, SF_EINVAL, "no NetVLAD model loaded (sf_netvlad_load)");
+  if (dims < 1 || dims > pca_dim)
+    return sf_fail(c, SF_EINVAL, "netvlad_dimensions %d is beyond the loaded model's %d WPCA outputs", dims, pca_dim);
+  if ((rc = sf_netvlad_check(c, n, height, width, dims)) != SF_OK) return rc;
+  if ((rc = sf_nn_reserve_rows(c, c->nn_local, n, dims)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->img_gray, 2 * (size_t)n * g_stride)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->img_desc, (size_t)n * dims * sizeof(float))) != SF_OK) return rc;
+  if ((rc = batch_reserve(c, n, width, height, &plan)) != SF_OK) return rc;
+  uint8_t* g_left = (uint8_t*)c->img_gray.p;
+  uint8_t* g_right = g_left + (size_t)n * g_stride;
+  if ((rc = sf_launch_image_gray(c, d_left, d_right, n, format, c->gray_rule, width, height, pitch, image_stride, 2 * n, g_left,
+                                 g_pitch, g_stride)) != SF_OK)
+    return rc;
+  if ((rc = sf_netvlad_infer_u8_batch_impl(c, d_rgb ? d_rgb : d_left, format, n, height, width, pitch, image_stride,
+                                           (float*)c->img_desc.p, dims)) != SF_OK)
+    return rc;
+  int32_t slot = -1;
+  if ((rc = batch_launch(c, plan, g_left, g_right, n, width, height, g_pitch, g_stride, cam, &slot, d_rows_out, d_desc_out,
+                         d_xyz_out, d_kpts_out)) != SF_OK)
+    return rc;
+  const int row = c->nn_local.n;
+  if ((rc = sf_nn_append(c, c->nn_local, c->img_desc.p, n, dims, 1)) != SF_OK) {
+    c->store.slots -= n;             // (the slots' rows stay behind the end of the store: the keyframes were never added)
+    return rc;
+  }
+  if (first_slot_out) *first_slot_out = slot;
+  if (first_nn_row_out) *first_nn_row_out = row;
+  return SF_OK;
+}
+
+extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                int32_t height, int32_t pitch, size_t image_stride,
+                                                const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, BATCH_GENERIC, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_add_keyframes_orb_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                    const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                    int32_t height, int32_t pitch, size_t image_stride,
+                                                    const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                    const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                    int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                    float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, BATCH_ORB, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_add_keyframes_surf_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                     const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                     int32_t height, int32_t pitch, size_t image_stride,
+                                                     const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                     const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                     int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                     float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, BATCH_SURF, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+extern "C" int sf_add_keyframes_sift_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
+                                                     const uint8_t* d_rgb, int32_t format, int32_t n_keyframes, int32_t width,
+                                                     int32_t height, int32_t pitch, size_t image_stride,
+                                                     const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                     const sf_stereo_flow_params* flow, int32_t* first_slot_out,
+                                                     int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                     float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  return add_keyframes_batch(c, BATCH_SIFT, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
