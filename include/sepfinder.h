@@ -99,6 +99,10 @@ extern "C" {
 /* 8, additions: sf_get_features_and_descriptor_sift_batch_device, sf_add_keyframes_sift_u8_batch_device,
       sf_sift_batch_status (the batch forms of Vis/FeatureType 1).  The six existing batch calls still refuse a type-1
       handle, now naming these; nothing existing changed, the version number, sizeof(sf_params) and SF_K_COUNT stay.  */
+/* 8, additions: sf_params.desc_type 2 (uint8 rows of 128 dimensions compared by L2, desc_bytes 128; sf_create refused the
+      value before), SF_DESC_BYTES_U8, sf_set_feature_type_sift on such a handle (SIFT rows as uint8), sf_debug_knn2_u8
+      (sf_experimental.h).  Handles with desc_type 0 or 1 are untouched; the version number, sizeof(sf_params) and
+      SF_K_COUNT stay.                                                                                                 */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -116,6 +120,7 @@ enum {
 #define SF_MAX_FEATURES   32767  /* KeyPoint3DVec.msg:1 / KeyPointVec.msg:1  `int16 size`   */
 #define SF_MAX_DESC_BYTES 64     /* 512-bit binary descriptors (BASELINE.json configs[4])   */
 #define SF_MAX_DESC_BYTES_F32 512 /* float32 descriptors (desc_type 1): 64 or 128 dimensions  */
+#define SF_DESC_BYTES_U8 128     /* uint8 descriptors compared by L2 (desc_type 2): 128 dimensions */
 
 /* ---- parameters -------------------------------------------------------------------------- */
 typedef struct sf_params {
@@ -184,7 +189,12 @@ typedef struct sf_params {
      1 = float32 rows (SURF / SIFT: `desc` points at rows x dims float32, `cols` = 4 * dims with dims = 64 or 128):
      brute-force kNN-2 on the L2 distance with the same NNDR / uniqueness / window rules -- squared distances in the
      global matching (myRegistrationVis.cpp:839-854 -> VWDictionary::addNewWords [upstream]), cv::BFMatcher(NORM_L2)
-     distances in the guided matching (:739-749).  north_star's "ORB/SURF ... Hamming/L2 matching".               */
+     distances in the guided matching (:739-749).  north_star's "ORB/SURF ... Hamming/L2 matching".
+     2 = uint8 rows compared by L2 (SIFT: `desc` points at rows x 128 uint8, `cols` = desc_bytes = 128; sf_create turns
+     the default desc_bytes 32 into 128, any other width is SF_EINVAL): the rules and the results of type 1 on the same
+     integers held as float32 -- a squared distance of 128 such differences is an integer below 2^24, exact in float32
+     in any order -- computed in int32, the global matching on the int8 matrix cores (k_match_u8.hip).  A quarter of
+     the bytes of type 1, and rows the reference's CV_8U wire can carry.  Stage kernels only, as type 1.             */
   int32_t desc_type;               /* 0 */
   /* Vis/CorGuessMatchToProjection: 0 = the guided pass matches every projected "from" point to the "to" keypoints in
      its window (myRegistrationVis.cpp:667-818); 1 = it matches every "to" keypoint to the projections in its window
@@ -607,7 +617,9 @@ int  sf_detect_surf_device(sf_handle h, const uint8_t* d_image, int32_t width, i
    sf_get_features_and_descriptor and its _u8 form run detector, sub-pixel refinement when it is on, LK or block matching,
    extraction (which reuses the detector's pyramid).  The batch forms are sf_get_features_and_descriptor_sift_batch_device
    and sf_add_keyframes_sift_u8_batch_device; the batch calls of the other types refuse a type-1 handle (the batch form of
-   type 1 is not built into them).  NOT BUILT under type 1 and refused with SF_EINVAL: Vis/RoiRatios and a grid of cells. */
+   type 1 is not built into them).  NOT BUILT under type 1 and refused with SF_EINVAL: Vis/RoiRatios and a grid of cells.
+   On a handle created with desc_type 2 (desc_bytes 128) every one of these calls does the same and writes the row's 128
+   integers as uint8 (128 bytes): the same keypoints, 3D points and row values, d_desc_out rows x 128 uint8.            */
 typedef struct sf_sift_params {
   int32_t n_features;          /* SIFT/NFeatures, 0; >= 0                         */
   int32_t n_octave_layers;     /* SIFT/NOctaveLayers, 3; 1 .. 8                   */
@@ -617,7 +629,8 @@ typedef struct sf_sift_params {
 } sf_sift_params;              /* 20 bytes */
 void sf_sift_defaults(sf_sift_params* p);
 /* Selects Vis/FeatureType 1 (sift NULL = defaults) on any handle with desc_type 1 and desc_bytes 512, whatever its current
-   type (6, 0 with extended rows, or 1); sf_set_feature_type_surf with extended = 1 leads back likewise.  Out-of-range
+   type (6, 0 with extended rows, or 1); sf_set_feature_type_surf with extended = 1 leads back likewise.  Also on a
+   handle with desc_type 2 (uint8 rows; type 6 before, 1 after: no other type writes such rows).  Out-of-range
    parameters and any other handle return SF_EINVAL and change nothing.  sf_get_feature_type reports 1 afterwards.      */
 int  sf_set_feature_type_sift(sf_handle h, const sf_sift_params* sift);
 int  sf_get_sift_params(sf_handle h, sf_sift_params* out);

@@ -152,6 +152,14 @@ int  sf_sift_batch_plan(int32_t width, int32_t height, const sf_sift_params* par
    pyramid with it.  SF_EINVAL: no such call, or no such plane.                                                       */
 int  sf_debug_sift_plane(sf_handle h, int32_t octave, int32_t layer, int32_t dog, int16_t* d_out);
 
+/* The kNN-2 scan of the global matching of uint8 L2 rows (desc_type 2; k_match_u8.hip) for one pair of store slots,
+   without the acceptance test: for every row t of the keyframe in slot_to, d_best[t] / d_second[t] = the smallest /
+   second smallest squared L2 distance to the rows of slot_from (equal where the smallest occurs twice; 2^31 - 1 where
+   there is no such row) and i_best[t] = the lowest row of slot_from at the smallest distance (-1: slot_from is empty).
+   Host arrays of at least the "to" keyframe's rows; waits for the stream.  SF_EINVAL: another desc_type, a slot outside
+   the store.                                                                                                          */
+int  sf_debug_knn2_u8(sf_handle h, int32_t slot_from, int32_t slot_to, int32_t* d_best, int32_t* d_second, int32_t* i_best);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ SF_OK, SF_EINVAL, SF_EHIP, SF_ENOMEM, SF_ERANGE, SF_ENODEV, SF_ERCCL = range(7)
 SF_MAX_FEATURES = 32767
 SF_MAX_DESC_BYTES = 64
 SF_MAX_DESC_BYTES_F32 = 512
+SF_DESC_BYTES_U8 = 128     # uint8 rows compared by L2 (sf_params.desc_type 2)
 
 (SF_K_MATCH, SF_K_RANSAC1, SF_K_GUIDED, SF_K_RANSAC2, SF_K_NN, SF_K_NN_SELECT, SF_K_NN_FILTER,
  SF_K_NN_REFINE, SF_K_FUSED, SF_K_NN_WALK, SF_K_BA, SF_K_GUIDED_TP, SF_K_COUNT) = range(13)
@@ -311,7 +312,7 @@ def surf_params(hessian_threshold=500.0, n_octaves=4, n_octave_layers=2, upright
 
 
 SURF_ORI_SAMPLES, SURF_PATCH = 109, 20
-FEATURE_SIFT = 1         # ... and of sf_set_feature_type_sift (a handle with desc_type 1 and desc_bytes 512)
+FEATURE_SIFT = 1         # ... and of sf_set_feature_type_sift (a handle with desc_type 1 and desc_bytes 512, or desc_type 2)
 
 
 class SiftParams(C.Structure):

@@ -481,9 +481,9 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
   if (kind.freak && (orb || bytes != FREAK_BYTES)) return sf_fail(c, SF_EINVAL, "FREAK rows are %d bytes, not %d", FREAK_BYTES, bytes);
   if (kind.surf && (orb || kind.freak || bytes != (kind.surf->extended ? 512 : 256)))
     return sf_fail(c, SF_EINVAL, "SURF rows are %d bytes, not %d", kind.surf->extended ? 512 : 256, bytes);
-  if (kind.has_sift && (orb || kind.freak || kind.surf || bytes != 512 || (n_img != 1 && !kind.sift.batch)))
-    return sf_fail(c, SF_EINVAL, "SIFT rows are 512 bytes, one keyframe per call unless the detector has left the chunk's pyramids (not %d bytes, %d keyframes)",
-                   bytes, n_img);
+  if (kind.has_sift && (orb || kind.freak || kind.surf || bytes != (kind.sift.u8 ? SF_DESC_BYTES_U8 : 512) || (n_img != 1 && !kind.sift.batch)))
+    return sf_fail(c, SF_EINVAL, "SIFT rows are %d bytes, one keyframe per call unless the detector has left the chunk's pyramids (not %d bytes, %d keyframes)",
+                   kind.sift.u8 ? SF_DESC_BYTES_U8 : 512, bytes, n_img);
   const size_t rows_all = (size_t)std::max(n, 1) * n_img;
   if ((rc = sf_buf_reserve(c, c->ex_desc, rows_all * bytes)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->ex_xyz, rows_all * 12)) != SF_OK) return rc;

@@ -227,7 +227,19 @@ __device__ __forceinline__ bool guided_finish(const StoreView& st, int pair, int
 // compared by their L2 distance -- sqrtf of the float32 sum of squared differences in dimension order, as
 // cv::BFMatcher(NORM_L2) reports it (:739-749) -- in the per-lane search loop (same tests, same decisions; the
 // candidate-parallel pass with its packed 32-bit keys is the binary descriptors').
-template <int W, bool L2 = false, int NW = 4>
+// U8 (with L2): uint8 rows of 4 W dimensions (desc_type 2).  The sum of squared differences is taken in integers -- it is
+// below 2^24 for 128 dimensions, so it is the float32 sum of the same integers held as float32, whatever the order -- and
+// goes through the float rows' own expressions from there.
+__device__ __forceinline__ uint32_t sqdiff_u8(uint32_t a, uint32_t b, uint32_t acc) {
+#pragma unroll
+  for (int k = 0; k < 32; k += 8) {
+    const int d = (int)((a >> k) & 255u) - (int)((b >> k) & 255u);
+    acc += (uint32_t)(d * d);
+  }
+  return acc;
+}
+
+template <int W, bool L2 = false, int NW = 4, bool U8 = false>
 __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int sF, int sT, const PassState& pass1,
                                             PassState& pass2_out, uint8_t& guided_flag_out, uint32_t* out,
                                             CorrHeader& hdr_out, int32_t* __restrict__ list,
@@ -652,10 +664,17 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
             const uint32_t* r = dT + (size_t)t * W;
             if constexpr (L2) {
               float sq = 0.f;
+              if constexpr (U8) {
+                uint32_t isq = 0u;
+#pragma unroll
+                for (int c = 0; c < W; ++c) isq = sqdiff_u8(q[c], r[c], isq);
+                sq = (float)isq;
+              } else {
 #pragma unroll
               for (int c = 0; c < W; ++c) {
                 const float dd = __uint_as_float(q[c]) - __uint_as_float(r[c]);
                 sq = sq + dd * dd;
+              }
               }
               const float d = sqrtf(sq);
               // (candidates arrive in grid order, not in "to" order: the better of two equal distances is the lower row,
@@ -698,7 +717,7 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
   return survivor;
 }
 
-template <int W, bool L2 = false>
+template <int W, bool L2 = false, bool U8 = false>
 __global__ void __launch_bounds__(SF_BLOCK)
 k_guided(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
          const PassState* __restrict__ pass1, PassState* __restrict__ pass2, uint8_t* __restrict__ guided_flag,
@@ -706,8 +725,8 @@ k_guided(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __r
          int32_t* __restrict__ counter, DeviceParams P) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
   const int pair = (int)blockIdx.x;
-  guided_body<W, L2>(st, pair, pair_from[pair], pair_to[pair], pass1[pair], pass2[pair], guided_flag[pair],
-                     corr + (size_t)pair * st.kcap, hdr[pair], list, counter, P, smem);
+  guided_body<W, L2, 4, U8>(st, pair, pair_from[pair], pair_to[pair], pass1[pair], pass2[pair], guided_flag[pair],
+                            corr + (size_t)pair * st.kcap, hdr[pair], list, counter, P, smem);
 }
 
 // ---- pass 2 with Vis/CorGuessMatchToProjection = true (myRegistrationVis.cpp:521-666): every "to" keypoint is matched
@@ -728,7 +747,7 @@ k_guided(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __r
 // candidate list and no cap: every frame the store holds takes the same path.  A "from" point's claims are one LDS
 // word: the first claimer's "to" index (atomicCAS on the empty word), bit 31 once a second one arrives -- "exactly one"
 // without depending on which lane came first.  The compaction is guided_body's.
-template <int W, bool L2>
+template <int W, bool L2, bool U8 = false>
 __device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, int sF, int sT, const PassState& pass1,
                                                PassState& pass2_out, uint8_t& guided_flag_out, uint32_t* out,
                                                CorrHeader& hdr_out, int32_t* __restrict__ list,
@@ -854,6 +873,15 @@ __device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, in
         const uint4* pt = reinterpret_cast<const uint4*>(r);
         if constexpr (L2) {
           float sq = 0.f;
+          if constexpr (U8) {
+            uint32_t isq = 0u;
+#pragma unroll
+            for (int q4 = 0; q4 < W / 4; ++q4) {
+              const uint4 a = pt[q4], b = pf[q4];
+              isq = sqdiff_u8(a.w, b.w, sqdiff_u8(a.z, b.z, sqdiff_u8(a.y, b.y, sqdiff_u8(a.x, b.x, isq))));
+            }
+            sq = (float)isq;
+          } else {
 #pragma unroll 8
           for (int q4 = 0; q4 < W / 4; ++q4) {
             const uint4 a = pt[q4], b = pf[q4];
@@ -861,6 +889,7 @@ __device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, in
             dd = __uint_as_float(a.y) - __uint_as_float(b.y); sq = sq + dd * dd;
             dd = __uint_as_float(a.z) - __uint_as_float(b.z); sq = sq + dd * dd;
             dd = __uint_as_float(a.w) - __uint_as_float(b.w); sq = sq + dd * dd;
+          }
           }
           // (cells are visited in grid order, not in index order: of two equal distances the lower index is the best)
           if (sq < f0 || (sq == f0 && i < i0)) { f1 = f0; f0 = sq; i0 = i; }
@@ -898,7 +927,7 @@ __device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, in
                            list, counter, P, misc);
 }
 
-template <int W, bool L2 = false>
+template <int W, bool L2 = false, bool U8 = false>
 __global__ void __launch_bounds__(SF_BLOCK)
 k_guided_tp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
             const PassState* __restrict__ pass1, PassState* __restrict__ pass2, uint8_t* __restrict__ guided_flag,
@@ -906,8 +935,8 @@ k_guided_tp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* 
             int32_t* __restrict__ counter, DeviceParams P) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
   const int pair = (int)blockIdx.x;
-  guided_tp_body<W, L2>(st, pair, pair_from[pair], pair_to[pair], pass1[pair], pass2[pair], guided_flag[pair],
-                        corr + (size_t)pair * st.kcap, hdr[pair], list, counter, P, smem);
+  guided_tp_body<W, L2, U8>(st, pair, pair_from[pair], pair_to[pair], pass1[pair], pass2[pair], guided_flag[pair],
+                            corr + (size_t)pair * st.kcap, hdr[pair], list, counter, P, smem);
 }
 
 // ---- result assembly: myRegistration.cpp:279-295 covariance clamp + MsgConversion.cpp:61-81 ------
@@ -1008,11 +1037,11 @@ static size_t sf_guided_tp_lds_bytes(int kcap, int n_cells) {
 }
 
 // Vis/CorGuessMatchToProjection = true: k_guided_tp in place of k_guided (same inputs, same outputs)
-template <int W, bool L2>
+template <int W, bool L2, bool U8 = false>
 static int launch_guided_tp(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, size_t lds) {
   if (lds > 64 * 1024)   // (K > ~3 000 features: above the default dynamic LDS limit; never at the bench's K = 500)
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_guided_tp<W, L2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((k_guided_tp<W, L2>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
+    SF_HIP(c, hipFuncSetAttribute((const void*)k_guided_tp<W, L2, U8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipLaunchKernelGGL((k_guided_tp<W, L2, U8>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
                      (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p, (uint32_t*)c->w->corr2.p,
                      (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, (int32_t*)c->w->counters.p + 2, c->dparams);
   return SF_OK;
@@ -1025,7 +1054,9 @@ static int sf_launch_guided_tp(sf_context* c, StoreView st, const int32_t* d_fro
                    st.kcap, lds);
   sf_prof_begin(c, SF_K_GUIDED_TP);
   int rc;
-  if (c->params.desc_type == 1)
+  if (c->params.desc_type == 2)         // uint8 rows, L2: 32 dwords
+    rc = launch_guided_tp<32, true, true>(c, st, d_from, d_to, n, lds);
+  else if (c->params.desc_type == 1)
     rc = st.w == 64 ? launch_guided_tp<64, true>(c, st, d_from, d_to, n, lds) : launch_guided_tp<128, true>(c, st, d_from, d_to, n, lds);
   else
     rc = st.w == 8 ? launch_guided_tp<8, false>(c, st, d_from, d_to, n, lds) : launch_guided_tp<16, false>(c, st, d_from, d_to, n, lds);
@@ -1042,7 +1073,11 @@ int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const i
   const size_t lds = sf_guided_lds_bytes(st.kcap, nc);
   int32_t* counters = (int32_t*)c->w->counters.p;
   sf_prof_begin(c, SF_K_GUIDED);
-  if (c->params.desc_type == 1) {
+  if (c->params.desc_type == 2) {       // uint8 rows, L2: 32 dwords
+    hipLaunchKernelGGL((k_guided<32, true, true>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
+                       (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
+                       (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2, c->dparams);
+  } else if (c->params.desc_type == 1) {
     if (st.w == 64)
       hipLaunchKernelGGL((k_guided<64, true>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
                          (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,

@@ -1302,6 +1302,7 @@ void launch_match_l2(sf_context* c, StoreView st, const int32_t* d_from, const i
 
 int sf_launch_match_global(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   if (n <= 0) return SF_OK;
+  if (c->params.desc_type == 2) return sf_launch_match_global_u8(c, st, d_from, d_to, n);   // uint8 rows, L2: k_match_u8.hip
   if (c->params.desc_type == 1) {       // float32 rows: exact L2 on the VALU (north_star: MFMA only for the NetVLAD matrix)
     sf_prof_begin(c, SF_K_MATCH);
     if (st.w == 64) launch_match_l2<64>(c, st, d_from, d_to, n);

@@ -476,7 +476,8 @@ __global__ void __launch_bounds__(256)
 k_sift_describe(SfSiftPlan P, const short* __restrict__ gauss, const sf_keypoint* __restrict__ kpts, const float* __restrict__ right_x,
                 const uint8_t* __restrict__ status, int n, ExtractCam cam, sf_keypoint* __restrict__ kpts_out,
                 float* __restrict__ desc_tmp, float* __restrict__ xyz_tmp, uint8_t* __restrict__ keep, ExtractBatch B,
-                size_t plane_stride) {
+                size_t plane_stride, int rows_u8) {
+  // rows_u8: desc_tmp holds rows of SIFT_DIMS uint8 (a handle with desc_type 2), not of SIFT_DIMS float32
   __shared__ unsigned long long s_bins[SIFT_HIST];
   __shared__ float s_row[SIFT_DIMS];
   const int tid = threadIdx.x, i = blockIdx.x;
@@ -488,7 +489,7 @@ k_sift_describe(SfSiftPlan P, const short* __restrict__ gauss, const sf_keypoint
     kpts += o; kpts_out += o;
     if (right_x) right_x += o;
     if (status) status += o;
-    desc_tmp += o * SIFT_DIMS; xyz_tmp += 3 * o; keep += o;
+    desc_tmp += rows_u8 ? o * (SIFT_DIMS / 4) : o * SIFT_DIMS; xyz_tmp += 3 * o; keep += o;
   }
   const sf_keypoint k = kpts[i];
   // (every thread holds the same keypoint: the conditions around the barriers below are the same in every thread)
@@ -581,7 +582,9 @@ k_sift_describe(SfSiftPlan P, const short* __restrict__ gauss, const sf_keypoint
     }
     const float scale = 512.0f / fmaxf((float)sqrt(nrm2), FLT_EPSILON);
     const float r = rintf(val * scale);
-    desc_tmp[(size_t)i * SIFT_DIMS + tid] = r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r);
+    const float clamped = r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r);
+    if (rows_u8) reinterpret_cast<uint8_t*>(desc_tmp)[(size_t)i * SIFT_DIMS + tid] = (uint8_t)(int)clamped;   // (an integer in 0 .. 255: exact)
+    else desc_tmp[(size_t)i * SIFT_DIMS + tid] = clamped;
   }
   if (tid != 0) return;
   kpts_out[i] = k;
@@ -951,7 +954,7 @@ int sf_launch_sift_describe(sf_context* c, const uint8_t* d_left, int pitch, int
         c->sift_planes.bytes < (size_t)bp.chunk * bp.plane_bytes)
       return sf_fail(c, SF_EINVAL, "SIFT batch: the chunk's pyramids are not the detector's");
     hipLaunchKernelGGL(k_sift_describe, dim3((unsigned)n, (unsigned)n_img), dim3(256), 0, c->stream, bp.P, (const short*)c->sift_planes.p,
-                       d_kpts, d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep, B, bp.plane_bytes / 2);
+                       d_kpts, d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep, B, bp.plane_bytes / 2, (int)kind.u8);
     return SF_OK;
   }
   const sf_sift_params& b = c->sift_last_prm;
@@ -960,7 +963,7 @@ int sf_launch_sift_describe(sf_context* c, const uint8_t* d_left, int pitch, int
   int rc;
   if (!reuse && (rc = sf_sift_build_pyramid(c, d_left, width, height, pitch, &kind.prm)) != SF_OK) return rc;
   hipLaunchKernelGGL(k_sift_describe, dim3((unsigned)n), dim3(256), 0, c->stream, c->sift_last, (const short*)c->sift_planes.p, d_kpts,
-                     d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep, B, (size_t)0);
+                     d_right_x, d_status, n, cam, d_kpts_out, desc_tmp, xyz_tmp, keep, B, (size_t)0, (int)kind.u8);
   return SF_OK;
 }
 

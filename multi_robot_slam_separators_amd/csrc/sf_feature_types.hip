@@ -126,8 +126,9 @@ extern "C" int sf_set_feature_type(sf_handle c, int32_t feature_type, const sf_o
   if (!t) return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d is not built (%s)", feature_type, built_types);
   if (t->takes)
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d (%s) takes %s: select it with %s", t->type, t->name, t->takes, t->setter);
-  // (the handle's own type needs no second look: a handle with desc_type 1 starts at GFTT/BRIEF and may stay)
-  if (t != &sf_type_of(c) && (rc = check_binary_rows(c, *t)) != SF_OK) return rc;
+  // (the handle's own type needs no second look: a handle with desc_type 1 starts at GFTT/BRIEF and may stay; on a
+  //  handle with desc_type 2 the starting type is asked like any other: only SIFT writes its rows)
+  if ((t != &sf_type_of(c) || c->params.desc_type == 2) && (rc = check_binary_rows(c, *t)) != SF_OK) return rc;
   if (t->rows == ROWS_ORB) {
     const sf_orb_params o = arg_or_defaults(orb, sf_orb_defaults);
     if ((rc = orb_validate(c, o)) != SF_OK) return rc;
@@ -345,7 +346,8 @@ extern "C" int sf_sift_check_params(const sf_sift_params* params) { return sf_si
 
 extern "C" int sf_set_feature_type_sift(sf_handle c, const sf_sift_params* sift) {
   if (!c) return SF_EINVAL;
-  if (c->params.desc_type != 1 || c->params.desc_bytes != 512)
+  const bool u8_rows = c->params.desc_type == 2 && c->params.desc_bytes == SF_DESC_BYTES_U8;   // (the same 128 integers as bytes)
+  if (!u8_rows && (c->params.desc_type != 1 || c->params.desc_bytes != 512))
     return sf_fail(c, SF_EINVAL, "SIFT writes 128 float32 per row: a handle with desc_type %d and desc_bytes %d cannot store them (create it with desc_type 1 and desc_bytes 512)",
                    c->params.desc_type, c->params.desc_bytes);
   const sf_sift_params p = arg_or_defaults(sift, sf_sift_defaults);
@@ -467,8 +469,9 @@ int sf_extract_kind(sf_context* c, ExtractKind* k) {
   *k = ExtractKind();
   if (t.binary_rows() && (rc = check_binary_rows(c, t)) != SF_OK) return rc;
   switch (t.rows) {
-    case ROWS_SIFT:                                        // (selected on a handle with desc_type 1 and 512-byte rows only)
-      k->bytes = 512; k->has_sift = true; k->sift.prm = c->sift;
+    case ROWS_SIFT:                                        // (selected on a handle with desc_type 1 and 512-byte rows, or desc_type 2, only)
+      k->sift.u8 = c->params.desc_type == 2;
+      k->bytes = k->sift.u8 ? SF_DESC_BYTES_U8 : 512; k->has_sift = true; k->sift.prm = c->sift;
       return SF_OK;
     case ROWS_SURF:                                        // (selected on a handle with desc_type 1 and these row bytes only)
       k->bytes = c->surf.extended ? 512 : 256; k->surf = &c->surf_dev;

@@ -161,13 +161,17 @@ int sf_fill_device_params(sf_context* c) {
     if (p.ba_iterations < 0 || !(p.ba_pixel_variance > 0.f) || !(p.ba_robust_kernel_delta > 0.f) || !(p.stereo_baseline >= 0.f))
       return sf_fail(c, SF_EINVAL, "bundle adjustment: ba_iterations >= 0, ba_pixel_variance > 0, ba_robust_kernel_delta > 0, stereo_baseline >= 0");
   }
-  if (p.desc_type != 0 && p.desc_type != 1) return sf_fail(c, SF_EINVAL, "desc_type %d unknown (0 = binary rows, 1 = float32 rows)", p.desc_type);
+  if (p.desc_type != 0 && p.desc_type != 1 && p.desc_type != 2)
+    return sf_fail(c, SF_EINVAL, "desc_type %d unknown (0 = binary rows, 1 = float32 rows, 2 = uint8 rows compared by L2)", p.desc_type);
   if (p.desc_type == 1 && p.desc_bytes != 256 && p.desc_bytes != 512 && p.desc_bytes != 32)
     return sf_fail(c, SF_EINVAL, "desc_type 1: desc_bytes %d (float32 rows of 64 or 128 dimensions: 256 or 512)", p.desc_bytes);
+  if (p.desc_type == 2 && p.desc_bytes != SF_DESC_BYTES_U8 && p.desc_bytes != 32)
+    return sf_fail(c, SF_EINVAL, "desc_type 2: desc_bytes %d (uint8 rows of 128 dimensions: %d)", p.desc_bytes, SF_DESC_BYTES_U8);
   // float32 descriptors with the width left at sf_default_params' 32 (a binary width): 64 dimensions.  The width only
   // matters before the first non-empty keyframe arrives -- an EMPTY first keyframe (the reference tolerates them: the
   // fake-words path) takes it for its row pitch, and 32 bytes per float row was refused by the store (round 4).
   if (p.desc_type == 1 && p.desc_bytes == 32) c->params.desc_bytes = 256;
+  if (p.desc_type == 2 && p.desc_bytes == 32) c->params.desc_bytes = SF_DESC_BYTES_U8;   // (the same for uint8 rows: the one width)
   if (p.guess_match_to_projection != 0 && p.guess_match_to_projection != 1)
     return sf_fail(c, SF_EINVAL, "guess_match_to_projection %d unknown (0 = projections to frame, 1 = frame to projections)",
                    p.guess_match_to_projection);

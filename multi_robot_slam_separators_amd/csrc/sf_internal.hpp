@@ -16,7 +16,8 @@
 #define SF_STEP_MAX_LANES 4      // ... dealt over at most this many streams (SF_OPT_STEP_LANES)
 
 // ---- device-resident keyframe store (one arena per field, fixed per-slot stride) ---------------
-// desc : [slots][kcap][W] uint32   W = 8 (<=256-bit descriptors) or 16 (<=512-bit), zero padded
+// desc : [slots][kcap][W] uint32   W = 8 (<=256-bit descriptors) or 16 (<=512-bit), zero padded; float32 rows (desc_type 1)
+//                                  W = 64 or 128, one dimension per dword; uint8 L2 rows (desc_type 2) W = 32, four per dword
 // xyz  : [slots][kcap][3] float    wire layout of KeyPoint3DVec (base frame)
 // kp   : [slots][kcap]    float4   {pt.x, pt.y, bit-cast sign-extended (octave & 255), 0}
 // meta : [slots]          int4     {rows, n3d, nkp, cols}
@@ -244,6 +245,7 @@ struct SfSiftKind {
   sf_sift_params prm = {};
   bool reuse = false;
   bool batch = false;
+  bool u8 = false;             // the rows as 128 uint8 (a handle with desc_type 2), not as 128 float32
 };
 struct SfSiftPlan {
   int n_octaves = 0, n_layers = 0;
@@ -709,6 +711,8 @@ inline int sf_detector_work(sf_context* c, int width, int height, int n_img, siz
 // ---- kernel launchers (one per translation unit) -----------------------------------------------
 // Pass-1 global matching for n pairs; also writes PassState defaults and the RANSAC work list.
 int sf_launch_match_global(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n);
+// the same for uint8 rows compared by L2 (desc_type 2; k_match_u8.hip), which sf_launch_match_global hands on to it
+int sf_launch_match_global_u8(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n);
 // RANSAC for the pairs in work list `list` (count in counters[ctr]); pass = 1 or 2.
 int sf_launch_ransac(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass);
 // PnP (estimation_type = 1) for the pairs in the same work lists.
@@ -786,7 +790,7 @@ struct ExtractKind {
   size_t pyr_stride = 0;
   const SfFreakTables* freak = nullptr;   // not null: FREAK rows (bytes 64; d_tests, orb and pyr unused)
   const SfSurfTables* surf = nullptr;     // not null: SURF rows (bytes 256 or 512, float32; the rest unused)
-  bool has_sift = false;                  // true: SIFT rows (bytes 512, float32; `sift` says how, the rest unused)
+  bool has_sift = false;                  // true: SIFT rows (bytes 512, float32, or 128 with sift.u8; `sift` says how, the rest unused)
   SfSiftKind sift;                        // read under has_sift: one image per call, or the chunk the batch detector has left
   // sf_launch_detect_surf_batch has left the integral images of the call's images in c->ex_integral: the extraction reads
   // them there and builds none (as pyr_stride for ORB's pyramids)

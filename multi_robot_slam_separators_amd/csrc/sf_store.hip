@@ -107,16 +107,24 @@ k_ingest_ragged(uint32_t* __restrict__ desc, float* __restrict__ xyz, float4* __
 
 }  // namespace
 
-// dwords per stored descriptor row: binary rows 8 (<= 256 bits) or 16; float32 rows (desc_type 1) one per dimension
+// dwords per stored descriptor row: binary rows 8 (<= 256 bits) or 16; float32 rows (desc_type 1) one per dimension;
+// uint8 L2 rows (desc_type 2) four dimensions per dword
 static int desc_dwords(const sf_context* c, int cols) {
-  if (c->params.desc_type == 1) return cols / 4;
+  if (c->params.desc_type != 0) return cols / 4;
   return cols <= 32 ? 8 : 16;
+}
+// the widest row a keyframe of the handle's descriptor type may have
+static int max_desc_bytes(const sf_context* c) {
+  return c->params.desc_type == 1 ? SF_MAX_DESC_BYTES_F32 : c->params.desc_type == 2 ? SF_DESC_BYTES_U8 : SF_MAX_DESC_BYTES;
 }
 
 int sf_store_reserve(sf_context* c, Store& s, int slots_needed, int rows, int cols) {
   if (c->params.desc_type == 1) {
     if (cols != 256 && cols != 512)
       return sf_fail(c, SF_ERANGE, "float32 descriptors: %d bytes per row (64 or 128 dimensions = 256 or 512 bytes)", cols);
+  } else if (c->params.desc_type == 2) {
+    if (cols != SF_DESC_BYTES_U8)
+      return sf_fail(c, SF_ERANGE, "uint8 L2 descriptors: %d bytes per row (128 dimensions = %d bytes)", cols, SF_DESC_BYTES_U8);
   } else if (cols < 1 || cols > SF_MAX_DESC_BYTES) {
     return sf_fail(c, SF_ERANGE, "descriptor bytes %d not in 1..%d", cols, SF_MAX_DESC_BYTES);
   }
@@ -318,8 +326,8 @@ int sf_store_add_host_batch(sf_context* c, Store& st, const sf_features* const* 
     if (feats[i]->rows > 0) {
       if (cols == 0) cols = feats[i]->cols;
       if (desc_dwords(c, feats[i]->cols) != desc_dwords(c, cols)) return sf_fail(c, SF_EINVAL, "descriptor width classes differ inside one batch");
-      if (feats[i]->cols > (c->params.desc_type == 1 ? SF_MAX_DESC_BYTES_F32 : SF_MAX_DESC_BYTES))
-        return sf_fail(c, SF_ERANGE, "descriptor bytes %d > %d", (int)feats[i]->cols, c->params.desc_type == 1 ? SF_MAX_DESC_BYTES_F32 : SF_MAX_DESC_BYTES);
+      if (feats[i]->cols > max_desc_bytes(c))
+        return sf_fail(c, SF_ERANGE, "descriptor bytes %d > %d", (int)feats[i]->cols, max_desc_bytes(c));
     }
   }
   if (cols == 0) cols = st.slots > 0 ? st.w * 4 : std::max(1, c->params.desc_bytes);

@@ -174,6 +174,7 @@ def load():
         "sf_debug_correspondences": (C.c_int, [vp, i32, i32, vp, vp, i32, P(i32)]),
         "sf_debug_pass_state": (C.c_int, [vp, i32, i32, vp, P(i32), P(i32), P(i32)]),
         "sf_debug_counters": (C.c_int, [vp, vp, i32]),
+        "sf_debug_knn2_u8": (C.c_int, [vp, i32, i32, vp, vp, vp]),
         "sf_debug_guided_points": (C.c_int, [vp, i32, vp, vp, P(i32)]),
         "sf_debug_plan_workspace": (C.c_int, [P(_abi.Params), i32, i32, i32, i32, i32, P(i64), i32]),
         "sf_pack_separators": (C.c_int, [vp, i32, C.c_int8, C.c_int8, vp, vp, vp, vp, vp]),
@@ -261,6 +262,7 @@ EXPORTED = [
     "sf_debug_sift_limits", "sf_debug_sift_plane",
     "sf_get_features_and_descriptor_sift_batch_device", "sf_add_keyframes_sift_u8_batch_device", "sf_sift_batch_status",
     "sf_debug_sift_batch_chunk", "sf_sift_batch_plan",
+    "sf_debug_knn2_u8",
 ]
 
 
@@ -603,7 +605,8 @@ class SeparatorFinder:
 
     def set_feature_type_sift(self, sift=None):
         """Vis/FeatureType 1 (SIFT) with sift (_abi.SiftParams; None = rtabmap's SIFT/ defaults) on a handle created with
-        desc_type 1 and desc_bytes 512: float32 rows of 128 dimensions."""
+        desc_type 1 and desc_bytes 512: float32 rows of 128 dimensions -- or with desc_type 2 (desc_bytes 128): the same
+        128 integers per row as uint8."""
         self._check(self._L.sf_set_feature_type_sift(self._h, C.byref(sift) if sift is not None else None))
 
     def get_sift_params(self):
@@ -633,7 +636,7 @@ class SeparatorFinder:
         if self.get_feature_type()[0] == _abi.FEATURE_SURF:
             return 512 if self.get_surf_params().extended else 256
         if self.get_feature_type()[0] == _abi.FEATURE_SIFT:
-            return 512
+            return _abi.SF_DESC_BYTES_U8 if self.params.desc_type == 2 else 512
         if self.get_feature_type()[0] in (_abi.FEATURE_FAST_FREAK, _abi.FEATURE_GFTT_FREAK):
             return _abi.FREAK_BYTES
         return 32 if self.get_feature_type()[0] in (_abi.FEATURE_GFTT_ORB, _abi.FEATURE_ORB) else self.brief_get_pattern().shape[0] // 8
@@ -1144,6 +1147,17 @@ class SeparatorFinder:
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._L.sf_debug_pass_state(self._h, pair, which_pass, T.ctypes.data, C.byref(a), C.byref(b), C.byref(c)))
         return T.reshape(3, 4), a.value, b.value, c.value
+
+    def debug_knn2_u8(self, slot_from, slot_to, rows_to):
+        """sf_debug_knn2_u8 (include/sf_experimental.h; a handle with desc_type 2): the kNN-2 scan of the uint8 L2 matcher
+        for one pair of store slots -> (d_best, d_second, i_best), int32 [rows_to]: per row of the "to" keyframe (rows_to =
+        its rows) the smallest and second smallest squared distance to the "from" rows (2^31 - 1: none) and the lowest
+        "from" row at the smallest (-1: none).  The integers a desc_type 1 handle computes in float32 on the float twin
+        (rows.astype(float32)) -- which is how the oracle, which knows desc_type 0 and 1 only, is asked about such rows:
+        desc_type 1, desc_bytes 512, the rows as float32."""
+        d1 = np.zeros(max(rows_to, 1), np.int32); d2 = np.zeros_like(d1); i1 = np.zeros_like(d1)
+        self._check(self._L.sf_debug_knn2_u8(self._h, slot_from, slot_to, d1.ctypes.data, d2.ctypes.data, i1.ctypes.data))
+        return d1[:rows_to], d2[:rows_to], i1[:rows_to]
 
     def debug_guided_points(self, pair, kcap=4096):
         a = np.zeros(kcap, dtype=np.uint64); b = np.zeros(kcap, dtype=np.uint64)

@@ -131,6 +131,19 @@ def float_descriptors(fa, dims, rng=None, jitter=0.0):
     return _abi.FeatureArrays(np.ascontiguousarray(bits, dtype=np.float32), fa.xyz, fa.kpts)
 
 
+def u8_descriptors(fa, dims, rng=None, jitter=0):
+    """The uint8-descriptor twin of a keyframe with binary descriptors (sf_params.desc_type 2; dims = 128): dimension d of a
+    row is 128 +- 64 by bit d of the binary descriptor, plus integer jitter uniform in -jitter .. jitter, clipped to
+    0 .. 255 -- integer rows as SIFT writes them.  A true partner's rows stay close to their originals (128^2 per flipped
+    bit), unrelated rows are ~128^2 * dims / 2 apart and, without jitter, distances tie often.  The oracle is asked about
+    such rows with desc_type 1 and desc_bytes 4 * dims on rows.astype(float32): the same integers, the same distances."""
+    bits = np.unpackbits(fa.desc, axis=1)[:, :dims].astype(np.int32)
+    rows = 64 + 128 * bits
+    if jitter > 0:
+        rows = rows + rng.integers(-jitter, jitter + 1, size=rows.shape)
+    return _abi.FeatureArrays(np.ascontiguousarray(np.clip(rows, 0, 255), dtype=np.uint8), fa.xyz, fa.kpts)
+
+
 def make_pairs(seed, n, k=500, cols=32, true_frac=0.2, overlap=0.4, noise=0.02, flip=0.05):
     """n candidate pairs (from=A, to=B).  Returns (list A, list B, is_true[n], T_gt list)."""
     rng = np.random.default_rng(seed)
