@@ -103,6 +103,10 @@ extern "C" {
       value before), SF_DESC_BYTES_U8, sf_set_feature_type_sift on such a handle (SIFT rows as uint8), sf_debug_knn2_u8
       (sf_experimental.h).  Handles with desc_type 0 or 1 are untouched; the version number, sizeof(sf_params) and
       SF_K_COUNT stay.                                                                                                 */
+/* 8, additions: sf_gftt_params, sf_gftt_defaults, sf_gftt_set_params, sf_gftt_get_params (GFTT/BlockSize,
+      GFTT/UseHarrisDetector, GFTT/K: the response of the GFTT detector, handle state read by sf_detect_corners_device and
+      by every extraction call under Vis/FeatureType 5, 6 and 8), sf_gftt_check_params (sf_experimental.h).  A fresh handle
+      holds (3, 0, 0.04), with which nothing existing changed; the version number, sizeof(sf_params) and SF_K_COUNT stay. */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -428,12 +432,13 @@ int  sf_netvlad_infer_batch_device(sf_handle h, const float* d_images_rgb, int32
                                    int32_t height, float* d_out, int32_t n_out);
 
 /* Corner detection of the reference's default feature type (rtabmap GFTT/BRIEF: Feature2D::generateKeypoints ->
-   cv::goodFeaturesToTrack, called from myRegistrationVis.cpp:281-283), on the device: minimum-eigenvalue response
-   (blockSize 3, Sobel 3), corners = local maxima above quality_level * max, strongest first, at least min_distance
-   apart, at most max_corners (<= 0: no limit).  d_kpts_out receives up to `cap` keypoints {x, y, size 3, angle -1,
-   response 0, octave 0, class_id -1} in that order; *n_out = corners found.  rtabmap's defaults: max_corners =
-   Vis/MaxFeatures (1000), quality_level 0.001, min_distance 3.  Synchronises the stream twice (candidate count,
-   result count).                                                                                              */
+   cv::goodFeaturesToTrack, called from myRegistrationVis.cpp:281-283), on the device: the response of the handle's
+   sf_gftt_params below (a fresh handle: minimum eigenvalue, blockSize 3; Sobel 3 always), corners = local maxima above
+   quality_level * max, strongest first, at least min_distance apart, at most max_corners (<= 0: no limit).  d_kpts_out
+   receives up to `cap` keypoints {x, y, size = block_size (3), angle -1, response 0, octave 0, class_id -1} in that
+   order; *n_out = corners found.  rtabmap's defaults: max_corners = Vis/MaxFeatures (1000), quality_level 0.001,
+   min_distance 3.  width, height >= max(3, block_size).  Synchronises the stream twice (candidate count, result
+   count).                                                                                                      */
 int  sf_detect_corners_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                               int32_t max_corners, double quality_level, double min_distance,
                               sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
@@ -457,6 +462,26 @@ void sf_fast_defaults(sf_fast_params* p);
    nothing.                                                                                                        */
 int  sf_fast_set_params(sf_handle h, const sf_fast_params* params);
 int  sf_fast_get_params(sf_handle h, sf_fast_params* params);
+/* The response of the GFTT detector (sf_detect_corners_device; Vis/FeatureType 5, 6 and 8): cv::cornerMinEigenVal /
+   cv::cornerHarris of OpenCV 3.2 as cv::goodFeaturesToTrack calls them [upstream, restated in tests/gftt_ref.py; DESIGN.md
+   section 3 lists what the restatement decides].  Sobel derivatives scaled by 1 / (4 * block_size * 255), their three
+   products A = sum dx dx, B = sum dx dy, C = sum dy dy over the block_size x block_size window whose first row and column
+   are y - block_size / 2 and x - block_size / 2 (BORDER_REFLECT_101; an even block leans up and left), float32, each
+   window row summed left to right, the rows top to bottom.  use_harris_detector 0: (A / 2 + C / 2) -
+   sqrt((A / 2 - C / 2)^2 + B^2); 1: A C - B^2 - k (A + C)^2, the products in float32, the term with k in double.  What
+   follows the response (threshold, local maxima, order, min_distance) does not depend on the block; a Harris image with
+   no positive response gives no corners, which is not an error.  Keypoints carry size = block_size, as
+   cv::GFTTDetector's do.  Handle state: a fresh handle holds the defaults; out-of-range values (block_size 1 and above 15
+   included) return SF_EINVAL, say why and change nothing.  An image, Vis/RoiRatios ROI or grid cell with a side below
+   block_size is refused with SF_EINVAL by the call that detects on it.  Feature types 0 .. 4 do not read the block.   */
+typedef struct sf_gftt_params {
+  int32_t block_size;           /* GFTT/BlockSize, 3; 2 .. 15            */
+  int32_t use_harris_detector;  /* GFTT/UseHarrisDetector, 0; 0 or 1     */
+  double  k;                    /* GFTT/K, 0.04; finite, 0 <= k <= 1     */
+} sf_gftt_params;
+void sf_gftt_defaults(sf_gftt_params* p);
+int  sf_gftt_set_params(sf_handle h, const sf_gftt_params* params);
+int  sf_gftt_get_params(sf_handle h, sf_gftt_params* params);
 /* Conventions of sf_detect_corners_device: d_kpts_out receives up to `cap` keypoints, *n_out = keypoints of the result
    (after the limit); width, height >= 3.  params NULL = the handle's.  Any image size up to 2^26 pixels.  Synchronises
    the stream twice (corner count, result count).                                                                  */

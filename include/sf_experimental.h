@@ -97,6 +97,8 @@ void sf_surf_build_tables(float* ori_w, int8_t* ori_xy, float* desc_w);
 /* The ranges sf_set_feature_type_surf and sf_detect_surf_device hold sf_surf_params to, without a handle: SF_OK or
    SF_EINVAL; NULL = the defaults.                                                                                 */
 int  sf_surf_check_params(const sf_surf_params* params);
+/* The ranges sf_gftt_set_params holds sf_gftt_params to, without a handle: SF_OK or SF_EINVAL; NULL = the defaults.   */
+int  sf_gftt_check_params(const sf_gftt_params* params);
 /* Small shapes for the tests of SURF's batch form; a fresh handle behaves as if neither had been called.  candidate_cap
    (0 = the default, at most 262144) takes the place of the 262144 maxima an image may have, in sf_detect_surf_device
    and the single extraction calls (more: SF_ERANGE) and in the batch forms (more: the keyframe holds no rows, see

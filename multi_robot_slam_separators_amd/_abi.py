@@ -159,6 +159,19 @@ def fast_params(threshold=20, nonmax_suppression=1):
     return p
 
 
+class GfttParams(C.Structure):
+    """sf_gftt_params (include/sepfinder.h): rtabmap's GFTT/BlockSize, GFTT/UseHarrisDetector and GFTT/K -- the response of
+    the GFTT detector (detect_corners_device; Vis/FeatureType 5, 6 and 8)."""
+    _fields_ = [("block_size", C.c_int32), ("use_harris_detector", C.c_int32), ("k", C.c_double)]
+
+
+def gftt_params(block_size=3, use_harris_detector=0, k=0.04):
+    """GFTT/BlockSize, GFTT/UseHarrisDetector, GFTT/K defaults (what sf_gftt_defaults fills)."""
+    p = GfttParams()
+    p.block_size, p.use_harris_detector, p.k = block_size, use_harris_detector, k
+    return p
+
+
 class FrontParams(C.Structure):
     """sf_front_params (include/sepfinder.h): what rtabmap's Feature2D::generateKeypoints puts around every detector --
     Vis/RoiRatios {left, right, top, bottom} and cv::cornerSubPix (Vis/SubPixWinSize, SubPixIterations, SubPixEps)."""

@@ -5,8 +5,12 @@
 //
 // The algorithm and the ONE float summation order used where OpenCV's depends on its build are spelled out next to
 // the CPU restatement the tests compare with (byte for byte; this file is compiled with -ffp-contract=off):
-//   k_gftt_products    per pixel: Sobel dx, dy (scale 1/3060, BORDER_REFLECT_101), the three products
-//   k_gftt_eig         per pixel: 3 x 3 sums of the products, eig = (a + c) - sqrt((a - c)^2 + b^2); max(eig)
+//   k_gftt_products    per pixel: Sobel dx, dy (scale 1 / (4 * 255 * GFTT/BlockSize): 1/3060 at the default block of 3,
+//                      BORDER_REFLECT_101), the three products
+//   k_gftt_eig         per pixel: 3 x 3 sums of the products, eig = (a + c) - sqrt((a - c)^2 + b^2); max(eig) -- the
+//                      handle's default GFTT parameters (block 3, no Harris)
+//   k_gftt_response    every other (GFTT/BlockSize, GFTT/UseHarrisDetector): b x b sums of the products as row sums then
+//                      column sums in LDS, the minimum eigenvalue or the Harris measure with GFTT/K; the same maximum
 //   k_gftt_candidates  interior pixels above quality * max that equal the maximum of their thresholded 3 x 3
 //                      neighbourhood -> 64-bit keys (response bits << 32 | pixel index), one global atomic per workgroup
 //   sf_sort_keys (sf_sort.hip) descending = decreasing response, ties by decreasing address (featureselect.cpp's
@@ -87,6 +91,87 @@ k_gftt_eig(const float* __restrict__ dxx, const float* __restrict__ dxy, const f
   }
 }
 
+// The response for every (block b, Harris) but the default (3, no): cv::cornerMinEigenVal / cv::cornerHarris with blockSize
+// b, restated in tests/gftt_ref.py.  The window of output (x, y) is rows y - b/2 .. y - b/2 + b - 1 and the same columns
+// (boxFilter's default anchor: an even b leans up and left), indices reflected (BORDER_REFLECT_101; the launcher's callers
+// refuse a side below b).  ONE summation order: each window row left to right, r = ((p[x0] + p[x0 + 1]) + p[x0 + 2]) + ..,
+// then the rows top to bottom, S = ((r_0 + r_1) + r_2) + .. -- box3's order at b = 3.  r depends on (row, x0) only, so a
+// workgroup sums separably: the 64 x 16 output tile's (64 + b - 1) x (16 + b - 1) patch of each product plane goes to LDS
+// (s_p), a horizontal pass leaves the 64 row sums of every patch row (s_r), a vertical pass adds b of them per output:
+// 2 b additions per plane and pixel instead of b * b.  Every LDS access has lane = column (unit stride across a wavefront:
+// conflict-free whatever the row stride, so the rows carry no padding; the patch fill walks s_p linearly).  51 KB of LDS:
+// three workgroups per CU.  Harris is OpenCV's scalar expression (float)(a * c - b * b - k * (a + c) * (a + c)) with k a
+// double: the two products, their difference and the trace in float32, the three operations with k in double.
+constexpr int GFTT_RESP_W = 64, GFTT_RESP_H = 16, GFTT_MAX_BLOCK = 15;
+constexpr int GFTT_RESP_PW = GFTT_RESP_W + GFTT_MAX_BLOCK - 1, GFTT_RESP_PH = GFTT_RESP_H + GFTT_MAX_BLOCK - 1;
+template <bool HARRIS>
+__global__ void __launch_bounds__(256)
+k_gftt_response(const float* __restrict__ dxx, const float* __restrict__ dxy, const float* __restrict__ dyy, int w, int h,
+                int b, double k, float* __restrict__ eig, int* __restrict__ max_bits, size_t plane_stride) {
+  __shared__ float s_p[3][GFTT_RESP_PH * GFTT_RESP_PW];
+  __shared__ float s_r[3][GFTT_RESP_PH][GFTT_RESP_W];
+  __shared__ int s_m[4];
+  const float* planes[3] = {dxx + blockIdx.z * plane_stride, dxy + blockIdx.z * plane_stride, dyy + blockIdx.z * plane_stride};
+  eig += blockIdx.z * plane_stride;
+  max_bits += blockIdx.z;
+  const int x0 = blockIdx.x * GFTT_RESP_W - b / 2, y0 = blockIdx.y * GFTT_RESP_H - b / 2;
+  const int pw = GFTT_RESP_W + b - 1, ph = GFTT_RESP_H + b - 1;
+  // (patch columns and rows no output of the image needs -- a tile that overhangs the right or bottom edge -- reflect
+  // to pixels of the image all the same: nothing is read out of bounds, nothing of it is written)
+  for (int i = threadIdx.x; i < ph * pw; i += 256) {
+    const int r = i / pw, col = i - r * pw;
+    const size_t o = (size_t)reflect101(y0 + r, h) * w + reflect101(x0 + col, w);
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) s_p[pl][i] = planes[pl][o];
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int r = wave; r < ph; r += 4) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      const float* p = &s_p[pl][r * pw + lane];
+      float s = p[0];
+      for (int j = 1; j < b; ++j) s = s + p[j];
+      s_r[pl][r][lane] = s;
+    }
+  }
+  __syncthreads();
+  const int x = blockIdx.x * GFTT_RESP_W + lane;
+  int m = 0;
+#pragma unroll
+  for (int t = 0; t < GFTT_RESP_H / 4; ++t) {
+    const int ty = wave * (GFTT_RESP_H / 4) + t, y = blockIdx.y * GFTT_RESP_H + ty;
+    float S[3];
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+      float s = s_r[pl][ty][lane];
+      for (int j = 1; j < b; ++j) s = s + s_r[pl][ty + j][lane];
+      S[pl] = s;
+    }
+    if (x < w && y < h) {
+      float e;
+      if (HARRIS) {
+        const float t0 = S[0] * S[2] - S[1] * S[1], u = S[0] + S[2];
+        e = (float)((double)t0 - (k * (double)u) * (double)u);
+      } else {
+        const float a = S[0] * 0.5f, c = S[2] * 0.5f;
+        e = (a + c) - sqrtf((a - c) * (a - c) + S[1] * S[1]);
+      }
+      eig[(size_t)y * w + x] = e;
+      m = max(m, e > 0.f ? __float_as_int(e) : 0);
+    }
+  }
+  // max(0, max e) as k_gftt_eig reduces it
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = max(m, __shfl_xor(m, off));
+  if (lane == 0) s_m[wave] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
+    if (m > __builtin_nontemporal_load(max_bits)) atomicMax(max_bits, m);
+  }
+}
+
 constexpr int GFTT_CAND_TILES = 4;      // 64 x 4 pixel tiles per workgroup of k_gftt_candidates
 __global__ void __launch_bounds__(256)
 k_gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __restrict__ max_bits, double quality,
@@ -131,7 +216,7 @@ k_gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __rest
 __global__ void __launch_bounds__(64)
 k_gftt_select(const unsigned long long* __restrict__ keys, int n, int w, int cell, int gw, int gh, float md2,
               int max_corners, int* __restrict__ head, int* __restrict__ next, int2* __restrict__ pts,
-              sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out) {
+              sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out, float kp_size) {
   const int lane = threadIdx.x;
   int out = 0;
   for (int base = 0; base < n && (max_corners <= 0 || out < max_corners); base += 64) {
@@ -170,7 +255,7 @@ k_gftt_select(const unsigned long long* __restrict__ keys, int n, int w, int cel
       const int o = out + rank;
       pts[o] = make_int2(x, y);
       if (cell > 0) next[o] = atomicExch(&head[(y / cell) * gw + x / cell], o);
-      if (o < cap) kp_out[o] = sf_make_keypoint((float)x, (float)y, 3.0f, 0.0f, 0);
+      if (o < cap) kp_out[o] = sf_make_keypoint((float)x, (float)y, kp_size, 0.0f, 0);
     }
     out += min(cnt, room);
     __threadfence();          // the lists written above are read by every lane in the next step
@@ -187,7 +272,7 @@ k_gftt_select(const unsigned long long* __restrict__ keys, int n, int w, int cel
 constexpr int GFTT_MAX_RADIUS = 64;
 __global__ void __launch_bounds__(256)
 k_gftt_select_lds(const unsigned long long* __restrict__ keys, int n, int w, int h, int wpr, float md2, int radius,
-                  int max_corners, sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out,
+                  int max_corners, sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out, float kp_size,
                   const unsigned* __restrict__ d_count = nullptr, unsigned key_cap = 0) {
   extern __shared__ unsigned gf_bm[];
   if (d_count) {     // batch: one workgroup per image, the candidate count read on the device
@@ -264,7 +349,7 @@ k_gftt_select_lds(const unsigned long long* __restrict__ keys, int n, int w, int
     if (good && rank < room) {
       const int o = out + rank;
       if (radius > 0) atomicOr(&gf_bm[y * wpr + (x >> 5)], 1u << (x & 31));
-      if (o < cap) kp_out[o] = sf_make_keypoint((float)x, (float)y, 3.0f, 0.0f, 0);
+      if (o < cap) kp_out[o] = sf_make_keypoint((float)x, (float)y, kp_size, 0.0f, 0);
     }
     out += min(cnt, room);
   }
@@ -278,7 +363,9 @@ __global__ void k_gftt_segments(const unsigned* __restrict__ count, unsigned key
 }
 
 // The front half of both launchers -- workspace and the three front kernels for n_img images of one size (blockIdx.z =
-// image): every image's candidate keys and their count are on the device when the stream gets there
+// image): every image's candidate keys and their count are on the device when the stream gets there.  The handle's
+// sf_gftt_params (validated when set; the callers have refused a side below block_size) give the Sobel scale and the
+// response kernel: k_gftt_eig for the defaults, k_gftt_response otherwise
 int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
                double quality_level, const SfCells& cells, SfDetectorWork* F) {
   const size_t np = (size_t)width * height;
@@ -289,12 +376,25 @@ int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_
   float* dyy = dxy + np;
   float* eig = dyy + np;
   const size_t plane_stride = 4 * np;
-  const double scale = 1.0 / ((double)(1 << 2) * 3.0 * 255.0);
+  const sf_gftt_params& g = c->gftt;
+  const double scale = 1.0 / ((double)(1 << 2) * (double)g.block_size * 255.0);
   const dim3 grid((width + 63) / 64, (height + 3) / 4, n_img), block(256);
   hipLaunchKernelGGL(k_gftt_products, grid, block, 0, c->stream, d_images, width, height, pitch, (float)(1.0 * scale),
                      (float)(2.0 * scale), dxx, dxy, dyy, img_stride, plane_stride, cells);
-  hipLaunchKernelGGL(k_gftt_eig, grid, block, 0, c->stream, (const float*)dxx, (const float*)dxy, (const float*)dyy, width,
-                     height, eig, F->max_bits, plane_stride);
+  if (g.block_size == 3 && !g.use_harris_detector) {
+    hipLaunchKernelGGL(k_gftt_eig, grid, block, 0, c->stream, (const float*)dxx, (const float*)dxy, (const float*)dyy, width,
+                       height, eig, F->max_bits, plane_stride);
+  } else {
+    if (g.block_size < 2 || g.block_size > GFTT_MAX_BLOCK || width < g.block_size || height < g.block_size)
+      return sf_fail(c, SF_EINVAL, "GFTT/BlockSize %d on a %d x %d image", g.block_size, width, height);
+    const dim3 grid_r((width + GFTT_RESP_W - 1) / GFTT_RESP_W, (height + GFTT_RESP_H - 1) / GFTT_RESP_H, n_img);
+    if (g.use_harris_detector)
+      hipLaunchKernelGGL(k_gftt_response<true>, grid_r, block, 0, c->stream, (const float*)dxx, (const float*)dxy,
+                         (const float*)dyy, width, height, g.block_size, g.k, eig, F->max_bits, plane_stride);
+    else
+      hipLaunchKernelGGL(k_gftt_response<false>, grid_r, block, 0, c->stream, (const float*)dxx, (const float*)dxy,
+                         (const float*)dyy, width, height, g.block_size, g.k, eig, F->max_bits, plane_stride);
+  }
   const dim3 grid_c((width + 63) / 64, (height + 4 * GFTT_CAND_TILES - 1) / (4 * GFTT_CAND_TILES), n_img);
   hipLaunchKernelGGL(k_gftt_candidates, grid_c, block, 0, c->stream, (const float*)eig, width, height, (const int*)F->max_bits,
                      quality_level, F->keys, F->count, F->key_cap, plane_stride);
@@ -332,7 +432,7 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
   if (bm_bytes <= 150 * 1024 && radius <= GFTT_MAX_RADIUS) {
     if ((rc = gftt_select_lds_attr(c)) != SF_OK) return rc;
     hipLaunchKernelGGL(k_gftt_select_lds, dim3(1), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, n,
-                       width, height, wpr, md2, radius, max_corners, d_kpts_out, cap, F.n_single);
+                       width, height, wpr, md2, radius, max_corners, d_kpts_out, cap, F.n_single, (float)c->gftt.block_size);
   } else {
     const int cell = min_distance >= 1.0 ? (int)std::lrint(min_distance) : 0;
     const int gw = cell > 0 ? (width + cell - 1) / cell : 1, gh = cell > 0 ? (height + cell - 1) / cell : 1;
@@ -344,7 +444,7 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
     int2* pts = (int2*)(head + n_int);
     SF_HIP(c, hipMemsetAsync(head, 0xFF, (size_t)gw * gh * sizeof(int), c->stream));
     hipLaunchKernelGGL(k_gftt_select, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)F.keys_sorted, n, width, cell,
-                       gw, gh, md2, max_corners, head, next, pts, d_kpts_out, cap, F.n_single);
+                       gw, gh, md2, max_corners, head, next, pts, d_kpts_out, cap, F.n_single, (float)c->gftt.block_size);
   }
   SF_HIP(c, hipGetLastError());
   return n_out ? sf_word_to_host(c, F.n_single, n_out) : SF_OK;
@@ -375,7 +475,7 @@ int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_
   if ((rc = gftt_select_lds_attr(c)) != SF_OK) return rc;
   hipLaunchKernelGGL(k_gftt_select_lds, dim3(n_img), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, 0,
                      width, height, wpr, (float)(min_distance * min_distance), radius, max_corners, d_kpts_out, cap, d_n_out,
-                     (const unsigned*)F.count, F.key_cap);
+                     (float)c->gftt.block_size, (const unsigned*)F.count, F.key_cap);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }

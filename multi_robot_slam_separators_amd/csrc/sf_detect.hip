@@ -10,6 +10,45 @@ int sf_check_gftt(sf_context* c, double quality_level, double min_distance) {
   return SF_OK;
 }
 
+// ---- GFTT/BlockSize, GFTT/UseHarrisDetector, GFTT/K: the response of k_gftt.hip, handle state as the FAST parameters are ----
+extern "C" void sf_gftt_defaults(sf_gftt_params* p) {
+  if (!p) return;
+  p->block_size = 3;           // GFTT/BlockSize [upstream rtabmap Parameters.h]
+  p->use_harris_detector = 0;  // GFTT/UseHarrisDetector
+  p->k = 0.04;                 // GFTT/K
+}
+
+int sf_gftt_validate(sf_context* c, const sf_gftt_params& g) {
+  if (g.block_size == 1)
+    return sf_fail(c, SF_EINVAL, "GFTT block_size 1: the response of a single product is rounding noise (2 .. 15)");
+  if (g.block_size < 1) return sf_fail(c, SF_EINVAL, "GFTT block_size %d outside 2 .. 15", g.block_size);
+  if (g.block_size > 15) return sf_fail(c, SF_EINVAL, "GFTT block_size %d is not built (2 .. 15)", g.block_size);
+  if (g.use_harris_detector != 0 && g.use_harris_detector != 1)
+    return sf_fail(c, SF_EINVAL, "GFTT use_harris_detector %d is neither 0 nor 1", g.use_harris_detector);
+  if (!std::isfinite(g.k) || g.k < 0.0 || g.k > 1.0) return sf_fail(c, SF_EINVAL, "GFTT k %g: finite, 0 <= k <= 1", g.k);
+  return SF_OK;
+}
+
+// the same ranges without a handle (sf_experimental.h; NULL = the defaults)
+extern "C" int sf_gftt_check_params(const sf_gftt_params* params) { return sf_gftt_validate(nullptr, arg_or_defaults(params, sf_gftt_defaults)); }
+
+extern "C" int sf_gftt_set_params(sf_handle c, const sf_gftt_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  int rc = sf_gftt_validate(c, *params);
+  if (rc != SF_OK) return rc;
+  c->gftt = *params;
+  return SF_OK;
+}
+
+extern "C" int sf_gftt_get_params(sf_handle c, sf_gftt_params* params) { return get_block(c, params, &sf_context::gftt); }
+
+int sf_check_gftt_side(sf_context* c, int width, int height, const char* what) {
+  const int b = c->gftt.block_size;
+  if (width < b || height < b)
+    return sf_fail(c, SF_EINVAL, "GFTT block_size %d needs %s of at least %d x %d, not %d x %d", b, what, b, b, width, height);
+  return SF_OK;
+}
+
 extern "C" void sf_detector_defaults(sf_detector_params* p) {
   if (!p) return;
   p->max_features = 1000;      // Vis/MaxFeatures [upstream rtabmap Parameters.h]; the reference sets only Vis/MinInliers
@@ -39,6 +78,7 @@ extern "C" int sf_detect_corners_device(sf_handle c, const uint8_t* d_image, int
                                         sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
   int rc;
   if ((rc = detect_prologue(c, d_image, width, height, pitch, d_kpts_out, cap, n_out)) != SF_OK) return rc;
+  if ((rc = sf_check_gftt_side(c, width, height, "an image")) != SF_OK) return rc;
   if ((rc = detect_ready(c, sf_check_gftt(c, quality_level, min_distance), width, height)) != SF_OK) return rc;
   return sf_launch_detect_corners(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out,
                                   cap, n_out);
@@ -176,6 +216,10 @@ int sf_front_plan(sf_context* c, int width, int height, FrontPlan* fp) {
   if (rc != SF_OK)
     return sf_fail(c, SF_EINVAL, "Vis/RoiRatios %g %g %g %g leave a ROI of %d x %d in a %d x %d image: both sides must be >= 3",
                    (double)f.roi_ratios[0], (double)f.roi_ratios[1], (double)f.roi_ratios[2], (double)f.roi_ratios[3], roi[2], roi[3], width, height);
+  if (t.corners == CORNERS_GFTT) {                         // (the ROI is the image when the ratios are zero)
+    const int side = sf_check_gftt_side(c, roi[2], roi[3], roi_is_zero(f.roi_ratios) ? "an image" : "a ROI");
+    if (side != SF_OK) return side;
+  }
   fp->x = roi[0]; fp->y = roi[1]; fp->w = roi[2]; fp->h = roi[3];
   fp->refine = f.subpix_win_size > 0 && f.subpix_iterations > 0;
   return fp->refine ? check_subpix(c, width, height, f.subpix_win_size, f.subpix_iterations) : SF_OK;
@@ -241,6 +285,10 @@ int sf_grid_plan(sf_context* c, int width, int height, int max_features, FrontPl
   if (rc != SF_OK)
     return sf_fail(c, SF_EINVAL, "a grid of %d x %d on a ROI of %d x %d leaves cells of %d x %d: both sides must be >= 3", g.grid_rows,
                    g.grid_cols, fp->w, fp->h, o[2], o[3]);
+  if (t.corners == CORNERS_GFTT) {
+    const int side = sf_check_gftt_side(c, o[2], o[3], "a grid cell");
+    if (side != SF_OK) return side;
+  }
   fp->rows = g.grid_rows; fp->cols = g.grid_cols;
   fp->col_size = o[2]; fp->row_size = o[3]; fp->quota = o[4]; fp->rows_cap = o[5];
   return SF_OK;

@@ -98,6 +98,9 @@ int sf_grid_plan(sf_context* c, int width, int height, int max_features, FrontPl
 int sf_grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_params& dp, const uint8_t* d_left, size_t image_stride,
                    int n, int pitch, sf_keypoint* d_kpts, int32_t* d_n);
 int sf_check_gftt(sf_context* c, double quality_level, double min_distance);
+int sf_gftt_validate(sf_context* c, const sf_gftt_params& g);
+// the GFTT window on what the detector is given (`what`: an image, a ROI, a grid cell): a side below GFTT/BlockSize is refused
+int sf_check_gftt_side(sf_context* c, int width, int height, const char* what);
 int sf_check_block_match(sf_context* c, const sf_stereo_flow_params& prm);   // what sf_stereo_block_match_device refuses
 #pragma GCC visibility pop
 

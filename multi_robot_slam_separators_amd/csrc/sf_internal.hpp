@@ -325,6 +325,9 @@ struct sf_context {
   Buf orb_tests, ex_blur, ex_kpts;
   // 4 = FAST/BRIEF: the detector is k_fast.hip's with these parameters (sf_fast_set_params), the rest is type 6's
   sf_fast_params fast = {20, 1};
+  // 5, 6, 8 and sf_detect_corners_device: the GFTT response of k_gftt.hip -- block size, Harris or minimum eigenvalue, k
+  // (sf_gftt_set_params); the defaults run the kernels the detector had before the block existed
+  sf_gftt_params gftt = {3, 0, 0.04};
   // 3 = FAST/FREAK, 5 = GFTT/FREAK (sf_set_feature_type_freak; k_freak.hip): type 4's / type 6's corners with 64-byte FREAK
   // rows.  freak_pairs: the 512 selected pairs in OpenCV's selectedPairs format (freak_pairs_set false: the generated
   // default selection, not made yet).  On the device, reserved by the first extraction under a FREAK type only:

@@ -92,6 +92,10 @@ def load():
         "sf_fast_set_params": (C.c_int, [vp, P(_abi.FastParams)]),
         "sf_fast_get_params": (C.c_int, [vp, P(_abi.FastParams)]),
         "sf_detect_fast_device": (C.c_int, [vp, vp, i32, i32, i32, i32, P(_abi.FastParams), vp, i32, P(i32)]),
+        "sf_gftt_defaults": (None, [P(_abi.GfttParams)]),
+        "sf_gftt_set_params": (C.c_int, [vp, P(_abi.GfttParams)]),
+        "sf_gftt_get_params": (C.c_int, [vp, P(_abi.GfttParams)]),
+        "sf_gftt_check_params": (C.c_int, [P(_abi.GfttParams)]),
         "sf_front_defaults": (None, [P(_abi.FrontParams)]),
         "sf_front_set_params": (C.c_int, [vp, P(_abi.FrontParams)]),
         "sf_front_get_params": (C.c_int, [vp, P(_abi.FrontParams)]),
@@ -245,6 +249,7 @@ EXPORTED = [
     "sf_kernel_name", "sf_stream_placement", "sf_streams_prepare",
     "sf_orb_defaults", "sf_set_feature_type", "sf_get_feature_type", "sf_orb_set_pattern", "sf_orb_get_pattern",
     "sf_fast_defaults", "sf_fast_set_params", "sf_fast_get_params", "sf_detect_fast_device",
+    "sf_gftt_defaults", "sf_gftt_set_params", "sf_gftt_get_params", "sf_gftt_check_params",
     "sf_orb_detector_defaults", "sf_set_feature_type_orb", "sf_get_orb_detector", "sf_detect_orb_device",
     "sf_image_set_gray_rule", "sf_image_get_gray_rule", "sf_image_to_gray_device", "sf_netvlad_infer_u8_batch_device",
     "sf_get_features_and_descriptor_u8", "sf_add_keyframes_u8_batch_device",
@@ -803,6 +808,17 @@ class SeparatorFinder:
                                                   C.byref(params) if params is not None else None,
                                                   C.c_void_p(d_kpts_out), cap, C.byref(n)))
         return n.value
+
+    def gftt_set_params(self, params):
+        """The handle's GFTT response parameters (_abi.GfttParams: block size, Harris or minimum eigenvalue, k): what
+        detect_corners_device and the extraction calls under feature types 5, 6 and 8 detect with; (3, 0, 0.04) on a
+        fresh handle."""
+        self._check(self._L.sf_gftt_set_params(self._h, C.byref(params)))
+
+    def gftt_get_params(self):
+        p = _abi.GfttParams()
+        self._check(self._L.sf_gftt_get_params(self._h, C.byref(p)))
+        return p
 
     def front_set_params(self, params):
         """The handle's _abi.FrontParams: the ROI every detector sees (Vis/RoiRatios) and cv::cornerSubPix on the kept

@@ -109,6 +109,16 @@ class SepfinderGeometricTools {
     n.param("fast_threshold", fast.threshold, 20);
     if (sf_fast_set_params(sf_, &fast) != SF_OK)
       ROS_ERROR("fast_threshold %d: %s", fast.threshold, sf_last_error(sf_));
+    sf_gftt_params gftt;
+    sf_gftt_defaults(&gftt);
+    bool use_harris = false;
+    n.param("gftt_block_size", gftt.block_size, 3);
+    n.param("gftt_use_harris_detector", use_harris, false);
+    n.param("gftt_k", gftt.k, 0.04);
+    gftt.use_harris_detector = use_harris ? 1 : 0;
+    if (sf_gftt_set_params(sf_, &gftt) != SF_OK)
+      ROS_ERROR("gftt_block_size %d, gftt_use_harris_detector %d, gftt_k %g: %s", gftt.block_size, gftt.use_harris_detector,
+                gftt.k, sf_last_error(sf_));
     sf_orb_params orb;
     sf_orb_defaults(&orb);
     orb.edge_threshold = edge_threshold;
