@@ -107,6 +107,12 @@ extern "C" {
       GFTT/UseHarrisDetector, GFTT/K: the response of the GFTT detector, handle state read by sf_detect_corners_device and
       by every extraction call under Vis/FeatureType 5, 6 and 8), sf_gftt_check_params (sf_experimental.h).  A fresh handle
       holds (3, 0, 0.04), with which nothing existing changed; the version number, sizeof(sf_params) and SF_K_COUNT stay. */
+/* 8, additions: sf_depth_format, sf_depth_params, sf_depth_defaults, sf_depth_set_params, sf_depth_get_params,
+      sf_depth_mask_device, sf_depth_points_device, sf_detect_corners_masked_device, sf_detect_fast_masked_device,
+      sf_extract_keyframe_depth_device, sf_get_features_and_descriptor_depth,
+      sf_get_features_and_descriptor_depth_batch_device, sf_add_keyframes_depth_batch_device (RGB-D keyframes: 3D points
+      from a registered depth image, Vis/DepthAsMask).  New calls only: every existing call keeps its behaviour and its
+      messages; the version number, sizeof(sf_params) and SF_K_COUNT stay.                                             */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -1034,6 +1040,103 @@ int  sf_add_keyframes_sift_u8_batch_device(sf_handle h, const uint8_t* d_left, c
                                            const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                            int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                            float* d_xyz_out, sf_keypoint* d_kpts_out);
+
+/* ---- RGB-D keyframes: 3D points from a registered depth image, Vis/DepthAsMask ------------------------------------ */
+/* replaces: the depth branch of Feature2D::generateKeypoints3D (called at myRegistrationVis.cpp:382) -- util3d::
+   generateKeypoints3DDepth -> projectDepthTo3D(smoothing = true) -> util2d::getDepth(depthErrorRatio 0.02,
+   estWithNeighborsIfNull false) -- and the detector mask Feature2D::generateKeypoints makes of the depth image
+   (myRegistrationVis.cpp:271-284, Vis/DepthAsMask) [upstream rtabmap, restated in tests/depth_ref.py; DESIGN.md section 3
+   lists what the restatement decides].  The depth image is registered to the image and has its width and height (a
+   decimated depth image, upstream's util2d::interpolate path, cannot be passed: not built); its rows are depth_pitch bytes
+   apart.  The camera is read as an sf_stereo_camera: fx, fy, cx, cy, local_transform, min_depth and max_depth are used,
+   baseline and cx_right ignored.
+     3D point of keypoint (x, y), float32 in this order: u = (int)(x + 0.5f), v = (int)(y + 0.5f) (u == width && x < width:
+     u = width - 1, likewise v; outside the image, or a coordinate that is not finite: no depth).  d = the depth at (u, v) in
+     metres; 0 or not finite: no point.  Smoothing over the 3 x 3 neighbours inside the image (columns outer, rows inner,
+     centre skipped): a neighbour dn counts iff dn != 0, finite and |dn - d| < 0.02f * d, with weight 2 and value dn * 2
+     in the centre's row or column, else weight 1; depth = (d * 4 + sum of values) / (sum of weights + 4).  cx_ = cx > 0 ?
+     cx : width / 2 - 0.5f (integer division), cy_ likewise; X = (x - cx_) * depth / fx, Y = (y - cy_) * depth / fy, Z =
+     depth; kept iff Z is finite, (min_depth < 0 or Z > min_depth) and (max_depth <= 0 or Z <= max_depth); then
+     local_transform as for stereo points.  Otherwise the point is three quiet NaNs.
+     mask of a pixel: 255 iff value > min_depth and (max_depth == 0 or value <= max_depth), else 0 (NaN compares false).   */
+enum sf_depth_format {
+  SF_DEPTH_U16_MM = 0,   /* CV_16UC1, millimetres; 0 and 65535 = no depth (value 0); metres = (float)v * 0.001f; pitch >= 2 * width */
+  SF_DEPTH_F32_M = 1     /* CV_32FC1, metres; 0, NaN and +-inf = no depth; pitch >= 4 * width                                        */
+};
+typedef struct sf_depth_params {
+  int32_t depth_as_mask;   /* Vis/DepthAsMask: 1 = the detector of the depth keyframe calls sees the mask of the depth image */
+} sf_depth_params;         /* 4 bytes */
+void sf_depth_defaults(sf_depth_params* p);     /* {1}: rtabmap's default */
+/* Values other than 0 or 1 return SF_EINVAL and change nothing.                                                      */
+int  sf_depth_set_params(sf_handle h, const sf_depth_params* params);
+int  sf_depth_get_params(sf_handle h, sf_depth_params* params);
+/* The masks of n_images depth images of one size, one launch, asynchronous on the handle's stream: image i at d_depth + i *
+   depth_stride bytes to the uint8 plane at d_mask + i * mask_stride (rows of mask_pitch >= width bytes; bytes outside the
+   width x height planes are not written).  Strides are ignored when n_images = 1.  SF_EINVAL: unknown format, depth_pitch
+   below a row (2 * width or 4 * width), a depth pitch or stride that is no multiple of the element size, a stride below
+   the rows it holds.  n_images = 0 is SF_OK.                                                                          */
+int  sf_depth_mask_device(sf_handle h, const void* d_depth, int32_t depth_format, int32_t width, int32_t height,
+                          int32_t depth_pitch, size_t depth_stride, int32_t n_images, float min_depth, float max_depth,
+                          uint8_t* d_mask, int32_t mask_pitch, size_t mask_stride);
+/* The 3D points of n keypoints (x and y are read) of one depth image, asynchronous: d_xyz_out [n][3], d_valid_out [n]
+   (optional; 1 = the point is finite).  cam->min_depth / max_depth filter as above.  n = 0 is SF_OK.                   */
+int  sf_depth_points_device(sf_handle h, const void* d_depth, int32_t depth_format, int32_t width, int32_t height,
+                            int32_t depth_pitch, const sf_keypoint* d_kpts, int32_t n, const sf_stereo_camera* cam,
+                            float* d_xyz_out, uint8_t* d_valid_out);
+/* sf_detect_corners_device as cv::goodFeaturesToTrack(image, ..., mask): d_mask is a uint8 plane of the image's size, rows
+   of mask_pitch >= width bytes.  The maximum that scales quality_level is taken over the pixels with mask != 0 (max(0, ..)
+   as without a mask), a corner must lie on such a pixel, and the 3 x 3 dilation still sees every pixel: a masked-out larger
+   neighbour suppresses a masked-in pixel.  A mask of zeros gives 0 corners and SF_OK.  Everything else -- parameters,
+   order, refusals -- is sf_detect_corners_device's; a mask without a zero gives that call's bytes.                       */
+int  sf_detect_corners_masked_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                     const uint8_t* d_mask, int32_t mask_pitch, int32_t max_corners, double quality_level,
+                                     double min_distance, sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
+/* sf_detect_fast_device as FastFeatureDetector::detect(image, keypoints, mask): score and 3 x 3 suppression run on every
+   pixel, corners with mask[y][x] == 0 are then dropped, before rtabmap's limitKeypoints.                              */
+int  sf_detect_fast_masked_device(sf_handle h, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                  const uint8_t* d_mask, int32_t mask_pitch, int32_t max_features,
+                                  const sf_fast_params* params, sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out);
+/* sf_extract_keyframe_device with the registered depth image of the keyframe in place of d_right_x / d_status: the same
+   descriptors under every feature type (0, 1, 2, 3, 4, 5, 6, 8), the 3D point of every corner from the depth image.  A
+   corner is kept iff its descriptor patch lies inside the image and, when cam->min_depth > 0 or cam->max_depth > 0, its
+   point is finite; with both limits 0 the rows and keypoints are those of sf_extract_keyframe_device on the same image.  */
+int  sf_extract_keyframe_depth_device(sf_handle h, const uint8_t* d_left, int32_t width, int32_t height, int32_t pitch,
+                                      const sf_keypoint* d_kpts, const void* d_depth, int32_t depth_format,
+                                      int32_t depth_pitch, int32_t n, const sf_stereo_camera* cam, int32_t* out_slot,
+                                      int32_t* out_rows, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* sf_get_features_and_descriptor_u8 for a SensorData(rgb, depth, model) caller: image (in image_format, an
+   sf_image_format, converted on the device as that call does) and depth in HOST memory.  Stages: the mask of the depth
+   image (when the handle's depth_as_mask is 1; limits cam->min_depth / max_depth), the detector of the handle's feature
+   type under that mask, sub-pixel refinement, extraction with depth points.  There is no stereo stage.  Under a ROI or a
+   grid the mask is cropped like the image; per-cell maxima and quotas apply as without a mask.  The mask is built for the
+   two corner detectors (types 3, 4, 5, 6, 8): on a handle of type 0, 1 or 2 with depth_as_mask = 1 the call returns
+   SF_EINVAL ("DepthAsMask ... not built"; sf_depth_set_params with 0 is the way out), with depth_as_mask = 0 those types
+   work.  Outputs and limits as sf_get_features_and_descriptor.  A refused call changes nothing.  Synchronous.          */
+int  sf_get_features_and_descriptor_depth(sf_handle h, const uint8_t* image, int32_t image_format, const void* depth,
+                                          int32_t depth_format, int32_t width, int32_t height, int32_t image_pitch,
+                                          int32_t depth_pitch, const sf_stereo_camera* cam, const sf_detector_params* det,
+                                          uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
+                                          int32_t* rows_out, int32_t* slot_out);
+/* n_keyframes depth keyframes from DEVICE memory in one launch sequence with no host wait: MONO8 planes (image i at
+   d_images + i * image_stride) and depth planes (at d_depth + i * depth_stride bytes), each with its own pitch and stride.
+   One call serves every feature type (it dispatches on the handle's family; SIFT runs chunk by chunk); per keyframe the
+   bytes are sf_get_features_and_descriptor_depth's.  Outputs as sf_get_features_and_descriptor_batch_device.            */
+int  sf_get_features_and_descriptor_depth_batch_device(sf_handle h, const uint8_t* d_images, const void* d_depth,
+                                                       int32_t depth_format, int32_t n_keyframes, int32_t width,
+                                                       int32_t height, int32_t image_pitch, size_t image_stride,
+                                                       int32_t depth_pitch, size_t depth_stride,
+                                                       const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                       int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                       float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* The same from the camera's colour images (image_format, an sf_image_format), which also feed the network
+   (sf_netvlad_infer_u8_batch_device): n store slots and n NN rows under one index, all or nothing, as
+   sf_add_keyframes_u8_batch_device.                                                                                   */
+int  sf_add_keyframes_depth_batch_device(sf_handle h, const uint8_t* d_images, int32_t image_format, const void* d_depth,
+                                         int32_t depth_format, int32_t n_keyframes, int32_t width, int32_t height,
+                                         int32_t image_pitch, size_t image_stride, int32_t depth_pitch, size_t depth_stride,
+                                         const sf_stereo_camera* cam, const sf_detector_params* det, int32_t* first_slot_out,
+                                         int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                         float* d_xyz_out, sf_keypoint* d_kpts_out);
 
 /* ---- geometric verification (stereoCamGeometricTools.cpp:122-178) ---------------------------- */
 /* One estimate_transformation service call on host buffers.                                  */

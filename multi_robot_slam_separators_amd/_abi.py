@@ -207,6 +207,33 @@ def stereo_params(optical_flow=1, ssd=1):
     return p
 
 
+SF_DEPTH_U16_MM, SF_DEPTH_F32_M = 0, 1          # sf_depth_format: uint16 millimetres / float32 metres
+DEPTH_DTYPES = {SF_DEPTH_U16_MM: np.dtype(np.uint16), SF_DEPTH_F32_M: np.dtype(np.float32)}
+
+
+class DepthParams(C.Structure):
+    """sf_depth_params (include/sepfinder.h): Vis/DepthAsMask of the depth keyframe calls."""
+    _fields_ = [("depth_as_mask", C.c_int32)]
+
+
+assert C.sizeof(DepthParams) == 4
+
+
+def depth_params(depth_as_mask=1):
+    """rtabmap's default (what sf_depth_defaults fills): the detector sees the mask of the depth image."""
+    p = DepthParams()
+    p.depth_as_mask = depth_as_mask
+    return p
+
+
+def depth_format_of(depth):
+    """The sf_depth_format of a depth image given as a uint16 or float32 array."""
+    for fmt, dt in DEPTH_DTYPES.items():
+        if depth.dtype == dt:
+            return fmt
+    raise ValueError("depth images are uint16 (millimetres) or float32 (metres), not %s" % depth.dtype)
+
+
 def compute_roi(width, height, ratios):
     """Feature2D::computeRoi restated: (x, y, w, h) of the sub-image the detector sees for Vis/RoiRatios {left, right,
     top, bottom}.  Float32 arithmetic with C++'s truncating assignment; ValueError for what sf_compute_roi refuses (a

@@ -469,7 +469,8 @@ int sf_launch_integral_batch(sf_context* c, const uint8_t* d_images, size_t img_
 int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_stride, int n_img, int width, int height,
                             int pitch, const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n,
                             const int32_t* d_n, const sf_stereo_camera* cam, const ExtractKind& kind, int slot,
-                            uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out, int32_t* d_rows_out) {
+                            uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out, int32_t* d_rows_out,
+                            const SfDepthIn* depth) {
   const int bytes = kind.bytes;
   const sf_orb_params* orb = kind.orb;
   const sf_orb_detector_params* pyr = kind.pyr;
@@ -522,15 +523,9 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                          (uint8_t*)c->ex_blur.p + P.off[l], orb_blur_taps(), Bl);
     }
   }
-  ExtractCam ec;
-  ec.fx = cam->fx; ec.fy = cam->fy; ec.cx = cam->cx; ec.cy = cam->cy; ec.cx_right = cam->cx_right;
-  ec.baseline = cam->baseline; ec.min_depth = cam->min_depth; ec.max_depth = cam->max_depth;
-  ec.identity_local = 1;
-  for (int e = 0; e < 12; ++e) {
-    ec.L[e] = cam->local_transform[e];
-    ec.identity_local = ec.identity_local && (ec.L[e] == ((e == 0 || e == 5 || e == 10) ? 1.0f : 0.0f));
-  }
-  ec.filter = cam->min_depth > 0.0f || cam->max_depth > 0.0f;
+  ExtractCam ec = sf_extract_cam(cam);
+  const ExtractCam ec_depth = ec;                          // a keyframe with a depth image: the describe kernel runs without right_x
+  if (depth) { d_right_x = nullptr; d_status = nullptr; ec.filter = 0; }   // and without the filter, k_depth_points behind it
   const sf_keypoint* kp_commit = d_kpts;
   if (n > 0) {
     const long long threads = (long long)n * bytes;
@@ -568,9 +563,12 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
                          orb->edge_threshold, kind.d_tests, ec, (uint8_t*)c->ex_desc.p, (float*)c->ex_xyz.p,
                          (uint8_t*)c->ex_keep.p, B);
     }
+    if (depth)
+      sf_launch_depth_points(c, *depth, width, height, d_kpts, n, n_img, ec_depth, (float*)c->ex_xyz.p, (uint8_t*)c->ex_keep.p,
+                             nullptr, B);
   }
   hipLaunchKernelGGL(k_extract_commit, dim3(n_img), dim3(256), 0, c->stream, kp_commit, (const uint8_t*)c->ex_desc.p,
-                     (const float*)c->ex_xyz.p, (const uint8_t*)c->ex_keep.p, n, bytes, d_right_x != nullptr,
+                     (const float*)c->ex_xyz.p, (const uint8_t*)c->ex_keep.p, n, bytes, depth != nullptr || d_right_x != nullptr,
                      (uint32_t*)st.desc.p, (float*)st.xyz.p, (float4*)st.kp.p, (int4*)st.meta.p, st.kcap, st.w, slot,
                      d_desc_out, d_xyz_out, d_kpts_out, d_rows_out, B, pyr ? P.n : 0);
   SF_HIP(c, hipGetLastError());

@@ -18,6 +18,8 @@
 //   k_fast_candidates  3 x 3 suppression on the score plane (strictly greater than all 8 neighbours) -> 64-bit keys
 //                      (score << 32 | pixel index), one global atomic per workgroup.  Without suppression every corner
 //                      is a candidate with score 0 (upstream reads a score buffer it only fills under suppression).
+//                      k_fast_candidates_masked: the same under a mask (sf_detect_fast_masked_device, the depth keyframe
+//                      calls), corners on mask == 0 dropped.
 //   k_fast_rekey       decides the order ON THE DEVICE once the count is known: corners <= max_features (or no limit)
 //                      -> raster order, the keys become (1 << 40 | (2^32 - 1 - index) << 8 | score); otherwise they
 //                      stay, and the descending sort below gives descending response with ties by descending index.
@@ -119,9 +121,14 @@ k_fast_score(const uint8_t* __restrict__ img, int w, int h, int pitch, int t, ui
 }
 
 constexpr int FAST_CAND_ROWS = 16;                   // 64 x 16 pixels per workgroup of k_fast_candidates
-__global__ void __launch_bounds__(256)
-k_fast_candidates(const uint8_t* __restrict__ score, int w, int h, int nonmax, unsigned long long* __restrict__ keys,
-                  unsigned* __restrict__ count, unsigned cap, size_t plane_stride) {
+// The body of the two candidate kernels.  MASKED (FastFeatureDetector::detect(image, keypoints, mask)): score and suppression
+// have seen every pixel; a corner on a pixel whose mask byte is 0 is dropped here, before the count that limitKeypoints
+// reads.  false: the kernel as it was, argument list included
+template <bool MASKED>
+__device__ __forceinline__ void
+fast_candidates(const uint8_t* __restrict__ score, int w, int h, int nonmax, unsigned long long* __restrict__ keys,
+                unsigned* __restrict__ count, unsigned cap, size_t plane_stride, const SfMask& mask) {
+  const uint8_t* mk = MASKED ? mask.p + sf_cell_base(blockIdx.z, mask.stride, mask.cells) : nullptr;
   score += blockIdx.z * plane_stride;
   keys += (size_t)blockIdx.z * cap;
   count += blockIdx.z;
@@ -137,7 +144,7 @@ k_fast_candidates(const uint8_t* __restrict__ score, int w, int h, int nonmax, u
     if (x >= 3 && x < w - 3 && y >= 3 && y < h - 3) {
       const uint8_t* p = score + (size_t)y * w + x;
       const unsigned v = p[0];
-      if (v) {
+      if (v && (!MASKED || mk[(size_t)y * mask.pitch + x] != 0)) {
         bool keep = true;
         if (nonmax) {
           const unsigned m = max(max(max(p[-w - 1], p[-w]), max(p[-w + 1], p[-1])),
@@ -152,6 +159,18 @@ k_fast_candidates(const uint8_t* __restrict__ score, int w, int h, int nonmax, u
     }
   }
   sf_flush_staged_keys(s_keys, &s_n, &s_base, keys, count, cap);
+}
+
+__global__ void __launch_bounds__(256)
+k_fast_candidates(const uint8_t* __restrict__ score, int w, int h, int nonmax, unsigned long long* __restrict__ keys,
+                  unsigned* __restrict__ count, unsigned cap, size_t plane_stride) {
+  fast_candidates<false>(score, w, h, nonmax, keys, count, cap, plane_stride, SfMask());
+}
+
+__global__ void __launch_bounds__(256)
+k_fast_candidates_masked(const uint8_t* __restrict__ score, int w, int h, int nonmax, unsigned long long* __restrict__ keys,
+                         unsigned* __restrict__ count, unsigned cap, size_t plane_stride, SfMask mask) {
+  fast_candidates<true>(score, w, h, nonmax, keys, count, cap, plane_stride, mask);
 }
 
 // blockIdx.y = image.  Raster order when the corners fit the limit; segment bounds for the batch's sort.
@@ -198,23 +217,28 @@ constexpr int FAST_REKEY_BLOCKS = 32;
 // ORB's pyramid levels in k_orb_detect.hip)
 void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
                           int threshold, int nonmax, uint8_t* score, size_t plane_stride, unsigned long long* keys, unsigned* count,
-                          unsigned key_cap, const SfCells& cells) {
+                          unsigned key_cap, const SfCells& cells, const SfMask& mask) {
   const dim3 block(256);
   hipLaunchKernelGGL(k_fast_score, dim3((width + FAST_TW - 1) / FAST_TW, (height + FAST_TH - 1) / FAST_TH, n_img), block, 0,
                      c->stream, d_images, width, height, pitch, threshold, score, img_stride, plane_stride, cells);
-  hipLaunchKernelGGL(k_fast_candidates, dim3((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS, n_img), block, 0,
-                     c->stream, (const uint8_t*)score, width, height, nonmax, keys, count, key_cap, plane_stride);
+  const dim3 grid_c((width + 63) / 64, (height + FAST_CAND_ROWS - 1) / FAST_CAND_ROWS, n_img);
+  if (mask.p)
+    hipLaunchKernelGGL(k_fast_candidates_masked, grid_c, block, 0, c->stream, (const uint8_t*)score, width, height, nonmax, keys,
+                       count, key_cap, plane_stride, mask);
+  else
+    hipLaunchKernelGGL(k_fast_candidates, grid_c, block, 0, c->stream, (const uint8_t*)score, width, height, nonmax, keys, count,
+                       key_cap, plane_stride);
 }
 
 // The front half of both launchers -- workspace and the three front kernels for n_img images of one size: every image's
 // keys, in the form of the order that applies to it, their count and its segment of the key array are on the device when
 // the stream gets there
 static int fast_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
-                      int max_features, const sf_fast_params* prm, const SfCells& cells, SfDetectorWork* F) {
+                      int max_features, const sf_fast_params* prm, const SfCells& cells, const SfMask& mask, SfDetectorWork* F) {
   int rc = sf_detector_work(c, width, height, n_img, (size_t)width * height, F);
   if (rc != SF_OK) return rc;
   sf_launch_fast_level(c, d_images, img_stride, n_img, width, height, pitch, prm->threshold, prm->nonmax_suppression,
-                       (uint8_t*)c->gf_planes.p, (size_t)F->key_cap, F->keys, F->count, F->key_cap, cells);
+                       (uint8_t*)c->gf_planes.p, (size_t)F->key_cap, F->keys, F->count, F->key_cap, cells, mask);
   hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, n_img), dim3(256), 0, c->stream, F->keys, (const unsigned*)F->count,
                      F->key_cap, max_features, F->seg_begin, F->seg_end);
   SF_HIP(c, hipGetLastError());
@@ -224,10 +248,10 @@ static int fast_front(sf_context* c, const uint8_t* d_images, size_t img_stride,
 // Launch sequence on the handle's stream.  The corner count crosses to the host once (the sort is sized by it); which
 // order applies is decided on the device before that.
 int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out) {
+                          const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out, const SfMask& mask) {
   SfDetectorWork F;
   int rc;
-  if ((rc = fast_front(c, d_image, 0, 1, width, height, pitch, max_features, prm, SfCells(), &F)) != SF_OK) return rc;
+  if ((rc = fast_front(c, d_image, 0, 1, width, height, pitch, max_features, prm, SfCells(), mask, &F)) != SF_OK) return rc;
   unsigned h_count = 0;
   if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
   const int n = (int)std::min(h_count, F.key_cap);
@@ -247,10 +271,10 @@ int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int 
 // a grid inside n_img / cells.per_image images (width x height: one cell), keypoints in the cell's own coordinates.
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out, const SfCells& cells) {
+                                int32_t* d_n_out, const SfCells& cells, const SfMask& mask) {
   SfDetectorWork F;
   int rc;
-  if ((rc = fast_front(c, d_images, img_stride, n_img, width, height, pitch, max_features, prm, cells, &F)) != SF_OK) return rc;
+  if ((rc = fast_front(c, d_images, img_stride, n_img, width, height, pitch, max_features, prm, cells, mask, &F)) != SF_OK) return rc;
   if ((rc = sf_sort_keys_segmented_desc(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img,
                                         F.seg_begin, F.seg_end, 0, FAST_KEY_BITS)) != SF_OK)
     return rc;

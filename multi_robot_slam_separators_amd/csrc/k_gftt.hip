@@ -13,6 +13,8 @@
 //                      column sums in LDS, the minimum eigenvalue or the Harris measure with GFTT/K; the same maximum
 //   k_gftt_candidates  interior pixels above quality * max that equal the maximum of their thresholded 3 x 3
 //                      neighbourhood -> 64-bit keys (response bits << 32 | pixel index), one global atomic per workgroup
+//   k_gftt_masked_max, k_gftt_candidates_masked   under a mask (cv's `mask` argument; sf_detect_corners_masked_device and
+//                      the depth keyframe calls) only: the maximum over the masked-in pixels, candidates on them
 //   sf_sort_keys (sf_sort.hip) descending = decreasing response, ties by decreasing address (featureselect.cpp's
 //                      greaterThanPtr); a plain library sort, the only library call of the product's compute path
 //   k_gftt_select_lds  ONE wavefront walks the sorted list 64 candidates at a time: every lane tests its candidate
@@ -173,9 +175,45 @@ k_gftt_response(const float* __restrict__ dxx, const float* __restrict__ dxy, co
 }
 
 constexpr int GFTT_CAND_TILES = 4;      // 64 x 4 pixel tiles per workgroup of k_gftt_candidates
+
+// cv::goodFeaturesToTrack(image, ..., mask): minMaxLoc under the mask -- max(0, max eig) over the pixels whose mask byte is
+// not 0, into max_bits (zeroed again behind the response kernel, which has left the unmasked maximum there).  A launch of
+// its own on the eig plane: the response kernels stay as they are.  The tiles of k_gftt_candidates, reduced as k_gftt_eig
 __global__ void __launch_bounds__(256)
-k_gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __restrict__ max_bits, double quality,
-                  unsigned long long* __restrict__ keys, unsigned* __restrict__ count, unsigned cap, size_t plane_stride) {
+k_gftt_masked_max(const float* __restrict__ eig, int w, int h, int* __restrict__ max_bits, size_t plane_stride, SfMask mask) {
+  const uint8_t* mk = mask.p + sf_cell_base(blockIdx.z, mask.stride, mask.cells);
+  eig += blockIdx.z * plane_stride;
+  max_bits += blockIdx.z;
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  int m = 0;
+#pragma unroll
+  for (int t = 0; t < GFTT_CAND_TILES; ++t) {
+    const int y = (blockIdx.y * GFTT_CAND_TILES + t) * 4 + (threadIdx.x >> 6);
+    if (x < w && y < h && mk[(size_t)y * mask.pitch + x] != 0) {
+      const float e = eig[(size_t)y * w + x];
+      m = max(m, e > 0.f ? __float_as_int(e) : 0);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = max(m, __shfl_xor(m, off));
+  __shared__ int s_m[4];
+  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
+    if (m > __builtin_nontemporal_load(max_bits)) atomicMax(max_bits, m);
+  }
+}
+
+// The body of the two candidate kernels.  MASKED: a candidate lies on a pixel whose mask byte is not 0; the thresholded 3 x 3
+// maximum still reads every pixel (a masked-out larger neighbour suppresses a masked-in pixel, as the dilation of the whole
+// eig image does).  false: the kernel as it was, argument list included
+template <bool MASKED>
+__device__ __forceinline__ void
+gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __restrict__ max_bits, double quality,
+                unsigned long long* __restrict__ keys, unsigned* __restrict__ count, unsigned cap, size_t plane_stride,
+                const SfMask& mask) {
+  const uint8_t* mk = MASKED ? mask.p + sf_cell_base(blockIdx.z, mask.stride, mask.cells) : nullptr;
   eig += blockIdx.z * plane_stride;
   max_bits += blockIdx.z;
   keys += (size_t)blockIdx.z * cap;
@@ -193,7 +231,7 @@ k_gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __rest
     const int y = (blockIdx.y * GFTT_CAND_TILES + t) * 4 + (threadIdx.x >> 6);
     if (x >= 1 && x < w - 1 && y >= 1 && y < h - 1) {
       const float v = eig[(size_t)y * w + x];
-      if (v > thr) {
+      if (v > thr && (!MASKED || mk[(size_t)y * mask.pitch + x] != 0)) {
         float m = 0.f;
 #pragma unroll
         for (int dy = -1; dy <= 1; ++dy)
@@ -211,6 +249,19 @@ k_gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __rest
     }
   }
   sf_flush_staged_keys(s_keys, &s_n, &s_base, keys, count, cap);
+}
+
+__global__ void __launch_bounds__(256)
+k_gftt_candidates(const float* __restrict__ eig, int w, int h, const int* __restrict__ max_bits, double quality,
+                  unsigned long long* __restrict__ keys, unsigned* __restrict__ count, unsigned cap, size_t plane_stride) {
+  gftt_candidates<false>(eig, w, h, max_bits, quality, keys, count, cap, plane_stride, SfMask());
+}
+
+__global__ void __launch_bounds__(256)
+k_gftt_candidates_masked(const float* __restrict__ eig, int w, int h, const int* __restrict__ max_bits, double quality,
+                         unsigned long long* __restrict__ keys, unsigned* __restrict__ count, unsigned cap, size_t plane_stride,
+                         SfMask mask) {
+  gftt_candidates<true>(eig, w, h, max_bits, quality, keys, count, cap, plane_stride, mask);
 }
 
 __global__ void __launch_bounds__(64)
@@ -367,7 +418,7 @@ __global__ void k_gftt_segments(const unsigned* __restrict__ count, unsigned key
 // sf_gftt_params (validated when set; the callers have refused a side below block_size) give the Sobel scale and the
 // response kernel: k_gftt_eig for the defaults, k_gftt_response otherwise
 int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
-               double quality_level, const SfCells& cells, SfDetectorWork* F) {
+               double quality_level, const SfCells& cells, const SfMask& mask, SfDetectorWork* F) {
   const size_t np = (size_t)width * height;
   int rc = sf_detector_work(c, width, height, n_img, np * 4 * sizeof(float), F);
   if (rc != SF_OK) return rc;
@@ -396,8 +447,16 @@ int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_
                          (const float*)dyy, width, height, g.block_size, g.k, eig, F->max_bits, plane_stride);
   }
   const dim3 grid_c((width + 63) / 64, (height + 4 * GFTT_CAND_TILES - 1) / (4 * GFTT_CAND_TILES), n_img);
-  hipLaunchKernelGGL(k_gftt_candidates, grid_c, block, 0, c->stream, (const float*)eig, width, height, (const int*)F->max_bits,
-                     quality_level, F->keys, F->count, F->key_cap, plane_stride);
+  if (mask.p) {
+    SF_HIP(c, hipMemsetAsync(F->max_bits, 0, (size_t)n_img * sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_gftt_masked_max, grid_c, block, 0, c->stream, (const float*)eig, width, height, F->max_bits, plane_stride,
+                       mask);
+    hipLaunchKernelGGL(k_gftt_candidates_masked, grid_c, block, 0, c->stream, (const float*)eig, width, height,
+                       (const int*)F->max_bits, quality_level, F->keys, F->count, F->key_cap, plane_stride, mask);
+  } else {
+    hipLaunchKernelGGL(k_gftt_candidates, grid_c, block, 0, c->stream, (const float*)eig, width, height, (const int*)F->max_bits,
+                       quality_level, F->keys, F->count, F->key_cap, plane_stride);
+  }
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }
@@ -416,10 +475,10 @@ int gftt_select_lds_attr(sf_context* c) {
 // Launch sequence on the handle's stream.  The candidate count crosses to the host once (the sort is sized by it).
 int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
-                             int32_t* n_out) {
+                             int32_t* n_out, const SfMask& mask) {
   SfDetectorWork F;
   int rc;
-  if ((rc = gftt_front(c, d_image, 0, 1, width, height, pitch, quality_level, SfCells(), &F)) != SF_OK) return rc;
+  if ((rc = gftt_front(c, d_image, 0, 1, width, height, pitch, quality_level, SfCells(), mask, &F)) != SF_OK) return rc;
   unsigned h_count = 0;
   if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
   const int n = (int)std::min(h_count, F.key_cap);
@@ -457,7 +516,8 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
 // keypoints in the cell's own coordinates.
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
-                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells) {
+                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells,
+                                   const SfMask& mask) {
   const int wpr = (width + 31) / 32;
   const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
   const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
@@ -465,7 +525,7 @@ int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_
     return sf_fail(c, SF_ERANGE, "batched corner detection: %d x %d image does not fit the LDS selection bitmap", width, height);
   SfDetectorWork F;
   int rc;
-  if ((rc = gftt_front(c, d_images, img_stride, n_img, width, height, pitch, quality_level, cells, &F)) != SF_OK) return rc;
+  if ((rc = gftt_front(c, d_images, img_stride, n_img, width, height, pitch, quality_level, cells, mask, &F)) != SF_OK) return rc;
   hipLaunchKernelGGL(k_gftt_segments, dim3((n_img + 63) / 64), dim3(64), 0, c->stream, (const unsigned*)F.count, F.key_cap,
                      n_img, F.seg_begin, F.seg_end);
   SF_HIP(c, hipGetLastError());

@@ -94,6 +94,107 @@ extern "C" int sf_detect_fast_device(sf_handle c, const uint8_t* d_image, int32_
   return sf_launch_detect_fast(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
 }
 
+// ---- the two corner detectors under a mask (cv's `mask` argument; Vis/DepthAsMask makes one of a depth image) --------------
+static int check_mask(sf_context* c, const char* call, const uint8_t* d_mask, int width, int mask_pitch) {
+  if (!d_mask || mask_pitch < width) return sf_fail(c, SF_EINVAL, "%s: mask missing or malformed (width %d, mask_pitch %d)", call, width, mask_pitch);
+  return SF_OK;
+}
+
+static SfMask single_mask(const uint8_t* d_mask, int mask_pitch) {
+  SfMask m;
+  m.p = d_mask; m.pitch = mask_pitch;
+  return m;
+}
+
+extern "C" int sf_detect_corners_masked_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                               const uint8_t* d_mask, int32_t mask_pitch, int32_t max_corners,
+                                               double quality_level, double min_distance, sf_keypoint* d_kpts_out, int32_t cap,
+                                               int32_t* n_out) {
+  int rc;
+  if ((rc = detect_prologue(c, d_image, width, height, pitch, d_kpts_out, cap, n_out)) != SF_OK) return rc;
+  if ((rc = check_mask(c, "sf_detect_corners_masked_device", d_mask, width, mask_pitch)) != SF_OK) return rc;
+  if ((rc = sf_check_gftt_side(c, width, height, "an image")) != SF_OK) return rc;
+  if ((rc = detect_ready(c, sf_check_gftt(c, quality_level, min_distance), width, height)) != SF_OK) return rc;
+  return sf_launch_detect_corners(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out,
+                                  cap, n_out, single_mask(d_mask, mask_pitch));
+}
+
+extern "C" int sf_detect_fast_masked_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
+                                            const uint8_t* d_mask, int32_t mask_pitch, int32_t max_features,
+                                            const sf_fast_params* params, sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
+  int rc;
+  if ((rc = detect_prologue(c, d_image, width, height, pitch, d_kpts_out, cap, n_out)) != SF_OK) return rc;
+  if ((rc = check_mask(c, "sf_detect_fast_masked_device", d_mask, width, mask_pitch)) != SF_OK) return rc;
+  const sf_fast_params prm = params ? *params : c->fast;
+  if ((rc = detect_ready(c, sf_fast_validate(c, prm), width, height)) != SF_OK) return rc;
+  return sf_launch_detect_fast(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out,
+                               single_mask(d_mask, mask_pitch));
+}
+
+// ---- depth images (kernels in k_depth.hip): Vis/DepthAsMask as handle state, the mask and the 3D points as calls --------------
+extern "C" void sf_depth_defaults(sf_depth_params* p) {
+  if (!p) return;
+  p->depth_as_mask = 1;        // Vis/DepthAsMask [upstream rtabmap Parameters.h]
+}
+
+extern "C" int sf_depth_set_params(sf_handle c, const sf_depth_params* params) {
+  if (!c || !params) return SF_EINVAL;
+  if (params->depth_as_mask != 0 && params->depth_as_mask != 1)
+    return sf_fail(c, SF_EINVAL, "Vis/DepthAsMask %d is neither 0 nor 1", params->depth_as_mask);
+  c->depth = *params;
+  return SF_OK;
+}
+
+extern "C" int sf_depth_get_params(sf_handle c, sf_depth_params* params) { return get_block(c, params, &sf_context::depth); }
+
+// what every depth call refuses of its depth images (`call` opens the message): n images of width x height, `stride` bytes apart
+int sf_check_depth(sf_context* c, const char* call, bool present, int format, int width, int height, int pitch, size_t stride, int n) {
+  if (format != SF_DEPTH_U16_MM && format != SF_DEPTH_F32_M)
+    return sf_fail(c, SF_EINVAL, "%s: depth format %d unknown (0 = uint16 millimetres, 1 = float32 metres)", call, format);
+  const int elem = format == SF_DEPTH_F32_M ? 4 : 2;
+  if (!present || width < 1 || height < 1) return sf_fail(c, SF_EINVAL, "%s: depth image missing or malformed (%d x %d)", call, width, height);
+  if ((long long)pitch < (long long)elem * width)
+    return sf_fail(c, SF_EINVAL, "%s: depth_pitch %d is less than a row of %d pixels of %d bytes", call, pitch, width, elem);
+  if (pitch % elem) return sf_fail(c, SF_EINVAL, "%s: depth_pitch %d is no multiple of the %d bytes of a pixel", call, pitch, elem);
+  if (n > 1) {
+    if (stride % (size_t)elem) return sf_fail(c, SF_EINVAL, "%s: depth stride %zu is no multiple of the %d bytes of a pixel", call, stride, elem);
+    if (stride < (size_t)pitch * (height - 1) + (size_t)elem * width)
+      return sf_fail(c, SF_EINVAL, "%s: depth stride %zu is less than an image (%d rows of pitch %d)", call, stride, height, pitch);
+  }
+  return SF_OK;
+}
+
+extern "C" int sf_depth_mask_device(sf_handle c, const void* d_depth, int32_t depth_format, int32_t width, int32_t height,
+                                    int32_t depth_pitch, size_t depth_stride, int32_t n_images, float min_depth, float max_depth,
+                                    uint8_t* d_mask, int32_t mask_pitch, size_t mask_stride) {
+  if (!c || n_images < 0) return SF_EINVAL;
+  if (n_images == 0) return sf_check_depth(c, "sf_depth_mask_device", true, depth_format, 1, 1, 4, 0, 0);   // (the format alone)
+  int rc = sf_check_depth(c, "sf_depth_mask_device", d_depth, depth_format, width, height, depth_pitch, depth_stride, n_images);
+  if (rc != SF_OK) return rc;
+  if (n_images > 65535) return sf_fail(c, SF_ERANGE, "sf_depth_mask_device: %d images (at most 65535 per call)", n_images);
+  if (!d_mask || mask_pitch < width) return sf_fail(c, SF_EINVAL, "sf_depth_mask_device: mask missing or malformed (width %d, mask_pitch %d)", width, mask_pitch);
+  if (n_images > 1 && mask_stride < (size_t)mask_pitch * (height - 1) + (size_t)width)
+    return sf_fail(c, SF_EINVAL, "sf_depth_mask_device: mask stride %zu is less than a plane (%d rows of pitch %d)", mask_stride, height, mask_pitch);
+  SF_HIP(c, hipSetDevice(c->device));
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = n_images > 1 ? depth_stride : 0;
+  return sf_launch_depth_mask(c, D, n_images, width, height, min_depth, max_depth, d_mask, mask_pitch, n_images > 1 ? mask_stride : 0);
+}
+
+extern "C" int sf_depth_points_device(sf_handle c, const void* d_depth, int32_t depth_format, int32_t width, int32_t height,
+                                      int32_t depth_pitch, const sf_keypoint* d_kpts, int32_t n, const sf_stereo_camera* cam,
+                                      float* d_xyz_out, uint8_t* d_valid_out) {
+  if (!c || !cam || n < 0) return SF_EINVAL;
+  int rc = sf_check_depth(c, "sf_depth_points_device", d_depth, depth_format, width, height, depth_pitch, 0, 1);
+  if (rc != SF_OK) return rc;
+  if (n > 0 && (!d_kpts || !d_xyz_out)) return sf_fail(c, SF_EINVAL, "sf_depth_points_device: keypoints or output array missing");
+  if (n == 0) return SF_OK;
+  SF_HIP(c, hipSetDevice(c->device));
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch;
+  return sf_launch_depth_points_only(c, D, width, height, d_kpts, n, cam, d_xyz_out, d_valid_out);
+}
+
 extern "C" int sf_detect_orb_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                                     int32_t max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
                                     sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
@@ -297,7 +398,7 @@ int sf_grid_plan(sf_context* c, int width, int height, int max_features, FrontPl
 // The detection stage under a grid, for n images (the single calls: n = 1): the batch launchers with the cells as their
 // images, then k_grid_gather -- d_kpts [n][rows_cap] in full-image coordinates, d_n [n], nothing waited for
 int sf_grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_params& dp, const uint8_t* d_left, size_t image_stride,
-                   int n, int pitch, sf_keypoint* d_kpts, int32_t* d_n) {
+                   int n, int pitch, sf_keypoint* d_kpts, int32_t* d_n, const SfMask& mask) {
   const int cells = fp.rows * fp.cols;
   const size_t count_bytes = ((size_t)n * cells * 4 + 255) & ~(size_t)255;
   int rc;
@@ -308,12 +409,15 @@ int sf_grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_params&
   g.per_image = cells; g.cols = fp.cols;
   g.row_step = (size_t)fp.row_size * pitch; g.col_step = (size_t)fp.col_size;
   const uint8_t* d_roi = d_left + (size_t)fp.y * pitch + fp.x;
+  SfMask m = sf_mask_at(mask, fp.x, fp.y);               // the mask cropped and cut like the image, at its own pitch
+  m.cells = g;
+  m.cells.row_step = (size_t)fp.row_size * mask.pitch;
   if (sf_type_of(c).corners == CORNERS_FAST)
     rc = sf_launch_detect_fast_batch(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota, &c->fast,
-                                     d_cell_kpts, fp.quota, d_cell_n, g);
+                                     d_cell_kpts, fp.quota, d_cell_n, g, m);
   else
     rc = sf_launch_detect_corners_batch(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota,
-                                        dp.quality_level, dp.min_distance, d_cell_kpts, fp.quota, d_cell_n, g);
+                                        dp.quality_level, dp.min_distance, d_cell_kpts, fp.quota, d_cell_n, g, m);
   if (rc != SF_OK) return rc;
   return sf_launch_grid_gather(c, d_cell_kpts, d_cell_n, n, fp.rows, fp.cols, fp.quota, fp.x, fp.y, fp.col_size, fp.row_size, d_kpts,
                                fp.rows_cap, d_n);

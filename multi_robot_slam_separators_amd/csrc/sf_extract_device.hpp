@@ -23,6 +23,26 @@ struct ExtractCam {
   int identity_local, filter;
 };
 
+// the kernels' view of the caller's camera; filter: a corner without a finite 3D point is dropped
+inline ExtractCam sf_extract_cam(const sf_stereo_camera* cam) {
+  ExtractCam ec;
+  ec.fx = cam->fx; ec.fy = cam->fy; ec.cx = cam->cx; ec.cy = cam->cy; ec.cx_right = cam->cx_right;
+  ec.baseline = cam->baseline; ec.min_depth = cam->min_depth; ec.max_depth = cam->max_depth;
+  ec.identity_local = 1;
+  for (int e = 0; e < 12; ++e) {
+    ec.L[e] = cam->local_transform[e];
+    ec.identity_local = ec.identity_local && (ec.L[e] == ((e == 0 || e == 5 || e == 10) ? 1.0f : 0.0f));
+  }
+  ec.filter = cam->min_depth > 0.0f || cam->max_depth > 0.0f;
+  return ec;
+}
+
+// k_depth_points (k_depth.hip) between the describe kernel and k_extract_commit of sf_launch_extract_batch, for a keyframe
+// with a depth image: the 3D point of every corner from `depth` into xyz_tmp, keep[i] &= !cam.filter || the point is finite
+// (the describe kernel has run without right_x and without the filter: keep = "patch inside")
+void sf_launch_depth_points(sf_context* c, const SfDepthIn& depth, int width, int height, const sf_keypoint* d_kpts, int n, int n_img,
+                            const ExtractCam& cam, float* xyz_tmp, uint8_t* keep, uint8_t* valid, const ExtractBatch& B);
+
 // Byte 0's thread of a corner: the 3D point of the stereo pair (NaN when there is none) and the keep flag -- shared by
 // the BRIEF and the ORB descriptor kernels
 __device__ __forceinline__ void extract_point(const sf_keypoint& k, int i, bool inside, const float* __restrict__ right_x,

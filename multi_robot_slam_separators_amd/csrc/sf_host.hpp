@@ -96,7 +96,15 @@ struct FrontPlan {
 int sf_front_plan(sf_context* c, int width, int height, FrontPlan* fp);
 int sf_grid_plan(sf_context* c, int width, int height, int max_features, FrontPlan* fp);
 int sf_grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_params& dp, const uint8_t* d_left, size_t image_stride,
-                   int n, int pitch, sf_keypoint* d_kpts, int32_t* d_n);
+                   int n, int pitch, sf_keypoint* d_kpts, int32_t* d_n, const SfMask& mask = SfMask());
+// a detector mask on the ROI whose first pixel is (x, y) of its planes (no mask stays no mask)
+inline SfMask sf_mask_at(const SfMask& mask, int x, int y) {
+  SfMask m = mask;
+  if (m.p) m.p += (size_t)y * mask.pitch + x;
+  return m;
+}
+// what the depth calls refuse of their depth images (sf_detect.hip); `call` opens the message
+int sf_check_depth(sf_context* c, const char* call, bool present, int format, int width, int height, int pitch, size_t stride, int n);
 int sf_check_gftt(sf_context* c, double quality_level, double min_distance);
 int sf_gftt_validate(sf_context* c, const sf_gftt_params& g);
 // the GFTT window on what the detector is given (`what`: an image, a ROI, a grid cell): a side below GFTT/BlockSize is refused

@@ -384,6 +384,10 @@ struct sf_context {
   // which stereo correspondence the extraction calls run (sf_stereo_set_params): pyramidal LK (k_lk.hip) or block
   // matching (k_stereo_bm.hip) with SSD or SAD scores
   sf_stereo_params stereo = {1, 1};
+  // the depth keyframe calls (sf_depth_set_params; k_depth.hip): Vis/DepthAsMask, the detector mask made of the depth image.
+  // dp_depth / dp_mask: the device copy of the host call's depth image, the mask planes of a call (the images' pitch and stride)
+  sf_depth_params depth = {1};
+  Buf dp_depth, dp_mask;
   // Vis/GridRows x Vis/GridCols (sf_grid_set_params; k_grid.hip): the detector of types 4, 6 and 8 runs per cell of the
   // ROI; 1 x 1 = no cells.  ft_cells: every cell's count, then every cell's keypoints, before k_grid_gather joins them
   sf_grid_params grid = {1, 1};
@@ -681,6 +685,22 @@ struct SfCells {
   size_t row_step = 0, col_step = 0;           // bytes: row_size * pitch, col_size
 };
 
+// ---- a detector mask (Vis/DepthAsMask; cv's `mask` argument): uint8 planes beside the images of a detector launch, 0 = no
+// corner here.  Image z's plane starts at p + sf_cell_base(z, stride, cells): planes with the images' pitch and stride share
+// the images' cells.  p null: no mask, today's kernels.
+struct SfMask {
+  const uint8_t* p = nullptr;
+  int pitch = 0;
+  size_t stride = 0;
+  SfCells cells;
+};
+// the depth images of an extraction launch (sf_depth_format): image i at p + i * stride bytes, rows `pitch` bytes apart
+struct SfDepthIn {
+  const void* p = nullptr;
+  int format = 0, pitch = 0;
+  size_t stride = 0;
+};
+
 // ---- workspace of the corner detectors (k_gftt.hip, k_fast.hip), one image and a batch alike --------------------------
 // c->gf_planes: plane_bytes per image for the detector's own planes.  c->gf_keys: the candidate keys of image i at keys +
 // i * key_cap, and as much again for their sorted copy.  c->gf_scalar: the single call's corner count at byte 0, from byte
@@ -754,7 +774,8 @@ int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, uns
                                 unsigned bit1);
 int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                    int pitch, int max_corners, double quality_level, double min_distance,
-                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells = SfCells());
+                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells = SfCells(),
+                                   const SfMask& mask = SfMask());
 // the pyramid of the two stereo paths (k_lk.hip builds it, k_lk_track and k_stereo_bm read it)
 constexpr int LK_MAX_LEVELS = 16;
 struct LkLevel {
@@ -847,22 +868,30 @@ void sf_freak_bit_table(const int32_t* selected /* [512] */, uint8_t* table /* [
 int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_stride, int n_img, int width, int height,
                             int pitch, const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n,
                             const int32_t* d_n, const sf_stereo_camera* cam, const ExtractKind& kind, int slot,
-                            uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out, int32_t* d_rows_out);
+                            uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out, int32_t* d_rows_out,
+                            const SfDepthIn* depth = nullptr);
+// depth keyframes (k_depth.hip).  The masks of n depth images of one size (Feature2D::generateKeypoints); the 3D points of
+// n keypoints of one depth image, xyz [n][3] and valid [n] (the building block: no keep flags, no store)
+int sf_launch_depth_mask(sf_context* c, const SfDepthIn& depth, int n_img, int width, int height, float min_depth, float max_depth,
+                         uint8_t* d_mask, int mask_pitch, size_t mask_stride);
+int sf_launch_depth_points_only(sf_context* c, const SfDepthIn& depth, int width, int height, const sf_keypoint* d_kpts, int n,
+                                const sf_stereo_camera* cam, float* d_xyz, uint8_t* d_valid);
 int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
-                             int32_t* n_out);
+                             int32_t* n_out, const SfMask& mask = SfMask());
 // FAST-9/16 + limitKeypoints (k_fast.hip); prm validated by the caller
 int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
+                          const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out,
+                          const SfMask& mask = SfMask());
 int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                                 int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out, const SfCells& cells = SfCells());
+                                int32_t* d_n_out, const SfCells& cells = SfCells(), const SfMask& mask = SfMask());
 // one level of FAST on n_img images img_stride bytes apart: k_fast_score + k_fast_candidates (image i: score plane at
 // + i * plane_stride, keys at + i * key_cap, keys = score << 32 | pixel index in arrival order, count[i] the corners found;
 // zeroed by the caller)
 void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
                           int threshold, int nonmax, uint8_t* score, size_t plane_stride, unsigned long long* keys, unsigned* count,
-                          unsigned key_cap, const SfCells& cells = SfCells());
+                          unsigned key_cap, const SfCells& cells = SfCells(), const SfMask& mask = SfMask());
 // ORB detector (k_orb_detect.hip); det / orb validated by the caller
 SfOrbPyr sf_orb_pyr_layout(int width, int height, float scale_factor, int n_levels);
 void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota);

@@ -24,7 +24,7 @@ static int check_camera_image(sf_context* c, bool present, int format, int width
 static int extract_keyframe(sf_context* c, const uint8_t* d_left, int32_t width, int32_t height, int32_t pitch,
                             const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int32_t n,
                             const sf_stereo_camera* cam, int32_t* out_slot, int32_t* out_rows, uint8_t* d_desc_out,
-                            float* d_xyz_out, sf_keypoint* d_kpts_out, bool reuse_sift_pyramid) {
+                            float* d_xyz_out, sf_keypoint* d_kpts_out, bool reuse_sift_pyramid, const SfDepthIn* depth = nullptr) {
   if (!c || !cam || n < 0) return SF_EINVAL;
   int rc = sf_check_image(c, d_left, width, height, pitch, 1, "left image");
   if (rc != SF_OK) return rc;
@@ -40,7 +40,7 @@ static int extract_keyframe(sf_context* c, const uint8_t* d_left, int32_t width,
   const int slot = c->store.slots;
   if ((rc = sf_launch_extract_batch(c, d_left, 0, 1, width, height, pitch, d_kpts, d_right_x, d_status, n, nullptr, cam, kind,
                                     slot, d_desc_out, d_xyz_out, d_kpts_out,
-                                    out_rows ? (int32_t*)c->ex_rows.p : nullptr)) != SF_OK)
+                                    out_rows ? (int32_t*)c->ex_rows.p : nullptr, depth)) != SF_OK)
     return rc;
   c->store.slots += 1;
   if (out_slot) *out_slot = slot;
@@ -54,6 +54,19 @@ extern "C" int sf_extract_keyframe_device(sf_handle c, const uint8_t* d_left, in
                                           float* d_xyz_out, sf_keypoint* d_kpts_out) {
   return extract_keyframe(c, d_left, width, height, pitch, d_kpts, d_right_x, d_status, n, cam, out_slot, out_rows, d_desc_out,
                           d_xyz_out, d_kpts_out, false);
+}
+
+extern "C" int sf_extract_keyframe_depth_device(sf_handle c, const uint8_t* d_left, int32_t width, int32_t height, int32_t pitch,
+                                                const sf_keypoint* d_kpts, const void* d_depth, int32_t depth_format,
+                                                int32_t depth_pitch, int32_t n, const sf_stereo_camera* cam, int32_t* out_slot,
+                                                int32_t* out_rows, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n < 0) return SF_EINVAL;
+  const int rc = sf_check_depth(c, "sf_extract_keyframe_depth_device", d_depth, depth_format, width, height, depth_pitch, 0, 1);
+  if (rc != SF_OK) return rc;
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch;
+  return extract_keyframe(c, d_left, width, height, pitch, d_kpts, nullptr, nullptr, n, cam, out_slot, out_rows, d_desc_out,
+                          d_xyz_out, d_kpts_out, false, &D);
 }
 
 // ---- what differs between the families of batch calls (the generic calls of types 3 .. 8; the _orb_, _surf_ and _sift_ calls of
@@ -111,8 +124,10 @@ static int family_reserve(sf_context* c, const SfFeatureType& t, int n, int widt
 
 // The detector on images [i0, i0 + m) of a batch, into that sub-range of c->ft_kpts / c->ft_counts; `kind`: what it leaves the extraction
 static int family_detect(sf_context* c, const SfFeatureType& t, const BatchPlan& plan, ExtractKind* kind, const uint8_t* d_left,
-                         size_t image_stride, int i0, int m, int width, int height, int pitch) {
+                         size_t image_stride, int i0, int m, int width, int height, int pitch, const SfMask& mask_all = SfMask()) {
   const FrontPlan& fp = plan.front;
+  SfMask mask = mask_all;                                  // (a depth call's mask, types 3 .. 8 only: planes laid out like the images)
+  if (mask.p) mask.p += (size_t)i0 * mask.stride;
   const int maxf = fp.rows_cap;                            // rows per keyframe: max_features, or the grid's R C quota
   const uint8_t* d_images = d_left + (size_t)i0 * image_stride;
   const uint8_t* d_roi = d_images + (size_t)fp.y * pitch + fp.x;   // the ROI, at the parent's pitch and stride
@@ -130,11 +145,12 @@ static int family_detect(sf_context* c, const SfFeatureType& t, const BatchPlan&
       return sf_launch_detect_sift_batch(c, d_images, image_stride, m, width, height, pitch, maxf, &c->sift, d_kpts, maxf, d_n);
     case BATCH_GENERIC:
       if (fp.grid())                                       // the cells as the detector's images, joined by k_grid_gather
-        return sf_grid_detect(c, fp, plan.dp, d_images, image_stride, m, pitch, d_kpts, d_n);
+        return sf_grid_detect(c, fp, plan.dp, d_images, image_stride, m, pitch, d_kpts, d_n, mask);
       if (t.corners == CORNERS_FAST)
-        return sf_launch_detect_fast_batch(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n);
+        return sf_launch_detect_fast_batch(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n, SfCells(),
+                                           sf_mask_at(mask, fp.x, fp.y));
       return sf_launch_detect_corners_batch(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, plan.dp.quality_level,
-                                            plan.dp.min_distance, d_kpts, maxf, d_n);
+                                            plan.dp.min_distance, d_kpts, maxf, d_n, SfCells(), sf_mask_at(mask, fp.x, fp.y));
   }
   return SF_EINVAL;
 }
@@ -259,6 +275,122 @@ extern "C" int sf_get_features_and_descriptor_u8(sf_handle c, const uint8_t* lef
                            rows_out, slot_out);
 }
 
+// ---- depth keyframes: SensorData(rgb, depth, model) in place of a stereo pair (kernels in k_depth.hip) --------------------
+// Vis/DepthAsMask is built for the two corner detectors: a type with a detector of its own takes no mask
+static int check_depth_as_mask(sf_context* c, const char* call) {
+  const SfFeatureType& t = sf_type_of(c);
+  if (c->depth.depth_as_mask && t.corners == CORNERS_OWN)
+    return sf_fail(c, SF_EINVAL, "%s: Vis/DepthAsMask under Vis/FeatureType %d (%s) is not built (its detector takes no mask); "
+                   "sf_depth_set_params with depth_as_mask = 0 runs it on the whole image", call, t.type, t.name);
+  return SF_OK;
+}
+
+// The depth twin of get_features_host: upload image and depth, mask (Vis/DepthAsMask), detect under it, refine, extract with
+// the depth image's 3D points, download.  No right image, no stereo stage
+extern "C" int sf_get_features_and_descriptor_depth(sf_handle c, const uint8_t* image, int32_t image_format, const void* depth,
+                                                    int32_t depth_format, int32_t width, int32_t height, int32_t image_pitch,
+                                                    int32_t depth_pitch, const sf_stereo_camera* cam,
+                                                    const sf_detector_params* det, uint8_t* desc_out, float* xyz_out,
+                                                    sf_keypoint* kpts_out, int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
+  static const char* const call = "sf_get_features_and_descriptor_depth";
+  if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
+  *rows_out = 0;
+  int rc = check_camera_image(c, image, image_format, width, height, image_pitch, 3, "sf_get_features_and_descriptor_depth: image");
+  if (rc != SF_OK) return rc;
+  if ((rc = sf_check_depth(c, call, depth, depth_format, width, height, depth_pitch, 0, 1)) != SF_OK) return rc;
+  if ((rc = check_depth_as_mask(c, call)) != SF_OK) return rc;
+  FrontPlan fp;
+  if ((rc = sf_front_plan(c, width, height, &fp)) != SF_OK) return rc;
+  const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
+  if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
+    return sf_fail(c, SF_ERANGE, "%s: max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", call, dp.max_features, SF_MAX_FEATURES);
+  if ((rc = sf_grid_plan(c, width, height, dp.max_features, &fp)) != SF_OK) return rc;
+  if ((rc = sf_check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
+  if (fp.grid() && (rc = sf_check_pixels(c, fp.col_size, fp.row_size)) != SF_OK) return rc;
+  SF_HIP(c, hipSetDevice(c->device));
+  ExtractKind kind;
+  if ((rc = sf_extract_kind(c, &kind)) != SF_OK) return rc;
+  const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
+  const int maxf = fp.rows_cap;
+  const int elem = depth_format == SF_DEPTH_F32_M ? 4 : 2;
+  const int dz_pitch = (elem * width + 15) & ~15;          // rows padded to 16 bytes: k_depth_mask's wide loads
+  if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->dp_depth, (size_t)dz_pitch * height)) != SF_OK) return rc;
+  if (c->depth.depth_as_mask && (rc = sf_buf_reserve(c, c->dp_mask, img_bytes)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->ft_counts, 4)) != SF_OK) return rc;
+  const size_t row_bytes = (size_t)kind.bytes + 12 + sizeof(sf_keypoint);
+  if ((rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64)) != SF_OK) return rc;
+  uint8_t* d_left = (uint8_t*)c->ft_images.p;
+  if (image_format == SF_IMAGE_MONO8) {
+    SF_HIP(c, hipMemcpy2DAsync(d_left, width, image, image_pitch, width, height, hipMemcpyHostToDevice, c->stream));
+  } else {                                                 // as sf_get_features_and_descriptor_u8 converts its pair
+    const int src_pitch = (3 * width + 15) & ~15;
+    const size_t src_bytes = ((size_t)src_pitch * height + 255) & ~(size_t)255;
+    if ((rc = sf_buf_reserve(c, c->img_src, src_bytes)) != SF_OK) return rc;
+    uint8_t* d_src = (uint8_t*)c->img_src.p;
+    SF_HIP(c, hipMemcpy2DAsync(d_src, src_pitch, image, image_pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
+    if ((rc = sf_launch_image_gray(c, d_src, nullptr, 1, image_format, c->gray_rule, width, height, src_pitch, src_bytes, 1, d_left,
+                                   width, img_bytes)) != SF_OK)
+      return rc;
+  }
+  SF_HIP(c, hipMemcpy2DAsync(c->dp_depth.p, dz_pitch, depth, depth_pitch, (size_t)elem * width, height, hipMemcpyHostToDevice, c->stream));
+  SfDepthIn D;
+  D.p = c->dp_depth.p; D.format = depth_format; D.pitch = dz_pitch;
+  SfMask mask;                                             // the image's pitch: cropped and cut into cells like the image
+  if (c->depth.depth_as_mask) {
+    if ((rc = sf_launch_depth_mask(c, D, 1, width, height, cam->min_depth, cam->max_depth, (uint8_t*)c->dp_mask.p, width, 0)) != SF_OK)
+      return rc;
+    mask.p = (const uint8_t*)c->dp_mask.p; mask.pitch = width;
+  }
+  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
+  int32_t n = 0;
+  const uint8_t* d_roi = d_left + (size_t)fp.y * width + fp.x;
+  const SfFeatureType& t = sf_type_of(c);
+  if (fp.grid()) {
+    if ((rc = sf_grid_detect(c, fp, dp, d_left, 0, 1, width, d_kpts, (int32_t*)c->ft_counts.p, mask)) != SF_OK) return rc;
+    rc = sf_word_to_host(c, c->ft_counts.p, &n);
+  } else if (t.family != BATCH_GENERIC || !mask.p) {       // no mask: the public detector call of the type's family
+    switch (t.family) {
+      case BATCH_ORB: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
+      case BATCH_SURF: rc = sf_detect_surf_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
+      case BATCH_SIFT: rc = sf_detect_sift_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
+      case BATCH_GENERIC:
+        rc = t.corners == CORNERS_FAST ? sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n)
+                                       : sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
+    }
+  } else {
+    const uint8_t* d_mask_roi = mask.p + (size_t)fp.y * width + fp.x;
+    rc = t.corners == CORNERS_FAST
+             ? sf_detect_fast_masked_device(c, d_roi, fp.w, fp.h, width, d_mask_roi, width, maxf, nullptr, d_kpts, maxf, &n)
+             : sf_detect_corners_masked_device(c, d_roi, fp.w, fp.h, width, d_mask_roi, width, maxf, dp.quality_level, dp.min_distance,
+                                               d_kpts, maxf, &n);
+  }
+  if (rc != SF_OK) return rc;
+  n = std::min(n, maxf);
+  if (fp.launch() &&
+      (rc = sf_launch_corner_subpix(c, d_left, 0, 1, width, height, width, d_kpts, n, nullptr, maxf, fp.off_x(), fp.off_y(),
+                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
+    return rc;
+  uint8_t* d_desc = (uint8_t*)c->ft_wire.p;
+  float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
+  sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
+  int32_t slot = -1, rows = 0;
+  if ((rc = extract_keyframe(c, d_left, width, height, width, d_kpts, nullptr, nullptr, n, cam, &slot, &rows, d_desc, d_xyz, d_kp_out,
+                             kind.has_sift, &D)) != SF_OK)
+    return rc;
+  *rows_out = rows;
+  if (slot_out) *slot_out = slot;
+  const int32_t k = std::min(rows, cap_rows);
+  if (k > 0) {
+    if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, d_desc, (size_t)k * kind.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (xyz_out) SF_HIP(c, hipMemcpyAsync(xyz_out, d_xyz, (size_t)k * 12, hipMemcpyDeviceToHost, c->stream));
+    if (kpts_out) SF_HIP(c, hipMemcpyAsync(kpts_out, d_kp_out, (size_t)k * sizeof(sf_keypoint), hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return SF_OK;
+}
+
 // n keyframes from device images to n store slots in ONE launch sequence: detector, stereo correspondence and
 // extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
 // host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.  In three parts, shared by the eight batch
@@ -314,18 +446,27 @@ static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan*
 // store slots from slot + i0 on
 static int batch_follow(sf_context* c, const BatchPlan& plan, const ExtractKind& kind, const uint8_t* d_left, const uint8_t* d_right,
                         int n, int i0, int m, int width, int height, int pitch, size_t image_stride, const sf_stereo_camera* cam,
-                        int slot, int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+                        int slot, int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
+                        const SfDepthIn* depth_all = nullptr) {
   const int maxf = plan.front.rows_cap;
   const size_t rows_all = (size_t)maxf * n, r0 = (size_t)maxf * i0;
   const FrontPlan& fp = plan.front;
   int rc;
-  d_left += (size_t)i0 * image_stride; d_right += (size_t)i0 * image_stride;
+  d_left += (size_t)i0 * image_stride;
+  if (d_right) d_right += (size_t)i0 * image_stride;
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p + r0;
   const int32_t* d_n = (const int32_t*)c->ft_counts.p + i0;
   if (fp.launch() &&
       (rc = sf_launch_corner_subpix(c, d_left, image_stride, m, width, height, pitch, d_kpts, maxf, d_n, maxf, fp.off_x(), fp.off_y(),
                                     fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
     return rc;
+  if (depth_all) {                                       // a depth keyframe: no stereo stage, the 3D points inside the extraction
+    SfDepthIn depth = *depth_all;
+    depth.p = (const char*)depth.p + (size_t)i0 * depth.stride;
+    return sf_launch_extract_batch(c, d_left, image_stride, m, width, height, pitch, d_kpts, nullptr, nullptr, maxf, d_n, cam, kind,
+                                   slot + i0, d_desc_out ? d_desc_out + r0 * kind.bytes : nullptr, d_xyz_out ? d_xyz_out + 3 * r0 : nullptr,
+                                   d_kpts_out ? d_kpts_out + r0 : nullptr, d_rows_out ? d_rows_out + i0 : nullptr, &depth);
+  }
   float* d_xy = (float*)c->ft_flow.p;                    // [n][maxf][2], then x [n][maxf], then status [n][maxf]
   float* d_rx = d_xy + 2 * rows_all;
   uint8_t* d_status = (uint8_t*)(d_rx + rows_all);
@@ -345,7 +486,8 @@ static int batch_follow(sf_context* c, const BatchPlan& plan, const ExtractKind&
 // large to keep for a whole batch, so a chunk's extraction reads them before the next chunk's detector overwrites them
 static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_left, const uint8_t* d_right, int n, int width,
                         int height, int pitch, size_t image_stride, const sf_stereo_camera* cam, int32_t* first_slot_out,
-                        int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+                        int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out,
+                        const SfDepthIn* depth = nullptr, const SfMask& mask = SfMask()) {
   const SfFeatureType& t = sf_type_of(c);
   const int slot = c->store.slots;
   ExtractKind kind = plan.kind;
@@ -356,9 +498,9 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   }
   for (int i0 = 0; i0 < n; i0 += chunk) {
     const int m = std::min(chunk, n - i0);
-    if ((rc = family_detect(c, t, plan, &kind, d_left, image_stride, i0, m, width, height, pitch)) != SF_OK) return rc;
+    if ((rc = family_detect(c, t, plan, &kind, d_left, image_stride, i0, m, width, height, pitch, mask)) != SF_OK) return rc;
     if ((rc = batch_follow(c, plan, kind, d_left, d_right, n, i0, m, width, height, pitch, image_stride, cam, slot, d_rows_out,
-                           d_desc_out, d_xyz_out, d_kpts_out)) != SF_OK)
+                           d_desc_out, d_xyz_out, d_kpts_out, depth)) != SF_OK)
       return rc;
   }
   c->store.slots += n;
@@ -622,4 +764,122 @@ extern "C" int sf_add_keyframes_sift_u8_batch_device(sf_handle c, const uint8_t*
                                                      float* d_xyz_out, sf_keypoint* d_kpts_out) {
   return add_keyframes_batch(c, BATCH_SIFT, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
                              flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+}
+
+// ---- the batch forms of the depth keyframes: one call for every family, the stages of sf_get_features_and_descriptor_depth in
+// one launch sequence -- masks of all n depth images, detector under them, refinement, extraction with depth points --------
+// what both refuse before anything is touched, and the plan (batch_check with the handle's own family and the flow defaults)
+static int depth_batch_check(sf_context* c, const char* call, bool images, const void* d_depth, int depth_format, int n, int width,
+                             int height, int pitch, size_t image_stride, int depth_pitch, size_t depth_stride,
+                             const sf_detector_params* det, BatchPlan* plan) {
+  int rc;
+  if (n > 0) {
+    if (!images || width < 3 || height < 3 || pitch < width)
+      return sf_fail(c, SF_EINVAL, "%s: images missing or malformed (%d x %d, pitch %d)", call, width, height, pitch);
+    if (image_stride < (size_t)pitch * height)
+      return sf_fail(c, SF_EINVAL, "%s: image stride %zu is less than an image (%d rows of pitch %d)", call, image_stride, height, pitch);
+    if ((rc = sf_check_depth(c, call, d_depth, depth_format, width, height, depth_pitch, depth_stride, n)) != SF_OK) return rc;
+  } else if ((rc = sf_check_depth(c, call, true, depth_format, 1, 1, 4, 0, 0)) != SF_OK) {
+    return rc;
+  }
+  if ((rc = check_depth_as_mask(c, call)) != SF_OK) return rc;
+  return batch_check(c, sf_type_of(c).family, images, n, width, height, pitch, image_stride, det, nullptr, plan);
+}
+
+// the masks of the n depth images, with the planes' pitch and stride (family_detect crops and cuts them like the images)
+static int depth_batch_mask(sf_context* c, const SfDepthIn& D, int n, int width, int height, int pitch, size_t image_stride,
+                            const sf_stereo_camera* cam, SfMask* mask) {
+  if (!c->depth.depth_as_mask) return SF_OK;
+  mask->p = (const uint8_t*)c->dp_mask.p; mask->pitch = pitch; mask->stride = image_stride;
+  return sf_launch_depth_mask(c, D, n, width, height, cam->min_depth, cam->max_depth, (uint8_t*)c->dp_mask.p, pitch, image_stride);
+}
+
+extern "C" int sf_get_features_and_descriptor_depth_batch_device(sf_handle c, const uint8_t* d_images, const void* d_depth,
+                                                                 int32_t depth_format, int32_t n_keyframes, int32_t width,
+                                                                 int32_t height, int32_t image_pitch, size_t image_stride,
+                                                                 int32_t depth_pitch, size_t depth_stride,
+                                                                 const sf_stereo_camera* cam, const sf_detector_params* det,
+                                                                 int32_t* first_slot_out, int32_t* d_rows_out,
+                                                                 uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  const int n = n_keyframes;
+  BatchPlan plan;
+  int rc = depth_batch_check(c, "sf_get_features_and_descriptor_depth_batch_device", d_images, d_depth, depth_format, n, width, height,
+                             image_pitch, image_stride, depth_pitch, depth_stride, det, &plan);
+  if (rc != SF_OK) return rc;
+  if (n == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
+  if (c->depth.depth_as_mask && (rc = sf_buf_reserve(c, c->dp_mask, (size_t)n * image_stride)) != SF_OK) return rc;
+  if ((rc = batch_reserve(c, n, width, height, &plan)) != SF_OK) return rc;
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = depth_stride;
+  SfMask mask;
+  if ((rc = depth_batch_mask(c, D, n, width, height, image_pitch, image_stride, cam, &mask)) != SF_OK) return rc;
+  return batch_launch(c, plan, d_images, nullptr, n, width, height, image_pitch, image_stride, cam, first_slot_out, d_rows_out,
+                      d_desc_out, d_xyz_out, d_kpts_out, &D, mask);
+}
+
+// add_keyframes_batch with depth images in place of the right images: the gray planes of the n colour images, the network on
+// the colour images, the depth stages on the planes, the NN rows last
+extern "C" int sf_add_keyframes_depth_batch_device(sf_handle c, const uint8_t* d_images, int32_t image_format, const void* d_depth,
+                                                   int32_t depth_format, int32_t n_keyframes, int32_t width, int32_t height,
+                                                   int32_t image_pitch, size_t image_stride, int32_t depth_pitch,
+                                                   size_t depth_stride, const sf_stereo_camera* cam,
+                                                   const sf_detector_params* det, int32_t* first_slot_out,
+                                                   int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                                                   float* d_xyz_out, sf_keypoint* d_kpts_out) {
+  static const char* const call = "sf_add_keyframes_depth_batch_device";
+  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
+  const int n = n_keyframes;
+  int rc;
+  if ((rc = check_format(c, image_format)) != SF_OK) return rc;
+  if (n > 0) {
+    if ((rc = check_camera_image(c, d_images, image_format, width, height, image_pitch, 3, "sf_add_keyframes_depth_batch_device: images")) != SF_OK)
+      return rc;
+    if (image_stride < (size_t)image_pitch * height)
+      return sf_fail(c, SF_EINVAL, "%s: image stride %zu is less than an image (%d rows of pitch %d)", call, image_stride, height, image_pitch);
+  }
+  const int g_pitch = n > 0 ? (width + 15) & ~15 : 0;      // the planes this call makes: rows padded to 16 bytes
+  const size_t g_stride = ((size_t)g_pitch * (n > 0 ? height : 0) + 255) & ~(size_t)255;
+  BatchPlan plan;
+  if ((rc = depth_batch_check(c, call, true, d_depth, depth_format, n, width, height, g_pitch, g_stride, depth_pitch, depth_stride, det,
+                              &plan)) != SF_OK)
+    return rc;
+  if (n == 0) {
+    if (first_slot_out) *first_slot_out = c->store.slots;
+    if (first_nn_row_out) *first_nn_row_out = c->nn_local.n;
+    return SF_OK;
+  }
+  const int dims = c->params.netvlad_dimensions, pca_dim = sf_netvlad_pca_dim(c);
+  if (pca_dim == 0) return sf_fail(c, SF_EINVAL, "%s: no NetVLAD model loaded (sf_netvlad_load)", call);
+  if (dims < 1 || dims > pca_dim)
+    return sf_fail(c, SF_EINVAL, "%s: netvlad_dimensions %d is beyond the loaded model's %d WPCA outputs", call, dims, pca_dim);
+  if ((rc = sf_netvlad_check(c, n, height, width, dims)) != SF_OK) return rc;
+  if ((rc = sf_nn_reserve_rows(c, c->nn_local, n, dims)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->img_gray, (size_t)n * g_stride)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->img_desc, (size_t)n * dims * sizeof(float))) != SF_OK) return rc;
+  if (c->depth.depth_as_mask && (rc = sf_buf_reserve(c, c->dp_mask, (size_t)n * g_stride)) != SF_OK) return rc;
+  if ((rc = batch_reserve(c, n, width, height, &plan)) != SF_OK) return rc;
+  uint8_t* g_images = (uint8_t*)c->img_gray.p;
+  if ((rc = sf_launch_image_gray(c, d_images, nullptr, n, image_format, c->gray_rule, width, height, image_pitch, image_stride, n,
+                                 g_images, g_pitch, g_stride)) != SF_OK)
+    return rc;
+  if ((rc = sf_netvlad_infer_u8_batch_impl(c, d_images, image_format, n, height, width, image_pitch, image_stride,
+                                           (float*)c->img_desc.p, dims)) != SF_OK)
+    return rc;
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = depth_stride;
+  SfMask mask;
+  if ((rc = depth_batch_mask(c, D, n, width, height, g_pitch, g_stride, cam, &mask)) != SF_OK) return rc;
+  int32_t slot = -1;
+  if ((rc = batch_launch(c, plan, g_images, nullptr, n, width, height, g_pitch, g_stride, cam, &slot, d_rows_out, d_desc_out,
+                         d_xyz_out, d_kpts_out, &D, mask)) != SF_OK)
+    return rc;
+  const int row = c->nn_local.n;
+  if ((rc = sf_nn_append(c, c->nn_local, c->img_desc.p, n, dims, 1)) != SF_OK) {
+    c->store.slots -= n;             // (the slots' rows stay behind the end of the store: the keyframes were never added)
+    return rc;
+  }
+  if (first_slot_out) *first_slot_out = slot;
+  if (first_nn_row_out) *first_nn_row_out = row;
+  return SF_OK;
 }

@@ -202,6 +202,25 @@ def load():
         "sf_add_keyframes_u8_batch_device": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_size_t,
                                                        P(_abi.StereoCamera), P(_abi.DetectorParams),
                                                        P(_abi.StereoFlowParams), P(i32), P(i32), vp, vp, vp, vp]),
+        "sf_depth_defaults": (None, [P(_abi.DepthParams)]),
+        "sf_depth_set_params": (C.c_int, [vp, P(_abi.DepthParams)]),
+        "sf_depth_get_params": (C.c_int, [vp, P(_abi.DepthParams)]),
+        "sf_depth_mask_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, C.c_float, C.c_float, vp, i32,
+                                           C.c_size_t]),
+        "sf_depth_points_device": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, P(_abi.StereoCamera), vp, vp]),
+        "sf_detect_corners_masked_device": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, vp, i32,
+                                                      P(i32)]),
+        "sf_detect_fast_masked_device": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, P(_abi.FastParams), vp, i32, P(i32)]),
+        "sf_extract_keyframe_depth_device": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, P(_abi.StereoCamera),
+                                                       P(i32), P(i32), vp, vp, vp]),
+        "sf_get_features_and_descriptor_depth": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, i32, P(_abi.StereoCamera),
+                                                           P(_abi.DetectorParams), vp, vp, vp, i32, P(i32), P(i32)]),
+        "sf_get_features_and_descriptor_depth_batch_device": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, C.c_size_t, i32,
+                                                                         C.c_size_t, P(_abi.StereoCamera),
+                                                                         P(_abi.DetectorParams), P(i32), vp, vp, vp, vp]),
+        "sf_add_keyframes_depth_batch_device": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, i32, C.c_size_t, i32,
+                                                          C.c_size_t, P(_abi.StereoCamera), P(_abi.DetectorParams), P(i32),
+                                                          P(i32), vp, vp, vp, vp]),
         "sf_prof_enable": (C.c_int, [vp, C.c_int]),
         "sf_prof_select": (C.c_int, [vp, C.c_uint32]),
         "sf_stream_placement": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
@@ -268,6 +287,10 @@ EXPORTED = [
     "sf_get_features_and_descriptor_sift_batch_device", "sf_add_keyframes_sift_u8_batch_device", "sf_sift_batch_status",
     "sf_debug_sift_batch_chunk", "sf_sift_batch_plan",
     "sf_debug_knn2_u8",
+    "sf_depth_defaults", "sf_depth_set_params", "sf_depth_get_params", "sf_depth_mask_device", "sf_depth_points_device",
+    "sf_detect_corners_masked_device", "sf_detect_fast_masked_device", "sf_extract_keyframe_depth_device",
+    "sf_get_features_and_descriptor_depth", "sf_get_features_and_descriptor_depth_batch_device",
+    "sf_add_keyframes_depth_batch_device",
 ]
 
 
@@ -1006,6 +1029,108 @@ class SeparatorFinder:
             C.c_void_p(d_status), n, C.byref(cam), C.byref(slot), C.byref(rows) if want_rows else None,
             C.c_void_p(d_desc_out), C.c_void_p(d_xyz_out), C.c_void_p(d_kpts_out)))
         return slot.value, (rows.value if want_rows else None)
+
+    # -- depth keyframes (RGB-D): 3D points from a registered depth image, Vis/DepthAsMask -----------------------------
+    def depth_set_params(self, params):
+        """The handle's _abi.DepthParams: Vis/DepthAsMask, whether the detector of the depth keyframe calls sees the mask
+        of the depth image (types 3, 4, 5, 6, 8; types 0, 1, 2 need 0); 1 on a fresh handle."""
+        self._check(self._L.sf_depth_set_params(self._h, C.byref(params)))
+
+    def depth_get_params(self):
+        p = _abi.DepthParams()
+        self._check(self._L.sf_depth_get_params(self._h, C.byref(p)))
+        return p
+
+    def depth_mask_device(self, d_depth, depth_format, width, height, depth_pitch, depth_stride, n_images, min_depth,
+                          max_depth, d_mask, mask_pitch, mask_stride):
+        """The detector masks of n_images device depth images (asynchronous); device pointers (ints), pitches and strides
+        in bytes."""
+        self._check(self._L.sf_depth_mask_device(self._h, C.c_void_p(d_depth), depth_format, width, height, depth_pitch,
+                                                 int(depth_stride), n_images, min_depth, max_depth, C.c_void_p(d_mask),
+                                                 mask_pitch, int(mask_stride)))
+
+    def depth_points_device(self, d_depth, depth_format, width, height, depth_pitch, d_kpts, n, cam, d_xyz_out,
+                            d_valid_out=None):
+        """The 3D points of n device keypoints from a device depth image (asynchronous): d_xyz_out [n][3] float32,
+        d_valid_out [n] uint8 (optional)."""
+        self._check(self._L.sf_depth_points_device(self._h, C.c_void_p(d_depth), depth_format, width, height, depth_pitch,
+                                                   C.c_void_p(d_kpts), n, C.byref(cam), C.c_void_p(d_xyz_out),
+                                                   C.c_void_p(d_valid_out)))
+
+    def detect_corners_masked_device(self, d_image, width, height, pitch, d_mask, mask_pitch, max_corners, quality_level,
+                                     min_distance, d_kpts_out, cap):
+        """detect_corners_device as cv::goodFeaturesToTrack(image, ..., mask): d_mask a uint8 plane of the image's size."""
+        n = C.c_int32()
+        self._check(self._L.sf_detect_corners_masked_device(
+            self._h, C.c_void_p(d_image), width, height, pitch, C.c_void_p(d_mask), mask_pitch, max_corners,
+            float(quality_level), float(min_distance), C.c_void_p(d_kpts_out), cap, C.byref(n)))
+        return n.value
+
+    def detect_fast_masked_device(self, d_image, width, height, pitch, d_mask, mask_pitch, max_features, d_kpts_out, cap,
+                                  params=None):
+        """detect_fast_device as FastFeatureDetector::detect(image, keypoints, mask)."""
+        n = C.c_int32()
+        self._check(self._L.sf_detect_fast_masked_device(
+            self._h, C.c_void_p(d_image), width, height, pitch, C.c_void_p(d_mask), mask_pitch, max_features,
+            C.byref(params) if params is not None else None, C.c_void_p(d_kpts_out), cap, C.byref(n)))
+        return n.value
+
+    def extract_keyframe_depth_device(self, d_left, width, height, pitch, d_kpts, d_depth, depth_format, depth_pitch, n, cam,
+                                      d_desc_out=None, d_xyz_out=None, d_kpts_out=None, want_rows=True):
+        """extract_keyframe_device with the keyframe's depth image in place of d_right_x / d_status.  Returns (slot, rows
+        kept or None)."""
+        slot, rows = C.c_int32(), C.c_int32()
+        self._check(self._L.sf_extract_keyframe_depth_device(
+            self._h, C.c_void_p(d_left), width, height, pitch, C.c_void_p(d_kpts), C.c_void_p(d_depth), depth_format,
+            depth_pitch, n, C.byref(cam), C.byref(slot), C.byref(rows) if want_rows else None, C.c_void_p(d_desc_out),
+            C.c_void_p(d_xyz_out), C.c_void_p(d_kpts_out)))
+        return slot.value, (rows.value if want_rows else None)
+
+    def get_features_and_descriptor_depth(self, image, depth, cam, det=None, image_format=_abi.SF_IMAGE_MONO8):
+        """GetFeatsAndDesc for a SensorData(rgb, depth, model) caller, on host arrays: image uint8 [h, w] (mono8) or
+        [h, w, 3] (rgb8 / bgr8), depth uint16 [h, w] millimetres or float32 [h, w] metres, registered to the image.
+        Returns what get_features_and_descriptor returns."""
+        image, w, h, image_pitch = _camera_image(image, image_format)
+        depth = np.asarray(depth)
+        fmt = _abi.depth_format_of(depth)
+        if depth.shape != (h, w) or depth.strides[1] != depth.itemsize:
+            raise ValueError("depth must be a 2-D array of the image's height and width with contiguous rows")
+        cap = self._rows_cap(w, h, det.max_features if det is not None else 1000)
+        desc = np.zeros((cap, self.descriptor_bytes()), np.uint8)
+        xyz = np.zeros((cap, 3), np.float32)
+        kp = np.zeros(cap, _abi.KEYPOINT_DTYPE)
+        rows, slot = C.c_int32(), C.c_int32()
+        self._check(self._L.sf_get_features_and_descriptor_depth(
+            self._h, C.c_void_p(image.ctypes.data), image_format, C.c_void_p(depth.ctypes.data), fmt, w, h, image_pitch,
+            depth.strides[0], C.byref(cam), C.byref(det) if det is not None else None, C.c_void_p(desc.ctypes.data),
+            C.c_void_p(xyz.ctypes.data), C.c_void_p(kp.ctypes.data), cap, C.byref(rows), C.byref(slot)))
+        n = min(rows.value, cap)
+        return desc[:n].copy(), xyz[:n].copy(), kp[:n].copy(), slot.value
+
+    def get_features_and_descriptor_depth_batch_device(self, d_images, d_depth, depth_format, n_keyframes, width, height,
+                                                       image_pitch, image_stride, depth_pitch, depth_stride, cam, det=None,
+                                                       d_rows_out=None, d_desc_out=None, d_xyz_out=None, d_kpts_out=None):
+        """n depth keyframes from device MONO8 planes and depth planes to n store slots in one launch sequence, no host
+        wait, under every feature type; outputs as get_features_and_descriptor_batch_device.  Returns the first slot."""
+        first = C.c_int32()
+        self._check(self._L.sf_get_features_and_descriptor_depth_batch_device(
+            self._h, C.c_void_p(d_images), C.c_void_p(d_depth), depth_format, n_keyframes, width, height, image_pitch,
+            int(image_stride), depth_pitch, int(depth_stride), C.byref(cam), C.byref(det) if det is not None else None,
+            C.byref(first), C.c_void_p(d_rows_out), C.c_void_p(d_desc_out), C.c_void_p(d_xyz_out), C.c_void_p(d_kpts_out)))
+        return first.value
+
+    def add_keyframes_depth_batch_device(self, d_images, image_format, d_depth, depth_format, n_keyframes, width, height,
+                                         image_pitch, image_stride, depth_pitch, depth_stride, cam, det=None,
+                                         d_rows_out=None, d_desc_out=None, d_xyz_out=None, d_kpts_out=None):
+        """add_keyframes_u8_batch_device for depth keyframes: the colour images feed the network and, as gray planes, the
+        depth stages.  Returns (first store slot, first local NN row)."""
+        first, row = C.c_int32(), C.c_int32()
+        self._check(self._L.sf_add_keyframes_depth_batch_device(
+            self._h, C.c_void_p(d_images), image_format, C.c_void_p(d_depth), depth_format, n_keyframes, width, height,
+            image_pitch, int(image_stride), depth_pitch, int(depth_stride), C.byref(cam),
+            C.byref(det) if det is not None else None, C.byref(first), C.byref(row), C.c_void_p(d_rows_out),
+            C.c_void_p(d_desc_out), C.c_void_p(d_xyz_out), C.c_void_p(d_kpts_out)))
+        return first.value, row.value
 
     def store_size(self):
         n = C.c_int32()
