@@ -1,6 +1,21 @@
 // sf_keyframes.hip -- images to keyframes of the store: sf_extract_keyframe_device, the full call on host images, the batch
 // pipeline of the four families of batch calls, the camera's own images and the calls that add keyframes with NetVLAD rows.
+// A stereo keyframe and a depth keyframe differ in their second input alone (SecondInput): every path here is written once
+// and branches on it -- get_features_host, features_batch, add_keyframes_batch -- and the public calls are argument adapters.
 #include "sf_host.hpp"
+
+// A keyframe's second input: the right image with the stereo stage that reads it (flow: its parameters), or a depth image --
+// under Vis/DepthAsMask with the detector's mask -- and no stereo stage.  Host or device pointers, as the call's left image.
+// `call`: the name that a depth call's refusals carry in front; the stereo calls carry none.  { right, flow } is a stereo
+// keyframe's, { nullptr, nullptr, &depth, call } a depth keyframe's
+struct SecondInput {
+  const uint8_t* right = nullptr;
+  const sf_stereo_flow_params* flow = nullptr;
+  const SfDepthIn* depth = nullptr;
+  const char* call = "";
+};
+
+static const char* colon(const char* call) { return *call ? ": " : ""; }   // "call: text", or "text" alone
 
 // a camera image (sf_image_format): a row holds 3 bytes per pixel for the colour formats
 static int check_format(sf_context* c, int format) {
@@ -11,13 +26,20 @@ static int check_format(sf_context* c, int format) {
 
 static long long image_row_bytes(int format, int width) { return (long long)width * (format == SF_IMAGE_MONO8 ? 1 : 3); }
 
-static int check_camera_image(sf_context* c, bool present, int format, int width, int height, int pitch, int min_side,
-                              const char* what) {
+static int check_camera_image(sf_context* c, const char* call, bool present, int format, int width, int height, int pitch,
+                              int min_side, const char* what) {
   int rc = check_format(c, format);
   if (rc != SF_OK) return rc;
   if (!present || width < min_side || height < min_side || pitch < image_row_bytes(format, width))
-    return sf_fail(c, SF_EINVAL, "%s missing or malformed (%d x %d, pitch %d, %d byte(s) per pixel)", what, width, height, pitch,
-                   format == SF_IMAGE_MONO8 ? 1 : 3);
+    return sf_fail(c, SF_EINVAL, "%s%s%s missing or malformed (%d x %d, pitch %d, %d byte(s) per pixel)", call, colon(call), what,
+                   width, height, pitch, format == SF_IMAGE_MONO8 ? 1 : 3);
+  return SF_OK;
+}
+
+static int check_max_features(sf_context* c, const char* call, int max_features) {
+  if (max_features <= 0 || max_features > SF_MAX_FEATURES)
+    return sf_fail(c, SF_ERANGE, "%s%smax_features %d outside 1 .. %d (KeyPointVec.size is an int16)", call, colon(call), max_features,
+                   SF_MAX_FEATURES);
   return SF_OK;
 }
 
@@ -63,8 +85,7 @@ extern "C" int sf_extract_keyframe_depth_device(sf_handle c, const uint8_t* d_le
   if (!c || !cam || n < 0) return SF_EINVAL;
   const int rc = sf_check_depth(c, "sf_extract_keyframe_depth_device", d_depth, depth_format, width, height, depth_pitch, 0, 1);
   if (rc != SF_OK) return rc;
-  SfDepthIn D;
-  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch;
+  const SfDepthIn D{d_depth, depth_format, depth_pitch};
   return extract_keyframe(c, d_left, width, height, pitch, d_kpts, nullptr, nullptr, n, cam, out_slot, out_rows, d_desc_out,
                           d_xyz_out, d_kpts_out, false, &D);
 }
@@ -155,103 +176,183 @@ static int family_detect(sf_context* c, const SfFeatureType& t, const BatchPlan&
   return SF_EINVAL;
 }
 
-// The GetFeatsAndDesc handler in one call on HOST buffers: upload the pair, detect, track, extract, download the
-// response.  Everything between the two copies stays on the device; the keyframe is in the store when it returns.
-// format < 0: rectified MONO8 planes (sf_get_features_and_descriptor); otherwise the camera's images in that
-// sf_image_format (sf_get_features_and_descriptor_u8), converted on the device behind the upload.
-static int get_features_host(sf_context* c, const uint8_t* left, const uint8_t* right, int format, int32_t width,
-                             int32_t height, int32_t pitch, const sf_stereo_camera* cam, const sf_detector_params* det,
-                             const sf_stereo_flow_params* flow, uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out,
-                             int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
+// ---- depth keyframes: SensorData(rgb, depth, model) in place of a stereo pair (kernels in k_depth.hip) --------------------
+// Vis/DepthAsMask is built for the two corner detectors: a type with a detector of its own takes no mask
+static int check_depth_as_mask(sf_context* c, const char* call) {
+  const SfFeatureType& t = sf_type_of(c);
+  if (c->depth.depth_as_mask && t.corners == CORNERS_OWN)
+    return sf_fail(c, SF_EINVAL, "%s: Vis/DepthAsMask under Vis/FeatureType %d (%s) is not built (its detector takes no mask); "
+                   "sf_depth_set_params with depth_as_mask = 0 runs it on the whole image", call, t.type, t.name);
+  return SF_OK;
+}
+
+// A host call's images on the device.  The left image, and the right image if there is one, as gray planes in c->ft_images:
+// rows `width` bytes apart, planes img_bytes apart.  format < 0 or mono8: the pitched copy is the upload; a colour format: the
+// images as they are (rows padded to 16 bytes: the conversion's wide path), then all planes in one launch.  Behind them the
+// depth image if there is one, in c->dp_depth: *d_depth describes the copy
+static int upload_inputs(sf_context* c, const uint8_t* left, const SecondInput& in, int format, int width, int height, int pitch,
+                         size_t img_bytes, SfDepthIn* d_depth) {
+  const uint8_t* const src[2] = {left, in.right};
+  const int count = in.right ? 2 : 1;
+  const int elem = in.depth && in.depth->format == SF_DEPTH_F32_M ? 4 : 2;
+  const int dz_pitch = (elem * width + 15) & ~15;          // rows padded to 16 bytes: k_depth_mask's wide loads
+  int rc = sf_buf_reserve(c, c->ft_images, count * img_bytes);
+  if (rc != SF_OK) return rc;
+  if (in.depth && (rc = sf_buf_reserve(c, c->dp_depth, (size_t)dz_pitch * height)) != SF_OK) return rc;
+  uint8_t* d_planes = (uint8_t*)c->ft_images.p;
+  if (format == SF_IMAGE_RGB8 || format == SF_IMAGE_BGR8) {
+    const int src_pitch = (3 * width + 15) & ~15;
+    const size_t src_bytes = ((size_t)src_pitch * height + 255) & ~(size_t)255;
+    if ((rc = sf_buf_reserve(c, c->img_src, count * src_bytes)) != SF_OK) return rc;
+    uint8_t* d_src = (uint8_t*)c->img_src.p;
+    for (int i = 0; i < count; ++i)
+      SF_HIP(c, hipMemcpy2DAsync(d_src + i * src_bytes, src_pitch, src[i], pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
+    if ((rc = sf_launch_image_gray(c, d_src, nullptr, count, format, c->gray_rule, width, height, src_pitch, src_bytes, count, d_planes,
+                                   width, img_bytes)) != SF_OK)
+      return rc;
+  } else {
+    for (int i = 0; i < count; ++i)
+      SF_HIP(c, hipMemcpy2DAsync(d_planes + i * img_bytes, width, src[i], pitch, width, height, hipMemcpyHostToDevice, c->stream));
+  }
+  if (!in.depth) return SF_OK;
+  *d_depth = SfDepthIn{c->dp_depth.p, in.depth->format, dz_pitch};
+  SF_HIP(c, hipMemcpy2DAsync(c->dp_depth.p, dz_pitch, in.depth->p, in.depth->pitch, (size_t)elem * width, height, hipMemcpyHostToDevice, c->stream));
+  return SF_OK;
+}
+
+// The detector on one device plane of pitch `width`, the count on the host: every cell of a grid in one launch sequence and
+// one wait for the keyframe's count; or the public detector call of the type's family on the ROI; or, under a mask (types
+// 3 .. 8: check_depth_as_mask), the masked call of the type's corner detector
+static int detect_single(sf_context* c, const FrontPlan& fp, const sf_detector_params& dp, const uint8_t* d_left, int width,
+                         const SfMask& mask, sf_keypoint* d_kpts, int32_t* n) {
+  const int maxf = fp.rows_cap;
+  int rc;
+  if (fp.grid()) {
+    if ((rc = sf_buf_reserve(c, c->ft_counts, 4)) != SF_OK) return rc;
+    if ((rc = sf_grid_detect(c, fp, dp, d_left, 0, 1, width, d_kpts, (int32_t*)c->ft_counts.p, mask)) != SF_OK) return rc;
+    return sf_word_to_host(c, c->ft_counts.p, n);
+  }
+  const SfFeatureType& t = sf_type_of(c);
+  const uint8_t* d_roi = d_left + (size_t)fp.y * width + fp.x;   // the detector's image: the ROI, at the parent's pitch
+  if (t.family == BATCH_GENERIC && mask.p) {
+    const uint8_t* d_mask_roi = sf_mask_at(mask, fp.x, fp.y).p;
+    return t.corners == CORNERS_FAST
+               ? sf_detect_fast_masked_device(c, d_roi, fp.w, fp.h, width, d_mask_roi, mask.pitch, maxf, nullptr, d_kpts, maxf, n)
+               : sf_detect_corners_masked_device(c, d_roi, fp.w, fp.h, width, d_mask_roi, mask.pitch, maxf, dp.quality_level,
+                                                 dp.min_distance, d_kpts, maxf, n);
+  }
+  switch (t.family) {
+    case BATCH_ORB: return sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, n);
+    case BATCH_SURF: return sf_detect_surf_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, n);   // (no ROI: sf_front_plan)
+    case BATCH_SIFT: return sf_detect_sift_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, n);   // (likewise)
+    case BATCH_GENERIC:
+      return t.corners == CORNERS_FAST ? sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, n)
+                                       : sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, n);
+  }
+  return SF_EINVAL;
+}
+
+// A host call's response in c->ft_wire: descriptors, 3D points, keypoints, maxf rows each
+struct Wire {
+  uint8_t* desc;
+  float* xyz;
+  sf_keypoint* kpts;
+};
+
+static int wire_reserve(sf_context* c, int maxf, int desc_bytes, Wire* w) {
+  const size_t row_bytes = (size_t)desc_bytes + 12 + sizeof(sf_keypoint);
+  const int rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64);
+  if (rc != SF_OK) return rc;
+  w->desc = (uint8_t*)c->ft_wire.p;
+  w->xyz = (float*)(w->desc + (((size_t)maxf * desc_bytes + 15) & ~(size_t)15));
+  w->kpts = (sf_keypoint*)(w->xyz + 3 * (size_t)maxf);
+  return SF_OK;
+}
+
+static int wire_download(sf_context* c, const Wire& w, int desc_bytes, int32_t k, uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out) {
+  if (k <= 0) return SF_OK;
+  if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, w.desc, (size_t)k * desc_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (xyz_out) SF_HIP(c, hipMemcpyAsync(xyz_out, w.xyz, (size_t)k * 12, hipMemcpyDeviceToHost, c->stream));
+  if (kpts_out) SF_HIP(c, hipMemcpyAsync(kpts_out, w.kpts, (size_t)k * sizeof(sf_keypoint), hipMemcpyDeviceToHost, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  return SF_OK;
+}
+
+// The GetFeatsAndDesc handler in one call on HOST buffers: upload the image and its second input, detect, refine, track (a
+// stereo pair) or mask the detector (a depth image, Vis/DepthAsMask), extract, download the response.  Everything between the
+// two copies stays on the device; the keyframe is in the store when it returns.  format < 0: rectified MONO8 planes
+// (sf_get_features_and_descriptor); otherwise the camera's images in that sf_image_format, converted on the device behind the
+// upload.  Everything an argument can be refused for is refused before the first reservation and the first upload.
+static int get_features_host(sf_context* c, const uint8_t* left, const SecondInput& in, int format, int32_t width, int32_t height,
+                             int32_t pitch, const sf_stereo_camera* cam, const sf_detector_params* det, uint8_t* desc_out,
+                             float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
   if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
   *rows_out = 0;
-  int rc = format < 0 ? sf_check_image(c, left && right, width, height, pitch, 3, "stereo pair")
-                      : check_camera_image(c, left && right, format, width, height, pitch, 3, "stereo pair");
+  const SfDepthIn* depth = in.depth;                      // (the host's depth image)
+  const bool present = left && (depth || in.right);
+  const char* what = depth ? "image" : "stereo pair";
+  int rc = format < 0 && !depth ? sf_check_image(c, present, width, height, pitch, 3, what)
+                                : check_camera_image(c, in.call, present, format, width, height, pitch, 3, what);
   if (rc != SF_OK) return rc;
+  if (depth) {
+    if ((rc = sf_check_depth(c, in.call, depth->p, depth->format, width, height, depth->pitch, 0, 1)) != SF_OK) return rc;
+    if ((rc = check_depth_as_mask(c, in.call)) != SF_OK) return rc;
+  }
   FrontPlan fp;
   if ((rc = sf_front_plan(c, width, height, &fp)) != SF_OK) return rc;
   const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
-  if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
-    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", dp.max_features, SF_MAX_FEATURES);
+  if ((rc = check_max_features(c, in.call, dp.max_features)) != SF_OK) return rc;
   if ((rc = sf_grid_plan(c, width, height, dp.max_features, &fp)) != SF_OK) return rc;
+  // (the GFTT parameters are checked under every feature type, FAST and ORB included, which do not use them)
+  if ((rc = sf_check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
+  if (fp.grid() && (rc = sf_check_pixels(c, fp.col_size, fp.row_size)) != SF_OK) return rc;
   SF_HIP(c, hipSetDevice(c->device));
   ExtractKind kind;
   if ((rc = sf_extract_kind(c, &kind)) != SF_OK) return rc;
   const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
   const int maxf = fp.rows_cap;                            // the rows of the call's buffers: max_features, or the grid's R C quota
-  if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
+  const bool masked = depth && c->depth.depth_as_mask;
+  Wire wire;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->ft_flow, (size_t)maxf * 16)) != SF_OK) return rc;
-  const size_t row_bytes = (size_t)kind.bytes + 12 + sizeof(sf_keypoint);
-  if ((rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64)) != SF_OK) return rc;
-  uint8_t* d_left = (uint8_t*)c->ft_images.p;
-  uint8_t* d_right = d_left + img_bytes;
-  if (format == SF_IMAGE_RGB8 || format == SF_IMAGE_BGR8) {
-    // the colour pair as it is (rows padded to 16 bytes: the conversion's wide path), then both planes in one launch
-    const int src_pitch = (3 * width + 15) & ~15;
-    const size_t src_bytes = ((size_t)src_pitch * height + 255) & ~(size_t)255;
-    if ((rc = sf_buf_reserve(c, c->img_src, 2 * src_bytes)) != SF_OK) return rc;
-    uint8_t* d_src = (uint8_t*)c->img_src.p;
-    SF_HIP(c, hipMemcpy2DAsync(d_src, src_pitch, left, pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
-    SF_HIP(c, hipMemcpy2DAsync(d_src + src_bytes, src_pitch, right, pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
-    if ((rc = sf_launch_image_gray(c, d_src, nullptr, 2, format, c->gray_rule, width, height, src_pitch, src_bytes, 2, d_left,
-                                   width, img_bytes)) != SF_OK)
+  if (!depth && (rc = sf_buf_reserve(c, c->ft_flow, (size_t)maxf * 16)) != SF_OK) return rc;
+  if (masked && (rc = sf_buf_reserve(c, c->dp_mask, img_bytes)) != SF_OK) return rc;
+  if ((rc = wire_reserve(c, maxf, kind.bytes, &wire)) != SF_OK) return rc;
+  SfDepthIn D;                                             // the device's copy of the depth image
+  if ((rc = upload_inputs(c, left, in, format, width, height, pitch, img_bytes, &D)) != SF_OK) return rc;
+  const uint8_t* d_left = (const uint8_t*)c->ft_images.p;
+  const uint8_t* d_right = d_left + img_bytes;
+  SfMask mask;                                             // the image's pitch: cropped and cut into cells like the image
+  if (masked) {
+    if ((rc = sf_launch_depth_mask(c, D, 1, width, height, cam->min_depth, cam->max_depth, (uint8_t*)c->dp_mask.p, width, 0)) != SF_OK)
       return rc;
-  } else {                                                 // MONO8 planes, or mono8 camera images: the pitched copy is the upload
-    SF_HIP(c, hipMemcpy2DAsync(d_left, width, left, pitch, width, height, hipMemcpyHostToDevice, c->stream));
-    SF_HIP(c, hipMemcpy2DAsync(d_right, width, right, pitch, width, height, hipMemcpyHostToDevice, c->stream));
+    mask.p = (const uint8_t*)c->dp_mask.p; mask.pitch = width;
   }
   sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
   int32_t n = 0;
-  // (the GFTT parameters are checked under every feature type, FAST and ORB included, which do not use them)
-  if ((rc = sf_check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
-  const uint8_t* d_roi = d_left + (size_t)fp.y * width + fp.x;   // the detector's image: the ROI, at the parent's pitch
-  if (fp.grid()) {                                       // every cell in one launch sequence, one wait for the keyframe's count
-    if ((rc = sf_check_pixels(c, fp.col_size, fp.row_size)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->ft_counts, 4)) != SF_OK) return rc;
-    if ((rc = sf_grid_detect(c, fp, dp, d_left, 0, 1, width, d_kpts, (int32_t*)c->ft_counts.p)) != SF_OK) return rc;
-    rc = sf_word_to_host(c, c->ft_counts.p, &n);
-  } else {                                               // the public detector call of the type's family, the count on the host
-    const SfFeatureType& t = sf_type_of(c);
-    switch (t.family) {
-      case BATCH_ORB: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
-      case BATCH_SURF: rc = sf_detect_surf_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;   // (no ROI: sf_front_plan)
-      case BATCH_SIFT: rc = sf_detect_sift_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;   // (likewise)
-      case BATCH_GENERIC:
-        rc = t.corners == CORNERS_FAST ? sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n)
-                                       : sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
-    }
-  }
-  if (rc != SF_OK) return rc;
+  if ((rc = detect_single(c, fp, dp, d_left, width, mask, d_kpts, &n)) != SF_OK) return rc;
   n = std::min(n, maxf);
   if (fp.launch() &&
       (rc = sf_launch_corner_subpix(c, d_left, 0, 1, width, height, width, d_kpts, n, nullptr, maxf, fp.off_x(), fp.off_y(),
                                     fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
     return rc;
-  float* d_xy = (float*)c->ft_flow.p;                    // [n][2], then x [n], then status [n]
-  float* d_rx = d_xy + 2 * (size_t)maxf;
-  uint8_t* d_status = (uint8_t*)(d_rx + maxf);
-  rc = c->stereo.optical_flow
-           ? sf_stereo_correspondences_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, d_xy, d_status, d_rx, nullptr)
-           : sf_stereo_block_match_device(c, d_left, d_right, width, height, width, d_kpts, n, flow, c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
-  if (rc != SF_OK) return rc;
-  uint8_t* d_desc = (uint8_t*)c->ft_wire.p;
-  float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
-  sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
+  float* d_rx = nullptr;
+  uint8_t* d_status = nullptr;
+  if (!depth) {
+    float* d_xy = (float*)c->ft_flow.p;                  // [n][2], then x [n], then status [n]
+    d_rx = d_xy + 2 * (size_t)maxf;
+    d_status = (uint8_t*)(d_rx + maxf);
+    rc = c->stereo.optical_flow
+             ? sf_stereo_correspondences_device(c, d_left, d_right, width, height, width, d_kpts, n, in.flow, d_xy, d_status, d_rx, nullptr)
+             : sf_stereo_block_match_device(c, d_left, d_right, width, height, width, d_kpts, n, in.flow, c->stereo.ssd, d_xy, d_status, d_rx, nullptr);
+    if (rc != SF_OK) return rc;
+  }
   int32_t slot = -1, rows = 0;
-  if ((rc = extract_keyframe(c, d_left, width, height, width, d_kpts, d_rx, d_status, n, cam, &slot, &rows, d_desc, d_xyz, d_kp_out,
-                             kind.has_sift)) != SF_OK)     // (SIFT: the detector's pyramid serves, the refinement moved x and y only)
-    return rc;
+  if ((rc = extract_keyframe(c, d_left, width, height, width, d_kpts, d_rx, d_status, n, cam, &slot, &rows, wire.desc, wire.xyz, wire.kpts,
+                             kind.has_sift, depth ? &D : nullptr)) != SF_OK)   // (SIFT: the detector's pyramid serves, the refinement
+    return rc;                                                                 // moved x and y only)
   *rows_out = rows;
   if (slot_out) *slot_out = slot;
-  const int32_t k = std::min(rows, cap_rows);
-  if (k > 0) {
-    if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, d_desc, (size_t)k * kind.bytes, hipMemcpyDeviceToHost, c->stream));
-    if (xyz_out) SF_HIP(c, hipMemcpyAsync(xyz_out, d_xyz, (size_t)k * 12, hipMemcpyDeviceToHost, c->stream));
-    if (kpts_out) SF_HIP(c, hipMemcpyAsync(kpts_out, d_kp_out, (size_t)k * sizeof(sf_keypoint), hipMemcpyDeviceToHost, c->stream));
-    SF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return SF_OK;
+  return wire_download(c, wire, kind.bytes, std::min(rows, cap_rows), desc_out, xyz_out, kpts_out);
 }
 
 extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, const uint8_t* right, int32_t width,
@@ -259,7 +360,7 @@ extern "C" int sf_get_features_and_descriptor(sf_handle c, const uint8_t* left, 
                                               const sf_detector_params* det, const sf_stereo_flow_params* flow,
                                               uint8_t* desc_out, float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows,
                                               int32_t* rows_out, int32_t* slot_out) {
-  return get_features_host(c, left, right, -1, width, height, pitch, cam, det, flow, desc_out, xyz_out, kpts_out, cap_rows,
+  return get_features_host(c, left, {right, flow}, -1, width, height, pitch, cam, det, desc_out, xyz_out, kpts_out, cap_rows,
                            rows_out, slot_out);
 }
 
@@ -271,133 +372,44 @@ extern "C" int sf_get_features_and_descriptor_u8(sf_handle c, const uint8_t* lef
   if (!c) return SF_EINVAL;
   const int rc = check_format(c, format);
   if (rc != SF_OK) return rc;
-  return get_features_host(c, left, right, format, width, height, pitch, cam, det, flow, desc_out, xyz_out, kpts_out, cap_rows,
+  return get_features_host(c, left, {right, flow}, format, width, height, pitch, cam, det, desc_out, xyz_out, kpts_out, cap_rows,
                            rows_out, slot_out);
 }
 
-// ---- depth keyframes: SensorData(rgb, depth, model) in place of a stereo pair (kernels in k_depth.hip) --------------------
-// Vis/DepthAsMask is built for the two corner detectors: a type with a detector of its own takes no mask
-static int check_depth_as_mask(sf_context* c, const char* call) {
-  const SfFeatureType& t = sf_type_of(c);
-  if (c->depth.depth_as_mask && t.corners == CORNERS_OWN)
-    return sf_fail(c, SF_EINVAL, "%s: Vis/DepthAsMask under Vis/FeatureType %d (%s) is not built (its detector takes no mask); "
-                   "sf_depth_set_params with depth_as_mask = 0 runs it on the whole image", call, t.type, t.name);
-  return SF_OK;
-}
-
-// The depth twin of get_features_host: upload image and depth, mask (Vis/DepthAsMask), detect under it, refine, extract with
-// the depth image's 3D points, download.  No right image, no stereo stage
+// (no right image, no stereo stage: the depth image gives the 3D points and, under Vis/DepthAsMask, the detector's mask)
 extern "C" int sf_get_features_and_descriptor_depth(sf_handle c, const uint8_t* image, int32_t image_format, const void* depth,
                                                     int32_t depth_format, int32_t width, int32_t height, int32_t image_pitch,
                                                     int32_t depth_pitch, const sf_stereo_camera* cam,
                                                     const sf_detector_params* det, uint8_t* desc_out, float* xyz_out,
                                                     sf_keypoint* kpts_out, int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
-  static const char* const call = "sf_get_features_and_descriptor_depth";
-  if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
-  *rows_out = 0;
-  int rc = check_camera_image(c, image, image_format, width, height, image_pitch, 3, "sf_get_features_and_descriptor_depth: image");
-  if (rc != SF_OK) return rc;
-  if ((rc = sf_check_depth(c, call, depth, depth_format, width, height, depth_pitch, 0, 1)) != SF_OK) return rc;
-  if ((rc = check_depth_as_mask(c, call)) != SF_OK) return rc;
-  FrontPlan fp;
-  if ((rc = sf_front_plan(c, width, height, &fp)) != SF_OK) return rc;
-  const sf_detector_params dp = arg_or_defaults(det, sf_detector_defaults);
-  if (dp.max_features <= 0 || dp.max_features > SF_MAX_FEATURES)
-    return sf_fail(c, SF_ERANGE, "%s: max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", call, dp.max_features, SF_MAX_FEATURES);
-  if ((rc = sf_grid_plan(c, width, height, dp.max_features, &fp)) != SF_OK) return rc;
-  if ((rc = sf_check_gftt(c, dp.quality_level, dp.min_distance)) != SF_OK) return rc;
-  if (fp.grid() && (rc = sf_check_pixels(c, fp.col_size, fp.row_size)) != SF_OK) return rc;
-  SF_HIP(c, hipSetDevice(c->device));
-  ExtractKind kind;
-  if ((rc = sf_extract_kind(c, &kind)) != SF_OK) return rc;
-  const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
-  const int maxf = fp.rows_cap;
-  const int elem = depth_format == SF_DEPTH_F32_M ? 4 : 2;
-  const int dz_pitch = (elem * width + 15) & ~15;          // rows padded to 16 bytes: k_depth_mask's wide loads
-  if ((rc = sf_buf_reserve(c, c->ft_images, 2 * img_bytes)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->dp_depth, (size_t)dz_pitch * height)) != SF_OK) return rc;
-  if (c->depth.depth_as_mask && (rc = sf_buf_reserve(c, c->dp_mask, img_bytes)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->ft_counts, 4)) != SF_OK) return rc;
-  const size_t row_bytes = (size_t)kind.bytes + 12 + sizeof(sf_keypoint);
-  if ((rc = sf_buf_reserve(c, c->ft_wire, (size_t)maxf * row_bytes + 64)) != SF_OK) return rc;
-  uint8_t* d_left = (uint8_t*)c->ft_images.p;
-  if (image_format == SF_IMAGE_MONO8) {
-    SF_HIP(c, hipMemcpy2DAsync(d_left, width, image, image_pitch, width, height, hipMemcpyHostToDevice, c->stream));
-  } else {                                                 // as sf_get_features_and_descriptor_u8 converts its pair
-    const int src_pitch = (3 * width + 15) & ~15;
-    const size_t src_bytes = ((size_t)src_pitch * height + 255) & ~(size_t)255;
-    if ((rc = sf_buf_reserve(c, c->img_src, src_bytes)) != SF_OK) return rc;
-    uint8_t* d_src = (uint8_t*)c->img_src.p;
-    SF_HIP(c, hipMemcpy2DAsync(d_src, src_pitch, image, image_pitch, 3 * (size_t)width, height, hipMemcpyHostToDevice, c->stream));
-    if ((rc = sf_launch_image_gray(c, d_src, nullptr, 1, image_format, c->gray_rule, width, height, src_pitch, src_bytes, 1, d_left,
-                                   width, img_bytes)) != SF_OK)
-      return rc;
-  }
-  SF_HIP(c, hipMemcpy2DAsync(c->dp_depth.p, dz_pitch, depth, depth_pitch, (size_t)elem * width, height, hipMemcpyHostToDevice, c->stream));
-  SfDepthIn D;
-  D.p = c->dp_depth.p; D.format = depth_format; D.pitch = dz_pitch;
-  SfMask mask;                                             // the image's pitch: cropped and cut into cells like the image
-  if (c->depth.depth_as_mask) {
-    if ((rc = sf_launch_depth_mask(c, D, 1, width, height, cam->min_depth, cam->max_depth, (uint8_t*)c->dp_mask.p, width, 0)) != SF_OK)
-      return rc;
-    mask.p = (const uint8_t*)c->dp_mask.p; mask.pitch = width;
-  }
-  sf_keypoint* d_kpts = (sf_keypoint*)c->ft_kpts.p;
-  int32_t n = 0;
-  const uint8_t* d_roi = d_left + (size_t)fp.y * width + fp.x;
-  const SfFeatureType& t = sf_type_of(c);
-  if (fp.grid()) {
-    if ((rc = sf_grid_detect(c, fp, dp, d_left, 0, 1, width, d_kpts, (int32_t*)c->ft_counts.p, mask)) != SF_OK) return rc;
-    rc = sf_word_to_host(c, c->ft_counts.p, &n);
-  } else if (t.family != BATCH_GENERIC || !mask.p) {       // no mask: the public detector call of the type's family
-    switch (t.family) {
-      case BATCH_ORB: rc = sf_detect_orb_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, nullptr, d_kpts, maxf, &n); break;
-      case BATCH_SURF: rc = sf_detect_surf_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
-      case BATCH_SIFT: rc = sf_detect_sift_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n); break;
-      case BATCH_GENERIC:
-        rc = t.corners == CORNERS_FAST ? sf_detect_fast_device(c, d_roi, fp.w, fp.h, width, maxf, nullptr, d_kpts, maxf, &n)
-                                       : sf_detect_corners_device(c, d_roi, fp.w, fp.h, width, maxf, dp.quality_level, dp.min_distance, d_kpts, maxf, &n);
-    }
-  } else {
-    const uint8_t* d_mask_roi = mask.p + (size_t)fp.y * width + fp.x;
-    rc = t.corners == CORNERS_FAST
-             ? sf_detect_fast_masked_device(c, d_roi, fp.w, fp.h, width, d_mask_roi, width, maxf, nullptr, d_kpts, maxf, &n)
-             : sf_detect_corners_masked_device(c, d_roi, fp.w, fp.h, width, d_mask_roi, width, maxf, dp.quality_level, dp.min_distance,
-                                               d_kpts, maxf, &n);
-  }
-  if (rc != SF_OK) return rc;
-  n = std::min(n, maxf);
-  if (fp.launch() &&
-      (rc = sf_launch_corner_subpix(c, d_left, 0, 1, width, height, width, d_kpts, n, nullptr, maxf, fp.off_x(), fp.off_y(),
-                                    fp.refine ? c->front.subpix_win_size : 0, c->front.subpix_iterations, c->front.subpix_eps)) != SF_OK)
-    return rc;
-  uint8_t* d_desc = (uint8_t*)c->ft_wire.p;
-  float* d_xyz = (float*)(d_desc + (((size_t)maxf * kind.bytes + 15) & ~(size_t)15));
-  sf_keypoint* d_kp_out = (sf_keypoint*)(d_xyz + 3 * (size_t)maxf);
-  int32_t slot = -1, rows = 0;
-  if ((rc = extract_keyframe(c, d_left, width, height, width, d_kpts, nullptr, nullptr, n, cam, &slot, &rows, d_desc, d_xyz, d_kp_out,
-                             kind.has_sift, &D)) != SF_OK)
-    return rc;
-  *rows_out = rows;
-  if (slot_out) *slot_out = slot;
-  const int32_t k = std::min(rows, cap_rows);
-  if (k > 0) {
-    if (desc_out) SF_HIP(c, hipMemcpyAsync(desc_out, d_desc, (size_t)k * kind.bytes, hipMemcpyDeviceToHost, c->stream));
-    if (xyz_out) SF_HIP(c, hipMemcpyAsync(xyz_out, d_xyz, (size_t)k * 12, hipMemcpyDeviceToHost, c->stream));
-    if (kpts_out) SF_HIP(c, hipMemcpyAsync(kpts_out, d_kp_out, (size_t)k * sizeof(sf_keypoint), hipMemcpyDeviceToHost, c->stream));
-    SF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return SF_OK;
+  const SfDepthIn D{depth, depth_format, depth_pitch};
+  return get_features_host(c, image, {nullptr, nullptr, &D, "sf_get_features_and_descriptor_depth"}, image_format, width, height,
+                           image_pitch, cam, det, desc_out, xyz_out, kpts_out, cap_rows, rows_out, slot_out);
+}
+
+// what a depth batch call refuses of its n depth images, behind the images' own checks (n = 0: of the format alone)
+static int depth_batch_check(sf_context* c, const char* call, const SfDepthIn& depth, int n, int width, int height) {
+  const int rc = n > 0 ? sf_check_depth(c, call, depth.p, depth.format, width, height, depth.pitch, depth.stride, n)
+                       : sf_check_depth(c, call, true, depth.format, 1, 1, 4, 0, 0);
+  return rc != SF_OK ? rc : check_depth_as_mask(c, call);
+}
+
+// the masks of the n depth images, with the planes' pitch and stride (family_detect crops and cuts them like the images)
+static int depth_batch_mask(sf_context* c, const SfDepthIn& D, int n, int width, int height, int pitch, size_t image_stride,
+                            const sf_stereo_camera* cam, SfMask* mask) {
+  if (!c->depth.depth_as_mask) return SF_OK;
+  mask->p = (const uint8_t*)c->dp_mask.p; mask->pitch = pitch; mask->stride = image_stride;
+  return sf_launch_depth_mask(c, D, n, width, height, cam->min_depth, cam->max_depth, (uint8_t*)c->dp_mask.p, pitch, image_stride);
 }
 
 // n keyframes from device images to n store slots in ONE launch sequence: detector, stereo correspondence and
 // extraction each run once over the batch (blockIdx = image), the corner counts stay in device memory between them, the
-// host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.  In three parts, shared by the eight batch
-// calls (`family`): batch_check refuses (nothing is touched; n_keyframes = 0 passes without a look at the images),
-// batch_reserve takes the store slots and the call's buffers, batch_launch queues the three stages, chunk by chunk.
-static int batch_check(sf_context* c, BatchFamily family, bool images, int n_keyframes, int width, int height, int pitch,
-                       size_t image_stride, const sf_detector_params* det, const sf_stereo_flow_params* flow, BatchPlan* plan) {
+// host never waits.  Same per-keyframe results as sf_get_features_and_descriptor.  In three parts, shared by the eight stereo
+// batch calls (`family`) and the two depth batch calls (`in`: depth images in place of the right images, under every family):
+// batch_check refuses (nothing is touched; n_keyframes = 0 passes without a look at the images), batch_reserve takes the
+// store slots and the call's buffers, batch_launch queues the three stages, chunk by chunk.
+static int batch_check(sf_context* c, BatchFamily family, const SecondInput& in, bool images, int n_keyframes, int width, int height,
+                       int pitch, size_t image_stride, const sf_detector_params* det, BatchPlan* plan) {
   const SfFeatureType& t = sf_type_of(c);
   if (t.family != family && t.other_call) return sf_fail(c, SF_EINVAL, "%s", t.other_call);   // a type with calls of its own
   if (t.family != family) {
@@ -405,20 +417,25 @@ static int batch_check(sf_context* c, BatchFamily family, bool images, int n_key
     return sf_fail(c, SF_EINVAL, "Vis/FeatureType %d: the %s batch calls need type %d (%s); use %s / %s", t.type, need.name, need.type,
                    need.setter, t.get_features_batch, t.add_keyframes_batch);
   }
+  int rc;
+  if (n_keyframes > 0) {
+    if (!images || width < 3 || height < 3 || pitch < width)
+      return sf_fail(c, SF_EINVAL, "%s%s%s missing or malformed (%d x %d, pitch %d)", in.call, colon(in.call),
+                     in.depth ? "images" : "stereo pairs", width, height, pitch);
+    if (image_stride < (size_t)pitch * height)
+      return sf_fail(c, SF_EINVAL, "%s%simage stride %zu is less than an image (%d rows of pitch %d)", in.call, colon(in.call),
+                     image_stride, height, pitch);
+  }
+  if (in.depth && (rc = depth_batch_check(c, in.call, *in.depth, n_keyframes, width, height)) != SF_OK) return rc;
   if (n_keyframes == 0) return SF_OK;
-  int rc = sf_check_image(c, images, width, height, pitch, 3, "stereo pairs");
-  if (rc != SF_OK) return rc;
-  if (image_stride < (size_t)pitch * height)
-    return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
   if ((rc = sf_front_plan(c, width, height, &plan->front)) != SF_OK) return rc;
   plan->dp = arg_or_defaults(det, sf_detector_defaults);
-  if (plan->dp.max_features <= 0 || plan->dp.max_features > SF_MAX_FEATURES)
-    return sf_fail(c, SF_ERANGE, "max_features %d outside 1 .. %d (KeyPointVec.size is an int16)", plan->dp.max_features, SF_MAX_FEATURES);
+  if ((rc = check_max_features(c, "", plan->dp.max_features)) != SF_OK) return rc;
   if ((rc = sf_check_gftt(c, plan->dp.quality_level, plan->dp.min_distance)) != SF_OK) return rc;
   if ((rc = sf_grid_plan(c, width, height, plan->dp.max_features, &plan->front)) != SF_OK) return rc;
   if (plan->front.grid() && (long long)n_keyframes * plan->front.rows * plan->front.cols > 65535)
     return sf_fail(c, SF_ERANGE, "%d keyframes of %d x %d cells: at most 65535 cells per call", n_keyframes, plan->front.rows, plan->front.cols);
-  plan->prm = arg_or_defaults(flow, sf_stereo_flow_defaults);
+  plan->prm = arg_or_defaults(in.flow, sf_stereo_flow_defaults);
   if (!c->stereo.optical_flow) {
     if ((rc = sf_check_block_match(c, plan->prm)) != SF_OK) return rc;
   } else if (!sf_stereo_flow_ok(plan->prm)) {
@@ -428,9 +445,10 @@ static int batch_check(sf_context* c, BatchFamily family, bool images, int n_key
   return family_check(c, family, n_keyframes, width, height);
 }
 
-static int batch_reserve(sf_context* c, int n, int width, int height, BatchPlan* plan) {
+static int batch_reserve(sf_context* c, const SecondInput& in, int n, int width, int height, size_t image_stride, BatchPlan* plan) {
   int rc;
   SF_HIP(c, hipSetDevice(c->device));
+  if (in.depth && c->depth.depth_as_mask && (rc = sf_buf_reserve(c, c->dp_mask, (size_t)n * image_stride)) != SF_OK) return rc;
   if ((rc = sf_extract_kind(c, &plan->kind)) != SF_OK) return rc;
   const int maxf = plan->front.rows_cap;                   // rows per keyframe: max_features, or the grid's R C quota
   const size_t rows_all = (size_t)maxf * n;
@@ -508,18 +526,20 @@ static int batch_launch(sf_context* c, const BatchPlan& plan, const uint8_t* d_l
   return SF_OK;
 }
 
-static int features_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const uint8_t* d_right, int32_t n_keyframes,
+static int features_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const SecondInput& in, int32_t n_keyframes,
                           int32_t width, int32_t height, int32_t pitch, size_t image_stride, const sf_stereo_camera* cam,
-                          const sf_detector_params* det, const sf_stereo_flow_params* flow, int32_t* first_slot_out,
-                          int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+                          const sf_detector_params* det, int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                          float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
   BatchPlan plan;
-  int rc = batch_check(c, family, d_left && d_right, n_keyframes, width, height, pitch, image_stride, det, flow, &plan);
+  int rc = batch_check(c, family, in, d_left && (in.depth || in.right), n_keyframes, width, height, pitch, image_stride, det, &plan);
   if (rc != SF_OK) return rc;
   if (n_keyframes == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
-  if ((rc = batch_reserve(c, n_keyframes, width, height, &plan)) != SF_OK) return rc;
-  return batch_launch(c, plan, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, first_slot_out, d_rows_out,
-                      d_desc_out, d_xyz_out, d_kpts_out);
+  if ((rc = batch_reserve(c, in, n_keyframes, width, height, image_stride, &plan)) != SF_OK) return rc;
+  SfMask mask;
+  if (in.depth && (rc = depth_batch_mask(c, *in.depth, n_keyframes, width, height, pitch, image_stride, cam, &mask)) != SF_OK) return rc;
+  return batch_launch(c, plan, d_left, in.right, n_keyframes, width, height, pitch, image_stride, cam, first_slot_out, d_rows_out,
+                      d_desc_out, d_xyz_out, d_kpts_out, in.depth, mask);
 }
 
 extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
@@ -528,7 +548,7 @@ extern "C" int sf_get_features_and_descriptor_batch_device(sf_handle c, const ui
                                                            const sf_detector_params* det, const sf_stereo_flow_params* flow,
                                                            int32_t* first_slot_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                            float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return features_batch(c, BATCH_GENERIC, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+  return features_batch(c, BATCH_GENERIC, d_left, {d_right, flow}, n_keyframes, width, height, pitch, image_stride, cam, det, first_slot_out,
                         d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
@@ -539,7 +559,7 @@ extern "C" int sf_get_features_and_descriptor_orb_batch_device(sf_handle c, cons
                                                                const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                                int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
                                                                sf_keypoint* d_kpts_out) {
-  return features_batch(c, BATCH_ORB, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+  return features_batch(c, BATCH_ORB, d_left, {d_right, flow}, n_keyframes, width, height, pitch, image_stride, cam, det, first_slot_out,
                         d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
@@ -550,7 +570,7 @@ extern "C" int sf_get_features_and_descriptor_surf_batch_device(sf_handle c, con
                                                                 const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                                 int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
                                                                 sf_keypoint* d_kpts_out) {
-  return features_batch(c, BATCH_SURF, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+  return features_batch(c, BATCH_SURF, d_left, {d_right, flow}, n_keyframes, width, height, pitch, image_stride, cam, det, first_slot_out,
                         d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
@@ -584,7 +604,7 @@ extern "C" int sf_get_features_and_descriptor_sift_batch_device(sf_handle c, con
                                                                 const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                                 int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out,
                                                                 sf_keypoint* d_kpts_out) {
-  return features_batch(c, BATCH_SIFT, d_left, d_right, n_keyframes, width, height, pitch, image_stride, cam, det, flow, first_slot_out,
+  return features_batch(c, BATCH_SIFT, d_left, {d_right, flow}, n_keyframes, width, height, pitch, image_stride, cam, det, first_slot_out,
                         d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
@@ -623,7 +643,7 @@ extern "C" int sf_image_to_gray_device(sf_handle c, const uint8_t* d_src, int32_
   int rc = check_format(c, format);
   if (rc != SF_OK) return rc;
   if (n_images == 0) return SF_OK;
-  if ((rc = check_camera_image(c, d_src, format, width, height, src_pitch, 1, "source images")) != SF_OK) return rc;
+  if ((rc = check_camera_image(c, "", d_src, format, width, height, src_pitch, 1, "source images")) != SF_OK) return rc;
   if ((rc = sf_check_image(c, d_dst, width, height, dst_pitch, 1, "gray planes")) != SF_OK) return rc;
   if ((rc = check_stride(c, n_images, src_stride, src_pitch, height, image_row_bytes(format, width), "source")) != SF_OK) return rc;
   if ((rc = check_stride(c, n_images, dst_stride, dst_pitch, height, width, "destination")) != SF_OK) return rc;
@@ -636,7 +656,7 @@ extern "C" int sf_netvlad_infer_u8_batch_device(sf_handle c, const uint8_t* d_im
                                                 int32_t width, int32_t height, int32_t pitch, size_t image_stride,
                                                 float* d_out, int32_t n_out) {
   if (!c || !d_out) return SF_EINVAL;
-  int rc = check_camera_image(c, d_images, format, width, height, pitch, 1, "images");
+  int rc = check_camera_image(c, "", d_images, format, width, height, pitch, 1, "images");
   if (rc != SF_OK) return rc;
   if ((rc = check_stride(c, n_images, image_stride, pitch, height, image_row_bytes(format, width), "image")) != SF_OK) return rc;
   SF_HIP(c, hipSetDevice(c->device));
@@ -663,54 +683,65 @@ extern "C" int sf_netvlad_infer_batch_device(sf_handle c, const float* d_images_
   return sf_netvlad_infer_batch_impl(c, d_images_rgb, n_images, height, width, d_out, n_out);
 }
 
+// what the calls that add NetVLAD rows need of the loaded model; *dims_out: the columns of a row
+static int check_netvlad_rows(sf_context* c, const char* call, int n, int width, int height, int* dims_out) {
+  const int dims = *dims_out = c->params.netvlad_dimensions, pca_dim = sf_netvlad_pca_dim(c);
+  if (pca_dim == 0) return sf_fail(c, SF_EINVAL, "%s%sno NetVLAD model loaded (sf_netvlad_load)", call, colon(call));
+  if (dims < 1 || dims > pca_dim)
+    return sf_fail(c, SF_EINVAL, "%s%snetvlad_dimensions %d is beyond the loaded model's %d WPCA outputs", call, colon(call), dims, pca_dim);
+  return sf_netvlad_check(c, n, height, width, dims);
+}
+
 // get_keyframes + compute_descriptors for n keyframes (data_handler.py:143-164, 212-295): gray planes of all 2 n stereo
-// images (one launch), the network on the colour images, the batch feature stages on the planes, the descriptors' prefix
-// into the local NN rows.  Everything that can refuse does so before the first launch; the store and the NN database
-// grow last, together.
-static int add_keyframes_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const uint8_t* d_right, const uint8_t* d_rgb,
+// images, or of the n images of depth keyframes (one launch), the network on the colour images, the batch feature stages on
+// the planes, the descriptors' prefix into the local NN rows.  Everything that can refuse does so before the first launch;
+// the store and the NN database grow last, together.
+static int add_keyframes_batch(sf_context* c, BatchFamily family, const uint8_t* d_left, const SecondInput& in, const uint8_t* d_rgb,
                                int32_t format, int32_t n_keyframes, int32_t width, int32_t height, int32_t pitch,
                                size_t image_stride, const sf_stereo_camera* cam, const sf_detector_params* det,
-                               const sf_stereo_flow_params* flow, int32_t* first_slot_out, int32_t* first_nn_row_out,
-                               int32_t* d_rows_out, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
+                               int32_t* first_slot_out, int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
+                               float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
-  const int n = n_keyframes;
+  const int n = n_keyframes, planes = in.depth ? n : 2 * n;
   int rc;
   if ((rc = check_format(c, format)) != SF_OK) return rc;
   if (n > 0) {
-    if ((rc = check_camera_image(c, d_left && d_right, format, width, height, pitch, 3, "stereo pairs")) != SF_OK) return rc;
+    if ((rc = check_camera_image(c, in.call, d_left && (in.depth || in.right), format, width, height, pitch, 3,
+                                 in.depth ? "images" : "stereo pairs")) != SF_OK)
+      return rc;
     if (image_stride < (size_t)pitch * height)
-      return sf_fail(c, SF_EINVAL, "image stride %zu is less than an image (%d rows of pitch %d)", image_stride, height, pitch);
+      return sf_fail(c, SF_EINVAL, "%s%simage stride %zu is less than an image (%d rows of pitch %d)", in.call, colon(in.call),
+                     image_stride, height, pitch);
   }
-  // the planes this call makes: rows padded to 16 bytes, n left then n right
+  // the planes this call makes: rows padded to 16 bytes, n left then, of stereo pairs, n right
   const int g_pitch = n > 0 ? (width + 15) & ~15 : 0;
   const size_t g_stride = ((size_t)g_pitch * (n > 0 ? height : 0) + 255) & ~(size_t)255;
   BatchPlan plan;
-  if ((rc = batch_check(c, family, true, n, width, height, g_pitch, g_stride, det, flow, &plan)) != SF_OK) return rc;
+  if ((rc = batch_check(c, family, in, true, n, width, height, g_pitch, g_stride, det, &plan)) != SF_OK) return rc;
   if (n == 0) {
     if (first_slot_out) *first_slot_out = c->store.slots;
     if (first_nn_row_out) *first_nn_row_out = c->nn_local.n;
     return SF_OK;
   }
-  const int dims = c->params.netvlad_dimensions, pca_dim = sf_netvlad_pca_dim(c);
-  if (pca_dim == 0) return sf_fail(c, SF_EINVAL, "no NetVLAD model loaded (sf_netvlad_load)");
-  if (dims < 1 || dims > pca_dim)
-    return sf_fail(c, SF_EINVAL, "netvlad_dimensions %d is beyond the loaded model's %d WPCA outputs", dims, pca_dim);
-  if ((rc = sf_netvlad_check(c, n, height, width, dims)) != SF_OK) return rc;
+  int dims;
+  if ((rc = check_netvlad_rows(c, in.call, n, width, height, &dims)) != SF_OK) return rc;
   if ((rc = sf_nn_reserve_rows(c, c->nn_local, n, dims)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->img_gray, 2 * (size_t)n * g_stride)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->img_gray, (size_t)planes * g_stride)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->img_desc, (size_t)n * dims * sizeof(float))) != SF_OK) return rc;
-  if ((rc = batch_reserve(c, n, width, height, &plan)) != SF_OK) return rc;
+  if ((rc = batch_reserve(c, in, n, width, height, g_stride, &plan)) != SF_OK) return rc;
   uint8_t* g_left = (uint8_t*)c->img_gray.p;
-  uint8_t* g_right = g_left + (size_t)n * g_stride;
-  if ((rc = sf_launch_image_gray(c, d_left, d_right, n, format, c->gray_rule, width, height, pitch, image_stride, 2 * n, g_left,
+  uint8_t* g_right = in.depth ? nullptr : g_left + (size_t)n * g_stride;
+  if ((rc = sf_launch_image_gray(c, d_left, in.right, n, format, c->gray_rule, width, height, pitch, image_stride, planes, g_left,
                                  g_pitch, g_stride)) != SF_OK)
     return rc;
   if ((rc = sf_netvlad_infer_u8_batch_impl(c, d_rgb ? d_rgb : d_left, format, n, height, width, pitch, image_stride,
                                            (float*)c->img_desc.p, dims)) != SF_OK)
     return rc;
+  SfMask mask;
+  if (in.depth && (rc = depth_batch_mask(c, *in.depth, n, width, height, g_pitch, g_stride, cam, &mask)) != SF_OK) return rc;
   int32_t slot = -1;
   if ((rc = batch_launch(c, plan, g_left, g_right, n, width, height, g_pitch, g_stride, cam, &slot, d_rows_out, d_desc_out,
-                         d_xyz_out, d_kpts_out)) != SF_OK)
+                         d_xyz_out, d_kpts_out, in.depth, mask)) != SF_OK)
     return rc;
   const int row = c->nn_local.n;
   if ((rc = sf_nn_append(c, c->nn_local, c->img_desc.p, n, dims, 1)) != SF_OK) {
@@ -729,8 +760,8 @@ extern "C" int sf_add_keyframes_u8_batch_device(sf_handle c, const uint8_t* d_le
                                                 const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                 int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                 float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return add_keyframes_batch(c, BATCH_GENERIC, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
-                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+  return add_keyframes_batch(c, BATCH_GENERIC, d_left, {d_right, flow}, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
 extern "C" int sf_add_keyframes_orb_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
@@ -740,8 +771,8 @@ extern "C" int sf_add_keyframes_orb_u8_batch_device(sf_handle c, const uint8_t* 
                                                     const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                     int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                     float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return add_keyframes_batch(c, BATCH_ORB, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
-                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+  return add_keyframes_batch(c, BATCH_ORB, d_left, {d_right, flow}, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
 extern "C" int sf_add_keyframes_surf_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
@@ -751,8 +782,8 @@ extern "C" int sf_add_keyframes_surf_u8_batch_device(sf_handle c, const uint8_t*
                                                      const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                      int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                      float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return add_keyframes_batch(c, BATCH_SURF, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
-                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+  return add_keyframes_batch(c, BATCH_SURF, d_left, {d_right, flow}, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
 extern "C" int sf_add_keyframes_sift_u8_batch_device(sf_handle c, const uint8_t* d_left, const uint8_t* d_right,
@@ -762,38 +793,13 @@ extern "C" int sf_add_keyframes_sift_u8_batch_device(sf_handle c, const uint8_t*
                                                      const sf_stereo_flow_params* flow, int32_t* first_slot_out,
                                                      int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                      float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  return add_keyframes_batch(c, BATCH_SIFT, d_left, d_right, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
-                             flow, first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
+  return add_keyframes_batch(c, BATCH_SIFT, d_left, {d_right, flow}, d_rgb, format, n_keyframes, width, height, pitch, image_stride, cam, det,
+                             first_slot_out, first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }
 
-// ---- the batch forms of the depth keyframes: one call for every family, the stages of sf_get_features_and_descriptor_depth in
-// one launch sequence -- masks of all n depth images, detector under them, refinement, extraction with depth points --------
-// what both refuse before anything is touched, and the plan (batch_check with the handle's own family and the flow defaults)
-static int depth_batch_check(sf_context* c, const char* call, bool images, const void* d_depth, int depth_format, int n, int width,
-                             int height, int pitch, size_t image_stride, int depth_pitch, size_t depth_stride,
-                             const sf_detector_params* det, BatchPlan* plan) {
-  int rc;
-  if (n > 0) {
-    if (!images || width < 3 || height < 3 || pitch < width)
-      return sf_fail(c, SF_EINVAL, "%s: images missing or malformed (%d x %d, pitch %d)", call, width, height, pitch);
-    if (image_stride < (size_t)pitch * height)
-      return sf_fail(c, SF_EINVAL, "%s: image stride %zu is less than an image (%d rows of pitch %d)", call, image_stride, height, pitch);
-    if ((rc = sf_check_depth(c, call, d_depth, depth_format, width, height, depth_pitch, depth_stride, n)) != SF_OK) return rc;
-  } else if ((rc = sf_check_depth(c, call, true, depth_format, 1, 1, 4, 0, 0)) != SF_OK) {
-    return rc;
-  }
-  if ((rc = check_depth_as_mask(c, call)) != SF_OK) return rc;
-  return batch_check(c, sf_type_of(c).family, images, n, width, height, pitch, image_stride, det, nullptr, plan);
-}
-
-// the masks of the n depth images, with the planes' pitch and stride (family_detect crops and cuts them like the images)
-static int depth_batch_mask(sf_context* c, const SfDepthIn& D, int n, int width, int height, int pitch, size_t image_stride,
-                            const sf_stereo_camera* cam, SfMask* mask) {
-  if (!c->depth.depth_as_mask) return SF_OK;
-  mask->p = (const uint8_t*)c->dp_mask.p; mask->pitch = pitch; mask->stride = image_stride;
-  return sf_launch_depth_mask(c, D, n, width, height, cam->min_depth, cam->max_depth, (uint8_t*)c->dp_mask.p, pitch, image_stride);
-}
-
+// ---- the batch forms of the depth keyframes: one call for every family (the handle's own), the stages of
+// sf_get_features_and_descriptor_depth in one launch sequence -- masks of all n depth images, detector under them, refinement,
+// extraction with depth points; the flow defaults stand in for the stereo stage's parameters --------------------------------
 extern "C" int sf_get_features_and_descriptor_depth_batch_device(sf_handle c, const uint8_t* d_images, const void* d_depth,
                                                                  int32_t depth_format, int32_t n_keyframes, int32_t width,
                                                                  int32_t height, int32_t image_pitch, size_t image_stride,
@@ -801,25 +807,13 @@ extern "C" int sf_get_features_and_descriptor_depth_batch_device(sf_handle c, co
                                                                  const sf_stereo_camera* cam, const sf_detector_params* det,
                                                                  int32_t* first_slot_out, int32_t* d_rows_out,
                                                                  uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
-  const int n = n_keyframes;
-  BatchPlan plan;
-  int rc = depth_batch_check(c, "sf_get_features_and_descriptor_depth_batch_device", d_images, d_depth, depth_format, n, width, height,
-                             image_pitch, image_stride, depth_pitch, depth_stride, det, &plan);
-  if (rc != SF_OK) return rc;
-  if (n == 0) { if (first_slot_out) *first_slot_out = c->store.slots; return SF_OK; }
-  if (c->depth.depth_as_mask && (rc = sf_buf_reserve(c, c->dp_mask, (size_t)n * image_stride)) != SF_OK) return rc;
-  if ((rc = batch_reserve(c, n, width, height, &plan)) != SF_OK) return rc;
-  SfDepthIn D;
-  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = depth_stride;
-  SfMask mask;
-  if ((rc = depth_batch_mask(c, D, n, width, height, image_pitch, image_stride, cam, &mask)) != SF_OK) return rc;
-  return batch_launch(c, plan, d_images, nullptr, n, width, height, image_pitch, image_stride, cam, first_slot_out, d_rows_out,
-                      d_desc_out, d_xyz_out, d_kpts_out, &D, mask);
+  if (!c) return SF_EINVAL;
+  const SfDepthIn D{d_depth, depth_format, depth_pitch, depth_stride};
+  return features_batch(c, sf_type_of(c).family, d_images, {nullptr, nullptr, &D, "sf_get_features_and_descriptor_depth_batch_device"},
+                        n_keyframes, width, height, image_pitch, image_stride, cam, det, first_slot_out, d_rows_out, d_desc_out,
+                        d_xyz_out, d_kpts_out);
 }
 
-// add_keyframes_batch with depth images in place of the right images: the gray planes of the n colour images, the network on
-// the colour images, the depth stages on the planes, the NN rows last
 extern "C" int sf_add_keyframes_depth_batch_device(sf_handle c, const uint8_t* d_images, int32_t image_format, const void* d_depth,
                                                    int32_t depth_format, int32_t n_keyframes, int32_t width, int32_t height,
                                                    int32_t image_pitch, size_t image_stride, int32_t depth_pitch,
@@ -827,59 +821,9 @@ extern "C" int sf_add_keyframes_depth_batch_device(sf_handle c, const uint8_t* d
                                                    const sf_detector_params* det, int32_t* first_slot_out,
                                                    int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                    float* d_xyz_out, sf_keypoint* d_kpts_out) {
-  static const char* const call = "sf_add_keyframes_depth_batch_device";
-  if (!c || !cam || n_keyframes < 0) return SF_EINVAL;
-  const int n = n_keyframes;
-  int rc;
-  if ((rc = check_format(c, image_format)) != SF_OK) return rc;
-  if (n > 0) {
-    if ((rc = check_camera_image(c, d_images, image_format, width, height, image_pitch, 3, "sf_add_keyframes_depth_batch_device: images")) != SF_OK)
-      return rc;
-    if (image_stride < (size_t)image_pitch * height)
-      return sf_fail(c, SF_EINVAL, "%s: image stride %zu is less than an image (%d rows of pitch %d)", call, image_stride, height, image_pitch);
-  }
-  const int g_pitch = n > 0 ? (width + 15) & ~15 : 0;      // the planes this call makes: rows padded to 16 bytes
-  const size_t g_stride = ((size_t)g_pitch * (n > 0 ? height : 0) + 255) & ~(size_t)255;
-  BatchPlan plan;
-  if ((rc = depth_batch_check(c, call, true, d_depth, depth_format, n, width, height, g_pitch, g_stride, depth_pitch, depth_stride, det,
-                              &plan)) != SF_OK)
-    return rc;
-  if (n == 0) {
-    if (first_slot_out) *first_slot_out = c->store.slots;
-    if (first_nn_row_out) *first_nn_row_out = c->nn_local.n;
-    return SF_OK;
-  }
-  const int dims = c->params.netvlad_dimensions, pca_dim = sf_netvlad_pca_dim(c);
-  if (pca_dim == 0) return sf_fail(c, SF_EINVAL, "%s: no NetVLAD model loaded (sf_netvlad_load)", call);
-  if (dims < 1 || dims > pca_dim)
-    return sf_fail(c, SF_EINVAL, "%s: netvlad_dimensions %d is beyond the loaded model's %d WPCA outputs", call, dims, pca_dim);
-  if ((rc = sf_netvlad_check(c, n, height, width, dims)) != SF_OK) return rc;
-  if ((rc = sf_nn_reserve_rows(c, c->nn_local, n, dims)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->img_gray, (size_t)n * g_stride)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->img_desc, (size_t)n * dims * sizeof(float))) != SF_OK) return rc;
-  if (c->depth.depth_as_mask && (rc = sf_buf_reserve(c, c->dp_mask, (size_t)n * g_stride)) != SF_OK) return rc;
-  if ((rc = batch_reserve(c, n, width, height, &plan)) != SF_OK) return rc;
-  uint8_t* g_images = (uint8_t*)c->img_gray.p;
-  if ((rc = sf_launch_image_gray(c, d_images, nullptr, n, image_format, c->gray_rule, width, height, image_pitch, image_stride, n,
-                                 g_images, g_pitch, g_stride)) != SF_OK)
-    return rc;
-  if ((rc = sf_netvlad_infer_u8_batch_impl(c, d_images, image_format, n, height, width, image_pitch, image_stride,
-                                           (float*)c->img_desc.p, dims)) != SF_OK)
-    return rc;
-  SfDepthIn D;
-  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = depth_stride;
-  SfMask mask;
-  if ((rc = depth_batch_mask(c, D, n, width, height, g_pitch, g_stride, cam, &mask)) != SF_OK) return rc;
-  int32_t slot = -1;
-  if ((rc = batch_launch(c, plan, g_images, nullptr, n, width, height, g_pitch, g_stride, cam, &slot, d_rows_out, d_desc_out,
-                         d_xyz_out, d_kpts_out, &D, mask)) != SF_OK)
-    return rc;
-  const int row = c->nn_local.n;
-  if ((rc = sf_nn_append(c, c->nn_local, c->img_desc.p, n, dims, 1)) != SF_OK) {
-    c->store.slots -= n;             // (the slots' rows stay behind the end of the store: the keyframes were never added)
-    return rc;
-  }
-  if (first_slot_out) *first_slot_out = slot;
-  if (first_nn_row_out) *first_nn_row_out = row;
-  return SF_OK;
+  if (!c) return SF_EINVAL;
+  const SfDepthIn D{d_depth, depth_format, depth_pitch, depth_stride};
+  return add_keyframes_batch(c, sf_type_of(c).family, d_images, {nullptr, nullptr, &D, "sf_add_keyframes_depth_batch_device"}, nullptr,
+                             image_format, n_keyframes, width, height, image_pitch, image_stride, cam, det, first_slot_out,
+                             first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);
 }

@@ -751,19 +751,10 @@ class SeparatorFinder:
         if pitch != pitch2:
             left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
             pitch = left.strides[0]
-        cap = self._rows_cap(w, h, det.max_features if det is not None else 1000)
-        nbytes = self.descriptor_bytes()
-        desc = np.zeros((cap, nbytes), np.uint8)
-        xyz = np.zeros((cap, 3), np.float32)
-        kp = np.zeros(cap, _abi.KEYPOINT_DTYPE)
-        rows, slot = C.c_int32(), C.c_int32()
-        self._check(self._L.sf_get_features_and_descriptor_u8(
-            self._h, C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data), int(fmt), w, h, pitch, C.byref(cam),
-            C.byref(det) if det is not None else None, C.byref(flow) if flow is not None else None,
-            C.c_void_p(desc.ctypes.data), C.c_void_p(xyz.ctypes.data), C.c_void_p(kp.ctypes.data), cap, C.byref(rows),
-            C.byref(slot)))
-        n = min(rows.value, cap)
-        return desc[:n].copy(), xyz[:n].copy(), kp[:n].copy(), slot.value
+        return self._host_keyframe(
+            self._L.sf_get_features_and_descriptor_u8,
+            (C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data), int(fmt), w, h, pitch), w, h, cam, det,
+            C.byref(flow) if flow is not None else None)
 
     def add_keyframes_u8_batch_device(self, d_left, d_right, d_rgb, fmt, n_keyframes, width, height, pitch, image_stride,
                                       cam, det=None, flow=None, d_rows_out=None, d_desc_out=None, d_xyz_out=None,
@@ -938,6 +929,20 @@ class SeparatorFinder:
         except (ValueError, OverflowError):
             return max_features
 
+    def _host_keyframe(self, fn, images, w, h, cam, det, *flow):
+        """The three host keyframe calls behind their images: the outputs for the rows a keyframe can hold, the call
+        fn(handle, *images, cam, det, *flow, outputs...), the rows it kept."""
+        cap = self._rows_cap(w, h, det.max_features if det is not None else 1000)
+        desc = np.zeros((cap, self.descriptor_bytes()), np.uint8)
+        xyz = np.zeros((cap, 3), np.float32)
+        kp = np.zeros(cap, _abi.KEYPOINT_DTYPE)
+        rows, slot = C.c_int32(), C.c_int32()
+        self._check(fn(self._h, *images, C.byref(cam), C.byref(det) if det is not None else None, *flow,
+                       C.c_void_p(desc.ctypes.data), C.c_void_p(xyz.ctypes.data), C.c_void_p(kp.ctypes.data), cap,
+                       C.byref(rows), C.byref(slot)))
+        n = min(rows.value, cap)
+        return desc[:n].copy(), xyz[:n].copy(), kp[:n].copy(), slot.value
+
     def get_features_and_descriptor(self, left, right, cam, det=None, flow=None):
         """GetFeatsAndDesc on host images (uint8 [h, w], same row stride): returns (descriptors [rows, bytes] uint8,
         kpts3D [rows, 3] float32, kpts [rows] KEYPOINT_DTYPE, slot of the keyframe in the device-resident store)."""
@@ -945,19 +950,10 @@ class SeparatorFinder:
         if left.ndim != 2 or left.shape != right.shape or left.strides != right.strides or left.strides[1] != 1:
             raise ValueError("left / right must be 2-D uint8 images of one shape and row stride")
         h, w = left.shape
-        cap = self._rows_cap(w, h, det.max_features if det is not None else 1000)
-        nbytes = self.descriptor_bytes()
-        desc = np.zeros((cap, nbytes), np.uint8)
-        xyz = np.zeros((cap, 3), np.float32)
-        kp = np.zeros(cap, _abi.KEYPOINT_DTYPE)
-        rows, slot = C.c_int32(), C.c_int32()
-        self._check(self._L.sf_get_features_and_descriptor(
-            self._h, C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data), w, h, left.strides[0], C.byref(cam),
-            C.byref(det) if det is not None else None, C.byref(flow) if flow is not None else None,
-            C.c_void_p(desc.ctypes.data), C.c_void_p(xyz.ctypes.data), C.c_void_p(kp.ctypes.data), cap, C.byref(rows),
-            C.byref(slot)))
-        n = min(rows.value, cap)
-        return desc[:n].copy(), xyz[:n].copy(), kp[:n].copy(), slot.value
+        return self._host_keyframe(
+            self._L.sf_get_features_and_descriptor,
+            (C.c_void_p(left.ctypes.data), C.c_void_p(right.ctypes.data), w, h, left.strides[0]), w, h, cam, det,
+            C.byref(flow) if flow is not None else None)
 
     def get_features_and_descriptor_batch_device(self, d_left, d_right, n_keyframes, width, height, pitch, image_stride,
                                                  cam, det=None, flow=None, d_rows_out=None, d_desc_out=None,
@@ -1095,17 +1091,10 @@ class SeparatorFinder:
         fmt = _abi.depth_format_of(depth)
         if depth.shape != (h, w) or depth.strides[1] != depth.itemsize:
             raise ValueError("depth must be a 2-D array of the image's height and width with contiguous rows")
-        cap = self._rows_cap(w, h, det.max_features if det is not None else 1000)
-        desc = np.zeros((cap, self.descriptor_bytes()), np.uint8)
-        xyz = np.zeros((cap, 3), np.float32)
-        kp = np.zeros(cap, _abi.KEYPOINT_DTYPE)
-        rows, slot = C.c_int32(), C.c_int32()
-        self._check(self._L.sf_get_features_and_descriptor_depth(
-            self._h, C.c_void_p(image.ctypes.data), image_format, C.c_void_p(depth.ctypes.data), fmt, w, h, image_pitch,
-            depth.strides[0], C.byref(cam), C.byref(det) if det is not None else None, C.c_void_p(desc.ctypes.data),
-            C.c_void_p(xyz.ctypes.data), C.c_void_p(kp.ctypes.data), cap, C.byref(rows), C.byref(slot)))
-        n = min(rows.value, cap)
-        return desc[:n].copy(), xyz[:n].copy(), kp[:n].copy(), slot.value
+        return self._host_keyframe(
+            self._L.sf_get_features_and_descriptor_depth,
+            (C.c_void_p(image.ctypes.data), image_format, C.c_void_p(depth.ctypes.data), fmt, w, h, image_pitch,
+             depth.strides[0]), w, h, cam, det)
 
     def get_features_and_descriptor_depth_batch_device(self, d_images, d_depth, depth_format, n_keyframes, width, height,
                                                        image_pitch, image_stride, depth_pitch, depth_stride, cam, det=None,

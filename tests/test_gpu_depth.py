@@ -429,6 +429,52 @@ def test_without_mask_and_limits_rows_and_keypoints_are_the_stereo_calls(ftype):
         fb.close()
 
 
+def colour(gray):
+    """A camera image whose gray plane is not the input's: red and green carry it, blue its negative."""
+    return np.stack([gray, gray, 255 - gray], axis=2)
+
+
+@pytest.mark.parametrize("ftype,grid", [(6, (2, 2)), (4, (1, 1))])
+def test_interleaved_stereo_and_depth_calls_on_one_handle_equal_fresh_handles(ftype, grid):
+    """The stereo and the depth host calls are one path: they share the handle's image planes, colour source, counts and
+    response buffer.  Four calls in turn on one handle, each the bytes of the same call on a fresh handle."""
+    img, d16 = frame(60 + ftype, U16)
+    d32 = frame(60 + ftype, F32M)[1]
+    right = np.ascontiguousarray(np.roll(img, -3, axis=1))
+    cam = ref.camera(W, H, min_depth=LIMITS[0], max_depth=LIMITS[1])
+    stereo_cam = _abi.stereo_camera(cam.fx, cam.fy, cam.cx, cam.cy, 0.1)
+    det = _abi.detector_params(200)
+    calls = [
+        lambda f: f.get_features_and_descriptor_u8(colour(img), colour(right), _abi.SF_IMAGE_RGB8, stereo_cam, det),
+        lambda f: f.get_features_and_descriptor_depth(img, d16, cam, det, _abi.SF_IMAGE_MONO8),
+        lambda f: f.get_features_and_descriptor(img, right, stereo_cam, det),
+        lambda f: f.get_features_and_descriptor_depth(colour(img), d32, cam, det, _abi.SF_IMAGE_RGB8),
+    ]
+
+    def fresh():
+        f = finder_of(ftype)
+        f.grid_set_params(_abi.grid_params(*grid))
+        assert f.depth_get_params().depth_as_mask == 1
+        return f
+
+    fa = fresh()
+    try:
+        for i, call in enumerate(calls):
+            got = call(fa)
+            fb = fresh()
+            try:
+                want = call(fb)
+            finally:
+                fb.close()
+            print("type %d, grid %d x %d, call %d: %d rows" % (ftype, grid[0], grid[1], i, len(want[0])))
+            assert len(want[0]) >= 5
+            assert_same_keyframe(got, want)
+            assert got[3] == i and want[3] == 0
+        assert fa.store_size() == len(calls)
+    finally:
+        fa.close()
+
+
 # ---- the batch forms -----------------------------------------------------------------------------------------------------
 def pack_planes(torch, planes, pitch, stride):
     """n 2-D arrays of one shape and dtype as one device buffer: rows `pitch` bytes, planes `stride` bytes apart."""

@@ -187,6 +187,48 @@ def test_host_handler_with_type_4(finder, threshold, limit):
     assert_same((d2, p2, k2), (d, p, k))
 
 
+@pytest.mark.parametrize("grid", [(1, 1), (3, 3)])
+def test_host_call_refuses_gftt_parameters_before_it_touches_anything(grid):
+    """quality_level / min_distance are refused in front of the first reservation and upload of the stereo host calls: the
+    handle is as it was, and the next valid call gives the bytes of a fresh handle's."""
+    import torch
+    from tests import depth_ref
+    from tests.test_gpu_depth import F32M, H, W, assert_same_keyframe, colour, frame
+    left = frame(64, F32M)[0]
+    right = np.ascontiguousarray(np.roll(left, -3, axis=1))
+    pinhole = depth_ref.camera(W, H)
+    cam = _abi.stereo_camera(pinhole.fx, pinhole.fy, pinhole.cx, pinhole.cy, 0.1)
+    limit = 200
+
+    def fresh():
+        p = synth.camera_params()
+        p.max_features = 2048
+        f = lib.SeparatorFinder(p, device=0)
+        f.set_stream(torch.cuda.current_stream().cuda_stream)
+        f.set_feature_type(_abi.FEATURE_FAST_BRIEF)
+        f.grid_set_params(_abi.grid_params(*grid))
+        return f
+
+    def call(f, det):
+        return f.get_features_and_descriptor_u8(colour(left), colour(right), _abi.SF_IMAGE_RGB8, cam, det)
+
+    fa, fb = fresh(), fresh()
+    try:
+        before = fa.store_size(), fa.nn_sizes()
+        for bad in (_abi.detector_params(limit, 0.0, 3.0), _abi.detector_params(limit, 0.001, -1.0)):
+            with pytest.raises(lib.SepfinderError) as e:
+                call(fa, bad)
+            assert e.value.code == _abi.SF_EINVAL and "qualityLevel" in str(e.value)
+            assert (fa.store_size(), fa.nn_sizes()) == before
+        got, want = call(fa, _abi.detector_params(limit)), call(fb, _abi.detector_params(limit))
+        print("type 4, grid %d x %d: %d rows" % (grid[0], grid[1], len(want[0])))
+        assert len(want[0]) >= 5 and got[3] == want[3] == 0
+        assert_same_keyframe(got, want)
+    finally:
+        fa.close()
+        fb.close()
+
+
 def _batch(finder, torch, pairs, cam, det):
     dev = torch.device("cuda:0")
     h, w = pairs[0][0].shape
