@@ -18,6 +18,7 @@
 // Compiled with -ffp-contract=off (canonical arithmetic).
 #include "sf_device_math.hpp"
 #include "sf_internal.hpp"
+#include "sf_match_device.hpp"
 
 namespace {
 
@@ -101,36 +102,6 @@ __device__ __forceinline__ bool guided_project(const DeviceParams& P, const floa
   return isfinite(u) && isfinite(v) && !(u < 0.f) && !(u >= P.wlim) && !(v < 0.f) && !(v >= P.hlim) && (zf > 0.f);
 }
 
-// The id-ordered compaction of the matches (wavefront ballots): out[k] = from | to << 16 for every "from" index i in
-// ascending order whose to_of(i) >= 0; returns the list's length.  Ends with a barrier.
-template <int NW, class ToOf>
-__device__ __forceinline__ int guided_compact(int Kf, uint32_t* out, int* misc, ToOf to_of) {
-  constexpr int NT = 64 * NW;
-  const int tid = (int)threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  int running = 0;
-  for (int base = 0; base < Kf; base += NT) {
-    const int i = base + tid;
-    const int m = (i < Kf) ? to_of(i) : -1;
-    const bool flag = m >= 0;
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) misc[4 + wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      int c = misc[4 + w];
-      if (w < wave) woff += c;
-      total += c;
-    }
-    if (flag) out[running + woff + before] = (uint32_t)i | ((uint32_t)m << 16);
-    running += total;
-    __syncthreads();
-  }
-  return running;
-}
-
 // Workgroup sums of the per-thread counts of finite "from" points and of projections in the image (misc[0], misc[1]:
 // 0 on entry).  Ends with a barrier.
 // LANES = false: the __shfl_xor loops, for k_guided_tp (its W = 16 instantiation sits at 64 registers, eight wavefronts per
@@ -202,19 +173,8 @@ __device__ __forceinline__ bool guided_finish(const StoreView& st, int pair, int
     h.words_to_2d = words_to_2d;
     hdr_out = h;
     guided_flag_out = 1;
-    PassState ps;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-    ps.var = 1.0; ps.var_ang = 1.0;
-    ps.is_null = 1;
-    ps.inliers = 0;
-    ps.matches = (motion && !survivor) ? misc[2] : 0;
-    ps.pad = 0;
-    pass2_out = ps;
-    if (survivor && list) {
-      int pos = atomicAdd(counter, 1);
-      list[pos] = pair;
-    }
+    write_null_pass(pass2_out, (motion && !survivor) ? misc[2] : 0);
+    if (survivor && list) worklist_append(list, counter, pair);
   }
   return survivor;
 }
@@ -710,7 +670,7 @@ __device__ __forceinline__ bool guided_body(const StoreView& st, int pair, int s
   guided_sum_counts(n_finite, n_proj, misc);
   SF_TRACE_MARK(P, pair, 9);
   // id-ordered compaction
-  const int n_corr = guided_compact<NW>(Kf, out, misc, [&](int i) { const int m = matched[i]; return (m >= 0 && claim[m] == i) ? m : -1; });
+  const int n_corr = corr_compact<NW>(Kf, out, misc, [&](int i) { const int m = matched[i]; return (m >= 0 && claim[m] == i) ? m : -1; });
   const bool survivor = guided_finish<NW>(st, pair, sT, mT, Kt, xF, n_finite, n_proj, n_corr, out, pass2_out, guided_flag_out,
                                           hdr_out, list, counter, P, misc);
   SF_TRACE_MARK(P, pair, 10);
@@ -919,7 +879,7 @@ __device__ __forceinline__ bool guided_tp_body(const StoreView& st, int pair, in
     if (m >= 0 && atomicCAS(&claimw[m], EMPTY, (uint32_t)t) != EMPTY) atomicOr(&claimw[m], SHARED);   // :604-625
   }
   guided_sum_counts<false>(n_finite, n_proj, misc);    // (its barrier also orders the claims before the compaction)
-  const int n_corr = guided_compact<NW>(Kf, out, misc, [&](int i) {
+  const int n_corr = corr_compact<NW>(Kf, out, misc, [&](int i) {
     const uint32_t w = claimw[i];
     return (w & SHARED) ? -1 : (int)w;          // (EMPTY has bit 31 set too)
   });

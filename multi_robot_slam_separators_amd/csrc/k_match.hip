@@ -20,6 +20,7 @@
 // The kernel is VALU-bound (~19 lane-ops per descriptor pair); HBM traffic is the two descriptor
 // blocks, read once (the "to" block coalesced 16 B/lane, the "from" block via the scalar cache).
 #include "sf_internal.hpp"
+#include "sf_match_device.hpp"
 #include <type_traits>
 
 namespace {
@@ -148,36 +149,15 @@ k_match_global(StoreView st, const int32_t* __restrict__ pair_from, const int32_
                float nndr, int min_inliers, int est, uint32_t* __restrict__ corr, CorrHeader* __restrict__ hdr,
                PassState* __restrict__ pass, int32_t* __restrict__ list, int32_t* __restrict__ counter) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
-  constexpr int NW = NT / 64;
   const int pair = blockIdx.x;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
   const int kcap = st.kcap;
-  const int sF = pair_from[pair], sT = pair_to[pair];
-  if ((unsigned)sF >= (unsigned)st.n_slots || (unsigned)sT >= (unsigned)st.n_slots) {
-    // caller-provided slot outside the store: report a failed estimation, touch nothing else
-    if (tid == 0) {
-      CorrHeader h = {0, 0, 0, 0};
-      hdr[pair] = h;
-      PassState ps;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-      ps.var = 1.0; ps.var_ang = 1.0; ps.is_null = 1; ps.inliers = 0; ps.matches = 0; ps.pad = 0;
-      pass[pair] = ps;
-    }
-    return;
-  }
-  const int4 mF = st.meta[sF], mT = st.meta[sT];
-  const int Kf = mF.x, Kt = mT.x;
-  const uint32_t* dF = st.desc + (size_t)sF * kcap * W;
-  const uint32_t* dT = st.desc + (size_t)sT * kcap * W;
-
-  int* cnt = smem;               // [kcap] "to" rows that matched each "from" word
-  int* owner = smem + kcap;      // [kcap] the matching "to" row (meaningful when cnt == 1)
-  int* misc = smem + 2 * kcap;   // [16]   0: rejected "to" rows, 2: finite corr, 4..7 wave totals
-
-  for (int i = tid; i < Kf; i += NT) cnt[i] = 0;
-  if (tid < 16) misc[tid] = 0;
+  MatchPair M;
+  if (match_slot_outside(st, pair_from[pair], pair_to[pair])) { match_report_outside(hdr[pair], pass[pair]); return; }
+  match_begin<NT>(st, pair_from[pair], pair_to[pair], smem, M);
+  const int Kf = M.mF.x, Kt = M.mT.x;
+  const uint32_t* dF = st.desc + (size_t)M.sF * kcap * W;
+  const uint32_t* dT = st.desc + (size_t)M.sT * kcap * W;
   __syncthreads();
 
   int rejected = 0;
@@ -199,12 +179,8 @@ k_match_global(StoreView st, const int32_t* __restrict__ pair_from, const int32_
         }
         if (t < Kt) {
           const bool acc = (Kf >= 2) && i1 >= 0 && !(d1 > nndr * d2);
-          if (acc) {
-            atomicAdd(&cnt[i1], 1);
-            owner[i1] = t;
-          } else {
-            ++rejected;
-          }
+          if (acc) match_claim(M.cnt, M.owner, i1, t);
+          else ++rejected;
         }
       }
     }
@@ -243,95 +219,13 @@ k_match_global(StoreView st, const int32_t* __restrict__ pair_from, const int32_
         const int t = base + j * NT + tid;
         if (t < Kt) {
           const bool acc = (Kf >= 2) && !((float)(k1[j] >> 16) > nndr * (float)(k2[j] >> 16));
-          if (acc) {
-            const int f = (int)(k1[j] & 0xFFFFu);
-            atomicAdd(&cnt[f], 1);
-            owner[f] = t;
-          } else {
-            ++rejected;
-          }
+          if (acc) match_claim(M.cnt, M.owner, (int)(k1[j] & 0xFFFFu), t);
+          else ++rejected;
         }
       }
     }
   }
-  // wave-reduce the rejected count, one LDS atomic per wave
-  for (int off = 32; off >= 1; off >>= 1) rejected += __shfl_xor(rejected, off);
-  if (lane == 0 && rejected) atomicAdd(&misc[0], rejected);
-  __syncthreads();
-
-  // id-ordered compaction of the "from" words matched by exactly one "to" row
-  uint32_t* out = corr + (size_t)pair * kcap;
-  int running = 0;
-  for (int base = 0; base < Kf; base += NT) {
-    const int f = base + tid;
-    const bool flag = (f < Kf) && (cnt[f] == 1);
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) misc[4 + wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      int c = misc[4 + w];
-      if (w < wave) woff += c;
-      total += c;
-    }
-    if (flag) out[running + woff + before] = (uint32_t)f | ((uint32_t)owner[f] << 16);
-    running += total;
-    __syncthreads();
-  }
-  const int n_corr = running;
-
-  // Gate of the 3D->3D estimation (myRegistrationVis.cpp:928,1117-1118) and, when RANSAC will not
-  // run, the `matches` count util3d::findCorrespondences would still report.
-  const int unique_to = (Kf > 0 && Kt > 0) ? misc[0] + n_corr : 0;
-  const int words_from = (Kf > 0 && mF.y > 0) ? Kf : 0;
-  const int words_to = (mT.y > 0) ? unique_to : 0;
-  // est: 0 = 3D->3D gate (:1117-1118); 1 = PnP gate (:1070-1071, 2D words of the "to" frame);
-  //      2 = PnP without a calibrated camera (:1059-1065): the estimation never runs
-  //      3 = PnP, both directions (Vis/ForwardEstOnly = false): either gate; every pair with a correspondence goes on,
-  //          the estimates count their own matches (the union of the two is not this kernel's to know)
-  const bool motion = est == 0 ? (unique_to > 0 && words_from >= min_inliers && words_to >= min_inliers)
-                    : est == 1 ? (unique_to > 0 && words_from >= min_inliers && unique_to >= min_inliers)
-                               : (est == 3 && unique_to > 0 && ((words_from >= min_inliers && unique_to >= min_inliers) ||
-                                                                (words_to >= min_inliers && Kf >= min_inliers)));
-  const bool survivor = est == 3 ? (motion && n_corr > 0) : (motion && n_corr >= min_inliers && n_corr >= (est == 0 ? 3 : 4));
-  if (motion && !survivor) {
-    const float* xF = st.xyz + (size_t)sF * kcap * 3;
-    const float* xT = st.xyz + (size_t)sT * kcap * 3;
-    for (int i = tid; i < n_corr; i += NT) {
-      uint32_t c = out[i];
-      const float* a = xF + 3 * (c & 0xFFFFu);
-      const float* b = xT + 3 * (c >> 16);
-      bool ok = isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]);
-      if (est == 0)   // findCorrespondences (3D-3D) also needs the "to" point and drops zero points
-        ok = ok && isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && (a[0] != 0.f || a[1] != 0.f || a[2] != 0.f) &&
-             (b[0] != 0.f || b[1] != 0.f || b[2] != 0.f);
-      if (ok) atomicAdd(&misc[2], 1);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    CorrHeader h;
-    h.n_corr = n_corr;
-    h.words_from = words_from;
-    h.words_to = words_to;
-    h.words_to_2d = unique_to;
-    hdr[pair] = h;
-    PassState ps;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-    ps.var = 1.0; ps.var_ang = 1.0;
-    ps.is_null = 1;
-    ps.inliers = 0;
-    ps.matches = (motion && !survivor) ? misc[2] : 0;
-    ps.pad = 0;
-    pass[pair] = ps;
-    if (survivor) {
-      int pos = atomicAdd(counter, 1);
-      list[pos] = pair;
-    }
-  }
+  match_finish<NT>(st, pair, M, min_inliers, est, rejected, corr + (size_t)pair * kcap, hdr[pair], pass[pair], list, counter);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -948,6 +842,9 @@ __device__ __forceinline__ bool mf_repair_accept(const uint32_t* fromD, int Kf, 
 // `out` = the pair's correspondence list (kcap entries; global in the stage kernels, LDS -- it may alias the
 // staged "from" block, which is dead by the time the list is written -- in the fused kernel); hdr_out / pass_out
 // = the pair's header and pass-1 state (same two homes).
+// Guard, prologue, compaction loop and header write are spelt out here and not taken from sf_match_device.hpp as
+// k_match_global does: this body is inlined into k_verify_fused and k_match_split, whose vector code and register
+// allocation move with any of them behind a function boundary (profiles/match_finish_isa.txt); the calls below do not.
 template <int W, int NQ, int NT, int MF_NTL = 2, bool MF_PIPE = false>
 __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int sF, int sT, float nndr, int min_inliers,
                                               int est, uint32_t* out, CorrHeader& hdr_out, PassState& pass_out,
@@ -963,11 +860,7 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
     if (tid == 0) {
       CorrHeader h = {0, 0, 0, 0};
       hdr_out = h;
-      PassState ps;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-      ps.var = 1.0; ps.var_ang = 1.0; ps.is_null = 1; ps.inliers = 0; ps.matches = 0; ps.pad = 0;
-      pass_out = ps;
+      write_null_pass(pass_out, 0);
     }
     return false;
   }
@@ -1086,10 +979,7 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
         }
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-          if (on[p] && acc[p]) {
-            atomicAdd(&cnt[f[p]], 1);
-            owner[f[p]] = t[p];
-          }
+          if (on[p] && acc[p]) match_claim(cnt, owner, f[p], t[p]);
           rejected += __popcll(__ballot(on[p] && !acc[p]));
         }
       };
@@ -1149,8 +1039,7 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
               for (int c = 0; c < W; ++c) d += __popc(r[c] ^ q[j][c]);
               if (d == b1) break;
             }
-            atomicAdd(&cnt[f], 1);
-            owner[f] = t;
+            match_claim(cnt, owner, f, t);
           } else {
             ++rejected;
           }
@@ -1188,53 +1077,19 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
   const int n_corr = running;
   SF_TRACE_ROW_MARK(trace_row, 35);   // list compacted
 
-  const int unique_to = (Kf > 0 && Kt > 0) ? misc[0] + n_corr : 0;
-  const int words_from = (Kf > 0 && mF.y > 0) ? Kf : 0;
-  const int words_to = (mT.y > 0) ? unique_to : 0;
-  // est: 0 = 3D->3D gate (:1117-1118); 1 = PnP gate (:1070-1071, 2D words of the "to" frame);
-  //      2 = PnP without a calibrated camera (:1059-1065): the estimation never runs
-  //      3 = PnP, both directions (Vis/ForwardEstOnly = false): either gate; every pair with a correspondence goes on,
-  //          the estimates count their own matches (the union of the two is not this kernel's to know)
-  const bool motion = est == 0 ? (unique_to > 0 && words_from >= min_inliers && words_to >= min_inliers)
-                    : est == 1 ? (unique_to > 0 && words_from >= min_inliers && unique_to >= min_inliers)
-                               : (est == 3 && unique_to > 0 && ((words_from >= min_inliers && unique_to >= min_inliers) ||
-                                                                (words_to >= min_inliers && Kf >= min_inliers)));
-  const bool survivor = est == 3 ? (motion && n_corr > 0) : (motion && n_corr >= min_inliers && n_corr >= (est == 0 ? 3 : 4));
-  if (motion && !survivor) {
-    const float* xF = st.xyz + (size_t)sF * kcap * 3;
-    const float* xT = st.xyz + (size_t)sT * kcap * 3;
-    for (int i = tid; i < n_corr; i += NT) {
-      uint32_t c = out[i];
-      const float* a = xF + 3 * (c & 0xFFFFu);
-      const float* b = xT + 3 * (c >> 16);
-      bool ok = isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]);
-      if (est == 0)   // findCorrespondences (3D-3D) also needs the "to" point and drops zero points
-        ok = ok && isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && (a[0] != 0.f || a[1] != 0.f || a[2] != 0.f) &&
-             (b[0] != 0.f || b[1] != 0.f || b[2] != 0.f);
-      if (ok) atomicAdd(&misc[2], 1);
-    }
-    __syncthreads();
-  }
+  const MatchGates G = match_gates(Kf, Kt, mF, mT, misc[0], n_corr, min_inliers, est);
+  const bool motion = G.motion, survivor = G.survivor;
+  if (motion && !survivor)
+    corr_count_finite<NT>(st.xyz + (size_t)sF * kcap * 3, st.xyz + (size_t)sT * kcap * 3, out, n_corr, est == 0, &misc[2]);
   if (tid == 0) {
     CorrHeader h;
     h.n_corr = n_corr;
-    h.words_from = words_from;
-    h.words_to = words_to;
-    h.words_to_2d = unique_to;
+    h.words_from = G.words_from;
+    h.words_to = G.words_to;
+    h.words_to_2d = G.unique_to;
     hdr_out = h;
-    PassState ps;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-    ps.var = 1.0; ps.var_ang = 1.0;
-    ps.is_null = 1;
-    ps.inliers = 0;
-    ps.matches = (motion && !survivor) ? misc[2] : 0;
-    ps.pad = 0;
-    pass_out = ps;
-    if (survivor && list) {
-      int pos = atomicAdd(counter, 1);
-      list[pos] = pair;
-    }
+    write_null_pass(pass_out, (motion && !survivor) ? misc[2] : 0);
+    if (survivor && list) worklist_append(list, counter, pair);
   }
   return survivor;
 }
@@ -1265,37 +1120,19 @@ k_match_global_mf(StoreView st, const int32_t* __restrict__ pair_from, const int
                              corr + (size_t)pair * st.kcap, hdr[pair], pass[pair], list, counter, smem);
 }
 
+// pass-1 stage launches: sf_launch_pass1 (sf_internal.hpp) holds the argument list
 template <int W, int NQ, int NT>
 void launch_match_v2(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   size_t lds = sf_match_lds_bytes(st.kcap, W);
   if (const char* v = getenv("SF_MATCH_LDS_PAD")) lds += (size_t)atoi(v);   // occupancy experiment (diagnostic)
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  if constexpr (NQ == 0)
-    hipLaunchKernelGGL((k_match_global_mf<W, NT>), dim3(n), dim3(NT), lds, c->stream, st, d_from, d_to,
-                       c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p,
-                       (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
-  else
-    hipLaunchKernelGGL((k_match_global_v2<W, NQ, NT>), dim3(n), dim3(NT), lds, c->stream, st, d_from, d_to,
-                       c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p,
-                       (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
+  if constexpr (NQ == 0) sf_launch_pass1(c, k_match_global_mf<W, NT>, NT, lds, st, d_from, d_to, n);
+  else sf_launch_pass1(c, k_match_global_v2<W, NQ, NT>, NT, lds, st, d_from, d_to, n);
 }
 
-template <int W, int NQ, int NT>
+// variant 1 and its float32 form: the bookkeeping is all the LDS they take
+template <int W, int NQ, int NT, bool L2 = false>
 void launch_match(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
-  const size_t lds = (size_t)(2 * st.kcap + 16) * sizeof(int);
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  hipLaunchKernelGGL((k_match_global<W, NQ, NT>), dim3(n), dim3(NT), lds, c->stream, st, d_from, d_to,
-                     c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p,
-                     (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
-}
-
-template <int W>
-void launch_match_l2(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
-  const size_t lds = (size_t)(2 * st.kcap + 16) * sizeof(int);
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  hipLaunchKernelGGL((k_match_global<W, 1, 256, true>), dim3(n), dim3(256), lds, c->stream, st, d_from, d_to,
-                     c->dparams.nndr, c->dparams.min_inliers, sf_est_mode(c), (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p,
-                     (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
+  sf_launch_pass1(c, k_match_global<W, NQ, NT, L2>, NT, (size_t)(2 * st.kcap + 16) * sizeof(int), st, d_from, d_to, n);
 }
 
 }  // namespace
@@ -1305,13 +1142,14 @@ int sf_launch_match_global(sf_context* c, StoreView st, const int32_t* d_from, c
   if (c->params.desc_type == 2) return sf_launch_match_global_u8(c, st, d_from, d_to, n);   // uint8 rows, L2: k_match_u8.hip
   if (c->params.desc_type == 1) {       // float32 rows: exact L2 on the VALU (north_star: MFMA only for the NetVLAD matrix)
     sf_prof_begin(c, SF_K_MATCH);
-    if (st.w == 64) launch_match_l2<64>(c, st, d_from, d_to, n);
-    else launch_match_l2<128>(c, st, d_from, d_to, n);
+    if (st.w == 64) launch_match<64, 1, 256, true>(c, st, d_from, d_to, n);
+    else launch_match<128, 1, 256, true>(c, st, d_from, d_to, n);
     sf_prof_end(c, SF_K_MATCH);
     SF_HIP(c, hipGetLastError());
     return SF_OK;
   }
-  // geometry: variant = NQ * 1000 + NT (tunable through SF_MATCH_VARIANT for A/B runs)
+  // geometry: variant = NQ * 1000 + NT of k_match_global, 10000 more for match_v2_body (SF_MATCH_VARIANT forces one for
+  // A/B runs; the geometries no rule chooses were retired)
   int variant = c->match_variant;
   if (variant == 0) {
     // default: LDS + u16 variant while the staged "from" block keeps >= 2 workgroups per CU
@@ -1319,35 +1157,23 @@ int sf_launch_match_global(sf_context* c, StoreView st, const int32_t* d_from, c
     variant = lds_v2 <= 64 * 1024 ? (c->match_mfma && st.kcap <= MF_MAX_ROWS ? 10256 : 12256) : 2256;
   }
   sf_prof_begin(c, SF_K_MATCH);
-#define SF_CASE(NQ_, NT_)                                                        \
-  case NQ_ * 1000 + NT_:                                                         \
-    if (st.w == 8) launch_match<8, NQ_, NT_>(c, st, d_from, d_to, n);            \
-    else launch_match<16, NQ_, NT_>(c, st, d_from, d_to, n);                     \
-    break;
   switch (variant) {
-    SF_CASE(1, 256)
-    SF_CASE(2, 256)
-    SF_CASE(4, 128)
-    SF_CASE(2, 128)
-    SF_CASE(4, 256)
-    SF_CASE(8, 64)
-    SF_CASE(4, 64)
-#define SF_CASE2(NQ_, NT_)                                                          \
-  case 10000 + NQ_ * 1000 + NT_:                                                    \
-    if (st.w == 8) launch_match_v2<8, NQ_, NT_>(c, st, d_from, d_to, n);            \
-    else launch_match_v2<16, NQ_, NT_>(c, st, d_from, d_to, n);                     \
-    break;
-    SF_CASE2(0, 256)   // NQ = 0: fp4 matrix-core variant
-    SF_CASE2(2, 256)
-    SF_CASE2(1, 256)
-    SF_CASE2(4, 128)
-    SF_CASE2(2, 128)
-#undef SF_CASE2
+    case 2256:
+      if (st.w == 8) launch_match<8, 2, 256>(c, st, d_from, d_to, n);
+      else launch_match<16, 2, 256>(c, st, d_from, d_to, n);
+      break;
+    case 10256:   // NQ = 0: fp4 matrix-core variant
+      if (st.w == 8) launch_match_v2<8, 0, 256>(c, st, d_from, d_to, n);
+      else launch_match_v2<16, 0, 256>(c, st, d_from, d_to, n);
+      break;
+    case 12256:
+      if (st.w == 8) launch_match_v2<8, 2, 256>(c, st, d_from, d_to, n);
+      else launch_match_v2<16, 2, 256>(c, st, d_from, d_to, n);
+      break;
     default:
       sf_prof_end(c, SF_K_MATCH);
       return sf_fail(c, SF_EINVAL, "unknown match kernel variant %d", variant);
   }
-#undef SF_CASE
   sf_prof_end(c, SF_K_MATCH);
   SF_HIP(c, hipGetLastError());
   return SF_OK;

@@ -17,11 +17,12 @@
 //     second best is the next distance (equal to the best where the best occurs twice).  The merge compares
 //     (distance, index) as two fields: a packed key would need 23 + 12 bits.
 // Everything around the scan -- the cnt / owner bookkeeping, the compaction, the gates, the survivor list -- is
-// k_match_global's (k_match.hip), restated here because that file is part of the unity translation unit.
+// match_slot_outside / match_begin / match_claim / match_finish (sf_match_device.hpp), the calls k_match_global makes.
 // No float arithmetic besides the accept test (both conversions exact), so no -ffp-contract=off.
 #include <climits>
 
 #include "sf_internal.hpp"
+#include "sf_match_device.hpp"
 
 namespace {
 
@@ -145,125 +146,28 @@ k_match_global_u8(StoreView st, const int32_t* __restrict__ pair_from, const int
                   int min_inliers, int est, int FB, uint32_t* __restrict__ corr, CorrHeader* __restrict__ hdr,
                   PassState* __restrict__ pass, int32_t* __restrict__ list, int32_t* __restrict__ counter) {
   extern __shared__ __attribute__((aligned(16))) int smem[];
-  constexpr int NT = U8_NT, NW = NT / 64;
   const int pair = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
   const int kcap = st.kcap;
-  const int sF = pair_from[pair], sT = pair_to[pair];
-  if ((unsigned)sF >= (unsigned)st.n_slots || (unsigned)sT >= (unsigned)st.n_slots) {
-    // caller-provided slot outside the store: report a failed estimation, touch nothing else
-    if (tid == 0) {
-      CorrHeader h = {0, 0, 0, 0};
-      hdr[pair] = h;
-      PassState ps;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-      ps.var = 1.0; ps.var_ang = 1.0; ps.is_null = 1; ps.inliers = 0; ps.matches = 0; ps.pad = 0;
-      pass[pair] = ps;
-    }
-    return;
-  }
-  const int4 mF = st.meta[sF], mT = st.meta[sT];
-  const int Kf = mF.x, Kt = mT.x;
-  const uint32_t* dF = st.desc + (size_t)sF * kcap * U8_W;
-  const uint32_t* dT = st.desc + (size_t)sT * kcap * U8_W;
-
-  int* cnt = smem;               // [kcap] "to" rows that matched each "from" word
-  int* owner = smem + kcap;      // [kcap] the matching "to" row (meaningful when cnt == 1)
-  int* misc = smem + 2 * kcap;   // [16]   0: rejected "to" rows, 2: finite corr, 4..7 wave totals
-  int* fnorm = misc + 16;        // [FB]   norms of the staged "from" rows
+  MatchPair M;
+  if (match_slot_outside(st, pair_from[pair], pair_to[pair])) { match_report_outside(hdr[pair], pass[pair]); return; }
+  match_begin<U8_NT>(st, pair_from[pair], pair_to[pair], smem, M);
+  const int Kf = M.mF.x, Kt = M.mT.x;
+  const uint32_t* dF = st.desc + (size_t)M.sF * kcap * U8_W;
+  const uint32_t* dT = st.desc + (size_t)M.sT * kcap * U8_W;
+  int* fnorm = M.misc + 16;      // [FB]   norms of the staged "from" rows, behind the bookkeeping
   uint32_t* frow = reinterpret_cast<uint32_t*>(fnorm + FB);   // [FB][U8_PITCH]
-
-  for (int i = tid; i < Kf; i += NT) cnt[i] = 0;
-  if (tid < 16) misc[tid] = 0;
   __syncthreads();
 
   int rejected = 0;
   if (Kf > 0) {
     knn2_scan_u8(dF, Kf, dT, Kt, FB, fnorm, frow, [&](int t, int d1, int d2, int i1) {
       const bool acc = (Kf >= 2) && i1 >= 0 && !((float)d1 > nndr * (float)d2);
-      if (acc) {
-        atomicAdd(&cnt[i1], 1);
-        owner[i1] = t;
-      } else {
-        ++rejected;
-      }
+      if (acc) match_claim(M.cnt, M.owner, i1, t);
+      else ++rejected;
     });
   }
-  // wave-reduce the rejected count, one LDS atomic per wave
-  for (int off = 32; off >= 1; off >>= 1) rejected += __shfl_xor(rejected, off);
-  if (lane == 0 && rejected) atomicAdd(&misc[0], rejected);
-  __syncthreads();
-
-  // id-ordered compaction of the "from" words matched by exactly one "to" row
-  uint32_t* out = corr + (size_t)pair * kcap;
-  int running = 0;
-  for (int base = 0; base < Kf; base += NT) {
-    const int f = base + tid;
-    const bool flag = (f < Kf) && (cnt[f] == 1);
-    const unsigned long long bal = __ballot(flag);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) misc[4 + wave] = __popcll(bal);
-    __syncthreads();
-    int woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      int c = misc[4 + w];
-      if (w < wave) woff += c;
-      total += c;
-    }
-    if (flag) out[running + woff + before] = (uint32_t)f | ((uint32_t)owner[f] << 16);
-    running += total;
-    __syncthreads();
-  }
-  const int n_corr = running;
-
-  // the gates of k_match_global (myRegistrationVis.cpp:928,1117-1118 / :1070-1071 / :1059-1065), unchanged
-  const int unique_to = (Kf > 0 && Kt > 0) ? misc[0] + n_corr : 0;
-  const int words_from = (Kf > 0 && mF.y > 0) ? Kf : 0;
-  const int words_to = (mT.y > 0) ? unique_to : 0;
-  const bool motion = est == 0 ? (unique_to > 0 && words_from >= min_inliers && words_to >= min_inliers)
-                    : est == 1 ? (unique_to > 0 && words_from >= min_inliers && unique_to >= min_inliers)
-                               : (est == 3 && unique_to > 0 && ((words_from >= min_inliers && unique_to >= min_inliers) ||
-                                                                (words_to >= min_inliers && Kf >= min_inliers)));
-  const bool survivor = est == 3 ? (motion && n_corr > 0) : (motion && n_corr >= min_inliers && n_corr >= (est == 0 ? 3 : 4));
-  if (motion && !survivor) {
-    const float* xF = st.xyz + (size_t)sF * kcap * 3;
-    const float* xT = st.xyz + (size_t)sT * kcap * 3;
-    for (int i = tid; i < n_corr; i += NT) {
-      uint32_t c = out[i];
-      const float* a = xF + 3 * (c & 0xFFFFu);
-      const float* b = xT + 3 * (c >> 16);
-      bool ok = isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]);
-      if (est == 0)   // findCorrespondences (3D-3D) also needs the "to" point and drops zero points
-        ok = ok && isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && (a[0] != 0.f || a[1] != 0.f || a[2] != 0.f) &&
-             (b[0] != 0.f || b[1] != 0.f || b[2] != 0.f);
-      if (ok) atomicAdd(&misc[2], 1);
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    CorrHeader h;
-    h.n_corr = n_corr;
-    h.words_from = words_from;
-    h.words_to = words_to;
-    h.words_to_2d = unique_to;
-    hdr[pair] = h;
-    PassState ps;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-    ps.var = 1.0; ps.var_ang = 1.0;
-    ps.is_null = 1;
-    ps.inliers = 0;
-    ps.matches = (motion && !survivor) ? misc[2] : 0;
-    ps.pad = 0;
-    pass[pair] = ps;
-    if (survivor) {
-      int pos = atomicAdd(counter, 1);
-      list[pos] = pair;
-    }
-  }
+  match_finish<U8_NT>(st, pair, M, min_inliers, est, rejected, corr + (size_t)pair * kcap, hdr[pair], pass[pair], list,
+                      counter);
 }
 
 // the scan alone, one pair: what it found per "to" row (sf_debug_knn2_u8)
@@ -291,11 +195,8 @@ int sf_launch_match_global_u8(sf_context* c, StoreView st, const int32_t* d_from
   if (st.w != U8_W) return sf_fail(c, SF_EINVAL, "uint8 L2 rows are %d dwords, the store holds %d", U8_W, st.w);
   const int FB = u8_block_rows(st.kcap);
   const size_t lds = (size_t)(2 * st.kcap + 16 + FB * (U8_PITCH + 1)) * sizeof(int);
-  int32_t* counters = (int32_t*)c->w->counters.p;
   sf_prof_begin(c, SF_K_MATCH);
-  hipLaunchKernelGGL(k_match_global_u8, dim3(n), dim3(U8_NT), lds, c->stream, st, d_from, d_to, c->dparams.nndr,
-                     c->dparams.min_inliers, sf_est_mode(c), FB, (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p,
-                     (PassState*)c->w->pass1.p, (int32_t*)c->w->list1.p, counters + 0);
+  sf_launch_pass1(c, k_match_global_u8, U8_NT, lds, st, d_from, d_to, n, FB);
   sf_prof_end(c, SF_K_MATCH);
   SF_HIP(c, hipGetLastError());
   return SF_OK;

@@ -28,6 +28,7 @@
 // Compiled with -ffp-contract=off.
 #include "sf_device_math.hpp"
 #include "sf_internal.hpp"
+#include "sf_match_device.hpp"
 #include "sf_pnp_math.hpp"
 #include "k_ba.hip"
 
@@ -384,13 +385,7 @@ __device__ __forceinline__ PnpTail pnp_body(const StoreView& st, int pair, const
   const float cxf = (float)P.cx, cyf = (float)P.cy;
   if (P.bidirectional && !sf_pnp_dir_gate(DIR, hdr[pair], st.meta[sF].x, guided, P.min_inliers)) {
     // this direction's gate (:1059, :1070-1071) is closed: covariances[dir] stays the identity, no matches, no inliers
-    if (tid == 0) {
-      PassState z;
-#pragma unroll
-      for (int i = 0; i < 12; ++i) z.T[i] = 0.f;
-      z.var = 1.0; z.var_ang = 1.0; z.is_null = 1; z.inliers = 0; z.matches = 0; z.pad = 0;
-      pass[pair] = z;
-    }
+    if (tid == 0) write_null_pass(pass[pair], 0);
     return none;
   }
   if (tid < 16) L.misc[tid] = 0;

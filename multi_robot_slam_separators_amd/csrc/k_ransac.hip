@@ -27,6 +27,7 @@
 // Compiled with -ffp-contract=off (canonical arithmetic, see sf_device_math.hpp).
 #include "sf_device_math.hpp"
 #include "sf_internal.hpp"
+#include "sf_match_device.hpp"
 #include "k_ba.hip"
 
 namespace {
@@ -387,20 +388,6 @@ __device__ __forceinline__ bool replay_round(const RansacLds& L, ScanState& S, i
 __host__ __device__ inline size_t sf_ransac_lds_bytes_dev(int kcap) {
   return (size_t)kcap * 32 + 64 * 8 + 4 * 8 + (size_t)kcap * 4 + 16 * 4 + (size_t)kcap * 2 + 12 * 64 * 4 + 5 * 64 * 4 +
          16 * 4 + 16 * 4 + (size_t)kcap * 4;
-}
-
-// The "no transform" state of a pass (identity covariance scale, `matches` correspondences seen): built where it is
-// written, so that no copy of it stays live in registers across the pass.
-__device__ __forceinline__ void write_null_pass(PassState& out, int matches) {
-  PassState ps;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-  ps.var = 1.0; ps.var_ang = 1.0;
-  ps.is_null = 1;
-  ps.inliers = 0;
-  ps.matches = matches;
-  ps.pad = 0;
-  out = ps;
 }
 
 // Body of one RANSAC pass for ONE pair (the calling 256-thread workgroup).  `cl` = the pair's n_corr

@@ -621,6 +621,18 @@ inline int sf_est_mode(const sf_context* c) {
   return c->dparams.estimation_type == 1 ? (c->dparams.calibrated ? (c->dparams.bidirectional ? 3 : 1) : 2) : 0;
 }
 
+// The argument list of the pass-1 stage kernels (k_match.hip, k_match_u8.hip):
+// kern(st, pair_from, pair_to, nndr, min_inliers, est, extra..., corr, hdr, pass, list, counter), one workgroup of `nt`
+// threads with `lds` bytes per pair, on the context's stream into its first-pass workspace.
+template <class Kern, class... Extra>
+void sf_launch_pass1(sf_context* c, Kern kern, int nt, size_t lds, StoreView st, const int32_t* d_from, const int32_t* d_to,
+                     int n, Extra... extra) {
+  int32_t* counters = (int32_t*)c->w->counters.p;
+  hipLaunchKernelGGL(kern, dim3(n), dim3(nt), lds, c->stream, st, d_from, d_to, c->dparams.nndr, c->dparams.min_inliers,
+                     sf_est_mode(c), extra..., (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p,
+                     (int32_t*)c->w->list1.p, counters + 0);
+}
+
 // Gate of one direction of the PnP estimate (myRegistrationVis.cpp:1059, :1070-1071 with A / B as :936-977 set them):
 // dir 0: 3D words of "from" and 2D words of "to"; dir 1: 3D words of "to" and 2D words of "from" -- every "from" row
 // after global matching (:856-875), the rows with a finite point after guided matching (:766-774).

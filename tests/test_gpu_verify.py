@@ -92,6 +92,27 @@ def test_other_configs(oracle, k, cols, iters):
     assert got["success"][is_true].all()
 
 
+def test_scalar_load_matcher_at_512_bit_rows(oracle):
+    """k_match_global<16, 2, 256> (variant 1: "from" rows by scalar loads) is the default once the LDS-staged matcher's
+    working set passes 64 KB: at 64-byte rows from kcap = 911.  K = 960: (960 * 16 + 2 * 960 + 16) * 4 = 69 184 B.  The
+    assertion shows that the stage form's global matching launch ran and the fused kernel did not; that the launch was
+    this geometry and not another stage geometry follows from that arithmetic and sf_launch_match_global's rule."""
+    from multi_robot_slam_separators_amd import lib
+    k, cols = 960, 64
+    p = synth.camera_params()
+    p.iterations = 300
+    p.max_features = k
+    A, B, is_true, _ = synth.make_pairs(100 + k, 10, k=k, cols=cols, true_frac=0.5)
+    with lib.SeparatorFinder(p) as f:
+        f.prof_enable(True)
+        got = f.estimate_transform_batch(A, B)
+        prof = f.prof_get()
+    assert prof["k_match_global"][0] >= 1 and prof["k_verify_fused"][0] == 0, prof
+    for i in range(len(A)):
+        assert_result_parity(got[i], oracle.estimate_transform(p, A[i], B[i]), "k=%d pair %d" % (k, i))
+    assert got["success"][is_true].all()
+
+
 def test_store_resident_pairs(finder, oracle):
     rng = np.random.default_rng(5)
     A, B, is_true, _ = synth.make_pairs(55, 12, k=400, true_frac=0.5)

@@ -10,7 +10,7 @@ from multi_robot_slam_separators_amd import lib, synth, _abi
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 500
 cols = int(sys.argv[3]) if len(sys.argv) > 3 else 32
-variants = [int(v) for v in sys.argv[4:]] or [2256, 1256, 4128, 2128, 4256, 8064, 4064]
+variants = [int(v) for v in sys.argv[4:]] or [2256, 12256, 10256]      # (the geometries sf_launch_match_global keeps)
 d = synth.make_store_batch(7, n, k=k, cols=cols, true_frac=0.2)
 dev = torch.device("cuda:0")
 def up(x):
