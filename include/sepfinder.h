@@ -113,6 +113,9 @@ extern "C" {
       sf_get_features_and_descriptor_depth_batch_device, sf_add_keyframes_depth_batch_device (RGB-D keyframes: 3D points
       from a registered depth image, Vis/DepthAsMask).  New calls only: every existing call keeps its behaviour and its
       messages; the version number, sizeof(sf_params) and SF_K_COUNT stay.                                             */
+/* 8, additions: sf_kfblob_header, sf_kfblob_entry, SF_KFBLOB_MAGIC, sf_store_export_plan, sf_store_export_keyframes_device,
+      sf_store_import_keyframes_device, sf_store_wire_status (store slots as one block of bytes, both directions on the
+      device).  New calls only; the version number, sizeof(sf_params) and SF_K_COUNT stay.                             */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -349,6 +352,73 @@ int  sf_store_add_keyframes_device(sf_handle h, int32_t n, int32_t rows, int32_t
                                    const sf_keypoint* d_kp, int32_t* out_first_slot);
 int  sf_store_size(sf_handle h, int32_t* n_slots);
 int  sf_store_clear(sf_handle h);
+
+/* ---- store slots as bytes: export, import (csrc/k_store_wire.hip) --------------------------------------------------- */
+/* A store slot holds exactly what verification reads -- descriptor rows, 3D points, {x, y, octave byte} per keypoint --
+   so n consecutive slots are a complete message by themselves: the features one robot ships to another
+   (GetFeatsAndDesc.srv), and what replicates a store over the GPUs of a node.  The blob is ONE contiguous,
+   position-independent, little-endian block of bytes:
+
+     [sf_kfblob_header][sf_kfblob_entry x n_keyframes][block of keyframe 0][block of keyframe 1] ...
+
+   The block of a keyframe, at `offset` from the start of the blob:
+     rows x cols descriptor bytes, tight (without the store's zero padding of a row to whole dwords);
+     rows x 12 bytes of float xyz, absent when n3d == 0;
+     rows x 12 bytes of {float x, float y, int32 octave}, the octave the sign-extended byte the store keeps;
+   every part padded with zero bytes to a multiple of 16; a keyframe of 0 rows has an empty block.
+   Canonical form (what export writes): blocks in slot order, tight, the first directly behind the table; all padding
+   and reserved bytes zero -- the blob is a pure function of the slots' contents.  Float payloads are copied bit for
+   bit.  size / angle / response / class_id of sf_keypoint are not in it: the store never held them.              */
+#define SF_KFBLOB_MAGIC   0x424B4653u   /* "SFKB" */
+#define SF_KFBLOB_VERSION 1
+typedef struct sf_kfblob_header {
+  uint32_t magic;        /* SF_KFBLOB_MAGIC; 0 in the header of an export that did not fit its buffer */
+  uint16_t version;      /* SF_KFBLOB_VERSION */
+  uint8_t  desc_type;    /* sf_params.desc_type of the exporting handle */
+  uint8_t  reserved;     /* 0 */
+  int32_t  n_keyframes;
+  int32_t  max_rows;     /* the largest `rows` of the table */
+  uint64_t total_bytes;  /* header + table + blocks (at byte 16: naturally aligned, so the struct has no hidden padding
+                            and is 32 bytes under every compiler; a further int32 in front of it would make it 40) */
+  uint64_t reserved2;    /* 0 */
+} sf_kfblob_header;      /* 32 bytes */
+typedef struct sf_kfblob_entry {
+  int32_t  rows;
+  int32_t  n3d;          /* 0 or rows */
+  int32_t  cols;         /* descriptor bytes per row */
+  int32_t  reserved;     /* 0 */
+  uint64_t offset;       /* of the keyframe's block from the start of the blob; a multiple of 16 */
+  uint64_t bytes;        /* length of the block */
+} sf_kfblob_entry;       /* 32 bytes */
+/* The size of the blob of slots [first_slot, first_slot + n): waits for the stream, *total_bytes and *max_rows (either
+   may be NULL) are the header's.  n = 0 is SF_OK (a blob of 32 bytes); a range outside [0, sf_store_size) or
+   n > 65535: SF_ERANGE.                                                                                           */
+int  sf_store_export_plan(sf_handle h, int32_t first_slot, int32_t n, uint64_t* total_bytes, int32_t* max_rows);
+/* Writes the blob of slots [first_slot, first_slot + n) to d_blob (device memory, 16-byte aligned, cap_bytes long):
+   asynchronous on the handle's stream, no host wait, and independent of an earlier sf_store_export_plan (it plans again
+   on the device).  A blob longer than cap_bytes is not written: only its header is (when cap_bytes >= 32), with magic
+   0 and the total_bytes it would have taken, nothing else of d_blob is touched, and sf_store_wire_status reports bit 1. */
+int  sf_store_export_keyframes_device(sf_handle h, int32_t first_slot, int32_t n, void* d_blob, uint64_t cap_bytes);
+/* Appends the n keyframes of the blob at d_blob (device memory, 16-byte aligned, `bytes` long) to the store: the ragged
+   form of sf_store_add_keyframes_device, asynchronous, no host wait.  n, max_rows and cols (a descriptor width of the
+   store's class, e.g. the blob's largest) are what the caller knows of the blob on the host -- from
+   sf_store_export_plan, or from the record that travelled ahead of the blob; they size the store exactly as
+   sf_store_add_keyframes_device's do, with its refusals.  The call ALWAYS appends n slots.  The kernel checks the blob
+   against these arguments and reads nothing outside [d_blob, d_blob + bytes), whatever the blob says:
+     header: magic, version, desc_type of this handle, n_keyframes == n, 32 + 32 n <= total_bytes <= bytes -- else all
+             n slots are left empty (status bit 2);
+     entry:  0 <= rows <= max_rows, n3d 0 or rows, cols of the store's width class, offset a multiple of 16 and at or
+             behind the table, offset + bytes <= total_bytes, bytes what rows, cols and n3d imply -- else this slot is
+             left empty (status bit 4).
+   An empty slot has meta {0, 0, 0, cols}.  An imported slot equals, bit for bit, the slot sf_store_add_keyframe makes
+   of the same features.  n = 0 is SF_OK; n > 65535: SF_ERANGE.                                                     */
+int  sf_store_import_keyframes_device(sf_handle h, const void* d_blob, uint64_t bytes, int32_t n, int32_t max_rows,
+                                      int32_t cols, int32_t* out_first_slot);
+/* What the most recent sf_store_export_keyframes_device or sf_store_import_keyframes_device call reported (each of the
+   two resets it; sf_store_export_plan does not touch it): waits for the stream.  out[0]: bits 1 = the
+   export did not fit cap_bytes, 2 = bad header, 4 = bad entry; out[1]: slots the import left empty; out[2]: the first of
+   them (index into the blob), or -1; out[3]: 0.  SF_OK when out[0] is 0, else SF_ERANGE (out is filled either way).  */
+int  sf_store_wire_status(sf_handle h, int32_t out[4]);
 
 /* ---- features of one stereo keyframe -------------------------------- */
 /* replaces: RegistrationVis::getFeaturesImpl (myRegistrationVis.cpp:343-436: descriptors for the given keypoints,

@@ -471,6 +471,31 @@ class StepResult(C.Structure):
 
 SF_ABI_VERSION = 8      # include/sepfinder.h
 
+# store slots as one block of bytes (sf_store_export_* / sf_store_import_keyframes_device): [header][entry x n][blocks]
+SF_KFBLOB_MAGIC = 0x424B4653      # "SFKB"
+SF_KFBLOB_VERSION = 1
+WIRE_EXPORT_OVERFLOW, WIRE_BAD_HEADER, WIRE_BAD_ENTRY = 1, 2, 4      # bits of sf_store_wire_status' first word
+
+
+class KfBlobHeader(C.LittleEndianStructure):
+    """sf_kfblob_header (include/sepfinder.h)."""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint16), ("desc_type", C.c_uint8), ("reserved", C.c_uint8),
+                ("n_keyframes", C.c_int32), ("max_rows", C.c_int32), ("total_bytes", C.c_uint64), ("reserved2", C.c_uint64)]
+
+
+class KfBlobEntry(C.LittleEndianStructure):
+    """sf_kfblob_entry (include/sepfinder.h): one keyframe of the table behind the header."""
+    _fields_ = [("rows", C.c_int32), ("n3d", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32),
+                ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+KFBLOB_HEADER_DTYPE = np.dtype([("magic", "<u4"), ("version", "<u2"), ("desc_type", "u1"), ("reserved", "u1"),
+                                ("n_keyframes", "<i4"), ("max_rows", "<i4"), ("total_bytes", "<u8"), ("reserved2", "<u8")])
+KFBLOB_ENTRY_DTYPE = np.dtype([("rows", "<i4"), ("n3d", "<i4"), ("cols", "<i4"), ("reserved", "<i4"), ("offset", "<u8"),
+                               ("bytes", "<u8")])
+assert KFBLOB_HEADER_DTYPE.itemsize == C.sizeof(KfBlobHeader) == 32
+assert KFBLOB_ENTRY_DTYPE.itemsize == C.sizeof(KfBlobEntry) == 32
+
 
 def default_params() -> Params:
     """Defaults: multi_robot_separators.launch:19-23 for the reference's own knobs; rtabmap

@@ -295,7 +295,7 @@ extern "C" void sf_destroy(sf_handle c) {
                  &c->ex_integral, &c->ex_desc, &c->ex_xyz, &c->ex_keep, &c->ex_rows, &c->brief_tests, &c->orb_tests,
                  &c->ex_blur, &c->ex_kpts, &c->orb_pyr, &c->orb_work, &c->freak_pattern, &c->freak_tables, &c->surf_planes, &c->surf_keys, &c->surf_tables, &c->surf_ctl, &c->sift_planes, &c->sift_keys, &c->sift_tables, &c->sift_ctl,
                  &c->gf_planes, &c->gf_keys, &c->gf_tmp, &c->gf_lists, &c->gf_scalar, &c->lk_pyr, &c->ft_images, &c->ft_kpts, &c->ft_flow, &c->ft_wire,
-                 &c->ft_counts, &c->ft_cells, &c->img_src, &c->img_gray, &c->img_desc};
+                 &c->ft_counts, &c->ft_cells, &c->img_src, &c->img_gray, &c->img_desc, &c->wire_plan, &c->wire_status};
   for (Buf* b : bufs) sf_buf_free(*b);
   for (int k = 0; k <= SF_STEP_MAX_LANES; ++k) {
     Workspace& w = c->ws[k];

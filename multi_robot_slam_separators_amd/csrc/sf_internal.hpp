@@ -286,6 +286,9 @@ struct sf_context {
   Store store;        // persistent keyframes
   Store scratch;      // staging slots for host-buffer calls
   Buf stage_desc, stage_xyz, stage_kp;   // H2D bounce buffers of the host-buffer ingest path
+  // store slots as bytes (sf_store_export_* / sf_store_import_keyframes_device; k_store_wire.hip): header and table of the
+  // most recent plan, and the four status words of the most recent export or import (sf_store_wire_status)
+  Buf wire_plan, wire_status;
   // host-buffer batch ingest (store_add_host_batch): pinned staging, table scratch and the packing workers all
   // belong to the handle and end with it (sf_destroy)
   void* ingest_pinned = nullptr;
@@ -940,6 +943,17 @@ int sf_launch_finalize(sf_context* c, int n, sf_result* d_out);
 // Ingest kernels
 int sf_launch_ingest(sf_context* c, Store& st, int first_slot, int n, int rows, int cols,
                      const uint8_t* d_desc, const float* d_xyz, const sf_keypoint* d_kp);
+// Store slots as one block of bytes (k_store_wire.hip; the layout: include/sepfinder.h, sf_kfblob_header).  All three are
+// asynchronous on the context's stream.  d_status: int32[4] {bits, emptied slots, first emptied keyframe or -1, 0}.
+// plan: header and table of slots [first_slot, first_slot + n) into d_plan (32 + 32 n bytes); resets d_status unless NULL
+int sf_launch_kfblob_plan(sf_context* c, const Store& st, int first_slot, int n, void* d_plan, int32_t* d_status);
+// pack: d_plan and the blocks it describes into d_blob, or -- the blob exceeds cap_bytes -- a header with magic 0 alone
+int sf_launch_kfblob_pack(sf_context* c, const Store& st, int first_slot, int n, const void* d_plan, void* d_blob,
+                          uint64_t cap_bytes, int32_t* d_status);
+// unpack: the n keyframes of the blob into slots first_slot ..., every one checked against (bytes, n, max_rows, the
+// handle's descriptor type and the store's width class); resets d_status
+int sf_launch_kfblob_unpack(sf_context* c, Store& st, int first_slot, int n, int max_rows, int cols, const void* d_blob,
+                            uint64_t bytes, int32_t* d_status);
 // NN stage
 int sf_nn_run(sf_context* c, sf_match* out, int cap, int* n_out);
 int sf_nn_row_minima_dev(sf_context* c, double* d_row_min, int32_t* d_row_arg, int32_t* d_status);

@@ -1,5 +1,6 @@
 // sf_store.hip -- the device-resident keyframe store: wire layout -> store layout (k_ingest, k_ingest_ragged), growth,
-// the host-buffer ingest with its packing workers, the sf_store_* entry points.
+// the host-buffer ingest with its packing workers, the sf_store_* entry points -- those that move slots as bytes included
+// (sf_store_export_*, sf_store_import_keyframes_device; their kernels are in k_store_wire.hip).
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -431,6 +432,72 @@ extern "C" int sf_store_add_keyframes_device(sf_handle c, int32_t n, int32_t row
   if (out_first_slot) *out_first_slot = c->store.slots;
   c->store.slots += n;
   return SF_OK;
+}
+
+// ---- store slots as bytes (kernels in k_store_wire.hip) -------------------------------------------
+#define SF_KFBLOB_MAX_KEYFRAMES 65535     // per call, as the batch calls
+
+// the range of an export, and the handle's plan and status buffers for it
+static int wire_export_begin(sf_context* c, int32_t first_slot, int32_t n) {
+  if (first_slot < 0 || n < 0 || (long long)first_slot + n > c->store.slots)
+    return sf_fail(c, SF_ERANGE, "slots %d .. %lld lie outside the store's %d", first_slot, (long long)first_slot + n, c->store.slots);
+  if (n > SF_KFBLOB_MAX_KEYFRAMES) return sf_fail(c, SF_ERANGE, "%d keyframes in one blob (at most %d)", n, SF_KFBLOB_MAX_KEYFRAMES);
+  SF_HIP(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->wire_plan, 32 + 32 * (size_t)n)) != SF_OK) return rc;
+  return sf_buf_reserve(c, c->wire_status, 16);
+}
+
+extern "C" int sf_store_export_plan(sf_handle c, int32_t first_slot, int32_t n, uint64_t* total_bytes, int32_t* max_rows) {
+  if (!c) return SF_EINVAL;
+  int rc = wire_export_begin(c, first_slot, n);
+  if (rc != SF_OK) return rc;
+  // (a size question: the status of the last export or import stays as it is)
+  if ((rc = sf_launch_kfblob_plan(c, c->store, first_slot, n, c->wire_plan.p, nullptr)) != SF_OK) return rc;
+  sf_kfblob_header h;
+  SF_HIP(c, hipMemcpyAsync(&h, c->wire_plan.p, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  if (total_bytes) *total_bytes = h.total_bytes;
+  if (max_rows) *max_rows = h.max_rows;
+  return SF_OK;
+}
+
+extern "C" int sf_store_export_keyframes_device(sf_handle c, int32_t first_slot, int32_t n, void* d_blob, uint64_t cap_bytes) {
+  if (!c) return SF_EINVAL;
+  if (!d_blob || ((uintptr_t)d_blob & 15)) return sf_fail(c, SF_EINVAL, "the blob's buffer is missing or not 16-byte aligned");
+  int rc = wire_export_begin(c, first_slot, n);
+  if (rc != SF_OK) return rc;
+  int32_t* status = (int32_t*)c->wire_status.p;
+  if ((rc = sf_launch_kfblob_plan(c, c->store, first_slot, n, c->wire_plan.p, status)) != SF_OK) return rc;
+  return sf_launch_kfblob_pack(c, c->store, first_slot, n, c->wire_plan.p, d_blob, cap_bytes, status);
+}
+
+extern "C" int sf_store_import_keyframes_device(sf_handle c, const void* d_blob, uint64_t bytes, int32_t n, int32_t max_rows,
+                                                int32_t cols, int32_t* out_first_slot) {
+  if (!c || n < 0 || max_rows < 0) return SF_EINVAL;
+  if (!d_blob || ((uintptr_t)d_blob & 15)) return sf_fail(c, SF_EINVAL, "the blob is missing or not 16-byte aligned");
+  if (n > SF_KFBLOB_MAX_KEYFRAMES) return sf_fail(c, SF_ERANGE, "%d keyframes in one blob (at most %d)", n, SF_KFBLOB_MAX_KEYFRAMES);
+  SF_HIP(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = sf_buf_reserve(c, c->wire_status, 16)) != SF_OK) return rc;
+  if (n > 0 && (rc = sf_store_reserve(c, c->store, c->store.slots + n, max_rows, cols)) != SF_OK) return rc;
+  if ((rc = sf_launch_kfblob_unpack(c, c->store, c->store.slots, n, max_rows, cols, d_blob, bytes, (int32_t*)c->wire_status.p)) != SF_OK)
+    return rc;
+  if (out_first_slot) *out_first_slot = c->store.slots;
+  c->store.slots += n;
+  return SF_OK;
+}
+
+extern "C" int sf_store_wire_status(sf_handle c, int32_t out[4]) {
+  if (!c || !out) return SF_EINVAL;
+  out[0] = 0; out[1] = 0; out[2] = -1; out[3] = 0;
+  SF_HIP(c, hipSetDevice(c->device));
+  if (c->wire_status.p) SF_HIP(c, hipMemcpyAsync(out, c->wire_status.p, 16, hipMemcpyDeviceToHost, c->stream));
+  SF_HIP(c, hipStreamSynchronize(c->stream));
+  if (out[0] == 0) return SF_OK;
+  return sf_fail(c, SF_ERANGE, "store wire:%s%s%s (%d slot(s) left empty, the first is keyframe %d of the blob)",
+                 (out[0] & 1) ? " the export did not fit its buffer" : "", (out[0] & 2) ? " bad header" : "",
+                 (out[0] & 4) ? " bad entry" : "", out[1], out[2]);
 }
 
 extern "C" int sf_store_size(sf_handle c, int32_t* n_slots) {

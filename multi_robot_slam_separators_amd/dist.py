@@ -249,6 +249,76 @@ class RecordExchange:
         return torch.cat(parts, dim=0), counts
 
 
+class KeyframeExchange:
+    """Replicates the keyframes every rank extracted: rank r adds its keyframes to its own `front` handle (any of the
+    store or batch extraction calls), exchange() ships them as blobs (include/sepfinder.h, sf_kfblob_header) and appends
+    every rank's, the rank's own included, to `main` in rank order -- all ranks end with byte-identical `main` stores and
+    the same slot numbers, which is what ShardedStep verifies over.
+
+    exchange():
+      1. plans on `front` (sf_store_export_plan: the size of this rank's blob) and exports into a staging block of that
+         size; the widest row of the blob's table is read off it ON THE DEVICE, so the width the receivers size their
+         stores with is the store's own and not a parameter that may differ from it;
+      2. all-gathers the (total_bytes, max_rows, n, cols) records -- the one host wait the exchange needs;
+      3. copies the staging block into a send block of the gathered maximum and all-gathers the blocks, device to device;
+      4. imports every rank's blob into `main` (sf_store_import_keyframes_device), then front.store_clear().
+    The blobs never touch the host.  On a GPU both handles run on the stream the collective is ordered against
+    (set_stream(torch.cuda.current_stream().cuda_stream), as for ShardedStep).
+
+    front / main: lib.SeparatorFinder, or anything with its store_size, export_plan, export_keyframes_device,
+    import_keyframes_device, wire_status and store_clear (the CPU tests run a NumPy restatement on host pointers).
+    cols: the descriptor width a rank WITHOUT keyframes puts into its record (default: front.params.desc_bytes; nothing
+    is imported from such a rank); device: where the blocks live (default: the handle's GPU).  The collective is
+    dist.collective(group): torch.distributed, or SelfCollective.  `waits` counts the host waits of all exchanges so far."""
+
+    def __init__(self, front, main, group=None, device=None, cols=None):
+        import torch
+        self.front, self.main, self.group = front, main, group
+        self.td = collective(group)
+        self.world = self.td.get_world_size(group)
+        self.rank = self.td.get_rank(group)
+        self.device = torch.device(device if device is not None else "cuda:%d" % front.device)
+        self.cols = int(cols if cols is not None else front.params.desc_bytes)
+        self._stage = self._send = self._recv = None
+        self.waits = 0
+
+    def _grown(self, t, nbytes):
+        import torch
+        return t if t is not None and t.numel() >= nbytes else torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+
+    def exchange(self, check=True):
+        """Returns [(first slot in main, keyframes)] per rank.  check (the default): main.wire_status() after every import, a
+        host wait each, so that a blob refused from ANY rank raises -- every import resets the status words, and without
+        the check only the last rank's import can still be asked about (main.wire_status())."""
+        import torch
+        n = self.front.store_size()
+        total, max_rows = self.front.export_plan(0, n)
+        self._stage = self._grown(self._stage, (total + 15) & ~15)
+        self.front.export_keyframes_device(0, n, self._stage.data_ptr(), total)
+        rec = torch.tensor([total, max_rows, n, self.cols], dtype=torch.int64).to(self.device)
+        if n:
+            rec[3] = self._stage[32: 32 + 32 * n].view(torch.int32).view(n, 8)[:, 2].max()      # sf_kfblob_entry.cols
+        recs = torch.zeros(self.world * 4, dtype=torch.int64, device=self.device)
+        self.td.all_gather_into_tensor(recs, rec, group=self.group)
+        recs = [[int(v) for v in row] for row in recs.view(self.world, 4).tolist()]      # the host wait
+        self.waits += 1
+        cap = (max(r[0] for r in recs) + 15) & ~15
+        self._send = self._grown(self._send, cap)
+        self._recv = self._grown(self._recv, self.world * cap)
+        send, recv = self._send[:cap], self._recv[: self.world * cap]
+        send[:total].copy_(self._stage[:total], non_blocking=True)
+        self.td.all_gather_into_tensor(recv, send, group=self.group)
+        placed = []
+        for r, (r_total, r_max_rows, r_n, r_cols) in enumerate(recs):
+            first = self.main.import_keyframes_device(recv[r * cap:].data_ptr(), r_total, r_n, r_max_rows, r_cols)
+            if check:
+                self.main.wire_status()
+                self.waits += 1
+            placed.append((first, r_n))
+        self.front.store_clear()
+        return placed
+
+
 def torch_int64():
     import torch
     return torch.int64

@@ -154,6 +154,10 @@ def load():
         "sf_netvlad_infer_device": (C.c_int, [vp, vp, i32, i32, vp, i32]),
         "sf_netvlad_infer_batch_device": (C.c_int, [vp, vp, i32, i32, i32, vp, i32]),
         "sf_store_size": (C.c_int, [vp, P(i32)]),
+        "sf_store_export_plan": (C.c_int, [vp, i32, i32, P(C.c_uint64), P(i32)]),
+        "sf_store_export_keyframes_device": (C.c_int, [vp, i32, i32, vp, C.c_uint64]),
+        "sf_store_import_keyframes_device": (C.c_int, [vp, vp, C.c_uint64, i32, i32, i32, P(i32)]),
+        "sf_store_wire_status": (C.c_int, [vp, P(i32)]),
         "sf_store_clear": (C.c_int, [vp]),
         "sf_estimate_transform": (C.c_int, [vp, P(_abi.Features), P(_abi.Features), vp]),
         "sf_estimate_transform_batch": (C.c_int, [vp, P(_abi.Features), P(_abi.Features), i32, vp]),
@@ -291,6 +295,7 @@ EXPORTED = [
     "sf_detect_corners_masked_device", "sf_detect_fast_masked_device", "sf_extract_keyframe_depth_device",
     "sf_get_features_and_descriptor_depth", "sf_get_features_and_descriptor_depth_batch_device",
     "sf_add_keyframes_depth_batch_device",
+    "sf_store_export_plan", "sf_store_export_keyframes_device", "sf_store_import_keyframes_device", "sf_store_wire_status",
 ]
 
 
@@ -1128,6 +1133,72 @@ class SeparatorFinder:
 
     def store_clear(self):
         self._check(self._L.sf_store_clear(self._h))
+
+    # -- store slots as bytes (include/sepfinder.h: sf_kfblob_header) ---------------------------------
+    def export_plan(self, first_slot, n):
+        """sf_store_export_plan: (total bytes, largest row count) of the blob of slots [first_slot, first_slot + n); waits
+        for the stream."""
+        total, max_rows = C.c_uint64(), C.c_int32()
+        self._check(self._L.sf_store_export_plan(self._h, int(first_slot), int(n), C.byref(total), C.byref(max_rows)))
+        return total.value, max_rows.value
+
+    def export_keyframes_device(self, first_slot, n, d_blob, cap_bytes):
+        """sf_store_export_keyframes_device: the blob of slots [first_slot, first_slot + n) into device memory (a raw,
+        16-byte aligned pointer and its length); asynchronous on the handle's stream.  A blob that does not fit is
+        reported by wire_status, not written."""
+        self._check(self._L.sf_store_export_keyframes_device(self._h, int(first_slot), int(n), C.c_void_p(d_blob),
+                                                             int(cap_bytes)))
+
+    def import_keyframes_device(self, d_blob, nbytes, n, max_rows, cols):
+        """sf_store_import_keyframes_device: appends the n keyframes of the blob in device memory (a raw, 16-byte aligned
+        pointer and its length); asynchronous, always n slots.  Returns the first slot; wire_status says what was refused."""
+        first = C.c_int32()
+        self._check(self._L.sf_store_import_keyframes_device(self._h, C.c_void_p(d_blob), int(nbytes), int(n), int(max_rows),
+                                                             int(cols), C.byref(first)))
+        return first.value
+
+    def wire_status(self, check=True):
+        """sf_store_wire_status: waits for the stream; [bits, emptied slots, first emptied keyframe or -1, 0] of the most
+        recent export or import (bits: _abi.WIRE_*).  check: raise SepfinderError (SF_ERANGE) when a bit is set."""
+        out = (C.c_int32 * 4)()
+        rc = self._L.sf_store_wire_status(self._h, out)
+        if check or rc not in (_abi.SF_OK, _abi.SF_ERANGE):
+            self._check(rc)
+        return list(out)
+
+    def _wire_staging(self, nbytes):
+        import torch
+        return torch.empty(max(int(nbytes), 32), dtype=torch.uint8, device=torch.device("cuda:%d" % self.device))
+
+    def export_keyframes(self, first_slot, n):
+        """Slots [first_slot, first_slot + n) as the bytes of one blob: what a robot sends for a GetFeatsAndDesc request.
+        Staged through a torch tensor on the handle's device."""
+        total, _ = self.export_plan(first_slot, n)
+        t = self._wire_staging(total)
+        self.export_keyframes_device(first_slot, n, t.data_ptr(), total)
+        self.wire_status()
+        return t[:total].cpu().numpy().tobytes()
+
+    def import_keyframes(self, blob, check=True):
+        """Appends the keyframes of a blob received as bytes; n, max_rows and the descriptor width are read from its header
+        and table HERE, on the host, and checked again on the device.  Returns (first slot, n); check: raise when the
+        device refused the header or an entry (the slots exist either way, empty)."""
+        import torch
+        raw = np.frombuffer(bytes(blob), np.uint8)
+        if raw.size < 32:
+            raise ValueError("a keyframe blob has at least 32 bytes, not %d" % raw.size)
+        hdr = raw[:32].view(_abi.KFBLOB_HEADER_DTYPE)[0]
+        n, max_rows = int(hdr["n_keyframes"]), int(hdr["max_rows"])
+        if not 0 <= n <= 65535 or raw.size < 32 + 32 * n or max_rows < 0:
+            raise ValueError("keyframe blob of %d bytes states %d keyframes of up to %d rows" % (raw.size, n, max_rows))
+        table = raw[32: 32 + 32 * n].view(_abi.KFBLOB_ENTRY_DTYPE)
+        cols = int(table["cols"].max()) if n else max(1, self.params.desc_bytes)
+        t = self._wire_staging(raw.size)
+        t[:raw.size].copy_(torch.from_numpy(raw.copy()))
+        torch.cuda.current_stream(t.device).synchronize()      # (the handle's stream is not torch's)
+        first = self.import_keyframes_device(t.data_ptr(), raw.size, n, max_rows, cols)
+        self.wire_status(check=check)       # (waits: the staging tensor may go)
+        return first, n
 
     # -- verification -----------------------------------------------------------------------------
     def estimate_transform(self, f_from, f_to):
