@@ -18,6 +18,7 @@
 // ~60 fp64 values are live per lane, so the kernels that include this body are built for 2 workgroups per CU.
 #include "sf_device_math.hpp"
 #include "sf_internal.hpp"
+#include "sf_match_device.hpp"
 #include "sf_pnp_math.hpp"
 
 namespace {
@@ -630,31 +631,13 @@ k_merge_directions_ba(StoreView st, const int32_t* __restrict__ pair_from, const
       a.inliers = n_ba;
     } else {
       a.inliers = uni;
-      if (!b.is_null) {
-        float inv[12];
-        sfd::rigid_inverse_canon(b.T, inv);
-        if (a.is_null) {
-#pragma unroll
-          for (int i = 0; i < 12; ++i) a.T[i] = inv[i];
-          a.is_null = 0;
-          a.var = b.var;
-          a.var_ang = b.var_ang;
-        } else {
-          float mid[12];
-          sfd::interpolate_half_canon(a.T, inv, mid);
-#pragma unroll
-          for (int i = 0; i < 12; ++i) a.T[i] = mid[i];
-          a.var = (a.var + b.var) / 2.0;
-          a.var_ang = (a.var_ang + b.var_ang) / 2.0;
-        }
-      }
+      merge_backward_pose(a, b);
     }
     fwd[pair] = a;
   }
   __syncthreads();
   if (misc[2]) ba_body(st, sF, sT, pts, cidx, ones, n_ba, fwd[pair], P, smem_raw + sf_merge_ba_head_bytes(kcap));
-  if (extra_3dof && tid == 0 && !fwd[pair].is_null)
-    for (int t = 0; t < extra_3dof; ++t) sfd::to3dof_canon(fwd[pair].T);
+  if (extra_3dof && tid == 0) pass_to3dof(fwd[pair], extra_3dof);
 }
 
 }  // namespace
@@ -663,29 +646,18 @@ size_t sf_ba_lds_bytes(int kcap) {
   return (size_t)kcap * (24 + 24 + 12 + 12) + 128 * 8 + 2 * 32 * 8 + 16 * 4;
 }
 
-// (both launchers of the stage pipeline end here when both options are on)
+// (the stage pipeline's estimate ends here when both options are on: sf_launch_estimate)
 int sf_launch_merge_directions_ba(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass,
                                   bool pnp, const uint8_t* mask_f, const uint8_t* mask_b) {
   const size_t lds = sf_merge_ba_head_bytes(st.kcap) + sf_ba_lds_bytes(st.kcap);
   if (lds > 160 * 1024) return sf_fail(c, SF_ERANGE, "bundle adjustment of both directions needs %zu B of LDS (> 160 KiB)", lds);
-  if (!c->merge_ba_attr_set) {
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_merge_directions_ba<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_merge_directions_ba<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    c->merge_ba_attr_set = true;
-  }
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  const int32_t* list = (const int32_t*)(pass == 1 ? c->w->list1.p : c->w->list3.p);
-  const int32_t* counter = counters + (pass == 1 ? 0 : 2);
-  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p);
-  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p);
-  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
-  const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
-  const uint8_t* guided_flag = pass == 2 ? (const uint8_t*)c->w->flags.p : nullptr;
-  if (pnp)
-    hipLaunchKernelGGL(k_merge_directions_ba<true>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, list, counter,
-                       corr, hdr, guided_flag, ps, (const PassState*)c->w->pass_back.p, mask_f, mask_b, end_3dof, c->dparams);
-  else
-    hipLaunchKernelGGL(k_merge_directions_ba<false>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, list, counter,
-                       corr, hdr, guided_flag, ps, (const PassState*)c->w->pass_back.p, mask_f, mask_b, end_3dof, c->dparams);
-  return SF_OK;
+  const PassBufs b = sf_pass_bufs(c, pass, pass == 1 ? 1 : 3);
+  return sf_with_bool(pnp, [&](auto PNP) {
+    const auto kern = k_merge_directions_ba<decltype(PNP)::value>;
+    const int rc = sf_dyn_lds(c, kern, lds);
+    if (rc != SF_OK) return rc;
+    hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, b.list, b.counter, b.corr, b.hdr,
+                       b.guided_flag, b.ps, c->w->back(), mask_f, mask_b, b.end_3dof, c->dparams);
+    return (int)SF_OK;
+  });
 }

@@ -321,6 +321,8 @@ k_gftt_select(const unsigned long long* __restrict__ keys, int n, int w, int cel
 // these integers -- only tabulated per row offset (span[dy] = largest |dx| inside the disc).  Within the 64 candidates
 // of a step the lanes that are still standing take their turn in list order and knock out the later ones.
 constexpr int GFTT_MAX_RADIUS = 64;
+// the largest taken-corner bitmap k_gftt_select_lds keeps in dynamic LDS (its static `span` counts against the CU's 160 KB too)
+constexpr size_t GFTT_SELECT_LDS_MAX = 150 * 1024;
 __global__ void __launch_bounds__(256)
 k_gftt_select_lds(const unsigned long long* __restrict__ keys, int n, int w, int h, int wpr, float md2, int radius,
                   int max_corners, sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out, float kp_size,
@@ -461,15 +463,6 @@ int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_
   return SF_OK;
 }
 
-// k_gftt_select_lds may ask for up to 150 KB of dynamic LDS: said once per handle
-int gftt_select_lds_attr(sf_context* c) {
-  if (!c->gf_select_attr) {
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_gftt_select_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    c->gf_select_attr = true;
-  }
-  return SF_OK;
-}
-
 }  // namespace
 
 // Launch sequence on the handle's stream.  The candidate count crosses to the host once (the sort is sized by it).
@@ -488,8 +481,8 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
   const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
   const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
   const float md2 = (float)(min_distance * min_distance);
-  if (bm_bytes <= 150 * 1024 && radius <= GFTT_MAX_RADIUS) {
-    if ((rc = gftt_select_lds_attr(c)) != SF_OK) return rc;
+  if (bm_bytes <= GFTT_SELECT_LDS_MAX && radius <= GFTT_MAX_RADIUS) {
+    if ((rc = sf_dyn_lds(c, k_gftt_select_lds, bm_bytes, GFTT_SELECT_LDS_MAX)) != SF_OK) return rc;
     hipLaunchKernelGGL(k_gftt_select_lds, dim3(1), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, n,
                        width, height, wpr, md2, radius, max_corners, d_kpts_out, cap, F.n_single, (float)c->gftt.block_size);
   } else {
@@ -521,7 +514,7 @@ int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_
   const int wpr = (width + 31) / 32;
   const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
   const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
-  if (bm_bytes > 150 * 1024 || radius > GFTT_MAX_RADIUS)
+  if (bm_bytes > GFTT_SELECT_LDS_MAX || radius > GFTT_MAX_RADIUS)
     return sf_fail(c, SF_ERANGE, "batched corner detection: %d x %d image does not fit the LDS selection bitmap", width, height);
   SfDetectorWork F;
   int rc;
@@ -532,7 +525,7 @@ int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_
   if ((rc = sf_sort_keys_segmented_desc(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img,
                                         F.seg_begin, F.seg_end, 0, 64)) != SF_OK)
     return rc;
-  if ((rc = gftt_select_lds_attr(c)) != SF_OK) return rc;
+  if ((rc = sf_dyn_lds(c, k_gftt_select_lds, bm_bytes, GFTT_SELECT_LDS_MAX)) != SF_OK) return rc;
   hipLaunchKernelGGL(k_gftt_select_lds, dim3(n_img), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, 0,
                      width, height, wpr, (float)(min_distance * min_distance), radius, max_corners, d_kpts_out, cap, d_n_out,
                      (float)c->gftt.block_size, (const unsigned*)F.count, F.key_cap);

@@ -996,68 +996,34 @@ static size_t sf_guided_tp_lds_bytes(int kcap, int n_cells) {
   return (size_t)(kcap + 16 + 2 * n_cells + 1 + 3 + 4 * kcap) * sizeof(int);
 }
 
-// Vis/CorGuessMatchToProjection = true: k_guided_tp in place of k_guided (same inputs, same outputs)
-template <int W, bool L2, bool U8 = false>
-static int launch_guided_tp(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, size_t lds) {
-  if (lds > 64 * 1024)   // (K > ~3 000 features: above the default dynamic LDS limit; never at the bench's K = 500)
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_guided_tp<W, L2, U8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((k_guided_tp<W, L2, U8>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                     (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p, (uint32_t*)c->w->corr2.p,
-                     (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, (int32_t*)c->w->counters.p + 2, c->dparams);
-  return SF_OK;
-}
-
-static int sf_launch_guided_tp(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
-  const size_t lds = sf_guided_tp_lds_bytes(st.kcap, c->dparams.grid_gx * c->dparams.grid_gy);
-  if (lds > 160 * 1024)
-    return sf_fail(c, SF_ERANGE, "guess_match_to_projection: %d features per keyframe need %zu B of LDS (> 160 KiB)",
-                   st.kcap, lds);
-  sf_prof_begin(c, SF_K_GUIDED_TP);
-  int rc;
-  if (c->params.desc_type == 2)         // uint8 rows, L2: 32 dwords
-    rc = launch_guided_tp<32, true, true>(c, st, d_from, d_to, n, lds);
-  else if (c->params.desc_type == 1)
-    rc = st.w == 64 ? launch_guided_tp<64, true>(c, st, d_from, d_to, n, lds) : launch_guided_tp<128, true>(c, st, d_from, d_to, n, lds);
-  else
-    rc = st.w == 8 ? launch_guided_tp<8, false>(c, st, d_from, d_to, n, lds) : launch_guided_tp<16, false>(c, st, d_from, d_to, n, lds);
-  sf_prof_end(c, SF_K_GUIDED_TP);
+// k_guided<W, L2, U8>, or with Vis/CorGuessMatchToProjection = true k_guided_tp<W, L2, U8> in its place: same inputs (the
+// pass-1 states), same outputs (pass 2's list, header, state, flag and work list)
+template <int W, bool L2, bool U8>
+static int launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, size_t lds, bool tp) {
+  const Workspace& w = *c->w;
+  const auto kern = tp ? k_guided_tp<W, L2, U8> : k_guided<W, L2, U8>;
+  const int rc = sf_dyn_lds(c, kern, lds);       // (k_guided from K ~ 1 600 features, k_guided_tp from ~ 3 000)
   if (rc != SF_OK) return rc;
-  SF_HIP(c, hipGetLastError());
+  hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, w.pass(1), w.pass(2), w.guided_flags(),
+                     w.corr(2), w.hdr(2), w.list(3), w.counter(3), c->dparams);
   return SF_OK;
 }
 
 int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   if (n <= 0) return SF_OK;
-  if (c->dparams.guess_match_to_projection) return sf_launch_guided_tp(c, st, d_from, d_to, n);
+  const bool tp = c->dparams.guess_match_to_projection != 0;
   const int nc = c->dparams.grid_gx * c->dparams.grid_gy;
-  const size_t lds = sf_guided_lds_bytes(st.kcap, nc);
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  sf_prof_begin(c, SF_K_GUIDED);
-  if (c->params.desc_type == 2) {       // uint8 rows, L2: 32 dwords
-    hipLaunchKernelGGL((k_guided<32, true, true>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                       (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
-                       (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2, c->dparams);
-  } else if (c->params.desc_type == 1) {
-    if (st.w == 64)
-      hipLaunchKernelGGL((k_guided<64, true>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                         (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
-                         (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2, c->dparams);
-    else
-      hipLaunchKernelGGL((k_guided<128, true>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                         (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
-                         (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2, c->dparams);
-  } else if (st.w == 8) {
-    hipLaunchKernelGGL(k_guided<8>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                       (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
-                       (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2,
-                       c->dparams);
-  } else {
-    hipLaunchKernelGGL(k_guided<16>, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                       (const PassState*)c->w->pass1.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
-                       (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (int32_t*)c->w->list3.p, counters + 2,
-                       c->dparams);
-  }
-  sf_prof_end(c, SF_K_GUIDED);
+  const size_t lds = tp ? sf_guided_tp_lds_bytes(st.kcap, nc) : sf_guided_lds_bytes(st.kcap, nc);
+  if (tp && lds > 160 * 1024)
+    return sf_fail(c, SF_ERANGE, "guess_match_to_projection: %d features per keyframe need %zu B of LDS (> 160 KiB)",
+                   st.kcap, lds);
+  const int kid = tp ? SF_K_GUIDED_TP : SF_K_GUIDED;
+  sf_prof_begin(c, kid);
+  const int rc = sf_with_desc(c->params.desc_type, st.w, [&](auto W, auto L2, auto U8) {
+    return launch_guided<W(), L2(), U8()>(c, st, d_from, d_to, n, lds, tp);
+  });
+  sf_prof_end(c, kid);
+  if (rc != SF_OK) return rc;
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }
@@ -1065,7 +1031,7 @@ int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const i
 int sf_launch_finalize(sf_context* c, int n, sf_result* d_out) {
   if (n <= 0) return SF_OK;
   hipLaunchKernelGGL(k_finalize, dim3((n + SF_BLOCK - 1) / SF_BLOCK), dim3(SF_BLOCK), 0, c->stream, n,
-                     (const PassState*)c->w->pass1.p, (const PassState*)c->w->pass2.p, (const uint8_t*)c->w->flags.p, d_out);
+                     c->w->pass(1), c->w->pass(2), c->w->guided_flags(), d_out);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }

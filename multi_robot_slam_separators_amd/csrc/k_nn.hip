@@ -1315,10 +1315,8 @@ static int nn_filter_launch(sf_context* c, const NnShape& sh, NnFilterBufs& fb, 
                        colc, gx, gy, tps, fb.cand, count, fb.cap, count_next);
     c->w->nn_count_primed = true;                 // (this launch zeroes the other block for the next one)
   } else if (kdims >= 256) {
-    if (!c->nn_t256_attr) {
-      SF_HIP(c, hipFuncSetAttribute((const void*)k_nn_filter_f16_t256, hipFuncAttributeMaxDynamicSharedMemorySize, NN256_LDS));
-      c->nn_t256_attr = true;
-    }
+    const int rc = sf_dyn_lds(c, k_nn_filter_f16_t256, NN256_LDS);
+    if (rc != SF_OK) return rc;
     const int gx256 = (n_r_pad + 255) / 256, gy256 = (n_l_pad + 255) / 256;
     hipLaunchKernelGGL(k_nn_filter_f16_t256, dim3(gx256 * gy256), dim3(512), NN256_LDS, c->stream, A16, B16, rowc, colc,
                        pitch16, kdims, gx256, gy256, n_l_pad, n_r_pad, fb.cand, count, fb.cap);

@@ -723,8 +723,7 @@ k_pnp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __rest
                                      guided_flag != nullptr && guided_flag[pair] != 0);
   (void)tail;      // (myRegistrationVis.cpp:1192-1370, the adjustment of this estimate: k_ba_pass, its own launch)
   // myRegistration.cpp:269-276, and for pass 1 the application its result meets as the guess of pass 2 (:245-248)
-  if (extra_3dof && threadIdx.x == 0 && !pass[pair].is_null)
-    for (int t = 0; t < extra_3dof; ++t) sfd::to3dof_canon(pass[pair].T);
+  if (extra_3dof && threadIdx.x == 0) pass_to3dof(pass[pair], extra_3dof);
 }
 
 // Vis/ForwardEstOnly = false with the PnP estimator: the two directions' estimates of a pass merged as
@@ -763,93 +762,11 @@ k_merge_directions_pnp(StoreView st, const int32_t* __restrict__ pair_from, cons
   const PassState b = back[pair];
   a.inliers = uni;
   a.matches = uni_m;
-  if (!b.is_null) {
-    float inv[12];
-    sfd::rigid_inverse_canon(b.T, inv);
-    if (a.is_null) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) a.T[i] = inv[i];
-      a.is_null = 0;
-      a.var = b.var;
-      a.var_ang = b.var_ang;
-    } else {
-      float mid[12];
-      sfd::interpolate_half_canon(a.T, inv, mid);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) a.T[i] = mid[i];
-      a.var = (a.var + b.var) / 2.0;
-      a.var_ang = (a.var_ang + b.var_ang) / 2.0;
-    }
-  }
-  if (!a.is_null)
-    for (int t = 0; t < extra_3dof; ++t) sfd::to3dof_canon(a.T);
+  merge_backward_pose(a, b);
+  pass_to3dof(a, extra_3dof);
   fwd[pair] = a;
 }
 
 }  // namespace
 
 size_t sf_pnp_lds_bytes(int kcap, int iterations) { return sf_pnp_lds_bytes_dev(kcap, iterations); }
-
-int sf_launch_pnp(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass) {
-  if (n <= 0) return SF_OK;
-  const bool ba = c->dparams.bundle_adjustment != 0;
-  // (the adjustment is a launch of its own behind the estimate: sf_launch_ba_pass; both directions WITH the adjustment:
-  //  plain estimates, then k_merge_directions_ba adjusts over the union)
-  const size_t lds = (sf_pnp_lds_bytes(st.kcap, c->dparams.iterations) + 15) & ~(size_t)15;
-  if (lds > 160 * 1024) return sf_fail(c, SF_ERANGE, "PnP workgroup needs %zu B of LDS (> 160 KiB)", lds);
-  const bool bidir = c->dparams.bidirectional != 0;
-  bool& attr = c->pnp_attr_set;
-  if (!attr) {   // per handle = per device
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_pnp<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_pnp<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  const int32_t* list = (const int32_t*)(pass == 1 ? c->w->list1.p : c->w->list3.p);
-  const int32_t* counter = counters + (pass == 1 ? 0 : 2);
-  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p);
-  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p);
-  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
-  const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
-  // (pass 1 always matches globally; pass 2's correspondences are the guided matcher's where its flag says so)
-  const uint8_t* guided_flag = pass == 2 ? (const uint8_t*)c->w->flags.p : nullptr;
-  uint8_t *mask_f = nullptr, *mask_b = nullptr;
-  if (bidir) {
-    int rc;
-    const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->w->dir_mask, 2 * mb)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->w->pass_back, (size_t)n * sizeof(PassState))) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->w->dir_mask.p;
-    mask_b = mask_f + mb;
-    SF_HIP(c, hipMemsetAsync(mask_f, 0, 2 * mb, c->stream));
-  } else if (ba) {      // the estimate's inlier set, one byte per "from" feature: what the adjustment's launch rebuilds its words from
-    int rc;
-    const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->w->dir_mask, mb)) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->w->dir_mask.p;
-    SF_HIP(c, hipMemsetAsync(mask_f, 0, mb, c->stream));
-  }
-  const int kid = pass == 1 ? SF_K_RANSAC1 : SF_K_RANSAC2;
-  sf_prof_begin(c, kid);
-  auto launch = [&](auto kern, PassState* out, uint8_t* mask, int extra) {
-    hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, list, counter, corr, hdr, out, extra,
-                       c->dparams, mask, guided_flag);
-  };
-  if (ba && !bidir) launch(k_pnp<0>, ps, mask_f, 0);      // (Reg/Force3DoF's end-of-pass application: behind the adjustment)
-  else if (!bidir) launch(k_pnp<0>, ps, nullptr, end_3dof);
-  else {
-    launch(k_pnp<0>, ps, mask_f, 0);
-    launch(k_pnp<1>, (PassState*)c->w->pass_back.p, mask_b, 0);
-    if (ba) {
-      const int rc = sf_launch_merge_directions_ba(c, st, d_from, d_to, n, pass, true, mask_f, mask_b);
-      if (rc != SF_OK) return rc;
-    } else
-    hipLaunchKernelGGL(k_merge_directions_pnp, dim3(n), dim3(64), 0, c->stream, st, d_from, d_to, list, counter, corr, hdr,
-                       guided_flag, ps, (const PassState*)c->w->pass_back.p, (const uint8_t*)mask_f, (const uint8_t*)mask_b,
-                       c->dparams.min_inliers, end_3dof);
-  }
-  sf_prof_end(c, kid);
-  SF_HIP(c, hipGetLastError());
-  if (ba && !bidir) return sf_launch_ba_pass(c, st, d_from, d_to, n, pass, pass == 1 ? 1 : 3, mask_f, nullptr, false, nullptr);
-  return SF_OK;
-}

@@ -759,13 +759,6 @@ __device__ __forceinline__ void ransac_body(const StoreView& st, int pair, int s
   SF_TRACE_MARK(P, pair, trace_base + 5);
 }
 
-// The end-of-pass to3DoF of myRegistration.cpp:269-276 and, for pass 1, the one its result meets as the guess of
-// pass 2 (:245-248): `times` applications by the thread that wrote the pass state.
-__device__ inline void pass_to3dof(PassState& ps, int times) {
-  if (ps.is_null) return;
-  for (int t = 0; t < times; ++t) sfd::to3dof_canon(ps.T);
-}
-
 template <int DIR>
 __global__ void __launch_bounds__(SF_BLOCK, 4)
 k_ransac(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
@@ -797,24 +790,7 @@ k_merge_directions(const int32_t* __restrict__ list, const int32_t* __restrict__
   const PassState b = back[pair];
   a.inliers = uni;
   a.matches = a.matches > b.matches ? a.matches : b.matches;
-  if (!b.is_null) {
-    float inv[12];
-    sfd::rigid_inverse_canon(b.T, inv);
-    if (a.is_null) {
-#pragma unroll
-      for (int i = 0; i < 12; ++i) a.T[i] = inv[i];
-      a.is_null = 0;
-      a.var = b.var;
-      a.var_ang = b.var_ang;
-    } else {
-      float mid[12];
-      sfd::interpolate_half_canon(a.T, inv, mid);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) a.T[i] = mid[i];
-      a.var = (a.var + b.var) / 2.0;
-      a.var_ang = (a.var_ang + b.var_ang) / 2.0;
-    }
-  }
+  merge_backward_pose(a, b);
   pass_to3dof(a, extra_3dof);
   fwd[pair] = a;
 }
@@ -826,63 +802,3 @@ size_t sf_ransac_lds_bytes(int kcap, int iterations) {
   return sf_ransac_lds_bytes_dev(kcap);
 }
 
-int sf_launch_ransac(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass) {
-  if (n <= 0) return SF_OK;
-  const bool ba = c->dparams.bundle_adjustment != 0;
-  // (the adjustment is a launch of its own behind the estimate: sf_launch_ba_pass; both directions WITH the adjustment:
-  //  plain estimates, then k_merge_directions_ba adjusts over the union)
-  const size_t lds = (sf_ransac_lds_bytes(st.kcap, c->dparams.iterations) + 15) & ~(size_t)15;
-  if (lds > 160 * 1024) return sf_fail(c, SF_ERANGE, "RANSAC workgroup needs %zu B of LDS (> 160 KiB)", lds);
-  const bool bidir = c->dparams.bidirectional != 0;
-  bool& attr = c->ransac_attr_set;
-  if (!attr) {   // per handle = per device
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_ransac<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_ransac<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  const int32_t* list = (const int32_t*)(pass == 1 ? c->w->list1.p : c->w->list3.p);
-  const int32_t* counter = counters + (pass == 1 ? 0 : 2);
-  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
-  // Reg/Force3DoF: the end-of-pass application, and for pass 1 the one its result meets as the guess of pass 2
-  const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
-  uint8_t *mask_f = nullptr, *mask_b = nullptr;
-  if (bidir) {
-    int rc;
-    const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->w->dir_mask, 2 * mb)) != SF_OK) return rc;
-    if ((rc = sf_buf_reserve(c, c->w->pass_back, (size_t)n * sizeof(PassState))) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->w->dir_mask.p;
-    mask_b = mask_f + mb;
-    SF_HIP(c, hipMemsetAsync(mask_f, 0, 2 * mb, c->stream));
-  } else if (ba) {      // the estimate's inlier set, one byte per "from" feature: what the adjustment's launch rebuilds its words from
-    int rc;
-    const size_t mb = (size_t)n * st.kcap;
-    if ((rc = sf_buf_reserve(c, c->w->dir_mask, mb)) != SF_OK) return rc;
-    mask_f = (uint8_t*)c->w->dir_mask.p;
-    SF_HIP(c, hipMemsetAsync(mask_f, 0, mb, c->stream));
-  }
-  const int kid = pass == 1 ? SF_K_RANSAC1 : SF_K_RANSAC2;
-  sf_prof_begin(c, kid);
-  auto launch = [&](auto kern, PassState* out, uint8_t* mask, int extra) {
-    hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, list, counter,
-                       (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p),
-                       (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p), out, mask, extra, c->dparams);
-  };
-  if (ba && !bidir) launch(k_ransac<0>, ps, mask_f, 0);     // (Reg/Force3DoF's end-of-pass application: behind the adjustment)
-  else if (!bidir) launch(k_ransac<0>, ps, nullptr, end_3dof);
-  else {
-    launch(k_ransac<0>, ps, mask_f, 0);
-    launch(k_ransac<1>, (PassState*)c->w->pass_back.p, mask_b, 0);
-    if (ba) {
-      const int rc = sf_launch_merge_directions_ba(c, st, d_from, d_to, n, pass, false, mask_f, mask_b);
-      if (rc != SF_OK) return rc;
-    } else
-    hipLaunchKernelGGL(k_merge_directions, dim3(n), dim3(64), 0, c->stream, list, counter, ps,
-                       (const PassState*)c->w->pass_back.p, (const uint8_t*)mask_f, (const uint8_t*)mask_b, st.kcap, end_3dof);
-  }
-  sf_prof_end(c, kid);
-  SF_HIP(c, hipGetLastError());
-  if (ba && !bidir) return sf_launch_ba_pass(c, st, d_from, d_to, n, pass, pass == 1 ? 1 : 3, mask_f, nullptr, false, nullptr);
-  return SF_OK;
-}

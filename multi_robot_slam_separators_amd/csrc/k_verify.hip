@@ -340,16 +340,12 @@ k_chain_est(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* 
 template <int W, int NQ, bool WIDE = false>
 int launch_fused(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, sf_result* d_out,
                  size_t lds, int tail_off) {
-  bool& attr_set = c->fused_attr[W == 16][NQ == 0][WIDE];   // one flag per instantiation
-  if (lds > 64 * 1024 && !attr_set) {
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_verify_fused<W, NQ, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_verify_fused<W, NQ, WIDE>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to,
-                     (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (uint32_t*)c->w->corr2.p,
-                     (CorrHeader*)c->w->hdr2.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p, d_out, c->dparams,
-                     tail_off, c->pair_src);
+  const Workspace& w = *c->w;
+  const int rc = sf_dyn_lds(c, k_verify_fused<W, NQ, WIDE>, lds);
+  if (rc != SF_OK) return rc;
+  hipLaunchKernelGGL((k_verify_fused<W, NQ, WIDE>), dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, w.corr(1),
+                     w.hdr(1), w.pass(1), w.corr(2), w.hdr(2), w.pass(2), w.guided_flags(), d_out, c->dparams, tail_off,
+                     c->pair_src);
   return SF_OK;
 }
 
@@ -529,44 +525,108 @@ int sf_launch_ba_pass(sf_context* c, StoreView st, const int32_t* d_from, const 
   if (n <= 0) return SF_OK;
   if (sf_ba_lds_bytes(st.kcap) > 160 * 1024)
     return sf_fail(c, SF_ERANGE, "bundle adjustment needs %zu B of LDS (> 160 KiB)", sf_ba_lds_bytes(st.kcap));
-  const bool pnp = c->dparams.estimation_type == 1;
-  const int nw = c->ba_nw;
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  const int32_t* list = (const int32_t*)(list_sel == 1 ? c->w->list1.p : c->w->list3.p);
-  const int32_t* counter = counters + (list_sel == 1 ? 0 : 2);
-  const uint32_t* corr = (const uint32_t*)(pass == 1 ? c->w->corr1.p : c->w->corr2.p);
-  const CorrHeader* hdr = (const CorrHeader*)(pass == 1 ? c->w->hdr1.p : c->w->hdr2.p);
-  PassState* ps = (PassState*)(pass == 1 ? c->w->pass1.p : c->w->pass2.p);
-  const int end_3dof = c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0;
+  const PassBufs b = sf_pass_bufs(c, pass, list_sel);
   const bool both = st.kcap > SF_BA_SMALL_CAP;       // (a keyframe cannot give more words than it has features)
   sf_prof_begin(c, SF_K_BA);
-  auto launch = [&](auto kern, int cap, bool& attr) -> int {
+  auto launch = [&](auto kern, int nw, int cap) -> int {
     const size_t lds = sf_ba_lds_bytes(cap);
-    if (lds > 64 * 1024 && !attr) {
-      SF_HIP(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(n), dim3(64 * nw), lds, c->stream, st, d_from, d_to, list, counter, corr, hdr, mask, run,
-                       ps, end_3dof, fin ? 1 : 0, (const PassState*)c->w->pass1.p, (const uint8_t*)c->w->flags.p, d_out,
-                       c->dparams, cap, both ? 1 : 0);
+    const int rc = sf_dyn_lds(c, kern, lds);
+    if (rc != SF_OK) return rc;
+    hipLaunchKernelGGL(kern, dim3(n), dim3(64 * nw), lds, c->stream, st, d_from, d_to, b.list, b.counter, b.corr, b.hdr, mask,
+                       run, b.ps, b.end_3dof, fin ? 1 : 0, c->w->pass(1), c->w->guided_flags(), d_out, c->dparams, cap,
+                       both ? 1 : 0);
     return SF_OK;
   };
-  int rc = SF_OK;
-  bool dummy = true;      // (the SMALL launch's LDS is under 64 KB: no attribute to set)
   const int cap_small = std::min(st.kcap, SF_BA_SMALL_CAP);
-#define SF_BA_CASE(NW_, PNP_)                                                                              \
-  do {                                                                                                     \
-    rc = (c->ba_occ ? c->ba_occ : (PNP_ ? 1 : 2)) == 2 ? launch(k_ba_pass<NW_, PNP_, true, 2>, cap_small, dummy)                          \
-                        : launch(k_ba_pass<NW_, PNP_, true, 1>, cap_small, dummy);                         \
-    if (rc == SF_OK && both) rc = launch(k_ba_pass<NW_, PNP_, false>, st.kcap, c->ba_pass_attr[PNP_][NW_ == 4 ? 2 : NW_ - 1]); \
-  } while (0)
-  if (pnp) { if (nw == 1) SF_BA_CASE(1, true); else if (nw == 2) SF_BA_CASE(2, true); else SF_BA_CASE(4, true); }
-  else { if (nw == 1) SF_BA_CASE(1, false); else if (nw == 2) SF_BA_CASE(2, false); else SF_BA_CASE(4, false); }
-#undef SF_BA_CASE
+  const int rc = sf_with_nw(c->ba_nw, [&](auto NW) {
+    return sf_with_bool(c->dparams.estimation_type == 1, [&](auto PNP) {
+      constexpr int nw = decltype(NW)::value;
+      constexpr bool pnp = decltype(PNP)::value;
+      int rc = (c->ba_occ ? c->ba_occ : (pnp ? 1 : 2)) == 2 ? launch(k_ba_pass<nw, pnp, true, 2>, nw, cap_small)
+                                                             : launch(k_ba_pass<nw, pnp, true, 1>, nw, cap_small);
+      if (rc == SF_OK && both) rc = launch(k_ba_pass<nw, pnp, false>, nw, st.kcap);
+      return rc;
+    });
+  });
   sf_prof_end(c, SF_K_BA);
   if (rc != SF_OK) return rc;
   SF_HIP(c, hipGetLastError());
   return SF_OK;
+}
+
+namespace {
+// The stage pipeline's estimate of one pass, whichever the estimator: the inlier masks the second direction or the
+// adjustment need (one byte per "from" feature, zeroed), the forward estimate, with Vis/ForwardEstOnly = false the backward
+// one and the merge, and with the bundle adjustment its launch -- behind a one-direction estimate sf_launch_ba_pass,
+// behind two k_merge_directions_ba, which adjusts over the union.  An estimator gives `name` and `lds`, its workgroup's
+// dynamic LDS, launch_dir(DIR, out, mask, extra_3dof), its kernel for direction DIR, and launch_merge(mask_f, mask_b).
+template <class Dir, class Merge>
+int estimate_sequence(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass,
+                      const PassBufs& b, const char* name, size_t lds, Dir launch_dir, Merge launch_merge) {
+  if (lds > 160 * 1024) return sf_fail(c, SF_ERANGE, "%s workgroup needs %zu B of LDS (> 160 KiB)", name, lds);
+  const bool ba = c->dparams.bundle_adjustment != 0, bidir = c->dparams.bidirectional != 0;
+  int rc;
+  uint8_t *mask_f = nullptr, *mask_b = nullptr;
+  if (bidir || ba) {
+    const size_t mb = (size_t)n * st.kcap, bytes = bidir ? 2 * mb : mb;
+    if ((rc = sf_buf_reserve(c, c->w->dir_mask, bytes)) != SF_OK) return rc;
+    if (bidir && (rc = sf_buf_reserve(c, c->w->pass_back, (size_t)n * sizeof(PassState))) != SF_OK) return rc;
+    mask_f = c->w->masks();
+    if (bidir) mask_b = mask_f + mb;
+    SF_HIP(c, hipMemsetAsync(mask_f, 0, bytes, c->stream));
+  }
+  sf_prof_begin(c, b.prof);
+  // (with the adjustment Reg/Force3DoF's end-of-pass applications come behind it: k_ba_pass, k_merge_directions_ba)
+  if (!bidir) rc = launch_dir(sf_int<0>{}, b.ps, mask_f, ba ? 0 : b.end_3dof);
+  else if ((rc = launch_dir(sf_int<0>{}, b.ps, mask_f, 0)) == SF_OK &&
+           (rc = launch_dir(sf_int<1>{}, c->w->back(), mask_b, 0)) == SF_OK)
+    rc = ba ? sf_launch_merge_directions_ba(c, st, d_from, d_to, n, pass, c->dparams.estimation_type == 1, mask_f, mask_b)
+            : launch_merge(mask_f, mask_b);
+  sf_prof_end(c, b.prof);
+  if (rc != SF_OK) return rc;
+  SF_HIP(c, hipGetLastError());
+  if (ba && !bidir) return sf_launch_ba_pass(c, st, d_from, d_to, n, pass, pass == 1 ? 1 : 3, mask_f, nullptr, false, nullptr);
+  return SF_OK;
+}
+}  // namespace
+
+int sf_launch_estimate(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass) {
+  if (n <= 0) return SF_OK;
+  const PassBufs b = sf_pass_bufs(c, pass, pass == 1 ? 1 : 3);
+  if (c->dparams.estimation_type == 1) {
+    const size_t lds = (sf_pnp_lds_bytes(st.kcap, c->dparams.iterations) + 15) & ~(size_t)15;
+    return estimate_sequence(
+        c, st, d_from, d_to, n, pass, b, "PnP", lds,
+        [&](auto DIR, PassState* out, uint8_t* mask, int extra) {
+          const auto kern = k_pnp<decltype(DIR)::value>;
+          const int rc = sf_dyn_lds(c, kern, lds);
+          if (rc != SF_OK) return rc;
+          hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, b.list, b.counter, b.corr, b.hdr,
+                             out, extra, c->dparams, mask, b.guided_flag);
+          return (int)SF_OK;
+        },
+        [&](const uint8_t* mask_f, const uint8_t* mask_b) {
+          hipLaunchKernelGGL(k_merge_directions_pnp, dim3(n), dim3(64), 0, c->stream, st, d_from, d_to, b.list, b.counter, b.corr,
+                             b.hdr, b.guided_flag, b.ps, c->w->back(), mask_f, mask_b, c->dparams.min_inliers, b.end_3dof);
+          return (int)SF_OK;
+        });
+  }
+  const size_t lds = (sf_ransac_lds_bytes(st.kcap, c->dparams.iterations) + 15) & ~(size_t)15;
+  return estimate_sequence(
+      c, st, d_from, d_to, n, pass, b, "RANSAC", lds,
+      [&](auto DIR, PassState* out, uint8_t* mask, int extra) {
+        const auto kern = k_ransac<decltype(DIR)::value>;
+        const int rc = sf_dyn_lds(c, kern, lds);
+        if (rc != SF_OK) return rc;
+        hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, b.list, b.counter, b.corr, b.hdr, out,
+                           mask, extra, c->dparams);
+        return (int)SF_OK;
+      },
+      [&](const uint8_t* mask_f, const uint8_t* mask_b) {
+        hipLaunchKernelGGL(k_merge_directions, dim3(n), dim3(64), 0, c->stream, b.list, b.counter, b.ps, c->w->back(), mask_f, mask_b,
+                           st.kcap, b.end_3dof);
+        return (int)SF_OK;
+      });
 }
 
 // The split pipeline (k_match_split + k_chain); applies where the fused kernel does.
@@ -590,18 +650,15 @@ bool sf_split_pnp_applicable(const sf_context* c, const StoreView& st) {
 namespace {
 template <int W, int NW, int PART>
 int launch_chain(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, sf_result* d_out,
-                 size_t lds, int tail_off, const BaHandover& H) {
-  static_assert(PART >= 0 && PART <= 3, "chain_attr has one row per part");
-  bool& attr_set = c->chain_attr[W == 16][PART][NW == 4 ? 2 : NW - 1];
-  if (lds > 64 * 1024 && !attr_set) {
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_chain<W, NW, PART>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  hipLaunchKernelGGL((k_chain<W, NW, PART>), dim3(n), dim3(64 * NW), lds, c->stream, st, d_from, d_to,
-                     (const uint32_t*)c->w->corr1.p, (const CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p,
-                     (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
-                     (const int32_t*)c->w->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams, tail_off, H);
+                 const BaHandover& H) {
+  const int tail_off = (int)fused_tail_offset(c, st, false);
+  const size_t lds = (size_t)tail_off + ((sizeof(FusedTail) + 15) & ~(size_t)15);
+  const Workspace& w = *c->w;
+  const int rc = sf_dyn_lds(c, k_chain<W, NW, PART>, lds);
+  if (rc != SF_OK) return rc;
+  hipLaunchKernelGGL((k_chain<W, NW, PART>), dim3(n), dim3(64 * NW), lds, c->stream, st, d_from, d_to, w.corr(1), w.hdr(1),
+                     w.pass(1), w.corr(2), w.hdr(2), w.pass(2), w.guided_flags(), w.list(1), w.counter(1), d_out, c->dparams,
+                     tail_off, H);
   return SF_OK;
 }
 
@@ -611,62 +668,42 @@ int launch_chain_pnp(sf_context* c, StoreView st, const int32_t* d_from, const i
   const int nc = c->dparams.grid_gx * c->dparams.grid_gy;
   const size_t lds = std::max((sf_pnp_lds_bytes_dev(st.kcap, c->dparams.iterations, NW == 4, NW) + 15) & ~(size_t)15,
                               sf_guided_lds_bytes(st.kcap, nc, NW != 4));
-  bool& attr = c->chain_pnp_attr[W == 16][PART][NW == 4 ? 2 : NW - 1];
-  if (lds > 64 * 1024 && !attr) {
-    SF_HIP(c, hipFuncSetAttribute((const void*)k_chain_pnp<W, PART, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr = true;
-  }
-  int32_t* counters = (int32_t*)c->w->counters.p;
-  hipLaunchKernelGGL((k_chain_pnp<W, PART, NW>), dim3(n), dim3(64 * NW), lds, c->stream, st, d_from, d_to,
-                     (const uint32_t*)c->w->corr1.p, (const CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p,
-                     (uint32_t*)c->w->corr2.p, (CorrHeader*)c->w->hdr2.p, (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p,
-                     (const int32_t*)c->w->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams, H);
+  const Workspace& w = *c->w;
+  const int rc = sf_dyn_lds(c, k_chain_pnp<W, PART, NW>, lds);
+  if (rc != SF_OK) return rc;
+  hipLaunchKernelGGL((k_chain_pnp<W, PART, NW>), dim3(n), dim3(64 * NW), lds, c->stream, st, d_from, d_to, w.corr(1), w.hdr(1),
+                     w.pass(1), w.corr(2), w.hdr(2), w.pass(2), w.guided_flags(), w.list(1), w.counter(1), d_out, c->dparams, H);
   return SF_OK;
 }
 
 template <int PART>
 int launch_chain_part(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, sf_result* d_out,
                       bool pnp, const BaHandover& H) {
-  int rc = SF_OK;
   if (PART == 3 && pnp) return sf_fail(c, SF_EINVAL, "the PnP chain has no three-launch form");
   if (PART != 3) sf_prof_begin(c, SF_K_FUSED);        // (part 3: its caller books the three launches as one interval)
-  if (pnp) {
-   if constexpr (PART != 3) {         // (k_chain_pnp has parts 0 .. 2 only)
-#define SF_CHAIN_PNP_CASE(W_)                                                                            \
-    rc = c->chain_pnp_nw == 1   ? launch_chain_pnp<W_, PART, 1>(c, st, d_from, d_to, n, d_out, H)          \
-         : c->chain_pnp_nw == 2 ? launch_chain_pnp<W_, PART, 2>(c, st, d_from, d_to, n, d_out, H)          \
-                                : launch_chain_pnp<W_, PART, 4>(c, st, d_from, d_to, n, d_out, H)
-    if (st.w == 8) SF_CHAIN_PNP_CASE(8); else SF_CHAIN_PNP_CASE(16);
-#undef SF_CHAIN_PNP_CASE
-   }
-  } else {
-    const int tail_off = (int)fused_tail_offset(c, st, false);
-    const size_t lds_c = (size_t)tail_off + ((sizeof(FusedTail) + 15) & ~(size_t)15);
-#define SF_CHAIN_CASE(W_)                                                                                             \
-    rc = c->chain_nw == 1   ? launch_chain<W_, 1, PART>(c, st, d_from, d_to, n, d_out, lds_c, tail_off, H)            \
-         : c->chain_nw == 2 ? launch_chain<W_, 2, PART>(c, st, d_from, d_to, n, d_out, lds_c, tail_off, H)            \
-                            : launch_chain<W_, 4, PART>(c, st, d_from, d_to, n, d_out, lds_c, tail_off, H)
-    if (st.w == 8) SF_CHAIN_CASE(8); else SF_CHAIN_CASE(16);
-#undef SF_CHAIN_CASE
-  }
+  const int rc = sf_with_w(st.w, [&](auto W) {
+    return sf_with_nw(pnp ? c->chain_pnp_nw : c->chain_nw, [&](auto NW) {
+      constexpr int w = decltype(W)::value, nw = decltype(NW)::value;
+      if constexpr (PART != 3) {         // (k_chain_pnp has parts 0 .. 2 only)
+        if (pnp) return launch_chain_pnp<w, PART, nw>(c, st, d_from, d_to, n, d_out, H);
+      }
+      return launch_chain<w, nw, PART>(c, st, d_from, d_to, n, d_out, H);
+    });
+  });
   if (PART != 3) sf_prof_end(c, SF_K_FUSED);
   if (rc != SF_OK) return rc;
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }
-}  // namespace
 
-namespace {
 // k_chain_est<PASS> over the survivor list: pass 1 reads the first lists, pass 2 the second and finishes the pairs
 template <int PASS>
 int launch_chain_est(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, sf_result* d_out,
                      const BaHandover& H) {
-  int32_t* counters = (int32_t*)c->w->counters.p;
+  const Workspace& w = *c->w;
   hipLaunchKernelGGL((k_chain_est<PASS>), dim3(n), dim3(64), sf_ransac_lds_bytes_dev(SF_EST_CAP), c->stream, st, d_from, d_to,
-                     (const uint32_t*)(PASS == 1 ? c->w->corr1.p : c->w->corr2.p),
-                     (const CorrHeader*)(PASS == 1 ? c->w->hdr1.p : c->w->hdr2.p), (PassState*)c->w->pass1.p,
-                     (PassState*)c->w->pass2.p, (const uint8_t*)c->w->flags.p, (const uint8_t*)H.est2,
-                     (const int32_t*)c->w->list1.p, (const int32_t*)(counters + 0), d_out, c->dparams);
+                     w.corr(PASS), w.hdr(PASS), w.pass(1), w.pass(2), w.guided_flags(), H.est2, w.list(1), w.counter(1), d_out,
+                     c->dparams);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }
@@ -687,31 +724,25 @@ int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, c
   //  the step as a whole is bound by vector instruction issue -- 425 M busy cycles of this kernel + 196 M of the chains +
   //  35 M of the NN kernels per step over 1 024 SIMDs = 0.32-0.36 ms of the 0.43 ms step, profiles/r05w_sq_*.)
   const size_t lds_m = sf_match_lds_bytes(st.kcap, st.w);
-  int32_t* counters = (int32_t*)c->w->counters.p;
+  const Workspace& w = *c->w;
   sf_prof_begin(c, SF_K_MATCH);
-  if (lds_m > 64 * 1024 && !c->split_match_attr[st.w == 16]) {
-    if (st.w == 8)
-      SF_HIP(c, hipFuncSetAttribute((const void*)k_match_split<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    else
-      SF_HIP(c, hipFuncSetAttribute((const void*)k_match_split<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    c->split_match_attr[st.w == 16] = true;
-  }
-#define SF_SPLIT_MATCH(...)                                                                                        \
-  hipLaunchKernelGGL((k_match_split<__VA_ARGS__>), dim3(n), dim3(SF_BLOCK), lds_m, c->stream, st, d_from, d_to,    \
-                     (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p, (CorrHeader*)c->w->hdr2.p, \
-                     (PassState*)c->w->pass2.p, (uint8_t*)c->w->flags.p, (int32_t*)c->w->list1.p, counters + 0, d_out, c->dparams, \
-                     sf_est_mode(c))
   // (shapes measured on the pipelined scan, profiles/r05t_match_split_shapes.txt: 4 tiles / 3 workgroups per CU 22.5 M
   //  pairs/s on the 3D-3D split step, 2 tiles / 4: 22.2, 2 tiles / 3: 21.3, 4 tiles / 2: 21.2; PnP 15.0 / 15.0 / 14.8 / 13.7)
-  if (st.w == 8) SF_SPLIT_MATCH(8); else SF_SPLIT_MATCH(16);
-#undef SF_SPLIT_MATCH
+  int rc = sf_with_w(st.w, [&](auto W) {
+    const auto kern = k_match_split<decltype(W)::value>;
+    const int rc = sf_dyn_lds(c, kern, lds_m);
+    if (rc != SF_OK) return rc;
+    hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds_m, c->stream, st, d_from, d_to, w.corr(1), w.hdr(1), w.pass(1),
+                       w.hdr(2), w.pass(2), w.guided_flags(), w.list(1), w.counter(1), d_out, c->dparams, sf_est_mode(c));
+    return (int)SF_OK;
+  });
   sf_prof_end(c, SF_K_MATCH);
+  if (rc != SF_OK) return rc;
   SF_HIP(c, hipGetLastError());
-  int rc;
   if (narrow_est) {
     if (pnp || c->dparams.bundle_adjustment) return sf_fail(c, SF_EINVAL, "narrow estimates: 3D-3D without bundle adjustment only");
     if ((rc = sf_buf_reserve(c, c->w->dir_mask, (size_t)n)) != SF_OK) return rc;      // (every survivor's byte is written by
-    const BaHandover H = {nullptr, nullptr, (uint8_t*)c->w->dir_mask.p};               //  the middle launch: no memset)
+    const BaHandover H = {nullptr, nullptr, c->w->masks()};                            //  the middle launch: no memset)
     sf_prof_begin(c, SF_K_FUSED);                // (the three launches are one entry of the chain's profiling slot)
     if ((rc = launch_chain_est<1>(c, st, d_from, d_to, n, d_out, H)) == SF_OK &&
         (rc = launch_chain_part<3>(c, st, d_from, d_to, n, d_out, false, H)) == SF_OK)
@@ -724,7 +755,7 @@ int sf_launch_verify_split(sf_context* c, StoreView st, const int32_t* d_from, c
   // bundle adjustment on: [estimate 1] -> adjustment -> [guided matching + estimate 2] -> adjustment + result
   const size_t mb = (size_t)n * st.kcap;
   if ((rc = sf_buf_reserve(c, c->w->dir_mask, 2 * mb + (size_t)n)) != SF_OK) return rc;
-  uint8_t* m1 = (uint8_t*)c->w->dir_mask.p;
+  uint8_t* m1 = c->w->masks();
   const BaHandover H = {m1, m1 + mb, m1 + 2 * mb};
   SF_HIP(c, hipMemsetAsync(m1, 0, 2 * mb + (size_t)n, c->stream));
   if ((rc = launch_chain_part<1>(c, st, d_from, d_to, n, d_out, pnp, H)) != SF_OK) return rc;

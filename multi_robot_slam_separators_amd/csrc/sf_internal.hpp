@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sepfinder.h"
@@ -169,6 +170,18 @@ struct Workspace {
   Buf results;                  // sf_result[n]
   Buf flags;                    // uint8[n] pass2_guided
   bool last_lists_valid = false;   // the last verification left correspondence lists in this workspace
+  // the verification buffers, typed.  sel: work list 1 (the matching's survivors) or 3 (pass 2's); pass: 1 or 2
+  int32_t* list(int sel) const { return (int32_t*)(sel == 1 ? list1 : list3).p; }
+  int32_t* counter(int sel) const { return (int32_t*)counters.p + (sel == 1 ? 0 : 2); }
+  uint32_t* corr(int pass) const { return (uint32_t*)(pass == 1 ? corr1 : corr2).p; }
+  CorrHeader* hdr(int pass) const { return (CorrHeader*)(pass == 1 ? hdr1 : hdr2).p; }
+  PassState* pass(int pass) const { return (PassState*)(pass == 1 ? pass1 : pass2).p; }
+  uint8_t* guided_flags() const { return (uint8_t*)flags.p; }
+  PassState* back() const { return (PassState*)pass_back.p; }
+  uint8_t* masks() const { return (uint8_t*)dir_mask.p; }
+  const int32_t* from() const { return (const int32_t*)pair_from.p; }
+  const int32_t* to() const { return (const int32_t*)pair_to.p; }
+  sf_result* out() const { return (sf_result*)results.p; }
 
   // NN stage and speculative verification
   Buf nn_cand;       // filter path: two 64-byte counter blocks (alternating per launch) + candidate (row, col) pairs + exact distances
@@ -422,29 +435,20 @@ struct sf_context {
   std::vector<uint8_t> nn_taken;
 
   int match_variant = 0;   // 0 = default geometry; see sf_launch_match_global
-  bool ransac_attr_set = false;
-  bool pnp_attr_set = false;
-  bool fused_attr[2][2][2] = {};   // [W == 16][matrix-core matcher][WIDE]: LDS attribute set
-  bool ransac_ba_attr_set = false, pnp_ba_attr_set = false, merge_ba_attr_set = false;
+  std::vector<const void*> dyn_lds_kernels;   // kernels whose dynamic LDS limit this handle has raised (sf_dyn_lds)
   bool debug_corr = false;      // SF_OPT_DEBUG_CORR: the fused kernel also writes lists / headers / states to HBM
   bool fused = true;        // fused per-pair verification kernel (SF_FUSED=0 selects the stage kernels)
   int cu_count = 0;         // compute units of the device (grids sized to the chip); read through sf_cu_count (k_nn.hip), which fills it on first use
-  bool gf_select_attr = false; // k_gftt_select_lds: dynamic LDS attribute set
-  bool nn_t256_attr = false;   // k_nn_filter_f16_t256: dynamic LDS attribute set
   bool split = false;       // SF_FUSED=2: one matching launch + one chain launch over the survivors (k_verify.hip)
   bool split_auto = true;   // SF_OPT_STEP_SPLIT: the split form inside overlapped steps (sf_use_split, sf_verify_host.hip); on again since
                             // round 5 (its matcher is software-pipelined: 23.0 against 22.7 M pairs/s, profiles/r05u_*)
   int split_auto_min = 2048;   // ... for queries of at least this many candidates (SF_STEP_SPLIT_MIN): below, one launch wins
   bool in_overlapped_step = false;   // set around sf_step_issue's body while the steps alternate between two streams
-  bool chain_attr[2][4][3] = {};   // k_chain [W == 16][part 0 .. 3][wavefronts per chain 1 / 2 / 4]: LDS attribute set
   int chain_nw = 4;                // wavefronts per motion-estimation chain of the split forms: 1, 2 (round 5), or 4 = the
                                    // 256-thread workgroup of rounds 2-4 (SF_CHAIN_NW)
   bool chain_narrow_est = SF_CHAIN_NARROW_EST_DEFAULT;   // SF_OPT_CHAIN_NARROW_EST: the 3D-3D split form's estimates on one wavefront
                                    // each, around the wide kernel's guided matching (k_chain_est, k_verify.hip)
-  bool split_match_attr[2] = {};   // k_match_split [W == 16]
-  bool chain_pnp_attr[2][3][3] = {};  // k_chain_pnp [W == 16][part 0 / 1 / 2][wavefronts 1 / 2 / 4]
   int chain_pnp_nw = 2;            // wavefronts per PnP chain (SF_CHAIN_PNP_NW; 2 measured fastest: profiles/r05i_pnp_chain_width.txt)
-  bool ba_pass_attr[2][3] = {};    // k_ba_pass [PnP][wavefronts 1 / 2 / 4]
   int ba_occ = 0;                  // wavefronts per SIMD the SMALL adjustment kernel is compiled for (SF_BA_OCC; 1 = 512 registers,
                                    // no scratch; 2 = 256 registers + 256 B of scratch; 0 = by estimator: PnP 1, 3D-3D 2 -- measured,
                                    // profiles/r05e_ba_occupancy.txt)
@@ -630,10 +634,44 @@ inline int sf_est_mode(const sf_context* c) {
 template <class Kern, class... Extra>
 void sf_launch_pass1(sf_context* c, Kern kern, int nt, size_t lds, StoreView st, const int32_t* d_from, const int32_t* d_to,
                      int n, Extra... extra) {
-  int32_t* counters = (int32_t*)c->w->counters.p;
+  const Workspace& w = *c->w;
   hipLaunchKernelGGL(kern, dim3(n), dim3(nt), lds, c->stream, st, d_from, d_to, c->dparams.nndr, c->dparams.min_inliers,
-                     sf_est_mode(c), extra..., (uint32_t*)c->w->corr1.p, (CorrHeader*)c->w->hdr1.p, (PassState*)c->w->pass1.p,
-                     (int32_t*)c->w->list1.p, counters + 0);
+                     sf_est_mode(c), extra..., w.corr(1), w.hdr(1), w.pass(1), w.list(1), w.counter(1));
+}
+
+// One pass's buffers out of the current workspace, as the estimators, the adjustment and the merges take them: the work
+// list `list_sel` (Workspace::list) with its counter, the pass's lists, headers and states, the guided matcher's flags
+// (pass 2 only: pass 1 always matches globally), Reg/Force3DoF's applications behind the pass (myRegistration.cpp:269-276,
+// and for pass 1 the one its result meets as the guess of pass 2, :245-248) and the estimate's profiling slot.
+struct PassBufs {
+  const int32_t* list;
+  const int32_t* counter;
+  uint32_t* corr;
+  CorrHeader* hdr;
+  PassState* ps;
+  const uint8_t* guided_flag;
+  int end_3dof;
+  int prof;
+};
+inline PassBufs sf_pass_bufs(const sf_context* c, int pass, int list_sel) {
+  const Workspace& w = *c->w;
+  return {w.list(list_sel), w.counter(list_sel), w.corr(pass), w.hdr(pass), w.pass(pass),
+          pass == 2 ? w.guided_flags() : nullptr, c->dparams.force_3dof ? (pass == 1 ? 2 : 1) : 0,
+          pass == 1 ? SF_K_RANSAC1 : SF_K_RANSAC2};
+}
+
+// ---- run-time value -> template argument: f gets the value as a std::integral_constant ---------------------------------
+template <int V> using sf_int = std::integral_constant<int, V>;
+// dwords per binary descriptor row of the matching / chain kernels
+template <class F> int sf_with_w(int w, F&& f) { return w == 8 ? f(sf_int<8>{}) : f(sf_int<16>{}); }
+// wavefronts per chain / adjustment (SF_CHAIN_NW, SF_CHAIN_PNP_NW, SF_BA_NW)
+template <class F> int sf_with_nw(int nw, F&& f) { return nw == 1 ? f(sf_int<1>{}) : nw == 2 ? f(sf_int<2>{}) : f(sf_int<4>{}); }
+template <class F> int sf_with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// the guided matchers' rows <W, L2, U8>: uint8 L2 rows (desc_type 2) of 32 dwords, float32 rows (1) of 64 / 128, binary rows of 8 / 16
+template <class F> int sf_with_desc(int desc_type, int w, F&& f) {
+  if (desc_type == 2) return f(sf_int<32>{}, std::true_type{}, std::true_type{});
+  if (desc_type == 1) return w == 64 ? f(sf_int<64>{}, std::true_type{}, std::false_type{}) : f(sf_int<128>{}, std::true_type{}, std::false_type{});
+  return w == 8 ? f(sf_int<8>{}, std::false_type{}, std::false_type{}) : f(sf_int<16>{}, std::false_type{}, std::false_type{});
 }
 
 // Gate of one direction of the PnP estimate (myRegistrationVis.cpp:1059, :1070-1071 with A / B as :936-977 set them):
@@ -684,6 +722,19 @@ inline SfOrbPyr sf_orb_single_level(int w, int h) {
     hipError_t _e = (expr);                                                                  \
     if (_e != hipSuccess) return sf_fail((c), SF_EHIP, "%s -> %s", #expr, hipGetErrorString(_e)); \
   } while (0)
+
+// Dynamic LDS above the 64 KB every kernel may ask for: the first launcher of `kernel` on this handle raises the kernel's
+// limit to the 160 KB of a CU (an upper bound, not a request; `max_bytes`: less for a kernel with static LDS of its own, which
+// counts against the same 160 KB -- the runtime refuses a limit the two exceed together).  Every launcher whose request can
+// pass 64 KB comes through here; a handful of kernels ever do, so the list is scanned.
+template <class... A> int sf_dyn_lds(sf_context* c, void (*kernel)(A...), size_t lds_bytes, size_t max_bytes = 160 * 1024) {
+  if (lds_bytes <= 64 * 1024) return SF_OK;
+  for (const void* k : c->dyn_lds_kernels)
+    if (k == (const void*)kernel) return SF_OK;
+  SF_HIP(c, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes));
+  c->dyn_lds_kernels.push_back((const void*)kernel);
+  return SF_OK;
+}
 
 // one 32-bit word from the device, waited for: the counts that size a launch and the counts a caller asked for
 inline int sf_word_to_host(sf_context* c, const void* d_word, void* h_word) {
@@ -751,15 +802,15 @@ inline int sf_detector_work(sf_context* c, int width, int height, int n_img, siz
 int sf_launch_match_global(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n);
 // the same for uint8 rows compared by L2 (desc_type 2; k_match_u8.hip), which sf_launch_match_global hands on to it
 int sf_launch_match_global_u8(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n);
-// RANSAC for the pairs in work list `list` (count in counters[ctr]); pass = 1 or 2.
-int sf_launch_ransac(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass);
-// PnP (estimation_type = 1) for the pairs in the same work lists.
-int sf_launch_pnp(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass);
+// The stage pipeline's motion estimate of pass 1 or 2 (3D-3D RANSAC or PnP by estimation_type) for the pairs in that
+// pass's work list, with the second direction, the merge and the bundle adjustment the parameters ask for (k_verify.hip).
+int sf_launch_estimate(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass);
 // Guided matching for pairs whose pass 1 succeeded; builds the pass-2 RANSAC work list.
 int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n);
-// Vis/ForwardEstOnly = false with bundle adjustment: merge of a pass's two estimates + adjustment over the union (k_ba.hip)
+// The bundle adjustment of a pass's estimates as a launch of its own (k_verify.hip)
 int sf_launch_ba_pass(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass, int list_sel,
                       const uint8_t* mask, const uint8_t* run, bool fin, sf_result* d_out);
+// Vis/ForwardEstOnly = false with bundle adjustment: merge of a pass's two estimates + adjustment over the union (k_ba.hip)
 int sf_launch_merge_directions_ba(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass,
                                   bool pnp, const uint8_t* mask_f, const uint8_t* mask_b);
 // Fused per-pair pipeline (k_verify.hip): match -> RANSAC -> guided -> RANSAC -> result in one launch.

@@ -1,7 +1,8 @@
 // sf_match_device.hpp -- what the matching stages share around their scans.
 //
 // General pieces (pass 1, pass 2 in k_guided.hip, the estimators in k_ransac.hip / k_pnp.hip): write_null_pass, the
-// id-ordered compaction corr_compact, the finite-point count corr_count_finite, worklist_append.
+// id-ordered compaction corr_compact, the finite-point count corr_count_finite, worklist_append; behind the estimators
+// (and in k_ba.hip) pass_to3dof and merge_backward_pose.
 //
 // Pass 1 (global matching) has three scans -- k_match_global (scalar-load Hamming, float32 L2), match_v2_body (LDS + u16,
 // fp4 matrix cores; both k_match.hip) and k_match_global_u8 (int8 matrix cores, k_match_u8.hip).  All three share
@@ -15,6 +16,7 @@
 // k_match_split, whose register allocation (the whole chain, in the fused kernel) moves with any of them behind a function
 // boundary; what it calls from here leaves those kernels' vector code as it was (profiles/match_finish_isa.txt).
 #pragma once
+#include "sf_device_math.hpp"
 #include "sf_internal.hpp"
 
 // The "no transform" state of a pass (identity covariance scale, `matches` correspondences seen): built where it is
@@ -29,6 +31,35 @@ __device__ __forceinline__ void write_null_pass(PassState& out, int matches) {
   ps.matches = matches;
   ps.pad = 0;
   out = ps;
+}
+
+// The end-of-pass to3DoF of myRegistration.cpp:269-276 and, for pass 1, the one its result meets as the guess of
+// pass 2 (:245-248): `times` applications by the thread that wrote the pass state.
+__device__ inline void pass_to3dof(PassState& ps, int times) {
+  if (ps.is_null) return;
+  for (int t = 0; t < times; ++t) sfd::to3dof_canon(ps.T);
+}
+
+// Vis/ForwardEstOnly = false, myRegistrationVis.cpp:1376-1394: the backward estimate b enters the forward one a as its
+// inverse -- taken as it is where a has no transform, else interpolate(0.5) with the two covariances' mean.
+__device__ inline void merge_backward_pose(PassState& a, const PassState& b) {
+  if (b.is_null) return;
+  float inv[12];
+  sfd::rigid_inverse_canon(b.T, inv);
+  if (a.is_null) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) a.T[i] = inv[i];
+    a.is_null = 0;
+    a.var = b.var;
+    a.var_ang = b.var_ang;
+  } else {
+    float mid[12];
+    sfd::interpolate_half_canon(a.T, inv, mid);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) a.T[i] = mid[i];
+    a.var = (a.var + b.var) / 2.0;
+    a.var_ang = (a.var_ang + b.var_ang) / 2.0;
+  }
 }
 
 // The id-ordered compaction of the matches (wavefront ballots): out[k] = from | to << 16 for every "from" index i in

@@ -148,7 +148,7 @@ extern "C" int sf_find_matches_and_verify_device(sf_handle c, int32_t slot_base_
     c->accept_streamed = false;
     if (!d_out) {       // the caller only wants sf_last_match_results: an internal block takes the results
       if ((rc = sf_buf_reserve(c, c->w->results, (size_t)n * sizeof(sf_result))) != SF_OK) return rc;
-      d_out = (sf_result*)c->w->results.p;
+      d_out = c->w->out();
     }
     if ((rc = sf_verify_matches_device(c, out, n, slot_base_other, slot_base_local, d_out)) != SF_OK) return rc;
     c->last_results = d_out; c->last_results_index = nullptr; c->last_results_n = n;

@@ -175,10 +175,9 @@ static int verify_sequence(sf_context* c, const StoreView& view, const int32_t* 
   c->w->last_lists_valid = true;
   SF_HIP(c, hipMemsetAsync(c->w->counters.p, 0, 64, c->stream));   // work-list counters of the stage kernels
   if ((rc = sf_launch_match_global(c, view, d_from, d_to, m)) != SF_OK) return rc;
-  const bool pnp = c->dparams.estimation_type == 1;
-  if ((rc = (pnp ? sf_launch_pnp : sf_launch_ransac)(c, view, d_from, d_to, m, 1)) != SF_OK) return rc;
+  if ((rc = sf_launch_estimate(c, view, d_from, d_to, m, 1)) != SF_OK) return rc;
   if ((rc = sf_launch_guided(c, view, d_from, d_to, m)) != SF_OK) return rc;
-  if ((rc = (pnp ? sf_launch_pnp : sf_launch_ransac)(c, view, d_from, d_to, m, 2)) != SF_OK) return rc;
+  if ((rc = sf_launch_estimate(c, view, d_from, d_to, m, 2)) != SF_OK) return rc;
   return sf_launch_finalize(c, m, d_out);
 }
 
@@ -289,7 +288,7 @@ extern "C" int sf_verify_matches_device(sf_handle c, const sf_match* matches, in
   SF_HIP(c, hipMemcpyAsync(c->w->pair_to.p, ht, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   if (!c->pairs_staged) SF_HIP(c, hipEventCreateWithFlags(&c->pairs_staged, hipEventDisableTiming));
   SF_HIP(c, hipEventRecord(c->pairs_staged, c->stream));
-  return sf_verify_device(c, c->store, (const int32_t*)c->w->pair_from.p, (const int32_t*)c->w->pair_to.p, n, d_out);
+  return sf_verify_device(c, c->store, c->w->from(), c->w->to(), n, d_out);
 }
 
 static int verify_host_indices(sf_context* c, const Store& st, const int32_t* from, const int32_t* to, int n,
@@ -304,8 +303,7 @@ static int verify_host_indices(sf_context* c, const Store& st, const int32_t* fr
   if ((rc = sf_buf_reserve(c, c->w->results, (size_t)n * sizeof(sf_result))) != SF_OK) return rc;
   SF_HIP(c, hipMemcpyAsync(c->w->pair_from.p, from, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   SF_HIP(c, hipMemcpyAsync(c->w->pair_to.p, to, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  if ((rc = sf_verify_device(c, st, (const int32_t*)c->w->pair_from.p, (const int32_t*)c->w->pair_to.p, n,
-                          (sf_result*)c->w->results.p)) != SF_OK) return rc;
+  if ((rc = sf_verify_device(c, st, c->w->from(), c->w->to(), n, c->w->out())) != SF_OK) return rc;
   SF_HIP(c, hipMemcpyAsync(out, c->w->results.p, (size_t)n * sizeof(sf_result), hipMemcpyDeviceToHost, c->stream));
   SF_HIP(c, hipStreamSynchronize(c->stream));
   return SF_OK;
@@ -617,12 +615,10 @@ extern "C" int sf_debug_correspondences(sf_handle c, int32_t pair, int32_t pass,
     return sf_fail(c, SF_EINVAL, "the fused kernel keeps correspondence lists in LDS: set SF_OPT_DEBUG_CORR (or "
                                  "SF_DEBUG_CORR=1) before the verification call");
   CorrHeader h;
-  const Buf& hb = pass == 1 ? w.hdr1 : w.hdr2;
-  const Buf& cb = pass == 1 ? w.corr1 : w.corr2;
-  SF_HIP(c, hipMemcpy(&h, (const CorrHeader*)hb.p + pair, sizeof(h), hipMemcpyDeviceToHost));
+  SF_HIP(c, hipMemcpy(&h, w.hdr(pass) + pair, sizeof(h), hipMemcpyDeviceToHost));
   int n = std::min(h.n_corr, cap);
   std::vector<uint32_t> tmp(std::max(n, 1));
-  if (n > 0) SF_HIP(c, hipMemcpy(tmp.data(), (const uint32_t*)cb.p + (size_t)pair * w.ws_kcap, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (n > 0) SF_HIP(c, hipMemcpy(tmp.data(), w.corr(pass) + (size_t)pair * w.ws_kcap, (size_t)n * 4, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; ++i) {
     if (from_idx) from_idx[i] = (uint16_t)(tmp[i] & 0xFFFFu);
     if (to_idx) to_idx[i] = (uint16_t)(tmp[i] >> 16);
@@ -641,7 +637,7 @@ extern "C" int sf_debug_pass_state(sf_handle c, int32_t pair, int32_t pass, floa
   if (pair >= w.ws_pairs) return SF_EINVAL;
   if (!w.last_lists_valid) return sf_fail(c, SF_EINVAL, "set SF_OPT_DEBUG_CORR before the verification call");
   PassState ps;
-  SF_HIP(c, hipMemcpy(&ps, (const PassState*)(pass == 1 ? w.pass1.p : w.pass2.p) + pair, sizeof(ps), hipMemcpyDeviceToHost));
+  SF_HIP(c, hipMemcpy(&ps, w.pass(pass) + pair, sizeof(ps), hipMemcpyDeviceToHost));
   if (T12) memcpy(T12, ps.T, sizeof(ps.T));
   if (is_null) *is_null = ps.is_null;
   if (inliers) *inliers = ps.inliers;
