@@ -23,13 +23,13 @@
 //   k_fast_rekey       decides the order ON THE DEVICE once the count is known: corners <= max_features (or no limit)
 //                      -> raster order, the keys become (1 << 40 | (2^32 - 1 - index) << 8 | score); otherwise they
 //                      stay, and the descending sort below gives descending response with ties by descending index.
-//                      It also writes the segment bounds that a batch's segmented sort reads.
-//   sf_sort_keys (sf_sort.hip) descending (bits 0 .. 40), segmented for a batch.  Keys are unique (the pixel index), so
-//                      the order does not depend on the arrival order of the atomics.
+//                      It also writes the image's segment of the key array, which the sort reads.
+//   sf_sort_segments (sf_sort.hip) descending (bits 0 .. 40), every image's segment on its own.  Keys are unique (the
+//                      pixel index), so the order does not depend on the arrival order of the atomics.
 //   k_fast_emit        the first min(count, max_features) keys -> sf_keypoint {x, y, 7, -1, score, 0, -1}
 // FAST has no minimum-distance rule: no selection bitmap, no image-size limit beyond the 2^26 pixels of the index.
-// The two launchers share fast_front (workspace, score / candidates / rekey); their tails differ: the single call sizes
-// a plain sort by the corner count on the host, the batch sorts the segments whose bounds k_fast_rekey wrote.
+// One launcher, sf_launch_detect_fast, for one image and for many (blockIdx.y or .z = image): counts, bounds and the
+// choice of order are read on the device; the sort alone treats a lone image differently (sf_sort_segments).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -173,13 +173,13 @@ k_fast_candidates_masked(const uint8_t* __restrict__ score, int w, int h, int no
   fast_candidates<true>(score, w, h, nonmax, keys, count, cap, plane_stride, mask);
 }
 
-// blockIdx.y = image.  Raster order when the corners fit the limit; segment bounds for the batch's sort.
+// blockIdx.y = image.  Raster order when the corners fit the limit; the image's segment of the key array for the sort.
 __global__ void __launch_bounds__(256)
 k_fast_rekey(unsigned long long* __restrict__ keys, const unsigned* __restrict__ count, unsigned key_cap, int limit,
              unsigned* __restrict__ seg_begin, unsigned* __restrict__ seg_end) {
   const unsigned img = blockIdx.y;
   const unsigned n = min(count[img], key_cap);
-  if (seg_begin && blockIdx.x == 0 && threadIdx.x == 0) { seg_begin[img] = img * key_cap; seg_end[img] = img * key_cap + n; }
+  if (blockIdx.x == 0 && threadIdx.x == 0) { seg_begin[img] = img * key_cap; seg_end[img] = img * key_cap + n; }
   if (limit > 0 && n > (unsigned)limit) return;
   keys += (size_t)img * key_cap;
   for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
@@ -189,14 +189,13 @@ k_fast_rekey(unsigned long long* __restrict__ keys, const unsigned* __restrict__
 }
 
 __global__ void __launch_bounds__(256)
-k_fast_emit(const unsigned long long* __restrict__ keys, int n, int w, int limit, sf_keypoint* __restrict__ kp_out, int cap,
-            int32_t* __restrict__ n_out, const unsigned* __restrict__ d_count, unsigned key_cap) {
-  if (d_count) {     // batch: blockIdx.y = image, the corner count read on the device
-    keys += (size_t)blockIdx.y * key_cap;
-    n = (int)min(d_count[blockIdx.y], key_cap);
-    kp_out += (size_t)blockIdx.y * cap;
-    n_out += blockIdx.y;
-  }
+k_fast_emit(const unsigned long long* __restrict__ keys, int w, int limit, sf_keypoint* __restrict__ kp_out, int cap,
+            int32_t* __restrict__ n_out, const unsigned* __restrict__ count, unsigned key_cap) {
+  // blockIdx.y = image, its corner count read here
+  keys += (size_t)blockIdx.y * key_cap;
+  const int n = (int)min(count[blockIdx.y], key_cap);
+  kp_out += (size_t)blockIdx.y * cap;
+  n_out += blockIdx.y;
   const int total = (limit > 0 && n > limit) ? limit : n;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i == 0) *n_out = total;
@@ -230,57 +229,30 @@ void sf_launch_fast_level(sf_context* c, const uint8_t* d_images, size_t img_str
                        key_cap, plane_stride);
 }
 
-// The front half of both launchers -- workspace and the three front kernels for n_img images of one size: every image's
-// keys, in the form of the order that applies to it, their count and its segment of the key array are on the device when
-// the stream gets there
-static int fast_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
-                      int max_features, const sf_fast_params* prm, const SfCells& cells, const SfMask& mask, SfDetectorWork* F) {
-  int rc = sf_detector_work(c, width, height, n_img, (size_t)width * height, F);
-  if (rc != SF_OK) return rc;
+// The detector on n_img images of one size: corner counts and the choice of order stay on the device, every image's keys
+// are its segment of the sort, k_fast_emit reads the counts there.  d_kpts_out [n_img][cap], d_n_out [n_img] (device).
+// With `cells` the n_img images are the cells of a grid inside n_img / cells.per_image images (width x height: one cell),
+// keypoints in the cell's own coordinates.  The emit grid is sized by max_features, or -- one image, whose corner count
+// the sort has brought to the host -- by the keypoints there are.
+int sf_launch_detect_fast(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out,
+                          const SfCells& cells, const SfMask& mask) {
+  SfDetectorWork F;
+  SfSortBounds hb;
+  int rc;
+  if ((rc = sf_check_limit(c, n_img, max_features)) != SF_OK) return rc;
+  if ((rc = sf_detector_work(c, width, height, n_img, (size_t)width * height, &F)) != SF_OK) return rc;
   sf_launch_fast_level(c, d_images, img_stride, n_img, width, height, pitch, prm->threshold, prm->nonmax_suppression,
-                       (uint8_t*)c->gf_planes.p, (size_t)F->key_cap, F->keys, F->count, F->key_cap, cells, mask);
-  hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, n_img), dim3(256), 0, c->stream, F->keys, (const unsigned*)F->count,
-                     F->key_cap, max_features, F->seg_begin, F->seg_end);
+                       (uint8_t*)c->gf_planes.p, (size_t)F.key_cap, F.keys, F.count, F.key_cap, cells, mask);
+  hipLaunchKernelGGL(k_fast_rekey, dim3(FAST_REKEY_BLOCKS, n_img), dim3(256), 0, c->stream, F.keys, (const unsigned*)F.count,
+                     F.key_cap, max_features, F.seg_begin, F.seg_end);
   SF_HIP(c, hipGetLastError());
-  return SF_OK;
-}
-
-// Launch sequence on the handle's stream.  The corner count crosses to the host once (the sort is sized by it); which
-// order applies is decided on the device before that.
-int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out, const SfMask& mask) {
-  SfDetectorWork F;
-  int rc;
-  if ((rc = fast_front(c, d_image, 0, 1, width, height, pitch, max_features, prm, SfCells(), mask, &F)) != SF_OK) return rc;
-  unsigned h_count = 0;
-  if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
-  const int n = (int)std::min(h_count, F.key_cap);
-  if (n > 0 && (rc = sf_sort_keys(c, F.keys, F.keys_sorted, (size_t)n, 0, FAST_KEY_BITS, true)) != SF_OK) return rc;
-  const int total = (max_features > 0 && n > max_features) ? max_features : n;
-  const int written = std::min(total, cap);
-  hipLaunchKernelGGL(k_fast_emit, dim3(std::max((written + 255) / 256, 1), 1), dim3(256), 0, c->stream,
-                     (const unsigned long long*)F.keys_sorted, n, width, max_features, d_kpts_out, cap, F.n_single,
-                     (const unsigned*)nullptr, 0u);
-  SF_HIP(c, hipGetLastError());
-  return n_out ? sf_word_to_host(c, F.n_single, n_out) : SF_OK;
-}
-
-// The detector on a batch of images of one size, no host round trip: corner counts and the choice of order stay on the
-// device, a segmented sort takes the place of the sort sized by the host.  d_kpts_out [n_img][cap], d_n_out [n_img]
-// (device).  max_features > 0 here (the batch's outputs are sized by it).  With `cells` the n_img images are the cells of
-// a grid inside n_img / cells.per_image images (width x height: one cell), keypoints in the cell's own coordinates.
-int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out, const SfCells& cells, const SfMask& mask) {
-  SfDetectorWork F;
-  int rc;
-  if ((rc = fast_front(c, d_images, img_stride, n_img, width, height, pitch, max_features, prm, cells, mask, &F)) != SF_OK) return rc;
-  if ((rc = sf_sort_keys_segmented_desc(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img,
-                                        F.seg_begin, F.seg_end, 0, FAST_KEY_BITS)) != SF_OK)
+  if ((rc = sf_sort_segments(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img, F.seg_begin,
+                             F.seg_end, 0, FAST_KEY_BITS, true, &hb)) != SF_OK)
     return rc;
-  const int written = std::min(max_features, cap);
+  const int written = std::min(n_img == 1 ? sf_limit_keypoints(hb.n(), max_features) : max_features, cap);
   hipLaunchKernelGGL(k_fast_emit, dim3(std::max((written + 255) / 256, 1), n_img), dim3(256), 0, c->stream,
-                     (const unsigned long long*)F.keys_sorted, 0, width, max_features, d_kpts_out, cap, d_n_out,
+                     (const unsigned long long*)F.keys_sorted, width, max_features, d_kpts_out, cap, d_n_out,
                      (const unsigned*)F.count, F.key_cap);
   SF_HIP(c, hipGetLastError());
   return SF_OK;

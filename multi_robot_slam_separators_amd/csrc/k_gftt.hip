@@ -15,16 +15,18 @@
 //                      neighbourhood -> 64-bit keys (response bits << 32 | pixel index), one global atomic per workgroup
 //   k_gftt_masked_max, k_gftt_candidates_masked   under a mask (cv's `mask` argument; sf_detect_corners_masked_device and
 //                      the depth keyframe calls) only: the maximum over the masked-in pixels, candidates on them
-//   sf_sort_keys (sf_sort.hip) descending = decreasing response, ties by decreasing address (featureselect.cpp's
+//   k_gftt_segments    every image's candidates as its segment of the key array
+//   sf_sort_segments (sf_sort.hip) descending = decreasing response, ties by decreasing address (featureselect.cpp's
 //                      greaterThanPtr); a plain library sort, the only library call of the product's compute path
 //   k_gftt_select_lds  ONE wavefront walks the sorted list 64 candidates at a time: every lane tests its candidate
 //                      against the corners already taken (a bitmap of the image in LDS), the 64 lanes settle
 //                      conflicts among themselves in list order (in rounds, not in 64 turns), the survivors are
 //                      appended -- the sequential minDistance rule of goodFeaturesToTrack, 64 candidates per step.
-//   k_gftt_select      the same with the taken corners in per-cell lists in HBM: images whose bitmap does not fit
+//   k_gftt_select      the same with the taken corners in per-cell lists in HBM: a lone image whose bitmap does not fit
 //                      LDS (above about 1.2 Mpixel).
-// The two launchers share gftt_front (workspace, the three front kernels); their tails differ: the single call sizes a
-// plain sort by the candidate count on the host, the batch sorts segments whose bounds stay on the device.
+// One launcher, sf_launch_detect_corners, for one image and for many (blockIdx.z or .x = image): gftt_front (workspace,
+// the three front kernels), the segments, the sort, the selection; counts are read on the device, and the sort alone
+// treats a lone image differently (sf_sort_segments).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -324,16 +326,15 @@ constexpr int GFTT_MAX_RADIUS = 64;
 // the largest taken-corner bitmap k_gftt_select_lds keeps in dynamic LDS (its static `span` counts against the CU's 160 KB too)
 constexpr size_t GFTT_SELECT_LDS_MAX = 150 * 1024;
 __global__ void __launch_bounds__(256)
-k_gftt_select_lds(const unsigned long long* __restrict__ keys, int n, int w, int h, int wpr, float md2, int radius,
+k_gftt_select_lds(const unsigned long long* __restrict__ keys, int w, int h, int wpr, float md2, int radius,
                   int max_corners, sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out, float kp_size,
-                  const unsigned* __restrict__ d_count = nullptr, unsigned key_cap = 0) {
+                  const unsigned* __restrict__ count, unsigned key_cap) {
   extern __shared__ unsigned gf_bm[];
-  if (d_count) {     // batch: one workgroup per image, the candidate count read on the device
-    keys += (size_t)blockIdx.x * key_cap;
-    n = (int)min(d_count[blockIdx.x], key_cap);
-    kp_out += (size_t)blockIdx.x * cap;
-    n_out += blockIdx.x;
-  }
+  // one workgroup per image, its candidate count read here
+  keys += (size_t)blockIdx.x * key_cap;
+  const int n = (int)min(count[blockIdx.x], key_cap);
+  kp_out += (size_t)blockIdx.x * cap;
+  n_out += blockIdx.x;
   __shared__ int span[2 * GFTT_MAX_RADIUS + 1];
   for (int i = threadIdx.x; i < wpr * h; i += 256) gf_bm[i] = 0u;
   if ((int)threadIdx.x <= 2 * radius) {
@@ -415,7 +416,7 @@ __global__ void k_gftt_segments(const unsigned* __restrict__ count, unsigned key
   if (i < n) { begin[i] = (unsigned)i * key_cap; end[i] = (unsigned)i * key_cap + min(count[i], key_cap); }
 }
 
-// The front half of both launchers -- workspace and the three front kernels for n_img images of one size (blockIdx.z =
+// The front half of the launcher -- workspace and the three front kernels for n_img images of one size (blockIdx.z =
 // image): every image's candidate keys and their count are on the device when the stream gets there.  The handle's
 // sf_gftt_params (validated when set; the callers have refused a side below block_size) give the Sobel scale and the
 // response kernel: k_gftt_eig for the defaults, k_gftt_response otherwise
@@ -465,27 +466,39 @@ int gftt_front(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_
 
 }  // namespace
 
-// Launch sequence on the handle's stream.  The candidate count crosses to the host once (the sort is sized by it).
-int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
-                             double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
-                             int32_t* n_out, const SfMask& mask) {
-  SfDetectorWork F;
-  int rc;
-  if ((rc = gftt_front(c, d_image, 0, 1, width, height, pitch, quality_level, SfCells(), mask, &F)) != SF_OK) return rc;
-  unsigned h_count = 0;
-  if ((rc = sf_word_to_host(c, F.count, &h_count)) != SF_OK) return rc;
-  const int n = (int)std::min(h_count, F.key_cap);
-  if (n > 0 && (rc = sf_sort_keys(c, F.keys, F.keys_sorted, (size_t)n, 0, 64, true)) != SF_OK) return rc;
-  // taken corners as a bitmap in LDS when the image fits (up to about 1.2 Mpixel), cell lists in HBM otherwise
+// The detector on n_img images of one size: candidate counts stay on the device, every image's keys are its segment of the
+// sort, one selection workgroup per image.  d_kpts_out [n_img][cap], d_n_out [n_img] (device).  With `cells` the n_img
+// images are the cells of a grid inside n_img / cells.per_image images (width x height: one cell; its edge reflects),
+// keypoints in the cell's own coordinates.  The taken corners are a bitmap in LDS when the image fits (up to about 1.2
+// Mpixel); a lone image that does not fit falls back to cell lists in HBM, sized by the candidate count that its sort has
+// brought to the host, and several such images are refused.
+int sf_launch_detect_corners(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                             int pitch, int max_corners, double quality_level, double min_distance,
+                             sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells, const SfMask& mask) {
   const int wpr = (width + 31) / 32;
   const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
   const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
   const float md2 = (float)(min_distance * min_distance);
-  if (bm_bytes <= GFTT_SELECT_LDS_MAX && radius <= GFTT_MAX_RADIUS) {
+  const bool in_lds = bm_bytes <= GFTT_SELECT_LDS_MAX && radius <= GFTT_MAX_RADIUS;
+  if (!in_lds && n_img > 1)
+    return sf_fail(c, SF_ERANGE, "batched corner detection: %d x %d image does not fit the LDS selection bitmap", width, height);
+  SfDetectorWork F;
+  SfSortBounds hb;
+  int rc;
+  if ((rc = gftt_front(c, d_images, img_stride, n_img, width, height, pitch, quality_level, cells, mask, &F)) != SF_OK) return rc;
+  hipLaunchKernelGGL(k_gftt_segments, dim3((n_img + 63) / 64), dim3(64), 0, c->stream, (const unsigned*)F.count, F.key_cap,
+                     n_img, F.seg_begin, F.seg_end);
+  SF_HIP(c, hipGetLastError());
+  if ((rc = sf_sort_segments(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img, F.seg_begin,
+                             F.seg_end, 0, 64, true, &hb)) != SF_OK)
+    return rc;
+  if (in_lds) {
     if ((rc = sf_dyn_lds(c, k_gftt_select_lds, bm_bytes, GFTT_SELECT_LDS_MAX)) != SF_OK) return rc;
-    hipLaunchKernelGGL(k_gftt_select_lds, dim3(1), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, n,
-                       width, height, wpr, md2, radius, max_corners, d_kpts_out, cap, F.n_single, (float)c->gftt.block_size);
+    hipLaunchKernelGGL(k_gftt_select_lds, dim3(n_img), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted,
+                       width, height, wpr, md2, radius, max_corners, d_kpts_out, cap, d_n_out, (float)c->gftt.block_size,
+                       (const unsigned*)F.count, F.key_cap);
   } else {
+    const int n = hb.n();
     const int cell = min_distance >= 1.0 ? (int)std::lrint(min_distance) : 0;
     const int gw = cell > 0 ? (width + cell - 1) / cell : 1, gh = cell > 0 ? (height + cell - 1) / cell : 1;
     const size_t list_n = (size_t)std::max(n, 1);
@@ -496,39 +509,8 @@ int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, i
     int2* pts = (int2*)(head + n_int);
     SF_HIP(c, hipMemsetAsync(head, 0xFF, (size_t)gw * gh * sizeof(int), c->stream));
     hipLaunchKernelGGL(k_gftt_select, dim3(1), dim3(64), 0, c->stream, (const unsigned long long*)F.keys_sorted, n, width, cell,
-                       gw, gh, md2, max_corners, head, next, pts, d_kpts_out, cap, F.n_single, (float)c->gftt.block_size);
+                       gw, gh, md2, max_corners, head, next, pts, d_kpts_out, cap, d_n_out, (float)c->gftt.block_size);
   }
-  SF_HIP(c, hipGetLastError());
-  return n_out ? sf_word_to_host(c, F.n_single, n_out) : SF_OK;
-}
-
-// The detector on a batch of images of one size, no host round trip: candidate counts stay on the device (a segmented
-// sort takes the place of the sort sized by the host), one selection workgroup per image.  d_kpts_out [n_img][cap],
-// d_n_out [n_img] (device).  Needs the LDS bitmap form of the selection (images up to about 1.2 Mpixel).  With `cells` the
-// n_img images are the cells of a grid inside n_img / cells.per_image images (width x height: one cell; its edge reflects),
-// keypoints in the cell's own coordinates.
-int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                   int pitch, int max_corners, double quality_level, double min_distance,
-                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells,
-                                   const SfMask& mask) {
-  const int wpr = (width + 31) / 32;
-  const size_t bm_bytes = (size_t)wpr * height * sizeof(unsigned);
-  const int radius = min_distance >= 1.0 ? (int)std::ceil(min_distance) : 0;
-  if (bm_bytes > GFTT_SELECT_LDS_MAX || radius > GFTT_MAX_RADIUS)
-    return sf_fail(c, SF_ERANGE, "batched corner detection: %d x %d image does not fit the LDS selection bitmap", width, height);
-  SfDetectorWork F;
-  int rc;
-  if ((rc = gftt_front(c, d_images, img_stride, n_img, width, height, pitch, quality_level, cells, mask, &F)) != SF_OK) return rc;
-  hipLaunchKernelGGL(k_gftt_segments, dim3((n_img + 63) / 64), dim3(64), 0, c->stream, (const unsigned*)F.count, F.key_cap,
-                     n_img, F.seg_begin, F.seg_end);
-  SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys_segmented_desc(c, F.keys, F.keys_sorted, (unsigned)((size_t)F.key_cap * n_img), (unsigned)n_img,
-                                        F.seg_begin, F.seg_end, 0, 64)) != SF_OK)
-    return rc;
-  if ((rc = sf_dyn_lds(c, k_gftt_select_lds, bm_bytes, GFTT_SELECT_LDS_MAX)) != SF_OK) return rc;
-  hipLaunchKernelGGL(k_gftt_select_lds, dim3(n_img), dim3(256), bm_bytes, c->stream, (const unsigned long long*)F.keys_sorted, 0,
-                     width, height, wpr, (float)(min_distance * min_distance), radius, max_corners, d_kpts_out, cap, d_n_out,
-                     (float)c->gftt.block_size, (const unsigned*)F.count, F.key_cap);
   SF_HIP(c, hipGetLastError());
   return SF_OK;
 }

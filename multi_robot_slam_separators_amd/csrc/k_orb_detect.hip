@@ -9,13 +9,12 @@
 //   k_orb_resize     one level from the level below: the 2 x 2 mean when it halves exactly, else 8-bit bilinear in 11-bit
 //                    fixed point; the coefficients of a pixel are computed by its thread (two double divisions)
 //   k_fast_score / k_fast_candidates (k_fast.hip, unchanged) per level -> keys (score << 32 | pixel) and a count per level
-//   -- the counts cross to the host once: everything below is sized by their sum C --
-//   k_orb_gather     every candidate: border filter, key (level << 40 | pixel << 8 | score), histogram of the FAST
-//                    scores of its level
+//   k_orb_gather     every candidate (C of them in an image: the sum of its levels' counts, taken on the device): border
+//                    filter, key (level << 40 | pixel << 8 | score), histogram of the FAST scores of its level
 //   k_orb_cut_a      per level: the score at rank 2 quota (Harris) or quota (FAST) from the histogram -- retainBest on
 //                    8-bit scores needs no sort -- and the level's segment in the sorted list
 //   k_orb_filter_a   drops the candidates below their level's cut
-//   sf_sort_keys (sf_sort.hip) ascending by (level, pixel): survivors first, raster order within a level
+//   sf_sort_segments (sf_sort.hip) ascending by (level, pixel): survivors first, raster order within a level
 //   k_orb_harris     (score type Harris) one candidate per wavefront: lanes 0 .. 48 own one pixel of the 7 x 7 block each,
 //                    three integer wave reductions, one float32 expression; key (level, inverted order-preserving bits)
 //   sort ascending -> per level descending response; k_orb_cut_b reads the response at rank quota - 1
@@ -27,12 +26,13 @@
 //   k_orb_finish     position * scale_l into the caller's array
 // About forty short launches for three levels: latency-bound like the rest of the front end, not tuned yet.
 //
-// Two launchers over these kernels (as in k_fast.hip).  sf_launch_detect_orb sizes the lists by the corner counts it
-// reads back.  sf_launch_detect_orb_batch runs n images of one size with no host round trip: the image is a grid axis
+// One launcher over these kernels, sf_launch_detect_orb, for n >= 1 images of one size: the image is a grid axis
 // (blockIdx.y; blockIdx.x for the one-workgroup kernels), every list has a fixed capacity per image (3 x 3 strict
 // maxima: a level of w x h pixels holds at most ceil(w / 2) ceil(h / 2) corners, so nothing is ever truncated), the
-// per-level segments of an image come from the counts on the device, and the three sorts are segmented sorts whose
-// bounds the kernels before them write (k_orb_gather, k_orb_cut_a, k_orb_compact).
+// per-level segments of an image come from the counts on the device, and the three sorts take their bounds from the
+// kernels before them (k_orb_gather, k_orb_cut_a, k_orb_compact).  Two or more images never wait for the host.  A lone
+// image's sorts (a single call's, and a batch call's with one keyframe alike) are device-wide and sized by C, which crosses to the host once, with the first of them (sf_sort_segments):
+// k_orb_harris and k_orb_compact fill their lists up to C with keys that sort behind the stage's own bound.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,30 +45,27 @@ namespace {
 
 constexpr unsigned long long ORB_NONE = ~0ull;
 constexpr unsigned long long ORB_RASTER = 1ull << 63, ORB_LIMITED = 1ull << 62;
-// the scalar block (ints): per-level arrays of 8, then the histograms
-// (a batch: one such block per image; S_NCAND = the image's candidates, which the single call knows on the host)
-constexpr int S_COUNT = 0, S_CUT_A = 8, S_BEGIN = 16, S_KEPT = 24, S_TOTAL = 32, S_NCAND = 33, S_NFINAL = 34, S_CUT_B = 40, S_HIST = 64;
+// the scalar block of an image (ints): per-level arrays of 8, then the histograms; S_NCAND = the image's candidates
+constexpr int S_CUT_A = 8, S_BEGIN = 16, S_KEPT = 24, S_TOTAL = 32, S_NCAND = 33, S_NFINAL = 34, S_CUT_B = 40, S_HIST = 64;
 constexpr int S_WORDS = S_HIST + SF_ORB_MAX_LEVELS * 256;
-constexpr int ORB_HARRIS_BLOCKS = 1024;    // k_orb_harris of a batch: workgroups per image (4 candidates each per step)
+constexpr int ORB_HARRIS_BLOCKS = 1024;    // k_orb_harris: workgroups per image at the most (4 candidates each per step)
 
 struct OrbSel {
   int n_levels, score_type, edge, max_features;
-  unsigned base[SF_ORB_MAX_LEVELS];     // first candidate of every level (0xFFFFFFFF past the last level)
   int quota[SF_ORB_MAX_LEVELS];
 };
 
-// Where the lists of one image are.  The single call: n_img 0, everything at its base, the counts known on the host.
-// A batch (n_img >= 1): image i's source at + i * img_stride, its pyramid at + i * pyr_stride, its entries of every work
-// list at + i * cand_cap, its scalar block at + i * S_WORDS, its keypoints at + i * kp_cap.
+// Where the lists of the n_img >= 1 images are: image i's source at + i * img_stride, its pyramid at + i * pyr_stride, its
+// entries of every work list at + i * cand_cap, its scalar block at + i * S_WORDS, its keypoints at + i * kp_cap.
 struct OrbBatch {
   size_t img_stride, pyr_stride;
   unsigned cand_cap;
   int n_img, kp_cap;
   unsigned key_off[SF_ORB_MAX_LEVELS];   // the FAST keys of (image i, level l) at keys_f + key_off[l] + i * key_cap[l]
   unsigned key_cap[SF_ORB_MAX_LEVELS];
-  const unsigned* d_count;               // [level][n_img] corners found by FAST (batch)
-  unsigned* seg;                         // [6][n_img] begin / end of the three segmented sorts (batch)
-  int32_t* n_out;                        // [n_img] keypoints of every image (batch)
+  const unsigned* d_count;               // [level][n_img] corners found by FAST
+  unsigned* seg;                         // [6][n_img] begin / end of the image's segment in each of the three sorts
+  int32_t* n_out;                        // [n_img] keypoints of every image
 };
 
 __device__ __forceinline__ int orb_quota_of(const OrbSel& S, int l) {
@@ -118,28 +115,25 @@ k_orb_resize(const uint8_t* __restrict__ src, int sw, int sh, int spitch, uint8_
 
 // keys_f: the FAST keys of level l of image blockIdx.y at keys_f + B.key_off[l] + blockIdx.y * B.key_cap[l] (arrival order)
 __global__ void __launch_bounds__(256)
-k_orb_gather(const unsigned long long* __restrict__ keys_f, SfOrbPyr P, OrbSel S, unsigned C, unsigned long long* __restrict__ cand,
+k_orb_gather(const unsigned long long* __restrict__ keys_f, SfOrbPyr P, OrbSel S, unsigned long long* __restrict__ cand,
              int* __restrict__ sc, OrbBatch B) {
   const unsigned i = blockIdx.x * 256 + threadIdx.x, img = blockIdx.y;
-  // candidate i's level, the level's first candidate and its FAST keys.  The single call has the level segments from
-  // the host (S.base); a batch sums the image's counts here, as the host does there
+  // candidate i's level, the level's first candidate and its FAST keys: the running sum of the image's counts
   int l = 0;
   unsigned first = 0u, koff = B.key_off[0], kcap = B.key_cap[0], run = 0u;
 #pragma unroll
   for (int k = 0; k < SF_ORB_MAX_LEVELS; ++k) {
-    const unsigned b = !B.n_img ? S.base[k] : (k < S.n_levels ? run : 0xFFFFFFFFu);
+    const unsigned b = k < S.n_levels ? run : 0xFFFFFFFFu;
     if (k > 0 && i >= b) { l = k; first = b; koff = B.key_off[k]; kcap = B.key_cap[k]; }
-    if (B.n_img && k < S.n_levels) run += min(B.d_count[(unsigned)k * (unsigned)B.n_img + img], B.key_cap[k]);
+    if (k < S.n_levels) run += min(B.d_count[(unsigned)k * (unsigned)B.n_img + img], B.key_cap[k]);
   }
-  if (B.n_img) {
-    C = run;
-    sc += (size_t)img * S_WORDS;
-    cand += (size_t)img * B.cand_cap;
-    if (i == 0) {
-      sc[S_NCAND] = (int)C;
-      B.seg[img] = img * B.cand_cap;
-      B.seg[B.n_img + img] = img * B.cand_cap + C;
-    }
+  const unsigned C = run;
+  sc += (size_t)img * S_WORDS;
+  cand += (size_t)img * B.cand_cap;
+  if (i == 0) {
+    sc[S_NCAND] = (int)C;
+    B.seg[img] = img * B.cand_cap;
+    B.seg[B.n_img + img] = img * B.cand_cap + C;
   }
   if (i >= C) return;
   const SfOrbLevel L = sf_orb_level(P, l);
@@ -182,22 +176,17 @@ k_orb_cut_a(OrbSel S, int* __restrict__ sc, OrbBatch B) {
       run += s_kept[k];
     }
     sc[S_TOTAL] = run;
-    if (B.n_img) {                     // the Harris sort's segment: the survivors of the first cut
-      B.seg[2 * B.n_img + img] = img * B.cand_cap;
-      B.seg[3 * B.n_img + img] = img * B.cand_cap + (unsigned)run;
-    }
+    B.seg[2 * B.n_img + img] = img * B.cand_cap;                  // the Harris sort's segment: the survivors of the first cut
+    B.seg[3 * B.n_img + img] = img * B.cand_cap + (unsigned)run;
   }
 }
 
 __global__ void __launch_bounds__(256)
-k_orb_filter_a(unsigned long long* __restrict__ cand, unsigned C, const int* __restrict__ sc, OrbBatch B) {
+k_orb_filter_a(unsigned long long* __restrict__ cand, const int* __restrict__ sc, OrbBatch B) {
   const unsigned i = blockIdx.x * 256 + threadIdx.x;
-  if (B.n_img) {
-    sc += (size_t)blockIdx.y * S_WORDS;
-    cand += (size_t)blockIdx.y * B.cand_cap;
-    C = (unsigned)sc[S_NCAND];
-  }
-  if (i >= C) return;
+  sc += (size_t)blockIdx.y * S_WORDS;
+  cand += (size_t)blockIdx.y * B.cand_cap;
+  if (i >= (unsigned)sc[S_NCAND]) return;
   const unsigned long long key = cand[i];
   if (key == ORB_NONE) return;
   if ((int)(key & 255ull) < sc[S_CUT_A + (int)(key >> 40)]) cand[i] = ORB_NONE;
@@ -213,21 +202,19 @@ __device__ __forceinline__ float orb_order_float(unsigned o) {
 }
 
 // one candidate per wavefront and step (HarrisResponses, block 7, k 0.04); edge >= 16 keeps the radius-4 window inside the
-// level.  The single call's grid covers its C candidates in one step; a batch's fixed grid strides over the image's.
+// level.  The grid strides over the image's C candidates; past the survivors of the first cut the keys are ORB_NONE, which
+// sorts behind them: a lone image's sort covers all C entries (the range the host knows), a segment ends at the survivors.
 __global__ void __launch_bounds__(256)
 k_orb_harris(const uint8_t* __restrict__ img, int pitch, const uint8_t* __restrict__ pyr, SfOrbPyr P,
-             const unsigned long long* __restrict__ cand_s, const int* __restrict__ sc, unsigned C, float* __restrict__ resp,
+             const unsigned long long* __restrict__ cand_s, const int* __restrict__ sc, float* __restrict__ resp,
              unsigned long long* __restrict__ key_b, OrbBatch B) {
   const int lane = threadIdx.x & 63;
-  if (B.n_img) {
-    const size_t o = (size_t)blockIdx.y * B.cand_cap;
-    sc += (size_t)blockIdx.y * S_WORDS;
-    img += blockIdx.y * B.img_stride;
-    pyr += blockIdx.y * B.pyr_stride;
-    cand_s += o; resp += o; key_b += o;
-    C = (unsigned)sc[S_NCAND];
-  }
-  const unsigned total = (unsigned)sc[S_TOTAL];
+  const size_t o = (size_t)blockIdx.y * B.cand_cap;
+  sc += (size_t)blockIdx.y * S_WORDS;
+  img += blockIdx.y * B.img_stride;
+  pyr += blockIdx.y * B.pyr_stride;
+  cand_s += o; resp += o; key_b += o;
+  const unsigned C = (unsigned)sc[S_NCAND], total = (unsigned)sc[S_TOTAL];
   for (unsigned i = blockIdx.x * 4 + (threadIdx.x >> 6); i < C; i += gridDim.x * 4) {
     if (i >= total) {
       if (lane == 0) key_b[i] = ORB_NONE;
@@ -286,18 +273,16 @@ k_orb_cut_b(OrbSel S, const unsigned long long* __restrict__ key_bs, int* __rest
 // ONE workgroup per image: stable compaction of the survivors, then the sort keys of limitKeypoints (C entries, 0 past the
 // end)
 __global__ void __launch_bounds__(256)
-k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const float* __restrict__ resp, unsigned C,
+k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const float* __restrict__ resp,
               unsigned long long* __restrict__ fin_key, float* __restrict__ fin_resp, unsigned long long* __restrict__ key_c,
               int* __restrict__ sc, OrbBatch B) {
   __shared__ int wave_cnt[4];
   const int tid = threadIdx.x;
   const unsigned img = blockIdx.x;
-  if (B.n_img) {
-    const size_t o = (size_t)img * B.cand_cap;
-    sc += (size_t)img * S_WORDS;
-    cand_s += o; resp += o; fin_key += o; fin_resp += o; key_c += o;
-    C = (unsigned)sc[S_NCAND];
-  }
+  const size_t off = (size_t)img * B.cand_cap;
+  sc += (size_t)img * S_WORDS;
+  cand_s += off; resp += off; fin_key += off; fin_resp += off; key_c += off;
+  const unsigned C = (unsigned)sc[S_NCAND];
   const int total = sc[S_TOTAL];
   int running = 0;
   for (int base = 0; base < total; base += 256) {
@@ -330,11 +315,9 @@ k_orb_compact(OrbSel S, const unsigned long long* __restrict__ cand_s, const flo
   if (tid == 0) {
     const int n_final = limited ? S.max_features : running;
     sc[S_NFINAL] = n_final;
-    if (B.n_img) {                     // the last sort's segment: the survivors; the image's count for the caller
-      B.seg[4 * B.n_img + img] = img * B.cand_cap;
-      B.seg[5 * B.n_img + img] = img * B.cand_cap + (unsigned)running;
-      B.n_out[img] = n_final;
-    }
+    B.seg[4 * B.n_img + img] = img * B.cand_cap;                  // the last sort's segment: the survivors;
+    B.seg[5 * B.n_img + img] = img * B.cand_cap + (unsigned)running;
+    B.n_out[img] = n_final;                                       // the image's count for the caller
   }
 }
 
@@ -343,12 +326,10 @@ __global__ void __launch_bounds__(256)
 k_orb_emit(SfOrbPyr P, const unsigned long long* __restrict__ key_cs, const unsigned long long* __restrict__ fin_key,
            const float* __restrict__ fin_resp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ kp, OrbBatch B) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (B.n_img) {
-    const size_t o = (size_t)blockIdx.y * B.cand_cap;
-    sc += (size_t)blockIdx.y * S_WORDS;
-    key_cs += o; fin_key += o; fin_resp += o;
-    kp += (size_t)blockIdx.y * B.kp_cap;
-  }
+  const size_t off = (size_t)blockIdx.y * B.cand_cap;
+  sc += (size_t)blockIdx.y * S_WORDS;
+  key_cs += off; fin_key += off; fin_resp += off;
+  kp += (size_t)blockIdx.y * B.kp_cap;
   if (i >= sc[S_NFINAL] || i >= cap) return;
   const unsigned long long kc = key_cs[i];
   const unsigned low = (unsigned)kc & 0x7FFFFFFFu;
@@ -364,13 +345,11 @@ k_orb_emit(SfOrbPyr P, const unsigned long long* __restrict__ key_cs, const unsi
 __global__ void __launch_bounds__(256)
 k_orb_finish(SfOrbPyr P, const sf_keypoint* __restrict__ kp, const int* __restrict__ sc, int cap, sf_keypoint* __restrict__ out,
              OrbBatch B, int out_cap) {
-  // (batch: image blockIdx.y's keypoints to out + blockIdx.y * out_cap)
+  // (image blockIdx.y's keypoints to out + blockIdx.y * out_cap)
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (B.n_img) {
-    sc += (size_t)blockIdx.y * S_WORDS;
-    kp += (size_t)blockIdx.y * B.kp_cap;
-    out += (size_t)blockIdx.y * out_cap;
-  }
+  sc += (size_t)blockIdx.y * S_WORDS;
+  kp += (size_t)blockIdx.y * B.kp_cap;
+  out += (size_t)blockIdx.y * out_cap;
   if (i >= sc[S_NFINAL] || i >= cap) return;
   sf_keypoint k = kp[i];
   const SfOrbLevel L = sf_orb_level(P, k.octave);
@@ -465,79 +444,7 @@ static OrbSel orb_selection(const SfOrbPyr& P, int max_features, const sf_orb_de
   return S;
 }
 
-// Launch sequence on the handle's stream.  The per-level corner counts cross to the host once (the sorts are sized by
-// their sum); the cuts, the survivors and the choice of order stay on the device.
-int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                         const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out, int cap,
-                         int32_t* n_out) {
-  const SfOrbPyr P = sf_orb_pyr_layout(width, height, det->scale_factor, det->n_levels);
-  int rc;
-  if ((rc = sf_launch_orb_pyramid(c, d_image, pitch, P, 1, 0)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_planes, P.total)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_keys, (size_t)P.total * sizeof(unsigned long long))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_scalar, (size_t)S_WORDS * 4)) != SF_OK) return rc;
-  const uint8_t* pyr = (const uint8_t*)c->orb_pyr.p;
-  uint8_t* score = (uint8_t*)c->gf_planes.p;
-  unsigned long long* keys_f = (unsigned long long*)c->gf_keys.p;
-  int* sc = (int*)c->gf_scalar.p;
-  SF_HIP(c, hipMemsetAsync(sc, 0, (size_t)S_WORDS * 4, c->stream));
-  OrbBatch B = {};                                     // (n_img 0: one image, the counts on the host)
-  for (int l = 0; l < P.n; ++l) {
-    B.key_off[l] = P.off[l];
-    B.key_cap[l] = (unsigned)(P.w[l] * P.h[l]);
-    if (P.w[l] < 7 || P.h[l] < 7) continue;            // (no FAST domain)
-    sf_launch_fast_level(c, l == 0 ? d_image : pyr + P.off[l], 0, 1, P.w[l], P.h[l], l == 0 ? pitch : P.w[l], det->fast_threshold,
-                         1, score + P.off[l], B.key_cap[l], keys_f + P.off[l], (unsigned*)sc + S_COUNT + l, B.key_cap[l]);
-  }
-  SF_HIP(c, hipGetLastError());
-  unsigned h_count[SF_ORB_MAX_LEVELS] = {};
-  SF_HIP(c, hipMemcpyAsync(h_count, sc + S_COUNT, sizeof h_count, hipMemcpyDeviceToHost, c->stream));
-  SF_HIP(c, hipStreamSynchronize(c->stream));
-  OrbSel S = orb_selection(P, max_features, det, orb);
-  size_t total = 0;
-  for (int l = 0; l < SF_ORB_MAX_LEVELS; ++l) {
-    S.base[l] = l < P.n ? (unsigned)total : 0xFFFFFFFFu;
-    if (l < P.n) total += std::min(h_count[l], B.key_cap[l]);
-  }
-  if (n_out) *n_out = 0;
-  if (total == 0) return SF_OK;
-  const unsigned C = (unsigned)total;
-  const int cap_tmp = (int)std::min<size_t>(C, (size_t)max_features);
-  OrbLists W;
-  if ((rc = orb_lists(c, C, (size_t)cap_tmp, &W)) != SF_OK) return rc;
-  const dim3 block(256), grid((C + 255) / 256);
-  hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, C, W.cand, sc, B);
-  hipLaunchKernelGGL(k_orb_cut_a, dim3(1), dim3(64), 0, c->stream, S, sc, B);
-  hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, W.cand, C, (const int*)sc, B);
-  SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys(c, W.cand, W.cand_s, C, 8, 44, false)) != SF_OK) return rc;
-  if (det->score_type == 0) {
-    hipLaunchKernelGGL(k_orb_harris, dim3((C + 3) / 4), block, 0, c->stream, d_image, pitch, pyr, P,
-                       (const unsigned long long*)W.cand_s, (const int*)sc, C, W.resp, W.key_b, B);
-    SF_HIP(c, hipGetLastError());
-    if ((rc = sf_sort_keys(c, W.key_b, W.key_bs, C, 0, 36, false)) != SF_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_orb_cut_b, dim3(1), dim3(64), 0, c->stream, S, (const unsigned long long*)W.key_bs, sc, B);
-  hipLaunchKernelGGL(k_orb_compact, dim3(1), block, 0, c->stream, S, (const unsigned long long*)W.cand_s, (const float*)W.resp, C,
-                     W.fin_key, W.fin_resp, W.key_c, sc, B);
-  SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys(c, W.key_c, W.key_cs, C, 0, 64, true)) != SF_OK) return rc;
-  const dim3 grid_kp((cap_tmp + 255) / 256);
-  hipLaunchKernelGGL(k_orb_emit, grid_kp, block, 0, c->stream, P, (const unsigned long long*)W.key_cs,
-                     (const unsigned long long*)W.fin_key, (const float*)W.fin_resp, (const int*)sc, cap_tmp, W.kp1, B);
-  SF_HIP(c, hipGetLastError());
-  if ((rc = sf_launch_orb_angle_levels(c, d_image, 0, 1, pitch, P, 0, W.kp1, cap_tmp, (const int32_t*)(sc + S_NFINAL),
-                                       orb->edge_threshold, W.kp2)) != SF_OK)
-    return rc;
-  const int written = std::min(cap_tmp, cap);
-  if (written > 0)
-    hipLaunchKernelGGL(k_orb_finish, dim3((written + 255) / 256), block, 0, c->stream, P, (const sf_keypoint*)W.kp2,
-                       (const int*)sc, written, d_kpts_out, B, 0);
-  SF_HIP(c, hipGetLastError());
-  return n_out ? sf_word_to_host(c, sc + S_NFINAL, n_out) : SF_OK;
-}
-
-// What sf_launch_detect_orb_batch keeps on the device for n_img images, from the image size, n_img and max_features alone
+// What sf_launch_detect_orb keeps on the device for n_img images, from the image size, n_img and max_features alone
 // (a level of w x h pixels holds at most ceil(w / 2) ceil(h / 2) strict 3 x 3 maxima):
 //   c->orb_pyr     P.total bytes per image            the pyramid (the extraction reuses it)
 //   c->gf_planes   P.total bytes per image            FAST score planes
@@ -546,12 +453,13 @@ int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int h
 //   c->gf_scalar   S_WORDS + 8 + 6 words per image    scalar blocks, FAST counts, segment bounds
 static unsigned orb_level_cap(const SfOrbPyr& P, int l) { return (unsigned)(((P.w[l] + 1) / 2) * ((P.h[l] + 1) / 2)); }
 
-// The detector on a batch of images of one size, no host round trip (see the head of the file).  d_kpts_out [n_img][cap],
-// d_n_out [n_img] (device): the keypoints of every image in the single call's order, their number (which `cap` does not
-// clip).  max_features >= 1.
-int sf_launch_detect_orb_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                               int pitch, int max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
-                               sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out) {
+// The detector on n_img images of one size (see the head of the file).  d_kpts_out [n_img][cap], d_n_out [n_img] (device):
+// the keypoints of every image, their number (which `cap` does not clip).  max_features >= 1.  The three sorts share one
+// SfSortBounds: a lone image's candidate count C comes to the host with the first sort and sizes all three -- past their
+// own bounds the stage kernels have filled the lists up to C with keys that sort last.
+int sf_launch_detect_orb(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                         int max_features, const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out,
+                         int cap, int32_t* d_n_out) {
   const SfOrbPyr P = sf_orb_pyr_layout(width, height, det->scale_factor, det->n_levels);
   int rc;
   if (n_img < 1 || n_img > 65535) return sf_fail(c, SF_ERANGE, "ORB batch of %d images (1 .. 65535)", n_img);
@@ -597,24 +505,26 @@ int sf_launch_detect_orb_batch(sf_context* c, const uint8_t* d_images, size_t im
   const OrbSel S = orb_selection(P, max_features, det, orb);
   const unsigned n = (unsigned)n_img, cap_all = (unsigned)entries;
   const dim3 block(256), grid((B.cand_cap + 255) / 256, n);
-  hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, 0u, W.cand, sc, B);
+  SfSortBounds hb;
+  hipLaunchKernelGGL(k_orb_gather, grid, block, 0, c->stream, (const unsigned long long*)keys_f, P, S, W.cand, sc, B);
   hipLaunchKernelGGL(k_orb_cut_a, dim3(n), dim3(64), 0, c->stream, S, sc, B);
-  hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, W.cand, 0u, (const int*)sc, B);
+  hipLaunchKernelGGL(k_orb_filter_a, grid, block, 0, c->stream, W.cand, (const int*)sc, B);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys_segmented(c, W.cand, W.cand_s, cap_all, n, B.seg, B.seg + n, 8, 44, false)) != SF_OK) return rc;
+  if ((rc = sf_sort_segments(c, W.cand, W.cand_s, cap_all, n, B.seg, B.seg + n, 8, 44, false, &hb)) != SF_OK) return rc;
   if (det->score_type == 0) {
-    const unsigned blocks = std::min((B.cand_cap + 3) / 4, (unsigned)ORB_HARRIS_BLOCKS);
+    const unsigned most = n == 1 ? (unsigned)hb.n() : B.cand_cap;   // (a lone image's candidates are known by now)
+    const unsigned blocks = std::max(std::min((most + 3) / 4, (unsigned)ORB_HARRIS_BLOCKS), 1u);
     hipLaunchKernelGGL(k_orb_harris, dim3(blocks, n), block, 0, c->stream, d_images, pitch, pyr, P,
-                       (const unsigned long long*)W.cand_s, (const int*)sc, 0u, W.resp, W.key_b, B);
+                       (const unsigned long long*)W.cand_s, (const int*)sc, W.resp, W.key_b, B);
     SF_HIP(c, hipGetLastError());
-    if ((rc = sf_sort_keys_segmented(c, W.key_b, W.key_bs, cap_all, n, B.seg + 2 * n, B.seg + 3 * n, 0, 36, false)) != SF_OK)
+    if ((rc = sf_sort_segments(c, W.key_b, W.key_bs, cap_all, n, B.seg + 2 * n, B.seg + 3 * n, 0, 36, false, &hb)) != SF_OK)
       return rc;
   }
   hipLaunchKernelGGL(k_orb_cut_b, dim3(n), dim3(64), 0, c->stream, S, (const unsigned long long*)W.key_bs, sc, B);
-  hipLaunchKernelGGL(k_orb_compact, dim3(n), block, 0, c->stream, S, (const unsigned long long*)W.cand_s, (const float*)W.resp, 0u,
+  hipLaunchKernelGGL(k_orb_compact, dim3(n), block, 0, c->stream, S, (const unsigned long long*)W.cand_s, (const float*)W.resp,
                      W.fin_key, W.fin_resp, W.key_c, sc, B);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys_segmented(c, W.key_c, W.key_cs, cap_all, n, B.seg + 4 * n, B.seg + 5 * n, 0, 64, true)) != SF_OK) return rc;
+  if ((rc = sf_sort_segments(c, W.key_c, W.key_cs, cap_all, n, B.seg + 4 * n, B.seg + 5 * n, 0, 64, true, &hb)) != SF_OK) return rc;
   hipLaunchKernelGGL(k_orb_emit, dim3((cap_tmp + 255) / 256, n), block, 0, c->stream, P, (const unsigned long long*)W.key_cs,
                      (const unsigned long long*)W.fin_key, (const float*)W.fin_resp, (const int*)sc, cap_tmp, W.kp1, B);
   SF_HIP(c, hipGetLastError());

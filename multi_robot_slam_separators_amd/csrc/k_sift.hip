@@ -18,12 +18,13 @@
 //                     a bitmap (atomicOr): two candidates that converge to one sample give bit-identical keypoints, the
 //                     first claim appends the sample to the list (wave-aggregated), the second does nothing -- whichever
 //                     comes first, the list holds the same set
-//   k_sift_orient     one wavefront per listed sample: the refinement again (it converges at once: the sample is the one
-//                     the loop ended on), the 36-bin histogram as 64-bit integers in LDS, smoothing, one sort key per
-//                     peak: response bits << 32 | ~(sample << 6 | bin)
-//   k_sift_segments   (the batch form only) one thread per image of a chunk: what the single call decides on the host
-//                     between its launches -- overflow, the cut and its rekey flag, the image's sort segment, its row count
-//   k_surf_rekey's twin, sf_sort_keys or sf_sort_keys_segmented_desc (sf_sort.hip), then
+//   k_sift_orient     a wavefront per listed sample, SIFT_ORIENT_BLOCKS of them striding over an image's list: the
+//                     refinement again (it converges at once: the sample is the one the loop ended on), the 36-bin
+//                     histogram as 64-bit integers in LDS, smoothing, one sort key per peak: response bits << 32 |
+//                     ~(sample << 6 | bin)
+//   k_sift_segments   one thread per image of a chunk: overflow, the cut and its rekey flag, the image's sort segment, its
+//                     row count
+//   k_sift_rekey      a cut list: the position bits flipped (as k_surf_segments does), sf_sort_segments (sf_sort.hip), then
 //   k_sift_emit       one wavefront per sorted key: refinement and histogram again, the lane of the key's bin writes the
 //                     keypoint
 //   k_sift_describe   (Vis/FeatureType 1) one workgroup of 256 per given keypoint: calcSIFTDescriptor on the Gaussian plane the
@@ -33,8 +34,8 @@
 //                     float32 once; then a thread per dimension adds the 128 float32 squares in index order in float64,
 //                     clamps at 0.2 of the norm, adds again and scales to 0 .. 255.  Thread 0 does the 3D point
 //                     (extract_point).  LDS: 2880 + 512 bytes.
-// Every kernel takes the image of a chunk as its last grid dimension (SiftBatch); the single calls run a chunk of one
-// through the same kernels, so the batch form (sf_launch_detect_sift_batch) has no arithmetic of its own.
+// Every kernel takes the image of a chunk as its last grid dimension (SiftBatch) and reads that image's counts on the
+// device; one launcher, sf_launch_detect_sift, runs a chunk, and sf_detect_sift_device runs it on a chunk of one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -51,8 +52,8 @@ constexpr int SIFT_BORDER = 5, SIFT_STEPS = 5, SIFT_BINS = 36;
 constexpr float SIFT_IMG_SCALE = 1.0f / (255 * 48);
 constexpr double SIFT_VOTE_SCALE = 1048576.0;       // votes are summed as rint(vote 2^20) in 64-bit integers
 
-// The batch form: every kernel below takes the image of the chunk as its last grid dimension and finds that image's data
-// these strides behind image 0's.  The single calls are a chunk of one: every stride 0.
+// Every kernel below takes the image of the chunk as its last grid dimension and finds that image's data these strides
+// behind image 0's.
 struct SiftBatch {
   size_t img_stride;          // bytes between the uint8 images
   size_t plane_stride;        // int16 samples between the images' plane blocks (Gaussian | difference | row plane)
@@ -354,8 +355,7 @@ __device__ __forceinline__ bool sift_peak(const float* hist, int j, float* angle
   return true;
 }
 
-// What the single call decides on the host between its launches and the batch form per image on the device
-// (k_sift_segments), [images of the chunk] each; all null in the single call, which passes the scalars beside them
+// What is decided per image on the device (k_sift_extrema's counter, k_sift_segments), [images of the chunk] each
 struct SiftCounts {
   const unsigned* n_list;     // k_sift_orient: the image's extrema (more than cap: none of them is read)
   const unsigned* n_keys;     // k_sift_rekey: the image's keys, and
@@ -364,17 +364,15 @@ struct SiftCounts {
 };
 
 // blocks of ONE wavefront: the __syncthreads() of sift_keypoint are this wavefront's own.  The wavefront takes the listed
-// samples blockIdx.x, + gridDim.x, ... : one apiece in the single call, whose grid is the list; the batch form bounds the grid
+// samples blockIdx.x, + gridDim.x, ... of its image's list, whose length it reads on the device
 __global__ void __launch_bounds__(64)
 k_sift_orient(SfSiftPlan P, const short* __restrict__ gauss, const short* __restrict__ dog, SiftPrm prm,
-              const unsigned* __restrict__ list, unsigned n_list, unsigned long long* __restrict__ keys,
-              unsigned* __restrict__ count, unsigned cap, SiftCounts C, SiftBatch B) {
+              const unsigned* __restrict__ list, unsigned long long* __restrict__ keys, unsigned* __restrict__ count, unsigned cap,
+              SiftCounts C, SiftBatch B) {
   __shared__ unsigned long long raw[SIFT_BINS];
   __shared__ float hist[2 * SIFT_BINS];
-  if (C.n_list) {
-    n_list = C.n_list[blockIdx.z];
-    if (n_list > cap) return;                          // (an overflowed image: its list is not whole)
-  }
+  const unsigned n_list = C.n_list[blockIdx.z];
+  if (n_list > cap) return;                            // (an overflowed image: its list is not whole)
   gauss += blockIdx.z * B.plane_stride; dog += blockIdx.z * B.plane_stride;
   list += blockIdx.z * B.key_stride; keys += blockIdx.z * B.key_stride; count += blockIdx.z;
   const int lane = threadIdx.x;
@@ -403,16 +401,14 @@ k_sift_orient(SfSiftPlan P, const short* __restrict__ gauss, const short* __rest
 
 // (key, image) grid: a thread takes the keys blockIdx.x 256 + threadIdx.x, + gridDim.x 256, ... of its image
 __global__ void __launch_bounds__(256)
-k_sift_rekey(unsigned long long* __restrict__ keys, unsigned n, SiftCounts C, SiftBatch B) {
-  if (C.n_keys) {
-    if (!C.flipped[blockIdx.z]) return;
-    n = C.n_keys[blockIdx.z];
-  }
+k_sift_rekey(unsigned long long* __restrict__ keys, SiftCounts C, SiftBatch B) {
+  if (!C.flipped[blockIdx.z]) return;
+  const unsigned n = C.n_keys[blockIdx.z];
   keys += blockIdx.z * B.key_stride;
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) keys[i] ^= 0xFFFFFFFFull;
 }
 
-// One thread per image of the chunk: what sf_launch_detect_sift decides on the host.  n_ext / n_kp: the counters of
+// One thread per image of the chunk: the decisions about the image's list.  n_ext / n_kp: the counters of
 // k_sift_extrema and k_sift_orient.  An image with more extrema or more keypoints than cap_img (as many is not more) is
 // never truncated: it gets an empty segment and no keypoint, and the call's counter counts it.  Otherwise the image's
 // keys are its segment of the segmented sort (bounds counted from the chunk's first key), and they are cut once, at the
@@ -426,15 +422,12 @@ k_sift_segments(const unsigned* __restrict__ n_ext, unsigned* __restrict__ n_kp,
   if (img >= n_img) return;
   const bool over = n_ext[img] > cap_img || n_kp[img] > cap_img;
   const unsigned n = over ? 0u : n_kp[img];
-  int limit = 0;
-  if (n_features > 0) limit = n_features;
-  if (max_features > 0 && (limit == 0 || max_features < limit)) limit = max_features;
+  const int limit = sf_sift_limit(n_features, max_features);
   const bool cut = limit > 0 && n > (unsigned)limit;
   const unsigned begin = (unsigned)(img * key_stride);
   seg_begin[img] = begin;
   seg_end[img] = begin + n;
-  flipped[img] = cut ? 1u : 0u;
-  n_kp[img] = n;                                       // (what k_sift_rekey reads: nothing of an overflowed image)
+  flipped[img] = cut ? 1u : 0u;                        // (k_sift_rekey reads n_kp under this flag alone: never an overflowed image's)
   total[img] = min((int)(cut ? (unsigned)limit : n), cap_rows);
   if (over) atomicAdd(overflowed, 1u);
 }
@@ -442,11 +435,10 @@ k_sift_segments(const unsigned* __restrict__ n_ext, unsigned* __restrict__ n_kp,
 // (keypoint, image) grid of one-wavefront blocks
 __global__ void __launch_bounds__(64)
 k_sift_emit(SfSiftPlan P, const short* __restrict__ gauss, const short* __restrict__ dog, SiftPrm prm,
-            const unsigned long long* __restrict__ keys, int total, int flipped, sf_keypoint* __restrict__ kp_out, int kp_stride,
-            SiftCounts C, SiftBatch B) {
+            const unsigned long long* __restrict__ keys, sf_keypoint* __restrict__ kp_out, int kp_stride, SiftCounts C, SiftBatch B) {
   __shared__ unsigned long long raw[SIFT_BINS];
   __shared__ float hist[2 * SIFT_BINS];
-  if (C.total) { total = C.total[blockIdx.z]; flipped = (int)C.flipped[blockIdx.z]; }
+  const int total = C.total[blockIdx.z], flipped = (int)C.flipped[blockIdx.z];
   const int item = blockIdx.x;
   if (item >= total) return;
   gauss += blockIdx.z * B.plane_stride; dog += blockIdx.z * B.plane_stride;
@@ -793,6 +785,12 @@ static int sift_launch_pyramids(sf_context* c, const SfSiftBatchPlan& bp, int n,
   return SF_OK;
 }
 
+// c->sift_last: the pyramid of ONE image that a chunk of one, planned by bp, has left in c->sift_planes
+static void sift_remember_pyramid(sf_context* c, const SfSiftBatchPlan& bp, const sf_sift_params* prm, int width, int height) {
+  c->sift_last = bp.P; c->sift_last_off_dog = bp.off_dog; c->sift_last_off_claim = bp.plane_bytes; c->sift_last_ok = true;
+  c->sift_last_prm = *prm; c->sift_last_width = width; c->sift_last_height = height;
+}
+
 // The Gaussian and difference pyramids of an image into c->sift_planes, on the handle's stream; c->sift_last describes them
 int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const sf_sift_params* prm) {
   SfSiftBatchPlan bp;
@@ -804,82 +802,21 @@ int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int 
   if ((rc = sift_upload_tables(c, prm)) != SF_OK) return rc;
   const SiftBatch one = {0, 0, 0, 0};
   if ((rc = sift_launch_pyramids(c, bp, prm->n_octave_layers, d_image, width, height, pitch, 1, one)) != SF_OK) return rc;
-  c->sift_last = bp.P; c->sift_last_off_dog = bp.off_dog; c->sift_last_off_claim = bp.plane_bytes; c->sift_last_ok = true;
-  c->sift_last_prm = *prm; c->sift_last_width = width; c->sift_last_height = height;
+  sift_remember_pyramid(c, bp, prm, width, height);
   return SF_OK;
 }
 
-// Launch sequence on the handle's stream.  Two counts cross to the host: the extrema (one wavefront each follows) and the
-// keypoints (the sort is sized by it; more than the key buffer holds is refused there).
-int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out) {
-  int rc;
-  // sift_keys: keys | sorted keys | the extrema list | two counters
-  if ((rc = sf_buf_reserve(c, c->sift_keys, (size_t)SIFT_MAX_CANDIDATES * 20 + 16)) != SF_OK) return rc;
-  if ((rc = sf_sift_build_pyramid(c, d_image, width, height, pitch, prm)) != SF_OK) return rc;
-  const SfSiftPlan P = c->sift_last;
-  const int n = prm->n_octave_layers;
-  const size_t base_samples = (size_t)P.w[0] * P.h[0];
-  short* gauss = (short*)c->sift_planes.p;
-  short* dog = (short*)((uint8_t*)c->sift_planes.p + c->sift_last_off_dog);
-  unsigned* claimed = (unsigned*)((uint8_t*)c->sift_planes.p + c->sift_last_off_claim);
-  unsigned long long* keys = (unsigned long long*)c->sift_keys.p;
-  unsigned long long* keys_sorted = keys + SIFT_MAX_CANDIDATES;
-  unsigned* list = (unsigned*)(keys_sorted + SIFT_MAX_CANDIDATES);
-  unsigned* count = list + SIFT_MAX_CANDIDATES;
-  const unsigned cand_cap = c->sift_debug_cap > 0 ? (unsigned)c->sift_debug_cap : SIFT_MAX_CANDIDATES;
-  SF_HIP(c, hipMemsetAsync(count, 0, 8, c->stream));
-
-  const SiftPrm K = sift_kernel_params(*prm);
-  const SiftBatch one = {0, 0, 0, 0};
-  const SiftCounts host = {nullptr, nullptr, nullptr, nullptr};   // the counts cross to the host below
-  hipLaunchKernelGGL(k_sift_extrema, dim3(blocks_of(base_samples), P.n_octaves * n), dim3(256), 0, c->stream, P, (const short*)dog, K,
-                     claimed, list, count, cand_cap, one);
-  SF_HIP(c, hipGetLastError());
-  unsigned n_ext = 0, h_count = 0;
-  if ((rc = sf_word_to_host(c, count, &n_ext)) != SF_OK) return rc;
-  if (n_ext > cand_cap)
-    return sf_fail(c, SF_ERANGE, "SIFT: %u extrema in a %d x %d image exceed the capacity %u; raise contrast_threshold", n_ext, width,
-                   height, cand_cap);
-  if (n_ext > 0) {
-    hipLaunchKernelGGL(k_sift_orient, dim3(n_ext), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
-                       (const unsigned*)list, n_ext, keys, count + 1, cand_cap, host, one);
-    SF_HIP(c, hipGetLastError());
-    if ((rc = sf_word_to_host(c, count + 1, &h_count)) != SF_OK) return rc;
-  }
-  if (h_count > cand_cap)
-    return sf_fail(c, SF_ERANGE, "SIFT: %u keypoints in a %d x %d image exceed the capacity %u; raise contrast_threshold", h_count,
-                   width, height, cand_cap);
-  const int total_found = (int)h_count;
-  int limit = 0;                                          // retainBest(n_features), limitKeypoints(max_features): one cut
-  if (prm->n_features > 0) limit = prm->n_features;
-  if (max_features > 0 && (limit == 0 || max_features < limit)) limit = max_features;
-  const bool cut = limit > 0 && total_found > limit;      // equal responses by descending position (sf_detect_fast_device)
-  const int total = cut ? limit : total_found, written = std::min(total, cap);
-  if (total_found > 0) {
-    if (cut)
-      hipLaunchKernelGGL(k_sift_rekey, dim3(blocks_of(total_found)), dim3(256), 0, c->stream, keys, (unsigned)total_found, host, one);
-    if ((rc = sf_sort_keys(c, keys, keys_sorted, (size_t)total_found, 0, 64, true)) != SF_OK) return rc;
-    if (written > 0)
-      hipLaunchKernelGGL(k_sift_emit, dim3(written), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
-                         (const unsigned long long*)keys_sorted, written, cut ? 1 : 0, d_kpts_out, 0, host, one);
-    SF_HIP(c, hipGetLastError());
-  }
-  if (n_out) *n_out = total;
-  return SF_OK;
-}
-
-// The plan of a batch under the handle's limits, its buffers and the blur tables.  sift_keys keeps room for the single
-// call's layout, which a call after the batch finds there.
+// The plan of n_img images under the handle's limits, its buffers and the blur tables
 int sf_sift_batch_reserve(sf_context* c, int width, int height, const sf_sift_params& p, int n_img) {
   SfSiftBatchPlan& bp = c->sift_batch;
   int rc;
   if ((rc = sf_sift_batch_plan_host(c, width, height, p, n_img, (unsigned)c->sift_debug_cap, c->sift_debug_chunk, &bp)) != SF_OK) return rc;
   const size_t ctl_words = ((size_t)bp.chunk + 15) & ~(size_t)15;
   if ((rc = sf_buf_reserve(c, c->sift_planes, (size_t)bp.chunk * (bp.plane_bytes + bp.claim_words * 4))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->sift_keys, std::max((size_t)bp.chunk * bp.cap_img * 20, (size_t)SIFT_MAX_CANDIDATES * 20 + 16))) != SF_OK)
-    return rc;
+  if ((rc = sf_buf_reserve(c, c->sift_keys, (size_t)bp.chunk * bp.cap_img * 20)) != SF_OK) return rc;
+  const bool fresh = !c->sift_ctl.p;
   if ((rc = sf_buf_reserve(c, c->sift_ctl, 64 + 5 * ctl_words * sizeof(unsigned))) != SF_OK) return rc;
+  if (fresh) SF_HIP(c, hipMemsetAsync(c->sift_ctl.p, 0, 64, c->stream));      // (no batch call yet: none of its keyframes overflowed)
   return sift_upload_tables(c, &p);
 }
 
@@ -889,20 +826,26 @@ int sf_sift_batch_begin(sf_context* c) {
   return SF_OK;
 }
 
-// The detector on one chunk of a batch with no host round trip.  What sf_launch_detect_sift reads on the host stays on the
-// device: k_sift_orient reads the image's extrema count and shares its list among SIFT_ORIENT_BLOCKS wavefronts,
-// k_sift_segments takes the decisions, the sort is segmented, k_sift_rekey and k_sift_emit exit past their image's counts.
-// sift_ctl from byte 64 on, [chunk] words each: extrema, keypoints, segment begin, segment end, rekey flag -- the two
-// counters are cleared per chunk, as the claim bitmaps are.
-int sf_launch_detect_sift_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                int pitch, int max_features, const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out) {
+// The detector on ONE chunk (n_img <= c->sift_batch.chunk images of the size sf_sift_batch_reserve has planned for).  Every
+// count stays on the device: k_sift_orient reads the image's extrema count and shares its list among SIFT_ORIENT_BLOCKS
+// wavefronts, k_sift_segments takes the decisions, every image's keys are its segment of the sort, k_sift_rekey and
+// k_sift_emit exit past their image's counts.  sift_ctl from byte 64 on, [chunk] words each: extrema, keypoints, segment
+// begin, segment end, rekey flag -- the two counters are cleared per chunk, as the claim bitmaps are.  An image with more
+// extrema or keypoints than cap_img keeps no keypoint and is counted in word 0 of sift_ctl (sf_sift_batch_status: the most
+// recent BATCH call's, which sf_sift_batch_begin clears).
+// `one` (the single-image entry point; a chunk of one): both counts come to the host with the wait of the image's sort and
+// the entry point refuses an overflow itself; the overflow is counted in word 1, which nobody reads, and c->sift_last
+// describes the image's pyramid afterwards.
+int sf_launch_detect_sift(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int max_features, const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out,
+                          SfDetectOne* one) {
   const SfSiftBatchPlan& bp = c->sift_batch;
   const SfSiftPlan& P = bp.P;
   const int n = prm->n_octave_layers, m = n_img;
   const size_t ctl_words = ((size_t)bp.chunk + 15) & ~(size_t)15;
+  if (one) c->sift_last_ok = false;
   if (m < 1 || m > bp.chunk || P.w[0] != 2 * width || P.h[0] != 2 * height || P.n_layers != n || !c->sift_tables_ok ||
-      c->sift_tables_n != n || c->sift_tables_sigma != prm->sigma || max_features < 1 ||
+      c->sift_tables_n != n || c->sift_tables_sigma != prm->sigma || (m > 1 && max_features < 1) ||
       c->sift_planes.bytes < (size_t)bp.chunk * (bp.plane_bytes + bp.claim_words * 4) ||
       c->sift_keys.bytes < (size_t)bp.chunk * bp.cap_img * 20 || c->sift_ctl.bytes < 64 + 5 * ctl_words * sizeof(unsigned))
     return sf_fail(c, SF_EINVAL, "SIFT batch: a chunk of %d images of %d x %d is not what sf_sift_batch_reserve has planned", m, width, height);
@@ -915,34 +858,46 @@ int sf_launch_detect_sift_batch(sf_context* c, const uint8_t* d_images, size_t i
   unsigned long long* keys = (unsigned long long*)c->sift_keys.p;
   unsigned long long* keys_sorted = keys + (size_t)bp.chunk * bp.cap_img;
   unsigned* list = (unsigned*)(keys_sorted + (size_t)bp.chunk * bp.cap_img);
-  unsigned* overflowed = (unsigned*)c->sift_ctl.p;
-  unsigned *n_ext = overflowed + 16, *n_kp = n_ext + ctl_words, *seg_begin = n_kp + ctl_words, *seg_end = seg_begin + ctl_words,
-           *flipped = seg_end + ctl_words;
+  unsigned* overflowed = (unsigned*)c->sift_ctl.p + (one ? 1 : 0);
+  unsigned *n_ext = (unsigned*)c->sift_ctl.p + 16, *n_kp = n_ext + ctl_words, *seg_begin = n_kp + ctl_words,
+           *seg_end = seg_begin + ctl_words, *flipped = seg_end + ctl_words;
+  if (one) SF_HIP(c, hipMemsetAsync(overflowed, 0, 4, c->stream));
   SF_HIP(c, hipMemsetAsync(n_ext, 0, 2 * ctl_words * sizeof(unsigned), c->stream));
   const SiftPrm K = sift_kernel_params(*prm);
   const SiftCounts C = {n_ext, n_kp, flipped, d_n_out};
   const unsigned z = (unsigned)m;
-  const int rows = std::min(max_features, cap);
+  const int rows = max_features > 0 ? std::min(max_features, cap) : cap;      // what an image writes at the most
   hipLaunchKernelGGL(k_sift_extrema, dim3(blocks_of((size_t)P.w[0] * P.h[0]), P.n_octaves * n, z), dim3(256), 0, c->stream, P,
                      (const short*)dog, K, claimed, list, n_ext, bp.cap_img, B);
   hipLaunchKernelGGL(k_sift_orient, dim3(std::min(SIFT_ORIENT_BLOCKS, bp.cap_img), 1, z), dim3(64), 0, c->stream, P, (const short*)gauss,
-                     (const short*)dog, K, (const unsigned*)list, 0u, keys, n_kp, bp.cap_img, C, B);
+                     (const short*)dog, K, (const unsigned*)list, keys, n_kp, bp.cap_img, C, B);
   hipLaunchKernelGGL(k_sift_segments, dim3(blocks_of(m)), dim3(256), 0, c->stream, (const unsigned*)n_ext, n_kp, m, bp.cap_img,
                      (size_t)bp.cap_img, prm->n_features, max_features, rows, seg_begin, seg_end, flipped, d_n_out, overflowed);
-  hipLaunchKernelGGL(k_sift_rekey, dim3(blocks_of(rows), 1, z), dim3(256), 0, c->stream, keys, 0u, C, B);
+  hipLaunchKernelGGL(k_sift_rekey, dim3(blocks_of(std::max(rows, 1)), 1, z), dim3(256), 0, c->stream, keys, C, B);
   SF_HIP(c, hipGetLastError());
-  if ((rc = sf_sort_keys_segmented_desc(c, keys, keys_sorted, (unsigned)((size_t)m * bp.cap_img), (unsigned)m, seg_begin, seg_end, 0,
-                                        64)) != SF_OK)
+  SfSortBounds hb;
+  if (one) { hb.d_also[0] = n_ext; hb.d_also[1] = n_kp; }   // (both counts arrive with the bounds)
+  if ((rc = sf_sort_segments(c, keys, keys_sorted, (unsigned)((size_t)m * bp.cap_img), (unsigned)m, seg_begin, seg_end, 0, 64, true,
+                             &hb)) != SF_OK)
     return rc;
-  hipLaunchKernelGGL(k_sift_emit, dim3(rows, 1, z), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
-                     (const unsigned long long*)keys_sorted, 0, 0, d_kpts_out, cap, C, B);
+  // the emit grid, a wavefront per keypoint: sized by the rows an image may write, or -- a lone image, whose count the
+  // sort has brought to the host -- by its keypoints
+  const int written = m == 1 ? std::min(sf_limit_keypoints(hb.n(), sf_sift_limit(prm->n_features, max_features)), cap) : rows;
+  if (written > 0)
+    hipLaunchKernelGGL(k_sift_emit, dim3(written, 1, z), dim3(64), 0, c->stream, P, (const short*)gauss, (const short*)dog, K,
+                       (const unsigned long long*)keys_sorted, d_kpts_out, cap, C, B);
   SF_HIP(c, hipGetLastError());
+  if (one) {
+    one->count[0] = hb.also[0];
+    one->count[1] = hb.also[1];
+    sift_remember_pyramid(c, bp, prm, width, height);
+  }
   return SF_OK;
 }
 
 // k_sift_describe for sf_launch_extract_batch (k_extract.hip).  One image: the pyramid is the detector's when the full call
 // has just run it on this image with these parameters (reuse), else it is built here.  kind.batch: the n_img images of the
-// chunk sf_launch_detect_sift_batch has just run -- their pyramids are read where it left them.
+// chunk sf_launch_detect_sift has just run -- their pyramids are read where it left them.
 int sf_launch_sift_describe(sf_context* c, const uint8_t* d_left, int pitch, int width, int height, const SfSiftKind& kind,
                             const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n, int n_img,
                             const ExtractCam& cam, sf_keypoint* d_kpts_out, float* desc_tmp, float* xyz_tmp, uint8_t* keep,

@@ -14,16 +14,16 @@
 //                    appends ONE 64-bit key (response bits << 32 | 2^32 - 1 - position) through a wave-aggregated
 //                    atomic.  position = the sample's offset in the enumeration of all middle layers, so keys are
 //                    unique and a descending sort gives descending response, then layer, then sample -- whatever
-//                    order the atomics arrived in.  The counter counts past the capacity; the host refuses then.
-//   k_surf_rekey     only when limitKeypoints will cut the list: flips the position bits, so that equal responses sort by
-//                    DESCENDING position -- the rule FAST and ORB share (tests/orb2_ref.py limit_keypoints)
-//   sf_sort_keys     (sf_sort.hip) descending, 64 bits
-//   k_surf_segments  the batch form's stand-in for the host's decisions (sf_launch_detect_surf_batch; blockIdx.y = image):
-//                    reads the image's count; more than the key capacity: the image is marked as overflowed (the handle's
-//                    counter) and gets an empty segment; else the rekey above where the count exceeds max_features, and
-//                    the image's segment of the key array for sf_sort_keys_segmented_desc
+//                    order the atomics arrived in.  The counter counts past the capacity.
+//   k_surf_segments  the decisions about an image's list (blockIdx.y = image): reads the image's count; more than the key
+//                    capacity: the image is counted as overflowed and gets an empty segment; else, where limitKeypoints
+//                    will cut the list, the rekey (position bits flipped: equal responses by DESCENDING position), and
+//                    the image's segment of the key array for the sort
+//   sf_sort_segments (sf_sort.hip) descending, 64 bits
 //   k_surf_emit      the first min(count, max_features) keys -> keypoints, the interpolation done again from the planes
-//                    (k_surf_emit_batch: blockIdx.y = image, count and rekey flag read on the device, the count written)
+//                    (blockIdx.y = image, count and rekey flag read on the device, the count written)
+// One launcher, sf_launch_detect_surf, for one image and for many; sf_detect_surf_device runs it on one image and turns
+// an overflow into its refusal.
 //   k_surf_describe  one workgroup of 512 per keypoint.  Wavefront 0: the 109 orientation samples over its lanes in two
 //                    rounds (Haar responses, weights, cvRound(fastAtan2)) into LDS; lanes 0 .. 63 and 0 .. 7 again sum
 //                    the 72 windows, each in sample order; the best window by a butterfly that prefers the lower
@@ -210,12 +210,6 @@ k_surf_maxima(SurfLayout L, const float* __restrict__ det, const float* __restri
   keys[slot] = ((unsigned long long)__float_as_uint(k.response) << 32) | (unsigned long long)(0xFFFFFFFFu - pos);
 }
 
-__global__ void __launch_bounds__(256)
-k_surf_rekey(unsigned long long* __restrict__ keys, unsigned n) {
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i < n) keys[i] ^= 0xFFFFFFFFull;
-}
-
 // key i of a sorted list -> its keypoint, the interpolation done again from the planes
 __device__ __forceinline__ sf_keypoint surf_emit_one(const SurfLayout& L, const float* __restrict__ det, const float* __restrict__ trace,
                                                      float thr, unsigned long long key, int flipped) {
@@ -233,19 +227,13 @@ __device__ __forceinline__ sf_keypoint surf_emit_one(const SurfLayout& L, const 
   return k;
 }
 
-__global__ void __launch_bounds__(256)
-k_surf_emit(SurfLayout L, const float* __restrict__ det, const float* __restrict__ trace, float thr,
-            const unsigned long long* __restrict__ keys, int total, int flipped, sf_keypoint* __restrict__ kp_out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  kp_out[i] = surf_emit_one(L, det, trace, thr, keys[i], flipped);
-}
-
-// ---- the batch form: what the host decides in sf_launch_detect_surf, per image on the device ---------------------------
+// ---- the decisions about an image's list, per image on the device -------------------------------------------------------
 constexpr int SURF_SEGMENT_BLOCKS = 32;
 
 // blockIdx.y = image.  count / seg_begin / seg_end / flipped: [images of the launch]; the segment bounds count from the
-// launch's first key.  overflowed: the handle's counter of the call.
+// launch's first key.  More maxima than cap_img: the image is counted in *overflowed and gets an empty segment.  More
+// than max_features: limitKeypoints will cut the list, and the position bits are flipped, so that equal responses sort by
+// DESCENDING position -- the rule FAST and ORB share (tests/orb2_ref.py limit_keypoints).
 __global__ void __launch_bounds__(256)
 k_surf_segments(unsigned long long* __restrict__ keys, const unsigned* __restrict__ count, unsigned cap_img, size_t key_stride,
                 int max_features, unsigned* __restrict__ seg_begin, unsigned* __restrict__ seg_end, unsigned* __restrict__ flipped,
@@ -269,10 +257,9 @@ k_surf_segments(unsigned long long* __restrict__ keys, const unsigned* __restric
 // blockIdx.y = image: the first min(count, max_features) sorted keys of the image -> kp_out [image][cap], n_out [image];
 // an overflowed image: no keypoint
 __global__ void __launch_bounds__(256)
-k_surf_emit_batch(SurfLayout L, const float* __restrict__ det, const float* __restrict__ trace, float thr,
-                  const unsigned long long* __restrict__ keys, const unsigned* __restrict__ count, const unsigned* __restrict__ flipped,
-                  unsigned cap_img, int max_features, sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out,
-                  SurfBatch B) {
+k_surf_emit(SurfLayout L, const float* __restrict__ det, const float* __restrict__ trace, float thr,
+            const unsigned long long* __restrict__ keys, const unsigned* __restrict__ count, const unsigned* __restrict__ flipped,
+            unsigned cap_img, int max_features, sf_keypoint* __restrict__ kp_out, int cap, int32_t* __restrict__ n_out, SurfBatch B) {
   const unsigned img = blockIdx.y;
   const unsigned n = count[img];
   int total = n > cap_img ? 0 : (int)n;
@@ -555,59 +542,14 @@ extern "C" void sf_surf_build_tables(float* ori_w, int8_t* ori_xy, float* desc_w
 }
 
 // The candidate capacity of one image: SURF_MAX_CANDIDATES, or what sf_debug_surf_limits has put in its place
-static unsigned surf_candidate_cap(const sf_context* c) { return c->surf_debug_cap > 0 ? (unsigned)c->surf_debug_cap : SURF_MAX_CANDIDATES; }
+unsigned sf_surf_candidate_cap(const sf_context* c) { return c->surf_debug_cap > 0 ? (unsigned)c->surf_debug_cap : SURF_MAX_CANDIDATES; }
 
-// Launch sequence on the handle's stream.  The count of maxima crosses to the host once: the sort is sized by it, and an
-// image with more maxima than the key buffer holds is refused there.
-int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out) {
-  SurfLayout L;
-  size_t floats = 0;
-  int rc;
-  if ((rc = surf_layout(c, width, height, *prm, &L, &floats)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->surf_planes, std::max<size_t>(floats, 1) * 2 * sizeof(float))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->surf_keys, (size_t)SURF_MAX_CANDIDATES * 16 + 16)) != SF_OK) return rc;
-  float* det = (float*)c->surf_planes.p;
-  float* trace = det + floats;
-  unsigned long long* keys = (unsigned long long*)c->surf_keys.p;
-  unsigned long long* keys_sorted = keys + SURF_MAX_CANDIDATES;
-  unsigned* count = (unsigned*)(keys_sorted + SURF_MAX_CANDIDATES);
-  const unsigned cand_cap = surf_candidate_cap(c);
-  const int32_t* S = nullptr;
-  if ((rc = sf_launch_integral(c, d_image, width, height, pitch, &S)) != SF_OK) return rc;
-  SF_HIP(c, hipMemsetAsync(count, 0, 4, c->stream));
-  const unsigned blocks = (unsigned)(((size_t)width * height + 255) / 256);
-  const int n_all = prm->n_octaves * (prm->n_octave_layers + 2), n_middle = prm->n_octaves * prm->n_octave_layers;
-  const SurfBatch one = {0, 0, 0};
-  hipLaunchKernelGGL(k_surf_hessian, dim3(blocks, n_all), dim3(256), 0, c->stream, S, L, det, trace, one);
-  hipLaunchKernelGGL(k_surf_maxima, dim3(blocks, n_middle), dim3(256), 0, c->stream, L, (const float*)det, (const float*)trace,
-                     prm->hessian_threshold, keys, count, cand_cap, one);
-  SF_HIP(c, hipGetLastError());
-  unsigned h_count = 0;
-  if ((rc = sf_word_to_host(c, count, &h_count)) != SF_OK) return rc;
-  if (h_count > cand_cap)
-    return sf_fail(c, SF_ERANGE, "SURF: %u maxima in a %d x %d image exceed the candidate capacity %u; raise hessian_threshold", h_count,
-                   width, height, cand_cap);
-  const int n = (int)h_count;
-  const bool cut = max_features > 0 && n > max_features;   // limitKeypoints: equal responses by descending position
-  const int total = cut ? max_features : n, written = std::min(total, cap);
-  if (n > 0) {
-    if (cut) hipLaunchKernelGGL(k_surf_rekey, dim3((n + 255) / 256), dim3(256), 0, c->stream, keys, (unsigned)n);
-    if ((rc = sf_sort_keys(c, keys, keys_sorted, (size_t)n, 0, 64, true)) != SF_OK) return rc;
-    if (written > 0)
-      hipLaunchKernelGGL(k_surf_emit, dim3((written + 255) / 256), dim3(256), 0, c->stream, L, (const float*)det, (const float*)trace,
-                         prm->hessian_threshold, (const unsigned long long*)keys_sorted, written, cut ? 1 : 0, d_kpts_out);
-    SF_HIP(c, hipGetLastError());
-  }
-  if (n_out) *n_out = total;
-  return SF_OK;
-}
-
-// The host arithmetic of the batch form (no device, c may be null).  B bounds the maxima an image of this layout can have:
-// surf_keypoint demands v > q of all 26 neighbours, so two maxima of one layer are never 8-adjacent, and a layer whose
-// interior (the samples k_surf_maxima looks at) is r x c holds at most ceil(r / 2) ceil(c / 2) of them.  An image's key
-// capacity is the smaller of B and the candidate capacity: where B is the smaller (up to about a megapixel under the
-// defaults) no image can overflow.
+// The host arithmetic of the detector's workspace (no device, c may be null).  B bounds the maxima an image of this layout
+// can have: surf_keypoint demands v > q of all 26 neighbours, so two maxima of one layer are never 8-adjacent, and a layer
+// whose interior (the samples k_surf_maxima looks at) is r x c holds at most ceil(r / 2) ceil(c / 2) of them.  An image's
+// key capacity is the smaller of B and the candidate capacity: where B is the smaller (up to about a megapixel under the
+// defaults) no image can overflow.  "More maxima than cap_img" is therefore the same refusal as "more than the candidate
+// capacity", which is what a single call reports: no image has more than B.
 int sf_surf_batch_plan_host(sf_context* c, int width, int height, const sf_surf_params& p, int n, unsigned candidate_cap,
                             int forced_chunk, SfSurfBatchPlan* out) {
   SurfLayout L;
@@ -640,43 +582,47 @@ int sf_surf_batch_plan_host(sf_context* c, int width, int height, const sf_surf_
 // below asks again and finds them there)
 int sf_surf_batch_reserve(sf_context* c, int width, int height, const sf_surf_params& p, int n_img, SfSurfBatchPlan* plan) {
   int rc;
-  if ((rc = sf_surf_batch_plan_host(c, width, height, p, n_img, surf_candidate_cap(c), c->surf_debug_chunk, plan)) != SF_OK) return rc;
+  if ((rc = sf_surf_batch_plan_host(c, width, height, p, n_img, sf_surf_candidate_cap(c), c->surf_debug_chunk, plan)) != SF_OK) return rc;
   const size_t ctl_words = ((size_t)n_img + 15) & ~(size_t)15;
   if ((rc = sf_buf_reserve(c, c->surf_planes, (size_t)plan->chunk * plan->plane_floats * 2 * sizeof(float))) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->surf_keys, std::max((size_t)plan->chunk * plan->key_stride * 16, (size_t)SURF_MAX_CANDIDATES * 16 + 16))) != SF_OK)
-    return rc;
+  if ((rc = sf_buf_reserve(c, c->surf_keys, (size_t)plan->chunk * plan->key_stride * 16)) != SF_OK) return rc;
+  const bool fresh = !c->surf_ctl.p;
   if ((rc = sf_buf_reserve(c, c->surf_ctl, 64 + 4 * ctl_words * sizeof(unsigned))) != SF_OK) return rc;
+  if (fresh) SF_HIP(c, hipMemsetAsync(c->surf_ctl.p, 0, 64, c->stream));     // (no batch call yet: none of its keyframes overflowed)
   return sf_buf_reserve(c, c->ex_integral, (size_t)(width + 1) * (height + 1) * sizeof(int32_t) * n_img);
 }
 
-// The detector on n_img images of one size with no host round trip: d_kpts_out [n_img][cap], d_n_out [n_img] on the device,
-// max_features > 0.  The integral images of ALL images are built first and stay in c->ex_integral for the extraction; the
-// rest runs over chunks of plan.chunk images -- consecutive launches on the handle's stream -- so that planes and keys keep
-// to SURF_BATCH_WORKSPACE_BYTES.  An image with more maxima than its key capacity keeps no keypoint and is counted in the
-// first word of c->surf_ctl (sf_surf_batch_status); the per-image words follow from byte 64 on.
-int sf_launch_detect_surf_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                int pitch, int max_features, const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out) {
+// The fast-Hessian detector + limitKeypoints on n_img images of one size: d_kpts_out [n_img][cap], d_n_out [n_img] on the
+// device.  The integral images of ALL images are built first and stay in c->ex_integral for the extraction; the rest runs
+// over chunks of plan.chunk images -- consecutive launches on the handle's stream -- so that planes and keys keep to
+// SURF_BATCH_WORKSPACE_BYTES.  An image with more maxima than its key capacity keeps no keypoint and is counted in the first
+// word of c->surf_ctl (sf_surf_batch_status: the most recent BATCH call's); the per-image words follow from byte 64 on.
+// `one` (the single-image entry point, n_img == 1): the count of maxima comes to the host with the wait of the image's
+// sort, the entry point refuses an overflow itself, and the overflow is counted in the second word, which nobody reads --
+// what the status call reports stays the batch call's.
+int sf_launch_detect_surf(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int max_features, const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out,
+                          SfDetectOne* one) {
   SurfLayout L;
   size_t floats = 0;
   SfSurfBatchPlan plan;
   int rc;
+  if ((rc = sf_check_limit(c, n_img, max_features)) != SF_OK) return rc;
   if ((rc = surf_layout(c, width, height, *prm, &L, &floats)) != SF_OK) return rc;
-  if ((rc = sf_surf_batch_reserve(c, width, height, *prm, n_img, &plan)) != SF_OK) return rc;   // (the caller's: nothing moves)
+  if ((rc = sf_surf_batch_reserve(c, width, height, *prm, n_img, &plan)) != SF_OK) return rc;   // (a batch caller's: nothing moves)
   const size_t ctl_words = ((size_t)n_img + 15) & ~(size_t)15;
   float* planes = (float*)c->surf_planes.p;
   unsigned long long* keys = (unsigned long long*)c->surf_keys.p;
   unsigned long long* keys_sorted = keys + (size_t)plan.chunk * plan.key_stride;
-  unsigned* overflowed = (unsigned*)c->surf_ctl.p;
-  unsigned* count = overflowed + 16;
+  unsigned* overflowed = (unsigned*)c->surf_ctl.p + (one ? 1 : 0);
+  unsigned* count = (unsigned*)c->surf_ctl.p + 16;
   unsigned *seg_begin = count + ctl_words, *seg_end = seg_begin + ctl_words, *flipped = seg_end + ctl_words;
   const int32_t* S = nullptr;
   size_t s_stride = 0;
   if ((rc = sf_launch_integral_batch(c, d_images, img_stride, n_img, width, height, pitch, &S, &s_stride)) != SF_OK) return rc;
-  SF_HIP(c, hipMemsetAsync(overflowed, 0, 64 + ctl_words * sizeof(unsigned), c->stream));   // the counter and every count
+  SF_HIP(c, hipMemsetAsync(overflowed, 0, (size_t)(count + ctl_words - overflowed) * sizeof(unsigned), c->stream));   // the call's counter and every count
   const unsigned blocks = (unsigned)(((size_t)width * height + 255) / 256);
   const int n_all = prm->n_octaves * (prm->n_octave_layers + 2), n_middle = prm->n_octaves * prm->n_octave_layers;
-  const int written = std::min(max_features, cap);
   const SurfBatch B = {s_stride, 2 * plan.plane_floats, plan.key_stride};
   float* det = planes;
   float* trace = planes + plan.plane_floats;
@@ -688,10 +634,15 @@ int sf_launch_detect_surf_batch(sf_context* c, const uint8_t* d_images, size_t i
     hipLaunchKernelGGL(k_surf_segments, dim3(SURF_SEGMENT_BLOCKS, m), dim3(256), 0, c->stream, keys, (const unsigned*)(count + i0),
                        plan.cap_img, plan.key_stride, max_features, seg_begin + i0, seg_end + i0, flipped + i0, overflowed);
     SF_HIP(c, hipGetLastError());
-    if ((rc = sf_sort_keys_segmented_desc(c, keys, keys_sorted, (unsigned)((size_t)m * plan.key_stride), (unsigned)m, seg_begin + i0,
-                                          seg_end + i0, 0, 64)) != SF_OK)
+    SfSortBounds hb;
+    if (one) hb.d_also[0] = count;                       // (the count of maxima arrives with the bounds)
+    if ((rc = sf_sort_segments(c, keys, keys_sorted, (unsigned)((size_t)m * plan.key_stride), (unsigned)m, seg_begin + i0,
+                               seg_end + i0, 0, 64, true, &hb)) != SF_OK)
       return rc;
-    hipLaunchKernelGGL(k_surf_emit_batch, dim3(std::max((written + 255) / 256, 1), m), dim3(256), 0, c->stream, L, (const float*)det,
+    if (one) one->count[0] = hb.also[0];
+    // the emit grid: sized by max_features, or -- a lone image, whose count the sort has brought to the host -- by its keypoints
+    const int written = std::min(m == 1 ? sf_limit_keypoints(hb.n(), max_features) : max_features, cap);
+    hipLaunchKernelGGL(k_surf_emit, dim3(std::max((written + 255) / 256, 1), m), dim3(256), 0, c->stream, L, (const float*)det,
                        (const float*)trace, prm->hessian_threshold, (const unsigned long long*)keys_sorted, (const unsigned*)(count + i0),
                        (const unsigned*)(flipped + i0), plan.cap_img, max_features, d_kpts_out + (size_t)i0 * cap, cap, d_n_out + i0, B);
     SF_HIP(c, hipGetLastError());

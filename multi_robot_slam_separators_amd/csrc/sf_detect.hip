@@ -73,6 +73,39 @@ static int detect_ready(sf_context* c, int validated, int width, int height, boo
   return SF_OK;
 }
 
+// Each entry point runs its detector's launcher on ONE image (d_kpts_out [1][cap], the count in a device word of the
+// handle's) and brings to the host what it returns: the keypoint count, read behind the last kernel (GFTT, FAST, ORB: the
+// call returns with its keypoints written, as it always has), or what came with the one wait of the image's sort
+// (SfDetectOne; SURF, SIFT: the candidate counts, from which the refusal and the keypoint count follow).
+static int single_count_word(sf_context* c, int32_t** d_n) {
+  const int rc = sf_buf_reserve(c, c->ft_counts, sizeof(int32_t));
+  *d_n = (int32_t*)c->ft_counts.p;
+  return rc;
+}
+
+static int detect_corners_one(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
+                              double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap, int32_t* n_out,
+                              const SfMask& mask) {
+  int32_t* d_n = nullptr;
+  int rc;
+  if ((rc = single_count_word(c, &d_n)) != SF_OK) return rc;
+  if ((rc = sf_launch_detect_corners(c, d_image, 0, 1, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out,
+                                     cap, d_n, SfCells(), mask)) != SF_OK)
+    return rc;
+  return sf_word_to_host(c, d_n, n_out);                 // (the selection decides it: minDistance drops candidates)
+}
+
+static int detect_fast_one(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
+                           const sf_fast_params& prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out, const SfMask& mask) {
+  int32_t* d_n = nullptr;
+  int rc;
+  if ((rc = single_count_word(c, &d_n)) != SF_OK) return rc;
+  if ((rc = sf_launch_detect_fast(c, d_image, 0, 1, width, height, pitch, max_features, &prm, d_kpts_out, cap, d_n, SfCells(),
+                                  mask)) != SF_OK)
+    return rc;
+  return sf_word_to_host(c, d_n, n_out);
+}
+
 extern "C" int sf_detect_corners_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
                                         int32_t max_corners, double quality_level, double min_distance,
                                         sf_keypoint* d_kpts_out, int32_t cap, int32_t* n_out) {
@@ -80,8 +113,8 @@ extern "C" int sf_detect_corners_device(sf_handle c, const uint8_t* d_image, int
   if ((rc = detect_prologue(c, d_image, width, height, pitch, d_kpts_out, cap, n_out)) != SF_OK) return rc;
   if ((rc = sf_check_gftt_side(c, width, height, "an image")) != SF_OK) return rc;
   if ((rc = detect_ready(c, sf_check_gftt(c, quality_level, min_distance), width, height)) != SF_OK) return rc;
-  return sf_launch_detect_corners(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out,
-                                  cap, n_out);
+  return detect_corners_one(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out, cap, n_out,
+                            SfMask());
 }
 
 extern "C" int sf_detect_fast_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
@@ -91,7 +124,7 @@ extern "C" int sf_detect_fast_device(sf_handle c, const uint8_t* d_image, int32_
   if ((rc = detect_prologue(c, d_image, width, height, pitch, d_kpts_out, cap, n_out)) != SF_OK) return rc;
   const sf_fast_params prm = params ? *params : c->fast;
   if ((rc = detect_ready(c, sf_fast_validate(c, prm), width, height)) != SF_OK) return rc;
-  return sf_launch_detect_fast(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
+  return detect_fast_one(c, d_image, width, height, pitch, max_features, prm, d_kpts_out, cap, n_out, SfMask());
 }
 
 // ---- the two corner detectors under a mask (cv's `mask` argument; Vis/DepthAsMask makes one of a depth image) --------------
@@ -115,8 +148,8 @@ extern "C" int sf_detect_corners_masked_device(sf_handle c, const uint8_t* d_ima
   if ((rc = check_mask(c, "sf_detect_corners_masked_device", d_mask, width, mask_pitch)) != SF_OK) return rc;
   if ((rc = sf_check_gftt_side(c, width, height, "an image")) != SF_OK) return rc;
   if ((rc = detect_ready(c, sf_check_gftt(c, quality_level, min_distance), width, height)) != SF_OK) return rc;
-  return sf_launch_detect_corners(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out,
-                                  cap, n_out, single_mask(d_mask, mask_pitch));
+  return detect_corners_one(c, d_image, width, height, pitch, max_corners, quality_level, min_distance, d_kpts_out, cap, n_out,
+                            single_mask(d_mask, mask_pitch));
 }
 
 extern "C" int sf_detect_fast_masked_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
@@ -127,8 +160,7 @@ extern "C" int sf_detect_fast_masked_device(sf_handle c, const uint8_t* d_image,
   if ((rc = check_mask(c, "sf_detect_fast_masked_device", d_mask, width, mask_pitch)) != SF_OK) return rc;
   const sf_fast_params prm = params ? *params : c->fast;
   if ((rc = detect_ready(c, sf_fast_validate(c, prm), width, height)) != SF_OK) return rc;
-  return sf_launch_detect_fast(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out,
-                               single_mask(d_mask, mask_pitch));
+  return detect_fast_one(c, d_image, width, height, pitch, max_features, prm, d_kpts_out, cap, n_out, single_mask(d_mask, mask_pitch));
 }
 
 // ---- depth images (kernels in k_depth.hip): Vis/DepthAsMask as handle state, the mask and the 3D points as calls --------------
@@ -204,7 +236,10 @@ extern "C" int sf_detect_orb_device(sf_handle c, const uint8_t* d_image, int32_t
   const sf_orb_detector_params d = det ? *det : c->orb_det;
   const sf_orb_params o = orb ? *orb : c->orb;
   if ((rc = detect_ready(c, sf_orb_detector_validate(c, d, o), width, height)) != SF_OK) return rc;
-  return sf_launch_detect_orb(c, d_image, width, height, pitch, max_features, &d, &o, d_kpts_out, cap, n_out);
+  int32_t* d_n = nullptr;
+  if ((rc = single_count_word(c, &d_n)) != SF_OK) return rc;
+  if ((rc = sf_launch_detect_orb(c, d_image, 0, 1, width, height, pitch, max_features, &d, &o, d_kpts_out, cap, d_n)) != SF_OK) return rc;
+  return sf_word_to_host(c, d_n, n_out);
 }
 
 extern "C" int sf_detect_surf_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
@@ -214,7 +249,17 @@ extern "C" int sf_detect_surf_device(sf_handle c, const uint8_t* d_image, int32_
   if ((rc = detect_prologue(c, d_image, width, height, pitch, d_kpts_out, cap, n_out)) != SF_OK) return rc;
   const sf_surf_params prm = surf ? *surf : c->surf;
   if ((rc = detect_ready(c, sf_surf_validate(c, prm), width, height, true)) != SF_OK) return rc;
-  return sf_launch_detect_surf(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
+  int32_t* d_n = nullptr;
+  SfDetectOne one;
+  if ((rc = single_count_word(c, &d_n)) != SF_OK) return rc;
+  if ((rc = sf_launch_detect_surf(c, d_image, 0, 1, width, height, pitch, max_features, &prm, d_kpts_out, cap, d_n, &one)) != SF_OK)
+    return rc;
+  const unsigned cand_cap = sf_surf_candidate_cap(c);     // (the image kept no keypoint: nothing was written)
+  if (one.count[0] > cand_cap)
+    return sf_fail(c, SF_ERANGE, "SURF: %u maxima in a %d x %d image exceed the candidate capacity %u; raise hessian_threshold",
+                   one.count[0], width, height, cand_cap);
+  *n_out = sf_limit_keypoints((int)one.count[0], max_features);
+  return SF_OK;
 }
 
 extern "C" int sf_detect_sift_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,
@@ -224,7 +269,21 @@ extern "C" int sf_detect_sift_device(sf_handle c, const uint8_t* d_image, int32_
   if ((rc = detect_prologue(c, d_image, width, height, pitch, d_kpts_out, cap, n_out)) != SF_OK) return rc;
   const sf_sift_params prm = sift ? *sift : c->sift;
   if ((rc = detect_ready(c, sf_sift_validate(c, prm), width, height)) != SF_OK) return rc;
-  return sf_launch_detect_sift(c, d_image, width, height, pitch, max_features, &prm, d_kpts_out, cap, n_out);
+  int32_t* d_n = nullptr;
+  SfDetectOne one;
+  if ((rc = single_count_word(c, &d_n)) != SF_OK) return rc;
+  if ((rc = sf_sift_batch_reserve(c, width, height, prm, 1)) != SF_OK) return rc;              // a chunk of one
+  if ((rc = sf_launch_detect_sift(c, d_image, 0, 1, width, height, pitch, max_features, &prm, d_kpts_out, cap, d_n, &one)) != SF_OK)
+    return rc;
+  const unsigned cand_cap = c->sift_batch.cap_img;        // (past it the image kept no keypoint: nothing was written)
+  if (one.count[0] > cand_cap)
+    return sf_fail(c, SF_ERANGE, "SIFT: %u extrema in a %d x %d image exceed the capacity %u; raise contrast_threshold", one.count[0],
+                   width, height, cand_cap);
+  if (one.count[1] > cand_cap)
+    return sf_fail(c, SF_ERANGE, "SIFT: %u keypoints in a %d x %d image exceed the capacity %u; raise contrast_threshold", one.count[1],
+                   width, height, cand_cap);
+  *n_out = sf_limit_keypoints((int)one.count[1], sf_sift_limit(prm.n_features, max_features));
+  return SF_OK;
 }
 
 extern "C" int sf_debug_sift_plane(sf_handle c, int32_t octave, int32_t layer, int32_t dog, int16_t* d_out) {
@@ -395,7 +454,7 @@ int sf_grid_plan(sf_context* c, int width, int height, int max_features, FrontPl
   return SF_OK;
 }
 
-// The detection stage under a grid, for n images (the single calls: n = 1): the batch launchers with the cells as their
+// The detection stage under a grid, for n images (the single calls: n = 1): the launchers with the cells as their
 // images, then k_grid_gather -- d_kpts [n][rows_cap] in full-image coordinates, d_n [n], nothing waited for
 int sf_grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_params& dp, const uint8_t* d_left, size_t image_stride,
                    int n, int pitch, sf_keypoint* d_kpts, int32_t* d_n, const SfMask& mask) {
@@ -413,11 +472,11 @@ int sf_grid_detect(sf_context* c, const FrontPlan& fp, const sf_detector_params&
   m.cells = g;
   m.cells.row_step = (size_t)fp.row_size * mask.pitch;
   if (sf_type_of(c).corners == CORNERS_FAST)
-    rc = sf_launch_detect_fast_batch(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota, &c->fast,
-                                     d_cell_kpts, fp.quota, d_cell_n, g, m);
+    rc = sf_launch_detect_fast(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota, &c->fast, d_cell_kpts,
+                               fp.quota, d_cell_n, g, m);
   else
-    rc = sf_launch_detect_corners_batch(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota,
-                                        dp.quality_level, dp.min_distance, d_cell_kpts, fp.quota, d_cell_n, g, m);
+    rc = sf_launch_detect_corners(c, d_roi, image_stride, n * cells, fp.col_size, fp.row_size, pitch, fp.quota, dp.quality_level,
+                                  dp.min_distance, d_cell_kpts, fp.quota, d_cell_n, g, m);
   if (rc != SF_OK) return rc;
   return sf_launch_grid_gather(c, d_cell_kpts, d_cell_n, n, fp.rows, fp.cols, fp.quota, fp.x, fp.y, fp.col_size, fp.row_size, d_kpts,
                                fp.rows_cap, d_n);

@@ -89,7 +89,7 @@ void sf_launch_surf_describe(sf_context* c, const uint8_t* d_left, int pitch, co
 
 // k_sift_describe (k_sift.hip) in the same place: SIFT rows (128 float32 holding 0 .. 255) into desc_tmp, every keypoint
 // unchanged into d_kpts_out, 3D points and keep flags.  One image (n_img 1): it builds or reuses the Gaussian pyramid;
-// kind.batch: the n_img images of the chunk sf_launch_detect_sift_batch has just run, whose pyramids it reads
+// kind.batch: the n_img images of the chunk sf_launch_detect_sift has just run, whose pyramids it reads
 int sf_launch_sift_describe(sf_context* c, const uint8_t* d_left, int pitch, int width, int height, const SfSiftKind& kind,
                             const sf_keypoint* d_kpts, const float* d_right_x, const uint8_t* d_status, int n, int n_img,
                             const ExtractCam& cam, sf_keypoint* d_kpts_out, float* desc_tmp, float* xyz_tmp, uint8_t* keep,

@@ -232,9 +232,9 @@ struct SfSurfTables {
 };
 constexpr int SURF_ORI_SAMPLES = 109, SURF_PATCH = 20, SURF_MAX_OCTAVES = 8, SURF_MAX_LAYERS = 8;
 constexpr unsigned SURF_MAX_CANDIDATES = 1u << 18;   // maxima per image; more is SF_ERANGE, never a truncated list
-// The batch form of the detector (sf_launch_detect_surf_batch) runs over chunks of images whose det / trace planes and keys
+// The detector (sf_launch_detect_surf) runs over chunks of images whose det / trace planes and keys
 // fit this much workspace: the size of the Infinity Cache, so that the planes k_surf_hessian writes are still on the die
-// when k_surf_maxima and k_surf_emit_batch read them, and two orders of magnitude more workgroups per launch than the chip
+// when k_surf_maxima and k_surf_emit read them, and two orders of magnitude more workgroups per launch than the chip
 // has compute units.  One image always runs, whatever it needs.
 constexpr size_t SURF_BATCH_WORKSPACE_BYTES = (size_t)256 << 20;
 // What sf_surf_batch_plan_host computes for n images of one size: the bound on an image's maxima, its key capacity
@@ -769,14 +769,13 @@ struct SfDepthIn {
 
 // ---- workspace of the corner detectors (k_gftt.hip, k_fast.hip), one image and a batch alike --------------------------
 // c->gf_planes: plane_bytes per image for the detector's own planes.  c->gf_keys: the candidate keys of image i at keys +
-// i * key_cap, and as much again for their sorted copy.  c->gf_scalar: the single call's corner count at byte 0, from byte
-// 64 the per-image arrays max_bits, count, seg_begin, seg_end; the first two are zeroed on the stream.
+// i * key_cap, and as much again for their sorted copy.  c->gf_scalar: the per-image arrays max_bits, count, seg_begin,
+// seg_end; the first two are zeroed on the stream.
 struct SfDetectorWork {
   unsigned key_cap;                            // = pixels of one image
   unsigned long long *keys, *keys_sorted;      // [n_img][key_cap] each
   int* max_bits;                               // [n_img] GFTT: float bits of max(eig)
-  unsigned *count, *seg_begin, *seg_end;       // [n_img] candidates found; the bounds of a batch's segmented sort
-  int32_t* n_single;
+  unsigned *count, *seg_begin, *seg_end;       // [n_img] candidates found; the image's segment for sf_sort_segments
 };
 inline int sf_detector_work(sf_context* c, int width, int height, int n_img, size_t plane_bytes, SfDetectorWork* W) {
   const size_t np = (size_t)width * height;
@@ -784,12 +783,11 @@ inline int sf_detector_work(sf_context* c, int width, int height, int n_img, siz
   int rc;
   if ((rc = sf_buf_reserve(c, c->gf_planes, plane_bytes * n_img)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->gf_keys, np * 2 * sizeof(unsigned long long) * n_img)) != SF_OK) return rc;
-  if ((rc = sf_buf_reserve(c, c->gf_scalar, 64 + (size_t)n_img * 16)) != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, c->gf_scalar, (size_t)n_img * 16)) != SF_OK) return rc;
   W->key_cap = (unsigned)np;
   W->keys = (unsigned long long*)c->gf_keys.p;
   W->keys_sorted = W->keys + np * n_img;
-  W->n_single = (int32_t*)c->gf_scalar.p;
-  W->max_bits = (int*)((char*)c->gf_scalar.p + 64);
+  W->max_bits = (int*)c->gf_scalar.p;
   W->count = (unsigned*)(W->max_bits + n_img);
   W->seg_begin = W->count + n_img;
   W->seg_end = W->seg_begin + n_img;
@@ -828,20 +826,46 @@ size_t sf_guided_lds_bytes(int kcap, int n_cells, bool narrow = false);   // nar
 void sf_brief_default_pattern(int8_t* tests, int bytes);
 void sf_orb_default_pattern(int8_t* tests);     // [256][4]: 32-byte ORB rows
 // The detectors' one library call (sf_sort.hip): radix sort of 64-bit keys by bits [bit0, bit1) on the handle's stream,
-// temporary storage in c->gf_tmp.  The segmented forms sort every [d_begin[s], d_end[s]) on its own, the bounds read on the
-// device.
-int sf_sort_keys(sf_context* c, const unsigned long long* in, unsigned long long* out, size_t n, unsigned bit0, unsigned bit1,
-                 bool descending);
-int sf_sort_keys_segmented(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
-                           unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0, unsigned bit1,
-                           bool descending);
-int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
-                                unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0,
-                                unsigned bit1);
-int sf_launch_detect_corners_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                   int pitch, int max_corners, double quality_level, double min_distance,
-                                   sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells = SfCells(),
-                                   const SfMask& mask = SfMask());
+// temporary storage in c->gf_tmp.  Every segment [d_begin[s], d_end[s]) is sorted on its own.  Several segments: the bounds
+// are read on the device.  ONE segment (a detector on one image): its two bounds cross to the host, with one wait, for a
+// device-wide sort of that range, and stay in *hb (hb->known on entry: they are there already, no wait).
+// d_also: up to two further words of the detector's control block to bring along with the bounds (-> also).
+struct SfSortBounds {
+  unsigned begin = 0, end = 0;
+  bool known = false;
+  const unsigned* d_also[2] = {nullptr, nullptr};
+  unsigned also[2] = {0, 0};
+  int n() const { return (int)(end - begin); }
+};
+int sf_sort_segments(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total, unsigned n_segments,
+                     const unsigned* d_begin, const unsigned* d_end, unsigned bit0, unsigned bit1, bool descending,
+                     SfSortBounds* hb);
+// ---- the five detectors, one launcher each: n_img >= 1 images of one size img_stride bytes apart, d_kpts_out [n_img][cap]
+// and d_n_out [n_img] on the device.  Counts, bounds and flags of every image stay on the device, where the kernels read
+// them; only the sort of a lone image (sf_sort_segments) waits for the host.  max_features <= 0 (no limit) is for n_img
+// == 1 alone: several images' emit grids are sized by it, a lone image's by the count that its sort has brought.
+// SfDetectOne: the counts that the single-image entry points of SURF and SIFT (sf_detect.hip; n_img == 1) get back with
+// that same wait, so that they wait no more often than they must.  Passing one says that the call is a single call, not
+// a batch's chunk: its overflow goes to a word of its own and (SIFT) its pyramid is remembered.
+struct SfDetectOne {
+  unsigned count[2] = {0, 0};                  // SURF: the maxima found; SIFT: the extrema and the keypoints found
+};
+// limitKeypoints: what an image keeps of the n it found
+inline int sf_limit_keypoints(int n, int max_features) { return max_features > 0 && n > max_features ? max_features : n; }
+// SIFT cuts its list once, at the smaller positive of retainBest(n_features) and limitKeypoints(max_features); 0: no cut
+__host__ __device__ inline int sf_sift_limit(int n_features, int max_features) {
+  int limit = n_features > 0 ? n_features : 0;
+  if (max_features > 0 && (limit == 0 || max_features < limit)) limit = max_features;
+  return limit;
+}
+inline int sf_check_limit(sf_context* c, int n_img, int max_features) {
+  if (n_img > 1 && max_features < 1) return sf_fail(c, SF_EINVAL, "a detector on %d images needs max_features >= 1, not %d", n_img, max_features);
+  return SF_OK;
+}
+int sf_launch_detect_corners(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
+                             int pitch, int max_corners, double quality_level, double min_distance,
+                             sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out, const SfCells& cells = SfCells(),
+                             const SfMask& mask = SfMask());
 // the pyramid of the two stereo paths (k_lk.hip builds it, k_lk_track and k_stereo_bm read it)
 constexpr int LK_MAX_LEVELS = 16;
 struct LkLevel {
@@ -870,7 +894,7 @@ int sf_launch_stereo_flow_batch(sf_context* c, const uint8_t* d_left, const uint
 // The descriptor of the handle's feature type: row bytes, device test table, ORB parameters (NULL: BRIEF rows, else ORB
 // rows), the pyramid of ORB (NULL: one level; else ORB rows on the keypoint's own level, type 2), the FREAK tables (NULL
 // unless the type is 3 or 5).  pyr_stride 0: the
-// extraction builds the pyramid of its one image; else sf_launch_detect_orb_batch has left the pyramids of the call's
+// extraction builds the pyramid of its one image; else sf_launch_detect_orb has left the pyramids of the call's
 // images in c->orb_pyr, pyr_stride bytes apart, and the extraction reads them there
 struct ExtractKind {
   int bytes = 0;
@@ -882,50 +906,47 @@ struct ExtractKind {
   const SfSurfTables* surf = nullptr;     // not null: SURF rows (bytes 256 or 512, float32; the rest unused)
   bool has_sift = false;                  // true: SIFT rows (bytes 512, float32, or 128 with sift.u8; `sift` says how, the rest unused)
   SfSiftKind sift;                        // read under has_sift: one image per call, or the chunk the batch detector has left
-  // sf_launch_detect_surf_batch has left the integral images of the call's images in c->ex_integral: the extraction reads
+  // sf_launch_detect_surf has left the integral images of the call's images in c->ex_integral: the extraction reads
   // them there and builds none (as pyr_stride for ORB's pyramids)
   bool integral_ready = false;
 };
 // the integral image of one image into c->ex_integral (k_extract.hip): (height + 1) x (width + 1) int32
 int sf_launch_integral(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const int32_t** S_out);
-// the fast-Hessian detector of SURF + limitKeypoints (k_surf.hip); prm validated by the caller
-int sf_launch_detect_surf(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
 // the integral images of n_img images img_stride bytes apart into c->ex_integral, *s_stride entries apart (k_extract.hip)
 int sf_launch_integral_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
                              int pitch, const int32_t** S_out, size_t* s_stride);
 // the SIFT detector + limitKeypoints (k_sift.hip); prm validated by the caller
 int sf_sift_validate(sf_context* c, const sf_sift_params& p);
 int sf_sift_plan_host(sf_context* c, int width, int height, const sf_sift_params& p, SfSiftPlan* P);
-int sf_launch_detect_sift(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out);
 int sf_sift_build_pyramid(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, const sf_sift_params* prm);
 int sf_sift_copy_plane(sf_context* c, int octave, int layer, int dog, int16_t* d_out);
 // the host arithmetic of SIFT's batch form, no device call (c may be null); candidate_cap 0 = SIFT_MAX_CANDIDATES,
 // forced_chunk 0 = what SIFT_BATCH_WORKSPACE_BYTES allows
 int sf_sift_batch_plan_host(sf_context* c, int width, int height, const sf_sift_params& p, int n, unsigned candidate_cap,
                             int forced_chunk, SfSiftBatchPlan* out);
-// the plan under the handle's limits into c->sift_batch, every buffer of the batch detector, and the blur tables of p (the
-// one wait, when they differ from the handle's): a batch call's last step before its first launch
+// the plan under the handle's limits into c->sift_batch, every buffer of the detector, and the blur tables of p (the one
+// wait, when they differ from the handle's): a call's last step before its first launch
 int sf_sift_batch_reserve(sf_context* c, int width, int height, const sf_sift_params& p, int n_img);
 // resets the call's counter of overflowed keyframes and retires the single call's pyramid (on the stream, no wait)
 int sf_sift_batch_begin(sf_context* c);
-// the detector on ONE chunk (n_img <= c->sift_batch.chunk images of the size reserved for) with no host round trip:
-// d_kpts_out [n_img][cap], d_n_out [n_img] on the device; the chunk's pyramids stay in c->sift_planes for the extraction
-int sf_launch_detect_sift_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                int pitch, int max_features, const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out);
+// the SIFT detector + limitKeypoints on ONE chunk (n_img <= c->sift_batch.chunk images of the size reserved for); the
+// chunk's pyramids stay in c->sift_planes for the extraction
+int sf_launch_detect_sift(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int max_features, const sf_sift_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out,
+                          SfDetectOne* one = nullptr);
 // the host arithmetic of SURF's batch form, no device call (c may be null); candidate_cap 0 = SURF_MAX_CANDIDATES,
 // forced_chunk 0 = what SURF_BATCH_WORKSPACE_BYTES allows
 int sf_surf_batch_plan_host(sf_context* c, int width, int height, const sf_surf_params& p, int n, unsigned candidate_cap,
                             int forced_chunk, SfSurfBatchPlan* out);
-// the plan under the handle's limits (sf_debug_surf_limits) and every buffer sf_launch_detect_surf_batch takes
+// the plan under the handle's limits (sf_debug_surf_limits) and every buffer sf_launch_detect_surf takes
 int sf_surf_batch_reserve(sf_context* c, int width, int height, const sf_surf_params& p, int n_img, SfSurfBatchPlan* plan);
-// the same detector on n_img images of one size with no host round trip: d_kpts_out [n_img][cap], d_n_out [n_img] on the
-// device; the integral images of all images stay in c->ex_integral for the extraction
-int sf_launch_detect_surf_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                int pitch, int max_features, const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out);
+// the candidate capacity of one image: SURF_MAX_CANDIDATES, or what sf_debug_surf_limits has put in its place
+unsigned sf_surf_candidate_cap(const sf_context* c);
+// the fast-Hessian detector of SURF + limitKeypoints (k_surf.hip); prm validated by the caller.  The integral images of all
+// images stay in c->ex_integral for the extraction
+int sf_launch_detect_surf(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int max_features, const sf_surf_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out,
+                          SfDetectOne* one = nullptr);
 // host halves of the FREAK tables (k_freak.hip): the orientation pairs' weights from scale 0 / orientation 0 of a pattern,
 // and the device layout of the selected pairs
 void sf_freak_orientation_table(const float* pattern, int32_t* orient /* [45][4] */);
@@ -942,16 +963,10 @@ int sf_launch_depth_mask(sf_context* c, const SfDepthIn& depth, int n_img, int w
                          uint8_t* d_mask, int mask_pitch, size_t mask_stride);
 int sf_launch_depth_points_only(sf_context* c, const SfDepthIn& depth, int width, int height, const sf_keypoint* d_kpts, int n,
                                 const sf_stereo_camera* cam, float* d_xyz, uint8_t* d_valid);
-int sf_launch_detect_corners(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_corners,
-                             double quality_level, double min_distance, sf_keypoint* d_kpts_out, int cap,
-                             int32_t* n_out, const SfMask& mask = SfMask());
 // FAST-9/16 + limitKeypoints (k_fast.hip); prm validated by the caller
-int sf_launch_detect_fast(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                          const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* n_out,
-                          const SfMask& mask = SfMask());
-int sf_launch_detect_fast_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                                int pitch, int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap,
-                                int32_t* d_n_out, const SfCells& cells = SfCells(), const SfMask& mask = SfMask());
+int sf_launch_detect_fast(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                          int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out,
+                          const SfCells& cells = SfCells(), const SfMask& mask = SfMask());
 // one level of FAST on n_img images img_stride bytes apart: k_fast_score + k_fast_candidates (image i: score plane at
 // + i * plane_stride, keys at + i * key_cap, keys = score << 32 | pixel index in arrival order, count[i] the corners found;
 // zeroed by the caller)
@@ -963,14 +978,10 @@ SfOrbPyr sf_orb_pyr_layout(int width, int height, float scale_factor, int n_leve
 void sf_orb_quotas(int nfeatures, float scale_factor, int n_levels, int* quota);
 // levels >= 1 of n_img images (img_stride bytes apart) into c->orb_pyr, image i's at + i * P.total
 int sf_launch_orb_pyramid(sf_context* c, const uint8_t* d_image, int pitch, const SfOrbPyr& P, int n_img, size_t img_stride);
-int sf_launch_detect_orb(sf_context* c, const uint8_t* d_image, int width, int height, int pitch, int max_features,
-                         const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out, int cap,
-                         int32_t* n_out);
-// the same on n_img images of one size with no host round trip: d_kpts_out [n_img][cap], d_n_out [n_img] on the device; the
-// pyramids stay in c->orb_pyr (P.total bytes apart) for the extraction
-int sf_launch_detect_orb_batch(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height,
-                               int pitch, int max_features, const sf_orb_detector_params* det, const sf_orb_params* orb,
-                               sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out);
+// max_features >= 1; the pyramids stay in c->orb_pyr (P.total bytes apart) for the extraction
+int sf_launch_detect_orb(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
+                         int max_features, const sf_orb_detector_params* det, const sf_orb_params* orb, sf_keypoint* d_kpts_out,
+                         int cap, int32_t* d_n_out);
 // k_orb_angle (k_extract.hip) on keypoints in LEVEL coordinates whose octave names their level: n_img images img_stride
 // apart, their pyramids pyr_stride apart in c->orb_pyr, n_max keypoints apiece, d_n [n_img] read on the device
 int sf_launch_orb_angle_levels(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int pitch, const SfOrbPyr& P,

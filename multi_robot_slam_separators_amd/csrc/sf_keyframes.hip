@@ -157,21 +157,21 @@ static int family_detect(sf_context* c, const SfFeatureType& t, const BatchPlan&
   switch (t.family) {
     case BATCH_ORB:                                        // (keypoints in level-0 coordinates; the pyramids stay for the extraction;
       kind->pyr_stride = sf_orb_pyr_layout(width, height, c->orb_det.scale_factor, c->orb_det.n_levels).total;   // no ROI: sf_front_plan)
-      return sf_launch_detect_orb_batch(c, d_images, image_stride, m, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
+      return sf_launch_detect_orb(c, d_images, image_stride, m, width, height, pitch, maxf, &c->orb_det, &c->orb, d_kpts, maxf, d_n);
     case BATCH_SURF:                                       // (no ROI, no grid: sf_front_plan, sf_grid_plan; the integral images stay
       kind->integral_ready = true;                         // for the extraction)
-      return sf_launch_detect_surf_batch(c, d_images, image_stride, m, width, height, pitch, maxf, &c->surf, d_kpts, maxf, d_n);
+      return sf_launch_detect_surf(c, d_images, image_stride, m, width, height, pitch, maxf, &c->surf, d_kpts, maxf, d_n);
     case BATCH_SIFT:                                       // (likewise; the chunk's pyramids stay for the extraction)
       kind->sift.batch = true;
-      return sf_launch_detect_sift_batch(c, d_images, image_stride, m, width, height, pitch, maxf, &c->sift, d_kpts, maxf, d_n);
+      return sf_launch_detect_sift(c, d_images, image_stride, m, width, height, pitch, maxf, &c->sift, d_kpts, maxf, d_n);
     case BATCH_GENERIC:
       if (fp.grid())                                       // the cells as the detector's images, joined by k_grid_gather
         return sf_grid_detect(c, fp, plan.dp, d_images, image_stride, m, pitch, d_kpts, d_n, mask);
       if (t.corners == CORNERS_FAST)
-        return sf_launch_detect_fast_batch(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n, SfCells(),
-                                           sf_mask_at(mask, fp.x, fp.y));
-      return sf_launch_detect_corners_batch(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, plan.dp.quality_level,
-                                            plan.dp.min_distance, d_kpts, maxf, d_n, SfCells(), sf_mask_at(mask, fp.x, fp.y));
+        return sf_launch_detect_fast(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, &c->fast, d_kpts, maxf, d_n, SfCells(),
+                                     sf_mask_at(mask, fp.x, fp.y));
+      return sf_launch_detect_corners(c, d_roi, image_stride, m, fp.w, fp.h, pitch, maxf, plan.dp.quality_level,
+                                      plan.dp.min_distance, d_kpts, maxf, d_n, SfCells(), sf_mask_at(mask, fp.x, fp.y));
   }
   return SF_EINVAL;
 }

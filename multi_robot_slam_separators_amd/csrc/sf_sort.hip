@@ -23,30 +23,53 @@ static int sort_with_tmp(sf_context* c, Sort sort) {
   return SF_OK;
 }
 
-// n keys by their bits [bit0, bit1), ascending or descending
-int sf_sort_keys(sf_context* c, const unsigned long long* in, unsigned long long* out, size_t n, unsigned bit0, unsigned bit1,
-                 bool descending) {
+// n keys by their bits [bit0, bit1), ascending or descending: one device-wide sort
+static int sort_keys(sf_context* c, const unsigned long long* in, unsigned long long* out, size_t n, unsigned bit0, unsigned bit1,
+                     bool descending) {
   return sort_with_tmp(c, [&](void* tmp, size_t& tmp_bytes) {
     return descending ? rocprim::radix_sort_keys_desc(tmp, tmp_bytes, in, out, n, bit0, bit1, c->stream)
                       : rocprim::radix_sort_keys(tmp, tmp_bytes, in, out, n, bit0, bit1, c->stream);
   });
 }
 
-// every segment [d_begin[s], d_end[s]) of the n_total keys on its own, ascending or descending; the bounds are read on the
-// device, keys outside every segment are neither read nor written
-int sf_sort_keys_segmented(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
-                           unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0, unsigned bit1,
-                           bool descending) {
-  return sort_with_tmp(c, [&](void* tmp, size_t& tmp_bytes) {
-    return descending ? rocprim::segmented_radix_sort_keys_desc(tmp, tmp_bytes, in, out, n_total, n_segments, d_begin, d_end,
-                                                                bit0, bit1, c->stream)
-                      : rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, in, out, n_total, n_segments, d_begin, d_end, bit0,
-                                                           bit1, c->stream);
-  });
-}
-
-int sf_sort_keys_segmented_desc(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total,
-                                unsigned n_segments, const unsigned* d_begin, const unsigned* d_end, unsigned bit0,
-                                unsigned bit1) {
-  return sf_sort_keys_segmented(c, in, out, n_total, n_segments, d_begin, d_end, bit0, bit1, true);
+// The detectors' sort: image s's keys are the segment [d_begin[s], d_end[s]) of the n_total keys, bounds its decide kernel
+// has written on the device; keys outside every segment are neither read nor written.  Several images: rocprim's segmented
+// sort reads the bounds on the device, nothing waits.  It gives each segment to ONE workgroup, though, and a lone image
+// has tens of thousands of keys in its one segment -- so one image is a device-wide sort sized by the host: its two
+// bounds cross to the host here, with the one wait a single call has for its count anyway, and come back in `hb` for
+// whatever else the caller sizes by them.  The rule goes by n_segments alone, so a batch call with one keyframe, the last
+// one-image chunk of a SURF or SIFT batch and a grid of one cell wait once here too.  A caller with several sorts over one range (ORB) passes the same `hb` again:
+// bounds that are known are not fetched twice.
+int sf_sort_segments(sf_context* c, const unsigned long long* in, unsigned long long* out, unsigned n_total, unsigned n_segments,
+                     const unsigned* d_begin, const unsigned* d_end, unsigned bit0, unsigned bit1, bool descending,
+                     SfSortBounds* hb) {
+  if (n_segments > 1)
+    return sort_with_tmp(c, [&](void* tmp, size_t& tmp_bytes) {
+      return descending ? rocprim::segmented_radix_sort_keys_desc(tmp, tmp_bytes, in, out, n_total, n_segments, d_begin, d_end,
+                                                                  bit0, bit1, c->stream)
+                        : rocprim::segmented_radix_sort_keys(tmp, tmp_bytes, in, out, n_total, n_segments, d_begin, d_end, bit0,
+                                                             bit1, c->stream);
+    });
+  if (!hb->known) {
+    // The bounds, and the further words that the caller wants with them (hb->d_also), with ONE wait.  A single call's
+    // words lie in one control block, within 64 words of each other, and then cross in one copy as the parent's count
+    // did; words further apart (the last one-image chunk of a large batch) cross one by one.  The addresses are compared
+    // as integers: they need not belong to one allocation.  That one copy is cheaper than four has not been measured.
+    const unsigned* src[4] = {d_begin, d_end, hb->d_also[0], hb->d_also[1]};
+    unsigned* dst[4] = {&hb->begin, &hb->end, &hb->also[0], &hb->also[1]};
+    uintptr_t lo = (uintptr_t)d_begin, hi = lo;
+    for (const unsigned* p : src)
+      if (p) { lo = std::min(lo, (uintptr_t)p); hi = std::max(hi, (uintptr_t)p); }
+    unsigned words[64];
+    const bool one_copy = hi - lo < sizeof(words);
+    if (one_copy) SF_HIP(c, hipMemcpyAsync(words, (const void*)lo, hi - lo + 4, hipMemcpyDeviceToHost, c->stream));
+    for (int i = 0; i < 4 && !one_copy; ++i)
+      if (src[i]) SF_HIP(c, hipMemcpyAsync(dst[i], src[i], 4, hipMemcpyDeviceToHost, c->stream));
+    SF_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 4 && one_copy; ++i)
+      if (src[i]) *dst[i] = words[((uintptr_t)src[i] - lo) / 4];
+    hb->known = true;
+  }
+  if (hb->end <= hb->begin) return SF_OK;
+  return sort_keys(c, in + hb->begin, out + hb->begin, (size_t)(hb->end - hb->begin), bit0, bit1, descending);
 }
