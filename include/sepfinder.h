@@ -116,6 +116,10 @@ extern "C" {
 /* 8, additions: sf_kfblob_header, sf_kfblob_entry, SF_KFBLOB_MAGIC, sf_store_export_plan, sf_store_export_keyframes_device,
       sf_store_import_keyframes_device, sf_store_wire_status (store slots as one block of bytes, both directions on the
       device).  New calls only; the version number, sizeof(sf_params) and SF_K_COUNT stay.                             */
+/* 8, additions: sf_depth_size, sf_depth_set_size, sf_depth_get_size, sf_depth_interpolate_device,
+      sf_depth_interpolation_factor (RGB-D keyframes from a decimated depth image, upstream's util2d::interpolate path).
+      A fresh handle holds {0, 0}, with which every depth call behaves and refuses as before; the version number,
+      sizeof(sf_params) and SF_K_COUNT stay.                                                                           */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -1116,9 +1120,9 @@ int  sf_add_keyframes_sift_u8_batch_device(sf_handle h, const uint8_t* d_left, c
    generateKeypoints3DDepth -> projectDepthTo3D(smoothing = true) -> util2d::getDepth(depthErrorRatio 0.02,
    estWithNeighborsIfNull false) -- and the detector mask Feature2D::generateKeypoints makes of the depth image
    (myRegistrationVis.cpp:271-284, Vis/DepthAsMask) [upstream rtabmap, restated in tests/depth_ref.py; DESIGN.md section 3
-   lists what the restatement decides].  The depth image is registered to the image and has its width and height (a
-   decimated depth image, upstream's util2d::interpolate path, cannot be passed: not built); its rows are depth_pitch bytes
-   apart.  The camera is read as an sf_stereo_camera: fx, fy, cx, cy, local_transform, min_depth and max_depth are used,
+   lists what the restatement decides].  The depth image is registered to the image and has its width and height, or,
+   after sf_depth_set_size, a size of its own that is not larger (a decimated depth image, upstream's util2d::interpolate
+   path: below); its rows are depth_pitch bytes apart.  The camera is read as an sf_stereo_camera: fx, fy, cx, cy, local_transform, min_depth and max_depth are used,
    baseline and cx_right ignored.
      3D point of keypoint (x, y), float32 in this order: u = (int)(x + 0.5f), v = (int)(y + 0.5f) (u == width && x < width:
      u = width - 1, likewise v; outside the image, or a coordinate that is not finite: no depth).  d = the depth at (u, v) in
@@ -1140,11 +1144,58 @@ void sf_depth_defaults(sf_depth_params* p);     /* {1}: rtabmap's default */
 /* Values other than 0 or 1 return SF_EINVAL and change nothing.                                                      */
 int  sf_depth_set_params(sf_handle h, const sf_depth_params* params);
 int  sf_depth_get_params(sf_handle h, sf_depth_params* params);
+/* A decimated depth image (myRegistrationVis.cpp:271-284: a depth image whose size divides the image's is enlarged with
+   util2d::interpolate(depth, factor, 0.1f) for the detector mask; generateKeypoints3D at :382 reads the small image with
+   scaled intrinsics).  The size is handle state like sf_depth_params: once set, width and height of EVERY depth call stay
+   the image's, the depth image is read as depth_width x depth_height, and depth_pitch and depth_stride are checked
+   against that size.  The host call uploads depth_height rows of depth_width elements.  A size equal to the image's gives
+   the bytes of {0, 0}.  At a call, a depth image larger than the image in either dimension returns SF_EINVAL ("not
+   built") and changes nothing.
+     the factor: f = height / depth_height iff height % depth_height == 0, width % depth_width == 0 and height /
+     depth_height == width / depth_width (:274-276); else 0.  f = 1: nothing is interpolated.  f = 0: the depth keyframe
+     calls build NO mask -- the detector runs unmasked whatever depth_as_mask says, as in the reference, where depthMask
+     stays empty -- and the 3D points are still taken from the small image; sf_depth_mask_device returns SF_EINVAL.
+     (A handle of type 0, 1 or 2 with depth_as_mask = 1 is refused as before, at every size.)
+     interpolation, as remembered from upstream rtabmap, not from the reference tree (restated in tests/depth_interp_ref.py;
+     DESIGN.md section 3): D the dw x dh input, f >= 2, the output dw f x dh f, zero at the start; float32 in the order
+     written, unfused.  A sample is present iff 0 < v < 65535 (uint16; its value (float)v, raw millimetres) or finite and
+     > 0 (float32).  Cell (a, b), 1 <= a < dw, 1 <= b < dh, has the corners TL = D[b-1][a-1], TR = D[b-1][a], BL =
+     D[b][a-1], BR = D[b][a]; it is valid iff all four are present and, with e = 0.1f * (((TL + TR) + BL) + BR) / 4.0f,
+     each of |TL-TR|, |TL-BL|, |TL-BR|, |TR-BL|, |TR-BR|, |BL-BR| is <= e.  A valid cell writes the pixels x = (a-1) f + p,
+     y = (b-1) f + q, p and q in 0 .. f: st = (TR - TL) / (float)f, sb = (BR - BL) / (float)f, top = TL + st * (float)p,
+     bot = BL + sb * (float)p, value = top + ((bot - top) / (float)f) * (float)q; a uint16 output holds
+     (uint16_t)(int)value.  Cells are visited with b outer and a inner and a later cell overwrites an earlier one: a pixel
+     holds the value of the last valid cell among the at most four that cover it.  Pixels with x > (dw-1) f or y >
+     (dh-1) f, and pixels no valid cell covers, stay 0.  The mask is the mask above of that image (uint16: value * 0.001f).
+     3D point from a small image: rx = 1.0f / ((float)width / (float)depth_width), ry likewise; the keypoint is read at
+     xs = x * rx, ys = y * ry; pixel and smoothing as above on the depth_width x depth_height image; cx_ = cx * rx, and
+     if that is not > 0, depth_width / 2 - 0.5f; fx_ = fx * rx; X = (xs - cx_) * depth / fx_, Y alike; limits and
+     local_transform as above.  At the image's size rx = ry = 1.0f.                                                      */
+typedef struct sf_depth_size {
+  int32_t depth_width, depth_height;   /* {0, 0} on a fresh handle: the depth image has the image's size */
+} sf_depth_size;                       /* 8 bytes */
+/* NULL or {0, 0}: the depth image has the image's size; else both >= 1.  One zero or a negative value returns SF_EINVAL
+   and changes nothing.                                                                                                */
+int  sf_depth_set_size(sf_handle h, const sf_depth_size* size);
+int  sf_depth_get_size(sf_handle h, sf_depth_size* out);
+/* No handle, no GPU: the factor above; 0 = none.                                                                      */
+int  sf_depth_interpolation_factor(int32_t width, int32_t height, int32_t depth_width, int32_t depth_height);
+/* util2d::interpolate for n_images depth images of depth_width x depth_height in one launch, asynchronous on the handle's
+   stream: image i at d_depth + i * depth_stride bytes to d_out + i * out_stride, enlarged to depth_width factor x
+   depth_height factor elements of the input's own format, rows out_pitch bytes apart; bytes outside the planes are not
+   written.  Pitches, strides and both addresses are multiples of the element size, nothing more; strides are ignored
+   when n_images = 1.  The handle's sf_depth_size is not read.  factor = 1 is a pitched copy.  SF_EINVAL: factor < 1, an
+   unknown format, a pitch below a row, a pitch, stride or address that is no multiple of the element size, a stride
+   below the rows it holds.  n_images = 0 is SF_OK.                                                                    */
+int  sf_depth_interpolate_device(sf_handle h, const void* d_depth, int32_t depth_format, int32_t depth_width,
+                                 int32_t depth_height, int32_t depth_pitch, size_t depth_stride, int32_t n_images,
+                                 int32_t factor, void* d_out, int32_t out_pitch, size_t out_stride);
 /* The masks of n_images depth images of one size, one launch, asynchronous on the handle's stream: image i at d_depth + i *
    depth_stride bytes to the uint8 plane at d_mask + i * mask_stride (rows of mask_pitch >= width bytes; bytes outside the
    width x height planes are not written).  Strides are ignored when n_images = 1.  SF_EINVAL: unknown format, depth_pitch
    below a row (2 * width or 4 * width), a depth pitch or stride that is no multiple of the element size, a stride below
-   the rows it holds.  n_images = 0 is SF_OK.                                                                          */
+   the rows it holds.  n_images = 0 is SF_OK.  After sf_depth_set_size the depth images have that size, the masks stay
+   width x height: the masks of the interpolated images, which are never in memory (factor 0: SF_EINVAL).              */
 int  sf_depth_mask_device(sf_handle h, const void* d_depth, int32_t depth_format, int32_t width, int32_t height,
                           int32_t depth_pitch, size_t depth_stride, int32_t n_images, float min_depth, float max_depth,
                           uint8_t* d_mask, int32_t mask_pitch, size_t mask_stride);

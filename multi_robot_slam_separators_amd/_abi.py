@@ -226,6 +226,21 @@ def depth_params(depth_as_mask=1):
     return p
 
 
+class DepthSize(C.Structure):
+    """sf_depth_size (include/sepfinder.h): the depth images' own size in the depth calls; {0, 0}: the image's."""
+    _fields_ = [("depth_width", C.c_int32), ("depth_height", C.c_int32)]
+
+
+assert C.sizeof(DepthSize) == 8
+
+
+def depth_size(w=0, h=0):
+    """A fresh handle's value: the depth image has the image's width and height."""
+    s = DepthSize()
+    s.depth_width, s.depth_height = w, h
+    return s
+
+
 def depth_format_of(depth):
     """The sf_depth_format of a depth image given as a uint16 or float32 array."""
     for fmt, dt in DEPTH_DTYPES.items():

@@ -179,8 +179,26 @@ extern "C" int sf_depth_set_params(sf_handle c, const sf_depth_params* params) {
 
 extern "C" int sf_depth_get_params(sf_handle c, sf_depth_params* params) { return get_block(c, params, &sf_context::depth); }
 
+extern "C" int sf_depth_set_size(sf_handle c, const sf_depth_size* size) {
+  if (!c) return SF_EINVAL;
+  const sf_depth_size v = size ? *size : sf_depth_size{0, 0};
+  if (!((v.depth_width == 0 && v.depth_height == 0) || (v.depth_width >= 1 && v.depth_height >= 1)))
+    return sf_fail(c, SF_EINVAL, "sf_depth_set_size: %d x %d is neither {0, 0} (the image's size) nor a size", v.depth_width, v.depth_height);
+  c->depth_size = v;
+  return SF_OK;
+}
+
+extern "C" int sf_depth_get_size(sf_handle c, sf_depth_size* out) { return get_block(c, out, &sf_context::depth_size); }
+
+// myRegistrationVis.cpp:274-276: the factor by which a depth image divides the image, both ways alike; 0: it does not
+extern "C" int sf_depth_interpolation_factor(int32_t width, int32_t height, int32_t depth_width, int32_t depth_height) {
+  if (width < 1 || height < 1 || depth_width < 1 || depth_height < 1) return 0;
+  if (height % depth_height != 0 || width % depth_width != 0 || height / depth_height != width / depth_width) return 0;
+  return height / depth_height;
+}
+
 // what every depth call refuses of its depth images (`call` opens the message): n images of width x height, `stride` bytes apart
-int sf_check_depth(sf_context* c, const char* call, bool present, int format, int width, int height, int pitch, size_t stride, int n) {
+static int sf_check_depth(sf_context* c, const char* call, bool present, int format, int width, int height, int pitch, size_t stride, int n) {
   if (format != SF_DEPTH_U16_MM && format != SF_DEPTH_F32_M)
     return sf_fail(c, SF_EINVAL, "%s: depth format %d unknown (0 = uint16 millimetres, 1 = float32 metres)", call, format);
   const int elem = format == SF_DEPTH_F32_M ? 4 : 2;
@@ -196,20 +214,33 @@ int sf_check_depth(sf_context* c, const char* call, bool present, int format, in
   return SF_OK;
 }
 
+int sf_depth_in(sf_context* c, const char* call, SfDepthIn* D, int width, int height, int n) {
+  if (n == 0) return sf_check_depth(c, call, true, D->format, 1, 1, 4, 0, 0);   // (the format alone)
+  const sf_depth_size& s = c->depth_size;
+  D->w = s.depth_width ? s.depth_width : width;
+  D->h = s.depth_height ? s.depth_height : height;
+  if (D->w > width || D->h > height)
+    return sf_fail(c, SF_EINVAL, "%s: a depth image of %d x %d (sf_depth_set_size) larger than the %d x %d image is not built", call,
+                   D->w, D->h, width, height);
+  return sf_check_depth(c, call, D->p != nullptr, D->format, D->w, D->h, D->pitch, D->stride, n);
+}
+
 extern "C" int sf_depth_mask_device(sf_handle c, const void* d_depth, int32_t depth_format, int32_t width, int32_t height,
                                     int32_t depth_pitch, size_t depth_stride, int32_t n_images, float min_depth, float max_depth,
                                     uint8_t* d_mask, int32_t mask_pitch, size_t mask_stride) {
   if (!c || n_images < 0) return SF_EINVAL;
-  if (n_images == 0) return sf_check_depth(c, "sf_depth_mask_device", true, depth_format, 1, 1, 4, 0, 0);   // (the format alone)
-  int rc = sf_check_depth(c, "sf_depth_mask_device", d_depth, depth_format, width, height, depth_pitch, depth_stride, n_images);
-  if (rc != SF_OK) return rc;
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = n_images > 1 ? depth_stride : 0;
+  int rc = sf_depth_in(c, "sf_depth_mask_device", &D, width, height, n_images);
+  if (rc != SF_OK || n_images == 0) return rc;
+  if (sf_depth_interpolation_factor(width, height, D.w, D.h) == 0)
+    return sf_fail(c, SF_EINVAL, "sf_depth_mask_device: a depth image of %d x %d (sf_depth_set_size) does not divide the %d x %d image: "
+                   "no mask (the depth keyframe calls run their detector without one)", D.w, D.h, width, height);
   if (n_images > 65535) return sf_fail(c, SF_ERANGE, "sf_depth_mask_device: %d images (at most 65535 per call)", n_images);
   if (!d_mask || mask_pitch < width) return sf_fail(c, SF_EINVAL, "sf_depth_mask_device: mask missing or malformed (width %d, mask_pitch %d)", width, mask_pitch);
   if (n_images > 1 && mask_stride < (size_t)mask_pitch * (height - 1) + (size_t)width)
     return sf_fail(c, SF_EINVAL, "sf_depth_mask_device: mask stride %zu is less than a plane (%d rows of pitch %d)", mask_stride, height, mask_pitch);
   SF_HIP(c, hipSetDevice(c->device));
-  SfDepthIn D;
-  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = n_images > 1 ? depth_stride : 0;
   return sf_launch_depth_mask(c, D, n_images, width, height, min_depth, max_depth, d_mask, mask_pitch, n_images > 1 ? mask_stride : 0);
 }
 
@@ -217,14 +248,45 @@ extern "C" int sf_depth_points_device(sf_handle c, const void* d_depth, int32_t 
                                       int32_t depth_pitch, const sf_keypoint* d_kpts, int32_t n, const sf_stereo_camera* cam,
                                       float* d_xyz_out, uint8_t* d_valid_out) {
   if (!c || !cam || n < 0) return SF_EINVAL;
-  int rc = sf_check_depth(c, "sf_depth_points_device", d_depth, depth_format, width, height, depth_pitch, 0, 1);
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch;
+  int rc = sf_depth_in(c, "sf_depth_points_device", &D, width, height, 1);
   if (rc != SF_OK) return rc;
   if (n > 0 && (!d_kpts || !d_xyz_out)) return sf_fail(c, SF_EINVAL, "sf_depth_points_device: keypoints or output array missing");
   if (n == 0) return SF_OK;
   SF_HIP(c, hipSetDevice(c->device));
-  SfDepthIn D;
-  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch;
   return sf_launch_depth_points_only(c, D, width, height, d_kpts, n, cam, d_xyz_out, d_valid_out);
+}
+
+extern "C" int sf_depth_interpolate_device(sf_handle c, const void* d_depth, int32_t depth_format, int32_t depth_width,
+                                           int32_t depth_height, int32_t depth_pitch, size_t depth_stride, int32_t n_images,
+                                           int32_t factor, void* d_out, int32_t out_pitch, size_t out_stride) {
+  static const char* const call = "sf_depth_interpolate_device";
+  if (!c || n_images < 0) return SF_EINVAL;
+  if (n_images == 0) return sf_check_depth(c, call, true, depth_format, 1, 1, 4, 0, 0);   // (the format alone)
+  int rc = sf_check_depth(c, call, d_depth, depth_format, depth_width, depth_height, depth_pitch, depth_stride, n_images);
+  if (rc != SF_OK) return rc;
+  if (factor < 1) return sf_fail(c, SF_EINVAL, "%s: factor %d is below 1", call, factor);
+  if (n_images > 65535) return sf_fail(c, SF_ERANGE, "%s: %d images (at most 65535 per call)", call, n_images);
+  const long long ow = (long long)depth_width * factor, oh = (long long)depth_height * factor;
+  if (ow > 262140 || oh > 262140) return sf_fail(c, SF_ERANGE, "%s: an enlarged image of %lld x %lld pixels (at most 262140 a side)", call, ow, oh);
+  const int elem = depth_format == SF_DEPTH_F32_M ? 4 : 2;
+  if (((uintptr_t)d_depth | (uintptr_t)d_out) % (uintptr_t)elem)
+    return sf_fail(c, SF_EINVAL, "%s: an image address is no multiple of the %d bytes of a pixel", call, elem);
+  // the enlarged images: what the input's own checks ask of a pitch and a stride, under the output's name
+  if (!d_out || (long long)out_pitch < elem * ow)
+    return sf_fail(c, SF_EINVAL, "%s: output missing or out_pitch %d less than a row of %lld pixels of %d bytes", call, out_pitch, ow, elem);
+  if (out_pitch % elem) return sf_fail(c, SF_EINVAL, "%s: out_pitch %d is no multiple of the %d bytes of a pixel", call, out_pitch, elem);
+  if (n_images > 1) {
+    if (out_stride % (size_t)elem) return sf_fail(c, SF_EINVAL, "%s: output stride %zu is no multiple of the %d bytes of a pixel", call, out_stride, elem);
+    if (out_stride < (size_t)out_pitch * (size_t)(oh - 1) + (size_t)(elem * ow))
+      return sf_fail(c, SF_EINVAL, "%s: output stride %zu is less than an image (%lld rows of pitch %d)", call, out_stride, oh, out_pitch);
+  }
+  SF_HIP(c, hipSetDevice(c->device));
+  SfDepthIn D;
+  D.p = d_depth; D.format = depth_format; D.pitch = depth_pitch; D.stride = n_images > 1 ? depth_stride : 0;
+  D.w = depth_width; D.h = depth_height;
+  return sf_launch_depth_interp(c, D, n_images, factor, d_out, out_pitch, n_images > 1 ? out_stride : 0);
 }
 
 extern "C" int sf_detect_orb_device(sf_handle c, const uint8_t* d_image, int32_t width, int32_t height, int32_t pitch,

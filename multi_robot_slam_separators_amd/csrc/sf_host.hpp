@@ -103,8 +103,13 @@ inline SfMask sf_mask_at(const SfMask& mask, int x, int y) {
   if (m.p) m.p += (size_t)y * mask.pitch + x;
   return m;
 }
-// what the depth calls refuse of their depth images (sf_detect.hip); `call` opens the message
-int sf_check_depth(sf_context* c, const char* call, bool present, int format, int width, int height, int pitch, size_t stride, int n);
+// The n depth images of a depth call on width x height images (sf_detect.hip): D's own size from the handle (sf_depth_set_size;
+// unset: the image's), then what the depth calls refuse of such images; `call` opens the message.  n = 0: the format alone
+int sf_depth_in(sf_context* c, const char* call, SfDepthIn* D, int width, int height, int n);
+// whether the depth keyframe calls make a mask of D on width x height images: Vis/DepthAsMask, and a size that divides the image's
+inline bool sf_depth_masks(const sf_context* c, const SfDepthIn& D, int width, int height) {
+  return c->depth.depth_as_mask && sf_depth_interpolation_factor(width, height, D.w ? D.w : width, D.h ? D.h : height) != 0;
+}
 int sf_check_gftt(sf_context* c, double quality_level, double min_distance);
 int sf_gftt_validate(sf_context* c, const sf_gftt_params& g);
 // the GFTT window on what the detector is given (`what`: an image, a ROI, a grid cell): a side below GFTT/BlockSize is refused

@@ -402,7 +402,9 @@ struct sf_context {
   sf_stereo_params stereo = {1, 1};
   // the depth keyframe calls (sf_depth_set_params; k_depth.hip): Vis/DepthAsMask, the detector mask made of the depth image.
   // dp_depth / dp_mask: the device copy of the host call's depth image, the mask planes of a call (the images' pitch and stride)
+  // depth_size: the depth images' own size (sf_depth_set_size), {0, 0} = the image's
   sf_depth_params depth = {1};
+  sf_depth_size depth_size = {0, 0};
   Buf dp_depth, dp_mask;
   // Vis/GridRows x Vis/GridCols (sf_grid_set_params; k_grid.hip): the detector of types 4, 6 and 8 runs per cell of the
   // ROI; 1 x 1 = no cells.  ft_cells: every cell's count, then every cell's keypoints, before k_grid_gather joins them
@@ -760,11 +762,13 @@ struct SfMask {
   size_t stride = 0;
   SfCells cells;
 };
-// the depth images of an extraction launch (sf_depth_format): image i at p + i * stride bytes, rows `pitch` bytes apart
+// the depth images of an extraction launch (sf_depth_format): image i at p + i * stride bytes, rows `pitch` bytes apart.
+// w x h: their own size (sf_depth_set_size; sf_depth_in fills it), 0 = the image's
 struct SfDepthIn {
   const void* p = nullptr;
   int format = 0, pitch = 0;
   size_t stride = 0;
+  int w = 0, h = 0;
 };
 
 // ---- workspace of the corner detectors (k_gftt.hip, k_fast.hip), one image and a batch alike --------------------------
@@ -961,6 +965,8 @@ int sf_launch_extract_batch(sf_context* c, const uint8_t* d_left, size_t img_str
 // n keypoints of one depth image, xyz [n][3] and valid [n] (the building block: no keep flags, no store)
 int sf_launch_depth_mask(sf_context* c, const SfDepthIn& depth, int n_img, int width, int height, float min_depth, float max_depth,
                          uint8_t* d_mask, int mask_pitch, size_t mask_stride);
+// util2d::interpolate: n depth images of depth.w x depth.h enlarged by `factor` >= 1 in their own format (factor 1: copied)
+int sf_launch_depth_interp(sf_context* c, const SfDepthIn& depth, int n_img, int factor, void* d_out, int out_pitch, size_t out_stride);
 int sf_launch_depth_points_only(sf_context* c, const SfDepthIn& depth, int width, int height, const sf_keypoint* d_kpts, int n,
                                 const sf_stereo_camera* cam, float* d_xyz, uint8_t* d_valid);
 // FAST-9/16 + limitKeypoints (k_fast.hip); prm validated by the caller

@@ -7,11 +7,11 @@
 // A keyframe's second input: the right image with the stereo stage that reads it (flow: its parameters), or a depth image --
 // under Vis/DepthAsMask with the detector's mask -- and no stereo stage.  Host or device pointers, as the call's left image.
 // `call`: the name that a depth call's refusals carry in front; the stereo calls carry none.  { right, flow } is a stereo
-// keyframe's, { nullptr, nullptr, &depth, call } a depth keyframe's
+// keyframe's, { nullptr, nullptr, &depth, call } a depth keyframe's (the call's checks fill in the depth images' own size)
 struct SecondInput {
   const uint8_t* right = nullptr;
   const sf_stereo_flow_params* flow = nullptr;
-  const SfDepthIn* depth = nullptr;
+  SfDepthIn* depth = nullptr;
   const char* call = "";
 };
 
@@ -83,9 +83,9 @@ extern "C" int sf_extract_keyframe_depth_device(sf_handle c, const uint8_t* d_le
                                                 int32_t depth_pitch, int32_t n, const sf_stereo_camera* cam, int32_t* out_slot,
                                                 int32_t* out_rows, uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c || !cam || n < 0) return SF_EINVAL;
-  const int rc = sf_check_depth(c, "sf_extract_keyframe_depth_device", d_depth, depth_format, width, height, depth_pitch, 0, 1);
+  SfDepthIn D{d_depth, depth_format, depth_pitch};
+  const int rc = sf_depth_in(c, "sf_extract_keyframe_depth_device", &D, width, height, 1);
   if (rc != SF_OK) return rc;
-  const SfDepthIn D{d_depth, depth_format, depth_pitch};
   return extract_keyframe(c, d_left, width, height, pitch, d_kpts, nullptr, nullptr, n, cam, out_slot, out_rows, d_desc_out,
                           d_xyz_out, d_kpts_out, false, &D);
 }
@@ -189,16 +189,16 @@ static int check_depth_as_mask(sf_context* c, const char* call) {
 // A host call's images on the device.  The left image, and the right image if there is one, as gray planes in c->ft_images:
 // rows `width` bytes apart, planes img_bytes apart.  format < 0 or mono8: the pitched copy is the upload; a colour format: the
 // images as they are (rows padded to 16 bytes: the conversion's wide path), then all planes in one launch.  Behind them the
-// depth image if there is one, in c->dp_depth: *d_depth describes the copy
+// depth image if there is one, its own h rows of w elements, in c->dp_depth: *d_depth describes the copy
 static int upload_inputs(sf_context* c, const uint8_t* left, const SecondInput& in, int format, int width, int height, int pitch,
                          size_t img_bytes, SfDepthIn* d_depth) {
   const uint8_t* const src[2] = {left, in.right};
   const int count = in.right ? 2 : 1;
   const int elem = in.depth && in.depth->format == SF_DEPTH_F32_M ? 4 : 2;
-  const int dz_pitch = (elem * width + 15) & ~15;          // rows padded to 16 bytes: k_depth_mask's wide loads
+  const int dz_pitch = in.depth ? (elem * in.depth->w + 15) & ~15 : 0;   // rows padded to 16 bytes: k_depth_mask's wide loads
   int rc = sf_buf_reserve(c, c->ft_images, count * img_bytes);
   if (rc != SF_OK) return rc;
-  if (in.depth && (rc = sf_buf_reserve(c, c->dp_depth, (size_t)dz_pitch * height)) != SF_OK) return rc;
+  if (in.depth && (rc = sf_buf_reserve(c, c->dp_depth, (size_t)dz_pitch * in.depth->h)) != SF_OK) return rc;
   uint8_t* d_planes = (uint8_t*)c->ft_images.p;
   if (format == SF_IMAGE_RGB8 || format == SF_IMAGE_BGR8) {
     const int src_pitch = (3 * width + 15) & ~15;
@@ -215,8 +215,9 @@ static int upload_inputs(sf_context* c, const uint8_t* left, const SecondInput& 
       SF_HIP(c, hipMemcpy2DAsync(d_planes + i * img_bytes, width, src[i], pitch, width, height, hipMemcpyHostToDevice, c->stream));
   }
   if (!in.depth) return SF_OK;
-  *d_depth = SfDepthIn{c->dp_depth.p, in.depth->format, dz_pitch};
-  SF_HIP(c, hipMemcpy2DAsync(c->dp_depth.p, dz_pitch, in.depth->p, in.depth->pitch, (size_t)elem * width, height, hipMemcpyHostToDevice, c->stream));
+  *d_depth = SfDepthIn{c->dp_depth.p, in.depth->format, dz_pitch, 0, in.depth->w, in.depth->h};
+  SF_HIP(c, hipMemcpy2DAsync(c->dp_depth.p, dz_pitch, in.depth->p, in.depth->pitch, (size_t)elem * in.depth->w, in.depth->h,
+                             hipMemcpyHostToDevice, c->stream));
   return SF_OK;
 }
 
@@ -280,7 +281,8 @@ static int wire_download(sf_context* c, const Wire& w, int desc_bytes, int32_t k
 
 // The GetFeatsAndDesc handler in one call on HOST buffers: upload the image and its second input, detect, refine, track (a
 // stereo pair) or mask the detector (a depth image, Vis/DepthAsMask), extract, download the response.  Everything between the
-// two copies stays on the device; the keyframe is in the store when it returns.  format < 0: rectified MONO8 planes
+// two copies stays on the device; the keyframe is in the store when it returns.  A depth image whose size does not divide the
+// image's makes no mask (sf_depth_masks): the detector runs as under Vis/DepthAsMask 0.  format < 0: rectified MONO8 planes
 // (sf_get_features_and_descriptor); otherwise the camera's images in that sf_image_format, converted on the device behind the
 // upload.  Everything an argument can be refused for is refused before the first reservation and the first upload.
 static int get_features_host(sf_context* c, const uint8_t* left, const SecondInput& in, int format, int32_t width, int32_t height,
@@ -288,14 +290,14 @@ static int get_features_host(sf_context* c, const uint8_t* left, const SecondInp
                              float* xyz_out, sf_keypoint* kpts_out, int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
   if (!c || !cam || !rows_out || cap_rows < 0) return SF_EINVAL;
   *rows_out = 0;
-  const SfDepthIn* depth = in.depth;                      // (the host's depth image)
+  SfDepthIn* depth = in.depth;                            // (the host's depth image)
   const bool present = left && (depth || in.right);
   const char* what = depth ? "image" : "stereo pair";
   int rc = format < 0 && !depth ? sf_check_image(c, present, width, height, pitch, 3, what)
                                 : check_camera_image(c, in.call, present, format, width, height, pitch, 3, what);
   if (rc != SF_OK) return rc;
   if (depth) {
-    if ((rc = sf_check_depth(c, in.call, depth->p, depth->format, width, height, depth->pitch, 0, 1)) != SF_OK) return rc;
+    if ((rc = sf_depth_in(c, in.call, depth, width, height, 1)) != SF_OK) return rc;
     if ((rc = check_depth_as_mask(c, in.call)) != SF_OK) return rc;
   }
   FrontPlan fp;
@@ -311,7 +313,7 @@ static int get_features_host(sf_context* c, const uint8_t* left, const SecondInp
   if ((rc = sf_extract_kind(c, &kind)) != SF_OK) return rc;
   const size_t img_bytes = ((size_t)width * height + 255) & ~(size_t)255;
   const int maxf = fp.rows_cap;                            // the rows of the call's buffers: max_features, or the grid's R C quota
-  const bool masked = depth && c->depth.depth_as_mask;
+  const bool masked = depth && sf_depth_masks(c, *depth, width, height);
   Wire wire;
   if ((rc = sf_buf_reserve(c, c->ft_kpts, (size_t)maxf * sizeof(sf_keypoint))) != SF_OK) return rc;
   if (!depth && (rc = sf_buf_reserve(c, c->ft_flow, (size_t)maxf * 16)) != SF_OK) return rc;
@@ -382,22 +384,22 @@ extern "C" int sf_get_features_and_descriptor_depth(sf_handle c, const uint8_t* 
                                                     int32_t depth_pitch, const sf_stereo_camera* cam,
                                                     const sf_detector_params* det, uint8_t* desc_out, float* xyz_out,
                                                     sf_keypoint* kpts_out, int32_t cap_rows, int32_t* rows_out, int32_t* slot_out) {
-  const SfDepthIn D{depth, depth_format, depth_pitch};
+  SfDepthIn D{depth, depth_format, depth_pitch};
   return get_features_host(c, image, {nullptr, nullptr, &D, "sf_get_features_and_descriptor_depth"}, image_format, width, height,
                            image_pitch, cam, det, desc_out, xyz_out, kpts_out, cap_rows, rows_out, slot_out);
 }
 
 // what a depth batch call refuses of its n depth images, behind the images' own checks (n = 0: of the format alone)
-static int depth_batch_check(sf_context* c, const char* call, const SfDepthIn& depth, int n, int width, int height) {
-  const int rc = n > 0 ? sf_check_depth(c, call, depth.p, depth.format, width, height, depth.pitch, depth.stride, n)
-                       : sf_check_depth(c, call, true, depth.format, 1, 1, 4, 0, 0);
+static int depth_batch_check(sf_context* c, const char* call, SfDepthIn* depth, int n, int width, int height) {
+  const int rc = sf_depth_in(c, call, depth, width, height, n);
   return rc != SF_OK ? rc : check_depth_as_mask(c, call);
 }
 
-// the masks of the n depth images, with the planes' pitch and stride (family_detect crops and cuts them like the images)
+// the masks of the n depth images, with the planes' pitch and stride (family_detect crops and cuts them like the images);
+// none of depth images whose size does not divide the image's
 static int depth_batch_mask(sf_context* c, const SfDepthIn& D, int n, int width, int height, int pitch, size_t image_stride,
                             const sf_stereo_camera* cam, SfMask* mask) {
-  if (!c->depth.depth_as_mask) return SF_OK;
+  if (!sf_depth_masks(c, D, width, height)) return SF_OK;
   mask->p = (const uint8_t*)c->dp_mask.p; mask->pitch = pitch; mask->stride = image_stride;
   return sf_launch_depth_mask(c, D, n, width, height, cam->min_depth, cam->max_depth, (uint8_t*)c->dp_mask.p, pitch, image_stride);
 }
@@ -426,7 +428,7 @@ static int batch_check(sf_context* c, BatchFamily family, const SecondInput& in,
       return sf_fail(c, SF_EINVAL, "%s%simage stride %zu is less than an image (%d rows of pitch %d)", in.call, colon(in.call),
                      image_stride, height, pitch);
   }
-  if (in.depth && (rc = depth_batch_check(c, in.call, *in.depth, n_keyframes, width, height)) != SF_OK) return rc;
+  if (in.depth && (rc = depth_batch_check(c, in.call, in.depth, n_keyframes, width, height)) != SF_OK) return rc;
   if (n_keyframes == 0) return SF_OK;
   if ((rc = sf_front_plan(c, width, height, &plan->front)) != SF_OK) return rc;
   plan->dp = arg_or_defaults(det, sf_detector_defaults);
@@ -808,7 +810,7 @@ extern "C" int sf_get_features_and_descriptor_depth_batch_device(sf_handle c, co
                                                                  int32_t* first_slot_out, int32_t* d_rows_out,
                                                                  uint8_t* d_desc_out, float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c) return SF_EINVAL;
-  const SfDepthIn D{d_depth, depth_format, depth_pitch, depth_stride};
+  SfDepthIn D{d_depth, depth_format, depth_pitch, depth_stride};
   return features_batch(c, sf_type_of(c).family, d_images, {nullptr, nullptr, &D, "sf_get_features_and_descriptor_depth_batch_device"},
                         n_keyframes, width, height, image_pitch, image_stride, cam, det, first_slot_out, d_rows_out, d_desc_out,
                         d_xyz_out, d_kpts_out);
@@ -822,7 +824,7 @@ extern "C" int sf_add_keyframes_depth_batch_device(sf_handle c, const uint8_t* d
                                                    int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                                    float* d_xyz_out, sf_keypoint* d_kpts_out) {
   if (!c) return SF_EINVAL;
-  const SfDepthIn D{d_depth, depth_format, depth_pitch, depth_stride};
+  SfDepthIn D{d_depth, depth_format, depth_pitch, depth_stride};
   return add_keyframes_batch(c, sf_type_of(c).family, d_images, {nullptr, nullptr, &D, "sf_add_keyframes_depth_batch_device"}, nullptr,
                              image_format, n_keyframes, width, height, image_pitch, image_stride, cam, det, first_slot_out,
                              first_nn_row_out, d_rows_out, d_desc_out, d_xyz_out, d_kpts_out);

@@ -211,6 +211,10 @@ def load():
         "sf_depth_get_params": (C.c_int, [vp, P(_abi.DepthParams)]),
         "sf_depth_mask_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, C.c_float, C.c_float, vp, i32,
                                            C.c_size_t]),
+        "sf_depth_set_size": (C.c_int, [vp, P(_abi.DepthSize)]),
+        "sf_depth_get_size": (C.c_int, [vp, P(_abi.DepthSize)]),
+        "sf_depth_interpolation_factor": (C.c_int, [i32, i32, i32, i32]),
+        "sf_depth_interpolate_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, i32, vp, i32, C.c_size_t]),
         "sf_depth_points_device": (C.c_int, [vp, vp, i32, i32, i32, i32, vp, i32, P(_abi.StereoCamera), vp, vp]),
         "sf_detect_corners_masked_device": (C.c_int, [vp, vp, i32, i32, i32, vp, i32, i32, C.c_double, C.c_double, vp, i32,
                                                       P(i32)]),
@@ -295,8 +299,15 @@ EXPORTED = [
     "sf_detect_corners_masked_device", "sf_detect_fast_masked_device", "sf_extract_keyframe_depth_device",
     "sf_get_features_and_descriptor_depth", "sf_get_features_and_descriptor_depth_batch_device",
     "sf_add_keyframes_depth_batch_device",
+    "sf_depth_set_size", "sf_depth_get_size", "sf_depth_interpolation_factor", "sf_depth_interpolate_device",
     "sf_store_export_plan", "sf_store_export_keyframes_device", "sf_store_import_keyframes_device", "sf_store_wire_status",
 ]
+
+
+def depth_interpolation_factor(width, height, depth_width, depth_height):
+    """sf_depth_interpolation_factor (no GPU, no handle): the integer factor by which a depth image of depth_width x
+    depth_height divides a width x height image in both dimensions alike; 0: none, the depth keyframe calls make no mask."""
+    return load().sf_depth_interpolation_factor(width, height, depth_width, depth_height)
 
 
 def freak_build_pattern(params=None):
@@ -1042,6 +1053,24 @@ class SeparatorFinder:
         self._check(self._L.sf_depth_get_params(self._h, C.byref(p)))
         return p
 
+    def depth_set_size(self, size=None):
+        """The handle's _abi.DepthSize: the depth images' own size in every depth call, whose width and height stay the
+        image's (a decimated depth image); None or {0, 0}, a fresh handle's: the image's size."""
+        self._check(self._L.sf_depth_set_size(self._h, C.byref(size) if size is not None else None))
+
+    def depth_get_size(self):
+        s = _abi.DepthSize()
+        self._check(self._L.sf_depth_get_size(self._h, C.byref(s)))
+        return s
+
+    def depth_interpolate_device(self, d_depth, depth_format, depth_width, depth_height, depth_pitch, depth_stride, n_images,
+                                 factor, d_out, out_pitch, out_stride):
+        """util2d::interpolate of n_images device depth images (asynchronous): each enlarged by the integer factor, in its
+        own format, to d_out; device pointers (ints), pitches and strides in bytes."""
+        self._check(self._L.sf_depth_interpolate_device(self._h, C.c_void_p(d_depth), depth_format, depth_width, depth_height,
+                                                        depth_pitch, int(depth_stride), n_images, factor, C.c_void_p(d_out),
+                                                        out_pitch, int(out_stride)))
+
     def depth_mask_device(self, d_depth, depth_format, width, height, depth_pitch, depth_stride, n_images, min_depth,
                           max_depth, d_mask, mask_pitch, mask_stride):
         """The detector masks of n_images device depth images (asynchronous); device pointers (ints), pitches and strides
@@ -1089,13 +1118,16 @@ class SeparatorFinder:
 
     def get_features_and_descriptor_depth(self, image, depth, cam, det=None, image_format=_abi.SF_IMAGE_MONO8):
         """GetFeatsAndDesc for a SensorData(rgb, depth, model) caller, on host arrays: image uint8 [h, w] (mono8) or
-        [h, w, 3] (rgb8 / bgr8), depth uint16 [h, w] millimetres or float32 [h, w] metres, registered to the image.
-        Returns what get_features_and_descriptor returns."""
+        [h, w, 3] (rgb8 / bgr8), depth uint16 [h, w] millimetres or float32 [h, w] metres, registered to the image -- after
+        depth_set_size an array of that size.  Returns what get_features_and_descriptor returns."""
         image, w, h, image_pitch = _camera_image(image, image_format)
         depth = np.asarray(depth)
         fmt = _abi.depth_format_of(depth)
-        if depth.shape != (h, w) or depth.strides[1] != depth.itemsize:
-            raise ValueError("depth must be a 2-D array of the image's height and width with contiguous rows")
+        size = self.depth_get_size()
+        want = (size.depth_height or h, size.depth_width or w)
+        if depth.shape != want or depth.strides[1] != depth.itemsize:
+            raise ValueError("depth must be a 2-D array of %d rows and %d columns (%s) with contiguous rows, not of shape %s"
+                             % (want + ("depth_set_size" if size.depth_width else "the image's height and width", depth.shape)))
         return self._host_keyframe(
             self._L.sf_get_features_and_descriptor_depth,
             (C.c_void_p(image.ctypes.data), image_format, C.c_void_p(depth.ctypes.data), fmt, w, h, image_pitch,
