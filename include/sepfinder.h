@@ -424,6 +424,47 @@ int  sf_store_import_keyframes_device(sf_handle h, const void* d_blob, uint64_t 
    them (index into the blob), or -1; out[3]: 0.  SF_OK when out[0] is 0, else SF_ERANGE (out is filled either way).  */
 int  sf_store_wire_status(sf_handle h, int32_t out[4]);
 
+/* ---- a camera model per keyframe: stores that hold the keyframes of unlike cameras -------------------------------- */
+/* The reference's registration takes two camera models, computeTransformationFromFeats(stereoCameraModelTo,
+   stereoCameraModelFrom, ..) (myRegistrationVis.cpp:441-443); its service hands it one robot's camera for both
+   (stereoCamGeometricTools.cpp:142-143), and sf_params carries that one camera.  A store that verifies across robots
+   holds keyframes whose 3D points are in their own robot's base frame and whose keypoints are pixels of their own
+   camera: the handle keeps a table of camera models and every store slot carries the id of the one it was taken with.
+   Id 0 is the sf_params camera; a store whose slots all carry id 0 behaves exactly as a handle without a table.
+   For a pair (from slot of camera X, to slot of camera Y):
+     guided matching (both forms): eligible iff Y is valid for projection (:474); guessCameraRef = (guess L_Y)^-1
+       (:486-487), projected through K_Y (:494) into Y's image (:505-506);
+     PnP: camera B of the direction -- forward Y, backward (forward_est_only = 0) X (:950-978, :1058-1073) -- with that
+       camera's calibrated gate;
+     bundle adjustment: view 1 is X's model if X is valid, else Y's (:1277); view 2 is Y's; each view has its own K and
+       baseline; invLocalTransformFrom comes from the TO model, as :1253 is written;
+     3D-3D estimates read no camera.
+   As soon as a slot of the store carries a non-zero id, verification calls on the store run the stage kernels
+   (SF_FUSED=0's launches).  The scratch slots of sf_estimate_transform(_batch) always carry id 0.
+   The blob of sf_store_export_* does not carry the ids: the camera is the receiver's knowledge.                    */
+typedef struct sf_camera_model {
+  double  fx, fy, cx, cy;
+  int32_t image_width, image_height;   /* 0 => not valid for projection, as in sf_params */
+  float   local_transform[12];         /* base <- camera optical frame, row-major 3x4 */
+  float   stereo_baseline;             /* metres, >= 0; read by the bundle adjustment only */
+  int32_t reserved;                    /* 0 */
+} sf_camera_model;                     /* 96 bytes */
+#define SF_MAX_CAMERAS 255             /* ids 1 .. 255 */
+/* Adds a model to the handle's table and uploads it: *id_out = 1, 2, ..  Non-finite or negative intrinsics, a negative
+   image size or baseline, a non-finite local_transform, reserved != 0: SF_EINVAL; a full table: SF_ERANGE.  Nothing
+   changes on a refusal.                                                                                             */
+int  sf_camera_add(sf_handle h, const sf_camera_model* m, int32_t* id_out);
+/* The model behind an id; id 0 = the handle's sf_params camera.  An id outside the table: SF_EINVAL.                */
+int  sf_camera_get(sf_handle h, int32_t id, sf_camera_model* out);
+int  sf_camera_count(sf_handle h, int32_t* n_out);        /* models added (id 0 not counted) */
+/* Slots appended from now on -- by sf_store_add_keyframe(s_device), every extraction and batch call,
+   sf_store_import_keyframes_device -- carry this id.  A fresh handle: 0.                                            */
+int  sf_camera_select(sf_handle h, int32_t id);
+/* The id of slots [first_slot, first_slot + n) / of one slot.  A range outside the store: SF_EINVAL.  sf_store_clear
+   drops the ids with the slots and keeps the table and the selection.                                               */
+int  sf_store_set_camera(sf_handle h, int32_t first_slot, int32_t n, int32_t id);
+int  sf_store_get_camera(sf_handle h, int32_t slot, int32_t* id_out);
+
 /* ---- features of one stereo keyframe -------------------------------- */
 /* replaces: RegistrationVis::getFeaturesImpl (myRegistrationVis.cpp:343-436: descriptors for the given keypoints,
    3D keypoints of the stereo pair, removal of keypoints without a finite 3D point) as called by

@@ -104,6 +104,33 @@ def stereo_camera(fx, fy, cx, cy, baseline, cx_right=0.0, local_transform=None, 
     return cam
 
 
+class CameraModel(C.Structure):
+    """sf_camera_model (include/sepfinder.h): one entry of the handle's camera table (sf_camera_add)."""
+    _fields_ = [
+        ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+        ("image_width", C.c_int32), ("image_height", C.c_int32),
+        ("local_transform", C.c_float * 12),
+        ("stereo_baseline", C.c_float),
+        ("reserved", C.c_int32),
+    ]
+
+
+assert C.sizeof(CameraModel) == 96
+SF_MAX_CAMERAS = 255
+
+
+def camera_model(fx, fy, cx, cy, image_width, image_height, local_transform=None, stereo_baseline=0.0):
+    m = CameraModel()
+    m.fx, m.fy, m.cx, m.cy = fx, fy, cx, cy
+    m.image_width, m.image_height = int(image_width), int(image_height)
+    lt = np.eye(4, dtype=np.float32)[:3] if local_transform is None else np.asarray(local_transform, np.float32).reshape(3, 4)
+    for i, v in enumerate(lt.ravel()):
+        m.local_transform[i] = float(v)
+    m.stereo_baseline = stereo_baseline
+    m.reserved = 0
+    return m
+
+
 class StereoFlowParams(C.Structure):
     """sf_stereo_flow_params (include/sepfinder.h): cv::calcOpticalFlowPyrLK + disparity gate of the stereo correspondence."""
     _fields_ = [

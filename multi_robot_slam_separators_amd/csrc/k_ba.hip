@@ -41,21 +41,54 @@ struct BaCam {
   double R1[9], t1[3];
 };
 
+// The two models of a pair whose slots carry camera ids (sf_camera_add; myRegistrationVis.cpp:1239-1278).  The base holds
+// view 2's K and baseline -- the To model's -- and in R1 / t1 the pose of view 1: the inverse local transform of the From
+// model if that is valid for projection, else of the To model (:1277).  fx1 / fy1 / b1 / cx1f / cy1f: view 1's K and
+// baseline.  Rd / td: the transform both frames' observed depths are taken with -- invLocalTransformTo (:1269, :1299) and
+// invLocalTransformFrom, which :1253 takes from the TO model as well.  has1: the From model is valid, so the words have
+// an edge to view 1 at all (:1288).
+struct BaCam2 : BaCam {
+  double fx1, fy1, b1;
+  double Rd[9], td[3];
+  float cx1f, cy1f;
+  bool has1;
+};
+// K and baseline of view `v` (0: view 1, 1: view 2), whether the words have an edge to view 1, the transform of the
+// observed depths, view 1's principal point (cxf / cyf: view 2's): one model, or two
+__device__ __forceinline__ double ba_fx(const BaCam& c, int) { return c.fx; }
+__device__ __forceinline__ double ba_fy(const BaCam& c, int) { return c.fy; }
+__device__ __forceinline__ double ba_b(const BaCam& c, int) { return c.b; }
+__device__ __forceinline__ bool ba_has1(const BaCam&) { return true; }
+__device__ __forceinline__ const double* ba_depth_R(const BaCam& c) { return c.R1; }
+__device__ __forceinline__ const double* ba_depth_t(const BaCam& c) { return c.t1; }
+__device__ __forceinline__ float ba_cx1(const BaCam&, float cxf) { return cxf; }
+__device__ __forceinline__ float ba_cy1(const BaCam&, float cyf) { return cyf; }
+__device__ __forceinline__ double ba_fx(const BaCam2& c, int v) { return v == 0 ? c.fx1 : c.fx; }
+__device__ __forceinline__ double ba_fy(const BaCam2& c, int v) { return v == 0 ? c.fy1 : c.fy; }
+__device__ __forceinline__ double ba_b(const BaCam2& c, int v) { return v == 0 ? c.b1 : c.b; }
+__device__ __forceinline__ bool ba_has1(const BaCam2& c) { return c.has1; }
+__device__ __forceinline__ const double* ba_depth_R(const BaCam2& c) { return c.Rd; }
+__device__ __forceinline__ const double* ba_depth_t(const BaCam2& c) { return c.td; }
+__device__ __forceinline__ float ba_cx1(const BaCam2& c, float) { return c.cx1f; }
+__device__ __forceinline__ float ba_cy1(const BaCam2& c, float) { return c.cy1f; }
+
 // one edge: residual rows (2 mono, 3 stereo) and their Jacobians wrt the camera-frame point; 0 = behind the camera
-__device__ __forceinline__ int ba_edge(const BaCam& cam, const double (&P)[3], const float* o, double (&r)[3],
+template <class Cam>
+__device__ __forceinline__ int ba_edge(const Cam& cam, int view, const double (&P)[3], const float* o, double (&r)[3],
                                        double (&J)[3][3]) {
   if (!(P[2] > 0.0)) return 0;
+  const double cam_fx = ba_fx(cam, view), cam_fy = ba_fy(cam, view), cam_b = ba_b(cam, view);
   const double iz = 1.0 / P[2];
   const double xn = P[0] * iz, yn = P[1] * iz;
-  const double a0 = cam.fx * iz, a2 = -(a0 * xn);
-  const double b1 = cam.fy * iz, b2 = -(b1 * yn);
-  r[0] = cam.fx * xn - (double)o[0];
-  r[1] = cam.fy * yn - (double)o[1];
+  const double a0 = cam_fx * iz, a2 = -(a0 * xn);
+  const double b1 = cam_fy * iz, b2 = -(b1 * yn);
+  r[0] = cam_fx * xn - (double)o[0];
+  r[1] = cam_fy * yn - (double)o[1];
   J[0][0] = a0; J[0][1] = 0.0; J[0][2] = a2;
   J[1][0] = 0.0; J[1][1] = b1; J[1][2] = b2;
-  if (cam.b > 0.0 && o[2] > 0.0f) {
-    const double fb = cam.fx * cam.b;
-    r[2] = (cam.fx * xn - fb * iz) - ((double)o[0] - fb / (double)o[2]);
+  if (cam_b > 0.0 && o[2] > 0.0f) {
+    const double fb = cam_fx * cam_b;
+    r[2] = (cam_fx * xn - fb * iz) - ((double)o[0] - fb / (double)o[2]);
     J[2][0] = a0; J[2][1] = 0.0; J[2][2] = a2 + (fb * iz) * iz;
     return 3;
   }
@@ -74,7 +107,8 @@ struct BaBlocks {
   bool ok;
 };
 
-__device__ inline void ba_point_blocks(const BaCam& cam, const double* Xp, const float* o1, const float* o2,
+template <class Cam>
+__device__ inline void ba_point_blocks(const Cam& cam, const double* Xp, const float* o1, const float* o2,
                                        const double (&R2)[9], const double (&t2)[3], BaBlocks& B) {
 #pragma unroll
   for (int k = 0; k < 6; ++k) B.A[k] = 0.0;
@@ -91,6 +125,7 @@ __device__ inline void ba_point_blocks(const BaCam& cam, const double* Xp, const
   const double X[3] = {Xp[0], Xp[1], Xp[2]};
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
+    if (c == 0 && !ba_has1(cam)) continue;
     double R[9], t[3];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = c == 0 ? cam.R1[k] : R2[k];
@@ -101,7 +136,7 @@ __device__ inline void ba_point_blocks(const BaCam& cam, const double* Xp, const
                          (R[6] * X[0] + R[7] * X[1]) + R[8] * X[2]};
     const double P[3] = {Y[0] + t[0], Y[1] + t[1], Y[2] + t[2]};
     double r[3], J[3][3];
-    const int rows = ba_edge(cam, P, o, r, J);
+    const int rows = ba_edge(cam, c, P, o, r, J);
     if (rows == 0) { B.cost += 1e30; B.ok = false; continue; }
     double chi2 = r[0] * r[0] + r[1] * r[1];
     if (rows == 3) chi2 = chi2 + r[2] * r[2];
@@ -157,8 +192,8 @@ __device__ __forceinline__ void ba_sym3_mul(const double (&Ai)[6], const double*
 
 // Schur-reduced normal equations at (q, t, points Xs): totals in `out` (LDS, [28])
 // SMALL: at most 256 words (k_ba_pass's first launch): one word per lane of the canonical 256-lane scheme
-template <int NW, bool SMALL = false>
-__device__ inline void ba_normal_eq(const BaLds& L, const BaCam& cam, int m, const double* Xs, const double (&q)[4],
+template <int NW, bool SMALL = false, class Cam = BaCam>
+__device__ inline void ba_normal_eq(const BaLds& L, const Cam& cam, int m, const double* Xs, const double (&q)[4],
                                     const double (&t)[3], double lambda, double* out, int tid) {
   double R2[9];
   sfd::quat_to_R(q, R2);
@@ -194,8 +229,8 @@ __device__ inline void ba_normal_eq(const BaLds& L, const BaCam& cam, int m, con
 }
 
 // candidate points Xc = X - A'^-1 (bp + C^T dc) at the current state
-template <int NW>
-__device__ inline void ba_backsub(const BaLds& L, const BaCam& cam, int m, const double (&q)[4], const double (&t)[3],
+template <int NW, class Cam = BaCam>
+__device__ inline void ba_backsub(const BaLds& L, const Cam& cam, int m, const double (&q)[4], const double (&t)[3],
                                   double lambda, const double (&dc)[6], int tid) {
   double R2[9];
   sfd::quat_to_R(q, R2);
@@ -245,28 +280,55 @@ __device__ __forceinline__ void ba_cam_setup(const DeviceParams& P, BaCam& cam) 
   }
 }
 
+// The two models of a pair (X: the "from" slot's camera, P: the kernel's DeviceParams with the "to" slot's camera laid over
+// them -- sf_camera_apply): view 2, the depths' transform and the result's local transform are the To model's; view 1 is
+// the From model if it is valid for projection, else the To model without edges (:1243-1254, :1272-1278, :1288).
+__device__ __forceinline__ void ba_cam_setup2(const DeviceParams& P, const CameraBlock& X, BaCam2& cam) {
+  ba_cam_setup(P, cam);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) cam.Rd[i] = cam.R1[i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) cam.td[i] = cam.t1[i];
+  cam.has1 = X.calibrated != 0;
+  cam.fx1 = cam.fx; cam.fy1 = cam.fy; cam.b1 = cam.b;
+  cam.cx1f = (float)P.cx; cam.cy1f = (float)P.cy;
+  if (cam.has1) {
+    cam.fx1 = X.fx; cam.fy1 = X.fy; cam.b1 = (double)X.stereo_baseline;
+    cam.cx1f = (float)X.cx; cam.cy1f = (float)X.cy;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) cam.R1[3 * i + j] = (double)X.L[4 * j + i];
+      cam.t1[i] = -(((double)X.L[i] * (double)X.L[3] + (double)X.L[4 + i] * (double)X.L[7]) + (double)X.L[8 + i] * (double)X.L[11]);
+    }
+  }
+}
+
 // one inlier word -> its slot k of the adjustment's working set: the point, both observations with their depths
-__device__ __forceinline__ void ba_put_word(const BaLds& L, const BaCam& cam, int k, float ax, float ay, float az, uint32_t c,
+template <class Cam>
+__device__ __forceinline__ void ba_put_word(const BaLds& L, const Cam& cam, int k, float ax, float ay, float az, uint32_t c,
                                             const float4* kF, const float4* kT, const float* xT, bool to3d, float cxf,
                                             float cyf) {
   const float4 k1 = kF[c & 0xFFFFu], k2 = kT[c >> 16];
+  const double* dR = ba_depth_R(cam);
+  const double* dt = ba_depth_t(cam);
   L.X[3 * k] = (double)ax; L.X[3 * k + 1] = (double)ay; L.X[3 * k + 2] = (double)az;
-  const float d1 = (float)(((cam.R1[6] * (double)ax + cam.R1[7] * (double)ay) + cam.R1[8] * (double)az) + cam.t1[2]);
-  L.o1[3 * k] = k1.x - cxf; L.o1[3 * k + 1] = k1.y - cyf; L.o1[3 * k + 2] = d1;
+  const float d1 = (float)(((dR[6] * (double)ax + dR[7] * (double)ay) + dR[8] * (double)az) + dt[2]);
+  L.o1[3 * k] = k1.x - ba_cx1(cam, cxf); L.o1[3 * k + 1] = k1.y - ba_cy1(cam, cyf); L.o1[3 * k + 2] = d1;
   float d2 = 0.0f;
   if (to3d) {
     const float* bq = xT + 3 * (size_t)(c >> 16);
     const float bx = bq[0], by = bq[1], bz = bq[2];
     if (sfd::finite3(bx, by, bz))
-      d2 = (float)(((cam.R1[6] * (double)bx + cam.R1[7] * (double)by) + cam.R1[8] * (double)bz) + cam.t1[2]);
+      d2 = (float)(((dR[6] * (double)bx + dR[7] * (double)by) + dR[8] * (double)bz) + dt[2]);
   }
   L.o2[3 * k] = k2.x - cxf; L.o2[3 * k + 1] = k2.y - cyf; L.o2[3 * k + 2] = d2;
 }
 
 // The adjustment itself over the n words already in L.X / L.o1 / L.o2 (correspondence order), from the estimate p0;
 // thread 0 writes the adjusted state to `ps`.
-template <int NW, bool SMALL = false>
-__device__ __forceinline__ void ba_solve(const BaLds& L, const BaCam& cam, int n, const PassState& p0, PassState& ps,
+template <int NW, bool SMALL = false, class Cam = BaCam>
+__device__ __forceinline__ void ba_solve(const BaLds& L, const Cam& cam, int n, const PassState& p0, PassState& ps,
                                          const DeviceParams& P) {
   constexpr int NT = 64 * NW;
   const int tid = (int)threadIdx.x;
@@ -350,6 +412,7 @@ __device__ __forceinline__ void ba_solve(const BaLds& L, const BaCam& cam, int n
     bool bad = false;
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
+      if (c == 0 && !ba_has1(cam)) continue;
       double R[9], tt[3];
 #pragma unroll
       for (int k = 0; k < 9; ++k) R[k] = c == 0 ? cam.R1[k] : R2[k];
@@ -360,7 +423,7 @@ __device__ __forceinline__ void ba_solve(const BaLds& L, const BaCam& cam, int n
                             ((R[3] * Xi[0] + R[4] * Xi[1]) + R[5] * Xi[2]) + tt[1],
                             ((R[6] * Xi[0] + R[7] * Xi[1]) + R[8] * Xi[2]) + tt[2]};
       double r[3], J[3][3];
-      const int rows = ba_edge(cam, Pc, (c == 0 ? L.o1 : L.o2) + 3 * i, r, J);
+      const int rows = ba_edge(cam, c, Pc, (c == 0 ? L.o1 : L.o2) + 3 * i, r, J);
       if (rows == 0) { bad = true; continue; }
       double chi2 = r[0] * r[0] + r[1] * r[1];
       if (rows == 3) chi2 = chi2 + r[2] * r[2];
@@ -417,10 +480,11 @@ __device__ __forceinline__ void ba_solve(const BaLds& L, const BaCam& cam, int n
 // Bundle adjustment of one pass.  pts[i] / cidx[i] / inl[i] (LDS, i < m): the estimate's compacted correspondences --
 // the "from" 3D point, the packed (from | to << 16) feature indices, the inlier flag.  `ps` (the pass state the
 // estimate just wrote; thread 0's view is authoritative): T, inliers and is_null are updated in place.
-template <int NW = 4>
-__device__ __forceinline__ void ba_body(const StoreView& st, int sF, int sT, const float4* pts, const uint32_t* cidx,
-                                        const uint8_t* inl, int m, PassState& ps, const DeviceParams& P,
-                                        unsigned char* lds) {
+// (ba_body_with: the models are the caller's -- one BaCam, or the BaCam2 of a pair whose slots carry camera ids)
+template <int NW, class Cam>
+__device__ __forceinline__ void ba_body_with(const StoreView& st, int sF, int sT, const float4* pts, const uint32_t* cidx,
+                                             const uint8_t* inl, int m, PassState& ps, const DeviceParams& P,
+                                             unsigned char* lds, const Cam* given) {
   constexpr int NT = 64 * NW;
   const int tid = (int)threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -431,8 +495,8 @@ __device__ __forceinline__ void ba_body(const StoreView& st, int sF, int sT, con
   // :1192-1197 gate (the words3From / wordsTo conditions hold whenever the estimate ran)
   if (p0.is_null || p0.inliers <= 0) return;
 
-  BaCam cam;
-  ba_cam_setup(P, cam);
+  Cam cam;
+  if constexpr (std::is_same<Cam, BaCam>::value) ba_cam_setup(P, cam); else cam = *given;
 
   // ---- the inlier words, in correspondence order -----------------------------------------------------------------------
   const float4* kF = st.kp + (size_t)sF * kcap;
@@ -468,6 +532,13 @@ __device__ __forceinline__ void ba_body(const StoreView& st, int sF, int sT, con
   ba_solve<NW>(L, cam, n, p0, ps, P);
 }
 
+template <int NW = 4>
+__device__ __forceinline__ void ba_body(const StoreView& st, int sF, int sT, const float4* pts, const uint32_t* cidx,
+                                        const uint8_t* inl, int m, PassState& ps, const DeviceParams& P,
+                                        unsigned char* lds) {
+  ba_body_with<NW, BaCam>(st, sF, sT, pts, cidx, inl, m, ps, P, lds, nullptr);
+}
+
 // The adjustment of one pass as a launch of its own (round 5): the estimate's kernel left its inlier set as one byte
 // per "from" feature (`mask`, [kcap] of this pair) next to the pass's correspondence list, and the words are rebuilt
 // from those -- the correspondences whose "from" point is finite (PnP) / whose two points are finite and non-zero
@@ -478,17 +549,19 @@ __device__ __forceinline__ void ba_body(const StoreView& st, int sF, int sT, con
 // `cap`: words the workgroup's LDS holds (sf_ba_lds_bytes(cap)); the caller has checked the estimate's inlier count
 // (an upper bound of the words) against it, and the gate of :1192-1197 (a non-null estimate with inliers).
 // SMALL: cap <= 256.
-template <int NW, bool PNP, bool SMALL>
+// (`given`: the BaCam2 of a pair whose slots carry camera ids; the one-model form makes its BaCam of P itself)
+template <int NW, bool PNP, bool SMALL, class Cam = BaCam>
 __device__ __forceinline__ void ba_pass_body(const StoreView& st, int sF, int sT, const uint32_t* __restrict__ cl,
                                              int n_corr, const uint8_t* __restrict__ mask, const PassState& p0,
-                                             PassState& ps, const DeviceParams& P, unsigned char* lds, int cap) {
+                                             PassState& ps, const DeviceParams& P, unsigned char* lds, int cap,
+                                             const Cam* given = nullptr) {
   constexpr int NT = 64 * NW;
   const int tid = (int)threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int kcap = st.kcap;
   const BaLds L = ba_carve(lds, cap);
-  BaCam cam;
-  ba_cam_setup(P, cam);
+  Cam cam;
+  if constexpr (std::is_same<Cam, BaCam>::value) ba_cam_setup(P, cam); else cam = *given;
   const float4* kF = st.kp + (size_t)sF * kcap;
   const float4* kT = st.kp + (size_t)sT * kcap;
   const float* xF = st.xyz + (size_t)sF * kcap * 3;
@@ -547,26 +620,24 @@ __host__ __device__ inline size_t sf_merge_ba_head_bytes(int kcap) {
   return (((size_t)kcap * 16 + (size_t)kcap * 4 + (size_t)kcap + 16 * 4) + 15) & ~(size_t)15;
 }
 
-template <bool PNP>
-__global__ void __launch_bounds__(SF_BLOCK, 2)
-k_merge_directions_ba(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
-                      const int32_t* __restrict__ list, const int32_t* __restrict__ counter,
+// (the body of both kernels.  cal0 / cal1: camera B of the PnP direction is valid -- the kernel without camera ids:
+//  both; given: the BaCam2 of a pair whose slots carry camera ids, nullptr: the one model of P)
+template <bool PNP, class Cam>
+__device__ __forceinline__ void merge_directions_ba_body(const StoreView& st, int pair, int sF, int sT,
                       const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr,
                       const uint8_t* __restrict__ guided_flag, PassState* __restrict__ fwd,
                       const PassState* __restrict__ back, const uint8_t* __restrict__ mask_f,
-                      const uint8_t* __restrict__ mask_b, int extra_3dof, DeviceParams P) {
-  if ((int)blockIdx.x >= *counter) return;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  const int pair = list[blockIdx.x], tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, kcap = st.kcap;
-  const int sF = pair_from[pair], sT = pair_to[pair];
+                      const uint8_t* __restrict__ mask_b, int extra_3dof, const DeviceParams& P, bool cal0, bool cal1,
+                      const Cam* given, unsigned char* smem_raw) {
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, kcap = st.kcap;
   float4* pts = (float4*)smem_raw;
   uint32_t* cidx = (uint32_t*)(smem_raw + (size_t)kcap * 16);
   uint8_t* ones = smem_raw + (size_t)kcap * 20;
   int* misc = (int*)(smem_raw + ((((size_t)kcap * 21) + 3) & ~(size_t)3));
   const CorrHeader h = hdr[pair];
   const bool guided = guided_flag != nullptr && guided_flag[pair] != 0;
-  const bool g0 = !PNP || sf_pnp_dir_gate(0, h, st.meta[sF].x, guided, P.min_inliers);
-  const bool g1 = !PNP || sf_pnp_dir_gate(1, h, st.meta[sF].x, guided, P.min_inliers);
+  const bool g0 = !PNP || (cal0 && sf_pnp_dir_gate(0, h, st.meta[sF].x, guided, P.min_inliers));
+  const bool g1 = !PNP || (cal1 && sf_pnp_dir_gate(1, h, st.meta[sF].x, guided, P.min_inliers));
   const float* xF = st.xyz + (size_t)sF * kcap * 3;
   const float* xT = st.xyz + (size_t)sT * kcap * 3;
   const uint32_t* cl = corr + (size_t)pair * kcap;
@@ -636,8 +707,47 @@ k_merge_directions_ba(StoreView st, const int32_t* __restrict__ pair_from, const
     fwd[pair] = a;
   }
   __syncthreads();
-  if (misc[2]) ba_body(st, sF, sT, pts, cidx, ones, n_ba, fwd[pair], P, smem_raw + sf_merge_ba_head_bytes(kcap));
+  if (misc[2]) ba_body_with<4, Cam>(st, sF, sT, pts, cidx, ones, n_ba, fwd[pair], P, smem_raw + sf_merge_ba_head_bytes(kcap), given);
   if (extra_3dof && tid == 0) pass_to3dof(fwd[pair], extra_3dof);
+}
+
+template <bool PNP>
+__global__ void __launch_bounds__(SF_BLOCK, 2)
+k_merge_directions_ba(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+                      const int32_t* __restrict__ list, const int32_t* __restrict__ counter,
+                      const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr,
+                      const uint8_t* __restrict__ guided_flag, PassState* __restrict__ fwd,
+                      const PassState* __restrict__ back, const uint8_t* __restrict__ mask_f,
+                      const uint8_t* __restrict__ mask_b, int extra_3dof, DeviceParams P) {
+  if ((int)blockIdx.x >= *counter) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int pair = list[blockIdx.x];
+  merge_directions_ba_body<PNP, BaCam>(st, pair, pair_from[pair], pair_to[pair], corr, hdr, guided_flag, fwd, back, mask_f, mask_b,
+                                       extra_3dof, P, true, true, nullptr, smem_raw);
+}
+
+// ... with a camera id per slot: each PnP direction's gate is also its camera B's, and the adjustment reads both models
+// (k_ba_pass_cam).  A To model that is not valid for projection: no adjustment can run (UASSERT, :1237), the directions
+// merge as without it.
+template <bool PNP>
+__global__ void __launch_bounds__(SF_BLOCK, 2)
+k_merge_directions_ba_cam(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+                          const int32_t* __restrict__ list, const int32_t* __restrict__ counter,
+                          const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr,
+                          const uint8_t* __restrict__ guided_flag, PassState* __restrict__ fwd,
+                          const PassState* __restrict__ back, const uint8_t* __restrict__ mask_f,
+                          const uint8_t* __restrict__ mask_b, int extra_3dof, DeviceParams P, CameraView cv) {
+  if ((int)blockIdx.x >= *counter) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int pair = list[blockIdx.x];
+  const int sF = pair_from[pair], sT = pair_to[pair];
+  const CameraBlock& X = sf_camera_of(cv, sF);
+  sf_camera_apply(P, sf_camera_of(cv, sT));
+  if (!P.calibrated) P.bundle_adjustment = 0;
+  BaCam2 cam;
+  ba_cam_setup2(P, X, cam);
+  merge_directions_ba_body<PNP, BaCam2>(st, pair, sF, sT, corr, hdr, guided_flag, fwd, back, mask_f, mask_b, extra_3dof, P,
+                                        P.calibrated != 0, X.calibrated != 0, &cam, smem_raw);
 }
 
 }  // namespace
@@ -653,6 +763,14 @@ int sf_launch_merge_directions_ba(sf_context* c, StoreView st, const int32_t* d_
   if (lds > 160 * 1024) return sf_fail(c, SF_ERANGE, "bundle adjustment of both directions needs %zu B of LDS (> 160 KiB)", lds);
   const PassBufs b = sf_pass_bufs(c, pass, pass == 1 ? 1 : 3);
   return sf_with_bool(pnp, [&](auto PNP) {
+    if (c->cam_view.table) {
+      const auto kern = k_merge_directions_ba_cam<decltype(PNP)::value>;
+      const int rc = sf_dyn_lds(c, kern, lds);
+      if (rc != SF_OK) return rc;
+      hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, b.list, b.counter, b.corr, b.hdr,
+                         b.guided_flag, b.ps, c->w->back(), mask_f, mask_b, b.end_3dof, c->dparams, c->cam_view);
+      return (int)SF_OK;
+    }
     const auto kern = k_merge_directions_ba<decltype(PNP)::value>;
     const int rc = sf_dyn_lds(c, kern, lds);
     if (rc != SF_OK) return rc;

@@ -899,6 +899,29 @@ k_guided_tp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* 
                             corr + (size_t)pair * st.kcap, hdr[pair], list, counter, P, smem);
 }
 
+// ---- the camera forms of k_guided and k_guided_tp (TP): a store whose slots carry camera ids (sf_camera_add) ----
+// The guided pass reads the TO camera alone (myRegistrationVis.cpp:469-507): whether it is valid for projection (:474),
+// its local transform in guessCameraRef (:486-487), its K (:494), its image bounds (:505-506) -- and the cell grid is laid
+// over its image.  The block of the "to" slot's camera is uniform over the workgroup: it is read once, into scalar
+// registers, over the kernel's own copy of DeviceParams, and the body is the one the plain kernels run.
+template <int W, bool L2, bool U8, bool TP>
+__global__ void __launch_bounds__(SF_BLOCK)
+k_guided_cam(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+             const PassState* __restrict__ pass1, PassState* __restrict__ pass2, uint8_t* __restrict__ guided_flag,
+             uint32_t* __restrict__ corr, CorrHeader* __restrict__ hdr, int32_t* __restrict__ list,
+             int32_t* __restrict__ counter, DeviceParams P, CameraView cv) {
+  extern __shared__ __attribute__((aligned(16))) int smem[];
+  const int pair = (int)blockIdx.x;
+  const int sF = pair_from[pair], sT = pair_to[pair];
+  sf_camera_apply(P, sf_camera_of(cv, sT));
+  if constexpr (TP)
+    guided_tp_body<W, L2, U8>(st, pair, sF, sT, pass1[pair], pass2[pair], guided_flag[pair], corr + (size_t)pair * st.kcap,
+                              hdr[pair], list, counter, P, smem);
+  else
+    guided_body<W, L2, 4, U8>(st, pair, sF, sT, pass1[pair], pass2[pair], guided_flag[pair], corr + (size_t)pair * st.kcap,
+                              hdr[pair], list, counter, P, smem);
+}
+
 // ---- result assembly: myRegistration.cpp:279-295 covariance clamp + MsgConversion.cpp:61-81 ------
 __device__ __forceinline__ void finalize_one(const PassState& pass1, const PassState& pass2, uint8_t guided_flag,
                                              sf_result& out) {
@@ -1001,6 +1024,14 @@ static size_t sf_guided_tp_lds_bytes(int kcap, int n_cells) {
 template <int W, bool L2, bool U8>
 static int launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, size_t lds, bool tp) {
   const Workspace& w = *c->w;
+  if (c->cam_view.table) {                       // a camera id per slot: the camera forms, same inputs and outputs
+    const auto kern = tp ? k_guided_cam<W, L2, U8, true> : k_guided_cam<W, L2, U8, false>;
+    const int rc = sf_dyn_lds(c, kern, lds);
+    if (rc != SF_OK) return rc;
+    hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, w.pass(1), w.pass(2), w.guided_flags(),
+                       w.corr(2), w.hdr(2), w.list(3), w.counter(3), c->dparams, c->cam_view);
+    return SF_OK;
+  }
   const auto kern = tp ? k_guided_tp<W, L2, U8> : k_guided<W, L2, U8>;
   const int rc = sf_dyn_lds(c, kern, lds);       // (k_guided from K ~ 1 600 features, k_guided_tp from ~ 3 000)
   if (rc != SF_OK) return rc;
@@ -1012,7 +1043,8 @@ static int launch_guided(sf_context* c, StoreView st, const int32_t* d_from, con
 int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n) {
   if (n <= 0) return SF_OK;
   const bool tp = c->dparams.guess_match_to_projection != 0;
-  const int nc = c->dparams.grid_gx * c->dparams.grid_gy;
+  // (with a camera per slot every pair lays its own camera's grid over the LDS: sized for the largest of the table)
+  const int nc = c->cam_view.table ? c->cam_max_cells : c->dparams.grid_gx * c->dparams.grid_gy;
   const size_t lds = tp ? sf_guided_tp_lds_bytes(st.kcap, nc) : sf_guided_lds_bytes(st.kcap, nc);
   if (tp && lds > 160 * 1024)
     return sf_fail(c, SF_ERANGE, "guess_match_to_projection: %d features per keyframe need %zu B of LDS (> 160 KiB)",

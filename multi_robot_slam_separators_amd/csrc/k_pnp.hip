@@ -726,24 +726,51 @@ k_pnp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __rest
   if (extra_3dof && threadIdx.x == 0) pass_to3dof(pass[pair], extra_3dof);
 }
 
+// The camera form of k_pnp: a store whose slots carry camera ids (sf_camera_add).  The estimate reads camera B of its
+// direction (myRegistrationVis.cpp:950-978, :1058, :1073): the "to" slot's forward (DIR 0), the "from" slot's backward
+// (DIR 1) -- its K in the observations and the solver, its local transform in the result, and its calibrated gate
+// (:1059-1065: without a valid camera B the direction's estimate does not run: no transform, no matches, no inliers).
+// The block is uniform over the workgroup and read once, into scalar registers, over the kernel's own DeviceParams.
+template <int DIR>
+__global__ void __launch_bounds__(SF_BLOCK, 3)
+k_pnp_cam(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+          const int32_t* __restrict__ list, const int32_t* __restrict__ counter,
+          const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr,
+          PassState* __restrict__ pass, int extra_3dof, DeviceParams P, uint8_t* __restrict__ mask,
+          const uint8_t* __restrict__ guided_flag, CameraView cv) {
+  if ((int)blockIdx.x >= *counter) return;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int pair = list[blockIdx.x];
+  sf_camera_apply(P, sf_camera_of(cv, DIR ? pair_from[pair] : pair_to[pair]));
+  if (!P.calibrated) {
+    if (threadIdx.x == 0) write_null_pass(pass[pair], 0);
+    return;
+  }
+  const PnpTail tail = pnp_body<DIR>(st, pair, pair_from, pair_to, corr, hdr, pass, P, smem_raw, 0,
+                                     mask ? mask + (size_t)pair * st.kcap : nullptr,
+                                     guided_flag != nullptr && guided_flag[pair] != 0);
+  (void)tail;
+  if (extra_3dof && threadIdx.x == 0) pass_to3dof(pass[pair], extra_3dof);
+}
+
 // Vis/ForwardEstOnly = false with the PnP estimator: the two directions' estimates of a pass merged as
 // myRegistrationVis.cpp:1155-1189 (union of the inlier ids and of the match ids -- direction d matches the ids whose
 // A-side point is finite, if its gate was open) and :1376-1394 (inverse of the backward transform; interpolate(0.5) when
 // both exist, covariance their mean).  One wavefront per pair.
-__global__ void __launch_bounds__(64)
-k_merge_directions_pnp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+// cal0 / cal1: camera B of the direction is valid (the kernel without camera ids: both, or the pair is not here).
+__device__ __forceinline__ void merge_directions_pnp_body(const StoreView& st, const int32_t* __restrict__ pair_from,
+                       const int32_t* __restrict__ pair_to,
                        const int32_t* __restrict__ list, const int32_t* __restrict__ counter,
                        const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr,
                        const uint8_t* __restrict__ guided_flag, PassState* __restrict__ fwd,
                        const PassState* __restrict__ back, const uint8_t* __restrict__ mask_f,
-                       const uint8_t* __restrict__ mask_b, int min_inliers, int extra_3dof) {
-  if ((int)blockIdx.x >= *counter) return;
+                       const uint8_t* __restrict__ mask_b, int min_inliers, int extra_3dof, bool cal0, bool cal1) {
   const int pair = list[blockIdx.x], lane = threadIdx.x, kcap = st.kcap;
   const int sF = pair_from[pair], sT = pair_to[pair];
   const CorrHeader h = hdr[pair];
   const bool guided = guided_flag != nullptr && guided_flag[pair] != 0;
-  const bool g0 = sf_pnp_dir_gate(0, h, st.meta[sF].x, guided, min_inliers);
-  const bool g1 = sf_pnp_dir_gate(1, h, st.meta[sF].x, guided, min_inliers);
+  const bool g0 = cal0 && sf_pnp_dir_gate(0, h, st.meta[sF].x, guided, min_inliers);
+  const bool g1 = cal1 && sf_pnp_dir_gate(1, h, st.meta[sF].x, guided, min_inliers);
   const float* xF = st.xyz + (size_t)sF * kcap * 3;
   const float* xT = st.xyz + (size_t)sT * kcap * 3;
   const uint32_t* cl = corr + (size_t)pair * kcap;
@@ -765,6 +792,33 @@ k_merge_directions_pnp(StoreView st, const int32_t* __restrict__ pair_from, cons
   merge_backward_pose(a, b);
   pass_to3dof(a, extra_3dof);
   fwd[pair] = a;
+}
+
+__global__ void __launch_bounds__(64)
+k_merge_directions_pnp(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+                       const int32_t* __restrict__ list, const int32_t* __restrict__ counter,
+                       const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr,
+                       const uint8_t* __restrict__ guided_flag, PassState* __restrict__ fwd,
+                       const PassState* __restrict__ back, const uint8_t* __restrict__ mask_f,
+                       const uint8_t* __restrict__ mask_b, int min_inliers, int extra_3dof) {
+  if ((int)blockIdx.x >= *counter) return;
+  merge_directions_pnp_body(st, pair_from, pair_to, list, counter, corr, hdr, guided_flag, fwd, back, mask_f, mask_b, min_inliers,
+                            extra_3dof, true, true);
+}
+
+// ... with a camera id per slot: each direction's gate is also its camera B's (k_pnp_cam)
+__global__ void __launch_bounds__(64)
+k_merge_directions_pnp_cam(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+                           const int32_t* __restrict__ list, const int32_t* __restrict__ counter,
+                           const uint32_t* __restrict__ corr, const CorrHeader* __restrict__ hdr,
+                           const uint8_t* __restrict__ guided_flag, PassState* __restrict__ fwd,
+                           const PassState* __restrict__ back, const uint8_t* __restrict__ mask_f,
+                           const uint8_t* __restrict__ mask_b, int min_inliers, int extra_3dof, CameraView cv) {
+  if ((int)blockIdx.x >= *counter) return;
+  const int pair = list[blockIdx.x];
+  const bool cal0 = sf_camera_of(cv, pair_to[pair]).calibrated != 0, cal1 = sf_camera_of(cv, pair_from[pair]).calibrated != 0;
+  merge_directions_pnp_body(st, pair_from, pair_to, list, counter, corr, hdr, guided_flag, fwd, back, mask_f, mask_b, min_inliers,
+                            extra_3dof, cal0, cal1);
 }
 
 }  // namespace

@@ -515,6 +515,46 @@ k_ba_pass(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __
   }
 }
 
+// The camera form of k_ba_pass: a store whose slots carry camera ids (sf_camera_add).  The adjustment reads both models
+// (myRegistrationVis.cpp:1239-1278; BaCam2, ba_cam_setup2): the "to" slot's block is laid over the kernel's DeviceParams
+// -- view 2, the depths' transform, the local transform of the result -- and the "from" slot's gives view 1.  Both are
+// uniform over the workgroup.  A To model that is not valid for projection stops the reference (UASSERT, :1237): no
+// adjustment runs, the pair keeps its estimate.
+template <int NW, bool PNP, bool SMALL, int OCC = 1>
+__global__ void __launch_bounds__(64 * NW, OCC)
+k_ba_pass_cam(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
+              const int32_t* __restrict__ list, const int32_t* __restrict__ counter, const uint32_t* __restrict__ corr,
+              const CorrHeader* __restrict__ hdr, const uint8_t* __restrict__ mask, const uint8_t* __restrict__ run,
+              PassState* __restrict__ pass, int extra_3dof, int fin, const PassState* __restrict__ pass1,
+              const uint8_t* __restrict__ guided_flag, sf_result* __restrict__ out, DeviceParams P, int cap, int both,
+              CameraView cv) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  if ((int)blockIdx.x >= *counter) return;
+  const int pair = list[blockIdx.x];
+  const int kcap = st.kcap;
+  const int sF = pair_from[pair], sT = pair_to[pair];
+  const CameraBlock& X = sf_camera_of(cv, sF);
+  sf_camera_apply(P, sf_camera_of(cv, sT));
+  const PassState p0 = pass[pair];
+  const bool adjust = (!run || run[pair]) && !p0.is_null && p0.inliers > 0 && P.calibrated;
+  const bool big = adjust && p0.inliers > SF_BA_SMALL_CAP;
+  if (both && big == SMALL) return;            // the other launch's pair
+  if (adjust) {
+    if (p0.inliers <= cap) {
+      BaCam2 cam;
+      ba_cam_setup2(P, X, cam);
+      ba_pass_body<NW, PNP, SMALL, BaCam2>(st, sF, sT, corr + (size_t)pair * kcap, hdr[pair].n_corr, mask + (size_t)pair * kcap,
+                                           p0, pass[pair], P, smem_raw, cap, &cam);
+    }
+  }
+  if (!run || run[pair]) {
+    if (extra_3dof && threadIdx.x == 0) pass_to3dof(pass[pair], extra_3dof);
+  }
+  if (!fin) return;
+  __syncthreads();
+  if (threadIdx.x == 0) finalize_one(pass1[pair], pass[pair], guided_flag[pair], out[pair]);
+}
+
 }  // namespace
 
 // The adjustment of pass `pass` (1 / 2) of the n pairs of a launch sequence, over that pass's work list.  mask: the
@@ -537,11 +577,25 @@ int sf_launch_ba_pass(sf_context* c, StoreView st, const int32_t* d_from, const 
                        both ? 1 : 0);
     return SF_OK;
   };
+  auto launch_cam = [&](auto kern, int nw, int cap) -> int {     // a camera id per slot: both models, per pair
+    const size_t lds = sf_ba_lds_bytes(cap);
+    const int rc = sf_dyn_lds(c, kern, lds);
+    if (rc != SF_OK) return rc;
+    hipLaunchKernelGGL(kern, dim3(n), dim3(64 * nw), lds, c->stream, st, d_from, d_to, b.list, b.counter, b.corr, b.hdr, mask,
+                       run, b.ps, b.end_3dof, fin ? 1 : 0, c->w->pass(1), c->w->guided_flags(), d_out, c->dparams, cap,
+                       both ? 1 : 0, c->cam_view);
+    return SF_OK;
+  };
   const int cap_small = std::min(st.kcap, SF_BA_SMALL_CAP);
   const int rc = sf_with_nw(c->ba_nw, [&](auto NW) {
     return sf_with_bool(c->dparams.estimation_type == 1, [&](auto PNP) {
       constexpr int nw = decltype(NW)::value;
       constexpr bool pnp = decltype(PNP)::value;
+      if (c->cam_view.table) {
+        int rc = launch_cam(k_ba_pass_cam<nw, pnp, true, 1>, nw, cap_small);
+        if (rc == SF_OK && both) rc = launch_cam(k_ba_pass_cam<nw, pnp, false>, nw, st.kcap);
+        return rc;
+      }
       int rc = (c->ba_occ ? c->ba_occ : (pnp ? 1 : 2)) == 2 ? launch(k_ba_pass<nw, pnp, true, 2>, nw, cap_small)
                                                              : launch(k_ba_pass<nw, pnp, true, 1>, nw, cap_small);
       if (rc == SF_OK && both) rc = launch(k_ba_pass<nw, pnp, false>, nw, st.kcap);
@@ -590,6 +644,30 @@ int estimate_sequence(sf_context* c, StoreView st, const int32_t* d_from, const 
 }
 }  // namespace
 
+namespace {
+// PnP, forward only, on a store whose cameras are not all valid for projection: the matcher ran the PnP gate for every
+// pair (sf_est_mode); a pair whose "to" camera is not valid never reaches the estimation in the reference
+// (myRegistrationVis.cpp:1059-1065) -- no transform, no matches.  Its pass-1 state is null already (the matcher's; the
+// estimate, k_pnp_cam, leaves it so): the match count goes too.
+__global__ void __launch_bounds__(SF_BLOCK)
+k_camera_gate(const int32_t* __restrict__ pair_to, int n, PassState* __restrict__ pass, CameraView cv) {
+  const int i = (int)(blockIdx.x * SF_BLOCK + threadIdx.x);
+  if (i >= n) return;
+  const int sT = pair_to[i];
+  const int id = (unsigned)sT < (unsigned)cv.n_slots ? cv.tags[sT] : 0;
+  if (!cv.table[id].calibrated) pass[i].matches = 0;
+}
+}  // namespace
+
+int sf_launch_camera_gate(sf_context* c, const int32_t* d_to, int n) {
+  if (n <= 0 || !c->cam_view.table || !c->cam_mixed_calibration || c->dparams.estimation_type != 1 || c->dparams.bidirectional)
+    return SF_OK;
+  hipLaunchKernelGGL(k_camera_gate, dim3((n + SF_BLOCK - 1) / SF_BLOCK), dim3(SF_BLOCK), 0, c->stream, d_to, n, c->w->pass(1),
+                     c->cam_view);
+  SF_HIP(c, hipGetLastError());
+  return SF_OK;
+}
+
 int sf_launch_estimate(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass) {
   if (n <= 0) return SF_OK;
   const PassBufs b = sf_pass_bufs(c, pass, pass == 1 ? 1 : 3);
@@ -598,6 +676,14 @@ int sf_launch_estimate(sf_context* c, StoreView st, const int32_t* d_from, const
     return estimate_sequence(
         c, st, d_from, d_to, n, pass, b, "PnP", lds,
         [&](auto DIR, PassState* out, uint8_t* mask, int extra) {
+          if (c->cam_view.table) {                  // a camera id per slot: camera B of the direction, per pair
+            const auto kern = k_pnp_cam<decltype(DIR)::value>;
+            const int rc = sf_dyn_lds(c, kern, lds);
+            if (rc != SF_OK) return rc;
+            hipLaunchKernelGGL(kern, dim3(n), dim3(SF_BLOCK), lds, c->stream, st, d_from, d_to, b.list, b.counter, b.corr, b.hdr,
+                               out, extra, c->dparams, mask, b.guided_flag, c->cam_view);
+            return (int)SF_OK;
+          }
           const auto kern = k_pnp<decltype(DIR)::value>;
           const int rc = sf_dyn_lds(c, kern, lds);
           if (rc != SF_OK) return rc;
@@ -606,8 +692,13 @@ int sf_launch_estimate(sf_context* c, StoreView st, const int32_t* d_from, const
           return (int)SF_OK;
         },
         [&](const uint8_t* mask_f, const uint8_t* mask_b) {
-          hipLaunchKernelGGL(k_merge_directions_pnp, dim3(n), dim3(64), 0, c->stream, st, d_from, d_to, b.list, b.counter, b.corr,
-                             b.hdr, b.guided_flag, b.ps, c->w->back(), mask_f, mask_b, c->dparams.min_inliers, b.end_3dof);
+          if (c->cam_view.table)
+            hipLaunchKernelGGL(k_merge_directions_pnp_cam, dim3(n), dim3(64), 0, c->stream, st, d_from, d_to, b.list, b.counter,
+                               b.corr, b.hdr, b.guided_flag, b.ps, c->w->back(), mask_f, mask_b, c->dparams.min_inliers,
+                               b.end_3dof, c->cam_view);
+          else
+            hipLaunchKernelGGL(k_merge_directions_pnp, dim3(n), dim3(64), 0, c->stream, st, d_from, d_to, b.list, b.counter, b.corr,
+                               b.hdr, b.guided_flag, b.ps, c->w->back(), mask_f, mask_b, c->dparams.min_inliers, b.end_3dof);
           return (int)SF_OK;
         });
   }

@@ -208,16 +208,30 @@ int sf_fill_device_params(sf_context* c) {
     d.pnp_thr2f = (float)(thr * thr);     // OpenCV: float t = (float)(thresh*thresh); err <= t
   }
   if (const char* v = getenv("SF_RANSAC_STOP")) d.dbg_stop = atoi(v);
-  {
-    // grid for the guided pass: cell >= window radius, at most 48 x 48 cells
-    const float w = (float)std::max(p.image_width, 1), h = (float)std::max(p.image_height, 1);
-    float cell = std::max((float)std::max(p.guess_win_size, 1), std::max(ceilf(w / 48.f), ceilf(h / 48.f)));
-    cell *= 1.001f;   // strictly larger than the padded reach used by the kernel
-    d.grid_gx = std::max(1, std::min(48, (int)ceilf(w / cell)));
-    d.grid_gy = std::max(1, std::min(48, (int)ceilf(h / cell)));
-    d.grid_inv_cell = 1.f / cell;
-  }
+  sf_guided_grid(p.image_width, p.image_height, p.guess_win_size, &d.grid_gx, &d.grid_gy, &d.grid_inv_cell);
   return SF_OK;
+}
+
+// grid for the guided pass over an image: cell >= window radius, at most 48 x 48 cells
+void sf_guided_grid(int image_width, int image_height, int guess_win_size, int32_t* gx, int32_t* gy, float* inv_cell) {
+  const float w = (float)std::max(image_width, 1), h = (float)std::max(image_height, 1);
+  float cell = std::max((float)std::max(guess_win_size, 1), std::max(ceilf(w / 48.f), ceilf(h / 48.f)));
+  cell *= 1.001f;   // strictly larger than the padded reach used by the kernel
+  *gx = std::max(1, std::min(48, (int)ceilf(w / cell)));
+  *gy = std::max(1, std::min(48, (int)ceilf(h / cell)));
+  *inv_cell = 1.f / cell;
+}
+
+// What DeviceParams derives from the sf_params camera, for one model of the handle's table (same expressions)
+void sf_camera_derive(const sf_camera_model& m, int guess_win_size, CameraBlock* b) {
+  memset(b, 0, sizeof(*b));
+  b->calibrated = (m.image_width > 0 && m.image_height > 0 && m.fx > 0.0 && m.fy > 0.0) ? 1 : 0;
+  b->fx = m.fx; b->fy = m.fy; b->cx = m.cx; b->cy = m.cy;
+  b->wlim = (float)(m.image_width - 1);
+  b->hlim = (float)(m.image_height - 1);
+  memcpy(b->L, m.local_transform, sizeof(b->L));
+  b->stereo_baseline = m.stereo_baseline;
+  sf_guided_grid(m.image_width, m.image_height, guess_win_size, &b->grid_gx, &b->grid_gy, &b->grid_inv_cell);
 }
 
 // The environment's knobs of a handle (sf_create; the device-free planner sf_debug_plan_workspace applies them too, so
@@ -295,7 +309,8 @@ extern "C" void sf_destroy(sf_handle c) {
                  &c->ex_integral, &c->ex_desc, &c->ex_xyz, &c->ex_keep, &c->ex_rows, &c->brief_tests, &c->orb_tests,
                  &c->ex_blur, &c->ex_kpts, &c->orb_pyr, &c->orb_work, &c->freak_pattern, &c->freak_tables, &c->surf_planes, &c->surf_keys, &c->surf_tables, &c->surf_ctl, &c->sift_planes, &c->sift_keys, &c->sift_tables, &c->sift_ctl,
                  &c->gf_planes, &c->gf_keys, &c->gf_tmp, &c->gf_lists, &c->gf_scalar, &c->lk_pyr, &c->ft_images, &c->ft_kpts, &c->ft_flow, &c->ft_wire,
-                 &c->ft_counts, &c->ft_cells, &c->img_src, &c->img_gray, &c->img_desc, &c->wire_plan, &c->wire_status};
+                 &c->ft_counts, &c->ft_cells, &c->img_src, &c->img_gray, &c->img_desc, &c->wire_plan, &c->wire_status,
+                 &c->cam_table, &c->cam_tags_dev};
   for (Buf* b : bufs) sf_buf_free(*b);
   for (int k = 0; k <= SF_STEP_MAX_LANES; ++k) {
     Workspace& w = c->ws[k];

@@ -14,6 +14,8 @@
 // ---- sf_handle.hip ------------------------------------------------------------------------------------------------------
 int sf_fill_device_params(sf_context* c);      // validates c->params and derives c->dparams
 void sf_env_knobs(sf_context* c);              // the SF_* environment knobs of a handle, applied to `c`
+void sf_guided_grid(int image_width, int image_height, int guess_win_size, int32_t* gx, int32_t* gy, float* inv_cell);
+void sf_camera_derive(const sf_camera_model& m, int guess_win_size, CameraBlock* b);   // a table entry from a model
 
 // ---- sf_store.hip -------------------------------------------------------------------------------------------------------
 int sf_validate_features(sf_context* c, const sf_features* f);
@@ -128,6 +130,7 @@ struct VerifyPlan {
   bool lists = true;        // the correspondence lists live in HBM (every form but the plain fused kernel)
   bool single = false;      // one launch sequence on one stream: a pair's index IS its position in the call
   bool narrow_est = false;  // SPLIT only: the survivors' chains as three launches, the estimates one wavefront wide (k_chain_est)
+  bool cameras = false;     // a slot of the store carries a camera id: STAGES / HALVES, their kernels in the camera forms
   bool streams() const { return single && (form == FUSED || form == SPLIT || form == SPLIT_PNP); }   // chain kernels that can
 };                                                                                                // stream accepted results
 VerifyPlan sf_verify_plan(const sf_context* c, const StoreView& v, int n);

@@ -98,6 +98,51 @@ struct DeviceParams {
   unsigned long long* dbg_trace;   // SF_CHAIN_TRACE builds only (tools/chain_trace.py): [pair][SF_TRACE_SLOTS] timestamps; else null
 };
 
+// ---- a camera model per store slot (sf_camera_add; include/sepfinder.h) ---------------------------------------------------
+// What DeviceParams derives from the sf_params camera, once per model of the handle's table: entry 0 is the sf_params
+// camera itself, entry id the model sf_camera_add returned id for.  `tags` holds one id per store slot, beside the
+// store's row counts.  The stage kernels' camera forms (k_guided_cam -- TP: k_guided_tp's --, k_pnp_cam, k_ba_pass_cam, ...) take
+// the view and lay the block of the slot whose camera they read over their DeviceParams; a handle none of whose slots
+// carries a non-zero id never launches them.
+struct CameraBlock {
+  double fx, fy, cx, cy;
+  int32_t calibrated;
+  float wlim, hlim;
+  int32_t grid_gx, grid_gy;
+  float grid_inv_cell;
+  float stereo_baseline;
+  int32_t pad;
+  float L[12];
+};
+struct CameraView {
+  const CameraBlock* table = nullptr;   // [SF_MAX_CAMERAS + 1]; nullptr: the call reads the sf_params camera only
+  const uint8_t* tags = nullptr;        // [n_slots]
+  int n_slots = 0;
+};
+#define SF_CAMERA_MAX_CELLS (48 * 48)   // every model's grid stays within it (sf_camera_derive): the guided passes' LDS bound
+
+#ifdef __HIPCC__
+// The block of the camera slot `slot` was taken with.  `slot` is uniform over the workgroup (a pair's "from" or "to"
+// slot), so the id and the block sit in scalar registers; a slot outside the store reads the sf_params camera (the pair
+// is void anyway: the bodies' own guards).
+__device__ __forceinline__ const CameraBlock& sf_camera_of(const CameraView& cv, int slot) {
+  int id = 0;
+  if ((unsigned)slot < (unsigned)cv.n_slots) id = cv.tags[slot];
+  id = __builtin_amdgcn_readfirstlane(id);
+  return cv.table[id];
+}
+// DeviceParams with the camera fields replaced by the block's
+__device__ __forceinline__ void sf_camera_apply(DeviceParams& P, const CameraBlock& b) {
+  P.calibrated = b.calibrated;
+  P.fx = b.fx; P.fy = b.fy; P.cx = b.cx; P.cy = b.cy;
+  P.wlim = b.wlim; P.hlim = b.hlim;
+  P.grid_gx = b.grid_gx; P.grid_gy = b.grid_gy; P.grid_inv_cell = b.grid_inv_cell;
+  P.stereo_baseline = b.stereo_baseline;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) P.L[i] = b.L[i];
+}
+#endif
+
 // Phase timestamps of the fused kernel's chain (diagnostic build -DSF_CHAIN_TRACE, libsepfinder_trace.so; the product
 // build compiles these to nothing): thread 0 of the pair's workgroup stores the 100 MHz wall clock.
 #ifdef SF_CHAIN_TRACE
@@ -131,6 +176,9 @@ struct Buf {
 
 struct Store {
   Buf desc, xyz, kp, meta;
+  // (slots only grows, except in sf_store_clear and inside one call that takes back what it has just appended: the slots'
+  //  camera ids are written out lazily, from cam_tags.size() up to `slots` -- camera_settle, sf_store.hip -- so a path that
+  //  drops slots and returns must drop their ids with them, as sf_store_clear does)
   int kcap = 0, w = 0, slots = 0, cap_slots = 0;
 };
 
@@ -298,6 +346,20 @@ struct sf_context {
 
   Store store;        // persistent keyframes
   Store scratch;      // staging slots for host-buffer calls
+  // a camera model per store slot (sf_store.hip, "camera models").  cam_models[id - 1]: what sf_camera_add took; cam_blocks:
+  // the derived blocks, [0] the sf_params camera (host copy of cam_table, uploaded by sf_camera_add).  cam_tags: the id of
+  // every slot below cam_tags.size(); the slots behind it, up to store.slots, were appended since and carry cam_sel
+  // (sf_camera_settle writes them out, before the selection changes and before anything reads a tag).  cam_nonzero: tags
+  // != 0 among cam_tags.  cam_tags_dev: the device copy, cam_dev_n entries of it current (sf_camera_sync, ahead of a
+  // verification).  cam_view: what the launchers of the sequence being queued hand their kernels (table nullptr: the
+  // forms without cameras).
+  std::vector<sf_camera_model> cam_models;
+  std::vector<CameraBlock> cam_blocks;
+  std::vector<uint8_t> cam_tags;
+  int cam_sel = 0, cam_nonzero = 0, cam_dev_n = 0, cam_max_cells = 0;
+  bool cam_mixed_calibration = false;     // some model of the table is valid for projection and another (or sf_params') is not
+  Buf cam_table, cam_tags_dev;
+  CameraView cam_view;
   Buf stage_desc, stage_xyz, stage_kp;   // H2D bounce buffers of the host-buffer ingest path
   // store slots as bytes (sf_store_export_* / sf_store_import_keyframes_device; k_store_wire.hip): header and table of the
   // most recent plan, and the four status words of the most recent export or import (sf_store_wire_status)
@@ -621,13 +683,25 @@ int sf_launch_image_gray(sf_context* c, const uint8_t* d_src0, const uint8_t* d_
 // k_nn.hip: room for n more rows of `dim` values in a database, without appending (SF_EINVAL: another dimension)
 int sf_nn_reserve_rows(sf_context* c, NNDb& db, int n, int dim);
 StoreView sf_store_view(const Store& s);
+// camera models (sf_store.hip): whether a slot of the store carries a non-zero id (what sends a verification of the store
+// to the stage kernels' camera forms), and the device copy of the ids brought up to date -- a synchronous upload through
+// the handle's own stream, needed only after slots were appended or re-tagged
+bool sf_camera_active(const sf_context* c);
+int sf_camera_sync(sf_context* c);
 void sf_prof_begin(sf_context* c, int kernel);
 void sf_prof_end(sf_context* c, int kernel);
 
 // gate selector of the matching kernels: 0 = 3D->3D, 1 = PnP, 2 = PnP without a calibrated camera, 3 = PnP with
 // Vis/ForwardEstOnly = false (either direction's gate sends the pair on; each estimate then checks its own)
+// With a camera id per slot (cam_view set: the stage sequence of a store with cameras) the gate is the pair's: the matcher
+// runs the PnP gate if ANY model of the table is valid, and the pairs whose camera B is not are closed behind it --
+// forward only by k_camera_gate, with both directions by each direction's estimate (k_pnp_cam) and their merge.
 inline int sf_est_mode(const sf_context* c) {
-  return c->dparams.estimation_type == 1 ? (c->dparams.calibrated ? (c->dparams.bidirectional ? 3 : 1) : 2) : 0;
+  if (c->dparams.estimation_type != 1) return 0;
+  bool calibrated = c->dparams.calibrated != 0;
+  if (c->cam_view.table)
+    for (const CameraBlock& b : c->cam_blocks) calibrated = calibrated || b.calibrated != 0;
+  return calibrated ? (c->dparams.bidirectional ? 3 : 1) : 2;
 }
 
 // The argument list of the pass-1 stage kernels (k_match.hip, k_match_u8.hip):
@@ -807,6 +881,7 @@ int sf_launch_match_global_u8(sf_context* c, StoreView st, const int32_t* d_from
 // The stage pipeline's motion estimate of pass 1 or 2 (3D-3D RANSAC or PnP by estimation_type) for the pairs in that
 // pass's work list, with the second direction, the merge and the bundle adjustment the parameters ask for (k_verify.hip).
 int sf_launch_estimate(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n, int pass);
+int sf_launch_camera_gate(sf_context* c, const int32_t* d_to, int n);   // behind the matcher, on a store with camera ids (k_verify.hip)
 // Guided matching for pairs whose pass 1 succeeded; builds the pass-2 RANSAC work list.
 int sf_launch_guided(sf_context* c, StoreView st, const int32_t* d_from, const int32_t* d_to, int n);
 // The bundle adjustment of a pass's estimates as a launch of its own (k_verify.hip)

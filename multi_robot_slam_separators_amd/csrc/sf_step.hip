@@ -576,6 +576,9 @@ extern "C" int sf_step_issue(sf_handle c, int32_t slot_base_other, int32_t slot_
   if (c->nn_local.n <= 0 || c->nn_recv.n <= 0)
     return sf_fail(c, SF_EINVAL, "empty descriptor database (data_handler.py:308 guards this case)");
   SF_HIP(c, hipSetDevice(c->device));
+  // camera ids of slots appended or re-tagged since the last step: uploaded through the handle's stream before a lane is
+  // picked (the steps in flight were settled by whatever changed the store)
+  if (sf_camera_active(c)) { const int rc0 = sf_camera_sync(c); if (rc0 != SF_OK) return rc0; }
   const bool mirrored = c->step_mirror_records[0] != nullptr;
   if (mirrored) {
     // A mirror has ONE caller buffer (and one caller-zeroed counter) per parity: step k + 2 writes where step k wrote.  The

@@ -511,5 +511,147 @@ extern "C" int sf_store_clear(sf_handle c) {
   (void)sf_lanes_touch(c, true);
   SF_HIP(c, hipStreamSynchronize(c->stream));
   c->store.slots = 0;
+  c->cam_tags.clear();           // (the ids go with the slots; the table and the selection stay)
+  c->cam_nonzero = 0;
+  c->cam_dev_n = 0;
+  return SF_OK;
+}
+
+// ---- camera models: a table per handle, an id per store slot ------------------------------------------------------------
+// No append path stamps its slots itself: the slots behind cam_tags.size() are the ones appended since the ids were last
+// written out, and they carry the id selected then -- written out here, before the selection changes and before an id is
+// read.
+static void camera_settle(sf_context* c) {
+  const size_t n = (size_t)std::max(c->store.slots, 0);
+  if (c->cam_tags.size() > n) {          // (slots were dropped without their ids -- see Store::slots: the ids go now)
+    c->cam_tags.resize(n);
+    c->cam_nonzero = (int)(n - (size_t)std::count(c->cam_tags.begin(), c->cam_tags.end(), (uint8_t)0));
+    c->cam_dev_n = 0;
+  }
+  if (c->cam_tags.size() >= n) return;
+  if (c->cam_sel) c->cam_nonzero += (int)(n - c->cam_tags.size());
+  c->cam_tags.resize(n, (uint8_t)c->cam_sel);
+}
+
+bool sf_camera_active(const sf_context* c) {
+  return c->cam_nonzero > 0 || (c->cam_sel != 0 && (size_t)std::max(c->store.slots, 0) > c->cam_tags.size());
+}
+
+int sf_camera_sync(sf_context* c) {
+  camera_settle(c);
+  const int n = c->store.slots;
+  if (c->cam_nonzero == 0 || c->cam_dev_n >= n) return SF_OK;     // (no kernel reads an id / the copy is current)
+  hipStream_t s0 = c->ws[0].stream;
+  if (c->cam_tags_dev.bytes < (size_t)n) {
+    (void)sf_lanes_touch(c, true);                                  // the old array is freed: nothing may still read it
+    SF_HIP(c, hipStreamSynchronize(s0));
+    const int rc = sf_buf_reserve(c, c->cam_tags_dev, (size_t)std::max(n, c->store.cap_slots));
+    if (rc != SF_OK) return rc;
+  }
+  // (every step in flight was settled by the append or by sf_store_set_camera; what is queued on the handle's stream is
+  //  ordered before the copy, and the wait makes the ids visible to whichever stream the verification runs on)
+  SF_HIP(c, hipMemcpyAsync(c->cam_tags_dev.p, c->cam_tags.data(), (size_t)n, hipMemcpyHostToDevice, s0));
+  SF_HIP(c, hipStreamSynchronize(s0));
+  c->cam_dev_n = n;
+  return SF_OK;
+}
+
+static sf_camera_model camera_of_params(const sf_params& p) {
+  sf_camera_model m;
+  memset(&m, 0, sizeof(m));
+  m.fx = p.fx; m.fy = p.fy; m.cx = p.cx; m.cy = p.cy;
+  m.image_width = p.image_width; m.image_height = p.image_height;
+  memcpy(m.local_transform, p.local_transform, sizeof(m.local_transform));
+  m.stereo_baseline = p.stereo_baseline;
+  return m;
+}
+
+static void camera_table_facts(sf_context* c) {
+  c->cam_max_cells = 0;
+  bool any_cal = false, any_uncal = false;
+  for (const CameraBlock& b : c->cam_blocks) {
+    c->cam_max_cells = std::max(c->cam_max_cells, b.grid_gx * b.grid_gy);
+    (b.calibrated ? any_cal : any_uncal) = true;
+  }
+  c->cam_mixed_calibration = any_cal && any_uncal;
+}
+
+extern "C" int sf_camera_add(sf_handle c, const sf_camera_model* m, int32_t* id_out) {
+  if (!c || !m || !id_out) return SF_EINVAL;
+  const double k[4] = {m->fx, m->fy, m->cx, m->cy};
+  for (double v : k)
+    if (!std::isfinite(v) || v < 0.0) return sf_fail(c, SF_EINVAL, "sf_camera_add: fx, fy, cx, cy must be finite and >= 0");
+  if (m->image_width < 0 || m->image_height < 0) return sf_fail(c, SF_EINVAL, "sf_camera_add: image size %d x %d", m->image_width, m->image_height);
+  if (!std::isfinite(m->stereo_baseline) || m->stereo_baseline < 0.f) return sf_fail(c, SF_EINVAL, "sf_camera_add: stereo_baseline must be finite and >= 0");
+  for (float v : m->local_transform)
+    if (!std::isfinite(v)) return sf_fail(c, SF_EINVAL, "sf_camera_add: local_transform holds a non-finite value");
+  if (m->reserved != 0) return sf_fail(c, SF_EINVAL, "sf_camera_add: reserved must be 0");
+  if ((int)c->cam_models.size() >= SF_MAX_CAMERAS) return sf_fail(c, SF_ERANGE, "sf_camera_add: the table holds %d models", SF_MAX_CAMERAS);
+  SF_HIP(c, hipSetDevice(c->device));
+  int rc;
+  // the whole table is reserved once, so the kernels of earlier calls keep reading valid memory while an entry no slot
+  // of theirs names is written
+  if ((rc = sf_buf_reserve(c, c->cam_table, (size_t)(SF_MAX_CAMERAS + 1) * sizeof(CameraBlock))) != SF_OK) return rc;
+  CameraBlock b0, b;
+  sf_camera_derive(camera_of_params(c->params), c->params.guess_win_size, &b0);
+  sf_camera_derive(*m, c->params.guess_win_size, &b);
+  const bool first = c->cam_blocks.empty();
+  const int id = (int)c->cam_models.size() + 1;
+  hipStream_t s0 = c->ws[0].stream;
+  if (first) SF_HIP(c, hipMemcpyAsync(c->cam_table.p, &b0, sizeof(b0), hipMemcpyHostToDevice, s0));
+  SF_HIP(c, hipMemcpyAsync((CameraBlock*)c->cam_table.p + id, &b, sizeof(b), hipMemcpyHostToDevice, s0));
+  SF_HIP(c, hipStreamSynchronize(s0));
+  if (first) c->cam_blocks.push_back(b0);
+  c->cam_blocks.push_back(b);
+  c->cam_models.push_back(*m);
+  camera_table_facts(c);
+  *id_out = id;
+  return SF_OK;
+}
+
+extern "C" int sf_camera_get(sf_handle c, int32_t id, sf_camera_model* out) {
+  if (!c || !out) return SF_EINVAL;
+  if (id < 0 || id > (int)c->cam_models.size()) return sf_fail(c, SF_EINVAL, "camera id %d outside the table (0 .. %d)", id, (int)c->cam_models.size());
+  *out = id == 0 ? camera_of_params(c->params) : c->cam_models[id - 1];
+  return SF_OK;
+}
+
+extern "C" int sf_camera_count(sf_handle c, int32_t* n_out) {
+  if (!c || !n_out) return SF_EINVAL;
+  *n_out = (int32_t)c->cam_models.size();
+  return SF_OK;
+}
+
+extern "C" int sf_camera_select(sf_handle c, int32_t id) {
+  if (!c) return SF_EINVAL;
+  if (id < 0 || id > (int)c->cam_models.size()) return sf_fail(c, SF_EINVAL, "camera id %d outside the table (0 .. %d)", id, (int)c->cam_models.size());
+  camera_settle(c);
+  c->cam_sel = id;
+  return SF_OK;
+}
+
+extern "C" int sf_store_set_camera(sf_handle c, int32_t first_slot, int32_t n, int32_t id) {
+  if (!c) return SF_EINVAL;
+  if (id < 0 || id > (int)c->cam_models.size()) return sf_fail(c, SF_EINVAL, "camera id %d outside the table (0 .. %d)", id, (int)c->cam_models.size());
+  if (first_slot < 0 || n < 0 || (long long)first_slot + n > c->store.slots)
+    return sf_fail(c, SF_EINVAL, "slots %d .. %lld lie outside the store's %d", first_slot, (long long)first_slot + n, c->store.slots);
+  if (n == 0) return SF_OK;
+  // the steps in flight were issued on the ids as they are: settled and drained before the device copy is written again
+  (void)sf_lanes_touch(c, true);
+  SF_HIP(c, hipStreamSynchronize(c->ws[0].stream));
+  camera_settle(c);
+  for (int i = first_slot; i < first_slot + n; ++i) {
+    c->cam_nonzero += (id != 0) - (c->cam_tags[i] != 0);
+    c->cam_tags[i] = (uint8_t)id;
+  }
+  c->cam_dev_n = 0;
+  return SF_OK;
+}
+
+extern "C" int sf_store_get_camera(sf_handle c, int32_t slot, int32_t* id_out) {
+  if (!c || !id_out) return SF_EINVAL;
+  if (slot < 0 || slot >= c->store.slots) return sf_fail(c, SF_EINVAL, "slot %d outside the store's %d", slot, c->store.slots);
+  camera_settle(c);
+  *id_out = c->cam_tags[slot];
   return SF_OK;
 }

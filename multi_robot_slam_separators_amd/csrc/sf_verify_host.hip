@@ -76,8 +76,12 @@ static bool sf_use_split(const sf_context* c, const StoreView& v, int n) {
 
 VerifyPlan sf_verify_plan(const sf_context* c, const StoreView& v, int n) {
   VerifyPlan p;
+  // a camera id on a slot of the store (not the scratch slots of sf_estimate_transform: always id 0): the stage kernels
+  // carry the per-pair camera, as they carry Vis/CorGuessMatchToProjection; the fused, split and chain forms do not
+  p.cameras = v.desc != nullptr && v.desc == (const uint32_t*)c->store.desc.p && sf_camera_active(c);
   if (c->overlap && n >= c->overlap_min_pairs) { p.form = VerifyPlan::HALVES; p.lists = true; p.single = false; return p; }
   p.single = n <= SF_CHUNK;
+  if (p.cameras) { p.form = VerifyPlan::STAGES; p.lists = true; return p; }
   // Vis/CorGuessMatchToProjection = true: pass 2 is k_guided_tp, a stage kernel; the fused, split and chain forms carry
   // only the other branch (guided_body) inline
   if (c->dparams.guess_match_to_projection) { p.form = VerifyPlan::STAGES; p.lists = true; return p; }
@@ -174,11 +178,21 @@ static int verify_sequence(sf_context* c, const StoreView& view, const int32_t* 
   }
   c->w->last_lists_valid = true;
   SF_HIP(c, hipMemsetAsync(c->w->counters.p, 0, 64, c->stream));   // work-list counters of the stage kernels
-  if ((rc = sf_launch_match_global(c, view, d_from, d_to, m)) != SF_OK) return rc;
-  if ((rc = sf_launch_estimate(c, view, d_from, d_to, m, 1)) != SF_OK) return rc;
-  if ((rc = sf_launch_guided(c, view, d_from, d_to, m)) != SF_OK) return rc;
-  if ((rc = sf_launch_estimate(c, view, d_from, d_to, m, 2)) != SF_OK) return rc;
-  return sf_launch_finalize(c, m, d_out);
+  // (the launchers of this sequence take the camera forms of their kernels iff the view names a table)
+  c->cam_view = CameraView();
+  if (plan.cameras) {
+    c->cam_view.table = (const CameraBlock*)c->cam_table.p;
+    c->cam_view.tags = (const uint8_t*)c->cam_tags_dev.p;
+    c->cam_view.n_slots = std::min(view.n_slots, c->cam_dev_n);
+  }
+  if ((rc = sf_launch_match_global(c, view, d_from, d_to, m)) == SF_OK &&
+      (rc = sf_launch_camera_gate(c, d_to, m)) == SF_OK &&
+      (rc = sf_launch_estimate(c, view, d_from, d_to, m, 1)) == SF_OK &&
+      (rc = sf_launch_guided(c, view, d_from, d_to, m)) == SF_OK &&
+      (rc = sf_launch_estimate(c, view, d_from, d_to, m, 2)) == SF_OK)
+    rc = sf_launch_finalize(c, m, d_out);
+  c->cam_view = CameraView();
+  return rc;
 }
 
 // The stream of the second half of the two-stream path (ws[SF_STEP_MAX_LANES]): created on first use.
@@ -213,10 +227,12 @@ int sf_verify_device(sf_context* c, const Store& st, const int32_t* d_from, cons
   const StoreView view = sf_store_view(st);
   const VerifyPlan plan = given ? *given : sf_verify_plan(c, view, n);
   int rc;
+  if (plan.cameras && (rc = sf_camera_sync(c)) != SF_OK) return rc;      // the slots' camera ids, current on the device
   if (plan.form == VerifyPlan::HALVES) {
     if ((rc = half_create(c)) != SF_OK) return rc;
     Workspace& h = c->ws[SF_STEP_MAX_LANES];
     VerifyPlan stages;                                   // (two FUSED halves on two streams were measured too and gain nothing)
+    stages.cameras = plan.cameras;
     const int span = std::min(n, 2 * SF_CHUNK);          // pairs per round: one chunk per stream
     const int half0 = (std::min(span, n) + 1) / 2;
     if ((rc = ws_reserve(c, std::min(half0, SF_CHUNK), st.kcap, stages.lists)) != SF_OK) return rc;

@@ -159,6 +159,12 @@ def load():
         "sf_store_import_keyframes_device": (C.c_int, [vp, vp, C.c_uint64, i32, i32, i32, P(i32)]),
         "sf_store_wire_status": (C.c_int, [vp, P(i32)]),
         "sf_store_clear": (C.c_int, [vp]),
+        "sf_camera_add": (C.c_int, [vp, P(_abi.CameraModel), P(i32)]),
+        "sf_camera_get": (C.c_int, [vp, i32, P(_abi.CameraModel)]),
+        "sf_camera_count": (C.c_int, [vp, P(i32)]),
+        "sf_camera_select": (C.c_int, [vp, i32]),
+        "sf_store_set_camera": (C.c_int, [vp, i32, i32, i32]),
+        "sf_store_get_camera": (C.c_int, [vp, i32, P(i32)]),
         "sf_estimate_transform": (C.c_int, [vp, P(_abi.Features), P(_abi.Features), vp]),
         "sf_estimate_transform_batch": (C.c_int, [vp, P(_abi.Features), P(_abi.Features), i32, vp]),
         "sf_verify_pairs": (C.c_int, [vp, vp, vp, i32, vp]),
@@ -267,6 +273,7 @@ EXPORTED = [
     "sf_set_option",
     "sf_nn_find_matches", "sf_nn_last_row_minima", "sf_nn_last_filter_dims", "sf_nn_walk", "sf_store_add_keyframe",
     "sf_store_add_keyframes_device", "sf_store_size", "sf_store_clear",
+    "sf_camera_add", "sf_camera_get", "sf_camera_count", "sf_camera_select", "sf_store_set_camera", "sf_store_get_camera",
     "sf_brief_set_pattern", "sf_brief_get_pattern", "sf_extract_keyframe_device", "sf_detect_corners_device", "sf_stereo_flow_defaults", "sf_stereo_correspondences_device", "sf_detector_defaults", "sf_get_features_and_descriptor", "sf_netvlad_load", "sf_netvlad_infer_device", "sf_netvlad_infer_batch_device", "sf_estimate_transform",
     "sf_estimate_transform_batch", "sf_verify_pairs", "sf_verify_pairs_device", "sf_verify_matches_device", "sf_find_matches_and_verify_device", "sf_compact_accepted_device",
     "sf_compact_accepted_device_async", "sf_step_issue", "sf_step_retire", "sf_memcpy_device_async", "sf_step_mirror", "sf_step_mirror_pair", "sf_step_mirror_streams", "sf_accept_stream_set", "sf_accept_stream_select", "sf_accept_stream_status", "sf_last_match_results", "sf_compact_accepted_indexed_device_async", "sf_compact_accepted_indexed_mirrored_device_async",
@@ -1165,6 +1172,36 @@ class SeparatorFinder:
 
     def store_clear(self):
         self._check(self._L.sf_store_clear(self._h))
+
+    # -- a camera model per keyframe (include/sepfinder.h: sf_camera_model) ---------------------------
+    def camera_add(self, model):
+        """sf_camera_add: adds an _abi.CameraModel to the handle's table; returns its id (1, 2, ..)."""
+        cid = C.c_int32()
+        self._check(self._L.sf_camera_add(self._h, C.byref(model), C.byref(cid)))
+        return cid.value
+
+    def camera_get(self, cam_id):
+        """sf_camera_get: the model behind an id (0: the handle's sf_params camera)."""
+        m = _abi.CameraModel()
+        self._check(self._L.sf_camera_get(self._h, int(cam_id), C.byref(m)))
+        return m
+
+    def camera_count(self):
+        n = C.c_int32()
+        self._check(self._L.sf_camera_count(self._h, C.byref(n)))
+        return n.value
+
+    def camera_select(self, cam_id):
+        """sf_camera_select: slots appended from now on carry this id."""
+        self._check(self._L.sf_camera_select(self._h, int(cam_id)))
+
+    def store_set_camera(self, first_slot, n, cam_id):
+        self._check(self._L.sf_store_set_camera(self._h, int(first_slot), int(n), int(cam_id)))
+
+    def store_get_camera(self, slot):
+        cid = C.c_int32()
+        self._check(self._L.sf_store_get_camera(self._h, int(slot), C.byref(cid)))
+        return cid.value
 
     # -- store slots as bytes (include/sepfinder.h: sf_kfblob_header) ---------------------------------
     def export_plan(self, first_slot, n):
