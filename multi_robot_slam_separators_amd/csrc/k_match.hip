@@ -845,11 +845,15 @@ __device__ __forceinline__ bool mf_repair_accept(const uint32_t* fromD, int Kf, 
 // Guard, prologue, compaction loop and header write are spelt out here and not taken from sf_match_device.hpp as
 // k_match_global does: this body is inlined into k_verify_fused and k_match_split, whose vector code and register
 // allocation move with any of them behind a function boundary (profiles/match_finish_isa.txt); the calls below do not.
-template <int W, int NQ, int NT, int MF_NTL = 2, bool MF_PIPE = false>
+// LEAN (k_match_split): the prologue and the compaction in the forms of docs/match_tail.md -- one staging loop with up to
+// four loads in flight that also zeroes cnt, all of a wavefront's ballots in front of ONE barrier -- and *null_matches =
+// the `matches` of the null pass state written here, for the caller's write_null_result (every thread; meaningful when
+// the return value is false).  Same bytes; the other callers keep the statements their register allocation was tuned on.
+template <int W, int NQ, int NT, int MF_NTL = 2, bool MF_PIPE = false, bool LEAN = false>
 __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int sF, int sT, float nndr, int min_inliers,
                                               int est, uint32_t* out, CorrHeader& hdr_out, PassState& pass_out,
                                               int32_t* __restrict__ list, int32_t* __restrict__ counter, int* smem,
-                                              unsigned long long* trace_row = nullptr) {
+                                              unsigned long long* trace_row = nullptr, int* null_matches = nullptr) {
   constexpr int NW = NT / 64;
   const int tid = threadIdx.x;
   // the wavefront's number as a scalar: the loop over its column groups is then scalar control flow, not a divergent
@@ -862,6 +866,7 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
       hdr_out = h;
       write_null_pass(pass_out, 0);
     }
+    if constexpr (LEAN) *null_matches = 0;
     return false;
   }
   const int4 mF = st.meta[sF], mT = st.meta[sT];
@@ -878,12 +883,35 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
   //  latency in front of a pair's first MFMA instead of two, at 128 registers and no scratch: 22.6 against 22.8 M pairs/s,
   //  profiles/r05p_preload_ab.txt.  With four to five workgroups of other pairs on the CU a pair's own staging latency is
   //  already covered; not kept.)
-  {
+  if constexpr (LEAN) {
+    // one loop: four 16-byte items per thread and trip, their loads issued before the first LDS store waits (one memory
+    // latency per 512 rows of W = 8 instead of one per 128), `cnt` zeroed beside the stores
+    // (the loads are unconditional, an item past the block re-reads the block's last one: loads under a condition came out
+    //  as one branch per item with the stores behind them laid out twice, and as an array written under a condition in scratch)
+    const int n16 = Kf * (W / 4);
+    const uint4* src = reinterpret_cast<const uint4*>(dF);
+    uint4* dst = reinterpret_cast<uint4*>(fromD);
+    for (int i = tid; i < n16; i += 4 * NT) {
+      uint4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)       // (a 32-bit byte offset from the block's scalar base: two instructions per address)
+        v[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(src) + (uint32_t)min(i + u * NT, n16 - 1) * 16u);
+      // (the four values exist HERE: without this the compiler sinks each load into the condition of its store and waits
+      //  for it there, four latencies one after the other again)
+      asm volatile("" ::"v"(v[0].x), "v"(v[0].y), "v"(v[0].z), "v"(v[0].w), "v"(v[1].x), "v"(v[1].y), "v"(v[1].z), "v"(v[1].w),
+                   "v"(v[2].x), "v"(v[2].y), "v"(v[2].z), "v"(v[2].w), "v"(v[3].x), "v"(v[3].y), "v"(v[3].z), "v"(v[3].w));
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (i + u * NT < n16) dst[i + u * NT] = v[u];
+        if (i + u * NT < Kf) cnt[i + u * NT] = 0;
+      }
+    }
+  } else {
     const uint4* src = reinterpret_cast<const uint4*>(dF);
     uint4* dst = reinterpret_cast<uint4*>(fromD);
     for (int i = tid; i < Kf * (W / 4); i += NT) dst[i] = src[i];
+    for (int i = tid; i < Kf; i += NT) cnt[i] = 0;
   }
-  for (int i = tid; i < Kf; i += NT) cnt[i] = 0;
   if (tid < 16) misc[tid] = 0;
   __syncthreads();
   SF_TRACE_ROW_MARK(trace_row, 32);   // "from" rows staged
@@ -1056,6 +1084,50 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
   SF_TRACE_ROW_MARK(trace_row, 34);   // all wavefronts done
 
   int running = 0;
+  if constexpr (LEAN) {
+    // All ballots first: trip t of this wavefront covers "from" rows t * NT + tid; its mask stays in scalar registers and
+    // its count travels as one byte (<= 64) of two words per wavefront, misc[4 + 2 wave], misc[5 + 2 wave].  Behind ONE
+    // barrier every wavefront sums the bytes of the NW rows in 16-bit fields (<= 256 per trip) -- the entries in front of
+    // its own, per trip -- and writes: the order of out[] (ascending "from" index) and n_corr are those of the loop below.
+    constexpr int MAXT = MF_MAX_ROWS / NT;
+    static_assert(MAXT <= 8 && NW <= 4, "two words of byte counts per wavefront in misc[4..12)");
+    const int ntrip = (Kf + NT - 1) / NT;          // (scalar; Kf <= kcap <= MF_MAX_ROWS on this path)
+    unsigned long long bal[MAXT];
+    uint32_t pk[2] = {0u, 0u};
+#pragma unroll
+    for (int t = 0; t < MAXT; ++t) bal[t] = 0ull;
+#pragma unroll
+    for (int t = 0; t < MAXT; ++t) {
+      if (t >= ntrip) break;
+      const int f = t * NT + tid;
+      bal[t] = __ballot((f < Kf) && (cnt[f] == 1));
+      pk[t >> 2] |= (uint32_t)__popcll(bal[t]) << (8 * (t & 3));
+    }
+    if (lane == 0) { misc[4 + 2 * wave] = (int)pk[0]; misc[5 + 2 * wave] = (int)pk[1]; }
+    __syncthreads();
+    uint32_t tot[2][2] = {{0u, 0u}, {0u, 0u}}, mine[2][2] = {{0u, 0u}, {0u, 0u}};   // [word][even / odd trips of it]
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        if (j == 1 && ntrip <= 4) continue;
+        const uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane(misc[4 + 2 * w + j]);
+        const uint32_t e = x & 0x00FF00FFu, o = (x >> 8) & 0x00FF00FFu;
+        tot[j][0] += e; tot[j][1] += o;
+        if (w < wave) { mine[j][0] += e; mine[j][1] += o; }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < MAXT; ++t) {
+      if (t >= ntrip) break;
+      const int sh = 16 * ((t & 3) >> 1);
+      const int total = (int)((tot[t >> 2][t & 1] >> sh) & 0xFFFFu), woff = (int)((mine[t >> 2][t & 1] >> sh) & 0xFFFFu);
+      const int f = t * NT + tid;
+      // (the mask is the condition: it goes to exec as it is, no per-lane flag is kept across the barrier)
+      if (__builtin_amdgcn_inverse_ballot_w64(bal[t])) out[running + woff + mf_rank_below(bal[t])] = (uint32_t)f | ((uint32_t)owner[f] << 16);
+      running += total;
+    }
+  } else
   for (int base = 0; base < Kf; base += NT) {
     const int f = base + tid;
     const bool flag = (f < Kf) && (cnt[f] == 1);
@@ -1079,8 +1151,10 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
 
   const MatchGates G = match_gates(Kf, Kt, mF, mT, misc[0], n_corr, min_inliers, est);
   const bool motion = G.motion, survivor = G.survivor;
-  if (motion && !survivor)
+  if (motion && !survivor) {
+    if constexpr (LEAN) __syncthreads();         // the list's entries are other threads' (the old loop ended with a barrier)
     corr_count_finite<NT>(st.xyz + (size_t)sF * kcap * 3, st.xyz + (size_t)sT * kcap * 3, out, n_corr, est == 0, &misc[2]);
+  }
   if (tid == 0) {
     CorrHeader h;
     h.n_corr = n_corr;
@@ -1091,6 +1165,7 @@ __device__ __forceinline__ bool match_v2_body(const StoreView& st, int pair, int
     write_null_pass(pass_out, (motion && !survivor) ? misc[2] : 0);
     if (survivor && list) worklist_append(list, counter, pair);
   }
+  if constexpr (LEAN) *null_matches = (motion && !survivor) ? misc[2] : 0;     // (misc[2]: final behind corr_count_finite's barrier)
   return survivor;
 }
 

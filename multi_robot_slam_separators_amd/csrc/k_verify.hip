@@ -221,6 +221,31 @@ k_verify_fused(StoreView st, const int32_t* __restrict__ pair_from, const int32_
 // bodies, same bytes.  On ONE stream the fused kernel is the faster form (its chains overlap other pairs' matching
 // inside the launch); since sf_step_issue alternates the steps between two streams the neighbouring step fills a
 // launch's tail anyway and the split form wins -- sf_use_split (sf_verify_host.hip) picks it there (SF_OPT_STEP_SPLIT).
+// The record finalize_one(p, p, 0, .) assembles from a null pass state p = write_null_pass(., matches), written by lanes
+// 0..22 of the workgroup's first wavefront as one 16-byte store each (368 B = 23 x 16).  Such a record is zero but for the
+// covariance diagonal -- SF_NULL_VAR under finalize_one's clamp, at doubles 0, 7, 14, 21, 28, 35 of the block -- and
+// `matches` / `matches_pass1`; inliers, the three flags and the padding are 0.  Called by the whole workgroup.
+__device__ __forceinline__ void write_null_result(sf_result& out, int matches) {
+  static_assert(sizeof(sf_result) == 23 * 16 && offsetof(sf_result, covariance) == 56 && offsetof(sf_result, inliers) == 344 &&
+                offsetof(sf_result, matches) == 348 && offsetof(sf_result, inliers_pass1) == 352 &&
+                offsetof(sf_result, matches_pass1) == 356 && offsetof(sf_result, success) == 360,
+                "the 16-byte chunks below follow sf_result's layout");
+  const int c = (int)threadIdx.x;                // chunk: bytes 16 c .. 16 c + 15 of the record
+  if (c >= 23) return;
+  constexpr double D = SF_NULL_VAR <= 1e-9 ? 1e-9 : SF_NULL_VAR;
+  const unsigned long long d = (unsigned long long)__double_as_longlong(D);
+  const uint32_t dlo = (uint32_t)d, dhi = (uint32_t)(d >> 32);
+  // covariance[7 k] starts at byte 56 + 56 k: the upper half of chunks 3, 10, 17 (k = 0, 2, 4), the lower half of chunks
+  // 7, 14, 21 (k = 1, 3, 5); chunk 21 ends with inliers and matches, chunk 22 is inliers_pass1, matches_pass1, flags, pad
+  const bool up = c == 3 || c == 10 || c == 17, low = c == 7 || c == 14 || c == 21;
+  uint4 v;
+  v.x = low ? dlo : 0u;
+  v.y = low ? dhi : (c == 22 ? (uint32_t)matches : 0u);
+  v.z = up ? dlo : 0u;
+  v.w = up ? dhi : (c == 21 ? (uint32_t)matches : 0u);
+  reinterpret_cast<uint4*>(&out)[c] = v;
+}
+
 template <int W, int NTL = 4, int MINW = 3>
 __global__ void __launch_bounds__(SF_BLOCK, MINW)
 k_match_split(StoreView st, const int32_t* __restrict__ pair_from, const int32_t* __restrict__ pair_to,
@@ -231,20 +256,24 @@ k_match_split(StoreView st, const int32_t* __restrict__ pair_from, const int32_t
   extern __shared__ __attribute__((aligned(16))) int smem_i[];
   const int pair = blockIdx.x;
   SF_TRACE_MARK(P, pair, 0);
-  const bool survivor = match_v2_body<W, 0, SF_BLOCK, NTL, SF_MATCH_PIPE != 0>(st, pair, pair_from[pair], pair_to[pair], P.nndr, P.min_inliers,
+  int matches = 0;       // of the null pass state the body wrote for a pair that does not survive
+  const bool survivor = match_v2_body<W, 0, SF_BLOCK, NTL, SF_MATCH_PIPE != 0, true>(st, pair, pair_from[pair], pair_to[pair], P.nndr, P.min_inliers,
                                                          est, corr1 + (size_t)pair * st.kcap, hdr1[pair], pass1[pair],
                                                          list, counter, smem_i,
-                                                         P.dbg_trace ? P.dbg_trace + (size_t)pair * SF_TRACE_SLOTS : nullptr);
+                                                         P.dbg_trace ? P.dbg_trace + (size_t)pair * SF_TRACE_SLOTS : nullptr,
+                                                         &matches);
   SF_TRACE_MARK(P, pair, 36);
-  if (!survivor && threadIdx.x == 0) {
-    // no motion estimate: guided matching is not eligible (its pass state is pass 1's), the result is final
-    const PassState p = pass1[pair];
-    if (P.dbg_corr) {
-      const CorrHeader h = {0, 0, 0, 0};
-      hdr2[pair] = h; pass2[pair] = p; guided_flag[pair] = 0;
+  if (!survivor) {
+    // no motion estimate: guided matching is not eligible (its pass state is pass 1's), the result is final -- the record
+    // of two null passes, from the one value that differs between such pairs (no read of pass1[pair] behind its write)
+    write_null_result(out[pair], matches);
+    if (threadIdx.x == 0) {
+      if (P.dbg_corr) {
+        const CorrHeader h = {0, 0, 0, 0};
+        hdr2[pair] = h; write_null_pass(pass2[pair], matches); guided_flag[pair] = 0;
+      }
+      if (P.accept_on && P.accept.flags) P.accept.flags[pair] = 0;      // (accepted-result stream: not accepted)
     }
-    finalize_one(p, p, 0, out[pair]);
-    if (P.accept_on && P.accept.flags) P.accept.flags[pair] = 0;      // (accepted-result stream: not accepted)
   }
 }
 

@@ -21,11 +21,12 @@
 
 // The "no transform" state of a pass (identity covariance scale, `matches` correspondences seen): built where it is
 // written, so that no copy of it stays live in registers across the pass.
+constexpr double SF_NULL_VAR = 1.0;     // var and var_ang of a null pass (write_null_result clamps it as finalize_one does)
 __device__ __forceinline__ void write_null_pass(PassState& out, int matches) {
   PassState ps;
 #pragma unroll
   for (int i = 0; i < 12; ++i) ps.T[i] = 0.f;
-  ps.var = 1.0; ps.var_ang = 1.0;
+  ps.var = SF_NULL_VAR; ps.var_ang = SF_NULL_VAR;
   ps.is_null = 1;
   ps.inliers = 0;
   ps.matches = matches;
@@ -121,7 +122,8 @@ __device__ __forceinline__ void worklist_append(int32_t* __restrict__ list, int3
 // The workgroup's bookkeeping in LDS, [2 kcap + 16] ints:
 //   cnt   [kcap] "to" rows that matched each "from" word
 //   owner [kcap] the matching "to" row (meaningful when cnt == 1)
-//   misc  [16]   0: rejected "to" rows, 2: finite corr, 4..7 wave totals
+//   misc  [16]   0: rejected "to" rows, 2: finite corr, 4..7 wave totals (k_match_split: 4..11, two words of per-trip
+//                byte counts per wavefront, match_v2_body's LEAN compaction)
 
 // "to" row t, accepted by the ratio test, takes "from" word f
 __device__ __forceinline__ void match_claim(int* cnt, int* owner, int f, int t) {

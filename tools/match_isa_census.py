@@ -28,8 +28,14 @@ repairs (no lane accepts against the optimistic second best: every pass of a pai
 model_valu_repaired one whose every group repairs ONCE, both passes' columns merged into one set of lanes and all of them
 certified (the repair region less its exact path, the certificate's loop four times).  Assembly from before the certificate
 (one kind of repair loop, one copy per decode pass) is modelled as it was: every pass repairing, its loop four times.
-  tools/match_isa_census.py [--asm FILE] [--json]
---asm: read an assembly file made before (the parent commit's, say) instead of compiling."""
+The EXECUTED model (docs/match_tail.md) adds what that leaves out: the trips of the loops outside the scan as a function of
+Kf (a prologue loop that loads runs once per 128 "from" rows and global load in it, one that only zeroes once per 256; the
+compaction once per 256, as a loop or as unrolled trips cut at their markers), lane 0's tail split by what its blocks hold,
+and, for a launch of given survivors, non-survivors and void slots, the total of vector and matrix instructions -- the
+counter SQ_INSTS_VALU holds both.
+  tools/match_isa_census.py [--asm FILE | --figures FILE] [--json] [--mix Kf,Kt,survivors,non_survivors,void ...]
+--asm: read an assembly file made before (the parent commit's, say) instead of compiling.
+--figures: run the executed model on the figures of an earlier --json output.  --mix: default the benchmark's launch."""
 import argparse, collections, json, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,6 +45,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-fun
 SPLIT = "13k_match_splitILi8ELi4ELi3EE"
 FUSED = "14k_verify_fusedILi8ELi0ELb0EE"
 KINDS = ("valu", "mfma", "salu", "lds", "vmem")
+BENCH_MIX = "500,500,2000,8000,1506"     # python bench.py: 10 000 pairs, one in five true, on a grid of 11 506 slots
 
 
 def compile_asm(path):
@@ -306,30 +313,150 @@ def census(fn):
             sys.exit("K = %d: not only 4-tile groups" % k)
         return once + (tiles // 4) * (per_group + (rep if repaired else 0) + (k // 32) * loop + (rag if k % 32 else 0))
 
+    # ---- the EXECUTED count: trip counts of the loops outside the scan, lane 0's tail by path (docs/match_tail.md) ------
+    def loops_of(region):            # the sets of blocks of `region` that lie on a cycle inside it, one set per loop
+        region, out, seen = set(region), [], set()
+        sub = {n: [s for s in succ[n] if s in region] for n in region}
+        for n in names:
+            if n in region and n not in seen:
+                fwd = reach([n], sub)
+                if n in fwd:
+                    scc = set(m for m in fwd if n in reach([m], sub))
+                    seen |= scc
+                    out.append(scc)
+        return out
+
+    n_ops = lambda bs, prefix: sum(op.startswith(prefix) for n in bs for op in by[n].ins)
+    # prologue: a loop that loads stages 256 sixteen-byte items per global load and trip (2 Kf items of 256-bit rows), one
+    # that does not zeroes 256 counters per trip; the report of a pair whose slots do not exist (the blocks that store to
+    # global memory in front of the first barrier) belongs to the void path
+    pro = to_bar1 - {bar1}
+    void_report = set(n for n in pro if by[n].has("global_store"))
+    pro_loops = loops_of(pro - void_report)
+    in_pro_loops = set().union(*pro_loops) if pro_loops else set()
+    ex_pro = {"base": total(pro - void_report - in_pro_loops, [cut(bar1, True)])["valu"],
+              "loops": [{"valu": total(lp)["valu"], "rows_per_trip": 128 * n_ops(lp, "global_load") or 256} for lp in pro_loops]}
+    # compaction: from the second barrier to the last barrier in front of the count of finite points (v_cmp_class_f32)
+    tail_all = behind - to_bar2
+    fin_blocks = set(n for n in tail_all if by[n].has("v_cmp_class_f32"))
+    fin = set(fin_blocks)
+    for lp in loops_of(tail_all):
+        if lp & fin_blocks:
+            fin |= lp
+    to_fin = reach(fin, back) if fin else set()
+    cbars = [n for n in bars if n in tail_all and n not in fin and (n in to_fin or not fin)]
+    if not cbars:
+        sys.exit("no barrier of the list compaction found")
+    comp = ((reach([cbars[-1]], back) | {cbars[-1]}) & tail_all) - fin
+    comp_loops = loops_of(comp)
+    ex_comp = {"always": 0, "trips": [], "loop": 0}
+    first_bar_extra = [cut(bar2, False)] if bar2 not in comp else []
+    if comp_loops:                   # a loop of one trip per 256 "from" rows
+        in_l = set().union(*comp_loops)
+        ex_comp["always"] = total(comp - in_l, first_bar_extra)["valu"]
+        ex_comp["loop"] = total(in_l)["valu"]
+    else:                            # unrolled: all ballots (one s_bcnt1_i32_b64 per trip), ONE barrier, all writes (one
+        order = [n for n in names if n in comp]          # v_mbcnt_hi_u32_b32 per trip); a trip's blocks end at its marker
+        cut_at = order.index(cbars[0])
+        trips = []
+        always = total([], first_bar_extra)["valu"]
+        for phase, marker in ((order[:cut_at + 1], "s_bcnt1_i32_b64"), (order[cut_at + 1:], "v_mbcnt_hi_u32_b32")):
+            n_mark = sum(by[n].has(marker) for n in phase)
+            k = 0
+            per = [0] * n_mark
+            for n in phase:
+                if k < n_mark:
+                    per[k] += by[n].count()["valu"]
+                else:
+                    always += by[n].count()["valu"]
+                k += by[n].has(marker)
+            trips.append(per)
+        if len(trips[0]) != len(trips[1]) or not trips[0]:
+            sys.exit("unrolled compaction: %d ballots, %d writes" % (len(trips[0]), len(trips[1])))
+        ex_comp["always"], ex_comp["trips"] = always, [a + b for a, b in zip(*trips)]
+    # lane 0's tail: what is left behind the compaction, by what it holds
+    tail = tail_all - comp - fin
+    pose = set(n for n in tail if any("_f64" in op for op in by[n].ins))       # the pose of an estimate: no null pass runs it
+    alone = set(n for n in live if n not in reaches_scan and n not in from_scan) | void_report
+    ex_tail = {"lane0": total(tail - pose)["valu"], "finite_count": total(fin)["valu"], "pose": total(pose)["valu"],
+               "void_only": total(alone)["valu"], "entry": by["entry"].count()["valu"]}
+    ex = {"prologue": ex_pro, "setup": rows[keys[1]]["valu"], "per_group": per_group, "loop": loop, "ragged": rag, "repair": rep,
+          "handover": rows[keys[8]]["valu"], "compaction": ex_comp, "tail": ex_tail}
+
     ks = (500, 512, 1000)
-    return rows, {k: model(k) for k in ks}, {k: model(k, True) for k in ks}, total(live)
+    return rows, {k: model(k) for k in ks}, {k: model(k, True) for k in ks}, total(live), ex
+
+
+def executed(ex, kf, kt):
+    """Vector instructions one wavefront of a pair EXECUTES, from the figures census() took from the assembly: the regions
+    outside the scan with their trip counts, the groups of wavefront 0, and lane 0's tail by path (first wavefront only)."""
+    ceil = lambda a, b: (a + b - 1) // b
+    pro = ex["prologue"]["base"] + sum(l["valu"] * ceil(kf, l["rows_per_trip"]) for l in ex["prologue"]["loops"])
+    ntrip = ceil(kf, 256)
+    c = ex["compaction"]
+    if c["trips"] and ntrip > len(c["trips"]):
+        sys.exit("Kf = %d: more compaction trips than the kernel has" % kf)
+    comp = c["always"] + sum(c["trips"][:ntrip]) + c["loop"] * ntrip
+    tiles = ceil(ceil(kt, 32), 4) if kf > 0 else 0
+    if tiles % 4:
+        sys.exit("Kt = %d: not only 4-tile groups" % kt)
+    groups = tiles // 4
+    scan = groups * (ex["per_group"] + (kf // 32) * ex["loop"] + (ex["ragged"] if kf % 32 else 0))
+    t = ex["tail"]
+    return {"prologue": pro, "setup": ex["setup"] if kf > 0 else 0, "groups": scan, "repair_per_wavefront": groups * ex["repair"],
+            "handover": ex["handover"], "compaction": comp, "outside_scan": pro + ex["handover"] + comp,
+            "mfma": groups * ceil(kf, 32) * 16,
+            "tail_survivor": t["lane0"], "tail_non_survivor": t["lane0"] + t["finite_count"],
+            "tail_void": t["void_only"] + t["lane0"], "void_wavefront": t["entry"]}
+
+
+def launch(ex, kf, kt, survivors, non_survivors, void):
+    """Vector instructions of one launch (4 wavefronts per slot; MFMAs listed apart: the counter SQ_INSTS_VALU holds both).
+    A survivor's wavefronts decide the second best again once per group, a non-survivor's never; lane 0's tail is counted
+    whole for survivors and void slots, which run less of it (an upper bound, 0.3 % of the total at the benchmark's mix)."""
+    e = executed(ex, kf, kt)
+    wave = e["prologue"] + e["setup"] + e["groups"] + e["handover"] + e["compaction"]
+    valu = (survivors * (4 * (wave + e["repair_per_wavefront"]) + e["tail_survivor"]) +
+            non_survivors * (4 * wave + e["tail_non_survivor"]) + void * (4 * e["void_wavefront"] + e["tail_void"]))
+    mfma = (survivors + non_survivors) * 4 * e["mfma"]
+    return {"valu": valu, "mfma": mfma, "valu_and_mfma": valu + mfma, "per_wavefront": e}
 
 
 def run(asm_path):
     lines = open(asm_path).readlines()
-    rows, model, repaired, whole = census(function_lines(lines, SPLIT))
+    rows, model, repaired, whole, ex = census(function_lines(lines, SPLIT))
     return {"regions": {k: {x: v[x] for x in KINDS} for k, v in rows.items()}, "model_valu": model,
             "model_valu_repaired": repaired,
-            "kernel_total": {x: whole[x] for x in KINDS},
+            "kernel_total": {x: whole[x] for x in KINDS}, "executed_model": ex,
             "k_match_split<8,4,3>": resources(lines, SPLIT), "k_verify_fused<8,0,false>": resources(lines, FUSED)}
+
+
+def mix_of(text):
+    """--mix "Kf,Kt,survivors,non-survivors,void slots" """
+    v = [int(x) for x in text.split(",")]
+    if len(v) != 5 or min(v) < 0:
+        sys.exit("--mix wants Kf,Kt,survivors,non_survivors,void_slots")
+    return v
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--figures", help="a --json output made before: the executed model runs on its figures, nothing is compiled")
+    ap.add_argument("--mix", action="append", help="Kf,Kt,survivors,non_survivors,void_slots of one launch (may repeat)")
     a = ap.parse_args()
-    if a.asm:
+    if a.figures:
+        r = json.load(open(a.figures))
+    elif a.asm:
         r = run(a.asm)
     else:
         with tempfile.TemporaryDirectory() as td:
             compile_asm(os.path.join(td, "tu.s"))
             r = run(os.path.join(td, "tu.s"))
+    mixes = [mix_of(m) for m in (a.mix or [BENCH_MIX])]
+    r["launches"] = [dict(zip(("kf", "kt", "survivors", "non_survivors", "void"), m), **launch(r["executed_model"], *m))
+                     for m in mixes]
     if a.json:
         print(json.dumps(r))
         return
@@ -343,6 +470,29 @@ def main():
               % (int(k), v, r["model_valu_repaired"][k]))
     for name in ("k_match_split<8,4,3>", "k_verify_fused<8,0,false>"):
         print("  %-28s VGPRs %s, scratch %s B, occupancy %s" % (name, r[name]["vgprs"], r[name]["scratch_bytes"], r[name]["occupancy"]))
+    ex = r["executed_model"]
+    print("executed model: what the loops outside the scan cost per trip, lane 0's tail by what it holds")
+    for lp in ex["prologue"]["loops"]:
+        print("  prologue loop, one trip per %4d \"from\" rows: %3d VALU  (the rest of the prologue: %d)"
+              % (lp["rows_per_trip"], lp["valu"], ex["prologue"]["base"]))
+    c = ex["compaction"]
+    print("  compaction: %d VALU always, %s" % (c["always"], "a loop of %d per 256 rows" % c["loop"] if c["loop"] else
+                                                "unrolled trips of %s" % " ".join(str(x) for x in c["trips"])))
+    t = ex["tail"]
+    print("  lane 0's tail: %d VALU; the count of finite points %d per trip; the pose of an estimate %d (never run: the "
+          "state is null); void slots only %d" % (t["lane0"], t["finite_count"], t["pose"], t["void_only"]))
+    for L in r["launches"]:
+        e = L["per_wavefront"]
+        print("launch of %d survivors, %d non-survivors, %d void slots at Kf = %d, Kt = %d:"
+              % (L["survivors"], L["non_survivors"], L["void"], L["kf"], L["kt"]))
+        print("  per wavefront: prologue %d, scan set-up %d, groups %d (+ %d where the second best is decided again), hand-over "
+              "%d, compaction %d; outside the scan %d; MFMA %d" % (e["prologue"], e["setup"], e["groups"],
+                                                                   e["repair_per_wavefront"], e["handover"], e["compaction"],
+                                                                   e["outside_scan"], e["mfma"]))
+        print("  first wavefront's tail: survivor %d, non-survivor %d, void slot %d"
+              % (e["tail_survivor"], e["tail_non_survivor"], e["tail_void"]))
+        print("  launch: VALU %.2f M + MFMA %.2f M = %.2f M  (SQ_INSTS_VALU counts both)"
+              % (L["valu"] / 1e6, L["mfma"] / 1e6, L["valu_and_mfma"] / 1e6))
 
 
 if __name__ == "__main__":
