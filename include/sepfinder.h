@@ -120,6 +120,11 @@ extern "C" {
       sf_depth_interpolation_factor (RGB-D keyframes from a decimated depth image, upstream's util2d::interpolate path).
       A fresh handle holds {0, 0}, with which every depth call behaves and refuses as before; the version number,
       sizeof(sf_params) and SF_K_COUNT stay.                                                                           */
+/* 8, additions: sf_camera_info, SF_MAX_RECTIFY_PLANS, sf_rectify_plan_create, sf_rectify_plan_from_maps,
+      sf_rectify_plan_count, sf_rectify_plan_get, sf_rectify_plan_clear, sf_rectify_maps_device, sf_image_rectify_device,
+      sf_stereo_camera_from_info, SF_OPT_RECTIFY_TABLE, sf_rectify_check_info (sf_experimental.h) (raw camera images:
+      undistortion and rectification on the device).  New calls only; the version number, sizeof(sf_params) and
+      SF_K_COUNT stay.                                                                                                  */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -1156,6 +1161,74 @@ int  sf_add_keyframes_sift_u8_batch_device(sf_handle h, const uint8_t* d_left, c
                                            int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                            float* d_xyz_out, sf_keypoint* d_kpts_out);
 
+/* ---- raw camera images: undistortion and rectification on the device ---------------------------------------------- */
+/* Every call above takes rectified images: the reference's launch files subscribe to image_rect topics.  A raw stereo
+   head (EuRoC-style cam0/image_raw with a radial-tangential calibration) leaves that job to stereo_image_proc, or to
+   rtabmap under Rtabmap/ImagesAlreadyRectified = false: cv::initUndistortRectifyMap + cv::remap(INTER_LINEAR,
+   BORDER_CONSTANT, 0) per image on a CPU core [upstream OpenCV 3.2, restated in tests/rectify_ref.py; as remembered, not
+   from the reference tree: DESIGN.md section 3 lists what the restatement decides].  The calls below do it on the device,
+   in front of sf_image_to_gray_device and the keyframe calls, whose device images with a pitch and a stride they write.
+     map of output pixel (column j, row i), float64, every step one rounded operation in this order:
+       iR = (P[:, :3] R)^-1 (host, adjugate over determinant)
+       X = ((iR00 j) + (iR01 i)) + iR02, likewise Y, W;  w = 1 / W;  x = X w;  y = Y w;  x2 = x x;  y2 = y y;
+       r2 = x2 + y2;  t = 2 x y;  kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2)
+       xd = x kr + p1 t + p2 (r2 + 2 x2);  yd = y kr + p1 (r2 + 2 y2) + p2 t
+       mapx = (float)(fx xd + cx);  mapy = (float)(fy yd + cy)            (fx, fy, cx, cy of K)
+     fixed point: sx = round-half-even(mapx * 32) with the product in float32, ix = sx >> 5, a = sx & 31 (sy, iy, b
+       likewise); a map value that is not finite or whose 32-fold reaches 2^30 in magnitude gives the pixel 0
+     taps: (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1) with the weights 32 (32 - a)(32 - b), 32 a (32 - b),
+       32 (32 - a) b, 32 a b (their sum is 32768); a tap outside the source reads 0; the pixel is
+       (sum of weight x tap + 16384) >> 15 per channel.                                                              */
+typedef struct sf_camera_info {
+  int32_t width, height;          /* the raw image, 1 .. 8192 each                                                   */
+  int32_t out_width, out_height;  /* the rectified image, 1 .. 8192; 0 = the raw size                                */
+  int32_t model;                  /* 0 = plumb_bob (D[0 .. 4]), 1 = rational_polynomial (D[0 .. 7])                   */
+  int32_t reserved;               /* 0                                                                               */
+  double  K[9];                   /* row-major 3 x 3: fx 0 cx / 0 fy cy / 0 0 1; fx, fy > 0, K[1] (skew) = 0          */
+  double  D[8];                   /* k1, k2, p1, p2, k3, k4, k5, k6                                                   */
+  double  R[9];                   /* row-major 3 x 3 rectification rotation                                          */
+  double  P[12];                  /* row-major 3 x 4 projection of the rectified camera; P[0], P[5] > 0               */
+} sf_camera_info;                 /* 328 bytes */
+#define SF_MAX_RECTIFY_PLANS 64   /* ids 1 .. 64 */
+/* Validates a block, derives the plan's constants (iR, K, D) and stores them on the handle and on the device:
+   *plan_out = 1, 2, ..  A value that is not finite, fx or fy <= 0 in K or P, a skew, a singular P[:, :3] R, a size outside
+   1 .. 8192, an unknown model, reserved != 0: SF_EINVAL with a message, nothing changes; a full table: SF_ERANGE.    */
+int  sf_rectify_plan_create(sf_handle h, const sf_camera_info* info, int32_t* plan_out);
+/* A plan from the caller's own float32 maps in HOST memory (row i of the out_width x out_height maps at byte i *
+   map_pitch; source pixel coordinates in a src_width x src_height image): for models the library does not compute -- an
+   equidistant fisheye, a vendor's table.  The maps are converted to the fixed-point form above as they are uploaded and
+   are not kept as floats.  Sizes outside 1 .. 8192, map_pitch below a row: SF_EINVAL; a full table: SF_ERANGE.       */
+int  sf_rectify_plan_from_maps(sf_handle h, const float* mapx, const float* mapy, int32_t out_width, int32_t out_height,
+                               int32_t map_pitch, int32_t src_width, int32_t src_height, int32_t* plan_out);
+int  sf_rectify_plan_count(sf_handle h, int32_t* n_out);
+/* The block a plan was created from; *from_maps (may be NULL) = 1 for a plan of caller maps, whose block holds the four
+   sizes and zeros.  An id outside 1 .. count: SF_EINVAL.                                                              */
+int  sf_rectify_plan_get(sf_handle h, int32_t plan, sf_camera_info* out, int32_t* from_maps);
+/* Drops every plan (after the work queued on them has finished); ids start at 1 again.  sf_store_clear keeps the plans. */
+int  sf_rectify_plan_clear(sf_handle h);
+/* The float32 maps of a computed plan, for inspection: row i of either map at byte i * pitch_bytes (>= 4 * out_width) of
+   the device arrays.  Asynchronous on the handle's stream.  A plan of caller maps: SF_EINVAL (its floats are not kept). */
+int  sf_rectify_maps_device(sf_handle h, int32_t plan, float* d_mapx, float* d_mapy, int32_t pitch_bytes);
+/* Rectifies n_images raw device images under plan_a -- image i at d_src_a + i * src_stride to d_dst_a + i * dst_stride --
+   and, when d_src_b is not NULL, as many under plan_b (d_src_b to d_dst_b: the right camera of a stereo head) in ONE launch,
+   asynchronous on the handle's stream, with no host wait.  Both plans hold the same raw and the same output size.  format
+   is an sf_image_format; out_format is format, or SF_IMAGE_MONO8 from a colour format: the rectified colour pixel goes
+   straight through the handle's gray rule and the planes hold, byte for byte, what sf_image_to_gray_device makes of the
+   rectified colour images.  Any pitches (>= a row), strides (>= the rows they hold; ignored when n_images = 1) and base
+   alignments; bytes outside the out_width x out_height images are never written.  n_images = 0: SF_OK.  A plan id
+   outside the table, plans of unlike sizes, another out_format, a pitch below a row, a missing array: SF_EINVAL.
+   A computed plan runs the computed form (every thread derives its map values from the plan's 21 constants) or the
+   table form (a fixed-point map built once per plan, 8 bytes per output pixel) as SF_OPT_RECTIFY_TABLE says; a plan of
+   caller maps, and the plan beside it in the same call, the table form.  The bytes are the same.                    */
+int  sf_image_rectify_device(sf_handle h, int32_t plan_a, const uint8_t* d_src_a, int32_t plan_b, const uint8_t* d_src_b,
+                             int32_t format, int32_t out_format, int32_t n_images, int32_t src_pitch, size_t src_stride,
+                             uint8_t* d_dst_a, uint8_t* d_dst_b, int32_t dst_pitch, size_t dst_stride);
+/* Host only: the camera of the rectified pair for the extraction calls -- fx = P[0], fy = P[5], cx = P[2], cy = P[6] of
+   the left block, cx_right = P[2] of the right block, baseline = -P_right[3] / P_right[0] (not > 0: SF_EINVAL), the
+   given local_transform (NULL = identity), min_depth = max_depth = 0.                                                */
+int  sf_stereo_camera_from_info(const sf_camera_info* left, const sf_camera_info* right, const float local_transform[12],
+                                sf_stereo_camera* out);
+
 /* ---- RGB-D keyframes: 3D points from a registered depth image, Vis/DepthAsMask ------------------------------------ */
 /* replaces: the depth branch of Feature2D::generateKeypoints3D (called at myRegistrationVis.cpp:382) -- util3d::
    generateKeypoints3DDepth -> projectDepthTo3D(smoothing = true) -> util2d::getDepth(depthErrorRatio 0.02,
@@ -1516,7 +1589,12 @@ enum {
                              and behind the guided matching: three chain launches instead of one.  0: one launch, four
                              wavefronts per survivor.  Results unchanged.  Environment twin: SF_CHAIN_NARROW_EST.
                              Measured faster on the bench step (docs/chain_narrow_estimates.md).                     */
-  SF_OPT_DEBUG_CORR = 4   /* 1: the fused kernel also copies every pair's correspondence lists, headers and pass states
+  SF_OPT_RECTIFY_TABLE = 13, /* the form sf_image_rectify_device runs a computed plan in: 1 (default): a fixed-point map
+                             built on the stream by the plan's first such call, 8 bytes per output pixel; 0: every thread
+                             derives its map values from the plan's constants in float64, no map in memory.  Results
+                             unchanged.  Environment twin: SF_RECTIFY_TABLE.  The default is the measured choice: 2.4
+                             against 3.1 us per 752 x 480 stereo pair in a batch of 64 (profiles/rectify_latency.json). */
+  SF_OPT_DEBUG_CORR = 4  /* 1: the fused kernel also copies every pair's correspondence lists, headers and pass states
                              to the global workspace, which sf_debug_correspondences reads (default 0: they never
                              leave the workgroup's LDS; the stage kernels always keep them in the workspace)       */
 };

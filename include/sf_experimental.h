@@ -99,6 +99,9 @@ void sf_surf_build_tables(float* ori_w, int8_t* ori_xy, float* desc_w);
 int  sf_surf_check_params(const sf_surf_params* params);
 /* The ranges sf_gftt_set_params holds sf_gftt_params to, without a handle: SF_OK or SF_EINVAL; NULL = the defaults.   */
 int  sf_gftt_check_params(const sf_gftt_params* params);
+/* What sf_rectify_plan_create holds an sf_camera_info to, without a handle or a GPU: SF_OK or SF_EINVAL.  iR_out (may be
+   NULL) receives the nine values of (P[:, :3] R)^-1, row-major, as the plan keeps them.                             */
+int  sf_rectify_check_info(const sf_camera_info* info, double* iR_out);
 /* Small shapes for the tests of SURF's batch form; a fresh handle behaves as if neither had been called.  candidate_cap
    (0 = the default, at most 262144) takes the place of the 262144 maxima an image may have, in sf_detect_surf_device
    and the single extraction calls (more: SF_ERANGE) and in the batch forms (more: the keyframe holds no rows, see

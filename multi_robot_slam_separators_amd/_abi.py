@@ -19,6 +19,7 @@ SF_DESC_BYTES_U8 = 128     # uint8 rows compared by L2 (sf_params.desc_type 2)
 (SF_OPT_MATCH_MFMA, SF_OPT_FUSED, SF_OPT_OVERLAP, SF_OPT_CHAIN_WAVES, SF_OPT_DEBUG_CORR, SF_OPT_NN_FULL_FILTER,
  SF_OPT_STEP_OVERLAP, SF_OPT_STEP_SPLIT, SF_OPT_STEP_DEPTH, SF_OPT_STEP_LANES, SF_OPT_STEP_DEVICE_WALK,
  SF_OPT_STEP_SPECULATE, SF_OPT_CHAIN_NARROW_EST) = range(13)      # sf_set_option
+SF_OPT_RECTIFY_TABLE = 13      # computed rectification plans: 1 (default) the table form, 0 the computed form
 
 STATUS_NAMES = {0: "SF_OK", 1: "SF_EINVAL", 2: "SF_EHIP", 3: "SF_ENOMEM", 4: "SF_ERANGE", 5: "SF_ENODEV", 6: "SF_ERCCL"}
 
@@ -419,6 +420,34 @@ SF_IMAGE_RGB8, SF_IMAGE_BGR8, SF_IMAGE_MONO8 = range(3)   # sf_image_format: the
 GRAY_RULE_OPENCV3, GRAY_RULE_OPENCV4 = 0, 1               # sf_image_set_gray_rule
 # (kr, kg, kb, shift) of gray = (R kr + G kg + B kb + (1 << (shift - 1))) >> shift
 GRAY_RULES = {GRAY_RULE_OPENCV3: (4899, 9617, 1868, 14), GRAY_RULE_OPENCV4: (9798, 19235, 3735, 15)}
+
+
+class CameraInfo(C.Structure):
+    """sf_camera_info (include/sepfinder.h): a sensor_msgs/CameraInfo-shaped block, what sf_rectify_plan_create takes."""
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32),
+        ("out_width", C.c_int32), ("out_height", C.c_int32),
+        ("model", C.c_int32), ("reserved", C.c_int32),
+        ("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9), ("P", C.c_double * 12),
+    ]
+
+
+assert C.sizeof(CameraInfo) == 328
+SF_MAX_RECTIFY_PLANS = 64
+DISTORTION_PLUMB_BOB, DISTORTION_RATIONAL_POLYNOMIAL = 0, 1
+
+
+def camera_info(width, height, K, D=(), R=None, P=None, model=DISTORTION_PLUMB_BOB, out_width=0, out_height=0):
+    """K [3, 3], D up to 8 values (k1 k2 p1 p2 k3 k4 k5 k6), R [3, 3] (None: identity), P [3, 4] (None: [K | 0])."""
+    m = CameraInfo()
+    m.width, m.height, m.out_width, m.out_height, m.model, m.reserved = int(width), int(height), int(out_width), int(out_height), int(model), 0
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    R = np.eye(3) if R is None else np.asarray(R, np.float64).reshape(3, 3)
+    P = np.hstack([K, np.zeros((3, 1))]) if P is None else np.asarray(P, np.float64).reshape(3, 4)
+    d = np.zeros(8, np.float64)
+    d[:len(D)] = np.asarray(D, np.float64)
+    m.K[:], m.D[:], m.R[:], m.P[:] = K.ravel().tolist(), d.tolist(), R.ravel().tolist(), P.ravel().tolist()
+    return m
 
 
 class NetvladWeights(C.Structure):

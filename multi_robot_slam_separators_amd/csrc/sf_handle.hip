@@ -250,6 +250,7 @@ void sf_env_knobs(sf_context* c) {
   if (const char* v = getenv("SF_CHAIN_PNP_NW")) { const int nw = atoi(v); c->chain_pnp_nw = (nw == 1 || nw == 2) ? nw : 4; }
   if (const char* v = getenv("SF_CHAIN_NW")) { const int nw = atoi(v); c->chain_nw = (nw == 1 || nw == 2) ? nw : 4; }
   if (const char* v = getenv("SF_CHAIN_NARROW_EST")) c->chain_narrow_est = atoi(v) != 0;   // the three-launch 3D-3D chain
+  if (const char* v = getenv("SF_RECTIFY_TABLE")) c->rect_table = atoi(v) != 0;   // 1: computed rectification plans run the table form
   if (const char* v = getenv("SF_MATCH_MFMA")) c->match_mfma = atoi(v) != 0;   // 0: VALU matcher (A/B reference)
   if (const char* v = getenv("SF_DEBUG_CORR")) c->debug_corr = atoi(v) != 0;   // 1: correspondence lists kept in HBM
   if (const char* v = getenv("SF_OVERLAP")) c->overlap = atoi(v) != 0;         // 1: two-stream halves (sf_verify_device)
@@ -312,6 +313,8 @@ extern "C" void sf_destroy(sf_handle c) {
                  &c->ft_counts, &c->ft_cells, &c->img_src, &c->img_gray, &c->img_desc, &c->wire_plan, &c->wire_status,
                  &c->cam_table, &c->cam_tags_dev};
   for (Buf* b : bufs) sf_buf_free(*b);
+  for (RectifyPlan& p : c->rect_plans) sf_buf_free(p.table);
+  sf_buf_free(c->rect_blocks);
   for (int k = 0; k <= SF_STEP_MAX_LANES; ++k) {
     Workspace& w = c->ws[k];
     w.for_each_buf(sf_buf_free);
@@ -442,6 +445,7 @@ extern "C" int sf_set_option(sf_handle c, int32_t option, int32_t value) {
     case SF_OPT_NN_FULL_FILTER: c->nn_force_full = value != 0; c->nn_coef_level = -1; return SF_OK;
     case SF_OPT_STEP_SPLIT: c->split_auto = value != 0; return SF_OK;
     case SF_OPT_CHAIN_NARROW_EST: c->chain_narrow_est = value != 0; return SF_OK;
+    case SF_OPT_RECTIFY_TABLE: c->rect_table = value != 0; return SF_OK;
     case SF_OPT_STEP_OVERLAP:
       if (c->step_inflight) return sf_fail(c, SF_EINVAL, "SF_OPT_STEP_OVERLAP cannot change while steps are in flight");
       c->step_overlap = value != 0;

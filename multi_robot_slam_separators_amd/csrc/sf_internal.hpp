@@ -15,6 +15,7 @@
 #define SF_STEP_MAX_DEPTH 16     // sf_step_issue: steps in flight at most (SF_OPT_STEP_DEPTH)
 #define SF_CHAIN_NARROW_EST_DEFAULT true   // SF_OPT_CHAIN_NARROW_EST as a handle starts (docs/chain_narrow_estimates.md)
 #define SF_STEP_MAX_LANES 4      // ... dealt over at most this many streams (SF_OPT_STEP_LANES)
+#define SF_RECTIFY_TABLE_DEFAULT true      // SF_OPT_RECTIFY_TABLE as a handle starts: the measured choice (profiles/rectify_latency.json)
 
 // ---- device-resident keyframe store (one arena per field, fixed per-slot stride) ---------------
 // desc : [slots][kcap][W] uint32   W = 8 (<=256-bit descriptors) or 16 (<=512-bit), zero padded; float32 rows (desc_type 1)
@@ -172,6 +173,23 @@ struct PairSource {
 struct Buf {
   void* p = nullptr;
   size_t bytes = 0;
+};
+
+// ---- rectification plans (sf_rectify_plan_create; include/sepfinder.h) ------------------------------------------------------
+// What a computed plan's kernels read with uniform loads: iR = (P[:, :3] R)^-1, K's fx fy cx cy and the eight distortion
+// terms (k4 k5 k6 zero under plumb_bob).  `table` is the fixed-point map {sx, sy} per output pixel: the upload of a plan of
+// caller maps, built on first use (k_rectify_map) for a computed plan that runs the table form.
+struct RectifyBlock {
+  double iR[9];
+  double fx, fy, cx, cy;
+  double D[8];
+};
+struct RectifyPlan {
+  sf_camera_info info;
+  bool from_maps = false;
+  int src_w = 0, src_h = 0, out_w = 0, out_h = 0;
+  Buf table;
+  bool table_ready = false;
 };
 
 struct Store {
@@ -390,6 +408,11 @@ struct sf_context {
   // coefficients (sf_image_set_gray_rule: 0 = OpenCV 3.x, 1 = OpenCV 4.x)
   Buf img_src, img_gray, img_desc;
   int gray_rule = 0;
+  // raw camera images (sf_rectify.hip, k_rectify.hip): rect_plans[id - 1], the device blocks of all of them
+  // ([SF_MAX_RECTIFY_PLANS] RectifyBlock, reserved once) and the form computed plans run in (SF_OPT_RECTIFY_TABLE)
+  std::vector<RectifyPlan> rect_plans;
+  Buf rect_blocks;
+  bool rect_table = SF_RECTIFY_TABLE_DEFAULT;
   struct sf_netvlad_model* netvlad = nullptr;   // NetVLAD inference (k_cnn.hip): weights + activation buffers
   int brief_bytes = 0;                 // 0: table not uploaded yet
   int8_t brief_host[64 * 8 * 4] = {};
@@ -680,6 +703,22 @@ bool sf_gray_rule(int rule, int* kr, int* kg, int* kb, int* shift);
 int sf_launch_image_gray(sf_context* c, const uint8_t* d_src0, const uint8_t* d_src1, int n_first, int format, int rule,
                          int width, int height, int src_pitch, size_t src_stride, int n_images, uint8_t* d_dst, int dst_pitch,
                          size_t dst_stride);
+// k_rectify.hip: the two launches of the rectification calls, asynchronous on the context's stream; the caller
+// (sf_rectify.hip) has validated everything.  sf_launch_rectify_maps writes a computed plan's float32 maps (d_mapx, rows of
+// pitch_bytes) or, with d_table, its fixed-point table [out_h][out_w] {sx, sy}.  sf_launch_rectify: n_a images under block /
+// table a, n_b under b; tab_a / tab_b nullptr = the computed form (both or neither).
+struct RectifyImages {
+  const uint8_t* src_a; const uint8_t* src_b;
+  uint8_t* dst_a; uint8_t* dst_b;
+  int n_a, n_b;
+  int src_w, src_h, out_w, out_h;
+  int src_pitch, dst_pitch;
+  size_t src_stride, dst_stride;
+};
+int sf_launch_rectify_maps(sf_context* c, const RectifyBlock* d_block, int out_w, int out_h, float* d_mapx, float* d_mapy,
+                           int pitch_bytes, int32_t* d_table);
+int sf_launch_rectify(sf_context* c, const RectifyImages& im, int format, int out_format, int rule, const RectifyBlock* blk_a,
+                      const RectifyBlock* blk_b, const int32_t* tab_a, const int32_t* tab_b);
 // k_nn.hip: room for n more rows of `dim` values in a database, without appending (SF_EINVAL: another dimension)
 int sf_nn_reserve_rows(sf_context* c, NNDb& db, int n, int dim);
 StoreView sf_store_view(const Store& s);

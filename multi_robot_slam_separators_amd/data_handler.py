@@ -29,10 +29,14 @@ class FinderBackend:
     """Adapter: the backend interface DataHandler / StereoCamGeometricTools use, served by a
     lib.SeparatorFinder (the product).  tests/ provide an oracle-backed twin for comparison."""
 
-    def __init__(self, finder, cam=None, detector=None, stereo_flow=None):
-        """cam (sf_stereo_camera), detector / stereo_flow (None: rtabmap's defaults): only get_features needs them."""
+    def __init__(self, finder, cam=None, detector=None, stereo_flow=None, rectify=None):
+        """cam (sf_stereo_camera), detector / stereo_flow (None: rtabmap's defaults): only get_features needs them.
+        rectify: None (the images are rectified already), or (plan_left, plan_right) of the finder's rectification plans:
+        get_features_u8 then takes the RAW pair and rectifies it on the device first (cam is the rectified pair's camera,
+        lib.stereo_camera_from_info)."""
         self.f = finder
         self.cam, self.detector, self.stereo_flow = cam, detector, stereo_flow
+        self.rectify = rectify
         self.slots = []               # store slot of every keyframe get_features produced, in call order
 
     def nn_append_local(self, rows):
@@ -68,6 +72,8 @@ class FinderBackend:
         """get_features on the camera's images ([h, w, 3] uint8 rgb8 / bgr8, [h, w] mono8): gray conversion on the device."""
         if self.cam is None:
             raise ValueError("FinderBackend needs the stereo camera model for get_features_u8")
+        if self.rectify is not None:
+            left, right = self.f.rectify_pair(left, right, format, self.rectify[0], self.rectify[1])
         desc, xyz, kp, slot = self.f.get_features_and_descriptor_u8(left, right, format, self.cam, self.detector,
                                                                     self.stereo_flow)
         self.slots.append(slot)

@@ -212,6 +212,15 @@ def load():
         "sf_add_keyframes_u8_batch_device": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_size_t,
                                                        P(_abi.StereoCamera), P(_abi.DetectorParams),
                                                        P(_abi.StereoFlowParams), P(i32), P(i32), vp, vp, vp, vp]),
+        "sf_rectify_check_info": (C.c_int, [P(_abi.CameraInfo), vp]),
+        "sf_rectify_plan_create": (C.c_int, [vp, P(_abi.CameraInfo), P(i32)]),
+        "sf_rectify_plan_from_maps": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, P(i32)]),
+        "sf_rectify_plan_count": (C.c_int, [vp, P(i32)]),
+        "sf_rectify_plan_get": (C.c_int, [vp, i32, P(_abi.CameraInfo), P(i32)]),
+        "sf_rectify_plan_clear": (C.c_int, [vp]),
+        "sf_rectify_maps_device": (C.c_int, [vp, i32, vp, vp, i32]),
+        "sf_image_rectify_device": (C.c_int, [vp, i32, vp, i32, vp, i32, i32, i32, i32, C.c_size_t, vp, vp, i32, C.c_size_t]),
+        "sf_stereo_camera_from_info": (C.c_int, [P(_abi.CameraInfo), P(_abi.CameraInfo), vp, P(_abi.StereoCamera)]),
         "sf_depth_defaults": (None, [P(_abi.DepthParams)]),
         "sf_depth_set_params": (C.c_int, [vp, P(_abi.DepthParams)]),
         "sf_depth_get_params": (C.c_int, [vp, P(_abi.DepthParams)]),
@@ -308,7 +317,30 @@ EXPORTED = [
     "sf_add_keyframes_depth_batch_device",
     "sf_depth_set_size", "sf_depth_get_size", "sf_depth_interpolation_factor", "sf_depth_interpolate_device",
     "sf_store_export_plan", "sf_store_export_keyframes_device", "sf_store_import_keyframes_device", "sf_store_wire_status",
+    "sf_rectify_check_info", "sf_rectify_plan_create", "sf_rectify_plan_from_maps", "sf_rectify_plan_count",
+    "sf_rectify_plan_get", "sf_rectify_plan_clear", "sf_rectify_maps_device", "sf_image_rectify_device",
+    "sf_stereo_camera_from_info",
 ]
+
+
+def rectify_check_info(info):
+    """sf_rectify_check_info (no GPU, no handle): (status, iR) -- SF_OK and the plan's (P[:, :3] R)^-1 as float64 [3, 3], or
+    SF_EINVAL and None for a block sf_rectify_plan_create refuses."""
+    iR = np.zeros(9, np.float64)
+    rc = load().sf_rectify_check_info(C.byref(info), C.c_void_p(iR.ctypes.data))
+    return rc, (iR.reshape(3, 3) if rc == _abi.SF_OK else None)
+
+
+def stereo_camera_from_info(left, right, local_transform=None):
+    """sf_stereo_camera_from_info (no GPU, no handle): the _abi.StereoCamera of the rectified pair of two _abi.CameraInfo
+    blocks; SepfinderError where the baseline -P_right[3] / P_right[0] is not positive."""
+    cam = _abi.StereoCamera()
+    lt = None if local_transform is None else np.ascontiguousarray(local_transform, np.float32).reshape(12)
+    rc = load().sf_stereo_camera_from_info(C.byref(left), C.byref(right), None if lt is None else C.c_void_p(lt.ctypes.data),
+                                           C.byref(cam))
+    if rc != _abi.SF_OK:
+        raise SepfinderError(rc, (load().sf_last_error(None) or b"").decode())
+    return cam
 
 
 def depth_interpolation_factor(width, height, depth_width, depth_height):
@@ -1172,6 +1204,74 @@ class SeparatorFinder:
 
     def store_clear(self):
         self._check(self._L.sf_store_clear(self._h))
+
+    # -- raw camera images: rectification plans (include/sepfinder.h: sf_camera_info) -----------------
+    def rectify_plan_create(self, info):
+        """sf_rectify_plan_create: validates an _abi.CameraInfo and stores its plan; returns the plan id (1, 2, ..)."""
+        pid = C.c_int32()
+        self._check(self._L.sf_rectify_plan_create(self._h, C.byref(info), C.byref(pid)))
+        return pid.value
+
+    def rectify_plan_from_maps(self, mapx, mapy, src_width, src_height):
+        """sf_rectify_plan_from_maps: a plan from the caller's float32 maps [out_h, out_w] (host arrays) into a source of
+        src_width x src_height; returns the plan id."""
+        mx, my = np.ascontiguousarray(mapx, np.float32), np.ascontiguousarray(mapy, np.float32)
+        if mx.ndim != 2 or mx.shape != my.shape:
+            raise ValueError("mapx / mapy must be two [out_h, out_w] arrays of one shape")
+        pid = C.c_int32()
+        self._check(self._L.sf_rectify_plan_from_maps(self._h, C.c_void_p(mx.ctypes.data), C.c_void_p(my.ctypes.data), mx.shape[1],
+                                                      mx.shape[0], mx.strides[0], int(src_width), int(src_height), C.byref(pid)))
+        return pid.value
+
+    def rectify_plan_count(self):
+        n = C.c_int32()
+        self._check(self._L.sf_rectify_plan_count(self._h, C.byref(n)))
+        return n.value
+
+    def rectify_plan_get(self, plan):
+        """sf_rectify_plan_get: (the _abi.CameraInfo the plan was created from, whether it is a plan of caller maps)."""
+        info, from_maps = _abi.CameraInfo(), C.c_int32()
+        self._check(self._L.sf_rectify_plan_get(self._h, int(plan), C.byref(info), C.byref(from_maps)))
+        return info, bool(from_maps.value)
+
+    def rectify_plan_clear(self):
+        self._check(self._L.sf_rectify_plan_clear(self._h))
+
+    def rectify_maps_device(self, plan, d_mapx, d_mapy, pitch_bytes):
+        """sf_rectify_maps_device: a computed plan's float32 maps into device arrays (raw pointers); asynchronous."""
+        self._check(self._L.sf_rectify_maps_device(self._h, int(plan), C.c_void_p(d_mapx), C.c_void_p(d_mapy), int(pitch_bytes)))
+
+    def image_rectify_device(self, plan_a, d_src_a, plan_b, d_src_b, fmt, out_fmt, n_images, src_pitch, src_stride, d_dst_a,
+                             d_dst_b, dst_pitch, dst_stride):
+        """sf_image_rectify_device: n_images raw device images under plan_a and (d_src_b not None) as many under plan_b in one
+        launch, to images in out_fmt (fmt, or SF_IMAGE_MONO8 from a colour format: the fused gray); asynchronous."""
+        self._check(self._L.sf_image_rectify_device(self._h, int(plan_a), C.c_void_p(d_src_a), int(plan_b), C.c_void_p(d_src_b),
+                                                    int(fmt), int(out_fmt), int(n_images), int(src_pitch), int(src_stride),
+                                                    C.c_void_p(d_dst_a), C.c_void_p(d_dst_b), int(dst_pitch), int(dst_stride)))
+
+    def rectify_pair(self, left, right, fmt, plan_left, plan_right, out_fmt=None):
+        """A raw host pair ([h, w, 3] rgb8 / bgr8 or [h, w] mono8) rectified on the device under two plans: uploads both
+        images, runs sf_image_rectify_device once, returns the two rectified host images in out_fmt (None: fmt)."""
+        out_fmt = fmt if out_fmt is None else out_fmt
+        left, w, h, pitch = _camera_image(left, fmt)
+        right, w2, h2, pitch2 = _camera_image(right, fmt)
+        if (w, h) != (w2, h2):
+            raise ValueError("left / right must be images of one shape")
+        info = self.rectify_plan_get(plan_left)[0]
+        if (info.width, info.height) != (w, h):
+            raise ValueError("plan %d rectifies %d x %d images, not %d x %d" % (plan_left, info.width, info.height, w, h))
+        ow, oh = info.out_width or info.width, info.out_height or info.height
+        import torch
+        d_l, d_r = upload(np.ascontiguousarray(left), self.device), upload(np.ascontiguousarray(right), self.device)
+        shape = (oh, ow) if out_fmt == _abi.SF_IMAGE_MONO8 else (oh, ow, 3)
+        d_out = torch.zeros((2,) + shape, dtype=torch.uint8, device=d_l.device)
+        torch.cuda.current_stream(d_l.device).synchronize()        # (the handle's stream may be another one)
+        row = ow * (1 if out_fmt == _abi.SF_IMAGE_MONO8 else 3)
+        self.image_rectify_device(plan_left, d_l.data_ptr(), plan_right, d_r.data_ptr(), fmt, out_fmt, 1,
+                                  w * (1 if fmt == _abi.SF_IMAGE_MONO8 else 3), 0, d_out[0].data_ptr(), d_out[1].data_ptr(), row, 0)
+        self.synchronize()
+        out = d_out.cpu().numpy()
+        return out[0], out[1]
 
     # -- a camera model per keyframe (include/sepfinder.h: sf_camera_model) ---------------------------
     def camera_add(self, model):
