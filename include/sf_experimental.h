@@ -88,6 +88,11 @@ int  sf_debug_guided_points(sf_handle h, int32_t pair, unsigned long long* plane
    one-wavefront launches of SF_OPT_CHAIN_NARROW_EST.                                                             */
 int  sf_debug_plan_workspace(const sf_params* p, int32_t kcap, int32_t desc_words, int32_t n_pairs,
                              int32_t in_overlapped_step, int32_t debug_corr, int64_t* out, int32_t n_out);
+/* What the library's handles hold at this moment, over the whole process: out[0] device blocks, [1] their bytes, [2]
+   pinned host blocks, [3] events (the profiling brackets' recycled timing events apart).  Counted where the handle's owning
+   types allocate and free, not read from the driver: a test on any machine can hold "sf_destroy returns everything" to
+   it, also on a card that other work shares.  No handle, no GPU needed.                                           */
+void sf_debug_live_resources(int64_t out[4]);
 
 /* The two Gaussian tables of SURF (Vis/FeatureType 0), handle-free and usable without a GPU; float64 arithmetic, every
    weight rounded to float32 once.  ori_xy [109][2] int8 {x, y}: the lattice points with x^2 + y^2 < 36, x outer, y

@@ -541,6 +541,8 @@ class StepResult(C.Structure):
 
 
 SF_ABI_VERSION = 8      # include/sepfinder.h
+# the four counts of sf_debug_live_resources (include/sf_experimental.h), in its order
+LIVE_RESOURCES = ("device_blocks", "device_bytes", "pinned_blocks", "events")
 
 # store slots as one block of bytes (sf_store_export_* / sf_store_import_keyframes_device): [header][entry x n][blocks]
 SF_KFBLOB_MAGIC = 0x424B4653      # "SFKB"

@@ -650,12 +650,7 @@ struct sf_netvlad_model {
 };
 
 void sf_netvlad_free(sf_context* c) {
-  if (!c->netvlad) return;
-  sf_netvlad_model* m = c->netvlad;
-  for (int i = 0; i < 13; ++i) { sf_buf_free(m->conv_w[i]); sf_buf_free(m->conv_b[i]); sf_buf_free(m->conv_wh[i]); sf_buf_free(m->conv_wl[i]); }
-  Buf* bs[] = {&m->mean, &m->assign_w, &m->centers, &m->pca_w, &m->pca_b, &m->act[0], &m->act[1], &m->vlad, &m->pca_y, &m->partial};
-  for (Buf* b : bs) sf_buf_free(*b);
-  delete m;
+  delete c->netvlad;          // (its buffers are members: they go with it)
   c->netvlad = nullptr;
 }
 

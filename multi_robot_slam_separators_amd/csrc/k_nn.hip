@@ -1052,9 +1052,8 @@ static int nn_reserve(sf_context* c, NNDb& db, int n_total, int ld) {
     // zero-padded for the old pitch.  Only an EMPTY database can change its pitch.
     if (db.n != 0) return sf_fail(c, SF_EINVAL, "NetVLAD row pitch changed on a non-empty database");
     SF_HIP(c, hipStreamSynchronize(c->stream));
-    if (db.rows.p) (void)hipFree(db.rows.p);
-    if (db.norms.p) (void)hipFree(db.norms.p);
-    db.rows = Buf(); db.norms = Buf();
+    sf_buf_free(db.rows);
+    sf_buf_free(db.norms);
     db.cap = 0;
     db.ld = ld;
     db.h_n = -1;
@@ -1093,16 +1092,9 @@ static int nn_stage_reserve(sf_context* c, size_t bytes) {
     SF_HIP(c, hipEventSynchronize(c->nn_stage_done));
     c->nn_stage_busy = false;
   }
-  if (!c->nn_stage_done) SF_HIP(c, hipEventCreateWithFlags(&c->nn_stage_done, hipEventDisableTiming));
-  if (bytes > c->nn_stage_pinned_bytes) {
-    if (c->nn_stage_pinned) (void)hipHostFree(c->nn_stage_pinned);
-    c->nn_stage_pinned = nullptr;
-    c->nn_stage_pinned_bytes = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, (size_t)1 << 16);
-    if (hipHostMalloc(&c->nn_stage_pinned, want, hipHostMallocDefault) != hipSuccess)
-      return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) failed", want);
-    c->nn_stage_pinned_bytes = want;
-  }
+  int rc;
+  if ((rc = sf_event_ensure(c, c->nn_stage_done)) != SF_OK) return rc;
+  if ((rc = sf_pinned_reserve(c, c->nn_stage_pinned, bytes, std::max<size_t>(bytes + bytes / 2, (size_t)1 << 16))) != SF_OK) return rc;
   return sf_buf_reserve(c, c->nn_stage_dev, std::max<size_t>(bytes, (size_t)1 << 16));
 }
 
@@ -1125,8 +1117,8 @@ int sf_nn_append(sf_context* c, NNDb& db, const void* src, int n, int dim, int s
   if (src_kind == 0) {
     const size_t bytes = (size_t)n * dim * 8;
     if ((rc = nn_stage_reserve(c, bytes)) != SF_OK) return rc;
-    memcpy(c->nn_stage_pinned, src, bytes);
-    SF_HIP(c, hipMemcpyAsync(c->nn_stage_dev.p, c->nn_stage_pinned, bytes, hipMemcpyHostToDevice, c->stream));
+    memcpy(c->nn_stage_pinned.p, src, bytes);
+    SF_HIP(c, hipMemcpyAsync(c->nn_stage_dev.p, c->nn_stage_pinned.p, bytes, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_nn_ingest_rows<double>, grid, dim3(256), 0, c->stream, (const double*)c->nn_stage_dev.p, dst, nrm, n,
                        dim, ld);
     SF_HIP(c, hipGetLastError());
@@ -1196,18 +1188,6 @@ struct NnTrace {
     t = now;
   }
 };
-
-static int nn_pinned_reserve(sf_context* c, size_t need) {
-  if (need <= c->nn_pinned_bytes) return SF_OK;
-  if (c->nn_pinned) (void)hipHostFree(c->nn_pinned);
-  c->nn_pinned = nullptr;
-  c->nn_pinned_bytes = 0;
-  const size_t want = need + need / 2;
-  if (hipHostMalloc(&c->nn_pinned, want, hipHostMallocDefault) != hipSuccess)
-    return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) failed", want);
-  c->nn_pinned_bytes = want;
-  return SF_OK;
-}
 
 // Stage 1 contracts only a PREFIX of the descriptor: the squared distance over the first k
 // dimensions is a lower bound of the full squared distance, so "prefix distance (within the fp16
@@ -1336,10 +1316,11 @@ struct NnHostCand {
   uint2* cand = nullptr;
   double* dist = nullptr;
   int reserve(sf_context* c, unsigned entries) {
-    const int rc = nn_pinned_reserve(c, (size_t)entries * 16 + 64);
+    const size_t need = (size_t)entries * 16 + 64;
+    const int rc = sf_pinned_reserve(c, c->nn_pinned, need, need + need / 2);
     if (rc != SF_OK) return rc;
-    cand = (uint2*)((char*)c->nn_pinned + 64);
-    dist = (double*)((char*)c->nn_pinned + 64 + (size_t)entries * 8);
+    cand = (uint2*)((char*)c->nn_pinned.p + 64);
+    dist = (double*)((char*)c->nn_pinned.p + 64 + (size_t)entries * 8);
     return SF_OK;
   }
 };
@@ -1378,7 +1359,7 @@ static int nn_refine_prefix(sf_context* c, const NnShape& sh, const NnFilterBufs
                        fb.cand, fb.count, spec, A, B, sh.dim, sh.ld, fb.cdist, 0u);
     sf_prof_end(c, SF_K_NN_REFINE);
   }
-  SF_HIP(c, hipMemcpyAsync(c->nn_pinned, fb.count, 4, hipMemcpyDeviceToHost, cs));
+  SF_HIP(c, hipMemcpyAsync(c->nn_pinned.p, fb.count, 4, hipMemcpyDeviceToHost, cs));
   SF_HIP(c, hipMemcpyAsync(hc.cand, fb.cand, (size_t)spec * 8, hipMemcpyDeviceToHost, cs));
   SF_HIP(c, hipMemcpyAsync(hc.dist, fb.cdist, (size_t)spec * 8, hipMemcpyDeviceToHost, cs));
   if (speculate) {
@@ -1387,7 +1368,7 @@ static int nn_refine_prefix(sf_context* c, const NnShape& sh, const NnFilterBufs
   } else {
     SF_HIP(c, hipStreamSynchronize(c->stream));
   }
-  hc.n = *(const unsigned*)c->nn_pinned;
+  hc.n = *(const unsigned*)c->nn_pinned.p;
   tr.mark("filter + refine + D2H", hc.n);
   *ok = hc.n <= limit;
   if (speculate) c->spec.valid = *ok && hc.n <= c->spec.grid;

@@ -4,6 +4,8 @@
 #include <math.h>
 #include <stdarg.h>
 
+#include <atomic>
+
 #include "sf_host.hpp"
 
 static thread_local std::string g_create_error;
@@ -18,31 +20,66 @@ int sf_fail(sf_context* c, int code, const char* fmt, ...) {
   return code;
 }
 
+// ---- the owning types' allocate and free paths (sf_internal.hpp), and the counts of what is live -----------------------------
+static std::atomic<int64_t> g_live[4];   // device blocks, device bytes, pinned blocks, events (sf_debug_live_resources)
+static void live_add(int what, int64_t n) { g_live[what].fetch_add(n, std::memory_order_relaxed); }
+
+extern "C" void sf_debug_live_resources(int64_t out[4]) {
+  for (int i = 0; i < 4; ++i) out[i] = g_live[i].load(std::memory_order_relaxed);
+}
+
 int sf_buf_reserve(sf_context* c, Buf& b, size_t bytes, bool keep) {
   if (bytes <= b.bytes) return SF_OK;
   size_t want = std::max(bytes, b.bytes + b.bytes / 2);
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, want);
+  Buf n;
+  hipError_t e = hipMalloc(&n.p, want);
   if (e != hipSuccess) return sf_fail(c, SF_ENOMEM, "hipMalloc(%zu) -> %s", want, hipGetErrorString(e));
+  n.bytes = want;
+  live_add(0, 1); live_add(1, (int64_t)want);
   if (b.p) {
     if (keep && b.bytes) {
-      e = hipMemcpyAsync(p, b.p, b.bytes, hipMemcpyDeviceToDevice, c->stream);
+      e = hipMemcpyAsync(n.p, b.p, b.bytes, hipMemcpyDeviceToDevice, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { (void)hipFree(p); return sf_fail(c, SF_EHIP, "grow copy -> %s", hipGetErrorString(e)); }
+      if (e != hipSuccess) return sf_fail(c, SF_EHIP, "grow copy -> %s", hipGetErrorString(e));
     } else {
       (void)hipStreamSynchronize(c->stream);
     }
-    (void)hipFree(b.p);
   }
-  b.p = p;
-  b.bytes = want;
+  b = std::move(n);
   return SF_OK;
 }
 
 void sf_buf_free(Buf& b) {
-  if (b.p) (void)hipFree(b.p);
+  if (b.p) { (void)hipFree(b.p); live_add(0, -1); live_add(1, -(int64_t)b.bytes); }
   b.p = nullptr;
   b.bytes = 0;
+}
+
+int sf_pinned_reserve(sf_context* c, Pinned& b, size_t need, size_t alloc) {
+  if (need <= b.bytes) return SF_OK;
+  sf_pinned_free(b);
+  if (hipHostMalloc(&b.p, alloc, hipHostMallocDefault) != hipSuccess) { b.p = nullptr; return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) failed", alloc); }
+  b.bytes = alloc;
+  live_add(2, 1);
+  return SF_OK;
+}
+
+void sf_pinned_free(Pinned& b) {
+  if (b.p) { (void)hipHostFree(b.p); live_add(2, -1); }
+  b.p = nullptr;
+  b.bytes = 0;
+}
+
+int sf_event_ensure(sf_context* c, Event& ev) {
+  if (ev.e) return SF_OK;
+  SF_HIP(c, hipEventCreateWithFlags(&ev.e, hipEventDisableTiming));
+  live_add(3, 1);
+  return SF_OK;
+}
+
+void sf_event_free(Event& ev) {
+  if (ev.e) { (void)hipEventDestroy(ev.e); live_add(3, -1); }
+  ev.e = nullptr;
 }
 
 // ---- profiling ------------------------------------------------------------------------------
@@ -291,35 +328,24 @@ extern "C" int sf_create(const sf_params* p, int device, sf_handle* out) {
   return SF_OK;
 }
 
+// Orders, does not enumerate: every buffer, pinned block and event is a member of an owning type and goes with `delete c`.
+// Nothing may be freed before the streams have drained, and the device is selected before the destructors run.
 extern "C" void sf_destroy(sf_handle c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  (void)sf_comm_destroy(c);
   for (Workspace& w : c->ws) {
     if (w.stream) (void)hipStreamSynchronize(w.stream);
     if (w.aux) (void)hipStreamSynchronize(w.aux);
   }
+  if (c->spec.copy_stream) (void)hipStreamSynchronize(c->spec.copy_stream);
   prof_resolve(c);
   for (hipEvent_t e : c->prof_event_pool) (void)hipEventDestroy(e);
-  Buf* bufs[] = {&c->store.desc, &c->store.xyz, &c->store.kp, &c->store.meta, &c->scratch.desc, &c->scratch.xyz,
-                 &c->scratch.kp, &c->scratch.meta, &c->nn_local.rows, &c->nn_local.norms, &c->nn_local.rows_h, &c->nn_local.norms_k, &c->nn_recv.norms_k, &c->nn_recv.rows,
-                 &c->nn_recv.norms, &c->nn_recv.rows_h, &c->d_mask_local, &c->d_mask_other, &c->d_ign_ptr,
-                 &c->d_ign_col, &c->nn_rowmin, &c->nn_exact, &c->nn_scalar, &c->comm_scratch, &c->trace, &c->stage_desc, &c->stage_xyz, &c->stage_kp,
-                 &c->ex_integral, &c->ex_desc, &c->ex_xyz, &c->ex_keep, &c->ex_rows, &c->brief_tests, &c->orb_tests,
-                 &c->ex_blur, &c->ex_kpts, &c->orb_pyr, &c->orb_work, &c->freak_pattern, &c->freak_tables, &c->surf_planes, &c->surf_keys, &c->surf_tables, &c->surf_ctl, &c->sift_planes, &c->sift_keys, &c->sift_tables, &c->sift_ctl,
-                 &c->gf_planes, &c->gf_keys, &c->gf_tmp, &c->gf_lists, &c->gf_scalar, &c->lk_pyr, &c->ft_images, &c->ft_kpts, &c->ft_flow, &c->ft_wire,
-                 &c->ft_counts, &c->ft_cells, &c->img_src, &c->img_gray, &c->img_desc, &c->wire_plan, &c->wire_status,
-                 &c->cam_table, &c->cam_tags_dev};
-  for (Buf* b : bufs) sf_buf_free(*b);
-  for (RectifyPlan& p : c->rect_plans) sf_buf_free(p.table);
-  sf_buf_free(c->rect_blocks);
+  (void)sf_comm_destroy(c);
+  sf_netvlad_free(c);
+  sf_ingest_pool_destroy(c);
+  // the streams stay explicit: whose they are depends on own_stream, the lane and the placement's hand-out
   for (int k = 0; k <= SF_STEP_MAX_LANES; ++k) {
     Workspace& w = c->ws[k];
-    w.for_each_buf(sf_buf_free);
-    for (hipEvent_t e : {w.ev_main, w.ev_filter, w.ev_walk})
-      if (e) (void)hipEventDestroy(e);
     if (w.aux) (void)hipStreamDestroy(w.aux);
     if (w.stream && (k > 0 || c->own_stream)) (void)hipStreamDestroy(w.stream);
   }
@@ -328,29 +354,7 @@ extern "C" void sf_destroy(sf_handle c) {
     if (c->placement.aux[k]) (void)hipStreamDestroy(c->placement.aux[k]);
   }
   if (c->placement.copy) (void)hipStreamDestroy(c->placement.copy);
-  if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
-  sf_netvlad_free(c);
-  sf_ingest_pool_destroy(c);
-  if (c->ingest_pinned) (void)hipHostFree(c->ingest_pinned);
-  if (c->nn_stage_pinned) (void)hipHostFree(c->nn_stage_pinned);
-  if (c->nn_stage_done) (void)hipEventDestroy(c->nn_stage_done);
-  sf_buf_free(c->nn_stage_dev);
-  if (c->nn_pinned) (void)hipHostFree(c->nn_pinned);
-  if (c->pairs_pinned) (void)hipHostFree(c->pairs_pinned);
-  if (c->count_pinned) (void)hipHostFree(c->count_pinned);
-  if (c->pairs_staged) (void)hipEventDestroy(c->pairs_staged);
-  if (c->spec_index_pinned) (void)hipHostFree(c->spec_index_pinned);
-  if (c->spec_index_staged) (void)hipEventDestroy(c->spec_index_staged);
-  if (c->spec.ev_refined) (void)hipEventDestroy(c->spec.ev_refined);
-  if (c->spec.ev_copied) (void)hipEventDestroy(c->spec.ev_copied);
-  if (c->spec.copy_stream) { (void)hipStreamSynchronize(c->spec.copy_stream); (void)hipStreamDestroy(c->spec.copy_stream); }
-  for (auto& sb : c->step_blocks) {
-    if (sb.pinned) (void)hipHostFree(sb.pinned);
-    if (sb.done) (void)hipEventDestroy(sb.done);
-    if (sb.copied) (void)hipEventDestroy(sb.copied);
-    sf_buf_free(sb.dev);
-    sf_buf_free(sb.dev_records);
-  }
+  if (c->spec.copy_stream) (void)hipStreamDestroy(c->spec.copy_stream);
   delete c;
 }
 

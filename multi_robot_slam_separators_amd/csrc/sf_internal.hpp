@@ -170,10 +170,65 @@ struct PairSource {
   int n_l = 0, n_r = 0, slot_other = 0, slot_local = 0, n_slots = 0;
 };
 
-struct Buf {
+// ---- owning types: a device block, a pinned host block, an event ------------------------------------------------------------
+// Whoever holds one as a member owns the resource: move-only, freed by the destructor when non-null, no HIP call when null
+// (a device-free context constructs and destructs without one).  Nothing lists them: sf_destroy drains the streams and
+// selects the device, `delete c` frees.  Their allocate and free paths (sf_handle.hip) keep the process-wide counts of
+// sf_debug_live_resources.
+struct sf_context;
+struct Buf;
+struct Pinned;
+struct Event;
+int sf_buf_reserve(sf_context* c, Buf& b, size_t bytes, bool keep = false);   // grow-only: max(bytes, 1.5 x the old size)
+void sf_buf_free(Buf& b);
+// grow-only: a block smaller than `need` is replaced by one of `alloc` >= need bytes (the site's growth rule), contents lost
+int sf_pinned_reserve(sf_context* c, Pinned& b, size_t need, size_t alloc);
+void sf_pinned_free(Pinned& b);
+int sf_event_ensure(sf_context* c, Event& ev);     // created on first use, timing disabled
+void sf_event_free(Event& ev);
+
+struct Buf {              // hipMalloc
   void* p = nullptr;
   size_t bytes = 0;
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) { sf_buf_free(*this); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+    return *this;
+  }
+  Buf(const Buf&) = delete;
+  Buf& operator=(const Buf&) = delete;
+  ~Buf() { sf_buf_free(*this); }
 };
+struct Pinned {           // hipHostMalloc
+  void* p = nullptr;
+  size_t bytes = 0;
+  Pinned() = default;
+  Pinned(Pinned&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+  Pinned& operator=(Pinned&& o) noexcept {
+    if (this != &o) { sf_pinned_free(*this); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; }
+    return *this;
+  }
+  Pinned(const Pinned&) = delete;
+  Pinned& operator=(const Pinned&) = delete;
+  ~Pinned() { sf_pinned_free(*this); }
+};
+struct Event {            // hipEventDisableTiming; reads as the hipEvent_t it holds (nullptr: not created yet)
+  hipEvent_t e = nullptr;
+  operator hipEvent_t() const { return e; }
+  Event() = default;
+  Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    if (this != &o) { sf_event_free(*this); e = o.e; o.e = nullptr; }
+    return *this;
+  }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() { sf_event_free(*this); }
+};
+static_assert(!std::is_copy_constructible<Buf>::value && !std::is_copy_assignable<Buf>::value, "Buf is move-only");
+static_assert(!std::is_copy_constructible<Pinned>::value && !std::is_copy_assignable<Pinned>::value, "Pinned is move-only");
+static_assert(!std::is_copy_constructible<Event>::value && !std::is_copy_assignable<Event>::value, "Event is move-only");
 
 // ---- rectification plans (sf_rectify_plan_create; include/sepfinder.h) ------------------------------------------------------
 // What a computed plan's kernels read with uniform loads: iR = (P[:, :3] R)^-1, K's fx fy cx cy and the eight distortion
@@ -221,8 +276,8 @@ struct ProfSlot {
 struct Workspace {
   hipStream_t stream = nullptr;
   hipStream_t aux = nullptr;             // speculative device step: exact re-evaluation + minima + walk beside the verification
-  hipEvent_t ev_filter = nullptr, ev_walk = nullptr;
-  hipEvent_t ev_main = nullptr;          // "the handle's stream up to here": awaited when the databases changed
+  Event ev_filter, ev_walk;
+  Event ev_main;                         // "the handle's stream up to here": awaited when the databases changed
 
   // verification (sized for `ws_pairs` pairs)
   int ws_pairs = 0, ws_kcap = 0;
@@ -263,14 +318,6 @@ struct Workspace {
 
   uint64_t seen_db_epoch = ~0ull;   // sf_context::db_epoch this lane last waited for
   uint64_t seen_prep = 0;           // sf_context::prep_epoch this lane last waited for
-
-  // every buffer above (sf_destroy frees them from this list)
-  template <class F> void for_each_buf(F&& f) {
-    for (Buf* b : {&pair_from, &pair_to, &corr1, &corr2, &hdr1, &hdr2, &pass1, &pass2, &pass_back, &dir_mask, &list1, &list3,
-                   &counters, &results, &flags, &nn_cand, &spec_from, &spec_to, &spec_results, &spec_index, &compact_scratch,
-                   &step_nn, &walk_scratch})
-      f(*b);
-  }
 };
 
 // FREAK rows (types 3 and 5): the tables of k_freak_points -- the integral image is BRIEF's, the rows are 64 bytes
@@ -356,6 +403,7 @@ struct sf_context {
   int device = 0;
   hipStream_t stream = nullptr;   // the stream the launchers queue on: ws[0].stream, or another inside a UseWorkspace scope
   bool own_stream = false;
+  int cu_count = 0;         // compute units of the device (grids sized to the chip); read through sf_cu_count (k_nn.hip), which fills it on first use
   // [0]: the handle's own; [1 .. SF_STEP_MAX_LANES - 1]: step lanes (SF_OPT_STEP_OVERLAP); [SF_STEP_MAX_LANES]: the second
   // half of a two-stream batch (sf_verify_device)
   Workspace ws[SF_STEP_MAX_LANES + 1];
@@ -384,16 +432,8 @@ struct sf_context {
   Buf wire_plan, wire_status;
   // host-buffer batch ingest (store_add_host_batch): pinned staging, table scratch and the packing workers all
   // belong to the handle and end with it (sf_destroy)
-  void* ingest_pinned = nullptr;
-  size_t ingest_pinned_bytes = 0;
+  Pinned ingest_pinned;
   struct IngestPool* ingest_pool = nullptr;
-  // per-tick NetVLAD append from host float64 rows (sf_nn_append): grow-only pinned + device staging, re-used once
-  // the previous append's copy has left it (nn_stage_done), so the path neither allocates nor synchronises
-  void* nn_stage_pinned = nullptr;
-  size_t nn_stage_pinned_bytes = 0;
-  Buf nn_stage_dev;
-  hipEvent_t nn_stage_done = nullptr;
-  bool nn_stage_busy = false;
 
   Buf ft_counts;                // batched feature extraction: corners per image (device)
   // feature extraction (k_extract.hip): integral image, per-corner scratch, the BRIEF test table
@@ -424,6 +464,11 @@ struct sf_context {
   bool orb_loaded = false;
   int8_t orb_host[32 * 8 * 4] = {};
   Buf orb_tests, ex_blur, ex_kpts;
+  // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
+  // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
+  // the image at hand; orb_work: the detector's candidate lists
+  sf_orb_detector_params orb_det = {2.0f, 3, 0, 0, 20};
+  Buf orb_pyr, orb_work;
   // 4 = FAST/BRIEF: the detector is k_fast.hip's with these parameters (sf_fast_set_params), the rest is type 6's
   sf_fast_params fast = {20, 1};
   // 5, 6, 8 and sf_detect_corners_device: the GFTT response of k_gftt.hip -- block size, Harris or minimum eigenvalue, k
@@ -475,10 +520,6 @@ struct sf_context {
   Buf sift_ctl;
   SfSiftBatchPlan sift_batch;
   int sift_debug_chunk = 0;
-  // 2 = ORB: the detector is k_orb_detect.hip's (FAST per pyramid level, Harris or FAST score, per-level quotas) with these
-  // parameters and `orb`; the descriptors are type 8's on the keypoint's own level.  orb_pyr: pyramid levels >= 1 of
-  // the image at hand; orb_work: the detector's candidate lists
-  sf_orb_detector_params orb_det = {2.0f, 3, 0, 0, 20};
   // every type: what Feature2D::generateKeypoints puts around the detector (sf_front_set_params; k_subpix.hip) -- the ROI
   // the detector sees and cv::cornerSubPix on the kept corners; both off on a fresh handle
   sf_front_params front = {{0.f, 0.f, 0.f, 0.f}, 3, 0, 0.02f};
@@ -495,7 +536,6 @@ struct sf_context {
   // ROI; 1 x 1 = no cells.  ft_cells: every cell's count, then every cell's keypoints, before k_grid_gather joins them
   sf_grid_params grid = {1, 1};
   Buf ft_cells;
-  Buf orb_pyr, orb_work;
   Buf trace;                    // SF_CHAIN_TRACE builds: uint64[n][32] phase timestamps of the fused kernel
 
   // NN stage
@@ -516,16 +556,23 @@ struct sf_context {
   const void* nn_coef_ptr = nullptr;
   std::vector<double> last_row_min;
   std::vector<int32_t> last_row_arg;
+  std::vector<int32_t> last_row_cand;   // candidate-list index of each row's minimum (filter path)
   std::vector<uint64_t> nn_sort_keys, nn_sort_keys2;   // host scratch of the walk (kept to avoid reallocation)
   std::vector<int32_t> nn_sort_rows, nn_sort_rows2;
   std::vector<uint32_t> nn_sort_hist;
   std::vector<uint8_t> nn_taken;
+  // per-tick NetVLAD append from host float64 rows (sf_nn_append): grow-only pinned + device staging, re-used once
+  // the previous append's copy has left it (nn_stage_done), so the path neither allocates nor synchronises
+  Pinned nn_stage_pinned;
+  Buf nn_stage_dev;
+  Event nn_stage_done;
+  bool nn_stage_busy = false;
+  Pinned nn_pinned;            // pinned host staging of the NN filter's small D2H copies
 
   int match_variant = 0;   // 0 = default geometry; see sf_launch_match_global
   std::vector<const void*> dyn_lds_kernels;   // kernels whose dynamic LDS limit this handle has raised (sf_dyn_lds)
   bool debug_corr = false;      // SF_OPT_DEBUG_CORR: the fused kernel also writes lists / headers / states to HBM
   bool fused = true;        // fused per-pair verification kernel (SF_FUSED=0 selects the stage kernels)
-  int cu_count = 0;         // compute units of the device (grids sized to the chip); read through sf_cu_count (k_nn.hip), which fills it on first use
   bool split = false;       // SF_FUSED=2: one matching launch + one chain launch over the survivors (k_verify.hip)
   bool split_auto = true;   // SF_OPT_STEP_SPLIT: the split form inside overlapped steps (sf_use_split, sf_verify_host.hip); on again since
                             // round 5 (its matcher is software-pipelined: 23.0 against 22.7 M pairs/s, profiles/r05u_*)
@@ -543,14 +590,11 @@ struct sf_context {
   bool chain_pnp = true;           // PnP estimator: k_match_split + k_chain_pnp instead of the five stage launches
                                    // (SF_CHAIN_PNP=0: the stage launches)
   bool match_mfma = true;   // Hamming table on the fp4 matrix cores (SF_MATCH_MFMA=0 selects the VALU matcher)
-  void* nn_pinned = nullptr;   // pinned host staging of the NN filter's small D2H copies
-  size_t nn_pinned_bytes = 0;
 
   // sf_verify_matches_device / sf_compact_accepted_device staging
-  void* pairs_pinned = nullptr;
-  size_t pairs_pinned_bytes = 0;
-  hipEvent_t pairs_staged = nullptr;
-  int32_t* count_pinned = nullptr;
+  Pinned pairs_pinned;
+  Event pairs_staged;
+  Pinned count_pinned;          // 64 bytes: the count of sf_compact_accepted_device
 
   // multi-GPU exchange (sf_comm.hip)
   void* comm = nullptr;    // ncclComm_t
@@ -562,7 +606,7 @@ struct sf_context {
   // its stage kernels on ws[SF_STEP_MAX_LANES] -- a stream, workspace and counters of its own -- so that the
   // latency-bound motion-estimation kernels of one half overlap the issue-bound matching kernel of the other.
   // Off unless SF_OVERLAP=1 (+3-6 %).
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  Event ev_fork, ev_join;
   bool overlap = false;
   int overlap_min_pairs = 4096;
   int ws_split = 0;             // pairs [0, ws_split) of the last batch live in ws[0], the rest in ws[SF_STEP_MAX_LANES]
@@ -582,8 +626,10 @@ struct sf_context {
     int32_t slot_other = 0, slot_local = 0;
     unsigned grid = 0;          // speculative pair slots (candidates beyond it invalidate the speculation)
     hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_refined = nullptr, ev_copied = nullptr;
+    Event ev_refined, ev_copied;
   } spec;
+  Pinned spec_index_pinned;     // the matches' candidate slots (sf_find_matches_and_verify_device), read by the gather ...
+  Event spec_index_staged;      // ... recorded behind it: the block may be rewritten after this
   // accepted-result streams (sf_accept_stream_set / _select): two registered blocks, the one selected for the next
   // speculative query is handed to the fused kernel; `streamed` says whether the last query used it
   struct AcceptHost { AcceptStream s = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}; bool set = false; } accept_blocks[3];   // [2]: the step pair's own
@@ -595,8 +641,7 @@ struct sf_context {
   // of `step_depth + 1` blocks: up to `step_depth` steps in flight, and the block of the step retired last stays
   // untouched until the next retire.
   struct StepBlock {
-    void* pinned = nullptr;            // ONE host-pinned allocation: records | index | flags | count | matches | walk words
-    size_t pinned_bytes = 0;
+    Pinned pinned;                     // ONE host-pinned allocation: records | index | flags | count | matches | walk words
     sf_result* records = nullptr;      // [cap] accepted results (streamed: completion order; compacted: match order)
     int32_t* index = nullptr;          // [cap] streamed: verified slot of each record, -1 = unused entry
     uint8_t* flags = nullptr;          // [cap] compacted: success of every match
@@ -617,10 +662,10 @@ struct sf_context {
     bool settled = false;              // its `done` event has been waited for (and a fallback, if needed, has run)
     int32_t slot_other = 0, slot_local = 0, parity = 0;   // (what a fallback needs to run the query again)
     int settle_rc = 0;
-    hipEvent_t done = nullptr;
+    Event done;
     // a caller's copy out of dev_records (sf_memcpy_device_async, on ANY stream) is recorded here; the step that next
     // uses the block waits for it before its kernels may write the buffer again
-    hipEvent_t copied = nullptr;
+    Event copied;
     bool copy_pending = false;
   } step_blocks[SF_STEP_MAX_DEPTH + 1];
   int step_depth = 6;                      // SF_OPT_STEP_DEPTH: steps in flight
@@ -645,7 +690,7 @@ struct sf_context {
   // whichever lane first needs it; it bumps prep_count, the issuing step records ev_prep behind it and the other lanes
   // wait for that event once (Workspace::seen_prep).
   uint64_t prep_count = 0, prep_epoch = 0;
-  hipEvent_t ev_prep = nullptr;
+  Event ev_prep;
   // SF_OPT_STEP_OVERLAP: the steps in flight run on `step_lanes` streams -- lane k on ws[k], with its own stream and its
   // own copy of every device buffer a step writes -- so that the tail of one step's verification (its last
   // motion-estimation chains on an emptying chip) and the NN stage of the next overlap.
@@ -655,10 +700,6 @@ struct sf_context {
   uint32_t* step_mirror_counter[2] = {nullptr, nullptr};    // accepted record and the caller's slot counter, per step parity
   int32_t step_mirror_cap = 0;
   bool step_mirror_lanes = false;             // sf_step_mirror_streams: the odd steps of a mirror pair run on lane 1
-  void* spec_index_pinned = nullptr;
-  size_t spec_index_pinned_bytes = 0;
-  hipEvent_t spec_index_staged = nullptr;
-  std::vector<int32_t> last_row_cand;   // candidate-list index of each row's minimum (filter path)
 
   // profiling
   bool prof = false;
@@ -685,8 +726,6 @@ struct UseWorkspace {
 int sf_fail(sf_context* c, int code, const char* fmt, ...);
 // a database is about to change (SF_OPT_STEP_OVERLAP): `drain` also waits for the step in flight on the second stream
 int sf_lanes_touch(sf_context* c, bool drain);
-int sf_buf_reserve(sf_context* c, Buf& b, size_t bytes, bool keep = false);
-void sf_buf_free(Buf& b);
 struct sf_netvlad_model;
 void sf_netvlad_free(sf_context* c);
 int sf_netvlad_load_impl(sf_context* c, const sf_netvlad_weights* w);

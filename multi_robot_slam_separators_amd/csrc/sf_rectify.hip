@@ -99,7 +99,7 @@ extern "C" int sf_rectify_plan_create(sf_handle c, const sf_camera_info* info, i
   p.src_w = info->width; p.src_h = info->height;
   p.out_w = info->out_width ? info->out_width : info->width;
   p.out_h = info->out_height ? info->out_height : info->height;
-  c->rect_plans.push_back(p);
+  c->rect_plans.push_back(std::move(p));
   *plan_out = id;
   return SF_OK;
 }
@@ -137,12 +137,9 @@ extern "C" int sf_rectify_plan_from_maps(sf_handle c, const float* mapx, const f
   if ((rc = sf_buf_reserve(c, p.table, table.size() * sizeof(int32_t))) != SF_OK) return rc;
   hipError_t e = hipMemcpyAsync(p.table.p, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    sf_buf_free(p.table);
-    return sf_fail(c, SF_EHIP, "sf_rectify_plan_from_maps: upload -> %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return sf_fail(c, SF_EHIP, "sf_rectify_plan_from_maps: upload -> %s", hipGetErrorString(e));
   p.table_ready = true;
-  c->rect_plans.push_back(p);
+  c->rect_plans.push_back(std::move(p));
   *plan_out = (int32_t)c->rect_plans.size();
   return SF_OK;
 }
@@ -168,8 +165,7 @@ extern "C" int sf_rectify_plan_clear(sf_handle c) {
   if (c->rect_plans.empty()) return SF_OK;
   SF_HIP(c, hipSetDevice(c->device));
   SF_HIP(c, hipStreamSynchronize(c->stream));            // the launches queued on the plans' tables
-  for (RectifyPlan& p : c->rect_plans) sf_buf_free(p.table);
-  c->rect_plans.clear();
+  c->rect_plans.clear();                                 // (each plan's table goes with it)
   return SF_OK;
 }
 

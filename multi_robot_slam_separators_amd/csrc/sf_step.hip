@@ -127,9 +127,8 @@ extern "C" int sf_find_matches_and_verify_device(sf_handle c, int32_t slot_base_
   if (speculate) {
     if (!c->spec.copy_stream) {
       if ((rc = sf_side_stream(c, SF_STREAM_COPY, 0, &c->spec.copy_stream)) != SF_OK) return rc;
-      SF_HIP(c, hipEventCreateWithFlags(&c->spec.ev_refined, hipEventDisableTiming));
-      SF_HIP(c, hipEventCreateWithFlags(&c->spec.ev_copied, hipEventDisableTiming));
-      SF_HIP(c, hipEventCreateWithFlags(&c->spec_index_staged, hipEventDisableTiming));
+      for (Event* ev : {&c->spec.ev_refined, &c->spec.ev_copied, &c->spec_index_staged})
+        if ((rc = sf_event_ensure(c, *ev)) != SF_OK) return rc;
     }
     if ((rc = spec_reserve(c, spec_grid(n_l), slot_base_other, slot_base_local)) != SF_OK) return rc;
   }
@@ -162,15 +161,8 @@ extern "C" int sf_find_matches_and_verify_device(sf_handle c, int32_t slot_base_
   }
   SF_HIP(c, hipEventSynchronize(c->spec_index_staged));   // (never recorded: returns at once) previous upload done
   const size_t need = (size_t)n * 4;
-  if (need > c->spec_index_pinned_bytes) {
-    if (c->spec_index_pinned) (void)hipHostFree(c->spec_index_pinned);
-    c->spec_index_pinned = nullptr;
-    c->spec_index_pinned_bytes = 0;
-    if (hipHostMalloc(&c->spec_index_pinned, need + need / 2, hipHostMallocDefault) != hipSuccess)
-      return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) failed", need + need / 2);
-    c->spec_index_pinned_bytes = need + need / 2;
-  }
-  int32_t* hi = (int32_t*)c->spec_index_pinned;
+  if ((rc = sf_pinned_reserve(c, c->spec_index_pinned, need, need + need / 2)) != SF_OK) return rc;
+  int32_t* hi = (int32_t*)c->spec_index_pinned.p;
   for (int i = 0; i < n; ++i) {
     const int ci = c->last_row_cand[out[i].idx_local];
     if (ci < 0 || (unsigned)ci >= c->spec.grid) return sf_fail(c, SF_EHIP, "speculation: match %d has no candidate slot", i);
@@ -230,26 +222,26 @@ extern "C" int sf_accept_stream_status(sf_handle c, int32_t* streamed, int32_t* 
 // retire then runs the query again on the synchronous path below (step_issue_sync: round 3's body), once, and the ladder
 // level it settles on serves the following steps.
 static int step_block_reserve(sf_context* c, sf_context::StepBlock& b, int32_t cap) {
-  if (!b.done) SF_HIP(c, hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
+  int rc = sf_event_ensure(c, b.done);
+  if (rc != SF_OK) return rc;
   if (cap <= b.cap) return SF_OK;
-  if (b.pinned) (void)hipHostFree(b.pinned);
-  b.pinned = nullptr; b.cap = 0; b.pinned_bytes = 0;
+  b.cap = 0;
   const int32_t want = cap + cap / 4 + 64;
   const size_t rec_bytes = (size_t)want * sizeof(sf_result);
   const size_t idx_off = rec_bytes, flag_off = idx_off + (size_t)want * 4, cnt_off = (flag_off + (size_t)want + 63) & ~(size_t)63;
   const size_t match_off = cnt_off + 64, slot_off = match_off + (size_t)want * sizeof(sf_match);
   const size_t word_off = (slot_off + (size_t)want * 4 + 63) & ~(size_t)63;
   const size_t total = word_off + 64;
-  if (hipHostMalloc(&b.pinned, total, hipHostMallocDefault) != hipSuccess)
-    return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) failed", total);
-  b.pinned_bytes = total;
-  b.records = (sf_result*)b.pinned;
-  b.index = (int32_t*)((char*)b.pinned + idx_off);
-  b.flags = (uint8_t*)b.pinned + flag_off;
-  b.count = (int32_t*)((char*)b.pinned + cnt_off);
-  b.walk_matches = (sf_match*)((char*)b.pinned + match_off);
-  b.walk_slots = (int32_t*)((char*)b.pinned + slot_off);
-  b.walk_n = (int32_t*)((char*)b.pinned + word_off);
+  sf_pinned_free(b.pinned);                 // (a larger cap: the block is replaced, by one of exactly `total` bytes)
+  if ((rc = sf_pinned_reserve(c, b.pinned, total, total)) != SF_OK) return rc;
+  char* base = (char*)b.pinned.p;
+  b.records = (sf_result*)base;
+  b.index = (int32_t*)(base + idx_off);
+  b.flags = (uint8_t*)base + flag_off;
+  b.count = (int32_t*)(base + cnt_off);
+  b.walk_matches = (sf_match*)(base + match_off);
+  b.walk_slots = (int32_t*)(base + slot_off);
+  b.walk_n = (int32_t*)(base + word_off);
   b.walk_status = b.walk_n + 1;
   b.cap = want;
   for (int32_t i = 0; i < want; ++i) b.index[i] = -1;
@@ -257,8 +249,7 @@ static int step_block_reserve(sf_context* c, sf_context::StepBlock& b, int32_t c
   *b.count = 0;
   *b.walk_n = 0;
   *b.walk_status = 0;
-  int rc = sf_buf_reserve(c, b.dev, 64 + (size_t)want * 8);
-  if (rc != SF_OK) return rc;
+  if ((rc = sf_buf_reserve(c, b.dev, 64 + (size_t)want * 8)) != SF_OK) return rc;
   return sf_buf_reserve(c, b.dev_records, (size_t)want * sizeof(sf_result));
 }
 
@@ -412,7 +403,7 @@ static int lane_create(sf_context* c, int k) {
   if (L.stream) return SF_OK;
   int rc0 = sf_side_stream(c, SF_STREAM_LANE, k, &L.stream);
   if (rc0 != SF_OK) return rc0;
-  SF_HIP(c, hipEventCreateWithFlags(&L.ev_main, hipEventDisableTiming));
+  if ((rc0 = sf_event_ensure(c, L.ev_main)) != SF_OK) return rc0;
   return sf_buf_reserve(c, L.counters, 64);          // (the work-list counters of the stage kernels; the handle's own
 }                                                    //  are reserved at sf_create)
 
@@ -460,8 +451,7 @@ static int step_issue_speculative(sf_context* c, sf_context::StepBlock& b, int l
   int rc;
   if (!c->w->aux) {
     if ((rc = sf_side_stream(c, SF_STREAM_AUX, lane, &c->w->aux)) != SF_OK) return rc;
-    SF_HIP(c, hipEventCreateWithFlags(&c->w->ev_filter, hipEventDisableTiming));
-    SF_HIP(c, hipEventCreateWithFlags(&c->w->ev_walk, hipEventDisableTiming));
+    if ((rc = sf_event_ensure(c, c->w->ev_filter)) != SF_OK || (rc = sf_event_ensure(c, c->w->ev_walk)) != SF_OK) return rc;
   }
   const size_t min_b = ((size_t)n_l * 8 + 63) & ~(size_t)63, i32_b = ((size_t)n_l * 4 + 63) & ~(size_t)63;
   if ((rc = sf_buf_reserve(c, c->w->step_nn, 2 * min_b + 2 * i32_b + 64)) != SF_OK) return rc;
@@ -622,7 +612,7 @@ extern "C" int sf_step_issue(sf_handle c, int32_t slot_base_other, int32_t slot_
   if (rc == SF_OK) rc = device ? step_issue_device(c, b, lane, slot_base_other, slot_base_local)
                                : step_issue_sync(c, b, slot_base_other, slot_base_local);
   if (c->prep_count != prep_before) {
-    if (!c->ev_prep) (void)hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming);
+    (void)sf_event_ensure(c, c->ev_prep);
     if (c->ev_prep) (void)hipEventRecord(c->ev_prep, c->stream);
     c->prep_epoch += 1;
     L.seen_prep = c->prep_epoch;
@@ -711,7 +701,8 @@ extern "C" int sf_memcpy_device_async(sf_handle c, void* d_dst, const void* d_sr
   for (auto& b : c->step_blocks) {
     const char* lo = (const char*)b.dev_records.p;
     if (!lo || (const char*)d_src < lo || (const char*)d_src >= lo + b.dev_records.bytes) continue;
-    if (!b.copied) SF_HIP(c, hipEventCreateWithFlags(&b.copied, hipEventDisableTiming));
+    const int rc = sf_event_ensure(c, b.copied);
+    if (rc != SF_OK) return rc;
     SF_HIP(c, hipEventRecord(b.copied, s));
     b.copy_pending = true;
     break;

@@ -147,10 +147,8 @@ int sf_store_reserve(sf_context* c, Store& s, int slots_needed, int rows, int co
   if ((rc = sf_buf_reserve(c, n.desc, (size_t)cap * kcap * w * 4)) != SF_OK ||
       (rc = sf_buf_reserve(c, n.xyz, (size_t)cap * kcap * 12)) != SF_OK ||
       (rc = sf_buf_reserve(c, n.kp, (size_t)cap * kcap * 16)) != SF_OK ||
-      (rc = sf_buf_reserve(c, n.meta, (size_t)cap * 16)) != SF_OK) {
-    sf_buf_free(n.desc); sf_buf_free(n.xyz); sf_buf_free(n.kp); sf_buf_free(n.meta);   // the old store stays valid
-    return rc;
-  }
+      (rc = sf_buf_reserve(c, n.meta, (size_t)cap * 16)) != SF_OK)
+    return rc;                      // (every early return frees what `n` holds; the old store stays valid)
   if (s.slots > 0) {
     SF_HIP(c, hipMemcpy2DAsync(n.desc.p, (size_t)kcap * w * 4, s.desc.p, (size_t)s.kcap * w * 4, (size_t)s.kcap * w * 4, s.slots, hipMemcpyDeviceToDevice, c->stream));
     SF_HIP(c, hipMemcpy2DAsync(n.xyz.p, (size_t)kcap * 12, s.xyz.p, (size_t)s.kcap * 12, (size_t)s.kcap * 12, s.slots, hipMemcpyDeviceToDevice, c->stream));
@@ -158,8 +156,7 @@ int sf_store_reserve(sf_context* c, Store& s, int slots_needed, int rows, int co
     SF_HIP(c, hipMemcpyAsync(n.meta.p, s.meta.p, (size_t)s.slots * 16, hipMemcpyDeviceToDevice, c->stream));
     SF_HIP(c, hipStreamSynchronize(c->stream));
   }
-  sf_buf_free(s.desc); sf_buf_free(s.xyz); sf_buf_free(s.kp); sf_buf_free(s.meta);
-  s = n;
+  s = std::move(n);
   return SF_OK;
 }
 
@@ -355,18 +352,10 @@ int sf_store_add_host_batch(sf_context* c, Store& st, const sf_features* const* 
     if (off - chunk_start >= chunk_bytes || i == n - 1) { chunks.push_back({off, i + 1}); chunk_start = off; }
   }
   const size_t total = off;
-  // pinned host staging owned by the handle (released by sf_destroy)
-  if (total > c->ingest_pinned_bytes) {
-    if (c->ingest_pinned) (void)hipHostFree(c->ingest_pinned);
-    c->ingest_pinned = nullptr;
-    c->ingest_pinned_bytes = 0;
-    const size_t want = total + total / 2;
-    hipError_t e = hipHostMalloc(&c->ingest_pinned, want, hipHostMallocDefault);
-    if (e != hipSuccess) return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) -> %s", want, hipGetErrorString(e));
-    c->ingest_pinned_bytes = want;
-  }
+  // pinned host staging owned by the handle
+  if ((rc = sf_pinned_reserve(c, c->ingest_pinned, total, total + total / 2)) != SF_OK) return rc;
   if ((rc = sf_buf_reserve(c, c->stage_desc, total)) != SF_OK) return rc;
-  uint8_t* hp = (uint8_t*)c->ingest_pinned;
+  uint8_t* hp = (uint8_t*)c->ingest_pinned.p;
   uint8_t* dp = (uint8_t*)c->stage_desc.p;
   memcpy(hp, tab.data(), (size_t)n * sizeof(IngestEntry));
 

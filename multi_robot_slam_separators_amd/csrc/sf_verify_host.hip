@@ -204,9 +204,8 @@ static int half_create(sf_context* c) {
   SF_HIP(c, hipStreamCreateWithFlags(&h.stream, hipStreamNonBlocking));
   int rc = sf_buf_reserve(c, h.counters, 64);
   if (rc != SF_OK) return rc;
-  SF_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-  SF_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  return SF_OK;
+  if ((rc = sf_event_ensure(c, c->ev_fork)) != SF_OK) return rc;
+  return sf_event_ensure(c, c->ev_join);
 }
 
 // d_from / d_to / d_out: device pointers. Asynchronous on the handle's stream.
@@ -284,15 +283,8 @@ extern "C" int sf_verify_matches_device(sf_handle c, const sf_match* matches, in
   // pinned staging of the two slot lists; the previous call's copies must have left it
   if (c->pairs_staged) SF_HIP(c, hipEventSynchronize(c->pairs_staged));
   const size_t need = (size_t)n * 8;
-  if (need > c->pairs_pinned_bytes) {
-    if (c->pairs_pinned) (void)hipHostFree(c->pairs_pinned);
-    c->pairs_pinned = nullptr;
-    c->pairs_pinned_bytes = 0;
-    if (hipHostMalloc(&c->pairs_pinned, need + need / 2, hipHostMallocDefault) != hipSuccess)
-      return sf_fail(c, SF_ENOMEM, "hipHostMalloc(%zu) failed", need + need / 2);
-    c->pairs_pinned_bytes = need + need / 2;
-  }
-  int32_t* hf = (int32_t*)c->pairs_pinned;
+  if ((rc = sf_pinned_reserve(c, c->pairs_pinned, need, need + need / 2)) != SF_OK) return rc;
+  int32_t* hf = (int32_t*)c->pairs_pinned.p;
   int32_t* ht = hf + n;
   for (int i = 0; i < n; ++i) {
     hf[i] = slot_base_other + matches[i].idx_other;   // "from" = the querying robot's frame
@@ -302,7 +294,7 @@ extern "C" int sf_verify_matches_device(sf_handle c, const sf_match* matches, in
   }
   SF_HIP(c, hipMemcpyAsync(c->w->pair_from.p, hf, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
   SF_HIP(c, hipMemcpyAsync(c->w->pair_to.p, ht, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  if (!c->pairs_staged) SF_HIP(c, hipEventCreateWithFlags(&c->pairs_staged, hipEventDisableTiming));
+  if ((rc = sf_event_ensure(c, c->pairs_staged)) != SF_OK) return rc;
   SF_HIP(c, hipEventRecord(c->pairs_staged, c->stream));
   return sf_verify_device(c, c->store, c->w->from(), c->w->to(), n, d_out);
 }
@@ -538,7 +530,7 @@ int sf_compact_launch(sf_context* c, const sf_result* d_results, int n, sf_resul
     hipLaunchKernelGGL(k_compact_chain, dim3(chunks), dim3(COMPACT_CHUNK), 0, c->stream, d_results, index, n, d_accepted, d_flags,
                        (unsigned long long*)c->w->compact_scratch.p, c->w->compact_epoch, d_count, d_accepted2, d_flags2, d_count2, cap2);
     SF_HIP(c, hipGetLastError());
-    if (index && index == (const int32_t*)c->spec_index_pinned)
+    if (index && index == (const int32_t*)c->spec_index_pinned.p)
       SF_HIP(c, hipEventRecord(c->spec_index_staged, c->stream));   // the pinned index block may be rewritten after this
     return SF_OK;
   }
@@ -602,12 +594,12 @@ extern "C" int sf_compact_accepted_device(sf_handle c, const sf_result* d_result
   if ((rc = sf_buf_reserve(c, c->w->compact_scratch, (size_t)(chunks + 2) * 8)) != SF_OK) return rc;
   int32_t* d_count = (int32_t*)((char*)c->w->compact_scratch.p + (size_t)(chunks + 1) * 8);   // behind the chunk states
   if ((rc = sf_compact_launch(c, d_results, n, d_accepted, d_flags, d_count)) != SF_OK) return rc;
-  if (!c->count_pinned && hipHostMalloc((void**)&c->count_pinned, 64, hipHostMallocDefault) != hipSuccess)
-    return sf_fail(c, SF_ENOMEM, "hipHostMalloc(64) failed");
-  SF_HIP(c, hipMemcpyAsync(c->count_pinned, d_count, 4, hipMemcpyDeviceToHost, c->stream));
+  if ((rc = sf_pinned_reserve(c, c->count_pinned, 64, 64)) != SF_OK) return rc;
+  const int32_t* count = (const int32_t*)c->count_pinned.p;
+  SF_HIP(c, hipMemcpyAsync(c->count_pinned.p, d_count, 4, hipMemcpyDeviceToHost, c->stream));
   SF_HIP(c, hipStreamSynchronize(c->stream));
-  if (*c->count_pinned < 0) return sf_fail(c, SF_EHIP, "ordered compaction: the look-back over earlier chunks timed out");
-  *n_accepted = *c->count_pinned;
+  if (*count < 0) return sf_fail(c, SF_EHIP, "ordered compaction: the look-back over earlier chunks timed out");
+  *n_accepted = *count;
   return SF_OK;
 }
 
