@@ -125,6 +125,9 @@ extern "C" {
       sf_stereo_camera_from_info, SF_OPT_RECTIFY_TABLE, sf_rectify_check_info (sf_experimental.h) (raw camera images:
       undistortion and rectification on the device).  New calls only; the version number, sizeof(sf_params) and
       SF_K_COUNT stay.                                                                                                  */
+/* 8, additions: sf_depth_registration, sf_depth_registration_defaults, sf_depth_register_check, sf_depth_register_device,
+      sf_depth_fill_holes_device, sf_debug_depth_register_limits (sf_experimental.h) (a depth image registered to the
+      colour camera on the device).  New calls only; the version number, sizeof(sf_params) and SF_K_COUNT stay.        */
 #define SF_ABI_VERSION 8
 
 /* ---- status codes ---------------------------------------------------------------------- */
@@ -1372,6 +1375,67 @@ int  sf_add_keyframes_depth_batch_device(sf_handle h, const uint8_t* d_images, i
                                          const sf_stereo_camera* cam, const sf_detector_params* det, int32_t* first_slot_out,
                                          int32_t* first_nn_row_out, int32_t* d_rows_out, uint8_t* d_desc_out,
                                          float* d_xyz_out, sf_keypoint* d_kpts_out);
+/* Depth registration: a depth image measured in the depth (IR) camera's frame -- other intrinsics, another size, a few
+   centimetres beside the colour camera -- made the registered image the calls above take.  replaces: util2d::registerDepth
+   and util2d::fillRegisteredDepthHoles(fillDoubleHoles = false) of rtabmap's camera drivers, one CPU pass per pixel
+   [upstream rtabmap, as remembered, not from the reference tree; restated in tests/depth_register_ref.py; DESIGN.md
+   section 3 lists what the restatement decides].  A forward scatter with a z-test: a minimum does not depend on the order
+   of arrival, so the result is compared byte for byte.  All arithmetic is float32, unfused, in the order written.
+     in: a depth_width x depth_height image D in a format above; the depth camera's fx, fy, cx, cy; the colour camera's rfx,
+     rfy, rcx, rcy and its size W x H = width x height; T = transform, row-major 3 x 4, which takes a point in the depth
+     camera's frame into the colour camera's.  out: a W x H image of the input's format, 0 where nothing lands.
+     presence: uint16 0 < v < 65535, dz = (float)v * 0.001f; float32 finite and > 0, dz = v.
+     depth pixel at column x, row y: X = (((float)x - cx) * dz) / fx, Y = (((float)y - cy) * dz) / fy;
+       px = ((T[0] * X + T[1] * Y) + T[2] * dz) + T[3], py and pz alike with T[4 .. 7] and T[8 .. 11];
+       dropped unless pz > 0; iz = 1.0f / pz; u = (rfx * px) * iz + rcx; v = (rfy * py) * iz + rcy;
+       dropped unless -1 < u < W and -1 < v < H (NaN compares false); column = (int)u, row = (int)v: truncation toward zero
+       as upstream, values between -1 and 0 land in column or row 0.
+     key: uint16: m = pz * 1000.0f, dropped unless m < 65535.0f, k = (int)m, dropped if k == 0; float32: k = the bits of pz
+       (positive, so their unsigned order is the float order).
+     result: the pixel holds the smallest k of all points that land on it, or 0.
+     hole filling, optional, one flag for the vertical and one for the horizontal pair; OUT OF PLACE on the registered
+     image A: pixels with 1 <= x <= W - 2 and 1 <= y <= H - 2 are candidates, all others are copied.  With b = A[y][x]:
+     first the vertical pair a = A[y - 1][x], c = A[y + 1][x] if its flag is set, then the horizontal pair a = A[y][x - 1],
+     c = A[y][x + 1] if its flag is set and the vertical pair did not set the pixel.  A pair sets the pixel to m iff a != 0,
+     c != 0, close, and b == 0 or far --
+       uint16: m = (a + c) / 2 in integers, e = 0.01f * (float)m, close: (float)|a - c| <= e, far: (float)b > (float)a + e and
+       (float)b > (float)c + e; float32: m = (a + c) / 2.0f, e = 0.01f * m, close: |a - c| <= e, far: b > a + e and b > c + e.
+     far removes background that shows through the gaps of a sparser foreground.
+   Truncation of u and v is upstream's: an identity registration moves about one pixel in ten to its left or upper
+   neighbour, because u falls a rounding error short of x.                                        */
+typedef struct sf_depth_registration {
+  int32_t depth_width, depth_height;       /* the depth images, 1 .. 8192 each                                       */
+  int32_t width, height;                   /* the colour camera's images W x H, 1 .. 8192 each                       */
+  float   fx, fy, cx, cy;                  /* the depth camera; fx, fy > 0                                           */
+  float   rfx, rfy, rcx, rcy;              /* the colour camera; rfx, rfy > 0                                        */
+  float   transform[12];                   /* T, row-major 3 x 4: depth camera frame to colour camera frame          */
+  int32_t fill_vertical, fill_horizontal;  /* 0 or 1 each: the pairs of the hole filling                             */
+  int32_t reserved;                        /* must be 0                                                              */
+} sf_depth_registration;                   /* 108 bytes */
+/* Zero sizes and intrinsics (to be filled in), the identity transform, both fills 0.                                 */
+void sf_depth_registration_defaults(sf_depth_registration* reg);
+/* What sf_depth_register_device holds a block to, host only, without a handle or a GPU: SF_OK, or SF_EINVAL (text via
+   sf_last_error with a NULL handle) for a size outside 1 .. 8192, a value that is not finite, an fx, fy, rfx or rfy <= 0,
+   a flag other than 0 or 1, reserved != 0.                                                                          */
+int  sf_depth_register_check(const sf_depth_registration* reg);
+/* n_images depth images registered in one launch sequence, asynchronous on the handle's stream with no host wait: image i
+   at d_depth + i * depth_stride bytes (rows depth_pitch bytes apart) to the width x height image of the same format at
+   d_out + i * out_stride (rows out_pitch bytes apart); bytes outside the planes are never written.  Pitches, strides and both
+   addresses are multiples of the element size, nothing more; strides are ignored when n_images = 1.  The handle's
+   sf_depth_size is not read.  The z-buffer, 4 width height bytes per image, is the handle's; a batch whose z-buffers pass
+   256 MB runs in chunks of images, queued back to back.  The one host wait there can be: a call that needs a larger
+   z-buffer than any before it (the first, or a larger shape or batch) waits for the stream before the buffer is replaced.  n_images = 0 is SF_OK.  SF_EINVAL, changing nothing: a block the
+   check refuses, an unknown format, a pitch below a row, a pitch, stride or address that is no multiple of the element size,
+   a stride below the rows it holds, a missing array, an output that overlaps the input.                              */
+int  sf_depth_register_device(sf_handle h, const sf_depth_registration* reg, const void* d_depth, int32_t depth_format,
+                              int32_t depth_pitch, size_t depth_stride, int32_t n_images, void* d_out, int32_t out_pitch,
+                              size_t out_stride);
+/* The hole filling alone on n_images images of width x height (1 .. 8192 each) registered elsewhere: the device function of
+   the call above, so the bytes are the same.  Out of place: an output that overlaps the input is refused; everything else
+   as above, without a workspace: no host wait, any number of images (65535 per launch).                                                                                                         */
+int  sf_depth_fill_holes_device(sf_handle h, const void* d_depth, int32_t depth_format, int32_t width, int32_t height,
+                                int32_t depth_pitch, size_t depth_stride, int32_t n_images, int32_t fill_vertical,
+                                int32_t fill_horizontal, void* d_out, int32_t out_pitch, size_t out_stride);
 
 /* ---- geometric verification (stereoCamGeometricTools.cpp:122-178) ---------------------------- */
 /* One estimate_transformation service call on host buffers.                                  */

@@ -107,6 +107,11 @@ int  sf_gftt_check_params(const sf_gftt_params* params);
 /* What sf_rectify_plan_create holds an sf_camera_info to, without a handle or a GPU: SF_OK or SF_EINVAL.  iR_out (may be
    NULL) receives the nine values of (P[:, :3] R)^-1, row-major, as the plan keeps them.                             */
 int  sf_rectify_check_info(const sf_camera_info* info, double* iR_out);
+/* Small shapes and single stages for the tests and the latency tool of sf_depth_register_device; a fresh handle behaves as
+   if it had not been called.  batch_chunk (0 = what the 256 MB workspace allows, at most 65535): the images per chunk.
+   stages (0 = all, else a sum of 1 = the z-buffer's initialisation, 2 = the scatter, 4 = the resolve): what a call
+   queues -- a call without stage 4 writes no output.  Out of range: SF_EINVAL, nothing changes.                   */
+int  sf_debug_depth_register_limits(sf_handle h, int32_t batch_chunk, int32_t stages);
 /* Small shapes for the tests of SURF's batch form; a fresh handle behaves as if neither had been called.  candidate_cap
    (0 = the default, at most 262144) takes the place of the 262144 maxima an image may have, in sf_detect_surf_device
    and the single extraction calls (more: SF_ERANGE) and in the batch forms (more: the keyframe holds no rows, see

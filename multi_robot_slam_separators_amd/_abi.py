@@ -269,6 +269,35 @@ def depth_size(w=0, h=0):
     return s
 
 
+class DepthRegistration(C.Structure):
+    """sf_depth_registration (include/sepfinder.h): the depth camera, the colour camera with its image size, the transform
+    between them and the two flags of the hole filling; what sf_depth_register_device takes."""
+    _fields_ = [
+        ("depth_width", C.c_int32), ("depth_height", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+        ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+        ("rfx", C.c_float), ("rfy", C.c_float), ("rcx", C.c_float), ("rcy", C.c_float),
+        ("transform", C.c_float * 12),
+        ("fill_vertical", C.c_int32), ("fill_horizontal", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+assert C.sizeof(DepthRegistration) == 108
+
+
+def depth_registration(depth_width, depth_height, depth_k, width, height, colour_k, transform=None, fill_vertical=0,
+                       fill_horizontal=0):
+    """depth_k = (fx, fy, cx, cy) of the depth camera, colour_k = (rfx, rfy, rcx, rcy) of the colour camera whose images are
+    width x height; transform [3, 4] takes a point of the depth camera's frame into the colour camera's (None: identity)."""
+    r = DepthRegistration()
+    r.depth_width, r.depth_height, r.width, r.height = int(depth_width), int(depth_height), int(width), int(height)
+    r.fx, r.fy, r.cx, r.cy = (float(v) for v in depth_k)
+    r.rfx, r.rfy, r.rcx, r.rcy = (float(v) for v in colour_k)
+    t = np.eye(3, 4, dtype=np.float32) if transform is None else np.asarray(transform, np.float32).reshape(3, 4)
+    r.transform[:] = t.ravel().tolist()
+    r.fill_vertical, r.fill_horizontal, r.reserved = int(fill_vertical), int(fill_horizontal), 0
+    return r
+
+
 def depth_format_of(depth):
     """The sf_depth_format of a depth image given as a uint16 or float32 array."""
     for fmt, dt in DEPTH_DTYPES.items():

@@ -532,6 +532,11 @@ struct sf_context {
   sf_depth_params depth = {1};
   sf_depth_size depth_size = {0, 0};
   Buf dp_depth, dp_mask;
+  // depth registration (sf_depth_register.hip, k_depth_register.hip): the z-buffer, one uint32 key per output pixel of a
+  // chunk's images.  dreg_debug_chunk / dreg_debug_stages (sf_debug_depth_register_limits; 0 = the defaults): the images per
+  // chunk, and which of memset (1), scatter (2) and resolve (4) a call queues
+  Buf dreg_keys;
+  int dreg_debug_chunk = 0, dreg_debug_stages = 0;
   // Vis/GridRows x Vis/GridCols (sf_grid_set_params; k_grid.hip): the detector of types 4, 6 and 8 runs per cell of the
   // ROI; 1 x 1 = no cells.  ft_cells: every cell's count, then every cell's keypoints, before k_grid_gather joins them
   sf_grid_params grid = {1, 1};
@@ -1122,6 +1127,23 @@ int sf_launch_depth_mask(sf_context* c, const SfDepthIn& depth, int n_img, int w
 int sf_launch_depth_interp(sf_context* c, const SfDepthIn& depth, int n_img, int factor, void* d_out, int out_pitch, size_t out_stride);
 int sf_launch_depth_points_only(sf_context* c, const SfDepthIn& depth, int width, int height, const sf_keypoint* d_kpts, int n,
                                 const sf_stereo_camera* cam, float* d_xyz, uint8_t* d_valid);
+// depth registration (k_depth_register.hip).  The block as the scatter kernel takes it, a kernel argument: the depth camera,
+// the colour camera, the row-major 3 x 4 transform between them, and both sizes (dw x dh depth images to W x H keys)
+struct SfDepthRegister {
+  float fx, fy, cx, cy, rfx, rfy, rcx, rcy;
+  float T[12];
+  int dw, dh, W, H;
+};
+// The keys of a batch fit this much workspace, or the batch runs in chunks of images (one image always runs): the size of
+// the Infinity Cache, as the SURF batch keeps it, so that the keys the scatter leaves are still on the die for the resolve
+constexpr size_t DEPTH_REGISTER_WORKSPACE_BYTES = (size_t)256 << 20;
+// n depth images (depth.w x depth.h = R.dw x R.dh) scattered into d_keys [n][R.H][R.W], which hold 0xFFFFFFFF; the keys
+// resolved and filled (fill bit 0: the vertical pair, bit 1: the horizontal pair) into n images of `format`; the fill alone
+// on n images of depth.w x depth.h.  Asynchronous on the context's stream; the caller has validated everything
+int sf_launch_depth_register_scatter(sf_context* c, const SfDepthIn& depth, int n_img, const SfDepthRegister& R, unsigned* d_keys);
+int sf_launch_depth_register_resolve(sf_context* c, const unsigned* d_keys, int format, int w, int h, int n_img, int fill, void* d_out,
+                                     int out_pitch, size_t out_stride);
+int sf_launch_depth_fill_holes(sf_context* c, const SfDepthIn& depth, int n_img, int fill, void* d_out, int out_pitch, size_t out_stride);
 // FAST-9/16 + limitKeypoints (k_fast.hip); prm validated by the caller
 int sf_launch_detect_fast(sf_context* c, const uint8_t* d_images, size_t img_stride, int n_img, int width, int height, int pitch,
                           int max_features, const sf_fast_params* prm, sf_keypoint* d_kpts_out, int cap, int32_t* d_n_out,

@@ -245,6 +245,11 @@ def load():
         "sf_add_keyframes_depth_batch_device": (C.c_int, [vp, vp, i32, vp, i32, i32, i32, i32, i32, C.c_size_t, i32,
                                                           C.c_size_t, P(_abi.StereoCamera), P(_abi.DetectorParams), P(i32),
                                                           P(i32), vp, vp, vp, vp]),
+        "sf_depth_registration_defaults": (None, [P(_abi.DepthRegistration)]),
+        "sf_depth_register_check": (C.c_int, [P(_abi.DepthRegistration)]),
+        "sf_depth_register_device": (C.c_int, [vp, P(_abi.DepthRegistration), vp, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]),
+        "sf_depth_fill_holes_device": (C.c_int, [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, i32, i32, vp, i32, C.c_size_t]),
+        "sf_debug_depth_register_limits": (C.c_int, [vp, i32, i32]),
         "sf_prof_enable": (C.c_int, [vp, C.c_int]),
         "sf_prof_select": (C.c_int, [vp, C.c_uint32]),
         "sf_stream_placement": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
@@ -321,6 +326,8 @@ EXPORTED = [
     "sf_rectify_check_info", "sf_rectify_plan_create", "sf_rectify_plan_from_maps", "sf_rectify_plan_count",
     "sf_rectify_plan_get", "sf_rectify_plan_clear", "sf_rectify_maps_device", "sf_image_rectify_device",
     "sf_stereo_camera_from_info",
+    "sf_depth_registration_defaults", "sf_depth_register_check", "sf_depth_register_device", "sf_depth_fill_holes_device",
+    "sf_debug_depth_register_limits",
 ]
 
 
@@ -342,6 +349,17 @@ def stereo_camera_from_info(left, right, local_transform=None):
     if rc != _abi.SF_OK:
         raise SepfinderError(rc, (load().sf_last_error(None) or b"").decode())
     return cam
+
+
+depth_registration = _abi.depth_registration   # the block sf_depth_register_device takes (see _abi.depth_registration)
+
+
+def depth_register_check(reg):
+    """sf_depth_register_check (no GPU, no handle): (status, text) -- SF_OK and "", or SF_EINVAL and the reason for a block
+    sf_depth_register_device refuses."""
+    L = load()
+    rc = L.sf_depth_register_check(C.byref(reg))
+    return rc, ("" if rc == _abi.SF_OK else (L.sf_last_error(None) or b"").decode())
 
 
 def depth_interpolation_factor(width, height, depth_width, depth_height):
@@ -1118,6 +1136,43 @@ class SeparatorFinder:
         self._check(self._L.sf_depth_interpolate_device(self._h, C.c_void_p(d_depth), depth_format, depth_width, depth_height,
                                                         depth_pitch, int(depth_stride), n_images, factor, C.c_void_p(d_out),
                                                         out_pitch, int(out_stride)))
+
+    def depth_register_device(self, reg, d_depth, depth_format, depth_pitch, depth_stride, n_images, d_out, out_pitch,
+                              out_stride):
+        """sf_depth_register_device: n_images device depth images of the depth camera registered to the colour camera
+        under an _abi.DepthRegistration (asynchronous), each to a reg.width x reg.height image of its own format at d_out;
+        device pointers (ints), pitches and strides in bytes."""
+        self._check(self._L.sf_depth_register_device(self._h, C.byref(reg), C.c_void_p(d_depth), depth_format, depth_pitch,
+                                                     int(depth_stride), n_images, C.c_void_p(d_out), out_pitch, int(out_stride)))
+
+    def depth_fill_holes_device(self, d_depth, depth_format, width, height, depth_pitch, depth_stride, n_images, fill_vertical,
+                                fill_horizontal, d_out, out_pitch, out_stride):
+        """sf_depth_fill_holes_device: the hole filling of the registration alone, out of place, on n_images device images
+        registered elsewhere (asynchronous)."""
+        self._check(self._L.sf_depth_fill_holes_device(self._h, C.c_void_p(d_depth), depth_format, width, height, depth_pitch,
+                                                       int(depth_stride), n_images, int(fill_vertical), int(fill_horizontal),
+                                                       C.c_void_p(d_out), out_pitch, int(out_stride)))
+
+    def debug_depth_register_limits(self, batch_chunk=0, stages=0):
+        """sf_debug_depth_register_limits: the images per chunk and the stages (1 init, 2 scatter, 4 resolve; 0 = all) of
+        depth_register_device, for the tests and the latency tool."""
+        self._check(self._L.sf_debug_depth_register_limits(self._h, int(batch_chunk), int(stages)))
+
+    def depth_register(self, depth, reg):
+        """A host depth image ([depth_height, depth_width] uint16 millimetres or float32 metres) registered on the device:
+        uploads it, runs sf_depth_register_device once, returns the registered [height, width] host image of the same dtype."""
+        depth = np.ascontiguousarray(depth)
+        fmt = _abi.depth_format_of(depth)
+        if depth.ndim != 2 or depth.shape != (reg.depth_height, reg.depth_width):
+            raise ValueError("the block registers depth images of %d x %d, not of shape %s" % (reg.depth_width, reg.depth_height,
+                                                                                              depth.shape))
+        import torch
+        d_in = upload(depth.view(np.uint8), self.device)
+        d_out = torch.zeros((max(reg.height, 1), max(reg.width, 1) * depth.itemsize), dtype=torch.uint8, device=d_in.device)
+        torch.cuda.current_stream(d_in.device).synchronize()        # (the handle's stream may be another one)
+        self.depth_register_device(reg, d_in.data_ptr(), fmt, depth.strides[0], 0, 1, d_out.data_ptr(), reg.width * depth.itemsize, 0)
+        self.synchronize()
+        return d_out.cpu().numpy().view(depth.dtype)
 
     def depth_mask_device(self, d_depth, depth_format, width, height, depth_pitch, depth_stride, n_images, min_depth,
                           max_depth, d_mask, mask_pitch, mask_stride):

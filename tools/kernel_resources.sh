@@ -4,7 +4,7 @@
 # usage: tools/kernel_resources.sh k_verify.hip [filter-regex]
 cd "$(dirname "$0")/../multi_robot_slam_separators_amd/csrc" || exit 1
 f=${1:-k_verify.hip}; pat=${2:-.}
-canon="-fno-slp-vectorize"; case "$f" in k_verify.hip|k_extract.hip|k_freak.hip|k_surf.hip|k_sift.hip|k_gftt.hip|k_lk.hip|k_orb_detect.hip|k_subpix.hip|k_stereo_bm.hip|k_grid.hip|k_depth.hip) canon="$canon -ffp-contract=off -fno-vectorize";; esac
+canon="-fno-slp-vectorize"; case "$f" in k_verify.hip|k_extract.hip|k_freak.hip|k_surf.hip|k_sift.hip|k_gftt.hip|k_lk.hip|k_orb_detect.hip|k_subpix.hip|k_stereo_bm.hip|k_grid.hip|k_depth.hip|k_depth_register.hip) canon="$canon -ffp-contract=off -fno-vectorize";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -Wno-pass-failed $canon \
   -c "$f" -o /tmp/kres_$$.o -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c '
